@@ -2,9 +2,9 @@
 """Headline benchmark: galaxy stamps/sec of the conv-VAE training step (fwd + ELBO + bwd + Adam),
 59x59x6 stamps, batch 256 per GPU, latent 32, fp32 (BASELINE.json configs[1]); weak scaling over N GPUs.
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4}]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4}] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W [--config {1,2,3,4}]
+        bench.py --gpus N --steps K --warmup W [--config {1,2,3,4}] [--dump-outputs DIR] [--full]
 
 --config selects the BASELINE configuration the line is about (default 1, the headline): 2 the same step on the bf16
 engine, 3 the 128x128x6 / six-level net at 64 stamps per GPU (global 512 on 8), 4 sharded deblend() inference over field
@@ -17,13 +17,19 @@ gradient all-reduce.  Rank 0's RCCL id, the barriers around the timed region and
 elapsed time travel over debvader_amd.parallel.HostGroup (a TCP star on MASTER_ADDR): no torch in a GPU process.
 Inputs are resident in HBM before the timed region (dv_data_upload), synthetic, random-init weights.
 
-The ONE JSON line also carries (rank 0, N = 1 only; --no-secondary / --no-cpu-baseline / --no-roofline switch them off):
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR then also writes what the last
+timed step computed (dump_outputs): the loss scalars and every weight after it (config 4: the composited fields of the
+timed call), rank 0's, from the same seeded inputs on every run.
+
+With --full the ONE JSON line also carries (rank 0, N = 1 only; --no-secondary / --no-cpu-baseline / --no-roofline switch
+them off, --quick shortens the secondary measurements):
   roofline      per-kernel-family HIP-event timing of the same K steps with the engine's streams serialised
   cpu_baseline  the same train step restated with torch-CPU ops (tests/torch_ref.py, oneDNN, all host cores), and the
                 numpy oracle as a second entry
   secondary     the other BASELINE configs, each measured here: bf16 train step (configs[2], HBM roofline), stage-2
                 train step (decoder frozen, train.py:175-183), 128 x 128 x 6 / 6-level net (configs[3]), deblend()
                 inference (configs[4]: cutouts of a tiled scene, 8192 per call)
+and with --config 4 the per-kernel roofline pass and `stamps_to_host`.
 """
 from __future__ import annotations
 
@@ -49,11 +55,32 @@ PARAM_STEP_BYTES = 5 * 33.27e6  # weights / gradients / Adam slots per step (fp3
 
 
 _T0 = time.perf_counter()
+DUMP_LIMIT_BYTES = 60 * 10**6   # --dump-outputs stays under 64 MB, .npy headers included
 
 
 def _progress(msg):
     """stderr only (stdout carries the one JSON line): where a long run is"""
     print(f"[bench {time.perf_counter() - _T0:6.1f}s] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes each array of `arrays` (name -> array) as out_dir/<name>.npy: float64 arrays as float64, all others as
+    float32.  When they hold more than DUMP_LIMIT_BYTES in all, every array is cut to the same fraction of its elements:
+    those at the flat indices np.random.default_rng(0).choice(size, k, replace=False), sorted - a fixed sample, the same
+    elements on every run, so that two builds can be compared file for file."""
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        arrs[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in arrs.values())
+    frac = DUMP_LIMIT_BYTES / total if total > DUMP_LIMIT_BYTES else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrs.items():
+        if frac < 1.0:
+            k = max(1, int(a.size * frac))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    _progress(f"outputs of the last timed step: {len(arrs)} arrays in {out_dir}" + (f" (sampled: {frac:.3f})" if frac < 1 else ""))
 
 
 def _cores():
@@ -444,23 +471,27 @@ def run_inference_config(args, E, ctx, group, rank, world):
     dt = time.perf_counter() - t0
     if group is not None:
         dt = group.max(dt)
-    # the same cutouts with every stamp's mean and stddev shipped to the host (PCIe-inclusive)
-    state = {"n": 0}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    dt_host = None
+    if args.full:
+        # the same cutouts with every stamp's mean and stddev shipped to the host (PCIe-inclusive)
+        state = {"n": 0}
 
-    def consume(first, mean, std):
-        state["n"] += mean.shape[0]
+        def consume(first, mean, std):
+            state["n"] += mean.shape[0]
 
-    eng.infer_cutouts_stream(scene, starts[wlo:whi], lambda *a: None, seed=1)
-    barrier()
-    t1 = time.perf_counter()
-    eng.infer_cutouts_stream(scene, starts[off + lo:off + hi], consume, seed=2)
-    ctx.sync()
-    barrier()
-    dt_host = time.perf_counter() - t1
-    if group is not None:
-        dt_host = group.max(dt_host)
+        eng.infer_cutouts_stream(scene, starts[wlo:whi], lambda *a: None, seed=1)
+        barrier()
+        t1 = time.perf_counter()
+        eng.infer_cutouts_stream(scene, starts[off + lo:off + hi], consume, seed=2)
+        ctx.sync()
+        barrier()
+        dt_host = time.perf_counter() - t1
+        if group is not None:
+            dt_host = group.max(dt_host)
     rows = None
-    if rank == 0 and not args.no_roofline and hasattr(eng, "prof_enable"):
+    if args.full and rank == 0 and not args.no_roofline and hasattr(eng, "prof_enable"):
         # per-kernel-family pass over two chunks (HIP events on the launch streams), as for the train configurations
         eng.prof_reset()
         eng.prof_enable(True)
@@ -509,7 +540,7 @@ def run_inference_config(args, E, ctx, group, rank, world):
                     "float32 cast, forward, mean / stddev / residual fields composited on the GPU; D2H of the three fields",
         "stamps_to_host": {"value": n_timed / dt_host, "unit": "stamps/s", "d2h_gbs": n_timed / dt_host * 2 * cs * cs * 6 * 4 / 1e9,
                            "note": "the same cutouts with mean and stddev of every stamp copied to the host (167 KB per stamp: "
-                                   "PCIe-inclusive, bound by the box's host link)"},
+                                   "PCIe-inclusive, bound by the box's host link)"} if dt_host else None,
         "roofline": roofline, "cpu_baseline": None, "checksum": float(out["mean_field"][::37, ::41, 2].sum()),
         **({"multi_rank": mr} if mr else {}),
     }
@@ -530,10 +561,15 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="stamps per GPU per step (default: the configuration's)")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default=None,
                     help="bf16 without --config selects configs[2]; with --config 4 the bf16 engine's inference")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="shorter secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel roofline pass, the CPU "
+                         "baselines, the secondary configurations (config 4: the host-streaming pass)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no per-kernel roofline pass")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary configurations")
+    ap.add_argument("--quick", action="store_true", help="with --full: shorter secondary measurements")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_child:
@@ -621,6 +657,10 @@ def main():
     dt = time.perf_counter() - t0
     if group is not None:
         dt = group.max(dt)
+    if args.dump_outputs and rank == 0:
+        # read back now: the comm-timing and roofline passes below train the same weights further
+        dump_outputs(args.dump_outputs, {**{k: np.float32(v) for k, v in scal.items()},
+                                         **{n.replace("/", "."): a for n, a in eng.get_params().items()}})
 
     enc_macs, dec_macs = E.arch_macs(cfg)
     fwd_flops = 2.0 * (enc_macs + dec_macs + cfg.latent_dim * (cfg.latent_dim + 1) // 2)
@@ -637,8 +677,8 @@ def main():
         roofline = {"bound": "hbm" if bf16 else "mfma", "kernel": None, "achieved": whole, "peak": peak, "unit": "TFLOP/s",
                     "frac": whole / peak, "traffic": None, "whole_step_tflops": whole, "whole_step_frac": whole / peak,
                     "note": "N > 1: whole-step algorithmic train FLOPs PER GPU over the dense MFMA peak of the dtype (the "
-                            "per-kernel rows need the serialised single-GPU pass: run with --gpus 1)"}
-    if not args.no_roofline and world == 1:
+                            "per-kernel rows need the serialised single-GPU pass: run with --gpus 1 --full)"}
+    if args.full and not args.no_roofline and world == 1:
         # HIP-event timing per kernel family on the stream each launch is queued on, over K steps of the same workload,
         # with the engine's streams SERIALISED (a separate pass: the records would perturb `value`, and overlapped
         # kernels cannot be told apart by events)
@@ -669,11 +709,11 @@ def main():
     eng.close()
 
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary and args.config == 1:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.config == 1:
         secondary = secondary_entries(E, ctx, synthetic_stamps, args.quick)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config in (1, 2):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config in (1, 2):
         # in a child process: torch brings its own copy of the HIP runtime, and a process that has loaded both it and
         # /opt/rocm's (libdebvader_hip.so) aborts in the static destructors at exit ("free(): invalid pointer")
         _progress("cpu baseline: torch-CPU restatement (child process)")

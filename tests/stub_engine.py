@@ -64,7 +64,15 @@ class Engine:
         self.max_batch = cfg.max_batch
 
     def init(self, seed=0):
+        self._seed, self._iterations = seed, 0
         _log(self.ctx.rank, event="init", seed=seed)
+
+    def get_params(self):
+        """Weights that depend on the init seed and the number of steps run, as the real engine's do."""
+        from debvader_amd.engine import arch_specs
+
+        rng = np.random.default_rng([self._seed, self._iterations])
+        return {n: rng.standard_normal(shape, dtype=np.float32) for n, shape, _ in arch_specs(self.cfg)}
 
     def upload(self, slot, x, y):
         return x.shape[0]
@@ -77,6 +85,7 @@ class Engine:
         if getattr(self.ctx, "_prof", False):
             self.ctx._steps = steps
         time.sleep(steps * (0.005 + 0.02 * self.ctx.rank))
+        self._iterations += steps
         _log(self.ctx.rank, event="train_steps", B=B, steps=steps, global_batch=global_batch, t=time.time(),
              torch_loaded="torch" in sys.modules)
         return {"loss": 1.0, "nll_mean": 1.0, "kl_reg": 0.0, "mse": 0.0}

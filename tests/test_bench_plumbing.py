@@ -11,6 +11,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytest.importorskip("torch")
@@ -105,3 +106,54 @@ def test_bench_config_flag_selects_the_baseline_configuration(tmp_path):
         assert f"configs[{conf}]" in d["config"]["workload"] and d["config"]["per_gpu_batch"] == want_batch
         assert d["config"]["global_batch"] == 2 * want_batch and want in d["metric"]
         assert d["dtype"] == ("bf16" if conf == 2 else "f32") and d["multi_rank"]["verified"]
+
+
+def test_plain_one_gpu_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`, the stub engine in place of the HIP library: the engine
+    runs the W warm-up steps and the K timed steps and nothing else, the line carries ms_per_step, and DIR holds the loss
+    scalars and every weight after the last timed step as float32 .npy files - the same files on a second run."""
+    dumps = []
+    for run in range(2):
+        log, out = str(tmp_path / f"stub{run}"), str(tmp_path / f"out{run}")
+        env = dict(os.environ, DV_BENCH_STUB_ENGINE="tests.stub_engine", DV_STUB_LOG=log, PYTHONPATH=ROOT, OMP_NUM_THREADS="1")
+        for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+            env.pop(k, None)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", out], capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] >= 5.0
+        assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert d["higher_is_better"] is True and d["unit"] == "stamps/s" and d["dtype"] == "f32"
+        ev = [json.loads(ln) for ln in open(log + ".0")]
+        assert [e["steps"] for e in ev if e["event"] == "train_steps"] == [2, 3]
+        files = sorted(os.listdir(out))
+        assert {"loss.npy", "nll_mean.npy", "kl_reg.npy", "mse.npy", "dec.convt3.kernel.npy"} <= set(files)
+        arrs = {f: np.load(os.path.join(out, f)) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert arrs["dec.convt3.kernel.npy"].ndim == 4 and float(arrs["loss.npy"]) == 1.0
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64 * 10**6
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_outputs_over_the_limit(tmp_path):
+    """Outputs over the limit are cut to a seeded sample of each array, the same elements on every call; float64 stays
+    float64, everything else is written as float32."""
+    import bench
+
+    big = np.arange(9 * 10**6, dtype=np.float64)              # 72 MB
+    small = np.arange(1000, dtype=np.int32).reshape(10, 100)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"big": big, "small": small, "loss": np.float32(2.5)})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "loss.npy", "small.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10**6
+    a, b = (np.load(tmp_path / run / "big.npy") for run in ("a", "b"))
+    assert a.dtype == np.float64 and 0 < a.size < big.size and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < big.size      # distinct elements of `big`, in index order
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.ndim == 1 and np.isin(s, np.arange(1000)).all()
+    assert np.load(tmp_path / "a" / "loss.npy").size == 1

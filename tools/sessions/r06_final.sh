@@ -9,7 +9,7 @@ DV_PARITY_MARGINS=$O/parity_margins.txt python -m pytest tests -x -q -m gpu --du
 tail -25 $O/gpu_tests.log
 [ $rc -ne 0 ] && exit $rc
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-python bench.py > $O/bench_line.json 2> $O/bench.err || exit 1
+python bench.py --full > $O/bench_line.json 2> $O/bench.err || exit 1
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r06_final/bench_line.json").read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r06_s1
 mkdir -p $O
 cd $R
-python bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 tail -c 600 $O/bench_default.json
 echo "== fp32: weight-gradient families left out (development build; 0 = all in, 1 = tiled, 3 = Winograd-domain, 4 = strip, 2 = all)"
 for rep in 1 2 3; do
