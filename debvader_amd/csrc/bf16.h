@@ -138,6 +138,8 @@ int launch_bgemm_tn(const BGemmTnParams& p, hipStream_t s);
 //   d(t)  = backward of z = mu + L eps and of the KL regulariser        -> dt    (sampler_bwd_kernel's arithmetic)
 // until round 6: split-K finish, PReLU backward, narrow Dense, PReLU backward, sampler backward - five launches of the
 // main stream's chain.  The batch sums (d(bias), d(alpha)) are column sums of the row outputs: launch_bt_colsums.
+// latent_dim > 64: the steps up to d(z) in one launch (bt_mid_wide_bwd_kernel), then the sampler backward in a second
+// (sampler_wide_bwd_kernel, pointwise.hip).
 struct BMidBwdParams {
   const float* slab;     // [nslab][*][lds]
   long slab_stride;

@@ -469,6 +469,56 @@ __device__ __forceinline__ int bt_tril_src(int d, int i, int j) {
   return q < m - d ? d + q : d * d - 1 - q;
 }
 
+// The first two steps of bt_mid_bwd_kernel (below), for bt_mid_wide_bwd_kernel; the narrow kernel keeps its own copy of
+// this code.  d(hidden pre-activation) of stamp b: every wave holds the row (lane + 64 t) in dv, wave 0 writes it (and the
+// d(alpha_h) terms) out
+template <int KC>
+__device__ __forceinline__ void bt_mid_hidden(const BMidBwdParams& p, int b, int lane, int w, float (&dv)[KC]) {
+  const int hid = p.hid;
+  const float* sb = p.slab + (size_t)b * p.lds;
+  const size_t ss = (size_t)p.slab_stride;
+  const int ns = p.nslab;
+#pragma unroll
+  for (int t = 0; t < KC; ++t) {
+    const int i = lane + 64 * t;
+    dv[t] = 0.f;
+    if (i < hid) {
+      const float v0 = sb[i], v1 = ns > 1 ? sb[ss + i] : 0.f, v2 = ns > 2 ? sb[2 * ss + i] : 0.f, v3 = ns > 3 ? sb[3 * ss + i] : 0.f;
+      float dsum = ((v0 + v1) + v2) + v3;
+      for (int sl = 4; sl < ns; ++sl) dsum += sb[(size_t)sl * ss + i];
+      const float u = p.uh[(size_t)b * hid + i];
+      const bool pos = u > 0.f;
+      dv[t] = pos ? dsum : dsum * p.alpha_h[i];
+      if (w == 0) {
+        p.duh[(size_t)b * hid + i] = dv[t];
+        if (p.dalh) p.dalh[(size_t)b * hid + i] = pos ? 0.f : dsum * u;
+      }
+    }
+  }
+}
+
+// d(z')[n] = sum_i duh[i] * W0[n][i] for n = n0, n0 + 4, n0 + 8, n0 + 12 (n < d), in every lane of the wave
+template <int KC>
+__device__ __forceinline__ void bt_mid_dense4(const BMidBwdParams& p, const float (&dv)[KC], int n0, int lane, float (&acc)[4]) {
+  const int hid = p.hid, d = p.d;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    acc[j] = 0.f;
+    const int n = n0 + 4 * j;
+    const float* wr = p.W0 + (size_t)(n < d ? n : 0) * hid;
+#pragma unroll
+    for (int t = 0; t < KC; ++t) {
+      const int k = lane + 64 * t;
+      acc[j] = fmaf(dv[t], k < hid ? wr[k] : 0.f, acc[j]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], o);
+  }
+}
+
 template <int KC>   // KC = ceil(hid / 64) values of the hidden row per lane
 __global__ __launch_bounds__(256) void bt_mid_bwd_kernel(const BMidBwdParams p) {
   __shared__ float dzs[64];
@@ -562,6 +612,34 @@ __global__ __launch_bounds__(256) void bt_mid_bwd_kernel(const BMidBwdParams p) 
   for (int i = lane; i < p.ldt; i += 64) dtb[i] = i < tw ? st[i] : 0.f;
 }
 
+// latent_dim > 64: the same steps up to d(z) (the hidden row, Dense(latent -> hid) data gradient looping over d, PReLU
+// gate of z, straight to dz / dalin); launch_bt_mid_bwd queues the sampler backward (sampler_wide_bwd_kernel) behind it
+template <int KC>
+__global__ __launch_bounds__(256) void bt_mid_wide_bwd_kernel(const BMidBwdParams p) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int b = blockIdx.x;
+  const int d = p.d;
+  const size_t zo = (size_t)b * p.ldz;
+  float dv[KC];
+  bt_mid_hidden<KC>(p, b, lane, w, dv);
+  for (int n0 = w; n0 < d; n0 += 16) {
+    float acc[4];
+    bt_mid_dense4<KC>(p, dv, n0, lane, acc);
+    const int n = n0 + 4 * lane;
+    if (lane < 4 && n < d) {
+      const float dzp = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+      const float zv = p.z[zo + n];
+      const bool pos = zv > 0.f;
+      p.dz[zo + n] = pos ? dzp : dzp * p.alpha_in[n];
+      if (p.dalin) p.dalin[zo + n] = pos ? 0.f : dzp * zv;
+    }
+  }
+  for (int n = d + (int)threadIdx.x; n < p.ldz; n += 256) {   // (pad columns: zeros)
+    p.dz[zo + n] = 0.f;
+    if (p.dalin) p.dalin[zo + n] = 0.f;
+  }
+}
+
 __global__ __launch_bounds__(256) void bt_colsums_kernel(const BColsums c) {
   const int q = blockIdx.y;
   const int col = blockIdx.x * 256 + threadIdx.x;
@@ -582,9 +660,20 @@ __global__ __launch_bounds__(256) void bt_colsums_kernel(const BColsums c) {
 
 int launch_bt_mid_bwd(const BMidBwdParams& p, hipStream_t s) {
   if (p.NB <= 0) return OK;
-  if (p.d < 1 || p.d > 64 || p.ldz < p.d || p.ldz > 64 || p.hid < 1 || p.hid > 1024 || p.nslab < 1 ||
+  if (p.d > 64) {
+    if (p.ldz < p.d || p.hid < 1 || p.hid > 1024 || p.nslab < 1 || p.ldt < p.d + p.d * (p.d + 1) / 2) {
+      set_error("trunk backward: the hidden width must be <= 1024 (%d, %d)", p.d, p.hid);
+      return E_INVALID;
+    }
+    if (p.hid <= 256) hipLaunchKernelGGL(bt_mid_wide_bwd_kernel<4>, dim3((unsigned)p.NB), dim3(256), 0, s, p);
+    else if (p.hid <= 576) hipLaunchKernelGGL(bt_mid_wide_bwd_kernel<9>, dim3((unsigned)p.NB), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(bt_mid_wide_bwd_kernel<16>, dim3((unsigned)p.NB), dim3(256), 0, s, p);
+    DV_HIP(hipGetLastError());
+    return launch_sampler_wide_bwd(p.t, p.eps, p.z, p.dz, p.dt, p.NB, p.d, p.ldt, p.ldz, p.diag_shift, p.kls, s);
+  }
+  if (p.d < 1 || p.ldz < p.d || p.ldz > 64 || p.hid < 1 || p.hid > 1024 || p.nslab < 1 ||
       p.ldt < p.d + p.d * (p.d + 1) / 2) {
-    set_error("trunk backward: latent_dim must be in [1,64] and the hidden width <= 1024 (%d, %d)", p.d, p.hid);
+    set_error("trunk backward: latent_dim must be >= 1 and the hidden width <= 1024 (%d, %d)", p.d, p.hid);
     return E_INVALID;
   }
   if (p.hid <= 256) hipLaunchKernelGGL(bt_mid_bwd_kernel<4>, dim3((unsigned)p.NB), dim3(256), 0, s, p);

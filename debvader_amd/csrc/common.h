@@ -400,6 +400,11 @@ int launch_sampler_fwd(const SamplerParams& p, hipStream_t s);
 // ldt: row stride of t and dt, ldz: of eps, z and dz (pad columns of dt are written as zeros)
 int launch_sampler_bwd(const float* t, const float* eps, const float* z, const float* dz, float* dt, int NB, int d,
                        int ldt, int ldz, float diag_shift, float kls, hipStream_t s);
+// the same two for latent_dim > 64 (one workgroup per stamp, any d; same arguments and semantics, the KL sum in another
+// fixed order)
+int launch_sampler_wide_fwd(const SamplerParams& p, hipStream_t s);
+int launch_sampler_wide_bwd(const float* t, const float* eps, const float* z, const float* dz, float* dt, int NB, int d,
+                            int ldt, int ldz, float diag_shift, float kls, hipStream_t s);
 
 int launch_adam(float* w, float* m, float* v, const float* g, long n, float lr_t, float b1, float b2, float eps,
                 hipStream_t s);

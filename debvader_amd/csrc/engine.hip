@@ -175,7 +175,7 @@ struct Arch {
       set_error("only square stamps are supported (reference uses input_shape[0] for both axes)");
       return E_INVALID;
     }
-    if (L < 1 || L > DV_MAX_LEVELS || C < 1 || C > 15 || d < 1 || d > 64 || H < 4) {
+    if (L < 1 || L > DV_MAX_LEVELS || C < 1 || C > 15 || d < 1 || H < 4) {
       set_error("unsupported architecture (levels=%d bands=%d latent=%d size=%d)", L, C, d, H);
       return E_INVALID;
     }
@@ -188,6 +188,16 @@ struct Arch {
         set_error("filters must be multiples of 4");
         return E_INVALID;
       }
+    }
+    // any latent_dim (d > 64: the workgroup-per-stamp sampler kernels); what bounds it is the 32-bit element offsets
+    // of the kernels that address one parameter tensor, the largest of which is the encoder Dense kernel [flat][tw]
+    const int64_t tw64 = (int64_t)d + (int64_t)d * (d + 1) / 2;
+    const int64_t flat64 = (int64_t)((H + (1 << L) - 1) >> L) * ((H + (1 << L) - 1) >> L) * c->filters[L - 1];
+    // (its padded copies: [flat][twp] fp32, [tw padded to 64][flat] bf16)
+    if (flat64 * ((tw64 + 63) & ~(int64_t)63) >= ((int64_t)1 << 31)) {
+      set_error("latent_dim %d: the encoder Dense kernel (%lld x %lld, padded) reaches 2^31 elements; a parameter tensor "
+                "must stay below 2^31 elements (32-bit element offsets)", d, (long long)flat64, (long long)tw64);
+      return E_INVALID;
     }
     tw = d + d * (d + 1) / 2;
     twp = (tw + 3) & ~3;
@@ -1918,7 +1928,7 @@ static int sampler_forward(dv_model* m, int NB, bool gen, uint64_t seed, unsigne
   sp.ain = LANE(m->dec_ain, A.dp);
   m->ain_done = true;
   ProfScope ps(m, 2);
-  return launch_sampler_fwd(sp, fwd_stream(m));
+  return A.d > 64 ? launch_sampler_wide_fwd(sp, fwd_stream(m)) : launch_sampler_fwd(sp, fwd_stream(m));
 }
 
 // head of the lane: per-block loss partials at part_off (blocks), optionally d(loss)/d(tpre) into gA
@@ -2258,7 +2268,8 @@ static int backward(dv_model* m, int NB, int Bg, const float* xsrc, const int* i
   {
     ProfScope ps(m, 2);
     DV_NEXT_OUT();
-    DV_TRY(launch_sampler_bwd(m->t, m->eps, m->z, cur, oth, NB, A.d, A.twp, A.dp, A.cfg.diag_shift, kls, s));
+    DV_TRY((A.d > 64 ? launch_sampler_wide_bwd : launch_sampler_bwd)(m->t, m->eps, m->z, cur, oth, NB, A.d, A.twp, A.dp,
+                                                                   A.cfg.diag_shift, kls, s));
   }
   advance();  // cur = d(t) [NB, twp]
   // encoder dense
@@ -3369,6 +3380,7 @@ int dv_model_create(dv_ctx* ctx, const dv_config* cfg, dv_model** out) {
       per_stamp = std::max(per_stamp, (size_t)hout * hout * cout);
     }
     per_stamp = std::max(per_stamp, (size_t)A.dec_out * A.dec_out * A.C2p);
+    per_stamp = std::max(per_stamp, (size_t)A.twp);   // the rows of t and d(t): the largest at a wide latent_dim
     if (Bc * per_stamp >= ((size_t)1 << 31)) {
       set_error("max_batch %d x %zu elements of the largest activation reaches 2^31: the fp32 engine addresses a layer with "
                 "32-bit element offsets; use max_batch <= %zu (inference splits larger inputs into chunks by itself)",
@@ -3381,6 +3393,13 @@ int dv_model_create(dv_ctx* ctx, const dv_config* cfg, dv_model** out) {
     return dv_model_destroy(m), DV_E_INVALID;
   }
   const bool bf16 = cfg->dtype == DV_DTYPE_BF16;
+  if (bf16 && Bc * A.twp >= ((size_t)1 << 31)) {
+    // (the trunk kernels address the t / d(t) rows and their K-split slabs with 64-bit offsets, but the Dense layers of
+    // the engine's fallback path take 32-bit element offsets)
+    set_error("max_batch %d x %d elements of the t / d(t) rows reaches 2^31: the Dense layers address a tensor with 32-bit "
+              "element offsets; use max_batch <= %zu", cfg->max_batch, A.twp, (((size_t)1 << 31) - 1) / A.twp);
+    return dv_model_destroy(m), DV_E_INVALID;
+  }
   const size_t Ba = bf16 ? 0 : Bc;   // fp32 activations of the conv stacks: not allocated by the bf16 engine
   size_t max_act = 0;  // largest per-stamp activation (elements) for the gradient ping-pong buffers
   auto track = [&](size_t e) { max_act = std::max(max_act, e); };
@@ -3492,6 +3511,8 @@ int dv_model_create(dv_ctx* ctx, const dv_config* cfg, dv_model** out) {
   size_t head_blocks = (Bc * A.dec_out * A.dec_out + 255) / 256;
   m->ws3_elems = std::max((size_t)1 << 20, head_blocks * 2 + 64);
   m->ws3_elems = std::max(m->ws3_elems, (size_t)64 * std::max((size_t)A.flat, r));
+  // the encoder Dense bias gradient's column partials (bias_grad_colsum over the rows of d(t)): wide at a large latent_dim
+  m->ws3_elems = std::max(m->ws3_elems, (std::max<size_t>((Bc + 2047) / 2048, 64) + 1) * A.twp);
   // BN statistics / BN backward partials: one 16-float row per 1024 pixels of the batch (the capacity used to
   // be derived from other users of the buffer and overran silently above ~19k stamps of 59 px)
   m->ws3_elems = std::max(m->ws3_elems, ((Bc * (size_t)A.H * A.H + 1023) / 1024 + 1) * (2 * DV_BN_MAXC));

@@ -928,7 +928,8 @@ static int bf_backward(dv_model* m, int NB, int Bg) {
   if (!bf.trunk_mfma) {
     {
       ProfScope ps(m, 2);
-      DV_TRY(launch_sampler_bwd(m->t, m->eps, m->z, tr2, tr3, NB, A.d, A.twp, A.dp, A.cfg.diag_shift, kls, s));
+      DV_TRY((A.d > 64 ? launch_sampler_wide_bwd : launch_sampler_bwd)(m->t, m->eps, m->z, tr2, tr3, NB, A.d, A.twp, A.dp,
+                                                                     A.cfg.diag_shift, kls, s));
     }
     m->main_marked = false;   // (the record prelu_bwd left behind predates the sampler: the dense weight gradient below needs its own)
     DV_TRY(bias_grad_colsum(m, tr3, NB, A.twp, A.tw, A.enc_db()));

@@ -598,8 +598,13 @@ int launch_gconv2(const GConv2Params& p0, hipStream_t s) {
     set_error("gconv2: unsupported shape (Cin=%d Cout=%d nclass=%d)", p.Cin, p.Cout, p.nclass);
     return E_INVALID;
   }
+  // (the weight offsets reach (largest weight tap + 1) x Cin x Cout: 9 slices for a 3 x 3 kernel, one for a Dense layer -
+  // whose kernel grows with params_size(latent_dim))
+  long wslices = 1;
+  for (int c = 0; c < p.nclass; ++c)
+    for (int t = 0; t < p.cls[c].ntaps && t < 16; ++t) wslices = std::max(wslices, (long)((p.cls[c].wtcode >> (4 * t)) & 15) + 1);
   if ((long)p.NB * p.Hin * p.Win * p.Cin >= (1L << 30) || (long)p.NB * p.Hout * p.Wout * p.Cout >= (1L << 30) ||
-      (long)9 * p.Cin * p.Cout >= (1L << 30)) {
+      wslices * p.Cin * p.Cout >= (1L << 30)) {
     set_error("gconv2: tensor too large for 32-bit byte offsets; lower max_batch");
     return E_INVALID;
   }

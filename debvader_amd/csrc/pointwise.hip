@@ -769,6 +769,156 @@ int launch_sampler_bwd(const float* t, const float* eps, const float* z, const f
 }
 
 // ------------------------------------------------------------------------------------------------
+// The same sampler for latent_dim > 64: one 256-thread workgroup per stamp, row i of L on wave i % 4, the wave's lanes
+// along the row.  A row of L is a contiguous run of t (forward or reversed, see tril_src), so every load of the row loop
+// is coalesced; eps is re-read from global memory (L1-resident: d floats per stamp) instead of staged, so the kernels
+// use no LDS beyond the four per-wave KL sums and have no upper limit on d.
+
+// sum over the 64 lanes, valid in every lane (fixed butterfly order)
+__device__ __forceinline__ float wave_allsum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// standard normal for element (row, col) of the eps draw: Philox4x32-10 at counter (row, col / 4, stream, 0), Box-Muller
+// on the pair of words the column's position in its group of four selects (the arithmetic of sampler_fwd_kernel, so a
+// wide draw reproduces a narrow one column for column)
+__device__ __forceinline__ float philox_normal_at(unsigned row, int col, unsigned stream, unsigned long long seed) {
+  unsigned r[4];
+  philox4x32_10(row, (unsigned)col >> 2, stream, 0u, (unsigned)seed, (unsigned)(seed >> 32), r);
+  const int a = col & 3;
+  const float u1 = ((float)r[a & ~1] + 1.0f) * 2.3283064365386963e-10f;
+  const float u2 = ((float)r[(a & ~1) + 1] + 1.0f) * 2.3283064365386963e-10f;
+  const float rad = sqrtf(-2.0f * logf(fminf(u1, 1.0f)));
+  float sn, cs;
+  sincosf(6.283185307179586f * u2, &sn, &cs);
+  return (a & 1) ? rad * sn : rad * cs;
+}
+
+__global__ __launch_bounds__(256) void sampler_wide_fwd_kernel(const SamplerParams p) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b = blockIdx.x;
+  const int d = p.d;
+  const int tw = d + d * (d + 1) / 2;
+  const int bs = p.rep_nb > 0 ? b % p.rep_nb : b;
+  const unsigned long long seed =
+      (p.seed_ptr ? *p.seed_ptr : p.seed) + (p.rep_nb > 0 ? (unsigned long long)(b / p.rep_nb) : 0ull);
+  const size_t zo = (size_t)b * p.ldz;
+  float* const eps = p.eps;   // (written below and read back by other waves of the block: no __restrict__)
+  // the row of t: read from memory, or - K-split slabs of the bf16 encoder Dense - summed here (tbias first, slabs in
+  // order, as sampler_fwd_kernel), written to t_out by the block that owns the stamp and read back from there
+  const float* sb = nullptr;
+  const size_t ss = (size_t)p.slab_stride;
+  const int ns = p.nslab;
+  const float* tr = p.t + (size_t)bs * p.ldt;
+  auto slab_sum = [&](int i) {
+    const float v0 = sb[i], v1 = ns > 1 ? sb[ss + i] : 0.f, v2 = ns > 2 ? sb[2 * ss + i] : 0.f, v3 = ns > 3 ? sb[3 * ss + i] : 0.f;
+    float v = (((p.tbias[i] + v0) + v1) + v2) + v3;
+    for (int sl = 4; sl < ns; ++sl) v += sb[(size_t)sl * ss + i];
+    return v;
+  };
+  if (ns > 0) {
+    sb = p.slab + (size_t)bs * p.lds;
+    if (p.rep_nb == 0 || b < p.rep_nb) {
+      float* to = p.t_out + (size_t)bs * p.ldt;
+      for (int i = tid; i < p.ldt; i += 256) to[i] = i < tw ? slab_sum(i) : 0.f;
+      tr = to;
+    } else {
+      tr = nullptr;                                  // (another block writes this stamp's t_out: sum the slabs again)
+    }
+  }
+  auto tv = [&](int i) { return tr ? tr[i] : slab_sum(i); };
+  if (p.gen) {
+    for (int c = tid; c < p.ldz; c += 256) eps[zo + c] = c < d ? philox_normal_at(p.row0 + bs, c, p.stream, seed) : 0.f;
+  }
+  for (int c = d + tid; c < p.ldz; c += 256) {       // (pad columns d .. ldz - 1: zeros)
+    p.z[zo + c] = 0.f;
+    if (p.ain) p.ain[zo + c] = 0.f;
+    if (p.stddev) p.stddev[zo + c] = 0.f;
+  }
+  __syncthreads();
+  float kacc = 0.f;                                  // this wave's KL terms, in row order (uniform across the wave)
+  for (int i = w; i < d; i += 4) {
+    const float ldiag = softplus_f(tv(d + tril_src(d, i, i))) + p.diag_shift;
+    float s = 0.f, q = 0.f;
+    for (int j = lane; j <= i; j += 64) {
+      const float l = j == i ? ldiag : tv(d + tril_src(d, i, j));
+      s = fmaf(l, eps[zo + j], s);
+      q = fmaf(l, l, q);
+    }
+    s = wave_allsum(s);
+    q = wave_allsum(q);
+    const float z = tv(i) + s, e = eps[zo + i];
+    kacc += 0.5f * z * z - 0.5f * e * e - logf(ldiag);
+    if (lane == 0) {
+      p.z[zo + i] = z;
+      if (p.ain) p.ain[zo + i] = z > 0.f ? z : p.alpha_in[i] * z;
+      if (p.stddev) p.stddev[zo + i] = sqrtf(q);
+    }
+  }
+  __shared__ float kw[4];
+  if (lane == 0) kw[w] = kacc;
+  __syncthreads();
+  if (tid == 0) p.kl[b] = ((kw[0] + kw[1]) + kw[2]) + kw[3];
+}
+
+int launch_sampler_wide_fwd(const SamplerParams& p, hipStream_t s) {
+  if (p.d < 1 || p.ldz < p.d || p.ldt < p.d + p.d * (p.d + 1) / 2) {
+    set_error("sampler: bad latent_dim %d or row strides %d / %d", p.d, p.ldt, p.ldz);
+    return E_INVALID;
+  }
+  if (p.NB == 0) return OK;
+  hipLaunchKernelGGL(sampler_wide_fwd_kernel, dim3((unsigned)p.NB), dim3(256), 0, s, p);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+// d(t) of sampler_wide_fwd_kernel: dt[i] = g_i (the means), dt[L_ij] = g_i eps_j below the diagonal and
+// (g_i eps_i - kls / L_ii) sigmoid(raw_ii) on it, g = dz + kls z.  Every element of the row is written once, coalesced
+// along the rows of L as in the forward kernel, pad columns tw .. ldt - 1 as zeros.
+__global__ __launch_bounds__(256) void sampler_wide_bwd_kernel(const float* __restrict__ t, const float* __restrict__ eps,
+                                                               const float* __restrict__ z, const float* __restrict__ dz,
+                                                               float* __restrict__ dt, int d, int ldt, int ldz,
+                                                               float diag_shift, float kls) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b = blockIdx.x;
+  const int tw = d + d * (d + 1) / 2;
+  const float* tb = t + (size_t)b * ldt;
+  float* dtb = dt + (size_t)b * ldt;
+  const size_t zo = (size_t)b * ldz;
+  for (int c = tid; c < d; c += 256) dtb[c] = dz[zo + c] + kls * z[zo + c];
+  for (int c = tw + tid; c < ldt; c += 256) dtb[c] = 0.f;
+  for (int i = w; i < d; i += 4) {
+    const float g = dz[zo + i] + kls * z[zo + i];
+    const int di = d + tril_src(d, i, i);
+    for (int j = lane; j <= i; j += 64) {
+      float v = g * eps[zo + j];
+      if (j == i) {
+        const float raw = tb[di];
+        const float ldiag = softplus_f(raw) + diag_shift;
+        const float sg = 1.0f / (1.0f + expf(-raw));
+        v = (v - kls / ldiag) * sg;
+      }
+      dtb[d + tril_src(d, i, j)] = v;
+    }
+  }
+}
+
+int launch_sampler_wide_bwd(const float* t, const float* eps, const float* z, const float* dz, float* dt, int NB, int d,
+                            int ldt, int ldz, float diag_shift, float kls, hipStream_t s) {
+  if (d < 1 || ldz < d || ldt < d + d * (d + 1) / 2) {
+    set_error("sampler backward: bad latent_dim %d or row strides %d / %d", d, ldt, ldz);
+    return E_INVALID;
+  }
+  if (NB == 0) return OK;
+  hipLaunchKernelGGL(sampler_wide_bwd_kernel, dim3((unsigned)NB), dim3(256), 0, s, t, eps, z, dz, dt, d, ldt, ldz,
+                     diag_shift, kls);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // tf.optimizers.legacy.Adam (reference train.py:126): m += (g-m)(1-b1); v += (g^2-v)(1-b2); w -= lr_t m/(sqrt(v)+eps)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
                                                    const float* __restrict__ g, long n4, float lr_t, float b1,

@@ -27,6 +27,11 @@ for size, bands, filters, latent, kernels in [(20, 5, (32, 64), 8, (5, 5)), (32,
                                               (20, 4, (32, 64), 5, (5, 3)), (59, 15, (32, 64), 30, (3, 3))]:
     for B in (1, 7, 64, 100):
         cases.append((size, bands, filters, latent, B, kernels))
+# latent sizes above 64 (workgroup-per-stamp sampler; the bf16 trunk's wide mid backward on the 64-multiple last level)
+for size, bands, filters, latent, kernels in [(20, 4, (16, 32), 65, (3, 3)), (32, 6, (32, 64), 130, (3, 3)),
+                                              (45, 5, (32, 64, 128), 97, (3, 5, 3)), (59, 6, (32, 64, 128, 256), 200, (3,) * 4)]:
+    for B in (1, 7, 64):
+        cases.append((size, bands, filters, latent, B, kernels))
 bad = 0
 for dtype in (0, 1):
     for size, bands, filters, latent, B, kernels in cases:
