@@ -100,6 +100,10 @@ SIGNATURES = {
     "dv_optimizer_set_iter": (C.c_int, [_p, C.c_int64]),
     "dv_data_upload": (C.c_int, [_p, C.c_int32, _f, _f, C.c_int64]),
     "dv_data_free": (C.c_int, [_p, C.c_int32]),
+    "dv_data_stream_open": (C.c_int, [_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                      C.c_int64]),
+    "dv_data_info": (C.c_int, [_p, C.c_int32, _i32, _i64, _i64]),
+    "dv_ctx_mem_info": (C.c_int, [_p, _i64, _i64]),
     "dv_train_step": (C.c_int, [_p, C.c_int32, _i32, C.c_int64, C.c_int32, C.c_int32, _f, C.c_uint64, _f]),
     "dv_eval_step": (C.c_int, [_p, C.c_int32, _i32, C.c_int64, C.c_int32, C.c_int32, _f, C.c_uint64, _f]),
     "dv_grad_step": (C.c_int, [_p, C.c_int32, _i32, C.c_int64, C.c_int32, C.c_int32, _f, C.c_uint64, _f]),

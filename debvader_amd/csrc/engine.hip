@@ -415,6 +415,47 @@ struct DataSlot {
   float* x = nullptr;
   float* y = nullptr;
   int64_t n = 0;
+  // streamed slot (dv_data_stream_open): the caller's host rows, gathered per step into the model's StreamRing
+  bool streamed = false;
+  const char *hx = nullptr, *hy = nullptr;
+  bool x64 = false, y64 = false;
+  int64_t sx = 0, sy = 0;        // row strides in bytes
+  int64_t h2d_bytes = 0;
+  // the per-step view of a streamed batch handed to enqueue_step: x / y point into a device ring slot, and every
+  // stream that reads them first waits for `ready` (the end of their host-to-device copy)
+  hipEvent_t ready = nullptr;
+};
+
+// Device ring of a streamed slot (shared by slots 0 and 1: the steps of both are queued in one order).  Entry r holds
+// one batch, x rows then y rows (y from yoff), in HBM (dev) and in pinned staging (host).
+//
+// Hazards.  fit() queues training steps two ahead under tickets 0..3, so up to three steps are in flight when the host
+// gathers the next one.  The batch of step k lives in entry k % 4 and is read by:
+//   - the comm stream: bn_prefetch's batch statistics and, on the bf16 engine, bf_input into xh_alt, queued at enqueue time
+//     ahead of the step's forward (shuffled batches);
+//   - the main stream: the fp32 forward's conv0 input (or the statistics / input kernel when nothing was prefetched) and
+//     the labels read by the fused head or the head kernel (forward lanes join the main stream);
+//   - the weight-gradient (aux) stream: conv0's weight gradient and the input BatchNorm's gradient read x;
+//   - the reduction stream, which is recorded as well so that no future change of what it reads opens a race.
+// At the end of step k's enqueue a release event is recorded on each of those streams (rel[r][..]): every reader of the
+// entry was queued before it.  The copy of step k + 4 into the same entry waits for all of them on the copy stream (which
+// nothing else waits on, so these waits stall no compute queue), and every reader of step k + 4 waits for that copy's
+// event (h2d[r]): the comm stream before bn_prefetch, the main stream before the forward; the aux and reduction streams
+// start a step's work only behind events of the main stream.  The pinned entry is rewritten by the host only after
+// h2d[r] has completed (the gather of step k + 4 synchronises on the copy of step k, long finished in steady state).
+struct StreamRing {
+  static constexpr int kDepth = 4;
+  static constexpr int kRel = 4;          // main, aux, comm, reduction stream
+  float* dev[kDepth] = {};
+  float* host[kDepth] = {};
+  size_t yoff = 0;                        // floats from an entry's x rows to its y rows (256-byte aligned)
+  hipStream_t copy = nullptr;
+  hipEvent_t h2d[kDepth] = {};
+  hipEvent_t rel[kDepth][kRel] = {};
+  bool queued[kDepth] = {};               // h2d / rel of the entry have been recorded
+  unsigned next = 0;
+  int threads = 1;
+  std::vector<int32_t> iota;              // [0, Bc): index vector of a gathered batch
 };
 
 // bf16 kernel family (BASELINE configs[2], bf16.h): stamp-inner bf16 activations of the conv stacks, bf16 weight
@@ -617,6 +658,7 @@ struct dv_model {
   float* zero_page = nullptr;  // 256 B of zeros (LDS-DMA source for out-of-image pieces)
   int* idx_dev = nullptr;
   DataSlot slots[2];
+  StreamRing* ring = nullptr;    // allocated by the first dv_data_stream_open, freed when no slot streams any more
   int lastB = 0;
   // profiling
   bool prof_on = false;
@@ -2408,8 +2450,8 @@ static int check_step_args(dv_model* m, int slot, const int32_t* idx, int64_t fi
     set_error("null model");
     return E_INVALID;
   }
-  if (slot < 0 || slot > 1 || !m->slots[slot].x) {
-    set_error("data slot %d is empty (call dv_data_upload first)", slot);
+  if (slot < 0 || slot > 1 || (!m->slots[slot].x && !m->slots[slot].streamed)) {
+    set_error("data slot %d is empty (call dv_data_upload or dv_data_stream_open first)", slot);
     return E_STATE;
   }
   if (B < 1 || B > m->Bc) {
@@ -2474,10 +2516,10 @@ static int bn_prefetch(dv_model* m, const float* x, int64_t first, int NB, int B
 }
 
 // enqueue one step (no host sync); scalars land in m->scal[0..2]
-static int enqueue_step(dv_model* m, StepMode mode, int slot, const int32_t* idx_host, int64_t first, int B, int Bg,
-                        const float* eps_host, uint64_t seed) {
+// `ds`: a resident slot, or the ring entry of a streamed batch (stream_stage), whose copy every reader waits for
+static int enqueue_step(dv_model* m, StepMode mode, const DataSlot& ds, const int32_t* idx_host, int64_t first, int B,
+                        int Bg, const float* eps_host, uint64_t seed) {
   hipStream_t s = m->ctx->stream;
-  const DataSlot& ds = m->slots[slot];
   const int* idx = nullptr;
   if (idx_host) {
       if (mode == MODE_TRAIN && !m->prof_on && m->idx_slots && m->bn_pre_part && m->ctx->comm_stream &&
@@ -2486,6 +2528,7 @@ static int enqueue_step(dv_model* m, StepMode mode, int slot, const int32_t* idx
       // host reaches while the previous step is still running (steps are queued two ahead) - the forward pass below
       // then starts with bn_finalize instead of a statistics pass over the batch
       int* slotp = m->idx_slots + (size_t)(m->idx_slot_next++ & 3) * m->Bc;
+      if (ds.ready) DV_HIP(hipStreamWaitEvent(m->ctx->comm_stream, ds.ready, 0));
       DV_TRY(bn_prefetch(m, ds.x, first, B, Bg, slotp, idx_host));
       idx = slotp;
     } else {
@@ -2496,6 +2539,7 @@ static int enqueue_step(dv_model* m, StepMode mode, int slot, const int32_t* idx
   const bool training = mode != MODE_EVAL;
   const bool bwd = mode != MODE_EVAL;
   m->lastB = B;
+  if (ds.ready) DV_HIP(hipStreamWaitEvent(s, ds.ready, 0));      // a streamed batch: its copy has landed
   // Philox stream: one counter row per (rank-local) stamp; ranks are separated through the stream id
   // loc / scale of a gradient or train step are only written on request (dv_model_set_keep_outputs: the parity
   // tests read them back) - 42 MB of stores per 256-stamp step that training has no reader for
@@ -2573,12 +2617,170 @@ static void scalars_from_sums(const dv_model* m, const float* h, int Bg, float* 
   }
 }
 
+// Host threads that copy stamps between the caller's arrays and pinned memory (the inference pipe, the streamed slots):
+// DV_COPY_THREADS, otherwise half the hardware threads, at most 8.
+static int copy_threads() {
+  const char* e = getenv("DV_COPY_THREADS");
+  const int hw = (int)std::thread::hardware_concurrency();
+  return e ? std::max(1, atoi(e)) : std::max(1, std::min(8, hw > 0 ? hw / 2 : 4));
+}
+
+// ---- streamed slots (StreamRing) ----------------------------------------------------------------------------------
+static int ring_sync_streams(dv_model* m) {
+  dv_ctx* c = m->ctx;
+  for (hipStream_t st : {c->stream, c->aux_stream, c->red_stream, c->comm_stream, m->ring ? m->ring->copy : nullptr})
+    if (st) DV_HIP(hipStreamSynchronize(st));
+  return OK;
+}
+
+static void ring_free(dv_model* m) {
+  StreamRing* R = m->ring;
+  if (!R) return;
+  for (int r = 0; r < StreamRing::kDepth; ++r) {
+    if (R->dev[r]) (void)hipFree(R->dev[r]);
+    if (R->host[r]) (void)hipHostFree(R->host[r]);
+    if (R->h2d[r]) (void)hipEventDestroy(R->h2d[r]);
+    for (auto e : R->rel[r])
+      if (e) (void)hipEventDestroy(e);
+  }
+  if (R->copy) (void)hipStreamDestroy(R->copy);
+  delete R;
+  m->ring = nullptr;
+}
+
+// the ring of the model's max_batch; on failure nothing is left allocated
+static int ring_get(dv_model* m) {
+  if (m->ring) return OK;
+  const Arch& A = m->A;
+  StreamRing* R = new StreamRing();
+  m->ring = R;
+  const size_t E = (size_t)A.H * A.H * A.C;
+  R->yoff = ((size_t)m->Bc * E + 63) & ~(size_t)63;
+  const size_t bytes = (R->yoff + (size_t)m->Bc * E) * sizeof(float);
+  int st = OK;
+#define RING_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); ring_free(m); return st; } } while (0)
+  // its own stream: on the comm stream a copy would queue behind the previous step's bucket all-reduces and early Adam
+  RING_HIP(hipStreamCreateWithFlags(&R->copy, hipStreamNonBlocking));
+  for (int r = 0; r < StreamRing::kDepth; ++r) {
+    RING_HIP(hipMalloc((void**)&R->dev[r], bytes));
+    RING_HIP(hipHostMalloc((void**)&R->host[r], bytes, hipHostMallocDefault));
+    RING_HIP(hipEventCreateWithFlags(&R->h2d[r], hipEventDisableTiming));    // copy -> kernels: system-scope release
+    for (auto& e : R->rel[r]) RING_HIP(hipEventCreateWithFlags(&e, sync_event_flags()));   // ordering only
+  }
+#undef RING_HIP
+  R->iota.resize(m->Bc);
+  for (int i = 0; i < m->Bc; ++i) R->iota[i] = i;
+  R->threads = copy_threads();
+  return OK;
+}
+
+// rows idx[0..B) (or first..first+B) of a streamed slot -> dx / dy as B contiguous float32 rows of E elements each; the
+// float64 -> float32 cast is a C cast (round to nearest even, as numpy's astype).  x and y rows are split over the threads.
+static void gather_rows(float* dx, float* dy, const DataSlot& ds, const int32_t* idx, int64_t first, int B, size_t E,
+                        int threads) {
+  auto work = [&](int lo, int hi) {
+    for (int u = lo; u < hi; ++u) {
+      const bool isy = u >= B;
+      const int i = isy ? u - B : u;
+      const int64_t row = idx ? (int64_t)idx[i] : first + i;
+      const char* src = (isy ? ds.hy : ds.hx) + row * (isy ? ds.sy : ds.sx);
+      float* dst = (isy ? dy : dx) + (size_t)i * E;
+      if (isy ? ds.y64 : ds.x64) {
+        const double* sd = reinterpret_cast<const double*>(src);
+        for (size_t j = 0; j < E; ++j) dst[j] = (float)sd[j];
+      } else {
+        memcpy(dst, src, E * sizeof(float));
+      }
+    }
+  };
+  const int units = 2 * B;
+  threads = std::max(1, std::min(threads, units));
+  if (threads == 1 || (size_t)units * E < (size_t)1 << 18) {
+    work(0, units);
+    return;
+  }
+  std::vector<std::thread> pool;
+  const int per = (units + threads - 1) / threads;
+  for (int t = 1; t < threads; ++t) {
+    const int lo = std::min(units, per * t), hi = std::min(units, per * (t + 1));
+    if (lo < hi) pool.emplace_back(work, lo, hi);
+  }
+  work(0, std::min(units, per));
+  for (auto& th : pool) th.join();
+}
+
+// Gathers the batch of one step of streamed slot `ds` into the next ring entry's pinned staging and queues its copy to
+// HBM on the copy stream (hazards: StreamRing).  *view addresses the batch as rows 0..B of a resident slot whose readers
+// wait for the copy; *entry is the ring entry, to be released with stream_release once the step is queued.
+static int stream_stage(dv_model* m, DataSlot& ds, const int32_t* idx, int64_t first, int B, DataSlot* view, int* entry) {
+  StreamRing* R = m->ring;
+  const Arch& A = m->A;
+  const size_t E = (size_t)A.H * A.H * A.C;
+  const int r = (int)(R->next % StreamRing::kDepth);
+  if (R->queued[r]) DV_HIP(hipEventSynchronize(R->h2d[r]));     // the pinned entry's previous copy has been read
+  gather_rows(R->host[r], R->host[r] + R->yoff, ds, idx, first, B, E, R->threads);
+  if (R->queued[r])
+    for (auto e : R->rel[r]) DV_HIP(hipStreamWaitEvent(R->copy, e, 0));   // every reader of the entry's last batch is done
+  const size_t bytes = (size_t)B * E * sizeof(float);
+  DV_HIP(hipMemcpyAsync(R->dev[r], R->host[r], bytes, hipMemcpyHostToDevice, R->copy));
+  DV_HIP(hipMemcpyAsync(R->dev[r] + R->yoff, R->host[r] + R->yoff, bytes, hipMemcpyHostToDevice, R->copy));
+  DV_HIP(hipEventRecord(R->h2d[r], R->copy));
+  R->next += 1;
+  ds.h2d_bytes += 2 * (int64_t)bytes;
+  *view = DataSlot();
+  view->x = R->dev[r];
+  view->y = R->dev[r] + R->yoff;
+  view->n = B;
+  view->ready = R->h2d[r];
+  *entry = r;
+  return OK;
+}
+
+// records the release events of ring entry r behind everything queued so far on the streams that read a step's batch
+static int stream_release(dv_model* m, int r) {
+  StreamRing* R = m->ring;
+  dv_ctx* c = m->ctx;
+  const hipStream_t readers[StreamRing::kRel] = {c->stream, c->aux_stream ? c->aux_stream : c->stream,
+                                                 c->comm_stream ? c->comm_stream : c->stream,
+                                                 c->red_stream ? c->red_stream : c->stream};
+  for (int k = 0; k < StreamRing::kRel; ++k) DV_HIP(hipEventRecord(R->rel[r][k], readers[k]));
+  R->queued[r] = true;
+  return OK;
+}
+
+// Queues one step on `slot`.  A streamed slot's rows are gathered and copied first; the step then reads them as rows
+// 0..B of the ring entry - through the identity index vector when the caller named rows by index, so that the step takes
+// exactly the kernels (and the comm-stream prefetch) the same batch takes on a resident slot.  idx_pinned (the deferred
+// step): the index vector the step reads is staged there, because the caller's may be gone before its copy runs.
+static int enqueue_slot_step(dv_model* m, StepMode mode, int slot, const int32_t* idx, int64_t first, int B, int Bg,
+                             const float* eps, uint64_t seed, int* idx_pinned = nullptr) {
+  DataSlot& ds = m->slots[slot];
+  DataSlot view;
+  int entry = -1;
+  if (ds.streamed) {
+    DV_TRY(stream_stage(m, ds, idx, first, B, &view, &entry));
+    if (idx) idx = m->ring->iota.data();
+    first = 0;
+  }
+  if (idx && idx_pinned) {
+    memcpy(idx_pinned, idx, (size_t)B * sizeof(int));
+    idx = idx_pinned;
+  }
+  const int st = enqueue_step(m, mode, entry >= 0 ? view : ds, idx, first, B, Bg, eps, seed);
+  if (entry >= 0) {
+    // also after a failed enqueue: whatever part of the step was queued may read the entry
+    const int rs = stream_release(m, entry);
+    if (st == OK) return rs;
+  }
+  return st;
+}
+
 static int run_step(dv_model* m, StepMode mode, int slot, const int32_t* idx, int64_t first, int B, int Bg,
                     const float* eps, uint64_t seed, float* out) {
   DV_TRY(check_step_args(m, slot, idx, first, B));
   if (Bg <= 0) Bg = B;
   DV_HIP(hipSetDevice(m->ctx->device));
-  DV_TRY(enqueue_step(m, mode, slot, idx, first, B, Bg, eps, seed));
+  DV_TRY(enqueue_slot_step(m, mode, slot, idx, first, B, Bg, eps, seed));
   DV_TRY(fetch_scalars(m, Bg, out));
   return prof_flush(m);
 }
@@ -2686,9 +2888,7 @@ static int pipe_get(dv_model* m, int cap, InferPipe** out, bool need_host = true
       return st;
     }
   }
-  const char* e = getenv("DV_COPY_THREADS");
-  int hw = (int)std::thread::hardware_concurrency();
-  p->threads = e ? std::max(1, atoi(e)) : std::max(1, std::min(8, hw > 0 ? hw / 2 : 4));
+  p->threads = copy_threads();
   m->pipe = p;
   *out = p;
   return OK;
@@ -3312,6 +3512,7 @@ int dv_model_destroy(dv_model* m) {
     v.erase(std::remove(v.begin(), v.end(), m), v.end());
   }
   if (g_process_exiting) {                   // see mark_process_exiting: host memory only
+    delete m->ring;
     delete m->pipe;
     delete m;
     return DV_OK;
@@ -3327,6 +3528,8 @@ int dv_model_destroy(dv_model* m) {
     if (m->slots[s].x) (void)hipFree(m->slots[s].x);
     if (m->slots[s].y) (void)hipFree(m->slots[s].y);
   }
+  if (m->ring && m->ring->copy) (void)hipStreamSynchronize(m->ring->copy);
+  ring_free(m);
   pipe_free(m->pipe);
   for (auto& kv : m->infer_graphs) (void)hipGraphExecDestroy(kv.second);
   for (int k = 0; k < 3; ++k) {
@@ -3745,6 +3948,67 @@ int dv_data_free(dv_model* m, int32_t slot) {
   if (m->slots[slot].x) (void)hipFree(m->slots[slot].x);
   if (m->slots[slot].y) (void)hipFree(m->slots[slot].y);
   m->slots[slot] = DataSlot();
+  if (m->ring && !m->slots[0].streamed && !m->slots[1].streamed) {
+    // no slot streams any more: the ring goes once nothing queued can still read or write it
+    DV_TRY(ring_sync_streams(m));
+    ring_free(m);
+  }
+  return DV_OK;
+}
+
+int dv_data_stream_open(dv_model* m, int32_t slot, const void* x, int32_t x_f64, const void* y, int32_t y_f64, int64_t n,
+                        int64_t row_stride_x, int64_t row_stride_y) {
+  if (!m || slot < 0 || slot > 1 || !x || !y || n < 1 || n > INT32_MAX) {
+    set_error("dv_data_stream_open: bad arguments (n must be in [1, 2^31))");
+    return DV_E_INVALID;
+  }
+  const Arch& A = m->A;
+  const int64_t ex = (int64_t)A.H * A.H * A.C * (x_f64 ? 8 : 4), ey = (int64_t)A.H * A.H * A.C * (y_f64 ? 8 : 4);
+  if ((n > 1 && (row_stride_x < ex && row_stride_x > -ex)) || (n > 1 && (row_stride_y < ey && row_stride_y > -ey))) {
+    set_error("dv_data_stream_open: row strides %lld / %lld overlap rows of %lld / %lld bytes", (long long)row_stride_x,
+              (long long)row_stride_y, (long long)ex, (long long)ey);
+    return DV_E_INVALID;
+  }
+  DV_HIP(hipSetDevice(m->ctx->device));
+  // Nothing queued may still read the slot's old rows, and nothing prefetched may belong to them.  A queued step's input
+  // normalised ahead (bf16 in_pre) whose step never ran - its enqueue failed, or a caller abandoned it - would otherwise
+  // refuse every later training step: once all streams have drained no step can consume it, so it is dropped here.
+  DV_TRY(ring_sync_streams(m));
+  m->bn_pre_valid = false;
+  m->bf.in_pre = false;
+  m->bnpre_go_pending = false;
+  DataSlot& d = m->slots[slot];
+  if (d.x) (void)hipFree(d.x);
+  if (d.y) (void)hipFree(d.y);
+  d = DataSlot();
+  DV_TRY(ring_get(m));
+  d.streamed = true;
+  d.hx = static_cast<const char*>(x);
+  d.hy = static_cast<const char*>(y);
+  d.x64 = x_f64 != 0;
+  d.y64 = y_f64 != 0;
+  d.sx = row_stride_x;
+  d.sy = row_stride_y;
+  d.n = n;
+  return DV_OK;
+}
+
+int dv_data_info(dv_model* m, int32_t slot, int32_t* mode, int64_t* n, int64_t* h2d_bytes) {
+  if (!m || slot < 0 || slot > 1) return DV_E_INVALID;
+  const DataSlot& d = m->slots[slot];
+  if (mode) *mode = d.streamed ? 2 : (d.x ? 1 : 0);
+  if (n) *n = d.n;
+  if (h2d_bytes) *h2d_bytes = d.h2d_bytes;
+  return DV_OK;
+}
+
+int dv_ctx_mem_info(dv_ctx* c, int64_t* free_bytes, int64_t* total_bytes) {
+  if (!c) return DV_E_INVALID;
+  DV_HIP(hipSetDevice(c->device));
+  size_t fr = 0, tot = 0;
+  DV_HIP(hipMemGetInfo(&fr, &tot));
+  if (free_bytes) *free_bytes = (int64_t)fr;
+  if (total_bytes) *total_bytes = (int64_t)tot;
   return DV_OK;
 }
 
@@ -3777,6 +4041,7 @@ int dv_data_upload(dv_model* m, int32_t slot, const float* x, const float* y, in
   d.n = n;
   DV_HIP(hipMemcpy(d.x, x, bytes, hipMemcpyHostToDevice));
   DV_HIP(hipMemcpy(d.y, y, bytes, hipMemcpyHostToDevice));
+  d.h2d_bytes = 2 * (int64_t)bytes;
   return DV_OK;
 }
 
@@ -3805,13 +4070,8 @@ int dv_train_step_async(dv_model* m, int32_t slot, const int32_t* idx, int64_t f
     DV_HIP(hipHostMalloc((void**)&m->ring_idx, (size_t)4 * m->Bc * sizeof(int), hipHostMallocDefault));
     for (auto& e : m->ring_ev) DV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
-  const int32_t* idx_staged = nullptr;
-  if (idx) {     // the caller's index array may be gone before the copy runs: stage it in pinned memory
-    int* dst = m->ring_idx + (size_t)ticket * m->Bc;
-    memcpy(dst, idx, (size_t)B * sizeof(int));
-    idx_staged = dst;
-  }
-  DV_TRY(enqueue_step(m, MODE_TRAIN, slot, idx_staged, first, B, Bg, nullptr, seed));
+  // the caller's index array may be gone before the copy runs: the step's index vector is staged in pinned memory
+  DV_TRY(enqueue_slot_step(m, MODE_TRAIN, slot, idx, first, B, Bg, nullptr, seed, m->ring_idx + (size_t)ticket * m->Bc));
   DV_HIP(hipMemcpyAsync(m->ring_scal + 4 * ticket, m->scal, 4 * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
   DV_HIP(hipEventRecord(m->ring_ev[ticket], m->ctx->stream));
   m->ring_bg[ticket] = Bg;
@@ -3843,6 +4103,10 @@ int dv_train_steps(dv_model* m, int32_t slot, int64_t first, int32_t B, int32_t 
                    float* out) {
   if (steps < 1) return DV_E_INVALID;
   DV_TRY(check_step_args(m, slot, nullptr, 0, B));
+  if (m->slots[slot].streamed) {
+    set_error("dv_train_steps runs on resident data only (slot %d streams from host memory): use dv_train_step_async", slot);
+    return DV_E_INVALID;
+  }
   if (Bg <= 0) Bg = B;
   DV_HIP(hipSetDevice(m->ctx->device));
   int64_t span = std::max<int64_t>(1, m->slots[slot].n - B + 1);
@@ -3853,7 +4117,7 @@ int dv_train_steps(dv_model* m, int32_t slot, int64_t first, int32_t B, int32_t 
   for (int k = 0; k < steps; ++k) {
     int64_t start = (first + (int64_t)k * B) % span;
     m->hint_next_first = k + 1 < steps ? (first + (int64_t)(k + 1) * B) % span : -1;   // lets step k prefetch k+1's BN sums
-    DV_TRY(enqueue_step(m, MODE_TRAIN, slot, nullptr, start, B, Bg, nullptr, seed + (uint64_t)k));
+    DV_TRY(enqueue_step(m, MODE_TRAIN, m->slots[slot], nullptr, start, B, Bg, nullptr, seed + (uint64_t)k));
     if (m->prof_on) DV_TRY(prof_flush(m));
   }
   if (time_enqueue) {

@@ -289,6 +289,12 @@ class Context:
         return dict(comm_ranks=n.value, comm_rank=r.value, device=d.value, bus_id=bus.value.decode(),
                     rehearsal=bool(reh.value), world=self.world, rank=self.rank)
 
+    def mem_info(self) -> Tuple[int, int]:
+        """(free, total) bytes of device memory on this context's GPU (hipMemGetInfo)."""
+        fr, tot = C.c_int64(), C.c_int64()
+        check(lib.dv_ctx_mem_info(self._h, C.byref(fr), C.byref(tot)))
+        return fr.value, tot.value
+
     def comm_prof(self, on: bool):
         """Time every collective on the comm stream and every wait of the main stream for one (dv_comm_prof_enable)."""
         check(lib.dv_comm_prof_enable(self._h, int(on)))
@@ -401,6 +407,7 @@ class Engine:
         self.tw = self.latent + self.latent * (self.latent + 1) // 2
         self.stamp_shape = (cfg.height, cfg.width, cfg.bands)
         self.max_batch = cfg.max_batch
+        self._streamed = {}            # slot -> (x, y) host arrays a streamed slot reads (kept alive here)
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
@@ -480,10 +487,46 @@ class Engine:
         if x.shape != y.shape or x.shape[1:] != self.stamp_shape:
             raise ValueError(f"expected x, y of shape (N,{self.stamp_shape}), got {x.shape} and {y.shape}")
         check(lib.dv_data_upload(self._h, slot, _fp(x), _fp(y), x.shape[0]))
+        self._streamed.pop(slot, None)
         return x.shape[0]
+
+    def open_stream(self, slot: int, x, y):
+        """Slot `slot` reads its rows from the host arrays x, y on every step (dv_data_stream_open) instead of holding
+        them in HBM: the step functions then name rows of x / y, which are gathered (float64 cast to float32) and copied
+        to the device step by step.  x, y: float32 or float64 arrays of shape (N, H, W, C) - np.memmap included - whose
+        rows are each contiguous; their own buffers are used, never a copy.  The engine keeps references to them until
+        the slot is freed, uploaded or reopened; their contents must not change meanwhile."""
+        arrs = []
+        for a, what in ((x, "x"), (y, "y")):
+            if not isinstance(a, np.ndarray):
+                raise TypeError(f"{what}: open_stream reads a numpy array's own buffer, got {type(a).__name__}")
+            if a.dtype not in (np.float32, np.float64) or not a.dtype.isnative:
+                raise ValueError(f"{what}: a streamed slot reads native float32 or float64 rows, got {a.dtype}")
+            if a.ndim != 4 or a.shape[1:] != self.stamp_shape:
+                raise ValueError(f"{what}: expected shape (N,{self.stamp_shape}), got {a.shape}")
+            row = np.empty(a.shape[1:], a.dtype)
+            if a.shape[0] and (a.strides[1:] != row.strides):
+                raise ValueError(f"{what}: every row of a streamed array must be contiguous (strides {a.strides})")
+            arrs.append(a)
+        x, y = arrs
+        if x.shape[0] != y.shape[0]:
+            raise ValueError(f"x has {x.shape[0]} rows, y {y.shape[0]}")
+        check(lib.dv_data_stream_open(self._h, slot, C.c_void_p(x.ctypes.data), int(x.dtype == np.float64),
+                                      C.c_void_p(y.ctypes.data), int(y.dtype == np.float64), x.shape[0],
+                                      x.strides[0], y.strides[0]))
+        self._streamed[slot] = (x, y)
+        return x.shape[0]
+
+    def data_info(self, slot: int) -> Dict[str, int]:
+        """mode (0 empty, 1 resident, 2 streamed), rows, and the bytes the slot has moved host -> device since it was
+        uploaded or opened."""
+        mode, n, h2d = C.c_int32(), C.c_int64(), C.c_int64()
+        check(lib.dv_data_info(self._h, slot, C.byref(mode), C.byref(n), C.byref(h2d)))
+        return {"mode": mode.value, "n": n.value, "h2d_bytes": h2d.value}
 
     def free_data(self, slot: int):
         check(lib.dv_data_free(self._h, slot))
+        self._streamed.pop(slot, None)
 
     # -- steps ------------------------------------------------------------------------------
     def _step(self, fn, slot, idx, first, B, global_batch, eps, seed) -> Dict[str, float]:

@@ -267,7 +267,8 @@ class VAENet:
         self.losses = [scal["kl_reg"] / k] * k
 
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, shuffle=True,
-            validation_data=None, validation_steps=None, initial_epoch=0, reuse_device_data=False, **kwargs):
+            validation_data=None, validation_steps=None, initial_epoch=0, reuse_device_data=False,
+            device_data_budget=None, **kwargs):
         """Keras Model.fit for in-memory arrays (train.py:27-37): per-epoch shuffle, last partial batch used,
         validation in inference mode, returns History with loss / mse / <metric fn names> / val_*.
 
@@ -282,7 +283,16 @@ class VAENet:
         reuse_device_data: Keras re-reads the arrays on every call, and so does this method (the upload is PCIe-bound,
         faster than any content hash of the arrays would be).  reuse_device_data=True skips the upload when the same
         array OBJECTS (identity, shape, batch geometry) are still resident from the previous fit() - the caller's
-        promise that their contents have not changed in between."""
+        promise that their contents have not changed in between.  A streamed slot (below) has nothing on the device to
+        reuse: it is reopened on every call.
+
+        device_data_budget: bytes of HBM the training and validation rows may occupy.  A set whose rows (x and y, as
+        float32: 2 * rows * stamp bytes) fit goes resident; a larger one is STREAMED: the engine reads the caller's
+        arrays (float32 or float64, np.memmap included) for every step, gathers the step's rows into pinned memory and
+        copies them to the device while the previous steps run (dv_data_stream_open), with bit-identical results.  0
+        forces streaming.  None (default): the context's free device memory minus a reserve (`_device_reserve`); a set
+        between that and the free memory itself tries the resident upload first, so every set that fits in HBM still
+        trains resident."""
         if not self._core.compiled:
             raise RuntimeError("You must compile your model before training/testing. Use `model.compile(...)`.")
         core, eng = self._core, self._core.engine
@@ -319,14 +329,17 @@ class VAENet:
             if small:
                 raise ValueError(f"a batch of {small[0]} stamp(s) cannot be split over {world} ranks: choose a batch size "
                                  f"(and data-set sizes modulo the batch size) of at least {world}")
-        # this rank's rows of the training set, per step; resident rows are addressed by their position in `home`
+        # this rank's rows of the training set, per step; resident rows are addressed by their position in `home`,
+        # streamed ones by their global row number home[...]
         home, pieces = self._home_rows(n, batch_size, rank, world)
-        self._upload(0, x_in, x, y_in, y, home, (n, batch_size, rank, world), reuse_device_data)
-        vpieces = []
+        streamed, held = self._place(0, x_in, x, y_in, y, home, (n, batch_size, rank, world), reuse_device_data,
+                                     device_data_budget)
+        vpieces, vstreamed = [], False
         if nv:
             vhome, vpieces = self._home_rows(min(nv, val_steps * batch_size), batch_size, rank, world)
-            self._upload(1, validation_data[0], xv, validation_data[1], yv, vhome, (nv, batch_size, val_steps, rank, world),
-                         reuse_device_data)
+            vstreamed, _ = self._place(1, validation_data[0], xv, validation_data[1], yv, vhome,
+                                       (nv, batch_size, val_steps, rank, world), reuse_device_data,
+                                       None if device_data_budget is None else max(0, device_data_budget - held))
         hist = History()
         cbs = list(callbacks or [])
         for cb in cbs:
@@ -366,8 +379,8 @@ class VAENet:
 
             try:
                 for (c0, c1, gb) in pieces:
-                    eng.train_step_async(ticket, 0, idx=order[c0:c1].astype(np.int32), global_batch=gb,
-                                         seed=core.next_seed())
+                    rows = home[order[c0:c1]] if streamed else order[c0:c1]
+                    eng.train_step_async(ticket, 0, idx=rows.astype(np.int32), global_batch=gb, seed=core.next_seed())
                     pending.append((ticket, gb))
                     ticket = (ticket + 1) % 4
                     if len(pending) > 2:
@@ -387,7 +400,9 @@ class VAENet:
                 vs: Dict[str, float] = {}
                 vseen = 0
                 for (c0, c1, gb) in vpieces:
-                    scal = eng.eval_step(1, first=c0, B=c1 - c0, global_batch=gb, seed=core.next_seed())
+                    # a rank's piece of a global batch is contiguous in the set as well: vhome[c0] is its first row
+                    scal = eng.eval_step(1, first=int(vhome[c0]) if vstreamed else c0, B=c1 - c0, global_batch=gb,
+                                         seed=core.next_seed())
                     self._set_losses(scal)
                     for k, v in self._metric_values(scal).items():
                         vs[k] = vs.get(k, 0.0) + v * gb
@@ -445,10 +460,76 @@ class VAENet:
         self._core.engine.upload(slot, xs, ys)
         cache[slot] = key
 
-    def evaluate(self, x, y, batch_size=32, verbose=0):
+    @staticmethod
+    def _device_reserve(total):
+        """Device memory the default budget leaves free of data: the workspaces the engine grows lazily (the per-step
+        buffer pool and weight-gradient slabs of the first overlapped backward, the streaming ring, the inference pipe's
+        transfer buffers - several GB at deblend()'s 8192-stamp chunks) and other processes on a shared GPU.  1/32 of
+        the GPU (9 GB of an MI355X's 288), at least 2 GiB."""
+        return max(2 << 30, int(total) // 32)
+
+    def _placement(self, slot, need, stamp_bytes, budget):
+        """'resident', 'stream', or 'try' (resident if the upload succeeds, streamed otherwise) for `need` bytes of rows
+        in `slot` under device_data_budget `budget`."""
+        if budget is not None:
+            return "resident" if need <= budget else "stream"
+        mem_info = getattr(self._core.ctx, "mem_info", None)
+        if mem_info is None:                 # a context that cannot report its device memory keeps the resident path
+            return "resident"
+        free, total = mem_info()
+        info = self._core.engine.data_info(slot)
+        if info["mode"] == 1:                # the slot's resident rows are freed before the new ones are allocated
+            free += 2 * info["n"] * stamp_bytes
+        if need <= free - self._device_reserve(total):
+            return "resident"
+        return "try" if need <= free else "stream"
+
+    def _place(self, slot, x_orig, x, y_orig, y, home, geometry, reuse, budget):
+        """This rank's rows of a set into `slot`: resident in HBM (_upload) or streamed from the caller's arrays
+        (Engine.open_stream, which reads their own buffers: no float32 copy, no x[home], nothing read from a memmap
+        beyond the rows of each step).  returns (streamed, device bytes the resident rows occupy)."""
+        stamp_bytes = 4 * int(np.prod(np.shape(x)[1:]))
+        need = 2 * int(home.size) * stamp_bytes
+        plan = self._placement(slot, need, stamp_bytes, budget)
+        if plan != "stream":
+            try:
+                self._upload(slot, x_orig, x, y_orig, y, home, geometry, reuse)
+                return False, need
+            except (MemoryError, RuntimeError):
+                if plan == "resident":
+                    raise
+        self._core.upload_keys.pop(slot, None)
+        self._core.engine.open_stream(slot, self._streamable(x), self._streamable(y))
+        return True, 0
+
+    @staticmethod
+    def _streamable(a):
+        """`a` itself when a streamed slot can read it (float32 / float64 rows, each contiguous), else a float32 copy"""
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64) or not a.dtype.isnative:
+            return np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim >= 2 and a.shape[0] and not a[0].flags.c_contiguous:
+            return np.ascontiguousarray(a)
+        return a
+
+    def evaluate(self, x, y, batch_size=32, verbose=0, device_data_budget=None):
+        """Keras Model.evaluate: loss and metrics over (x, y) in inference mode.  device_data_budget as in fit(): a set
+        too large for it is streamed from the caller's arrays (slot 1)."""
         eng, core = self._core.engine, self._core
         core.upload_keys.pop(1, None)        # slot 1 no longer holds fit()'s validation set (reuse_device_data)
-        n = eng.upload(1, x, y)
+        n = np.shape(x)[0]
+        stamp_bytes = 4 * int(np.prod(np.shape(x)[1:]))
+        plan = self._placement(1, 2 * n * stamp_bytes, stamp_bytes, device_data_budget)
+        streamed = plan == "stream"
+        if not streamed:
+            try:
+                n = eng.upload(1, x, y)
+            except (MemoryError, RuntimeError):
+                if plan == "resident":
+                    raise
+                streamed = True
+        if streamed:
+            n = eng.open_stream(1, self._streamable(x), self._streamable(y))
         tot: Dict[str, float] = {}
         for b0 in range(0, n, batch_size):
             gb = min(batch_size, n - b0)

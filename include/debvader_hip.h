@@ -147,10 +147,24 @@ int dv_optimizer_reset(dv_model* m, float lr, float beta1, float beta2, float ep
 int dv_optimizer_get_iter(dv_model* m, int64_t* iter);
 int dv_optimizer_set_iter(dv_model* m, int64_t iter);
 
-/* ---- data resident in HBM ------------------------------------------------------------------ */
+/* ---- data resident in HBM (or streamed, below) ----------------------------------------------- */
 /* slot 0/1 (train / validation): copies n stamps x[n,H,W,C], y[n,H,W,C] to the device once per fit() */
 int dv_data_upload(dv_model* m, int32_t slot, const float* x, const float* y, int64_t n);
 int dv_data_free(dv_model* m, int32_t slot);
+/* ---- data streamed from host memory (a set larger than HBM) ---------------------------------- */
+/* slot 0/1 reads its rows from host memory for every step instead of from HBM.  x, y: n rows of H*W*C elements each
+ * contiguous, float32 or float64 (x_f64 / y_f64: cast to float32 as a C cast / numpy's astype do), row_stride_* bytes
+ * apart; the caller keeps them alive and unchanged until dv_data_free(slot) or the next dv_data_upload /
+ * dv_data_stream_open of the slot.  The step functions then name rows of these arrays; each call gathers its rows
+ * into pinned staging and queues their host-to-device copy into a device ring of four batches.  dv_train_steps
+ * refuses a streamed slot. */
+int dv_data_stream_open(dv_model* m, int32_t slot, const void* x, int32_t x_f64, const void* y, int32_t y_f64,
+                        int64_t n, int64_t row_stride_x, int64_t row_stride_y);
+/* mode of a slot (0 empty, 1 resident, 2 streamed), its rows, and the bytes it has moved host->device since it was
+ * uploaded or opened */
+int dv_data_info(dv_model* m, int32_t slot, int32_t* mode, int64_t* n, int64_t* h2d_bytes);
+/* free / total device memory of the context's GPU (hipMemGetInfo) */
+int dv_ctx_mem_info(dv_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes);
 
 /* ---- steps: replace one Keras train_function / test_function call inside net.fit (train.py:27-37) ---- */
 /* Batch = rows idx[0..B) of `slot` (idx == NULL: rows first..first+B).  eps == NULL: the engine draws
