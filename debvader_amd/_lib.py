@@ -123,6 +123,8 @@ SIGNATURES = {
                                              C.c_uint64, _d, _d, _d, _d]),
     "dv_scene_extract": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _d]),
     "dv_scene_composite": (C.c_int, [_p, _d, C.c_int32, C.c_int32, _d, _d, C.c_int32, C.c_int32, C.c_double]),
+    "dv_scene_fit_shifts": (C.c_int, [_p, _d, C.c_int32, _d, C.c_int32, C.c_int32, _d, C.c_double, C.c_int32, _d, _d,
+                                      _i32, _i32]),
     "dv_infer_mc": (C.c_int, [_p, _f, C.c_int64, C.c_int32, C.c_uint64, _f, _f]),
     "dv_encode": (C.c_int, [_p, _f, C.c_int64, _f]),
     "dv_decode": (C.c_int, [_p, _f, C.c_int64, _f, _f]),

@@ -169,6 +169,10 @@ int scene_extract(const double* field_h, int F, int nb, const int32_t* starts_h,
                   hipStream_t s);
 int scene_composite(double* field_h, int F, int nb, const double* stamps_h, const double* pos_h, int N, int cs,
                     double sign, hipStream_t s);
+// batched sub-pixel position fit on the r band (posfit.hip): host float64 buffers in and out
+int scene_fit_shifts(const double* field_h, int F, const double* stamps_h, int N, int cs, const double* dist_h,
+                     double bound, int max_iter, double* shifts_h, double* objective_h, int32_t* iters_h,
+                     int32_t* status_h, hipStream_t s);
 
 // Strip form of the stride-1 3x3 gather-GEMM for the 32-channel high-resolution layers (gconv_strip.hip)
 struct GStripParams {

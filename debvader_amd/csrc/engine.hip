@@ -3495,6 +3495,15 @@ int dv_scene_composite(dv_ctx* c, double* field, int32_t F, int32_t nb, const do
   return scene_composite(field, F, nb, stamps, pos, N, cs, sign, c->stream);
 }
 
+int dv_scene_fit_shifts(dv_ctx* c, const double* field_r, int32_t F, const double* stamps_r, int32_t N, int32_t cs,
+                        const double* dist, double bound, int32_t max_iter, double* shifts_inout, double* objective,
+                        int32_t* iters, int32_t* status) {
+  if (!c) return DV_E_INVALID;
+  DV_HIP(hipSetDevice(c->device));
+  return scene_fit_shifts(field_r, F, stamps_r, N, cs, dist, bound, max_iter, shifts_inout, objective, iters, status,
+                          c->stream);
+}
+
 int dv_ctx_allreduce_host(dv_ctx* c, float* buf, int32_t n) {
   if (!c || !buf || n < 0 || n > 4096) return DV_E_INVALID;
   if (!c->comm || n == 0) return DV_OK;

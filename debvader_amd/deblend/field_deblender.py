@@ -3,8 +3,10 @@
 Same class and method names as the reference.  What runs on the GPU: cutout extraction, the network
 (`deblend`), the epistemic Monte-Carlo estimate (one engine call for all objects instead of a Python loop of
 100-stamp batches) and the residual / predicted field compositing (instead of one scipy.ndimage.shift of a
-field-sized image per object and band).  Not provided: source detection (`sep`, detect/detection.py) and the
-scipy.optimize position fit (deblend_cutout/optimization.py) - `optimise_positions=True` raises.
+field-sized image per object and band) and the sub-pixel position fit (deblend_cutout/optimization.py, one batched engine
+call for all galaxies instead of a scipy.optimize run per galaxy): `optimise_positions()` fits the rows of a deblended
+recarray and writes their `shifts`.  `deblend_field(optimise_positions=True)` still raises: run `deblend_field` and then
+`optimise_positions()`.  Not provided: source detection (`sep`, detect/detection.py).
 """
 import numpy as np
 import pandas as pd
@@ -135,6 +137,35 @@ class DeblendField:
         meta.update(self.get_predicted_field(res_deblend))
         return meta
 
+    # -- position fit ------------------------------------------------------------------------------
+    def optimise_positions(self, res_deblend=None, field_image=None):
+        """Fit the sub-pixel shift of every row of `res_deblend` (None: self.res_deblend) and write it to the `shifts` column.
+
+        The reference's per-galaxy position_optimization (field_deblender.py:337-352, deblend_cutout/optimization.py) for
+        all rows at once, whatever `passed_cuts` says, as the reference does: the r band of `field_image` (None:
+        self.field_image) against each row's `output_images_mean` placed at its distance to the centre, shifts in
+        [-3, 3]^2.  Each `shifts` entry becomes a float64 np.array([shift_x, shift_y]); get_residual_field() and
+        get_predicted_field() then place the galaxies at distance + shift.  Returns the recarray.  A recarray from
+        deblend_field(on_device=True) carries no stamps and raises ValueError."""
+        from debvader_amd.deblend_cutout.optimization import position_optimization_batch
+
+        if res_deblend is None:
+            res_deblend = self.res_deblend
+        if res_deblend is None or getattr(getattr(res_deblend, "dtype", None), "names", None) is None:
+            raise ValueError("optimise_positions() needs the recarray of a deblend_field() pass")
+        if len(res_deblend) == 0:
+            return res_deblend
+        stamps = self._stack(res_deblend, "output_images_mean")
+        dist = np.array([[row["galaxy_distances_to_center_x"], row["galaxy_distances_to_center_y"]] for row in res_deblend],
+                        dtype=np.float64)
+        shifts = position_optimization_batch(self.field_image if field_image is None else field_image, stamps, dist,
+                                             bound=3.0, ctx=self._ctx)
+        col = np.empty(len(res_deblend), dtype=object)
+        for i in range(len(res_deblend)):
+            col[i] = np.array([shifts[i, 0], shifts[i, 1]], dtype=np.float64)
+        res_deblend["shifts"] = col
+        return res_deblend
+
     # -- one deblending pass -----------------------------------------------------------------------
     def deblend_field(self, galaxy_distances_to_center, cutout_images=None, optimise_positions=False,
                       epistemic_criterion=100.0, mse_criterion=100.0, field_image=None, on_device=False):
@@ -160,8 +191,9 @@ class DeblendField:
         cutouts and no epistemic pass (each raises with a message otherwise).
         """
         if optimise_positions:
-            raise NotImplementedError("optimise_positions=True needs the scipy.optimize position fit of "
-                                      "deblend_cutout/optimization.py, which is outside this engine's scope")
+            raise NotImplementedError("optimise_positions=True is not wired into deblend_field: call deblend_field() and then "
+                                      "DeblendField.optimise_positions(), which fits the positions of all rows on the GPU "
+                                      "(deblend_cutout/optimization.py)")
         if on_device:
             if isinstance(cutout_images, np.ndarray):
                 raise ValueError("on_device=True cuts the stamps out of the field on the GPU; caller-supplied cutout_images "

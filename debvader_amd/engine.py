@@ -342,6 +342,43 @@ class Context:
                                      stamps.shape[1], float(sign)))
         return out
 
+    FIT_CONVERGED, FIT_ON_BOUND, FIT_ITER_LIMIT, FIT_STALLED = 0, 1, 2, 3     # status codes of scene_fit_shifts
+
+    def scene_fit_shifts(self, field_r, stamps_r, distances, shifts=None, bound: float = 3.0,
+                         max_iter: int = 50) -> Dict[str, np.ndarray]:
+        """Sub-pixel position fit of every galaxy on the r band (deblend_cutout/optimization.py, batched on the GPU).
+
+        field_r (F, F), stamps_r (N, cs, cs), distances (N, 2) {row, column} to the centre.  Galaxy i minimises
+        J(s) = mean over the field of (field_r - shift(shift(pad(stamps_r[i]), distances[i]), s))^2 over s in
+        [-bound, bound]^2, started from shifts[i] (zeros by default), with scipy.ndimage.shift semantics.
+        Returns {shifts (N, 2), objective (N,) J at them, iters (N,), status (N,): FIT_CONVERGED, FIT_ON_BOUND,
+        FIT_ITER_LIMIT or FIT_STALLED (no damped step lowered J)}.  max_iter = 0 evaluates J at the given shifts."""
+        field_r = np.ascontiguousarray(field_r, dtype=np.float64)
+        stamps_r = np.ascontiguousarray(stamps_r, dtype=np.float64)
+        dist = np.ascontiguousarray(distances, dtype=np.float64)
+        if field_r.ndim != 2 or field_r.shape[0] != field_r.shape[1] or field_r.shape[0] < 2:
+            raise ValueError(f"expected a square r-band field (F, F), got {field_r.shape}")
+        if stamps_r.ndim != 3 or stamps_r.shape[1] != stamps_r.shape[2] or stamps_r.shape[1] > field_r.shape[0]:
+            raise ValueError(f"expected square r-band stamps (N, cs, cs) with cs <= {field_r.shape[0]}, got {stamps_r.shape}")
+        n = stamps_r.shape[0]
+        if dist.shape != (n, 2):
+            raise ValueError(f"expected distances ({n}, 2), got {dist.shape}")
+        out = np.zeros((n, 2), np.float64) if shifts is None else np.array(shifts, dtype=np.float64, order="C", copy=True)
+        if out.shape != (n, 2):
+            raise ValueError(f"expected shifts ({n}, 2), got {out.shape}")
+        if not (np.isfinite(bound) and bound >= 0) or int(max_iter) < 0:
+            raise ValueError(f"bound must be finite and >= 0, max_iter >= 0 (got {bound}, {max_iter})")
+        obj = np.zeros(n, np.float64)
+        iters = np.zeros(n, np.int32)
+        status = np.zeros(n, np.int32)
+        if n:
+            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+            check(lib.dv_scene_fit_shifts(self._h, field_r.ctypes.data_as(dp), field_r.shape[0], stamps_r.ctypes.data_as(dp),
+                                          n, stamps_r.shape[1], dist.ctypes.data_as(dp), float(bound), int(max_iter),
+                                          out.ctypes.data_as(dp), obj.ctypes.data_as(dp), iters.ctypes.data_as(ip),
+                                          status.ctypes.data_as(ip)))
+        return dict(shifts=out, objective=obj, iters=iters, status=status)
+
     def close(self):
         """Destroys the engines created on this context, then the context.  Idempotent."""
         for eng in list(self._engines):

@@ -283,6 +283,19 @@ int dv_scene_extract(dv_ctx* ctx, const double* field, int32_t F, int32_t nb, co
                      int32_t cs, double* out);
 int dv_scene_composite(dv_ctx* ctx, double* field, int32_t F, int32_t nb, const double* stamps, const double* pos,
                        int32_t N, int32_t cs, double sign);
+/* dv_scene_fit_shifts: the sub-pixel position fit of deblend_cutout/optimization.py (position_optimization), batched.
+ * For galaxy i, on the r band only: net = shift(pad(stamps_r[i]), dist[i]), J(s) = mean over the F x F field of
+ * (field_r - shift(net, s))^2, minimised over s in [-bound, bound]^2 from shifts_inout[i] (box-projected Newton with
+ * analytic derivatives, float64).  field_r [F][F], stamps_r [N][cs][cs], dist / shifts_inout [N][2] as {row, column}.
+ * Out: shifts_inout[i] = the fitted shift, objective[i] = J there, iters[i] = accepted Newton steps, status[i] =
+ * 0 converged (step or projected gradient below 1e-10 px), 1 converged on a bound, 2 max_iter reached, 3 stalled (no
+ * damped step lowered J: the shift is the best one found, not a certified optimum).
+ * max_iter = 0 evaluates J at the given shifts and returns status 2.  Distances, start shifts and bound must lie within
+ * +-1e6, F within 2 .. 32768; a galaxy whose window needs more than 1 GiB of workspace is refused (DV_E_INVALID).
+ * Bit-reproducible for any N. */
+int dv_scene_fit_shifts(dv_ctx* ctx, const double* field_r, int32_t F, const double* stamps_r, int32_t N, int32_t cs,
+                        const double* dist, double bound, int32_t max_iter, double* shifts_inout, double* objective,
+                        int32_t* iters, int32_t* status);
 
 /* ---- introspection for tests and bench ----------------------------------------------------- */
 /* copy a named activation of the last step to host: "t","z","kl","eps","loc","scale","head_pre" */
