@@ -18,10 +18,12 @@ _LAZY = {
     "train_deblender": ("debvader_amd.training.train", "train_deblender"),
     "extract_cutouts": ("debvader_amd.extract.extraction", "extract_cutouts"),
 }
-# reference: src/debvader/__init__.py:2 - the iterative procedure needs `sep` source detection (detect/detection.py), which is
-# outside this engine's scope; the name is answered with the reason instead of an AttributeError
-_OUT_OF_SCOPE = {"IterativeDeblendField": "the iterative procedure of deblend_iterative/ drives `sep` source detection, which this "
-                                          "engine does not provide; run the reference's loop around debvader_amd.DeblendField"}
+# reference: src/debvader/__init__.py:2 - the iterative procedure drives `sep` source detection (detect/detection.py).  This
+# engine's detector is SExtractor's method on the GPU, not sep, so the root name stays unbound and answers with where the
+# class lives instead of an AttributeError
+_OUT_OF_SCOPE = {"IterativeDeblendField": "the reference's iterative procedure drives `sep` source detection; this engine's "
+                                          "detector is SExtractor's method on the GPU (DESIGN.md section 7e), not sep: import "
+                                          "debvader_amd.deblend_iterative.iterative_deblender.IterativeDeblendField"}
 
 __all__ = ["__version__"] + sorted(_LAZY)
 

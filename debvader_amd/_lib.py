@@ -35,6 +35,16 @@ class DvConfig(C.Structure):
 DV_DTYPE_F32, DV_DTYPE_BF16 = 0, 1
 
 
+class DvDetectParams(C.Structure):
+    """dv_detect_params (include/debvader_hip.h)"""
+    _fields_ = [
+        ("thresh", C.c_double), ("cont", C.c_double),
+        ("minarea", C.c_int32), ("nthresh", C.c_int32), ("back_size", C.c_int32), ("back_filter", C.c_int32),
+        ("kernel", C.POINTER(C.c_double)), ("kh", C.c_int32), ("kw", C.c_int32),
+        ("workspace_bytes", C.c_int64),
+    ]
+
+
 class DvError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libdebvader_hip status {status}: {msg}")
@@ -125,6 +135,8 @@ SIGNATURES = {
     "dv_scene_composite": (C.c_int, [_p, _d, C.c_int32, C.c_int32, _d, _d, C.c_int32, C.c_int32, C.c_double]),
     "dv_scene_fit_shifts": (C.c_int, [_p, _d, C.c_int32, _d, C.c_int32, C.c_int32, _d, C.c_double, C.c_int32, _d, _d,
                                       _i32, _i32]),
+    "dv_scene_detect": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams), C.c_int64, _i64,
+                                  _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d, _d, _d, _d, _i32]),
     "dv_infer_mc": (C.c_int, [_p, _f, C.c_int64, C.c_int32, C.c_uint64, _f, _f]),
     "dv_encode": (C.c_int, [_p, _f, C.c_int64, _f]),
     "dv_decode": (C.c_int, [_p, _f, C.c_int64, _f, _f]),

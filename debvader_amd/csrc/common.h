@@ -173,6 +173,12 @@ int scene_composite(double* field_h, int F, int nb, const double* stamps_h, cons
 int scene_fit_shifts(const double* field_h, int F, const double* stamps_h, int N, int cs, const double* dist_h,
                      double bound, int max_iter, double* shifts_h, double* objective_h, int32_t* iters_h,
                      int32_t* status_h, hipStream_t s);
+// batched source detection on one band (detect.hip): host float64 fields in, host catalog out
+int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
+                 int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
+                 int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
+                 int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
+                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s);
 
 // Strip form of the stride-1 3x3 gather-GEMM for the 32-channel high-resolution layers (gconv_strip.hip)
 struct GStripParams {

@@ -1,0 +1,982 @@
+// Source detection (reference: detect/detection.py, which calls sep), batched over fields, float64 throughout.
+//
+// SExtractor's published method (Bertin & Arnouts 1996) with the rules of DESIGN.md section 7e; tests/detect_oracle.py is
+// the same definition in numpy.  Per chunk of fields:
+//  1. bkg_mesh_kernel    one workgroup per mesh (<= 64 x 64 values): bitonic sort in LDS, then every kept set of the
+//                        sigma clipping is a contiguous range of the sorted values (two binary searches and two fixed-order
+//                        reductions per round).
+//  2. bkg_grid_kernel    one workgroup per field: median filter over the meshes, globalrms, spline second derivatives along
+//                        the mesh rows.
+//  3. bkg_row_kernel     one thread per pixel row: the mesh-row splines at that row, then the spline along the columns.
+//  4. bkg_pixel_kernel   back (and rms) per pixel, v = data - back.
+//  5. filter_kernel      16 x 16 output tiles with the kernel's halo in LDS: D, and the segmentation's initial parents.
+//  6. cc_merge_kernel    8-connected union-find over the field on a global parent array: links always go from the larger
+//                        root to the smaller (atomic min), so every root is the smallest raster index of its component
+//                        whatever the dispatch order.  Parents other threads write in the same launch are read with relaxed
+//                        agent-scope atomics.  cc_flatten_kernel (next launch) writes the labels, areas and bounding boxes.
+//  7. cc_compact_kernel  one workgroup per field: the components of >= minarea pixels in root order (block scans).
+//  8. deblend_kernel     one workgroup per component: pixel list in raster order (scan of the bounding box), the nthresh - 1
+//                        levels with a union-find per level, the decision rule, the argmax assignment and the catalog, each
+//                        reduction in a fixed order.  Components of <= DB_LDS pixels keep their hot arrays in LDS, larger ones
+//                        run the same code on global scratch.
+// The catalog is sized in two phases: the component table comes back to the host, which places every component's
+// scratch and catalog slots (an object holds >= minarea core pixels, so a component has at most n / minarea of them).
+// fp64 VALU and integer work; nothing here has a matrix shape for MFMA.
+#include "common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <initializer_list>
+#include <vector>
+
+// Every multiply and add is rounded on its own, as in the numpy restatement (tests/detect_oracle.py): a contracted FMA
+// could move a D value across the threshold or reorder two near-equal assignment scores.
+#pragma clang fp contract(off)
+
+namespace dv {
+
+namespace {
+constexpr int DT = 256;              // threads of every workgroup here (four waves)
+constexpr int MESH_MAX = 4096;       // back_size <= 64
+constexpr int DB_LDS = 2048;         // component pixels the deblend keeps in LDS
+constexpr int MF_MAX = 7;            // back_filter <= 7
+constexpr int KMAX = 15;             // filter kernels up to 15 x 15
+constexpr int FT = 16;               // filter output tile
+constexpr int DIM_MAX = 1 << 19;     // H, W (filter grid rows)
+constexpr int CHUNK_MAX = 65535;     // fields per launch (filter grid z)
+
+__device__ __forceinline__ int ald(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int amin(int* p, int v) {
+  return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void ast(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void aadd(int* p, int v) {
+  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// sum of v over the workgroup in a fixed order; every thread gets the result
+template <int K>
+__device__ __forceinline__ void blk_sum(double (&v)[K], double* s_red) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+  }
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) s_red[wave * K + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = ((s_red[k] + s_red[K + k]) + (s_red[2 * K + k] + s_red[3 * K + k]));
+}
+
+// (max v, smallest i at it) over the workgroup; every thread gets the result
+__device__ __forceinline__ void blk_argmax(double& v, int& i, double* s_v, int* s_i) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+  __syncthreads();
+  if (lane == 0) { s_v[wave] = v; s_i[wave] = i; }
+  __syncthreads();
+  v = s_v[0];
+  i = s_i[0];
+  for (int w = 1; w < 4; ++w)
+    if (s_v[w] > v || (s_v[w] == v && s_i[w] < i)) { v = s_v[w]; i = s_i[w]; }
+}
+
+// exclusive prefix sum of x over the workgroup in thread order; total = the sum
+__device__ __forceinline__ int blk_scan(int x, int* s_w, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = x;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  __syncthreads();
+  if (lane == 63) s_w[wave] = inc;
+  __syncthreads();
+  int base = 0;
+  total = 0;
+  for (int w = 0; w < 4; ++w) {
+    if (w < wave) base += s_w[w];
+    total += s_w[w];
+  }
+  return base + inc - x;
+}
+
+__device__ __forceinline__ int blk_isum(int x, int* s_w) {
+  int t;
+  (void)blk_scan(x, s_w, t);
+  return t;
+}
+
+// ---- background --------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double median_sorted(const double* s, int n) {
+  return (n & 1) ? s[n / 2] : 0.5 * (s[n / 2 - 1] + s[n / 2]);
+}
+
+__global__ __launch_bounds__(DT) void bkg_mesh_kernel(const double* __restrict__ data, int H, int W, int bs, int ny,
+                                                      int nx, double* __restrict__ mback, double* __restrict__ mrms) {
+  __shared__ double s[MESH_MAX];
+  __shared__ double s_red[4];
+  const int tid = threadIdx.x;
+  const long mesh = blockIdx.x;
+  const int per = ny * nx;
+  const long f = mesh / per;
+  const int mi = (int)(mesh - f * per), i = mi / nx, j = mi - (mi / nx) * nx;
+  const int r0 = i * bs, c0 = j * bs;
+  const int bh = min(bs, H - r0), bw = min(bs, W - c0);
+  const int n = bh * bw;
+  int N = 1;
+  while (N < n) N <<= 1;
+  const double* src = data + f * (long)H * W;
+  for (int e = tid; e < N; e += DT) s[e] = e < n ? src[(long)(r0 + e / bw) * W + c0 + e % bw] : INFINITY;
+  __syncthreads();
+  for (int k = 2; k <= N; k <<= 1) {            // bitonic sort, ascending
+    for (int jj = k >> 1; jj > 0; jj >>= 1) {
+      for (int e = tid; e < N; e += DT) {
+        const int p = e ^ jj;
+        if (p > e) {
+          const double a = s[e], b = s[p];
+          if ((e & k) == 0 ? a > b : a < b) { s[e] = b; s[p] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  int lo = 0, hi = n;
+  double mean = 0.0, sig = 0.0, med = 0.0;
+  for (int round = 0; round <= 100; ++round) {
+    const int m = hi - lo;
+    double a[1] = {0.0};
+    for (int e = lo + tid; e < hi; e += DT) a[0] += s[e];
+    blk_sum<1>(a, s_red);
+    mean = a[0] / m;
+    double b[1] = {0.0};
+    for (int e = lo + tid; e < hi; e += DT) {
+      const double d = s[e] - mean;
+      b[0] += d * d;
+    }
+    blk_sum<1>(b, s_red);
+    sig = sqrt(b[0] / m);
+    med = median_sorted(s + lo, m);
+    if (round == 100) break;                       // the statistics of the set after 100 rounds
+    const double la = med - 3.0 * sig, ha = med + 3.0 * sig;
+    int l = lo, h = hi;
+    while (l < h) { const int c = (l + h) >> 1; if (s[c] < la) l = c + 1; else h = c; }
+    const int nlo = l;
+    l = lo; h = hi;
+    while (l < h) { const int c = (l + h) >> 1; if (s[c] <= ha) l = c + 1; else h = c; }
+    const int nhi = l;
+    if (nlo == lo && nhi == hi) break;            // the kept set did not change: these are its statistics
+    lo = nlo;
+    hi = nhi;
+  }
+  if (tid == 0) {
+    mback[mesh] = fabs(mean - med) < 0.3 * sig ? 2.5 * med - 1.5 * mean : med;
+    mrms[mesh] = sig;
+  }
+}
+
+// second derivatives of the natural cubic spline through y[0], y[st], ... (n values, unit spacing) into m (same stride);
+// cco[i] = the Thomas coefficients of the (1, 4, 1) tridiagonal system, the same for every n
+__device__ void spline_d2(const double* y, long st, int n, const double* __restrict__ cco, double* m) {
+  for (int i = 0; i < n; ++i) m[i * st] = 0.0;
+  if (n < 3) return;
+  const int k = n - 2;
+  double dp = 0.0;
+  for (int i = 0; i < k; ++i) {
+    const double r = 6.0 * (y[(i + 2) * st] - 2.0 * y[(i + 1) * st] + y[i * st]);
+    const double d = i == 0 ? r * 0.25 : (r - dp) * cco[i];
+    m[(i + 1) * st] = d;
+    dp = d;
+  }
+  for (int i = k - 2; i >= 0; --i) m[(i + 1) * st] = m[(i + 1) * st] - cco[i] * m[(i + 2) * st];
+}
+
+__device__ __forceinline__ double spline_eval(const double* y, const double* m, long st, int n, double u) {
+  if (n == 1) return y[0];
+  const double fk = fmin(fmax(floor(u), 0.0), (double)(n - 2));
+  const int k = (int)fk;
+  const double t = u - fk, a = 1.0 - t;
+  return a * y[k * st] + t * y[(k + 1) * st] + (a * a * a - a) * m[k * st] / 6.0 +
+         (t * t * t - t) * m[(k + 1) * st] / 6.0;
+}
+
+// per field: median-filtered mesh grids (fb, fr), globalrms, second derivatives along the mesh rows (d2b, d2r)
+__global__ __launch_bounds__(DT) void bkg_grid_kernel(const double* __restrict__ mback, const double* __restrict__ mrms,
+                                                      int ny, int nx, int fs, const double* __restrict__ cco,
+                                                      double* fb, double* fr, double* d2b, double* d2r,
+                                                      double* __restrict__ grms) {
+  __shared__ double s_red[4];
+  const int tid = threadIdx.x;
+  const int per = ny * nx;
+  const long base = (long)blockIdx.x * per;
+  const int h = fs / 2;
+  for (int e = tid; e < 2 * per; e += DT) {
+    const int which = e / per, mi = e - which * per, i = mi / nx, j = mi - (mi / nx) * nx;
+    const double* g = (which ? mrms : mback) + base;
+    double w[MF_MAX * MF_MAX];
+    int n = 0;
+    for (int a = max(0, i - h); a <= min(ny - 1, i + h); ++a)
+      for (int b = max(0, j - h); b <= min(nx - 1, j + h); ++b) {
+        const double x = g[a * nx + b];
+        int q = n++;
+        while (q > 0 && w[q - 1] > x) { w[q] = w[q - 1]; --q; }
+        w[q] = x;
+      }
+    (which ? fr : fb)[base + mi] = median_sorted(w, n);
+  }
+  __syncthreads();
+  double a[1] = {0.0};
+  for (int e = tid; e < per; e += DT) a[0] += fr[base + e];
+  blk_sum<1>(a, s_red);
+  if (tid == 0) grms[blockIdx.x] = a[0] / per;
+  for (int e = tid; e < 2 * nx; e += DT) {
+    const int which = e / nx, j = e - which * nx;
+    spline_d2((which ? fr : fb) + base + j, nx, ny, cco, (which ? d2r : d2b) + base + j);
+  }
+}
+
+// one thread per (field, pixel row): the mesh-row splines at the row (g) and their spline along the columns (g2)
+__global__ __launch_bounds__(DT) void bkg_row_kernel(const double* __restrict__ fb, const double* __restrict__ fr,
+                                                     const double* __restrict__ d2b, const double* __restrict__ d2r,
+                                                     int M, int H, int ny, int nx, int bs, int want_rms,
+                                                     const double* __restrict__ cco, double* gb, double* gb2,
+                                                     double* gr, double* gr2) {
+  const long e = (long)blockIdx.x * DT + threadIdx.x;
+  if (e >= (long)M * H) return;
+  const long f = e / H;
+  const int r = (int)(e - f * H);
+  const double u = (r + 0.5) / bs - 0.5;
+  const long gbase = f * (long)ny * nx;
+  for (int which = 0; which < 1 + want_rms; ++which) {
+    const double* y = (which ? fr : fb) + gbase;
+    const double* m = (which ? d2r : d2b) + gbase;
+    double* g = (which ? gr : gb) + e * nx;
+    double* g2 = (which ? gr2 : gb2) + e * nx;
+    for (int j = 0; j < nx; ++j) g[j] = spline_eval(y + j, m + j, nx, ny, u);
+    spline_d2(g, 1, nx, cco, g2);
+  }
+}
+
+__global__ __launch_bounds__(DT) void bkg_pixel_kernel(const double* __restrict__ data, long total, int W, int nx,
+                                                       int bs, const double* __restrict__ gb, const double* __restrict__ gb2,
+                                                       const double* __restrict__ gr, const double* __restrict__ gr2,
+                                                       double* __restrict__ v, double* __restrict__ back,
+                                                       double* __restrict__ rms) {
+  const long e = (long)blockIdx.x * DT + threadIdx.x;
+  if (e >= total) return;
+  const long row = e / W;                         // field * H + pixel row
+  const int c = (int)(e - row * W);
+  const double u = (c + 0.5) / bs - 0.5;
+  const double b = spline_eval(gb + row * nx, gb2 + row * nx, 1, nx, u);
+  v[e] = data[e] - b;
+  if (back) back[e] = b;
+  if (rms) rms[e] = spline_eval(gr + row * nx, gr2 + row * nx, 1, nx, u);
+}
+
+// D = correlation of v with kn (normalised taps), zero outside the field; par = own index where D > thresh * globalrms
+__global__ __launch_bounds__(DT) void filter_kernel(const double* __restrict__ v, int H, int W,
+                                                    const double* __restrict__ kn, int kh, int kw,
+                                                    const double* __restrict__ grms, double thresh,
+                                                    double* __restrict__ D, int* __restrict__ par) {
+  __shared__ double t[(FT + KMAX - 1) * (FT + KMAX - 1)];
+  const int tid = threadIdx.x;
+  const long f = blockIdx.z;
+  const int r0 = blockIdx.y * FT, c0 = blockIdx.x * FT, ry = kh / 2, rx = kw / 2;
+  const int TH = FT + kh - 1, TW = FT + kw - 1;
+  const long fb = f * (long)H * W;
+  for (int e = tid; e < TH * TW; e += DT) {
+    const int a = e / TW, b = e - (e / TW) * TW, r = r0 - ry + a, c = c0 - rx + b;
+    t[e] = (r >= 0 && r < H && c >= 0 && c < W) ? v[fb + (long)r * W + c] : 0.0;
+  }
+  __syncthreads();
+  const int ty = tid / FT, tx = tid % FT, r = r0 + ty, c = c0 + tx;
+  if (r >= H || c >= W) return;
+  double acc = 0.0;
+  for (int a = 0; a < kh; ++a)
+    for (int b = 0; b < kw; ++b) acc += kn[a * kw + b] * t[(ty + a) * TW + tx + b];
+  const long o = fb + (long)r * W + c;
+  D[o] = acc;
+  par[o] = acc > thresh * grms[f] ? r * W + c : -1;
+}
+
+// ---- connected components ---------------------------------------------------------------------------------------
+__device__ __forceinline__ int uf_find(int* par, int x) {
+  int p = ald(par + x);
+  while (p != x) {
+    x = p;
+    p = ald(par + x);
+  }
+  return x;
+}
+
+// links the larger root under the smaller one; a failed link (the root was linked meanwhile, or the min replaced a parent)
+// carries on with the entry it found there, so no connection is lost
+__device__ void uf_union(int* par, int a, int b) {
+  for (;;) {
+    a = uf_find(par, a);
+    b = uf_find(par, b);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = amin(par + a, b);
+    if (old == a) return;
+    a = old;
+  }
+}
+
+__global__ __launch_bounds__(DT) void cc_merge_kernel(int* par, long total, int W, long HW) {
+  const long e = (long)blockIdx.x * DT + threadIdx.x;
+  if (e >= total) return;
+  const long f = e / HW;
+  const int p = (int)(e - f * HW), r = p / W, c = p - (p / W) * W;
+  int* P = par + f * HW;
+  if (ald(P + p) < 0) return;
+  if (c > 0 && ald(P + p - 1) >= 0) uf_union(P, p, p - 1);
+  if (r > 0) {
+    const int q = p - W;
+    if (c > 0 && ald(P + q - 1) >= 0) uf_union(P, p, q - 1);
+    if (ald(P + q) >= 0) uf_union(P, p, q);
+    if (c + 1 < W && ald(P + q + 1) >= 0) uf_union(P, p, q + 1);
+  }
+}
+
+// label = root (smallest raster index of the component) or -1; area and bounding box per root
+__global__ __launch_bounds__(DT) void cc_flatten_kernel(int* par, long total, int W, long HW, int* __restrict__ lab,
+                                                        int* area, int* cmin, int* cmax, int* rmax) {
+  const long e = (long)blockIdx.x * DT + threadIdx.x;
+  if (e >= total) return;
+  const long f = e / HW;
+  const int p = (int)(e - f * HW);
+  int* P = par + f * HW;
+  if (ald(P + p) < 0) { lab[e] = -1; return; }
+  const int rt = uf_find(P, p);
+  lab[e] = rt;
+  const long o = f * HW + rt;
+  aadd(area + o, 1);
+  const int r = p / W, c = p - (p / W) * W;
+  (void)__hip_atomic_fetch_min(cmin + o, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  (void)__hip_atomic_fetch_max(cmax + o, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  (void)__hip_atomic_fetch_max(rmax + o, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+constexpr int CC_PER = 16;                        // consecutive pixels per thread in the compaction scan
+
+// per field: the components of >= minarea pixels in root order -> table [ccap][5] = root, area, cmin, cmax, rmax
+__global__ __launch_bounds__(DT) void cc_compact_kernel(const int* __restrict__ lab, const int* __restrict__ area,
+                                                        const int* __restrict__ cmin, const int* __restrict__ cmax,
+                                                        const int* __restrict__ rmax, long HW, int minarea, long ccap,
+                                                        int* __restrict__ table, int* __restrict__ ncomp) {
+  __shared__ int s_w[4];
+  const long fb = (long)blockIdx.x * HW;
+  int* tab = table + (long)blockIdx.x * ccap * 5;
+  int count = 0;
+  for (long base = 0; base < HW; base += (long)DT * CC_PER) {
+    const long p0 = base + (long)threadIdx.x * CC_PER;
+    int mine = 0;
+    for (int q = 0; q < CC_PER; ++q) {
+      const long p = p0 + q;
+      if (p < HW && lab[fb + p] == (int)p && area[fb + p] >= minarea) ++mine;
+    }
+    int tot;
+    int at = count + blk_scan(mine, s_w, tot);
+    for (int q = 0; q < CC_PER && mine > 0; ++q) {
+      const long p = p0 + q;
+      if (p < HW && lab[fb + p] == (int)p && area[fb + p] >= minarea) {
+        int* row = tab + (long)at * 5;
+        row[0] = (int)p;
+        row[1] = area[fb + p];
+        row[2] = cmin[fb + p];
+        row[3] = cmax[fb + p];
+        row[4] = rmax[fb + p];
+        ++at;
+        --mine;
+      }
+    }
+    count += tot;
+  }
+  if (threadIdx.x == 0) ncomp[blockIdx.x] = count;
+}
+
+// labels map of the API: the component's root for the pixels of components of >= minarea pixels, -1 elsewhere
+__global__ __launch_bounds__(DT) void cc_labels_kernel(const int* __restrict__ lab, const int* __restrict__ area, long total,
+                                                       long HW, int minarea, int* __restrict__ out) {
+  const long e = (long)blockIdx.x * DT + threadIdx.x;
+  if (e >= total) return;
+  const int l = lab[e];
+  out[e] = (l >= 0 && area[e - e % HW + l] >= minarea) ? l : -1;
+}
+
+// ---- deblending -------------------------------------------------------------------------------------------------
+struct DbJob {
+  long fbase;          // first pixel of the component's field in the chunk arrays
+  long dws, iws;       // double / int scratch offsets
+  long slot;           // first catalog slot
+  int root, n, c0, c1, r1, cap;
+  double T;
+};
+
+// object table row (doubles): threshold, mx, my, sxx, sxy, syy, det, A
+constexpr int OBJ_D = 8;
+
+__global__ __launch_bounds__(DT) void deblend_kernel(const DbJob* __restrict__ jobs, int W, const double* __restrict__ Dall,
+                                                     const double* __restrict__ vall, const int* __restrict__ laball,
+                                                     int* lidxall, double* dscr, int* iscr, int nthresh, int minarea,
+                                                     double cont, int* __restrict__ o_npix, int* __restrict__ o_peakpix,
+                                                     double* __restrict__ o_peak, double* __restrict__ o_flux,
+                                                     double* __restrict__ o_x, double* __restrict__ o_y,
+                                                     int* __restrict__ nobj_out) {
+  __shared__ double s_D[DB_LDS];
+  __shared__ int s_pix[DB_LDS], s_par[DB_LDS], s_obj[DB_LDS];
+  __shared__ double s_red[4 * 8];
+  __shared__ int s_w[4], s_i[4], s_b[2];
+  const int tid = threadIdx.x;
+  const DbJob J = jobs[blockIdx.x];
+  const int n = J.n, cap = J.cap;
+  const bool small = n <= DB_LDS;
+  double* dw = dscr + J.dws;
+  int* iw = iscr + J.iws;
+  // scratch: doubles Dp[n] | nflux[cap] | object table [cap][OBJ_D] | next thresholds [cap]
+  //          ints    pix[n] | par[n] | obj[n] | rk[n] | cnt[n] | chid[n] | nodes[cap] | ostate[cap] | nsig[cap]
+  double* Dp = small ? s_D : dw;
+  double* nflux = dw + n;
+  double* otab = nflux + cap;
+  double* othr2 = otab + (long)OBJ_D * cap;
+  int* pix = small ? s_pix : iw;
+  int* par = small ? s_par : iw + n;
+  int* obj = small ? s_obj : iw + 2L * n;
+  int* rk = iw + 3L * n;
+  int* cnt = iw + 4L * n;
+  int* chid = iw + 5L * n;
+  int* nodes = iw + 6L * n;
+  int* ostate = nodes + cap;
+  int* nsig = ostate + cap;
+  const double* Df = Dall + J.fbase;
+  const double* vf = vall + J.fbase;
+  const int* labf = laball + J.fbase;
+  int* lidx = lidxall + J.fbase;
+
+  // a. the pixels in raster order (scan of the bounding box)
+  {
+    const int r0 = J.root / W, bw = J.c1 - J.c0 + 1;
+    const long total = (long)(J.r1 - r0 + 1) * bw;
+    int count = 0;
+    for (long base = 0; base < total; base += DT) {
+      const long e = base + tid;
+      int p = 0;
+      bool on = false;
+      if (e < total) {
+        p = (r0 + (int)(e / bw)) * W + J.c0 + (int)(e % bw);
+        on = labf[p] == J.root;
+      }
+      int tot;
+      const int at = count + blk_scan(on ? 1 : 0, s_w, tot);
+      if (on) {
+        pix[at] = p;
+        Dp[at] = Df[p];
+        lidx[p] = at;
+      }
+      count += tot;
+    }
+  }
+  __syncthreads();
+  // b. peak and flux of the component
+  double P = -INFINITY;
+  int pidx = 0x7fffffff;
+  double cf[1] = {0.0};
+  for (int i = tid; i < n; i += DT) {
+    cf[0] += Dp[i];
+    if (Dp[i] > P) { P = Dp[i]; pidx = i; }
+  }
+  blk_argmax(P, pidx, s_red, s_i);
+  blk_sum<1>(cf, s_red);
+  const double cflux = cf[0];
+  for (int i = tid; i < n; i += DT) obj[i] = 0;
+  if (tid == 0) otab[0] = J.T;
+  int nobj = 1;
+  __syncthreads();
+
+  // c. the levels
+  for (int k = 1; k < nthresh; ++k) {
+    const double t = J.T * pow(P / J.T, (double)k / (double)nthresh);
+    int mine = 0;
+    for (int i = tid; i < n; i += DT) {
+      const bool up = Dp[i] > t;
+      ast(par + i, up ? i : -1);                    // words the union-find updates with atomics: atomics only
+      ast(cnt + i, 0);
+      chid[i] = -1;
+      mine += up;
+    }
+    if (blk_isum(mine, s_w) < minarea) break;      // no node at this level or above (the same for every thread)
+    __syncthreads();
+    for (int i = tid; i < n; i += DT) {
+      if (ald(par + i) < 0) continue;
+      const int p = pix[i], r = p / W, c = p - (p / W) * W;
+      int q[4];
+      int nq = 0;
+      if (c > 0) q[nq++] = p - 1;
+      if (r > 0) {
+        if (c > 0) q[nq++] = p - W - 1;
+        q[nq++] = p - W;
+        if (c + 1 < W) q[nq++] = p - W + 1;
+      }
+      for (int a = 0; a < nq; ++a) {
+        if (labf[q[a]] != J.root) continue;
+        const int j = lidx[q[a]];
+        if (ald(par + j) >= 0) uf_union(par, i, j);
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += DT) {
+      const int rt = ald(par + i) < 0 ? -1 : uf_find(par, i);
+      rk[i] = rt;
+      if (rt >= 0) aadd(cnt + rt, 1);
+    }
+    __syncthreads();
+    // the nodes in root order
+    int nn = 0;
+    for (int base = 0; base < n; base += DT) {
+      const int i = base + tid;
+      const bool nd = i < n && rk[i] == i && ald(cnt + i) >= minarea;
+      int tot;
+      const int at = nn + blk_scan(nd ? 1 : 0, s_w, tot);
+      if (nd) nodes[at] = i;
+      nn += tot;
+    }
+    __syncthreads();
+    // node fluxes in a fixed order; nodes outside every object do not matter
+    for (int q = 0; q < nn; ++q) {
+      const int rt = nodes[q];
+      if (obj[rt] < 0) {
+        if (tid == 0) nflux[q] = 0.0;
+        continue;
+      }
+      double a[1] = {0.0};
+      for (int i = rt + tid; i < n; i += DT)
+        if (rk[i] == rt) a[0] += Dp[i];
+      blk_sum<1>(a, s_red);
+      if (tid == 0) nflux[q] = a[0];
+    }
+    __syncthreads();
+    // the decision rule (one thread: the object list is short)
+    if (tid == 0) {
+      for (int o = 0; o < nobj; ++o) nsig[o] = 0;
+      for (int q = 0; q < nn; ++q) {
+        const int o = obj[nodes[q]];
+        if (o >= 0 && nflux[q] > cont * cflux) ++nsig[o];
+      }
+      int nnew = 0, split = 0;
+      for (int o = 0; o < nobj; ++o) {
+        if (nsig[o] >= 2) {
+          split = 1;
+          ostate[o] = -1;
+          for (int q = 0; q < nn; ++q) {
+            const int rt = nodes[q];
+            if (obj[rt] == o && nflux[q] > cont * cflux) {
+              chid[rt] = nnew;
+              othr2[nnew++] = t;
+            }
+          }
+        } else {
+          ostate[o] = nnew;
+          othr2[nnew++] = otab[(long)o * OBJ_D];
+        }
+      }
+      for (int o = 0; o < nnew; ++o) otab[(long)o * OBJ_D] = othr2[o];
+      s_b[0] = nnew;
+      s_b[1] = split;
+    }
+    __syncthreads();
+    const int split = s_b[1];
+    nobj = s_b[0];
+    if (split) {
+      for (int i = tid; i < n; i += DT) {
+        const int o = obj[i];
+        if (o < 0) continue;
+        const int st = ostate[o];
+        obj[i] = st >= 0 ? st : (rk[i] >= 0 ? chid[rk[i]] : -1);
+      }
+    }
+    __syncthreads();
+  }
+
+  // d. the pixels outside every core go to the object of the largest A exp(-d' S^-1 d / 2)
+  if (nobj == 1) {
+    for (int i = tid; i < n; i += DT) obj[i] = 0;
+  } else {
+    for (int o = 0; o < nobj; ++o) {
+      double* row = otab + (long)o * OBJ_D;
+      const double th = row[0];
+      double a[3] = {0.0, 0.0, 0.0};
+      double A = -INFINITY;
+      int ai = 0x7fffffff;
+      for (int i = tid; i < n; i += DT) {
+        if (obj[i] != o) continue;
+        const double w = Dp[i] - th;
+        const int p = pix[i];
+        a[0] += w;
+        a[1] += w * (p - (p / W) * W);
+        a[2] += w * (p / W);
+        if (Dp[i] > A) { A = Dp[i]; ai = i; }
+      }
+      blk_sum<3>(a, s_red);
+      blk_argmax(A, ai, s_red + 12, s_i);
+      const double mx = a[1] / a[0], my = a[2] / a[0];
+      double b[3] = {0.0, 0.0, 0.0};
+      for (int i = tid; i < n; i += DT) {
+        if (obj[i] != o) continue;
+        const double w = Dp[i] - th;
+        const int p = pix[i];
+        const double dx = (p - (p / W) * W) - mx, dy = (p / W) - my;
+        b[0] += w * dx * dx;
+        b[1] += w * dx * dy;
+        b[2] += w * dy * dy;
+      }
+      blk_sum<3>(b, s_red);
+      if (tid == 0) {
+        const double sxx = b[0] / a[0] + 1.0 / 12.0, sxy = b[1] / a[0], syy = b[2] / a[0] + 1.0 / 12.0;
+        row[1] = mx;
+        row[2] = my;
+        row[3] = sxx;
+        row[4] = sxy;
+        row[5] = syy;
+        row[6] = sxx * syy - sxy * sxy;
+        row[7] = A;
+      }
+      __syncthreads();
+    }
+    for (int i = tid; i < n; i += DT) {
+      if (obj[i] >= 0) continue;
+      const int p = pix[i];
+      const double cx = p - (p / W) * W, cy = p / W;
+      double best = -INFINITY;
+      int bo = 0;
+      for (int o = 0; o < nobj; ++o) {
+        const double* row = otab + (long)o * OBJ_D;
+        const double ex = cx - row[1], ey = cy - row[2];
+        const double q = (row[5] * ex * ex - 2.0 * row[4] * ex * ey + row[3] * ey * ey) / row[6];
+        const double sc = row[7] * exp(-0.5 * q);
+        if (sc > best) { best = sc; bo = o; }
+      }
+      rk[i] = bo;
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += DT)
+      if (obj[i] < 0) obj[i] = rk[i];
+  }
+  __syncthreads();
+
+  // e. the catalog, then the objects ordered by peak pixel
+  for (int o = 0; o < nobj; ++o) {
+    double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // npix, sum v, sum v c, sum v r, sum c, sum r
+    double pk = -INFINITY;
+    int pi = 0x7fffffff;
+    for (int i = tid; i < n; i += DT) {
+      if (obj[i] != o) continue;
+      const int p = pix[i];
+      const double v = vf[p], c = p - (p / W) * W, r = p / W;
+      a[0] += 1.0;
+      a[1] += v;
+      a[2] += v * c;
+      a[3] += v * r;
+      a[4] += c;
+      a[5] += r;
+      if (Dp[i] > pk) { pk = Dp[i]; pi = i; }
+    }
+    blk_sum<6>(a, s_red);
+    blk_argmax(pk, pi, s_red + 24, s_i);
+    if (tid == 0) {
+      const long sl = J.slot + o;
+      o_npix[sl] = (int)a[0];
+      o_peakpix[sl] = pix[pi];
+      o_peak[sl] = pk;
+      o_flux[sl] = a[1];
+      o_x[sl] = a[1] > 0.0 ? a[2] / a[1] : a[4] / a[0];
+      o_y[sl] = a[1] > 0.0 ? a[3] / a[1] : a[5] / a[0];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const long b = J.slot;
+    for (int o = 1; o < nobj; ++o) {                 // insertion sort of the slots by peak pixel
+      const int kp = o_peakpix[b + o], kn = o_npix[b + o];
+      const double k1 = o_peak[b + o], k2 = o_flux[b + o], k3 = o_x[b + o], k4 = o_y[b + o];
+      int q = o;
+      while (q > 0 && o_peakpix[b + q - 1] > kp) {
+        o_peakpix[b + q] = o_peakpix[b + q - 1];
+        o_npix[b + q] = o_npix[b + q - 1];
+        o_peak[b + q] = o_peak[b + q - 1];
+        o_flux[b + q] = o_flux[b + q - 1];
+        o_x[b + q] = o_x[b + q - 1];
+        o_y[b + q] = o_y[b + q - 1];
+        --q;
+      }
+      o_peakpix[b + q] = kp;
+      o_npix[b + q] = kn;
+      o_peak[b + q] = k1;
+      o_flux[b + q] = k2;
+      o_x[b + q] = k3;
+      o_y[b + q] = k4;
+    }
+    nobj_out[blockIdx.x] = nobj;
+  }
+}
+
+inline unsigned nblk(long total) { return (unsigned)((total + DT - 1) / DT); }
+
+// device bytes one H x W field can need in a launch: deblend scratch and catalog slots sized as if every pixel lay in
+// a component
+long field_bytes(long H, long W, long ny, long nx, int minarea, bool maps) {
+  const long HW = H * W, capn = HW / minarea + 1;
+  long b = HW * (8 + 8 + 8 + 4 * 7);                          // data v D | par lab area cmin cmax rmax lidx
+  if (maps) b += HW * (8 + 8 + 4);                            // back rms labels
+  b += H * nx * 4 * 8 + ny * nx * 6 * 8;                      // row splines, mesh grids
+  b += capn * 5 * 4;                                          // component table
+  b += HW * (8 + 6 * 4) + capn * ((2 + OBJ_D) * 8 + 3 * 4);   // deblend scratch
+  b += capn * ((long)sizeof(DbJob) + 4 * 4 + 4 * 8);          // jobs and catalog slots
+  return b;
+}
+}  // namespace
+
+int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
+                 int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
+                 int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
+                 int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
+                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s) {
+  if (!fields_h || M < 0 || H < 1 || W < 1 || H > DIM_MAX || W > DIM_MAX || (long)H * W > 0x7fffffffL ||
+      !std::isfinite(thresh) || !std::isfinite(cont) || minarea < 1 || nthresh < 1 || nthresh > 1024 ||
+      back_size < 1 || back_size > 64 || back_filter < 1 || back_filter > MF_MAX || (back_filter & 1) == 0 || cap < 0 ||
+      !n_out || !offsets_h || !globalrms_h || workspace_bytes < 0 ||
+      (cap > 0 && (!field_h || !parent_h || !npix_h || !peak_h || !flux_h || !x_h || !y_h))) {
+    set_error("scene_detect: bad arguments");
+    return E_INVALID;
+  }
+  if (kernel_h && (kh < 1 || kw < 1 || kh > KMAX || kw > KMAX || (kh & 1) == 0 || (kw & 1) == 0)) {
+    set_error("scene_detect: the filter kernel must have odd sizes of 1 .. %d (got %d x %d)", KMAX, kh, kw);
+    return E_INVALID;
+  }
+  // the filter taps divided by sum |k|; the default is the pixel-integrated circular Gaussian of DESIGN 7e
+  std::vector<double> kn;
+  if (kernel_h) {
+    kn.assign(kernel_h, kernel_h + (size_t)kh * kw);
+  } else {
+    kh = kw = 7;
+    const double sq = std::sqrt(2.0) * 1.27627;
+    double g[7];
+    for (int a = 0; a < 7; ++a) g[a] = std::erf((a - 3 + 0.5) / sq) - std::erf((a - 3 - 0.5) / sq);
+    kn.resize(49);
+    for (int a = 0; a < 7; ++a)
+      for (int b = 0; b < 7; ++b) kn[a * 7 + b] = g[a] * g[b];
+  }
+  double ksum = 0.0;
+  for (double k : kn) ksum += std::fabs(k);
+  if (!(ksum > 0.0) || !std::isfinite(ksum)) {
+    set_error("scene_detect: the filter kernel has no finite non-zero tap");
+    return E_INVALID;
+  }
+  for (double& k : kn) k /= ksum;
+
+  const int ny = (H + back_size - 1) / back_size, nx = (W + back_size - 1) / back_size;
+  const bool maps = back_h || rms_h || D_h || labels_h;
+  const long cap_ws = workspace_bytes > 0 ? (long)workspace_bytes : (4L << 30);
+  const long per_field = field_bytes(H, W, ny, nx, minarea, maps);
+  if (M > 0 && per_field > cap_ws) {
+    set_error("scene_detect: one %d x %d field needs up to %ld bytes of device workspace, above the cap of %ld bytes per "
+              "launch", H, W, per_field, cap_ws);
+    return E_INVALID;
+  }
+  const long HW = (long)H * W;
+  const long ccap = HW / minarea + 1;
+  const int chunk = M > 0 ? (int)std::min<long>({(long)M, (long)CHUNK_MAX, std::max<long>(1, cap_ws / per_field)}) : 0;
+
+  std::vector<double> cco((size_t)std::max(ny, nx) + 1);
+  cco[0] = 0.25;
+  for (size_t i = 1; i < cco.size(); ++i) cco[i] = 1.0 / (4.0 - cco[i - 1]);
+
+  std::vector<int32_t> c_field, c_parent, c_npix;      // the catalog of all fields
+  std::vector<double> c_peak, c_flux, c_x, c_y;
+  offsets_h[0] = 0;
+
+  double *data = nullptr, *v = nullptr, *D = nullptr, *mb = nullptr, *mr = nullptr, *fbk = nullptr, *frm = nullptr;
+  double *d2b = nullptr, *d2r = nullptr, *gb = nullptr, *gb2 = nullptr, *gr = nullptr, *gr2 = nullptr, *grms = nullptr;
+  double *kdev = nullptr, *cdev = nullptr, *back = nullptr, *rms = nullptr, *dscr = nullptr;
+  int *par = nullptr, *lab = nullptr, *area = nullptr, *cmin = nullptr, *cmax = nullptr, *rmax = nullptr, *lidx = nullptr;
+  int *table = nullptr, *ncomp = nullptr, *labout = nullptr, *iscr = nullptr, *o_npix = nullptr, *o_pp = nullptr;
+  int* nobj = nullptr;
+  double *o_peak = nullptr, *o_flux = nullptr, *o_x = nullptr, *o_y = nullptr;
+  DbJob* djobs = nullptr;
+  int st = OK;
+  auto free_deblend = [&]() {
+    for (void* p : {(void*)dscr, (void*)iscr, (void*)o_npix, (void*)o_pp, (void*)nobj, (void*)o_peak, (void*)o_flux,
+                    (void*)o_x, (void*)o_y, (void*)djobs})
+      (void)hipFree(p);
+    dscr = nullptr; iscr = nullptr; o_npix = nullptr; o_pp = nullptr; nobj = nullptr; o_peak = nullptr;
+    o_flux = nullptr; o_x = nullptr; o_y = nullptr; djobs = nullptr;
+  };
+  auto cleanup = [&]() {
+    for (void* p : {(void*)data, (void*)v, (void*)D, (void*)mb, (void*)mr, (void*)fbk, (void*)frm, (void*)d2b,
+                    (void*)d2r, (void*)gb, (void*)gb2, (void*)gr, (void*)gr2, (void*)grms, (void*)kdev, (void*)cdev,
+                    (void*)back, (void*)rms, (void*)par, (void*)lab, (void*)area, (void*)cmin, (void*)cmax,
+                    (void*)rmax, (void*)lidx, (void*)table, (void*)ncomp, (void*)labout})
+      (void)hipFree(p);
+    free_deblend();
+  };
+#define DT_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
+#define DT_ALLOC(ptr, count) DT_HIP(hipMalloc((void**)&(ptr), std::max<size_t>(1, (size_t)(count)) * sizeof(*(ptr))))
+  if (chunk > 0) {
+    const long px = (long)chunk * HW, grid = (long)chunk * ny * nx, rows = (long)chunk * H * nx;
+    DT_ALLOC(data, px); DT_ALLOC(v, px); DT_ALLOC(D, px);
+    DT_ALLOC(par, px); DT_ALLOC(lab, px); DT_ALLOC(area, px); DT_ALLOC(cmin, px); DT_ALLOC(cmax, px);
+    DT_ALLOC(rmax, px); DT_ALLOC(lidx, px);
+    DT_ALLOC(mb, grid); DT_ALLOC(mr, grid); DT_ALLOC(fbk, grid); DT_ALLOC(frm, grid); DT_ALLOC(d2b, grid);
+    DT_ALLOC(d2r, grid);
+    DT_ALLOC(gb, rows); DT_ALLOC(gb2, rows); DT_ALLOC(gr, rows); DT_ALLOC(gr2, rows);
+    DT_ALLOC(grms, chunk); DT_ALLOC(kdev, kn.size()); DT_ALLOC(cdev, cco.size());
+    DT_ALLOC(table, (long)chunk * ccap * 5); DT_ALLOC(ncomp, chunk);
+    if (back_h) DT_ALLOC(back, px);
+    if (rms_h) DT_ALLOC(rms, px);
+    if (labels_h) DT_ALLOC(labout, px);
+    DT_HIP(hipMemcpyAsync(kdev, kn.data(), kn.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    DT_HIP(hipMemcpyAsync(cdev, cco.data(), cco.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  }
+  std::vector<int> h_ncomp((size_t)std::max(chunk, 1));
+  std::vector<int> h_tab;
+  for (int f0 = 0; f0 < M; f0 += chunk) {
+    const int m = std::min(chunk, M - f0);
+    const long px = (long)m * HW;
+    DT_HIP(hipMemcpyAsync(data, fields_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(bkg_mesh_kernel, dim3((unsigned)((long)m * ny * nx)), dim3(DT), 0, s, data, H, W, back_size, ny,
+                       nx, mb, mr);
+    DT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkg_grid_kernel, dim3((unsigned)m), dim3(DT), 0, s, mb, mr, ny, nx, back_filter, cdev, fbk, frm,
+                       d2b, d2r, grms);
+    DT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkg_row_kernel, dim3(nblk((long)m * H)), dim3(DT), 0, s, fbk, frm, d2b, d2r, m, H, ny, nx,
+                       back_size, rms ? 1 : 0, cdev, gb, gb2, gr, gr2);
+    DT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkg_pixel_kernel, dim3(nblk(px)), dim3(DT), 0, s, data, px, W, nx, back_size, gb, gb2, gr, gr2, v,
+                       back, rms);
+    DT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(filter_kernel, dim3((unsigned)((W + FT - 1) / FT), (unsigned)((H + FT - 1) / FT), (unsigned)m),
+                       dim3(DT), 0, s, v, H, W, kdev, kh, kw, grms, thresh, D, par);
+    DT_HIP(hipGetLastError());
+    DT_HIP(hipMemsetAsync(area, 0, (size_t)px * sizeof(int), s));
+    DT_HIP(hipMemsetAsync(cmin, 0x7f, (size_t)px * sizeof(int), s));
+    DT_HIP(hipMemsetAsync(cmax, 0xff, (size_t)px * sizeof(int), s));
+    DT_HIP(hipMemsetAsync(rmax, 0xff, (size_t)px * sizeof(int), s));
+    hipLaunchKernelGGL(cc_merge_kernel, dim3(nblk(px)), dim3(DT), 0, s, par, px, W, HW);
+    DT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(nblk(px)), dim3(DT), 0, s, par, px, W, HW, lab, area, cmin, cmax, rmax);
+    DT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cc_compact_kernel, dim3((unsigned)m), dim3(DT), 0, s, lab, area, cmin, cmax, rmax, HW, minarea,
+                       ccap, table, ncomp);
+    DT_HIP(hipGetLastError());
+    if (labout) {
+      hipLaunchKernelGGL(cc_labels_kernel, dim3(nblk(px)), dim3(DT), 0, s, lab, area, px, HW, minarea, labout);
+      DT_HIP(hipGetLastError());
+    }
+    DT_HIP(hipMemcpyAsync(globalrms_h + f0, grms, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    DT_HIP(hipMemcpyAsync(h_ncomp.data(), ncomp, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (back_h) DT_HIP(hipMemcpyAsync(back_h + (size_t)f0 * HW, back, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+    if (rms_h) DT_HIP(hipMemcpyAsync(rms_h + (size_t)f0 * HW, rms, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+    if (D_h) DT_HIP(hipMemcpyAsync(D_h + (size_t)f0 * HW, D, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+    if (labels_h) DT_HIP(hipMemcpyAsync(labels_h + (size_t)f0 * HW, labout, (size_t)px * 4, hipMemcpyDeviceToHost, s));
+    DT_HIP(hipStreamSynchronize(s));
+    // phase two: every component's scratch and catalog slots
+    std::vector<DbJob> jobs;
+    std::vector<int> jfield;
+    long dws = 0, iws = 0, slots = 0;
+    std::vector<long> tab_off((size_t)m + 1, 0);          // every field's component table, one synchronisation
+    for (int f = 0; f < m; ++f) tab_off[f + 1] = tab_off[f] + h_ncomp[f];
+    h_tab.resize((size_t)std::max(tab_off[m], 1L) * 5);
+    for (int f = 0; f < m; ++f)
+      if (h_ncomp[f] > 0)
+        DT_HIP(hipMemcpyAsync(h_tab.data() + tab_off[f] * 5, table + (long)f * ccap * 5, (size_t)h_ncomp[f] * 5 * sizeof(int),
+                              hipMemcpyDeviceToHost, s));
+    DT_HIP(hipStreamSynchronize(s));
+    for (int f = 0; f < m; ++f) {
+      const int nc = h_ncomp[f];
+      for (int c = 0; c < nc; ++c) {
+        const int* row = &h_tab[(size_t)(tab_off[f] + c) * 5];
+        DbJob j{};
+        j.fbase = (long)f * HW;
+        j.root = row[0];
+        j.n = row[1];
+        j.c0 = row[2];
+        j.c1 = row[3];
+        j.r1 = row[4];
+        j.cap = std::max(1, j.n / minarea);
+        j.T = thresh * globalrms_h[f0 + f];
+        j.dws = dws;
+        j.iws = iws;
+        j.slot = slots;
+        dws += (long)j.n + (long)j.cap * (2 + OBJ_D);
+        iws += 6L * j.n + 3L * j.cap;
+        slots += j.cap;
+        jobs.push_back(j);
+        jfield.push_back(f0 + f);
+      }
+    }
+    const long nj = (long)jobs.size();
+    std::vector<int> h_nobj((size_t)nj), h_npix((size_t)slots);
+    std::vector<double> h_peak((size_t)slots), h_flux((size_t)slots), h_x((size_t)slots), h_y((size_t)slots);
+    if (nj > 0) {
+      DT_ALLOC(djobs, nj); DT_ALLOC(dscr, dws); DT_ALLOC(iscr, iws); DT_ALLOC(nobj, nj);
+      DT_ALLOC(o_npix, slots); DT_ALLOC(o_pp, slots); DT_ALLOC(o_peak, slots); DT_ALLOC(o_flux, slots);
+      DT_ALLOC(o_x, slots); DT_ALLOC(o_y, slots);
+      DT_HIP(hipMemcpyAsync(djobs, jobs.data(), (size_t)nj * sizeof(DbJob), hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(deblend_kernel, dim3((unsigned)nj), dim3(DT), 0, s, djobs, W, D, v, lab, lidx, dscr, iscr,
+                         nthresh, minarea, cont, o_npix, o_pp, o_peak, o_flux, o_x, o_y, nobj);
+      DT_HIP(hipGetLastError());
+      DT_HIP(hipMemcpyAsync(h_nobj.data(), nobj, (size_t)nj * 4, hipMemcpyDeviceToHost, s));
+      DT_HIP(hipMemcpyAsync(h_npix.data(), o_npix, (size_t)slots * 4, hipMemcpyDeviceToHost, s));
+      DT_HIP(hipMemcpyAsync(h_peak.data(), o_peak, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DT_HIP(hipMemcpyAsync(h_flux.data(), o_flux, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DT_HIP(hipMemcpyAsync(h_x.data(), o_x, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DT_HIP(hipMemcpyAsync(h_y.data(), o_y, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DT_HIP(hipStreamSynchronize(s));
+      free_deblend();
+    }
+    long ji = 0;
+    for (int f = 0; f < m; ++f) {
+      for (; ji < nj && jfield[ji] == f0 + f; ++ji) {
+        const DbJob& j = jobs[ji];
+        for (int o = 0; o < h_nobj[ji]; ++o) {
+          const long sl = j.slot + o;
+          c_field.push_back(f0 + f);
+          c_parent.push_back(j.root);
+          c_npix.push_back(h_npix[sl]);
+          c_peak.push_back(h_peak[sl]);
+          c_flux.push_back(h_flux[sl]);
+          c_x.push_back(h_x[sl]);
+          c_y.push_back(h_y[sl]);
+        }
+      }
+      offsets_h[f0 + f + 1] = (int64_t)c_field.size();
+    }
+  }
+  cleanup();
+#undef DT_ALLOC
+#undef DT_HIP
+  const size_t n = c_field.size();
+  *n_out = (int64_t)n;
+  if ((int64_t)n <= cap && n > 0) {
+    std::copy(c_field.begin(), c_field.end(), field_h);
+    std::copy(c_parent.begin(), c_parent.end(), parent_h);
+    std::copy(c_npix.begin(), c_npix.end(), npix_h);
+    std::copy(c_peak.begin(), c_peak.end(), peak_h);
+    std::copy(c_flux.begin(), c_flux.end(), flux_h);
+    std::copy(c_x.begin(), c_x.end(), x_h);
+    std::copy(c_y.begin(), c_y.end(), y_h);
+  }
+  return OK;
+}
+
+}  // namespace dv

@@ -3504,6 +3504,17 @@ int dv_scene_fit_shifts(dv_ctx* c, const double* field_r, int32_t F, const doubl
                           c->stream);
 }
 
+int dv_scene_detect(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, const dv_detect_params* p,
+                    int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms, int32_t* field, int32_t* parent,
+                    int32_t* npix, double* peak, double* flux, double* x, double* y, double* back, double* rms,
+                    double* D, int32_t* labels) {
+  if (!c || !p) return DV_E_INVALID;
+  DV_HIP(hipSetDevice(c->device));
+  return scene_detect(fields, M, H, W, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
+                      p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, offsets, globalrms, field, parent, npix,
+                      peak, flux, x, y, back, rms, D, labels, c->stream);
+}
+
 int dv_ctx_allreduce_host(dv_ctx* c, float* buf, int32_t n) {
   if (!c || !buf || n < 0 || n > 4096) return DV_E_INVALID;
   if (!c->comm || n == 0) return DV_OK;

@@ -6,7 +6,7 @@ Same class and method names as the reference.  What runs on the GPU: cutout extr
 field-sized image per object and band) and the sub-pixel position fit (deblend_cutout/optimization.py, one batched engine
 call for all galaxies instead of a scipy.optimize run per galaxy): `optimise_positions()` fits the rows of a deblended
 recarray and writes their `shifts`.  `deblend_field(optimise_positions=True)` still raises: run `deblend_field` and then
-`optimise_positions()`.  Not provided: source detection (`sep`, detect/detection.py).
+`optimise_positions()`.  Source detection: debvader_amd.detect.detection (SExtractor's method on the GPU, not sep).
 """
 import numpy as np
 import pandas as pd

@@ -1,0 +1,57 @@
+"""Source detection (reference: src/debvader/detect/detection.py).
+
+The reference runs sep (SExtractor's library) on band 2 (r) of the field.  This engine has no sep: the same method -
+SExtractor's published algorithm (Bertin & Arnouts 1996) with the rules of DESIGN.md section 7e - runs on the GPU
+(Context.scene_detect, csrc/detect.hip), float64, with the reference's settings (thresh 1.5 x globalrms, minarea 4,
+64 deblending levels, contrast 1e-5, a 7 x 7 Gaussian matched filter, 64-pixel background meshes).  It is not sep, and
+its catalogue is not claimed to equal sep's: INTEGRATION.md lists the known differences.  There is no CPU fallback.
+"""
+import numpy as np
+
+from debvader_amd import engine as E
+
+R_BAND = 2        # the reference detects on field_image[0, :, :, 2]
+
+
+def _distances(x, y, field_size):
+    """the reference's (row, column) distances to the centre, rounded half to even as np.round does"""
+    if len(x) == 0:
+        return np.array([])
+    h = -int(field_size / 2)
+    return np.array([(np.round(h + yy), np.round(h + xx)) for xx, yy in zip(x, y)])
+
+
+def _bands_r(images):
+    a = np.asarray(images)
+    if a.ndim != 4:
+        raise ValueError(f"expected fields (N, F, F, bands), got {a.shape}")
+    if a.shape[3] <= R_BAND:
+        raise ValueError(f"detection uses band {R_BAND} (r); these fields have {a.shape[3]} band(s)")
+    return a[:, :, :, R_BAND]
+
+
+def detect_objects_batch(field_images, ctx=None, **kw):
+    """detect_objects for every field of (N, F, F, bands) in one engine call; returns a list of N arrays as
+    detect_objects returns them.  kw: the detector's settings (Context.scene_detect)."""
+    r_band = _bands_r(field_images)
+    ctx = ctx or E.default_context()
+    r = ctx.scene_detect(r_band, **kw)
+    F = r_band.shape[1]
+    off = r["offsets"]
+    return [_distances(r["x"][off[i]:off[i + 1]], r["y"][off[i]:off[i + 1]], F) for i in range(r_band.shape[0])]
+
+
+def detect_objects(field_image, ctx=None, **kw):
+    """
+    Detect the objects in the field_image image using the SExtractor detection algorithm (on the GPU).
+    field_image: (1, F, F, bands); returns the (row, column) distances of the objects to the centre of the field,
+    np.round(-int(F / 2) + barycentre), as an (n, 2) array, or np.array([]) when nothing is found.
+    """
+    field_image = np.asarray(field_image)
+    if field_image.ndim != 4 or field_image.shape[0] < 1:
+        raise ValueError(f"expected a field (1, F, F, bands), got {field_image.shape}")
+    field_size = field_image.shape[1]
+    r_band = _bands_r(field_image[:1])
+    ctx = ctx or E.default_context()
+    r = ctx.scene_detect(r_band, **kw)
+    return _distances(r["x"], r["y"], field_size)

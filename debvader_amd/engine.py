@@ -103,6 +103,28 @@ def _i32_rows(a, what: str) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32).reshape(-1, 2)
 
 
+def check_detect_args(fields_r, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
+                      workspace_bytes=0) -> np.ndarray:
+    """Context.scene_detect's argument checks (before any GPU work); returns the fields as float64 (M, H, W)."""
+    f = np.ascontiguousarray(fields_r, dtype=np.float64)
+    if f.ndim != 3 or f.shape[1] < 1 or f.shape[2] < 1:
+        raise ValueError(f"expected fields (M, H, W), got {f.shape}")
+    if not np.isfinite(f).all():
+        raise ValueError("the fields must be finite")
+    if not (np.isfinite(thresh) and np.isfinite(cont)) or int(minarea) < 1 or not 1 <= int(nthresh) <= 1024:
+        raise ValueError(f"thresh and cont must be finite, minarea >= 1 and nthresh 1 .. 1024 "
+                         f"(got {thresh}, {cont}, {minarea}, {nthresh})")
+    if not 1 <= int(back_size) <= 64 or int(back_filter) not in (1, 3, 5, 7) or int(workspace_bytes) < 0:
+        raise ValueError(f"back_size must be 1 .. 64 and back_filter odd 1 .. 7 (got {back_size}, {back_filter})")
+    if filter_kernel is not None:
+        k = np.asarray(filter_kernel, dtype=np.float64)
+        if k.ndim != 2 or k.shape[0] % 2 == 0 or k.shape[1] % 2 == 0 or max(k.shape) > 15 \
+                or not np.isfinite(k).all() or not np.abs(k).sum() > 0:
+            raise ValueError(f"filter_kernel must be a finite, non-zero, odd-sized 2-d array up to 15 x 15, got shape "
+                             f"{k.shape}")
+    return f
+
+
 class _Lease:
     """Owner token of one hand-out of a pool block.  The array the caller receives is built on this object
     (__array_interface__), so numpy makes it the END of the `base` chain of that array and of everything derived from it -
@@ -378,6 +400,59 @@ class Context:
                                           out.ctypes.data_as(dp), obj.ctypes.data_as(dp), iters.ctypes.data_as(ip),
                                           status.ctypes.data_as(ip)))
         return dict(shifts=out, objective=obj, iters=iters, status=status)
+
+    CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
+
+    def scene_detect(self, fields_r, thresh: float = 1.5, minarea: int = 4, nthresh: int = 64, cont: float = 1e-5,
+                     filter_kernel=None, back_size: int = 64, back_filter: int = 3, return_maps: bool = False,
+                     workspace_bytes: int = 0) -> Dict[str, np.ndarray]:
+        """Source detection on one band of M fields (detect/detection.py's sep call, on the GPU).
+
+        fields_r (M, H, W).  SExtractor's method, float64: background meshes of back_size px with a back_filter median
+        filter, D = the background-subtracted field correlated with filter_kernel / sum|k| (None: the 7 x 7
+        pixel-integrated Gaussian), components of D > thresh * globalrms with >= minarea pixels, nthresh-level
+        deblending with contrast cont.  Returns the catalog {field, parent, npix, peak, flux, x (column), y (row)}, one row
+        per object ordered by field, component and peak pixel, plus offsets (M + 1: the rows of field f are
+        offsets[f]:offsets[f + 1]) and globalrms (M,); with return_maps also back, rms, D (M, H, W) and labels (M, H, W)
+        (the component's parent, -1 outside kept components).  workspace_bytes caps the device workspace per launch
+        (0: 4 GiB); a field that needs more is refused."""
+        f = check_detect_args(fields_r, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
+                              workspace_bytes)
+        kern, kptr, kh, kw = None, None, 0, 0
+        if filter_kernel is not None:
+            kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
+            kptr, (kh, kw) = kern.ctypes.data_as(C.POINTER(C.c_double)), kern.shape
+        M, H, W = f.shape
+        params = _lib.DvDetectParams(float(thresh), float(cont), int(minarea), int(nthresh), int(back_size),
+                                     int(back_filter), kptr, kh, kw, int(workspace_bytes))
+        offsets = np.zeros(M + 1, np.int64)
+        grms = np.zeros(M, np.float64)
+        maps = {}
+        if return_maps:
+            maps = dict(back=np.empty((M, H, W)), rms=np.empty((M, H, W)), D=np.empty((M, H, W)),
+                        labels=np.empty((M, H, W), np.int32))
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+
+        def _ptr(a, t):
+            return None if a is None else a.ctypes.data_as(t)
+
+        # one call unless the catalog exceeds one object per 1024 pixels (then a second call with the exact size)
+        cap = max(4096, 64 * M, M * H * W // 1024)
+        while True:                                   # the catalog's size is known after the call: grow once if needed
+            cat = {k: np.empty(cap, np.int32 if k in ("field", "parent", "npix") else np.float64)
+                   for k in self.CATALOG_KEYS}
+            n = C.c_int64()
+            check(lib.dv_scene_detect(self._h, f.ctypes.data_as(dp), M, H, W, C.byref(params), cap, C.byref(n),
+                                      offsets.ctypes.data_as(C.POINTER(C.c_int64)), grms.ctypes.data_as(dp),
+                                      *[_ptr(cat[k], ip if cat[k].dtype == np.int32 else dp) for k in self.CATALOG_KEYS],
+                                      _ptr(maps.get("back"), dp), _ptr(maps.get("rms"), dp), _ptr(maps.get("D"), dp),
+                                      _ptr(maps.get("labels"), ip)))
+            if n.value <= cap:
+                break
+            cap = n.value
+        out = {k: v[:n.value].copy() for k, v in cat.items()}
+        out.update(offsets=offsets, globalrms=grms, **maps)
+        return out
 
     def close(self):
         """Destroys the engines created on this context, then the context.  Idempotent."""

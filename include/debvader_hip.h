@@ -296,6 +296,37 @@ int dv_scene_composite(dv_ctx* ctx, double* field, int32_t F, int32_t nb, const 
 int dv_scene_fit_shifts(dv_ctx* ctx, const double* field_r, int32_t F, const double* stamps_r, int32_t N, int32_t cs,
                         const double* dist, double bound, int32_t max_iter, double* shifts_inout, double* objective,
                         int32_t* iters, int32_t* status);
+/* dv_scene_detect: source detection (reference: detect/detection.py, which runs sep on band 2) on M fields of one band,
+ * fields [M][H][W] float64.  SExtractor's method (Bertin & Arnouts 1996) with the rules of DESIGN.md section 7e, float64
+ * throughout: sigma-clipped mesh background (exact medians), median-filtered meshes, natural-cubic-spline interpolation,
+ * D = correlation of data - back with kernel / sum|kernel|, 8-connected components of D > thresh * globalrms with at least
+ * minarea pixels, nthresh-level deblending with contrast cont and the argmax pixel assignment.  Not sep, and not claimed
+ * to match it bit for bit.
+ * Out: globalrms [M]; offsets [M + 1] (the objects of field f are catalog rows offsets[f] .. offsets[f + 1]); *n_out =
+ * the number of objects; the catalog rows field, parent (raster index of the component's first pixel), npix, peak
+ * (max D), flux (sum of data - back), x (column) and y (row) barycentres weighted by data - back, ordered by field, then
+ * component, then peak pixel.  The rows are written only when *n_out <= cap: call again with cap >= *n_out otherwise
+ * (the result is deterministic).  back / rms / D / labels [M][H][W] (each optional, NULL: not returned) are the maps of
+ * DESIGN 7e, labels = the component's parent for pixels of kept components, -1 elsewhere.
+ * Limits: back_size 1 .. 64, back_filter odd 1 .. 7, kernel odd kh x kw up to 15 x 15 (NULL: the default 7 x 7
+ * pixel-integrated Gaussian, sigma 1.27627), H and W up to 2^19 with H * W < 2^31.  Fields are processed in chunks whose
+ * device workspace stays under workspace_bytes (0: 4 GiB); a single field that needs more is refused (DV_E_INVALID).
+ * Bit-reproducible, and the same for a field whatever the batch it is in. */
+typedef struct dv_detect_params {
+  double thresh;           /* detection threshold in units of globalrms (1.5) */
+  double cont;             /* deblending contrast (1e-5) */
+  int32_t minarea;         /* minimum pixels of a component and of a deblending node (4) */
+  int32_t nthresh;         /* deblending levels (64) */
+  int32_t back_size;       /* background mesh size (64) */
+  int32_t back_filter;     /* median filter over the meshes (3) */
+  const double* kernel;    /* filter taps [kh][kw] or NULL */
+  int32_t kh, kw;
+  int64_t workspace_bytes; /* device workspace cap per launch, 0: the default */
+} dv_detect_params;
+int dv_scene_detect(dv_ctx* ctx, const double* fields, int32_t M, int32_t H, int32_t W, const dv_detect_params* params,
+                    int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms, int32_t* field, int32_t* parent,
+                    int32_t* npix, double* peak, double* flux, double* x, double* y, double* back, double* rms,
+                    double* D, int32_t* labels);
 
 /* ---- introspection for tests and bench ----------------------------------------------------- */
 /* copy a named activation of the last step to host: "t","z","kl","eps","loc","scale","head_pre" */
