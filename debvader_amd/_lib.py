@@ -131,10 +131,17 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p]),
     "dv_infer_cutouts_composite": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64,
                                              C.c_uint64, _d, _d, _d, _d]),
+    "dv_infer_fields": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i64, C.c_int64, C.c_uint64, _f, _f, _f, _f, _f]),
+    "dv_infer_fields_keep": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i64, C.c_int64, C.c_uint64, _f, _f, _f, _f,
+                                       _f, _d]),
+    "dv_infer_fields_composite": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
+                                            _d, _d, _d, _d]),
     "dv_scene_extract": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _d]),
     "dv_scene_composite": (C.c_int, [_p, _d, C.c_int32, C.c_int32, _d, _d, C.c_int32, C.c_int32, C.c_double]),
     "dv_scene_fit_shifts": (C.c_int, [_p, _d, C.c_int32, _d, C.c_int32, C.c_int32, _d, C.c_double, C.c_int32, _d, _d,
                                       _i32, _i32]),
+    "dv_scene_fit_shifts_fields": (C.c_int, [_p, _d, C.c_int32, C.c_int32, _d, _i64, C.c_int64, C.c_int32, _d, C.c_double,
+                                             C.c_int32, _d, _d, _i32, _i32]),
     "dv_scene_detect": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams), C.c_int64, _i64,
                                   _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d, _d, _d, _d, _i32]),
     "dv_infer_mc": (C.c_int, [_p, _f, C.c_int64, C.c_int32, C.c_uint64, _f, _f]),

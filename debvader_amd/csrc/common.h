@@ -156,15 +156,19 @@ void gconv2_tile_geometry(const GConv2Params& p, int* bm, int* wgm, long* mtiles
 void debug_set_gconv2_tile(int code);
 
 // Scene compositing (scene.hip): host float64 buffers in, host float64 buffers out
-// device-resident gather + float32 cast (dv_infer_cutouts): starts_dev points at the first cutout of the chunk
+// device-resident gather + float32 cast (dv_infer_cutouts): starts_dev points at the first cutout of the chunk.
+// Many fields (dv_infer_fields*): field_dev is field f0 of a stack of fields and sfield_dev[i] the field of cutout i.
 int launch_scene_extract_f32(const double* field_dev, int F, int nb, const int* starts_dev, long count, int cs,
-                             float* out_dev, hipStream_t s);
+                             float* out_dev, hipStream_t s, const int* sfield_dev = nullptr, int f0 = 0);
 // compositing of one inference chunk on the device (dv_infer_cutouts_composite): mean / stddev / residual fields += the
-// chunk's stamps at integer placements, in object order; per-stamp centre MSE against the field's own cutout
+// chunk's stamps at integer placements, in object order; per-stamp centre MSE against the field's own cutout.
+// Many fields: the result pointers are field f0 of a stack, fptr_dev [M + 1] the global stamp number where each field's
+// objects begin, the chunk holds stamps obase .. obase + n of fields fy0 .. fy0 + nfields - 1.
 int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, int F, int nb, const float* loc,
-                                 const float* scale, const int* places_dev, int n, int cs, hipStream_t s);
+                                 const float* scale, const int* places_dev, int n, int cs, hipStream_t s,
+                                 const int* fptr_dev = nullptr, int f0 = 0, int fy0 = 0, int nfields = 1, long obase = 0);
 int launch_scene_center_mse(const double* field_dev, int F, int nb, const int* starts_dev, const float* loc, int n, int cs,
-                            double* out_dev, hipStream_t s);
+                            double* out_dev, hipStream_t s, const int* sfield_dev = nullptr, int f0 = 0);
 int scene_extract(const double* field_h, int F, int nb, const int32_t* starts_h, int N, int cs, double* out_h,
                   hipStream_t s);
 int scene_composite(double* field_h, int F, int nb, const double* stamps_h, const double* pos_h, int N, int cs,
@@ -173,6 +177,11 @@ int scene_composite(double* field_h, int F, int nb, const double* stamps_h, cons
 int scene_fit_shifts(const double* field_h, int F, const double* stamps_h, int N, int cs, const double* dist_h,
                      double bound, int max_iter, double* shifts_h, double* objective_h, int32_t* iters_h,
                      int32_t* status_h, hipStream_t s);
+// the same for M fields [M][F][F]: galaxies field_ptr[m] .. field_ptr[m + 1] are fitted against field m.  Fields are
+// uploaded in groups of at most budget_bytes (a single field that needs more is refused).
+int scene_fit_shifts_fields(const double* fields_h, int M, int F, const double* stamps_h, const int64_t* field_ptr, int N,
+                            int cs, const double* dist_h, double bound, int max_iter, double* shifts_h, double* objective_h,
+                            int32_t* iters_h, int32_t* status_h, size_t budget_bytes, hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

@@ -2922,12 +2922,14 @@ static void host_copy(float* dst, const void* src, size_t n, bool src_f64, int t
 // `threads` host threads: cs row copies of cs * nb doubles per window (what numpy's slice assignment does in
 // extract/extraction.py:26-32).  Used for the float64 cutout_images the reference's recarray carries: the windows are exact
 // copies of host data, so they are assembled on the host beside the GPU's forward passes and never cross the host link.
+// sfield (may be null: one field): the field of a stack [M][F][F][nb] each window is cut from.
 static void host_gather_cutouts(double* out, const double* field, int F, int nb, const int32_t* starts, int64_t n, int cs,
-                                int threads) {
+                                int threads, const int32_t* sfield = nullptr) {
   auto work = [=](int64_t lo, int64_t hi) {
     const size_t row = (size_t)cs * nb;
     for (int64_t i = lo; i < hi; ++i) {
-      const double* src = field + ((size_t)starts[2 * i] * F + starts[2 * i + 1]) * nb;
+      const double* src = field + (sfield ? (size_t)sfield[i] * F * F * nb : (size_t)0) +
+                          ((size_t)starts[2 * i] * F + starts[2 * i + 1]) * nb;
       double* dst = out + (size_t)i * cs * row;
       for (int r = 0; r < cs; ++r) memcpy(dst + r * row, src + (size_t)r * F * nb, row * sizeof(double));
     }
@@ -2952,6 +2954,7 @@ struct CutoutKeep {
   const double* field;   // host, [F][F][nb]
   const int32_t* starts; // host, [N][2]
   double* out;           // host, [N][cs][cs][nb]
+  const int32_t* sfield = nullptr;   // host, [N]: the field of each window when `field` is a stack [M][F][F][nb]
 };
 
 // input of the pipeline when the stamps are cutouts of a field that already sits in HBM (dv_infer_cutouts)
@@ -2959,7 +2962,23 @@ struct CutoutSrc {
   const double* field;   // device, [F][F][nb]
   const int* starts;     // device, [N][2]
   int F, nb, cs;
+  // many fields (dv_infer_fields*): `field` is field f0 of a stack of resident fields, and this call runs stamps
+  // row0 .. row0 + N of a longer global list - starts, places, mse and the result arrays point at stamp row0, Philox rows
+  // and fptr count from stamp 0 - in chunks of `chunk` stamps (the split of the whole list)
+  const int* sfield = nullptr;         // device, [N]: field of each stamp
+  const int32_t* sfield_h = nullptr;   // host copy of it
+  const int* fptr = nullptr;           // device, [M + 1]: first global stamp of each field
+  int f0 = 0;
+  int64_t row0 = 0;
+  int chunk = 0;
 };
+
+// stamps per chunk of an N-stamp call: the workspace capacity for long inputs, a quarter of the input (>= 128 stamps) for
+// short ones
+static int infer_chunk(const dv_model* m, int64_t N) {
+  if (N < 2 * (int64_t)m->Bc) return (int)std::min<int64_t>(m->Bc, std::max<int64_t>(128, ((N + 3) / 4 + 63) / 64 * 64));
+  return m->Bc;
+}
 
 // results of the pipeline composited on the device instead of copied out (dv_infer_cutouts_composite): every chunk's mean
 // and stddev stamps are added into float64 fields in HBM right behind its forward pass, on the same stream
@@ -2976,9 +2995,8 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
   const Arch& A = m->A;
   hipStream_t s = m->ctx->stream;
   const size_t stamp = (size_t)A.H * A.H * A.C;
-  // chunk: the workspace capacity for long inputs, a quarter of the input (>= 128 stamps) for short ones
-  int chunk = m->Bc;
-  if (N < 2 * (int64_t)m->Bc) chunk = (int)std::min<int64_t>(m->Bc, std::max<int64_t>(128, ((N + 3) / 4 + 63) / 64 * 64));
+  const int chunk = cut && cut->chunk ? cut->chunk : infer_chunk(m, N);
+  const int64_t row0 = cut ? cut->row0 : 0;
   InferPipe* p = nullptr;
   DV_TRY(pipe_get(m, chunk, &p, !(comp && cut)));
   const int64_t K = (N + chunk - 1) / chunk;
@@ -2988,7 +3006,8 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
     const int64_t o = k * chunk;
     const int nb = (int)std::min<int64_t>(chunk, N - o);
     // the caller's float64 cutouts of this chunk: host work that needs nothing from the GPU, done before the wait
-    if (keep) host_gather_cutouts(keep->out + o * stamp, keep->field, cut->F, cut->nb, keep->starts + 2 * o, nb, cut->cs, p->threads);
+    if (keep) host_gather_cutouts(keep->out + o * stamp, keep->field, cut->F, cut->nb, keep->starts + 2 * o, nb, cut->cs, p->threads,
+                                  keep->sfield ? keep->sfield + o : nullptr);
     DV_HIP(hipEventSynchronize(p->ev_d2h[b]));
     if (sink) {
       // streaming consumer: it reads the pinned transfer buffers in place (valid until it returns), nothing is copied
@@ -3027,7 +3046,8 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
     if (k >= 2) DV_HIP(hipStreamWaitEvent(p->s_in, p->ev_comp[b], 0));   // forward of chunk k-2 has read din[b]
     if (trace) DV_HIP(hipEventRecord(tev[6 * k + 0], p->s_in));
     if (cut)
-      DV_TRY(launch_scene_extract_f32(cut->field, cut->F, cut->nb, cut->starts + 2 * k * chunk, nb, cut->cs, p->din[b], p->s_in));
+      DV_TRY(launch_scene_extract_f32(cut->field, cut->F, cut->nb, cut->starts + 2 * k * chunk, nb, cut->cs, p->din[b], p->s_in,
+                                      cut->sfield ? cut->sfield + k * chunk : nullptr, cut->f0));
     else
       DV_HIP(hipMemcpyAsync(p->din[b], p->hin[b], nb * stamp * sizeof(float), hipMemcpyHostToDevice, p->s_in));
     if (trace) DV_HIP(hipEventRecord(tev[6 * k + 1], p->s_in));
@@ -3060,7 +3080,7 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
       m->loc = p->dloc[b];
       m->scale = p->dscale[b];
       const int st = forward_all(m, p->din[b], nullptr, nullptr, 0, nb, nb, false, false, false,
-                                 eps ? eps + o * d : nullptr, seed, (unsigned)m->ctx->rank, (unsigned)o, zstd != nullptr,
+                                 eps ? eps + o * d : nullptr, seed, (unsigned)m->ctx->rank, (unsigned)(row0 + o), zstd != nullptr,
                                  false, true);
       m->loc = keep_loc;
       m->scale = keep_scale;
@@ -3086,11 +3106,19 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
       // latency-bound ones); chunks composite in order because they share this stream, and the forward of chunk k + 2
       // waits for ev_d2h below before it overwrites the outputs this launch reads
       ProfScope ps(m, 2, p->s_out);
-      DV_TRY(launch_scene_composite_chunk(comp->mean_f, comp->std_f, comp->res_f, cut->F, cut->nb, p->dloc[b], p->dscale[b],
-                                          comp->places + 2 * o, nb, cut->cs, p->s_out));
+      if (cut->fptr) {
+        // the fields this chunk's stamps belong to: one row of workgroups per field, each scanning its own objects
+        const int fy0 = cut->sfield_h[o], fy1 = cut->sfield_h[o + nb - 1];
+        DV_TRY(launch_scene_composite_chunk(comp->mean_f, comp->std_f, comp->res_f, cut->F, cut->nb, p->dloc[b], p->dscale[b],
+                                            comp->places + 2 * o, nb, cut->cs, p->s_out, cut->fptr, cut->f0, fy0,
+                                            fy1 - fy0 + 1, (long)(row0 + o)));
+      } else {
+        DV_TRY(launch_scene_composite_chunk(comp->mean_f, comp->std_f, comp->res_f, cut->F, cut->nb, p->dloc[b], p->dscale[b],
+                                            comp->places + 2 * o, nb, cut->cs, p->s_out));
+      }
       if (comp->mse)
         DV_TRY(launch_scene_center_mse(cut->field, cut->F, cut->nb, cut->starts + 2 * o, p->dloc[b], nb, cut->cs,
-                                       comp->mse + o, p->s_out));
+                                       comp->mse + o, p->s_out, cut->sfield ? cut->sfield + o : nullptr, cut->f0));
     }
     if (loc || sink) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (scale || sink) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
@@ -3502,6 +3530,25 @@ int dv_scene_fit_shifts(dv_ctx* c, const double* field_r, int32_t F, const doubl
   DV_HIP(hipSetDevice(c->device));
   return scene_fit_shifts(field_r, F, stamps_r, N, cs, dist, bound, max_iter, shifts_inout, objective, iters, status,
                           c->stream);
+}
+
+int dv_scene_fit_shifts_fields(dv_ctx* c, const double* fields_r, int32_t M, int32_t F, const double* stamps_r,
+                               const int64_t* field_ptr, int64_t N, int32_t cs, const double* dist, double bound,
+                               int32_t max_iter, double* shifts_inout, double* objective, int32_t* iters, int32_t* status) {
+  if (!c || N < 0 || N >= ((int64_t)1 << 31)) return DV_E_INVALID;
+  DV_HIP(hipSetDevice(c->device));
+  // the fields go up in groups that leave room for the fit's own buffers (up to 1.5 GiB per launch)
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t reserve = (size_t)2 << 30;
+  size_t budget = free_b > reserve ? (free_b - reserve) / 10 * 8 : 0;
+  if (const char* e = getenv("DV_FIELDS_GROUP_MB")) {
+    const long mb = atol(e);
+    if (mb > 0) budget = std::min(budget, (size_t)mb << 20);
+  }
+  if (budget == 0) budget = 1;                    // 0 would mean "no limit" below
+  return scene_fit_shifts_fields(fields_r, M, F, stamps_r, field_ptr, (int)N, cs, dist, bound, max_iter, shifts_inout,
+                                 objective, iters, status, budget, c->stream);
 }
 
 int dv_scene_detect(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, const dv_detect_params* p,
@@ -4427,6 +4474,226 @@ int dv_infer_cutouts_stream(dv_model* m, const double* field, int32_t F, int32_t
                             uint64_t seed, dv_chunk_fn consumer, void* user) {
   if (!consumer) return DV_E_INVALID;
   return infer_cutouts_impl(m, field, F, nb, starts, N, seed, nullptr, nullptr, nullptr, nullptr, nullptr, consumer, user);
+}
+
+// ---- many fields in one call (dv_infer_fields, _keep, _composite) ------------------------------------------
+// The stamps of M fields form one global list (field_ptr[m] .. field_ptr[m + 1] are cut from field m) that runs through the
+// pipeline in the chunks dv_infer makes for N stamps, whatever field a stamp belongs to; stamp i draws Philox row i.  The
+// fields are uploaded in groups of consecutive fields sized against free device memory; a group covers whole chunks, so a
+// field whose stamps straddle two groups is resident in both (and its partly composited results travel with it).
+struct FieldsOut {                  // result fields of dv_infer_fields_composite, host [M][F][F][nb]; null otherwise
+  double *mean = nullptr, *stddev = nullptr, *residual = nullptr, *mse = nullptr;
+  const int32_t* places = nullptr;
+};
+
+static int infer_fields_impl(dv_model* m, const char* who, const double* fields, int32_t M, int32_t F, int32_t nb,
+                             const int32_t* starts, const int64_t* field_ptr, int64_t N, uint64_t seed, float* loc,
+                             float* scale, float* mu, float* zstd, float* z, double* cutouts, const FieldsOut* fo) {
+  if (!m || !field_ptr || M < 0 || N < 0 || F < 1 || (M > 0 && !fields) || (N > 0 && !starts)) return DV_E_INVALID;
+  const Arch& A = m->A;
+  const int cs = A.H;
+  if (nb != A.C || cs > F) {
+    set_error("%s: the fields have %d bands and %d pixels, the network takes %d x %d x %d stamps", who, nb, F, cs, cs, A.C);
+    return DV_E_INVALID;
+  }
+  if (N >= ((int64_t)1 << 31)) {
+    set_error("%s: %ld stamps, at most 2^31 - 1 per call", who, (long)N);
+    return DV_E_INVALID;
+  }
+  if (field_ptr[0] != 0 || field_ptr[M] != N) {
+    set_error("%s: field_ptr must run from 0 to the number of stamps (%ld), got %ld .. %ld", who, (long)N,
+              (long)field_ptr[0], (long)field_ptr[M]);
+    return DV_E_INVALID;
+  }
+  for (int32_t f = 0; f < M; ++f)
+    if (field_ptr[f + 1] < field_ptr[f]) {
+      set_error("%s: field_ptr decreases at field %d (%ld after %ld)", who, f, (long)field_ptr[f + 1], (long)field_ptr[f]);
+      return DV_E_INVALID;
+    }
+  std::vector<int32_t> sfield((size_t)N);
+  std::vector<int> fptr32((size_t)M + 1);
+  for (int32_t f = 0; f < M; ++f) {
+    fptr32[f] = (int)field_ptr[f];
+    for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) {
+      sfield[i] = f;
+      const int x = starts[2 * i], y = starts[2 * i + 1];
+      if (x < 0 || y < 0 || x > F - cs || y > F - cs) {   // (cs <= F holds; no x + cs: it overflows near INT_MAX)
+        set_error("%s: cutout %ld of field %d (start %d,%d size %d) leaves the %d-pixel field", who, (long)i, f, x, y, cs, F);
+        return DV_E_INVALID;
+      }
+      if (fo) {
+        const int pr = fo->places[2 * i], pc = fo->places[2 * i + 1];
+        if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
+          set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
+          return DV_E_INVALID;
+        }
+      }
+    }
+  }
+  fptr32[M] = (int)N;
+  const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
+  if (fo)                                       // a field without stamps: nothing predicted, nothing subtracted
+    for (int32_t f = 0; f < M; ++f)
+      if (field_ptr[f + 1] == field_ptr[f]) {
+        memset(fo->mean + (size_t)f * felems, 0, fb);
+        memset(fo->stddev + (size_t)f * felems, 0, fb);
+        if (fo->residual) memcpy(fo->residual + (size_t)f * felems, fields + (size_t)f * felems, fb);
+      }
+  if (N == 0) return DV_OK;
+  TinyCall tiny(m, N);
+  DV_HIP(hipSetDevice(m->ctx->device));
+  hipStream_t s = m->ctx->stream;
+  const int chunk = infer_chunk(m, N);
+  const int64_t K = (N + chunk - 1) / chunk;
+  InferPipe* pipe = nullptr;
+  DV_TRY(pipe_get(m, chunk, &pipe, fo == nullptr));   // before the budget below: the pipeline's buffers come first
+
+  // fields per group: what free memory holds beside the per-stamp tables; DV_FIELDS_GROUP_MB lowers it
+  const size_t per_field = fb * (fo ? (fo->residual ? 4 : 3) : 1);
+  const size_t tables = (size_t)N * (5 * sizeof(int) + sizeof(double)) + ((size_t)M + 1) * sizeof(int);
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  size_t budget = free_b / 10 * 8;
+  budget = budget > tables ? budget - tables : 0;
+  if (const char* e = getenv("DV_FIELDS_GROUP_MB")) {
+    const long mb = atol(e);
+    if (mb > 0) budget = std::min(budget, (size_t)mb << 20);
+  }
+  const int64_t G = (int64_t)(budget / per_field);
+  if (G < 1) {
+    set_error("%s: one %d-pixel field needs %zu bytes of device memory (field%s), %zu are available for fields", who, F,
+              per_field, fo ? " and its result fields" : "", budget);
+    return DV_E_NOMEM;
+  }
+  struct Group { int64_t k0, k1; int f0, f1; };      // chunks [k0, k1), fields [f0, f1]
+  std::vector<Group> groups;
+  int64_t gmax = 0;
+  for (int64_t k = 0; k < K;) {
+    const int f0 = sfield[k * chunk];
+    int64_t k1 = k;
+    int f1 = f0;
+    while (k1 < K) {
+      const int last = sfield[std::min<int64_t>(N, (k1 + 1) * chunk) - 1];
+      if ((int64_t)last - f0 + 1 > G) break;
+      f1 = last;
+      ++k1;
+    }
+    if (k1 == k) {
+      set_error("%s: the %d stamps of chunk %ld come from %d fields, device memory holds %ld at a time: lower max_batch",
+                who, chunk, (long)k, sfield[std::min<int64_t>(N, (k + 1) * chunk) - 1] - f0 + 1, (long)G);
+      return DV_E_NOMEM;
+    }
+    groups.push_back({k, k1, f0, f1});
+    gmax = std::max<int64_t>(gmax, f1 - f0 + 1);
+    k = k1;
+  }
+
+  double *fdev = nullptr, *mf = nullptr, *sf = nullptr, *rf = nullptr, *mse = nullptr;
+  int *sdev = nullptr, *pdev = nullptr, *sfdev = nullptr, *fpdev = nullptr;
+  int st = OK;
+  auto cleanup = [&]() {
+    if (st != OK && pipe->s_out) (void)hipStreamSynchronize(pipe->s_out);   // nothing may still read these
+    if (st != OK && pipe->s_in) (void)hipStreamSynchronize(pipe->s_in);
+    (void)hipFree(fdev); (void)hipFree(mf); (void)hipFree(sf); (void)hipFree(rf); (void)hipFree(mse);
+    (void)hipFree(sdev); (void)hipFree(pdev); (void)hipFree(sfdev); (void)hipFree(fpdev);
+  };
+#define FF_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
+  const size_t sb = (size_t)N * 2 * sizeof(int);
+  FF_HIP(hipMalloc((void**)&fdev, (size_t)gmax * fb));
+  if (fo) {
+    FF_HIP(hipMalloc((void**)&mf, (size_t)gmax * fb));
+    FF_HIP(hipMalloc((void**)&sf, (size_t)gmax * fb));
+    if (fo->residual) FF_HIP(hipMalloc((void**)&rf, (size_t)gmax * fb));
+    if (fo->mse) FF_HIP(hipMalloc((void**)&mse, (size_t)N * sizeof(double)));
+    FF_HIP(hipMalloc((void**)&pdev, sb));
+    FF_HIP(hipMemcpyAsync(pdev, fo->places, sb, hipMemcpyHostToDevice, s));
+  }
+  FF_HIP(hipMalloc((void**)&sdev, sb));
+  FF_HIP(hipMalloc((void**)&sfdev, (size_t)N * sizeof(int)));
+  FF_HIP(hipMalloc((void**)&fpdev, ((size_t)M + 1) * sizeof(int)));
+  FF_HIP(hipMemcpyAsync(sdev, starts, sb, hipMemcpyHostToDevice, s));
+  FF_HIP(hipMemcpyAsync(sfdev, sfield.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+  FF_HIP(hipMemcpyAsync(fpdev, fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  const size_t stamp = (size_t)A.H * A.H * A.C;
+  const int d = A.d;
+  int prev_last = -1;
+  for (const Group& g : groups) {
+    const size_t ng = (size_t)(g.f1 - g.f0 + 1), goff = (size_t)g.f0 * felems;
+    FF_HIP(hipMemcpyAsync(fdev, fields + goff, ng * fb, hipMemcpyHostToDevice, s));
+    if (fo) {
+      FF_HIP(hipMemsetAsync(mf, 0, ng * fb, s));
+      FF_HIP(hipMemsetAsync(sf, 0, ng * fb, s));
+      if (rf) FF_HIP(hipMemcpyAsync(rf, fdev, ng * fb, hipMemcpyDeviceToDevice, s));
+      if (g.f0 == prev_last) {
+        // the first field's earlier stamps were composited with the previous group: go on from those sums
+        FF_HIP(hipMemcpyAsync(mf, fo->mean + goff, fb, hipMemcpyHostToDevice, s));
+        FF_HIP(hipMemcpyAsync(sf, fo->stddev + goff, fb, hipMemcpyHostToDevice, s));
+        if (rf) FF_HIP(hipMemcpyAsync(rf, fo->residual + goff, fb, hipMemcpyHostToDevice, s));
+      }
+    }
+    FF_HIP(hipStreamSynchronize(s));               // the gather runs on the pipeline's copy stream
+    const int64_t r0 = g.k0 * chunk, n = std::min<int64_t>(N, g.k1 * chunk) - r0;
+    CutoutSrc cut{fdev, sdev + 2 * r0, F, nb, cs};
+    cut.sfield = sfdev + r0;
+    cut.sfield_h = sfield.data() + r0;
+    cut.fptr = fpdev;
+    cut.f0 = g.f0;
+    cut.row0 = r0;
+    cut.chunk = chunk;
+    CutoutKeep keep{fields, starts + 2 * r0, cutouts ? cutouts + r0 * stamp : nullptr, sfield.data() + r0};
+    CompositeSink comp{mf, sf, rf, pdev ? pdev + 2 * r0 : nullptr, mse ? mse + r0 : nullptr};
+    st = infer_pipelined(m, nullptr, false, n, nullptr, seed, loc ? loc + r0 * stamp : nullptr,
+                         scale ? scale + r0 * stamp : nullptr, mu ? mu + r0 * d : nullptr, zstd ? zstd + r0 * d : nullptr,
+                         z ? z + r0 * d : nullptr, &cut, nullptr, nullptr, fo ? &comp : nullptr, cutouts ? &keep : nullptr);
+    if (st != OK) {
+      (void)hipStreamSynchronize(s);
+      cleanup();
+      return st;
+    }
+    if (fo) {
+      FF_HIP(hipMemcpyAsync(fo->mean + goff, mf, ng * fb, hipMemcpyDeviceToHost, s));
+      FF_HIP(hipMemcpyAsync(fo->stddev + goff, sf, ng * fb, hipMemcpyDeviceToHost, s));
+      if (rf) FF_HIP(hipMemcpyAsync(fo->residual + goff, rf, ng * fb, hipMemcpyDeviceToHost, s));
+      FF_HIP(hipStreamSynchronize(s));
+    }
+    prev_last = g.f1;
+  }
+  if (mse) {
+    FF_HIP(hipMemcpyAsync(fo->mse, mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipStreamSynchronize(s));
+  }
+#undef FF_HIP
+  cleanup();
+  return prof_flush(m);
+}
+
+int dv_infer_fields(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                    const int64_t* field_ptr, int64_t N, uint64_t seed, float* loc, float* scale, float* mu, float* zstd,
+                    float* z) {
+  return infer_fields_impl(m, "dv_infer_fields", fields, M, F, nb, starts, field_ptr, N, seed, loc, scale, mu, zstd, z,
+                           nullptr, nullptr);
+}
+
+int dv_infer_fields_keep(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                         const int64_t* field_ptr, int64_t N, uint64_t seed, float* loc, float* scale, float* mu,
+                         float* zstd, float* z, double* cutouts) {
+  if (!cutouts && N > 0) return DV_E_INVALID;
+  return infer_fields_impl(m, "dv_infer_fields_keep", fields, M, F, nb, starts, field_ptr, N, seed, loc, scale, mu, zstd, z,
+                           cutouts, nullptr);
+}
+
+int dv_infer_fields_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                              const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                              double* mean_fields, double* stddev_fields, double* residual_fields, double* mse_center) {
+  if ((M > 0 && (!mean_fields || !stddev_fields)) || (N > 0 && !places)) return DV_E_INVALID;
+  FieldsOut fo;
+  fo.mean = mean_fields;
+  fo.stddev = stddev_fields;
+  fo.residual = residual_fields;
+  fo.mse = mse_center;
+  fo.places = places;
+  return infer_fields_impl(m, "dv_infer_fields_composite", fields, M, F, nb, starts, field_ptr, N, seed, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, &fo);
 }
 
 int dv_infer_mc(dv_model* m, const float* x, int64_t N, int32_t nsamples, uint64_t seed, float* mean_out,

@@ -45,6 +45,7 @@ struct PosfitGeom {
   double s0r, s0c;     // start shifts
   long ws;             // offset of this galaxy's workspace in doubles
   int stamp;           // stamp index within the chunk
+  int field;           // the galaxy's field within the resident stack of fields (0 for a single field)
   int integer;         // 1: d is integer, net is a translation
   int empty;           // 1: net is zero everywhere (the stamp misses the field)
   int nr_lo, nr_n, nc_lo, nc_n;   // net support
@@ -207,6 +208,7 @@ __device__ __forceinline__ void pf_projected(const PfEval& e, double sr, double 
   pc = pf_held(sc, e.gc, B) ? 0.0 : e.gc;
 }
 
+// img: the resident stack of r-band fields [G][F][F], total_sq [G] their sums of squares; galaxy gi reads field geoms[gi].field
 __global__ __launch_bounds__(PF_THREADS) void posfit_kernel(const double* __restrict__ img, int F,
                                                             const double* __restrict__ stamps, int cs,
                                                             const PosfitGeom* __restrict__ geoms,
@@ -217,7 +219,8 @@ __global__ __launch_bounds__(PF_THREADS) void posfit_kernel(const double* __rest
   __shared__ double s_red[4 * 6];
   const int gi = blockIdx.x;
   const PosfitGeom g = geoms[gi];
-  const double tot = total_sq[0];
+  img += (long)g.field * F * F;
+  const double tot = total_sq[g.field];
   const double inv = 1.0 / ((double)F * (double)F);
   if (g.empty) {                      // net = 0: J is constant, nothing to fit
     if (threadIdx.x == 0) {
@@ -364,14 +367,15 @@ __global__ __launch_bounds__(PF_THREADS) void posfit_kernel(const double* __rest
   }
 }
 
-// sum of img^2 over the field, one workgroup, fixed order
+// sum of img^2 over a field of n elements, one workgroup per field of the stack, fixed order
 __global__ __launch_bounds__(PF_THREADS) void posfit_total_sq_kernel(const double* __restrict__ img, long n,
                                                                      double* __restrict__ out) {
   __shared__ double s_red[4];
+  img += (long)blockIdx.x * n;
   double a[1] = {0.0};
   for (long e = threadIdx.x; e < n; e += PF_THREADS) a[0] += img[e] * img[e];
   pf_block_sum<1>(a, s_red);
-  if (threadIdx.x == 0) out[0] = a[0];
+  if (threadIdx.x == 0) out[blockIdx.x] = a[0];
 }
 
 // [lo, hi) intersected with [0, F) -> (lo, n); n = 0 if empty
@@ -386,11 +390,34 @@ void pf_clip(long lo, long hi, int F, int& olo, int& on) {
 int scene_fit_shifts(const double* field_h, int F, const double* stamps_h, int N, int cs, const double* dist_h,
                      double bound, int max_iter, double* shifts_h, double* objective_h, int32_t* iters_h,
                      int32_t* status_h, hipStream_t s) {
-  if (!field_h || F < 2 || F > 32768 || cs < 1 || cs > F || N < 0 || max_iter < 0 || !(bound >= 0.0) || bound > 1e6 ||
+  const int64_t one_field[2] = {0, N};
+  return scene_fit_shifts_fields(field_h, 1, F, stamps_h, one_field, N, cs, dist_h, bound, max_iter, shifts_h, objective_h,
+                                 iters_h, status_h, 0, s);
+}
+
+// M fields [M][F][F]; galaxies field_ptr[m] .. field_ptr[m + 1] belong to field m.  A galaxy's fit reads its own field, its
+// own stamp and its own workspace only, and every reduction has a fixed order, so its result does not depend on which
+// other galaxies or fields share its launch: M fields give what M single-field calls give, bit for bit.
+// The fields are uploaded in groups of consecutive fields that fit budget_bytes (0: no limit other than a failed
+// allocation); a group's galaxies are fitted, CHUNK per launch, before the next group goes up.
+int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* stamps_h, const int64_t* field_ptr, int N,
+                            int cs, const double* dist_h, double bound, int max_iter, double* shifts_h, double* objective_h,
+                            int32_t* iters_h, int32_t* status_h, size_t budget_bytes, hipStream_t s) {
+  if (!field_h || !field_ptr || M < 1 || F < 2 || F > 32768 || cs < 1 || cs > F || N < 0 || max_iter < 0 || !(bound >= 0.0) || bound > 1e6 ||
       (N > 0 && (!stamps_h || !dist_h || !shifts_h || !objective_h || !iters_h || !status_h))) {
     set_error("scene_fit_shifts: bad arguments");
     return E_INVALID;
   }
+  if (field_ptr[0] != 0 || field_ptr[M] != N) {
+    set_error("scene_fit_shifts: field_ptr must run from 0 to the number of galaxies (%d), got %ld .. %ld", N,
+              (long)field_ptr[0], (long)field_ptr[M]);
+    return E_INVALID;
+  }
+  for (int m = 0; m < M; ++m)
+    if (field_ptr[m + 1] < field_ptr[m]) {
+      set_error("scene_fit_shifts: field_ptr decreases at field %d", m);
+      return E_INVALID;
+    }
   if (N == 0) return OK;
   const int T = PF_T;
   const int po = (F - cs) / 2;
@@ -458,6 +485,16 @@ int scene_fit_shifts(const double* field_h, int F, const double* stamps_h, int N
   }
 
   const size_t img_elems = (size_t)F * F, stamp_elems = (size_t)cs * cs;
+  // fields per group
+  size_t G = (size_t)M;
+  if (budget_bytes) {
+    G = std::min<size_t>(G, budget_bytes / (img_elems * sizeof(double)));
+    if (G < 1) {
+      set_error("scene_fit_shifts: one %d-pixel field (%zu bytes) does not fit the %zu bytes of device memory available "
+                "for fields", F, img_elems * sizeof(double), budget_bytes);
+      return E_NOMEM;
+    }
+  }
   // galaxies per launch: at most CHUNK, and at most STAMP_BUDGET doubles of stamps (a few for field-sized stamps)
   const int chunk = (int)std::min<size_t>({(size_t)N, (size_t)CHUNK, std::max<size_t>(1, STAMP_BUDGET / stamp_elems)});
   double *img = nullptr, *stamps = nullptr, *work = nullptr, *tot = nullptr, *out_s = nullptr, *out_j = nullptr;
@@ -470,46 +507,55 @@ int scene_fit_shifts(const double* field_h, int F, const double* stamps_h, int N
     (void)hipFree(out_j); (void)hipFree(out_it); (void)hipFree(out_st); (void)hipFree(dgeo);
   };
 #define PF_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
-  PF_HIP(hipMalloc((void**)&img, img_elems * sizeof(double)));
-  PF_HIP(hipMalloc((void**)&tot, sizeof(double)));
+  PF_HIP(hipMalloc((void**)&img, G * img_elems * sizeof(double)));
+  PF_HIP(hipMalloc((void**)&tot, G * sizeof(double)));
   PF_HIP(hipMalloc((void**)&stamps, (size_t)chunk * stamp_elems * sizeof(double)));
   PF_HIP(hipMalloc((void**)&out_s, (size_t)chunk * 2 * sizeof(double)));
   PF_HIP(hipMalloc((void**)&out_j, (size_t)chunk * sizeof(double)));
   PF_HIP(hipMalloc((void**)&out_it, (size_t)chunk * sizeof(int)));
   PF_HIP(hipMalloc((void**)&out_st, (size_t)chunk * sizeof(int)));
   PF_HIP(hipMalloc((void**)&dgeo, (size_t)chunk * sizeof(PosfitGeom)));
-  PF_HIP(hipMemcpyAsync(img, field_h, img_elems * sizeof(double), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(posfit_total_sq_kernel, dim3(1), dim3(PF_THREADS), 0, s, img, (long)img_elems, tot);
-  PF_HIP(hipGetLastError());
-  for (int base = 0; base < N;) {
-    // as many galaxies as the chunk and the workspace budget allow
-    int n = 0;
-    long w = 0;
-    while (base + n < N && n < chunk && w + need[base + n] <= WS_BUDGET) {   // (need <= WS_BUDGET: n >= 1)
-      PosfitGeom& g = geo[base + n];
-      g.stamp = n;
-      g.ws = w;
-      w += need[base + n];
-      ++n;
-    }
-    if (w > work_cap) {
-      (void)hipFree(work);
-      work = nullptr;
-      PF_HIP(hipMalloc((void**)&work, (size_t)std::max(w, 1L) * sizeof(double)));
-      work_cap = w;
-    }
-    PF_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)base * stamp_elems, (size_t)n * stamp_elems * sizeof(double),
+  for (int g0 = 0; g0 < M; g0 += (int)G) {
+    const int g1 = (int)std::min<size_t>((size_t)M, (size_t)g0 + G);
+    const int ga = (int)field_ptr[g0], gb = (int)field_ptr[g1];
+    if (ga == gb) continue;                        // no galaxy in these fields
+    PF_HIP(hipMemcpyAsync(img, field_h + (size_t)g0 * img_elems, (size_t)(g1 - g0) * img_elems * sizeof(double),
                           hipMemcpyHostToDevice, s));
-    PF_HIP(hipMemcpyAsync(dgeo, geo.data() + base, (size_t)n * sizeof(PosfitGeom), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(posfit_kernel, dim3((unsigned)n), dim3(PF_THREADS), 0, s, img, F, stamps, cs, dgeo, work, tot,
-                       bound, max_iter, out_s, out_j, out_it, out_st);
+    hipLaunchKernelGGL(posfit_total_sq_kernel, dim3((unsigned)(g1 - g0)), dim3(PF_THREADS), 0, s, img, (long)img_elems, tot);
     PF_HIP(hipGetLastError());
-    PF_HIP(hipMemcpyAsync(shifts_h + 2 * (size_t)base, out_s, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    PF_HIP(hipMemcpyAsync(objective_h + base, out_j, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    PF_HIP(hipMemcpyAsync(iters_h + base, out_it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    PF_HIP(hipMemcpyAsync(status_h + base, out_st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    PF_HIP(hipStreamSynchronize(s));             // the device buffers are reused by the next chunk
-    base += n;
+    int fm = g0;                                   // field of galaxy base + n
+    for (int base = ga; base < gb;) {
+      // as many galaxies as the chunk and the workspace budget allow
+      int n = 0;
+      long w = 0;
+      while (base + n < gb && n < chunk && w + need[base + n] <= WS_BUDGET) {   // (need <= WS_BUDGET: n >= 1)
+        PosfitGeom& g = geo[base + n];
+        while (field_ptr[fm + 1] <= base + n) ++fm;
+        g.field = fm - g0;
+        g.stamp = n;
+        g.ws = w;
+        w += need[base + n];
+        ++n;
+      }
+      if (w > work_cap) {
+        (void)hipFree(work);
+        work = nullptr;
+        PF_HIP(hipMalloc((void**)&work, (size_t)std::max(w, 1L) * sizeof(double)));
+        work_cap = w;
+      }
+      PF_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)base * stamp_elems, (size_t)n * stamp_elems * sizeof(double),
+                            hipMemcpyHostToDevice, s));
+      PF_HIP(hipMemcpyAsync(dgeo, geo.data() + base, (size_t)n * sizeof(PosfitGeom), hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(posfit_kernel, dim3((unsigned)n), dim3(PF_THREADS), 0, s, img, F, stamps, cs, dgeo, work, tot,
+                         bound, max_iter, out_s, out_j, out_it, out_st);
+      PF_HIP(hipGetLastError());
+      PF_HIP(hipMemcpyAsync(shifts_h + 2 * (size_t)base, out_s, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+      PF_HIP(hipMemcpyAsync(objective_h + base, out_j, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+      PF_HIP(hipMemcpyAsync(iters_h + base, out_it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+      PF_HIP(hipMemcpyAsync(status_h + base, out_st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+      PF_HIP(hipStreamSynchronize(s));             // the device buffers are reused by the next chunk
+      base += n;
+    }
   }
   cleanup();
   return OK;

@@ -33,11 +33,15 @@ struct SceneObj {
 // (the first version decoded a flat 64-bit element index with four divisions per element: 1.08 ms per 8192-cutout chunk of
 // the inference pipeline, 0.41 ms now).  OUT = double: the reference's cutouts; OUT = float: cast as deblend() does
 // (tf.cast, deblender.py:18), straight into the network's input buffer.
+// Many fields (dv_infer_fields*): `field` is the first resident field f0 of a stack of F x F x nb fields and sfield[n] the
+// field cutout n is cut from - one lookup per workgroup, uniform for all its threads.  sfield = null: one field.
 template <typename OUT>
 __global__ __launch_bounds__(256) void scene_extract_kernel(const double* __restrict__ field, int F, int nb,
-                                                            const int* __restrict__ starts, int cs, OUT* __restrict__ out) {
+                                                            const int* __restrict__ starts, int cs, OUT* __restrict__ out,
+                                                            const int* __restrict__ sfield, int f0) {
   const int n = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int x0 = starts[2 * n], y0 = starts[2 * n + 1];
+  if (sfield) field += (long)(sfield[n] - f0) * F * F * nb;
   const int rowlen = cs * nb;
   OUT* o = out + (long)n * cs * rowlen;
   for (int i = wave; i < cs; i += 4) {
@@ -172,6 +176,12 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(double* __restrict
 // list (a prefix sum of the hit counts over the 256 threads), then every thread walks the list for its pixel.  Uniformly
 // scattered cutouts leave ~4 entries per round and tile; a pile of objects on one spot just makes the lists long (a
 // round's list holds all 2048) - no capacity limit, no atomics, no float non-determinism.
+//
+// Many fields (dv_infer_fields_composite, fptr != null): the three result pointers address a stack of fields starting at
+// field f0, blockIdx.y + fy0 is the field this workgroup's tile belongs to, and the workgroup scans only that field's objects
+// of the chunk: fptr[m] .. fptr[m + 1] (global stamp numbers) cut to the chunk [obase, obase + n).  A field has its own
+// workgroups, so two fields never meet in a sum, and within a field the order of additions is object order as before: a
+// field's result has the bits the single-field call gives.  A field without objects in the chunk returns at once.
 constexpr int CT = 32;       // tile edge: a thread owns the four pixels (ty + 16 a, tx + 16 b) of its 32 x 32 tile
 constexpr int CSEG = 2048;   // objects per scan round (8 per thread)
 template <int NBMAX>
@@ -179,7 +189,9 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
                                                                     double* __restrict__ res_f, int F, int nb,
                                                                     const float* __restrict__ loc,
                                                                     const float* __restrict__ scale,
-                                                                    const int* __restrict__ places, int n, int cs) {
+                                                                    const int* __restrict__ places, int n, int cs,
+                                                                    const int* __restrict__ fptr, int f0, int fy0,
+                                                                    long obase) {
   __shared__ int s_list[CSEG];        // objects of the round that meet the tile, in object order
   __shared__ int s_lr[CSEG], s_lc[CSEG];   // their placements
   __shared__ int s_wsum[4];
@@ -194,7 +206,19 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
     for (int b = 0; b < NBMAX; ++b) am[q][b] = as[q][b] = ar[q][b] = 0.0;
   bool loaded = false;
   unsigned touched = 0;
-  for (int seg = 0; seg < n; seg += CSEG) {
+  int olo = 0;
+  if (fptr) {                            // uniform over the workgroup
+    const int m = fy0 + (int)blockIdx.y;
+    const long lo = (long)fptr[m] - obase, hi = (long)fptr[m + 1] - obase;
+    olo = (int)(lo > 0 ? lo : 0);
+    n = (int)(hi < n ? hi : n);
+    if (olo >= n) return;
+    const long fo = (long)(m - f0) * F * F * nb;
+    mean_f += fo;
+    std_f += fo;
+    if (res_f) res_f += fo;
+  }
+  for (int seg = olo; seg < n; seg += CSEG) {
     // thread t tests objects seg + 8 t .. + 7 (four 16-byte loads of their placements): order by (thread, bit) = object order
     const int o0 = seg + tid * 8;
     unsigned hits = 0;
@@ -301,27 +325,83 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
 
 // mse_center[i] = mean over the centre 10 x 10 pixels and all bands of (cutout_i - mean_i)^2 in float64
 // (field_deblender.py:323-327: mse(cutout_images[k, c0:c1, c0:c1], output_images_mean[i, c0:c1, c0:c1]) with
-// c0 = int(cs/2) - 5, c1 = int(cs/2) + 5; training/metrics.py:4-12); one wave per stamp
+// c0 = int(cs/2) - 5, c1 = int(cs/2) + 5; training/metrics.py:4-12); one wave per stamp.
+// The 100 * nb squares are added in the order numpy's np.mean adds them (pairwise summation: halves cut at multiples of
+// eight down to blocks of at most 128, a block as eight interleaved partial sums combined ((0+1)+(2+3))+((4+5)+(6+7)), then
+// its tail), so the value has the bits of the reference's host formula and of DeblendField's default path.  The wave's
+// lanes write the squares to LDS; lane 0 adds them (a few hundred additions per stamp).
+constexpr int MSE_MAX = 100 * 8;     // squares per stamp: 10 x 10 pixels, at most 8 bands
+
+__device__ double mse_block_sum(const double* a, int n) {
+  if (n < 8) {
+    double res = 0.0;
+    for (int i = 0; i < n; ++i) res += a[i];
+    return res;
+  }
+  double r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = a[j];
+  int i = 8;
+  for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+  }
+  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += a[i];
+  return res;
+}
+
+// sum(a[0..n)) in numpy's pairwise order, n <= MSE_MAX (at most three levels of halving above the 128-element blocks)
+__device__ double mse_pairwise_sum(const double* a, int n) {
+  int off[8], len[8], stage[8], sp = 0, vt = 0;
+  double val[8];
+  off[0] = 0; len[0] = n; stage[0] = 0; sp = 1;
+  while (sp > 0) {
+    const int t = sp - 1;
+    if (len[t] <= 128) {
+      val[vt++] = mse_block_sum(a + off[t], len[t]);
+      --sp;
+    } else if (stage[t] < 2) {
+      int n2 = len[t] / 2;
+      n2 -= n2 % 8;
+      const int left = stage[t] == 0;
+      ++stage[t];
+      off[sp] = left ? off[t] : off[t] + n2;
+      len[sp] = left ? n2 : len[t] - n2;
+      stage[sp] = 0;
+      ++sp;
+    } else {
+      val[vt - 2] = val[vt - 2] + val[vt - 1];
+      --vt;
+      --sp;
+    }
+  }
+  return val[0];
+}
+
 __global__ __launch_bounds__(256) void scene_center_mse_kernel(const double* __restrict__ field, int F, int nb,
                                                                const int* __restrict__ starts,
                                                                const float* __restrict__ loc, int n, int cs,
-                                                               double* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= n) return;
+                                                               double* __restrict__ out,
+                                                               const int* __restrict__ sfield, int f0) {
+  __shared__ double s_sq[4][MSE_MAX];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * 4 + wave;
+  const bool valid = i < n;                                      // (uniform over the wave)
+  if (valid && sfield) field += (long)(sfield[i] - f0) * F * F * nb;      // the field stamp i was cut from (uniform over the wave)
   const int c0 = cs / 2 - 5, w = 10;
-  const int x0 = starts[2 * i], y0 = starts[2 * i + 1];
-  double acc = 0.0;
+  const int x0 = valid ? starts[2 * i] : 0, y0 = valid ? starts[2 * i + 1] : 0;
   const int total = w * w * nb;
-  for (int e = lane; e < total; e += 64) {
+  double* sq = s_sq[wave];
+  for (int e = lane; valid && e < total; e += 64) {
     const int b = e % nb, q = e / nb, cc = q % w, rr = q / w;
     const double a = field[((long)(x0 + c0 + rr) * F + (y0 + c0 + cc)) * nb + b];
     const double m = (double)loc[(((long)i * cs + c0 + rr) * cs + c0 + cc) * nb + b];
-    acc += (a - m) * (a - m);
+    const double d = a - m;
+    sq[e] = __dmul_rn(d, d);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (lane == 0) out[i] = acc / (double)total;
+  __syncthreads();
+  if (valid && lane == 0) out[i] = mse_pairwise_sum(sq, total) / (double)total;
 }
 }  // namespace
 
@@ -350,7 +430,8 @@ int scene_extract(const double* field_h, int F, int nb, const int32_t* starts_h,
   SC_HIP(hipMalloc((void**)&starts, (size_t)N * 2 * sizeof(int)));
   SC_HIP(hipMemcpyAsync(field, field_h, fb, hipMemcpyHostToDevice, s));
   SC_HIP(hipMemcpyAsync(starts, starts_h, (size_t)N * 2 * sizeof(int), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(scene_extract_kernel<double>, dim3((unsigned)N), dim3(256), 0, s, field, F, nb, starts, cs, out);
+  hipLaunchKernelGGL(scene_extract_kernel<double>, dim3((unsigned)N), dim3(256), 0, s, field, F, nb, starts, cs, out,
+                     (const int*)nullptr, 0);
   SC_HIP(hipGetLastError());
   SC_HIP(hipMemcpyAsync(out_h, out, ob, hipMemcpyDeviceToHost, s));
   SC_HIP(hipStreamSynchronize(s));
@@ -359,11 +440,11 @@ int scene_extract(const double* field_h, int F, int nb, const int32_t* starts_h,
 }
 
 int launch_scene_extract_f32(const double* field_dev, int F, int nb, const int* starts_dev, long count, int cs,
-                             float* out_dev, hipStream_t s) {
+                             float* out_dev, hipStream_t s, const int* sfield_dev, int f0) {
   const long total = count * cs * cs * nb;
   if (total <= 0) return OK;
   hipLaunchKernelGGL(scene_extract_kernel<float>, dim3((unsigned)count), dim3(256), 0, s, field_dev, F, nb, starts_dev, cs,
-                     out_dev);
+                     out_dev, sfield_dev, f0);
   DV_HIP(hipGetLastError());
   return OK;
 }
@@ -439,32 +520,42 @@ int scene_composite(double* field_h, int F, int nb, const double* stamps_h, cons
 
 namespace dv {
 int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, int F, int nb, const float* loc,
-                                 const float* scale, const int* places_dev, int n, int cs, hipStream_t s) {
+                                 const float* scale, const int* places_dev, int n, int cs, hipStream_t s,
+                                 const int* fptr_dev, int f0, int fy0, int nfields, long obase) {
   if (n <= 0) return OK;
   if (nb < 1 || nb > 8) {
     set_error("scene composite: 1 .. 8 bands");
     return E_INVALID;
   }
   const int ntx = (F + CT - 1) / CT;
+  if (fptr_dev && (nfields < 1 || nfields > 65535)) {
+    set_error("scene composite: a chunk spans %d fields, at most 65535", nfields);
+    return E_INVALID;
+  }
+  const dim3 grid((unsigned)(ntx * ntx), fptr_dev ? (unsigned)nfields : 1u);
   if (nb <= 6)
-    hipLaunchKernelGGL(scene_composite_chunk_kernel<6>, dim3((unsigned)(ntx * ntx)), dim3(256), 0, s, mean_f, std_f, res_f, F,
-                       nb, loc, scale, places_dev, n, cs);
+    hipLaunchKernelGGL(scene_composite_chunk_kernel<6>, grid, dim3(256), 0, s, mean_f, std_f, res_f, F, nb, loc, scale,
+                       places_dev, n, cs, fptr_dev, f0, fy0, obase);
   else
-    hipLaunchKernelGGL(scene_composite_chunk_kernel<8>, dim3((unsigned)(ntx * ntx)), dim3(256), 0, s, mean_f, std_f, res_f, F,
-                       nb, loc, scale, places_dev, n, cs);
+    hipLaunchKernelGGL(scene_composite_chunk_kernel<8>, grid, dim3(256), 0, s, mean_f, std_f, res_f, F, nb, loc, scale,
+                       places_dev, n, cs, fptr_dev, f0, fy0, obase);
   DV_HIP(hipGetLastError());
   return OK;
 }
 
 int launch_scene_center_mse(const double* field_dev, int F, int nb, const int* starts_dev, const float* loc, int n, int cs,
-                            double* out_dev, hipStream_t s) {
+                            double* out_dev, hipStream_t s, const int* sfield_dev, int f0) {
   if (n <= 0) return OK;
   if (cs < 10) {
     set_error("centre MSE needs stamps of at least 10 pixels");
     return E_INVALID;
   }
+  if (nb < 1 || nb > 8) {
+    set_error("centre MSE: 1 .. 8 bands");
+    return E_INVALID;
+  }
   hipLaunchKernelGGL(scene_center_mse_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, field_dev, F, nb, starts_dev, loc,
-                     n, cs, out_dev);
+                     n, cs, out_dev, sfield_dev, f0);
   DV_HIP(hipGetLastError());
   return OK;
 }

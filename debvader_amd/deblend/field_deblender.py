@@ -354,3 +354,218 @@ class DeblendField:
         }).to_records(index=False)
         self._device_fields = (self.res_deblend, out)      # the fields and the recarray they belong to, set together
         return self.res_deblend
+
+
+# -- many fields at once (engine-specific) -------------------------------------------------------
+def batch_windows(field_size, galaxy_distances_to_center, cutout_size=59):
+    """The windows of the galaxies of M fields as one list, for the many-field engine calls.
+
+    galaxy_distances_to_center: M arrays (n_m, 2) of distances to the centre of each galaxy's own field.  Window validity is
+    cutout_windows' (the reference's rule, extraction.py:26-41), field by field.  Returns (starts (N, 2) int32, field_ptr
+    (M + 1,) int64, list_idx: M int64 arrays of the galaxies of each field that were kept, distances (N, 2) float64 of the
+    kept galaxies): rows field_ptr[m]:field_ptr[m + 1] belong to field m, in the order of its list_idx."""
+    starts, kept, dists = [], [], []
+    field_ptr = np.zeros(len(galaxy_distances_to_center) + 1, dtype=np.int64)
+    for m, d in enumerate(galaxy_distances_to_center):
+        d = np.asarray(d, dtype=np.float64)
+        if d.size == 0:
+            d = d.reshape(0, 2)
+        if d.ndim != 2 or d.shape[1] != 2:
+            raise ValueError(f"field {m}: expected distances (n, 2), got {d.shape}")
+        st, ok = cutout_windows(field_size, d, cutout_size) if len(d) else (np.zeros((0, 2), np.int32), np.zeros(0, bool))
+        starts.append(st[ok])
+        kept.append(np.nonzero(ok)[0].astype(np.int64))
+        dists.append(d[ok])
+        field_ptr[m + 1] = field_ptr[m] + int(ok.sum())
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt).reshape(-1, 2) if parts else np.zeros((0, 2), dt)
+    return cat(starts, np.int32), field_ptr, kept, cat(dists, np.float64)
+
+
+class DeblendFieldBatch:
+    """DeblendField for M fields of one size: every pass is ONE engine call for the galaxies of all fields, so a survey of
+    small fields runs the network in full chunks instead of one latency-bound call per field.  Per field the results are
+    those of DeblendField on that field, for the noise rows its galaxies have in the call (galaxies are numbered over all
+    fields, field after field).  No epistemic estimate."""
+
+    DEFAULT_COLUMNS = [("cutout_images", "O"), ("output_images_mean", "O"), ("output_images_stddev", "O"), ("shifts", "O"),
+                       ("list_idx", "<i8"), ("galaxy_distances_to_center_x", "<f8"), ("galaxy_distances_to_center_y", "<f8"),
+                       ("epistemic_uncertainty", "O"), ("passed_cuts", "?")]
+    ON_DEVICE_COLUMNS = [("list_idx", "<i8"), ("shifts", "O"), ("galaxy_distances_to_center_x", "<f8"),
+                         ("galaxy_distances_to_center_y", "<f8"), ("mse_center", "<f8"), ("passed_cuts", "?")]
+
+    def __init__(self, net, field_images, cutout_size=59, nb_of_bands=6, normalise=False):
+        """
+        parameters:
+            net: network used to deblend the fields
+            field_images: the fields, shape (M, size, size, bands)
+            cutout_size: size of the stamps
+            nb_of_bands: number of filters in the images
+            normalise: normalise the stamps before the network
+        """
+        f = np.array(field_images, dtype=np.float64, copy=True, order="C")
+        if f.ndim != 4 or f.shape[1] != f.shape[2] or f.shape[3] != nb_of_bands:
+            raise ValueError(f"expected fields (M, F, F, {nb_of_bands}), got {f.shape}")
+        self.net = net
+        self.field_images = f
+        self.nb_of_fields = f.shape[0]
+        self.field_size = f.shape[1]
+        self.cutout_size = cutout_size
+        self.nb_of_bands = nb_of_bands
+        self.normalise = normalise
+        self.nb_of_detected_objects = []
+        self.nb_of_deblended_galaxies = []
+        self.res_deblend = None
+        self._ctx_obj = getattr(getattr(net, "_core", None), "ctx", None)
+        self._device_fields = None      # (res_deblend list, fields composited on the GPU) of the last on-device pass
+
+    @property
+    def _ctx(self):
+        if self._ctx_obj is None:
+            self._ctx_obj = E.default_context()
+        return self._ctx_obj
+
+    def _shifts_column(self, n):
+        col = np.empty(n, dtype=object)
+        for i in range(n):
+            col[i] = np.array([0, 0])
+        return col
+
+    def deblend_fields(self, galaxy_distances_to_center=None, mse_criterion=100.0, on_device=False):
+        """Deblend the galaxies of every field in one engine call.
+
+        galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
+        Returns a list of M recarrays (kept in self.res_deblend) with the columns DeblendField.deblend_field gives in the
+        same mode: by default the stamps (dv_infer_fields_keep), with on_device=True the per-galaxy scalars and mse_center
+        only, the fields being composited on the GPU (dv_infer_fields_composite; integer positions).  A field without a
+        valid galaxy gets an empty recarray."""
+        if galaxy_distances_to_center is None:
+            from debvader_amd.detect.detection import detect_objects_batch
+            galaxy_distances_to_center = detect_objects_batch(self.field_images, ctx=self._ctx)
+        if len(galaxy_distances_to_center) != self.nb_of_fields:
+            raise ValueError(f"{self.nb_of_fields} fields but {len(galaxy_distances_to_center)} lists of galaxy distances")
+        F, cs, nb = self.field_size, self.cutout_size, self.nb_of_bands
+        starts, field_ptr, kept, dd = batch_windows(F, galaxy_distances_to_center, cs)
+        n_det = [len(d) for d in galaxy_distances_to_center]
+        if sum(len(k) for k in kept) != sum(n_det):
+            print("Some galaxies are too close from the border of the field to be considered here.")
+        if on_device and not np.array_equal(dd, np.floor(dd)):
+            raise ValueError("on_device=True places stamps at integer positions; fractional distances need the default path")
+        core = getattr(self.net, "_core", None)
+        eng = getattr(core, "engine", None)
+        if eng is None:
+            raise ValueError("DeblendFieldBatch needs a net that runs on the engine (debvader_amd.model.model.load_deblender)")
+        self.res_deblend = None
+        self._device_fields = None
+        N = len(starts)
+        eng.set_normalise(bool(self.normalise))
+        try:
+            if on_device:
+                # where get_predicted_field puts a stamp: padded at int((F - cs) / 2) and shifted by the distance to the centre
+                places = (int((F - cs) / 2) + dd).astype(np.int64)
+                out = eng.infer_fields_composite(self.field_images, starts, places, field_ptr, seed=core.next_seed())
+            else:
+                out = eng.infer_fields_keep(self.field_images, starts, field_ptr, seed=core.next_seed())
+        finally:
+            eng.set_normalise(False)
+        if on_device:
+            mse_center = out["mse_center"]
+        else:
+            c0, c1 = int(cs / 2) - 5, int(cs / 2) + 5
+            diff = out["cutouts"][:, c0:c1, c0:c1] - out["loc"][:, c0:c1, c0:c1]
+            mse_center = np.mean(np.square(diff).reshape(N, -1), axis=1) if N else np.zeros(0)
+            no_epistemic = np.zeros((cs, cs, nb))
+            no_epistemic.flags.writeable = False          # one array stands for every row's zeros
+        passed = ~(mse_center > mse_criterion)
+        res = []
+        for m in range(self.nb_of_fields):
+            lo, hi = int(field_ptr[m]), int(field_ptr[m + 1])
+            n = hi - lo
+            rec = np.recarray((n,), dtype=self.ON_DEVICE_COLUMNS if on_device else self.DEFAULT_COLUMNS)
+            rec["list_idx"] = kept[m]
+            rec["shifts"] = self._shifts_column(n)
+            rec["galaxy_distances_to_center_x"] = dd[lo:hi, 0]
+            rec["galaxy_distances_to_center_y"] = dd[lo:hi, 1]
+            rec["passed_cuts"] = passed[lo:hi]
+            if on_device:
+                rec["mse_center"] = mse_center[lo:hi]
+            else:
+                for i in range(n):
+                    rec["cutout_images"][i] = out["cutouts"][lo + i]
+                    rec["output_images_mean"][i] = out["loc"][lo + i]
+                    rec["output_images_stddev"][i] = out["scale"][lo + i]
+                    rec["epistemic_uncertainty"][i] = no_epistemic
+            res.append(rec)
+        self.nb_of_detected_objects += [n_det]
+        self.nb_of_deblended_galaxies += [[len(k) for k in kept]]
+        self.res_deblend = res
+        if on_device:
+            self._device_fields = (res, out)
+        return res
+
+    def _own_device_fields(self):
+        if self._device_fields is not None and self._device_fields[0] is self.res_deblend:
+            return self._device_fields[1]
+        return None
+
+    def _stack(self, rec, key):
+        if key not in rec.dtype.names:
+            raise ValueError(f"these recarrays have no {key!r} column: they come from deblend_fields(on_device=True), whose "
+                             "stamps stayed on the GPU; run the default path to work from stamps")
+        return np.array([np.asarray(row[key], dtype=np.float64) for row in rec], dtype=np.float64).reshape(
+            -1, self.cutout_size, self.cutout_size, self.nb_of_bands)
+
+    def _need_pass(self):
+        if self.res_deblend is None:
+            raise ValueError("no deblend_fields() pass yet")
+
+    def get_residual_fields(self):
+        """The fields minus every predicted galaxy at its position, (M, F, F, bands)."""
+        self._need_pass()
+        dev = self._own_device_fields()
+        if dev is not None:
+            return dev["residual_fields"].copy()
+        out = self.field_images.copy()
+        for m, rec in enumerate(self.res_deblend):
+            if len(rec):
+                out[m] = self._ctx.scene_composite(self.field_images[m], self._stack(rec, "output_images_mean"),
+                                                   DeblendField._positions(rec), -1.0)
+        return out
+
+    def get_predicted_fields(self):
+        """{"predicted_mean_fields", "predicted_stddev_fields"}, each (M, F, F, bands)."""
+        self._need_pass()
+        dev = self._own_device_fields()
+        if dev is not None:
+            return {"predicted_mean_fields": dev["mean_fields"].copy(), "predicted_stddev_fields": dev["stddev_fields"].copy()}
+        out = {"predicted_mean_fields": np.zeros_like(self.field_images),
+               "predicted_stddev_fields": np.zeros_like(self.field_images)}
+        zeros = np.zeros(self.field_images.shape[1:])
+        for m, rec in enumerate(self.res_deblend):
+            if len(rec):
+                pos = DeblendField._positions(rec)
+                out["predicted_mean_fields"][m] = self._ctx.scene_composite(zeros, self._stack(rec, "output_images_mean"), pos)
+                out["predicted_stddev_fields"][m] = self._ctx.scene_composite(zeros, self._stack(rec, "output_images_stddev"), pos)
+        return out
+
+    def optimise_positions(self):
+        """Fit the sub-pixel shift of every row of every field in one engine call (position_optimization_fields) and write
+        it to the `shifts` column, as DeblendField.optimise_positions does.  Returns the list of recarrays."""
+        from debvader_amd.deblend_cutout.optimization import position_optimization_fields
+
+        self._need_pass()
+        res = self.res_deblend
+        field_ptr = np.concatenate([[0], np.cumsum([len(r) for r in res])]).astype(np.int64)
+        if field_ptr[-1] == 0:
+            return res
+        stamps = np.concatenate([self._stack(r, "output_images_mean") for r in res])
+        dist = np.concatenate([np.stack([r["galaxy_distances_to_center_x"], r["galaxy_distances_to_center_y"]], axis=1)
+                               for r in res]).astype(np.float64)
+        shifts = position_optimization_fields(self.field_images, stamps, dist, field_ptr, bound=3.0, ctx=self._ctx)
+        for m, rec in enumerate(res):
+            lo = int(field_ptr[m])
+            col = np.empty(len(rec), dtype=object)
+            for i in range(len(rec)):
+                col[i] = np.array([shifts[lo + i, 0], shifts[lo + i, 1]], dtype=np.float64)
+            rec["shifts"] = col
+        self._device_fields = None
+        return res

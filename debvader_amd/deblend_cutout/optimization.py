@@ -58,6 +58,35 @@ def position_optimization_batch(field_image, stamps, distances, bound=3.0, ctx=N
     return r["shifts"]
 
 
+def position_optimization_fields(field_images, stamps, distances, field_ptr, bound=3.0, ctx=None, max_iter=50,
+                                 return_details=False):
+    """position_optimization_batch for the galaxies of many fields in one engine call (dv_scene_fit_shifts_fields).
+
+    parameters:
+        field_images: (M, F, F, bands)
+        stamps: (N, cs, cs, bands) predicted images of the galaxies of all fields, field after field
+        distances: (N, 2) distances to the centre of each galaxy's own field, {row, column}
+        field_ptr: (M + 1,) - galaxies field_ptr[m]:field_ptr[m + 1] belong to field m
+    returns the (N, 2) shifts; with return_details, (shifts, details).  Every galaxy gets the shift
+    position_optimization_batch gives it on its own field, bit for bit.
+    """
+    f = np.asarray(field_images)
+    if f.ndim != 4 or f.shape[1] != f.shape[2]:
+        raise ValueError(f"expected square fields (M, F, F, bands), got {f.shape}")
+    if f.shape[3] <= R_BAND:
+        raise ValueError(f"the position fit uses band {R_BAND} (r); these fields have {f.shape[3]} band(s)")
+    stamps_r = _stamps_r(stamps)
+    dist = np.asarray(distances, dtype=np.float64).reshape(-1, 2)
+    if dist.shape[0] != stamps_r.shape[0]:
+        raise ValueError(f"{stamps_r.shape[0]} stamps but {dist.shape[0]} distances")
+    fp = E.check_field_ptr(field_ptr, f.shape[0], stamps_r.shape[0])
+    ctx = ctx or E.default_context()
+    r = ctx.scene_fit_shifts_fields(f[:, :, :, R_BAND], stamps_r, dist, fp, bound=bound, max_iter=max_iter)
+    if return_details:
+        return r["shifts"], {k: r[k] for k in ("objective", "iters", "status")}
+    return r["shifts"]
+
+
 def position_optimization(field_image, output_image_mean_padded, galaxy_distance_to_center):
     """
     Find shifts in the position of the deblended galaxy to minimize the mse between field_image

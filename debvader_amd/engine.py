@@ -103,6 +103,32 @@ def _i32_rows(a, what: str) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32).reshape(-1, 2)
 
 
+def check_field_ptr(field_ptr, n_fields: int, n_stamps: int) -> np.ndarray:
+    """The field_ptr of the many-field calls (dv_infer_fields*, dv_scene_fit_shifts_fields) as int64 (n_fields + 1,):
+    stamps field_ptr[m]:field_ptr[m + 1] belong to field m, so it starts at 0, never decreases and ends at n_stamps."""
+    fp = np.asarray(field_ptr)
+    if fp.dtype.kind not in "iu":
+        r = np.rint(np.asarray(fp, dtype=np.float64))
+        if fp.size and not np.array_equal(r, np.asarray(fp, dtype=np.float64)):
+            raise ValueError("field_ptr must be integers")
+        fp = r
+    fp = np.ascontiguousarray(fp, dtype=np.int64)
+    if fp.ndim != 1 or fp.shape[0] != int(n_fields) + 1:
+        raise ValueError(f"field_ptr must have one entry per field plus one ({int(n_fields) + 1}), got shape {fp.shape}")
+    if fp[0] != 0 or fp[-1] != int(n_stamps):
+        raise ValueError(f"field_ptr must start at 0 and end at the number of stamps ({int(n_stamps)}), got {fp[0]} .. {fp[-1]}")
+    if (np.diff(fp) < 0).any():
+        raise ValueError(f"field_ptr must not decrease (it does at field {int(np.argmax(np.diff(fp) < 0))})")
+    return fp
+
+
+def _check_fields(fields) -> np.ndarray:
+    fields = np.ascontiguousarray(fields, dtype=np.float64)
+    if fields.ndim != 4 or fields.shape[1] != fields.shape[2]:
+        raise ValueError(f"expected square fields (M, F, F, bands), got {fields.shape}")
+    return fields
+
+
 def check_detect_args(fields_r, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
                       workspace_bytes=0) -> np.ndarray:
     """Context.scene_detect's argument checks (before any GPU work); returns the fields as float64 (M, H, W)."""
@@ -399,6 +425,39 @@ class Context:
                                           n, stamps_r.shape[1], dist.ctypes.data_as(dp), float(bound), int(max_iter),
                                           out.ctypes.data_as(dp), obj.ctypes.data_as(dp), iters.ctypes.data_as(ip),
                                           status.ctypes.data_as(ip)))
+        return dict(shifts=out, objective=obj, iters=iters, status=status)
+
+    def scene_fit_shifts_fields(self, fields_r, stamps_r, distances, field_ptr, shifts=None, bound: float = 3.0,
+                                max_iter: int = 50) -> Dict[str, np.ndarray]:
+        """scene_fit_shifts for the galaxies of M fields in one engine call (dv_scene_fit_shifts_fields): fields_r (M, F, F),
+        stamps_r (N, cs, cs), distances (N, 2), field_ptr (M + 1,) - galaxies field_ptr[m]:field_ptr[m + 1] are fitted against
+        field m.  Same result dictionary; every galaxy gets what scene_fit_shifts gives it on its own field, bit for bit."""
+        fields_r = np.ascontiguousarray(fields_r, dtype=np.float64)
+        stamps_r = np.ascontiguousarray(stamps_r, dtype=np.float64)
+        dist = np.ascontiguousarray(distances, dtype=np.float64)
+        if fields_r.ndim != 3 or fields_r.shape[1] != fields_r.shape[2] or fields_r.shape[1] < 2:
+            raise ValueError(f"expected square r-band fields (M, F, F), got {fields_r.shape}")
+        if stamps_r.ndim != 3 or stamps_r.shape[1] != stamps_r.shape[2] or stamps_r.shape[1] > fields_r.shape[1]:
+            raise ValueError(f"expected square r-band stamps (N, cs, cs) with cs <= {fields_r.shape[1]}, got {stamps_r.shape}")
+        n = stamps_r.shape[0]
+        if dist.shape != (n, 2):
+            raise ValueError(f"expected distances ({n}, 2), got {dist.shape}")
+        fp = check_field_ptr(field_ptr, fields_r.shape[0], n)
+        out = np.zeros((n, 2), np.float64) if shifts is None else np.array(shifts, dtype=np.float64, order="C", copy=True)
+        if out.shape != (n, 2):
+            raise ValueError(f"expected shifts ({n}, 2), got {out.shape}")
+        if not (np.isfinite(bound) and bound >= 0) or int(max_iter) < 0:
+            raise ValueError(f"bound must be finite and >= 0, max_iter >= 0 (got {bound}, {max_iter})")
+        obj = np.zeros(n, np.float64)
+        iters = np.zeros(n, np.int32)
+        status = np.zeros(n, np.int32)
+        if n:
+            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+            check(lib.dv_scene_fit_shifts_fields(self._h, fields_r.ctypes.data_as(dp), fields_r.shape[0], fields_r.shape[1],
+                                                 stamps_r.ctypes.data_as(dp), fp.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                                 stamps_r.shape[1], dist.ctypes.data_as(dp), float(bound), int(max_iter),
+                                                 out.ctypes.data_as(dp), obj.ctypes.data_as(dp), iters.ctypes.data_as(ip),
+                                                 status.ctypes.data_as(ip)))
         return dict(shifts=out, objective=obj, iters=iters, status=status)
 
     CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
@@ -797,6 +856,83 @@ class Engine:
                                              places.ctypes.data_as(C.POINTER(C.c_int32)), N, int(seed),
                                              out["mean_field"].ctypes.data_as(dp), out["stddev_field"].ctypes.data_as(dp),
                                              opt("residual_field"), opt("mse_center")))
+        return out
+
+    # -- many fields in one call -------------------------------------------
+    def _fields_bufs(self, N, want, out):
+        bufs = {}
+        for k in ("loc", "scale", "mu", "zstd", "z"):
+            shape = (N,) + self.stamp_shape if k in ("loc", "scale") else (N, self.latent)
+            if k not in want:
+                bufs[k] = None
+            elif out is not None and k in out:
+                if out[k].shape != shape or out[k].dtype != np.float32 or not out[k].flags.c_contiguous:
+                    raise ValueError(f"out[{k!r}] must be a C-contiguous float32 array of shape {shape}")
+                bufs[k] = out[k]
+            else:
+                bufs[k] = _host_pool.empty(shape, np.float32)
+        return bufs
+
+    def infer_fields(self, fields, starts, field_ptr, seed=0, want=("loc", "scale"), out=None) -> Dict[str, np.ndarray]:
+        """infer_cutouts() for the cutouts of M fields (M, F, F, bands) in one engine call (dv_infer_fields): rows
+        field_ptr[m]:field_ptr[m + 1] of `starts` are windows of field m.  The N stamps of all fields form one list that runs
+        through the network in full chunks, whatever field a stamp belongs to; stamp i draws noise row i.  Bit-identical to
+        infer() on the concatenated cutouts with the same seed."""
+        fields = _check_fields(fields)
+        starts = _i32_rows(starts, "cutout starts")
+        N = starts.shape[0]
+        fp = check_field_ptr(field_ptr, fields.shape[0], N)
+        bufs = self._fields_bufs(N, want, out)
+        check(lib.dv_infer_fields(self._h, fields.ctypes.data_as(C.POINTER(C.c_double)), fields.shape[0], fields.shape[1],
+                                  fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                  fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed), _fp(bufs["loc"]), _fp(bufs["scale"]),
+                                  _fp(bufs["mu"]), _fp(bufs["zstd"]), _fp(bufs["z"])))
+        return {k: v for k, v in bufs.items() if v is not None}
+
+    def infer_fields_keep(self, fields, starts, field_ptr, seed=0, want=("loc", "scale")) -> Dict[str, np.ndarray]:
+        """infer_fields() for a caller that also needs the float64 cutouts (dv_infer_fields_keep): the wanted outputs plus
+        "cutouts" (N,) + stamp shape, assembled on the host from the fields while the GPU runs the forward passes."""
+        fields = _check_fields(fields)
+        starts = _i32_rows(starts, "cutout starts")
+        N = starts.shape[0]
+        fp = check_field_ptr(field_ptr, fields.shape[0], N)
+        bufs = self._fields_bufs(N, want, None)
+        cut = _host_pool.empty((N,) + self.stamp_shape, np.float64)
+        check(lib.dv_infer_fields_keep(self._h, fields.ctypes.data_as(C.POINTER(C.c_double)), fields.shape[0],
+                                       fields.shape[1], fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed), _fp(bufs["loc"]),
+                                       _fp(bufs["scale"]), _fp(bufs["mu"]), _fp(bufs["zstd"]), _fp(bufs["z"]),
+                                       cut.ctypes.data_as(C.POINTER(C.c_double))))
+        res = {k: v for k, v in bufs.items() if v is not None}
+        res["cutouts"] = cut
+        return res
+
+    def infer_fields_composite(self, fields, starts, places, field_ptr, seed=0, residual=True,
+                               mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_cutouts_composite() for M fields in one engine call (dv_infer_fields_composite): returns {"mean_fields",
+        "stddev_fields", ["residual_fields"]} (M, F, F, bands) and ["mse_center"] (N,).  A field's results are the sums of
+        its own stamps in object order - the bits infer_cutouts_composite gives for the same stamps and noise rows; a field
+        without stamps gets zeros and its residual is the field."""
+        fields = _check_fields(fields)
+        starts = _i32_rows(starts, "cutout starts")
+        places = _i32_rows(places, "stamp placements")
+        if places.shape != starts.shape:
+            raise ValueError(f"{starts.shape[0]} cutout starts but {places.shape[0]} placements")
+        N = starts.shape[0]
+        fp = check_field_ptr(field_ptr, fields.shape[0], N)
+        dp = C.POINTER(C.c_double)
+        out = {"mean_fields": np.empty(fields.shape, np.float64), "stddev_fields": np.empty(fields.shape, np.float64)}
+        if residual:
+            out["residual_fields"] = np.empty(fields.shape, np.float64)
+        if mse_center:
+            out["mse_center"] = np.empty((N,), np.float64)
+        opt = lambda k: out[k].ctypes.data_as(dp) if k in out else None
+        check(lib.dv_infer_fields_composite(self._h, fields.ctypes.data_as(dp), fields.shape[0], fields.shape[1],
+                                            fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            places.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed),
+                                            out["mean_fields"].ctypes.data_as(dp), out["stddev_fields"].ctypes.data_as(dp),
+                                            opt("residual_fields"), opt("mse_center")))
         return out
 
     def infer_cutouts_stream(self, field, starts, consumer, seed=0):

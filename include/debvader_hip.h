@@ -255,11 +255,33 @@ int dv_infer_cutouts_stream(dv_model* m, const double* field, int32_t F, int32_t
  * places[i] is int((F - cs) / 2) + the galaxy's distance to the field centre, as the reference pads and shifts
  * (field_deblender.py:70,130-160); parts of a stamp that leave the field are dropped (scipy.ndimage.shift, mode
  * "constant").  mse_center (optional, [N]) receives each stamp's centre-10x10 MSE against its cutout (:323-327), the input
- * of the reference's quality cut.  Only the F x F x bands float64 fields (and N doubles) travel back.  Sums are in float64
- * and in object order: bit-identical to dv_scene_composite on the stamps dv_infer_cutouts returns for the same seed. */
+ * of the reference's quality cut, summed in numpy's pairwise order: the bits of the reference's host formula.  Only the
+ * F x F x bands float64 fields (and N doubles) travel back.  Sums are in float64 and in object order: bit-identical to dv_scene_composite on the stamps dv_infer_cutouts returns for the same seed. */
 int dv_infer_cutouts_composite(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts,
                                const int32_t* places, int64_t N, uint64_t seed, double* mean_field, double* stddev_field,
                                double* residual_field, double* mse_center);
+
+/* ---- many fields in one call ----
+ * The batched forms of dv_infer_cutouts, _keep and _composite for a survey of many small fields: fields [M][F][F][nb]
+ * (float64, host), starts [N][2], and field_ptr [M + 1] (non-decreasing, field_ptr[0] = 0, field_ptr[M] = N): stamps
+ * field_ptr[m] .. field_ptr[m + 1] are cut from field m, every window inside its field.  Stamps are numbered 0 .. N-1
+ * over all fields; that number is the Philox row of a stamp's noise and the row of its results, and the list runs through
+ * the network in the chunks dv_infer makes for N stamps, whatever field a stamp belongs to.  Results are bit-identical to
+ * dv_infer_f64 on the concatenated cutouts with the same seed, and each field's composited results to
+ * dv_scene_composite on its own stamps in object order: a field never sees another field's stamps.  N < 2^31.
+ * The fields are uploaded in groups sized against free device memory (DV_FIELDS_GROUP_MB lowers the group size); a
+ * single field that does not fit, or a chunk whose stamps come from more fields than fit, is refused (DV_E_NOMEM).
+ * dv_infer_fields_composite: places [N][2] as in dv_infer_cutouts_composite; mean_fields / stddev_fields / optional
+ * residual_fields [M][F][F][nb], optional mse_center [N].  A field without stamps gets zeros and residual = field. */
+int dv_infer_fields(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                    const int64_t* field_ptr, int64_t N, uint64_t seed, float* loc, float* scale, float* mu, float* zstd,
+                    float* z);
+int dv_infer_fields_keep(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                         const int64_t* field_ptr, int64_t N, uint64_t seed, float* loc, float* scale, float* mu,
+                         float* zstd, float* z, double* cutouts);
+int dv_infer_fields_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                              const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                              double* mean_fields, double* stddev_fields, double* residual_fields, double* mse_center);
 
 /* Monte-Carlo epistemic uncertainty: encode each stamp once, decode it `nsamples` times with fresh eps, return the
  * mean and the standard deviation (ddof 0) of the predicted means over the samples.  Replaces the per-object loop
@@ -296,6 +318,12 @@ int dv_scene_composite(dv_ctx* ctx, double* field, int32_t F, int32_t nb, const 
 int dv_scene_fit_shifts(dv_ctx* ctx, const double* field_r, int32_t F, const double* stamps_r, int32_t N, int32_t cs,
                         const double* dist, double bound, int32_t max_iter, double* shifts_inout, double* objective,
                         int32_t* iters, int32_t* status);
+/* dv_scene_fit_shifts for M fields: fields_r [M][F][F], galaxies field_ptr[m] .. field_ptr[m + 1] (field_ptr as in
+ * dv_infer_fields) are fitted against field m.  Every galaxy gets what dv_scene_fit_shifts gives it on its own field, bit
+ * for bit.  Fields are uploaded in groups sized against free device memory. */
+int dv_scene_fit_shifts_fields(dv_ctx* ctx, const double* fields_r, int32_t M, int32_t F, const double* stamps_r,
+                               const int64_t* field_ptr, int64_t N, int32_t cs, const double* dist, double bound,
+                               int32_t max_iter, double* shifts_inout, double* objective, int32_t* iters, int32_t* status);
 /* dv_scene_detect: source detection (reference: detect/detection.py, which runs sep on band 2) on M fields of one band,
  * fields [M][H][W] float64.  SExtractor's method (Bertin & Arnouts 1996) with the rules of DESIGN.md section 7e, float64
  * throughout: sigma-clipped mesh background (exact medians), median-filtered meshes, natural-cubic-spline interpolation,

@@ -1,0 +1,144 @@
+"""Deblending many small fields: one engine call for all of them (DeblendFieldBatch) against a loop of single-field calls
+(DeblendField), on one GPU.  M synthetic six-band fields of F px (Gaussian noise plus ~40 Gaussian galaxies per 259 px, some
+blended, as tools/detect_bench.py makes them), detected once with detect_objects_batch; then, alternating, after a warm-up,
+
+    loop :  for every field  DeblendField(net, field).deblend_field(d, on_device=True)
+    batch:  DeblendFieldBatch(net, fields).deblend_fields(d, on_device=True)
+
+for both engine dtypes, --repeat times each; stamps/s and fields/s per repetition, the median and the spread (max - min
+over the median).  Also, on --default-fields fields, the default (stamps returned) mode of both and optimise_positions().
+GPU only; prints a table and one JSON line.
+
+    python tools/fields_bench.py [--fields 1024] [--size 259] [--repeat 5] [--max-batch 8192]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from debvader_amd.deblend.field_deblender import DeblendField, DeblendFieldBatch  # noqa: E402
+from debvader_amd.detect.detection import detect_objects_batch  # noqa: E402
+from debvader_amd.model import model  # noqa: E402
+
+ARCH = dict(input_shape=(59, 59, 6), latent_dim=32, filters=[32, 64, 128, 256], kernels=[3, 3, 3, 3])
+
+
+def _field(rng, F, n, nb=6):
+    f = np.zeros((F, F))
+    ys, xs = rng.uniform(0, F, n), rng.uniform(0, F, n)
+    sig, amp = rng.uniform(1.2, 4.0, n), rng.uniform(3.0, 60.0, n)
+    for y, x, s, a in zip(ys, xs, sig, amp):
+        r0, r1 = max(0, int(y - 5 * s)), min(F, int(y + 5 * s) + 1)
+        c0, c1 = max(0, int(x - 5 * s)), min(F, int(x + 5 * s) + 1)
+        yy, xx = np.mgrid[r0:r1, c0:c1]
+        f[r0:r1, c0:c1] += a * np.exp(-0.5 * ((yy - y) ** 2 + (xx - x) ** 2) / s ** 2)
+    return f[:, :, None] * rng.uniform(0.4, 1.0, nb) + rng.normal(0, 1.0, (F, F, nb))
+
+
+def _loop(net, fields, dists, on_device):
+    n = 0
+    for m in range(len(fields)):
+        r = DeblendField(net, fields[m:m + 1]).deblend_field(dists[m], on_device=on_device)
+        n += 0 if isinstance(r, dict) else len(r)
+    return n
+
+
+def _batch(net, fields, dists, on_device):
+    return sum(len(r) for r in DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=on_device))
+
+
+def _alternate(fa, fb, repeat):
+    ta, tb, n = [], [], 0
+    for _ in range(repeat):
+        for fn, ts in ((fa, ta), (fb, tb)):
+            t0 = time.perf_counter()
+            n = fn()
+            ts.append(time.perf_counter() - t0)
+    return np.array(ta), np.array(tb), n
+
+
+def _row(label, t, stamps, fields):
+    med = float(np.median(t))
+    return (f"{label:<34s} {stamps / med:12.0f} stamps/s {fields / med:10.1f} fields/s   median {1e3 * med:9.1f} ms   "
+            f"spread {100 * (t.max() - t.min()) / med:5.1f} %   runs " + " ".join(f"{1e3 * x:.1f}" for x in t))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--fields", type=int, default=1024)
+    ap.add_argument("--size", type=int, default=259)
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--max-batch", type=int, default=8192)
+    ap.add_argument("--default-fields", type=int, default=64)
+    a = ap.parse_args()
+    rng = np.random.default_rng(0)
+    F, M = a.size, a.fields
+    base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
+    fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    import io
+    from contextlib import redirect_stdout
+    quiet = io.StringIO()                      # the classes print the reference's notes about dropped galaxies
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat}
+    dists = None
+    for dtype in ("float32", "bf16"):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.asarray(d, dtype=np.float64).reshape(-1, 2) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections "
+                  f"({sum(len(d) for d in dists) / M:.1f} per field); max_batch {a.max_batch}")
+        with redirect_stdout(quiet):
+            _loop(net, fields[:8], dists[:8], True)                                   # warm-up
+            _batch(net, fields, dists, True)
+            tl, tb, n = _alternate(lambda: _loop(net, fields, dists, True), lambda: _batch(net, fields, dists, True), a.repeat)
+        print(_row(f"{dtype} on_device loop", tl, n, M))
+        print(_row(f"{dtype} on_device batch", tb, n, M))
+        factor = float(np.median(tl) / np.median(tb))
+        print(f"{dtype} on_device batch / loop: {factor:.2f} x  (slowest batch {1e3 * tb.max():.1f} ms, fastest loop "
+              f"{1e3 * tl.min():.1f} ms)")
+        result[dtype] = {"stamps": n, "loop_ms": [round(1e3 * x, 2) for x in tl], "batch_ms": [round(1e3 * x, 2) for x in tb],
+                         "factor": round(factor, 3), "batch_stamps_per_s": round(n / float(np.median(tb)), 1),
+                         "loop_stamps_per_s": round(n / float(np.median(tl)), 1)}
+        # default mode (stamps returned) and the position fit, on fewer fields: 334 KB of results per stamp on the host
+        Md = min(M, a.default_fields)
+        with redirect_stdout(quiet):
+            _batch(net, fields[:Md], dists[:Md], False)
+            tl, tb, n = _alternate(lambda: _loop(net, fields[:Md], dists[:Md], False),
+                                   lambda: _batch(net, fields[:Md], dists[:Md], False), a.repeat)
+        print(_row(f"{dtype} default loop ({Md} fields)", tl, n, Md))
+        print(_row(f"{dtype} default batch ({Md} fields)", tb, n, Md))
+        result[dtype]["default"] = {"fields": Md, "stamps": n, "loop_ms": [round(1e3 * x, 2) for x in tl],
+                                    "batch_ms": [round(1e3 * x, 2) for x in tb]}
+        if dtype == "float32":
+            with redirect_stdout(quiet):
+                db = DeblendFieldBatch(net, fields[:Md])
+                db.deblend_fields(dists[:Md])
+                singles = [DeblendField(net, fields[m:m + 1]) for m in range(Md)]
+
+                def fit_loop():
+                    for m in range(Md):
+                        if len(db.res_deblend[m]):
+                            singles[m].optimise_positions(db.res_deblend[m])
+                    return n
+
+                def fit_batch():
+                    db.optimise_positions()
+                    return n
+
+                fit_batch()
+                tl, tb, _ = _alternate(fit_loop, fit_batch, a.repeat)
+            print(_row(f"optimise_positions loop ({Md} fields)", tl, n, Md))
+            print(_row(f"optimise_positions batch ({Md} fields)", tb, n, Md))
+            result["optimise_positions"] = {"fields": Md, "galaxies": n, "loop_ms": [round(1e3 * x, 2) for x in tl],
+                                            "batch_ms": [round(1e3 * x, 2) for x in tb]}
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
