@@ -1855,6 +1855,13 @@ struct TinyCall {          // scope of one public inference call of at most 16 s
   ~TinyCall() { m->tiny_call = false; }
 };
 
+struct LongCallKernels {   // scope inside a TinyCall in which kernels are selected as in a call of more than 16 stamps
+  dv_model* m;
+  bool was_tiny;
+  explicit LongCallKernels(dv_model* mm) : m(mm), was_tiny(mm->tiny_call) { m->tiny_call = false; }
+  ~LongCallKernels() { m->tiny_call = was_tiny; }
+};
+
 // DV_EXP_NO_A=<min size> (a MEASUREMENT switch, results are wrong): training forwards of the layers at least that many
 // pixels wide store the pre-activation only (epilogue 1: no PReLU, no activation store) - the upper bound of what "store u
 // only"  can save before any consumer pays for applying PReLU on load
@@ -2805,6 +2812,7 @@ static int stage_host_batch(dv_model* m, const float* x, int nb) {
 struct InferPipe {
   int cap = 0;                      // stamps per buffer
   float *hin[2] = {}, *hloc[3] = {}, *hscale[3] = {}, *hsmall[3] = {};      // pinned host (outputs: three deep)
+  float* heps[3] = {};              // pinned host, third image slot of the ring: Monte-Carlo std stamps (dv_infer_fields_mc_keep only)
   float *din[2] = {}, *dloc[2] = {}, *dscale[2] = {}, *dsmall[2] = {};      // device
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_h2d[2] = {}, ev_comp[2] = {}, ev_d2h[3] = {};
@@ -2816,6 +2824,7 @@ static void pipe_free(InferPipe* p) {
   if (!p) return;
   for (int b = 0; b < 3; ++b) {
     (void)hipHostFree(p->hloc[b]); (void)hipHostFree(p->hscale[b]); (void)hipHostFree(p->hsmall[b]);
+    (void)hipHostFree(p->heps[b]);
     if (p->ev_d2h[b]) (void)hipEventDestroy(p->ev_d2h[b]);
   }
   for (int b = 0; b < 2; ++b) {
@@ -2847,6 +2856,21 @@ static int pipe_host_buffers(dv_model* m, InferPipe* p) {
     }
   }
   p->host_ok = true;
+  return OK;
+}
+
+// the third image slot of the pinned ring, allocated by the first call that sends Monte-Carlo std stamps to the host
+static int pipe_eps_buffers(dv_model* m, InferPipe* p) {
+  const Arch& A = m->A;
+  const size_t img = (size_t)p->cap * A.H * A.H * A.C * sizeof(float);
+  for (int b = 0; b < 3; ++b) {
+    if (p->heps[b]) continue;
+    hipError_t e = hipHostMalloc((void**)&p->heps[b], img, hipHostMallocDefault);
+    if (e != hipSuccess) {
+      p->heps[b] = nullptr;
+      return hip_fail(e, "hipHostMalloc(pinned transfer ring, epistemic slot)", __FILE__, __LINE__);
+    }
+  }
   return OK;
 }
 
@@ -2986,12 +3010,53 @@ struct CompositeSink {
   double *mean_f, *std_f, *res_f;   // device [F][F][nb]; res_f may be null
   const int* places;                // device [N][2]: field position (row, col) of each stamp's top-left corner
   double* mse;                      // device [N] centre MSE of every stamp against its cutout, or null
+  double* eps_f = nullptr;          // device [F][F][nb]: sum of the Monte-Carlo std stamps (McStage), or null
+  double* eps_norm = nullptr;       // device [N]: sum(std[:, :, 2]) / sum(mean[:, :, 2]) of every stamp (McStage), or null
 };
+
+// Monte-Carlo stage of the pipeline (dv_infer_fields_mc_*): behind every chunk's forward pass, nsamples more
+// decodes of the encoder output that pass left in the workspace, folded into per-pixel statistics
+struct McStage {
+  int nsamples;
+  uint64_t seed;
+  float* eps_out;                   // host [N][cs][cs][nb] std stamps (keep form), or null
+};
+
+// The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
+// workspace takes - the decoder runs on nb * reps rows, row r being sample k + r / nb of stamp r % nb (the sampler reads that
+// stamp's t and draws the noise sample k + r / nb would get in a pass of its own: Philox (seed + sample, row0 + stamp)), and
+// the per-stamp statistics fold the samples in order.  A handful of objects with 100 samples each - the per-field use of the
+// reference - is one or two decoder passes instead of 100.  Leaves the mean in m->gA and the standard deviation in m->gB
+// (the two gradient ping-pong buffers, unused during inference).
+static int mc_decode_stats(dv_model* m, int nb, int nsamples, uint64_t seed, unsigned row0) {
+  const Arch& A = m->A;
+  hipStream_t s = m->ctx->stream;
+  const size_t stamp = (size_t)A.H * A.H * A.C;
+  float* mean = m->gA;
+  float* m2 = m->gB;
+  const int per_pass = std::max(1, m->Bc / nb);
+  for (int k = 0; k < nsamples; k += per_pass) {
+    const int reps = std::min(per_pass, nsamples - k);
+    int nblk = 0;
+    DV_TRY(sampler_forward(m, nb * reps, true, seed + (uint64_t)k, (unsigned)m->ctx->rank, row0, false, reps > 1 ? nb : 0));
+    DV_TRY(decoder_forward(m, nb * reps, false));
+    DV_TRY(head_lane(m, nullptr, nullptr, 0, nb * reps, nb * reps, false, true, 0, &nblk));
+    // normalise=True: the recipe is np.std(deblend(net, [stamp]*100, normalise=True)[0], axis=0), i.e. the statistics
+    // of the DENORMALISED means - each decoded pass goes back through sinh(arctanh(.)) before it is folded in
+    if (m->normalise) DV_TRY(launch_normalise(m->loc, (long)nb * reps * stamp, true, s));
+    if (reps > 1)
+      DV_TRY(launch_welford_update_multi(m->loc, mean, m2, (long)nb * stamp, reps, k, s));
+    else
+      DV_TRY(launch_welford_update(m->loc, mean, m2, ((long)(nb * stamp) + 3) & ~3L, k, s));   // buffers carry slack
+  }
+  DV_TRY(launch_welford_finish(m2, ((long)(nb * stamp) + 3) & ~3L, nsamples, s));
+  return OK;
+}
 
 static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, const float* eps, uint64_t seed,
                            float* loc, float* scale, float* mu, float* zstd, float* z, const CutoutSrc* cut = nullptr,
                            dv_chunk_fn sink = nullptr, void* sink_user = nullptr, const CompositeSink* comp = nullptr,
-                           const CutoutKeep* keep = nullptr) {
+                           const CutoutKeep* keep = nullptr, const McStage* mc = nullptr) {
   const Arch& A = m->A;
   hipStream_t s = m->ctx->stream;
   const size_t stamp = (size_t)A.H * A.H * A.C;
@@ -2999,6 +3064,8 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
   const int64_t row0 = cut ? cut->row0 : 0;
   InferPipe* p = nullptr;
   DV_TRY(pipe_get(m, chunk, &p, !(comp && cut)));
+  float* eps_out = mc ? mc->eps_out : nullptr;
+  if (eps_out) DV_TRY(pipe_eps_buffers(m, p));
   const int64_t K = (N + chunk - 1) / chunk;
   const int d = A.d;
   auto finish = [&](int64_t k) -> int {       // stage D: pinned -> caller's arrays
@@ -3019,6 +3086,7 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
     }
     if (loc) host_copy(loc + o * stamp, p->hloc[b], nb * stamp, false, p->threads);
     if (scale) host_copy(scale + o * stamp, p->hscale[b], nb * stamp, false, p->threads);
+    if (eps_out) host_copy(eps_out + o * stamp, p->heps[b], nb * stamp, false, p->threads);
     if (mu) memcpy(mu + o * d, p->hsmall[b], (size_t)nb * d * sizeof(float));
     if (zstd) memcpy(zstd + o * d, p->hsmall[b] + (size_t)chunk * d, (size_t)nb * d * sizeof(float));
     if (z) memcpy(z + o * d, p->hsmall[b] + (size_t)2 * chunk * d, (size_t)nb * d * sizeof(float));
@@ -3094,6 +3162,22 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
       DV_TRY(copy_rows(p->dsmall[b] + (size_t)chunk * d, d, m->zstd, A.dp, d, nb, hipMemcpyDeviceToDevice, s));
     if (z)
       DV_TRY(copy_rows(p->dsmall[b] + (size_t)2 * chunk * d, d, m->z, A.dp, d, nb, hipMemcpyDeviceToDevice, s));
+    if (mc) {
+      // Monte-Carlo stage: dv_infer_mc's decodes on the encoder output the forward pass above left in m->t (no second
+      // encoder pass, nothing staged from the host); sample j of stamp i draws Philox (mc seed + j, global stamp number), what
+      // dv_infer_mc draws for row i of the whole stamp list.  The std stamps stay in m->gB for this chunk's sinks on the
+      // output stream, so the statistics of chunk k wait until the sinks of chunk k - 1 have read theirs (they finished
+      // during this chunk's forward pass).
+      if (k >= 1) DV_HIP(hipStreamWaitEvent(s, p->ev_d2h[(k - 1) % 3], 0));
+      LongCallKernels lk(m);             // dv_infer_mc selects kernels as a long call does, whatever N is
+      if (lk.was_tiny) {
+        // a call of at most 16 stamps ran its forward pass with the small-call kernels (K sliced over workgroups), whose t
+        // differs from dv_infer_mc's in the last bits: encode these few stamps once more the way dv_infer_mc does
+        DV_TRY(bn_prepare(m, p->din[b], nullptr, 0, nb, nb, false, false));
+        DV_TRY(encoder_forward(m, p->din[b], nullptr, 0, nb, false));
+      }
+      DV_TRY(mc_decode_stats(m, nb, mc->nsamples, mc->seed, (unsigned)(row0 + o)));
+    }
     if (trace) DV_HIP(hipEventRecord(tev[6 * k + 3], s));
     DV_HIP(hipEventRecord(p->ev_comp[b], s));
     // stage C: device -> pinned (three-deep ring) on the second copy stream
@@ -3111,17 +3195,20 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
         const int fy0 = cut->sfield_h[o], fy1 = cut->sfield_h[o + nb - 1];
         DV_TRY(launch_scene_composite_chunk(comp->mean_f, comp->std_f, comp->res_f, cut->F, cut->nb, p->dloc[b], p->dscale[b],
                                             comp->places + 2 * o, nb, cut->cs, p->s_out, cut->fptr, cut->f0, fy0,
-                                            fy1 - fy0 + 1, (long)(row0 + o)));
+                                            fy1 - fy0 + 1, (long)(row0 + o), comp->eps_f, comp->eps_f ? m->gB : nullptr));
       } else {
         DV_TRY(launch_scene_composite_chunk(comp->mean_f, comp->std_f, comp->res_f, cut->F, cut->nb, p->dloc[b], p->dscale[b],
                                             comp->places + 2 * o, nb, cut->cs, p->s_out));
       }
+      if (comp->eps_norm)
+        DV_TRY(launch_scene_eps_norm(m->gB, p->dloc[b], nb, cut->cs, cut->nb, comp->eps_norm + o, p->s_out));
       if (comp->mse)
         DV_TRY(launch_scene_center_mse(cut->field, cut->F, cut->nb, cut->starts + 2 * o, p->dloc[b], nb, cut->cs,
                                        comp->mse + o, p->s_out, cut->sfield ? cut->sfield + o : nullptr, cut->f0));
     }
     if (loc || sink) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (scale || sink) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
+    if (eps_out) DV_HIP(hipMemcpyAsync(p->heps[h], m->gB, nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (mu || zstd || z)
       DV_HIP(hipMemcpyAsync(p->hsmall[h], p->dsmall[b], (size_t)chunk * 3 * d * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (trace) DV_HIP(hipEventRecord(tev[6 * k + 5], p->s_out));
@@ -4484,11 +4571,13 @@ int dv_infer_cutouts_stream(dv_model* m, const double* field, int32_t F, int32_t
 struct FieldsOut {                  // result fields of dv_infer_fields_composite, host [M][F][F][nb]; null otherwise
   double *mean = nullptr, *stddev = nullptr, *residual = nullptr, *mse = nullptr;
   const int32_t* places = nullptr;
+  double *epistemic = nullptr, *eps_norm = nullptr;   // dv_infer_fields_mc_composite: [M][F][F][nb] and [N]
 };
 
 static int infer_fields_impl(dv_model* m, const char* who, const double* fields, int32_t M, int32_t F, int32_t nb,
                              const int32_t* starts, const int64_t* field_ptr, int64_t N, uint64_t seed, float* loc,
-                             float* scale, float* mu, float* zstd, float* z, double* cutouts, const FieldsOut* fo) {
+                             float* scale, float* mu, float* zstd, float* z, double* cutouts, const FieldsOut* fo,
+                             const McStage* mc = nullptr) {
   if (!m || !field_ptr || M < 0 || N < 0 || F < 1 || (M > 0 && !fields) || (N > 0 && !starts)) return DV_E_INVALID;
   const Arch& A = m->A;
   const int cs = A.H;
@@ -4537,6 +4626,7 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
       if (field_ptr[f + 1] == field_ptr[f]) {
         memset(fo->mean + (size_t)f * felems, 0, fb);
         memset(fo->stddev + (size_t)f * felems, 0, fb);
+        if (fo->epistemic) memset(fo->epistemic + (size_t)f * felems, 0, fb);
         if (fo->residual) memcpy(fo->residual + (size_t)f * felems, fields + (size_t)f * felems, fb);
       }
   if (N == 0) return DV_OK;
@@ -4549,8 +4639,9 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
   DV_TRY(pipe_get(m, chunk, &pipe, fo == nullptr));   // before the budget below: the pipeline's buffers come first
 
   // fields per group: what free memory holds beside the per-stamp tables; DV_FIELDS_GROUP_MB lowers it
-  const size_t per_field = fb * (fo ? (fo->residual ? 4 : 3) : 1);
-  const size_t tables = (size_t)N * (5 * sizeof(int) + sizeof(double)) + ((size_t)M + 1) * sizeof(int);
+  // (with the Monte-Carlo estimate a resident field carries one more result field, a stamp one more scalar)
+  const size_t per_field = fb * (fo ? (fo->residual ? 4 : 3) + (fo->epistemic ? 1 : 0) : 1);
+  const size_t tables = (size_t)N * (5 * sizeof(int) + sizeof(double) * (fo && fo->eps_norm ? 2 : 1)) + ((size_t)M + 1) * sizeof(int);
   size_t free_b = 0, total_b = 0;
   DV_HIP(hipMemGetInfo(&free_b, &total_b));
   size_t budget = free_b / 10 * 8;
@@ -4588,13 +4679,14 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
     k = k1;
   }
 
-  double *fdev = nullptr, *mf = nullptr, *sf = nullptr, *rf = nullptr, *mse = nullptr;
+  double *fdev = nullptr, *mf = nullptr, *sf = nullptr, *rf = nullptr, *mse = nullptr, *ef = nullptr, *en = nullptr;
   int *sdev = nullptr, *pdev = nullptr, *sfdev = nullptr, *fpdev = nullptr;
   int st = OK;
   auto cleanup = [&]() {
     if (st != OK && pipe->s_out) (void)hipStreamSynchronize(pipe->s_out);   // nothing may still read these
     if (st != OK && pipe->s_in) (void)hipStreamSynchronize(pipe->s_in);
     (void)hipFree(fdev); (void)hipFree(mf); (void)hipFree(sf); (void)hipFree(rf); (void)hipFree(mse);
+    (void)hipFree(ef); (void)hipFree(en);
     (void)hipFree(sdev); (void)hipFree(pdev); (void)hipFree(sfdev); (void)hipFree(fpdev);
   };
 #define FF_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
@@ -4605,6 +4697,8 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
     FF_HIP(hipMalloc((void**)&sf, (size_t)gmax * fb));
     if (fo->residual) FF_HIP(hipMalloc((void**)&rf, (size_t)gmax * fb));
     if (fo->mse) FF_HIP(hipMalloc((void**)&mse, (size_t)N * sizeof(double)));
+    if (fo->epistemic) FF_HIP(hipMalloc((void**)&ef, (size_t)gmax * fb));
+    if (fo->eps_norm) FF_HIP(hipMalloc((void**)&en, (size_t)N * sizeof(double)));
     FF_HIP(hipMalloc((void**)&pdev, sb));
     FF_HIP(hipMemcpyAsync(pdev, fo->places, sb, hipMemcpyHostToDevice, s));
   }
@@ -4623,11 +4717,13 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
     if (fo) {
       FF_HIP(hipMemsetAsync(mf, 0, ng * fb, s));
       FF_HIP(hipMemsetAsync(sf, 0, ng * fb, s));
+      if (ef) FF_HIP(hipMemsetAsync(ef, 0, ng * fb, s));
       if (rf) FF_HIP(hipMemcpyAsync(rf, fdev, ng * fb, hipMemcpyDeviceToDevice, s));
       if (g.f0 == prev_last) {
         // the first field's earlier stamps were composited with the previous group: go on from those sums
         FF_HIP(hipMemcpyAsync(mf, fo->mean + goff, fb, hipMemcpyHostToDevice, s));
         FF_HIP(hipMemcpyAsync(sf, fo->stddev + goff, fb, hipMemcpyHostToDevice, s));
+        if (ef) FF_HIP(hipMemcpyAsync(ef, fo->epistemic + goff, fb, hipMemcpyHostToDevice, s));
         if (rf) FF_HIP(hipMemcpyAsync(rf, fo->residual + goff, fb, hipMemcpyHostToDevice, s));
       }
     }
@@ -4642,9 +4738,14 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
     cut.chunk = chunk;
     CutoutKeep keep{fields, starts + 2 * r0, cutouts ? cutouts + r0 * stamp : nullptr, sfield.data() + r0};
     CompositeSink comp{mf, sf, rf, pdev ? pdev + 2 * r0 : nullptr, mse ? mse + r0 : nullptr};
+    comp.eps_f = ef;
+    comp.eps_norm = en ? en + r0 : nullptr;
+    McStage mcg{0, 0, nullptr};
+    if (mc) mcg = McStage{mc->nsamples, mc->seed, mc->eps_out ? mc->eps_out + r0 * stamp : nullptr};
     st = infer_pipelined(m, nullptr, false, n, nullptr, seed, loc ? loc + r0 * stamp : nullptr,
                          scale ? scale + r0 * stamp : nullptr, mu ? mu + r0 * d : nullptr, zstd ? zstd + r0 * d : nullptr,
-                         z ? z + r0 * d : nullptr, &cut, nullptr, nullptr, fo ? &comp : nullptr, cutouts ? &keep : nullptr);
+                         z ? z + r0 * d : nullptr, &cut, nullptr, nullptr, fo ? &comp : nullptr, cutouts ? &keep : nullptr,
+                         mc ? &mcg : nullptr);
     if (st != OK) {
       (void)hipStreamSynchronize(s);
       cleanup();
@@ -4653,6 +4754,7 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
     if (fo) {
       FF_HIP(hipMemcpyAsync(fo->mean + goff, mf, ng * fb, hipMemcpyDeviceToHost, s));
       FF_HIP(hipMemcpyAsync(fo->stddev + goff, sf, ng * fb, hipMemcpyDeviceToHost, s));
+      if (ef) FF_HIP(hipMemcpyAsync(fo->epistemic + goff, ef, ng * fb, hipMemcpyDeviceToHost, s));
       if (rf) FF_HIP(hipMemcpyAsync(fo->residual + goff, rf, ng * fb, hipMemcpyDeviceToHost, s));
       FF_HIP(hipStreamSynchronize(s));
     }
@@ -4660,6 +4762,10 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
   }
   if (mse) {
     FF_HIP(hipMemcpyAsync(fo->mse, mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipStreamSynchronize(s));
+  }
+  if (en) {
+    FF_HIP(hipMemcpyAsync(fo->eps_norm, en, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
     FF_HIP(hipStreamSynchronize(s));
   }
 #undef FF_HIP
@@ -4696,6 +4802,56 @@ int dv_infer_fields_composite(dv_model* m, const double* fields, int32_t M, int3
                            nullptr, nullptr, nullptr, nullptr, &fo);
 }
 
+// the refusals of the two Monte-Carlo forms, before any GPU work
+static int infer_fields_mc_check(dv_model* m, const char* who, int32_t nb, int32_t nsamples) {
+  if (!m) return DV_E_INVALID;
+  if (nsamples < 1) {
+    set_error("%s: %d Monte-Carlo samples asked for, at least 1 is needed", who, nsamples);
+    return DV_E_INVALID;
+  }
+  if (nb < 3 || m->A.C < 3) {
+    set_error("%s: the normalised epistemic uncertainty is read from band 2, the stamps have %d bands", who,
+              std::min<int>(nb, m->A.C));
+    return DV_E_INVALID;
+  }
+  return DV_OK;
+}
+
+int dv_infer_fields_mc_keep(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                            const int64_t* field_ptr, int64_t N, uint64_t seed, uint64_t mc_seed, int32_t nsamples,
+                            float* loc, float* scale, double* cutouts, float* epistemic) {
+  DV_TRY(infer_fields_mc_check(m, "dv_infer_fields_mc_keep", nb, nsamples));
+  if (N > 0 && (!loc || !scale || !cutouts || !epistemic)) {
+    set_error("dv_infer_fields_mc_keep: loc, scale, cutouts and epistemic must all be given");
+    return DV_E_INVALID;
+  }
+  McStage mc{nsamples, mc_seed, epistemic};
+  return infer_fields_impl(m, "dv_infer_fields_mc_keep", fields, M, F, nb, starts, field_ptr, N, seed, loc, scale, nullptr,
+                           nullptr, nullptr, cutouts, nullptr, &mc);
+}
+
+int dv_infer_fields_mc_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                 const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed, uint64_t mc_seed,
+                                 int32_t nsamples, double* mean_fields, double* stddev_fields, double* epistemic_fields,
+                                 double* residual_fields, double* mse_center, double* eps_norm) {
+  DV_TRY(infer_fields_mc_check(m, "dv_infer_fields_mc_composite", nb, nsamples));
+  if ((M > 0 && (!mean_fields || !stddev_fields || !epistemic_fields)) || (N > 0 && (!eps_norm || !places))) {
+    set_error("dv_infer_fields_mc_composite: mean_fields, stddev_fields, epistemic_fields, eps_norm and places must all be given");
+    return DV_E_INVALID;
+  }
+  FieldsOut fo;
+  fo.mean = mean_fields;
+  fo.stddev = stddev_fields;
+  fo.residual = residual_fields;
+  fo.mse = mse_center;
+  fo.places = places;
+  fo.epistemic = epistemic_fields;
+  fo.eps_norm = eps_norm;
+  McStage mc{nsamples, mc_seed, nullptr};
+  return infer_fields_impl(m, "dv_infer_fields_mc_composite", fields, M, F, nb, starts, field_ptr, N, seed, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, &fo, &mc);
+}
+
 int dv_infer_mc(dv_model* m, const float* x, int64_t N, int32_t nsamples, uint64_t seed, float* mean_out,
                 float* std_out) {
   if (!m || !x || N < 0 || nsamples < 1 || (!mean_out && !std_out)) return DV_E_INVALID;
@@ -4712,27 +4868,7 @@ int dv_infer_mc(dv_model* m, const float* x, int64_t N, int32_t nsamples, uint64
     if (m->normalise) DV_TRY(launch_normalise(m->stage_x, (long)nb * stamp, false, s));
     DV_TRY(bn_prepare(m, m->stage_x, nullptr, 0, nb, nb, false, false));
     DV_TRY(encoder_forward(m, m->stage_x, nullptr, 0, nb, false));           // once per chunk
-    // nsamples stochastic decodes, as many per pass as the workspace takes: the decoder runs on nb * reps rows, row r
-    // being sample k + r / nb of stamp r % nb (the sampler reads that stamp's t and draws the noise sample k + r / nb
-    // would get in a pass of its own), and the per-stamp statistics fold the samples in order.  A handful of objects
-    // with 100 samples each - the per-field use of the reference - is one or two decoder passes instead of 100.
-    const int per_pass = std::max(1, m->Bc / nb);
-    for (int k = 0; k < nsamples; k += per_pass) {
-      const int reps = std::min(per_pass, nsamples - k);
-      int nblk = 0;
-      DV_TRY(sampler_forward(m, nb * reps, true, seed + (uint64_t)k, (unsigned)m->ctx->rank, (unsigned)o, false,
-                             reps > 1 ? nb : 0));
-      DV_TRY(decoder_forward(m, nb * reps, false));
-      DV_TRY(head_lane(m, nullptr, nullptr, 0, nb * reps, nb * reps, false, true, 0, &nblk));
-      // normalise=True: the recipe is np.std(deblend(net, [stamp]*100, normalise=True)[0], axis=0), i.e. the statistics
-      // of the DENORMALISED means - each decoded pass goes back through sinh(arctanh(.)) before it is folded in
-      if (m->normalise) DV_TRY(launch_normalise(m->loc, (long)nb * reps * stamp, true, s));
-      if (reps > 1)
-        DV_TRY(launch_welford_update_multi(m->loc, mean, m2, (long)nb * stamp, reps, k, s));
-      else
-        DV_TRY(launch_welford_update(m->loc, mean, m2, ((long)(nb * stamp) + 3) & ~3L, k, s));   // buffers carry slack
-    }
-    DV_TRY(launch_welford_finish(m2, ((long)(nb * stamp) + 3) & ~3L, nsamples, s));
+    DV_TRY(mc_decode_stats(m, nb, nsamples, seed, (unsigned)o));   // nsamples decodes: mean in gA, std in gB
     if (mean_out)
       DV_HIP(hipMemcpyAsync(mean_out + o * stamp, mean, nb * stamp * sizeof(float), hipMemcpyDeviceToHost, s));
     if (std_out) DV_HIP(hipMemcpyAsync(std_out + o * stamp, m2, nb * stamp * sizeof(float), hipMemcpyDeviceToHost, s));

@@ -182,16 +182,21 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(double* __restrict
 // of the chunk: fptr[m] .. fptr[m + 1] (global stamp numbers) cut to the chunk [obase, obase + n).  A field has its own
 // workgroups, so two fields never meet in a sum, and within a field the order of additions is object order as before: a
 // field's result has the bits the single-field call gives.  A field without objects in the chunk returns at once.
+//
+// EPS (dv_infer_fields_mc_composite): a third sum, eps_f += the chunk's Monte-Carlo std stamps `eps` (float32, one per stamp,
+// as the Welford fold left them), with the placement, the object order and the load-add-store across chunks of the other two;
+// the instantiation without it is the kernel as it was.
 constexpr int CT = 32;       // tile edge: a thread owns the four pixels (ty + 16 a, tx + 16 b) of its 32 x 32 tile
 constexpr int CSEG = 2048;   // objects per scan round (8 per thread)
-template <int NBMAX>
+template <int NBMAX, bool EPS>
 __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __restrict__ mean_f, double* __restrict__ std_f,
                                                                     double* __restrict__ res_f, int F, int nb,
                                                                     const float* __restrict__ loc,
                                                                     const float* __restrict__ scale,
                                                                     const int* __restrict__ places, int n, int cs,
                                                                     const int* __restrict__ fptr, int f0, int fy0,
-                                                                    long obase) {
+                                                                    long obase, double* __restrict__ eps_f,
+                                                                    const float* __restrict__ eps) {
   __shared__ int s_list[CSEG];        // objects of the round that meet the tile, in object order
   __shared__ int s_lr[CSEG], s_lc[CSEG];   // their placements
   __shared__ int s_wsum[4];
@@ -199,11 +204,14 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
   const int ntx = (F + CT - 1) / CT;
   const int tr0 = (blockIdx.x / ntx) * CT, tc0 = (blockIdx.x % ntx) * CT;
   const int ty = tid >> 4, tx = tid & 15;
-  double am[4][NBMAX], as[4][NBMAX], ar[4][NBMAX];
+  double am[4][NBMAX], as[4][NBMAX], ar[4][NBMAX], ae[EPS ? 4 : 1][NBMAX];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
 #pragma unroll
-    for (int b = 0; b < NBMAX; ++b) am[q][b] = as[q][b] = ar[q][b] = 0.0;
+    for (int b = 0; b < NBMAX; ++b) {
+      am[q][b] = as[q][b] = ar[q][b] = 0.0;
+      if constexpr (EPS) ae[q][b] = 0.0;
+    }
   bool loaded = false;
   unsigned touched = 0;
   int olo = 0;
@@ -217,6 +225,7 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
     mean_f += fo;
     std_f += fo;
     if (res_f) res_f += fo;
+    if constexpr (EPS) eps_f += fo;
   }
   for (int seg = olo; seg < n; seg += CSEG) {
     // thread t tests objects seg + 8 t .. + 7 (four 16-byte loads of their placements): order by (thread, bit) = object order
@@ -278,6 +287,7 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
                 am[q][b] = mean_f[e0 + b];
                 as[q][b] = std_f[e0 + b];
                 if (res_f) ar[q][b] = res_f[e0 + b];
+                if constexpr (EPS) ae[q][b] = eps_f[e0 + b];
               }
           }
         }
@@ -298,6 +308,7 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
                 am[q][b] += v;
                 ar[q][b] -= v;
                 as[q][b] += (double)scale[so + b];
+                if constexpr (EPS) ae[q][b] += (double)eps[so + b];
               }
           }
         }
@@ -317,6 +328,7 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
             mean_f[e0 + b] = am[q][b];
             std_f[e0 + b] = as[q][b];
             if (res_f) res_f[e0 + b] = ar[q][b];
+            if constexpr (EPS) eps_f[e0 + b] = ae[q][b];
           }
       }
     }
@@ -377,6 +389,31 @@ __device__ double mse_pairwise_sum(const double* a, int n) {
     }
   }
   return val[0];
+}
+
+// eps_norm[i] = sum(std_i[:, :, 2]) / sum(mean_i[:, :, 2]) (field_deblender.py:315-318: the Monte-Carlo std of a galaxy's
+// r band over its predicted r-band flux), both sums in float64; one wave per stamp, four stamps per workgroup.  Lane l adds
+// the pixels l, l + 64, ... of both stamps in that order (the band-2 element of every pixel is read once), then the 64 partial
+// sums meet in a fixed shuffle tree: the same bits on every run, whatever else the chunk holds.  The division is IEEE's, so
+// an all-zero mean gives numpy's inf / nan without a trap.
+__global__ __launch_bounds__(256) void scene_eps_norm_kernel(const float* __restrict__ eps, const float* __restrict__ loc,
+                                                             int n, int cs, int nb, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long i = (long)blockIdx.x * 4 + wave;
+  if (i >= n) return;                                            // (uniform over the wave)
+  const int px = cs * cs;
+  const long base = i * px * nb + 2;
+  double se = 0.0, sm = 0.0;
+  for (int e = lane; e < px; e += 64) {
+    se += (double)eps[base + (long)e * nb];
+    sm += (double)loc[base + (long)e * nb];
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    se += __shfl_down(se, d, 64);
+    sm += __shfl_down(sm, d, 64);
+  }
+  if (lane == 0) out[i] = se / sm;
 }
 
 __global__ __launch_bounds__(256) void scene_center_mse_kernel(const double* __restrict__ field, int F, int nb,
@@ -521,8 +558,13 @@ int scene_composite(double* field_h, int F, int nb, const double* stamps_h, cons
 namespace dv {
 int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, int F, int nb, const float* loc,
                                  const float* scale, const int* places_dev, int n, int cs, hipStream_t s,
-                                 const int* fptr_dev, int f0, int fy0, int nfields, long obase) {
+                                 const int* fptr_dev, int f0, int fy0, int nfields, long obase, double* eps_f,
+                                 const float* eps) {
   if (n <= 0) return OK;
+  if ((eps_f == nullptr) != (eps == nullptr)) {
+    set_error("scene composite: the epistemic field and the std stamps go together");
+    return E_INVALID;
+  }
   if (nb < 1 || nb > 8) {
     set_error("scene composite: 1 .. 8 bands");
     return E_INVALID;
@@ -533,12 +575,26 @@ int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, i
     return E_INVALID;
   }
   const dim3 grid((unsigned)(ntx * ntx), fptr_dev ? (unsigned)nfields : 1u);
-  if (nb <= 6)
-    hipLaunchKernelGGL(scene_composite_chunk_kernel<6>, grid, dim3(256), 0, s, mean_f, std_f, res_f, F, nb, loc, scale,
-                       places_dev, n, cs, fptr_dev, f0, fy0, obase);
-  else
-    hipLaunchKernelGGL(scene_composite_chunk_kernel<8>, grid, dim3(256), 0, s, mean_f, std_f, res_f, F, nb, loc, scale,
-                       places_dev, n, cs, fptr_dev, f0, fy0, obase);
+#define SCC_LAUNCH(NBMAX, EPS)                                                                                          \
+  hipLaunchKernelGGL((scene_composite_chunk_kernel<NBMAX, EPS>), grid, dim3(256), 0, s, mean_f, std_f, res_f, F, nb, loc, \
+                     scale, places_dev, n, cs, fptr_dev, f0, fy0, obase, eps_f, eps)
+  if (nb <= 6) {
+    if (eps_f) SCC_LAUNCH(6, true); else SCC_LAUNCH(6, false);
+  } else {
+    if (eps_f) SCC_LAUNCH(8, true); else SCC_LAUNCH(8, false);
+  }
+#undef SCC_LAUNCH
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+int launch_scene_eps_norm(const float* eps, const float* loc, int n, int cs, int nb, double* out_dev, hipStream_t s) {
+  if (n <= 0) return OK;
+  if (nb < 3 || cs < 1) {
+    set_error("normalised epistemic uncertainty: band 2 of stamps with at least 3 bands");
+    return E_INVALID;
+  }
+  hipLaunchKernelGGL(scene_eps_norm_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, eps, loc, n, cs, nb, out_dev);
   DV_HIP(hipGetLastError());
   return OK;
 }

@@ -116,7 +116,8 @@ class DeblendField:
         if dev is not None:
             # deblend_field(on_device=True) composited them on the GPU behind the forward passes
             return {"predicted_mean_field": dev["mean_field"].copy(), "predicted_stddev_field": dev["stddev_field"].copy(),
-                    "predicted_epistemic_field": np.zeros_like(dev["mean_field"])}
+                    "predicted_epistemic_field": dev["epistemic_field"].copy() if "epistemic_field" in dev
+                    else np.zeros_like(dev["mean_field"])}
         if res_deblend is None:
             res_deblend = self.res_deblend
         zeros = np.zeros((self.field_size, self.field_size, self.nb_of_bands))
@@ -187,8 +188,14 @@ class DeblendField:
         167 GB of mean and stddev stamps that no longer cross the host link.  The recarray then carries the per-galaxy
         scalars (list_idx, positions, shifts, passed_cuts, mse_center) but no stamp images, and get_predicted_field() /
         get_residual_field() return the fields composited on the GPU - the same sums in the same order, bit for bit, as
-        compositing the stamps of the default path.  Needs integer positions, the object's own field, no caller-supplied
-        cutouts and no epistemic pass (each raises with a message otherwise).
+        compositing the stamps of the default path.  Needs integer positions, the object's own field and no caller-supplied
+        cutouts (each raises with a message otherwise).
+
+        epistemic_uncertainty_estimation=True (constructor): the 100 Monte-Carlo decodes per galaxy are a stage of the same
+        engine call in both modes (dv_infer_fields_mc_keep / _mc_composite with one field) - they run on the
+        encoder output of the deblending pass, with the seed that follows the pass's own.  The default path returns the
+        recarray it always did, bit for bit; on_device=True composites `predicted_epistemic_field` on the GPU and adds the
+        per-galaxy `epistemic_norm` the cut is taken on next to `mse_center`.
         """
         if optimise_positions:
             raise NotImplementedError("optimise_positions=True is not wired into deblend_field: call deblend_field() and then "
@@ -198,7 +205,8 @@ class DeblendField:
             if isinstance(cutout_images, np.ndarray):
                 raise ValueError("on_device=True cuts the stamps out of the field on the GPU; caller-supplied cutout_images "
                                  "need the default path")
-            return self._deblend_field_on_device(galaxy_distances_to_center, mse_criterion, field_image)
+            return self._deblend_field_on_device(galaxy_distances_to_center, mse_criterion, field_image, epistemic_criterion)
+        eps_std = None                   # the Monte-Carlo std stamps, when the deblending call itself estimated them
         res_deblend = {"cutout_images": None, "output_images_mean": None, "output_images_stddev": None,
                        "shifts": None, "list_idx": None}
         if field_image is None:
@@ -253,7 +261,15 @@ class DeblendField:
                 eng = core.engine
                 eng.set_normalise(bool(self.normalise))
                 try:
-                    r = eng.infer_cutouts_keep(field_image[0], starts[ok], seed=core.next_seed())
+                    if self.epistemic_uncertainty_estimation:
+                        # the deblending pass and, on its encoder output, the 100 decodes of the estimate below in one
+                        # call: the two seeds deblend() and deblend_epistemic() would draw, in that order
+                        seed = core.next_seed()
+                        r = eng.infer_cutouts_mc_keep(field_image[0], starts[ok], seed=seed, mc_seed=core.next_seed(),
+                                                      nsamples=100)
+                        eps_std = r["epistemic"]
+                    else:
+                        r = eng.infer_cutouts_keep(field_image[0], starts[ok], seed=core.next_seed())
                 finally:
                     eng.set_normalise(False)
                 output_images_mean, output_images_stddev, cutouts = r["loc"], r["scale"], r["cutouts"]
@@ -264,7 +280,8 @@ class DeblendField:
 
         if self.epistemic_uncertainty_estimation:
             # reference: np.std(deblend(net, [cutout] * 100)[0], axis=0) per object (field_deblender.py:303-313)
-            _, eps_std = deblend_epistemic(self.net, rows, n_samples=100, normalise=self.normalise)
+            if eps_std is None:
+                _, eps_std = deblend_epistemic(self.net, rows, n_samples=100, normalise=self.normalise)
             epistemic_uncertainty = [e.astype(np.float64) for e in eps_std]
             eps_norm = np.array([np.sum(e[:, :, 2]) for e in epistemic_uncertainty]) / \
                 np.array([np.sum(m[:, :, 2]) for m in output_images_mean])
@@ -309,10 +326,7 @@ class DeblendField:
         self._device_fields = None          # the composited fields of an earlier on-device pass belonged to ITS recarray
         return self.res_deblend
 
-    def _deblend_field_on_device(self, galaxy_distances_to_center, mse_criterion, field_image):
-        if self.epistemic_uncertainty_estimation:
-            raise NotImplementedError("on_device=True composites the mean and stddev fields; the epistemic estimate needs the "
-                                      "default path")
+    def _deblend_field_on_device(self, galaxy_distances_to_center, mse_criterion, field_image, epistemic_criterion=100.0):
         # the reference's get_residual_field always subtracts from self.field_image (:60), whatever field the stamps were cut
         # from: the device-composited residual can only stand in for it when both are the same field
         if field_image is not None and field_image is not self.field_image and not (
@@ -341,17 +355,26 @@ class DeblendField:
         eng = core.engine
         eng.set_normalise(bool(self.normalise))
         try:
-            out = eng.infer_cutouts_composite(field, starts[ok], places, seed=core.next_seed())
+            if self.epistemic_uncertainty_estimation:
+                seed = core.next_seed()          # the default path's order: deblending pass, then Monte Carlo
+                out = eng.infer_cutouts_mc_composite(field, starts[ok], places, seed=seed, mc_seed=core.next_seed(),
+                                                     nsamples=100)
+            else:
+                out = eng.infer_cutouts_composite(field, starts[ok], places, seed=core.next_seed())
         finally:
             eng.set_normalise(False)
         self.nb_of_detected_objects += [len(d)]
         self.nb_of_deblended_galaxies += [len(list_idx)]
         n = len(list_idx)
-        self.res_deblend = pd.DataFrame({
-            "list_idx": list_idx, "shifts": [np.array([0, 0])] * n,
-            "galaxy_distances_to_center_x": list(dd[:, 0]), "galaxy_distances_to_center_y": list(dd[:, 1]),
-            "mse_center": list(out["mse_center"]), "passed_cuts": list(~(out["mse_center"] > mse_criterion)),
-        }).to_records(index=False)
+        cols = {"list_idx": list_idx, "shifts": [np.array([0, 0])] * n,
+                "galaxy_distances_to_center_x": list(dd[:, 0]), "galaxy_distances_to_center_y": list(dd[:, 1]),
+                "mse_center": list(out["mse_center"])}
+        if self.epistemic_uncertainty_estimation:
+            cols["epistemic_norm"] = list(out["eps_norm"])
+            cols["passed_cuts"] = list(~((out["eps_norm"] > epistemic_criterion) | (out["mse_center"] > mse_criterion)))
+        else:
+            cols["passed_cuts"] = list(~(out["mse_center"] > mse_criterion))
+        self.res_deblend = pd.DataFrame(cols).to_records(index=False)
         self._device_fields = (self.res_deblend, out)      # the fields and the recarray they belong to, set together
         return self.res_deblend
 
@@ -385,13 +408,16 @@ class DeblendFieldBatch:
     """DeblendField for M fields of one size: every pass is ONE engine call for the galaxies of all fields, so a survey of
     small fields runs the network in full chunks instead of one latency-bound call per field.  Per field the results are
     those of DeblendField on that field, for the noise rows its galaxies have in the call (galaxies are numbered over all
-    fields, field after field).  No epistemic estimate."""
+    fields, field after field).  The epistemic estimate is an option of the pass (deblend_fields(...,
+    epistemic_uncertainty_estimation=True)), not of the object: the Monte-Carlo decodes of all fields run inside the same
+    engine call, on the encoder output of the deblending pass."""
 
     DEFAULT_COLUMNS = [("cutout_images", "O"), ("output_images_mean", "O"), ("output_images_stddev", "O"), ("shifts", "O"),
                        ("list_idx", "<i8"), ("galaxy_distances_to_center_x", "<f8"), ("galaxy_distances_to_center_y", "<f8"),
                        ("epistemic_uncertainty", "O"), ("passed_cuts", "?")]
     ON_DEVICE_COLUMNS = [("list_idx", "<i8"), ("shifts", "O"), ("galaxy_distances_to_center_x", "<f8"),
                          ("galaxy_distances_to_center_y", "<f8"), ("mse_center", "<f8"), ("passed_cuts", "?")]
+    ON_DEVICE_EPISTEMIC_COLUMNS = ON_DEVICE_COLUMNS[:-1] + [("epistemic_norm", "<f8"), ("passed_cuts", "?")]
 
     def __init__(self, net, field_images, cutout_size=59, nb_of_bands=6, normalise=False):
         """
@@ -417,6 +443,7 @@ class DeblendFieldBatch:
         self.res_deblend = None
         self._ctx_obj = getattr(getattr(net, "_core", None), "ctx", None)
         self._device_fields = None      # (res_deblend list, fields composited on the GPU) of the last on-device pass
+        self._epistemic_pass = None     # the res_deblend list of the last pass, if it estimated the epistemic uncertainty
 
     @property
     def _ctx(self):
@@ -430,14 +457,29 @@ class DeblendFieldBatch:
             col[i] = np.array([0, 0])
         return col
 
-    def deblend_fields(self, galaxy_distances_to_center=None, mse_criterion=100.0, on_device=False):
+    def deblend_fields(self, galaxy_distances_to_center=None, mse_criterion=100.0, on_device=False,
+                       epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
         Returns a list of M recarrays (kept in self.res_deblend) with the columns DeblendField.deblend_field gives in the
         same mode: by default the stamps (dv_infer_fields_keep), with on_device=True the per-galaxy scalars and mse_center
         only, the fields being composited on the GPU (dv_infer_fields_composite; integer positions).  A field without a
-        valid galaxy gets an empty recarray."""
+        valid galaxy gets an empty recarray.
+
+        epistemic_uncertainty_estimation=True: `epistemic_samples` more stochastic decodes of every galaxy run in the same
+        call (dv_infer_fields_mc_keep / _mc_composite; two consecutive seeds: the pass, then the Monte-Carlo stage), and a
+        galaxy whose normalised uncertainty sum(std[:, :, 2]) / sum(mean[:, :, 2]) exceeds `epistemic_criterion` fails the
+        cuts, as in DeblendField.  By default the `epistemic_uncertainty` column carries the float64 std stamps; with
+        on_device=True the std stamps are composited on the GPU (get_predicted_fields()["predicted_epistemic_fields"]) and
+        the recarrays gain an `epistemic_norm` column."""
+        mc = bool(epistemic_uncertainty_estimation)
+        if mc:
+            if int(epistemic_samples) < 1:
+                raise ValueError(f"epistemic_samples must be at least 1, got {epistemic_samples}")
+            if self.nb_of_bands < 3:
+                raise ValueError("the normalised epistemic uncertainty is read from band 2, these fields have "
+                                 f"{self.nb_of_bands} bands")
         if galaxy_distances_to_center is None:
             from debvader_amd.detect.detection import detect_objects_batch
             galaxy_distances_to_center = detect_objects_batch(self.field_images, ctx=self._ctx)
@@ -456,17 +498,34 @@ class DeblendFieldBatch:
             raise ValueError("DeblendFieldBatch needs a net that runs on the engine (debvader_amd.model.model.load_deblender)")
         self.res_deblend = None
         self._device_fields = None
+        self._epistemic_pass = None
         N = len(starts)
         eng.set_normalise(bool(self.normalise))
         try:
+            seed = core.next_seed()
+            if mc:
+                mc_args = {"seed": seed, "mc_seed": core.next_seed(), "nsamples": int(epistemic_samples)}
             if on_device:
                 # where get_predicted_field puts a stamp: padded at int((F - cs) / 2) and shifted by the distance to the centre
                 places = (int((F - cs) / 2) + dd).astype(np.int64)
-                out = eng.infer_fields_composite(self.field_images, starts, places, field_ptr, seed=core.next_seed())
+                if mc:
+                    out = eng.infer_fields_mc_composite(self.field_images, starts, places, field_ptr, **mc_args)
+                else:
+                    out = eng.infer_fields_composite(self.field_images, starts, places, field_ptr, seed=seed)
+            elif mc:
+                out = eng.infer_fields_mc_keep(self.field_images, starts, field_ptr, **mc_args)
             else:
-                out = eng.infer_fields_keep(self.field_images, starts, field_ptr, seed=core.next_seed())
+                out = eng.infer_fields_keep(self.field_images, starts, field_ptr, seed=seed)
         finally:
             eng.set_normalise(False)
+        eps_norm = None
+        if mc and on_device:
+            eps_norm = out["eps_norm"]
+        elif mc:
+            # DeblendField's host formula, row by row (float64 std stamps over numpy's float32 sum of the mean)
+            eps64 = out["epistemic"].astype(np.float64)
+            eps_norm = np.array([np.sum(e[:, :, 2]) for e in eps64]) / np.array([np.sum(m[:, :, 2]) for m in out["loc"]]) \
+                if N else np.zeros(0)
         if on_device:
             mse_center = out["mse_center"]
         else:
@@ -475,12 +534,15 @@ class DeblendFieldBatch:
             mse_center = np.mean(np.square(diff).reshape(N, -1), axis=1) if N else np.zeros(0)
             no_epistemic = np.zeros((cs, cs, nb))
             no_epistemic.flags.writeable = False          # one array stands for every row's zeros
-        passed = ~(mse_center > mse_criterion)
+        passed = ~(mse_center > mse_criterion) if eps_norm is None else \
+            ~((eps_norm > epistemic_criterion) | (mse_center > mse_criterion))
+        columns = self.DEFAULT_COLUMNS if not on_device else \
+            self.ON_DEVICE_EPISTEMIC_COLUMNS if mc else self.ON_DEVICE_COLUMNS
         res = []
         for m in range(self.nb_of_fields):
             lo, hi = int(field_ptr[m]), int(field_ptr[m + 1])
             n = hi - lo
-            rec = np.recarray((n,), dtype=self.ON_DEVICE_COLUMNS if on_device else self.DEFAULT_COLUMNS)
+            rec = np.recarray((n,), dtype=columns)
             rec["list_idx"] = kept[m]
             rec["shifts"] = self._shifts_column(n)
             rec["galaxy_distances_to_center_x"] = dd[lo:hi, 0]
@@ -488,18 +550,22 @@ class DeblendFieldBatch:
             rec["passed_cuts"] = passed[lo:hi]
             if on_device:
                 rec["mse_center"] = mse_center[lo:hi]
+                if mc:
+                    rec["epistemic_norm"] = eps_norm[lo:hi]
             else:
                 for i in range(n):
                     rec["cutout_images"][i] = out["cutouts"][lo + i]
                     rec["output_images_mean"][i] = out["loc"][lo + i]
                     rec["output_images_stddev"][i] = out["scale"][lo + i]
-                    rec["epistemic_uncertainty"][i] = no_epistemic
+                    rec["epistemic_uncertainty"][i] = eps64[lo + i] if mc else no_epistemic
             res.append(rec)
         self.nb_of_detected_objects += [n_det]
         self.nb_of_deblended_galaxies += [[len(k) for k in kept]]
         self.res_deblend = res
         if on_device:
             self._device_fields = (res, out)
+        if mc:
+            self._epistemic_pass = res
         return res
 
     def _own_device_fields(self):
@@ -532,19 +598,29 @@ class DeblendFieldBatch:
         return out
 
     def get_predicted_fields(self):
-        """{"predicted_mean_fields", "predicted_stddev_fields"}, each (M, F, F, bands)."""
+        """{"predicted_mean_fields", "predicted_stddev_fields"}, each (M, F, F, bands); after a pass that estimated the
+        epistemic uncertainty also "predicted_epistemic_fields"."""
         self._need_pass()
+        mc = self._epistemic_pass is not None and self._epistemic_pass is self.res_deblend
         dev = self._own_device_fields()
         if dev is not None:
-            return {"predicted_mean_fields": dev["mean_fields"].copy(), "predicted_stddev_fields": dev["stddev_fields"].copy()}
+            out = {"predicted_mean_fields": dev["mean_fields"].copy(), "predicted_stddev_fields": dev["stddev_fields"].copy()}
+            if mc and "epistemic_fields" in dev:
+                out["predicted_epistemic_fields"] = dev["epistemic_fields"].copy()
+            return out
         out = {"predicted_mean_fields": np.zeros_like(self.field_images),
                "predicted_stddev_fields": np.zeros_like(self.field_images)}
+        if mc:
+            out["predicted_epistemic_fields"] = np.zeros_like(self.field_images)
         zeros = np.zeros(self.field_images.shape[1:])
         for m, rec in enumerate(self.res_deblend):
             if len(rec):
                 pos = DeblendField._positions(rec)
                 out["predicted_mean_fields"][m] = self._ctx.scene_composite(zeros, self._stack(rec, "output_images_mean"), pos)
                 out["predicted_stddev_fields"][m] = self._ctx.scene_composite(zeros, self._stack(rec, "output_images_stddev"), pos)
+                if mc:
+                    out["predicted_epistemic_fields"][m] = self._ctx.scene_composite(
+                        zeros, self._stack(rec, "epistemic_uncertainty"), pos)
         return out
 
     def optimise_positions(self):

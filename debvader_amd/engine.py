@@ -935,6 +935,91 @@ class Engine:
                                             opt("residual_fields"), opt("mse_center")))
         return out
 
+    # -- the same with the Monte-Carlo epistemic estimate as a pipeline stage --
+    @staticmethod
+    def _check_mc(nsamples, bands):
+        if int(nsamples) < 1:
+            raise ValueError(f"nsamples must be at least 1, got {nsamples}")
+        if int(bands) < 3:
+            raise ValueError(f"the normalised epistemic uncertainty is read from band 2, the fields have {int(bands)} bands")
+
+    def infer_fields_mc_keep(self, fields, starts, field_ptr, seed=0, mc_seed=0, nsamples=100) -> Dict[str, np.ndarray]:
+        """infer_fields_keep() plus "epistemic" (N,) + stamp shape, float32: the standard deviation of `nsamples` more
+        stochastic decodes of every stamp (dv_infer_fields_mc_keep), run on the GPU behind each chunk's forward pass on the
+        encoder output that pass left there.  loc / scale / cutouts are infer_fields_keep's for `seed`, bit for bit;
+        "epistemic" is infer_mc(cutouts.astype(float32), nsamples, seed=mc_seed)[1], bit for bit."""
+        fields = _check_fields(fields)
+        starts = _i32_rows(starts, "cutout starts")
+        N = starts.shape[0]
+        fp = check_field_ptr(field_ptr, fields.shape[0], N)
+        Engine._check_mc(nsamples, fields.shape[3])
+        out = {"loc": _host_pool.empty((N,) + self.stamp_shape, np.float32),
+               "scale": _host_pool.empty((N,) + self.stamp_shape, np.float32),
+               "cutouts": _host_pool.empty((N,) + self.stamp_shape, np.float64),
+               "epistemic": _host_pool.empty((N,) + self.stamp_shape, np.float32)}
+        check(lib.dv_infer_fields_mc_keep(self._h, fields.ctypes.data_as(C.POINTER(C.c_double)), fields.shape[0],
+                                          fields.shape[1], fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed), int(mc_seed), int(nsamples),
+                                          _fp(out["loc"]), _fp(out["scale"]),
+                                          out["cutouts"].ctypes.data_as(C.POINTER(C.c_double)), _fp(out["epistemic"])))
+        return out
+
+    def infer_fields_mc_composite(self, fields, starts, places, field_ptr, seed=0, mc_seed=0, nsamples=100, residual=True,
+                                  mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_composite() plus "epistemic_fields" (M, F, F, bands) - the Monte-Carlo std stamps of
+        infer_fields_mc_keep summed at `places` in float64, object order - and "eps_norm" (N,): sum(std[:, :, 2]) /
+        sum(mean[:, :, 2]) per stamp in float64 (dv_infer_fields_mc_composite).  No stamp visits the host; the other
+        results are infer_fields_composite's for `seed`, bit for bit."""
+        fields = _check_fields(fields)
+        starts = _i32_rows(starts, "cutout starts")
+        places = _i32_rows(places, "stamp placements")
+        if places.shape != starts.shape:
+            raise ValueError(f"{starts.shape[0]} cutout starts but {places.shape[0]} placements")
+        N = starts.shape[0]
+        fp = check_field_ptr(field_ptr, fields.shape[0], N)
+        Engine._check_mc(nsamples, fields.shape[3])
+        dp = C.POINTER(C.c_double)
+        out = {"mean_fields": np.empty(fields.shape, np.float64), "stddev_fields": np.empty(fields.shape, np.float64),
+               "epistemic_fields": np.empty(fields.shape, np.float64)}
+        if residual:
+            out["residual_fields"] = np.empty(fields.shape, np.float64)
+        if mse_center:
+            out["mse_center"] = np.empty((N,), np.float64)
+        out["eps_norm"] = np.empty((N,), np.float64)
+        opt = lambda k: out[k].ctypes.data_as(dp) if k in out else None
+        check(lib.dv_infer_fields_mc_composite(self._h, fields.ctypes.data_as(dp), fields.shape[0], fields.shape[1],
+                                               fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               places.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed), int(mc_seed),
+                                               int(nsamples), out["mean_fields"].ctypes.data_as(dp),
+                                               out["stddev_fields"].ctypes.data_as(dp),
+                                               out["epistemic_fields"].ctypes.data_as(dp), opt("residual_fields"),
+                                               opt("mse_center"), out["eps_norm"].ctypes.data_as(dp)))
+        return out
+
+    @staticmethod
+    def _one_field(field):
+        field = np.ascontiguousarray(field, dtype=np.float64)
+        if field.ndim != 3 or field.shape[0] != field.shape[1]:
+            raise ValueError(f"expected a square field (F, F, bands), got {field.shape}")
+        return field[None]
+
+    def infer_cutouts_mc_keep(self, field, starts, seed=0, mc_seed=0, nsamples=100) -> Dict[str, np.ndarray]:
+        """infer_cutouts_keep() plus "epistemic": infer_fields_mc_keep for one field (M = 1 of the same engine call)."""
+        fields = Engine._one_field(field)
+        n = _i32_rows(starts, "cutout starts").shape[0]
+        return self.infer_fields_mc_keep(fields, starts, [0, n], seed=seed, mc_seed=mc_seed, nsamples=nsamples)
+
+    def infer_cutouts_mc_composite(self, field, starts, places, seed=0, mc_seed=0, nsamples=100, residual=True,
+                                   mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_cutouts_composite() plus "epistemic_field" and "eps_norm": infer_fields_mc_composite for one field (M = 1
+        of the same engine call), with the single-field key names."""
+        fields = Engine._one_field(field)
+        n = _i32_rows(starts, "cutout starts").shape[0]
+        out = self.infer_fields_mc_composite(fields, starts, places, [0, n], seed=seed, mc_seed=mc_seed, nsamples=nsamples,
+                                             residual=residual, mse_center=mse_center)
+        return {(k[:-1] if k.endswith("_fields") else k): (v[0] if k.endswith("_fields") else v) for k, v in out.items()}
+
     def infer_cutouts_stream(self, field, starts, consumer, seed=0):
         """infer_cutouts() for inputs whose outputs do not belong on one host (a million cutouts: 167 GB): every finished
         chunk is handed to consumer(first, mean, stddev) - float32 views (count, H, H, bands) of the pinned transfer

@@ -283,6 +283,26 @@ int dv_infer_fields_composite(dv_model* m, const double* fields, int32_t M, int3
                               const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
                               double* mean_fields, double* stddev_fields, double* residual_fields, double* mse_center);
 
+/* ---- epistemic uncertainty in the many-field calls ----
+ * dv_infer_fields_keep and dv_infer_fields_composite with the Monte-Carlo estimate of dv_infer_mc as a stage of the
+ * pipeline: behind every chunk's ordinary stochastic pass (`seed`, Philox rows = global stamp numbers, results bit-identical
+ * to the calls above) the encoder output that pass left on the GPU is decoded `nsamples` more times (sample k of stamp i
+ * draws Philox (mc_seed + k, i)) and folded into per-pixel statistics: no second encoder pass, nothing staged from the host.
+ * The std stamps are bit-identical to dv_infer_mc's std_out for the concatenated float32 cutouts, nsamples and mc_seed.
+ * _mc_keep: epistemic [N][cs][cs][nb] float32 beside loc, scale and the float64 cutouts (all four required).
+ * _mc_composite: epistemic_fields [M][F][F][nb] = the std stamps summed at `places` in float64, object order (the bits of
+ * dv_scene_composite on them); eps_norm [N] = sum(std[i,:,:,2]) / sum(mean[i,:,:,2]), both sums float64 (a zero denominator
+ * gives IEEE inf / nan); residual_fields and mse_center may be null, the other outputs are required.
+ * A resident field costs one more field-sized buffer than in dv_infer_fields_composite.  Refused before any GPU work:
+ * nsamples < 1, nb < 3 (the formula reads band 2), a missing output.  The single-field forms are M = 1. */
+int dv_infer_fields_mc_keep(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                            const int64_t* field_ptr, int64_t N, uint64_t seed, uint64_t mc_seed, int32_t nsamples,
+                            float* loc, float* scale, double* cutouts, float* epistemic);
+int dv_infer_fields_mc_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                 const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed, uint64_t mc_seed,
+                                 int32_t nsamples, double* mean_fields, double* stddev_fields, double* epistemic_fields,
+                                 double* residual_fields, double* mse_center, double* eps_norm);
+
 /* Monte-Carlo epistemic uncertainty: encode each stamp once, decode it `nsamples` times with fresh eps, return the
  * mean and the standard deviation (ddof 0) of the predicted means over the samples.  Replaces the per-object loop
  * `np.std(deblend(net, [stamp]*100)[0], axis=0)` of deblend/field_deblender.py:303-313. */

@@ -10,6 +10,23 @@ over the median).  Also, on --default-fields fields, the default (stamps returne
 GPU only; prints a table and one JSON line.
 
     python tools/fields_bench.py [--fields 1024] [--size 259] [--repeat 5] [--max-batch 8192]
+
+--epistemic N runs another comparison INSTEAD: the predicted mean / stddev / epistemic fields and the
+cuts of every field with N Monte-Carlo samples per galaxy,
+
+    before:  for every field, the engine calls DeblendField(epistemic_uncertainty_estimation=True) made before the estimate
+             became a pipeline stage: deblend_field() (infer_cutouts_keep), deblend_epistemic() on the stamps (infer_mc:
+             float32 stamps up again, a second encoder pass, std stamps down), get_predicted_field() (three composites of
+             stamps sent up once more).  An emulation, not the old code: the same engine calls with the
+             same arguments, three composites per field (mean and stddev in get_predicted_field(), the std stamps in a
+             call of their own) and the cut on the host, as before; it stacks the cutouts into one array once more than
+             the old path did (a host copy of 167 KB per stamp)
+    loop  :  for every field  DeblendField(..., epistemic_uncertainty_estimation=True): deblend_field() +
+             get_predicted_field() as they are now (N = 100 only: the class fixes the reference's 100 samples)
+    batch :  DeblendFieldBatch(net, fields).deblend_fields(d, on_device=True, epistemic_uncertainty_estimation=True,
+             epistemic_samples=N) + get_predicted_fields()
+
+alternating, --repeat times each, both engines.
 """
 import argparse
 import json
@@ -52,6 +69,83 @@ def _batch(net, fields, dists, on_device):
     return sum(len(r) for r in DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=on_device))
 
 
+def _before_field(net, field, d, nsamples):
+    from debvader_amd.deblend_cutout.deblender import deblend_epistemic
+
+    db = DeblendField(net, field)
+    r = db.deblend_field(d)
+    if isinstance(r, dict):
+        return 0
+    rows = np.array(list(r["cutout_images"]))
+    _, eps = deblend_epistemic(net, rows, n_samples=nsamples)
+    eps = eps.astype(np.float64)
+    norm = np.array([np.sum(e[:, :, 2]) for e in eps]) / np.array([np.sum(m[:, :, 2]) for m in r["output_images_mean"]])
+    r["passed_cuts"] = r["passed_cuts"] & ~(norm > 100.0)
+    db.get_predicted_field()
+    db._ctx.scene_composite(np.zeros(field.shape[1:]), eps, DeblendField._positions(r))
+    return len(r)
+
+
+def _epistemic_loop(net, fields, dists):
+    n = 0
+    for m in range(len(fields)):
+        db = DeblendField(net, fields[m:m + 1], epistemic_uncertainty_estimation=True)
+        r = db.deblend_field(dists[m])
+        if not isinstance(r, dict):
+            db.get_predicted_field()
+            n += len(r)
+    return n
+
+
+def _epistemic_batch(net, fields, dists, nsamples):
+    db = DeblendFieldBatch(net, fields)
+    res = db.deblend_fields(dists, on_device=True, epistemic_uncertainty_estimation=True, epistemic_samples=nsamples)
+    db.get_predicted_fields()
+    return sum(len(r) for r in res)
+
+
+def _epistemic_leg(a, fields, quiet, redirect_stdout):
+    M, F, ns = len(fields), fields.shape[1], a.epistemic
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "epistemic_samples": ns}
+    dists = None
+    for dtype in ("float32", "bf16"):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections; {ns} Monte-Carlo samples; "
+                  f"max_batch {a.max_batch}")
+        legs = {"before": lambda: sum(_before_field(net, fields[m:m + 1], dists[m], ns) for m in range(M)),
+                "batch": lambda: _epistemic_batch(net, fields, dists, ns)}
+        if ns == 100:
+            legs["loop"] = lambda: _epistemic_loop(net, fields, dists)
+        times = {k: [] for k in legs}
+        n = 0
+        with redirect_stdout(quiet):
+            _before_field(net, fields[:1], dists[0], ns)                               # warm-up
+            _epistemic_batch(net, fields[:min(M, 64)], dists[:min(M, 64)], ns)
+            if a.profile_one:                  # one batched call, for a kernel trace
+                _epistemic_batch(net, fields, dists, ns)
+                net._core.engine.close()
+                return
+            for _ in range(a.repeat):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    n = fn()
+                    times[k].append(time.perf_counter() - t0)
+        result[dtype] = {"stamps": n}
+        for k in legs:
+            t = np.array(times[k])
+            print(_row(f"{dtype} epistemic {k}", t, n, M))
+            result[dtype][k + "_ms"] = [round(1e3 * x, 2) for x in t]
+        tb, tl = np.array(times["batch"]), np.array(times["before"])
+        print(f"{dtype} epistemic before / batch: {float(np.median(tl) / np.median(tb)):.2f} x  (slowest batch "
+              f"{1e3 * tb.max():.1f} ms, fastest before {1e3 * tl.min():.1f} ms)")
+        result[dtype]["factor"] = round(float(np.median(tl) / np.median(tb)), 3)
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
 def _alternate(fa, fb, repeat):
     ta, tb, n = [], [], 0
     for _ in range(repeat):
@@ -75,6 +169,8 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--max-batch", type=int, default=8192)
     ap.add_argument("--default-fields", type=int, default=64)
+    ap.add_argument("--epistemic", type=int, default=0, help="Monte-Carlo samples: run the epistemic comparison instead")
+    ap.add_argument("--profile-one", action="store_true", help="with --epistemic: warm up, one fp32 batched call, exit")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     F, M = a.size, a.fields
@@ -83,6 +179,9 @@ def main():
     import io
     from contextlib import redirect_stdout
     quiet = io.StringIO()                      # the classes print the reference's notes about dropped galaxies
+    if a.epistemic > 0:
+        _epistemic_leg(a, fields, quiet, redirect_stdout)
+        return
     result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat}
     dists = None
     for dtype in ("float32", "bf16"):
