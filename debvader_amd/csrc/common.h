@@ -156,23 +156,23 @@ void gconv2_tile_geometry(const GConv2Params& p, int* bm, int* wgm, long* mtiles
 void debug_set_gconv2_tile(int code);
 
 // Scene compositing (scene.hip): host float64 buffers in, host float64 buffers out
-// device-resident gather + float32 cast (dv_infer_cutouts): starts_dev points at the first cutout of the chunk.
-// Many fields (dv_infer_fields*): field_dev is field f0 of a stack of fields and sfield_dev[i] the field of cutout i.
+// device-resident gather + float32 cast (dv_infer_cutouts*, dv_infer_fields*): starts_dev points at the first cutout of the
+// chunk, field_dev is field f0 of a stack of fields and sfield_dev[i] the field of cutout i.
 int launch_scene_extract_f32(const double* field_dev, int F, int nb, const int* starts_dev, long count, int cs,
-                             float* out_dev, hipStream_t s, const int* sfield_dev = nullptr, int f0 = 0);
-// compositing of one inference chunk on the device (dv_infer_cutouts_composite): mean / stddev / residual fields += the
-// chunk's stamps at integer placements, in object order; per-stamp centre MSE against the field's own cutout.
-// Many fields: the result pointers are field f0 of a stack, fptr_dev [M + 1] the global stamp number where each field's
+                             float* out_dev, hipStream_t s, const int* sfield_dev, int f0);
+// compositing of one inference chunk on the device (dv_infer_cutouts_composite, dv_infer_fields_composite): mean / stddev /
+// residual fields += the chunk's stamps at integer placements, in object order; per-stamp centre MSE against the field's own
+// cutout.  The result pointers are field f0 of a stack, fptr_dev [M + 1] the global stamp number where each field's
 // objects begin, the chunk holds stamps obase .. obase + n of fields fy0 .. fy0 + nfields - 1.
 // eps_f / eps (both or neither): a third field of the same stack, += the chunk's float32 Monte-Carlo std stamps.
 int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, int F, int nb, const float* loc,
                                  const float* scale, const int* places_dev, int n, int cs, hipStream_t s,
-                                 const int* fptr_dev = nullptr, int f0 = 0, int fy0 = 0, int nfields = 1, long obase = 0,
-                                 double* eps_f = nullptr, const float* eps = nullptr);
+                                 const int* fptr_dev, int f0, int fy0, int nfields, long obase, double* eps_f,
+                                 const float* eps);
 // out[i] = sum(eps_i[:, :, 2]) / sum(loc_i[:, :, 2]) in float64 for the n stamps of a chunk (both device, [n][cs][cs][nb])
 int launch_scene_eps_norm(const float* eps, const float* loc, int n, int cs, int nb, double* out_dev, hipStream_t s);
 int launch_scene_center_mse(const double* field_dev, int F, int nb, const int* starts_dev, const float* loc, int n, int cs,
-                            double* out_dev, hipStream_t s, const int* sfield_dev = nullptr, int f0 = 0);
+                            double* out_dev, hipStream_t s, const int* sfield_dev, int f0);
 int scene_extract(const double* field_h, int F, int nb, const int32_t* starts_h, int N, int cs, double* out_h,
                   hipStream_t s);
 int scene_composite(double* field_h, int F, int nb, const double* stamps_h, const double* pos_h, int N, int cs,

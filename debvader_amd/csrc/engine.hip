@@ -2946,14 +2946,13 @@ static void host_copy(float* dst, const void* src, size_t n, bool src_f64, int t
 // `threads` host threads: cs row copies of cs * nb doubles per window (what numpy's slice assignment does in
 // extract/extraction.py:26-32).  Used for the float64 cutout_images the reference's recarray carries: the windows are exact
 // copies of host data, so they are assembled on the host beside the GPU's forward passes and never cross the host link.
-// sfield (may be null: one field): the field of a stack [M][F][F][nb] each window is cut from.
+// sfield: the field of the stack [M][F][F][nb] each window is cut from.
 static void host_gather_cutouts(double* out, const double* field, int F, int nb, const int32_t* starts, int64_t n, int cs,
-                                int threads, const int32_t* sfield = nullptr) {
+                                int threads, const int32_t* sfield) {
   auto work = [=](int64_t lo, int64_t hi) {
     const size_t row = (size_t)cs * nb;
     for (int64_t i = lo; i < hi; ++i) {
-      const double* src = field + (sfield ? (size_t)sfield[i] * F * F * nb : (size_t)0) +
-                          ((size_t)starts[2 * i] * F + starts[2 * i + 1]) * nb;
+      const double* src = field + (size_t)sfield[i] * F * F * nb + ((size_t)starts[2 * i] * F + starts[2 * i + 1]) * nb;
       double* dst = out + (size_t)i * cs * row;
       for (int r = 0; r < cs; ++r) memcpy(dst + r * row, src + (size_t)r * F * nb, row * sizeof(double));
     }
@@ -2972,31 +2971,6 @@ static void host_gather_cutouts(double* out, const double* field, int F, int nb,
   for (auto& th : pool) th.join();
 }
 
-// the float64 cutouts themselves, wanted by the caller beside the network's outputs (dv_infer_cutouts_keep): host copies of
-// the field and of the window starts, and where the windows go
-struct CutoutKeep {
-  const double* field;   // host, [F][F][nb]
-  const int32_t* starts; // host, [N][2]
-  double* out;           // host, [N][cs][cs][nb]
-  const int32_t* sfield = nullptr;   // host, [N]: the field of each window when `field` is a stack [M][F][F][nb]
-};
-
-// input of the pipeline when the stamps are cutouts of a field that already sits in HBM (dv_infer_cutouts)
-struct CutoutSrc {
-  const double* field;   // device, [F][F][nb]
-  const int* starts;     // device, [N][2]
-  int F, nb, cs;
-  // many fields (dv_infer_fields*): `field` is field f0 of a stack of resident fields, and this call runs stamps
-  // row0 .. row0 + N of a longer global list - starts, places, mse and the result arrays point at stamp row0, Philox rows
-  // and fptr count from stamp 0 - in chunks of `chunk` stamps (the split of the whole list)
-  const int* sfield = nullptr;         // device, [N]: field of each stamp
-  const int32_t* sfield_h = nullptr;   // host copy of it
-  const int* fptr = nullptr;           // device, [M + 1]: first global stamp of each field
-  int f0 = 0;
-  int64_t row0 = 0;
-  int chunk = 0;
-};
-
 // stamps per chunk of an N-stamp call: the workspace capacity for long inputs, a quarter of the input (>= 128 stamps) for
 // short ones
 static int infer_chunk(const dv_model* m, int64_t N) {
@@ -3004,22 +2978,47 @@ static int infer_chunk(const dv_model* m, int64_t N) {
   return m->Bc;
 }
 
-// results of the pipeline composited on the device instead of copied out (dv_infer_cutouts_composite): every chunk's mean
-// and stddev stamps are added into float64 fields in HBM right behind its forward pass, on the same stream
-struct CompositeSink {
-  double *mean_f, *std_f, *res_f;   // device [F][F][nb]; res_f may be null
-  const int* places;                // device [N][2]: field position (row, col) of each stamp's top-left corner
-  double* mse;                      // device [N] centre MSE of every stamp against its cutout, or null
-  double* eps_f = nullptr;          // device [F][F][nb]: sum of the Monte-Carlo std stamps (McStage), or null
-  double* eps_norm = nullptr;       // device [N]: sum(std[:, :, 2]) / sum(mean[:, :, 2]) of every stamp (McStage), or null
-};
-
-// Monte-Carlo stage of the pipeline (dv_infer_fields_mc_*): behind every chunk's forward pass, nsamples more
-// decodes of the encoder output that pass left in the workspace, folded into per-pixel statistics
-struct McStage {
-  int nsamples;
-  uint64_t seed;
-  float* eps_out;                   // host [N][cs][cs][nb] std stamps (keep form), or null
+// One run of the inference pipeline (infer_pipelined): stamps row0 .. row0 + N of the caller's list.  Every per-stamp array
+// below, host or device, input or output, starts at stamp 0 of that list and is indexed by the global stamp number, as the
+// Philox rows and fptr are: a caller that runs its list in several jobs (dv_infer_fields*: one per group of resident
+// fields) changes row0, N, f0 and what fields_d holds between them, nothing else.  A null member is an output that is not
+// wanted or a stage that does not run.
+struct PipeJob {
+  // source, one of two: stamps in a host array ...
+  const void* x = nullptr;             // host [.][H][H][C], float32 or (x_f64) float64, cast while it is staged
+  bool x_f64 = false;
+  // ... or windows of float64 fields that sit in HBM, gathered and cast on the GPU (dv_infer_cutouts*, dv_infer_fields*)
+  const double* fields = nullptr;      // host [M][F][F][nb]: the whole stack
+  const double* fields_d = nullptr;  // device: its fields f0, f0 + 1, ...
+  int F = 0, nb = 0, f0 = 0;
+  const int32_t* starts = nullptr;     // host [.][2]: corner of every stamp's window
+  const int* starts_d = nullptr;     // device copy of it
+  const int32_t* sfield = nullptr;     // host [.]: field of every stamp
+  const int* sfield_d = nullptr;     // device copy of it
+  const int* fptr_d = nullptr;       // device [M + 1]: first stamp of every field
+  // rows
+  int64_t row0 = 0, N = 0;
+  int chunk = 0;                       // stamps per chunk: infer_chunk() of the whole list
+  const float* eps = nullptr;          // host [.][d] noise; null: stamp i draws Philox (seed, i)
+  uint64_t seed = 0;
+  // host outputs
+  float *loc = nullptr, *scale = nullptr, *mu = nullptr, *zstd = nullptr, *z = nullptr;
+  double* cutouts = nullptr;           // the float64 windows themselves (dv_infer_cutouts_keep), assembled on the host
+  float* eps_out = nullptr;            // the Monte-Carlo std stamps (dv_infer_fields_mc_keep)
+  // streaming consumer (dv_infer_cutouts_stream): reads every chunk's mean / stddev in the pinned ring, nothing is copied
+  dv_chunk_fn consumer = nullptr;
+  void* user = nullptr;
+  // composite sums (dv_infer_cutouts_composite): every chunk's mean and stddev stamps are added into float64
+  // fields in HBM right behind its forward pass instead of copied out; mean_f decides
+  double *mean_f = nullptr, *std_f = nullptr, *res_f = nullptr;   // device, fields f0 .. like fields_d
+  double* eps_f = nullptr;             // the same sum of the Monte-Carlo std stamps
+  const int* places_d = nullptr;     // device [.][2]: field position (row, col) of every stamp's top-left corner
+  double* mse = nullptr;               // device [.]: centre MSE of every stamp against its cutout
+  double* eps_norm = nullptr;          // device [.]: sum(std[:, :, 2]) / sum(mean[:, :, 2]) of every stamp
+  // Monte-Carlo stage (dv_infer_fields_mc_*): behind every chunk's forward pass, mc_samples more decodes of
+  // the encoder output that pass left in the workspace, folded into per-pixel statistics; mc_samples > 0 decides
+  int mc_samples = 0;
+  uint64_t mc_seed = 0;
 };
 
 // The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
@@ -3053,53 +3052,50 @@ static int mc_decode_stats(dv_model* m, int nb, int nsamples, uint64_t seed, uns
   return OK;
 }
 
-static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, const float* eps, uint64_t seed,
-                           float* loc, float* scale, float* mu, float* zstd, float* z, const CutoutSrc* cut = nullptr,
-                           dv_chunk_fn sink = nullptr, void* sink_user = nullptr, const CompositeSink* comp = nullptr,
-                           const CutoutKeep* keep = nullptr, const McStage* mc = nullptr) {
+static int infer_pipelined(dv_model* m, const PipeJob& j) {
   const Arch& A = m->A;
   hipStream_t s = m->ctx->stream;
   const size_t stamp = (size_t)A.H * A.H * A.C;
-  const int chunk = cut && cut->chunk ? cut->chunk : infer_chunk(m, N);
-  const int64_t row0 = cut ? cut->row0 : 0;
+  const int chunk = j.chunk, cs = A.H;
+  const int64_t N = j.N, row0 = j.row0;
+  const bool comp = j.mean_f != nullptr;
   InferPipe* p = nullptr;
-  DV_TRY(pipe_get(m, chunk, &p, !(comp && cut)));
-  float* eps_out = mc ? mc->eps_out : nullptr;
-  if (eps_out) DV_TRY(pipe_eps_buffers(m, p));
+  DV_TRY(pipe_get(m, chunk, &p, !comp));
+  if (j.eps_out) DV_TRY(pipe_eps_buffers(m, p));
   const int64_t K = (N + chunk - 1) / chunk;
   const int d = A.d;
   auto finish = [&](int64_t k) -> int {       // stage D: pinned -> caller's arrays
     const int b = (int)(k % 3);
-    const int64_t o = k * chunk;
-    const int nb = (int)std::min<int64_t>(chunk, N - o);
+    const int64_t r = row0 + k * chunk;       // the chunk's first stamp
+    const int nb = (int)std::min<int64_t>(chunk, N - k * chunk);
     // the caller's float64 cutouts of this chunk: host work that needs nothing from the GPU, done before the wait
-    if (keep) host_gather_cutouts(keep->out + o * stamp, keep->field, cut->F, cut->nb, keep->starts + 2 * o, nb, cut->cs, p->threads,
-                                  keep->sfield ? keep->sfield + o : nullptr);
+    if (j.cutouts)
+      host_gather_cutouts(j.cutouts + r * stamp, j.fields, j.F, j.nb, j.starts + 2 * r, nb, cs, p->threads, j.sfield + r);
     DV_HIP(hipEventSynchronize(p->ev_d2h[b]));
-    if (sink) {
+    if (j.consumer) {
       // streaming consumer: it reads the pinned transfer buffers in place (valid until it returns), nothing is copied
-      if (sink(sink_user, o, nb, p->hloc[b], p->hscale[b]) != 0) {
-        set_error("the chunk consumer of dv_infer_cutouts_stream asked to stop at stamp %ld", (long)o);
+      if (j.consumer(j.user, r, nb, p->hloc[b], p->hscale[b]) != 0) {
+        set_error("the chunk consumer of dv_infer_cutouts_stream asked to stop at stamp %ld", (long)r);
         return E_STATE;
       }
       return OK;
     }
-    if (loc) host_copy(loc + o * stamp, p->hloc[b], nb * stamp, false, p->threads);
-    if (scale) host_copy(scale + o * stamp, p->hscale[b], nb * stamp, false, p->threads);
-    if (eps_out) host_copy(eps_out + o * stamp, p->heps[b], nb * stamp, false, p->threads);
-    if (mu) memcpy(mu + o * d, p->hsmall[b], (size_t)nb * d * sizeof(float));
-    if (zstd) memcpy(zstd + o * d, p->hsmall[b] + (size_t)chunk * d, (size_t)nb * d * sizeof(float));
-    if (z) memcpy(z + o * d, p->hsmall[b] + (size_t)2 * chunk * d, (size_t)nb * d * sizeof(float));
+    if (j.loc) host_copy(j.loc + r * stamp, p->hloc[b], nb * stamp, false, p->threads);
+    if (j.scale) host_copy(j.scale + r * stamp, p->hscale[b], nb * stamp, false, p->threads);
+    if (j.eps_out) host_copy(j.eps_out + r * stamp, p->heps[b], nb * stamp, false, p->threads);
+    if (j.mu) memcpy(j.mu + r * d, p->hsmall[b], (size_t)nb * d * sizeof(float));
+    if (j.zstd) memcpy(j.zstd + r * d, p->hsmall[b] + (size_t)chunk * d, (size_t)nb * d * sizeof(float));
+    if (j.z) memcpy(j.z + r * d, p->hsmall[b] + (size_t)2 * chunk * d, (size_t)nb * d * sizeof(float));
     return OK;
   };
   auto stage_in = [&](int64_t k) -> int {     // stage A, host part: caller's array -> pinned (float64 cast here)
-    if (cut) return OK;                       // cutouts are gathered on the GPU, no host staging
+    if (!j.x) return OK;                      // cutouts are gathered on the GPU, no host staging
     const int b = (int)(k & 1);
-    const int64_t o = k * chunk;
-    const int nb = (int)std::min<int64_t>(chunk, N - o);
+    const int64_t r = row0 + k * chunk;
+    const int nb = (int)std::min<int64_t>(chunk, N - k * chunk);
     if (k >= 2) DV_HIP(hipEventSynchronize(p->ev_h2d[b]));            // pinned input buffer b is free again
-    const char* xb = static_cast<const char*>(x) + (size_t)o * stamp * (x_f64 ? sizeof(double) : sizeof(float));
-    host_copy(p->hin[b], xb, nb * stamp, x_f64, p->threads);
+    const char* xb = static_cast<const char*>(j.x) + (size_t)r * stamp * (j.x_f64 ? sizeof(double) : sizeof(float));
+    host_copy(p->hin[b], xb, nb * stamp, j.x_f64, p->threads);
     return OK;
   };
   static const bool trace = getenv("DV_PIPE_TRACE") != nullptr;
@@ -3113,11 +3109,13 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
     const int nb = (int)std::min<int64_t>(chunk, N - k * chunk);
     if (k >= 2) DV_HIP(hipStreamWaitEvent(p->s_in, p->ev_comp[b], 0));   // forward of chunk k-2 has read din[b]
     if (trace) DV_HIP(hipEventRecord(tev[6 * k + 0], p->s_in));
-    if (cut)
-      DV_TRY(launch_scene_extract_f32(cut->field, cut->F, cut->nb, cut->starts + 2 * k * chunk, nb, cut->cs, p->din[b], p->s_in,
-                                      cut->sfield ? cut->sfield + k * chunk : nullptr, cut->f0));
-    else
+    if (j.x) {
       DV_HIP(hipMemcpyAsync(p->din[b], p->hin[b], nb * stamp * sizeof(float), hipMemcpyHostToDevice, p->s_in));
+    } else {
+      const int64_t r = row0 + k * chunk;
+      DV_TRY(launch_scene_extract_f32(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, nb, cs, p->din[b], p->s_in,
+                                      j.sfield_d + r, j.f0));
+    }
     if (trace) DV_HIP(hipEventRecord(tev[6 * k + 1], p->s_in));
     DV_HIP(hipEventRecord(p->ev_h2d[b], p->s_in));
     return OK;
@@ -3128,8 +3126,8 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
   }
   for (int64_t k = 0; k < K; ++k) {
     const int b = (int)(k & 1);
-    const int64_t o = k * chunk;
-    const int nb = (int)std::min<int64_t>(chunk, N - o);
+    const int64_t r = row0 + k * chunk;       // the chunk's first stamp
+    const int nb = (int)std::min<int64_t>(chunk, N - k * chunk);
     // the NEXT chunk's input goes into the copy queue before this chunk's outputs: copies issued later would
     // otherwise sit behind a D2H that cannot start until this chunk's forward has finished
     if (k + 1 < K) {
@@ -3148,23 +3146,23 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
       m->loc = p->dloc[b];
       m->scale = p->dscale[b];
       const int st = forward_all(m, p->din[b], nullptr, nullptr, 0, nb, nb, false, false, false,
-                                 eps ? eps + o * d : nullptr, seed, (unsigned)m->ctx->rank, (unsigned)(row0 + o), zstd != nullptr,
-                                 false, true);
+                                 j.eps ? j.eps + r * d : nullptr, j.seed, (unsigned)m->ctx->rank, (unsigned)r,
+                                 j.zstd != nullptr, false, true);
       m->loc = keep_loc;
       m->scale = keep_scale;
       DV_TRY(st);
     }
-    if (m->normalise && (loc || sink || comp)) DV_TRY(launch_normalise(p->dloc[b], (long)nb * stamp, true, s));
-    if (mu)
+    if (m->normalise && (j.loc || j.consumer || comp)) DV_TRY(launch_normalise(p->dloc[b], (long)nb * stamp, true, s));
+    if (j.mu)
       DV_HIP(hipMemcpy2DAsync(p->dsmall[b], d * sizeof(float), m->t, A.twp * sizeof(float), d * sizeof(float), nb,
                               hipMemcpyDeviceToDevice, s));
-    if (zstd)
+    if (j.zstd)
       DV_TRY(copy_rows(p->dsmall[b] + (size_t)chunk * d, d, m->zstd, A.dp, d, nb, hipMemcpyDeviceToDevice, s));
-    if (z)
+    if (j.z)
       DV_TRY(copy_rows(p->dsmall[b] + (size_t)2 * chunk * d, d, m->z, A.dp, d, nb, hipMemcpyDeviceToDevice, s));
-    if (mc) {
+    if (j.mc_samples > 0) {
       // Monte-Carlo stage: dv_infer_mc's decodes on the encoder output the forward pass above left in m->t (no second
-      // encoder pass, nothing staged from the host); sample j of stamp i draws Philox (mc seed + j, global stamp number), what
+      // encoder pass, nothing staged from the host); sample q of stamp i draws Philox (mc seed + q, global stamp number), what
       // dv_infer_mc draws for row i of the whole stamp list.  The std stamps stay in m->gB for this chunk's sinks on the
       // output stream, so the statistics of chunk k wait until the sinks of chunk k - 1 have read theirs (they finished
       // during this chunk's forward pass).
@@ -3176,7 +3174,7 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
         DV_TRY(bn_prepare(m, p->din[b], nullptr, 0, nb, nb, false, false));
         DV_TRY(encoder_forward(m, p->din[b], nullptr, 0, nb, false));
       }
-      DV_TRY(mc_decode_stats(m, nb, mc->nsamples, mc->seed, (unsigned)(row0 + o)));
+      DV_TRY(mc_decode_stats(m, nb, j.mc_samples, j.mc_seed, (unsigned)r));
     }
     if (trace) DV_HIP(hipEventRecord(tev[6 * k + 3], s));
     DV_HIP(hipEventRecord(p->ev_comp[b], s));
@@ -3190,26 +3188,20 @@ static int infer_pipelined(dv_model* m, const void* x, bool x_f64, int64_t N, co
       // latency-bound ones); chunks composite in order because they share this stream, and the forward of chunk k + 2
       // waits for ev_d2h below before it overwrites the outputs this launch reads
       ProfScope ps(m, 2, p->s_out);
-      if (cut->fptr) {
-        // the fields this chunk's stamps belong to: one row of workgroups per field, each scanning its own objects
-        const int fy0 = cut->sfield_h[o], fy1 = cut->sfield_h[o + nb - 1];
-        DV_TRY(launch_scene_composite_chunk(comp->mean_f, comp->std_f, comp->res_f, cut->F, cut->nb, p->dloc[b], p->dscale[b],
-                                            comp->places + 2 * o, nb, cut->cs, p->s_out, cut->fptr, cut->f0, fy0,
-                                            fy1 - fy0 + 1, (long)(row0 + o), comp->eps_f, comp->eps_f ? m->gB : nullptr));
-      } else {
-        DV_TRY(launch_scene_composite_chunk(comp->mean_f, comp->std_f, comp->res_f, cut->F, cut->nb, p->dloc[b], p->dscale[b],
-                                            comp->places + 2 * o, nb, cut->cs, p->s_out));
-      }
-      if (comp->eps_norm)
-        DV_TRY(launch_scene_eps_norm(m->gB, p->dloc[b], nb, cut->cs, cut->nb, comp->eps_norm + o, p->s_out));
-      if (comp->mse)
-        DV_TRY(launch_scene_center_mse(cut->field, cut->F, cut->nb, cut->starts + 2 * o, p->dloc[b], nb, cut->cs,
-                                       comp->mse + o, p->s_out, cut->sfield ? cut->sfield + o : nullptr, cut->f0));
+      // the fields this chunk's stamps belong to: one row of workgroups per field, each scanning its own objects
+      const int fy0 = j.sfield[r], fy1 = j.sfield[r + nb - 1];
+      DV_TRY(launch_scene_composite_chunk(j.mean_f, j.std_f, j.res_f, j.F, j.nb, p->dloc[b], p->dscale[b],
+                                          j.places_d + 2 * r, nb, cs, p->s_out, j.fptr_d, j.f0, fy0, fy1 - fy0 + 1,
+                                          (long)r, j.eps_f, j.eps_f ? m->gB : nullptr));
+      if (j.eps_norm) DV_TRY(launch_scene_eps_norm(m->gB, p->dloc[b], nb, cs, j.nb, j.eps_norm + r, p->s_out));
+      if (j.mse)
+        DV_TRY(launch_scene_center_mse(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, p->dloc[b], nb, cs, j.mse + r, p->s_out,
+                                       j.sfield_d + r, j.f0));
     }
-    if (loc || sink) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
-    if (scale || sink) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
-    if (eps_out) DV_HIP(hipMemcpyAsync(p->heps[h], m->gB, nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
-    if (mu || zstd || z)
+    if (j.loc || j.consumer) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
+    if (j.scale || j.consumer) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
+    if (j.eps_out) DV_HIP(hipMemcpyAsync(p->heps[h], m->gB, nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
+    if (j.mu || j.zstd || j.z)
       DV_HIP(hipMemcpyAsync(p->hsmall[h], p->dsmall[b], (size_t)chunk * 3 * d * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (trace) DV_HIP(hipEventRecord(tev[6 * k + 5], p->s_out));
     DV_HIP(hipEventRecord(p->ev_d2h[h], p->s_out));
@@ -4291,7 +4283,19 @@ static int infer_entry(dv_model* m, const void* x, bool x_f64, int64_t N, const 
   hipStream_t s = m->ctx->stream;
   const size_t stamp = (size_t)A.H * A.H * A.C;
   if (N > 256 && !m->prof_on) {
-    DV_TRY(infer_pipelined(m, x, x_f64, N, eps, seed, loc, scale, mu, zstd, z));
+    PipeJob j;
+    j.x = x;
+    j.x_f64 = x_f64;
+    j.N = N;
+    j.chunk = infer_chunk(m, N);
+    j.eps = eps;
+    j.seed = seed;
+    j.loc = loc;
+    j.scale = scale;
+    j.mu = mu;
+    j.zstd = zstd;
+    j.z = z;
+    DV_TRY(infer_pipelined(m, j));
     return prof_flush(m);
   }
   std::vector<float> cast;
@@ -4408,176 +4412,25 @@ int dv_infer_f64(dv_model* m, const double* x, int64_t N, const float* eps, uint
   return infer_entry(m, x, true, N, eps, seed, loc, scale, mu, zstd, z);
 }
 
-static int infer_cutouts_impl(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts, int64_t N,
-                              uint64_t seed, float* loc, float* scale, float* mu, float* zstd, float* z, dv_chunk_fn sink,
-                              void* sink_user, double* cutouts = nullptr) {
-  if (!m || !field || !starts || N < 0 || F < 1) return DV_E_INVALID;
-  const Arch& A = m->A;
-  const int cs = A.H;
-  if (nb != A.C || cs > F) {
-    set_error("dv_infer_cutouts: the field has %d bands and %d pixels, the network takes %d x %d x %d stamps", nb, F, cs, cs,
-              A.C);
-    return DV_E_INVALID;
-  }
-  for (int64_t i = 0; i < N; ++i) {
-    const int x = starts[2 * i], y = starts[2 * i + 1];
-    if (x < 0 || y < 0 || x > F - cs || y > F - cs) {   // (cs <= F holds; no x + cs: it overflows near INT_MAX)
-      set_error("dv_infer_cutouts: cutout %ld (start %d,%d size %d) leaves the %d-pixel field", (long)i, x, y, cs, F);
-      return DV_E_INVALID;
-    }
-  }
-  if (N == 0) return DV_OK;
-  TinyCall tiny(m, N);
-  DV_HIP(hipSetDevice(m->ctx->device));
-  hipStream_t s = m->ctx->stream;
-  double* fdev = nullptr;
-  int* sdev = nullptr;
-  const size_t fb = (size_t)F * F * nb * sizeof(double), sb = (size_t)N * 2 * sizeof(int);
-  if (hipMalloc((void**)&fdev, fb) != hipSuccess || hipMalloc((void**)&sdev, sb) != hipSuccess) {
-    (void)hipFree(fdev);
-    set_error("dv_infer_cutouts: out of device memory for the field (%zu bytes)", fb);
-    return DV_E_NOMEM;
-  }
-  static const bool trace = getenv("DV_PIPE_TRACE") != nullptr;
-  const auto t0 = std::chrono::steady_clock::now();
-  auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-  int st = OK;
-  if (hipMemcpyAsync(fdev, field, fb, hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(sdev, starts, sb, hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)      // the gather runs on the pipeline's copy stream
-    st = E_HIP;
-  const double t_up = since();
-  if (st == OK) {
-    CutoutSrc cut{fdev, sdev, F, nb, cs};
-    CutoutKeep keep{field, starts, cutouts};
-    st = infer_pipelined(m, nullptr, false, N, nullptr, seed, loc, scale, mu, zstd, z, &cut, sink, sink_user, nullptr,
-                         cutouts ? &keep : nullptr);
-  }
-  (void)hipStreamSynchronize(s);
-  const double t_pipe = since();
-  (void)hipFree(fdev);
-  (void)hipFree(sdev);
-  if (trace)
-    fprintf(stderr, "cutouts call: field + starts upload %.1f ms, pipeline %.1f ms, free %.1f ms (%ld stamps)\n", t_up,
-            t_pipe - t_up, since() - t_pipe, (long)N);
-  if (st != OK) return st;
-  return prof_flush(m);
-}
-
-int dv_infer_cutouts_composite(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts,
-                               const int32_t* places, int64_t N, uint64_t seed, double* mean_field, double* stddev_field,
-                               double* residual_field, double* mse_center) {
-  if (!m || !field || !starts || !places || !mean_field || !stddev_field || N < 0 || F < 1) return DV_E_INVALID;
-  const Arch& A = m->A;
-  const int cs = A.H;
-  if (nb != A.C || cs > F) {
-    set_error("dv_infer_cutouts_composite: the field has %d bands and %d pixels, the network takes %d x %d x %d stamps", nb, F,
-              cs, cs, A.C);
-    return DV_E_INVALID;
-  }
-  for (int64_t i = 0; i < N; ++i) {
-    const int x = starts[2 * i], y = starts[2 * i + 1];
-    if (x < 0 || y < 0 || x > F - cs || y > F - cs) {
-      set_error("dv_infer_cutouts_composite: cutout %ld (start %d,%d size %d) leaves the %d-pixel field", (long)i, x, y, cs, F);
-      return DV_E_INVALID;
-    }
-    const int pr = places[2 * i], pc = places[2 * i + 1];
-    if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
-      set_error("dv_infer_cutouts_composite: placement %ld (%d,%d) out of range", (long)i, pr, pc);
-      return DV_E_INVALID;
-    }
-  }
-  const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
-  if (N == 0) {
-    memset(mean_field, 0, fb);
-    memset(stddev_field, 0, fb);
-    if (residual_field) memcpy(residual_field, field, fb);
-    return DV_OK;
-  }
-  TinyCall tiny(m, N);
-  DV_HIP(hipSetDevice(m->ctx->device));
-  hipStream_t s = m->ctx->stream;
-  double *fdev = nullptr, *mf = nullptr, *sf = nullptr, *rf = nullptr, *mse = nullptr;
-  int *sdev = nullptr, *pdev = nullptr;
-  const size_t sb = (size_t)N * 2 * sizeof(int);
-  int st = OK;
-  auto cleanup = [&]() {
-    if (st != OK && m->pipe && m->pipe->s_out) (void)hipStreamSynchronize(m->pipe->s_out);   // nothing may still read these
-    (void)hipFree(fdev); (void)hipFree(mf); (void)hipFree(sf); (void)hipFree(rf); (void)hipFree(mse);
-    (void)hipFree(sdev); (void)hipFree(pdev);
-  };
-#define CC_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
-  CC_HIP(hipMalloc((void**)&fdev, fb));
-  CC_HIP(hipMalloc((void**)&mf, fb));
-  CC_HIP(hipMalloc((void**)&sf, fb));
-  if (residual_field) CC_HIP(hipMalloc((void**)&rf, fb));
-  if (mse_center) CC_HIP(hipMalloc((void**)&mse, (size_t)N * sizeof(double)));
-  CC_HIP(hipMalloc((void**)&sdev, sb));
-  CC_HIP(hipMalloc((void**)&pdev, sb));
-  CC_HIP(hipMemcpyAsync(fdev, field, fb, hipMemcpyHostToDevice, s));
-  CC_HIP(hipMemcpyAsync(sdev, starts, sb, hipMemcpyHostToDevice, s));
-  CC_HIP(hipMemcpyAsync(pdev, places, sb, hipMemcpyHostToDevice, s));
-  CC_HIP(hipMemsetAsync(mf, 0, fb, s));
-  CC_HIP(hipMemsetAsync(sf, 0, fb, s));
-  if (rf) CC_HIP(hipMemcpyAsync(rf, fdev, fb, hipMemcpyDeviceToDevice, s));
-  CC_HIP(hipStreamSynchronize(s));               // the gather runs on the pipeline's copy stream
-  {
-    CutoutSrc cut{fdev, sdev, F, nb, cs};
-    CompositeSink comp{mf, sf, rf, pdev, mse};
-    st = infer_pipelined(m, nullptr, false, N, nullptr, seed, nullptr, nullptr, nullptr, nullptr, nullptr, &cut, nullptr,
-                         nullptr, &comp);
-  }
-  if (st == OK) {
-    CC_HIP(hipMemcpyAsync(mean_field, mf, fb, hipMemcpyDeviceToHost, s));
-    CC_HIP(hipMemcpyAsync(stddev_field, sf, fb, hipMemcpyDeviceToHost, s));
-    if (rf) CC_HIP(hipMemcpyAsync(residual_field, rf, fb, hipMemcpyDeviceToHost, s));
-    if (mse) CC_HIP(hipMemcpyAsync(mse_center, mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  // the results are only defined once the copies have landed: a failed synchronise is this call's error.  On any failure
-  // the pipeline's output stream may still hold compositing launches that read the buffers freed below - drain it first.
-  {
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess && st == OK) st = hip_fail(e, "hipStreamSynchronize(result fields)", __FILE__, __LINE__);
-  }
-  if (st != OK && m->pipe && m->pipe->s_out) (void)hipStreamSynchronize(m->pipe->s_out);
-#undef CC_HIP
-  cleanup();
-  if (st != OK) return st;
-  return prof_flush(m);
-}
-
-int dv_infer_cutouts(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts, int64_t N,
-                     uint64_t seed, float* loc, float* scale, float* mu, float* zstd, float* z) {
-  return infer_cutouts_impl(m, field, F, nb, starts, N, seed, loc, scale, mu, zstd, z, nullptr, nullptr);
-}
-
-int dv_infer_cutouts_keep(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts, int64_t N,
-                          uint64_t seed, float* loc, float* scale, double* cutouts) {
-  if (!cutouts) return DV_E_INVALID;
-  return infer_cutouts_impl(m, field, F, nb, starts, N, seed, loc, scale, nullptr, nullptr, nullptr, nullptr, nullptr, cutouts);
-}
-
-int dv_infer_cutouts_stream(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts, int64_t N,
-                            uint64_t seed, dv_chunk_fn consumer, void* user) {
-  if (!consumer) return DV_E_INVALID;
-  return infer_cutouts_impl(m, field, F, nb, starts, N, seed, nullptr, nullptr, nullptr, nullptr, nullptr, consumer, user);
-}
-
 // ---- many fields in one call (dv_infer_fields, _keep, _composite) ------------------------------------------
 // The stamps of M fields form one global list (field_ptr[m] .. field_ptr[m + 1] are cut from field m) that runs through the
 // pipeline in the chunks dv_infer makes for N stamps, whatever field a stamp belongs to; stamp i draws Philox row i.  The
 // fields are uploaded in groups of consecutive fields sized against free device memory; a group covers whole chunks, so a
 // field whose stamps straddle two groups is resident in both (and its partly composited results travel with it).
+// The single-field calls (dv_infer_cutouts*) are this with M = 1.
 struct FieldsOut {                  // result fields of dv_infer_fields_composite, host [M][F][F][nb]; null otherwise
   double *mean = nullptr, *stddev = nullptr, *residual = nullptr, *mse = nullptr;
   const int32_t* places = nullptr;
   double *epistemic = nullptr, *eps_norm = nullptr;   // dv_infer_fields_mc_composite: [M][F][F][nb] and [N]
 };
 
-static int infer_fields_impl(dv_model* m, const char* who, const double* fields, int32_t M, int32_t F, int32_t nb,
-                             const int32_t* starts, const int64_t* field_ptr, int64_t N, uint64_t seed, float* loc,
-                             float* scale, float* mu, float* zstd, float* z, double* cutouts, const FieldsOut* fo,
-                             const McStage* mc = nullptr) {
+// j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
+// the device side and the rows are filled in here
+static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
+                             const FieldsOut* fo = nullptr) {
+  const double* fields = j.fields;
+  const int32_t* starts = j.starts;
+  const int F = j.F, nb = j.nb;
   if (!m || !field_ptr || M < 0 || N < 0 || F < 1 || (M > 0 && !fields) || (N > 0 && !starts)) return DV_E_INVALID;
   const Arch& A = m->A;
   const int cs = A.H;
@@ -4708,8 +4561,19 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
   FF_HIP(hipMemcpyAsync(sdev, starts, sb, hipMemcpyHostToDevice, s));
   FF_HIP(hipMemcpyAsync(sfdev, sfield.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
   FF_HIP(hipMemcpyAsync(fpdev, fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-  const size_t stamp = (size_t)A.H * A.H * A.C;
-  const int d = A.d;
+  j.fields_d = fdev;
+  j.starts_d = sdev;
+  j.sfield = sfield.data();
+  j.sfield_d = sfdev;
+  j.fptr_d = fpdev;
+  j.chunk = chunk;
+  j.mean_f = mf;
+  j.std_f = sf;
+  j.res_f = rf;
+  j.eps_f = ef;
+  j.places_d = pdev;
+  j.mse = mse;
+  j.eps_norm = en;
   int prev_last = -1;
   for (const Group& g : groups) {
     const size_t ng = (size_t)(g.f1 - g.f0 + 1), goff = (size_t)g.f0 * felems;
@@ -4728,24 +4592,10 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
       }
     }
     FF_HIP(hipStreamSynchronize(s));               // the gather runs on the pipeline's copy stream
-    const int64_t r0 = g.k0 * chunk, n = std::min<int64_t>(N, g.k1 * chunk) - r0;
-    CutoutSrc cut{fdev, sdev + 2 * r0, F, nb, cs};
-    cut.sfield = sfdev + r0;
-    cut.sfield_h = sfield.data() + r0;
-    cut.fptr = fpdev;
-    cut.f0 = g.f0;
-    cut.row0 = r0;
-    cut.chunk = chunk;
-    CutoutKeep keep{fields, starts + 2 * r0, cutouts ? cutouts + r0 * stamp : nullptr, sfield.data() + r0};
-    CompositeSink comp{mf, sf, rf, pdev ? pdev + 2 * r0 : nullptr, mse ? mse + r0 : nullptr};
-    comp.eps_f = ef;
-    comp.eps_norm = en ? en + r0 : nullptr;
-    McStage mcg{0, 0, nullptr};
-    if (mc) mcg = McStage{mc->nsamples, mc->seed, mc->eps_out ? mc->eps_out + r0 * stamp : nullptr};
-    st = infer_pipelined(m, nullptr, false, n, nullptr, seed, loc ? loc + r0 * stamp : nullptr,
-                         scale ? scale + r0 * stamp : nullptr, mu ? mu + r0 * d : nullptr, zstd ? zstd + r0 * d : nullptr,
-                         z ? z + r0 * d : nullptr, &cut, nullptr, nullptr, fo ? &comp : nullptr, cutouts ? &keep : nullptr,
-                         mc ? &mcg : nullptr);
+    j.f0 = g.f0;
+    j.row0 = g.k0 * chunk;
+    j.N = std::min<int64_t>(N, g.k1 * chunk) - j.row0;
+    st = infer_pipelined(m, j);
     if (st != OK) {
       (void)hipStreamSynchronize(s);
       cleanup();
@@ -4773,19 +4623,92 @@ static int infer_fields_impl(dv_model* m, const char* who, const double* fields,
   return prof_flush(m);
 }
 
+// the host side of a field-sourced job: what every dv_infer_cutouts* / dv_infer_fields* call gives
+static PipeJob fields_job(const double* fields, int32_t F, int32_t nb, const int32_t* starts, uint64_t seed) {
+  PipeJob j;
+  j.fields = fields;
+  j.F = F;
+  j.nb = nb;
+  j.starts = starts;
+  j.seed = seed;
+  return j;
+}
+
+// ---- one field (dv_infer_cutouts, _keep, _stream, _composite): the many-field call with M = 1 ------------------------------
+static int infer_one_field(dv_model* m, const char* who, int64_t N, const PipeJob& j, const FieldsOut* fo = nullptr) {
+  if (!j.fields || !j.starts) return DV_E_INVALID;
+  const int64_t field_ptr[2] = {0, N};
+  return infer_fields_impl(m, who, 1, field_ptr, N, j, fo);
+}
+
+int dv_infer_cutouts(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts, int64_t N,
+                     uint64_t seed, float* loc, float* scale, float* mu, float* zstd, float* z) {
+  PipeJob j = fields_job(field, F, nb, starts, seed);
+  j.loc = loc;
+  j.scale = scale;
+  j.mu = mu;
+  j.zstd = zstd;
+  j.z = z;
+  return infer_one_field(m, "dv_infer_cutouts", N, j);
+}
+
+int dv_infer_cutouts_keep(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts, int64_t N,
+                          uint64_t seed, float* loc, float* scale, double* cutouts) {
+  if (!cutouts) return DV_E_INVALID;
+  PipeJob j = fields_job(field, F, nb, starts, seed);
+  j.loc = loc;
+  j.scale = scale;
+  j.cutouts = cutouts;
+  return infer_one_field(m, "dv_infer_cutouts_keep", N, j);
+}
+
+int dv_infer_cutouts_stream(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts, int64_t N,
+                            uint64_t seed, dv_chunk_fn consumer, void* user) {
+  if (!consumer) return DV_E_INVALID;
+  PipeJob j = fields_job(field, F, nb, starts, seed);
+  j.consumer = consumer;
+  j.user = user;
+  return infer_one_field(m, "dv_infer_cutouts_stream", N, j);
+}
+
+int dv_infer_cutouts_composite(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts,
+                               const int32_t* places, int64_t N, uint64_t seed, double* mean_field, double* stddev_field,
+                               double* residual_field, double* mse_center) {
+  if (!places || !mean_field || !stddev_field) return DV_E_INVALID;
+  FieldsOut fo;
+  fo.mean = mean_field;
+  fo.stddev = stddev_field;
+  fo.residual = residual_field;
+  fo.mse = mse_center;
+  fo.places = places;
+  return infer_one_field(m, "dv_infer_cutouts_composite", N, fields_job(field, F, nb, starts, seed), &fo);
+}
+
+// ---- many fields ------------------------------------------------------------------------------------------------------------
 int dv_infer_fields(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
                     const int64_t* field_ptr, int64_t N, uint64_t seed, float* loc, float* scale, float* mu, float* zstd,
                     float* z) {
-  return infer_fields_impl(m, "dv_infer_fields", fields, M, F, nb, starts, field_ptr, N, seed, loc, scale, mu, zstd, z,
-                           nullptr, nullptr);
+  PipeJob j = fields_job(fields, F, nb, starts, seed);
+  j.loc = loc;
+  j.scale = scale;
+  j.mu = mu;
+  j.zstd = zstd;
+  j.z = z;
+  return infer_fields_impl(m, "dv_infer_fields", M, field_ptr, N, j);
 }
 
 int dv_infer_fields_keep(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
                          const int64_t* field_ptr, int64_t N, uint64_t seed, float* loc, float* scale, float* mu,
                          float* zstd, float* z, double* cutouts) {
   if (!cutouts && N > 0) return DV_E_INVALID;
-  return infer_fields_impl(m, "dv_infer_fields_keep", fields, M, F, nb, starts, field_ptr, N, seed, loc, scale, mu, zstd, z,
-                           cutouts, nullptr);
+  PipeJob j = fields_job(fields, F, nb, starts, seed);
+  j.loc = loc;
+  j.scale = scale;
+  j.mu = mu;
+  j.zstd = zstd;
+  j.z = z;
+  j.cutouts = cutouts;
+  return infer_fields_impl(m, "dv_infer_fields_keep", M, field_ptr, N, j);
 }
 
 int dv_infer_fields_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
@@ -4798,8 +4721,7 @@ int dv_infer_fields_composite(dv_model* m, const double* fields, int32_t M, int3
   fo.residual = residual_fields;
   fo.mse = mse_center;
   fo.places = places;
-  return infer_fields_impl(m, "dv_infer_fields_composite", fields, M, F, nb, starts, field_ptr, N, seed, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, &fo);
+  return infer_fields_impl(m, "dv_infer_fields_composite", M, field_ptr, N, fields_job(fields, F, nb, starts, seed), &fo);
 }
 
 // the refusals of the two Monte-Carlo forms, before any GPU work
@@ -4825,9 +4747,14 @@ int dv_infer_fields_mc_keep(dv_model* m, const double* fields, int32_t M, int32_
     set_error("dv_infer_fields_mc_keep: loc, scale, cutouts and epistemic must all be given");
     return DV_E_INVALID;
   }
-  McStage mc{nsamples, mc_seed, epistemic};
-  return infer_fields_impl(m, "dv_infer_fields_mc_keep", fields, M, F, nb, starts, field_ptr, N, seed, loc, scale, nullptr,
-                           nullptr, nullptr, cutouts, nullptr, &mc);
+  PipeJob j = fields_job(fields, F, nb, starts, seed);
+  j.loc = loc;
+  j.scale = scale;
+  j.cutouts = cutouts;
+  j.eps_out = epistemic;
+  j.mc_samples = nsamples;
+  j.mc_seed = mc_seed;
+  return infer_fields_impl(m, "dv_infer_fields_mc_keep", M, field_ptr, N, j);
 }
 
 int dv_infer_fields_mc_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
@@ -4847,9 +4774,10 @@ int dv_infer_fields_mc_composite(dv_model* m, const double* fields, int32_t M, i
   fo.places = places;
   fo.epistemic = epistemic_fields;
   fo.eps_norm = eps_norm;
-  McStage mc{nsamples, mc_seed, nullptr};
-  return infer_fields_impl(m, "dv_infer_fields_mc_composite", fields, M, F, nb, starts, field_ptr, N, seed, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, &fo, &mc);
+  PipeJob j = fields_job(fields, F, nb, starts, seed);
+  j.mc_samples = nsamples;
+  j.mc_seed = mc_seed;
+  return infer_fields_impl(m, "dv_infer_fields_mc_composite", M, field_ptr, N, j, &fo);
 }
 
 int dv_infer_mc(dv_model* m, const float* x, int64_t N, int32_t nsamples, uint64_t seed, float* mean_out,

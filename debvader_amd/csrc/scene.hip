@@ -33,8 +33,8 @@ struct SceneObj {
 // (the first version decoded a flat 64-bit element index with four divisions per element: 1.08 ms per 8192-cutout chunk of
 // the inference pipeline, 0.41 ms now).  OUT = double: the reference's cutouts; OUT = float: cast as deblend() does
 // (tf.cast, deblender.py:18), straight into the network's input buffer.
-// Many fields (dv_infer_fields*): `field` is the first resident field f0 of a stack of F x F x nb fields and sfield[n] the
-// field cutout n is cut from - one lookup per workgroup, uniform for all its threads.  sfield = null: one field.
+// `field` is the first resident field f0 of a stack of F x F x nb fields and sfield[n] the field cutout n is cut from - one
+// lookup per workgroup, uniform for all its threads.  sfield = null (dv_scene_extract only): one field.
 template <typename OUT>
 __global__ __launch_bounds__(256) void scene_extract_kernel(const double* __restrict__ field, int F, int nb,
                                                             const int* __restrict__ starts, int cs, OUT* __restrict__ out,
@@ -177,11 +177,11 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(double* __restrict
 // scattered cutouts leave ~4 entries per round and tile; a pile of objects on one spot just makes the lists long (a
 // round's list holds all 2048) - no capacity limit, no atomics, no float non-determinism.
 //
-// Many fields (dv_infer_fields_composite, fptr != null): the three result pointers address a stack of fields starting at
-// field f0, blockIdx.y + fy0 is the field this workgroup's tile belongs to, and the workgroup scans only that field's objects
+// The three result pointers address a stack of fields starting at field f0 (one field for dv_infer_cutouts_composite),
+// blockIdx.y + fy0 is the field this workgroup's tile belongs to, and the workgroup scans only that field's objects
 // of the chunk: fptr[m] .. fptr[m + 1] (global stamp numbers) cut to the chunk [obase, obase + n).  A field has its own
-// workgroups, so two fields never meet in a sum, and within a field the order of additions is object order as before: a
-// field's result has the bits the single-field call gives.  A field without objects in the chunk returns at once.
+// workgroups, so two fields never meet in a sum, and within a field the order of additions is object order: a field's
+// result has the same bits whatever other fields the call holds.  A field without objects in the chunk returns at once.
 //
 // EPS (dv_infer_fields_mc_composite): a third sum, eps_f += the chunk's Monte-Carlo std stamps `eps` (float32, one per stamp,
 // as the Welford fold left them), with the placement, the object order and the load-add-store across chunks of the other two;
@@ -214,19 +214,16 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
     }
   bool loaded = false;
   unsigned touched = 0;
-  int olo = 0;
-  if (fptr) {                            // uniform over the workgroup
-    const int m = fy0 + (int)blockIdx.y;
-    const long lo = (long)fptr[m] - obase, hi = (long)fptr[m + 1] - obase;
-    olo = (int)(lo > 0 ? lo : 0);
-    n = (int)(hi < n ? hi : n);
-    if (olo >= n) return;
-    const long fo = (long)(m - f0) * F * F * nb;
-    mean_f += fo;
-    std_f += fo;
-    if (res_f) res_f += fo;
-    if constexpr (EPS) eps_f += fo;
-  }
+  const int m = fy0 + (int)blockIdx.y;   // uniform over the workgroup
+  const long lo = (long)fptr[m] - obase, hi = (long)fptr[m + 1] - obase;
+  const int olo = (int)(lo > 0 ? lo : 0);
+  n = (int)(hi < n ? hi : n);
+  if (olo >= n) return;
+  const long fo = (long)(m - f0) * F * F * nb;
+  mean_f += fo;
+  std_f += fo;
+  if (res_f) res_f += fo;
+  if constexpr (EPS) eps_f += fo;
   for (int seg = olo; seg < n; seg += CSEG) {
     // thread t tests objects seg + 8 t .. + 7 (four 16-byte loads of their placements): order by (thread, bit) = object order
     const int o0 = seg + tid * 8;
@@ -425,7 +422,7 @@ __global__ __launch_bounds__(256) void scene_center_mse_kernel(const double* __r
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * 4 + wave;
   const bool valid = i < n;                                      // (uniform over the wave)
-  if (valid && sfield) field += (long)(sfield[i] - f0) * F * F * nb;      // the field stamp i was cut from (uniform over the wave)
+  if (valid) field += (long)(sfield[i] - f0) * F * F * nb;      // the field stamp i was cut from (uniform over the wave)
   const int c0 = cs / 2 - 5, w = 10;
   const int x0 = valid ? starts[2 * i] : 0, y0 = valid ? starts[2 * i + 1] : 0;
   const int total = w * w * nb;
@@ -570,11 +567,11 @@ int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, i
     return E_INVALID;
   }
   const int ntx = (F + CT - 1) / CT;
-  if (fptr_dev && (nfields < 1 || nfields > 65535)) {
+  if (nfields < 1 || nfields > 65535) {
     set_error("scene composite: a chunk spans %d fields, at most 65535", nfields);
     return E_INVALID;
   }
-  const dim3 grid((unsigned)(ntx * ntx), fptr_dev ? (unsigned)nfields : 1u);
+  const dim3 grid((unsigned)(ntx * ntx), (unsigned)nfields);
 #define SCC_LAUNCH(NBMAX, EPS)                                                                                          \
   hipLaunchKernelGGL((scene_composite_chunk_kernel<NBMAX, EPS>), grid, dim3(256), 0, s, mean_f, std_f, res_f, F, nb, loc, \
                      scale, places_dev, n, cs, fptr_dev, f0, fy0, obase, eps_f, eps)

@@ -89,6 +89,16 @@ def _fp(a: Optional[np.ndarray]):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _dp(a: Optional[np.ndarray]):
+    if a is None:
+        return None
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _ip(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
 def _i32_rows(a, what: str) -> np.ndarray:
     """Integer (x, y) rows for the C-ABI's int32 arrays.  A plain astype would wrap 64-bit values into range silently -
     a start of 2**32 + 5 would fetch the cutout at 5 - so the range is checked before the cast."""
@@ -756,110 +766,9 @@ class Engine:
         off by default - a train step has no reader for them."""
         check(lib.dv_model_set_keep_outputs(self._h, 1 if on else 0))
 
-    def infer(self, x, eps=None, seed=0, want=("loc", "scale"), out=None) -> Dict[str, np.ndarray]:
-        """One stochastic forward pass over all stamps.  float64 arrays (numpy's default, what the reference's callers
-        pass) go to the engine as they are: the float32 cast of deblender.py:18 happens while the library stages them."""
-        x = np.asarray(x)
-        f64 = x.dtype == np.float64 and x.flags.c_contiguous
-        if not f64:
-            x = _f32c(x)
-        if x.ndim != 4 or x.shape[1:] != self.stamp_shape:
-            raise ValueError(f"expected images of shape (N,{self.stamp_shape}), got {x.shape}")
-        N = x.shape[0]
-        bufs = {}
-        for k in ("loc", "scale", "mu", "zstd", "z"):
-            shape = (N,) + self.stamp_shape if k in ("loc", "scale") else (N, self.latent)
-            if k not in want:
-                bufs[k] = None
-            elif out is not None and k in out:      # caller-provided result array (reused across calls)
-                if out[k].shape != shape or out[k].dtype != np.float32 or not out[k].flags.c_contiguous:
-                    raise ValueError(f"out[{k!r}] must be a C-contiguous float32 array of shape {shape}")
-                bufs[k] = out[k]
-            else:
-                bufs[k] = _host_pool.empty(shape, np.float32)
-        if eps is not None:
-            eps = _f32c(eps, (N, self.latent))
-        if f64:
-            check(lib.dv_infer_f64(self._h, x.ctypes.data_as(C.POINTER(C.c_double)), N, _fp(eps), int(seed),
-                                   _fp(bufs["loc"]), _fp(bufs["scale"]), _fp(bufs["mu"]), _fp(bufs["zstd"]), _fp(bufs["z"])))
-        else:
-            check(lib.dv_infer(self._h, _fp(x), N, _fp(eps), int(seed), _fp(bufs["loc"]), _fp(bufs["scale"]),
-                               _fp(bufs["mu"]), _fp(bufs["zstd"]), _fp(bufs["z"])))
-        return {k: v for k, v in bufs.items() if v is not None}
-
-    def infer_cutouts(self, field, starts, seed=0, want=("loc", "scale"), out=None) -> Dict[str, np.ndarray]:
-        """infer() on the cutouts field[x:x+H, y:y+H, :] of a float64 field (F, F, bands) for every row (x, y) of `starts`,
-        gathered and cast on the GPU (dv_infer_cutouts): the stamps never visit the host.  Bit-identical to
-        infer(ctx.scene_extract(field, starts, H)) with the same seed."""
-        field = np.ascontiguousarray(field, dtype=np.float64)
-        starts = _i32_rows(starts, "cutout starts")
-        if field.ndim != 3 or field.shape[0] != field.shape[1]:
-            raise ValueError(f"expected a square field (F, F, bands), got {field.shape}")
-        N = starts.shape[0]
-        bufs = {}
-        for k in ("loc", "scale", "mu", "zstd", "z"):
-            shape = (N,) + self.stamp_shape if k in ("loc", "scale") else (N, self.latent)
-            if k not in want:
-                bufs[k] = None
-            elif out is not None and k in out:
-                if out[k].shape != shape or out[k].dtype != np.float32 or not out[k].flags.c_contiguous:
-                    raise ValueError(f"out[{k!r}] must be a C-contiguous float32 array of shape {shape}")
-                bufs[k] = out[k]
-            else:
-                bufs[k] = _host_pool.empty(shape, np.float32)
-        check(lib.dv_infer_cutouts(self._h, field.ctypes.data_as(C.POINTER(C.c_double)), field.shape[0], field.shape[2],
-                                   starts.ctypes.data_as(C.POINTER(C.c_int32)), N, int(seed), _fp(bufs["loc"]),
-                                   _fp(bufs["scale"]), _fp(bufs["mu"]), _fp(bufs["zstd"]), _fp(bufs["z"])))
-        return {k: v for k, v in bufs.items() if v is not None}
-
-    def infer_cutouts_keep(self, field, starts, seed=0) -> Dict[str, np.ndarray]:
-        """infer_cutouts() for a caller that also needs the float64 cutouts (dv_infer_cutouts_keep): returns
-        {"loc", "scale" (float32), "cutouts" (float64)}, all (N,) + stamp shape.  The cutouts are assembled on the host from the
-        field the caller holds while the GPU runs the forward passes - bit-identical to ctx.scene_extract(field, starts, H) -
-        and mean / stddev are bit-identical to infer(cutouts) with the same seed."""
-        field = np.ascontiguousarray(field, dtype=np.float64)
-        starts = _i32_rows(starts, "cutout starts")
-        if field.ndim != 3 or field.shape[0] != field.shape[1]:
-            raise ValueError(f"expected a square field (F, F, bands), got {field.shape}")
-        N = starts.shape[0]
-        out = {"loc": _host_pool.empty((N,) + self.stamp_shape, np.float32),
-               "scale": _host_pool.empty((N,) + self.stamp_shape, np.float32),
-               "cutouts": _host_pool.empty((N,) + self.stamp_shape, np.float64)}
-        check(lib.dv_infer_cutouts_keep(self._h, field.ctypes.data_as(C.POINTER(C.c_double)), field.shape[0], field.shape[2],
-                                        starts.ctypes.data_as(C.POINTER(C.c_int32)), N, int(seed), _fp(out["loc"]),
-                                        _fp(out["scale"]), out["cutouts"].ctypes.data_as(C.POINTER(C.c_double))))
-        return out
-
-    def infer_cutouts_composite(self, field, starts, places, seed=0, residual=True, mse_center=True) -> Dict[str, np.ndarray]:
-        """infer_cutouts() with the compositing that follows it in the reference done on the GPU (dv_infer_cutouts_composite):
-        returns {"mean_field", "stddev_field", ["residual_field"], ["mse_center"]} - float64 (F, F, bands) sums of the
-        network's mean / stddev stamps placed at `places` (row, col of each stamp's top-left corner; off-field parts are
-        dropped) in object order, the field minus the mean stamps, and each stamp's centre-10x10 MSE against its cutout.
-        No stamp visits the host."""
-        field = np.ascontiguousarray(field, dtype=np.float64)
-        starts = _i32_rows(starts, "cutout starts")
-        places = _i32_rows(places, "stamp placements")
-        if field.ndim != 3 or field.shape[0] != field.shape[1]:
-            raise ValueError(f"expected a square field (F, F, bands), got {field.shape}")
-        if places.shape != starts.shape:
-            raise ValueError(f"{starts.shape[0]} cutout starts but {places.shape[0]} placements")
-        N = starts.shape[0]
-        dp = C.POINTER(C.c_double)
-        out = {"mean_field": np.empty(field.shape, np.float64), "stddev_field": np.empty(field.shape, np.float64)}
-        if residual:
-            out["residual_field"] = np.empty(field.shape, np.float64)
-        if mse_center:
-            out["mse_center"] = np.empty((N,), np.float64)
-        opt = lambda k: out[k].ctypes.data_as(dp) if k in out else None
-        check(lib.dv_infer_cutouts_composite(self._h, field.ctypes.data_as(dp), field.shape[0], field.shape[2],
-                                             starts.ctypes.data_as(C.POINTER(C.c_int32)),
-                                             places.ctypes.data_as(C.POINTER(C.c_int32)), N, int(seed),
-                                             out["mean_field"].ctypes.data_as(dp), out["stddev_field"].ctypes.data_as(dp),
-                                             opt("residual_field"), opt("mse_center")))
-        return out
-
-    # -- many fields in one call (DESIGN.md section 7f) -------------------------------------------
-    def _fields_bufs(self, N, want, out):
+    def _infer_bufs(self, N, want, out=None):
+        """The float32 result arrays of an N-stamp inference call in the C-ABI's order (loc, scale, mu, zstd, z), None for
+        what is not in `want`: the caller's own out[k] (reused across calls) where given, otherwise from the host pool."""
         bufs = {}
         for k in ("loc", "scale", "mu", "zstd", "z"):
             shape = (N,) + self.stamp_shape if k in ("loc", "scale") else (N, self.latent)
@@ -873,66 +782,95 @@ class Engine:
                 bufs[k] = _host_pool.empty(shape, np.float32)
         return bufs
 
-    def infer_fields(self, fields, starts, field_ptr, seed=0, want=("loc", "scale"), out=None) -> Dict[str, np.ndarray]:
-        """infer_cutouts() for the cutouts of M fields (M, F, F, bands) in one engine call (dv_infer_fields): rows
-        field_ptr[m]:field_ptr[m + 1] of `starts` are windows of field m.  The N stamps of all fields form one list that runs
-        through the network in full chunks, whatever field a stamp belongs to; stamp i draws noise row i.  Bit-identical to
-        infer() on the concatenated cutouts with the same seed."""
+    def infer(self, x, eps=None, seed=0, want=("loc", "scale"), out=None) -> Dict[str, np.ndarray]:
+        """One stochastic forward pass over all stamps.  float64 arrays (numpy's default, what the reference's callers
+        pass) go to the engine as they are: the float32 cast of deblender.py:18 happens while the library stages them."""
+        x = np.asarray(x)
+        f64 = x.dtype == np.float64 and x.flags.c_contiguous
+        if not f64:
+            x = _f32c(x)
+        if x.ndim != 4 or x.shape[1:] != self.stamp_shape:
+            raise ValueError(f"expected images of shape (N,{self.stamp_shape}), got {x.shape}")
+        N = x.shape[0]
+        bufs = self._infer_bufs(N, want, out)
+        if eps is not None:
+            eps = _f32c(eps, (N, self.latent))
+        if f64:
+            check(lib.dv_infer_f64(self._h, _dp(x), N, _fp(eps), int(seed), *map(_fp, bufs.values())))
+        else:
+            check(lib.dv_infer(self._h, _fp(x), N, _fp(eps), int(seed), *map(_fp, bufs.values())))
+        return {k: v for k, v in bufs.items() if v is not None}
+
+    # -- cutouts of fields that sit on the GPU (DESIGN.md sections 7, 7f) --------------------------
+    @staticmethod
+    def _field_args(fields, starts, field_ptr, places=None):
+        """The checked inputs of the many-field calls: the float64 fields (M, F, F, bands), the number of stamps, and the
+        C-ABI's arguments from `fields` to `N` (with `places` before field_ptr where the call takes them)."""
         fields = _check_fields(fields)
         starts = _i32_rows(starts, "cutout starts")
+        if places is not None:
+            places = _i32_rows(places, "stamp placements")
+            if places.shape != starts.shape:
+                raise ValueError(f"{starts.shape[0]} cutout starts but {places.shape[0]} placements")
         N = starts.shape[0]
         fp = check_field_ptr(field_ptr, fields.shape[0], N)
-        bufs = self._fields_bufs(N, want, out)
-        check(lib.dv_infer_fields(self._h, fields.ctypes.data_as(C.POINTER(C.c_double)), fields.shape[0], fields.shape[1],
-                                  fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
-                                  fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed), _fp(bufs["loc"]), _fp(bufs["scale"]),
-                                  _fp(bufs["mu"]), _fp(bufs["zstd"]), _fp(bufs["z"])))
+        args = [_dp(fields), fields.shape[0], fields.shape[1], fields.shape[3], _ip(starts)]
+        if places is not None:
+            args.append(_ip(places))
+        return fields, N, args + [fp.ctypes.data_as(C.POINTER(C.c_int64)), N]
+
+    @staticmethod
+    def _composite_out(shape, N, residual, mse_center, epistemic=False):
+        """The result dictionary of the composite calls - float64 fields of `shape`, per-stamp scalars (N,) - and its
+        pointers in the C-ABI's order, None for what is not wanted."""
+        out = {"mean_fields": np.empty(shape, np.float64), "stddev_fields": np.empty(shape, np.float64)}
+        if epistemic:
+            out["epistemic_fields"] = np.empty(shape, np.float64)
+        if residual:
+            out["residual_fields"] = np.empty(shape, np.float64)
+        if mse_center:
+            out["mse_center"] = np.empty((N,), np.float64)
+        if epistemic:
+            out["eps_norm"] = np.empty((N,), np.float64)
+        keys = ["mean_fields", "stddev_fields", "residual_fields", "mse_center"]
+        if epistemic:
+            keys = keys[:2] + ["epistemic_fields"] + keys[2:] + ["eps_norm"]
+        return out, [_dp(out.get(k)) for k in keys]
+
+    def infer_fields(self, fields, starts, field_ptr, seed=0, want=("loc", "scale"), out=None) -> Dict[str, np.ndarray]:
+        """infer() on the cutouts fields[m, x:x+H, y:y+H, :] of M float64 fields (M, F, F, bands), gathered and cast on the
+        GPU in one engine call (dv_infer_fields): rows field_ptr[m]:field_ptr[m + 1] of `starts` are windows (x, y) of field
+        m.  The N stamps of all fields form one list that runs through the network in full chunks, whatever field a stamp
+        belongs to; stamp i draws noise row i, and no stamp visits the host.  Bit-identical to infer() on the concatenated
+        cutouts with the same seed."""
+        fields, N, args = Engine._field_args(fields, starts, field_ptr)
+        bufs = self._infer_bufs(N, want, out)
+        check(lib.dv_infer_fields(self._h, *args, int(seed), *map(_fp, bufs.values())))
         return {k: v for k, v in bufs.items() if v is not None}
 
     def infer_fields_keep(self, fields, starts, field_ptr, seed=0, want=("loc", "scale")) -> Dict[str, np.ndarray]:
         """infer_fields() for a caller that also needs the float64 cutouts (dv_infer_fields_keep): the wanted outputs plus
-        "cutouts" (N,) + stamp shape, assembled on the host from the fields while the GPU runs the forward passes."""
-        fields = _check_fields(fields)
-        starts = _i32_rows(starts, "cutout starts")
-        N = starts.shape[0]
-        fp = check_field_ptr(field_ptr, fields.shape[0], N)
-        bufs = self._fields_bufs(N, want, None)
+        "cutouts" (N,) + stamp shape, assembled on the host from the fields while the GPU runs the forward passes -
+        bit-identical to ctx.scene_extract(field, starts, H) field by field."""
+        fields, N, args = Engine._field_args(fields, starts, field_ptr)
+        bufs = self._infer_bufs(N, want)
         cut = _host_pool.empty((N,) + self.stamp_shape, np.float64)
-        check(lib.dv_infer_fields_keep(self._h, fields.ctypes.data_as(C.POINTER(C.c_double)), fields.shape[0],
-                                       fields.shape[1], fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
-                                       fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed), _fp(bufs["loc"]),
-                                       _fp(bufs["scale"]), _fp(bufs["mu"]), _fp(bufs["zstd"]), _fp(bufs["z"]),
-                                       cut.ctypes.data_as(C.POINTER(C.c_double))))
+        check(lib.dv_infer_fields_keep(self._h, *args, int(seed), *map(_fp, bufs.values()), _dp(cut)))
         res = {k: v for k, v in bufs.items() if v is not None}
         res["cutouts"] = cut
         return res
 
     def infer_fields_composite(self, fields, starts, places, field_ptr, seed=0, residual=True,
                                mse_center=True) -> Dict[str, np.ndarray]:
-        """infer_cutouts_composite() for M fields in one engine call (dv_infer_fields_composite): returns {"mean_fields",
-        "stddev_fields", ["residual_fields"]} (M, F, F, bands) and ["mse_center"] (N,).  A field's results are the sums of
-        its own stamps in object order - the bits infer_cutouts_composite gives for the same stamps and noise rows; a field
-        without stamps gets zeros and its residual is the field."""
-        fields = _check_fields(fields)
-        starts = _i32_rows(starts, "cutout starts")
-        places = _i32_rows(places, "stamp placements")
-        if places.shape != starts.shape:
-            raise ValueError(f"{starts.shape[0]} cutout starts but {places.shape[0]} placements")
-        N = starts.shape[0]
-        fp = check_field_ptr(field_ptr, fields.shape[0], N)
-        dp = C.POINTER(C.c_double)
-        out = {"mean_fields": np.empty(fields.shape, np.float64), "stddev_fields": np.empty(fields.shape, np.float64)}
-        if residual:
-            out["residual_fields"] = np.empty(fields.shape, np.float64)
-        if mse_center:
-            out["mse_center"] = np.empty((N,), np.float64)
-        opt = lambda k: out[k].ctypes.data_as(dp) if k in out else None
-        check(lib.dv_infer_fields_composite(self._h, fields.ctypes.data_as(dp), fields.shape[0], fields.shape[1],
-                                            fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
-                                            places.ctypes.data_as(C.POINTER(C.c_int32)),
-                                            fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed),
-                                            out["mean_fields"].ctypes.data_as(dp), out["stddev_fields"].ctypes.data_as(dp),
-                                            opt("residual_fields"), opt("mse_center")))
+        """infer_fields() with the compositing that follows it in the reference done on the GPU
+        (dv_infer_fields_composite): returns {"mean_fields", "stddev_fields", ["residual_fields"]} (M, F, F, bands) and
+        ["mse_center"] (N,) - float64 sums of the network's mean / stddev stamps placed at `places` (row, col of each
+        stamp's top-left corner; off-field parts are dropped), the fields minus the mean stamps, and each stamp's
+        centre-10x10 MSE against its cutout.  A field's results are the sums of its own stamps in object order, the same
+        bits whatever other fields the call holds; a field without stamps gets zeros and its residual is the field."""
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places)
+        out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
+        check(lib.dv_infer_fields_composite(self._h, *args, int(seed), *ptrs))
         return out
 
     # -- the same with the Monte-Carlo epistemic estimate as a pipeline stage (DESIGN.md section 7g) --
@@ -948,20 +886,14 @@ class Engine:
         stochastic decodes of every stamp (dv_infer_fields_mc_keep), run on the GPU behind each chunk's forward pass on the
         encoder output that pass left there.  loc / scale / cutouts are infer_fields_keep's for `seed`, bit for bit;
         "epistemic" is infer_mc(cutouts.astype(float32), nsamples, seed=mc_seed)[1], bit for bit."""
-        fields = _check_fields(fields)
-        starts = _i32_rows(starts, "cutout starts")
-        N = starts.shape[0]
-        fp = check_field_ptr(field_ptr, fields.shape[0], N)
+        fields, N, args = Engine._field_args(fields, starts, field_ptr)
         Engine._check_mc(nsamples, fields.shape[3])
         out = {"loc": _host_pool.empty((N,) + self.stamp_shape, np.float32),
                "scale": _host_pool.empty((N,) + self.stamp_shape, np.float32),
                "cutouts": _host_pool.empty((N,) + self.stamp_shape, np.float64),
                "epistemic": _host_pool.empty((N,) + self.stamp_shape, np.float32)}
-        check(lib.dv_infer_fields_mc_keep(self._h, fields.ctypes.data_as(C.POINTER(C.c_double)), fields.shape[0],
-                                          fields.shape[1], fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
-                                          fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed), int(mc_seed), int(nsamples),
-                                          _fp(out["loc"]), _fp(out["scale"]),
-                                          out["cutouts"].ctypes.data_as(C.POINTER(C.c_double)), _fp(out["epistemic"])))
+        check(lib.dv_infer_fields_mc_keep(self._h, *args, int(seed), int(mc_seed), int(nsamples), _fp(out["loc"]),
+                                          _fp(out["scale"]), _dp(out["cutouts"]), _fp(out["epistemic"])))
         return out
 
     def infer_fields_mc_composite(self, fields, starts, places, field_ptr, seed=0, mc_seed=0, nsamples=100, residual=True,
@@ -970,65 +902,64 @@ class Engine:
         infer_fields_mc_keep summed at `places` in float64, object order - and "eps_norm" (N,): sum(std[:, :, 2]) /
         sum(mean[:, :, 2]) per stamp in float64 (dv_infer_fields_mc_composite).  No stamp visits the host; the other
         results are infer_fields_composite's for `seed`, bit for bit."""
-        fields = _check_fields(fields)
-        starts = _i32_rows(starts, "cutout starts")
-        places = _i32_rows(places, "stamp placements")
-        if places.shape != starts.shape:
-            raise ValueError(f"{starts.shape[0]} cutout starts but {places.shape[0]} placements")
-        N = starts.shape[0]
-        fp = check_field_ptr(field_ptr, fields.shape[0], N)
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places)
         Engine._check_mc(nsamples, fields.shape[3])
-        dp = C.POINTER(C.c_double)
-        out = {"mean_fields": np.empty(fields.shape, np.float64), "stddev_fields": np.empty(fields.shape, np.float64),
-               "epistemic_fields": np.empty(fields.shape, np.float64)}
-        if residual:
-            out["residual_fields"] = np.empty(fields.shape, np.float64)
-        if mse_center:
-            out["mse_center"] = np.empty((N,), np.float64)
-        out["eps_norm"] = np.empty((N,), np.float64)
-        opt = lambda k: out[k].ctypes.data_as(dp) if k in out else None
-        check(lib.dv_infer_fields_mc_composite(self._h, fields.ctypes.data_as(dp), fields.shape[0], fields.shape[1],
-                                               fields.shape[3], starts.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               places.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed), int(mc_seed),
-                                               int(nsamples), out["mean_fields"].ctypes.data_as(dp),
-                                               out["stddev_fields"].ctypes.data_as(dp),
-                                               out["epistemic_fields"].ctypes.data_as(dp), opt("residual_fields"),
-                                               opt("mse_center"), out["eps_norm"].ctypes.data_as(dp)))
+        out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center, epistemic=True)
+        check(lib.dv_infer_fields_mc_composite(self._h, *args, int(seed), int(mc_seed), int(nsamples), *ptrs))
         return out
 
+    # -- one field: M = 1 views of the calls above, the field-sized results under singular key names --
     @staticmethod
-    def _one_field(field):
+    def _one_field(field, starts):
+        """(fields, starts, field_ptr) of the many-field calls for one square float64 field (F, F, bands)."""
         field = np.ascontiguousarray(field, dtype=np.float64)
         if field.ndim != 3 or field.shape[0] != field.shape[1]:
             raise ValueError(f"expected a square field (F, F, bands), got {field.shape}")
-        return field[None]
+        starts = _i32_rows(starts, "cutout starts")
+        return field[None], starts, [0, starts.shape[0]]
+
+    @staticmethod
+    def _singular(out):
+        return {(k[:-1] if k.endswith("_fields") else k): (v[0] if k.endswith("_fields") else v) for k, v in out.items()}
+
+    def infer_cutouts(self, field, starts, seed=0, want=("loc", "scale"), out=None) -> Dict[str, np.ndarray]:
+        """infer() on the cutouts field[x:x+H, y:y+H, :] of a float64 field (F, F, bands) for every row (x, y) of `starts`,
+        gathered and cast on the GPU: the stamps never visit the host.  Bit-identical to
+        infer(ctx.scene_extract(field, starts, H)) with the same seed."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return self.infer_fields(fields, starts, fp, seed=seed, want=want, out=out)
+
+    def infer_cutouts_keep(self, field, starts, seed=0) -> Dict[str, np.ndarray]:
+        """infer_cutouts() for a caller that also needs the float64 cutouts: returns {"loc", "scale" (float32), "cutouts"
+        (float64)}, all (N,) + stamp shape.  mean / stddev are bit-identical to infer(cutouts) with the same seed."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return self.infer_fields_keep(fields, starts, fp, seed=seed)
+
+    def infer_cutouts_composite(self, field, starts, places, seed=0, residual=True, mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_composite() for one field: returns {"mean_field", "stddev_field", ["residual_field"]} (F, F, bands)
+        and ["mse_center"] (N,)."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_composite(fields, starts, places, fp, seed=seed, residual=residual,
+                                                            mse_center=mse_center))
 
     def infer_cutouts_mc_keep(self, field, starts, seed=0, mc_seed=0, nsamples=100) -> Dict[str, np.ndarray]:
-        """infer_cutouts_keep() plus "epistemic": infer_fields_mc_keep for one field (M = 1 of the same engine call)."""
-        fields = Engine._one_field(field)
-        n = _i32_rows(starts, "cutout starts").shape[0]
-        return self.infer_fields_mc_keep(fields, starts, [0, n], seed=seed, mc_seed=mc_seed, nsamples=nsamples)
+        """infer_cutouts_keep() plus "epistemic": infer_fields_mc_keep for one field."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return self.infer_fields_mc_keep(fields, starts, fp, seed=seed, mc_seed=mc_seed, nsamples=nsamples)
 
     def infer_cutouts_mc_composite(self, field, starts, places, seed=0, mc_seed=0, nsamples=100, residual=True,
                                    mse_center=True) -> Dict[str, np.ndarray]:
-        """infer_cutouts_composite() plus "epistemic_field" and "eps_norm": infer_fields_mc_composite for one field (M = 1
-        of the same engine call), with the single-field key names."""
-        fields = Engine._one_field(field)
-        n = _i32_rows(starts, "cutout starts").shape[0]
-        out = self.infer_fields_mc_composite(fields, starts, places, [0, n], seed=seed, mc_seed=mc_seed, nsamples=nsamples,
-                                             residual=residual, mse_center=mse_center)
-        return {(k[:-1] if k.endswith("_fields") else k): (v[0] if k.endswith("_fields") else v) for k, v in out.items()}
+        """infer_cutouts_composite() plus "epistemic_field" and "eps_norm": infer_fields_mc_composite for one field."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_mc_composite(fields, starts, places, fp, seed=seed, mc_seed=mc_seed,
+                                                               nsamples=nsamples, residual=residual, mse_center=mse_center))
 
     def infer_cutouts_stream(self, field, starts, consumer, seed=0):
         """infer_cutouts() for inputs whose outputs do not belong on one host (a million cutouts: 167 GB): every finished
         chunk is handed to consumer(first, mean, stddev) - float32 views (count, H, H, bands) of the pinned transfer
         buffers, valid until the consumer returns, stamps [first, first + count) in input order.  Nothing is copied on
         the host; the GPU works on the next chunks meanwhile."""
-        field = np.ascontiguousarray(field, dtype=np.float64)
-        starts = _i32_rows(starts, "cutout starts")
-        if field.ndim != 3 or field.shape[0] != field.shape[1]:
-            raise ValueError(f"expected a square field (F, F, bands), got {field.shape}")
+        fields, starts, _ = Engine._one_field(field, starts)
         failure = []
 
         def trampoline(_user, first, count, mean_p, std_p):
@@ -1041,8 +972,7 @@ class Engine:
                 return 1
 
         cb = _lib.CHUNK_FN(trampoline)
-        rc = lib.dv_infer_cutouts_stream(self._h, field.ctypes.data_as(C.POINTER(C.c_double)), field.shape[0],
-                                         field.shape[2], starts.ctypes.data_as(C.POINTER(C.c_int32)), starts.shape[0],
+        rc = lib.dv_infer_cutouts_stream(self._h, _dp(fields), fields.shape[1], fields.shape[3], _ip(starts), starts.shape[0],
                                          int(seed), C.cast(cb, C.c_void_p), None)
         if failure:
             raise failure[0]

@@ -683,6 +683,28 @@ def test_deblend_field_cutouts_equals_extract_then_deblend_bit_for_bit():
     assert np.isfinite(m2).all()
 
 
+def test_infer_cutouts_stream_hands_out_every_chunk_at_its_global_offset():
+    """The chunk consumer is one sink of the implementation behind all field-sourced calls: for a call of more than two
+    chunks, consumer(first, ...) gets first = the chunk's global stamp number, chunk after chunk without gaps, and the
+    stamps are infer_cutouts' for the same seed, bit for bit."""
+    from debvader_amd.model import model
+
+    net, _, _, _ = model.create_model_vae(**ARCH, max_batch=128, seed=3)
+    eng = net._core.engine
+    rng = np.random.default_rng(23)
+    F, n = 200, 128 * 4 + 37
+    field = rng.normal(0, 0.4, size=(F, F, 6))
+    starts = rng.integers(0, F - 59 + 1, size=(n, 2)).astype(np.int32)
+    ref = eng.infer_cutouts(field, starts, seed=91)
+    chunks = []
+    eng.infer_cutouts_stream(field, starts, lambda first, mean, std: chunks.append((first, mean.copy(), std.copy())), seed=91)
+    assert [c[0] for c in chunks] == [0, 128, 256, 384, 512]
+    assert [len(c[1]) for c in chunks] == [128, 128, 128, 128, 37]
+    for first, mean, std in chunks:
+        np.testing.assert_array_equal(mean, ref["loc"][first:first + len(mean)])
+        np.testing.assert_array_equal(std, ref["scale"][first:first + len(std)])
+
+
 def test_config0_plumbing_1000_stamps_batch_5_and_256():
     """BASELINE configs[0] / SURVEY 8(d) "Config 1 (plumbing)": 1000 synthetic stamps of the survey's generator, latent 32,
     one epoch of net.fit at the reference's default batch 5 (train.py:88) and at 256, through the same surface
