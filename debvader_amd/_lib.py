@@ -148,6 +148,12 @@ SIGNATURES = {
                                              C.c_int32, _d, _d, _i32, _i32]),
     "dv_scene_detect": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams), C.c_int64, _i64,
                                   _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d, _d, _d, _d, _i32]),
+    "dv_field_set_open": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
+    "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
+                                      _i32, _i32, _d, _d, _d, _d]),
+    "dv_field_set_pass": (C.c_int, [_p, _i32, _i32, _i64, C.c_int64, C.c_uint64, _d, _d]),
+    "dv_field_set_read": (C.c_int, [_p, C.c_int32, _d]),
+    "dv_field_set_close": (C.c_int, [_p]),
     "dv_infer_mc": (C.c_int, [_p, _f, C.c_int64, C.c_int32, C.c_uint64, _f, _f]),
     "dv_encode": (C.c_int, [_p, _f, C.c_int64, _f]),
     "dv_decode": (C.c_int, [_p, _f, C.c_int64, _f, _f]),

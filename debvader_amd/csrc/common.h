@@ -165,10 +165,19 @@ int launch_scene_extract_f32(const double* field_dev, int F, int nb, const int* 
 // cutout.  The result pointers are field f0 of a stack, fptr_dev [M + 1] the global stamp number where each field's
 // objects begin, the chunk holds stamps obase .. obase + n of fields fy0 .. fy0 + nfields - 1.
 // eps_f / eps (both or neither): a third field of the same stack, += the chunk's float32 Monte-Carlo std stamps.
+// res2_f (with res_f, without eps_f): a second residual of the same stack, -= the mean stamps like res_f (dv_field_set_pass).
 int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, int F, int nb, const float* loc,
                                  const float* scale, const int* places_dev, int n, int cs, hipStream_t s,
                                  const int* fptr_dev, int f0, int fy0, int nfields, long obase, double* eps_f,
-                                 const float* eps);
+                                 const float* eps, double* res2_f = nullptr);
+// resident field sets (dv_field_set_pass), stacks of M fields of felems doubles, fptr_dev [M + 1] as above; only
+// the fields that have stamps (fptr[m + 1] > fptr[m]) are read or written.
+// dst[m] = src[m]
+int launch_scene_fields_copy(double* dst_dev, const double* src_dev, const int* fptr_dev, int M, long felems, hipStream_t s);
+// out[m] = mean((a[m] - b[m])^2) in float64, summed in a fixed order; part_dev: M * scene_field_mse_blocks(felems) doubles
+long scene_field_mse_blocks(long felems);
+int launch_scene_field_mse(const double* a_dev, const double* b_dev, const int* fptr_dev, int M, long felems,
+                           double* part_dev, double* out_dev, hipStream_t s);
 // out[i] = sum(eps_i[:, :, 2]) / sum(loc_i[:, :, 2]) in float64 for the n stamps of a chunk (both device, [n][cs][cs][nb])
 int launch_scene_eps_norm(const float* eps, const float* loc, int n, int cs, int nb, double* out_dev, hipStream_t s);
 int launch_scene_center_mse(const double* field_dev, int F, int nb, const int* starts_dev, const float* loc, int n, int cs,
@@ -192,6 +201,18 @@ int scene_detect(const double* fields_h, int M, int H, int W, double thresh, dou
                  int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
                  int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
                  double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s);
+// the same detector on one band of fields that lie in device memory (dv_field_set_detect): field i of the call is band
+// `band` of the [H][W][nb] field number which_h[i] of the stack fields_dev, gathered into the detector's planes on the GPU
+struct DetectDevSrc {
+  const double* fields_dev;
+  int nb, band;
+  const int32_t* which_h;
+};
+int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
+                     int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
+                     int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
+                     int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
+                     hipStream_t s);
 
 // Strip form of the stride-1 3x3 gather-GEMM for the 32-channel high-resolution layers (gconv_strip.hip)
 struct GStripParams {

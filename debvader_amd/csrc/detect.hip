@@ -743,14 +743,27 @@ long field_bytes(long H, long W, long ny, long nx, int minarea, bool maps) {
   b += capn * ((long)sizeof(DbJob) + 4 * 4 + 4 * 8);          // jobs and catalog slots
   return b;
 }
-}  // namespace
 
-int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
-                 int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
-                 int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
-                 int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s) {
-  if (!fields_h || M < 0 || H < 1 || W < 1 || H > DIM_MAX || W > DIM_MAX || (long)H * W > 0x7fffffffL ||
+// data[i] = band `band` of field which[i] of a stack of [HW][nb] fields: the contiguous planes the detector kernels read
+__global__ __launch_bounds__(DT) void band_gather_kernel(const double* __restrict__ fields, long HW, int nb, int band,
+                                                         const int* __restrict__ which, double* __restrict__ data) {
+  const long e = (long)blockIdx.x * DT + threadIdx.x;
+  if (e >= HW) return;
+  const long f = which[blockIdx.y];
+  data[(long)blockIdx.y * HW + e] = fields[(f * HW + e) * nb + band];
+}
+
+// the detector: the fields come from the host (fields_h) or, with `dev`, from a stack that lies in device memory
+int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, int W, double thresh, double cont, int minarea,
+                int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
+                int64_t workspace_bytes, int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h,
+                int32_t* field_h, int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h,
+                double* y_h, double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s) {
+  if (dev && (!dev->fields_dev || !dev->which_h || dev->nb < 1 || dev->band < 0 || dev->band >= dev->nb)) {
+    set_error("scene_detect: bad device source");
+    return E_INVALID;
+  }
+  if ((!fields_h && !dev) || M < 0 || H < 1 || W < 1 || H > DIM_MAX || W > DIM_MAX || (long)H * W > 0x7fffffffL ||
       !std::isfinite(thresh) || !std::isfinite(cont) || minarea < 1 || nthresh < 1 || nthresh > 1024 ||
       back_size < 1 || back_size > 64 || back_filter < 1 || back_filter > MF_MAX || (back_filter & 1) == 0 || cap < 0 ||
       !n_out || !offsets_h || !globalrms_h || workspace_bytes < 0 ||
@@ -809,7 +822,7 @@ int scene_detect(const double* fields_h, int M, int H, int W, double thresh, dou
   double *kdev = nullptr, *cdev = nullptr, *back = nullptr, *rms = nullptr, *dscr = nullptr;
   int *par = nullptr, *lab = nullptr, *area = nullptr, *cmin = nullptr, *cmax = nullptr, *rmax = nullptr, *lidx = nullptr;
   int *table = nullptr, *ncomp = nullptr, *labout = nullptr, *iscr = nullptr, *o_npix = nullptr, *o_pp = nullptr;
-  int* nobj = nullptr;
+  int *nobj = nullptr, *wdev = nullptr;
   double *o_peak = nullptr, *o_flux = nullptr, *o_x = nullptr, *o_y = nullptr;
   DbJob* djobs = nullptr;
   int st = OK;
@@ -824,7 +837,7 @@ int scene_detect(const double* fields_h, int M, int H, int W, double thresh, dou
     for (void* p : {(void*)data, (void*)v, (void*)D, (void*)mb, (void*)mr, (void*)fbk, (void*)frm, (void*)d2b,
                     (void*)d2r, (void*)gb, (void*)gb2, (void*)gr, (void*)gr2, (void*)grms, (void*)kdev, (void*)cdev,
                     (void*)back, (void*)rms, (void*)par, (void*)lab, (void*)area, (void*)cmin, (void*)cmax,
-                    (void*)rmax, (void*)lidx, (void*)table, (void*)ncomp, (void*)labout})
+                    (void*)rmax, (void*)lidx, (void*)table, (void*)ncomp, (void*)labout, (void*)wdev})
       (void)hipFree(p);
     free_deblend();
   };
@@ -845,13 +858,23 @@ int scene_detect(const double* fields_h, int M, int H, int W, double thresh, dou
     if (labels_h) DT_ALLOC(labout, px);
     DT_HIP(hipMemcpyAsync(kdev, kn.data(), kn.size() * sizeof(double), hipMemcpyHostToDevice, s));
     DT_HIP(hipMemcpyAsync(cdev, cco.data(), cco.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    if (dev) {
+      DT_ALLOC(wdev, M);
+      DT_HIP(hipMemcpyAsync(wdev, dev->which_h, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
+    }
   }
   std::vector<int> h_ncomp((size_t)std::max(chunk, 1));
   std::vector<int> h_tab;
   for (int f0 = 0; f0 < M; f0 += chunk) {
     const int m = std::min(chunk, M - f0);
     const long px = (long)m * HW;
-    DT_HIP(hipMemcpyAsync(data, fields_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
+    if (dev) {
+      hipLaunchKernelGGL(band_gather_kernel, dim3(nblk(HW), (unsigned)m), dim3(DT), 0, s, dev->fields_dev, HW, dev->nb,
+                         dev->band, wdev + f0, data);
+      DT_HIP(hipGetLastError());
+    } else {
+      DT_HIP(hipMemcpyAsync(data, fields_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
+    }
     hipLaunchKernelGGL(bkg_mesh_kernel, dim3((unsigned)((long)m * ny * nx)), dim3(DT), 0, s, data, H, W, back_size, ny,
                        nx, mb, mr);
     DT_HIP(hipGetLastError());
@@ -977,6 +1000,31 @@ int scene_detect(const double* fields_h, int M, int H, int W, double thresh, dou
     std::copy(c_y.begin(), c_y.end(), y_h);
   }
   return OK;
+}
+}  // namespace
+
+int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
+                 int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
+                 int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
+                 int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
+                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s) {
+  if (!fields_h) {
+    set_error("scene_detect: bad arguments");
+    return E_INVALID;
+  }
+  return detect_impl(fields_h, nullptr, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
+                     workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
+                     y_h, back_h, rms_h, D_h, labels_h, s);
+}
+
+int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
+                     int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
+                     int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
+                     int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
+                     hipStream_t s) {
+  return detect_impl(nullptr, &src, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
+                     workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
+                     y_h, nullptr, nullptr, nullptr, nullptr, s);
 }
 
 }  // namespace dv

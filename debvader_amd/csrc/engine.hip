@@ -533,6 +533,34 @@ struct WinoEntry {
   uint64_t epoch = ~(uint64_t)0;   // parameter epoch the transform was computed at
 };
 
+// a resident field set (dv_field_set_*), owned by its model
+struct dv_field_set {
+  dv_model* m = nullptr;
+  int M = 0, F = 0, nb = 0;
+  bool cumulative = false, open = false;
+  // [M][F][F][nb] each.  reference mode: base, work, next, fin, mean, stddev; cumulative mode: `fin` is `work` and `base` is
+  // not kept (every pass starts from the working residual).  `next` receives a pass's new working residual while the
+  // pass's later chunks still gather from `work`.
+  double *base = nullptr, *work = nullptr, *next = nullptr, *fin = nullptr, *mean = nullptr, *stddev = nullptr;
+  double *mse_part = nullptr, *fmse = nullptr;   // partial sums and results of the field_mse reduction
+  // per-stamp tables of a pass (windows, placements, field numbers, centre MSE), kept between passes and grown on demand
+  // to tab_cap stamps; fptr: the M + 1 first stamps of the fields
+  int *starts_d = nullptr, *places_d = nullptr, *sfield_d = nullptr, *fptr_d = nullptr;
+  double* mse_d = nullptr;
+  size_t tab_cap = 0;
+  std::vector<double> fmse_h;                     // host side of fmse
+};
+
+static void field_set_release(dv_field_set* fs) {
+  for (double* p : {fs->base, fs->work, fs->next, fs->fin, fs->mean, fs->stddev, fs->mse_part, fs->fmse, fs->mse_d})
+    (void)hipFree(p);
+  for (int* p : {fs->starts_d, fs->places_d, fs->sfield_d, fs->fptr_d}) (void)hipFree(p);
+  fs->base = fs->work = fs->next = fs->fin = fs->mean = fs->stddev = fs->mse_part = fs->fmse = fs->mse_d = nullptr;
+  fs->starts_d = fs->places_d = fs->sfield_d = fs->fptr_d = nullptr;
+  fs->tab_cap = 0;
+  fs->open = false;
+}
+
 struct dv_model {
   dv_ctx* ctx = nullptr;
   dv::Arch A;
@@ -589,6 +617,7 @@ struct dv_model {
   float *scal = nullptr, *bnstate = nullptr, *bnsums = nullptr;
   float* stage_x = nullptr;  // host-batch staging (infer / encode)
   dv::InferPipe* pipe = nullptr;
+  std::vector<dv_field_set*> field_sets;   // every set opened on this model, closed ones included: freed with the model
   // deferred step results (dv_train_step_async / dv_step_result): pinned scalars and staged indices per ticket
   float* ring_scal = nullptr;    // [4][4] pinned
   int* ring_idx = nullptr;       // [4][Bc] pinned
@@ -3012,6 +3041,7 @@ struct PipeJob {
   // fields in HBM right behind its forward pass instead of copied out; mean_f decides
   double *mean_f = nullptr, *std_f = nullptr, *res_f = nullptr;   // device, fields f0 .. like fields_d
   double* eps_f = nullptr;             // the same sum of the Monte-Carlo std stamps
+  double* res2_f = nullptr;            // a second residual, -= the mean stamps like res_f (dv_field_set_pass; not with eps_f)
   const int* places_d = nullptr;     // device [.][2]: field position (row, col) of every stamp's top-left corner
   double* mse = nullptr;               // device [.]: centre MSE of every stamp against its cutout
   double* eps_norm = nullptr;          // device [.]: sum(std[:, :, 2]) / sum(mean[:, :, 2]) of every stamp
@@ -3192,7 +3222,7 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
       const int fy0 = j.sfield[r], fy1 = j.sfield[r + nb - 1];
       DV_TRY(launch_scene_composite_chunk(j.mean_f, j.std_f, j.res_f, j.F, j.nb, p->dloc[b], p->dscale[b],
                                           j.places_d + 2 * r, nb, cs, p->s_out, j.fptr_d, j.f0, fy0, fy1 - fy0 + 1,
-                                          (long)r, j.eps_f, j.eps_f ? m->gB : nullptr));
+                                          (long)r, j.eps_f, j.eps_f ? m->gB : nullptr, j.res2_f));
       if (j.eps_norm) DV_TRY(launch_scene_eps_norm(m->gB, p->dloc[b], nb, cs, j.nb, j.eps_norm + r, p->s_out));
       if (j.mse)
         DV_TRY(launch_scene_center_mse(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, p->dloc[b], nb, cs, j.mse + r, p->s_out,
@@ -3660,6 +3690,7 @@ int dv_model_destroy(dv_model* m) {
   if (g_process_exiting) {                   // see mark_process_exiting: host memory only
     delete m->ring;
     delete m->pipe;
+    for (dv_field_set* fs : m->field_sets) delete fs;
     delete m;
     return DV_OK;
   }
@@ -3677,6 +3708,10 @@ int dv_model_destroy(dv_model* m) {
   if (m->ring && m->ring->copy) (void)hipStreamSynchronize(m->ring->copy);
   ring_free(m);
   pipe_free(m->pipe);
+  for (dv_field_set* fs : m->field_sets) {
+    field_set_release(fs);
+    delete fs;
+  }
   for (auto& kv : m->infer_graphs) (void)hipGraphExecDestroy(kv.second);
   for (int k = 0; k < 3; ++k) {
     if (m->ev_wk[k]) (void)hipEventDestroy(m->ev_wk[k]);
@@ -4424,14 +4459,12 @@ struct FieldsOut {                  // result fields of dv_infer_fields_composit
   double *epistemic = nullptr, *eps_norm = nullptr;   // dv_infer_fields_mc_composite: [M][F][F][nb] and [N]
 };
 
-// j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
-// the device side and the rows are filled in here
-static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
-                             const FieldsOut* fo = nullptr) {
-  const double* fields = j.fields;
-  const int32_t* starts = j.starts;
-  const int F = j.F, nb = j.nb;
-  if (!m || !field_ptr || M < 0 || N < 0 || F < 1 || (M > 0 && !fields) || (N > 0 && !starts)) return DV_E_INVALID;
+// the refusals every field-sourced call takes before any GPU work, and the two tables it works from: sfield[i] = the field
+// of stamp i, fptr32 = field_ptr as the kernels read it.  places: the placements of a compositing call, or null.
+static int fields_tables(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, int F, int nb,
+                         const int32_t* starts, const int32_t* places, std::vector<int32_t>& sfield,
+                         std::vector<int>& fptr32) {
+  if (!m || !field_ptr || M < 0 || N < 0 || F < 1 || (N > 0 && !starts)) return DV_E_INVALID;
   const Arch& A = m->A;
   const int cs = A.H;
   if (nb != A.C || cs > F) {
@@ -4452,8 +4485,8 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
       set_error("%s: field_ptr decreases at field %d (%ld after %ld)", who, f, (long)field_ptr[f + 1], (long)field_ptr[f]);
       return DV_E_INVALID;
     }
-  std::vector<int32_t> sfield((size_t)N);
-  std::vector<int> fptr32((size_t)M + 1);
+  sfield.assign((size_t)N, 0);
+  fptr32.assign((size_t)M + 1, 0);
   for (int32_t f = 0; f < M; ++f) {
     fptr32[f] = (int)field_ptr[f];
     for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) {
@@ -4463,8 +4496,8 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
         set_error("%s: cutout %ld of field %d (start %d,%d size %d) leaves the %d-pixel field", who, (long)i, f, x, y, cs, F);
         return DV_E_INVALID;
       }
-      if (fo) {
-        const int pr = fo->places[2 * i], pc = fo->places[2 * i + 1];
+      if (places) {
+        const int pr = places[2 * i], pc = places[2 * i + 1];
         if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
           set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
           return DV_E_INVALID;
@@ -4473,6 +4506,20 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     }
   }
   fptr32[M] = (int)N;
+  return DV_OK;
+}
+
+// j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
+// the device side and the rows are filled in here
+static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
+                             const FieldsOut* fo = nullptr) {
+  const double* fields = j.fields;
+  const int32_t* starts = j.starts;
+  const int F = j.F, nb = j.nb;
+  if (M > 0 && !fields) return DV_E_INVALID;
+  std::vector<int32_t> sfield;
+  std::vector<int> fptr32;
+  DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, starts, fo ? fo->places : nullptr, sfield, fptr32));
   const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
   if (fo)                                       // a field without stamps: nothing predicted, nothing subtracted
     for (int32_t f = 0; f < M; ++f)
@@ -4778,6 +4825,249 @@ int dv_infer_fields_mc_composite(dv_model* m, const double* fields, int32_t M, i
   j.mc_samples = nsamples;
   j.mc_seed = mc_seed;
   return infer_fields_impl(m, "dv_infer_fields_mc_composite", M, field_ptr, N, j, &fo);
+}
+
+// ---- resident field sets (dv_field_set_*) ---------------------------------------------------------------------
+// M fields uploaded once; the working residuals, the final residuals and the predicted sums of an iterative deblending loop
+// stay in HBM between its passes.  A pass is infer_fields_impl's composite job with the set's `work` stack as the source and
+// the set's stacks as the sinks; nothing field-sized crosses the host link until dv_field_set_read.
+static int field_set_live(const dv_field_set* fs, const char* who) {
+  if (!fs) return DV_E_INVALID;
+  if (!fs->open) {
+    set_error("%s: the field set has been closed", who);
+    return DV_E_STATE;
+  }
+  return DV_OK;
+}
+
+int dv_field_set_open(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, int32_t cumulative,
+                      dv_field_set** out) {
+  if (!m || !out || M < 0 || F < 1 || (M > 0 && !fields)) return DV_E_INVALID;
+  *out = nullptr;
+  const Arch& A = m->A;
+  if (nb != A.C || A.H > F) {
+    set_error("dv_field_set_open: the fields have %d bands and %d pixels, the network takes %d x %d x %d stamps", nb, F, A.H,
+              A.H, A.C);
+    return DV_E_INVALID;
+  }
+  if (M > 65535) {
+    set_error("dv_field_set_open: %d fields, at most 65535 per set", M);
+    return DV_E_INVALID;
+  }
+  DV_HIP(hipSetDevice(m->ctx->device));
+  const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
+  const int nbuf = cumulative ? 4 : 6;
+  const size_t nblk = (size_t)scene_field_mse_blocks((long)felems);
+  const size_t need = (size_t)M * ((size_t)nbuf * fb + (nblk + 1) * sizeof(double));
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  // what the passes allocate beside the set comes off the free memory first, as infer_fields_impl takes its pipeline
+  // before its budget: the inference pipeline for the longest chunk a pass can make (unless the model already has it), the
+  // detector's workspace for the fields of one launch (at most its 4 GiB cap; ~128 bytes per pixel), and 64 MiB for the
+  // per-stamp tables (28 bytes per stamp)
+  const size_t img = (size_t)m->Bc * A.H * A.H * A.C * sizeof(float);
+  const size_t pipe_need = (m->pipe && m->pipe->cap >= m->Bc) ? 0 : 6 * img + 2 * (size_t)m->Bc * 3 * A.d * sizeof(float);
+  const size_t det_need = std::min<size_t>((size_t)4 << 30, (size_t)M * F * F * 128);
+  const size_t reserve = pipe_need + det_need + ((size_t)64 << 20);
+  size_t budget = free_b / 10 * 8;
+  budget = budget > reserve ? budget - reserve : 0;
+  if (const char* e = getenv("DV_FIELDS_GROUP_MB")) {
+    const long mb = atol(e);
+    if (mb > 0) budget = std::min(budget, (size_t)mb << 20);
+  }
+  if (need > budget) {
+    set_error("dv_field_set_open: %d resident %d-pixel fields with their %d buffers each need %zu bytes of device memory, "
+              "%zu bytes are available for fields (a set is never split: open fewer fields per set)", M, F, nbuf, need, budget);
+    return DV_E_NOMEM;
+  }
+  dv_field_set* fs = new dv_field_set();
+  fs->m = m;
+  fs->M = M;
+  fs->F = F;
+  fs->nb = nb;
+  fs->cumulative = cumulative != 0;
+  fs->open = true;
+  hipStream_t s = m->ctx->stream;
+  int st = DV_OK;
+#define FS_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); (void)hipStreamSynchronize(s); field_set_release(fs); delete fs; return st; } } while (0)
+  const size_t all = std::max<size_t>(1, (size_t)M * fb);
+  FS_HIP(hipMalloc((void**)&fs->work, all));
+  FS_HIP(hipMalloc((void**)&fs->next, all));
+  FS_HIP(hipMalloc((void**)&fs->mean, all));
+  FS_HIP(hipMalloc((void**)&fs->stddev, all));
+  if (!fs->cumulative) {
+    FS_HIP(hipMalloc((void**)&fs->base, all));
+    FS_HIP(hipMalloc((void**)&fs->fin, all));
+  }
+  FS_HIP(hipMalloc((void**)&fs->mse_part, std::max<size_t>(1, (size_t)M * nblk) * sizeof(double)));
+  FS_HIP(hipMalloc((void**)&fs->fmse, std::max<size_t>(1, (size_t)M) * sizeof(double)));
+  FS_HIP(hipMalloc((void**)&fs->fptr_d, ((size_t)M + 1) * sizeof(int)));
+  fs->fmse_h.assign((size_t)M, 0.0);
+  if (M > 0) {
+    FS_HIP(hipMemcpyAsync(fs->work, fields, (size_t)M * fb, hipMemcpyHostToDevice, s));
+    FS_HIP(hipMemsetAsync(fs->mean, 0, (size_t)M * fb, s));
+    FS_HIP(hipMemsetAsync(fs->stddev, 0, (size_t)M * fb, s));
+    if (!fs->cumulative) {
+      FS_HIP(hipMemcpyAsync(fs->base, fs->work, (size_t)M * fb, hipMemcpyDeviceToDevice, s));
+      FS_HIP(hipMemcpyAsync(fs->fin, fs->work, (size_t)M * fb, hipMemcpyDeviceToDevice, s));
+    }
+    FS_HIP(hipStreamSynchronize(s));
+  }
+#undef FS_HIP
+  m->field_sets.push_back(fs);
+  *out = fs;
+  return DV_OK;
+}
+
+int dv_field_set_close(dv_field_set* fs) {
+  DV_TRY(field_set_live(fs, "dv_field_set_close"));
+  (void)hipSetDevice(fs->m->ctx->device);
+  (void)hipStreamSynchronize(fs->m->ctx->stream);
+  field_set_release(fs);                      // the handle itself lives as long as its model: later calls find it closed
+  return DV_OK;
+}
+
+int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect_params* p, int64_t cap, int64_t* n_out,
+                        int64_t* offsets, double* globalrms, int32_t* field, int32_t* parent, int32_t* npix, double* peak,
+                        double* flux, double* x, double* y) {
+  DV_TRY(field_set_live(fs, "dv_field_set_detect"));
+  if (!p || !n_out || !offsets || !globalrms) return DV_E_INVALID;
+  if (fs->nb < 3) {
+    set_error("dv_field_set_detect: detection reads band 2, the fields have %d band(s)", fs->nb);
+    return DV_E_INVALID;
+  }
+  std::vector<int32_t> act;
+  for (int f = 0; f < fs->M; ++f)
+    if (!active || active[f]) act.push_back(f);
+  const int Ma = (int)act.size();
+  std::vector<int64_t> off((size_t)Ma + 1, 0);
+  std::vector<double> grms((size_t)std::max(Ma, 1), 0.0);
+  DV_HIP(hipSetDevice(fs->m->ctx->device));
+  DetectDevSrc src{fs->work, fs->nb, 2, act.data()};
+  *n_out = 0;
+  if (Ma > 0)
+    DV_TRY(scene_detect_dev(src, Ma, fs->F, fs->F, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
+                          p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, off.data(), grms.data(), field, parent,
+                          npix, peak, flux, x, y, fs->m->ctx->stream));
+  // the catalogue of the active fields in the numbering of the set: an inactive field has an empty range
+  offsets[0] = 0;
+  int a = 0;
+  for (int f = 0; f < fs->M; ++f) {
+    const bool on = a < Ma && act[a] == f;
+    offsets[f + 1] = offsets[f] + (on ? off[a + 1] - off[a] : 0);
+    globalrms[f] = on ? grms[a] : 0.0;
+    if (on) ++a;
+  }
+  if (*n_out <= cap)
+    for (int64_t i = 0; i < *n_out; ++i) field[i] = act[field[i]];
+  return DV_OK;
+}
+
+int dv_field_set_pass(dv_field_set* fs, const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                      uint64_t seed, double* mse_center, double* field_mse) {
+  DV_TRY(field_set_live(fs, "dv_field_set_pass"));
+  dv_model* m = fs->m;
+  const int M = fs->M, F = fs->F, nb = fs->nb;
+  if (N > 0 && (!places || !mse_center || !field_mse)) {
+    set_error("dv_field_set_pass: places, mse_center and field_mse must all be given");
+    return DV_E_INVALID;
+  }
+  std::vector<int32_t> sfield;
+  std::vector<int> fptr32;
+  DV_TRY(fields_tables(m, "dv_field_set_pass", M, field_ptr, N, F, nb, starts, places, sfield, fptr32));
+  if (N == 0) return DV_OK;
+  TinyCall tiny(m, N);
+  DV_HIP(hipSetDevice(m->ctx->device));
+  hipStream_t s = m->ctx->stream;
+  const int chunk = infer_chunk(m, N);
+  InferPipe* pipe = nullptr;
+  DV_TRY(pipe_get(m, chunk, &pipe, false));
+  const long felems = (long)F * F * nb;
+  int st = OK;
+  auto cleanup = [&]() {
+    if (st != OK) {                                  // nothing may still read the set's tables
+      (void)hipStreamSynchronize(s);
+      if (pipe->s_out) (void)hipStreamSynchronize(pipe->s_out);
+      if (pipe->s_in) (void)hipStreamSynchronize(pipe->s_in);
+    }
+  };
+#define FP_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
+#define FP_TRY(call) do { st = (call); if (st != OK) { cleanup(); return st; } } while (0)
+  if ((size_t)N > fs->tab_cap) {                     // the per-stamp tables grow to the largest pass so far
+    for (int* p : {fs->starts_d, fs->places_d, fs->sfield_d}) (void)hipFree(p);
+    (void)hipFree(fs->mse_d);
+    fs->starts_d = fs->places_d = fs->sfield_d = nullptr;
+    fs->mse_d = nullptr;
+    fs->tab_cap = 0;
+    const size_t cap = std::max<size_t>((size_t)N, 1024);
+    FP_HIP(hipMalloc((void**)&fs->starts_d, cap * 2 * sizeof(int)));
+    FP_HIP(hipMalloc((void**)&fs->places_d, cap * 2 * sizeof(int)));
+    FP_HIP(hipMalloc((void**)&fs->sfield_d, cap * sizeof(int)));
+    FP_HIP(hipMalloc((void**)&fs->mse_d, cap * sizeof(double)));
+    fs->tab_cap = cap;
+  }
+  double* mse = fs->mse_d;
+  int *sdev = fs->starts_d, *pdev = fs->places_d, *sfdev = fs->sfield_d, *fpdev = fs->fptr_d;
+  const size_t sb = (size_t)N * 2 * sizeof(int);
+  FP_HIP(hipMemcpyAsync(sdev, starts, sb, hipMemcpyHostToDevice, s));
+  FP_HIP(hipMemcpyAsync(pdev, places, sb, hipMemcpyHostToDevice, s));
+  FP_HIP(hipMemcpyAsync(sfdev, sfield.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+  FP_HIP(hipMemcpyAsync(fpdev, fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  // the new working residual of every field that has stamps starts from the buffer the mode says
+  FP_TRY(launch_scene_fields_copy(fs->next, fs->cumulative ? fs->work : fs->base, fpdev, M, felems, s));
+  FP_HIP(hipStreamSynchronize(s));                   // the gather and the sinks run on the pipeline's copy streams
+  PipeJob j;
+  j.fields_d = fs->work;
+  j.F = F;
+  j.nb = nb;
+  j.f0 = 0;
+  j.starts = starts;
+  j.starts_d = sdev;
+  j.sfield = sfield.data();
+  j.sfield_d = sfdev;
+  j.fptr_d = fpdev;
+  j.row0 = 0;
+  j.N = N;
+  j.chunk = chunk;
+  j.seed = seed;
+  j.mean_f = fs->mean;
+  j.std_f = fs->stddev;
+  j.res_f = fs->next;
+  j.res2_f = fs->cumulative ? nullptr : fs->fin;
+  j.places_d = pdev;
+  j.mse = mse;
+  FP_TRY(infer_pipelined(m, j));
+  // field_mse of the working residual against its successor, then the successor takes its place (fields with stamps only)
+  FP_TRY(launch_scene_field_mse(fs->work, fs->next, fpdev, M, felems, fs->mse_part, fs->fmse, s));
+  FP_TRY(launch_scene_fields_copy(fs->work, fs->next, fpdev, M, felems, s));
+  std::vector<double>& fm = fs->fmse_h;
+  FP_HIP(hipMemcpyAsync(mse_center, mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+  FP_HIP(hipMemcpyAsync(fm.data(), fs->fmse, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
+  FP_HIP(hipStreamSynchronize(s));
+  for (int f = 0; f < M; ++f)
+    if (fptr32[f + 1] > fptr32[f]) field_mse[f] = fm[f];
+#undef FP_TRY
+#undef FP_HIP
+  cleanup();
+  return prof_flush(m);
+}
+
+int dv_field_set_read(dv_field_set* fs, int32_t which, double* out) {
+  DV_TRY(field_set_live(fs, "dv_field_set_read"));
+  const double* src = which == DV_FIELD_SET_WORK ? fs->work
+                      : which == DV_FIELD_SET_FINAL ? (fs->cumulative ? fs->work : fs->fin)
+                      : which == DV_FIELD_SET_MEAN ? fs->mean
+                      : which == DV_FIELD_SET_STDDEV ? fs->stddev : nullptr;
+  if (!src || (fs->M > 0 && !out)) {
+    set_error("dv_field_set_read: which = %d, expected DV_FIELD_SET_WORK, _FINAL, _MEAN or _STDDEV", which);
+    return DV_E_INVALID;
+  }
+  if (fs->M == 0) return DV_OK;
+  DV_HIP(hipSetDevice(fs->m->ctx->device));
+  hipStream_t s = fs->m->ctx->stream;
+  DV_HIP(hipMemcpyAsync(out, src, (size_t)fs->M * fs->F * fs->F * fs->nb * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipStreamSynchronize(s));
+  return DV_OK;
 }
 
 int dv_infer_mc(dv_model* m, const float* x, int64_t N, int32_t nsamples, uint64_t seed, float* mean_out,

@@ -183,12 +183,16 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(double* __restrict
 // workgroups, so two fields never meet in a sum, and within a field the order of additions is object order: a field's
 // result has the same bits whatever other fields the call holds.  A field without objects in the chunk returns at once.
 //
-// EPS (dv_infer_fields_mc_composite): a third sum, eps_f += the chunk's Monte-Carlo std stamps `eps` (float32, one per stamp,
-// as the Welford fold left them), with the placement, the object order and the load-add-store across chunks of the other two;
-// the instantiation without it is the kernel as it was.
+// X4, a fourth sum with the placement, the object order and the load-add-store across chunks of the other three (the
+// instantiation without it is the kernel as it was):
+//  X4_EPS  (dv_infer_fields_mc_composite): eps_f += the chunk's Monte-Carlo std stamps `eps` (float32, one per stamp, as the
+//          Welford fold left them);
+//  X4_RES2 (dv_field_set_pass, reference mode): eps_f -= the mean stamps, a second residual beside res_f - the pass's
+//          working residual starts from the base field, the set's `final` continues the earlier passes.
 constexpr int CT = 32;       // tile edge: a thread owns the four pixels (ty + 16 a, tx + 16 b) of its 32 x 32 tile
 constexpr int CSEG = 2048;   // objects per scan round (8 per thread)
-template <int NBMAX, bool EPS>
+constexpr int X4_NONE = 0, X4_EPS = 1, X4_RES2 = 2;
+template <int NBMAX, int X4>
 __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __restrict__ mean_f, double* __restrict__ std_f,
                                                                     double* __restrict__ res_f, int F, int nb,
                                                                     const float* __restrict__ loc,
@@ -204,6 +208,7 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
   const int ntx = (F + CT - 1) / CT;
   const int tr0 = (blockIdx.x / ntx) * CT, tc0 = (blockIdx.x % ntx) * CT;
   const int ty = tid >> 4, tx = tid & 15;
+  constexpr bool EPS = X4 != X4_NONE;
   double am[4][NBMAX], as[4][NBMAX], ar[4][NBMAX], ae[EPS ? 4 : 1][NBMAX];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
@@ -305,7 +310,8 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
                 am[q][b] += v;
                 ar[q][b] -= v;
                 as[q][b] += (double)scale[so + b];
-                if constexpr (EPS) ae[q][b] += (double)eps[so + b];
+                if constexpr (X4 == X4_EPS) ae[q][b] += (double)eps[so + b];
+                if constexpr (X4 == X4_RES2) ae[q][b] -= v;
               }
           }
         }
@@ -437,6 +443,69 @@ __global__ __launch_bounds__(256) void scene_center_mse_kernel(const double* __r
   __syncthreads();
   if (valid && lane == 0) out[i] = mse_pairwise_sum(sq, total) / (double)total;
 }
+
+// ---- resident field sets (dv_field_set_*) ---------------------------------------------------------------
+// dst[m] = src[m] for the fields of a stack that have stamps in the pass (fptr[m + 1] > fptr[m]); the others are not touched.
+__global__ __launch_bounds__(256) void scene_fields_copy_kernel(double* __restrict__ dst, const double* __restrict__ src,
+                                                                const int* __restrict__ fptr, long felems) {
+  const int m = blockIdx.y;
+  if (fptr[m + 1] <= fptr[m]) return;                            // (uniform over the workgroup)
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e < felems) dst[(long)m * felems + e] = src[(long)m * felems + e];
+}
+
+// field_mse[m] = mean((a[m] - b[m])^2) over the felems elements of field m, float64, for the fields that have stamps.
+// A fixed decomposition, so that a field's value has the same bits on every run, for any number of fields and whatever
+// the other fields hold: workgroup k of a field sums elements [k * MSE_BLK, (k + 1) * MSE_BLK) - thread t adds the squares
+// of elements t, t + 256, ... of the block in that order, the 64 lanes of a wave meet in the shuffle tree (32, 16, .. 1),
+// the four wave sums are added ((0 + 1) + (2 + 3)) - and writes one partial; the finish kernel (one workgroup per field)
+// adds the partials the same way: thread t takes partials t, t + 256, ... in order, then the same two trees.  Every
+// product and sum is rounded on its own (no contraction into FMAs).
+constexpr int MSE_BLK = 2048;        // elements per workgroup: 8 per thread
+__device__ __forceinline__ double field_mse_block_tree(double acc, double* s_w) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_down(acc, d, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) s_w[wave] = acc;
+  __syncthreads();
+  return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);                  // (every thread; thread 0 stores it)
+}
+
+__global__ __launch_bounds__(256) void scene_field_mse_part_kernel(const double* __restrict__ a, const double* __restrict__ b,
+                                                                   const int* __restrict__ fptr, long felems, int nblk,
+                                                                   double* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double s_w[4];
+  const int m = blockIdx.y;
+  if (fptr[m + 1] <= fptr[m]) return;                            // (uniform over the workgroup)
+  const double* fa = a + (long)m * felems;
+  const double* fb = b + (long)m * felems;
+  const long e0 = (long)blockIdx.x * MSE_BLK + threadIdx.x;
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < MSE_BLK / 256; ++k) {
+    const long e = e0 + (long)k * 256;
+    if (e < felems) {
+      const double d = fa[e] - fb[e];
+      acc += __dmul_rn(d, d);
+    }
+  }
+  const double tot = field_mse_block_tree(acc, s_w);
+  if (threadIdx.x == 0) part[(long)m * nblk + blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void scene_field_mse_finish_kernel(const double* __restrict__ part,
+                                                                     const int* __restrict__ fptr, long felems, int nblk,
+                                                                     double* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double s_w[4];
+  const int m = blockIdx.x;
+  if (fptr[m + 1] <= fptr[m]) return;                            // (uniform over the workgroup)
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 256) acc += part[(long)m * nblk + i];
+  const double tot = field_mse_block_tree(acc, s_w);
+  if (threadIdx.x == 0) out[m] = tot / (double)felems;
+}
 }  // namespace
 
 int scene_extract(const double* field_h, int F, int nb, const int32_t* starts_h, int N, int cs, double* out_h,
@@ -556,10 +625,14 @@ namespace dv {
 int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, int F, int nb, const float* loc,
                                  const float* scale, const int* places_dev, int n, int cs, hipStream_t s,
                                  const int* fptr_dev, int f0, int fy0, int nfields, long obase, double* eps_f,
-                                 const float* eps) {
+                                 const float* eps, double* res2_f) {
   if (n <= 0) return OK;
   if ((eps_f == nullptr) != (eps == nullptr)) {
     set_error("scene composite: the epistemic field and the std stamps go together");
+    return E_INVALID;
+  }
+  if (res2_f && (eps_f || !res_f)) {
+    set_error("scene composite: a second residual goes with the first and without the epistemic field");
     return E_INVALID;
   }
   if (nb < 1 || nb > 8) {
@@ -572,13 +645,14 @@ int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, i
     return E_INVALID;
   }
   const dim3 grid((unsigned)(ntx * ntx), (unsigned)nfields);
-#define SCC_LAUNCH(NBMAX, EPS)                                                                                          \
-  hipLaunchKernelGGL((scene_composite_chunk_kernel<NBMAX, EPS>), grid, dim3(256), 0, s, mean_f, std_f, res_f, F, nb, loc, \
-                     scale, places_dev, n, cs, fptr_dev, f0, fy0, obase, eps_f, eps)
+  double* x4_f = res2_f ? res2_f : eps_f;
+#define SCC_LAUNCH(NBMAX, X4)                                                                                          \
+  hipLaunchKernelGGL((scene_composite_chunk_kernel<NBMAX, X4>), grid, dim3(256), 0, s, mean_f, std_f, res_f, F, nb, loc, \
+                     scale, places_dev, n, cs, fptr_dev, f0, fy0, obase, x4_f, eps)
   if (nb <= 6) {
-    if (eps_f) SCC_LAUNCH(6, true); else SCC_LAUNCH(6, false);
+    if (res2_f) SCC_LAUNCH(6, X4_RES2); else if (eps_f) SCC_LAUNCH(6, X4_EPS); else SCC_LAUNCH(6, X4_NONE);
   } else {
-    if (eps_f) SCC_LAUNCH(8, true); else SCC_LAUNCH(8, false);
+    if (res2_f) SCC_LAUNCH(8, X4_RES2); else if (eps_f) SCC_LAUNCH(8, X4_EPS); else SCC_LAUNCH(8, X4_NONE);
   }
 #undef SCC_LAUNCH
   DV_HIP(hipGetLastError());
@@ -592,6 +666,38 @@ int launch_scene_eps_norm(const float* eps, const float* loc, int n, int cs, int
     return E_INVALID;
   }
   hipLaunchKernelGGL(scene_eps_norm_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, eps, loc, n, cs, nb, out_dev);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+int launch_scene_fields_copy(double* dst_dev, const double* src_dev, const int* fptr_dev, int M, long felems,
+                             hipStream_t s) {
+  if (M <= 0 || felems <= 0) return OK;
+  if (M > 65535) {
+    set_error("field set: %d fields, at most 65535", M);
+    return E_INVALID;
+  }
+  hipLaunchKernelGGL(scene_fields_copy_kernel, dim3((unsigned)((felems + 255) / 256), (unsigned)M), dim3(256), 0, s, dst_dev,
+                     src_dev, fptr_dev, felems);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+long scene_field_mse_blocks(long felems) { return (felems + MSE_BLK - 1) / MSE_BLK; }
+
+int launch_scene_field_mse(const double* a_dev, const double* b_dev, const int* fptr_dev, int M, long felems,
+                           double* part_dev, double* out_dev, hipStream_t s) {
+  if (M <= 0 || felems <= 0) return OK;
+  const long nblk = scene_field_mse_blocks(felems);
+  if (M > 65535 || nblk > 0x7fffffffL) {
+    set_error("field set: %d fields of %ld elements are beyond the reduction's grid", M, felems);
+    return E_INVALID;
+  }
+  hipLaunchKernelGGL(scene_field_mse_part_kernel, dim3((unsigned)nblk, (unsigned)M), dim3(256), 0, s, a_dev, b_dev, fptr_dev,
+                     felems, (int)nblk, part_dev);
+  DV_HIP(hipGetLastError());
+  hipLaunchKernelGGL(scene_field_mse_finish_kernel, dim3((unsigned)M), dim3(256), 0, s, part_dev, fptr_dev, felems, (int)nblk,
+                     out_dev);
   DV_HIP(hipGetLastError());
   return OK;
 }

@@ -12,11 +12,14 @@ are the reference's.  Three departures:
    optimise_positions=False and then fits the positions of its rows against the field it deblended
    (DeblendField.optimise_positions, on the GPU) - the reference's fit.
  - Detection runs on the net's GPU context.
+
+IterativeDeblendFieldBatch (engine-specific) runs the same loop for M fields that stay on the GPU:
+one detector call and one network call per pass for all fields that are still iterating.
 """
 import numpy as np
 
-from debvader_amd.deblend.field_deblender import DeblendField
-from debvader_amd.detect.detection import detect_objects
+from debvader_amd.deblend.field_deblender import DeblendField, DeblendFieldBatch, batch_windows
+from debvader_amd.detect.detection import _distances, detect_objects
 from debvader_amd.training.metrics import mse
 
 
@@ -158,3 +161,168 @@ class IterativeDeblendField(DeblendField):
         print(f"Deblend {self.nb_of_deblended_galaxies[-1]} more galaxy(ies)")
 
         return res_step
+
+
+class IterativeDeblendFieldBatch:
+    """The loop of IterativeDeblendField for M fields of one size that are uploaded once and stay on the GPU
+    (Engine.open_field_set): every pass is ONE detector call over the fields that are still iterating
+    and ONE network call over their galaxies; the working residuals, the final residuals and the predicted fields never
+    leave the device between passes - detections, mse_center and one mse per field do - and the composited fields come
+    back once, at the end.
+
+    Per field the loop is the reference's: pass 0 detects on the field, pass k on the residual of pass k - 1; galaxies
+    whose window fits the field are deblended; the records of all passes are concatenated with the reference's list_idx
+    offset.  Stamps are numbered over the active fields, field after field, and that number is a stamp's noise row; every
+    pass that has stamps draws one seed.
+
+    One deliberate departure from IterativeDeblendField: a pass in which a field has no detection, or none that fits a
+    window, ends that field's loop and contributes nothing - no rows and no `mse` entry (the single-field class appends its
+    previous records a second time, with an mse of 0).  The epistemic estimate and the position fit are not part of this
+    loop; IterativeDeblendField has both."""
+
+    COLUMNS = DeblendFieldBatch.ON_DEVICE_COLUMNS + [("iteration", "<i8")]
+    DEFAULT_MAX_ITERATIONS_CUMULATIVE = 10
+
+    def __init__(self, net, field_images, cutout_size=59, nb_of_bands=6, normalise=False):
+        """
+        parameters:
+            net: network used to deblend the fields (it must run on the engine: load_deblender)
+            field_images: the fields, shape (M, size, size, bands)
+            cutout_size: size of the stamps
+            nb_of_bands: number of filters in the images (at least 3: detection reads band 2)
+            normalise: normalise the stamps before the network
+        """
+        core = getattr(net, "_core", None)
+        if core is None or getattr(core, "engine", None) is None:
+            raise ValueError("IterativeDeblendFieldBatch keeps the fields on the GPU and needs a net that runs on the engine "
+                             "(debvader_amd.model.model.load_deblender); for any other net loop IterativeDeblendField over "
+                             "the fields")
+        if nb_of_bands < 3:
+            raise ValueError(f"detection reads band 2 (r), these fields have {nb_of_bands} band(s); deblend given positions "
+                             "with DeblendFieldBatch.deblend_fields instead")
+        f = np.array(field_images, dtype=np.float64, copy=True, order="C")
+        if f.ndim != 4 or f.shape[1] != f.shape[2] or f.shape[3] != nb_of_bands:
+            raise ValueError(f"expected fields (M, F, F, {nb_of_bands}), got {f.shape}")
+        self.net = net
+        self.field_images = f
+        self.nb_of_fields = f.shape[0]
+        self.field_size = f.shape[1]
+        self.cutout_size = cutout_size
+        self.nb_of_bands = nb_of_bands
+        self.normalise = normalise
+        self.nb_of_detected_objects = []
+        self.nb_of_deblended_galaxies = []
+        self.res_deblend = None
+        self.mse = [[] for _ in range(self.nb_of_fields)]
+        self._fields = None
+
+    def _records(self, kept, dd, mse_center, passed, offset, iteration):
+        n = len(kept)
+        rec = np.recarray((n,), dtype=self.COLUMNS)
+        rec["list_idx"] = np.asarray(kept, dtype=np.int64) + offset
+        col = np.empty(n, dtype=object)
+        for i in range(n):
+            col[i] = np.array([0, 0])
+        rec["shifts"] = col
+        rec["galaxy_distances_to_center_x"] = dd[:, 0]
+        rec["galaxy_distances_to_center_y"] = dd[:, 1]
+        rec["mse_center"] = mse_center
+        rec["passed_cuts"] = passed
+        rec["iteration"] = iteration
+        return rec
+
+    def iterative_deblending(self, mse_criterion=100.0, mode="reference", max_iterations=None):
+        """Run the loop on every field; returns a list of M recarrays (kept in self.res_deblend) with the columns of
+        DeblendFieldBatch's on-device pass plus `iteration`, the pass a row was deblended in.  self.mse[m] has one entry
+        per pass field m took.
+
+        mode="reference": the reference's rule.  The residual after pass k is the ORIGINAL field minus the stamps of pass
+            k only; a field goes on while a pass deblends more galaxies than the pass before it (the first counts against
+            0).  mse[0] is the mse of the field against the residual of pass 0, mse[k] of residual k - 1 against residual k.
+            max_iterations=None: no limit beside the rule.
+        mode="cumulative" (engine-specific): every pass subtracts from the working residual, so pass k sees the field
+            with everything found so far removed; a field goes on while a pass deblends at least one galaxy, for at most
+            max_iterations passes (None: DEFAULT_MAX_ITERATIONS_CUMULATIVE = 10).
+        In both modes get_residual_fields() is the field minus every deblended galaxy of every pass."""
+        if mode not in ("reference", "cumulative"):
+            raise ValueError(f"mode must be 'reference' (the reference's residual and stopping rule) or 'cumulative' "
+                             f"(every pass subtracts from the working residual), got {mode!r}")
+        cumulative = mode == "cumulative"
+        if max_iterations is None and cumulative:
+            max_iterations = self.DEFAULT_MAX_ITERATIONS_CUMULATIVE
+        if max_iterations is not None and int(max_iterations) < 0:
+            raise ValueError(f"max_iterations must be at least 0, got {max_iterations}")
+        M, F, cs = self.nb_of_fields, self.field_size, self.cutout_size
+        core = self.net._core
+        eng = core.engine
+        self.nb_of_detected_objects = []
+        self.nb_of_deblended_galaxies = []
+        self.mse = [[] for _ in range(M)]
+        steps = [[] for _ in range(M)]
+        active = np.ones(M, dtype=bool)
+        previous = [0] * M                   # galaxies the field's previous pass deblended
+        total = [0] * M                      # ... and all its passes so far: the list_idx offset of the next one
+        po = int((F - cs) / 2)
+        fs = eng.open_field_set(self.field_images, cumulative=cumulative)
+        try:
+            k = 0
+            while active.any() and (max_iterations is None or k < int(max_iterations)):
+                det = fs.detect(active=active)
+                off = det["offsets"]
+                dist = [_distances(det["x"][off[m]:off[m + 1]], det["y"][off[m]:off[m + 1]], F) if active[m]
+                        else np.zeros((0, 2)) for m in range(M)]
+                starts, field_ptr, kept, dd = batch_windows(F, dist, cs)
+                N = len(starts)
+                if N == 0:
+                    active[:] = False       # an empty pass contributes nothing, for any field
+                    break
+                # where get_predicted_field puts a stamp: padded at int((F - cs) / 2) and shifted by the distance
+                places = (po + dd).astype(np.int64)
+                eng.set_normalise(bool(self.normalise))
+                try:
+                    out = fs.deblend_pass(starts, places, field_ptr, seed=core.next_seed())
+                finally:
+                    eng.set_normalise(False)
+                passed = ~(out["mse_center"] > mse_criterion)
+                counts = [0] * M
+                for m in range(M):
+                    if not active[m]:
+                        continue
+                    lo, hi = int(field_ptr[m]), int(field_ptr[m + 1])
+                    n = hi - lo
+                    if n == 0:              # departure: this field's loop ends here, without rows or an mse entry
+                        active[m] = False
+                        continue
+                    counts[m] = n
+                    steps[m].append(self._records(kept[m], dd[lo:hi], out["mse_center"][lo:hi], passed[lo:hi], total[m], k))
+                    self.mse[m].append(float(out["field_mse"][m]))
+                    total[m] += n
+                    if not cumulative and not n > previous[m]:
+                        active[m] = False
+                    previous[m] = n
+                self.nb_of_detected_objects += [[len(d) for d in dist]]
+                self.nb_of_deblended_galaxies += [counts]
+                print(f"iteration {k}: {N} galaxy(ies) deblended in {sum(c > 0 for c in counts)} field(s), "
+                      f"{int(active.sum())} field(s) go on")
+                k += 1
+            self._fields = {"final": fs.read("final"), "mean": fs.read("mean"), "stddev": fs.read("stddev")}
+        finally:
+            fs.close()
+        empty = np.recarray((0,), dtype=self.COLUMNS)
+        self.res_deblend = [np.concatenate(s).view(np.recarray) if s else empty.copy() for s in steps]
+        return self.res_deblend
+
+    def _need_run(self):
+        if self._fields is None:
+            raise ValueError("no iterative_deblending() run yet")
+
+    def get_residual_fields(self):
+        """The fields minus every deblended galaxy of every pass, (M, F, F, bands)."""
+        self._need_run()
+        return self._fields["final"].copy()
+
+    def get_predicted_fields(self):
+        """{"predicted_mean_fields", "predicted_stddev_fields"}, each (M, F, F, bands): sums over all passes."""
+        self._need_run()
+        return {"predicted_mean_fields": self._fields["mean"].copy(),
+                "predicted_stddev_fields": self._fields["stddev"].copy()}

@@ -589,10 +589,13 @@ class Engine:
         self.stamp_shape = (cfg.height, cfg.width, cfg.bands)
         self.max_batch = cfg.max_batch
         self._streamed = {}            # slot -> (x, y) host arrays a streamed slot reads (kept alive here)
+        self._field_sets = weakref.WeakSet()    # resident field sets opened on this engine (the library frees them with it)
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
         if self._h:
+            for fs in list(self._field_sets):
+                fs._h = C.c_void_p()           # dv_model_destroy frees the sets: their handles die with the model
             lib.dv_model_destroy(self._h)
             self._h = C.c_void_p()
         try:
@@ -873,6 +876,11 @@ class Engine:
         check(lib.dv_infer_fields_composite(self._h, *args, int(seed), *ptrs))
         return out
 
+    def open_field_set(self, fields, cumulative=False) -> "FieldSet":
+        """Upload M float64 fields (M, F, F, bands) once and keep them, their working and final residuals and the predicted
+        sums on the GPU between the passes of an iterative deblending loop (dv_field_set_open)."""
+        return FieldSet(self, fields, cumulative)
+
     # -- the same with the Monte-Carlo epistemic estimate as a pipeline stage (DESIGN.md section 7g) --
     @staticmethod
     def _check_mc(nsamples, bands):
@@ -1039,3 +1047,113 @@ class Engine:
         n, ms = C.c_int64(), C.c_double()
         check(lib.dv_prof_read(self._h, klass, C.byref(n), C.byref(ms)))
         return n.value, ms.value
+
+
+class FieldSet:
+    """M fields resident on the GPU for an iterative deblending loop (dv_field_set_*).
+
+    Per field the set keeps `work` (what the next pass detects on and cuts from; at first the field), `final` (the field minus
+    every stamp of every pass), `mean` and `stddev` (sums over all passes).  cumulative=False: a pass's new working residual
+    is the uploaded field minus the stamps of that pass only (the reference's rule); cumulative=True: every pass subtracts
+    from the working residual, and `final` is `work`.  Only catalogues and per-stamp / per-field scalars cross the host link
+    between passes; read() brings a stack of fields back."""
+
+    WHICH = {"work": 0, "final": 1, "mean": 2, "stddev": 3}
+
+    def __init__(self, engine: Engine, fields, cumulative=False):
+        fields = _check_fields(fields)
+        if not np.isfinite(fields).all():
+            raise ValueError("the fields must be finite")
+        self.engine = engine
+        self.shape = fields.shape
+        self.cumulative = bool(cumulative)
+        self._h = C.c_void_p()
+        if not engine._h:
+            raise RuntimeError("the Engine of this FieldSet has been closed")
+        M, F, _, nb = fields.shape
+        check(lib.dv_field_set_open(engine._h, _dp(fields), M, F, nb, int(self.cumulative), C.byref(self._h)))
+        engine._field_sets.add(self)
+
+    def _handle(self):
+        if not self._h:
+            raise _lib.DvError(-5, "the field set has been closed")
+        return self._h
+
+    def detect(self, active=None, thresh: float = 1.5, minarea: int = 4, nthresh: int = 64, cont: float = 1e-5,
+               filter_kernel=None, back_size: int = 64, back_filter: int = 3, workspace_bytes: int = 0) -> Dict[str, np.ndarray]:
+        """Context.scene_detect on band 2 of the working residuals, which do not leave the GPU (dv_field_set_detect).
+        active: (M,) booleans, None for all fields; an inactive field gets an empty catalogue range.  Returns the
+        catalogue, offsets (M + 1,) and globalrms (M,) of scene_detect, without maps, in the set's field numbering."""
+        h = self._handle()
+        M, F = self.shape[0], self.shape[1]
+        check_detect_args(np.zeros((0, F, F)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
+                          workspace_bytes)
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(np.asarray(active, dtype=bool).astype(np.uint8))
+            if act.shape != (M,):
+                raise ValueError(f"expected one active flag per field ({M}), got shape {act.shape}")
+        kern, kptr, kh, kw = None, None, 0, 0
+        if filter_kernel is not None:
+            kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
+            kptr, (kh, kw) = kern.ctypes.data_as(C.POINTER(C.c_double)), kern.shape
+        params = _lib.DvDetectParams(float(thresh), float(cont), int(minarea), int(nthresh), int(back_size),
+                                     int(back_filter), kptr, kh, kw, int(workspace_bytes))
+        offsets = np.zeros(M + 1, np.int64)
+        grms = np.zeros(M, np.float64)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        cap = max(4096, 64 * M, M * F * F // 1024)
+        while True:                                   # the catalog's size is known after the call: grow once if needed
+            cat = {k: np.empty(cap, np.int32 if k in ("field", "parent", "npix") else np.float64)
+                   for k in Context.CATALOG_KEYS}
+            n = C.c_int64()
+            check(lib.dv_field_set_detect(h, None if act is None else act.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          C.byref(params), cap, C.byref(n), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          grms.ctypes.data_as(dp),
+                                          *[cat[k].ctypes.data_as(ip if cat[k].dtype == np.int32 else dp)
+                                            for k in Context.CATALOG_KEYS]))
+            if n.value <= cap:
+                break
+            cap = n.value
+        out = {k: v[:n.value].copy() for k, v in cat.items()}
+        out.update(offsets=offsets, globalrms=grms)
+        return out
+
+    def deblend_pass(self, starts, places, field_ptr, seed=0) -> Dict[str, np.ndarray]:
+        """One deblending pass over the stamps of all fields (dv_field_set_pass): starts / places (N, 2) and field_ptr
+        (M + 1,) as in Engine.infer_fields_composite, the stamps being cut from the working residuals as they are before
+        the pass.  Returns {"mse_center" (N,), "field_mse" (M,)}: field_mse[m] = mean((work - work_new)^2) of a field that
+        has stamps, NaN for a field without (which the pass does not touch)."""
+        h = self._handle()
+        starts = _i32_rows(starts, "cutout starts")
+        places = _i32_rows(places, "stamp placements")
+        if places.shape != starts.shape:
+            raise ValueError(f"{starts.shape[0]} cutout starts but {places.shape[0]} placements")
+        N = starts.shape[0]
+        fp = check_field_ptr(field_ptr, self.shape[0], N)
+        mse_center = np.empty(N, np.float64)
+        field_mse = np.full(self.shape[0], np.nan)
+        check(lib.dv_field_set_pass(h, _ip(starts), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed),
+                                    _dp(mse_center), _dp(field_mse)))
+        return {"mse_center": mse_center, "field_mse": field_mse}
+
+    def read(self, which: str) -> np.ndarray:
+        """One of the set's stacks as (M, F, F, bands) float64: "work", "final", "mean" or "stddev"."""
+        h = self._handle()
+        if which not in self.WHICH:
+            raise ValueError(f"which must be one of {sorted(self.WHICH)}, got {which!r}")
+        out = np.empty(self.shape, np.float64)
+        check(lib.dv_field_set_read(h, self.WHICH[which], _dp(out)))
+        return out
+
+    def close(self):
+        """Frees the set's device memory.  Idempotent; any other call on a closed set raises DvError (DV_E_STATE)."""
+        if self._h:
+            lib.dv_field_set_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

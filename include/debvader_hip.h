@@ -37,6 +37,7 @@ extern "C" {
 
 typedef struct dv_ctx dv_ctx;
 typedef struct dv_model dv_model;
+typedef struct dv_field_set dv_field_set;
 
 /* Architecture + numerics of create_model_vae(input_shape, latent_dim, filters, kernels)
  * (src/debvader/model/model.py:164-218; fixed values used by train_deblender: training/train.py:104-107). */
@@ -375,6 +376,43 @@ int dv_scene_detect(dv_ctx* ctx, const double* fields, int32_t M, int32_t H, int
                     int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms, int32_t* field, int32_t* parent,
                     int32_t* npix, double* peak, double* flux, double* x, double* y, double* back, double* rms,
                     double* D, int32_t* labels);
+
+/* ---- resident field sets: iterative deblending with the fields on the GPU ----
+ * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)
+ * keeps per field, in device memory, `work` (what the next pass detects on and cuts from, at first the field), `final`
+ * (the field minus every stamp of every pass so far), `mean` and `stddev` (sums over all passes), and in reference mode
+ * (cumulative = 0) `base`, the field as uploaded.  The whole set is resident: M fields times 6 buffers (4 in cumulative
+ * mode, where `final` is `work`) must fit 80 % of free device memory less a reserve for what the passes allocate (the
+ * inference pipeline, the detector's workspace, the per-stamp tables), or DV_FIELDS_GROUP_MB if that is lower, else
+ * DV_E_NOMEM before any GPU work (a set never splits itself: the noise rows would change).  nb must be the network's.
+ * dv_field_set_detect: dv_scene_detect on band 2 of `work` (nb >= 3) for the fields with active[m] != 0 (NULL: all), gathered
+ * on the GPU; the catalogue of dv_scene_detect without maps, `field` and offsets [M + 1] in the set's numbering, an
+ * inactive field has an empty range and globalrms 0.  Same bits as dv_scene_detect on the fields read back.
+ * dv_field_set_pass: one deblending pass.  starts, places [N][2], field_ptr [M + 1] and seed as in
+ * dv_infer_fields_composite; the stamps are cut from `work` as it is before the pass.  For every field m that has stamps,
+ * in object order and in float64: work_new = (cumulative ? work : base) - mean stamps, final -= mean stamps, mean += mean
+ * stamps, stddev += stddev stamps, field_mse[m] = mean((work - work_new)^2) over the F * F * nb elements, then work =
+ * work_new.  Fields without stamps are untouched and their field_mse entry is not written.  mse_center [N] is
+ * dv_infer_fields_composite's.  The sums have the bits of dv_scene_composite on dv_infer_fields' stamps; field_mse is
+ * summed in a fixed order of its own (blocks of 2048 elements, a fixed tree): the same bits on every run, for any M and
+ * whatever the other fields hold, but not numpy's.  The refusals of dv_infer_fields_composite apply, before any GPU work,
+ * and leave the set as it was.
+ * dv_field_set_read copies one of the stacks to out [M][F][F][nb].  dv_field_set_close frees the device memory; every
+ * call on a closed set returns DV_E_STATE (the handle stays valid until its model is destroyed: a closed set keeps ~150
+ * bytes of host memory with its model, so a model that opens many sets in its life grows by that much per set). */
+#define DV_FIELD_SET_WORK 0
+#define DV_FIELD_SET_FINAL 1
+#define DV_FIELD_SET_MEAN 2
+#define DV_FIELD_SET_STDDEV 3
+int dv_field_set_open(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, int32_t cumulative,
+                      dv_field_set** out);
+int dv_field_set_detect(dv_field_set* set, const uint8_t* active, const dv_detect_params* params, int64_t cap,
+                        int64_t* n_out, int64_t* offsets, double* globalrms, int32_t* field, int32_t* parent,
+                        int32_t* npix, double* peak, double* flux, double* x, double* y);
+int dv_field_set_pass(dv_field_set* set, const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                      uint64_t seed, double* mse_center, double* field_mse);
+int dv_field_set_read(dv_field_set* set, int32_t which, double* out);
+int dv_field_set_close(dv_field_set* set);
 
 /* ---- introspection for tests and bench ----------------------------------------------------- */
 /* copy a named activation of the last step to host: "t","z","kl","eps","loc","scale","head_pre" */

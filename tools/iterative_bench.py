@@ -1,0 +1,142 @@
+"""Iterative deblending of many small fields: the fields resident on the GPU (IterativeDeblendFieldBatch, DESIGN.md section
+7h) against a Python loop of IterativeDeblendField over the same fields - the form that existed before - on one GPU.
+M synthetic six-band fields of F px as tools/fields_bench.py makes them; then, alternating, after a warm-up,
+
+    loop :  for every field  IterativeDeblendField(net, field).iterative_deblending()
+    batch:  IterativeDeblendFieldBatch(net, fields).iterative_deblending(mode="reference")
+
+for both engine dtypes (--dtype picks one), --repeat times each: fields/s per repetition, the median and the spread (max -
+min over the median).  Both forms apply the reference's residual and stopping rule, so they make the same passes on a field
+until the single-field class meets an empty pass (which it records once more, section 7h).  The bytes that cross the host
+link per pass are counted from the passes the run made: field-sized arrays and float32 stamps in the loop, catalogues
+and per-stamp scalars in the batched form.  GPU only; prints a table and one JSON line.
+
+    python tools/iterative_bench.py [--fields 64] [--size 259] [--repeat 5] [--max-batch 8192] [--dtype both]
+
+--profile-one: warm up, run the batched form once (float32 unless --dtype says otherwise) and exit - for a kernel trace.
+"""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+from contextlib import redirect_stdout
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from fields_bench import ARCH, _field  # noqa: E402
+from debvader_amd.deblend_iterative import IterativeDeblendField, IterativeDeblendFieldBatch  # noqa: E402
+from debvader_amd.model import model  # noqa: E402
+
+CS, NB = 59, 6
+
+
+def _loop(net, fields):
+    """-> galaxies deblended, [(detections, galaxies) per deblending pass and field]"""
+    n, passes = 0, []
+    for m in range(len(fields)):
+        it = IterativeDeblendField(net, fields[m:m + 1])
+        it.iterative_deblending()
+        n += sum(it.nb_of_deblended_galaxies)
+        passes += list(zip(it.nb_of_detected_objects, it.nb_of_deblended_galaxies))
+        passes += [(0, 0)] * (len(it.mse) - len(it.nb_of_deblended_galaxies))       # passes that found nothing to deblend
+    return n, passes
+
+
+def _batch(net, fields):
+    """-> galaxies deblended, [(active fields, detections, galaxies) per pass]"""
+    it = IterativeDeblendFieldBatch(net, fields)
+    res = it.iterative_deblending(mode="reference")
+    passes = [(sum(1 for c in g if c > 0), sum(d), sum(g)) for d, g in zip(it.nb_of_detected_objects,
+                                                                         it.nb_of_deblended_galaxies)]
+    return sum(len(r) for r in res), passes
+
+
+def loop_pass_bytes(F, detections, galaxies):
+    """Host-link bytes of one pass of IterativeDeblendField on one field: the r band to the detector and its catalogue
+    back; the float64 residual and the windows to dv_infer_cutouts_keep, float32 mean and stddev stamps back; the field and
+    the float64 mean stamps to dv_scene_composite, the residual back."""
+    field = F * F * NB * 8
+    up = F * F * 8 + (field + galaxies * 8 if galaxies else 0) + field + galaxies * (CS * CS * NB * 8 + 16)
+    down = detections * 44 + galaxies * 2 * CS * CS * NB * 4 + field
+    return up + down
+
+
+def batch_pass_bytes(M, detections, galaxies):
+    """Host-link bytes of one pass of IterativeDeblendFieldBatch over M fields: the active mask up, the catalogue (44 bytes
+    per detection, offsets and globalrms per field) down; windows, placements and field numbers up (20 bytes per galaxy
+    plus the field table), mse_center and one field_mse per field down."""
+    return M + detections * 44 + (M + 1) * 8 + M * 8 + galaxies * 20 + (M + 1) * 4 + galaxies * 8 + M * 8
+
+
+def _row(label, t, fields, galaxies):
+    med = float(np.median(t))
+    return (f"{label:<22s} {fields / med:9.1f} fields/s {galaxies / med:10.0f} galaxies/s   median {1e3 * med:9.1f} ms   "
+            f"spread {100 * (t.max() - t.min()) / med:5.1f} %   runs " + " ".join(f"{1e3 * x:.1f}" for x in t))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--fields", type=int, default=64)
+    ap.add_argument("--size", type=int, default=259)
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--max-batch", type=int, default=8192)
+    ap.add_argument("--dtype", choices=("both", "float32", "bf16"), default="both")
+    ap.add_argument("--profile-one", action="store_true", help="warm up, one batched run, exit")
+    a = ap.parse_args()
+    rng = np.random.default_rng(0)
+    F, M = a.size, a.fields
+    base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
+    fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    quiet = io.StringIO()                      # both classes print their progress
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat}
+    print(f"{M} fields of {F} px, six bands; max_batch {a.max_batch}; reference mode")
+    for dtype in (("float32", "bf16") if a.dtype == "both" else (a.dtype,)):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        core = net._core
+        with redirect_stdout(quiet):
+            _loop(net, fields[:2])                                                    # warm-up
+            _batch(net, fields[:min(M, 8)])
+            if a.profile_one:
+                _batch(net, fields)
+                core.engine.close()
+                return
+        tl, tb = [], []
+        for _ in range(a.repeat):              # alternating; every run of either form starts from the same seed counter
+            for fn, ts in ((_loop, tl), (_batch, tb)):
+                core.seed_counter = 1000
+                with redirect_stdout(quiet):
+                    t0 = time.perf_counter()
+                    n, passes = fn(net, fields)
+                    ts.append(time.perf_counter() - t0)
+                if fn is _loop:
+                    nl, pl = n, passes
+                else:
+                    nb_, pb = n, passes
+        tl, tb = np.array(tl), np.array(tb)
+        print(_row(f"{dtype} loop", tl, M, nl))
+        print(_row(f"{dtype} batch", tb, M, nb_))
+        factor = float(np.median(tl) / np.median(tb))
+        print(f"{dtype} loop / batch: {factor:.2f} x  (slowest batch {1e3 * tb.max():.1f} ms, fastest loop {1e3 * tl.min():.1f} ms)")
+        lb = [loop_pass_bytes(F, d, g) for d, g in pl]
+        bb = [batch_pass_bytes(M, d, g) for _, d, g in pb]
+        print(f"{dtype} host link: loop {len(pl)} field passes, {np.mean(lb) / 1e6:.2f} MB per field and pass, "
+              f"{sum(lb) / 1e6:.1f} MB in all; batch {len(pb)} passes over {[p[0] for p in pb]} fields, "
+              f"{np.mean(bb) / 1e3:.1f} KB per pass ({np.mean(bb) / 1e3 / max(1, np.mean([p[0] for p in pb])):.2f} KB per "
+              f"field and pass), {sum(bb) / 1e6:.3f} MB in all, plus {4 * M * F * F * NB * 8 / 1e6:.1f} MB once (fields up, three "
+              f"result stacks down)")
+        result[dtype] = {"loop_ms": [round(1e3 * x, 2) for x in tl], "batch_ms": [round(1e3 * x, 2) for x in tb],
+                         "factor": round(factor, 3), "galaxies_loop": int(nl), "galaxies_batch": int(nb_),
+                         "loop_field_passes": len(pl), "batch_passes": len(pb),
+                         "loop_link_bytes": int(sum(lb)), "batch_link_bytes_between_passes": int(sum(bb)),
+                         "batch_link_bytes_once": int(4 * M * F * F * NB * 8)}
+        core.engine.close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
