@@ -140,6 +140,9 @@ SIGNATURES = {
                                           C.c_int32, _f, _f, _d, _f]),
     "dv_infer_fields_mc_composite": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
                                                C.c_uint64, C.c_int32, _d, _d, _d, _d, _d, _d]),
+    "dv_infer_fields_fit_composite": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _d, _i64, C.c_int64, C.c_uint64,
+                                                C.c_double, C.c_int32, _d, C.c_uint64, C.c_int32, _d, _d, _d, _d, _d, _d, _d,
+                                                _i32, _i32]),
     "dv_scene_extract": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _d]),
     "dv_scene_composite": (C.c_int, [_p, _d, C.c_int32, C.c_int32, _d, _d, C.c_int32, C.c_int32, C.c_double]),
     "dv_scene_fit_shifts": (C.c_int, [_p, _d, C.c_int32, _d, C.c_int32, C.c_int32, _d, C.c_double, C.c_int32, _d, _d,

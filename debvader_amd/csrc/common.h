@@ -182,6 +182,17 @@ int launch_scene_field_mse(const double* a_dev, const double* b_dev, const int* 
 int launch_scene_eps_norm(const float* eps, const float* loc, int n, int cs, int nb, double* out_dev, hipStream_t s);
 int launch_scene_center_mse(const double* field_dev, int F, int nb, const int* starts_dev, const float* loc, int n, int cs,
                             double* out_dev, hipStream_t s, const int* sfield_dev, int f0);
+// the same at fractional positions (dv_infer_fields_fit_composite): objs_dev holds the chunk's placements as
+// launch_scene_places derives them from the distances and (fitted) shifts on the device; the chunk goes in sub-chunks in
+// object order, each with its B-spline coefficients in coef_dev (scene_frac_coef_doubles, independent of n).
+size_t scene_frac_coef_doubles(int cs, int nb, int planes);
+size_t scene_frac_obj_bytes(size_t n);
+int launch_scene_places(const double* dist_dev, const double* shifts_dev, int n, int F, int cs, void* objs_dev,
+                        hipStream_t s);
+int launch_scene_composite_frac(double* mean_f, double* std_f, double* res_f, int F, int nb, const float* loc,
+                                const float* scale, const void* objs_dev, int n, int cs, hipStream_t s, const int* fptr_dev,
+                                int f0, const int32_t* sfield_h, long obase, double* eps_f, const float* eps,
+                                double* res2_f, double* coef_dev);
 int scene_extract(const double* field_h, int F, int nb, const int32_t* starts_h, int N, int cs, double* out_h,
                   hipStream_t s);
 int scene_composite(double* field_h, int F, int nb, const double* stamps_h, const double* pos_h, int N, int cs,
@@ -195,6 +206,27 @@ int scene_fit_shifts(const double* field_h, int F, const double* stamps_h, int N
 int scene_fit_shifts_fields(const double* fields_h, int M, int F, const double* stamps_h, const int64_t* field_ptr, int N,
                             int cs, const double* dist_h, double bound, int max_iter, double* shifts_h, double* objective_h,
                             int32_t* iters_h, int32_t* status_h, size_t budget_bytes, hipStream_t s);
+// the fit's geometry and launch layout, shared by the calls above and the device-resident stage of
+// dv_infer_fields_fit_composite: a plan holds every galaxy's windows; posfit_plan_layout cuts galaxies [a, b) into launches
+// (at most max_n galaxies and 1 GiB of workspace each; stamp0 < 0: stamps resident per launch) and returns the first one's
+// index; posfit_plan_run runs launches [l0, l1) of an uploaded plan on planes, stamps and [N] result arrays in HBM.
+struct PosfitPlan;
+int posfit_plan_create(int F, int cs, int N, const double* dist_h, const double* shifts_h, double bound, int max_iter,
+                       PosfitPlan** out);
+void posfit_plan_destroy(PosfitPlan* p);
+int posfit_plan_layout(PosfitPlan* p, int a, int b, int max_n, const int32_t* sfield, int f0, int stamp0);
+void posfit_plan_rebase(PosfitPlan* p, int a, int b, int f0);   // fields of [a, b) relative to f0 (laid out with f0 = 0)
+int posfit_plan_launch_count(const PosfitPlan* p);
+long posfit_plan_work_doubles(const PosfitPlan* p);
+size_t posfit_plan_geom_bytes(size_t n);
+int posfit_plan_upload(PosfitPlan* p, hipStream_t s);
+int posfit_plan_run(const PosfitPlan* p, int l0, int l1, const double* img_dev, const double* total_sq_dev,
+                    const double* stamps_dev, double* work_dev, double* shifts_dev, double* objective_dev, int* iters_dev,
+                    int* status_dev, hipStream_t s);
+// out[f] = sum of squares of plane f of nfields planes of elems doubles; dst[e] = band `band` of pixel e of src [npix][nb]
+int launch_posfit_total_sq(const double* img_dev, int nfields, long elems, double* out_dev, hipStream_t s);
+int launch_posfit_band_f64(const double* src_dev, long npix, int nb, int band, double* dst_dev, hipStream_t s);
+int launch_posfit_band_f32(const float* src_dev, long npix, int nb, int band, double* dst_dev, hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

@@ -3049,6 +3049,18 @@ struct PipeJob {
   // the encoder output that pass left in the workspace, folded into per-pixel statistics; mc_samples > 0 decides
   int mc_samples = 0;
   uint64_t mc_seed = 0;
+  // position fit and fractional placements (dv_infer_fields_fit_composite): behind every chunk's forward pass
+  // (and Monte-Carlo stage) the r band of its mean stamps is fitted against the resident r-band planes, the placements
+  // follow from the fitted shifts on the device, and the chunk is composited there; fit_plan decides (places_d is unused)
+  const PosfitPlan* fit_plan = nullptr;
+  const int* fit_l0 = nullptr;         // host: chunk k of the whole list runs the plan's launches fit_l0[k] .. fit_l0[k + 1]
+  const double *fit_img = nullptr, *fit_totsq = nullptr;   // device: r-band planes of fields f0 .. and their sums of squares
+  const double* dist_d = nullptr;      // device [.][2]: integer distances to the field centre
+  double *fit_stamps = nullptr, *fit_work = nullptr;       // device: r band of a chunk's mean stamps, the fit's workspace
+  double *shifts_d = nullptr, *fit_obj = nullptr;          // device [.][2], [.]: start shifts in, fitted out; objective
+  int *fit_iters = nullptr, *fit_status = nullptr;         // device [.]
+  void* objs_d = nullptr;              // device [chunk]: a chunk's placements
+  double* coef_d = nullptr;            // device: B-spline coefficients of a sub-chunk
 };
 
 // The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
@@ -3220,9 +3232,20 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
       ProfScope ps(m, 2, p->s_out);
       // the fields this chunk's stamps belong to: one row of workgroups per field, each scanning its own objects
       const int fy0 = j.sfield[r], fy1 = j.sfield[r + nb - 1];
-      DV_TRY(launch_scene_composite_chunk(j.mean_f, j.std_f, j.res_f, j.F, j.nb, p->dloc[b], p->dscale[b],
-                                          j.places_d + 2 * r, nb, cs, p->s_out, j.fptr_d, j.f0, fy0, fy1 - fy0 + 1,
-                                          (long)r, j.eps_f, j.eps_f ? m->gB : nullptr, j.res2_f));
+      if (j.fit_plan) {
+        const int64_t kg = r / chunk;      // (a job starts on a chunk boundary of the whole list)
+        DV_TRY(launch_posfit_band_f32(p->dloc[b], (long)nb * cs * cs, j.nb, 2, j.fit_stamps, p->s_out));
+        DV_TRY(posfit_plan_run(j.fit_plan, j.fit_l0[kg], j.fit_l0[kg + 1], j.fit_img, j.fit_totsq, j.fit_stamps, j.fit_work,
+                               j.shifts_d, j.fit_obj, j.fit_iters, j.fit_status, p->s_out));
+        DV_TRY(launch_scene_places(j.dist_d + 2 * r, j.shifts_d + 2 * r, nb, j.F, cs, j.objs_d, p->s_out));
+        DV_TRY(launch_scene_composite_frac(j.mean_f, j.std_f, j.res_f, j.F, j.nb, p->dloc[b], p->dscale[b], j.objs_d, nb, cs,
+                                           p->s_out, j.fptr_d, j.f0, j.sfield + r, (long)r, j.eps_f,
+                                           j.eps_f ? m->gB : nullptr, j.res2_f, j.coef_d));
+      } else {
+        DV_TRY(launch_scene_composite_chunk(j.mean_f, j.std_f, j.res_f, j.F, j.nb, p->dloc[b], p->dscale[b],
+                                            j.places_d + 2 * r, nb, cs, p->s_out, j.fptr_d, j.f0, fy0, fy1 - fy0 + 1,
+                                            (long)r, j.eps_f, j.eps_f ? m->gB : nullptr, j.res2_f));
+      }
       if (j.eps_norm) DV_TRY(launch_scene_eps_norm(m->gB, p->dloc[b], nb, cs, j.nb, j.eps_norm + r, p->s_out));
       if (j.mse)
         DV_TRY(launch_scene_center_mse(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, p->dloc[b], nb, cs, j.mse + r, p->s_out,
@@ -4457,6 +4480,12 @@ struct FieldsOut {                  // result fields of dv_infer_fields_composit
   double *mean = nullptr, *stddev = nullptr, *residual = nullptr, *mse = nullptr;
   const int32_t* places = nullptr;
   double *epistemic = nullptr, *eps_norm = nullptr;   // dv_infer_fields_mc_composite: [M][F][F][nb] and [N]
+  // dv_infer_fields_fit_composite: dist instead of places, the fit's parameters and per-galaxy results (host [N])
+  const double* dist = nullptr;
+  double bound = 0.0;
+  int max_iter = 0;
+  double *shifts = nullptr, *objective = nullptr;
+  int32_t *iters = nullptr, *status = nullptr;
 };
 
 // the refusals every field-sourced call takes before any GPU work, and the two tables it works from: sfield[i] = the field
@@ -4537,11 +4566,37 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   const int64_t K = (N + chunk - 1) / chunk;
   InferPipe* pipe = nullptr;
   DV_TRY(pipe_get(m, chunk, &pipe, fo == nullptr));   // before the budget below: the pipeline's buffers come first
+  // the fit's plan: every galaxy's windows, laid out chunk by chunk against field 0 (rebased once the groups are known);
+  // its workspace, the coefficient workspace of the fractional compositing and a chunk's r-band stamps and placements are
+  // allocated once per call and come off the budget like the tables
+  const bool fit = fo && fo->dist;
+  const int cs = m->A.H;
+  PosfitPlan* plan = nullptr;
+  std::vector<int> fit_l0;
+  size_t fit_fixed = 0, coef_doubles = 0;
+  if (fit) {
+    DV_TRY(posfit_plan_create(F, cs, (int)N, fo->dist, fo->shifts, fo->bound, fo->max_iter, &plan));
+    fit_l0.resize((size_t)K + 1);
+    for (int64_t k = 0; k < K; ++k)
+      fit_l0[k] = posfit_plan_layout(plan, (int)(k * chunk), (int)std::min<int64_t>(N, (k + 1) * chunk), chunk, sfield.data(),
+                                     0, (int)(k * chunk));
+    fit_l0[K] = posfit_plan_launch_count(plan);
+    coef_doubles = scene_frac_coef_doubles(cs, nb, fo->epistemic ? 3 : 2);
+    fit_fixed = ((size_t)posfit_plan_work_doubles(plan) + coef_doubles + (size_t)chunk * cs * cs) * sizeof(double) +
+                scene_frac_obj_bytes((size_t)chunk) + posfit_plan_geom_bytes((size_t)N) +
+                (size_t)N * (5 * sizeof(double) + 2 * sizeof(int));
+  }
+  struct PlanGuard {                                  // (the plan's device copy goes with it)
+    PosfitPlan* p;
+    ~PlanGuard() { posfit_plan_destroy(p); }
+  } plan_guard{plan};
 
   // fields per group: what free memory holds beside the per-stamp tables; DV_FIELDS_GROUP_MB lowers it
   // (with the Monte-Carlo estimate a resident field carries one more result field, a stamp one more scalar)
-  const size_t per_field = fb * (fo ? (fo->residual ? 4 : 3) + (fo->epistemic ? 1 : 0) : 1);
-  const size_t tables = (size_t)N * (5 * sizeof(int) + sizeof(double) * (fo && fo->eps_norm ? 2 : 1)) + ((size_t)M + 1) * sizeof(int);
+  const size_t per_field = fb * (fo ? (fo->residual ? 4 : 3) + (fo->epistemic ? 1 : 0) : 1) +
+                           (fit ? ((size_t)F * F + 1) * sizeof(double) : 0);   // (the fit: an r-band plane and its sum of squares)
+  const size_t tables = (size_t)N * (5 * sizeof(int) + sizeof(double) * (fo && fo->eps_norm ? 2 : 1)) + ((size_t)M + 1) * sizeof(int) +
+                        fit_fixed;
   size_t free_b = 0, total_b = 0;
   DV_HIP(hipMemGetInfo(&free_b, &total_b));
   size_t budget = free_b / 10 * 8;
@@ -4581,10 +4636,17 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
 
   double *fdev = nullptr, *mf = nullptr, *sf = nullptr, *rf = nullptr, *mse = nullptr, *ef = nullptr, *en = nullptr;
   int *sdev = nullptr, *pdev = nullptr, *sfdev = nullptr, *fpdev = nullptr;
+  double *f_img = nullptr, *f_tot = nullptr, *f_dist = nullptr, *f_stamps = nullptr, *f_work = nullptr, *f_shifts = nullptr,
+         *f_obj = nullptr, *f_coef = nullptr;
+  int *f_iters = nullptr, *f_status = nullptr;
+  void* f_objs = nullptr;
   int st = OK;
   auto cleanup = [&]() {
     if (st != OK && pipe->s_out) (void)hipStreamSynchronize(pipe->s_out);   // nothing may still read these
     if (st != OK && pipe->s_in) (void)hipStreamSynchronize(pipe->s_in);
+    (void)hipFree(f_img); (void)hipFree(f_tot); (void)hipFree(f_dist); (void)hipFree(f_stamps); (void)hipFree(f_work);
+    (void)hipFree(f_shifts); (void)hipFree(f_obj); (void)hipFree(f_coef); (void)hipFree(f_iters); (void)hipFree(f_status);
+    (void)hipFree(f_objs);
     (void)hipFree(fdev); (void)hipFree(mf); (void)hipFree(sf); (void)hipFree(rf); (void)hipFree(mse);
     (void)hipFree(ef); (void)hipFree(en);
     (void)hipFree(sdev); (void)hipFree(pdev); (void)hipFree(sfdev); (void)hipFree(fpdev);
@@ -4599,8 +4661,46 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     if (fo->mse) FF_HIP(hipMalloc((void**)&mse, (size_t)N * sizeof(double)));
     if (fo->epistemic) FF_HIP(hipMalloc((void**)&ef, (size_t)gmax * fb));
     if (fo->eps_norm) FF_HIP(hipMalloc((void**)&en, (size_t)N * sizeof(double)));
-    FF_HIP(hipMalloc((void**)&pdev, sb));
-    FF_HIP(hipMemcpyAsync(pdev, fo->places, sb, hipMemcpyHostToDevice, s));
+    if (!fit) {
+      FF_HIP(hipMalloc((void**)&pdev, sb));
+      FF_HIP(hipMemcpyAsync(pdev, fo->places, sb, hipMemcpyHostToDevice, s));
+    }
+  }
+  if (fit) {
+    const size_t nd = (size_t)N * sizeof(double);
+    FF_HIP(hipMalloc((void**)&f_img, (size_t)gmax * F * F * sizeof(double)));
+    FF_HIP(hipMalloc((void**)&f_tot, (size_t)gmax * sizeof(double)));
+    FF_HIP(hipMalloc((void**)&f_dist, 2 * nd));
+    FF_HIP(hipMalloc((void**)&f_shifts, 2 * nd));
+    FF_HIP(hipMalloc((void**)&f_obj, nd));
+    FF_HIP(hipMalloc((void**)&f_iters, (size_t)N * sizeof(int)));
+    FF_HIP(hipMalloc((void**)&f_status, (size_t)N * sizeof(int)));
+    FF_HIP(hipMalloc((void**)&f_stamps, (size_t)chunk * cs * cs * sizeof(double)));
+    FF_HIP(hipMalloc((void**)&f_work, (size_t)posfit_plan_work_doubles(plan) * sizeof(double)));
+    FF_HIP(hipMalloc((void**)&f_coef, coef_doubles * sizeof(double)));
+    FF_HIP(hipMalloc(&f_objs, scene_frac_obj_bytes((size_t)chunk)));
+    FF_HIP(hipMemcpyAsync(f_dist, fo->dist, 2 * nd, hipMemcpyHostToDevice, s));
+    FF_HIP(hipMemcpyAsync(f_shifts, fo->shifts, 2 * nd, hipMemcpyHostToDevice, s));
+    for (const Group& g : groups)
+      posfit_plan_rebase(plan, (int)(g.k0 * chunk), (int)std::min<int64_t>(N, g.k1 * chunk), g.f0);
+    st = posfit_plan_upload(plan, s);
+    if (st != OK) {
+      cleanup();
+      return st;
+    }
+    j.fit_plan = plan;
+    j.fit_l0 = fit_l0.data();
+    j.fit_img = f_img;
+    j.fit_totsq = f_tot;
+    j.dist_d = f_dist;
+    j.fit_stamps = f_stamps;
+    j.fit_work = f_work;
+    j.shifts_d = f_shifts;
+    j.fit_obj = f_obj;
+    j.fit_iters = f_iters;
+    j.fit_status = f_status;
+    j.objs_d = f_objs;
+    j.coef_d = f_coef;
   }
   FF_HIP(hipMalloc((void**)&sdev, sb));
   FF_HIP(hipMalloc((void**)&sfdev, (size_t)N * sizeof(int)));
@@ -4638,6 +4738,14 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
         if (rf) FF_HIP(hipMemcpyAsync(rf, fo->residual + goff, fb, hipMemcpyHostToDevice, s));
       }
     }
+    if (fit) {                                     // the r band of the resident fields as planes, once per group
+      st = launch_posfit_band_f64(fdev, (long)ng * F * F, nb, 2, f_img, s);
+      if (st == OK) st = launch_posfit_total_sq(f_img, (int)ng, (long)F * F, f_tot, s);
+      if (st != OK) {
+        cleanup();
+        return st;
+      }
+    }
     FF_HIP(hipStreamSynchronize(s));               // the gather runs on the pipeline's copy stream
     j.f0 = g.f0;
     j.row0 = g.k0 * chunk;
@@ -4663,6 +4771,13 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   }
   if (en) {
     FF_HIP(hipMemcpyAsync(fo->eps_norm, en, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipStreamSynchronize(s));
+  }
+  if (fit) {
+    FF_HIP(hipMemcpyAsync(fo->shifts, f_shifts, (size_t)N * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipMemcpyAsync(fo->objective, f_obj, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipMemcpyAsync(fo->iters, f_iters, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipMemcpyAsync(fo->status, f_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
     FF_HIP(hipStreamSynchronize(s));
   }
 #undef FF_HIP
@@ -4825,6 +4940,63 @@ int dv_infer_fields_mc_composite(dv_model* m, const double* fields, int32_t M, i
   j.mc_samples = nsamples;
   j.mc_seed = mc_seed;
   return infer_fields_impl(m, "dv_infer_fields_mc_composite", M, field_ptr, N, j, &fo);
+}
+
+// ---- position fit and fractional placements in the many-field composite call -------------------------------
+int dv_infer_fields_fit_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                  const double* dist, const int64_t* field_ptr, int64_t N, uint64_t seed, double bound,
+                                  int32_t max_iter, double* shifts_inout, uint64_t mc_seed, int32_t nsamples,
+                                  double* mean_fields, double* stddev_fields, double* epistemic_fields,
+                                  double* residual_fields, double* mse_center, double* eps_norm, double* objective,
+                                  int32_t* iters, int32_t* status) {
+  const char* who = "dv_infer_fields_fit_composite";
+  if (!m || N < 0 || N >= ((int64_t)1 << 31)) return DV_E_INVALID;
+  if (nb < 3 || m->A.C < 3) {
+    set_error("%s: the fit reads band 2, the stamps have %d bands", who, std::min<int>(nb, m->A.C));
+    return DV_E_INVALID;
+  }
+  if (max_iter < 0 || !(bound >= 0.0) || bound > 1e6) {
+    set_error("%s: bound must lie in 0 .. 1e6 and max_iter be >= 0 (got %g, %d)", who, bound, max_iter);
+    return DV_E_INVALID;
+  }
+  if ((M > 0 && (!mean_fields || !stddev_fields)) || (N > 0 && (!dist || !shifts_inout || !objective || !iters || !status))) {
+    set_error("%s: mean_fields, stddev_fields, dist, shifts_inout, objective, iters and status must all be given", who);
+    return DV_E_INVALID;
+  }
+  const bool mc = nsamples != 0 || epistemic_fields || eps_norm;
+  if (mc) {
+    DV_TRY(infer_fields_mc_check(m, who, nb, nsamples));
+    if ((M > 0 && !epistemic_fields) || (N > 0 && !eps_norm)) {
+      set_error("%s: epistemic_fields and eps_norm go with nsamples > 0 (nsamples = 0 and both null: no Monte-Carlo stage)", who);
+      return DV_E_INVALID;
+    }
+  }
+  for (int64_t i = 0; i < 2 * N; ++i)
+    if (!(dist[i] == floor(dist[i])) || dist[i] > 1e6 || dist[i] < -1e6) {
+      set_error("%s: distance %g of galaxy %ld: the device path places at integer distances within +-1e6", who, dist[i],
+                (long)(i / 2));
+      return DV_E_INVALID;
+    }
+  FieldsOut fo;
+  fo.mean = mean_fields;
+  fo.stddev = stddev_fields;
+  fo.residual = residual_fields;
+  fo.mse = mse_center;
+  fo.epistemic = mc ? epistemic_fields : nullptr;
+  fo.eps_norm = mc ? eps_norm : nullptr;
+  fo.dist = dist;
+  fo.bound = bound;
+  fo.max_iter = max_iter;
+  fo.shifts = shifts_inout;
+  fo.objective = objective;
+  fo.iters = iters;
+  fo.status = status;
+  PipeJob j = fields_job(fields, F, nb, starts, seed);
+  if (mc) {
+    j.mc_samples = nsamples;
+    j.mc_seed = mc_seed;
+  }
+  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo);
 }
 
 // ---- resident field sets (dv_field_set_*) ---------------------------------------------------------------------

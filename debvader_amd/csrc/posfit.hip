@@ -385,52 +385,64 @@ void pf_clip(long lo, long hi, int F, int& olo, int& on) {
   olo = (int)lo;
   on = hi > lo ? (int)(hi - lo) : 0;
 }
+
+// dst[e] = band `band` of pixel e of src [npix][nb], as float64 (exact for float32 sources): the contiguous r-band planes
+// and stamps posfit_kernel reads, gathered from fields and network outputs that lie in device memory
+template <typename T>
+__global__ __launch_bounds__(PF_THREADS) void posfit_band_kernel(const T* __restrict__ src, long npix, int nb, int band,
+                                                                 double* __restrict__ dst) {
+  const long e = (long)blockIdx.x * PF_THREADS + threadIdx.x;
+  if (e < npix) dst[e] = (double)src[e * nb + band];
+}
 }  // namespace
 
-int scene_fit_shifts(const double* field_h, int F, const double* stamps_h, int N, int cs, const double* dist_h,
-                     double bound, int max_iter, double* shifts_h, double* objective_h, int32_t* iters_h,
-                     int32_t* status_h, hipStream_t s) {
-  const int64_t one_field[2] = {0, N};
-  return scene_fit_shifts_fields(field_h, 1, F, stamps_h, one_field, N, cs, dist_h, bound, max_iter, shifts_h, objective_h,
-                                 iters_h, status_h, 0, s);
+// ---- geometry and launch layout, shared by the host-stamp calls and the device-resident stage -------------------------
+struct PosfitLaunch {
+  int base, n;         // galaxies base .. base + n of the plan
+  long work;           // doubles of workspace
+};
+
+struct PosfitPlan {
+  int F = 0, cs = 0, max_iter = 0;
+  double bound = 0.0;
+  std::vector<PosfitGeom> geo;
+  std::vector<long> need;              // workspace doubles per galaxy
+  std::vector<PosfitLaunch> launches;  // in galaxy order
+  long work_max = 0;                   // the largest launch's workspace
+  PosfitGeom* geo_dev = nullptr;       // posfit_plan_upload
+};
+
+static const int PF_CHUNK = 512;                  // galaxies per launch
+static const long PF_WS_BUDGET = 128L << 20;      // workspace doubles per launch (1 GiB); no galaxy may need more
+
+void posfit_plan_destroy(PosfitPlan* p) {
+  if (!p) return;
+  (void)hipFree(p->geo_dev);
+  delete p;
 }
 
-// M fields [M][F][F]; galaxies field_ptr[m] .. field_ptr[m + 1] belong to field m.  A galaxy's fit reads its own field, its
-// own stamp and its own workspace only, and every reduction has a fixed order, so its result does not depend on which
-// other galaxies or fields share its launch (DESIGN.md 7d): M fields give what M single-field calls give, bit for bit.
-// The fields are uploaded in groups of consecutive fields that fit budget_bytes (0: no limit other than a failed
-// allocation); a group's galaxies are fitted, CHUNK per launch, before the next group goes up.
-int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* stamps_h, const int64_t* field_ptr, int N,
-                            int cs, const double* dist_h, double bound, int max_iter, double* shifts_h, double* objective_h,
-                            int32_t* iters_h, int32_t* status_h, size_t budget_bytes, hipStream_t s) {
-  if (!field_h || !field_ptr || M < 1 || F < 2 || F > 32768 || cs < 1 || cs > F || N < 0 || max_iter < 0 || !(bound >= 0.0) || bound > 1e6 ||
-      (N > 0 && (!stamps_h || !dist_h || !shifts_h || !objective_h || !iters_h || !status_h))) {
+// windows and workspace need of every galaxy; refuses what dv_scene_fit_shifts refuses
+int posfit_plan_create(int F, int cs, int N, const double* dist_h, const double* shifts_h, double bound, int max_iter,
+                       PosfitPlan** out) {
+  if (!out || F < 2 || F > 32768 || cs < 1 || cs > F || N < 0 || max_iter < 0 || !(bound >= 0.0) || bound > 1e6 ||
+      (N > 0 && (!dist_h || !shifts_h))) {
     set_error("scene_fit_shifts: bad arguments");
     return E_INVALID;
   }
-  if (field_ptr[0] != 0 || field_ptr[M] != N) {
-    set_error("scene_fit_shifts: field_ptr must run from 0 to the number of galaxies (%d), got %ld .. %ld", N,
-              (long)field_ptr[0], (long)field_ptr[M]);
-    return E_INVALID;
-  }
-  for (int m = 0; m < M; ++m)
-    if (field_ptr[m + 1] < field_ptr[m]) {
-      set_error("scene_fit_shifts: field_ptr decreases at field %d", m);
-      return E_INVALID;
-    }
-  if (N == 0) return OK;
   const int T = PF_T;
   const int po = (F - cs) / 2;
-  const int CHUNK = 512;                          // galaxies per launch
-  const long WS_BUDGET = 128L << 20;              // workspace doubles per launch (1 GiB); no galaxy may need more
-  const size_t STAMP_BUDGET = (size_t)64 << 20;   // stamp doubles per launch (512 MiB)
-  std::vector<PosfitGeom> geo((size_t)N);
-  std::vector<long> need((size_t)N);
+  PosfitPlan* plan = new PosfitPlan();
+  plan->F = F; plan->cs = cs; plan->max_iter = max_iter; plan->bound = bound;
+  std::vector<PosfitGeom>& geo = plan->geo;
+  std::vector<long>& need = plan->need;
+  geo.resize((size_t)N);
+  need.resize((size_t)N);
   for (int i = 0; i < N; ++i) {
     const double d[2] = {dist_h[2 * i], dist_h[2 * i + 1]}, s0[2] = {shifts_h[2 * i], shifts_h[2 * i + 1]};
     for (int k = 0; k < 2; ++k) {
       if (!(d[k] == d[k]) || d[k] > 1e6 || d[k] < -1e6 || !(s0[k] == s0[k]) || s0[k] > 1e6 || s0[k] < -1e6) {
         set_error("scene_fit_shifts: galaxy %d has a non-finite or out-of-range distance or start shift", i);
+        delete plan;
         return E_INVALID;
       }
     }
@@ -476,13 +488,135 @@ int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* s
         g.o_net = w;   w += (long)nn[0] * nn[1];
       }
     }
-    if (w > WS_BUDGET) {
-      set_error("scene_fit_shifts: galaxy %d needs %ld doubles of workspace, above the %ld of one launch", i, w, WS_BUDGET);
+    if (w > PF_WS_BUDGET) {
+      set_error("scene_fit_shifts: galaxy %d needs %ld doubles of workspace, above the %ld of one launch", i, w, PF_WS_BUDGET);
+      delete plan;
       return E_INVALID;
     }
     geo[i] = g;
     need[i] = w;
   }
+  *out = plan;
+  return OK;
+}
+
+// the workspace loop: galaxies [a, b) go into launches of as many as max_n (at most PF_CHUNK) and the workspace budget
+// allow.  A galaxy reads field sfield[i] - f0 of the resident planes and stamp i - stamp0 of the resident stamps (stamp0 < 0:
+// the stamps of each launch are resident on their own, stamp i - its launch's base).  Returns the index of the first launch.
+int posfit_plan_layout(PosfitPlan* p, int a, int b, int max_n, const int32_t* sfield, int f0, int stamp0) {
+  const int first = (int)p->launches.size();
+  max_n = std::max(1, std::min(max_n, PF_CHUNK));
+  for (int base = a; base < b;) {
+    int n = 0;
+    long w = 0;
+    while (base + n < b && n < max_n && w + p->need[base + n] <= PF_WS_BUDGET) {   // (need <= PF_WS_BUDGET: n >= 1)
+      PosfitGeom& g = p->geo[base + n];
+      g.field = sfield[base + n] - f0;
+      g.stamp = stamp0 < 0 ? n : base + n - stamp0;
+      g.ws = w;
+      w += p->need[base + n];
+      ++n;
+    }
+    p->launches.push_back({base, n, w});
+    p->work_max = std::max(p->work_max, w);
+    base += n;
+  }
+  return first;
+}
+
+// the planes a group holds start at field f0: galaxies [a, b), laid out against field 0, read field sfield - f0
+void posfit_plan_rebase(PosfitPlan* p, int a, int b, int f0) {
+  for (int i = a; i < b; ++i) p->geo[i].field -= f0;
+}
+
+int posfit_plan_launch_count(const PosfitPlan* p) { return (int)p->launches.size(); }
+long posfit_plan_work_doubles(const PosfitPlan* p) { return std::max(p->work_max, 1L); }
+
+// the laid-out geometry of all galaxies to the device (the device-resident stage: one upload per call)
+int posfit_plan_upload(PosfitPlan* p, hipStream_t s) {
+  const size_t n = p->geo.size();
+  if (n == 0 || p->geo_dev) return OK;
+  DV_HIP(hipMalloc((void**)&p->geo_dev, n * sizeof(PosfitGeom)));
+  DV_HIP(hipMemcpyAsync(p->geo_dev, p->geo.data(), n * sizeof(PosfitGeom), hipMemcpyHostToDevice, s));
+  return OK;
+}
+size_t posfit_plan_geom_bytes(size_t n) { return n * sizeof(PosfitGeom); }
+
+// launches [l0, l1) of an uploaded plan on device-resident planes, stamps and outputs ([N] arrays indexed by galaxy)
+int posfit_plan_run(const PosfitPlan* p, int l0, int l1, const double* img_dev, const double* total_sq_dev,
+                    const double* stamps_dev, double* work_dev, double* shifts_dev, double* objective_dev, int* iters_dev,
+                    int* status_dev, hipStream_t s) {
+  for (int l = l0; l < l1; ++l) {
+    const PosfitLaunch& L = p->launches[l];
+    hipLaunchKernelGGL(posfit_kernel, dim3((unsigned)L.n), dim3(PF_THREADS), 0, s, img_dev, p->F, stamps_dev, p->cs,
+                       p->geo_dev + L.base, work_dev, total_sq_dev, p->bound, p->max_iter, shifts_dev + 2 * (size_t)L.base,
+                       objective_dev + L.base, iters_dev + L.base, status_dev + L.base);
+    DV_HIP(hipGetLastError());
+  }
+  return OK;
+}
+
+int launch_posfit_total_sq(const double* img_dev, int nfields, long elems, double* out_dev, hipStream_t s) {
+  if (nfields <= 0) return OK;
+  hipLaunchKernelGGL(posfit_total_sq_kernel, dim3((unsigned)nfields), dim3(PF_THREADS), 0, s, img_dev, elems, out_dev);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+int launch_posfit_band_f64(const double* src_dev, long npix, int nb, int band, double* dst_dev, hipStream_t s) {
+  if (npix <= 0) return OK;
+  hipLaunchKernelGGL(posfit_band_kernel<double>, dim3((unsigned)((npix + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0,
+                     s, src_dev, npix, nb, band, dst_dev);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+int launch_posfit_band_f32(const float* src_dev, long npix, int nb, int band, double* dst_dev, hipStream_t s) {
+  if (npix <= 0) return OK;
+  hipLaunchKernelGGL(posfit_band_kernel<float>, dim3((unsigned)((npix + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0,
+                     s, src_dev, npix, nb, band, dst_dev);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+int scene_fit_shifts(const double* field_h, int F, const double* stamps_h, int N, int cs, const double* dist_h,
+                     double bound, int max_iter, double* shifts_h, double* objective_h, int32_t* iters_h,
+                     int32_t* status_h, hipStream_t s) {
+  const int64_t one_field[2] = {0, N};
+  return scene_fit_shifts_fields(field_h, 1, F, stamps_h, one_field, N, cs, dist_h, bound, max_iter, shifts_h, objective_h,
+                                 iters_h, status_h, 0, s);
+}
+
+// M fields [M][F][F]; galaxies field_ptr[m] .. field_ptr[m + 1] belong to field m.  A galaxy's fit reads its own field, its
+// own stamp and its own workspace only, and every reduction has a fixed order, so its result does not depend on which
+// other galaxies or fields share its launch (DESIGN.md 7d): M fields give what M single-field calls give, bit for bit.
+// The fields are uploaded in groups of consecutive fields that fit budget_bytes (0: no limit other than a failed
+// allocation); a group's galaxies are fitted, a launch of the plan at a time, before the next group goes up.
+int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* stamps_h, const int64_t* field_ptr, int N,
+                            int cs, const double* dist_h, double bound, int max_iter, double* shifts_h, double* objective_h,
+                            int32_t* iters_h, int32_t* status_h, size_t budget_bytes, hipStream_t s) {
+  if (!field_h || !field_ptr || M < 1 || F < 2 || F > 32768 || cs < 1 || cs > F || N < 0 || max_iter < 0 || !(bound >= 0.0) || bound > 1e6 ||
+      (N > 0 && (!stamps_h || !dist_h || !shifts_h || !objective_h || !iters_h || !status_h))) {
+    set_error("scene_fit_shifts: bad arguments");
+    return E_INVALID;
+  }
+  if (field_ptr[0] != 0 || field_ptr[M] != N) {
+    set_error("scene_fit_shifts: field_ptr must run from 0 to the number of galaxies (%d), got %ld .. %ld", N,
+              (long)field_ptr[0], (long)field_ptr[M]);
+    return E_INVALID;
+  }
+  for (int m = 0; m < M; ++m)
+    if (field_ptr[m + 1] < field_ptr[m]) {
+      set_error("scene_fit_shifts: field_ptr decreases at field %d", m);
+      return E_INVALID;
+    }
+  if (N == 0) return OK;
+  const size_t STAMP_BUDGET = (size_t)64 << 20;   // stamp doubles per launch (512 MiB)
+  PosfitPlan* plan = nullptr;
+  DV_TRY(posfit_plan_create(F, cs, N, dist_h, shifts_h, bound, max_iter, &plan));
+  std::vector<int32_t> sfield((size_t)N);
+  for (int m = 0; m < M; ++m)
+    for (int64_t i = field_ptr[m]; i < field_ptr[m + 1]; ++i) sfield[i] = m;
 
   const size_t img_elems = (size_t)F * F, stamp_elems = (size_t)cs * cs;
   // fields per group
@@ -492,11 +626,12 @@ int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* s
     if (G < 1) {
       set_error("scene_fit_shifts: one %d-pixel field (%zu bytes) does not fit the %zu bytes of device memory available "
                 "for fields", F, img_elems * sizeof(double), budget_bytes);
+      posfit_plan_destroy(plan);
       return E_NOMEM;
     }
   }
-  // galaxies per launch: at most CHUNK, and at most STAMP_BUDGET doubles of stamps (a few for field-sized stamps)
-  const int chunk = (int)std::min<size_t>({(size_t)N, (size_t)CHUNK, std::max<size_t>(1, STAMP_BUDGET / stamp_elems)});
+  // galaxies per launch: at most PF_CHUNK, and at most STAMP_BUDGET doubles of stamps (a few for field-sized stamps)
+  const int chunk = (int)std::min<size_t>({(size_t)N, (size_t)PF_CHUNK, std::max<size_t>(1, STAMP_BUDGET / stamp_elems)});
   double *img = nullptr, *stamps = nullptr, *work = nullptr, *tot = nullptr, *out_s = nullptr, *out_j = nullptr;
   int *out_it = nullptr, *out_st = nullptr;
   PosfitGeom* dgeo = nullptr;
@@ -505,6 +640,7 @@ int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* s
   auto cleanup = [&]() {
     (void)hipFree(img); (void)hipFree(stamps); (void)hipFree(work); (void)hipFree(tot); (void)hipFree(out_s);
     (void)hipFree(out_j); (void)hipFree(out_it); (void)hipFree(out_st); (void)hipFree(dgeo);
+    posfit_plan_destroy(plan);
   };
 #define PF_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
   PF_HIP(hipMalloc((void**)&img, G * img_elems * sizeof(double)));
@@ -523,20 +659,10 @@ int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* s
                           hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(posfit_total_sq_kernel, dim3((unsigned)(g1 - g0)), dim3(PF_THREADS), 0, s, img, (long)img_elems, tot);
     PF_HIP(hipGetLastError());
-    int fm = g0;                                   // field of galaxy base + n
-    for (int base = ga; base < gb;) {
-      // as many galaxies as the chunk and the workspace budget allow
-      int n = 0;
-      long w = 0;
-      while (base + n < gb && n < chunk && w + need[base + n] <= WS_BUDGET) {   // (need <= WS_BUDGET: n >= 1)
-        PosfitGeom& g = geo[base + n];
-        while (field_ptr[fm + 1] <= base + n) ++fm;
-        g.field = fm - g0;
-        g.stamp = n;
-        g.ws = w;
-        w += need[base + n];
-        ++n;
-      }
+    const int l0 = posfit_plan_layout(plan, ga, gb, chunk, sfield.data(), g0, -1);
+    for (int l = l0; l < (int)plan->launches.size(); ++l) {
+      const int base = plan->launches[l].base, n = plan->launches[l].n;
+      const long w = plan->launches[l].work;
       if (w > work_cap) {
         (void)hipFree(work);
         work = nullptr;
@@ -545,7 +671,7 @@ int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* s
       }
       PF_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)base * stamp_elems, (size_t)n * stamp_elems * sizeof(double),
                             hipMemcpyHostToDevice, s));
-      PF_HIP(hipMemcpyAsync(dgeo, geo.data() + base, (size_t)n * sizeof(PosfitGeom), hipMemcpyHostToDevice, s));
+      PF_HIP(hipMemcpyAsync(dgeo, plan->geo.data() + base, (size_t)n * sizeof(PosfitGeom), hipMemcpyHostToDevice, s));
       hipLaunchKernelGGL(posfit_kernel, dim3((unsigned)n), dim3(PF_THREADS), 0, s, img, F, stamps, cs, dgeo, work, tot,
                          bound, max_iter, out_s, out_j, out_it, out_st);
       PF_HIP(hipGetLastError());
@@ -553,8 +679,7 @@ int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* s
       PF_HIP(hipMemcpyAsync(objective_h + base, out_j, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
       PF_HIP(hipMemcpyAsync(iters_h + base, out_it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
       PF_HIP(hipMemcpyAsync(status_h + base, out_st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-      PF_HIP(hipStreamSynchronize(s));             // the device buffers are reused by the next chunk
-      base += n;
+      PF_HIP(hipStreamSynchronize(s));             // the device buffers are reused by the next launch
     }
   }
   cleanup();

@@ -51,14 +51,12 @@ __global__ __launch_bounds__(256) void scene_extract_kernel(const double* __rest
   }
 }
 
-// cubic B-spline coefficients of stamp `objs[o]` zero-extended by T on every side: coef[k][P][P][nb]
-__global__ __launch_bounds__(256) void scene_prefilter_kernel(const double* __restrict__ stamps,
-                                                              const int* __restrict__ which, int cs, int nb,
-                                                              double* __restrict__ coef) {
+// cubic B-spline coefficients of one stamp plane set st [cs][cs][nb] (float64, or the network's float32 cast exactly)
+// zero-extended by T on every side: c [P][P][nb].  One workgroup.
+template <typename T>
+__device__ __forceinline__ void scene_prefilter_body(const T* __restrict__ st, int cs, int nb, double* __restrict__ c) {
   const int P = cs + 2 * T_MARGIN;
   const double z1 = -0.26794919243112270647;   // sqrt(3) - 2
-  const double* st = stamps + (long)which[blockIdx.x] * cs * cs * nb;
-  double* c = coef + (long)blockIdx.x * P * P * nb;
   // axis 0 (rows) for the cs stamp columns; the other columns of the extended image are zero and stay zero
   for (int t = threadIdx.x; t < cs * nb; t += 256) {
     const int j = t / nb, b = t - j * nb;
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(256) void scene_prefilter_kernel(const double* __re
     double acc = 0.0;
     for (int k = 0; k < P; ++k) {
       const int i = k - T_MARGIN;
-      const double s = (i >= 0 && i < cs) ? st[((long)i * cs + j) * nb + b] : 0.0;
+      const double s = (i >= 0 && i < cs) ? (double)st[((long)i * cs + j) * nb + b] : 0.0;
       acc = 6.0 * s + z1 * acc;
       col[k * ks] = acc;
     }
@@ -97,12 +95,81 @@ __global__ __launch_bounds__(256) void scene_prefilter_kernel(const double* __re
   }
 }
 
+// coefficients of stamp which[k] of the chunk: coef[k][P][P][nb]
+__global__ __launch_bounds__(256) void scene_prefilter_kernel(const double* __restrict__ stamps,
+                                                              const int* __restrict__ which, int cs, int nb,
+                                                              double* __restrict__ coef) {
+  const int P = cs + 2 * T_MARGIN;
+  scene_prefilter_body(stamps + (long)which[blockIdx.x] * cs * cs * nb, cs, nb, coef + (long)blockIdx.x * P * P * nb);
+}
+
 __device__ __forceinline__ void bspline3(double t, double w[4]) {
   const double u = 1.0 - t;
   w[0] = u * u * u / 6.0;
   w[1] = (3.0 * t * t * t - 6.0 * t * t + 4.0) / 6.0;
   w[2] = (-3.0 * t * t * t + 3.0 * t * t + 3.0 * t + 1.0) / 6.0;
   w[3] = t * t * t / 6.0;
+}
+
+// shift(pad(stamp), pos) at field pixel (r, c) from the stamp's coefficients, for NP planes of NB consecutive bands each
+// (cf[p] = band 0 of plane p's [P][P][nb] coefficients); false: the pixel gets nothing from this object.
+// scipy.ndimage.shift, mode "constant": output is cval where the input coordinate leaves [0, F-1]; the spline
+// coefficients are those of the F x F padded image with MIRROR boundaries at its edge samples, and nodes
+// outside the image are looked up mirrored.  With the infinite-domain coefficients cinf of the zero-extended
+// stamp (what the prefilter computes) the mirrored ones are cm[i] = cinf[i] + cinf[-i] + cinf[2(F-1)-i].
+// The reflected terms vanish unless the padded stamp sits within ~T pixels of the image edge (po < T).
+// The 4 x 4 weights and the tap indices are worked out once for all planes and bands.
+template <int NP, int NB>
+__device__ __forceinline__ bool scene_spline_eval(const double* const (&cf)[NP], int nbands, int nb, int cs, int F, int po,
+                                                  double sx, double sy, int r, int c, double (&v)[NP][NB]) {
+  const int P = cs + 2 * T_MARGIN;
+  const double xin = (double)r - (sx - po), yin = (double)c - (sy - po);
+  if (xin < 0.0 || yin < 0.0 || xin > F - 1.0 || yin > F - 1.0) return false;
+  const int off = po - T_MARGIN;                 // padded-image index of coefficient-image index 0
+  const bool refl = off < 2;
+  if (!refl && (xin - off < -2.0 || yin - off < -2.0 || xin - off > P + 1.0 || yin - off > P + 1.0)) return false;
+  const double fx = floor(xin), fy = floor(yin);
+  double wx[4], wy[4];
+  bspline3(xin - fx, wx);
+  bspline3(yin - fy, wy);
+  const int nr = refl ? 3 : 1;
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) v[p][b] = 0.0;
+  for (int a = 0; a < 4; ++a) {
+    int i = (int)fx - 1 + a;
+    i = i < 0 ? -i : (i > F - 1 ? 2 * (F - 1) - i : i);
+    const int ri[3] = {i - off, -i - off, 2 * (F - 1) - i - off};
+    for (int d = 0; d < 4; ++d) {
+      int j = (int)fy - 1 + d;
+      j = j < 0 ? -j : (j > F - 1 ? 2 * (F - 1) - j : j);
+      const int rj[3] = {j - off, -j - off, 2 * (F - 1) - j - off};
+      double cm[NP][NB];
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) cm[p][b] = 0.0;
+      for (int u = 0; u < nr; ++u) {
+        if ((unsigned)ri[u] >= (unsigned)P) continue;
+        for (int w = 0; w < nr; ++w)
+          if ((unsigned)rj[w] < (unsigned)P) {
+            const long ce = ((long)ri[u] * P + rj[w]) * nb;
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+              for (int b = 0; b < NB; ++b)
+                if (b < nbands) cm[p][b] += cf[p][ce + b];
+          }
+      }
+      const double wgt = wx[a] * wy[d];
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) v[p][b] += wgt * cm[p][b];
+    }
+  }
+  return true;
 }
 
 __global__ __launch_bounds__(256) void scene_composite_kernel(double* __restrict__ field, int F, int nb,
@@ -125,41 +192,9 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(double* __restrict
         acc += sign * stamps[(((long)o * cs + rr) * cs + cc) * nb + b];
       continue;
     }
-    // scipy.ndimage.shift, mode "constant": output is cval where the input coordinate leaves [0, F-1]; the spline
-    // coefficients are those of the F x F padded image with MIRROR boundaries at its edge samples, and nodes
-    // outside the image are looked up mirrored.  With the infinite-domain coefficients cinf of the zero-extended
-    // stamp (what the prefilter kernel computes) the mirrored ones are cm[i] = cinf[i] + cinf[-i] + cinf[2(F-1)-i].
-    // The reflected terms vanish unless the padded stamp sits within ~T pixels of the image edge (po < T).
-    const double xin = (double)r - (ob.sx - po), yin = (double)c - (ob.sy - po);
-    if (xin < 0.0 || yin < 0.0 || xin > F - 1.0 || yin > F - 1.0) continue;
-    const int off = po - T_MARGIN;                 // padded-image index of coefficient-image index 0
-    const bool refl = off < 2;
-    if (!refl && (xin - off < -2.0 || yin - off < -2.0 || xin - off > P + 1.0 || yin - off > P + 1.0)) continue;
-    const double fx = floor(xin), fy = floor(yin);
-    double wx[4], wy[4];
-    bspline3(xin - fx, wx);
-    bspline3(yin - fy, wy);
-    const double* cf = coef + (long)ob.coef * P * P * nb + b;
-    const int nr = refl ? 3 : 1;
-    double v = 0.0;
-    for (int a = 0; a < 4; ++a) {
-      int i = (int)fx - 1 + a;
-      i = i < 0 ? -i : (i > F - 1 ? 2 * (F - 1) - i : i);
-      const int ri[3] = {i - off, -i - off, 2 * (F - 1) - i - off};
-      for (int d = 0; d < 4; ++d) {
-        int j = (int)fy - 1 + d;
-        j = j < 0 ? -j : (j > F - 1 ? 2 * (F - 1) - j : j);
-        const int rj[3] = {j - off, -j - off, 2 * (F - 1) - j - off};
-        double cm = 0.0;
-        for (int u = 0; u < nr; ++u) {
-          if ((unsigned)ri[u] >= (unsigned)P) continue;
-          for (int w = 0; w < nr; ++w)
-            if ((unsigned)rj[w] < (unsigned)P) cm += cf[((long)ri[u] * P + rj[w]) * nb];
-        }
-        v += wx[a] * wy[d] * cm;
-      }
-    }
-    acc += sign * v;
+    const double* const cf[1] = {coef + (long)ob.coef * P * P * nb + b};
+    double v[1][1];
+    if (scene_spline_eval<1, 1>(cf, 1, nb, cs, F, po, ob.sx, ob.sy, r, c, v)) acc += sign * v[0][0];
   }
   field[e] = acc;
 }
@@ -336,6 +371,163 @@ __global__ __launch_bounds__(256) void scene_composite_chunk_kernel(double* __re
       }
     }
   }
+}
+
+// ---- the same at fractional positions (dv_infer_fields_fit_composite) ------------------------------------
+// objs[i] of stamp i from its integer distance to the field centre and its (fitted) shift: total position dist + shift,
+// top-left corner at po + that.  Both totals integer: an exact translation (coef = -1), as in scene_composite.
+__global__ __launch_bounds__(256) void scene_places_kernel(const double* __restrict__ dist,
+                                                           const double* __restrict__ shifts, int n, int po,
+                                                           SceneObj* __restrict__ objs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double px = dist[2 * i] + shifts[2 * i], py = dist[2 * i + 1] + shifts[2 * i + 1];
+  SceneObj o;
+  o.sx = po + px; o.sy = po + py;
+  o.ix = (int)floor(o.sx); o.iy = (int)floor(o.sy);
+  o.coef = (px == floor(px) && py == floor(py)) ? -1 : 0;
+  o.pad_ = 0;
+  objs[i] = o;
+}
+
+// coefficients of the float32 stamps of a sub-chunk, cast exactly: coef[o][plane][P][P][nb] for the objects that are not
+// exact translations; blockIdx.y = plane (mean, stddev, Monte-Carlo std)
+__global__ __launch_bounds__(256) void scene_prefilter_chunk_kernel(const float* __restrict__ loc,
+                                                                    const float* __restrict__ scale,
+                                                                    const float* __restrict__ eps,
+                                                                    const SceneObj* __restrict__ objs, int cs, int nb,
+                                                                    double* __restrict__ coef) {
+  const int o = blockIdx.x, pl = blockIdx.y;
+  if (objs[o].coef < 0) return;                                  // (uniform over the workgroup)
+  const int P = cs + 2 * T_MARGIN;
+  const float* src = pl == 0 ? loc : (pl == 1 ? scale : eps);
+  scene_prefilter_body(src + (long)o * cs * cs * nb, cs, nb, coef + ((long)o * gridDim.y + pl) * P * P * nb);
+}
+
+// scene_composite_chunk_kernel for a sub-chunk of at most FSUB objects some of which sit at fractional positions: the same
+// sums, order and ownership - a workgroup owns a field tile (16 x 16, one pixel per thread: the spline terms take the
+// registers the other three pixels had), tests one object per thread, compacts the hits IN ORDER into an LDS list and
+// walks it; float64, no atomics, load-add-store across sub-chunks and chunks, only touched pixels written, a field's
+// workgroups scan that field's objects only.  An exact translation adds the float32 stamp as the integer kernel does (the
+// same bits); any other object is evaluated by scene_spline_eval from the sub-chunk's coefficients, whose support
+// rings T + 2 pixels beyond the stamp: the hit test uses that window.
+// The sub-chunk bounds the coefficient workspace (FSUB * planes * P * P * nb doubles) whatever the chunk or the call holds.
+constexpr int FT = 16;       // tile edge
+constexpr int FSUB = 64;     // objects per launch
+template <int NBMAX, int X4>
+__global__ __launch_bounds__(256) void scene_composite_frac_kernel(double* __restrict__ mean_f, double* __restrict__ std_f,
+                                                                   double* __restrict__ res_f, int F, int nb,
+                                                                   const float* __restrict__ loc,
+                                                                   const float* __restrict__ scale,
+                                                                   const SceneObj* __restrict__ objs, int n, int cs, int po,
+                                                                   const int* __restrict__ fptr, int f0, int fy0,
+                                                                   long obase, double* __restrict__ eps_f,
+                                                                   const float* __restrict__ eps,
+                                                                   const double* __restrict__ coef) {
+  __shared__ int s_list[FSUB];
+  __shared__ int s_wsum[4];
+  constexpr bool EPS = X4 != X4_NONE;
+  constexpr int NP = X4 == X4_EPS ? 3 : 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ntx = (F + FT - 1) / FT;
+  const int tr0 = (blockIdx.x / ntx) * FT, tc0 = (blockIdx.x % ntx) * FT;
+  const int r = tr0 + (tid >> 4), c = tc0 + (tid & 15);
+  const int m = fy0 + (int)blockIdx.y;   // uniform over the workgroup
+  const long lo = (long)fptr[m] - obase, hi = (long)fptr[m + 1] - obase;
+  const int olo = (int)(lo > 0 ? lo : 0);
+  n = (int)(hi < n ? hi : n);
+  if (olo >= n) return;
+  // thread t tests object olo + t (n <= FSUB <= 256: one round)
+  const int o = olo + tid;
+  int hit = 0;
+  if (o < n) {
+    const SceneObj ob = objs[o];
+    const int wlo = ob.coef < 0 ? 0 : T_MARGIN + 2, whi = ob.coef < 0 ? cs : cs + T_MARGIN + 3;
+    hit = ob.ix - wlo < tr0 + FT && ob.ix + whi > tr0 && ob.iy - wlo < tc0 + FT && ob.iy + whi > tc0;
+  }
+  int incl = hit;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int v = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += v;
+  }
+  if (lane == 63) s_wsum[wave] = incl;
+  __syncthreads();
+  int base = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+    if (w < wave) base += s_wsum[w];
+  const int total = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+  if (hit) s_list[base + incl - 1] = o;
+  __syncthreads();
+  if (total == 0 || r >= F || c >= F) return;   // (no barrier below)
+  const long fo = (long)(m - f0) * F * F * nb;
+  const long e0 = fo + ((long)r * F + c) * nb;
+  double am[NBMAX], as[NBMAX], ar[NBMAX], ae[NBMAX];
+#pragma unroll
+  for (int b = 0; b < NBMAX; ++b) {
+    am[b] = as[b] = ar[b] = ae[b] = 0.0;
+    if (b < nb) {
+      am[b] = mean_f[e0 + b];
+      as[b] = std_f[e0 + b];
+      if (res_f) ar[b] = res_f[e0 + b];
+      if constexpr (EPS) ae[b] = eps_f[e0 + b];
+    }
+  }
+  bool touched = false;
+  const long PP = (long)(cs + 2 * T_MARGIN) * (cs + 2 * T_MARGIN) * nb;
+  for (int k = 0; k < total; ++k) {
+    const int oo = s_list[k];
+    const SceneObj ob = objs[oo];
+    if (ob.coef < 0) {
+      const int rr = r - ob.ix, cc = c - ob.iy;
+      if ((unsigned)rr < (unsigned)cs && (unsigned)cc < (unsigned)cs) {
+        const long so = (((long)oo * cs + rr) * cs + cc) * nb;
+        touched = true;
+#pragma unroll
+        for (int b = 0; b < NBMAX; ++b)
+          if (b < nb) {
+            const double v = (double)loc[so + b];
+            am[b] += v;
+            ar[b] -= v;
+            as[b] += (double)scale[so + b];
+            if constexpr (X4 == X4_EPS) ae[b] += (double)eps[so + b];
+            if constexpr (X4 == X4_RES2) ae[b] -= v;
+          }
+      }
+      continue;
+    }
+    const double* cb = coef + (long)oo * NP * PP;
+    double v[NP][NBMAX];
+    bool in;
+    if constexpr (NP == 3) {
+      const double* const cf[3] = {cb, cb + PP, cb + 2 * PP};
+      in = scene_spline_eval<3, NBMAX>(cf, nb, nb, cs, F, po, ob.sx, ob.sy, r, c, v);
+    } else {
+      const double* const cf[2] = {cb, cb + PP};
+      in = scene_spline_eval<2, NBMAX>(cf, nb, nb, cs, F, po, ob.sx, ob.sy, r, c, v);
+    }
+    if (!in) continue;
+    touched = true;
+#pragma unroll
+    for (int b = 0; b < NBMAX; ++b)
+      if (b < nb) {
+        am[b] += v[0][b];
+        ar[b] -= v[0][b];
+        as[b] += v[1][b];
+        if constexpr (X4 == X4_EPS) ae[b] += v[2][b];
+        if constexpr (X4 == X4_RES2) ae[b] -= v[0][b];
+      }
+  }
+  if (!touched) return;
+#pragma unroll
+  for (int b = 0; b < NBMAX; ++b)
+    if (b < nb) {
+      mean_f[e0 + b] = am[b];
+      std_f[e0 + b] = as[b];
+      if (res_f) res_f[e0 + b] = ar[b];
+      if constexpr (EPS) eps_f[e0 + b] = ae[b];
+    }
 }
 
 // mse_center[i] = mean over the centre 10 x 10 pixels and all bands of (cutout_i - mean_i)^2 in float64
@@ -656,6 +848,75 @@ int launch_scene_composite_chunk(double* mean_f, double* std_f, double* res_f, i
   }
 #undef SCC_LAUNCH
   DV_HIP(hipGetLastError());
+  return OK;
+}
+
+// doubles of coefficient workspace launch_scene_composite_frac needs (planes: 2, or 3 with the epistemic field)
+size_t scene_frac_coef_doubles(int cs, int nb, int planes) {
+  const size_t P = (size_t)cs + 2 * T_MARGIN;
+  return (size_t)FSUB * planes * P * P * nb;
+}
+size_t scene_frac_obj_bytes(size_t n) { return n * sizeof(SceneObj); }
+
+// objs_dev[i] for the n stamps of a chunk from their distances and shifts (device [n][2] each)
+int launch_scene_places(const double* dist_dev, const double* shifts_dev, int n, int F, int cs, void* objs_dev,
+                        hipStream_t s) {
+  if (n <= 0) return OK;
+  hipLaunchKernelGGL(scene_places_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dist_dev, shifts_dev, n,
+                     (F - cs) / 2, static_cast<SceneObj*>(objs_dev));
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+// launch_scene_composite_chunk at the placements objs_dev (launch_scene_places), FSUB objects at a time in object order:
+// the sub-chunk's coefficients into coef_dev, then its sums.  sfield_h [n]: the field of every stamp of the chunk (host).
+int launch_scene_composite_frac(double* mean_f, double* std_f, double* res_f, int F, int nb, const float* loc,
+                                const float* scale, const void* objs_dev, int n, int cs, hipStream_t s, const int* fptr_dev,
+                                int f0, const int32_t* sfield_h, long obase, double* eps_f, const float* eps,
+                                double* res2_f, double* coef_dev) {
+  if (n <= 0) return OK;
+  if ((eps_f == nullptr) != (eps == nullptr)) {
+    set_error("scene composite: the epistemic field and the std stamps go together");
+    return E_INVALID;
+  }
+  if (res2_f && (eps_f || !res_f)) {
+    set_error("scene composite: a second residual goes with the first and without the epistemic field");
+    return E_INVALID;
+  }
+  if (nb < 1 || nb > 8 || cs > F || !coef_dev || !objs_dev) {
+    set_error("scene composite: 1 .. 8 bands, stamps within the field, a coefficient workspace");
+    return E_INVALID;
+  }
+  const int ntx = (F + FT - 1) / FT, po = (F - cs) / 2;
+  const int planes = eps_f ? 3 : 2;
+  const size_t stamp = (size_t)cs * cs * nb;
+  double* x4_f = res2_f ? res2_f : eps_f;
+  const SceneObj* objs = static_cast<const SceneObj*>(objs_dev);
+  for (int a = 0; a < n; a += FSUB) {
+    const int ns = n - a < FSUB ? n - a : FSUB;
+    const int fy0 = sfield_h[a], nfields = sfield_h[a + ns - 1] - fy0 + 1;
+    if (nfields < 1 || nfields > 65535) {
+      set_error("scene composite: a sub-chunk spans %d fields, at most 65535", nfields);
+      return E_INVALID;
+    }
+    const float* l = loc + (size_t)a * stamp;
+    const float* sc = scale + (size_t)a * stamp;
+    const float* ep = eps ? eps + (size_t)a * stamp : nullptr;
+    hipLaunchKernelGGL(scene_prefilter_chunk_kernel, dim3((unsigned)ns, (unsigned)planes), dim3(256), 0, s, l, sc, ep,
+                       objs + a, cs, nb, coef_dev);
+    DV_HIP(hipGetLastError());
+    const dim3 grid((unsigned)(ntx * ntx), (unsigned)nfields);
+#define SCF_LAUNCH(NBMAX, X4)                                                                                            \
+  hipLaunchKernelGGL((scene_composite_frac_kernel<NBMAX, X4>), grid, dim3(256), 0, s, mean_f, std_f, res_f, F, nb, l, sc, \
+                     objs + a, ns, cs, po, fptr_dev, f0, fy0, obase + a, x4_f, ep, coef_dev)
+    if (nb <= 6) {
+      if (res2_f) SCF_LAUNCH(6, X4_RES2); else if (eps_f) SCF_LAUNCH(6, X4_EPS); else SCF_LAUNCH(6, X4_NONE);
+    } else {
+      if (res2_f) SCF_LAUNCH(8, X4_RES2); else if (eps_f) SCF_LAUNCH(8, X4_EPS); else SCF_LAUNCH(8, X4_NONE);
+    }
+#undef SCF_LAUNCH
+    DV_HIP(hipGetLastError());
+  }
   return OK;
 }
 

@@ -410,7 +410,12 @@ class DeblendFieldBatch:
     those of DeblendField on that field, for the noise rows its galaxies have in the call (galaxies are numbered over all
     fields, field after field).  The epistemic estimate is an option of the pass (deblend_fields(...,
     epistemic_uncertainty_estimation=True)), not of the object: the Monte-Carlo decodes of all fields run inside the same
-    engine call, on the encoder output of the deblending pass."""
+    engine call, on the encoder output of the deblending pass.
+
+    deblend_fields(..., optimise_positions=True) also fits every galaxy's sub-pixel shift - with on_device=True inside the
+    same engine call, on stamps that stay on the GPU, the fields being composited there at the fitted positions (DESIGN.md
+    section 7i).  One field is this class with M = 1: DeblendField.deblend_field(optimise_positions=True) stays
+    unimplemented."""
 
     DEFAULT_COLUMNS = [("cutout_images", "O"), ("output_images_mean", "O"), ("output_images_stddev", "O"), ("shifts", "O"),
                        ("list_idx", "<i8"), ("galaxy_distances_to_center_x", "<f8"), ("galaxy_distances_to_center_y", "<f8"),
@@ -444,6 +449,7 @@ class DeblendFieldBatch:
         self._ctx_obj = getattr(getattr(net, "_core", None), "ctx", None)
         self._device_fields = None      # (res_deblend list, fields composited on the GPU) of the last on-device pass
         self._epistemic_pass = None     # the res_deblend list of the last pass, if it estimated the epistemic uncertainty
+        self.position_fit = None        # per field {objective, iters, status} of the last on-device pass that fitted positions
 
     @property
     def _ctx(self):
@@ -457,8 +463,16 @@ class DeblendFieldBatch:
             col[i] = np.array([0, 0])
         return col
 
+    @staticmethod
+    def _fitted_column(shifts):
+        col = np.empty(len(shifts), dtype=object)
+        for i in range(len(shifts)):
+            col[i] = np.array([shifts[i, 0], shifts[i, 1]], dtype=np.float64)
+        return col
+
     def deblend_fields(self, galaxy_distances_to_center=None, mse_criterion=100.0, on_device=False,
-                       epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100):
+                       epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100,
+                       optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -472,8 +486,17 @@ class DeblendFieldBatch:
         galaxy whose normalised uncertainty sum(std[:, :, 2]) / sum(mean[:, :, 2]) exceeds `epistemic_criterion` fails the
         cuts, as in DeblendField.  By default the `epistemic_uncertainty` column carries the float64 std stamps; with
         on_device=True the std stamps are composited on the GPU (get_predicted_fields()["predicted_epistemic_fields"]) and
-        the recarrays gain an `epistemic_norm` column."""
+        the recarrays gain an `epistemic_norm` column.
+
+        optimise_positions=True: every galaxy's sub-pixel shift is fitted within [-3, 3]^2 from zero and written to the
+        `shifts` column as float64 np.array([sx, sy]).  With on_device=True the fit runs inside the same engine call on the
+        stamps in device memory (dv_infer_fields_fit_composite), the fields are composited on the GPU at the fitted
+        positions and self.position_fit holds, per field, the fit's {objective, iters, status}; by default the pass is
+        followed by self.optimise_positions(), and the fields are composited on request from the stamps."""
         mc = bool(epistemic_uncertainty_estimation)
+        fit = bool(optimise_positions)
+        if fit and self.nb_of_bands < 3:
+            raise ValueError(f"the position fit uses band 2 (r); these fields have {self.nb_of_bands} band(s)")
         if mc:
             if int(epistemic_samples) < 1:
                 raise ValueError(f"epistemic_samples must be at least 1, got {epistemic_samples}")
@@ -499,13 +522,17 @@ class DeblendFieldBatch:
         self.res_deblend = None
         self._device_fields = None
         self._epistemic_pass = None
+        self.position_fit = None
         N = len(starts)
         eng.set_normalise(bool(self.normalise))
         try:
             seed = core.next_seed()
             if mc:
                 mc_args = {"seed": seed, "mc_seed": core.next_seed(), "nsamples": int(epistemic_samples)}
-            if on_device:
+            if on_device and fit:
+                out = eng.infer_fields_fit_composite(self.field_images, starts, dd, field_ptr, bound=3.0,
+                                                     **(mc_args if mc else {"seed": seed}))
+            elif on_device:
                 # where get_predicted_field puts a stamp: padded at int((F - cs) / 2) and shifted by the distance to the centre
                 places = (int((F - cs) / 2) + dd).astype(np.int64)
                 if mc:
@@ -544,7 +571,7 @@ class DeblendFieldBatch:
             n = hi - lo
             rec = np.recarray((n,), dtype=columns)
             rec["list_idx"] = kept[m]
-            rec["shifts"] = self._shifts_column(n)
+            rec["shifts"] = self._shifts_column(n) if not (on_device and fit) else self._fitted_column(out["shifts"][lo:hi])
             rec["galaxy_distances_to_center_x"] = dd[lo:hi, 0]
             rec["galaxy_distances_to_center_y"] = dd[lo:hi, 1]
             rec["passed_cuts"] = passed[lo:hi]
@@ -566,6 +593,11 @@ class DeblendFieldBatch:
             self._device_fields = (res, out)
         if mc:
             self._epistemic_pass = res
+        if fit and on_device:
+            self.position_fit = [{k: out[k][int(field_ptr[m]):int(field_ptr[m + 1])].copy() for k in ("objective", "iters", "status")}
+                                 for m in range(self.nb_of_fields)]
+        elif fit:
+            self.optimise_positions()
         return res
 
     def _own_device_fields(self):
@@ -638,10 +670,6 @@ class DeblendFieldBatch:
                                for r in res]).astype(np.float64)
         shifts = position_optimization_fields(self.field_images, stamps, dist, field_ptr, bound=3.0, ctx=self._ctx)
         for m, rec in enumerate(res):
-            lo = int(field_ptr[m])
-            col = np.empty(len(rec), dtype=object)
-            for i in range(len(rec)):
-                col[i] = np.array([shifts[lo + i, 0], shifts[lo + i, 1]], dtype=np.float64)
-            rec["shifts"] = col
+            rec["shifts"] = self._fitted_column(shifts[int(field_ptr[m]):int(field_ptr[m + 1])])
         self._device_fields = None
         return res

@@ -916,6 +916,51 @@ class Engine:
         check(lib.dv_infer_fields_mc_composite(self._h, *args, int(seed), int(mc_seed), int(nsamples), *ptrs))
         return out
 
+    # -- the same with the sub-pixel position fit and fractional placements on the GPU --
+    def infer_fields_fit_composite(self, fields, starts, distances, field_ptr, seed=0, shifts=None, bound: float = 3.0,
+                                   max_iter: int = 50, mc_seed=0, nsamples=0, residual=True,
+                                   mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_composite() with every galaxy's sub-pixel shift fitted on the GPU (scene_fit_shifts_fields on the r
+        band of the mean stamps, which stay in device memory) and the stamps placed at int((F - cs) / 2) + distances + shifts
+        with scipy.ndimage.shift's cubic spline (dv_infer_fields_fit_composite).  distances (N, 2) {row, column}: integers.
+        shifts (N, 2): the start (zeros by default); max_iter = 0 places at them without fitting.  nsamples > 0 adds
+        infer_fields_mc_composite's "epistemic_fields" and "eps_norm".  Returns the fields and scalars of those calls plus
+        {"shifts" (N, 2), "objective", "iters", "status" (N,)} as scene_fit_shifts returns them."""
+        fields = _check_fields(fields)
+        dist = np.ascontiguousarray(distances, dtype=np.float64).reshape(-1, 2)
+        starts_c = _i32_rows(starts, "cutout starts")
+        N = starts_c.shape[0]
+        if dist.shape != (N, 2):
+            raise ValueError(f"{N} cutout starts but distances of shape {dist.shape}")
+        if not (np.isfinite(dist).all() and np.array_equal(dist, np.floor(dist)) and (np.abs(dist) <= 1e6).all()):
+            raise ValueError("the device path places stamps at integer distances (within +-1e6); fractional distances need "
+                             "the default path")
+        if fields.shape[3] < 3:
+            raise ValueError(f"the position fit uses band 2 (r); these fields have {fields.shape[3]} band(s)")
+        if not (np.isfinite(bound) and 0 <= bound <= 1e6) or int(max_iter) < 0:
+            raise ValueError(f"bound must lie in 0 .. 1e6 and max_iter be >= 0 (got {bound}, {max_iter})")
+        sh = np.zeros((N, 2), np.float64) if shifts is None else np.array(shifts, dtype=np.float64, order="C", copy=True)
+        if sh.shape != (N, 2) or not np.isfinite(sh).all() or (np.abs(sh) > 1e6).any():
+            raise ValueError(f"expected finite start shifts ({N}, 2) within +-1e6, got shape {sh.shape}")
+        mc = int(nsamples) != 0
+        if mc:
+            Engine._check_mc(nsamples, fields.shape[3])
+        fields, N, args = Engine._field_args(fields, starts_c, field_ptr)
+        out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center, epistemic=mc)
+        if not mc:
+            ptrs = ptrs[:2] + [None] + ptrs[2:] + [None]
+        out.update(shifts=sh, objective=np.zeros(N, np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
+        args = args[:5] + [_dp(dist)] + args[5:]
+        check(lib.dv_infer_fields_fit_composite(self._h, *args, int(seed), float(bound), int(max_iter), _dp(sh), int(mc_seed),
+                                                int(nsamples), *ptrs, _dp(out["objective"]), _ip(out["iters"]),
+                                                _ip(out["status"])))
+        return out
+
+    def infer_cutouts_fit_composite(self, field, starts, distances, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_fit_composite() for one field (F, F, bands): the field-sized results under singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_fit_composite(fields, starts, distances, fp, seed=seed, **kw))
+
     # -- one field: M = 1 views of the calls above, the field-sized results under singular key names --
     @staticmethod
     def _one_field(field, starts):

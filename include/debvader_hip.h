@@ -304,6 +304,30 @@ int dv_infer_fields_mc_composite(dv_model* m, const double* fields, int32_t M, i
                                  int32_t nsamples, double* mean_fields, double* stddev_fields, double* epistemic_fields,
                                  double* residual_fields, double* mse_center, double* eps_norm);
 
+/* ---- sub-pixel positions in the many-field composite call ----
+ * dv_infer_fields_composite with the position fit of dv_scene_fit_shifts as a stage of the pipeline and the stamps
+ * placed at the fitted positions, all on stamps that stay in device memory.  Behind every chunk's forward pass (`seed`; the
+ * network's outputs and mse_center have the bits of the calls above) and, where asked for, its Monte-Carlo stage, the r band
+ * (band 2) of the chunk's mean stamps is fitted against the r band of the resident fields - galaxy i from shifts_inout[i]
+ * within [-bound, bound]^2, at most max_iter Newton steps, objective / iters / status [N] as dv_scene_fit_shifts returns
+ * them and with the bits dv_scene_fit_shifts_fields gives on the stamps dv_infer_fields_keep returns - and the chunk is
+ * composited at int((F - cs) / 2) + dist[i] + shifts_inout[i]: an object whose two total positions are integers as an exact
+ * translation (the bits of dv_infer_fields_composite), any other with scipy.ndimage.shift's cubic B-spline (order 3, mode
+ * "constant") as dv_scene_composite evaluates it, float64 sums in object order.  max_iter = 0 fits nothing: the stamps are
+ * placed at the given shifts (objective = J there, status 2).
+ * dist [N][2] {row, column}: integer values within +-1e6.  nsamples = 0 with epistemic_fields and eps_norm null: no
+ * Monte-Carlo stage; otherwise both are required and filled as by dv_infer_fields_mc_composite (mc_seed, nsamples >= 1).
+ * residual_fields and mse_center may be null.  Refused before any GPU work (DV_E_INVALID): nb < 3, a fractional or
+ * out-of-range distance, bound outside 0 .. 1e6, max_iter < 0, a non-finite start shift, a missing output.
+ * Beside the fields of dv_infer_fields_composite a resident field holds its r-band plane; the fit's workspace (at most
+ * 1 GiB) and the B-spline coefficients of 64 stamps are allocated once per call, whatever N is. */
+int dv_infer_fields_fit_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                  const double* dist, const int64_t* field_ptr, int64_t N, uint64_t seed, double bound,
+                                  int32_t max_iter, double* shifts_inout, uint64_t mc_seed, int32_t nsamples,
+                                  double* mean_fields, double* stddev_fields, double* epistemic_fields,
+                                  double* residual_fields, double* mse_center, double* eps_norm, double* objective,
+                                  int32_t* iters, int32_t* status);
+
 /* Monte-Carlo epistemic uncertainty: encode each stamp once, decode it `nsamples` times with fresh eps, return the
  * mean and the standard deviation (ddof 0) of the predicted means over the samples.  Replaces the per-object loop
  * `np.std(deblend(net, [stamp]*100)[0], axis=0)` of deblend/field_deblender.py:303-313. */

@@ -27,6 +27,15 @@ cuts of every field with N Monte-Carlo samples per galaxy,
              epistemic_samples=N) + get_predicted_fields()
 
 alternating, --repeat times each, both engines.
+
+--optimise-positions runs a third comparison INSTEAD: fields with every galaxy at its fitted sub-pixel
+position (distances rounded to integers, as the device path needs),
+
+    host  :  db.deblend_fields(d); db.optimise_positions(); db.get_predicted_fields(); db.get_residual_fields()
+             (stamps to the host, their r band up again for the fit, all of them up again for three composites per field)
+    device:  db.deblend_fields(d, on_device=True, optimise_positions=True); get_predicted_fields(); get_residual_fields()
+
+alternating, --repeat times each, both engines; --profile-one: warm up, one fp32 device call, exit (for a kernel trace).
 """
 import argparse
 import json
@@ -146,6 +155,52 @@ def _epistemic_leg(a, fields, quiet, redirect_stdout):
     print(json.dumps(result))
 
 
+def _fit_host(net, fields, dists):
+    db = DeblendFieldBatch(net, fields)
+    res = db.deblend_fields(dists)
+    db.optimise_positions()
+    db.get_predicted_fields()
+    db.get_residual_fields()
+    return sum(len(r) for r in res)
+
+
+def _fit_device(net, fields, dists):
+    db = DeblendFieldBatch(net, fields)
+    res = db.deblend_fields(dists, on_device=True, optimise_positions=True)
+    db.get_predicted_fields()
+    db.get_residual_fields()
+    return sum(len(r) for r in res)
+
+
+def _fit_leg(a, fields, quiet, redirect_stdout):
+    M, F = len(fields), fields.shape[1]
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "optimise_positions": True}
+    dists = None
+    for dtype in ("float32", "bf16"):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections; max_batch {a.max_batch}")
+        with redirect_stdout(quiet):
+            _fit_host(net, fields[:8], dists[:8])                                      # warm-up
+            _fit_device(net, fields, dists)
+            if a.profile_one:
+                _fit_device(net, fields, dists)
+                net._core.engine.close()
+                return
+            th, td, n = _alternate(lambda: _fit_host(net, fields, dists), lambda: _fit_device(net, fields, dists), a.repeat)
+        print(_row(f"{dtype} fitted fields, host", th, n, M))
+        print(_row(f"{dtype} fitted fields, device", td, n, M))
+        factor = float(np.median(th) / np.median(td))
+        print(f"{dtype} fitted fields host / device: {factor:.2f} x  (slowest device {1e3 * td.max():.1f} ms, fastest host "
+              f"{1e3 * th.min():.1f} ms)")
+        result[dtype] = {"stamps": n, "host_ms": [round(1e3 * x, 2) for x in th], "device_ms": [round(1e3 * x, 2) for x in td],
+                         "factor": round(factor, 3)}
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
 def _alternate(fa, fb, repeat):
     ta, tb, n = [], [], 0
     for _ in range(repeat):
@@ -170,7 +225,9 @@ def main():
     ap.add_argument("--max-batch", type=int, default=8192)
     ap.add_argument("--default-fields", type=int, default=64)
     ap.add_argument("--epistemic", type=int, default=0, help="Monte-Carlo samples: run the epistemic comparison instead")
-    ap.add_argument("--profile-one", action="store_true", help="with --epistemic: warm up, one fp32 batched call, exit")
+    ap.add_argument("--optimise-positions", action="store_true", help="run the fitted-positions comparison instead")
+    ap.add_argument("--profile-one", action="store_true",
+                    help="with --epistemic or --optimise-positions: warm up, one fp32 batched call, exit")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     F, M = a.size, a.fields
@@ -181,6 +238,9 @@ def main():
     quiet = io.StringIO()                      # the classes print the reference's notes about dropped galaxies
     if a.epistemic > 0:
         _epistemic_leg(a, fields, quiet, redirect_stdout)
+        return
+    if a.optimise_positions:
+        _fit_leg(a, fields, quiet, redirect_stdout)
         return
     result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat}
     dists = None
