@@ -45,6 +45,11 @@ class DvDetectParams(C.Structure):
     ]
 
 
+class DvMeasureParams(C.Structure):
+    """dv_measure_params (include/debvader_hip.h)"""
+    _fields_ = [("band", C.c_int32), ("sigma0", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int32)]
+
+
 class DvError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libdebvader_hip status {status}: {msg}")
@@ -151,6 +156,11 @@ SIGNATURES = {
                                              C.c_int32, _d, _d, _i32, _i32]),
     "dv_scene_detect": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams), C.c_int64, _i64,
                                   _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d, _d, _d, _d, _i32]),
+    "dv_measure_params_default": (C.c_int, [C.POINTER(DvMeasureParams)]),
+    "dv_scene_measure": (C.c_int, [_p, _f, _f, C.c_int64, C.c_int32, C.c_int32, C.POINTER(DvMeasureParams), _d, _d, _d, _i32,
+                                   _i32]),
+    "dv_infer_fields_measure": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
+                                          C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32]),
     "dv_field_set_open": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),

@@ -227,6 +227,18 @@ int posfit_plan_run(const PosfitPlan* p, int l0, int l1, const double* img_dev, 
 int launch_posfit_total_sq(const double* img_dev, int nfields, long elems, double* out_dev, hipStream_t s);
 int launch_posfit_band_f64(const double* src_dev, long npix, int nb, int band, double* dst_dev, hipStream_t s);
 int launch_posfit_band_f32(const float* src_dev, long npix, int nb, int band, double* dst_dev, hipStream_t s);
+// catalogue measurement (measure.hip): per-band fluxes and errors and the adaptive moments of band `band` of
+// float32 mean / stddev stamps [.][cs][cs][nb]; flux / flux_err [.][nb], shape [.][5] = {r0, c0, Mrr, Mrc, Mcc}, iters and
+// status [.].  measure_check: the refusals, before any GPU work.  launch_measure: n stamps in device memory, the output
+// pointers at their first row (stddev is read only when flux_err is wanted).  scene_measure: host arrays, at most `chunk`
+// stamps on the device at a time.
+int measure_check(const char* who, int cs, int nb, int band, double sigma0, double tol, int max_iter);
+int launch_measure(const float* mean_dev, const float* stddev_dev, int n, int cs, int nb, int band, double sigma0,
+                   double tol, int max_iter, double* flux_dev, double* flux_err_dev, double* shape_dev, int* iters_dev,
+                   int* status_dev, hipStream_t s);
+int scene_measure(const float* mean_h, const float* stddev_h, int64_t N, int cs, int nb, int band, double sigma0, double tol,
+                  int max_iter, double* flux_h, double* flux_err_h, double* shape_h, int32_t* iters_h, int32_t* status_h,
+                  int64_t chunk, hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

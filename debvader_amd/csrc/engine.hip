@@ -3061,6 +3061,13 @@ struct PipeJob {
   int *fit_iters = nullptr, *fit_status = nullptr;         // device [.]
   void* objs_d = nullptr;              // device [chunk]: a chunk's placements
   double* coef_d = nullptr;            // device: B-spline coefficients of a sub-chunk
+  // catalogue measurement (dv_infer_fields_measure): behind every chunk's forward pass, fluxes and adaptive
+  // moments of its mean / stddev stamps as they lie in HBM; ms_flux decides.  Without mean_f this is the catalogue-only
+  // call: no stamp and no field leaves the device
+  double *ms_flux = nullptr, *ms_ferr = nullptr, *ms_shape = nullptr;   // device [.][nb], [.][nb], [.][5]
+  int *ms_iters = nullptr, *ms_status = nullptr;                        // device [.]
+  int ms_band = 0, ms_max_iter = 0;
+  double ms_sigma0 = 0.0, ms_tol = 0.0;
 };
 
 // The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
@@ -3101,8 +3108,9 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
   const int chunk = j.chunk, cs = A.H;
   const int64_t N = j.N, row0 = j.row0;
   const bool comp = j.mean_f != nullptr;
+  const bool meas = j.ms_flux != nullptr;
   InferPipe* p = nullptr;
-  DV_TRY(pipe_get(m, chunk, &p, !comp));
+  DV_TRY(pipe_get(m, chunk, &p, !comp && !meas));
   if (j.eps_out) DV_TRY(pipe_eps_buffers(m, p));
   const int64_t K = (N + chunk - 1) / chunk;
   const int d = A.d;
@@ -3194,7 +3202,7 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
       m->scale = keep_scale;
       DV_TRY(st);
     }
-    if (m->normalise && (j.loc || j.consumer || comp)) DV_TRY(launch_normalise(p->dloc[b], (long)nb * stamp, true, s));
+    if (m->normalise && (j.loc || j.consumer || comp || meas)) DV_TRY(launch_normalise(p->dloc[b], (long)nb * stamp, true, s));
     if (j.mu)
       DV_HIP(hipMemcpy2DAsync(p->dsmall[b], d * sizeof(float), m->t, A.twp * sizeof(float), d * sizeof(float), nb,
                               hipMemcpyDeviceToDevice, s));
@@ -3250,6 +3258,17 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
       if (j.mse)
         DV_TRY(launch_scene_center_mse(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, p->dloc[b], nb, cs, j.mse + r, p->s_out,
                                        j.sfield_d + r, j.f0));
+    }
+    if (meas) {
+      // the catalogue of this chunk, on the output stream like the compositing: one workgroup per stamp reads the chunk's
+      // mean and stddev stamps where the head kernel left them; the forward of chunk k + 2 waits for ev_d2h below
+      ProfScope ps(m, 2, p->s_out);
+      if (!comp && j.mse)                  // the catalogue-only call: the quality cut's input without the fields
+        DV_TRY(launch_scene_center_mse(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, p->dloc[b], nb, cs, j.mse + r, p->s_out,
+                                       j.sfield_d + r, j.f0));
+      DV_TRY(launch_measure(p->dloc[b], p->dscale[b], nb, cs, j.nb, j.ms_band, j.ms_sigma0, j.ms_tol, j.ms_max_iter,
+                            j.ms_flux + (size_t)r * j.nb, j.ms_ferr + (size_t)r * j.nb, j.ms_shape + (size_t)r * 5,
+                            j.ms_iters + r, j.ms_status + r, p->s_out));
     }
     if (j.loc || j.consumer) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (j.scale || j.consumer) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
@@ -3681,6 +3700,30 @@ int dv_scene_fit_shifts_fields(dv_ctx* c, const double* fields_r, int32_t M, int
   if (budget == 0) budget = 1;                    // 0 would mean "no limit" below
   return scene_fit_shifts_fields(fields_r, M, F, stamps_r, field_ptr, (int)N, cs, dist, bound, max_iter, shifts_inout,
                                  objective, iters, status, budget, c->stream);
+}
+
+int dv_measure_params_default(dv_measure_params* p) {
+  if (!p) return DV_E_INVALID;
+  p->band = 2;
+  p->sigma0 = 3.0;
+  p->tol = 1e-10;
+  p->max_iter = 200;
+  return DV_OK;
+}
+
+int dv_scene_measure(dv_ctx* c, const float* mean, const float* stddev, int64_t N, int32_t cs, int32_t nb,
+                     const dv_measure_params* p, double* flux, double* flux_err, double* shape, int32_t* iters,
+                     int32_t* status) {
+  if (!c || !p) return DV_E_INVALID;
+  DV_TRY(measure_check("dv_scene_measure", cs, nb, p->band, p->sigma0, p->tol, p->max_iter));   // before any GPU work
+  DV_HIP(hipSetDevice(c->device));
+  // stamps per chunk: half of free device memory holds a chunk's mean and stddev stamps and its catalogue rows
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t per_stamp = (size_t)cs * cs * nb * 2 * sizeof(float) + (2 * (size_t)nb + 6) * sizeof(double);
+  const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 2 / per_stamp);
+  return scene_measure(mean, stddev, N, cs, nb, p->band, p->sigma0, p->tol, p->max_iter, flux, flux_err, shape, iters,
+                       status, chunk, c->stream);
 }
 
 int dv_scene_detect(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, const dv_detect_params* p,
@@ -4488,6 +4531,13 @@ struct FieldsOut {                  // result fields of dv_infer_fields_composit
   int32_t *iters = nullptr, *status = nullptr;
 };
 
+struct MeasureOut {                 // the catalogue of dv_infer_fields_measure, host, rows = global stamp numbers
+  dv_measure_params par{};
+  double *flux = nullptr, *flux_err = nullptr, *shape = nullptr;   // [N][nb], [N][nb], [N][5]
+  int32_t *iters = nullptr, *status = nullptr;                     // [N]
+  double* mse = nullptr;            // [N], optional: mse_center of the catalogue-only call (no FieldsOut to carry it)
+};
+
 // the refusals every field-sourced call takes before any GPU work, and the two tables it works from: sfield[i] = the field
 // of stamp i, fptr32 = field_ptr as the kernels read it.  places: the placements of a compositing call, or null.
 static int fields_tables(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, int F, int nb,
@@ -4541,7 +4591,7 @@ static int fields_tables(dv_model* m, const char* who, int32_t M, const int64_t*
 // j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
 // the device side and the rows are filled in here
 static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
-                             const FieldsOut* fo = nullptr) {
+                             const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr) {
   const double* fields = j.fields;
   const int32_t* starts = j.starts;
   const int F = j.F, nb = j.nb;
@@ -4565,7 +4615,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   const int chunk = infer_chunk(m, N);
   const int64_t K = (N + chunk - 1) / chunk;
   InferPipe* pipe = nullptr;
-  DV_TRY(pipe_get(m, chunk, &pipe, fo == nullptr));   // before the budget below: the pipeline's buffers come first
+  DV_TRY(pipe_get(m, chunk, &pipe, fo == nullptr && mo == nullptr));   // before the budget below: the pipeline's buffers come first
   // the fit's plan: every galaxy's windows, laid out chunk by chunk against field 0 (rebased once the groups are known);
   // its workspace, the coefficient workspace of the fractional compositing and a chunk's r-band stamps and placements are
   // allocated once per call and come off the budget like the tables
@@ -4596,7 +4646,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   const size_t per_field = fb * (fo ? (fo->residual ? 4 : 3) + (fo->epistemic ? 1 : 0) : 1) +
                            (fit ? ((size_t)F * F + 1) * sizeof(double) : 0);   // (the fit: an r-band plane and its sum of squares)
   const size_t tables = (size_t)N * (5 * sizeof(int) + sizeof(double) * (fo && fo->eps_norm ? 2 : 1)) + ((size_t)M + 1) * sizeof(int) +
-                        fit_fixed;
+                        fit_fixed + (mo ? (size_t)N * ((2 * (size_t)nb + 6) * sizeof(double) + 2 * sizeof(int)) : 0);   // (the catalogue)
   size_t free_b = 0, total_b = 0;
   DV_HIP(hipMemGetInfo(&free_b, &total_b));
   size_t budget = free_b / 10 * 8;
@@ -4640,6 +4690,9 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
          *f_obj = nullptr, *f_coef = nullptr;
   int *f_iters = nullptr, *f_status = nullptr;
   void* f_objs = nullptr;
+  double *c_flux = nullptr, *c_ferr = nullptr, *c_shape = nullptr;
+  int *c_iters = nullptr, *c_status = nullptr;
+  double* mse_h = fo ? fo->mse : mo ? mo->mse : nullptr;
   int st = OK;
   auto cleanup = [&]() {
     if (st != OK && pipe->s_out) (void)hipStreamSynchronize(pipe->s_out);   // nothing may still read these
@@ -4647,6 +4700,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     (void)hipFree(f_img); (void)hipFree(f_tot); (void)hipFree(f_dist); (void)hipFree(f_stamps); (void)hipFree(f_work);
     (void)hipFree(f_shifts); (void)hipFree(f_obj); (void)hipFree(f_coef); (void)hipFree(f_iters); (void)hipFree(f_status);
     (void)hipFree(f_objs);
+    (void)hipFree(c_flux); (void)hipFree(c_ferr); (void)hipFree(c_shape); (void)hipFree(c_iters); (void)hipFree(c_status);
     (void)hipFree(fdev); (void)hipFree(mf); (void)hipFree(sf); (void)hipFree(rf); (void)hipFree(mse);
     (void)hipFree(ef); (void)hipFree(en);
     (void)hipFree(sdev); (void)hipFree(pdev); (void)hipFree(sfdev); (void)hipFree(fpdev);
@@ -4658,13 +4712,29 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     FF_HIP(hipMalloc((void**)&mf, (size_t)gmax * fb));
     FF_HIP(hipMalloc((void**)&sf, (size_t)gmax * fb));
     if (fo->residual) FF_HIP(hipMalloc((void**)&rf, (size_t)gmax * fb));
-    if (fo->mse) FF_HIP(hipMalloc((void**)&mse, (size_t)N * sizeof(double)));
     if (fo->epistemic) FF_HIP(hipMalloc((void**)&ef, (size_t)gmax * fb));
     if (fo->eps_norm) FF_HIP(hipMalloc((void**)&en, (size_t)N * sizeof(double)));
     if (!fit) {
       FF_HIP(hipMalloc((void**)&pdev, sb));
       FF_HIP(hipMemcpyAsync(pdev, fo->places, sb, hipMemcpyHostToDevice, s));
     }
+  }
+  if (mse_h) FF_HIP(hipMalloc((void**)&mse, (size_t)N * sizeof(double)));
+  if (mo) {
+    FF_HIP(hipMalloc((void**)&c_flux, (size_t)N * nb * sizeof(double)));
+    FF_HIP(hipMalloc((void**)&c_ferr, (size_t)N * nb * sizeof(double)));
+    FF_HIP(hipMalloc((void**)&c_shape, (size_t)N * 5 * sizeof(double)));
+    FF_HIP(hipMalloc((void**)&c_iters, (size_t)N * sizeof(int)));
+    FF_HIP(hipMalloc((void**)&c_status, (size_t)N * sizeof(int)));
+    j.ms_flux = c_flux;
+    j.ms_ferr = c_ferr;
+    j.ms_shape = c_shape;
+    j.ms_iters = c_iters;
+    j.ms_status = c_status;
+    j.ms_band = mo->par.band;
+    j.ms_sigma0 = mo->par.sigma0;
+    j.ms_tol = mo->par.tol;
+    j.ms_max_iter = mo->par.max_iter;
   }
   if (fit) {
     const size_t nd = (size_t)N * sizeof(double);
@@ -4766,7 +4836,15 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     prev_last = g.f1;
   }
   if (mse) {
-    FF_HIP(hipMemcpyAsync(fo->mse, mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipMemcpyAsync(mse_h, mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipStreamSynchronize(s));
+  }
+  if (mo) {
+    FF_HIP(hipMemcpyAsync(mo->flux, c_flux, (size_t)N * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipMemcpyAsync(mo->flux_err, c_ferr, (size_t)N * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipMemcpyAsync(mo->shape, c_shape, (size_t)N * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipMemcpyAsync(mo->iters, c_iters, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    FF_HIP(hipMemcpyAsync(mo->status, c_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
     FF_HIP(hipStreamSynchronize(s));
   }
   if (en) {
@@ -4884,6 +4962,46 @@ int dv_infer_fields_composite(dv_model* m, const double* fields, int32_t M, int3
   fo.mse = mse_center;
   fo.places = places;
   return infer_fields_impl(m, "dv_infer_fields_composite", M, field_ptr, N, fields_job(fields, F, nb, starts, seed), &fo);
+}
+
+// ---- catalogue measurement as a stage of the many-field call -----------------------------------------------
+int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                            const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                            const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                            double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                            int32_t* iters, int32_t* status) {
+  const char* who = "dv_infer_fields_measure";
+  if (!m || !params) return DV_E_INVALID;
+  DV_TRY(measure_check(who, m->A.H, nb, params->band, params->sigma0, params->tol, params->max_iter));
+  if (N > 0 && (!flux || !flux_err || !shape || !iters || !status)) {
+    set_error("%s: flux, flux_err, shape, iters and status must all be given", who);
+    return DV_E_INVALID;
+  }
+  const bool with_fields = mean_fields || stddev_fields || residual_fields;
+  if (with_fields && ((M > 0 && (!mean_fields || !stddev_fields)) || (N > 0 && !places))) {
+    set_error("%s: mean_fields, stddev_fields and places go together (residual_fields is optional beside them); the "
+              "catalogue-only call passes all three fields as null", who);
+    return DV_E_INVALID;
+  }
+  MeasureOut mo;
+  mo.par = *params;
+  mo.flux = flux;
+  mo.flux_err = flux_err;
+  mo.shape = shape;
+  mo.iters = iters;
+  mo.status = status;
+  PipeJob j = fields_job(fields, F, nb, starts, seed);
+  if (!with_fields) {
+    mo.mse = mse_center;
+    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo);
+  }
+  FieldsOut fo;
+  fo.mean = mean_fields;
+  fo.stddev = stddev_fields;
+  fo.residual = residual_fields;
+  fo.mse = mse_center;
+  fo.places = places;
+  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo);
 }
 
 // the refusals of the two Monte-Carlo forms, before any GPU work

@@ -139,6 +139,35 @@ def _check_fields(fields) -> np.ndarray:
     return fields
 
 
+def measure_params(band, sigma0, tol, max_iter, bands: int) -> "_lib.DvMeasureParams":
+    """The checked dv_measure_params of the measurement calls (the library refuses the same, after the arrays are built)."""
+    if int(band) != band or not 0 <= int(band) < int(bands):
+        raise ValueError(f"band {band} asked for, the stamps have bands 0 .. {int(bands) - 1}")
+    if not (np.isfinite(sigma0) and sigma0 > 0) or not (np.isfinite(tol) and tol > 0):
+        raise ValueError(f"sigma0 and tol must be finite and positive (got {sigma0}, {tol})")
+    if int(max_iter) != max_iter or int(max_iter) < 0:
+        raise ValueError(f"max_iter must be an integer >= 0 (got {max_iter})")
+    return _lib.DvMeasureParams(int(band), float(sigma0), float(tol), int(max_iter))
+
+
+MEASURE_MAX_STAMP = 90      # the float64 band plane of a larger stamp does not fit the measurement kernel's 64 KB of LDS
+
+
+def check_measure_args(mean, stddev, band, sigma0, tol, max_iter):
+    """(mean, stddev, params) of scene_measure: C-contiguous float32 stamps (N, cs, cs, bands), stddev None or of the same
+    shape."""
+    mean = _f32c(mean)
+    if mean.ndim != 4 or mean.shape[1] != mean.shape[2] or mean.shape[1] < 1 or mean.shape[3] < 1:
+        raise ValueError(f"expected square stamps (N, cs, cs, bands), got {mean.shape}")
+    if mean.shape[1] > MEASURE_MAX_STAMP:
+        raise ValueError(f"stamps of {mean.shape[1]} pixels: the measurement takes at most {MEASURE_MAX_STAMP}")
+    if stddev is not None:
+        stddev = _f32c(stddev)
+        if stddev.shape != mean.shape:
+            raise ValueError(f"mean stamps {mean.shape} but stddev stamps {stddev.shape}")
+    return mean, stddev, measure_params(band, sigma0, tol, max_iter, mean.shape[3])
+
+
 def check_detect_args(fields_r, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
                       workspace_bytes=0) -> np.ndarray:
     """Context.scene_detect's argument checks (before any GPU work); returns the fields as float64 (M, H, W)."""
@@ -469,6 +498,27 @@ class Context:
                                                  out.ctypes.data_as(dp), obj.ctypes.data_as(dp), iters.ctypes.data_as(ip),
                                                  status.ctypes.data_as(ip)))
         return dict(shifts=out, objective=obj, iters=iters, status=status)
+
+    MEASURE_CONVERGED, MEASURE_ITER_LIMIT, MEASURE_FAILED = 0, 2, 3           # status codes of scene_measure
+
+    def scene_measure(self, mean, stddev=None, band: int = 2, sigma0: float = 3.0, tol: float = 1e-10,
+                      max_iter: int = 200) -> Dict[str, np.ndarray]:
+        """Catalogue measurement of N stamps on the GPU (dv_scene_measure): mean, stddev (N, cs, cs,
+        bands) - the network's mean and stddev stamps, taken as float32.  Returns {"flux" (N, bands): the sum of every
+        band's mean stamp, ["flux_err" (N, bands): sqrt of the sum of the squared stddev stamp, when stddev is given],
+        "shape" (N, 5): {row, col, Mrr, Mrc, Mcc}, the adaptive moments of band `band` (rows and columns counted from the
+        stamp's pixel 0), "iters" (N,), "status" (N,): MEASURE_CONVERGED, MEASURE_ITER_LIMIT or MEASURE_FAILED (degenerate
+        moments, no positive weighted flux, or a centroid that left the stamp)}, float64 throughout."""
+        mean, stddev, par = check_measure_args(mean, stddev, band, sigma0, tol, max_iter)
+        n, cs, nb = mean.shape[0], mean.shape[1], mean.shape[3]
+        out = {"flux": np.zeros((n, nb), np.float64)}
+        if stddev is not None:
+            out["flux_err"] = np.zeros((n, nb), np.float64)
+        out.update(shape=np.zeros((n, 5), np.float64), iters=np.zeros(n, np.int32), status=np.zeros(n, np.int32))
+        if n:
+            check(lib.dv_scene_measure(self._h, _fp(mean), _fp(stddev), n, cs, nb, C.byref(par), _dp(out["flux"]),
+                                       _dp(out.get("flux_err")), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"])))
+        return out
 
     CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
 
@@ -875,6 +925,41 @@ class Engine:
         out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
         check(lib.dv_infer_fields_composite(self._h, *args, int(seed), *ptrs))
         return out
+
+    def infer_fields_measure(self, fields, starts, field_ptr, places=None, seed=0, band: int = 2, sigma0: float = 3.0,
+                             tol: float = 1e-10, max_iter: int = 200, return_fields=True, residual=True,
+                             mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_composite() with the catalogue measurement of scene_measure as one more stage of the pipeline
+        (dv_infer_fields_measure): behind every chunk's forward pass the chunk's mean and stddev stamps
+        are measured where they lie in device memory.  Returns infer_fields_composite's dictionary plus {"flux", "flux_err"
+        (N, bands), "shape" (N, 5), "iters", "status" (N,)} - rows are the global stamp numbers, the bits those of
+        scene_measure on the stamps infer_fields returns for the same seed.  return_fields=False is the catalogue-only
+        call: no field is composited, allocated or downloaded, `places` is not needed, and the dictionary holds the
+        catalogue (and mse_center) only."""
+        if return_fields and places is None:
+            raise ValueError("places are needed to composite the fields; return_fields=False measures without them")
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places if return_fields else None)
+        par = measure_params(band, sigma0, tol, max_iter, fields.shape[3])
+        if return_fields:
+            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
+        else:
+            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
+            ptrs = [None, None, None, _dp(out.get("mse_center"))]
+            args = args[:5] + [None] + args[5:]
+        out.update(flux=np.zeros((N, fields.shape[3]), np.float64), flux_err=np.zeros((N, fields.shape[3]), np.float64),
+                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
+        check(lib.dv_infer_fields_measure(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
+                                          _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"])))
+        return out
+
+    def infer_cutouts_measure(self, field, starts, places=None, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure() for one field (F, F, bands): the field-sized results under singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure(fields, starts, fp, places=places, seed=seed, **kw))
+
+    def scene_measure(self, mean, stddev=None, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_measure on this engine's GPU context."""
+        return self.ctx.scene_measure(mean, stddev, **kw)
 
     def open_field_set(self, fields, cumulative=False) -> "FieldSet":
         """Upload M float64 fields (M, F, F, bands) once and keep them, their working and final residuals and the predicted

@@ -1,0 +1,67 @@
+"""Catalogue measurement of deblended galaxies: a flux and a shape per galaxy.
+
+The reference ships `debvader.measure` as an empty package: measurement was meant to live there and was never written, so
+there is no reference code behind this module.  The measurement itself is defined in DESIGN.md section 7j and runs on the
+GPU (csrc/measure.hip): per-band fluxes and their errors summed over the network's mean / stddev stamps, and the adaptive
+moments of one band - the centroid and second moments of the stamp under a Gaussian weight that is iterated until it matches
+the object.  Errors on the moments and a PSF correction are not part of it.
+"""
+import numpy as np
+
+from debvader_amd import engine as E
+
+STATUS_CONVERGED, STATUS_ITER_LIMIT, STATUS_FAILED = 0, 2, 3
+
+
+def catalogue_dtype(nb_of_bands):
+    """The columns of measure_stamps' recarray: what the GPU measures, then what the host derives from it."""
+    nb = int(nb_of_bands)
+    return [("flux", "<f8", (nb,)), ("flux_err", "<f8", (nb,)), ("row", "<f8"), ("col", "<f8"), ("Mrr", "<f8"),
+            ("Mrc", "<f8"), ("Mcc", "<f8"), ("iters", "<i4"), ("status", "<i4"), ("sigma", "<f8"), ("e1", "<f8"),
+            ("e2", "<f8")]
+
+
+def catalogue_records(flux, flux_err, shape, iters, status):
+    """The recarray of measure_stamps from the arrays the engine returns (flux_err None: NaN).  Derived on the host:
+    sigma = det(M)^(1/4), e1 = (Mcc - Mrr) / (Mcc + Mrr), e2 = 2 Mrc / (Mcc + Mrr); NaN where status is 3."""
+    flux = np.asarray(flux, dtype=np.float64)
+    n, nb = flux.shape
+    shape = np.asarray(shape, dtype=np.float64).reshape(n, 5)
+    rec = np.recarray((n,), dtype=catalogue_dtype(nb))
+    rec["flux"] = flux
+    rec["flux_err"] = np.nan if flux_err is None else np.asarray(flux_err, dtype=np.float64)
+    for k, name in enumerate(("row", "col", "Mrr", "Mrc", "Mcc")):
+        rec[name] = shape[:, k]
+    rec["iters"] = iters
+    rec["status"] = status
+    Mrr, Mrc, Mcc = shape[:, 2], shape[:, 3], shape[:, 4]
+    failed = np.asarray(status) == STATUS_FAILED
+    with np.errstate(all="ignore"):
+        det, tr = Mrr * Mcc - Mrc * Mrc, Mcc + Mrr
+        rec["sigma"] = np.where(failed, np.nan, np.sqrt(np.sqrt(det)))
+        rec["e1"] = np.where(failed, np.nan, (Mcc - Mrr) / tr)
+        rec["e2"] = np.where(failed, np.nan, 2.0 * Mrc / tr)
+    return rec
+
+
+def measure_stamps(mean, stddev=None, band=2, sigma0=3.0, tol=1e-10, max_iter=200, ctx=None):
+    """Measure N deblended galaxies on the GPU.
+
+    parameters:
+        mean: the network's mean stamps, (N, cutout_size, cutout_size, bands) - `output_images_mean` of a deblending pass
+        stddev: its stddev stamps of the same shape (`output_images_stddev`), or None: `flux_err` is then NaN
+        band: the band whose adaptive moments are taken (2, the r band)
+        sigma0: width in pixels of the first Gaussian weight
+        tol: the iteration stops when the centroid step (pixels) and the relative change of the moments are below it
+        max_iter: iteration limit; 0 returns the initial state with status 2
+        ctx: the engine context to run on (None: the default context)
+    returns a np.recarray with, per galaxy: flux, flux_err (one entry per band), row, col (the centroid, in pixels from
+    the stamp's pixel (0, 0)), Mrr, Mrc, Mcc (the adaptive second moments), iters, status (0 converged, 2 iteration limit,
+    3 failed: degenerate moments, no positive weighted flux, or a centroid that left the stamp) and, derived on the host,
+    sigma = det(M)^(1/4), e1 = (Mcc - Mrr) / (Mcc + Mrr), e2 = 2 Mrc / (Mcc + Mrr) - NaN where status is 3.
+    """
+    mean, stddev, _ = E.check_measure_args(mean, stddev, band, sigma0, tol, max_iter)
+    if ctx is None:
+        ctx = E.default_context()
+    out = ctx.scene_measure(mean, stddev, band=band, sigma0=sigma0, tol=tol, max_iter=max_iter)
+    return catalogue_records(out["flux"], out.get("flux_err"), out["shape"], out["iters"], out["status"])

@@ -401,6 +401,47 @@ int dv_scene_detect(dv_ctx* ctx, const double* fields, int32_t M, int32_t H, int
                     int32_t* npix, double* peak, double* flux, double* x, double* y, double* back, double* rms,
                     double* D, int32_t* labels);
 
+/* ---- catalogue measurement: fluxes and adaptive moments per galaxy ----
+ * The reference ships an empty debvader.measure package; the measurement is defined here, float64 throughout.  Per stamp,
+ * with P the network's mean stamp [cs][cs][nb] and S its stddev stamp (float32 widened to double; with normalise on, the
+ * denormalised values the composite stage adds), rows r and columns c from 0 to cs - 1:
+ *   flux[b] = sum P[r,c,b], flux_err[b] = sqrt(sum S[r,c,b]^2) for every band b;
+ *   adaptive moments of I = P[:,:,band]: from r0 = c0 = (cs-1)/2, Mrr = Mcc = sigma0^2, Mrc = 0, iteration k = 1 .. max_iter
+ *   weights every pixel of the stamp with w = exp(-(Mcc dr^2 - 2 Mrc dr dc + Mrr dc^2) / (2 det M)) I, dr = r - r0,
+ *   dc = c - c0, takes S0 = sum w, mr = sum w dr / S0, mc = sum w dc / S0 and N = 2 (sum w d d^T / S0 - m m^T), then sets
+ *   r0 += 2 mr, c0 += 2 mc, M = N.  status 0: 2 max(|mr|,|mc|) < tol and max|N - M| / (Nrr + Ncc) < tol at iteration
+ *   iters; 2: max_iter reached (max_iter = 0 returns the initial state); 3: det M not finite or <= 1e-6, S0 not finite or
+ *   <= 0 (both before the update of that iteration), or after it a centroid further than cs / 2 from the stamp centre or
+ *   a trace Nrr + Ncc that is negative or not finite.  shape[5] = {r0, c0, Mrr, Mrc, Mcc} in their last state whatever
+ *   the status.  A stamp's results have the same bits wherever it sits in a batch.
+ * dv_scene_measure: host stamps mean / stddev [N][cs][cs][nb] (float32), in chunks sized against free device memory; flux /
+ * flux_err [N][nb], shape [N][5], iters / status [N].  stddev and flux_err may be null together.
+ * dv_infer_fields_measure: dv_infer_fields_composite with the measurement as one more stage of the pipeline, behind every
+ * chunk's forward pass on the chunk's mean and stddev stamps in device memory; the per-stamp outputs are indexed by the
+ * global stamp number and have the bits dv_scene_measure gives on the stamps dv_infer_fields returns for the same seed.
+ * mean_fields, stddev_fields and residual_fields may be null TOGETHER: the catalogue-only call, in which nothing
+ * field-sized is allocated for results or downloaded and places may be null.  With mean_fields and stddev_fields given
+ * (residual_fields and mse_center optional) the fields and mse_center have the bits of dv_infer_fields_composite.
+ * Refused before any GPU work (DV_E_INVALID) beside what dv_infer_fields_composite refuses: band outside 0 .. nb - 1,
+ * sigma0 or tol not finite and positive, max_iter < 0, a missing catalogue output (flux, flux_err, shape, iters, status),
+ * mean_fields without stddev_fields or residual_fields without them, a stamp of more than 90 pixels (its float64 band plane
+ * does not fit the 64 KB of LDS of a workgroup). */
+typedef struct dv_measure_params {
+  int32_t band;            /* band of the adaptive moments (2, the r band) */
+  double sigma0;           /* initial width in pixels (3.0) */
+  double tol;              /* convergence tolerance on the step and on the relative change of M (1e-10) */
+  int32_t max_iter;        /* iteration limit (200) */
+} dv_measure_params;
+int dv_measure_params_default(dv_measure_params* params);
+int dv_scene_measure(dv_ctx* ctx, const float* mean, const float* stddev, int64_t N, int32_t cs, int32_t nb,
+                     const dv_measure_params* params, double* flux, double* flux_err, double* shape, int32_t* iters,
+                     int32_t* status);
+int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                            const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                            const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                            double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                            int32_t* iters, int32_t* status);
+
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)
  * keeps per field, in device memory, `work` (what the next pass detects on and cuts from, at first the field), `final`

@@ -1,0 +1,123 @@
+"""A catalogue of deblended galaxies - a flux and a shape per galaxy - for many small fields, on one GPU (DESIGN.md section
+7j).  M synthetic six-band fields of F px as tools/fields_bench.py makes them (the section 7f workload: 1024 fields of 259 px),
+detected once with detect_objects_batch, distances rounded to integers; then, alternating after a warm-up, --repeat times:
+
+    (a) catalogue :  deblend_fields(d, on_device=True, measure=True, return_fields=False)   nothing field-sized comes back
+    (b) both      :  deblend_fields(d, on_device=True, measure=True)                          catalogue and fields
+    (c) fields    :  deblend_fields(d, on_device=True)                                        what the call was before
+    (d) host      :  deblend_fields(d) on --host-fields fields (stamps to the host), then the numpy restatement of the
+                     measurement (tests/measure_oracle.py) on every returned stamp: the only route to a catalogue before
+                     the measurement existed.  Timed on the subset and EXTRAPOLATED to all fields by the ratio of stamps;
+                     its two parts are reported separately.
+
+Per leg: the median, the spread (max - min over the median) and every run.  GPU only; prints a table and one JSON line.
+
+    python tools/measure_bench.py [--fields 1024] [--size 259] [--repeat 5] [--max-batch 8192] [--host-fields 16]
+
+--profile-one: warm up, one fp32 catalogue-only call, exit (for a kernel trace).
+"""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+from contextlib import redirect_stdout
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from debvader_amd.deblend.field_deblender import DeblendFieldBatch  # noqa: E402
+from debvader_amd.detect.detection import detect_objects_batch  # noqa: E402
+from debvader_amd.model import model  # noqa: E402
+from tests import measure_oracle  # noqa: E402
+from tools.fields_bench import ARCH, _field, _row  # noqa: E402
+
+
+def _device(net, fields, dists, **kw):
+    return sum(len(r) for r in DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=True, **kw))
+
+
+def _host(net, fields, dists, parts):
+    t0 = time.perf_counter()
+    res = DeblendFieldBatch(net, fields).deblend_fields(dists)
+    t1 = time.perf_counter()
+    n = 0
+    for rec in res:
+        if len(rec):
+            mean, std = np.stack(list(rec["output_images_mean"])), np.stack(list(rec["output_images_stddev"]))
+            measure_oracle.measure(mean, std)
+            n += len(rec)
+    parts.append((t1 - t0, time.perf_counter() - t1))
+    return n
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--fields", type=int, default=1024)
+    ap.add_argument("--size", type=int, default=259)
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--max-batch", type=int, default=8192)
+    ap.add_argument("--host-fields", type=int, default=16)
+    ap.add_argument("--dtypes", default="float32,bf16")
+    ap.add_argument("--profile-one", action="store_true")
+    a = ap.parse_args()
+    rng = np.random.default_rng(0)
+    F, M = a.size, a.fields
+    base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
+    fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    quiet = io.StringIO()                      # the classes print the reference's notes about dropped galaxies
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "host_fields": min(M, a.host_fields)}
+    dists = None
+    Mh = min(M, a.host_fields)
+    for dtype in a.dtypes.split(","):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections; max_batch {a.max_batch}")
+        legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False),
+                "both": lambda: _device(net, fields, dists, measure=True),
+                "fields": lambda: _device(net, fields, dists)}
+        parts = []
+        with redirect_stdout(quiet):
+            for fn in legs.values():           # warm-up
+                fn()
+            if a.profile_one:
+                legs["catalogue"]()
+                net._core.engine.close()
+                return
+            _host(net, fields[:2], dists[:2], [])
+            times = {k: [] for k in legs}
+            host_t, n, nh = [], 0, 0
+            for _ in range(a.repeat):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    n = fn()
+                    times[k].append(time.perf_counter() - t0)
+                t0 = time.perf_counter()
+                nh = _host(net, fields[:Mh], dists[:Mh], parts)
+                host_t.append(time.perf_counter() - t0)
+        result[dtype] = {"stamps": n, "host_stamps": nh}
+        for k in legs:
+            t = np.array(times[k])
+            print(_row(f"{dtype} {k}", t, n, M))
+            result[dtype][k + "_ms"] = [round(1e3 * x, 2) for x in t]
+        th = np.array(host_t)
+        print(_row(f"{dtype} host route ({Mh} fields)", th, nh, Mh))
+        scale = n / max(nh, 1)
+        pd, pm = np.median([p[0] for p in parts]), np.median([p[1] for p in parts])
+        print(f"{dtype} host route EXTRAPOLATED to {M} fields ({n} stamps, x {scale:.1f}): {1e3 * np.median(th) * scale:.0f} ms "
+              f"(deblend_fields {1e3 * pd * scale:.0f} ms + numpy measurement {1e3 * pm * scale:.0f} ms)")
+        tc, tb, tf = (float(np.median(times[k])) for k in ("catalogue", "both", "fields"))
+        print(f"{dtype} catalogue / fields {tc / tf:.3f}, both / fields {tb / tf:.3f}, extrapolated host route / catalogue "
+              f"{np.median(th) * scale / tc:.1f}")
+        result[dtype].update(host_ms=[round(1e3 * x, 2) for x in th], host_extrapolated_ms=round(1e3 * float(np.median(th)) * scale, 1),
+                             host_deblend_ms=round(1e3 * float(pd), 2), host_numpy_ms=round(1e3 * float(pm), 2))
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
