@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <memory>
+#include <utility>
 
 namespace dv {
 
@@ -31,6 +33,57 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
     int s__ = (call);           \
     if (s__ != dv::OK) return s__; \
   } while (0)
+
+// ---- owning buffers of the host code --------------------------------------------------------------------------------
+// DevBuf<T>: elements of device memory that the destructor frees; PinBuf<T>: the same of pinned host memory.  Move-only, no
+// pool, no sharing.  alloc() gets at least one element and reports a failure through hip_fail with the caller's file and
+// line; ensure() only ever grows (the old content is dropped).
+template <typename T, bool Pinned = false>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }   // (o frees the old one)
+  ~DevBuf() { reset(); }
+  int alloc(size_t count, const char* what = Pinned ? "hipHostMalloc" : "hipMalloc", const char* file = __builtin_FILE(),
+            int line = __builtin_LINE()) {
+    reset();
+    cap_ = count ? count : 1;
+    const hipError_t e = Pinned ? hipHostMalloc((void**)&p_, cap_ * sizeof(T), hipHostMallocDefault)
+                                : hipMalloc((void**)&p_, cap_ * sizeof(T));
+    if (e == hipSuccess) return OK;
+    p_ = nullptr; cap_ = 0;
+    return hip_fail(e, what, file, line);
+  }
+  int ensure(size_t count, const char* file = __builtin_FILE(), int line = __builtin_LINE()) {
+    return count <= cap_ ? OK : alloc(count, Pinned ? "hipHostMalloc" : "hipMalloc", file, line);
+  }
+  void reset() {
+    if (p_) Pinned ? (void)hipHostFree(p_) : (void)hipFree(p_);
+    p_ = nullptr; cap_ = 0;
+  }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+ private:
+  T* p_ = nullptr;
+  size_t cap_ = 0;     // elements
+};
+template <typename T>
+using PinBuf = DevBuf<T, true>;
+
+// A failed call must not free buffers that queued work may still read: declared AFTER the buffers it protects (so that it
+// runs first), it waits for the given streams when the scope is left - unless the call succeeded and dismissed it.
+struct StreamDrain {
+  hipStream_t streams[3];
+  bool armed = true;
+  explicit StreamDrain(hipStream_t a, hipStream_t b = nullptr, hipStream_t c = nullptr) : streams{a, b, c} {}
+  StreamDrain(const StreamDrain&) = delete;
+  ~StreamDrain() {
+    for (hipStream_t q : streams)
+      if (armed && q) (void)hipStreamSynchronize(q);
+  }
+  void dismiss() { armed = false; }
+};
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -214,6 +267,8 @@ struct PosfitPlan;
 int posfit_plan_create(int F, int cs, int N, const double* dist_h, const double* shifts_h, double bound, int max_iter,
                        PosfitPlan** out);
 void posfit_plan_destroy(PosfitPlan* p);
+struct PosfitPlanFree { void operator()(PosfitPlan* p) const { posfit_plan_destroy(p); } };
+using PosfitPlanOwner = std::unique_ptr<PosfitPlan, PosfitPlanFree>;   // a created plan (and its device copy) goes with its scope
 int posfit_plan_layout(PosfitPlan* p, int a, int b, int max_n, const int32_t* sfield, int f0, int stamp0);
 void posfit_plan_rebase(PosfitPlan* p, int a, int b, int f0);   // fields of [a, b) relative to f0 (laid out with f0 = 0)
 int posfit_plan_launch_count(const PosfitPlan* p);

@@ -753,6 +753,43 @@ __global__ __launch_bounds__(DT) void band_gather_kernel(const double* __restric
   data[(long)blockIdx.y * HW + e] = fields[(f * HW + e) * nb + band];
 }
 
+// the device buffers of detect_impl.  DetectWork: the workspace of one launch's fields (chunk fields of H x W pixels on
+// ny x nx background meshes); back / rms / labout exist only when the caller wants those maps, wdev (the nwhich field numbers
+// of a device source) only when the fields come from device memory.
+struct DetectWork {
+  DevBuf<double> data, v, D, mb, mr, fbk, frm, d2b, d2r, gb, gb2, gr, gr2, grms, kdev, cdev, back, rms;
+  DevBuf<int> par, lab, area, cmin, cmax, rmax, lidx, table, ncomp, labout, wdev;
+  int alloc(int chunk, int H, int W, int ny, int nx, long ccap, size_t ktaps, size_t ccoef, bool want_back, bool want_rms,
+            bool want_labels, int nwhich) {
+    const size_t px = (size_t)chunk * H * W, grid = (size_t)chunk * ny * nx, rows = (size_t)chunk * H * nx;
+    for (DevBuf<double>* b : {&data, &v, &D}) DV_TRY(b->alloc(px));
+    for (DevBuf<int>* b : {&par, &lab, &area, &cmin, &cmax, &rmax, &lidx}) DV_TRY(b->alloc(px));
+    for (DevBuf<double>* b : {&mb, &mr, &fbk, &frm, &d2b, &d2r}) DV_TRY(b->alloc(grid));
+    for (DevBuf<double>* b : {&gb, &gb2, &gr, &gr2}) DV_TRY(b->alloc(rows));
+    DV_TRY(grms.alloc((size_t)chunk)); DV_TRY(ncomp.alloc((size_t)chunk)); DV_TRY(table.alloc((size_t)chunk * ccap * 5));
+    DV_TRY(kdev.alloc(ktaps)); DV_TRY(cdev.alloc(ccoef));
+    if (want_back) DV_TRY(back.alloc(px));
+    if (want_rms) DV_TRY(rms.alloc(px));
+    if (want_labels) DV_TRY(labout.alloc(px));
+    if (nwhich > 0) DV_TRY(wdev.alloc((size_t)nwhich));
+    return OK;
+  }
+};
+// DeblendScratch: the jobs of one launch's components, their scratch and their catalogue slots, sized once the components
+// are known and freed before the next launch sizes its own
+struct DeblendScratch {
+  DevBuf<DbJob> djobs;
+  DevBuf<double> dscr, o_peak, o_flux, o_x, o_y;
+  DevBuf<int> iscr, nobj, o_npix, o_pp;
+  int alloc(long nj, long dws, long iws, long slots) {
+    DV_TRY(djobs.alloc((size_t)nj)); DV_TRY(nobj.alloc((size_t)nj));
+    DV_TRY(dscr.alloc((size_t)dws)); DV_TRY(iscr.alloc((size_t)iws));
+    for (DevBuf<int>* b : {&o_npix, &o_pp}) DV_TRY(b->alloc((size_t)slots));
+    for (DevBuf<double>* b : {&o_peak, &o_flux, &o_x, &o_y}) DV_TRY(b->alloc((size_t)slots));
+    return OK;
+  }
+};
+
 // the detector: the fields come from the host (fields_h) or, with `dev`, from a stack that lies in device memory
 int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, int W, double thresh, double cont, int minarea,
                 int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
@@ -817,51 +854,13 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
   std::vector<double> c_peak, c_flux, c_x, c_y;
   offsets_h[0] = 0;
 
-  double *data = nullptr, *v = nullptr, *D = nullptr, *mb = nullptr, *mr = nullptr, *fbk = nullptr, *frm = nullptr;
-  double *d2b = nullptr, *d2r = nullptr, *gb = nullptr, *gb2 = nullptr, *gr = nullptr, *gr2 = nullptr, *grms = nullptr;
-  double *kdev = nullptr, *cdev = nullptr, *back = nullptr, *rms = nullptr, *dscr = nullptr;
-  int *par = nullptr, *lab = nullptr, *area = nullptr, *cmin = nullptr, *cmax = nullptr, *rmax = nullptr, *lidx = nullptr;
-  int *table = nullptr, *ncomp = nullptr, *labout = nullptr, *iscr = nullptr, *o_npix = nullptr, *o_pp = nullptr;
-  int *nobj = nullptr, *wdev = nullptr;
-  double *o_peak = nullptr, *o_flux = nullptr, *o_x = nullptr, *o_y = nullptr;
-  DbJob* djobs = nullptr;
-  int st = OK;
-  auto free_deblend = [&]() {
-    for (void* p : {(void*)dscr, (void*)iscr, (void*)o_npix, (void*)o_pp, (void*)nobj, (void*)o_peak, (void*)o_flux,
-                    (void*)o_x, (void*)o_y, (void*)djobs})
-      (void)hipFree(p);
-    dscr = nullptr; iscr = nullptr; o_npix = nullptr; o_pp = nullptr; nobj = nullptr; o_peak = nullptr;
-    o_flux = nullptr; o_x = nullptr; o_y = nullptr; djobs = nullptr;
-  };
-  auto cleanup = [&]() {
-    for (void* p : {(void*)data, (void*)v, (void*)D, (void*)mb, (void*)mr, (void*)fbk, (void*)frm, (void*)d2b,
-                    (void*)d2r, (void*)gb, (void*)gb2, (void*)gr, (void*)gr2, (void*)grms, (void*)kdev, (void*)cdev,
-                    (void*)back, (void*)rms, (void*)par, (void*)lab, (void*)area, (void*)cmin, (void*)cmax,
-                    (void*)rmax, (void*)lidx, (void*)table, (void*)ncomp, (void*)labout, (void*)wdev})
-      (void)hipFree(p);
-    free_deblend();
-  };
-#define DT_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
-#define DT_ALLOC(ptr, count) DT_HIP(hipMalloc((void**)&(ptr), std::max<size_t>(1, (size_t)(count)) * sizeof(*(ptr))))
+  DetectWork w;
   if (chunk > 0) {
-    const long px = (long)chunk * HW, grid = (long)chunk * ny * nx, rows = (long)chunk * H * nx;
-    DT_ALLOC(data, px); DT_ALLOC(v, px); DT_ALLOC(D, px);
-    DT_ALLOC(par, px); DT_ALLOC(lab, px); DT_ALLOC(area, px); DT_ALLOC(cmin, px); DT_ALLOC(cmax, px);
-    DT_ALLOC(rmax, px); DT_ALLOC(lidx, px);
-    DT_ALLOC(mb, grid); DT_ALLOC(mr, grid); DT_ALLOC(fbk, grid); DT_ALLOC(frm, grid); DT_ALLOC(d2b, grid);
-    DT_ALLOC(d2r, grid);
-    DT_ALLOC(gb, rows); DT_ALLOC(gb2, rows); DT_ALLOC(gr, rows); DT_ALLOC(gr2, rows);
-    DT_ALLOC(grms, chunk); DT_ALLOC(kdev, kn.size()); DT_ALLOC(cdev, cco.size());
-    DT_ALLOC(table, (long)chunk * ccap * 5); DT_ALLOC(ncomp, chunk);
-    if (back_h) DT_ALLOC(back, px);
-    if (rms_h) DT_ALLOC(rms, px);
-    if (labels_h) DT_ALLOC(labout, px);
-    DT_HIP(hipMemcpyAsync(kdev, kn.data(), kn.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    DT_HIP(hipMemcpyAsync(cdev, cco.data(), cco.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    if (dev) {
-      DT_ALLOC(wdev, M);
-      DT_HIP(hipMemcpyAsync(wdev, dev->which_h, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
-    }
+    DV_TRY(w.alloc(chunk, H, W, ny, nx, ccap, kn.size(), cco.size(), back_h != nullptr, rms_h != nullptr,
+                   labels_h != nullptr, dev ? M : 0));
+    DV_HIP(hipMemcpyAsync(w.kdev, kn.data(), kn.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(w.cdev, cco.data(), cco.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    if (dev) DV_HIP(hipMemcpyAsync(w.wdev, dev->which_h, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
   }
   std::vector<int> h_ncomp((size_t)std::max(chunk, 1));
   std::vector<int> h_tab;
@@ -870,48 +869,49 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
     const long px = (long)m * HW;
     if (dev) {
       hipLaunchKernelGGL(band_gather_kernel, dim3(nblk(HW), (unsigned)m), dim3(DT), 0, s, dev->fields_dev, HW, dev->nb,
-                         dev->band, wdev + f0, data);
-      DT_HIP(hipGetLastError());
+                         dev->band, w.wdev + f0, w.data);
+      DV_HIP(hipGetLastError());
     } else {
-      DT_HIP(hipMemcpyAsync(data, fields_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
+      DV_HIP(hipMemcpyAsync(w.data, fields_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    hipLaunchKernelGGL(bkg_mesh_kernel, dim3((unsigned)((long)m * ny * nx)), dim3(DT), 0, s, data, H, W, back_size, ny,
-                       nx, mb, mr);
-    DT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bkg_grid_kernel, dim3((unsigned)m), dim3(DT), 0, s, mb, mr, ny, nx, back_filter, cdev, fbk, frm,
-                       d2b, d2r, grms);
-    DT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bkg_row_kernel, dim3(nblk((long)m * H)), dim3(DT), 0, s, fbk, frm, d2b, d2r, m, H, ny, nx,
-                       back_size, rms ? 1 : 0, cdev, gb, gb2, gr, gr2);
-    DT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bkg_pixel_kernel, dim3(nblk(px)), dim3(DT), 0, s, data, px, W, nx, back_size, gb, gb2, gr, gr2, v,
-                       back, rms);
-    DT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkg_mesh_kernel, dim3((unsigned)((long)m * ny * nx)), dim3(DT), 0, s, w.data, H, W, back_size, ny,
+                       nx, w.mb, w.mr);
+    DV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkg_grid_kernel, dim3((unsigned)m), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev, w.fbk,
+                       w.frm, w.d2b, w.d2r, w.grms);
+    DV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkg_row_kernel, dim3(nblk((long)m * H)), dim3(DT), 0, s, w.fbk, w.frm, w.d2b, w.d2r, m, H, ny, nx,
+                       back_size, w.rms ? 1 : 0, w.cdev, w.gb, w.gb2, w.gr, w.gr2);
+    DV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkg_pixel_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.data, px, W, nx, back_size, w.gb, w.gb2, w.gr,
+                       w.gr2, w.v, w.back, w.rms);
+    DV_HIP(hipGetLastError());
     hipLaunchKernelGGL(filter_kernel, dim3((unsigned)((W + FT - 1) / FT), (unsigned)((H + FT - 1) / FT), (unsigned)m),
-                       dim3(DT), 0, s, v, H, W, kdev, kh, kw, grms, thresh, D, par);
-    DT_HIP(hipGetLastError());
-    DT_HIP(hipMemsetAsync(area, 0, (size_t)px * sizeof(int), s));
-    DT_HIP(hipMemsetAsync(cmin, 0x7f, (size_t)px * sizeof(int), s));
-    DT_HIP(hipMemsetAsync(cmax, 0xff, (size_t)px * sizeof(int), s));
-    DT_HIP(hipMemsetAsync(rmax, 0xff, (size_t)px * sizeof(int), s));
-    hipLaunchKernelGGL(cc_merge_kernel, dim3(nblk(px)), dim3(DT), 0, s, par, px, W, HW);
-    DT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cc_flatten_kernel, dim3(nblk(px)), dim3(DT), 0, s, par, px, W, HW, lab, area, cmin, cmax, rmax);
-    DT_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cc_compact_kernel, dim3((unsigned)m), dim3(DT), 0, s, lab, area, cmin, cmax, rmax, HW, minarea,
-                       ccap, table, ncomp);
-    DT_HIP(hipGetLastError());
-    if (labout) {
-      hipLaunchKernelGGL(cc_labels_kernel, dim3(nblk(px)), dim3(DT), 0, s, lab, area, px, HW, minarea, labout);
-      DT_HIP(hipGetLastError());
+                       dim3(DT), 0, s, w.v, H, W, w.kdev, kh, kw, w.grms, thresh, w.D, w.par);
+    DV_HIP(hipGetLastError());
+    DV_HIP(hipMemsetAsync(w.area, 0, (size_t)px * sizeof(int), s));
+    DV_HIP(hipMemsetAsync(w.cmin, 0x7f, (size_t)px * sizeof(int), s));
+    DV_HIP(hipMemsetAsync(w.cmax, 0xff, (size_t)px * sizeof(int), s));
+    DV_HIP(hipMemsetAsync(w.rmax, 0xff, (size_t)px * sizeof(int), s));
+    hipLaunchKernelGGL(cc_merge_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.par, px, W, HW);
+    DV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.par, px, W, HW, w.lab, w.area, w.cmin,
+                       w.cmax, w.rmax);
+    DV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cc_compact_kernel, dim3((unsigned)m), dim3(DT), 0, s, w.lab, w.area, w.cmin, w.cmax, w.rmax, HW,
+                       minarea, ccap, w.table, w.ncomp);
+    DV_HIP(hipGetLastError());
+    if (w.labout) {
+      hipLaunchKernelGGL(cc_labels_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.lab, w.area, px, HW, minarea, w.labout);
+      DV_HIP(hipGetLastError());
     }
-    DT_HIP(hipMemcpyAsync(globalrms_h + f0, grms, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-    DT_HIP(hipMemcpyAsync(h_ncomp.data(), ncomp, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (back_h) DT_HIP(hipMemcpyAsync(back_h + (size_t)f0 * HW, back, (size_t)px * 8, hipMemcpyDeviceToHost, s));
-    if (rms_h) DT_HIP(hipMemcpyAsync(rms_h + (size_t)f0 * HW, rms, (size_t)px * 8, hipMemcpyDeviceToHost, s));
-    if (D_h) DT_HIP(hipMemcpyAsync(D_h + (size_t)f0 * HW, D, (size_t)px * 8, hipMemcpyDeviceToHost, s));
-    if (labels_h) DT_HIP(hipMemcpyAsync(labels_h + (size_t)f0 * HW, labout, (size_t)px * 4, hipMemcpyDeviceToHost, s));
-    DT_HIP(hipStreamSynchronize(s));
+    DV_HIP(hipMemcpyAsync(globalrms_h + f0, w.grms, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(h_ncomp.data(), w.ncomp, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (back_h) DV_HIP(hipMemcpyAsync(back_h + (size_t)f0 * HW, w.back, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+    if (rms_h) DV_HIP(hipMemcpyAsync(rms_h + (size_t)f0 * HW, w.rms, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+    if (D_h) DV_HIP(hipMemcpyAsync(D_h + (size_t)f0 * HW, w.D, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+    if (labels_h) DV_HIP(hipMemcpyAsync(labels_h + (size_t)f0 * HW, w.labout, (size_t)px * 4, hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));
     // phase two: every component's scratch and catalog slots
     std::vector<DbJob> jobs;
     std::vector<int> jfield;
@@ -921,9 +921,9 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
     h_tab.resize((size_t)std::max(tab_off[m], 1L) * 5);
     for (int f = 0; f < m; ++f)
       if (h_ncomp[f] > 0)
-        DT_HIP(hipMemcpyAsync(h_tab.data() + tab_off[f] * 5, table + (long)f * ccap * 5, (size_t)h_ncomp[f] * 5 * sizeof(int),
-                              hipMemcpyDeviceToHost, s));
-    DT_HIP(hipStreamSynchronize(s));
+        DV_HIP(hipMemcpyAsync(h_tab.data() + tab_off[f] * 5, w.table + (long)f * ccap * 5,
+                              (size_t)h_ncomp[f] * 5 * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));
     for (int f = 0; f < m; ++f) {
       const int nc = h_ncomp[f];
       for (int c = 0; c < nc; ++c) {
@@ -951,21 +951,19 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
     std::vector<int> h_nobj((size_t)nj), h_npix((size_t)slots);
     std::vector<double> h_peak((size_t)slots), h_flux((size_t)slots), h_x((size_t)slots), h_y((size_t)slots);
     if (nj > 0) {
-      DT_ALLOC(djobs, nj); DT_ALLOC(dscr, dws); DT_ALLOC(iscr, iws); DT_ALLOC(nobj, nj);
-      DT_ALLOC(o_npix, slots); DT_ALLOC(o_pp, slots); DT_ALLOC(o_peak, slots); DT_ALLOC(o_flux, slots);
-      DT_ALLOC(o_x, slots); DT_ALLOC(o_y, slots);
-      DT_HIP(hipMemcpyAsync(djobs, jobs.data(), (size_t)nj * sizeof(DbJob), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(deblend_kernel, dim3((unsigned)nj), dim3(DT), 0, s, djobs, W, D, v, lab, lidx, dscr, iscr,
-                         nthresh, minarea, cont, o_npix, o_pp, o_peak, o_flux, o_x, o_y, nobj);
-      DT_HIP(hipGetLastError());
-      DT_HIP(hipMemcpyAsync(h_nobj.data(), nobj, (size_t)nj * 4, hipMemcpyDeviceToHost, s));
-      DT_HIP(hipMemcpyAsync(h_npix.data(), o_npix, (size_t)slots * 4, hipMemcpyDeviceToHost, s));
-      DT_HIP(hipMemcpyAsync(h_peak.data(), o_peak, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
-      DT_HIP(hipMemcpyAsync(h_flux.data(), o_flux, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
-      DT_HIP(hipMemcpyAsync(h_x.data(), o_x, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
-      DT_HIP(hipMemcpyAsync(h_y.data(), o_y, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
-      DT_HIP(hipStreamSynchronize(s));
-      free_deblend();
+      DeblendScratch d;
+      DV_TRY(d.alloc(nj, dws, iws, slots));
+      DV_HIP(hipMemcpyAsync(d.djobs, jobs.data(), (size_t)nj * sizeof(DbJob), hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(deblend_kernel, dim3((unsigned)nj), dim3(DT), 0, s, d.djobs, W, w.D, w.v, w.lab, w.lidx, d.dscr,
+                         d.iscr, nthresh, minarea, cont, d.o_npix, d.o_pp, d.o_peak, d.o_flux, d.o_x, d.o_y, d.nobj);
+      DV_HIP(hipGetLastError());
+      DV_HIP(hipMemcpyAsync(h_nobj.data(), d.nobj, (size_t)nj * 4, hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(h_npix.data(), d.o_npix, (size_t)slots * 4, hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(h_peak.data(), d.o_peak, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(h_flux.data(), d.o_flux, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(h_x.data(), d.o_x, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(h_y.data(), d.o_y, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DV_HIP(hipStreamSynchronize(s));
     }
     long ji = 0;
     for (int f = 0; f < m; ++f) {
@@ -985,9 +983,6 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
       offsets_h[f0 + f + 1] = (int64_t)c_field.size();
     }
   }
-  cleanup();
-#undef DT_ALLOC
-#undef DT_HIP
   const size_t n = c_field.size();
   *n_out = (int64_t)n;
   if ((int64_t)n <= cap && n > 0) {

@@ -20,6 +20,7 @@
 #include <string>
 #include <thread>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <vector>
@@ -370,6 +371,32 @@ static int ilog2_exact(int v) {
 // --------------------------------------------------------------------------------------------
 namespace dv {
 struct InferPipe;
+
+// The per-stamp tables of a field-sourced job in device memory: the windows' corners, the integer placements (compositing
+// calls), the field of every stamp, the first stamp of every field, and the centre MSE the job writes.  One call's locals in
+// infer_fields_impl, a resident field set's growable member.
+struct StampTables {
+  DevBuf<int> starts, places, sfield, fptr;
+  DevBuf<double> mse;
+  // what a call sets aside for them, whichever of them it fills
+  static size_t bytes(size_t N, size_t M) { return N * (5 * sizeof(int) + sizeof(double)) + (M + 1) * sizeof(int); }
+  // grows the tables to N stamps (at least min_stamps) of M fields and queues their upload on s; places_h null / want_mse
+  // false: the job has no use for that table, it stays as it is
+  int upload(int64_t N, int M, const int32_t* starts_h, const int32_t* places_h, const int32_t* sfield_h, const int* fptr_h,
+             bool want_mse, size_t min_stamps, hipStream_t s) {
+    const size_t n = std::max((size_t)N, min_stamps), sb = (size_t)N * 2 * sizeof(int);
+    DV_TRY(starts.ensure(2 * n));
+    if (places_h) DV_TRY(places.ensure(2 * n));
+    DV_TRY(sfield.ensure(n));
+    DV_TRY(fptr.ensure((size_t)M + 1));
+    if (want_mse) DV_TRY(mse.ensure(n));
+    DV_HIP(hipMemcpyAsync(starts, starts_h, sb, hipMemcpyHostToDevice, s));
+    if (places_h) DV_HIP(hipMemcpyAsync(places, places_h, sb, hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(sfield, sfield_h, (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(fptr, fptr_h, ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    return OK;
+  }
+};
 }
 
 struct dv_ctx {
@@ -446,8 +473,8 @@ struct DataSlot {
 struct StreamRing {
   static constexpr int kDepth = 4;
   static constexpr int kRel = 4;          // main, aux, comm, reduction stream
-  float* dev[kDepth] = {};
-  float* host[kDepth] = {};
+  dv::DevBuf<float> dev[kDepth];
+  dv::PinBuf<float> host[kDepth];
   size_t yoff = 0;                        // floats from an entry's x rows to its y rows (256-byte aligned)
   hipStream_t copy = nullptr;
   hipEvent_t h2d[kDepth] = {};
@@ -456,6 +483,14 @@ struct StreamRing {
   unsigned next = 0;
   int threads = 1;
   std::vector<int32_t> iota;              // [0, Bc): index vector of a gathered batch
+  ~StreamRing() {                         // (the buffers free themselves)
+    for (int r = 0; r < kDepth; ++r) {
+      if (h2d[r]) (void)hipEventDestroy(h2d[r]);
+      for (auto e : rel[r])
+        if (e) (void)hipEventDestroy(e);
+    }
+    if (copy) (void)hipStreamDestroy(copy);
+  }
 };
 
 // bf16 kernel family (BASELINE configs[2], bf16.h): stamp-inner bf16 activations of the conv stacks, bf16 weight
@@ -541,23 +576,16 @@ struct dv_field_set {
   // [M][F][F][nb] each.  reference mode: base, work, next, fin, mean, stddev; cumulative mode: `fin` is `work` and `base` is
   // not kept (every pass starts from the working residual).  `next` receives a pass's new working residual while the
   // pass's later chunks still gather from `work`.
-  double *base = nullptr, *work = nullptr, *next = nullptr, *fin = nullptr, *mean = nullptr, *stddev = nullptr;
-  double *mse_part = nullptr, *fmse = nullptr;   // partial sums and results of the field_mse reduction
-  // per-stamp tables of a pass (windows, placements, field numbers, centre MSE), kept between passes and grown on demand
-  // to tab_cap stamps; fptr: the M + 1 first stamps of the fields
-  int *starts_d = nullptr, *places_d = nullptr, *sfield_d = nullptr, *fptr_d = nullptr;
-  double* mse_d = nullptr;
-  size_t tab_cap = 0;
+  dv::DevBuf<double> base, work, next, fin, mean, stddev;
+  dv::DevBuf<double> mse_part, fmse;             // partial sums and results of the field_mse reduction
+  dv::StampTables tab;                           // the per-stamp tables of a pass, kept between passes and grown on demand
   std::vector<double> fmse_h;                     // host side of fmse
 };
 
 static void field_set_release(dv_field_set* fs) {
-  for (double* p : {fs->base, fs->work, fs->next, fs->fin, fs->mean, fs->stddev, fs->mse_part, fs->fmse, fs->mse_d})
-    (void)hipFree(p);
-  for (int* p : {fs->starts_d, fs->places_d, fs->sfield_d, fs->fptr_d}) (void)hipFree(p);
-  fs->base = fs->work = fs->next = fs->fin = fs->mean = fs->stddev = fs->mse_part = fs->fmse = fs->mse_d = nullptr;
-  fs->starts_d = fs->places_d = fs->sfield_d = fs->fptr_d = nullptr;
-  fs->tab_cap = 0;
+  for (dv::DevBuf<double>* b : {&fs->base, &fs->work, &fs->next, &fs->fin, &fs->mean, &fs->stddev, &fs->mse_part, &fs->fmse})
+    b->reset();
+  fs->tab = dv::StampTables();
   fs->open = false;
 }
 
@@ -2670,17 +2698,7 @@ static int ring_sync_streams(dv_model* m) {
 }
 
 static void ring_free(dv_model* m) {
-  StreamRing* R = m->ring;
-  if (!R) return;
-  for (int r = 0; r < StreamRing::kDepth; ++r) {
-    if (R->dev[r]) (void)hipFree(R->dev[r]);
-    if (R->host[r]) (void)hipHostFree(R->host[r]);
-    if (R->h2d[r]) (void)hipEventDestroy(R->h2d[r]);
-    for (auto e : R->rel[r])
-      if (e) (void)hipEventDestroy(e);
-  }
-  if (R->copy) (void)hipStreamDestroy(R->copy);
-  delete R;
+  delete m->ring;
   m->ring = nullptr;
 }
 
@@ -2688,25 +2706,22 @@ static void ring_free(dv_model* m) {
 static int ring_get(dv_model* m) {
   if (m->ring) return OK;
   const Arch& A = m->A;
-  StreamRing* R = new StreamRing();
-  m->ring = R;
+  std::unique_ptr<StreamRing> R(new StreamRing());
   const size_t E = (size_t)A.H * A.H * A.C;
   R->yoff = ((size_t)m->Bc * E + 63) & ~(size_t)63;
-  const size_t bytes = (R->yoff + (size_t)m->Bc * E) * sizeof(float);
-  int st = OK;
-#define RING_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); ring_free(m); return st; } } while (0)
+  const size_t floats = R->yoff + (size_t)m->Bc * E;
   // its own stream: on the comm stream a copy would queue behind the previous step's bucket all-reduces and early Adam
-  RING_HIP(hipStreamCreateWithFlags(&R->copy, hipStreamNonBlocking));
+  DV_HIP(hipStreamCreateWithFlags(&R->copy, hipStreamNonBlocking));
   for (int r = 0; r < StreamRing::kDepth; ++r) {
-    RING_HIP(hipMalloc((void**)&R->dev[r], bytes));
-    RING_HIP(hipHostMalloc((void**)&R->host[r], bytes, hipHostMallocDefault));
-    RING_HIP(hipEventCreateWithFlags(&R->h2d[r], hipEventDisableTiming));    // copy -> kernels: system-scope release
-    for (auto& e : R->rel[r]) RING_HIP(hipEventCreateWithFlags(&e, sync_event_flags()));   // ordering only
+    DV_TRY(R->dev[r].alloc(floats));
+    DV_TRY(R->host[r].alloc(floats));
+    DV_HIP(hipEventCreateWithFlags(&R->h2d[r], hipEventDisableTiming));    // copy -> kernels: system-scope release
+    for (auto& e : R->rel[r]) DV_HIP(hipEventCreateWithFlags(&e, sync_event_flags()));   // ordering only
   }
-#undef RING_HIP
   R->iota.resize(m->Bc);
   for (int i = 0; i < m->Bc; ++i) R->iota[i] = i;
   R->threads = copy_threads();
+  m->ring = R.release();
   return OK;
 }
 
@@ -2840,48 +2855,34 @@ static int stage_host_batch(dv_model* m, const float* x, int nb) {
 // ---------------------------------------------------------------------------------------------------------------
 struct InferPipe {
   int cap = 0;                      // stamps per buffer
-  float *hin[2] = {}, *hloc[3] = {}, *hscale[3] = {}, *hsmall[3] = {};      // pinned host (outputs: three deep)
-  float* heps[3] = {};              // pinned host, third image slot of the ring: Monte-Carlo std stamps (dv_infer_fields_mc_keep only)
-  float *din[2] = {}, *dloc[2] = {}, *dscale[2] = {}, *dsmall[2] = {};      // device
+  PinBuf<float> hin[2], hloc[3], hscale[3], hsmall[3];                      // pinned host (outputs: three deep)
+  PinBuf<float> heps[3];            // pinned host, third image slot of the ring: Monte-Carlo std stamps (dv_infer_fields_mc_keep only)
+  DevBuf<float> din[2], dloc[2], dscale[2], dsmall[2];                      // device
   hipStream_t s_in = nullptr, s_out = nullptr;
   hipEvent_t ev_h2d[2] = {}, ev_comp[2] = {}, ev_d2h[3] = {};
   int threads = 4;
   bool host_ok = false;             // the pinned image buffers exist (calls that keep their results on the device skip them)
+  ~InferPipe() {                    // (the buffers free themselves)
+    for (hipEvent_t e : {ev_d2h[0], ev_d2h[1], ev_d2h[2], ev_h2d[0], ev_h2d[1], ev_comp[0], ev_comp[1]})
+      if (e) (void)hipEventDestroy(e);
+  }
 };
 
-static void pipe_free(InferPipe* p) {
-  if (!p) return;
-  for (int b = 0; b < 3; ++b) {
-    (void)hipHostFree(p->hloc[b]); (void)hipHostFree(p->hscale[b]); (void)hipHostFree(p->hsmall[b]);
-    (void)hipHostFree(p->heps[b]);
-    if (p->ev_d2h[b]) (void)hipEventDestroy(p->ev_d2h[b]);
-  }
-  for (int b = 0; b < 2; ++b) {
-    (void)hipHostFree(p->hin[b]);
-    (void)hipFree(p->din[b]); (void)hipFree(p->dloc[b]); (void)hipFree(p->dscale[b]); (void)hipFree(p->dsmall[b]);
-    if (p->ev_h2d[b]) (void)hipEventDestroy(p->ev_h2d[b]);
-    if (p->ev_comp[b]) (void)hipEventDestroy(p->ev_comp[b]);
-  }
-  delete p;
-}
+static void pipe_free(InferPipe* p) { delete p; }
 
 static int pipe_host_buffers(dv_model* m, InferPipe* p) {
   if (p->host_ok) return OK;
   const Arch& A = m->A;
-  const size_t img = (size_t)p->cap * A.H * A.H * A.C * sizeof(float);
-  // a failed allocation frees what this call got so far and leaves the slots null, so that a retry on a reused pipe neither
-  // leaks pinned memory (several GB at 8192 stamps per chunk) nor overwrites live pointers
-  float** slots[8] = {&p->hloc[0], &p->hscale[0], &p->hloc[1], &p->hscale[1], &p->hloc[2], &p->hscale[2], &p->hin[0], &p->hin[1]};
-  for (int i = 0; i < 8; ++i) {
-    if (*slots[i]) continue;
-    hipError_t e = hipHostMalloc((void**)slots[i], img, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      *slots[i] = nullptr;
-      for (int j = 0; j < 8; ++j) {
-        if (*slots[j]) (void)hipHostFree(*slots[j]);
-        *slots[j] = nullptr;
-      }
-      return hip_fail(e, "hipHostMalloc(pinned transfer ring)", __FILE__, __LINE__);
+  const size_t img = (size_t)p->cap * A.H * A.H * A.C;
+  // a failed allocation frees what this call got so far and leaves every slot null, so that a retry on a reused pipe does
+  // not keep pinned memory it cannot use (several GB at 8192 stamps per chunk)
+  PinBuf<float>* slots[8] = {&p->hloc[0], &p->hscale[0], &p->hloc[1], &p->hscale[1], &p->hloc[2], &p->hscale[2], &p->hin[0], &p->hin[1]};
+  for (PinBuf<float>* q : slots) {
+    if (*q) continue;
+    const int st = q->alloc(img, "hipHostMalloc(pinned transfer ring)");
+    if (st != OK) {
+      for (PinBuf<float>* r : slots) r->reset();
+      return st;
     }
   }
   p->host_ok = true;
@@ -2891,15 +2892,9 @@ static int pipe_host_buffers(dv_model* m, InferPipe* p) {
 // the third image slot of the pinned ring, allocated by the first call that sends Monte-Carlo std stamps to the host
 static int pipe_eps_buffers(dv_model* m, InferPipe* p) {
   const Arch& A = m->A;
-  const size_t img = (size_t)p->cap * A.H * A.H * A.C * sizeof(float);
-  for (int b = 0; b < 3; ++b) {
-    if (p->heps[b]) continue;
-    hipError_t e = hipHostMalloc((void**)&p->heps[b], img, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      p->heps[b] = nullptr;
-      return hip_fail(e, "hipHostMalloc(pinned transfer ring, epistemic slot)", __FILE__, __LINE__);
-    }
-  }
+  const size_t img = (size_t)p->cap * A.H * A.H * A.C;
+  for (int b = 0; b < 3; ++b)
+    if (!p->heps[b]) DV_TRY(p->heps[b].alloc(img, "hipHostMalloc(pinned transfer ring, epistemic slot)"));
   return OK;
 }
 
@@ -2914,36 +2909,24 @@ static int pipe_get(dv_model* m, int cap, InferPipe** out, bool need_host = true
   }
   pipe_free(m->pipe);
   m->pipe = nullptr;
-  InferPipe* p = new InferPipe();
+  std::unique_ptr<InferPipe> p(new InferPipe());
   p->cap = cap;
-  const size_t img = (size_t)cap * A.H * A.H * A.C * sizeof(float), small = (size_t)cap * 3 * A.d * sizeof(float);   // (dense rows of d: the strided device rows are packed on the way)
-  int st = OK;
-#define PP_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); pipe_free(p); return st; } } while (0)
+  const size_t img = (size_t)cap * A.H * A.H * A.C, small = (size_t)cap * 3 * A.d;   // floats (dense rows of d: the strided device rows are packed on the way)
   for (int b = 0; b < 3; ++b) {
-    PP_HIP(hipHostMalloc((void**)&p->hsmall[b], small, hipHostMallocDefault));
-    PP_HIP(hipEventCreateWithFlags(&p->ev_d2h[b], hipEventDisableTiming));
+    DV_TRY(p->hsmall[b].alloc(small));
+    DV_HIP(hipEventCreateWithFlags(&p->ev_d2h[b], hipEventDisableTiming));
   }
   for (int b = 0; b < 2; ++b) {
-    PP_HIP(hipMalloc((void**)&p->din[b], img + 64));
-    PP_HIP(hipMalloc((void**)&p->dloc[b], img + 64));
-    PP_HIP(hipMalloc((void**)&p->dscale[b], img + 64));
-    PP_HIP(hipMalloc((void**)&p->dsmall[b], small));
-    PP_HIP(hipEventCreateWithFlags(&p->ev_h2d[b], hipEventDisableTiming));
-    PP_HIP(hipEventCreateWithFlags(&p->ev_comp[b], hipEventDisableTiming));
+    for (DevBuf<float>* q : {&p->din[b], &p->dloc[b], &p->dscale[b]}) DV_TRY(q->alloc(img + 16));
+    DV_TRY(p->dsmall[b].alloc(small));
+    DV_HIP(hipEventCreateWithFlags(&p->ev_h2d[b], hipEventDisableTiming));
+    DV_HIP(hipEventCreateWithFlags(&p->ev_comp[b], hipEventDisableTiming));
   }
   p->s_in = m->ctx->red_stream;       // both idle during inference; a fifth stream would share a hardware queue
   p->s_out = m->ctx->comm_stream;
-#undef PP_HIP
-  if (need_host) {
-    st = pipe_host_buffers(m, p);
-    if (st != OK) {
-      pipe_free(p);
-      return st;
-    }
-  }
+  if (need_host) DV_TRY(pipe_host_buffers(m, p.get()));
   p->threads = copy_threads();
-  m->pipe = p;
-  *out = p;
+  *out = m->pipe = p.release();
   return OK;
 }
 
@@ -3039,35 +3022,41 @@ struct PipeJob {
   void* user = nullptr;
   // composite sums (dv_infer_cutouts_composite): every chunk's mean and stddev stamps are added into float64
   // fields in HBM right behind its forward pass instead of copied out; mean_f decides
-  double *mean_f = nullptr, *std_f = nullptr, *res_f = nullptr;   // device, fields f0 .. like fields_d
-  double* eps_f = nullptr;             // the same sum of the Monte-Carlo std stamps
-  double* res2_f = nullptr;            // a second residual, -= the mean stamps like res_f (dv_field_set_pass; not with eps_f)
-  const int* places_d = nullptr;     // device [.][2]: field position (row, col) of every stamp's top-left corner
-  double* mse = nullptr;               // device [.]: centre MSE of every stamp against its cutout
-  double* eps_norm = nullptr;          // device [.]: sum(std[:, :, 2]) / sum(mean[:, :, 2]) of every stamp
+  struct Sinks {
+    double *mean_f = nullptr, *std_f = nullptr, *res_f = nullptr;   // device, fields f0 .. like fields_d
+    double* eps_f = nullptr;           // the same sum of the Monte-Carlo std stamps
+    double* res2_f = nullptr;          // a second residual, -= the mean stamps like res_f (dv_field_set_pass; not with eps_f)
+    const int* places_d = nullptr;     // device [.][2]: field position (row, col) of every stamp's top-left corner
+    double* mse = nullptr;             // device [.]: centre MSE of every stamp against its cutout
+    double* eps_norm = nullptr;        // device [.]: sum(std[:, :, 2]) / sum(mean[:, :, 2]) of every stamp
+  } sinks;
   // Monte-Carlo stage (dv_infer_fields_mc_*): behind every chunk's forward pass, mc_samples more decodes of
   // the encoder output that pass left in the workspace, folded into per-pixel statistics; mc_samples > 0 decides
   int mc_samples = 0;
   uint64_t mc_seed = 0;
   // position fit and fractional placements (dv_infer_fields_fit_composite): behind every chunk's forward pass
   // (and Monte-Carlo stage) the r band of its mean stamps is fitted against the resident r-band planes, the placements
-  // follow from the fitted shifts on the device, and the chunk is composited there; fit_plan decides (places_d is unused)
-  const PosfitPlan* fit_plan = nullptr;
-  const int* fit_l0 = nullptr;         // host: chunk k of the whole list runs the plan's launches fit_l0[k] .. fit_l0[k + 1]
-  const double *fit_img = nullptr, *fit_totsq = nullptr;   // device: r-band planes of fields f0 .. and their sums of squares
-  const double* dist_d = nullptr;      // device [.][2]: integer distances to the field centre
-  double *fit_stamps = nullptr, *fit_work = nullptr;       // device: r band of a chunk's mean stamps, the fit's workspace
-  double *shifts_d = nullptr, *fit_obj = nullptr;          // device [.][2], [.]: start shifts in, fitted out; objective
-  int *fit_iters = nullptr, *fit_status = nullptr;         // device [.]
-  void* objs_d = nullptr;              // device [chunk]: a chunk's placements
-  double* coef_d = nullptr;            // device: B-spline coefficients of a sub-chunk
+  // follow from the fitted shifts on the device, and the chunk is composited there; plan decides (sinks.places_d is unused)
+  struct Fit {
+    const PosfitPlan* plan = nullptr;
+    const int* l0 = nullptr;           // host: chunk k of the whole list runs the plan's launches l0[k] .. l0[k + 1]
+    const double *img = nullptr, *totsq = nullptr;   // device: r-band planes of fields f0 .. and their sums of squares
+    const double* dist_d = nullptr;    // device [.][2]: integer distances to the field centre
+    double *stamps = nullptr, *work = nullptr;       // device: r band of a chunk's mean stamps, the fit's workspace
+    double *shifts_d = nullptr, *obj = nullptr;      // device [.][2], [.]: start shifts in, fitted out; objective
+    int *iters = nullptr, *status = nullptr;         // device [.]
+    void* objs_d = nullptr;            // device [chunk]: a chunk's placements
+    double* coef_d = nullptr;          // device: B-spline coefficients of a sub-chunk
+  } fit;
   // catalogue measurement (dv_infer_fields_measure): behind every chunk's forward pass, fluxes and adaptive
-  // moments of its mean / stddev stamps as they lie in HBM; ms_flux decides.  Without mean_f this is the catalogue-only
+  // moments of its mean / stddev stamps as they lie in HBM; flux decides.  Without sinks.mean_f this is the catalogue-only
   // call: no stamp and no field leaves the device
-  double *ms_flux = nullptr, *ms_ferr = nullptr, *ms_shape = nullptr;   // device [.][nb], [.][nb], [.][5]
-  int *ms_iters = nullptr, *ms_status = nullptr;                        // device [.]
-  int ms_band = 0, ms_max_iter = 0;
-  double ms_sigma0 = 0.0, ms_tol = 0.0;
+  struct Measure {
+    double *flux = nullptr, *ferr = nullptr, *shape = nullptr;   // device [.][nb], [.][nb], [.][5]
+    int *iters = nullptr, *status = nullptr;                     // device [.]
+    int band = 0, max_iter = 0;
+    double sigma0 = 0.0, tol = 0.0;
+  } ms;
 };
 
 // The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
@@ -3107,8 +3096,8 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
   const size_t stamp = (size_t)A.H * A.H * A.C;
   const int chunk = j.chunk, cs = A.H;
   const int64_t N = j.N, row0 = j.row0;
-  const bool comp = j.mean_f != nullptr;
-  const bool meas = j.ms_flux != nullptr;
+  const bool comp = j.sinks.mean_f != nullptr;
+  const bool meas = j.ms.flux != nullptr;
   InferPipe* p = nullptr;
   DV_TRY(pipe_get(m, chunk, &p, !comp && !meas));
   if (j.eps_out) DV_TRY(pipe_eps_buffers(m, p));
@@ -3240,35 +3229,35 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
       ProfScope ps(m, 2, p->s_out);
       // the fields this chunk's stamps belong to: one row of workgroups per field, each scanning its own objects
       const int fy0 = j.sfield[r], fy1 = j.sfield[r + nb - 1];
-      if (j.fit_plan) {
+      if (j.fit.plan) {
         const int64_t kg = r / chunk;      // (a job starts on a chunk boundary of the whole list)
-        DV_TRY(launch_posfit_band_f32(p->dloc[b], (long)nb * cs * cs, j.nb, 2, j.fit_stamps, p->s_out));
-        DV_TRY(posfit_plan_run(j.fit_plan, j.fit_l0[kg], j.fit_l0[kg + 1], j.fit_img, j.fit_totsq, j.fit_stamps, j.fit_work,
-                               j.shifts_d, j.fit_obj, j.fit_iters, j.fit_status, p->s_out));
-        DV_TRY(launch_scene_places(j.dist_d + 2 * r, j.shifts_d + 2 * r, nb, j.F, cs, j.objs_d, p->s_out));
-        DV_TRY(launch_scene_composite_frac(j.mean_f, j.std_f, j.res_f, j.F, j.nb, p->dloc[b], p->dscale[b], j.objs_d, nb, cs,
-                                           p->s_out, j.fptr_d, j.f0, j.sfield + r, (long)r, j.eps_f,
-                                           j.eps_f ? m->gB : nullptr, j.res2_f, j.coef_d));
+        DV_TRY(launch_posfit_band_f32(p->dloc[b], (long)nb * cs * cs, j.nb, 2, j.fit.stamps, p->s_out));
+        DV_TRY(posfit_plan_run(j.fit.plan, j.fit.l0[kg], j.fit.l0[kg + 1], j.fit.img, j.fit.totsq, j.fit.stamps, j.fit.work,
+                               j.fit.shifts_d, j.fit.obj, j.fit.iters, j.fit.status, p->s_out));
+        DV_TRY(launch_scene_places(j.fit.dist_d + 2 * r, j.fit.shifts_d + 2 * r, nb, j.F, cs, j.fit.objs_d, p->s_out));
+        DV_TRY(launch_scene_composite_frac(j.sinks.mean_f, j.sinks.std_f, j.sinks.res_f, j.F, j.nb, p->dloc[b], p->dscale[b],
+                                           j.fit.objs_d, nb, cs, p->s_out, j.fptr_d, j.f0, j.sfield + r, (long)r,
+                                           j.sinks.eps_f, j.sinks.eps_f ? m->gB : nullptr, j.sinks.res2_f, j.fit.coef_d));
       } else {
-        DV_TRY(launch_scene_composite_chunk(j.mean_f, j.std_f, j.res_f, j.F, j.nb, p->dloc[b], p->dscale[b],
-                                            j.places_d + 2 * r, nb, cs, p->s_out, j.fptr_d, j.f0, fy0, fy1 - fy0 + 1,
-                                            (long)r, j.eps_f, j.eps_f ? m->gB : nullptr, j.res2_f));
+        DV_TRY(launch_scene_composite_chunk(j.sinks.mean_f, j.sinks.std_f, j.sinks.res_f, j.F, j.nb, p->dloc[b], p->dscale[b],
+                                            j.sinks.places_d + 2 * r, nb, cs, p->s_out, j.fptr_d, j.f0, fy0, fy1 - fy0 + 1,
+                                            (long)r, j.sinks.eps_f, j.sinks.eps_f ? m->gB : nullptr, j.sinks.res2_f));
       }
-      if (j.eps_norm) DV_TRY(launch_scene_eps_norm(m->gB, p->dloc[b], nb, cs, j.nb, j.eps_norm + r, p->s_out));
-      if (j.mse)
-        DV_TRY(launch_scene_center_mse(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, p->dloc[b], nb, cs, j.mse + r, p->s_out,
+      if (j.sinks.eps_norm) DV_TRY(launch_scene_eps_norm(m->gB, p->dloc[b], nb, cs, j.nb, j.sinks.eps_norm + r, p->s_out));
+      if (j.sinks.mse)
+        DV_TRY(launch_scene_center_mse(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, p->dloc[b], nb, cs, j.sinks.mse + r, p->s_out,
                                        j.sfield_d + r, j.f0));
     }
     if (meas) {
       // the catalogue of this chunk, on the output stream like the compositing: one workgroup per stamp reads the chunk's
       // mean and stddev stamps where the head kernel left them; the forward of chunk k + 2 waits for ev_d2h below
       ProfScope ps(m, 2, p->s_out);
-      if (!comp && j.mse)                  // the catalogue-only call: the quality cut's input without the fields
-        DV_TRY(launch_scene_center_mse(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, p->dloc[b], nb, cs, j.mse + r, p->s_out,
+      if (!comp && j.sinks.mse)                  // the catalogue-only call: the quality cut's input without the fields
+        DV_TRY(launch_scene_center_mse(j.fields_d, j.F, j.nb, j.starts_d + 2 * r, p->dloc[b], nb, cs, j.sinks.mse + r, p->s_out,
                                        j.sfield_d + r, j.f0));
-      DV_TRY(launch_measure(p->dloc[b], p->dscale[b], nb, cs, j.nb, j.ms_band, j.ms_sigma0, j.ms_tol, j.ms_max_iter,
-                            j.ms_flux + (size_t)r * j.nb, j.ms_ferr + (size_t)r * j.nb, j.ms_shape + (size_t)r * 5,
-                            j.ms_iters + r, j.ms_status + r, p->s_out));
+      DV_TRY(launch_measure(p->dloc[b], p->dscale[b], nb, cs, j.nb, j.ms.band, j.ms.sigma0, j.ms.tol, j.ms.max_iter,
+                            j.ms.flux + (size_t)r * j.nb, j.ms.ferr + (size_t)r * j.nb, j.ms.shape + (size_t)r * 5,
+                            j.ms.iters + r, j.ms.status + r, p->s_out));
     }
     if (j.loc || j.consumer) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (j.scale || j.consumer) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
@@ -3499,7 +3488,8 @@ int dv_comm_unique_id(void* out_id) {
 
 // Set by an exit handler that is registered at the first dv_ctx_create, i.e. AFTER the HIP runtime registered its own:
 // exit() runs handlers in reverse order, so from the moment this flag is up the runtime may already be gone and the
-// destroy calls only release host memory (the process is going away; the driver reclaims the rest).
+// destroy calls only release host memory (the process is going away; the driver reclaims the rest).  Objects whose
+// destructors call the runtime (StreamRing, InferPipe, dv_field_set: DevBuf / PinBuf members, events) are NOT deleted then.
 static bool g_process_exiting = false;
 static void mark_process_exiting() { g_process_exiting = true; }
 
@@ -3753,10 +3743,9 @@ int dv_model_destroy(dv_model* m) {
     auto& v = m->ctx->models;
     v.erase(std::remove(v.begin(), v.end(), m), v.end());
   }
-  if (g_process_exiting) {                   // see mark_process_exiting: host memory only
-    delete m->ring;
-    delete m->pipe;
-    for (dv_field_set* fs : m->field_sets) delete fs;
+  if (g_process_exiting) {
+    // see mark_process_exiting: host memory only.  The ring, the pipeline and the field sets own device and pinned memory,
+    // events and a stream, which their destructors would hand back to a runtime that may be gone: they are left behind
     delete m;
     return DV_OK;
   }
@@ -4588,82 +4577,37 @@ static int fields_tables(dv_model* m, const char* who, int32_t M, const int64_t*
   return DV_OK;
 }
 
-// j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
-// the device side and the rows are filled in here
-static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
-                             const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr) {
-  const double* fields = j.fields;
-  const int32_t* starts = j.starts;
-  const int F = j.F, nb = j.nb;
-  if (M > 0 && !fields) return DV_E_INVALID;
-  std::vector<int32_t> sfield;
-  std::vector<int> fptr32;
-  DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, starts, fo ? fo->places : nullptr, sfield, fptr32));
-  const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
-  if (fo)                                       // a field without stamps: nothing predicted, nothing subtracted
-    for (int32_t f = 0; f < M; ++f)
-      if (field_ptr[f + 1] == field_ptr[f]) {
-        memset(fo->mean + (size_t)f * felems, 0, fb);
-        memset(fo->stddev + (size_t)f * felems, 0, fb);
-        if (fo->epistemic) memset(fo->epistemic + (size_t)f * felems, 0, fb);
-        if (fo->residual) memcpy(fo->residual + (size_t)f * felems, fields + (size_t)f * felems, fb);
-      }
-  if (N == 0) return DV_OK;
-  TinyCall tiny(m, N);
-  DV_HIP(hipSetDevice(m->ctx->device));
-  hipStream_t s = m->ctx->stream;
-  const int chunk = infer_chunk(m, N);
-  const int64_t K = (N + chunk - 1) / chunk;
-  InferPipe* pipe = nullptr;
-  DV_TRY(pipe_get(m, chunk, &pipe, fo == nullptr && mo == nullptr));   // before the budget below: the pipeline's buffers come first
-  // the fit's plan: every galaxy's windows, laid out chunk by chunk against field 0 (rebased once the groups are known);
-  // its workspace, the coefficient workspace of the fractional compositing and a chunk's r-band stamps and placements are
-  // allocated once per call and come off the budget like the tables
-  const bool fit = fo && fo->dist;
-  const int cs = m->A.H;
-  PosfitPlan* plan = nullptr;
-  std::vector<int> fit_l0;
-  size_t fit_fixed = 0, coef_doubles = 0;
-  if (fit) {
-    DV_TRY(posfit_plan_create(F, cs, (int)N, fo->dist, fo->shifts, fo->bound, fo->max_iter, &plan));
-    fit_l0.resize((size_t)K + 1);
-    for (int64_t k = 0; k < K; ++k)
-      fit_l0[k] = posfit_plan_layout(plan, (int)(k * chunk), (int)std::min<int64_t>(N, (k + 1) * chunk), chunk, sfield.data(),
-                                     0, (int)(k * chunk));
-    fit_l0[K] = posfit_plan_launch_count(plan);
-    coef_doubles = scene_frac_coef_doubles(cs, nb, fo->epistemic ? 3 : 2);
-    fit_fixed = ((size_t)posfit_plan_work_doubles(plan) + coef_doubles + (size_t)chunk * cs * cs) * sizeof(double) +
-                scene_frac_obj_bytes((size_t)chunk) + posfit_plan_geom_bytes((size_t)N) +
-                (size_t)N * (5 * sizeof(double) + 2 * sizeof(int));
-  }
-  struct PlanGuard {                                  // (the plan's device copy goes with it)
-    PosfitPlan* p;
-    ~PlanGuard() { posfit_plan_destroy(p); }
-  } plan_guard{plan};
+// ---- the many-field call, stage by stage ------------------------------------------------------------------------------------
+// Every optional stage of the call owns its device buffers in one struct with three steps: allocate from the call's sizes,
+// bind into the job (one nested PipeJob member), download into the caller's arrays.  What a stage adds to the memory a
+// resident field or a stamp costs stands beside its allocations (bytes_per_field / bytes_per_stamp / bytes_fixed).
+struct FieldsCall {                 // the sizes of one call
+  int64_t N, K;                     // stamps, chunks
+  int F, nb, cs, chunk;
+  hipStream_t s;
+};
 
-  // fields per group: what free memory holds beside the per-stamp tables; DV_FIELDS_GROUP_MB lowers it
-  // (with the Monte-Carlo estimate a resident field carries one more result field, a stamp one more scalar)
-  const size_t per_field = fb * (fo ? (fo->residual ? 4 : 3) + (fo->epistemic ? 1 : 0) : 1) +
-                           (fit ? ((size_t)F * F + 1) * sizeof(double) : 0);   // (the fit: an r-band plane and its sum of squares)
-  const size_t tables = (size_t)N * (5 * sizeof(int) + sizeof(double) * (fo && fo->eps_norm ? 2 : 1)) + ((size_t)M + 1) * sizeof(int) +
-                        fit_fixed + (mo ? (size_t)N * ((2 * (size_t)nb + 6) * sizeof(double) + 2 * sizeof(int)) : 0);   // (the catalogue)
+// device memory a call may fill with fields: 8/10 of what is free, less what the call allocates beside them, and at most
+// DV_FIELDS_GROUP_MB
+static int fields_budget(size_t reserve, size_t* budget) {
   size_t free_b = 0, total_b = 0;
   DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  size_t budget = free_b / 10 * 8;
-  budget = budget > tables ? budget - tables : 0;
+  *budget = free_b / 10 * 8;
+  *budget = *budget > reserve ? *budget - reserve : 0;
   if (const char* e = getenv("DV_FIELDS_GROUP_MB")) {
     const long mb = atol(e);
-    if (mb > 0) budget = std::min(budget, (size_t)mb << 20);
+    if (mb > 0) *budget = std::min(*budget, (size_t)mb << 20);
   }
-  const int64_t G = (int64_t)(budget / per_field);
-  if (G < 1) {
-    set_error("%s: one %d-pixel field needs %zu bytes of device memory (field%s), %zu are available for fields", who, F,
-              per_field, fo ? " and its result fields" : "", budget);
-    return DV_E_NOMEM;
-  }
-  struct Group { int64_t k0, k1; int f0, f1; };      // chunks [k0, k1), fields [f0, f1]
-  std::vector<Group> groups;
-  int64_t gmax = 0;
+  return DV_OK;
+}
+
+// groups of consecutive fields, at most G resident at a time, each covering whole chunks: a field whose stamps straddle two
+// groups is resident in both
+struct FieldGroup { int64_t k0, k1; int f0, f1; };      // chunks [k0, k1), fields [f0, f1]
+static int plan_field_groups(const char* who, const int32_t* sfield, int64_t N, int chunk, int64_t G,
+                             std::vector<FieldGroup>& groups, int64_t* gmax) {
+  const int64_t K = (N + chunk - 1) / chunk;
+  *gmax = 0;
   for (int64_t k = 0; k < K;) {
     const int f0 = sfield[k * chunk];
     int64_t k1 = k;
@@ -4680,186 +4624,275 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
       return DV_E_NOMEM;
     }
     groups.push_back({k, k1, f0, f1});
-    gmax = std::max<int64_t>(gmax, f1 - f0 + 1);
+    *gmax = std::max<int64_t>(*gmax, f1 - f0 + 1);
     k = k1;
   }
+  return DV_OK;
+}
 
-  double *fdev = nullptr, *mf = nullptr, *sf = nullptr, *rf = nullptr, *mse = nullptr, *ef = nullptr, *en = nullptr;
-  int *sdev = nullptr, *pdev = nullptr, *sfdev = nullptr, *fpdev = nullptr;
-  double *f_img = nullptr, *f_tot = nullptr, *f_dist = nullptr, *f_stamps = nullptr, *f_work = nullptr, *f_shifts = nullptr,
-         *f_obj = nullptr, *f_coef = nullptr;
-  int *f_iters = nullptr, *f_status = nullptr;
-  void* f_objs = nullptr;
-  double *c_flux = nullptr, *c_ferr = nullptr, *c_shape = nullptr;
-  int *c_iters = nullptr, *c_status = nullptr;
+// a field without stamps: nothing predicted, nothing subtracted
+static void fields_write_empty(const FieldsOut& fo, const double* fields, int32_t M, const int64_t* field_ptr, size_t felems) {
+  const size_t fb = felems * sizeof(double);
+  for (int32_t f = 0; f < M; ++f)
+    if (field_ptr[f + 1] == field_ptr[f]) {
+      memset(fo.mean + (size_t)f * felems, 0, fb);
+      memset(fo.stddev + (size_t)f * felems, 0, fb);
+      if (fo.epistemic) memset(fo.epistemic + (size_t)f * felems, 0, fb);
+      if (fo.residual) memcpy(fo.residual + (size_t)f * felems, fields + (size_t)f * felems, fb);
+    }
+}
+
+// one result stack of the resident group and the caller's [M][F][F][nb] array it ends up in (null: not wanted)
+struct ResultStack {
+  DevBuf<double> dev;
+  double* host = nullptr;
+  int alloc(double* h, size_t elems) { host = h; return h ? dev.alloc(elems) : DV_OK; }
+  // a group begins: zeros, or the source fields for a residual
+  int begin(const double* source, size_t bytes, hipStream_t s) {
+    if (!host) return DV_OK;
+    if (source) DV_HIP(hipMemcpyAsync(dev, source, bytes, hipMemcpyDeviceToDevice, s));
+    else DV_HIP(hipMemsetAsync(dev, 0, bytes, s));
+    return DV_OK;
+  }
+  // the group's first field was composited in part with the previous group: go on from those sums
+  int carry(size_t goff, size_t fb, hipStream_t s) {
+    if (host) DV_HIP(hipMemcpyAsync(dev, host + goff, fb, hipMemcpyHostToDevice, s));
+    return DV_OK;
+  }
+  int end(size_t bytes, size_t goff, hipStream_t s) {
+    if (host) DV_HIP(hipMemcpyAsync(host + goff, dev, bytes, hipMemcpyDeviceToHost, s));
+    return DV_OK;
+  }
+};
+
+struct CompositeStage {             // the mean / stddev / residual sums
+  ResultStack mean, stddev, residual;
+  static size_t bytes_per_field(const FieldsOut& fo, size_t fb) { return fb * (fo.residual ? 3 : 2); }
+  int alloc(const FieldsOut& fo, size_t elems) {
+    DV_TRY(mean.alloc(fo.mean, elems));
+    DV_TRY(stddev.alloc(fo.stddev, elems));
+    return residual.alloc(fo.residual, elems);
+  }
+  void bind(PipeJob::Sinks& k) const { k.mean_f = mean.dev; k.std_f = stddev.dev; k.res_f = residual.dev; }
+};
+
+struct MonteCarloStage {            // what the Monte-Carlo estimate adds: one more result field, one more scalar per stamp (7g)
+  ResultStack eps;
+  DevBuf<double> norm;
+  double* norm_h = nullptr;
+  static size_t bytes_per_field(const FieldsOut& fo, size_t fb) { return fo.epistemic ? fb : 0; }
+  static size_t bytes_per_stamp(const FieldsOut& fo) { return fo.eps_norm ? sizeof(double) : 0; }
+  int alloc(const FieldsOut& fo, size_t elems, int64_t N) {
+    DV_TRY(eps.alloc(fo.epistemic, elems));
+    norm_h = fo.eps_norm;
+    return norm_h ? norm.alloc((size_t)N) : DV_OK;
+  }
+  void bind(PipeJob::Sinks& k) const { k.eps_f = eps.dev; k.eps_norm = norm; }
+  int download(int64_t N, hipStream_t s) {
+    if (!norm_h) return DV_OK;
+    DV_HIP(hipMemcpyAsync(norm_h, norm, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return DV_OK;
+  }
+};
+
+struct FitStage {                   // the position fit and the fractional placements (7i)
+  PosfitPlanOwner plan;             // (the plan's device copy goes with it)
+  std::vector<int> l0;
+  size_t coef_doubles = 0;
+  DevBuf<double> img, totsq, dist, stamps, work, shifts, obj, coef;
+  DevBuf<int> iters, status;
+  DevBuf<char> objs;
+  // the plan: every galaxy's windows, laid out chunk by chunk against field 0 (rebased once the groups are known)
+  int make_plan(const FieldsOut& fo, const FieldsCall& c, const int32_t* sfield) {
+    PosfitPlan* p = nullptr;
+    DV_TRY(posfit_plan_create(c.F, c.cs, (int)c.N, fo.dist, fo.shifts, fo.bound, fo.max_iter, &p));
+    plan.reset(p);
+    l0.resize((size_t)c.K + 1);
+    for (int64_t k = 0; k < c.K; ++k)
+      l0[k] = posfit_plan_layout(plan.get(), (int)(k * c.chunk), (int)std::min<int64_t>(c.N, (k + 1) * c.chunk), c.chunk, sfield, 0,
+                                 (int)(k * c.chunk));
+    l0[c.K] = posfit_plan_launch_count(plan.get());
+    coef_doubles = scene_frac_coef_doubles(c.cs, c.nb, fo.epistemic ? 3 : 2);
+    return DV_OK;
+  }
+  static size_t bytes_per_field(int F) { return ((size_t)F * F + 1) * sizeof(double); }   // an r-band plane and its sum of squares
+  // allocated once per call: the fit's workspace, the coefficient workspace of the fractional compositing, a chunk's r-band
+  // stamps and placements, the plan's device copy and the per-galaxy arrays
+  size_t bytes_fixed(const FieldsCall& c) const {
+    return ((size_t)posfit_plan_work_doubles(plan.get()) + coef_doubles + (size_t)c.chunk * c.cs * c.cs) * sizeof(double) +
+           scene_frac_obj_bytes((size_t)c.chunk) + posfit_plan_geom_bytes((size_t)c.N) +
+           (size_t)c.N * (5 * sizeof(double) + 2 * sizeof(int));
+  }
+  int alloc(const FieldsOut& fo, const FieldsCall& c, int64_t gmax, const std::vector<FieldGroup>& groups) {
+    const size_t n = (size_t)c.N;
+    DV_TRY(img.alloc((size_t)gmax * c.F * c.F));
+    DV_TRY(totsq.alloc((size_t)gmax));
+    for (DevBuf<double>* b : {&dist, &shifts}) DV_TRY(b->alloc(2 * n));
+    DV_TRY(obj.alloc(n));
+    for (DevBuf<int>* b : {&iters, &status}) DV_TRY(b->alloc(n));
+    DV_TRY(stamps.alloc((size_t)c.chunk * c.cs * c.cs));
+    DV_TRY(work.alloc((size_t)posfit_plan_work_doubles(plan.get())));
+    DV_TRY(coef.alloc(coef_doubles));
+    DV_TRY(objs.alloc(scene_frac_obj_bytes((size_t)c.chunk)));
+    DV_HIP(hipMemcpyAsync(dist, fo.dist, 2 * n * sizeof(double), hipMemcpyHostToDevice, c.s));
+    DV_HIP(hipMemcpyAsync(shifts, fo.shifts, 2 * n * sizeof(double), hipMemcpyHostToDevice, c.s));
+    for (const FieldGroup& g : groups)
+      posfit_plan_rebase(plan.get(), (int)(g.k0 * c.chunk), (int)std::min<int64_t>(c.N, g.k1 * c.chunk), g.f0);
+    return posfit_plan_upload(plan.get(), c.s);
+  }
+  void bind(PipeJob::Fit& f) const {
+    f.plan = plan.get(); f.l0 = l0.data();
+    f.img = img; f.totsq = totsq; f.dist_d = dist;
+    f.stamps = stamps; f.work = work;
+    f.shifts_d = shifts; f.obj = obj; f.iters = iters; f.status = status;
+    f.objs_d = objs.get(); f.coef_d = coef;
+  }
+  // a group begins: the r band of its resident fields as planes
+  int begin(const double* fields_d, size_t ng, const FieldsCall& c) {
+    DV_TRY(launch_posfit_band_f64(fields_d, (long)ng * c.F * c.F, c.nb, 2, img, c.s));
+    return launch_posfit_total_sq(img, (int)ng, (long)c.F * c.F, totsq, c.s);
+  }
+  int download(const FieldsOut& fo, int64_t N, hipStream_t s) {
+    DV_HIP(hipMemcpyAsync(fo.shifts, shifts, (size_t)N * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(fo.objective, obj, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(fo.iters, iters, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(fo.status, status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return DV_OK;
+  }
+};
+
+struct CatalogueStage {             // fluxes, errors and adaptive moments of every stamp (7j)
+  DevBuf<double> flux, ferr, shape;
+  DevBuf<int> iters, status;
+  static size_t bytes_per_stamp(int nb) { return (2 * (size_t)nb + 6) * sizeof(double) + 2 * sizeof(int); }
+  int alloc(int64_t N, int nb) {
+    for (DevBuf<double>* b : {&flux, &ferr}) DV_TRY(b->alloc((size_t)N * nb));
+    for (DevBuf<int>* b : {&iters, &status}) DV_TRY(b->alloc((size_t)N));
+    return shape.alloc((size_t)N * 5);
+  }
+  void bind(PipeJob::Measure& q, const dv_measure_params& par) const {
+    q.flux = flux; q.ferr = ferr; q.shape = shape; q.iters = iters; q.status = status;
+    q.band = par.band; q.max_iter = par.max_iter; q.sigma0 = par.sigma0; q.tol = par.tol;
+  }
+  int download(const MeasureOut& mo, int64_t N, int nb, hipStream_t s) {
+    DV_HIP(hipMemcpyAsync(mo.flux, flux, (size_t)N * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(mo.flux_err, ferr, (size_t)N * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(mo.shape, shape, (size_t)N * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(mo.iters, iters, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(mo.status, status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return DV_OK;
+  }
+};
+
+// j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
+// the device side and the rows are filled in here
+static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
+                             const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr) {
+  // check
+  const double* fields = j.fields;
+  const int F = j.F, nb = j.nb;
+  if (M > 0 && !fields) return DV_E_INVALID;
+  std::vector<int32_t> sfield;
+  std::vector<int> fptr32;
+  DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, j.starts, fo ? fo->places : nullptr, sfield, fptr32));
+  const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
+  if (fo) fields_write_empty(*fo, fields, M, field_ptr, felems);
+  if (N == 0) return DV_OK;
+  TinyCall tiny(m, N);
+  DV_HIP(hipSetDevice(m->ctx->device));
+  hipStream_t s = m->ctx->stream;
+  const int chunk = infer_chunk(m, N);
+  const FieldsCall c{N, (N + chunk - 1) / chunk, F, nb, m->A.H, chunk, s};
+  InferPipe* pipe = nullptr;
+  DV_TRY(pipe_get(m, chunk, &pipe, fo == nullptr && mo == nullptr));   // before the budget below: the pipeline's buffers come first
+  // plan the groups: fields per group = what free memory holds beside the per-stamp tables and the stages' own arrays
+  const bool fitting = fo && fo->dist;
   double* mse_h = fo ? fo->mse : mo ? mo->mse : nullptr;
-  int st = OK;
-  auto cleanup = [&]() {
-    if (st != OK && pipe->s_out) (void)hipStreamSynchronize(pipe->s_out);   // nothing may still read these
-    if (st != OK && pipe->s_in) (void)hipStreamSynchronize(pipe->s_in);
-    (void)hipFree(f_img); (void)hipFree(f_tot); (void)hipFree(f_dist); (void)hipFree(f_stamps); (void)hipFree(f_work);
-    (void)hipFree(f_shifts); (void)hipFree(f_obj); (void)hipFree(f_coef); (void)hipFree(f_iters); (void)hipFree(f_status);
-    (void)hipFree(f_objs);
-    (void)hipFree(c_flux); (void)hipFree(c_ferr); (void)hipFree(c_shape); (void)hipFree(c_iters); (void)hipFree(c_status);
-    (void)hipFree(fdev); (void)hipFree(mf); (void)hipFree(sf); (void)hipFree(rf); (void)hipFree(mse);
-    (void)hipFree(ef); (void)hipFree(en);
-    (void)hipFree(sdev); (void)hipFree(pdev); (void)hipFree(sfdev); (void)hipFree(fpdev);
-  };
-#define FF_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
-  const size_t sb = (size_t)N * 2 * sizeof(int);
-  FF_HIP(hipMalloc((void**)&fdev, (size_t)gmax * fb));
+  DevBuf<double> fdev;                                // the resident group of source fields
+  StampTables tab;
+  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat;   // (a stage that does not run stays empty)
+  ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
+  if (fitting) DV_TRY(fit.make_plan(*fo, c, sfield.data()));
+  size_t per_field = fb, reserve = StampTables::bytes((size_t)N, (size_t)M);
   if (fo) {
-    FF_HIP(hipMalloc((void**)&mf, (size_t)gmax * fb));
-    FF_HIP(hipMalloc((void**)&sf, (size_t)gmax * fb));
-    if (fo->residual) FF_HIP(hipMalloc((void**)&rf, (size_t)gmax * fb));
-    if (fo->epistemic) FF_HIP(hipMalloc((void**)&ef, (size_t)gmax * fb));
-    if (fo->eps_norm) FF_HIP(hipMalloc((void**)&en, (size_t)N * sizeof(double)));
-    if (!fit) {
-      FF_HIP(hipMalloc((void**)&pdev, sb));
-      FF_HIP(hipMemcpyAsync(pdev, fo->places, sb, hipMemcpyHostToDevice, s));
-    }
+    per_field += CompositeStage::bytes_per_field(*fo, fb) + MonteCarloStage::bytes_per_field(*fo, fb);
+    reserve += (size_t)N * MonteCarloStage::bytes_per_stamp(*fo);
   }
-  if (mse_h) FF_HIP(hipMalloc((void**)&mse, (size_t)N * sizeof(double)));
+  if (fitting) {
+    per_field += FitStage::bytes_per_field(F);
+    reserve += fit.bytes_fixed(c);
+  }
+  if (mo) reserve += (size_t)N * CatalogueStage::bytes_per_stamp(nb);
+  size_t budget = 0;
+  DV_TRY(fields_budget(reserve, &budget));
+  const int64_t G = (int64_t)(budget / per_field);
+  if (G < 1) {
+    set_error("%s: one %d-pixel field needs %zu bytes of device memory (field%s), %zu are available for fields", who, F,
+              per_field, fo ? " and its result fields" : "", budget);
+    return DV_E_NOMEM;
+  }
+  std::vector<FieldGroup> groups;
+  int64_t gmax = 0;
+  DV_TRY(plan_field_groups(who, sfield.data(), N, chunk, G, groups, &gmax));
+  // allocate the stages and bind them into the job; from here on a failure waits for the streams before the buffers go
+  StreamDrain drain(s, pipe->s_in, pipe->s_out);
+  const size_t gelems = (size_t)gmax * felems;
+  DV_TRY(fdev.alloc(gelems));
+  if (fo) {
+    DV_TRY(comp.alloc(*fo, gelems));
+    DV_TRY(mc.alloc(*fo, gelems, N));
+    comp.bind(j.sinks);
+    mc.bind(j.sinks);
+  }
   if (mo) {
-    FF_HIP(hipMalloc((void**)&c_flux, (size_t)N * nb * sizeof(double)));
-    FF_HIP(hipMalloc((void**)&c_ferr, (size_t)N * nb * sizeof(double)));
-    FF_HIP(hipMalloc((void**)&c_shape, (size_t)N * 5 * sizeof(double)));
-    FF_HIP(hipMalloc((void**)&c_iters, (size_t)N * sizeof(int)));
-    FF_HIP(hipMalloc((void**)&c_status, (size_t)N * sizeof(int)));
-    j.ms_flux = c_flux;
-    j.ms_ferr = c_ferr;
-    j.ms_shape = c_shape;
-    j.ms_iters = c_iters;
-    j.ms_status = c_status;
-    j.ms_band = mo->par.band;
-    j.ms_sigma0 = mo->par.sigma0;
-    j.ms_tol = mo->par.tol;
-    j.ms_max_iter = mo->par.max_iter;
+    DV_TRY(cat.alloc(N, nb));
+    cat.bind(j.ms, mo->par);
   }
-  if (fit) {
-    const size_t nd = (size_t)N * sizeof(double);
-    FF_HIP(hipMalloc((void**)&f_img, (size_t)gmax * F * F * sizeof(double)));
-    FF_HIP(hipMalloc((void**)&f_tot, (size_t)gmax * sizeof(double)));
-    FF_HIP(hipMalloc((void**)&f_dist, 2 * nd));
-    FF_HIP(hipMalloc((void**)&f_shifts, 2 * nd));
-    FF_HIP(hipMalloc((void**)&f_obj, nd));
-    FF_HIP(hipMalloc((void**)&f_iters, (size_t)N * sizeof(int)));
-    FF_HIP(hipMalloc((void**)&f_status, (size_t)N * sizeof(int)));
-    FF_HIP(hipMalloc((void**)&f_stamps, (size_t)chunk * cs * cs * sizeof(double)));
-    FF_HIP(hipMalloc((void**)&f_work, (size_t)posfit_plan_work_doubles(plan) * sizeof(double)));
-    FF_HIP(hipMalloc((void**)&f_coef, coef_doubles * sizeof(double)));
-    FF_HIP(hipMalloc(&f_objs, scene_frac_obj_bytes((size_t)chunk)));
-    FF_HIP(hipMemcpyAsync(f_dist, fo->dist, 2 * nd, hipMemcpyHostToDevice, s));
-    FF_HIP(hipMemcpyAsync(f_shifts, fo->shifts, 2 * nd, hipMemcpyHostToDevice, s));
-    for (const Group& g : groups)
-      posfit_plan_rebase(plan, (int)(g.k0 * chunk), (int)std::min<int64_t>(N, g.k1 * chunk), g.f0);
-    st = posfit_plan_upload(plan, s);
-    if (st != OK) {
-      cleanup();
-      return st;
-    }
-    j.fit_plan = plan;
-    j.fit_l0 = fit_l0.data();
-    j.fit_img = f_img;
-    j.fit_totsq = f_tot;
-    j.dist_d = f_dist;
-    j.fit_stamps = f_stamps;
-    j.fit_work = f_work;
-    j.shifts_d = f_shifts;
-    j.fit_obj = f_obj;
-    j.fit_iters = f_iters;
-    j.fit_status = f_status;
-    j.objs_d = f_objs;
-    j.coef_d = f_coef;
+  if (fitting) {
+    DV_TRY(fit.alloc(*fo, c, gmax, groups));
+    fit.bind(j.fit);
   }
-  FF_HIP(hipMalloc((void**)&sdev, sb));
-  FF_HIP(hipMalloc((void**)&sfdev, (size_t)N * sizeof(int)));
-  FF_HIP(hipMalloc((void**)&fpdev, ((size_t)M + 1) * sizeof(int)));
-  FF_HIP(hipMemcpyAsync(sdev, starts, sb, hipMemcpyHostToDevice, s));
-  FF_HIP(hipMemcpyAsync(sfdev, sfield.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
-  FF_HIP(hipMemcpyAsync(fpdev, fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_TRY(tab.upload(N, M, j.starts, fo && !fitting ? fo->places : nullptr, sfield.data(), fptr32.data(), mse_h != nullptr, 0, s));
   j.fields_d = fdev;
-  j.starts_d = sdev;
+  j.starts_d = tab.starts;
   j.sfield = sfield.data();
-  j.sfield_d = sfdev;
-  j.fptr_d = fpdev;
+  j.sfield_d = tab.sfield;
+  j.fptr_d = tab.fptr;
   j.chunk = chunk;
-  j.mean_f = mf;
-  j.std_f = sf;
-  j.res_f = rf;
-  j.eps_f = ef;
-  j.places_d = pdev;
-  j.mse = mse;
-  j.eps_norm = en;
+  j.sinks.places_d = tab.places;
+  j.sinks.mse = tab.mse;
+  // per group: upload -> the pipeline -> download the sinks
   int prev_last = -1;
-  for (const Group& g : groups) {
+  for (const FieldGroup& g : groups) {
     const size_t ng = (size_t)(g.f1 - g.f0 + 1), goff = (size_t)g.f0 * felems;
-    FF_HIP(hipMemcpyAsync(fdev, fields + goff, ng * fb, hipMemcpyHostToDevice, s));
-    if (fo) {
-      FF_HIP(hipMemsetAsync(mf, 0, ng * fb, s));
-      FF_HIP(hipMemsetAsync(sf, 0, ng * fb, s));
-      if (ef) FF_HIP(hipMemsetAsync(ef, 0, ng * fb, s));
-      if (rf) FF_HIP(hipMemcpyAsync(rf, fdev, ng * fb, hipMemcpyDeviceToDevice, s));
-      if (g.f0 == prev_last) {
-        // the first field's earlier stamps were composited with the previous group: go on from those sums
-        FF_HIP(hipMemcpyAsync(mf, fo->mean + goff, fb, hipMemcpyHostToDevice, s));
-        FF_HIP(hipMemcpyAsync(sf, fo->stddev + goff, fb, hipMemcpyHostToDevice, s));
-        if (ef) FF_HIP(hipMemcpyAsync(ef, fo->epistemic + goff, fb, hipMemcpyHostToDevice, s));
-        if (rf) FF_HIP(hipMemcpyAsync(rf, fo->residual + goff, fb, hipMemcpyHostToDevice, s));
-      }
-    }
-    if (fit) {                                     // the r band of the resident fields as planes, once per group
-      st = launch_posfit_band_f64(fdev, (long)ng * F * F, nb, 2, f_img, s);
-      if (st == OK) st = launch_posfit_total_sq(f_img, (int)ng, (long)F * F, f_tot, s);
-      if (st != OK) {
-        cleanup();
-        return st;
-      }
-    }
-    FF_HIP(hipStreamSynchronize(s));               // the gather runs on the pipeline's copy stream
+    DV_HIP(hipMemcpyAsync(fdev, fields + goff, ng * fb, hipMemcpyHostToDevice, s));
+    for (ResultStack* r : stacks) DV_TRY(r->begin(r == &comp.residual ? fdev.get() : nullptr, ng * fb, s));
+    if (g.f0 == prev_last)
+      for (ResultStack* r : stacks) DV_TRY(r->carry(goff, fb, s));
+    if (fitting) DV_TRY(fit.begin(fdev, ng, c));
+    DV_HIP(hipStreamSynchronize(s));               // the gather runs on the pipeline's copy stream
     j.f0 = g.f0;
     j.row0 = g.k0 * chunk;
     j.N = std::min<int64_t>(N, g.k1 * chunk) - j.row0;
-    st = infer_pipelined(m, j);
-    if (st != OK) {
-      (void)hipStreamSynchronize(s);
-      cleanup();
-      return st;
-    }
+    DV_TRY(infer_pipelined(m, j));
     if (fo) {
-      FF_HIP(hipMemcpyAsync(fo->mean + goff, mf, ng * fb, hipMemcpyDeviceToHost, s));
-      FF_HIP(hipMemcpyAsync(fo->stddev + goff, sf, ng * fb, hipMemcpyDeviceToHost, s));
-      if (ef) FF_HIP(hipMemcpyAsync(fo->epistemic + goff, ef, ng * fb, hipMemcpyDeviceToHost, s));
-      if (rf) FF_HIP(hipMemcpyAsync(fo->residual + goff, rf, ng * fb, hipMemcpyDeviceToHost, s));
-      FF_HIP(hipStreamSynchronize(s));
+      for (ResultStack* r : stacks) DV_TRY(r->end(ng * fb, goff, s));
+      DV_HIP(hipStreamSynchronize(s));
     }
     prev_last = g.f1;
   }
-  if (mse) {
-    FF_HIP(hipMemcpyAsync(mse_h, mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipStreamSynchronize(s));
+  // download the per-stamp results
+  if (mse_h) {
+    DV_HIP(hipMemcpyAsync(mse_h, tab.mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));
   }
-  if (mo) {
-    FF_HIP(hipMemcpyAsync(mo->flux, c_flux, (size_t)N * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipMemcpyAsync(mo->flux_err, c_ferr, (size_t)N * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipMemcpyAsync(mo->shape, c_shape, (size_t)N * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipMemcpyAsync(mo->iters, c_iters, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipMemcpyAsync(mo->status, c_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipStreamSynchronize(s));
-  }
-  if (en) {
-    FF_HIP(hipMemcpyAsync(fo->eps_norm, en, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipStreamSynchronize(s));
-  }
-  if (fit) {
-    FF_HIP(hipMemcpyAsync(fo->shifts, f_shifts, (size_t)N * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipMemcpyAsync(fo->objective, f_obj, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipMemcpyAsync(fo->iters, f_iters, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipMemcpyAsync(fo->status, f_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
-    FF_HIP(hipStreamSynchronize(s));
-  }
-#undef FF_HIP
-  cleanup();
+  if (mo) DV_TRY(cat.download(*mo, N, nb, s));
+  if (fo) DV_TRY(mc.download(N, s));
+  if (fitting) DV_TRY(fit.download(*fo, N, s));
+  drain.dismiss();
   return prof_flush(m);
 }
 
@@ -5149,8 +5182,6 @@ int dv_field_set_open(dv_model* m, const double* fields, int32_t M, int32_t F, i
   const int nbuf = cumulative ? 4 : 6;
   const size_t nblk = (size_t)scene_field_mse_blocks((long)felems);
   const size_t need = (size_t)M * ((size_t)nbuf * fb + (nblk + 1) * sizeof(double));
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
   // what the passes allocate beside the set comes off the free memory first, as infer_fields_impl takes its pipeline
   // before its budget: the inference pipeline for the longest chunk a pass can make (unless the model already has it), the
   // detector's workspace for the fields of one launch (at most its 4 GiB cap; ~128 bytes per pixel), and 64 MiB for the
@@ -5159,18 +5190,14 @@ int dv_field_set_open(dv_model* m, const double* fields, int32_t M, int32_t F, i
   const size_t pipe_need = (m->pipe && m->pipe->cap >= m->Bc) ? 0 : 6 * img + 2 * (size_t)m->Bc * 3 * A.d * sizeof(float);
   const size_t det_need = std::min<size_t>((size_t)4 << 30, (size_t)M * F * F * 128);
   const size_t reserve = pipe_need + det_need + ((size_t)64 << 20);
-  size_t budget = free_b / 10 * 8;
-  budget = budget > reserve ? budget - reserve : 0;
-  if (const char* e = getenv("DV_FIELDS_GROUP_MB")) {
-    const long mb = atol(e);
-    if (mb > 0) budget = std::min(budget, (size_t)mb << 20);
-  }
+  size_t budget = 0;
+  DV_TRY(fields_budget(reserve, &budget));
   if (need > budget) {
     set_error("dv_field_set_open: %d resident %d-pixel fields with their %d buffers each need %zu bytes of device memory, "
               "%zu bytes are available for fields (a set is never split: open fewer fields per set)", M, F, nbuf, need, budget);
     return DV_E_NOMEM;
   }
-  dv_field_set* fs = new dv_field_set();
+  std::unique_ptr<dv_field_set> fs(new dv_field_set());
   fs->m = m;
   fs->M = M;
   fs->F = F;
@@ -5178,34 +5205,28 @@ int dv_field_set_open(dv_model* m, const double* fields, int32_t M, int32_t F, i
   fs->cumulative = cumulative != 0;
   fs->open = true;
   hipStream_t s = m->ctx->stream;
-  int st = DV_OK;
-#define FS_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); (void)hipStreamSynchronize(s); field_set_release(fs); delete fs; return st; } } while (0)
-  const size_t all = std::max<size_t>(1, (size_t)M * fb);
-  FS_HIP(hipMalloc((void**)&fs->work, all));
-  FS_HIP(hipMalloc((void**)&fs->next, all));
-  FS_HIP(hipMalloc((void**)&fs->mean, all));
-  FS_HIP(hipMalloc((void**)&fs->stddev, all));
-  if (!fs->cumulative) {
-    FS_HIP(hipMalloc((void**)&fs->base, all));
-    FS_HIP(hipMalloc((void**)&fs->fin, all));
-  }
-  FS_HIP(hipMalloc((void**)&fs->mse_part, std::max<size_t>(1, (size_t)M * nblk) * sizeof(double)));
-  FS_HIP(hipMalloc((void**)&fs->fmse, std::max<size_t>(1, (size_t)M) * sizeof(double)));
-  FS_HIP(hipMalloc((void**)&fs->fptr_d, ((size_t)M + 1) * sizeof(int)));
+  StreamDrain drain(s);                       // a failure waits for the stream before the set's buffers go
+  const size_t all = (size_t)M * felems;
+  for (DevBuf<double>* b : {&fs->work, &fs->next, &fs->mean, &fs->stddev}) DV_TRY(b->alloc(all));
+  if (!fs->cumulative)
+    for (DevBuf<double>* b : {&fs->base, &fs->fin}) DV_TRY(b->alloc(all));
+  DV_TRY(fs->mse_part.alloc((size_t)M * nblk));
+  DV_TRY(fs->fmse.alloc((size_t)M));
+  DV_TRY(fs->tab.fptr.alloc((size_t)M + 1));
   fs->fmse_h.assign((size_t)M, 0.0);
   if (M > 0) {
-    FS_HIP(hipMemcpyAsync(fs->work, fields, (size_t)M * fb, hipMemcpyHostToDevice, s));
-    FS_HIP(hipMemsetAsync(fs->mean, 0, (size_t)M * fb, s));
-    FS_HIP(hipMemsetAsync(fs->stddev, 0, (size_t)M * fb, s));
+    DV_HIP(hipMemcpyAsync(fs->work, fields, (size_t)M * fb, hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemsetAsync(fs->mean, 0, (size_t)M * fb, s));
+    DV_HIP(hipMemsetAsync(fs->stddev, 0, (size_t)M * fb, s));
     if (!fs->cumulative) {
-      FS_HIP(hipMemcpyAsync(fs->base, fs->work, (size_t)M * fb, hipMemcpyDeviceToDevice, s));
-      FS_HIP(hipMemcpyAsync(fs->fin, fs->work, (size_t)M * fb, hipMemcpyDeviceToDevice, s));
+      DV_HIP(hipMemcpyAsync(fs->base, fs->work, (size_t)M * fb, hipMemcpyDeviceToDevice, s));
+      DV_HIP(hipMemcpyAsync(fs->fin, fs->work, (size_t)M * fb, hipMemcpyDeviceToDevice, s));
     }
-    FS_HIP(hipStreamSynchronize(s));
+    DV_HIP(hipStreamSynchronize(s));
   }
-#undef FS_HIP
-  m->field_sets.push_back(fs);
-  *out = fs;
+  drain.dismiss();
+  m->field_sets.push_back(fs.get());
+  *out = fs.release();
   return DV_OK;
 }
 
@@ -5273,81 +5294,50 @@ int dv_field_set_pass(dv_field_set* fs, const int32_t* starts, const int32_t* pl
   InferPipe* pipe = nullptr;
   DV_TRY(pipe_get(m, chunk, &pipe, false));
   const long felems = (long)F * F * nb;
-  int st = OK;
-  auto cleanup = [&]() {
-    if (st != OK) {                                  // nothing may still read the set's tables
-      (void)hipStreamSynchronize(s);
-      if (pipe->s_out) (void)hipStreamSynchronize(pipe->s_out);
-      if (pipe->s_in) (void)hipStreamSynchronize(pipe->s_in);
-    }
-  };
-#define FP_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
-#define FP_TRY(call) do { st = (call); if (st != OK) { cleanup(); return st; } } while (0)
-  if ((size_t)N > fs->tab_cap) {                     // the per-stamp tables grow to the largest pass so far
-    for (int* p : {fs->starts_d, fs->places_d, fs->sfield_d}) (void)hipFree(p);
-    (void)hipFree(fs->mse_d);
-    fs->starts_d = fs->places_d = fs->sfield_d = nullptr;
-    fs->mse_d = nullptr;
-    fs->tab_cap = 0;
-    const size_t cap = std::max<size_t>((size_t)N, 1024);
-    FP_HIP(hipMalloc((void**)&fs->starts_d, cap * 2 * sizeof(int)));
-    FP_HIP(hipMalloc((void**)&fs->places_d, cap * 2 * sizeof(int)));
-    FP_HIP(hipMalloc((void**)&fs->sfield_d, cap * sizeof(int)));
-    FP_HIP(hipMalloc((void**)&fs->mse_d, cap * sizeof(double)));
-    fs->tab_cap = cap;
-  }
-  double* mse = fs->mse_d;
-  int *sdev = fs->starts_d, *pdev = fs->places_d, *sfdev = fs->sfield_d, *fpdev = fs->fptr_d;
-  const size_t sb = (size_t)N * 2 * sizeof(int);
-  FP_HIP(hipMemcpyAsync(sdev, starts, sb, hipMemcpyHostToDevice, s));
-  FP_HIP(hipMemcpyAsync(pdev, places, sb, hipMemcpyHostToDevice, s));
-  FP_HIP(hipMemcpyAsync(sfdev, sfield.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
-  FP_HIP(hipMemcpyAsync(fpdev, fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  StreamDrain drain(s, pipe->s_in, pipe->s_out);     // on a failure nothing may still read the set's tables
+  StampTables& tab = fs->tab;                        // they grow to the largest pass so far
+  DV_TRY(tab.upload(N, M, starts, places, sfield.data(), fptr32.data(), true, 1024, s));
   // the new working residual of every field that has stamps starts from the buffer the mode says
-  FP_TRY(launch_scene_fields_copy(fs->next, fs->cumulative ? fs->work : fs->base, fpdev, M, felems, s));
-  FP_HIP(hipStreamSynchronize(s));                   // the gather and the sinks run on the pipeline's copy streams
+  DV_TRY(launch_scene_fields_copy(fs->next, fs->cumulative ? fs->work : fs->base, tab.fptr, M, felems, s));
+  DV_HIP(hipStreamSynchronize(s));                   // the gather and the sinks run on the pipeline's copy streams
   PipeJob j;
   j.fields_d = fs->work;
   j.F = F;
   j.nb = nb;
-  j.f0 = 0;
   j.starts = starts;
-  j.starts_d = sdev;
+  j.starts_d = tab.starts;
   j.sfield = sfield.data();
-  j.sfield_d = sfdev;
-  j.fptr_d = fpdev;
-  j.row0 = 0;
+  j.sfield_d = tab.sfield;
+  j.fptr_d = tab.fptr;
   j.N = N;
   j.chunk = chunk;
   j.seed = seed;
-  j.mean_f = fs->mean;
-  j.std_f = fs->stddev;
-  j.res_f = fs->next;
-  j.res2_f = fs->cumulative ? nullptr : fs->fin;
-  j.places_d = pdev;
-  j.mse = mse;
-  FP_TRY(infer_pipelined(m, j));
+  j.sinks.mean_f = fs->mean;
+  j.sinks.std_f = fs->stddev;
+  j.sinks.res_f = fs->next;
+  j.sinks.res2_f = fs->cumulative ? nullptr : fs->fin.get();
+  j.sinks.places_d = tab.places;
+  j.sinks.mse = tab.mse;
+  DV_TRY(infer_pipelined(m, j));
   // field_mse of the working residual against its successor, then the successor takes its place (fields with stamps only)
-  FP_TRY(launch_scene_field_mse(fs->work, fs->next, fpdev, M, felems, fs->mse_part, fs->fmse, s));
-  FP_TRY(launch_scene_fields_copy(fs->work, fs->next, fpdev, M, felems, s));
+  DV_TRY(launch_scene_field_mse(fs->work, fs->next, tab.fptr, M, felems, fs->mse_part, fs->fmse, s));
+  DV_TRY(launch_scene_fields_copy(fs->work, fs->next, tab.fptr, M, felems, s));
   std::vector<double>& fm = fs->fmse_h;
-  FP_HIP(hipMemcpyAsync(mse_center, mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-  FP_HIP(hipMemcpyAsync(fm.data(), fs->fmse, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
-  FP_HIP(hipStreamSynchronize(s));
+  DV_HIP(hipMemcpyAsync(mse_center, tab.mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(fm.data(), fs->fmse, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipStreamSynchronize(s));
   for (int f = 0; f < M; ++f)
     if (fptr32[f + 1] > fptr32[f]) field_mse[f] = fm[f];
-#undef FP_TRY
-#undef FP_HIP
-  cleanup();
+  drain.dismiss();
   return prof_flush(m);
 }
 
 int dv_field_set_read(dv_field_set* fs, int32_t which, double* out) {
   DV_TRY(field_set_live(fs, "dv_field_set_read"));
-  const double* src = which == DV_FIELD_SET_WORK ? fs->work
-                      : which == DV_FIELD_SET_FINAL ? (fs->cumulative ? fs->work : fs->fin)
-                      : which == DV_FIELD_SET_MEAN ? fs->mean
-                      : which == DV_FIELD_SET_STDDEV ? fs->stddev : nullptr;
+  const double* src = which == DV_FIELD_SET_WORK ? fs->work.get()
+                      : which == DV_FIELD_SET_FINAL ? (fs->cumulative ? fs->work : fs->fin).get()
+                      : which == DV_FIELD_SET_MEAN ? fs->mean.get()
+                      : which == DV_FIELD_SET_STDDEV ? fs->stddev.get() : nullptr;
   if (!src || (fs->M > 0 && !out)) {
     set_error("dv_field_set_read: which = %d, expected DV_FIELD_SET_WORK, _FINAL, _MEAN or _STDDEV", which);
     return DV_E_INVALID;

@@ -209,45 +209,33 @@ int scene_measure(const float* mean_h, const float* stddev_h, int64_t N, int cs,
   if (N == 0) return OK;
   const size_t stamp = (size_t)cs * cs * nb;
   chunk = std::max<int64_t>(1, std::min<int64_t>({chunk, N, (int64_t)1 << 20}));
-  float *mean = nullptr, *sd = nullptr;
-  double *flux = nullptr, *ferr = nullptr, *shape = nullptr;
-  int *it = nullptr, *st = nullptr;
-  int rc = OK;
-  auto cleanup = [&]() {
-    (void)hipFree(mean); (void)hipFree(sd); (void)hipFree(flux); (void)hipFree(ferr); (void)hipFree(shape);
-    (void)hipFree(it); (void)hipFree(st);
-  };
-#define MS_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { rc = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return rc; } } while (0)
-  MS_HIP(hipMalloc((void**)&mean, (size_t)chunk * stamp * sizeof(float)));
+  DevBuf<float> mean, sd;
+  DevBuf<double> flux, ferr, shape;
+  DevBuf<int> it, st;
+  DV_TRY(mean.alloc((size_t)chunk * stamp));
   if (stddev_h) {
-    MS_HIP(hipMalloc((void**)&sd, (size_t)chunk * stamp * sizeof(float)));
-    MS_HIP(hipMalloc((void**)&ferr, (size_t)chunk * nb * sizeof(double)));
+    DV_TRY(sd.alloc((size_t)chunk * stamp));
+    DV_TRY(ferr.alloc((size_t)chunk * nb));
   }
-  MS_HIP(hipMalloc((void**)&flux, (size_t)chunk * nb * sizeof(double)));
-  MS_HIP(hipMalloc((void**)&shape, (size_t)chunk * 5 * sizeof(double)));
-  MS_HIP(hipMalloc((void**)&it, (size_t)chunk * sizeof(int)));
-  MS_HIP(hipMalloc((void**)&st, (size_t)chunk * sizeof(int)));
+  DV_TRY(flux.alloc((size_t)chunk * nb));
+  DV_TRY(shape.alloc((size_t)chunk * 5));
+  DV_TRY(it.alloc((size_t)chunk));
+  DV_TRY(st.alloc((size_t)chunk));
   for (int64_t base = 0; base < N; base += chunk) {
     const int n = (int)std::min<int64_t>(chunk, N - base);
-    MS_HIP(hipMemcpyAsync(mean, mean_h + (size_t)base * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(mean, mean_h + (size_t)base * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
     if (sd)
-      MS_HIP(hipMemcpyAsync(sd, stddev_h + (size_t)base * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    rc = launch_measure(mean, sd, n, cs, nb, band, sigma0, tol, max_iter, flux, ferr, shape, it, st, s);
-    if (rc != OK) {
-      cleanup();
-      return rc;
-    }
-    MS_HIP(hipMemcpyAsync(flux_h + (size_t)base * nb, flux, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(sd, stddev_h + (size_t)base * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
+    DV_TRY(launch_measure(mean, sd, n, cs, nb, band, sigma0, tol, max_iter, flux, ferr, shape, it, st, s));
+    DV_HIP(hipMemcpyAsync(flux_h + (size_t)base * nb, flux, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
     if (ferr)
-      MS_HIP(hipMemcpyAsync(flux_err_h + (size_t)base * nb, ferr, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    MS_HIP(hipMemcpyAsync(shape_h + (size_t)base * 5, shape, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
-    MS_HIP(hipMemcpyAsync(iters_h + base, it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    MS_HIP(hipMemcpyAsync(status_h + base, st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    MS_HIP(hipStreamSynchronize(s));               // the device buffers are reused by the next chunk
+      DV_HIP(hipMemcpyAsync(flux_err_h + (size_t)base * nb, ferr, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(shape_h + (size_t)base * 5, shape, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(iters_h + base, it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(status_h + base, st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));               // the device buffers are reused by the next chunk
   }
-  cleanup();
   return OK;
-#undef MS_HIP
 }
 
 }  // namespace dv

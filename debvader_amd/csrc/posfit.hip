@@ -409,17 +409,13 @@ struct PosfitPlan {
   std::vector<long> need;              // workspace doubles per galaxy
   std::vector<PosfitLaunch> launches;  // in galaxy order
   long work_max = 0;                   // the largest launch's workspace
-  PosfitGeom* geo_dev = nullptr;       // posfit_plan_upload
+  DevBuf<PosfitGeom> geo_dev;          // posfit_plan_upload
 };
 
 static const int PF_CHUNK = 512;                  // galaxies per launch
 static const long PF_WS_BUDGET = 128L << 20;      // workspace doubles per launch (1 GiB); no galaxy may need more
 
-void posfit_plan_destroy(PosfitPlan* p) {
-  if (!p) return;
-  (void)hipFree(p->geo_dev);
-  delete p;
-}
+void posfit_plan_destroy(PosfitPlan* p) { delete p; }
 
 // windows and workspace need of every galaxy; refuses what dv_scene_fit_shifts refuses
 int posfit_plan_create(int F, int cs, int N, const double* dist_h, const double* shifts_h, double bound, int max_iter,
@@ -536,7 +532,7 @@ long posfit_plan_work_doubles(const PosfitPlan* p) { return std::max(p->work_max
 int posfit_plan_upload(PosfitPlan* p, hipStream_t s) {
   const size_t n = p->geo.size();
   if (n == 0 || p->geo_dev) return OK;
-  DV_HIP(hipMalloc((void**)&p->geo_dev, n * sizeof(PosfitGeom)));
+  DV_TRY(p->geo_dev.alloc(n));
   DV_HIP(hipMemcpyAsync(p->geo_dev, p->geo.data(), n * sizeof(PosfitGeom), hipMemcpyHostToDevice, s));
   return OK;
 }
@@ -549,7 +545,7 @@ int posfit_plan_run(const PosfitPlan* p, int l0, int l1, const double* img_dev, 
   for (int l = l0; l < l1; ++l) {
     const PosfitLaunch& L = p->launches[l];
     hipLaunchKernelGGL(posfit_kernel, dim3((unsigned)L.n), dim3(PF_THREADS), 0, s, img_dev, p->F, stamps_dev, p->cs,
-                       p->geo_dev + L.base, work_dev, total_sq_dev, p->bound, p->max_iter, shifts_dev + 2 * (size_t)L.base,
+                       p->geo_dev.get() + L.base, work_dev, total_sq_dev, p->bound, p->max_iter, shifts_dev + 2 * (size_t)L.base,
                        objective_dev + L.base, iters_dev + L.base, status_dev + L.base);
     DV_HIP(hipGetLastError());
   }
@@ -614,6 +610,7 @@ int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* s
   const size_t STAMP_BUDGET = (size_t)64 << 20;   // stamp doubles per launch (512 MiB)
   PosfitPlan* plan = nullptr;
   DV_TRY(posfit_plan_create(F, cs, N, dist_h, shifts_h, bound, max_iter, &plan));
+  PosfitPlanOwner owner(plan);
   std::vector<int32_t> sfield((size_t)N);
   for (int m = 0; m < M; ++m)
     for (int64_t i = field_ptr[m]; i < field_ptr[m + 1]; ++i) sfield[i] = m;
@@ -626,65 +623,49 @@ int scene_fit_shifts_fields(const double* field_h, int M, int F, const double* s
     if (G < 1) {
       set_error("scene_fit_shifts: one %d-pixel field (%zu bytes) does not fit the %zu bytes of device memory available "
                 "for fields", F, img_elems * sizeof(double), budget_bytes);
-      posfit_plan_destroy(plan);
       return E_NOMEM;
     }
   }
   // galaxies per launch: at most PF_CHUNK, and at most STAMP_BUDGET doubles of stamps (a few for field-sized stamps)
   const int chunk = (int)std::min<size_t>({(size_t)N, (size_t)PF_CHUNK, std::max<size_t>(1, STAMP_BUDGET / stamp_elems)});
-  double *img = nullptr, *stamps = nullptr, *work = nullptr, *tot = nullptr, *out_s = nullptr, *out_j = nullptr;
-  int *out_it = nullptr, *out_st = nullptr;
-  PosfitGeom* dgeo = nullptr;
-  long work_cap = 0;
-  int st = OK;
-  auto cleanup = [&]() {
-    (void)hipFree(img); (void)hipFree(stamps); (void)hipFree(work); (void)hipFree(tot); (void)hipFree(out_s);
-    (void)hipFree(out_j); (void)hipFree(out_it); (void)hipFree(out_st); (void)hipFree(dgeo);
-    posfit_plan_destroy(plan);
-  };
-#define PF_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
-  PF_HIP(hipMalloc((void**)&img, G * img_elems * sizeof(double)));
-  PF_HIP(hipMalloc((void**)&tot, G * sizeof(double)));
-  PF_HIP(hipMalloc((void**)&stamps, (size_t)chunk * stamp_elems * sizeof(double)));
-  PF_HIP(hipMalloc((void**)&out_s, (size_t)chunk * 2 * sizeof(double)));
-  PF_HIP(hipMalloc((void**)&out_j, (size_t)chunk * sizeof(double)));
-  PF_HIP(hipMalloc((void**)&out_it, (size_t)chunk * sizeof(int)));
-  PF_HIP(hipMalloc((void**)&out_st, (size_t)chunk * sizeof(int)));
-  PF_HIP(hipMalloc((void**)&dgeo, (size_t)chunk * sizeof(PosfitGeom)));
+  DevBuf<double> img, tot, stamps, work, out_s, out_j;
+  DevBuf<int> out_it, out_st;
+  DevBuf<PosfitGeom> dgeo;
+  DV_TRY(img.alloc(G * img_elems));
+  DV_TRY(tot.alloc(G));
+  DV_TRY(stamps.alloc((size_t)chunk * stamp_elems));
+  DV_TRY(out_s.alloc((size_t)chunk * 2));
+  DV_TRY(out_j.alloc((size_t)chunk));
+  DV_TRY(out_it.alloc((size_t)chunk));
+  DV_TRY(out_st.alloc((size_t)chunk));
+  DV_TRY(dgeo.alloc((size_t)chunk));
   for (int g0 = 0; g0 < M; g0 += (int)G) {
     const int g1 = (int)std::min<size_t>((size_t)M, (size_t)g0 + G);
     const int ga = (int)field_ptr[g0], gb = (int)field_ptr[g1];
     if (ga == gb) continue;                        // no galaxy in these fields
-    PF_HIP(hipMemcpyAsync(img, field_h + (size_t)g0 * img_elems, (size_t)(g1 - g0) * img_elems * sizeof(double),
+    DV_HIP(hipMemcpyAsync(img, field_h + (size_t)g0 * img_elems, (size_t)(g1 - g0) * img_elems * sizeof(double),
                           hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(posfit_total_sq_kernel, dim3((unsigned)(g1 - g0)), dim3(PF_THREADS), 0, s, img, (long)img_elems, tot);
-    PF_HIP(hipGetLastError());
+    DV_HIP(hipGetLastError());
     const int l0 = posfit_plan_layout(plan, ga, gb, chunk, sfield.data(), g0, -1);
     for (int l = l0; l < (int)plan->launches.size(); ++l) {
       const int base = plan->launches[l].base, n = plan->launches[l].n;
-      const long w = plan->launches[l].work;
-      if (w > work_cap) {
-        (void)hipFree(work);
-        work = nullptr;
-        PF_HIP(hipMalloc((void**)&work, (size_t)std::max(w, 1L) * sizeof(double)));
-        work_cap = w;
-      }
-      PF_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)base * stamp_elems, (size_t)n * stamp_elems * sizeof(double),
+      DV_TRY(work.ensure((size_t)plan->launches[l].work));     // (grows to the largest launch so far)
+      DV_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)base * stamp_elems, (size_t)n * stamp_elems * sizeof(double),
                             hipMemcpyHostToDevice, s));
-      PF_HIP(hipMemcpyAsync(dgeo, plan->geo.data() + base, (size_t)n * sizeof(PosfitGeom), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(posfit_kernel, dim3((unsigned)n), dim3(PF_THREADS), 0, s, img, F, stamps, cs, dgeo, work, tot,
-                         bound, max_iter, out_s, out_j, out_it, out_st);
-      PF_HIP(hipGetLastError());
-      PF_HIP(hipMemcpyAsync(shifts_h + 2 * (size_t)base, out_s, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-      PF_HIP(hipMemcpyAsync(objective_h + base, out_j, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-      PF_HIP(hipMemcpyAsync(iters_h + base, out_it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-      PF_HIP(hipMemcpyAsync(status_h + base, out_st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-      PF_HIP(hipStreamSynchronize(s));             // the device buffers are reused by the next launch
+      DV_HIP(hipMemcpyAsync(dgeo, plan->geo.data() + base, (size_t)n * sizeof(PosfitGeom), hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(posfit_kernel, dim3((unsigned)n), dim3(PF_THREADS), 0, s, img, F, stamps, cs,
+                         dgeo, work, tot, bound, max_iter, out_s, out_j, out_it,
+                         out_st);
+      DV_HIP(hipGetLastError());
+      DV_HIP(hipMemcpyAsync(shifts_h + 2 * (size_t)base, out_s, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(objective_h + base, out_j, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(iters_h + base, out_it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(status_h + base, out_st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipStreamSynchronize(s));             // the device buffers are reused by the next launch
     }
   }
-  cleanup();
   return OK;
-#undef PF_HIP
 }
 
 }  // namespace dv

@@ -715,22 +715,18 @@ int scene_extract(const double* field_h, int F, int nb, const int32_t* starts_h,
     }
   }
   const size_t fb = (size_t)F * F * nb * sizeof(double), ob = (size_t)N * cs * cs * nb * sizeof(double);
-  double *field = nullptr, *out = nullptr;
-  int* starts = nullptr;
-  int st = OK;
-  auto cleanup = [&]() { (void)hipFree(field); (void)hipFree(out); (void)hipFree(starts); };
-#define SC_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { st = hip_fail(e__, #call, __FILE__, __LINE__); cleanup(); return st; } } while (0)
-  SC_HIP(hipMalloc((void**)&field, fb));
-  SC_HIP(hipMalloc((void**)&out, ob));
-  SC_HIP(hipMalloc((void**)&starts, (size_t)N * 2 * sizeof(int)));
-  SC_HIP(hipMemcpyAsync(field, field_h, fb, hipMemcpyHostToDevice, s));
-  SC_HIP(hipMemcpyAsync(starts, starts_h, (size_t)N * 2 * sizeof(int), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(scene_extract_kernel<double>, dim3((unsigned)N), dim3(256), 0, s, field, F, nb, starts, cs, out,
-                     (const int*)nullptr, 0);
-  SC_HIP(hipGetLastError());
-  SC_HIP(hipMemcpyAsync(out_h, out, ob, hipMemcpyDeviceToHost, s));
-  SC_HIP(hipStreamSynchronize(s));
-  cleanup();
+  DevBuf<double> field, out;
+  DevBuf<int> starts;
+  DV_TRY(field.alloc((size_t)F * F * nb));
+  DV_TRY(out.alloc((size_t)N * cs * cs * nb));
+  DV_TRY(starts.alloc((size_t)N * 2));
+  DV_HIP(hipMemcpyAsync(field, field_h, fb, hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(starts, starts_h, (size_t)N * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(scene_extract_kernel<double>, dim3((unsigned)N), dim3(256), 0, s, field, F, nb, starts, cs,
+                     out, (const int*)nullptr, 0);
+  DV_HIP(hipGetLastError());
+  DV_HIP(hipMemcpyAsync(out_h, out, ob, hipMemcpyDeviceToHost, s));
+  DV_HIP(hipStreamSynchronize(s));
   return OK;
 }
 
@@ -756,18 +752,14 @@ int scene_composite(double* field_h, int F, int nb, const double* stamps_h, cons
   const int CHUNK = 256;                       // objects per pass (coefficient buffer <= 256 * P*P*nb doubles)
   const size_t fb = (size_t)F * F * nb * sizeof(double);
   const size_t stamp_elems = (size_t)cs * cs * nb;
-  double *field = nullptr, *stamps = nullptr, *coef = nullptr;
-  SceneObj* objs = nullptr;
-  int* which = nullptr;
-  int st = OK;
-  auto cleanup = [&]() {
-    (void)hipFree(field); (void)hipFree(stamps); (void)hipFree(coef); (void)hipFree(objs); (void)hipFree(which);
-  };
-  SC_HIP(hipMalloc((void**)&field, fb));
-  SC_HIP(hipMalloc((void**)&stamps, (size_t)CHUNK * stamp_elems * sizeof(double)));
-  SC_HIP(hipMalloc((void**)&objs, (size_t)CHUNK * sizeof(SceneObj)));
-  SC_HIP(hipMalloc((void**)&which, (size_t)CHUNK * sizeof(int)));
-  SC_HIP(hipMemcpyAsync(field, field_h, fb, hipMemcpyHostToDevice, s));
+  DevBuf<double> field, stamps, coef;     // (coef: allocated by the first chunk that has a fractional position)
+  DevBuf<SceneObj> objs;
+  DevBuf<int> which;
+  DV_TRY(field.alloc((size_t)F * F * nb));
+  DV_TRY(stamps.alloc((size_t)CHUNK * stamp_elems));
+  DV_TRY(objs.alloc((size_t)CHUNK));
+  DV_TRY(which.alloc((size_t)CHUNK));
+  DV_HIP(hipMemcpyAsync(field, field_h, fb, hipMemcpyHostToDevice, s));
   SceneObj hobj[256];
   int hwhich[256];
   for (int base = 0; base < N; base += CHUNK) {
@@ -777,7 +769,6 @@ int scene_composite(double* field_h, int F, int nb, const double* stamps_h, cons
       const double px = pos_h[2 * (base + i)], py = pos_h[2 * (base + i) + 1];
       if (!(px == px) || !(py == py) || px > 1e9 || px < -1e9 || py > 1e9 || py < -1e9) {
         set_error("scene_composite: object %d has a non-finite position", base + i);
-        cleanup();
         return E_INVALID;
       }
       SceneObj o;
@@ -789,26 +780,24 @@ int scene_composite(double* field_h, int F, int nb, const double* stamps_h, cons
       if (!integer) hwhich[nsub++] = i;
       hobj[i] = o;
     }
-    SC_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)base * stamp_elems, (size_t)n * stamp_elems * sizeof(double),
+    DV_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)base * stamp_elems, (size_t)n * stamp_elems * sizeof(double),
                           hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(objs, hobj, (size_t)n * sizeof(SceneObj), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(objs, hobj, (size_t)n * sizeof(SceneObj), hipMemcpyHostToDevice, s));
     if (nsub > 0) {
-      if (!coef) SC_HIP(hipMalloc((void**)&coef, (size_t)CHUNK * P * P * nb * sizeof(double)));
-      SC_HIP(hipMemcpyAsync(which, hwhich, (size_t)nsub * sizeof(int), hipMemcpyHostToDevice, s));
+      DV_TRY(coef.ensure((size_t)CHUNK * P * P * nb));
+      DV_HIP(hipMemcpyAsync(which, hwhich, (size_t)nsub * sizeof(int), hipMemcpyHostToDevice, s));
       hipLaunchKernelGGL(scene_prefilter_kernel, dim3(nsub), dim3(256), 0, s, stamps, which, cs, nb, coef);
-      SC_HIP(hipGetLastError());
+      DV_HIP(hipGetLastError());
     }
     const long total = (long)F * F * nb;
-    hipLaunchKernelGGL(scene_composite_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, field, F, nb,
-                       stamps, coef, objs, n, cs, po, sign);
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipStreamSynchronize(s));           // hobj / hwhich are reused by the next chunk
+    hipLaunchKernelGGL(scene_composite_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, field, F,
+                       nb, stamps, coef, objs, n, cs, po, sign);
+    DV_HIP(hipGetLastError());
+    DV_HIP(hipStreamSynchronize(s));           // hobj / hwhich are reused by the next chunk
   }
-  SC_HIP(hipMemcpyAsync(field_h, field, fb, hipMemcpyDeviceToHost, s));
-  SC_HIP(hipStreamSynchronize(s));
-  cleanup();
+  DV_HIP(hipMemcpyAsync(field_h, field, fb, hipMemcpyDeviceToHost, s));
+  DV_HIP(hipStreamSynchronize(s));
   return OK;
-#undef SC_HIP
 }
 
 }  // namespace dv
