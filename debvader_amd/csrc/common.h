@@ -294,6 +294,27 @@ int launch_measure(const float* mean_dev, const float* stddev_dev, int n, int cs
 int scene_measure(const float* mean_h, const float* stddev_h, int64_t N, int cs, int nb, int band, double sigma0, double tol,
                   int max_iter, double* flux_h, double* flux_err_h, double* shape_h, int32_t* iters_h, int32_t* status_h,
                   int64_t chunk, hipStream_t s);
+// Monte-Carlo catalogue (measure.hip): every sample stamp of a decoder pass measured without a stddev stamp into
+// scratch rows, the rows folded per galaxy (Welford, ascending sample order) into means and standard deviations of the nb
+// fluxes and of the 8 shape quantities {row, col, Mrr, Mrc, Mcc, sigma, e1, e2}.  McScratch: the rows of one pass (device).
+// McState: the results, which also carry the running state between passes ([.][nb], [.][nb], [.][8], [.][8], [.]); the
+// per-sample rows [.][S][nb], [.][S][5], [.][S] are given together or not at all.  launch_measure_mc_samples: `rows` stamps
+// of a pass.  launch_measure_mc_fold: the pass's n galaxies x reps samples (row r * n + g = sample k0 + r of galaxy g) into
+// rows row0 .. of the state; the pass with the last sample writes the standard deviations.  scene_measure_mc: host samples
+// [S][N][cs][cs][nb] in, host results (an McState of host pointers) out, at most `chunk` galaxies on the device at a time.
+struct McScratch { double *flux, *shape; int *iters, *status; };
+struct McState {
+  double *flux_mean, *flux_std, *shape_mean, *shape_std;
+  int* n_ok;
+  double *sample_flux, *sample_shape;
+  int* sample_status;
+};
+int launch_measure_mc_samples(const float* pass_dev, int rows, int cs, int nb, int band, double sigma0, double tol,
+                              int max_iter, const McScratch& w, hipStream_t s);
+int launch_measure_mc_fold(const McScratch& w, int n, int reps, int k0, int S, int nb, const McState& st, int64_t row0,
+                           hipStream_t s);
+int scene_measure_mc(const float* samples_h, int S, int64_t N, int cs, int nb, int band, double sigma0, double tol,
+                     int max_iter, const McState& out_h, int64_t chunk, hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

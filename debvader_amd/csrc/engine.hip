@@ -3057,6 +3057,15 @@ struct PipeJob {
     int band = 0, max_iter = 0;
     double sigma0 = 0.0, tol = 0.0;
   } ms;
+  // Monte-Carlo catalogue (dv_infer_fields_measure_mc): every decoder pass of the Monte-Carlo stage is measured
+  // where it lies and folded into per-galaxy means and standard deviations; st.flux_mean decides (needs mc_samples > 0).  The
+  // per-pixel statistics of the stage have no reader in that call and are not taken
+  struct MeasureMc {
+    McState st{};                      // device, rows = global stamp numbers; the running state between passes
+    McScratch w{};                     // device: the rows of one decoder pass (the workspace capacity)
+    int band = 0, max_iter = 0;
+    double sigma0 = 0.0, tol = 0.0;
+  } mcm;
 };
 
 // The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
@@ -3065,7 +3074,11 @@ struct PipeJob {
 // the per-stamp statistics fold the samples in order.  A handful of objects with 100 samples each - the per-field use of the
 // reference - is one or two decoder passes instead of 100.  Leaves the mean in m->gA and the standard deviation in m->gB
 // (the two gradient ping-pong buffers, unused during inference).
-static int mc_decode_stats(dv_model* m, int nb, int nsamples, uint64_t seed, unsigned row0) {
+// mm: the per-pass hook of the Monte-Carlo catalogue - every pass is measured and folded on the main stream before the next
+// pass overwrites m->loc.  pixel_stats = false (with a hook only): nothing reads the per-pixel statistics, their launches
+// are left out and gA / gB keep what they held.
+static int mc_decode_stats(dv_model* m, int nb, int nsamples, uint64_t seed, unsigned row0,
+                           const PipeJob::MeasureMc* mm = nullptr, bool pixel_stats = true) {
   const Arch& A = m->A;
   hipStream_t s = m->ctx->stream;
   const size_t stamp = (size_t)A.H * A.H * A.C;
@@ -3081,12 +3094,17 @@ static int mc_decode_stats(dv_model* m, int nb, int nsamples, uint64_t seed, uns
     // normalise=True: the recipe is np.std(deblend(net, [stamp]*100, normalise=True)[0], axis=0), i.e. the statistics
     // of the DENORMALISED means - each decoded pass goes back through sinh(arctanh(.)) before it is folded in
     if (m->normalise) DV_TRY(launch_normalise(m->loc, (long)nb * reps * stamp, true, s));
+    if (mm) {
+      DV_TRY(launch_measure_mc_samples(m->loc, nb * reps, A.H, A.C, mm->band, mm->sigma0, mm->tol, mm->max_iter, mm->w, s));
+      DV_TRY(launch_measure_mc_fold(mm->w, nb, reps, k, nsamples, A.C, mm->st, (int64_t)row0, s));
+    }
+    if (!pixel_stats) continue;
     if (reps > 1)
       DV_TRY(launch_welford_update_multi(m->loc, mean, m2, (long)nb * stamp, reps, k, s));
     else
       DV_TRY(launch_welford_update(m->loc, mean, m2, ((long)(nb * stamp) + 3) & ~3L, k, s));   // buffers carry slack
   }
-  DV_TRY(launch_welford_finish(m2, ((long)(nb * stamp) + 3) & ~3L, nsamples, s));
+  if (pixel_stats) DV_TRY(launch_welford_finish(m2, ((long)(nb * stamp) + 3) & ~3L, nsamples, s));
   return OK;
 }
 
@@ -3213,7 +3231,8 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
         DV_TRY(bn_prepare(m, p->din[b], nullptr, 0, nb, nb, false, false));
         DV_TRY(encoder_forward(m, p->din[b], nullptr, 0, nb, false));
       }
-      DV_TRY(mc_decode_stats(m, nb, j.mc_samples, j.mc_seed, (unsigned)r));
+      const bool mcm = j.mcm.st.flux_mean != nullptr;
+      DV_TRY(mc_decode_stats(m, nb, j.mc_samples, j.mc_seed, (unsigned)r, mcm ? &j.mcm : nullptr, !mcm));
     }
     if (trace) DV_HIP(hipEventRecord(tev[6 * k + 3], s));
     DV_HIP(hipEventRecord(p->ev_comp[b], s));
@@ -3714,6 +3733,39 @@ int dv_scene_measure(dv_ctx* c, const float* mean, const float* stddev, int64_t 
   const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 2 / per_stamp);
   return scene_measure(mean, stddev, N, cs, nb, p->band, p->sigma0, p->tol, p->max_iter, flux, flux_err, shape, iters,
                        status, chunk, c->stream);
+}
+
+int dv_scene_measure_mc(dv_ctx* c, const float* samples, int32_t S, int64_t N, int32_t cs, int32_t nb,
+                        const dv_measure_params* p, double* flux_mean, double* flux_std, double* shape_mean,
+                        double* shape_std, int32_t* n_ok, double* sample_flux, double* sample_shape, int32_t* sample_status) {
+  const char* who = "dv_scene_measure_mc";
+  if (!c || !p) return DV_E_INVALID;
+  DV_TRY(measure_check(who, cs, nb, p->band, p->sigma0, p->tol, p->max_iter));   // before any GPU work
+  if (S < 1) {
+    set_error("%s: %d Monte-Carlo samples given, at least 1 is needed", who, S);
+    return DV_E_INVALID;
+  }
+  if (N < 0 || (N > 0 && (!samples || !flux_mean || !flux_std || !shape_mean || !shape_std || !n_ok))) {
+    set_error("%s: samples and the Monte-Carlo outputs flux_mean, flux_std, shape_mean, shape_std and n_ok must all be given", who);
+    return DV_E_INVALID;
+  }
+  const int given = (sample_flux != nullptr) + (sample_shape != nullptr) + (sample_status != nullptr);
+  if (given != 0 && given != 3) {
+    set_error("%s: the per-sample outputs sample_flux, sample_shape and sample_status go together (all given or all null)", who);
+    return DV_E_INVALID;
+  }
+  if (N == 0) return DV_OK;
+  DV_HIP(hipSetDevice(c->device));
+  // galaxies per chunk: half of free device memory holds a chunk's S sample stamps per galaxy, their scratch rows, the
+  // results and (when asked for) the per-sample rows
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t row = ((size_t)nb + 5) * sizeof(double) + 2 * sizeof(int);
+  const size_t per_galaxy = (size_t)S * ((size_t)cs * cs * nb * sizeof(float) + row * (given ? 2 : 1)) +
+                            (2 * (size_t)nb + 16) * sizeof(double) + sizeof(int);
+  const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 2 / per_galaxy);
+  const McState out{flux_mean, flux_std, shape_mean, shape_std, n_ok, sample_flux, sample_shape, sample_status};
+  return scene_measure_mc(samples, S, N, cs, nb, p->band, p->sigma0, p->tol, p->max_iter, out, chunk, c->stream);
 }
 
 int dv_scene_detect(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, const dv_detect_params* p,
@@ -4527,6 +4579,11 @@ struct MeasureOut {                 // the catalogue of dv_infer_fields_measure,
   double* mse = nullptr;            // [N], optional: mse_center of the catalogue-only call (no FieldsOut to carry it)
 };
 
+struct MeasureMcOut {               // the Monte-Carlo catalogue of dv_infer_fields_measure_mc, host, rows = global stamp numbers
+  McState st{};                     // the per-sample rows given together or not at all
+  int nsamples = 0;
+};
+
 // the refusals every field-sourced call takes before any GPU work, and the two tables it works from: sfield[i] = the field
 // of stamp i, fptr32 = field_ptr as the kernels read it.  places: the placements of a compositing call, or null.
 static int fields_tables(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, int F, int nb,
@@ -4787,10 +4844,57 @@ struct CatalogueStage {             // fluxes, errors and adaptive moments of ev
   }
 };
 
+struct CatalogueMcStage {           // means and standard deviations over the Monte-Carlo decodes of every stamp (7k)
+  DevBuf<double> fmean, fstd, smean, sstd, kflux, kshape, wflux, wshape;
+  DevBuf<int> nok, kst, wit, wst;
+  // the results (and running state) of a stamp; with the per-sample rows, S rows of nb fluxes, 5 moments and a status more
+  static size_t bytes_per_stamp(int nb, int S, bool keep) {
+    return (2 * (size_t)nb + 16) * sizeof(double) + sizeof(int) +
+           (keep ? (size_t)S * (((size_t)nb + 5) * sizeof(double) + sizeof(int)) : 0);
+  }
+  // the scratch rows of one decoder pass: at most the workspace capacity
+  static size_t bytes_fixed(int Bc, int nb) { return (size_t)Bc * (((size_t)nb + 5) * sizeof(double) + 2 * sizeof(int)); }
+  int alloc(int64_t N, int nb, int S, bool keep, int Bc) {
+    for (DevBuf<double>* b : {&fmean, &fstd}) DV_TRY(b->alloc((size_t)N * nb));
+    for (DevBuf<double>* b : {&smean, &sstd}) DV_TRY(b->alloc((size_t)N * 8));
+    DV_TRY(nok.alloc((size_t)N));
+    if (keep) {
+      DV_TRY(kflux.alloc((size_t)N * S * nb));
+      DV_TRY(kshape.alloc((size_t)N * S * 5));
+      DV_TRY(kst.alloc((size_t)N * S));
+    }
+    DV_TRY(wflux.alloc((size_t)Bc * nb));
+    DV_TRY(wshape.alloc((size_t)Bc * 5));
+    DV_TRY(wit.alloc((size_t)Bc));
+    return wst.alloc((size_t)Bc);
+  }
+  void bind(PipeJob::MeasureMc& q, const dv_measure_params& par) const {
+    q.st = McState{fmean, fstd, smean, sstd, nok, kflux, kshape, kst};
+    q.w = McScratch{wflux, wshape, wit, wst};
+    q.band = par.band; q.max_iter = par.max_iter; q.sigma0 = par.sigma0; q.tol = par.tol;
+  }
+  int download(const MeasureMcOut& o, int64_t N, int nb, hipStream_t s) {
+    const size_t n = (size_t)N, S = (size_t)o.nsamples;
+    DV_HIP(hipMemcpyAsync(o.st.flux_mean, fmean, n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(o.st.flux_std, fstd, n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(o.st.shape_mean, smean, n * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(o.st.shape_std, sstd, n * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(o.st.n_ok, nok, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (o.st.sample_flux) {
+      DV_HIP(hipMemcpyAsync(o.st.sample_flux, kflux, n * S * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(o.st.sample_shape, kshape, n * S * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(o.st.sample_status, kst, n * S * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    DV_HIP(hipStreamSynchronize(s));
+    return DV_OK;
+  }
+};
+
 // j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
 // the device side and the rows are filled in here
 static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
-                             const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr) {
+                             const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr,
+                             const MeasureMcOut* mco = nullptr) {
   // check
   const double* fields = j.fields;
   const int F = j.F, nb = j.nb;
@@ -4813,7 +4917,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   double* mse_h = fo ? fo->mse : mo ? mo->mse : nullptr;
   DevBuf<double> fdev;                                // the resident group of source fields
   StampTables tab;
-  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat;   // (a stage that does not run stays empty)
+  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc;   // (a stage that does not run stays empty)
   ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
   if (fitting) DV_TRY(fit.make_plan(*fo, c, sfield.data()));
   size_t per_field = fb, reserve = StampTables::bytes((size_t)N, (size_t)M);
@@ -4826,6 +4930,9 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     reserve += fit.bytes_fixed(c);
   }
   if (mo) reserve += (size_t)N * CatalogueStage::bytes_per_stamp(nb);
+  const bool keep_samples = mco && mco->st.sample_flux;
+  if (mco)
+    reserve += (size_t)N * CatalogueMcStage::bytes_per_stamp(nb, mco->nsamples, keep_samples) + CatalogueMcStage::bytes_fixed(m->Bc, nb);
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
@@ -4850,6 +4957,10 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (mo) {
     DV_TRY(cat.alloc(N, nb));
     cat.bind(j.ms, mo->par);
+  }
+  if (mco) {
+    DV_TRY(catmc.alloc(N, nb, mco->nsamples, keep_samples, m->Bc));
+    catmc.bind(j.mcm, mo->par);
   }
   if (fitting) {
     DV_TRY(fit.alloc(*fo, c, gmax, groups));
@@ -4890,6 +5001,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     DV_HIP(hipStreamSynchronize(s));
   }
   if (mo) DV_TRY(cat.download(*mo, N, nb, s));
+  if (mco) DV_TRY(catmc.download(*mco, N, nb, s));
   if (fo) DV_TRY(mc.download(N, s));
   if (fitting) DV_TRY(fit.download(*fo, N, s));
   drain.dismiss();
@@ -5035,6 +5147,67 @@ int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_
   fo.mse = mse_center;
   fo.places = places;
   return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo);
+}
+
+// ---- the Monte-Carlo catalogue beside it: dv_infer_fields_measure plus means and standard deviations of
+// the measurement over nsamples stochastic decodes of every galaxy; no epistemic field, no eps_norm
+int dv_infer_fields_measure_mc(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                               const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed, uint64_t mc_seed,
+                               int32_t nsamples, const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                               double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                               int32_t* iters, int32_t* status, double* flux_mean, double* flux_std, double* shape_mean,
+                               double* shape_std, int32_t* n_ok, double* sample_flux, double* sample_shape,
+                               int32_t* sample_status) {
+  const char* who = "dv_infer_fields_measure_mc";
+  if (!m || !params) return DV_E_INVALID;
+  DV_TRY(measure_check(who, m->A.H, nb, params->band, params->sigma0, params->tol, params->max_iter));
+  if (nsamples < 1) {
+    set_error("%s: %d Monte-Carlo samples asked for, at least 1 is needed", who, nsamples);
+    return DV_E_INVALID;
+  }
+  if (N > 0 && (!flux || !flux_err || !shape || !iters || !status)) {
+    set_error("%s: flux, flux_err, shape, iters and status must all be given", who);
+    return DV_E_INVALID;
+  }
+  if (N > 0 && (!flux_mean || !flux_std || !shape_mean || !shape_std || !n_ok)) {
+    set_error("%s: the Monte-Carlo outputs flux_mean, flux_std, shape_mean, shape_std and n_ok must all be given", who);
+    return DV_E_INVALID;
+  }
+  const int given = (sample_flux != nullptr) + (sample_shape != nullptr) + (sample_status != nullptr);
+  if (given != 0 && given != 3) {
+    set_error("%s: the per-sample outputs sample_flux, sample_shape and sample_status go together (all given or all null)", who);
+    return DV_E_INVALID;
+  }
+  const bool with_fields = mean_fields || stddev_fields || residual_fields;
+  if (with_fields && ((M > 0 && (!mean_fields || !stddev_fields)) || (N > 0 && !places))) {
+    set_error("%s: mean_fields, stddev_fields and places go together (residual_fields is optional beside them); the "
+              "catalogue-only call passes all three fields as null", who);
+    return DV_E_INVALID;
+  }
+  MeasureOut mo;
+  mo.par = *params;
+  mo.flux = flux;
+  mo.flux_err = flux_err;
+  mo.shape = shape;
+  mo.iters = iters;
+  mo.status = status;
+  MeasureMcOut mco;
+  mco.st = McState{flux_mean, flux_std, shape_mean, shape_std, n_ok, sample_flux, sample_shape, sample_status};
+  mco.nsamples = nsamples;
+  PipeJob j = fields_job(fields, F, nb, starts, seed);
+  j.mc_samples = nsamples;
+  j.mc_seed = mc_seed;
+  if (!with_fields) {
+    mo.mse = mse_center;
+    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, &mco);
+  }
+  FieldsOut fo;
+  fo.mean = mean_fields;
+  fo.stddev = stddev_fields;
+  fo.residual = residual_fields;
+  fo.mse = mse_center;
+  fo.places = places;
+  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, &mco);
 }
 
 // the refusals of the two Monte-Carlo forms, before any GPU work

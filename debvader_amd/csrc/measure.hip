@@ -50,36 +50,36 @@ __device__ __forceinline__ void ms_block_sum(double (&v)[K], double* s_red) {
 
 __device__ __forceinline__ bool ms_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN
 
-// mean / stddev: stamps [n][cs][cs][nb] float32 (stddev and flux_err null together); outputs indexed by stamp
-__global__ __launch_bounds__(MS_THREADS) void measure_kernel(const float* __restrict__ mean, const float* __restrict__ stddev,
-                                                             int cs, int nb, int band, double sigma0, double tol,
-                                                             int max_iter, double* __restrict__ flux,
-                                                             double* __restrict__ flux_err, double* __restrict__ shape,
-                                                             int* __restrict__ iters, int* __restrict__ status) {
-  extern __shared__ double s_mem[];
+// The measurement of one stamp by its workgroup: P / S the stamp's mean / stddev [cs][cs][nb] float32 (S null: no flux_err),
+// the output pointers at the stamp's own rows.  ERR = false leaves the sigma^2 sums out altogether (the Monte-Carlo samples
+// have no stddev stamp); the sums that remain are reduced in the same order, so the results have the same bits.
+template <bool ERR>
+__device__ __forceinline__ void measure_stamp(const float* __restrict__ P, const float* __restrict__ S, int cs, int nb,
+                                              int band, double sigma0, double tol, int max_iter, double* __restrict__ flux,
+                                              double* __restrict__ flux_err, double* __restrict__ sh,
+                                              int* __restrict__ iters, int* __restrict__ status, double* s_mem) {
   const int npix = cs * cs;
   double* plane = s_mem;                    // [cs][cs]
   double* s_red = s_mem + npix;             // [MS_RED]
-  const long gi = blockIdx.x;
-  const float* P = mean + gi * npix * nb;
-  const float* S = stddev ? stddev + gi * npix * nb : nullptr;
 
   // one pass over the stamp: the band plane to LDS, the per-band sums in registers
-  double f[MS_MAX_BANDS], q[MS_MAX_BANDS];
+  double f[MS_MAX_BANDS], q[ERR ? MS_MAX_BANDS : 1];
 #pragma unroll
-  for (int b = 0; b < MS_MAX_BANDS; ++b) f[b] = q[b] = 0.0;
+  for (int b = 0; b < MS_MAX_BANDS; ++b) f[b] = 0.0;
+#pragma unroll
+  for (int b = 0; b < (ERR ? MS_MAX_BANDS : 1); ++b) q[b] = 0.0;
   for (int e = threadIdx.x; e < npix; e += MS_THREADS) {
     const float* p = P + (long)e * nb;
-    const float* sp = S ? S + (long)e * nb : nullptr;
+    const float* sp = ERR && S ? S + (long)e * nb : nullptr;
 #pragma unroll
     for (int b = 0; b < MS_MAX_BANDS; ++b) {
       if (b < nb) {
         const double v = (double)p[b];
         f[b] += v;
         if (b == band) plane[e] = v;
-        if (sp) {
+        if (ERR && sp) {
           const double sv = (double)sp[b];
-          q[b] += sv * sv;
+          q[ERR ? b : 0] += sv * sv;
         }
       }
     }
@@ -87,11 +87,17 @@ __global__ __launch_bounds__(MS_THREADS) void measure_kernel(const float* __rest
 #pragma unroll
   for (int b = 0; b < MS_MAX_BANDS; ++b) {
     if (b < nb) {                           // (nb is uniform: every thread takes the same barriers)
-      double a[2] = {f[b], q[b]};
-      ms_block_sum<2>(a, s_red);
-      if (threadIdx.x == 0) {
-        flux[gi * nb + b] = a[0];
-        if (flux_err) flux_err[gi * nb + b] = sqrt(a[1]);
+      if (ERR) {
+        double a[2] = {f[b], q[ERR ? b : 0]};
+        ms_block_sum<2>(a, s_red);
+        if (threadIdx.x == 0) {
+          flux[b] = a[0];
+          if (flux_err) flux_err[b] = sqrt(a[1]);
+        }
+      } else {
+        double a[1] = {f[b]};
+        ms_block_sum<1>(a, s_red);
+        if (threadIdx.x == 0) flux[b] = a[0];
       }
     }
   }
@@ -141,14 +147,112 @@ __global__ __launch_bounds__(MS_THREADS) void measure_kernel(const float* __rest
     if (step < tol && dM < tol) { st = 0; break; }
   }
   if (threadIdx.x == 0) {
-    double* sh = shape + gi * 5;
     sh[0] = r0;
     sh[1] = c0;
     sh[2] = Mrr;
     sh[3] = Mrc;
     sh[4] = Mcc;
-    iters[gi] = it;
-    status[gi] = st;
+    *iters = it;
+    *status = st;
+  }
+}
+
+// mean / stddev: stamps [n][cs][cs][nb] float32 (stddev and flux_err null together); outputs indexed by stamp
+__global__ __launch_bounds__(MS_THREADS) void measure_kernel(const float* __restrict__ mean, const float* __restrict__ stddev,
+                                                             int cs, int nb, int band, double sigma0, double tol,
+                                                             int max_iter, double* __restrict__ flux,
+                                                             double* __restrict__ flux_err, double* __restrict__ shape,
+                                                             int* __restrict__ iters, int* __restrict__ status) {
+  extern __shared__ double s_mem[];
+  const long gi = blockIdx.x;
+  const long stamp = (long)cs * cs * nb;
+  measure_stamp<true>(mean + gi * stamp, stddev ? stddev + gi * stamp : nullptr, cs, nb, band, sigma0, tol, max_iter,
+                      flux + gi * nb, flux_err ? flux_err + gi * nb : nullptr, shape + gi * 5, iters + gi, status + gi, s_mem);
+}
+
+// ---- Monte-Carlo catalogue: every decode of every galaxy measured, the rows folded per galaxy ------------------
+// One decoder pass as it lies in HBM: `rows` sample stamps [rows][cs][cs][nb], one workgroup each, measured without a stddev
+// stamp into the pass's scratch rows.  The bits are measure_kernel's for the same stamp.
+__global__ __launch_bounds__(MS_THREADS) void measure_mc_sample_kernel(const float* __restrict__ pass, int cs, int nb, int band,
+                                                                       double sigma0, double tol, int max_iter,
+                                                                       double* __restrict__ flux, double* __restrict__ shape,
+                                                                       int* __restrict__ iters, int* __restrict__ status) {
+  extern __shared__ double s_mem[];
+  const long r = blockIdx.x;
+  measure_stamp<false>(pass + r * cs * cs * nb, nullptr, cs, nb, band, sigma0, tol, max_iter, flux + r * nb, nullptr,
+                       shape + r * 5, iters + r, status + r, s_mem);
+}
+
+// Welford's recurrence on one quantity, every operation rounded on its own
+__device__ __forceinline__ void mc_fold(double x, double n, double& mean, double& m2) {
+#pragma clang fp contract(off)
+  const double d = x - mean;
+  mean += d / n;
+  m2 += d * (x - mean);
+}
+
+// Folds the scratch rows of one pass - row r * n + g is sample k0 + r of galaxy g of the pass's n galaxies - into the running
+// state of those galaxies, in ascending sample order: (mean, M2) of the nb fluxes over all samples, (mean, M2) of the 8 shape
+// quantities {row, col, Mrr, Mrc, Mcc, sigma, e1, e2} over the accepted samples (status 0, det > 0, tr > 0), counted in n_ok.
+// The state lives in the output arrays themselves (M2 in the std arrays), whose pointers stand at the pass's first galaxy;
+// k0 = 0 starts it, finish (the pass that holds sample S - 1) turns M2 into std = sqrt(M2 / n), NaN where n_ok = 0.  One
+// thread per galaxy: a galaxy's result depends on nothing but its own samples; no atomics.
+__global__ __launch_bounds__(256) void measure_mc_fold_kernel(const double* __restrict__ sflux, const double* __restrict__ sshape,
+                                                              const int* __restrict__ sstatus, int n, int reps, int k0, int S,
+                                                              int nb, int finish, double* __restrict__ fmean,
+                                                              double* __restrict__ fstd, double* __restrict__ smean,
+                                                              double* __restrict__ sstd, int* __restrict__ n_ok,
+                                                              double* __restrict__ sample_flux,
+                                                              double* __restrict__ sample_shape,
+                                                              int* __restrict__ sample_status) {
+#pragma clang fp contract(off)
+  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  for (int b = 0; b < nb; ++b) {
+    double mean = k0 ? fmean[g * nb + b] : 0.0, m2 = k0 ? fstd[g * nb + b] : 0.0;
+    for (int r = 0; r < reps; ++r) {
+      const double x = sflux[((long)r * n + g) * nb + b];
+      mc_fold(x, (double)(k0 + r + 1), mean, m2);
+      if (sample_flux) sample_flux[(g * S + k0 + r) * nb + b] = x;
+    }
+    fmean[g * nb + b] = mean;
+    fstd[g * nb + b] = finish ? __dsqrt_rn(m2 / (double)S) : m2;
+  }
+  double mean[8], m2[8];
+  int cnt = k0 ? n_ok[g] : 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    mean[k] = k0 ? smean[g * 8 + k] : 0.0;
+    m2[k] = k0 ? sstd[g * 8 + k] : 0.0;
+  }
+  for (int r = 0; r < reps; ++r) {
+    const long row = (long)r * n + g;
+    double x[8];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) x[k] = sshape[row * 5 + k];
+    const int st = sstatus[row];
+    if (sample_shape) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) sample_shape[(g * S + k0 + r) * 5 + k] = x[k];
+      sample_status[g * S + k0 + r] = st;
+    }
+    const double Mrr = x[2], Mrc = x[3], Mcc = x[4];
+    const double tr = Mcc + Mrr, det = Mrr * Mcc - Mrc * Mrc;
+    if (st == 0 && det > 0.0 && tr > 0.0) {
+      x[5] = __dsqrt_rn(__dsqrt_rn(det));
+      x[6] = (Mcc - Mrr) / tr;
+      x[7] = 2.0 * Mrc / tr;
+      ++cnt;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) mc_fold(x[k], (double)cnt, mean[k], m2[k]);
+    }
+  }
+  n_ok[g] = cnt;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    smean[g * 8 + k] = finish && cnt == 0 ? nan : mean[k];
+    sstd[g * 8 + k] = !finish ? m2[k] : cnt == 0 ? nan : __dsqrt_rn(m2[k] / (double)cnt);
   }
 }
 }  // namespace
@@ -233,6 +337,80 @@ int scene_measure(const float* mean_h, const float* stddev_h, int64_t N, int cs,
     DV_HIP(hipMemcpyAsync(shape_h + (size_t)base * 5, shape, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
     DV_HIP(hipMemcpyAsync(iters_h + base, it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
     DV_HIP(hipMemcpyAsync(status_h + base, st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));               // the device buffers are reused by the next chunk
+  }
+  return OK;
+}
+
+// a decoder pass in device memory: `rows` sample stamps measured into the scratch rows
+int launch_measure_mc_samples(const float* pass_dev, int rows, int cs, int nb, int band, double sigma0, double tol,
+                              int max_iter, const McScratch& w, hipStream_t s) {
+  if (rows <= 0) return OK;
+  hipLaunchKernelGGL(measure_mc_sample_kernel, dim3((unsigned)rows), dim3(MS_THREADS), measure_lds_bytes(cs), s, pass_dev, cs,
+                     nb, band, sigma0, tol, max_iter, w.flux, w.shape, w.iters, w.status);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+// the scratch rows of a pass of n galaxies x reps samples (the first is sample k0 of S) folded into rows row0 .. of the state
+int launch_measure_mc_fold(const McScratch& w, int n, int reps, int k0, int S, int nb, const McState& st, int64_t row0,
+                           hipStream_t s) {
+  if (n <= 0 || reps <= 0) return OK;
+  const size_t r = (size_t)row0;
+  hipLaunchKernelGGL(measure_mc_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.flux, w.shape, w.status, n,
+                     reps, k0, S, nb, k0 + reps == S ? 1 : 0, st.flux_mean + r * nb, st.flux_std + r * nb, st.shape_mean + r * 8,
+                     st.shape_std + r * 8, st.n_ok + r, st.sample_flux ? st.sample_flux + r * S * nb : nullptr,
+                     st.sample_shape ? st.sample_shape + r * S * 5 : nullptr,
+                     st.sample_status ? st.sample_status + r * S : nullptr);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+// host sample stamps [S][N][cs][cs][nb] in, host Monte-Carlo catalogue out, in chunks of at most `chunk` galaxies with all
+// their samples (sized by the caller against free device memory): a chunk is one pass of n galaxies x S samples
+int scene_measure_mc(const float* samples_h, int S, int64_t N, int cs, int nb, int band, double sigma0, double tol,
+                     int max_iter, const McState& out_h, int64_t chunk, hipStream_t s) {
+  if (N == 0) return OK;
+  const size_t stamp = (size_t)cs * cs * nb;
+  chunk = std::max<int64_t>(1, std::min<int64_t>({chunk, N, ((int64_t)1 << 20) / S}));
+  const size_t rows = (size_t)chunk * S;
+  const bool keep = out_h.sample_flux != nullptr;
+  DevBuf<float> pass;
+  DevBuf<double> wflux, wshape, fmean, fstd, smean, sstd, kflux, kshape;
+  DevBuf<int> wit, wst, nok, kst;
+  DV_TRY(pass.alloc(rows * stamp));
+  DV_TRY(wflux.alloc(rows * nb));
+  DV_TRY(wshape.alloc(rows * 5));
+  DV_TRY(wit.alloc(rows));
+  DV_TRY(wst.alloc(rows));
+  for (DevBuf<double>* b : {&fmean, &fstd}) DV_TRY(b->alloc((size_t)chunk * nb));
+  for (DevBuf<double>* b : {&smean, &sstd}) DV_TRY(b->alloc((size_t)chunk * 8));
+  DV_TRY(nok.alloc((size_t)chunk));
+  if (keep) {
+    DV_TRY(kflux.alloc(rows * nb));
+    DV_TRY(kshape.alloc(rows * 5));
+    DV_TRY(kst.alloc(rows));
+  }
+  const McScratch w{wflux, wshape, wit, wst};
+  const McState st{fmean, fstd, smean, sstd, nok, kflux, kshape, kst};
+  for (int64_t base = 0; base < N; base += chunk) {
+    const int n = (int)std::min<int64_t>(chunk, N - base);
+    for (int q = 0; q < S; ++q)
+      DV_HIP(hipMemcpyAsync(pass.get() + (size_t)q * n * stamp, samples_h + ((size_t)q * N + base) * stamp, (size_t)n * stamp * sizeof(float),
+                            hipMemcpyHostToDevice, s));
+    DV_TRY(launch_measure_mc_samples(pass, n * S, cs, nb, band, sigma0, tol, max_iter, w, s));
+    DV_TRY(launch_measure_mc_fold(w, n, S, 0, S, nb, st, 0, s));
+    const size_t b = (size_t)base;
+    DV_HIP(hipMemcpyAsync(out_h.flux_mean + b * nb, fmean, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(out_h.flux_std + b * nb, fstd, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(out_h.shape_mean + b * 8, smean, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(out_h.shape_std + b * 8, sstd, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(out_h.n_ok + b, nok, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (keep) {
+      DV_HIP(hipMemcpyAsync(out_h.sample_flux + b * S * nb, kflux, (size_t)n * S * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(out_h.sample_shape + b * S * 5, kshape, (size_t)n * S * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(out_h.sample_status + b * S, kst, (size_t)n * S * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
     DV_HIP(hipStreamSynchronize(s));               // the device buffers are reused by the next chunk
   }
   return OK;

@@ -432,6 +432,14 @@ class DeblendFieldBatch:
 
         return catalogue_dtype(nb_of_bands) + [("measured_distance_x", "<f8"), ("measured_distance_y", "<f8")]
 
+    @staticmethod
+    def measure_mc_columns(nb_of_bands):
+        """What deblend_fields(measure_samples=S) appends behind measure_columns: the Monte-Carlo catalogue of
+        measure_stamps_mc."""
+        from debvader_amd.measure.measurement import catalogue_mc_dtype
+
+        return catalogue_mc_dtype(nb_of_bands)
+
     def __init__(self, net, field_images, cutout_size=59, nb_of_bands=6, normalise=False):
         """
         parameters:
@@ -480,7 +488,7 @@ class DeblendFieldBatch:
 
     def deblend_fields(self, galaxy_distances_to_center=None, mse_criterion=100.0, on_device=False,
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
-                       measure=False, return_fields=True, optimise_positions=False):
+                       measure=False, return_fields=True, measure_samples=0, optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -510,10 +518,28 @@ class DeblendFieldBatch:
         returned stamps are measured with measure_stamps.  return_fields=False (with on_device=True and measure=True
         only) is the catalogue-only call: no field is composited or downloaded, and get_predicted_fields() /
         get_residual_fields() raise.  The measurement is not available inside the position-fit and Monte-Carlo calls:
-        measure=True with optimise_positions=True or epistemic_uncertainty_estimation=True raises."""
+        measure=True with optimise_positions=True or epistemic_uncertainty_estimation=True raises.
+
+        measure_samples=S > 0 (with measure=True and on_device=True, with or without return_fields): errors on the
+        catalogue from the network's own Monte-Carlo decodes (dv_infer_fields_measure_mc).  S more
+        stochastic decodes of every galaxy run in the same call (two consecutive seeds, as with the epistemic estimate: the
+        pass, then the decodes), each is measured on the GPU, and the recarrays gain flux_mc_mean, flux_mc_std (per band)
+        and <q>_mc_mean, <q>_mc_std for q in row, col, Mrr, Mrc, Mcc, sigma, e1, e2 over the n_ok samples whose
+        measurement converged (measure_mc_columns).  The other columns and the fields are those of the same call without
+        it.  It is not available with optimise_positions=True or epistemic_uncertainty_estimation=True either."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
+        if int(measure_samples) != measure_samples or int(measure_samples) < 0:
+            raise ValueError(f"measure_samples must be an integer >= 0, got {measure_samples}")
+        nmc = int(measure_samples)
+        if nmc and (fit or mc):
+            raise ValueError("measure_samples cannot be combined with optimise_positions=True or "
+                             "epistemic_uncertainty_estimation=True: the Monte-Carlo catalogue is a stage of the measuring "
+                             "composite call only (dv_infer_fields_measure_mc)")
+        if nmc and not (measure and on_device):
+            raise ValueError("measure_samples needs measure=True and on_device=True: the Monte-Carlo decodes are measured "
+                             "where they lie in device memory")
         if measure and (fit or mc):
             raise ValueError("measure=True cannot be combined with optimise_positions=True or "
                              "epistemic_uncertainty_estimation=True: the measurement is a stage of the plain composite call "
@@ -565,6 +591,10 @@ class DeblendFieldBatch:
                 places = (int((F - cs) / 2) + dd).astype(np.int64)
                 if mc:
                     out = eng.infer_fields_mc_composite(self.field_images, starts, places, field_ptr, **mc_args)
+                elif nmc:
+                    out = eng.infer_fields_measure_mc(self.field_images, starts, field_ptr, places=places if return_fields else None,
+                                                      seed=seed, mc_seed=core.next_seed(), nsamples=nmc,
+                                                      return_fields=bool(return_fields))
                 elif measure:
                     out = eng.infer_fields_measure(self.field_images, starts, field_ptr, places=places if return_fields else None,
                                                    seed=seed, return_fields=bool(return_fields))
@@ -597,9 +627,13 @@ class DeblendFieldBatch:
         columns = self.DEFAULT_COLUMNS if not on_device else \
             self.ON_DEVICE_EPISTEMIC_COLUMNS if mc else self.ON_DEVICE_COLUMNS
         if measure:
-            from debvader_amd.measure.measurement import catalogue_records, measure_stamps
+            from debvader_amd.measure.measurement import catalogue_mc_records, catalogue_records, measure_stamps
 
             columns = columns + self.measure_columns(nb)
+            if nmc:
+                columns = columns + self.measure_mc_columns(nb)
+                cat_mc = catalogue_mc_records(out["flux_mc_mean"], out["flux_mc_std"], out["shape_mc_mean"],
+                                              out["shape_mc_std"], out["n_ok"])
             cat = catalogue_records(out["flux"], out["flux_err"], out["shape"], out["iters"], out["status"]) if on_device \
                 else measure_stamps(out["loc"], out["scale"], ctx=self._ctx)
             # a stamp's pixel (row, col) is the field's pixel start + (row, col); distances count from pixel int(F / 2)
@@ -619,6 +653,9 @@ class DeblendFieldBatch:
                     rec[k] = cat[k][lo:hi]
                 rec["measured_distance_x"] = measured[lo:hi, 0]
                 rec["measured_distance_y"] = measured[lo:hi, 1]
+                if nmc:
+                    for k in cat_mc.dtype.names:
+                        rec[k] = cat_mc[k][lo:hi]
             if on_device:
                 rec["mse_center"] = mse_center[lo:hi]
                 if mc:

@@ -168,6 +168,35 @@ def check_measure_args(mean, stddev, band, sigma0, tol, max_iter):
     return mean, stddev, measure_params(band, sigma0, tol, max_iter, mean.shape[3])
 
 
+MC_SHAPE_NAMES = ("row", "col", "Mrr", "Mrc", "Mcc", "sigma", "e1", "e2")     # the columns of shape_mc_mean / shape_mc_std
+
+
+def check_measure_mc_args(samples, band, sigma0, tol, max_iter):
+    """(samples, params) of scene_measure_mc: C-contiguous float32 sample stamps (S, N, cs, cs, bands), S >= 1."""
+    samples = _f32c(samples)
+    if samples.ndim != 5 or samples.shape[2] != samples.shape[3] or samples.shape[2] < 1 or samples.shape[4] < 1:
+        raise ValueError(f"expected sample stamps (S, N, cs, cs, bands), got {samples.shape}")
+    if samples.shape[0] < 1:
+        raise ValueError("at least one Monte-Carlo sample per galaxy is needed, got 0")
+    if samples.shape[2] > MEASURE_MAX_STAMP:
+        raise ValueError(f"stamps of {samples.shape[2]} pixels: the measurement takes at most {MEASURE_MAX_STAMP}")
+    return samples, measure_params(band, sigma0, tol, max_iter, samples.shape[4])
+
+
+def _measure_mc_out(n, nb, S, keep_samples):
+    """The result dictionary of the Monte-Carlo catalogue calls and its pointers in the C-ABI's order."""
+    out = dict(flux_mc_mean=np.zeros((n, nb), np.float64), flux_mc_std=np.zeros((n, nb), np.float64),
+               shape_mc_mean=np.zeros((n, 8), np.float64), shape_mc_std=np.zeros((n, 8), np.float64),
+               n_ok=np.zeros(n, np.int32))
+    if keep_samples:
+        out.update(sample_flux=np.zeros((n, S, nb), np.float64), sample_shape=np.zeros((n, S, 5), np.float64),
+                   sample_status=np.zeros((n, S), np.int32))
+    ptrs = [_dp(out["flux_mc_mean"]), _dp(out["flux_mc_std"]), _dp(out["shape_mc_mean"]), _dp(out["shape_mc_std"]),
+            _ip(out["n_ok"]), _dp(out.get("sample_flux")), _dp(out.get("sample_shape")),
+            _ip(out["sample_status"]) if keep_samples else None]
+    return out, ptrs
+
+
 def check_detect_args(fields_r, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
                       workspace_bytes=0) -> np.ndarray:
     """Context.scene_detect's argument checks (before any GPU work); returns the fields as float64 (M, H, W)."""
@@ -518,6 +547,27 @@ class Context:
         if n:
             check(lib.dv_scene_measure(self._h, _fp(mean), _fp(stddev), n, cs, nb, C.byref(par), _dp(out["flux"]),
                                        _dp(out.get("flux_err")), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"])))
+        return out
+
+    def scene_measure_mc(self, samples, band: int = 2, sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200,
+                         keep_samples: bool = False, _chunk=None) -> Dict[str, np.ndarray]:
+        """Monte-Carlo catalogue of N galaxies on the GPU (dv_scene_measure_mc): samples (S, N, cs, cs,
+        bands), S stochastic decodes of every galaxy, taken as float32.  Every sample is measured as scene_measure does
+        without a stddev stamp; per galaxy the rows are folded in sample order (Welford) into {"flux_mc_mean", "flux_mc_std"
+        (N, bands): over all S samples, "shape_mc_mean", "shape_mc_std" (N, 8): {row, col, Mrr, Mrc, Mcc, sigma, e1, e2}
+        (MC_SHAPE_NAMES) over the accepted samples - status 0, det M > 0, trace > 0 -, "n_ok" (N,): how many those were
+        (0: NaN, 1: std 0)}, float64, std in the population form.  keep_samples=True adds the per-sample rows "sample_flux"
+        (N, S, bands), "sample_shape" (N, S, 5) and "sample_status" (N, S).  A galaxy's result depends on its own samples
+        only.  (_chunk: galaxies per library call, for tests.)"""
+        samples, par = check_measure_mc_args(samples, band, sigma0, tol, max_iter)
+        S, n, cs, nb = samples.shape[0], samples.shape[1], samples.shape[2], samples.shape[4]
+        out, ptrs = _measure_mc_out(n, nb, S, keep_samples)
+        if _chunk is not None and 0 < int(_chunk) < n:
+            parts = [self.scene_measure_mc(samples[:, g:g + int(_chunk)], band, sigma0, tol, max_iter, keep_samples)
+                     for g in range(0, n, int(_chunk))]
+            return {k: np.concatenate([q[k] for q in parts]) for k in out}
+        if n:
+            check(lib.dv_scene_measure_mc(self._h, _fp(samples), S, n, cs, nb, C.byref(par), *ptrs))
         return out
 
     CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
@@ -960,6 +1010,46 @@ class Engine:
     def scene_measure(self, mean, stddev=None, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_measure on this engine's GPU context."""
         return self.ctx.scene_measure(mean, stddev, **kw)
+
+    def infer_fields_measure_mc(self, fields, starts, field_ptr, places=None, seed=0, mc_seed=0, nsamples=100, band: int = 2,
+                                sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, return_fields=True,
+                                residual=True, mse_center=True, keep_samples=False) -> Dict[str, np.ndarray]:
+        """infer_fields_measure() plus the Monte-Carlo catalogue (dv_infer_fields_measure_mc): behind
+        every chunk's forward pass `nsamples` more stochastic decodes of its encoder output are measured where they lie in
+        device memory and folded per galaxy.  Returns infer_fields_measure's dictionary, bit for bit for the same `seed`, plus
+        scene_measure_mc's {"flux_mc_mean", "flux_mc_std", "shape_mc_mean", "shape_mc_std", "n_ok"} (and the per-sample rows
+        with keep_samples=True) - the bits of scene_measure_mc on the stacked stamps infer_mc(cutouts.astype(float32), 1,
+        mc_seed + q)[0].  No epistemic field and no eps_norm are computed; return_fields=False is the catalogue-only call."""
+        if return_fields and places is None:
+            raise ValueError("places are needed to composite the fields; return_fields=False measures without them")
+        if int(nsamples) < 1:
+            raise ValueError(f"nsamples must be at least 1, got {nsamples}")
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places if return_fields else None)
+        nb = fields.shape[3]
+        par = measure_params(band, sigma0, tol, max_iter, nb)
+        if return_fields:
+            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
+        else:
+            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
+            ptrs = [None, None, None, _dp(out.get("mse_center"))]
+            args = args[:5] + [None] + args[5:]
+        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
+                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
+        mc, mc_ptrs = _measure_mc_out(N, nb, int(nsamples), keep_samples)
+        out.update(mc)
+        check(lib.dv_infer_fields_measure_mc(self._h, *args, int(seed), int(mc_seed), int(nsamples), C.byref(par), *ptrs,
+                                             _dp(out["flux"]), _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]),
+                                             _ip(out["status"]), *mc_ptrs))
+        return out
+
+    def infer_cutouts_measure_mc(self, field, starts, places=None, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_mc() for one field (F, F, bands): the field-sized results under singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_mc(fields, starts, fp, places=places, seed=seed, **kw))
+
+    def scene_measure_mc(self, samples, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_measure_mc on this engine's GPU context."""
+        return self.ctx.scene_measure_mc(samples, **kw)
 
     def open_field_set(self, fields, cumulative=False) -> "FieldSet":
         """Upload M float64 fields (M, F, F, bands) once and keep them, their working and final residuals and the predicted

@@ -4,7 +4,9 @@ The reference ships `debvader.measure` as an empty package: measurement was mean
 there is no reference code behind this module.  The measurement itself is defined in DESIGN.md section 7j and runs on the
 GPU (csrc/measure.hip): per-band fluxes and their errors summed over the network's mean / stddev stamps, and the adaptive
 moments of one band - the centroid and second moments of the stamp under a Gaussian weight that is iterated until it matches
-the object.  Errors on the moments and a PSF correction are not part of it.
+the object.  Errors on the centroid, the moments, sigma, e1 and e2 (and a second error on the fluxes) come from the network's
+own Monte-Carlo decodes (measure_stamps_mc): every decode of a galaxy is measured and the measured
+rows are folded into a mean and a standard deviation per quantity.  A PSF correction is not part of it.
 """
 import numpy as np
 
@@ -41,6 +43,57 @@ def catalogue_records(flux, flux_err, shape, iters, status):
         rec["sigma"] = np.where(failed, np.nan, np.sqrt(np.sqrt(det)))
         rec["e1"] = np.where(failed, np.nan, (Mcc - Mrr) / tr)
         rec["e2"] = np.where(failed, np.nan, 2.0 * Mrc / tr)
+    return rec
+
+
+MC_SHAPE_NAMES = E.MC_SHAPE_NAMES
+
+
+def catalogue_mc_dtype(nb_of_bands):
+    """The columns of measure_stamps_mc's recarray: mean and standard deviation over the Monte-Carlo decodes of the per-band
+    fluxes (all samples) and of row, col, Mrr, Mrc, Mcc, sigma, e1, e2 (the n_ok accepted samples)."""
+    nb = int(nb_of_bands)
+    cols = [("flux_mc_mean", "<f8", (nb,)), ("flux_mc_std", "<f8", (nb,))]
+    for q in MC_SHAPE_NAMES:
+        cols += [(q + "_mc_mean", "<f8"), (q + "_mc_std", "<f8")]
+    return cols + [("n_ok", "<i4")]
+
+
+def catalogue_mc_records(flux_mc_mean, flux_mc_std, shape_mc_mean, shape_mc_std, n_ok):
+    """The recarray of measure_stamps_mc from the arrays the engine returns."""
+    flux_mc_mean = np.asarray(flux_mc_mean, dtype=np.float64)
+    n, nb = flux_mc_mean.shape
+    rec = np.recarray((n,), dtype=catalogue_mc_dtype(nb))
+    rec["flux_mc_mean"] = flux_mc_mean
+    rec["flux_mc_std"] = flux_mc_std
+    for k, q in enumerate(MC_SHAPE_NAMES):
+        rec[q + "_mc_mean"] = np.asarray(shape_mc_mean).reshape(n, 8)[:, k]
+        rec[q + "_mc_std"] = np.asarray(shape_mc_std).reshape(n, 8)[:, k]
+    rec["n_ok"] = n_ok
+    return rec
+
+
+def measure_stamps_mc(samples, band=2, sigma0=3.0, tol=1e-10, max_iter=200, keep_samples=False, ctx=None):
+    """Errors on the catalogue from Monte-Carlo decodes, on the GPU.
+
+    parameters:
+        samples: (S, N, cutout_size, cutout_size, bands) - S stochastic decodes (mean stamps) of each of N galaxies
+        band, sigma0, tol, max_iter: as in measure_stamps; every sample is measured with them, without a stddev stamp
+        keep_samples: also return the per-sample measurements
+        ctx: the engine context to run on (None: the default context)
+    returns a np.recarray with, per galaxy: flux_mc_mean, flux_mc_std (one entry per band, over all S samples) and
+    <q>_mc_mean, <q>_mc_std for q in row, col, Mrr, Mrc, Mcc, sigma, e1, e2 over the n_ok samples whose measurement
+    converged (status 0) with det M > 0 and a positive trace; n_ok = 0 gives NaN, n_ok = 1 a standard deviation of 0.  The
+    standard deviations are the population form (np.std).  With keep_samples=True returns (recarray, {"sample_flux" (N, S,
+    bands), "sample_shape" (N, S, 5), "sample_status" (N, S)}).
+    """
+    samples, _ = E.check_measure_mc_args(samples, band, sigma0, tol, max_iter)
+    if ctx is None:
+        ctx = E.default_context()
+    out = ctx.scene_measure_mc(samples, band=band, sigma0=sigma0, tol=tol, max_iter=max_iter, keep_samples=bool(keep_samples))
+    rec = catalogue_mc_records(out["flux_mc_mean"], out["flux_mc_std"], out["shape_mc_mean"], out["shape_mc_std"], out["n_ok"])
+    if keep_samples:
+        return rec, {k: out[k] for k in ("sample_flux", "sample_shape", "sample_status")}
     return rec
 
 

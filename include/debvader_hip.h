@@ -442,6 +442,34 @@ int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_
                             double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
                             int32_t* iters, int32_t* status);
 
+/* ---- Monte-Carlo catalogue: errors on fluxes and shapes from stochastic decodes ----
+ * Sample q of galaxy i is one decoded mean stamp (what dv_infer_mc folds: Philox (mc_seed + q, global stamp number i),
+ * denormalised with normalise on).  Every sample is measured as above without a stddev stamp; from its moments follow
+ * tr = Mcc + Mrr, det = Mrr Mcc - Mrc^2, sigma = sqrt(sqrt(det)), e1 = (Mcc - Mrr) / tr, e2 = 2 Mrc / tr, and the sample's
+ * shape row {row, col, Mrr, Mrc, Mcc, sigma, e1, e2} is accepted iff status == 0, det > 0 and tr > 0 (its flux row always).
+ * Per galaxy the rows are folded in ascending sample order with Welford's recurrence (n += 1; d = x - mean; mean += d / n;
+ * M2 += d (x - mean); from zeros) and std = sqrt(M2 / n), the population form; every operation is rounded on its own, so a
+ * float64 restatement of the same scalar operations gives the same bits.  Outputs, float64: flux_mean / flux_std [N][nb]
+ * (n = S), shape_mean / shape_std [N][8] over the n_ok [N] accepted samples (n_ok = 0: NaN; n_ok = 1: std 0).  The
+ * per-sample rows sample_flux [N][S][nb], sample_shape [N][S][5], sample_status [N][S] are optional: all given or all null.
+ * dv_scene_measure_mc: host sample stamps [S][N][cs][cs][nb] (float32), in chunks of galaxies sized against free device
+ * memory.  dv_infer_fields_measure_mc: dv_infer_fields_measure (same arguments, same bits in every output it shares with
+ * it) with nsamples more decodes of every chunk's encoder output measured and folded behind its forward pass; the
+ * Monte-Carlo catalogue has the bits of dv_scene_measure_mc on the sample stamps dv_infer_mc(nsamples = 1, seed = mc_seed +
+ * q) returns for the float32 cutouts.  No epistemic field and no eps_norm are computed.  Refused before any GPU work
+ * (DV_E_INVALID) beside what dv_infer_fields_measure refuses: nsamples (S) < 1, a missing Monte-Carlo output, per-sample
+ * outputs given in part. */
+int dv_scene_measure_mc(dv_ctx* ctx, const float* samples, int32_t S, int64_t N, int32_t cs, int32_t nb,
+                        const dv_measure_params* params, double* flux_mean, double* flux_std, double* shape_mean,
+                        double* shape_std, int32_t* n_ok, double* sample_flux, double* sample_shape, int32_t* sample_status);
+int dv_infer_fields_measure_mc(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                               const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed, uint64_t mc_seed,
+                               int32_t nsamples, const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                               double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                               int32_t* iters, int32_t* status, double* flux_mean, double* flux_std, double* shape_mean,
+                               double* shape_std, int32_t* n_ok, double* sample_flux, double* sample_shape,
+                               int32_t* sample_status);
+
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)
  * keeps per field, in device memory, `work` (what the next pass detects on and cuts from, at first the field), `final`

@@ -15,6 +15,19 @@ Per leg: the median, the spread (max - min over the median) and every run.  GPU 
     python tools/measure_bench.py [--fields 1024] [--size 259] [--repeat 5] [--max-batch 8192] [--host-fields 16]
 
 --profile-one: warm up, one fp32 catalogue-only call, exit (for a kernel trace).
+
+--samples S (256 fields of 259 px is the section 7g workload): the Monte-Carlo catalogue instead -
+
+    (a) mc catalogue :  deblend_fields(d, on_device=True, measure=True, return_fields=False, measure_samples=S)
+    (b) mc composite :  deblend_fields(d, on_device=True, epistemic_uncertainty_estimation=True, epistemic_samples=S): the
+                        nearest call before it, the same decodes folded per pixel and composited
+    (c) route before :  infer_fields_keep, then S x infer_mc(cutouts, nsamples=1, seed=mc_seed + q), then S x scene_measure
+                        on the downloaded sample stamps - the only route to these numbers before the stage existed.  Timed on
+                        --host-fields fields and EXTRAPOLATED to all fields by the ratio of stamps.
+
+    python tools/measure_bench.py --samples 100 --fields 256 [--repeat 5] [--host-fields 4]
+
+With --profile-one: warm up, one fp32 call (a), exit.
 """
 import argparse
 import io
@@ -53,6 +66,74 @@ def _host(net, fields, dists, parts):
     return n
 
 
+def _route_before(net, fields, dists, S):
+    """Route (c): every sample stamp visits the host and goes up again to be measured"""
+    from debvader_amd.deblend.field_deblender import batch_windows
+
+    eng = net._core.engine
+    starts, field_ptr, _, _ = batch_windows(fields.shape[1], dists, ARCH["input_shape"][0])
+    seed, mc_seed = net._core.next_seed(), net._core.next_seed()
+    cut = eng.infer_fields_keep(fields, starts, field_ptr, seed=seed)["cutouts"].astype(np.float32)
+    for q in range(S):
+        eng.scene_measure(eng.infer_mc(cut, 1, mc_seed + q)[0])
+    return len(starts)
+
+
+def main_samples(a):
+    rng = np.random.default_rng(0)
+    F, M, S = a.size, a.fields, a.samples
+    base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
+    fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    quiet = io.StringIO()
+    Mh = min(M, a.host_fields)
+    result = {"fields": M, "F": F, "samples": S, "max_batch": a.max_batch, "repeat": a.repeat, "route_before_fields": Mh}
+    dists = None
+    for dtype in a.dtypes.split(","):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections; {S} Monte-Carlo samples; "
+                  f"max_batch {a.max_batch}")
+        legs = {"mc catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False, measure_samples=S),
+                "mc composite": lambda: _device(net, fields, dists, epistemic_uncertainty_estimation=True, epistemic_samples=S)}
+        with redirect_stdout(quiet):
+            for fn in legs.values():           # warm-up
+                fn()
+            if a.profile_one:
+                legs["mc catalogue"]()
+                net._core.engine.close()
+                return
+            _route_before(net, fields[:1], dists[:1], 2)
+            times = {k: [] for k in legs}
+            before_t, n, nh = [], 0, 0
+            for _ in range(a.repeat):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    n = fn()
+                    times[k].append(time.perf_counter() - t0)
+                t0 = time.perf_counter()
+                nh = _route_before(net, fields[:Mh], dists[:Mh], S)
+                before_t.append(time.perf_counter() - t0)
+        result[dtype] = {"stamps": n, "route_before_stamps": nh}
+        for k in legs:
+            t = np.array(times[k])
+            print(_row(f"{dtype} {k}", t, n, M))
+            result[dtype][k.replace(" ", "_") + "_ms"] = [round(1e3 * x, 2) for x in t]
+        tb = np.array(before_t)
+        print(_row(f"{dtype} route before ({Mh} fields)", tb, nh, Mh))
+        scale = n / max(nh, 1)
+        ta, tc = (float(np.median(times[k])) for k in ("mc catalogue", "mc composite"))
+        ext = float(np.median(tb)) * scale
+        spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
+        print(f"{dtype} route before EXTRAPOLATED to {M} fields ({n} stamps, x {scale:.1f}): {1e3 * ext:.0f} ms")
+        print(f"{dtype} mc catalogue / mc composite {ta / tc:.3f}; extrapolated route before / mc catalogue {ext / ta:.1f} "
+              f"(spreads {spread(times['mc catalogue']):.3f} and {spread(tb):.3f})")
+        result[dtype].update(route_before_ms=[round(1e3 * x, 2) for x in tb], route_before_extrapolated_ms=round(1e3 * ext, 1))
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fields", type=int, default=1024)
@@ -62,7 +143,10 @@ def main():
     ap.add_argument("--host-fields", type=int, default=16)
     ap.add_argument("--dtypes", default="float32,bf16")
     ap.add_argument("--profile-one", action="store_true")
+    ap.add_argument("--samples", type=int, default=0)
     a = ap.parse_args()
+    if a.samples > 0:
+        return main_samples(a)
     rng = np.random.default_rng(0)
     F, M = a.size, a.fields
     base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
