@@ -315,6 +315,25 @@ int launch_measure_mc_fold(const McScratch& w, int n, int reps, int k0, int S, i
                            hipStream_t s);
 int scene_measure_mc(const float* samples_h, int S, int64_t N, int cs, int nb, int band, double sigma0, double tol,
                      int max_iter, const McState& out_h, int64_t chunk, hipStream_t s);
+// blendedness sums (blend.hip): per galaxy {W, A, Bm, Bd} = the sums of g, g P, g T, g D over the stamp pixels
+// inside the field, g the Gaussian of the galaxy's adaptive moments; an ineligible row (status not 0 or 2, a non-finite
+// shape value, det <= 1e-6) gets four NaN and npix -1.  launch_blend_child: W, A and npix of n stamps in device memory
+// (and the NaN of the ineligible rows), every per-galaxy pointer at the first stamp's row.  launch_blend_parent: Bm and Bd
+// of n galaxies whose fields are complete: sfield_dev [n] their fields, model_dev / data_dev stacks [.][F][F][nb] that start
+// at field f0 (data_dev null: Bd = NaN).  launch_blend_composite_mean: the mean sum of launch_scene_composite_chunk alone
+// (the same additions in the same order, so the same bits), for a call that keeps no stddev field.  scene_blend: host
+// arrays, at most `chunk` stamps and the `gmax` fields they may span on the device at a time.
+int blend_check(const char* who, int cs, int nb, int band);
+int launch_blend_child(const float* stamps_dev, const double* shape_dev, const int* status_dev, const int* places_dev, int n,
+                       int cs, int nb, int band, int F, double* blend_dev, int* npix_dev, hipStream_t s);
+int launch_blend_parent(const double* shape_dev, const int* status_dev, const int* places_dev, const int* sfield_dev, int f0,
+                        int n, int cs, int nb, int band, int F, const double* model_dev, const double* data_dev,
+                        double* blend_dev, hipStream_t s);
+int launch_blend_composite_mean(double* mean_f, int F, int nb, const float* loc, const int* places_dev, int n, int cs,
+                                const int* fptr_dev, int f0, int fy0, int nfields, long obase, hipStream_t s);
+int scene_blend(const float* stamps_h, const double* shape_h, const int32_t* status_h, const int32_t* places_h,
+                const int64_t* field_ptr, int64_t N, int cs, int nb, int band, const double* model_h, const double* data_h,
+                int M, int F, double* blend_h, int32_t* npix_h, int64_t chunk, int64_t gmax, hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

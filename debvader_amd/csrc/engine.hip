@@ -3066,6 +3066,15 @@ struct PipeJob {
     int band = 0, max_iter = 0;
     double sigma0 = 0.0, tol = 0.0;
   } mcm;
+  // blendedness sums (dv_infer_fields_measure_blend): behind every chunk's measurement, the child sums W, A and
+  // npix of its stamps (they need the chunk's catalogue rows and sinks.places_d); blend decides.  The parent sums are the
+  // caller's, once a field's composite is complete.  Without sinks.mean_f (the catalogue-only form) the chunk's mean stamps
+  // are composited into mean_f, a device-side mean field per resident field that nothing downloads
+  struct Blend {
+    double* blend = nullptr;           // device [.][4]
+    int* npix = nullptr;               // device [.]
+    double* mean_f = nullptr;          // device, fields f0 .. like fields_d (the catalogue-only form)
+  } bl;
 };
 
 // The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
@@ -3277,6 +3286,13 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
       DV_TRY(launch_measure(p->dloc[b], p->dscale[b], nb, cs, j.nb, j.ms.band, j.ms.sigma0, j.ms.tol, j.ms.max_iter,
                             j.ms.flux + (size_t)r * j.nb, j.ms.ferr + (size_t)r * j.nb, j.ms.shape + (size_t)r * 5,
                             j.ms.iters + r, j.ms.status + r, p->s_out));
+      if (j.bl.blend) {
+        if (!comp)
+          DV_TRY(launch_blend_composite_mean(j.bl.mean_f, j.F, j.nb, p->dloc[b], j.sinks.places_d + 2 * r, nb, cs, j.fptr_d, j.f0,
+                                             j.sfield[r], j.sfield[r + nb - 1] - j.sfield[r] + 1, (long)r, p->s_out));
+        DV_TRY(launch_blend_child(p->dloc[b], j.ms.shape + (size_t)r * 5, j.ms.status + r, j.sinks.places_d + 2 * r, nb, cs,
+                                  j.nb, j.ms.band, j.F, j.bl.blend + (size_t)r * 4, j.bl.npix + r, p->s_out));
+      }
     }
     if (j.loc || j.consumer) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (j.scale || j.consumer) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
@@ -3733,6 +3749,23 @@ int dv_scene_measure(dv_ctx* c, const float* mean, const float* stddev, int64_t 
   const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 2 / per_stamp);
   return scene_measure(mean, stddev, N, cs, nb, p->band, p->sigma0, p->tol, p->max_iter, flux, flux_err, shape, iters,
                        status, chunk, c->stream);
+}
+
+int dv_scene_blend(dv_ctx* c, const float* stamps, const double* shape, const int32_t* status, const int32_t* places,
+                   const int64_t* field_ptr, int64_t N, int32_t cs, int32_t nb, int32_t band, const double* model_fields,
+                   const double* data_fields, int32_t M, int32_t F, double* blend, int32_t* npix) {
+  if (!c) return DV_E_INVALID;
+  DV_TRY(blend_check("dv_scene_blend", cs, nb, band));   // before any GPU work
+  DV_HIP(hipSetDevice(c->device));
+  // a quarter of free device memory for a chunk's stamps and rows, a quarter for the fields they lie in
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t per_stamp = (size_t)cs * cs * nb * sizeof(float) + 9 * sizeof(double) + 5 * sizeof(int);
+  const size_t per_field = (size_t)std::max(F, 1) * std::max(F, 1) * nb * sizeof(double) * (data_fields ? 2 : 1);
+  const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 4 / per_stamp);
+  const int64_t gmax = (int64_t)std::max<size_t>(1, free_b / 4 / per_field);
+  return scene_blend(stamps, shape, status, places, field_ptr, N, cs, nb, band, model_fields, data_fields, M, F, blend, npix,
+                     chunk, gmax, c->stream);
 }
 
 int dv_scene_measure_mc(dv_ctx* c, const float* samples, int32_t S, int64_t N, int32_t cs, int32_t nb,
@@ -4890,18 +4923,51 @@ struct CatalogueMcStage {           // means and standard deviations over the Mo
   }
 };
 
+struct BlendOut { double* blend = nullptr; int32_t* npix = nullptr; };   // dv_infer_fields_measure_blend, host [N][4], [N]
+
+struct BlendStage {                 // the blendedness sums of every stamp (7l)
+  DevBuf<double> blend, mean;       // mean: the device-side mean field of the catalogue-only form (else the composite stage's)
+  DevBuf<int> npix;
+  static size_t bytes_per_stamp() { return 4 * sizeof(double) + sizeof(int); }
+  static size_t bytes_per_field(bool own_mean, size_t fb) { return own_mean ? fb : 0; }
+  int alloc(int64_t N, bool own_mean, size_t elems) {
+    DV_TRY(blend.alloc((size_t)N * 4));
+    DV_TRY(npix.alloc((size_t)N));
+    return own_mean ? mean.alloc(elems) : DV_OK;
+  }
+  void bind(PipeJob::Blend& q) const { q.blend = blend; q.npix = npix; q.mean_f = mean; }
+  // a group begins (the catalogue-only form): zeros, but for a first field that was composited in part with the previous
+  // group, whose sums lie in slot `from` and go on in slot 0
+  int begin(size_t ng, size_t felems, long from, hipStream_t s) {
+    if (!mean) return DV_OK;
+    const size_t fb = felems * sizeof(double);
+    if (from > 0) DV_HIP(hipMemcpyAsync(mean, mean.get() + (size_t)from * felems, fb, hipMemcpyDeviceToDevice, s));
+    const size_t keep = from >= 0 ? 1 : 0;
+    if (ng > keep) DV_HIP(hipMemsetAsync(mean.get() + keep * felems, 0, (ng - keep) * fb, s));
+    return DV_OK;
+  }
+  int download(const BlendOut& o, int64_t N, hipStream_t s) {
+    DV_HIP(hipMemcpyAsync(o.blend, blend, (size_t)N * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(o.npix, npix, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return DV_OK;
+  }
+};
+
 // j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
 // the device side and the rows are filled in here
 static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
                              const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr,
-                             const MeasureMcOut* mco = nullptr) {
+                             const MeasureMcOut* mco = nullptr, const BlendOut* bo = nullptr,
+                             const int32_t* blend_places = nullptr) {
   // check
   const double* fields = j.fields;
   const int F = j.F, nb = j.nb;
   if (M > 0 && !fields) return DV_E_INVALID;
   std::vector<int32_t> sfield;
   std::vector<int> fptr32;
-  DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, j.starts, fo ? fo->places : nullptr, sfield, fptr32));
+  const int32_t* places = fo ? fo->places : blend_places;   // (blend_places: the catalogue-only form of the blendedness call)
+  DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, j.starts, places, sfield, fptr32));
   const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
   if (fo) fields_write_empty(*fo, fields, M, field_ptr, felems);
   if (N == 0) return DV_OK;
@@ -4917,7 +4983,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   double* mse_h = fo ? fo->mse : mo ? mo->mse : nullptr;
   DevBuf<double> fdev;                                // the resident group of source fields
   StampTables tab;
-  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc;   // (a stage that does not run stays empty)
+  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls;   // (a stage that does not run stays empty)
   ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
   if (fitting) DV_TRY(fit.make_plan(*fo, c, sfield.data()));
   size_t per_field = fb, reserve = StampTables::bytes((size_t)N, (size_t)M);
@@ -4933,12 +4999,16 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   const bool keep_samples = mco && mco->st.sample_flux;
   if (mco)
     reserve += (size_t)N * CatalogueMcStage::bytes_per_stamp(nb, mco->nsamples, keep_samples) + CatalogueMcStage::bytes_fixed(m->Bc, nb);
+  if (bo) {
+    per_field += BlendStage::bytes_per_field(!fo, fb);
+    reserve += (size_t)N * BlendStage::bytes_per_stamp();
+  }
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
   if (G < 1) {
     set_error("%s: one %d-pixel field needs %zu bytes of device memory (field%s), %zu are available for fields", who, F,
-              per_field, fo ? " and its result fields" : "", budget);
+              per_field, fo ? " and its result fields" : bo ? " and its device-side mean field" : "", budget);
     return DV_E_NOMEM;
   }
   std::vector<FieldGroup> groups;
@@ -4962,11 +5032,15 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     DV_TRY(catmc.alloc(N, nb, mco->nsamples, keep_samples, m->Bc));
     catmc.bind(j.mcm, mo->par);
   }
+  if (bo) {
+    DV_TRY(bls.alloc(N, !fo, gelems));
+    bls.bind(j.bl);
+  }
   if (fitting) {
     DV_TRY(fit.alloc(*fo, c, gmax, groups));
     fit.bind(j.fit);
   }
-  DV_TRY(tab.upload(N, M, j.starts, fo && !fitting ? fo->places : nullptr, sfield.data(), fptr32.data(), mse_h != nullptr, 0, s));
+  DV_TRY(tab.upload(N, M, j.starts, !fitting ? places : nullptr, sfield.data(), fptr32.data(), mse_h != nullptr, 0, s));
   j.fields_d = fdev;
   j.starts_d = tab.starts;
   j.sfield = sfield.data();
@@ -4976,24 +5050,39 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   j.sinks.places_d = tab.places;
   j.sinks.mse = tab.mse;
   // per group: upload -> the pipeline -> download the sinks
-  int prev_last = -1;
-  for (const FieldGroup& g : groups) {
+  int prev_last = -1, prev_first = -1;
+  for (size_t gi = 0; gi < groups.size(); ++gi) {
+    const FieldGroup& g = groups[gi];
     const size_t ng = (size_t)(g.f1 - g.f0 + 1), goff = (size_t)g.f0 * felems;
     DV_HIP(hipMemcpyAsync(fdev, fields + goff, ng * fb, hipMemcpyHostToDevice, s));
     for (ResultStack* r : stacks) DV_TRY(r->begin(r == &comp.residual ? fdev.get() : nullptr, ng * fb, s));
     if (g.f0 == prev_last)
       for (ResultStack* r : stacks) DV_TRY(r->carry(goff, fb, s));
     if (fitting) DV_TRY(fit.begin(fdev, ng, c));
+    if (bo) DV_TRY(bls.begin(ng, felems, g.f0 == prev_last ? (long)(prev_last - prev_first) : -1, s));
     DV_HIP(hipStreamSynchronize(s));               // the gather runs on the pipeline's copy stream
     j.f0 = g.f0;
     j.row0 = g.k0 * chunk;
     j.N = std::min<int64_t>(N, g.k1 * chunk) - j.row0;
     DV_TRY(infer_pipelined(m, j));
+    if (bo) {
+      // the completed-field seam: every field of the group has all its stamps composited now, but for a last field that
+      // the next group goes on with (it is complete there); the parent sums of the complete fields' galaxies - one
+      // contiguous range of rows - read the mean field, the source field and the catalogue rows where they lie
+      const int fa = g.f0, fz = gi + 1 < groups.size() && groups[gi + 1].f0 == g.f1 ? g.f1 - 1 : g.f1;
+      if (fz >= fa) {
+        const int r0 = fptr32[fa], r1 = fptr32[fz + 1];
+        DV_TRY(launch_blend_parent(cat.shape.get() + (size_t)r0 * 5, cat.status.get() + r0, tab.places.get() + 2 * (size_t)r0,
+                                   tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, mo->par.band, F,
+                                   fo ? comp.mean.dev.get() : bls.mean.get(), fdev, bls.blend.get() + (size_t)r0 * 4, s));
+      }
+    }
     if (fo) {
       for (ResultStack* r : stacks) DV_TRY(r->end(ng * fb, goff, s));
       DV_HIP(hipStreamSynchronize(s));
     }
     prev_last = g.f1;
+    prev_first = g.f0;
   }
   // download the per-stamp results
   if (mse_h) {
@@ -5002,6 +5091,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   }
   if (mo) DV_TRY(cat.download(*mo, N, nb, s));
   if (mco) DV_TRY(catmc.download(*mco, N, nb, s));
+  if (bo) DV_TRY(bls.download(*bo, N, s));
   if (fo) DV_TRY(mc.download(N, s));
   if (fitting) DV_TRY(fit.download(*fo, N, s));
   drain.dismiss();
@@ -5110,12 +5200,13 @@ int dv_infer_fields_composite(dv_model* m, const double* fields, int32_t M, int3
 }
 
 // ---- catalogue measurement as a stage of the many-field call -----------------------------------------------
-int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
-                            const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
-                            const dv_measure_params* params, double* mean_fields, double* stddev_fields,
-                            double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
-                            int32_t* iters, int32_t* status) {
-  const char* who = "dv_infer_fields_measure";
+// bo: the blendedness call, which adds its two outputs and always needs the placements
+static int infer_fields_measure_entry(const char* who, dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb,
+                                      const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                                      uint64_t seed, const dv_measure_params* params, double* mean_fields,
+                                      double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
+                                      double* flux_err, double* shape, int32_t* iters, int32_t* status,
+                                      const BlendOut* bo = nullptr) {
   if (!m || !params) return DV_E_INVALID;
   DV_TRY(measure_check(who, m->A.H, nb, params->band, params->sigma0, params->tol, params->max_iter));
   if (N > 0 && (!flux || !flux_err || !shape || !iters || !status)) {
@@ -5135,10 +5226,14 @@ int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_
   mo.shape = shape;
   mo.iters = iters;
   mo.status = status;
+  if (bo && N > 0 && (!places || !bo->blend || !bo->npix)) {
+    set_error("%s: places, blend and npix must all be given (the catalogue-only form needs the placements too)", who);
+    return DV_E_INVALID;
+  }
   PipeJob j = fields_job(fields, F, nb, starts, seed);
   if (!with_fields) {
     mo.mse = mse_center;
-    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo);
+    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo ? places : nullptr);
   }
   FieldsOut fo;
   fo.mean = mean_fields;
@@ -5146,7 +5241,31 @@ int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_
   fo.residual = residual_fields;
   fo.mse = mse_center;
   fo.places = places;
-  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo);
+  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo);
+}
+
+int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                            const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                            const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                            double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                            int32_t* iters, int32_t* status) {
+  return infer_fields_measure_entry("dv_infer_fields_measure", m, fields, M, F, nb, starts, places, field_ptr, N, seed, params,
+                                    mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape, iters,
+                                    status);
+}
+
+// ---- blendedness beside the catalogue: dv_infer_fields_measure plus the four weighted sums per galaxy
+int dv_infer_fields_measure_blend(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                  const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                  const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                  double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                  int32_t* iters, int32_t* status, double* blend, int32_t* npix) {
+  BlendOut bo;
+  bo.blend = blend;
+  bo.npix = npix;
+  return infer_fields_measure_entry("dv_infer_fields_measure_blend", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
+                                    params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
+                                    iters, status, &bo);
 }
 
 // ---- the Monte-Carlo catalogue beside it: dv_infer_fields_measure plus means and standard deviations of

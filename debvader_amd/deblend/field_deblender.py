@@ -440,6 +440,13 @@ class DeblendFieldBatch:
 
         return catalogue_mc_dtype(nb_of_bands)
 
+    @staticmethod
+    def blend_columns():
+        """What deblend_fields(blendedness=True) appends behind measure_columns: the recarray of measure_blendedness."""
+        from debvader_amd.measure.measurement import blend_dtype
+
+        return blend_dtype()
+
     def __init__(self, net, field_images, cutout_size=59, nb_of_bands=6, normalise=False):
         """
         parameters:
@@ -488,7 +495,8 @@ class DeblendFieldBatch:
 
     def deblend_fields(self, galaxy_distances_to_center=None, mse_criterion=100.0, on_device=False,
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
-                       measure=False, return_fields=True, measure_samples=0, optimise_positions=False):
+                       measure=False, return_fields=True, measure_samples=0, blendedness=False,
+                       optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -526,10 +534,31 @@ class DeblendFieldBatch:
         pass, then the decodes), each is measured on the GPU, and the recarrays gain flux_mc_mean, flux_mc_std (per band)
         and <q>_mc_mean, <q>_mc_std for q in row, col, Mrr, Mrc, Mcc, sigma, e1, e2 over the n_ok samples whose
         measurement converged (measure_mc_columns).  The other columns and the fields are those of the same call without
-        it.  It is not available with optimise_positions=True or epistemic_uncertainty_estimation=True either."""
+        it.  It is not available with optimise_positions=True or epistemic_uncertainty_estimation=True either.
+
+        blendedness=True (with measure=True and on_device=True, with or without return_fields): how much of the light
+        under every galaxy's own weight belongs to its neighbours (dv_infer_fields_measure_blend).
+        The recarrays gain blend_weight, blend_child, blend_model, blend_data, blend_npix, blendedness and
+        blendedness_data (blend_columns; debvader_amd.measure.measurement.measure_blendedness describes them): sums under
+        the Gaussian of the galaxy's adaptive moments over its stamp, the composited mean field and the observed field,
+        taken on the GPU once the field's composite is complete.  The other columns and the fields are those of the same
+        call without it.  It is not available with optimise_positions=True, epistemic_uncertainty_estimation=True or
+        measure_samples."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
+        blendedness = bool(blendedness)
+        if blendedness and not measure:
+            raise ValueError("blendedness=True needs measure=True: the weight of the blendedness sums is the Gaussian of the "
+                             "measured adaptive moments")
+        if blendedness and not on_device:
+            raise ValueError("blendedness=True needs on_device=True: the sums are taken where the stamps and the composited "
+                             "fields lie in device memory (dv_infer_fields_measure_blend); on the default path use "
+                             "debvader_amd.measure.measurement.measure_blendedness on the returned stamps")
+        if blendedness and (fit or mc or int(measure_samples or 0)):
+            raise ValueError("blendedness=True cannot be combined with optimise_positions=True, "
+                             "epistemic_uncertainty_estimation=True or measure_samples: the blendedness sums are a stage of "
+                             "the plain measuring composite call only (dv_infer_fields_measure_blend)")
         if int(measure_samples) != measure_samples or int(measure_samples) < 0:
             raise ValueError(f"measure_samples must be an integer >= 0, got {measure_samples}")
         nmc = int(measure_samples)
@@ -595,6 +624,9 @@ class DeblendFieldBatch:
                     out = eng.infer_fields_measure_mc(self.field_images, starts, field_ptr, places=places if return_fields else None,
                                                       seed=seed, mc_seed=core.next_seed(), nsamples=nmc,
                                                       return_fields=bool(return_fields))
+                elif blendedness:
+                    out = eng.infer_fields_measure_blend(self.field_images, starts, field_ptr, places, seed=seed,
+                                                         return_fields=bool(return_fields))
                 elif measure:
                     out = eng.infer_fields_measure(self.field_images, starts, field_ptr, places=places if return_fields else None,
                                                    seed=seed, return_fields=bool(return_fields))
@@ -634,6 +666,11 @@ class DeblendFieldBatch:
                 columns = columns + self.measure_mc_columns(nb)
                 cat_mc = catalogue_mc_records(out["flux_mc_mean"], out["flux_mc_std"], out["shape_mc_mean"],
                                               out["shape_mc_std"], out["n_ok"])
+            if blendedness:
+                from debvader_amd.measure.measurement import blend_records
+
+                columns = columns + self.blend_columns()
+                cat_bl = blend_records(out["blend"], out["npix"])
             cat = catalogue_records(out["flux"], out["flux_err"], out["shape"], out["iters"], out["status"]) if on_device \
                 else measure_stamps(out["loc"], out["scale"], ctx=self._ctx)
             # a stamp's pixel (row, col) is the field's pixel start + (row, col); distances count from pixel int(F / 2)
@@ -656,6 +693,9 @@ class DeblendFieldBatch:
                 if nmc:
                     for k in cat_mc.dtype.names:
                         rec[k] = cat_mc[k][lo:hi]
+                if blendedness:
+                    for k in cat_bl.dtype.names:
+                        rec[k] = cat_bl[k][lo:hi]
             if on_device:
                 rec["mse_center"] = mse_center[lo:hi]
                 if mc:

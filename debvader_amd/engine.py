@@ -570,6 +570,49 @@ class Context:
             check(lib.dv_scene_measure_mc(self._h, _fp(samples), S, n, cs, nb, C.byref(par), *ptrs))
         return out
 
+    def scene_blend(self, stamps, shape, status, places, model_fields, data_fields=None, field_ptr=None,
+                    band: int = 2) -> Dict[str, np.ndarray]:
+        """Blendedness sums of N galaxies on the GPU (dv_scene_blend): stamps (N, cs, cs, bands), the
+        mean stamps taken as float32; shape (N, 5) and status (N,), their scene_measure rows; places (N, 2), the field
+        position (row, col) of every stamp's top-left corner; model_fields (M, F, F, bands), the composited mean fields;
+        data_fields the observed fields of the same shape, or None; field_ptr (M + 1,): stamps field_ptr[m]:field_ptr[m + 1]
+        lie in field m (None: one field holds them all).  Returns {"blend" (N, 4): {W, A, Bm, Bd} = the sums of g, g * stamp,
+        g * model field, g * data field over the stamp's pixels inside the field, g the Gaussian of the galaxy's adaptive
+        moments in band `band`; "npix" (N,): the pixels summed}.  A row whose status is neither 0 nor 2, whose shape is not
+        finite or whose det M is not above 1e-6 gets four NaN and npix -1; without data_fields Bd is NaN."""
+        stamps = np.ascontiguousarray(stamps, dtype=np.float32)
+        if stamps.ndim != 4 or stamps.shape[1] != stamps.shape[2]:
+            raise ValueError(f"expected square stamps (N, cs, cs, bands), got {stamps.shape}")
+        n, cs, nb = stamps.shape[0], stamps.shape[1], stamps.shape[3]
+        model = np.ascontiguousarray(model_fields, dtype=np.float64)
+        if model.ndim != 4 or model.shape[1] != model.shape[2] or model.shape[3] != nb:
+            raise ValueError(f"expected model fields (M, F, F, {nb}), got {model.shape}")
+        data = None
+        if data_fields is not None:
+            data = np.ascontiguousarray(data_fields, dtype=np.float64)
+            if data.shape != model.shape:
+                raise ValueError(f"expected data fields {model.shape}, got {data.shape}")
+        shape = np.ascontiguousarray(shape, dtype=np.float64)
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        places = _i32_rows(places, "stamp placements")
+        if shape.shape != (n, 5) or status.shape != (n,) or places.shape != (n, 2):
+            raise ValueError(f"expected shape ({n}, 5), status ({n},) and places ({n}, 2), got {shape.shape}, {status.shape}, "
+                             f"{places.shape}")
+        if not 0 <= int(band) < nb:
+            raise ValueError(f"band {band} asked for, the stamps have bands 0 .. {nb - 1}")
+        M = model.shape[0]
+        if field_ptr is None:
+            if M != 1:
+                raise ValueError(f"field_ptr is needed with {M} fields")
+            field_ptr = [0, n]
+        fp = check_field_ptr(field_ptr, M, n)
+        out = dict(blend=np.zeros((n, 4), np.float64), npix=np.zeros(n, np.int32))
+        if n:
+            check(lib.dv_scene_blend(self._h, _fp(stamps), _dp(shape), _ip(status), _ip(places),
+                                     fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs, nb, int(band), _dp(model), _dp(data), M,
+                                     model.shape[1], _dp(out["blend"]), _ip(out["npix"])))
+        return out
+
     CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
 
     def scene_detect(self, fields_r, thresh: float = 1.5, minarea: int = 4, nthresh: int = 64, cont: float = 1e-5,
@@ -1010,6 +1053,41 @@ class Engine:
     def scene_measure(self, mean, stddev=None, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_measure on this engine's GPU context."""
         return self.ctx.scene_measure(mean, stddev, **kw)
+
+    def infer_fields_measure_blend(self, fields, starts, field_ptr, places, seed=0, band: int = 2, sigma0: float = 3.0,
+                                   tol: float = 1e-10, max_iter: int = 200, return_fields=True, residual=True,
+                                   mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure() plus the blendedness sums (dv_infer_fields_measure_blend): returns its
+        dictionary, bit for bit, plus scene_blend's {"blend" (N, 4), "npix" (N,)} - the bits of scene_blend on infer_fields'
+        mean stamps, infer_fields_measure's rows, infer_fields_composite's mean fields and the source fields as data.  The
+        stamp sums run behind every chunk's measurement, the field sums once a field's composite is complete.  `places` is
+        always needed: with return_fields=False the mean field is still composited on the device (and never downloaded)."""
+        if places is None:
+            raise ValueError("places are needed for the blendedness sums, with return_fields=False too")
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places)
+        nb = fields.shape[3]
+        par = measure_params(band, sigma0, tol, max_iter, nb)
+        if return_fields:
+            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
+        else:
+            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
+            ptrs = [None, None, None, _dp(out.get("mse_center"))]
+        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
+                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32),
+                   blend=np.zeros((N, 4), np.float64), npix=np.zeros(N, np.int32))
+        check(lib.dv_infer_fields_measure_blend(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
+                                                _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]),
+                                                _ip(out["status"]), _dp(out["blend"]), _ip(out["npix"])))
+        return out
+
+    def infer_cutouts_measure_blend(self, field, starts, places, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_blend() for one field (F, F, bands): the field-sized results under singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_blend(fields, starts, fp, places, seed=seed, **kw))
+
+    def scene_blend(self, stamps, shape, status, places, model_fields, data_fields=None, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_blend on this engine's GPU context."""
+        return self.ctx.scene_blend(stamps, shape, status, places, model_fields, data_fields, **kw)
 
     def infer_fields_measure_mc(self, fields, starts, field_ptr, places=None, seed=0, mc_seed=0, nsamples=100, band: int = 2,
                                 sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, return_fields=True,

@@ -6,7 +6,9 @@ GPU (csrc/measure.hip): per-band fluxes and their errors summed over the network
 moments of one band - the centroid and second moments of the stamp under a Gaussian weight that is iterated until it matches
 the object.  Errors on the centroid, the moments, sigma, e1 and e2 (and a second error on the fluxes) come from the network's
 own Monte-Carlo decodes (measure_stamps_mc): every decode of a galaxy is measured and the measured
-rows are folded into a mean and a standard deviation per quantity.  A PSF correction is not part of it.
+rows are folded into a mean and a standard deviation per quantity.  Blendedness - how much of the light under a galaxy's
+own weight belongs to its neighbours - is DESIGN.md section 7l (measure_blendedness, csrc/blend.hip).  A PSF correction is not
+part of it.
 """
 import numpy as np
 
@@ -71,6 +73,63 @@ def catalogue_mc_records(flux_mc_mean, flux_mc_std, shape_mc_mean, shape_mc_std,
         rec[q + "_mc_std"] = np.asarray(shape_mc_std).reshape(n, 8)[:, k]
     rec["n_ok"] = n_ok
     return rec
+
+
+def blend_dtype():
+    """The columns of measure_blendedness' recarray: the four weighted sums and the pixel count the GPU takes, then the two
+    ratios the host derives from them."""
+    return [("blend_weight", "<f8"), ("blend_child", "<f8"), ("blend_model", "<f8"), ("blend_data", "<f8"),
+            ("blend_npix", "<i4"), ("blendedness", "<f8"), ("blendedness_data", "<f8")]
+
+
+def blend_records(blend, npix):
+    """The recarray of measure_blendedness from the arrays the engine returns: blend (N, 4) = {W, A, Bm, Bd}, npix (N,).
+    Derived on the host: blendedness = 1 - A / Bm, NaN where the row is ineligible (npix -1) or Bm <= 0;
+    blendedness_data = 1 - A / Bd, NaN where the row is ineligible or Bd <= 0 (or no data field was given)."""
+    blend = np.asarray(blend, dtype=np.float64).reshape(-1, 4)
+    npix = np.asarray(npix)
+    rec = np.recarray((blend.shape[0],), dtype=blend_dtype())
+    for k, name in enumerate(("blend_weight", "blend_child", "blend_model", "blend_data")):
+        rec[name] = blend[:, k]
+    rec["blend_npix"] = npix
+    A = blend[:, 1]
+    with np.errstate(all="ignore"):
+        for name, B in (("blendedness", blend[:, 2]), ("blendedness_data", blend[:, 3])):
+            ok = (npix >= 0) & (B > 0)                       # (NaN > 0 is False)
+            rec[name] = np.where(ok, 1.0 - A / np.where(ok, B, 1.0), np.nan)
+    return rec
+
+
+def measure_blendedness(stamps_mean, catalogue, places, model_fields, data_fields=None, field_ptr=None, band=2, ctx=None):
+    """Blendedness of N deblended galaxies on the GPU.
+
+    parameters:
+        stamps_mean: the network's mean stamps, (N, cutout_size, cutout_size, bands)
+        catalogue: their measure_stamps recarray (row, col, Mrr, Mrc, Mcc and status are read), measured in `band`
+        places: (N, 2), the field position (row, col) of every stamp's top-left corner - where the stamp was composited
+        model_fields: (M, F, F, bands), the composited mean fields (the sum of all mean stamps of a field); (F, F, bands)
+            for one field
+        data_fields: the observed fields of the same shape, or None
+        field_ptr: (M + 1,), stamps field_ptr[m]:field_ptr[m + 1] lie in field m; None: one field holds them all
+        ctx: the engine context to run on (None: the default context)
+    returns a np.recarray with, per galaxy, under the Gaussian weight g of its adaptive moments and over the stamp pixels
+    that lie inside the field: blend_weight = sum g, blend_child = sum g * stamp, blend_model = sum g * model field,
+    blend_data = sum g * data field (NaN without data_fields), blend_npix = the pixels summed, and, derived on the host,
+    blendedness = 1 - blend_child / blend_model - the share of the neighbours in the model, 0 for a galaxy alone in its
+    field - and blendedness_data = 1 - blend_child / blend_data, the same against the observed pixels (noisy, may be
+    negative).  A galaxy whose measurement failed (status 3), or whose moments are not finite or have det M <= 1e-6, gets
+    NaN and blend_npix = -1; a ratio whose denominator is not positive is NaN.
+    """
+    model = np.asarray(model_fields, dtype=np.float64)
+    if model.ndim == 3:
+        model = model[None]
+        data_fields = None if data_fields is None else np.asarray(data_fields, dtype=np.float64)[None]
+    shape = np.stack([np.asarray(catalogue[k], dtype=np.float64) for k in ("row", "col", "Mrr", "Mrc", "Mcc")], axis=1)
+    if ctx is None:
+        ctx = E.default_context()
+    out = ctx.scene_blend(stamps_mean, shape, np.asarray(catalogue["status"], dtype=np.int32), places, model, data_fields,
+                          field_ptr=field_ptr, band=band)
+    return blend_records(out["blend"], out["npix"])
 
 
 def measure_stamps_mc(samples, band=2, sigma0=3.0, tol=1e-10, max_iter=200, keep_samples=False, ctx=None):

@@ -470,6 +470,41 @@ int dv_infer_fields_measure_mc(dv_model* m, const double* fields, int32_t M, int
                                double* shape_std, int32_t* n_ok, double* sample_flux, double* sample_shape,
                                int32_t* sample_status);
 
+/* ---- blendedness: the share of its neighbours in the light under a galaxy's weight ----
+ * Float64 throughout.  For galaxy i of field m: P its mean stamp [cs][cs][nb] (float32 widened), {r0, c0, Mrr, Mrc, Mcc} and
+ * status its row of the measurement above, (pr, pc) = places[i], T the composited mean field of m ([F][F][nb]: the sum of all
+ * mean stamps of m in object order, the bits of dv_infer_fields_composite), D the observed field of m.  The row is eligible
+ * iff status is 0 or 2, the five shape values are finite and det = Mrr Mcc - Mrc^2 is finite and above 1e-6; an ineligible
+ * row gets blend = 4 NaN and npix = -1.  Otherwise, over the stamp pixels (r, c) with 0 <= pr + r < F and 0 <= pc + c < F
+ * (the pixels the composite keeps), with dr = r - r0, dc = c - c0 and
+ *   g = exp(qa dr^2 + qb dr dc + qc dc^2), qa = -Mcc / (2 det), qb = Mrc / det, qc = -Mrr / (2 det):
+ *   blend[i] = {W, A, Bm, Bd} = {sum g, sum g P[r,c,band], sum g T[pr+r,pc+c,band], sum g D[pr+r,pc+c,band]},
+ *   npix[i] = the number of pixels summed (0, with four zero sums, for a stamp wholly outside its field).
+ * The four sums visit the pixels with the same assignment to threads, round every product and sum on its own and reduce
+ * in one fixed order: a galaxy's row has the same bits wherever it sits in a batch, and for a galaxy alone in its field A
+ * and Bm have the same bits.  blendedness = 1 - A / Bm and blendedness_data = 1 - A / Bd are left to the caller.
+ * dv_scene_blend: host arrays; stamps [N][cs][cs][nb] float32, shape [N][5], status [N], places [N][2], field_ptr [M + 1]
+ * (stamps field_ptr[m] .. field_ptr[m + 1] lie in field m), model_fields and data_fields [M][F][F][nb]; data_fields may be
+ * null (Bd is NaN on every row); blend [N][4], npix [N].  Chunked against free device memory.
+ * dv_infer_fields_measure_blend: dv_infer_fields_measure (same arguments, same bits in every output it shares with it) with
+ * blend / npix as one more stage: A and W behind the measurement of every chunk, Bm and Bd once a field's composite is
+ * complete; T is the call's mean field, D the source field.  places is always needed.  In the catalogue-only form (the
+ * three field outputs null) the mean field is still composited in device memory (one more resident field per field); it is
+ * never downloaded.  The rows have the bits of dv_scene_blend on dv_infer_fields' stamps, dv_infer_fields_measure's rows
+ * and dv_infer_fields_composite's mean fields.  Refused before any GPU work (DV_E_INVALID): by
+ * dv_infer_fields_measure_blend what dv_infer_fields_measure refuses and a null places, blend or npix; by dv_scene_blend cs
+ * or nb outside 1 .. 4096 (the kernels keep nothing per pixel: no LDS bound), band outside 0 .. nb - 1, a missing array, a
+ * field_ptr that does not run from 0 to N without decreasing (checked whole before anything is indexed by it), a placement
+ * beyond +-2^28. */
+int dv_scene_blend(dv_ctx* ctx, const float* stamps, const double* shape, const int32_t* status, const int32_t* places,
+                   const int64_t* field_ptr, int64_t N, int32_t cs, int32_t nb, int32_t band, const double* model_fields,
+                   const double* data_fields, int32_t M, int32_t F, double* blend, int32_t* npix);
+int dv_infer_fields_measure_blend(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                  const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                  const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                  double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                  int32_t* iters, int32_t* status, double* blend, int32_t* npix);
+
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)
  * keeps per field, in device memory, `work` (what the next pass detects on and cuts from, at first the field), `final`

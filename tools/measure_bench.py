@@ -28,6 +28,16 @@ Per leg: the median, the spread (max - min over the median) and every run.  GPU 
     python tools/measure_bench.py --samples 100 --fields 256 [--repeat 5] [--host-fields 4]
 
 With --profile-one: warm up, one fp32 call (a), exit.
+
+--blend: what the blendedness stage costs in the catalogue-only call, on the same build and box -
+
+    (a) catalogue       :  deblend_fields(d, on_device=True, measure=True, return_fields=False)
+    (b) catalogue+blend :  the same with blendedness=True: the device-side mean field is composited, the child sums run
+                           behind every chunk's measurement, the parent sums once a field is complete
+
+    python tools/measure_bench.py --blend [--fields 1024] [--size 259] [--repeat 5]
+
+The cost is reported, not gated.
 """
 import argparse
 import io
@@ -134,6 +144,45 @@ def main_samples(a):
     print(json.dumps(result))
 
 
+def main_blend(a):
+    rng = np.random.default_rng(0)
+    F, M = a.size, a.fields
+    base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
+    fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    quiet = io.StringIO()
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "blend": True}
+    dists = None
+    for dtype in a.dtypes.split(","):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections; max_batch {a.max_batch}")
+        legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False),
+                "catalogue+blend": lambda: _device(net, fields, dists, measure=True, return_fields=False, blendedness=True)}
+        with redirect_stdout(quiet):
+            for fn in legs.values():           # warm-up
+                fn()
+            times = {k: [] for k in legs}
+            n = 0
+            for _ in range(a.repeat):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    n = fn()
+                    times[k].append(time.perf_counter() - t0)
+        result[dtype] = {"stamps": n}
+        for k in legs:
+            t = np.array(times[k])
+            print(_row(f"{dtype} {k}", t, n, M))
+            result[dtype][k.replace("+", "_") + "_ms"] = [round(1e3 * x, 2) for x in t]
+        tc, tb = (float(np.median(times[k])) for k in legs)
+        spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
+        print(f"{dtype} catalogue+blend / catalogue {tb / tc:.3f}: {1e3 * (tb - tc):+.1f} ms for {n} galaxies "
+              f"(spreads {spread(times['catalogue']):.3f} and {spread(times['catalogue+blend']):.3f})")
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fields", type=int, default=1024)
@@ -144,7 +193,10 @@ def main():
     ap.add_argument("--dtypes", default="float32,bf16")
     ap.add_argument("--profile-one", action="store_true")
     ap.add_argument("--samples", type=int, default=0)
+    ap.add_argument("--blend", action="store_true")
     a = ap.parse_args()
+    if a.blend:
+        return main_blend(a)
     if a.samples > 0:
         return main_samples(a)
     rng = np.random.default_rng(0)
