@@ -172,6 +172,56 @@ __global__ __launch_bounds__(256) void blend_composite_mean_kernel(double* __res
     }
   }
 }
+
+// ---- the end-of-loop sums of a resident field set (dv_field_set_blend) ------------------------------------
+// Row gi of the set's resident rows (shape, status, places, sfield: every stamp of every measured pass, in call order)
+// against the set's stacks as they are now: sums [n][4] = {Bm, Bd, R1, R2} = sum g mean, sum g base, sum g final,
+// sum g (final final) over the stamp pixels inside the field - the pixels, the weight and the eligibility of the two
+// kernels above.  One walk of the footprint reads the three stacks at the same field element; the square is a product of
+// its own, rounded before it meets g.  The first two sums are blend_parent_kernel's operations in its order (the block sum
+// treats every k on its own), so they have its bits for the same row and stacks.  base null (a cumulative set keeps none):
+// Bd is NaN.  An ineligible row gets four NaN.
+__global__ __launch_bounds__(BL_THREADS) void blend_set_kernel(const double* __restrict__ shape,
+                                                               const int* __restrict__ status,
+                                                               const int* __restrict__ places,
+                                                               const int* __restrict__ sfield, int cs, int nb, int band,
+                                                               int F, const double* __restrict__ mean,
+                                                               const double* __restrict__ base,
+                                                               const double* __restrict__ fin, double* __restrict__ sums) {
+  __shared__ double s_red[4 * 4];
+  const long gi = blockIdx.x;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  BlWeight w;
+  if (!bl_weight(shape + gi * 5, status[gi], w)) {     // (uniform: every thread read the same row)
+    if (threadIdx.x == 0) sums[gi * 4 + 0] = sums[gi * 4 + 1] = sums[gi * 4 + 2] = sums[gi * 4 + 3] = nan;
+    return;
+  }
+  const int pr = places[2 * gi], pc = places[2 * gi + 1];
+  const long fo = (long)sfield[gi] * F * F * nb + band;
+  const double* T = mean + fo;
+  const double* D = base ? base + fo : nullptr;
+  const double* R = fin + fo;
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int e = threadIdx.x; e < cs * cs; e += BL_THREADS) {
+    const int r = e / cs, c = e - r * cs;
+    if ((unsigned)(pr + r) >= (unsigned)F || (unsigned)(pc + c) >= (unsigned)F) continue;
+    const double g = bl_gauss(w, r, c);
+    const long fe = ((long)(pr + r) * F + (pc + c)) * nb;
+    a[0] += g * T[fe];
+    if (D) a[1] += g * D[fe];
+    const double x = R[fe];
+    const double xx = x * x;
+    a[2] += g * x;
+    a[3] += g * xx;
+  }
+  bl_block_sum<4>(a, s_red);
+  if (threadIdx.x == 0) {
+    sums[gi * 4 + 0] = a[0];
+    sums[gi * 4 + 1] = D ? a[1] : nan;
+    sums[gi * 4 + 2] = a[2];
+    sums[gi * 4 + 3] = a[3];
+  }
+}
 }  // namespace
 
 // the refusals of the stamp-level call, before any GPU work: the kernels hold nothing per pixel, so the sizes are bounded
@@ -217,6 +267,17 @@ int launch_blend_composite_mean(double* mean_f, int F, int nb, const float* loc,
   const dim3 grid((unsigned)(((long)F * F + 255) / 256), (unsigned)nfields);
   hipLaunchKernelGGL(blend_composite_mean_kernel, grid, dim3(256), 0, s, mean_f, F, nb, loc, places_dev, n, cs, fptr_dev, f0,
                      fy0, obase);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+// the n resident rows of a field set against its stacks [M][F][F][nb] (sfield counts from field 0); base_dev null: Bd = NaN
+int launch_blend_set(const double* shape_dev, const int* status_dev, const int* places_dev, const int* sfield_dev, int n, int cs,
+                     int nb, int band, int F, const double* mean_dev, const double* base_dev, const double* final_dev,
+                     double* sums_dev, hipStream_t s) {
+  if (n <= 0) return OK;
+  hipLaunchKernelGGL(blend_set_kernel, dim3((unsigned)n), dim3(BL_THREADS), 0, s, shape_dev, status_dev, places_dev,
+                     sfield_dev, cs, nb, band, F, mean_dev, base_dev, final_dev, sums_dev);
   DV_HIP(hipGetLastError());
   return OK;
 }

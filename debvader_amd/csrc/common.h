@@ -331,6 +331,12 @@ int launch_blend_parent(const double* shape_dev, const int* status_dev, const in
                         double* blend_dev, hipStream_t s);
 int launch_blend_composite_mean(double* mean_f, int F, int nb, const float* loc, const int* places_dev, int n, int cs,
                                 const int* fptr_dev, int f0, int fy0, int nfields, long obase, hipStream_t s);
+// the end-of-loop sums of a resident field set: per resident row {Bm, Bd, R1, R2} = the sums of g mean, g base,
+// g final, g final^2 over the stamp pixels inside the field, against stacks [M][F][F][nb] that start at field 0; base_dev
+// null: Bd = NaN; an ineligible row gets four NaN
+int launch_blend_set(const double* shape_dev, const int* status_dev, const int* places_dev, const int* sfield_dev, int n, int cs,
+                     int nb, int band, int F, const double* mean_dev, const double* base_dev, const double* final_dev,
+                     double* sums_dev, hipStream_t s);
 int scene_blend(const float* stamps_h, const double* shape_h, const int32_t* status_h, const int32_t* places_h,
                 const int64_t* field_ptr, int64_t N, int cs, int nb, int band, const double* model_h, const double* data_h,
                 int M, int F, double* blend_h, int32_t* npix_h, int64_t chunk, int64_t gmax, hipStream_t s);

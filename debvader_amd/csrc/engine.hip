@@ -580,11 +580,46 @@ struct dv_field_set {
   dv::DevBuf<double> mse_part, fmse;             // partial sums and results of the field_mse reduction
   dv::StampTables tab;                           // the per-stamp tables of a pass, kept between passes and grown on demand
   std::vector<double> fmse_h;                     // host side of fmse
+  // the catalogue of the measured passes (dv_field_set_pass_measure).  Resident rows: {shape[5], status,
+  // place, field} of every stamp of every pass that took child sums, in call order; nrows of them are kept, the tail up
+  // to rcap is where the running pass measures.  The other columns of a pass leave with it: per-pass buffers.
+  dv::DevBuf<double> rshape, rsums;              // [rcap][5]; [nrows][4]: the sums of dv_field_set_blend
+  dv::DevBuf<int> rstatus, rplaces, rfield;      // [rcap], [rcap][2], [rcap]
+  size_t nrows = 0, rcap = 0;
+  dv::DevBuf<double> cflux, cferr, cblend;       // [N][nb], [N][nb], [N][4] of the running pass
+  dv::DevBuf<int> citers, cnpix;                 // [N]
+  // room for `need` resident rows: a larger set of buffers takes the kept rows over on s (the old ones go once s is idle)
+  int rows_reserve(size_t need, hipStream_t s) {
+    if (need <= rcap) return dv::OK;
+    const size_t cap = std::max<size_t>({need, 2 * rcap, 1024});
+    dv::DevBuf<double> sh;
+    dv::DevBuf<int> st, pl, fi;
+    DV_TRY(sh.alloc(cap * 5));
+    DV_TRY(st.alloc(cap));
+    DV_TRY(pl.alloc(cap * 2));
+    DV_TRY(fi.alloc(cap));
+    if (nrows > 0) {
+      DV_HIP(hipMemcpyAsync(sh, rshape, nrows * 5 * sizeof(double), hipMemcpyDeviceToDevice, s));
+      DV_HIP(hipMemcpyAsync(st, rstatus, nrows * sizeof(int), hipMemcpyDeviceToDevice, s));
+      DV_HIP(hipMemcpyAsync(pl, rplaces, nrows * 2 * sizeof(int), hipMemcpyDeviceToDevice, s));
+      DV_HIP(hipMemcpyAsync(fi, rfield, nrows * sizeof(int), hipMemcpyDeviceToDevice, s));
+      DV_HIP(hipStreamSynchronize(s));
+    }
+    rshape = std::move(sh);
+    rstatus = std::move(st);
+    rplaces = std::move(pl);
+    rfield = std::move(fi);
+    rcap = cap;
+    return dv::OK;
+  }
 };
 
 static void field_set_release(dv_field_set* fs) {
-  for (dv::DevBuf<double>* b : {&fs->base, &fs->work, &fs->next, &fs->fin, &fs->mean, &fs->stddev, &fs->mse_part, &fs->fmse})
+  for (dv::DevBuf<double>* b : {&fs->base, &fs->work, &fs->next, &fs->fin, &fs->mean, &fs->stddev, &fs->mse_part, &fs->fmse,
+                                &fs->rshape, &fs->rsums, &fs->cflux, &fs->cferr, &fs->cblend})
     b->reset();
+  for (dv::DevBuf<int>* b : {&fs->rstatus, &fs->rplaces, &fs->rfield, &fs->citers, &fs->cnpix}) b->reset();
+  fs->nrows = fs->rcap = 0;
   fs->tab = dv::StampTables();
   fs->open = false;
 }
@@ -5566,18 +5601,33 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
   return DV_OK;
 }
 
-int dv_field_set_pass(dv_field_set* fs, const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
-                      uint64_t seed, double* mse_center, double* field_mse) {
-  DV_TRY(field_set_live(fs, "dv_field_set_pass"));
+// mo: dv_field_set_pass_measure - the measurement of 7j behind every chunk's forward pass; bo beside it: the child sums of 7l
+// behind that, and the pass's rows join the set's resident rows.  Without mo this is dv_field_set_pass as it
+// was: the same launches in the same order.
+static int field_set_pass_impl(dv_field_set* fs, const char* who, const int32_t* starts, const int32_t* places,
+                               const int64_t* field_ptr, int64_t N, uint64_t seed, double* mse_center, double* field_mse,
+                               const MeasureOut* mo = nullptr, const BlendOut* bo = nullptr) {
+  DV_TRY(field_set_live(fs, who));
   dv_model* m = fs->m;
   const int M = fs->M, F = fs->F, nb = fs->nb;
   if (N > 0 && (!places || !mse_center || !field_mse)) {
-    set_error("dv_field_set_pass: places, mse_center and field_mse must all be given");
+    set_error("%s: places, mse_center and field_mse must all be given", who);
     return DV_E_INVALID;
+  }
+  if (mo) {
+    DV_TRY(measure_check(who, m->A.H, nb, mo->par.band, mo->par.sigma0, mo->par.tol, mo->par.max_iter));
+    if (N > 0 && (!mo->flux || !mo->flux_err || !mo->shape || !mo->iters || !mo->status)) {
+      set_error("%s: flux, flux_err, shape, iters and status must all be given", who);
+      return DV_E_INVALID;
+    }
+    if (bo && N >= 0 && (int64_t)fs->nrows + N >= ((int64_t)1 << 31)) {
+      set_error("%s: %zu resident rows and %ld more, at most 2^31 - 1 per set", who, fs->nrows, (long)N);
+      return DV_E_INVALID;
+    }
   }
   std::vector<int32_t> sfield;
   std::vector<int> fptr32;
-  DV_TRY(fields_tables(m, "dv_field_set_pass", M, field_ptr, N, F, nb, starts, places, sfield, fptr32));
+  DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, starts, places, sfield, fptr32));
   if (N == 0) return DV_OK;
   TinyCall tiny(m, N);
   DV_HIP(hipSetDevice(m->ctx->device));
@@ -5610,6 +5660,29 @@ int dv_field_set_pass(dv_field_set* fs, const int32_t* starts, const int32_t* pl
   j.sinks.res2_f = fs->cumulative ? nullptr : fs->fin.get();
   j.sinks.places_d = tab.places;
   j.sinks.mse = tab.mse;
+  const size_t n = (size_t)N, row0 = fs->nrows;
+  if (mo) {
+    // the pass measures into the tail of the resident rows (pipeline row r is resident row row0 + r); they are kept, and
+    // the placements and fields set beside them, only if the pass took child sums and ran to its end
+    DV_TRY(fs->rows_reserve(row0 + n, s));
+    for (DevBuf<double>* b : {&fs->cflux, &fs->cferr}) DV_TRY(b->ensure(n * nb));
+    DV_TRY(fs->citers.ensure(n));
+    j.ms.flux = fs->cflux;
+    j.ms.ferr = fs->cferr;
+    j.ms.shape = fs->rshape.get() + row0 * 5;
+    j.ms.iters = fs->citers;
+    j.ms.status = fs->rstatus.get() + row0;
+    j.ms.band = mo->par.band;
+    j.ms.max_iter = mo->par.max_iter;
+    j.ms.sigma0 = mo->par.sigma0;
+    j.ms.tol = mo->par.tol;
+    if (bo) {
+      DV_TRY(fs->cblend.ensure(n * 4));
+      DV_TRY(fs->cnpix.ensure(n));
+      j.bl.blend = fs->cblend;
+      j.bl.npix = fs->cnpix;
+    }
+  }
   DV_TRY(infer_pipelined(m, j));
   // field_mse of the working residual against its successor, then the successor takes its place (fields with stamps only)
   DV_TRY(launch_scene_field_mse(fs->work, fs->next, tab.fptr, M, felems, fs->mse_part, fs->fmse, s));
@@ -5617,11 +5690,87 @@ int dv_field_set_pass(dv_field_set* fs, const int32_t* starts, const int32_t* pl
   std::vector<double>& fm = fs->fmse_h;
   DV_HIP(hipMemcpyAsync(mse_center, tab.mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
   DV_HIP(hipMemcpyAsync(fm.data(), fs->fmse, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (mo) {
+    DV_HIP(hipMemcpyAsync(mo->flux, fs->cflux, n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(mo->flux_err, fs->cferr, n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(mo->shape, fs->rshape.get() + row0 * 5, n * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(mo->iters, fs->citers, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(mo->status, fs->rstatus.get() + row0, n * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+  if (bo) {
+    // {W, A}: the first two of the four doubles the child kernel's rows have
+    DV_HIP(hipMemcpy2DAsync(bo->blend, 2 * sizeof(double), fs->cblend, 4 * sizeof(double), 2 * sizeof(double), n,
+                            hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(bo->npix, fs->cnpix, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(fs->rplaces.get() + row0 * 2, tab.places, n * 2 * sizeof(int), hipMemcpyDeviceToDevice, s));
+    DV_HIP(hipMemcpyAsync(fs->rfield.get() + row0, tab.sfield, n * sizeof(int), hipMemcpyDeviceToDevice, s));
+  }
   DV_HIP(hipStreamSynchronize(s));
   for (int f = 0; f < M; ++f)
     if (fptr32[f + 1] > fptr32[f]) field_mse[f] = fm[f];
+  if (bo) fs->nrows = row0 + n;
   drain.dismiss();
   return prof_flush(m);
+}
+
+int dv_field_set_pass(dv_field_set* fs, const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                      uint64_t seed, double* mse_center, double* field_mse) {
+  return field_set_pass_impl(fs, "dv_field_set_pass", starts, places, field_ptr, N, seed, mse_center, field_mse);
+}
+
+// ---- the catalogue of the iterative loop -----------------------------------------------------------------------
+int dv_field_set_pass_measure(dv_field_set* fs, const int32_t* starts, const int32_t* places, const int64_t* field_ptr,
+                              int64_t N, uint64_t seed, const dv_measure_params* params, double* mse_center, double* field_mse,
+                              double* flux, double* flux_err, double* shape, int32_t* iters, int32_t* status, double* child,
+                              int32_t* npix) {
+  const char* who = "dv_field_set_pass_measure";
+  DV_TRY(field_set_live(fs, who));
+  if (!params) {
+    set_error("%s: params must be given", who);
+    return DV_E_INVALID;
+  }
+  if ((child == nullptr) != (npix == nullptr)) {
+    set_error("%s: child and npix go together (both null: no child sums are taken and no resident rows are kept)", who);
+    return DV_E_INVALID;
+  }
+  MeasureOut mo;
+  mo.par = *params;
+  mo.flux = flux;
+  mo.flux_err = flux_err;
+  mo.shape = shape;
+  mo.iters = iters;
+  mo.status = status;
+  BlendOut bo;
+  bo.blend = child;
+  bo.npix = npix;
+  return field_set_pass_impl(fs, who, starts, places, field_ptr, N, seed, mse_center, field_mse, &mo, child ? &bo : nullptr);
+}
+
+int dv_field_set_blend(dv_field_set* fs, int32_t band, int64_t n_expected, double* sums) {
+  const char* who = "dv_field_set_blend";
+  DV_TRY(field_set_live(fs, who));
+  DV_TRY(blend_check(who, fs->m->A.H, fs->nb, band));
+  if (n_expected != (int64_t)fs->nrows) {
+    set_error("%s: %ld rows expected, the set holds %zu resident rows", who, (long)n_expected, fs->nrows);
+    return DV_E_INVALID;
+  }
+  if (fs->nrows > 0 && !sums) {
+    set_error("%s: sums must be given", who);
+    return DV_E_INVALID;
+  }
+  if (fs->nrows == 0) return DV_OK;
+  DV_HIP(hipSetDevice(fs->m->ctx->device));
+  hipStream_t s = fs->m->ctx->stream;
+  StreamDrain drain(s);
+  const size_t n = fs->nrows;
+  DV_TRY(fs->rsums.ensure(n * 4));
+  DV_TRY(launch_blend_set(fs->rshape, fs->rstatus, fs->rplaces, fs->rfield, (int)n, fs->m->A.H, fs->nb, band, fs->F, fs->mean,
+                          fs->cumulative ? nullptr : fs->base.get(), (fs->cumulative ? fs->work : fs->fin).get(), fs->rsums,
+                          s));
+  DV_HIP(hipMemcpyAsync(sums, fs->rsums, n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipStreamSynchronize(s));
+  drain.dismiss();
+  return DV_OK;
 }
 
 int dv_field_set_read(dv_field_set* fs, int32_t which, double* out) {

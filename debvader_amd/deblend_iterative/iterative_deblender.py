@@ -215,6 +215,7 @@ class IterativeDeblendFieldBatch:
         self.res_deblend = None
         self.mse = [[] for _ in range(self.nb_of_fields)]
         self._fields = None
+        self._no_fields = False
 
     def _records(self, kept, dd, mse_center, passed, offset, iteration):
         n = len(kept)
@@ -231,6 +232,35 @@ class IterativeDeblendFieldBatch:
         rec["iteration"] = iteration
         return rec
 
+    @staticmethod
+    def catalogue_columns(nb_of_bands, blendedness=False):
+        """What iterative_catalogue(measure=True) appends behind COLUMNS: the catalogue of measure_stamps and `seen_before`;
+        with blendedness=True also the columns of measure_blendedness and the residual statistic."""
+        from debvader_amd.measure.measurement import blend_dtype, catalogue_dtype, residual_dtype
+
+        cols = catalogue_dtype(nb_of_bands) + [("seen_before", "<i8")]
+        return cols + (blend_dtype() + residual_dtype() if blendedness else [])
+
+    @staticmethod
+    def seen_before(iteration, centroids, match_radius):
+        """For the rows of one field in recarray order: the index of the nearest row of an EARLIER pass whose centroid
+        (field coordinates) lies within match_radius pixels, a tie going to the lowest index; -1 without one, and for
+        every row of pass 0."""
+        iteration = np.asarray(iteration)
+        c = np.asarray(centroids, dtype=np.float64).reshape(-1, 2)
+        out = np.full(len(c), -1, dtype=np.int64)
+        for i in np.nonzero(iteration > 0)[0]:
+            earlier = np.nonzero(iteration < iteration[i])[0]
+            if not len(earlier):
+                continue
+            with np.errstate(invalid="ignore"):
+                d2 = ((c[earlier] - c[i]) ** 2).sum(axis=1)
+                d2 = np.where(d2 <= float(match_radius) ** 2, d2, np.inf)      # (a NaN centroid matches nothing)
+            j = int(np.argmin(d2))                                             # (the first minimum: the lowest index)
+            if np.isfinite(d2[j]):
+                out[i] = earlier[j]
+        return out
+
     def iterative_deblending(self, mse_criterion=100.0, mode="reference", max_iterations=None):
         """Run the loop on every field; returns a list of M recarrays (kept in self.res_deblend) with the columns of
         DeblendFieldBatch's on-device pass plus `iteration`, the pass a row was deblended in.  self.mse[m] has one entry
@@ -243,7 +273,39 @@ class IterativeDeblendFieldBatch:
         mode="cumulative" (engine-specific): every pass subtracts from the working residual, so pass k sees the field
             with everything found so far removed; a field goes on while a pass deblends at least one galaxy, for at most
             max_iterations passes (None: DEFAULT_MAX_ITERATIONS_CUMULATIVE = 10).
-        In both modes get_residual_fields() is the field minus every deblended galaxy of every pass."""
+        In both modes get_residual_fields() is the field minus every deblended galaxy of every pass.
+
+        iterative_catalogue() is this loop with the catalogue arguments behind these three; this method is that one with
+        every one of them at its default, which makes the calls this method always made."""
+        return self.iterative_catalogue(mse_criterion=mse_criterion, mode=mode, max_iterations=max_iterations)
+
+    def iterative_catalogue(self, mse_criterion=100.0, mode="reference", max_iterations=None, measure=False,
+                            blendedness=False, return_fields=True, band=2, sigma0=3.0, tol=1e-10, max_iter=200,
+                            match_radius=2.0):
+        """iterative_deblending() with a catalogue measured on the GPU: the same loop, the same
+        list of M recarrays (kept in self.res_deblend), self.mse and fields, and with every argument behind the first
+        three left at its default the same calls.  The arguments are a method of their own because the parameter list of
+        iterative_deblending is the reference's and is kept as it is.
+
+        measure=True: every pass also measures its stamps where they lie on the GPU
+            (FieldSet.deblend_pass_measure with band, sigma0, tol, max_iter as in measure_stamps) and the recarrays carry
+            COLUMNS plus measurement.catalogue_dtype(bands) plus `seen_before`: for a row of pass k > 0 the index, in its
+            field's recarray, of the nearest row of an earlier pass whose centroid - place + (row, col) in field pixels, the
+            stamp's centre pixel for a row with status 3 - lies within match_radius pixels (a tie goes to the lowest
+            index); -1 when there is none, and for every row of pass 0.  Every column shared with a measure=False run from
+            the same seed counter, self.mse and the fields have the same bits.
+        blendedness=True (needs measure=True): after the last pass one FieldSet.blend_sums call takes, per galaxy of
+            every pass, the sums that need the complete set, and the recarrays also carry measurement.blend_dtype() -
+            blend_model against the predicted mean fields of ALL passes, blend_data against the fields as given - and
+            measurement.residual_dtype(): resid_sum, resid_sq, resid_mean, resid_rms of the final residual under the
+            galaxy's weight.  In mode="reference" a galaxy that is deblended in several passes is in the predicted mean
+            field several times, so its blendedness counts its own earlier copies as neighbours (seen_before finds
+            them).  In mode="cumulative" the set keeps no copy of the fields as given: blend_data and blendedness_data are
+            NaN on every row.
+        return_fields=False: the three field-sized downloads at the end of the loop are skipped;
+            get_residual_fields() and get_predicted_fields() then raise.
+
+        mse_criterion, mode, max_iterations: as in iterative_deblending."""
         if mode not in ("reference", "cumulative"):
             raise ValueError(f"mode must be 'reference' (the reference's residual and stopping rule) or 'cumulative' "
                              f"(every pass subtracts from the working residual), got {mode!r}")
@@ -252,7 +314,15 @@ class IterativeDeblendFieldBatch:
             max_iterations = self.DEFAULT_MAX_ITERATIONS_CUMULATIVE
         if max_iterations is not None and int(max_iterations) < 0:
             raise ValueError(f"max_iterations must be at least 0, got {max_iterations}")
+        if blendedness and not measure:
+            raise ValueError("blendedness=True needs measure=True: the weight of the sums is the measured galaxy's")
+        if measure and not (np.isfinite(match_radius) and match_radius >= 0):
+            raise ValueError(f"match_radius must be finite and at least 0, got {match_radius}")
         M, F, cs = self.nb_of_fields, self.field_size, self.cutout_size
+        self._fields = None
+        self._no_fields = not return_fields
+        extra = [[] for _ in range(M)]       # measure=True: per field and pass, what joins the records at the end
+        nrows = 0                            # stamps of the measured passes so far: the resident row of a pass's stamp 0
         core = self.net._core
         eng = core.engine
         self.nb_of_detected_objects = []
@@ -280,7 +350,11 @@ class IterativeDeblendFieldBatch:
                 places = (po + dd).astype(np.int64)
                 eng.set_normalise(bool(self.normalise))
                 try:
-                    out = fs.deblend_pass(starts, places, field_ptr, seed=core.next_seed())
+                    if measure:
+                        out = fs.deblend_pass_measure(starts, places, field_ptr, seed=core.next_seed(), band=band,
+                                                      sigma0=sigma0, tol=tol, max_iter=max_iter, blend=bool(blendedness))
+                    else:
+                        out = fs.deblend_pass(starts, places, field_ptr, seed=core.next_seed())
                 finally:
                     eng.set_normalise(False)
                 passed = ~(out["mse_center"] > mse_criterion)
@@ -295,6 +369,12 @@ class IterativeDeblendFieldBatch:
                         continue
                     counts[m] = n
                     steps[m].append(self._records(kept[m], dd[lo:hi], out["mse_center"][lo:hi], passed[lo:hi], total[m], k))
+                    if measure:
+                        e = {k: out[k][lo:hi] for k in ("flux", "flux_err", "shape", "iters", "status")}
+                        e["places"] = np.asarray(places[lo:hi], dtype=np.float64)
+                        if blendedness:
+                            e.update(child=out["child"][lo:hi], npix=out["npix"][lo:hi], rows=np.arange(nrows + lo, nrows + hi))
+                        extra[m].append(e)
                     self.mse[m].append(float(out["field_mse"][m]))
                     total[m] += n
                     if not cumulative and not n > previous[m]:
@@ -304,16 +384,57 @@ class IterativeDeblendFieldBatch:
                 self.nb_of_deblended_galaxies += [counts]
                 print(f"iteration {k}: {N} galaxy(ies) deblended in {sum(c > 0 for c in counts)} field(s), "
                       f"{int(active.sum())} field(s) go on")
+                if measure:
+                    nrows += N
                 k += 1
-            self._fields = {"final": fs.read("final"), "mean": fs.read("mean"), "stddev": fs.read("stddev")}
+            sums = fs.blend_sums(band=band) if blendedness else None
+            if return_fields:
+                self._fields = {"final": fs.read("final"), "mean": fs.read("mean"), "stddev": fs.read("stddev")}
         finally:
             fs.close()
         empty = np.recarray((0,), dtype=self.COLUMNS)
         self.res_deblend = [np.concatenate(s).view(np.recarray) if s else empty.copy() for s in steps]
+        if measure:
+            self.res_deblend = [self._with_catalogue(r, e, sums, bool(blendedness), match_radius)
+                                for r, e in zip(self.res_deblend, extra)]
         return self.res_deblend
+
+    def _with_catalogue(self, rec, extra, sums, blendedness, match_radius):
+        """The records of one field with the catalogue columns behind them: the rows every pass measured, the end-of-loop
+        sums joined to them by the resident row number, and seen_before."""
+        from debvader_amd.measure.measurement import (STATUS_FAILED, blend_records, catalogue_records, residual_records)
+
+        nb = self.nb_of_bands
+        out = np.recarray((len(rec),), dtype=self.COLUMNS + self.catalogue_columns(nb, blendedness))
+        for k in rec.dtype.names:
+            out[k] = rec[k]
+
+        def col(name, width):
+            parts = [np.asarray(e[name]).reshape(len(e["status"]), *width) for e in extra]
+            return np.concatenate(parts) if parts else np.zeros((0, *width))
+
+        cat = catalogue_records(col("flux", (nb,)), col("flux_err", (nb,)), col("shape", (5,)),
+                                col("iters", ()).astype(np.int32), col("status", ()).astype(np.int32))
+        parts = [cat]
+        # the centroid in field pixels; a failed measurement stands at the pixel its window is centred on
+        centre = np.where((cat["status"] == STATUS_FAILED)[:, None], float(int(self.cutout_size / 2)),
+                          np.stack([cat["row"], cat["col"]], axis=1))
+        out["seen_before"] = self.seen_before(rec["iteration"], col("places", (2,)) + centre, match_radius)
+        if blendedness:
+            child, npix, rows = col("child", (2,)), col("npix", ()).astype(np.int32), col("rows", ()).astype(np.int64)
+            s = np.asarray(sums, dtype=np.float64).reshape(-1, 4)[rows]
+            parts += [blend_records(np.concatenate([child, s[:, :2]], axis=1), npix),
+                      residual_records(child[:, 0], npix, s[:, 2], s[:, 3])]
+        for p in parts:
+            for k in p.dtype.names:
+                out[k] = p[k]
+        return out
 
     def _need_run(self):
         if self._fields is None:
+            if getattr(self, "_no_fields", False):
+                raise ValueError("iterative_catalogue() ran with return_fields=False: the fields were not read back; "
+                                 "run it with return_fields=True")
             raise ValueError("no iterative_deblending() run yet")
 
     def get_residual_fields(self):

@@ -1366,6 +1366,7 @@ class FieldSet:
         self.shape = fields.shape
         self.cumulative = bool(cumulative)
         self._h = C.c_void_p()
+        self._rows = 0                      # stamps of the deblend_pass_measure(blend=True) calls: the set's resident rows
         if not engine._h:
             raise RuntimeError("the Engine of this FieldSet has been closed")
         M, F, _, nb = fields.shape
@@ -1434,6 +1435,52 @@ class FieldSet:
         check(lib.dv_field_set_pass(h, _ip(starts), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed),
                                     _dp(mse_center), _dp(field_mse)))
         return {"mse_center": mse_center, "field_mse": field_mse}
+
+    def deblend_pass_measure(self, starts, places, field_ptr, seed=0, band: int = 2, sigma0: float = 3.0, tol: float = 1e-10,
+                             max_iter: int = 200, blend=True) -> Dict[str, np.ndarray]:
+        """deblend_pass() with every stamp measured where it lies in device memory (dv_field_set_pass_measure, DESIGN.md
+        section 7m).  Returns deblend_pass's dictionary, bit for bit, plus {"flux", "flux_err" (N, bands), "shape" (N, 5),
+        "iters", "status" (N,)} - the bits of Context.scene_measure on the stamps Engine.infer_fields returns for the working
+        residuals and the same seed - and, with blend=True, {"child" (N, 2) = {W, A}, "npix" (N,)}: the stamp sums of
+        Context.scene_blend.  With blend=True the set also keeps every stamp's shape, status, placement and field on the
+        device, in call order over all passes: the rows blend_sums() works on."""
+        h = self._handle()
+        starts = _i32_rows(starts, "cutout starts")
+        places = _i32_rows(places, "stamp placements")
+        if places.shape != starts.shape:
+            raise ValueError(f"{starts.shape[0]} cutout starts but {places.shape[0]} placements")
+        N = starts.shape[0]
+        fp = check_field_ptr(field_ptr, self.shape[0], N)
+        nb = self.shape[3]
+        par = measure_params(band, sigma0, tol, max_iter, nb)
+        cs = self.engine.stamp_shape[0]
+        if cs > MEASURE_MAX_STAMP:
+            raise ValueError(f"stamps of {cs} pixels: the measurement takes at most {MEASURE_MAX_STAMP}")
+        out = {"mse_center": np.empty(N, np.float64), "field_mse": np.full(self.shape[0], np.nan),
+               "flux": np.zeros((N, nb), np.float64), "flux_err": np.zeros((N, nb), np.float64),
+               "shape": np.zeros((N, 5), np.float64), "iters": np.zeros(N, np.int32), "status": np.zeros(N, np.int32)}
+        if blend:
+            out.update(child=np.zeros((N, 2), np.float64), npix=np.zeros(N, np.int32))
+        check(lib.dv_field_set_pass_measure(h, _ip(starts), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), N, int(seed),
+                                            C.byref(par), _dp(out["mse_center"]), _dp(out["field_mse"]), _dp(out["flux"]),
+                                            _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"]),
+                                            _dp(out.get("child")), _ip(out["npix"]) if blend else None))
+        if blend:
+            self._rows += N
+        return out
+
+    def blend_sums(self, band: int = 2) -> np.ndarray:
+        """(Ntot, 4) float64 {Bm, Bd, R1, R2} for the Ntot stamps of all deblend_pass_measure(blend=True) calls so far, in call
+        order, against the set's stacks as they are now (dv_field_set_blend): under the Gaussian weight g of a stamp's
+        adaptive moments and over its pixels inside the field, Bm = sum g mean, Bd = sum g base (the field as uploaded; NaN
+        on every row of a cumulative set, which keeps no base), R1 = sum g final, R2 = sum g final^2.  An ineligible row
+        (Context.scene_blend's rule) gets four NaN."""
+        h = self._handle()
+        if int(band) != band or not 0 <= int(band) < self.shape[3]:
+            raise ValueError(f"band {band} asked for, the fields have bands 0 .. {self.shape[3] - 1}")
+        sums = np.zeros((self._rows, 4), np.float64)
+        check(lib.dv_field_set_blend(h, int(band), self._rows, _dp(sums)))
+        return sums
 
     def read(self, which: str) -> np.ndarray:
         """One of the set's stacks as (M, F, F, bands) float64: "work", "final", "mean" or "stddev"."""

@@ -100,6 +100,30 @@ def blend_records(blend, npix):
     return rec
 
 
+def residual_dtype():
+    """The columns the iterative loop's end-of-loop sums add behind blend_dtype(): the two weighted
+    sums the GPU takes over the final residual, then the two ratios the host derives from them."""
+    return [("resid_sum", "<f8"), ("resid_sq", "<f8"), ("resid_mean", "<f8"), ("resid_rms", "<f8")]
+
+
+def residual_records(weight, npix, resid_sum, resid_sq):
+    """The recarray of residual_dtype() from W = sum g and npix (the child sums of a pass) and R1 = sum g final, R2 = sum g
+    final^2 (FieldSet.blend_sums), all (N,).  Derived on the host: resid_mean = R1 / W, the mean of what the loop left under
+    the galaxy's weight, and resid_rms = sqrt(R2 / W); both NaN where the row is ineligible (npix < 0) or W <= 0."""
+    W = np.asarray(weight, dtype=np.float64).reshape(-1)
+    npix = np.asarray(npix)
+    R1, R2 = np.asarray(resid_sum, dtype=np.float64), np.asarray(resid_sq, dtype=np.float64)
+    rec = np.recarray((W.shape[0],), dtype=residual_dtype())
+    rec["resid_sum"] = R1
+    rec["resid_sq"] = R2
+    ok = (npix >= 0) & (W > 0)                               # (NaN > 0 is False)
+    with np.errstate(all="ignore"):
+        den = np.where(ok, W, 1.0)
+        rec["resid_mean"] = np.where(ok, R1 / den, np.nan)
+        rec["resid_rms"] = np.where(ok, np.sqrt(R2 / den), np.nan)
+    return rec
+
+
 def measure_blendedness(stamps_mean, catalogue, places, model_fields, data_fields=None, field_ptr=None, band=2, ctx=None):
     """Blendedness of N deblended galaxies on the GPU.
 

@@ -542,6 +542,32 @@ int dv_field_set_pass(dv_field_set* set, const int32_t* starts, const int32_t* p
 int dv_field_set_read(dv_field_set* set, int32_t which, double* out);
 int dv_field_set_close(dv_field_set* set);
 
+/* ---- the catalogue of the iterative loop, measured on the resident set ----
+ * dv_field_set_pass_measure: dv_field_set_pass (same arguments, same bits in the stacks, mse_center and field_mse) with two
+ * more stages behind every chunk's forward pass, on the chunk's mean and stddev stamps in device memory: the measurement
+ * above (flux, flux_err [N][nb], shape [N][5], iters, status [N]: the bits of dv_scene_measure on the stamps dv_infer_fields
+ * returns for the working residuals and the same seed) and the child sums of the blendedness (child [N][2] = {W, A}, npix
+ * [N]: the bits of dv_scene_blend's W, A and npix for those stamps, rows and placements).  child and npix may be null
+ * TOGETHER: no child sums are taken.  With them given the set appends {shape[5], status, place, field} of every stamp to
+ * resident rows it owns in device memory, in call order (the first stamp of a pass follows the last stamp of the pass
+ * before); they grow like the per-stamp tables, never cross the host link again and are freed by dv_field_set_close.
+ * Refused before any GPU work (DV_E_INVALID), the set and its resident rows left as they were: what dv_field_set_pass and
+ * dv_infer_fields_measure refuse (a stamp of more than 90 pixels among it), null params, child without npix or npix without
+ * child.
+ * dv_field_set_blend: for all Ntot resident rows, against the set's stacks as they are at the time of the call (usually:
+ * after the last pass), with the pixels, the weight g and the eligibility rule of the blendedness above and pr, pc, field
+ * the row's: sums [Ntot][4] = {Bm, Bd, R1, R2} = {sum g mean, sum g base, sum g final, sum g (final final)} at band `band`,
+ * the square rounded on its own.  Bm and Bd have the bits of dv_scene_blend's on the stacks read back (base is the field as
+ * uploaded).  A cumulative set keeps no `base`: Bd is NaN on every row.  An ineligible row gets four NaN.  In reference
+ * mode a galaxy deblended again in a later pass is in `mean` once per pass: its Bm counts its earlier copies as neighbours.
+ * n_expected must be Ntot, the number of stamps of all passes that took child sums (DV_E_INVALID otherwise, and for a band
+ * outside 0 .. nb - 1), so that a caller whose rows and the set's have come apart learns it before it joins them. */
+int dv_field_set_pass_measure(dv_field_set* set, const int32_t* starts, const int32_t* places, const int64_t* field_ptr,
+                              int64_t N, uint64_t seed, const dv_measure_params* params, double* mse_center,
+                              double* field_mse, double* flux, double* flux_err, double* shape, int32_t* iters,
+                              int32_t* status, double* child, int32_t* npix);
+int dv_field_set_blend(dv_field_set* set, int32_t band, int64_t n_expected, double* sums);
+
 /* ---- introspection for tests and bench ----------------------------------------------------- */
 /* copy a named activation of the last step to host: "t","z","kl","eps","loc","scale","head_pre" */
 int dv_model_get_activation(dv_model* m, const char* name, float* host, size_t nbytes);

@@ -12,8 +12,12 @@ link per pass are counted from the passes the run made: field-sized arrays and f
 and per-stamp scalars in the batched form.  GPU only; prints a table and one JSON line.
 
     python tools/iterative_bench.py [--fields 64] [--size 259] [--repeat 5] [--max-batch 8192] [--dtype both]
+                                    [--measure] [--no-fields]
 
 --profile-one: warm up, run the batched form once (float32 unless --dtype says otherwise) and exit - for a kernel trace.
+--measure / --no-fields: instead of the loop, the batched form against itself through
+iterative_catalogue with measure=True, blendedness=True and / or return_fields=False - every combination the switches name,
+alternating from the same seed counter: the cost of the catalogue stage and of the three field-sized downloads.
 """
 import argparse
 import io
@@ -47,10 +51,10 @@ def _loop(net, fields):
     return n, passes
 
 
-def _batch(net, fields):
+def _batch(net, fields, **kw):
     """-> galaxies deblended, [(active fields, detections, galaxies) per pass]"""
     it = IterativeDeblendFieldBatch(net, fields)
-    res = it.iterative_deblending(mode="reference")
+    res = it.iterative_catalogue(mode="reference", **kw) if kw else it.iterative_deblending(mode="reference")
     passes = [(sum(1 for c in g if c > 0), sum(d), sum(g)) for d, g in zip(it.nb_of_detected_objects,
                                                                          it.nb_of_deblended_galaxies)]
     return sum(len(r) for r in res), passes
@@ -87,6 +91,8 @@ def main():
     ap.add_argument("--max-batch", type=int, default=8192)
     ap.add_argument("--dtype", choices=("both", "float32", "bf16"), default="both")
     ap.add_argument("--profile-one", action="store_true", help="warm up, one batched run, exit")
+    ap.add_argument("--measure", action="store_true", help="time the batched form with and without the catalogue")
+    ap.add_argument("--no-fields", action="store_true", help="time the batched form with and without the field downloads")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     F, M = a.size, a.fields
@@ -105,6 +111,35 @@ def main():
                 _batch(net, fields)
                 core.engine.close()
                 return
+        if a.measure or a.no_fields:
+            cat = dict(measure=True, blendedness=True)
+            forms = [("batch", {})]
+            if a.measure:
+                forms.append(("batch + catalogue", cat))
+            if a.no_fields:
+                forms.append(("batch, no fields", dict(return_fields=False)))
+            if a.measure and a.no_fields:
+                forms.append(("catalogue, no fields", dict(cat, return_fields=False)))
+            with redirect_stdout(quiet):
+                for _, kw in forms[1:]:                                               # warm-up of the new stages
+                    _batch(net, fields[:min(M, 8)], **kw)
+            times = {label: [] for label, _ in forms}
+            for _ in range(a.repeat):          # alternating; every run starts from the same seed counter
+                for label, kw in forms:
+                    core.seed_counter = 1000
+                    with redirect_stdout(quiet):
+                        t0 = time.perf_counter()
+                        n, _ = _batch(net, fields, **kw)
+                        times[label].append(time.perf_counter() - t0)
+            for label, _ in forms:
+                print(_row(f"{dtype} {label}", np.array(times[label]), M, n))
+            med = {label: float(np.median(t)) for label, t in times.items()}
+            for label, _ in forms[1:]:
+                print(f"{dtype} {label} / batch: {med[label] / med['batch']:.3f} x")
+            result[dtype] = {label: [round(1e3 * x, 2) for x in t] for label, t in times.items()}
+            result[dtype]["galaxies"] = int(n)
+            core.engine.close()
+            continue
         tl, tb = [], []
         for _ in range(a.repeat):              # alternating; every run of either form starts from the same seed counter
             for fn, ts in ((_loop, tl), (_batch, tb)):
