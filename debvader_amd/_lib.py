@@ -170,6 +170,11 @@ SIGNATURES = {
                                  C.c_int32, _d, _i32]),
     "dv_infer_fields_measure_blend": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
                                                 C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32, _d, _i32]),
+    "dv_scene_regauss": (C.c_int, [_p, _f, _d, _i32, _i32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _d, C.c_int32, C.c_int32,
+                                   C.c_double, C.c_double, C.c_int32, _d, _i32, _i32, _d, _d, _i32, _i32]),
+    "dv_infer_fields_measure_psf": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
+                                              C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32, _d, C.c_int32,
+                                              C.c_int32, _i32, C.c_double, _d, _i32, _i32, _d, _d, _i32, _i32]),
     "dv_field_set_open": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),

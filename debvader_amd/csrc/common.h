@@ -340,6 +340,30 @@ int launch_blend_set(const double* shape_dev, const int* status_dev, const int* 
 int scene_blend(const float* stamps_h, const double* shape_h, const int32_t* status_h, const int32_t* places_h,
                 const int64_t* field_ptr, int64_t N, int cs, int nb, int band, const double* model_h, const double* data_h,
                 int M, int F, double* blend_h, int32_t* npix_h, int64_t chunk, int64_t gmax, hipStream_t s);
+// PSF-corrected shapes (regauss.hip): per galaxy the adaptive moments {r', c', Mrr', Mrc', Mcc'} and the kurtosis
+// rho4 of the re-Gaussianized band plane, iterations and status (0 / 2 / 3 of the iteration; 4 an ineligible catalogue row,
+// 5 no usable PSF, 6 a galaxy its PSF does not resolve: six NaN, 0 iterations).  regauss_check: the refusals, before any GPU
+// work.  RegaussPsf: the K PSF images of a call in device memory with their rows - shape [K][5], aux [K][3] = {A_P, FQ,
+// rho4}, iters, status - and residuals eps [K][ps][ps]; measure() uploads and measures them on a stream, once per call.
+// launch_regauss: n stamps in device memory with their catalogue rows and PSF indices, every per-galaxy pointer at the
+// first stamp's row.  scene_regauss: host arrays, at most `chunk` stamps on the device at a time.
+int regauss_check(const char* who, int cs, int nb, int band, int K, int ps, double psf_sigma0, double tol, int max_iter);
+size_t regauss_lds_bytes(int cs, int ps);
+struct RegaussPsf {
+  DevBuf<double> img, eps, shape, aux;
+  DevBuf<int> iters, status;
+  static size_t bytes(int K, int ps) { return (size_t)K * ((2 * (size_t)ps * ps + 8) * sizeof(double) + 2 * sizeof(int)); }
+  int alloc(int K, int ps);
+  int measure(const double* psf_h, int K, int ps, double psf_sigma0, double tol, int max_iter, hipStream_t s);
+  int download(int K, double* shape_h, double* aux_h, int32_t* iters_h, int32_t* status_h, hipStream_t s);
+};
+int launch_regauss(const float* stamps_dev, const double* shape_dev, const int* status_dev, const int* psf_index_dev, int n,
+                   int cs, int nb, int band, const RegaussPsf& psf, int K, int ps, double tol, int max_iter, double* out_dev,
+                   int* iters_dev, int* ostatus_dev, hipStream_t s);
+int scene_regauss(const float* stamps_h, const double* shape_h, const int32_t* status_h, const int32_t* psf_index_h, int64_t N,
+                  int cs, int nb, int band, const double* psf_h, int K, int ps, double psf_sigma0, double tol, int max_iter,
+                  double* out_h, int32_t* iters_h, int32_t* ostatus_h, double* psf_shape_h, double* psf_aux_h,
+                  int32_t* psf_iters_h, int32_t* psf_status_h, int64_t chunk, hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

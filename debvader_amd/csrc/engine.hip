@@ -3110,6 +3110,16 @@ struct PipeJob {
     int* npix = nullptr;               // device [.]
     double* mean_f = nullptr;          // device, fields f0 .. like fields_d (the catalogue-only form)
   } bl;
+  // PSF-corrected shapes (dv_infer_fields_measure_psf): behind every chunk's measurement, the re-Gaussianized
+  // moments of its mean stamps from the chunk's catalogue rows and the call's PSF rows (measured before the first chunk); out
+  // decides
+  struct Regauss {
+    const RegaussPsf* psf = nullptr;   // device: the K PSF images, their rows and residuals
+    int K = 0, ps = 0;
+    const int* index = nullptr;        // device [.]: PSF of every stamp
+    double* out = nullptr;             // device [.][6]
+    int *iters = nullptr, *status = nullptr;   // device [.]
+  } rg;
 };
 
 // The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
@@ -3328,6 +3338,10 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
         DV_TRY(launch_blend_child(p->dloc[b], j.ms.shape + (size_t)r * 5, j.ms.status + r, j.sinks.places_d + 2 * r, nb, cs,
                                   j.nb, j.ms.band, j.F, j.bl.blend + (size_t)r * 4, j.bl.npix + r, p->s_out));
       }
+      if (j.rg.out)
+        DV_TRY(launch_regauss(p->dloc[b], j.ms.shape + (size_t)r * 5, j.ms.status + r, j.rg.index + r, nb, cs, j.nb, j.ms.band,
+                              *j.rg.psf, j.rg.K, j.rg.ps, j.ms.tol, j.ms.max_iter, j.rg.out + (size_t)r * 6, j.rg.iters + r,
+                              j.rg.status + r, p->s_out));
     }
     if (j.loc || j.consumer) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (j.scale || j.consumer) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
@@ -3801,6 +3815,23 @@ int dv_scene_blend(dv_ctx* c, const float* stamps, const double* shape, const in
   const int64_t gmax = (int64_t)std::max<size_t>(1, free_b / 4 / per_field);
   return scene_blend(stamps, shape, status, places, field_ptr, N, cs, nb, band, model_fields, data_fields, M, F, blend, npix,
                      chunk, gmax, c->stream);
+}
+
+int dv_scene_regauss(dv_ctx* c, const float* stamps, const double* shape, const int32_t* status, const int32_t* psf_index,
+                     int64_t N, int32_t cs, int32_t nb, int32_t band, const double* psf, int32_t K, int32_t ps,
+                     double psf_sigma0, double tol, int32_t max_iter, double* regauss, int32_t* regauss_iters,
+                     int32_t* regauss_status, double* psf_shape, double* psf_aux, int32_t* psf_iters, int32_t* psf_status) {
+  if (!c) return DV_E_INVALID;
+  DV_TRY(regauss_check("dv_scene_regauss", cs, nb, band, K, ps, psf_sigma0, tol, max_iter));   // before any GPU work
+  DV_HIP(hipSetDevice(c->device));
+  // stamps per chunk: half of free device memory, less the PSFs, holds a chunk's stamps and rows
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t per_stamp = (size_t)cs * cs * nb * sizeof(float) + 11 * sizeof(double) + 4 * sizeof(int);
+  const size_t fixed = RegaussPsf::bytes(K, ps), half = free_b / 2;
+  const int64_t chunk = (int64_t)std::max<size_t>(1, (half > fixed ? half - fixed : 0) / per_stamp);
+  return scene_regauss(stamps, shape, status, psf_index, N, cs, nb, band, psf, K, ps, psf_sigma0, tol, max_iter, regauss,
+                       regauss_iters, regauss_status, psf_shape, psf_aux, psf_iters, psf_status, chunk, c->stream);
 }
 
 int dv_scene_measure_mc(dv_ctx* c, const float* samples, int32_t S, int64_t N, int32_t cs, int32_t nb,
@@ -4989,12 +5020,50 @@ struct BlendStage {                 // the blendedness sums of every stamp (7l)
   }
 };
 
+struct RegaussOut {                 // dv_infer_fields_measure_psf: the PSFs and the index in, the corrected rows out (host)
+  const double* psf = nullptr;      // [K][ps][ps]
+  int K = 0, ps = 0;
+  const int32_t* index = nullptr;   // [N]
+  double psf_sigma0 = 0.0;
+  double* out = nullptr;            // [N][6]
+  int32_t *iters = nullptr, *status = nullptr;           // [N]
+  double *psf_shape = nullptr, *psf_aux = nullptr;       // [K][5], [K][3]
+  int32_t *psf_iters = nullptr, *psf_status = nullptr;   // [K]
+};
+
+struct RegaussStage {               // the PSF-corrected moments of every stamp (7n)
+  RegaussPsf psf;
+  DevBuf<double> out;
+  DevBuf<int> index, iters, status;
+  static size_t bytes_per_stamp() { return 6 * sizeof(double) + 3 * sizeof(int); }
+  static size_t bytes_fixed(const RegaussOut& o) { return RegaussPsf::bytes(o.K, o.ps); }
+  // the per-stamp rows, and the PSFs uploaded and measured on the call's stream: once, before the first chunk
+  int alloc(const RegaussOut& o, int64_t N, const dv_measure_params& par, hipStream_t s) {
+    DV_TRY(psf.alloc(o.K, o.ps));
+    DV_TRY(out.alloc((size_t)N * 6));
+    for (DevBuf<int>* b : {&index, &iters, &status}) DV_TRY(b->alloc((size_t)N));
+    DV_HIP(hipMemcpyAsync(index, o.index, (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+    return psf.measure(o.psf, o.K, o.ps, o.psf_sigma0, par.tol, par.max_iter, s);
+  }
+  void bind(PipeJob::Regauss& q, const RegaussOut& o) const {
+    q.psf = &psf; q.K = o.K; q.ps = o.ps; q.index = index; q.out = out; q.iters = iters; q.status = status;
+  }
+  int download(const RegaussOut& o, int64_t N, hipStream_t s) {
+    DV_HIP(hipMemcpyAsync(o.out, out, (size_t)N * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(o.iters, iters, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(o.status, status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_TRY(psf.download(o.K, o.psf_shape, o.psf_aux, o.psf_iters, o.psf_status, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return DV_OK;
+  }
+};
+
 // j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
 // the device side and the rows are filled in here
 static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
                              const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr,
                              const MeasureMcOut* mco = nullptr, const BlendOut* bo = nullptr,
-                             const int32_t* blend_places = nullptr) {
+                             const int32_t* blend_places = nullptr, const RegaussOut* ro = nullptr) {
   // check
   const double* fields = j.fields;
   const int F = j.F, nb = j.nb;
@@ -5018,7 +5087,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   double* mse_h = fo ? fo->mse : mo ? mo->mse : nullptr;
   DevBuf<double> fdev;                                // the resident group of source fields
   StampTables tab;
-  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls;   // (a stage that does not run stays empty)
+  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs;   // (a stage that does not run stays empty)
   ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
   if (fitting) DV_TRY(fit.make_plan(*fo, c, sfield.data()));
   size_t per_field = fb, reserve = StampTables::bytes((size_t)N, (size_t)M);
@@ -5038,6 +5107,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     per_field += BlendStage::bytes_per_field(!fo, fb);
     reserve += (size_t)N * BlendStage::bytes_per_stamp();
   }
+  if (ro) reserve += (size_t)N * RegaussStage::bytes_per_stamp() + RegaussStage::bytes_fixed(*ro);
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
@@ -5070,6 +5140,10 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (bo) {
     DV_TRY(bls.alloc(N, !fo, gelems));
     bls.bind(j.bl);
+  }
+  if (ro) {
+    DV_TRY(rgs.alloc(*ro, N, mo->par, s));
+    rgs.bind(j.rg, *ro);
   }
   if (fitting) {
     DV_TRY(fit.alloc(*fo, c, gmax, groups));
@@ -5127,6 +5201,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (mo) DV_TRY(cat.download(*mo, N, nb, s));
   if (mco) DV_TRY(catmc.download(*mco, N, nb, s));
   if (bo) DV_TRY(bls.download(*bo, N, s));
+  if (ro) DV_TRY(rgs.download(*ro, N, s));
   if (fo) DV_TRY(mc.download(N, s));
   if (fitting) DV_TRY(fit.download(*fo, N, s));
   drain.dismiss();
@@ -5241,9 +5316,18 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
                                       uint64_t seed, const dv_measure_params* params, double* mean_fields,
                                       double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
                                       double* flux_err, double* shape, int32_t* iters, int32_t* status,
-                                      const BlendOut* bo = nullptr) {
+                                      const BlendOut* bo = nullptr, const RegaussOut* ro = nullptr) {
   if (!m || !params) return DV_E_INVALID;
   DV_TRY(measure_check(who, m->A.H, nb, params->band, params->sigma0, params->tol, params->max_iter));
+  if (ro) {
+    DV_TRY(regauss_check(who, m->A.H, nb, params->band, ro->K, ro->ps, ro->psf_sigma0, params->tol, params->max_iter));
+    if (!ro->psf || !ro->psf_shape || !ro->psf_aux || !ro->psf_iters || !ro->psf_status ||
+        (N > 0 && (!ro->index || !ro->out || !ro->iters || !ro->status))) {
+      set_error("%s: psf, psf_index, regauss, regauss_iters, regauss_status, psf_shape, psf_aux, psf_iters and psf_status must "
+                "all be given", who);
+      return DV_E_INVALID;
+    }
+  }
   if (N > 0 && (!flux || !flux_err || !shape || !iters || !status)) {
     set_error("%s: flux, flux_err, shape, iters and status must all be given", who);
     return DV_E_INVALID;
@@ -5268,7 +5352,7 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
   PipeJob j = fields_job(fields, F, nb, starts, seed);
   if (!with_fields) {
     mo.mse = mse_center;
-    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo ? places : nullptr);
+    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo ? places : nullptr, ro);
   }
   FieldsOut fo;
   fo.mean = mean_fields;
@@ -5276,7 +5360,7 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
   fo.residual = residual_fields;
   fo.mse = mse_center;
   fo.places = places;
-  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo);
+  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo, nullptr, ro);
 }
 
 int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
@@ -5301,6 +5385,33 @@ int dv_infer_fields_measure_blend(dv_model* m, const double* fields, int32_t M, 
   return infer_fields_measure_entry("dv_infer_fields_measure_blend", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
                                     params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
                                     iters, status, &bo);
+}
+
+// ---- PSF-corrected shapes beside the catalogue: dv_infer_fields_measure plus the re-Gaussianized moments
+int dv_infer_fields_measure_psf(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                int32_t* iters, int32_t* status, const double* psf, int32_t K, int32_t ps,
+                                const int32_t* psf_index, double psf_sigma0, double* regauss, int32_t* regauss_iters,
+                                int32_t* regauss_status, double* psf_shape, double* psf_aux, int32_t* psf_iters,
+                                int32_t* psf_status) {
+  RegaussOut ro;
+  ro.psf = psf;
+  ro.K = K;
+  ro.ps = ps;
+  ro.index = psf_index;
+  ro.psf_sigma0 = psf_sigma0;
+  ro.out = regauss;
+  ro.iters = regauss_iters;
+  ro.status = regauss_status;
+  ro.psf_shape = psf_shape;
+  ro.psf_aux = psf_aux;
+  ro.psf_iters = psf_iters;
+  ro.psf_status = psf_status;
+  return infer_fields_measure_entry("dv_infer_fields_measure_psf", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
+                                    params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
+                                    iters, status, nullptr, &ro);
 }
 
 // ---- the Monte-Carlo catalogue beside it: dv_infer_fields_measure plus means and standard deviations of

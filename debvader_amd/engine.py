@@ -170,6 +170,43 @@ def check_measure_args(mean, stddev, band, sigma0, tol, max_iter):
 
 MC_SHAPE_NAMES = ("row", "col", "Mrr", "Mrc", "Mcc", "sigma", "e1", "e2")     # the columns of shape_mc_mean / shape_mc_std
 
+REGAUSS_MAX_STAMP = 64          # a thread of the correction kernel keeps at most 16 pixels of the corrected plane in registers
+REGAUSS_PSF_SIZES = (5, 33)     # PSF images of 5 .. 33 pixels: with a 64-pixel stamp the largest still fits a workgroup's LDS
+
+
+def check_psf_args(psf, psf_index, n: int, psf_sigma0):
+    """(psf, psf_index) of the PSF-corrected measurement: C-contiguous float64 PSF images (K, ps, ps) - one image (ps, ps) is
+    K = 1 - and the int32 index (n,) of every galaxy's PSF (None: PSF 0 for all).  An index outside 0 .. K - 1 is not an
+    error: that galaxy's row gets regauss_status 5."""
+    psf = np.ascontiguousarray(psf, dtype=np.float64)
+    if psf.ndim == 2:
+        psf = psf[None]
+    if psf.ndim != 3 or psf.shape[1] != psf.shape[2] or psf.shape[0] < 1:
+        raise ValueError(f"expected square PSF images (K, ps, ps) with K >= 1, got {psf.shape}")
+    if not REGAUSS_PSF_SIZES[0] <= psf.shape[1] <= REGAUSS_PSF_SIZES[1]:
+        raise ValueError(f"PSF images of {psf.shape[1]} pixels: {REGAUSS_PSF_SIZES[0]} .. {REGAUSS_PSF_SIZES[1]} are taken")
+    if not (np.isfinite(psf_sigma0) and psf_sigma0 > 0):
+        raise ValueError(f"psf_sigma0 must be finite and positive (got {psf_sigma0})")
+    if psf_index is None:
+        index = np.zeros(int(n), np.int32)
+    else:
+        index = np.asarray(psf_index)
+        if index.dtype.kind not in "iu":
+            raise ValueError("psf_index must be integers")
+        if index.shape != (int(n),):
+            raise ValueError(f"psf_index must have one entry per galaxy ({int(n)},), got {index.shape}")
+        index = np.ascontiguousarray(np.clip(index, -1, 2 ** 31 - 1), dtype=np.int32)     # (any negative index stays out of range)
+    return psf, index
+
+
+def _regauss_out(n, K):
+    """The result dictionary of the PSF-corrected measurement and its pointers in the C-ABI's order."""
+    out = dict(regauss=np.zeros((n, 6), np.float64), regauss_iters=np.zeros(n, np.int32), regauss_status=np.zeros(n, np.int32),
+               psf_shape=np.zeros((K, 5), np.float64), psf_aux=np.zeros((K, 3), np.float64), psf_iters=np.zeros(K, np.int32),
+               psf_status=np.zeros(K, np.int32))
+    return out, [_dp(out["regauss"]), _ip(out["regauss_iters"]), _ip(out["regauss_status"]), _dp(out["psf_shape"]),
+                 _dp(out["psf_aux"]), _ip(out["psf_iters"]), _ip(out["psf_status"])]
+
 
 def check_measure_mc_args(samples, band, sigma0, tol, max_iter):
     """(samples, params) of scene_measure_mc: C-contiguous float32 sample stamps (S, N, cs, cs, bands), S >= 1."""
@@ -611,6 +648,39 @@ class Context:
             check(lib.dv_scene_blend(self._h, _fp(stamps), _dp(shape), _ip(status), _ip(places),
                                      fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs, nb, int(band), _dp(model), _dp(data), M,
                                      model.shape[1], _dp(out["blend"]), _ip(out["npix"])))
+        return out
+
+    REGAUSS_INELIGIBLE, REGAUSS_NO_PSF, REGAUSS_UNRESOLVED = 4, 5, 6          # status codes scene_regauss adds to scene_measure's
+
+    def scene_regauss(self, stamps, shape, status, psf, psf_index=None, band: int = 2, psf_sigma0: float = 2.0,
+                      tol: float = 1e-10, max_iter: int = 200) -> Dict[str, np.ndarray]:
+        """PSF-corrected moments of N galaxies on the GPU by re-Gaussianization (dv_scene_regauss):
+        stamps (N, cs, cs, bands), the mean stamps taken as float32; shape (N, 5) and status (N,), their scene_measure rows in
+        band `band`; psf (K, ps, ps) float64 PSF images (or one (ps, ps)), psf_index (N,) the PSF of every galaxy (None: PSF
+        0).  Returns {"regauss" (N, 6): {row', col', Mrr', Mrc', Mcc', rho4} - the adaptive moments and the kurtosis of the
+        galaxy's band plane less the part of it that the PSF's departure from its own best Gaussian accounts for -,
+        "regauss_iters", "regauss_status" (N,): 0 / 2 / 3 as scene_measure, REGAUSS_INELIGIBLE (the row's status is 3, a value
+        is not finite or det M <= 1e-6), REGAUSS_NO_PSF (psf_index outside 0 .. K - 1, or a PSF that is not usable),
+        REGAUSS_UNRESOLVED (M - M_P is not positive definite) - the last three with six NaN and 0 iterations; "psf_shape"
+        (K, 5), "psf_aux" (K, 3): {A_P, sum Q, psf_rho4}, "psf_iters", "psf_status" (K,): the PSFs' own adaptive moments from
+        the width psf_sigma0}.  The corrected moments are regauss[:, 2:5] - psf_shape[psf_index, 2:5]
+        (debvader_amd.measure.measurement.psf_records derives sigma, e1, e2 and the resolution from them)."""
+        stamps = np.ascontiguousarray(stamps, dtype=np.float32)
+        if stamps.ndim != 4 or stamps.shape[1] != stamps.shape[2] or stamps.shape[1] < 1 or stamps.shape[3] < 1:
+            raise ValueError(f"expected square stamps (N, cs, cs, bands), got {stamps.shape}")
+        n, cs, nb = stamps.shape[0], stamps.shape[1], stamps.shape[3]
+        if cs > REGAUSS_MAX_STAMP:
+            raise ValueError(f"stamps of {cs} pixels: the PSF correction takes at most {REGAUSS_MAX_STAMP}")
+        shape = np.ascontiguousarray(shape, dtype=np.float64)
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        if shape.shape != (n, 5) or status.shape != (n,):
+            raise ValueError(f"expected shape ({n}, 5) and status ({n},), got {shape.shape}, {status.shape}")
+        par = measure_params(band, 1.0, tol, max_iter, nb)
+        psf, index = check_psf_args(psf, psf_index, n, psf_sigma0)
+        K, ps = psf.shape[0], psf.shape[1]
+        out, ptrs = _regauss_out(n, K)
+        check(lib.dv_scene_regauss(self._h, _fp(stamps), _dp(shape), _ip(status), _ip(index), n, cs, nb, par.band, _dp(psf), K, ps,
+                                   float(psf_sigma0), par.tol, par.max_iter, *ptrs))
         return out
 
     CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
@@ -1088,6 +1158,49 @@ class Engine:
     def scene_blend(self, stamps, shape, status, places, model_fields, data_fields=None, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_blend on this engine's GPU context."""
         return self.ctx.scene_blend(stamps, shape, status, places, model_fields, data_fields, **kw)
+
+    def infer_fields_measure_psf(self, fields, starts, field_ptr, psf, psf_index=None, places=None, seed=0, band: int = 2,
+                                 sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, psf_sigma0: float = 2.0,
+                                 return_fields=True, residual=True, mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure() plus the PSF-corrected moments (dv_infer_fields_measure_psf): returns
+        its dictionary, bit for bit, plus scene_regauss' {"regauss", "regauss_iters", "regauss_status", "psf_shape",
+        "psf_aux", "psf_iters", "psf_status"} - the bits of scene_regauss on infer_fields' mean stamps and
+        infer_fields_measure's rows.  The PSFs (K, ps, ps) are uploaded and measured once; the correction runs behind every
+        chunk's measurement on the stamps in device memory.  psf_index (N,) picks every stamp's PSF (None: PSF 0).
+        return_fields=False is the catalogue-only call, as there."""
+        if return_fields and places is None:
+            raise ValueError("places are needed to composite the fields; return_fields=False measures without them")
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places if return_fields else None)
+        nb = fields.shape[3]
+        par = measure_params(band, sigma0, tol, max_iter, nb)
+        psf, index = check_psf_args(psf, psf_index, N, psf_sigma0)
+        if return_fields:
+            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
+        else:
+            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
+            ptrs = [None, None, None, _dp(out.get("mse_center"))]
+            args = args[:5] + [None] + args[5:]
+        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
+                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
+        rg, rg_ptrs = _regauss_out(N, psf.shape[0])
+        out.update(rg)
+        if N == 0:                          # (the library has nothing to run; the PSF rows come from the stamp-level call)
+            empty = self.ctx.scene_regauss(np.zeros((0,) + tuple(self.stamp_shape), np.float32), np.zeros((0, 5)), np.zeros(0, np.int32),
+                                           psf, band=band, psf_sigma0=psf_sigma0, tol=tol, max_iter=max_iter)
+            out.update({k: empty[k] for k in ("psf_shape", "psf_aux", "psf_iters", "psf_status")})
+        check(lib.dv_infer_fields_measure_psf(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
+                                              _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"]),
+                                              _dp(psf), psf.shape[0], psf.shape[1], _ip(index), float(psf_sigma0), *rg_ptrs))
+        return out
+
+    def infer_cutouts_measure_psf(self, field, starts, psf, psf_index=None, places=None, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_psf() for one field (F, F, bands): the field-sized results under singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_psf(fields, starts, fp, psf, psf_index, places=places, seed=seed, **kw))
+
+    def scene_regauss(self, stamps, shape, status, psf, psf_index=None, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_regauss on this engine's GPU context."""
+        return self.ctx.scene_regauss(stamps, shape, status, psf, psf_index, **kw)
 
     def infer_fields_measure_mc(self, fields, starts, field_ptr, places=None, seed=0, mc_seed=0, nsamples=100, band: int = 2,
                                 sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, return_fields=True,

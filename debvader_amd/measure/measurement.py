@@ -7,14 +7,20 @@ moments of one band - the centroid and second moments of the stamp under a Gauss
 the object.  Errors on the centroid, the moments, sigma, e1 and e2 (and a second error on the fluxes) come from the network's
 own Monte-Carlo decodes (measure_stamps_mc): every decode of a galaxy is measured and the measured
 rows are folded into a mean and a standard deviation per quantity.  Blendedness - how much of the light under a galaxy's
-own weight belongs to its neighbours - is DESIGN.md section 7l (measure_blendedness, csrc/blend.hip).  A PSF correction is not
-part of it.
+own weight belongs to its neighbours - is DESIGN.md section 7l (measure_blendedness, csrc/blend.hip).  The PSF correction
+is DESIGN.md section 7n (measure_stamps_psf, csrc/regauss.hip): the re-Gaussianization of Hirata & Seljak (2003) - the part
+of the galaxy's image that the PSF's departure from its own best-fitting Gaussian accounts for is taken off the stamp, the
+adaptive moments of what remains are measured, and the PSF's moments are subtracted from them - which gives sigma_corr,
+e1_corr, e2_corr and the resolution of every galaxy from a PSF image per galaxy, per field or for all.
 """
 import numpy as np
 
 from debvader_amd import engine as E
 
 STATUS_CONVERGED, STATUS_ITER_LIMIT, STATUS_FAILED = 0, 2, 3
+# what the PSF correction adds (regauss_status): the catalogue row could not be used, no usable PSF, the galaxy is narrower
+# than its PSF
+STATUS_INELIGIBLE, STATUS_NO_PSF, STATUS_UNRESOLVED = 4, 5, 6
 
 
 def catalogue_dtype(nb_of_bands):
@@ -122,6 +128,100 @@ def residual_records(weight, npix, resid_sum, resid_sq):
         rec["resid_mean"] = np.where(ok, R1 / den, np.nan)
         rec["resid_rms"] = np.where(ok, np.sqrt(R2 / den), np.nan)
     return rec
+
+
+def psf_dtype():
+    """The columns of measure_stamps_psf's recarray: the moments of the re-Gaussianized stamp and the galaxy's PSF the GPU
+    measures, then what the host derives from them."""
+    return [("regauss_row", "<f8"), ("regauss_col", "<f8"), ("regauss_Mrr", "<f8"), ("regauss_Mrc", "<f8"),
+            ("regauss_Mcc", "<f8"), ("rho4", "<f8"), ("regauss_iters", "<i4"), ("regauss_status", "<i4"), ("psf_index", "<i4"),
+            ("psf_Mrr", "<f8"), ("psf_Mrc", "<f8"), ("psf_Mcc", "<f8"), ("psf_rho4", "<f8"), ("sigma_corr", "<f8"),
+            ("e1_corr", "<f8"), ("e2_corr", "<f8"), ("resolution", "<f8")]
+
+
+def psf_records(regauss, regauss_iters, regauss_status, psf_shape, psf_aux, psf_index):
+    """The recarray of measure_stamps_psf from the arrays the engine returns: regauss (N, 6) = {row', col', Mrr', Mrc', Mcc',
+    rho4}, regauss_iters, regauss_status (N,), psf_shape (K, 5), psf_aux (K, 3) and the index (N,) of every galaxy's PSF.
+    psf_Mrr, psf_Mrc, psf_Mcc and psf_rho4 are the rows of the galaxy's PSF (NaN for an index outside 0 .. K - 1).  Derived
+    on the host from M_g = M' - M_P: sigma_corr = det(M_g)^(1/4), e1_corr = (Mcc - Mrr) / (Mcc + Mrr), e2_corr = 2 Mrc /
+    (Mcc + Mrr), resolution = 1 - tr M_P / tr M'; the three shapes are NaN where regauss_status is 3 or above, det M_g <= 0
+    or tr M_g <= 0, the resolution where regauss_status is 3 or above."""
+    regauss = np.asarray(regauss, dtype=np.float64).reshape(-1, 6)
+    n = regauss.shape[0]
+    psf_shape = np.asarray(psf_shape, dtype=np.float64).reshape(-1, 5)
+    psf_aux = np.asarray(psf_aux, dtype=np.float64).reshape(-1, 3)
+    index = np.asarray(psf_index).reshape(n)
+    status = np.asarray(regauss_status).reshape(n)
+    rec = np.recarray((n,), dtype=psf_dtype())
+    for k, name in enumerate(("regauss_row", "regauss_col", "regauss_Mrr", "regauss_Mrc", "regauss_Mcc", "rho4")):
+        rec[name] = regauss[:, k]
+    rec["regauss_iters"] = regauss_iters
+    rec["regauss_status"] = status
+    rec["psf_index"] = index
+    known = (index >= 0) & (index < psf_shape.shape[0])
+    safe = np.where(known, index, 0)
+    P = np.where(known[:, None], psf_shape[safe, 2:5], np.nan) if psf_shape.shape[0] else np.full((n, 3), np.nan)
+    rec["psf_Mrr"], rec["psf_Mrc"], rec["psf_Mcc"] = P[:, 0], P[:, 1], P[:, 2]
+    rec["psf_rho4"] = np.where(known, psf_aux[safe, 2], np.nan) if psf_aux.shape[0] else np.nan
+    with np.errstate(all="ignore"):
+        Grr, Grc, Gcc = regauss[:, 2] - P[:, 0], regauss[:, 3] - P[:, 1], regauss[:, 4] - P[:, 2]
+        det, tr = Grr * Gcc - Grc * Grc, Gcc + Grr
+        ok = (status < STATUS_FAILED) & (det > 0) & (tr > 0)              # (NaN > 0 is False)
+        rec["sigma_corr"] = np.where(ok, np.sqrt(np.sqrt(np.where(ok, det, 1.0))), np.nan)
+        rec["e1_corr"] = np.where(ok, (Gcc - Grr) / np.where(ok, tr, 1.0), np.nan)
+        rec["e2_corr"] = np.where(ok, 2.0 * Grc / np.where(ok, tr, 1.0), np.nan)
+        rec["resolution"] = np.where(status < STATUS_FAILED, 1.0 - (P[:, 0] + P[:, 2]) / (regauss[:, 2] + regauss[:, 4]), np.nan)
+    return rec
+
+
+def measure_psf_moments(psf, psf_sigma0=2.0, tol=1e-10, max_iter=200, ctx=None):
+    """The adaptive moments of PSF images on the GPU, as the PSF correction takes them.
+
+    parameters:
+        psf: (K, ps, ps) float64 PSF images, or one (ps, ps); they need not be normalised
+        psf_sigma0: width in pixels of the first Gaussian weight
+    returns {"psf_shape" (K, 5): {row, col, Mrr, Mrc, Mcc}, "psf_aux" (K, 3): {A_P - the amplitude of the best Gaussian -,
+    the sum of the image, psf_rho4 - its kurtosis, 2 for a Gaussian}, "psf_iters", "psf_status" (K,)}.
+    """
+    if ctx is None:
+        ctx = E.default_context()
+    out = ctx.scene_regauss(np.zeros((0, 8, 8, 1), np.float32), np.zeros((0, 5)), np.zeros(0, np.int32), psf, band=0,
+                            psf_sigma0=psf_sigma0, tol=tol, max_iter=max_iter)
+    return {k: out[k] for k in ("psf_shape", "psf_aux", "psf_iters", "psf_status")}
+
+
+def measure_stamps_psf(mean, psf, psf_index=None, catalogue=None, band=2, sigma0=3.0, tol=1e-10, max_iter=200, psf_sigma0=2.0,
+                       ctx=None):
+    """PSF-corrected shapes of N deblended galaxies on the GPU by re-Gaussianization.
+
+    parameters:
+        mean: the network's mean stamps, (N, cutout_size, cutout_size, bands)
+        psf: (K, ps, ps) float64 PSF images in the stamps' pixel scale, or one (ps, ps) for all galaxies
+        psf_index: (N,), the PSF of every galaxy; None: PSF 0
+        catalogue: the measure_stamps recarray of the same stamps in `band` (row, col, Mrr, Mrc, Mcc and status are read);
+            None: the stamps are measured first with band, sigma0, tol, max_iter
+        psf_sigma0: width in pixels of the first Gaussian weight on the PSF images
+        ctx: the engine context to run on (None: the default context)
+    returns a np.recarray with, per galaxy: regauss_row, regauss_col, regauss_Mrr, regauss_Mrc, regauss_Mcc - the adaptive
+    moments of the stamp less the part the PSF's departure from its best Gaussian accounts for -, rho4 - its kurtosis -,
+    regauss_iters, regauss_status (0 converged, 2 iteration limit, 3 failed, 4 the catalogue row could not be used, 5 no
+    usable PSF, 6 the galaxy is narrower than its PSF), psf_index, psf_Mrr, psf_Mrc, psf_Mcc, psf_rho4 - the moments of the
+    galaxy's PSF - and, derived on the host from M_g = M' - M_P, sigma_corr, e1_corr, e2_corr and resolution = 1 - tr M_P /
+    tr M' (psf_records).  rho4 and psf_rho4 are there for a caller that wants the fourth-order factor of Bernstein & Jarvis
+    (2002) in the last step; the subtraction here is the plain one.
+    """
+    mean, _, _ = E.check_measure_args(mean, None, band, sigma0, tol, max_iter)
+    if ctx is None:
+        ctx = E.default_context()
+    if catalogue is None:
+        out = ctx.scene_measure(mean, None, band=band, sigma0=sigma0, tol=tol, max_iter=max_iter)
+        shape, status = out["shape"], out["status"]
+    else:
+        shape = np.stack([np.asarray(catalogue[k], dtype=np.float64) for k in ("row", "col", "Mrr", "Mrc", "Mcc")], axis=1)
+        status = np.asarray(catalogue["status"], dtype=np.int32)
+    _, index = E.check_psf_args(psf, psf_index, mean.shape[0], psf_sigma0)
+    out = ctx.scene_regauss(mean, shape, status, psf, index, band=band, psf_sigma0=psf_sigma0, tol=tol, max_iter=max_iter)
+    return psf_records(out["regauss"], out["regauss_iters"], out["regauss_status"], out["psf_shape"], out["psf_aux"], index)
 
 
 def measure_blendedness(stamps_mean, catalogue, places, model_fields, data_fields=None, field_ptr=None, band=2, ctx=None):

@@ -505,6 +505,48 @@ int dv_infer_fields_measure_blend(dv_model* m, const double* fields, int32_t M, 
                                   double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
                                   int32_t* iters, int32_t* status, double* blend, int32_t* npix);
 
+/* ---- PSF-corrected shapes: re-Gaussianization (Hirata & Seljak 2003) ----
+ * Float64 throughout.  Per PSF image Q [ps][ps] (not necessarily normalised), once per call: the adaptive-moments iteration
+ * of the measurement above on Q, from the centre and the width psf_sigma0, with the call's tol and max_iter, gives
+ * psf_shape[k] = {q0r, q0c, Mrr, Mrc, Mcc}, psf_iters[k], psf_status[k]; psf_aux[k] = {A_P, FQ, psf_rho4} with FQ = sum Q,
+ * A_P = sum g_P Q / sum g_P^2 (g_X the Gaussian weight of X's moments, as in the measurement) and rho4 as below (A_P and
+ * psf_rho4 are NaN where psf_status is 3 or det M_P is not above 1e-6); eps[j] = (Q[j] - A_P g_P(j)) / FQ.  A PSF is usable
+ * iff psf_status is 0, FQ is finite and positive and det M_P > 1e-6.
+ * Per galaxy i: I = band `band` of its mean stamp, {r0, c0, M_I} = shape[i] and status[i] its row of the measurement,
+ * psf_index[i] its PSF.  regauss_status[i] is 4 when the row is ineligible (status neither 0 nor 2, a value that is not
+ * finite, det M_I not above 1e-6), 5 when psf_index[i] is outside 0 .. K - 1 or the PSF is not usable, 6 when
+ * M_0 = M_I - M_P has Mrr <= 0 or det <= 1e-6 (the galaxy is not resolved); such a row gets six NaN and 0 iterations.
+ * Otherwise A_I = sum g_I I / sum g_I^2, F0 = 2 pi sqrt(det M_I) A_I, f0(d) = F0 / (2 pi sqrt(det M_0)) exp(-d^T M_0^-1 d / 2),
+ *   I'(x) = I(x) - sum_j eps[j] f0(x - (r0, c0) - (j - q0)), j over the ps^2 PSF pixels in row-major order,
+ * and the iteration of the measurement on I', started from (r0, c0, M_I), gives regauss[i] = {r', c', Mrr', Mrc', Mcc',
+ * rho4}, regauss_iters[i] and regauss_status[i] (0 / 2 / 3 as there), with, at the final state,
+ *   rho4 = sum e^(-rho^2 / 2) I' rho^4 / sum e^(-rho^2 / 2) I', rho^2 = (Mcc dr^2 - 2 Mrc dr dc + Mrr dc^2) / det
+ * (2 for a Gaussian; NaN on status 3 or a denominator that is not positive).  The corrected moments M' - M_P, and sigma, e1,
+ * e2 and the resolution 1 - tr M_P / tr M' from them, are left to the caller.  A row has the same bits wherever it sits in
+ * a batch.
+ * dv_scene_regauss: host arrays; stamps [N][cs][cs][nb] float32, shape [N][5], status [N], psf_index [N], psf [K][ps][ps];
+ * regauss [N][6], regauss_iters [N], regauss_status [N], psf_shape [K][5], psf_aux [K][3], psf_iters [K], psf_status [K].
+ * Chunked against free device memory; the PSFs are uploaded and measured once.
+ * dv_infer_fields_measure_psf: dv_infer_fields_measure (same arguments, same bits in every output it shares with it) with the
+ * correction as one more stage behind every chunk's measurement; the new outputs have the bits of dv_scene_regauss on
+ * dv_infer_fields' stamps and dv_infer_fields_measure's rows.  The catalogue-only form (three null field outputs) works as
+ * there.  Refused before any GPU work (DV_E_INVALID): what dv_infer_fields_measure refuses; a null psf or a null output;
+ * K < 1; ps outside 5 .. 33; cs above 64 (a thread keeps at most 16 pixels of I' in registers; every (cs, ps) within these
+ * bounds fits a workgroup's LDS); psf_sigma0 not finite and positive.  A psf_index out of range is the row's status 5, not
+ * a refusal. */
+int dv_scene_regauss(dv_ctx* ctx, const float* stamps, const double* shape, const int32_t* status, const int32_t* psf_index,
+                     int64_t N, int32_t cs, int32_t nb, int32_t band, const double* psf, int32_t K, int32_t ps,
+                     double psf_sigma0, double tol, int32_t max_iter, double* regauss, int32_t* regauss_iters,
+                     int32_t* regauss_status, double* psf_shape, double* psf_aux, int32_t* psf_iters, int32_t* psf_status);
+int dv_infer_fields_measure_psf(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                int32_t* iters, int32_t* status, const double* psf, int32_t K, int32_t ps,
+                                const int32_t* psf_index, double psf_sigma0, double* regauss, int32_t* regauss_iters,
+                                int32_t* regauss_status, double* psf_shape, double* psf_aux, int32_t* psf_iters,
+                                int32_t* psf_status);
+
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)
  * keeps per field, in device memory, `work` (what the next pass detects on and cuts from, at first the field), `final`

@@ -37,6 +37,17 @@ With --profile-one: warm up, one fp32 call (a), exit.
 
     python tools/measure_bench.py --blend [--fields 1024] [--size 259] [--repeat 5]
 
+--psf: what the PSF correction costs, on the same build and box, one 21-px double-Gaussian PSF per
+field -
+
+    (a) catalogue     :  deblend_fields(d, on_device=True, measure=True, return_fields=False): the call as it was
+    (b) catalogue+psf :  the same with psf=(M, 21, 21): the PSFs are measured once, the re-Gaussianization runs behind every
+                         chunk's measurement
+
+    python tools/measure_bench.py --psf [--fields 1024] [--size 259] [--repeat 5]
+
+With --profile-one: warm up, one fp32 call (b), exit.
+
 The cost is reported, not gated.
 """
 import argparse
@@ -183,6 +194,76 @@ def main_blend(a):
     print(json.dumps(result))
 
 
+def _bench_psfs(M, ps=21):
+    """One PSF per field: 0.85 core + 0.15 wing (the wing's covariance 4x the core's), core sigma 1.2 - 1.6 px, a little
+    elliptical, off the pixel centre"""
+    rng = np.random.default_rng(5)
+    r = np.arange(ps, dtype=np.float64)[:, None] - (ps - 1) / 2.0
+    c = np.arange(ps, dtype=np.float64)[None, :] - (ps - 1) / 2.0
+    out = np.zeros((M, ps, ps))
+    for m in range(M):
+        sig, e1, e2 = rng.uniform(1.2, 1.6), rng.uniform(-0.08, 0.08), rng.uniform(-0.08, 0.08)
+        t = 2.0 * sig * sig / np.sqrt(1.0 - e1 * e1 - e2 * e2)
+        Mrr, Mrc, Mcc = 0.5 * t * (1.0 - e1), 0.5 * t * e2, 0.5 * t * (1.0 + e1)
+        dr, dc = r - rng.uniform(-0.5, 0.5), c - rng.uniform(-0.5, 0.5)
+        for w, k in ((0.85, 1.0), (0.15, 4.0)):
+            det = k * k * (Mrr * Mcc - Mrc * Mrc)
+            out[m] += w / (2.0 * np.pi * np.sqrt(det)) * np.exp(-0.5 * k * (Mcc * dr * dr - 2.0 * Mrc * dr * dc + Mrr * dc * dc) / det)
+    return out
+
+
+def main_psf(a):
+    rng = np.random.default_rng(0)
+    F, M = a.size, a.fields
+    base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
+    fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    psf = _bench_psfs(M)
+    quiet = io.StringIO()
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "psf": int(psf.shape[1])}
+    dists = None
+    for dtype in a.dtypes.split(","):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections; one {psf.shape[1]}-px PSF per field; "
+                  f"max_batch {a.max_batch}")
+        status = []
+
+        def with_psf():
+            res = DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=True, measure=True, return_fields=False, psf=psf)
+            status[:] = [np.concatenate([r["regauss_status"] for r in res])]
+            return sum(len(r) for r in res)
+
+        legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False), "catalogue+psf": with_psf}
+        with redirect_stdout(quiet):
+            for fn in legs.values():           # warm-up
+                fn()
+            if a.profile_one:
+                legs["catalogue+psf"]()
+                net._core.engine.close()
+                return
+            times = {k: [] for k in legs}
+            n = 0
+            for _ in range(a.repeat):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    n = fn()
+                    times[k].append(time.perf_counter() - t0)
+        result[dtype] = {"stamps": n, "regauss_status": np.bincount(status[0], minlength=7).tolist()}
+        for k in legs:
+            t = np.array(times[k])
+            print(_row(f"{dtype} {k}", t, n, M))
+            result[dtype][k.replace("+", "_") + "_ms"] = [round(1e3 * x, 2) for x in t]
+        tc, tp = (float(np.median(times[k])) for k in legs)
+        spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
+        print(f"{dtype} catalogue+psf / catalogue {tp / tc:.3f}: {1e3 * (tp - tc):+.1f} ms for {n} galaxies, "
+              f"{1e6 * (tp - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times['catalogue']):.3f} and "
+              f"{spread(times['catalogue+psf']):.3f}); regauss_status 0 .. 6: {result[dtype]['regauss_status']}")
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fields", type=int, default=1024)
@@ -194,7 +275,10 @@ def main():
     ap.add_argument("--profile-one", action="store_true")
     ap.add_argument("--samples", type=int, default=0)
     ap.add_argument("--blend", action="store_true")
+    ap.add_argument("--psf", action="store_true")
     a = ap.parse_args()
+    if a.psf:
+        return main_psf(a)
     if a.blend:
         return main_blend(a)
     if a.samples > 0:
