@@ -50,6 +50,13 @@ class DvMeasureParams(C.Structure):
     _fields_ = [("band", C.c_int32), ("sigma0", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int32)]
 
 
+class DvApertureParams(C.Structure):
+    """dv_aperture_params (include/debvader_hip.h)"""
+    _fields_ = [("n_radii", C.c_int32), ("n_fractions", C.c_int32), ("subsample", C.c_int32), ("bisect_iters", C.c_int32),
+                ("radii", C.c_double * 8), ("fractions", C.c_double * 4), ("kron_factor", C.c_double), ("kron_min", C.c_double),
+                ("kron_limit", C.c_double)]
+
+
 class DvError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libdebvader_hip status {status}: {msg}")
@@ -175,6 +182,12 @@ SIGNATURES = {
     "dv_infer_fields_measure_psf": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
                                               C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32, _d, C.c_int32,
                                               C.c_int32, _i32, C.c_double, _d, _i32, _i32, _d, _d, _i32, _i32]),
+    "dv_aperture_params_default": (C.c_int, [C.POINTER(DvApertureParams)]),
+    "dv_scene_aperture": (C.c_int, [_p, _f, _f, _d, _i32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvApertureParams),
+                                    _d, _d, _d, _d, _d, _d, _d, _i32, _i32]),
+    "dv_infer_fields_measure_aper": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
+                                               C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
+                                               C.POINTER(DvApertureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32]),
     "dv_field_set_open": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),

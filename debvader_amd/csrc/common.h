@@ -364,6 +364,43 @@ int scene_regauss(const float* stamps_h, const double* shape_h, const int32_t* s
                   int cs, int nb, int band, const double* psf_h, int K, int ps, double psf_sigma0, double tol, int max_iter,
                   double* out_h, int32_t* iters_h, int32_t* ostatus_h, double* psf_shape_h, double* psf_aux_h,
                   int32_t* psf_iters_h, int32_t* psf_status_h, int64_t chunk, hipStream_t s);
+// aperture photometry (aperture.hip): per galaxy the fluxes, errors and areas of K circular apertures, the Kron
+// radius {r1, rho_auto, auto_area}, the flux and error in the automatic ellipse, J flux radii in units of the moment ellipse,
+// flags and a status (0; 4 an ineligible catalogue row: every float NaN; 7 no Kron radius: the Kron outputs NaN).
+// ApertureParams: dv_aperture_params as the kernel takes it.  ApertureRows: the output rows, device or host - ap_flux / ap_err
+// [.][K][nb], ap_area [.][K], flux_auto / auto_err [.][nb], kron [.][3], flux_rho [.][J], flags, status [.]; the two errors are
+// null without a stddev stamp.  aperture_check: the refusals, before any GPU work; aperture_rows_check: a missing output.
+// ApertureBufs: the rows of n stamps in device memory.  launch_aperture: n stamps in device memory with their catalogue rows,
+// every per-galaxy pointer at the first stamp's row.  scene_aperture: host arrays, at most `chunk` stamps on the device at a
+// time.
+constexpr int AP_MAX_RADII = 8, AP_MAX_FRACTIONS = 4;
+struct ApertureParams {
+  int K, J, subsample, bisect_iters;
+  double radii[AP_MAX_RADII], fractions[AP_MAX_FRACTIONS];
+  double kron_factor, kron_min, kron_limit;
+};
+struct ApertureRows {
+  double *ap_flux, *ap_err, *ap_area, *flux_auto, *auto_err, *kron, *flux_rho;
+  int *flags, *status;
+};
+int aperture_check(const char* who, int cs, int nb, int band, const ApertureParams& p);
+int aperture_rows_check(const char* who, const ApertureRows& o, const ApertureParams& p, bool err, int64_t n);
+size_t aperture_lds_bytes(int cs);
+ApertureRows aperture_rows_at(const ApertureRows& o, int64_t r, const ApertureParams& p, int nb);
+struct ApertureBufs {
+  DevBuf<double> ap_flux, ap_err, ap_area, flux_auto, auto_err, kron, flux_rho;
+  DevBuf<int> flags, status;
+  static size_t bytes_per_stamp(const ApertureParams& p, int nb) {
+    return ((size_t)(2 * p.K + 2) * nb + p.K + 3 + p.J) * sizeof(double) + 2 * sizeof(int);
+  }
+  int alloc(int64_t n, const ApertureParams& p, int nb, bool err);
+  ApertureRows rows() const;
+  int download(const ApertureRows& h, int64_t n, const ApertureParams& p, int nb, hipStream_t s) const;
+};
+int launch_aperture(const float* mean_dev, const float* stddev_dev, const double* shape_dev, const int* status_dev, int n, int cs,
+                    int nb, int band, const ApertureParams& p, const ApertureRows& rows, hipStream_t s);
+int scene_aperture(const float* mean_h, const float* stddev_h, const double* shape_h, const int32_t* status_h, int64_t N, int cs,
+                   int nb, int band, const ApertureParams& p, const ApertureRows& out_h, int64_t chunk, hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

@@ -3120,6 +3120,13 @@ struct PipeJob {
     double* out = nullptr;             // device [.][6]
     int *iters = nullptr, *status = nullptr;   // device [.]
   } rg;
+  // aperture photometry (dv_infer_fields_measure_aper): behind every chunk's measurement, the circular, Kron
+  // and flux-radius photometry of its mean and stddev stamps from the chunk's catalogue rows; on decides
+  struct Aper {
+    bool on = false;
+    ApertureParams par{};
+    ApertureRows rows{};               // device, row 0 = global stamp 0
+  } ap;
 };
 
 // The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
@@ -3342,6 +3349,9 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
         DV_TRY(launch_regauss(p->dloc[b], j.ms.shape + (size_t)r * 5, j.ms.status + r, j.rg.index + r, nb, cs, j.nb, j.ms.band,
                               *j.rg.psf, j.rg.K, j.rg.ps, j.ms.tol, j.ms.max_iter, j.rg.out + (size_t)r * 6, j.rg.iters + r,
                               j.rg.status + r, p->s_out));
+      if (j.ap.on)
+        DV_TRY(launch_aperture(p->dloc[b], p->dscale[b], j.ms.shape + (size_t)r * 5, j.ms.status + r, nb, cs, j.nb, j.ms.band,
+                               j.ap.par, aperture_rows_at(j.ap.rows, r, j.ap.par, j.nb), p->s_out));
     }
     if (j.loc || j.consumer) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (j.scale || j.consumer) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
@@ -3832,6 +3842,64 @@ int dv_scene_regauss(dv_ctx* c, const float* stamps, const double* shape, const 
   const int64_t chunk = (int64_t)std::max<size_t>(1, (half > fixed ? half - fixed : 0) / per_stamp);
   return scene_regauss(stamps, shape, status, psf_index, N, cs, nb, band, psf, K, ps, psf_sigma0, tol, max_iter, regauss,
                        regauss_iters, regauss_status, psf_shape, psf_aux, psf_iters, psf_status, chunk, c->stream);
+}
+
+static ApertureParams aperture_params(const dv_aperture_params& a) {
+  ApertureParams p{};
+  p.K = a.n_radii;
+  p.J = a.n_fractions;
+  p.subsample = a.subsample;
+  p.bisect_iters = a.bisect_iters;
+  for (int k = 0; k < AP_MAX_RADII; ++k) p.radii[k] = k < a.n_radii ? a.radii[k] : 0.0;
+  for (int k = 0; k < AP_MAX_FRACTIONS; ++k) p.fractions[k] = k < a.n_fractions ? a.fractions[k] : 0.0;
+  p.kron_factor = a.kron_factor;
+  p.kron_min = a.kron_min;
+  p.kron_limit = a.kron_limit;
+  return p;
+}
+
+int dv_aperture_params_default(dv_aperture_params* p) {
+  if (!p) return DV_E_INVALID;
+  *p = dv_aperture_params{};
+  p->n_radii = 3;
+  p->n_fractions = 3;
+  p->subsample = 5;
+  p->bisect_iters = 32;
+  p->radii[0] = 3.0;
+  p->radii[1] = 5.0;
+  p->radii[2] = 8.0;
+  p->fractions[0] = 0.2;
+  p->fractions[1] = 0.5;
+  p->fractions[2] = 0.8;
+  p->kron_factor = 2.5;
+  p->kron_min = 3.5;
+  p->kron_limit = 6.0;
+  return DV_OK;
+}
+
+int dv_scene_aperture(dv_ctx* c, const float* mean, const float* stddev, const double* shape, const int32_t* status, int64_t N,
+                      int32_t cs, int32_t nb, int32_t band, const dv_aperture_params* params, double* ap_flux,
+                      double* ap_flux_err, double* ap_area, double* flux_auto, double* flux_auto_err, double* kron,
+                      double* flux_rho, int32_t* aper_flags, int32_t* aper_status) {
+  if (!c) return DV_E_INVALID;
+  if (!params) {
+    set_error("dv_scene_aperture: params must be given");
+    return DV_E_INVALID;
+  }
+  const ApertureParams par = aperture_params(*params);
+  DV_TRY(aperture_check("dv_scene_aperture", cs, nb, band, par));   // before any GPU work
+  const ApertureRows out{ap_flux, ap_flux_err, ap_area, flux_auto, flux_auto_err, kron, flux_rho, aper_flags, aper_status};
+  if (N <= 0 || !mean || !shape || !status)          // (nothing to size: scene_aperture refuses or returns)
+    return scene_aperture(mean, stddev, shape, status, N, cs, nb, band, par, out, 1, c->stream);
+  DV_TRY(aperture_rows_check("dv_scene_aperture", out, par, stddev != nullptr, N));
+  DV_HIP(hipSetDevice(c->device));
+  // stamps per chunk: half of free device memory holds a chunk's mean and stddev stamps and its rows
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t per_stamp = (size_t)cs * cs * nb * 2 * sizeof(float) + 5 * sizeof(double) + sizeof(int) +
+                           ApertureBufs::bytes_per_stamp(par, nb);
+  const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 2 / per_stamp);
+  return scene_aperture(mean, stddev, shape, status, N, cs, nb, band, par, out, chunk, c->stream);
 }
 
 int dv_scene_measure_mc(dv_ctx* c, const float* samples, int32_t S, int64_t N, int32_t cs, int32_t nb,
@@ -5058,12 +5126,30 @@ struct RegaussStage {               // the PSF-corrected moments of every stamp 
   }
 };
 
+struct ApertureOut {                // dv_infer_fields_measure_aper: the parameters in, the photometry rows out (host)
+  ApertureParams par{};
+  ApertureRows rows{};
+};
+
+struct ApertureStage {              // the aperture photometry of every stamp (7o)
+  ApertureBufs bufs;
+  static size_t bytes_per_stamp(const ApertureOut& o, int nb) { return ApertureBufs::bytes_per_stamp(o.par, nb); }
+  int alloc(const ApertureOut& o, int64_t N, int nb) { return bufs.alloc(N, o.par, nb, true); }
+  void bind(PipeJob::Aper& q, const ApertureOut& o) const { q.on = true; q.par = o.par; q.rows = bufs.rows(); }
+  int download(const ApertureOut& o, int64_t N, int nb, hipStream_t s) {
+    DV_TRY(bufs.download(o.rows, N, o.par, nb, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return DV_OK;
+  }
+};
+
 // j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
 // the device side and the rows are filled in here
 static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
                              const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr,
                              const MeasureMcOut* mco = nullptr, const BlendOut* bo = nullptr,
-                             const int32_t* blend_places = nullptr, const RegaussOut* ro = nullptr) {
+                             const int32_t* blend_places = nullptr, const RegaussOut* ro = nullptr,
+                             const ApertureOut* ao = nullptr) {
   // check
   const double* fields = j.fields;
   const int F = j.F, nb = j.nb;
@@ -5087,7 +5173,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   double* mse_h = fo ? fo->mse : mo ? mo->mse : nullptr;
   DevBuf<double> fdev;                                // the resident group of source fields
   StampTables tab;
-  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs;   // (a stage that does not run stays empty)
+  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs; ApertureStage aps;   // (a stage that does not run stays empty)
   ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
   if (fitting) DV_TRY(fit.make_plan(*fo, c, sfield.data()));
   size_t per_field = fb, reserve = StampTables::bytes((size_t)N, (size_t)M);
@@ -5108,6 +5194,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     reserve += (size_t)N * BlendStage::bytes_per_stamp();
   }
   if (ro) reserve += (size_t)N * RegaussStage::bytes_per_stamp() + RegaussStage::bytes_fixed(*ro);
+  if (ao) reserve += (size_t)N * ApertureStage::bytes_per_stamp(*ao, nb);
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
@@ -5144,6 +5231,10 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (ro) {
     DV_TRY(rgs.alloc(*ro, N, mo->par, s));
     rgs.bind(j.rg, *ro);
+  }
+  if (ao) {
+    DV_TRY(aps.alloc(*ao, N, nb));
+    aps.bind(j.ap, *ao);
   }
   if (fitting) {
     DV_TRY(fit.alloc(*fo, c, gmax, groups));
@@ -5202,6 +5293,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (mco) DV_TRY(catmc.download(*mco, N, nb, s));
   if (bo) DV_TRY(bls.download(*bo, N, s));
   if (ro) DV_TRY(rgs.download(*ro, N, s));
+  if (ao) DV_TRY(aps.download(*ao, N, nb, s));
   if (fo) DV_TRY(mc.download(N, s));
   if (fitting) DV_TRY(fit.download(*fo, N, s));
   drain.dismiss();
@@ -5316,9 +5408,14 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
                                       uint64_t seed, const dv_measure_params* params, double* mean_fields,
                                       double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
                                       double* flux_err, double* shape, int32_t* iters, int32_t* status,
-                                      const BlendOut* bo = nullptr, const RegaussOut* ro = nullptr) {
+                                      const BlendOut* bo = nullptr, const RegaussOut* ro = nullptr,
+                                      const ApertureOut* ao = nullptr) {
   if (!m || !params) return DV_E_INVALID;
   DV_TRY(measure_check(who, m->A.H, nb, params->band, params->sigma0, params->tol, params->max_iter));
+  if (ao) {
+    DV_TRY(aperture_check(who, m->A.H, nb, params->band, ao->par));
+    DV_TRY(aperture_rows_check(who, ao->rows, ao->par, true, N));
+  }
   if (ro) {
     DV_TRY(regauss_check(who, m->A.H, nb, params->band, ro->K, ro->ps, ro->psf_sigma0, params->tol, params->max_iter));
     if (!ro->psf || !ro->psf_shape || !ro->psf_aux || !ro->psf_iters || !ro->psf_status ||
@@ -5352,7 +5449,7 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
   PipeJob j = fields_job(fields, F, nb, starts, seed);
   if (!with_fields) {
     mo.mse = mse_center;
-    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo ? places : nullptr, ro);
+    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo ? places : nullptr, ro, ao);
   }
   FieldsOut fo;
   fo.mean = mean_fields;
@@ -5360,7 +5457,7 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
   fo.residual = residual_fields;
   fo.mse = mse_center;
   fo.places = places;
-  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo, nullptr, ro);
+  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo, nullptr, ro, ao);
 }
 
 int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
@@ -5412,6 +5509,28 @@ int dv_infer_fields_measure_psf(dv_model* m, const double* fields, int32_t M, in
   return infer_fields_measure_entry("dv_infer_fields_measure_psf", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
                                     params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
                                     iters, status, nullptr, &ro);
+}
+
+// ---- aperture photometry beside the catalogue: dv_infer_fields_measure plus circular apertures, the Kron flux
+// and radius and the flux radii of every stamp
+int dv_infer_fields_measure_aper(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                 const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                 const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                 double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                 int32_t* iters, int32_t* status, const dv_aperture_params* aper, double* ap_flux,
+                                 double* ap_flux_err, double* ap_area, double* flux_auto, double* flux_auto_err, double* kron,
+                                 double* flux_rho, int32_t* aper_flags, int32_t* aper_status) {
+  if (!m) return DV_E_INVALID;
+  if (!aper) {
+    set_error("dv_infer_fields_measure_aper: the aperture params must be given");
+    return DV_E_INVALID;
+  }
+  ApertureOut ao;
+  ao.par = aperture_params(*aper);
+  ao.rows = ApertureRows{ap_flux, ap_flux_err, ap_area, flux_auto, flux_auto_err, kron, flux_rho, aper_flags, aper_status};
+  return infer_fields_measure_entry("dv_infer_fields_measure_aper", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
+                                    params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
+                                    iters, status, nullptr, nullptr, &ao);
 }
 
 // ---- the Monte-Carlo catalogue beside it: dv_infer_fields_measure plus means and standard deviations of

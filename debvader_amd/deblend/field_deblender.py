@@ -454,6 +454,14 @@ class DeblendFieldBatch:
 
         return psf_dtype()
 
+    @staticmethod
+    def aperture_columns(nb_of_bands, n_radii, n_fractions):
+        """What deblend_fields(measure=True, apertures=...) appends behind measure_columns: the recarray of
+        measure_apertures."""
+        from debvader_amd.measure.measurement import aperture_dtype
+
+        return aperture_dtype(nb_of_bands, n_radii, n_fractions)
+
     def _psf_index(self, psf, psf_index, field_ptr):
         """(psf (K, ps, ps), index (N,)) of a deblend_fields(psf=...) call: one image for all galaxies, one per field (the
         index follows from field_ptr), or K images with the caller's index per galaxy - a flat (N,) array or a list of M
@@ -529,7 +537,7 @@ class DeblendFieldBatch:
     def deblend_fields(self, galaxy_distances_to_center=None, mse_criterion=100.0, on_device=False,
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
                        measure=False, return_fields=True, measure_samples=0, blendedness=False,
-                       psf=None, psf_index=None, optimise_positions=False):
+                       psf=None, psf_index=None, apertures=None, flux_fractions=None, optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -586,7 +594,18 @@ class DeblendFieldBatch:
         rho4, psf_index, psf_Mrr, psf_Mrc, psf_Mcc, psf_rho4 and the derived sigma_corr, e1_corr, e2_corr, resolution;
         debvader_amd.measure.measurement.measure_stamps_psf describes them) and self.psf_moments holds the PSFs' own rows.
         The other columns and the fields are those of the same call without it.  It is not available with blendedness,
-        measure_samples, optimise_positions=True or epistemic_uncertainty_estimation=True."""
+        measure_samples, optimise_positions=True or epistemic_uncertainty_estimation=True.
+
+        apertures=(R, ...) (with measure=True and on_device=True, with or without return_fields): aperture photometry
+        (dv_infer_fields_measure_aper) behind every chunk's measurement on the stamps in device memory:
+        the flux, its error and the area in up to 8 circles of the given radii in pixels about the measured centroid, the
+        Kron radius and the flux in the Kron ellipse of the galaxy's own moments, and the radii that hold flux_fractions
+        (up to 4, by default 0.2, 0.5 and 0.8) of that flux.  The recarrays gain aperture_columns (ap_flux, ap_flux_err,
+        ap_area, flux_auto, flux_auto_err, kron_radius, rho_auto, auto_area, flux_rho, aper_flags, aper_status and the derived
+        flux_radius, kron_a, kron_b, concentration; debvader_amd.measure.measurement.measure_apertures describes them).
+        apertures=() gives the Kron columns alone.  The other columns and the fields are those of the same call without it.
+        It is not available with psf, blendedness, measure_samples, optimise_positions=True or
+        epistemic_uncertainty_estimation=True."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
@@ -623,6 +642,37 @@ class DeblendFieldBatch:
             raise ValueError("psf cannot be combined with epistemic_uncertainty_estimation=True: the PSF correction is a "
                              "stage of the plain measuring composite call only (dv_infer_fields_measure_psf), not of the "
                              "Monte-Carlo call")
+        with_aper = apertures is not None
+        if flux_fractions is not None and not with_aper:
+            raise ValueError("flux_fractions are fractions of the Kron flux of the aperture photometry: give apertures too "
+                             "(apertures=() for the Kron columns alone)")
+        if with_aper and not (measure and on_device):
+            raise ValueError("apertures need measure=True and on_device=True: the apertures are centred on the measured "
+                             "centroid and taken where the stamps lie in device memory (dv_infer_fields_measure_aper); on the "
+                             "default path use debvader_amd.measure.measurement.measure_apertures on the returned stamps")
+        if with_aper and with_psf:
+            raise ValueError("apertures cannot be combined with psf: the aperture photometry and the PSF correction are "
+                             "stages of two different measuring calls (dv_infer_fields_measure_aper, "
+                             "dv_infer_fields_measure_psf)")
+        if with_aper and blendedness:
+            raise ValueError("apertures cannot be combined with blendedness=True: the aperture photometry and the blendedness "
+                             "sums are stages of two different measuring calls (dv_infer_fields_measure_aper, "
+                             "dv_infer_fields_measure_blend)")
+        if with_aper and int(measure_samples or 0):
+            raise ValueError("apertures cannot be combined with measure_samples: the aperture photometry is not a stage of "
+                             "the Monte-Carlo catalogue call (dv_infer_fields_measure_mc)")
+        if with_aper and fit:
+            raise ValueError("apertures cannot be combined with optimise_positions=True: the aperture photometry is a stage "
+                             "of the plain measuring composite call only (dv_infer_fields_measure_aper), not of the "
+                             "position-fit call")
+        if with_aper and mc:
+            raise ValueError("apertures cannot be combined with epistemic_uncertainty_estimation=True: the aperture "
+                             "photometry is a stage of the plain measuring composite call only "
+                             "(dv_infer_fields_measure_aper), not of the Monte-Carlo call")
+        if with_aper:
+            from debvader_amd.engine import aperture_params
+
+            aper_par = aperture_params(apertures, (0.2, 0.5, 0.8) if flux_fractions is None else flux_fractions)   # (ValueError)
         if int(measure_samples) != measure_samples or int(measure_samples) < 0:
             raise ValueError(f"measure_samples must be an integer >= 0, got {measure_samples}")
         nmc = int(measure_samples)
@@ -698,6 +748,12 @@ class DeblendFieldBatch:
                     out = eng.infer_fields_measure_psf(self.field_images, starts, field_ptr, psf, psf_index,
                                                        places=places if return_fields else None, seed=seed,
                                                        return_fields=bool(return_fields))
+                elif with_aper:
+                    out = eng.infer_fields_measure_aper(self.field_images, starts, field_ptr,
+                                                        places=places if return_fields else None, seed=seed,
+                                                        radii=list(aper_par.radii)[:aper_par.n_radii],
+                                                        fractions=list(aper_par.fractions)[:aper_par.n_fractions],
+                                                        return_fields=bool(return_fields))
                 elif measure:
                     out = eng.infer_fields_measure(self.field_images, starts, field_ptr, places=places if return_fields else None,
                                                    seed=seed, return_fields=bool(return_fields))
@@ -749,6 +805,13 @@ class DeblendFieldBatch:
                 cat_psf = psf_records(out["regauss"], out["regauss_iters"], out["regauss_status"], out["psf_shape"],
                                       out["psf_aux"], psf_index)
                 self.psf_moments = {k: out[k] for k in ("psf_shape", "psf_aux", "psf_iters", "psf_status")}
+            if with_aper:
+                from debvader_amd.measure.measurement import aperture_records
+
+                columns = columns + self.aperture_columns(nb, aper_par.n_radii, aper_par.n_fractions)
+                cat_ap = aperture_records(out["ap_flux"], out["ap_flux_err"], out["ap_area"], out["flux_auto"],
+                                          out["flux_auto_err"], out["kron"], out["flux_rho"], out["aper_flags"],
+                                          out["aper_status"], out["shape"])
             cat = catalogue_records(out["flux"], out["flux_err"], out["shape"], out["iters"], out["status"]) if on_device \
                 else measure_stamps(out["loc"], out["scale"], ctx=self._ctx)
             # a stamp's pixel (row, col) is the field's pixel start + (row, col); distances count from pixel int(F / 2)
@@ -777,6 +840,9 @@ class DeblendFieldBatch:
                 if with_psf:
                     for k in cat_psf.dtype.names:
                         rec[k] = cat_psf[k][lo:hi]
+                if with_aper:
+                    for k in cat_ap.dtype.names:
+                        rec[k] = cat_ap[k][lo:hi]
             if on_device:
                 rec["mse_center"] = mse_center[lo:hi]
                 if mc:

@@ -208,6 +208,59 @@ def _regauss_out(n, K):
                  _dp(out["psf_aux"]), _ip(out["psf_iters"]), _ip(out["psf_status"])]
 
 
+APERTURE_MAX_RADII, APERTURE_MAX_FRACTIONS = 8, 4      # what dv_aperture_params holds
+APERTURE_KEYS = ("ap_flux", "ap_flux_err", "ap_area", "flux_auto", "flux_auto_err", "kron", "flux_rho", "aper_flags",
+                 "aper_status")                        # the outputs of the aperture photometry, in the C-ABI's order
+
+
+def aperture_params(radii=(3.0, 5.0, 8.0), fractions=(0.2, 0.5, 0.8), subsample=5, kron_factor=2.5, kron_min=3.5,
+                    kron_limit=6.0, bisect_iters=32) -> "_lib.DvApertureParams":
+    """The checked dv_aperture_params of the aperture photometry (the library refuses the same, after the arrays are
+    built): up to 8 radii in pixels, up to 4 flux fractions strictly between 0 and 1."""
+    radii = np.asarray(radii, dtype=np.float64).reshape(-1)
+    fractions = np.asarray(fractions, dtype=np.float64).reshape(-1)
+    if radii.size > APERTURE_MAX_RADII or fractions.size > APERTURE_MAX_FRACTIONS:
+        raise ValueError(f"{radii.size} aperture radii and {fractions.size} flux fractions: at most {APERTURE_MAX_RADII} "
+                         f"radii and {APERTURE_MAX_FRACTIONS} fractions are taken")
+    if not np.all(np.isfinite(radii) & (radii > 0)):
+        raise ValueError(f"aperture radii must be finite and positive (got {radii.tolist()})")
+    if not np.all((fractions > 0) & (fractions < 1)):
+        raise ValueError(f"flux fractions must lie strictly between 0 and 1 (got {fractions.tolist()})")
+    if int(subsample) != subsample or not 1 <= int(subsample) <= 9:
+        raise ValueError(f"subsample must be an integer 1 .. 9 (got {subsample})")
+    if int(bisect_iters) != bisect_iters or not 1 <= int(bisect_iters) <= 60:
+        raise ValueError(f"bisect_iters must be an integer 1 .. 60 (got {bisect_iters})")
+    for name, v in (("kron_factor", kron_factor), ("kron_min", kron_min), ("kron_limit", kron_limit)):
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{name} must be finite and positive (got {v})")
+    par = _lib.DvApertureParams()
+    par.n_radii, par.n_fractions, par.subsample, par.bisect_iters = radii.size, fractions.size, int(subsample), int(bisect_iters)
+    for k, v in enumerate(radii):
+        par.radii[k] = float(v)
+    for k, v in enumerate(fractions):
+        par.fractions[k] = float(v)
+    par.kron_factor, par.kron_min, par.kron_limit = float(kron_factor), float(kron_min), float(kron_limit)
+    return par
+
+
+def _aperture_out(n, nb, par, err=True):
+    """The result dictionary of the aperture photometry and its pointers in the C-ABI's order (the two errors only with a
+    stddev stamp; an output without rows - no radii, no fractions - goes as a null pointer)."""
+    K, J = par.n_radii, par.n_fractions
+    out = dict(ap_flux=np.zeros((n, K, nb), np.float64), ap_flux_err=np.zeros((n, K, nb), np.float64),
+               ap_area=np.zeros((n, K), np.float64), flux_auto=np.zeros((n, nb), np.float64),
+               flux_auto_err=np.zeros((n, nb), np.float64), kron=np.zeros((n, 3), np.float64),
+               flux_rho=np.zeros((n, J), np.float64), aper_flags=np.zeros(n, np.int32), aper_status=np.zeros(n, np.int32))
+    if not err:
+        del out["ap_flux_err"], out["flux_auto_err"]
+    ptrs = []
+    for k in APERTURE_KEYS:
+        a = out.get(k)
+        empty = a is None or (K == 0 and k.startswith("ap_")) or (J == 0 and k == "flux_rho")
+        ptrs.append(None if empty else (_ip(a) if a.dtype == np.int32 else _dp(a)))
+    return out, ptrs
+
+
 def check_measure_mc_args(samples, band, sigma0, tol, max_iter):
     """(samples, params) of scene_measure_mc: C-contiguous float32 sample stamps (S, N, cs, cs, bands), S >= 1."""
     samples = _f32c(samples)
@@ -681,6 +734,35 @@ class Context:
         out, ptrs = _regauss_out(n, K)
         check(lib.dv_scene_regauss(self._h, _fp(stamps), _dp(shape), _ip(status), _ip(index), n, cs, nb, par.band, _dp(psf), K, ps,
                                    float(psf_sigma0), par.tol, par.max_iter, *ptrs))
+        return out
+
+    APER_OK, APER_INELIGIBLE, APER_NO_KRON = 0, 4, 7          # aper_status of scene_aperture
+    APER_FLAG_AUTO_TRUNCATED, APER_FLAG_LIMIT_TRUNCATED, APER_FLAG_KRON_MIN = 1 << 8, 1 << 9, 1 << 10   # (bit k < 8: circle k truncated)
+
+    def scene_aperture(self, mean, shape, status, stddev=None, radii=(3.0, 5.0, 8.0), fractions=(0.2, 0.5, 0.8), band: int = 2,
+                       subsample: int = 5, kron_factor: float = 2.5, kron_min: float = 3.5, kron_limit: float = 6.0,
+                       bisect_iters: int = 32) -> Dict[str, np.ndarray]:
+        """Aperture photometry of N galaxies on the GPU (dv_scene_aperture): mean, stddev (N, cs, cs,
+        bands) the network's stamps, taken as float32 (stddev optional); shape (N, 5) and status (N,) their scene_measure rows
+        in band `band`.  Returns {"ap_flux", ["ap_flux_err"] (N, K, bands): the flux in K circles of `radii` pixels about the
+        measured centroid, pixels weighted by the share of their subsample x subsample sub-pixels inside; "ap_area" (N, K);
+        "flux_auto", ["flux_auto_err"] (N, bands): the flux in the Kron ellipse; "kron" (N, 3): {r1 - the first radial moment
+        of band `band` in units of the moment ellipse, taken inside kron_limit -, rho_auto = max(kron_factor r1, kron_min),
+        auto_area}; "flux_rho" (N, J): the ellipse radii that hold `fractions` of flux_auto[band]; "aper_flags" (N,): bit k
+        circle k leaves the stamp, APER_FLAG_AUTO_TRUNCATED, APER_FLAG_LIMIT_TRUNCATED, APER_FLAG_KRON_MIN; "aper_status"
+        (N,): APER_OK, APER_INELIGIBLE (the row's status is 3, a value is not finite or det M <= 1e-6: every float NaN),
+        APER_NO_KRON (no positive flux inside kron_limit: the Kron outputs NaN, the circles given)}, float64 throughout."""
+        mean, stddev, mpar = check_measure_args(mean, stddev, band, 1.0, 1.0, 0)
+        n, cs, nb = mean.shape[0], mean.shape[1], mean.shape[3]
+        shape = np.ascontiguousarray(shape, dtype=np.float64)
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        if shape.shape != (n, 5) or status.shape != (n,):
+            raise ValueError(f"expected shape ({n}, 5) and status ({n},), got {shape.shape}, {status.shape}")
+        par = aperture_params(radii, fractions, subsample, kron_factor, kron_min, kron_limit, bisect_iters)
+        out, ptrs = _aperture_out(n, nb, par, err=stddev is not None)
+        if n:
+            check(lib.dv_scene_aperture(self._h, _fp(mean), _fp(stddev), _dp(shape), _ip(status), n, cs, nb, mpar.band,
+                                        C.byref(par), *ptrs))
         return out
 
     CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
@@ -1201,6 +1283,46 @@ class Engine:
     def scene_regauss(self, stamps, shape, status, psf, psf_index=None, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_regauss on this engine's GPU context."""
         return self.ctx.scene_regauss(stamps, shape, status, psf, psf_index, **kw)
+
+    def infer_fields_measure_aper(self, fields, starts, field_ptr, places=None, seed=0, band: int = 2, sigma0: float = 3.0,
+                                  tol: float = 1e-10, max_iter: int = 200, radii=(3.0, 5.0, 8.0), fractions=(0.2, 0.5, 0.8),
+                                  subsample: int = 5, kron_factor: float = 2.5, kron_min: float = 3.5, kron_limit: float = 6.0,
+                                  bisect_iters: int = 32, return_fields=True, residual=True,
+                                  mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure() plus the aperture photometry (dv_infer_fields_measure_aper): returns
+        its dictionary, bit for bit, plus scene_aperture's {"ap_flux", "ap_flux_err", "ap_area", "flux_auto",
+        "flux_auto_err", "kron", "flux_rho", "aper_flags", "aper_status"} - the bits of scene_aperture on infer_fields' mean
+        and stddev stamps and infer_fields_measure's rows.  The photometry runs behind every chunk's measurement on the
+        stamps in device memory.  return_fields=False is the catalogue-only call, as there."""
+        if return_fields and places is None:
+            raise ValueError("places are needed to composite the fields; return_fields=False measures without them")
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places if return_fields else None)
+        nb = fields.shape[3]
+        par = measure_params(band, sigma0, tol, max_iter, nb)
+        apar = aperture_params(radii, fractions, subsample, kron_factor, kron_min, kron_limit, bisect_iters)
+        if return_fields:
+            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
+        else:
+            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
+            ptrs = [None, None, None, _dp(out.get("mse_center"))]
+            args = args[:5] + [None] + args[5:]
+        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
+                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
+        ap, ap_ptrs = _aperture_out(N, nb, apar)
+        out.update(ap)
+        check(lib.dv_infer_fields_measure_aper(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
+                                               _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"]),
+                                               C.byref(apar), *ap_ptrs))
+        return out
+
+    def infer_cutouts_measure_aper(self, field, starts, places=None, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_aper() for one field (F, F, bands): the field-sized results under singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_aper(fields, starts, fp, places=places, seed=seed, **kw))
+
+    def scene_aperture(self, mean, shape, status, stddev=None, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_aperture on this engine's GPU context."""
+        return self.ctx.scene_aperture(mean, shape, status, stddev, **kw)
 
     def infer_fields_measure_mc(self, fields, starts, field_ptr, places=None, seed=0, mc_seed=0, nsamples=100, band: int = 2,
                                 sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, return_fields=True,

@@ -11,7 +11,10 @@ own weight belongs to its neighbours - is DESIGN.md section 7l (measure_blendedn
 is DESIGN.md section 7n (measure_stamps_psf, csrc/regauss.hip): the re-Gaussianization of Hirata & Seljak (2003) - the part
 of the galaxy's image that the PSF's departure from its own best-fitting Gaussian accounts for is taken off the stamp, the
 adaptive moments of what remains are measured, and the PSF's moments are subtracted from them - which gives sigma_corr,
-e1_corr, e2_corr and the resolution of every galaxy from a PSF image per galaxy, per field or for all.
+e1_corr, e2_corr and the resolution of every galaxy from a PSF image per galaxy, per field or for all.  Aperture photometry
+is DESIGN.md section 7o (measure_apertures, csrc/aperture.hip): fluxes in fixed circular apertures about the measured
+centroid, the Kron radius and the flux in the Kron ellipse of the galaxy's own moments (SExtractor's FLUX_AUTO and
+KRON_RADIUS), and the radii that hold given fractions of that flux (FLUX_RADIUS).
 """
 import numpy as np
 
@@ -222,6 +225,105 @@ def measure_stamps_psf(mean, psf, psf_index=None, catalogue=None, band=2, sigma0
     _, index = E.check_psf_args(psf, psf_index, mean.shape[0], psf_sigma0)
     out = ctx.scene_regauss(mean, shape, status, psf, index, band=band, psf_sigma0=psf_sigma0, tol=tol, max_iter=max_iter)
     return psf_records(out["regauss"], out["regauss_iters"], out["regauss_status"], out["psf_shape"], out["psf_aux"], index)
+
+
+# aper_status of the aperture photometry: the catalogue row could not be used, no Kron radius (no positive flux inside
+# kron_limit); aper_flags: bit k < 8 circle k is truncated by the stamp, then these
+STATUS_NO_KRON = 7
+APER_FLAG_AUTO_TRUNCATED, APER_FLAG_LIMIT_TRUNCATED, APER_FLAG_KRON_MIN = 1 << 8, 1 << 9, 1 << 10
+
+
+def aperture_dtype(nb_of_bands, n_radii, n_fractions):
+    """The columns of measure_apertures' recarray: what the GPU measures, then what the host derives from it."""
+    nb, K, J = int(nb_of_bands), int(n_radii), int(n_fractions)
+    return [("ap_flux", "<f8", (K, nb)), ("ap_flux_err", "<f8", (K, nb)), ("ap_area", "<f8", (K,)), ("flux_auto", "<f8", (nb,)),
+            ("flux_auto_err", "<f8", (nb,)), ("kron_radius", "<f8"), ("rho_auto", "<f8"), ("auto_area", "<f8"),
+            ("flux_rho", "<f8", (J,)), ("aper_flags", "<i4"), ("aper_status", "<i4"), ("flux_radius", "<f8", (J,)),
+            ("kron_a", "<f8"), ("kron_b", "<f8"), ("concentration", "<f8")]
+
+
+def aperture_records(ap_flux, ap_flux_err, ap_area, flux_auto, flux_auto_err, kron, flux_rho, aper_flags, aper_status, shape):
+    """The recarray of measure_apertures from the arrays the engine returns (scene_aperture's, the two errors None without a
+    stddev stamp: NaN) and shape (N, 5), the catalogue rows they were measured from.  kron_radius, rho_auto and auto_area are
+    the three columns of kron.  Derived on the host, M = {Mrr, Mrc, Mcc} of shape: flux_radius = flux_rho det(M)^(1/4), the
+    radii in circularised pixels; kron_a >= kron_b = rho_auto sqrt(lambda) with lambda the eigenvalues of M, the semi-axes of
+    the automatic ellipse in pixels; concentration = 5 log10(flux_radius[J - 1] / flux_radius[0]) with at least two
+    fractions.  NaN follows the GPU's: the three are NaN where aper_status is not 0, the concentration also with fewer than
+    two fractions or a flux radius that is not positive."""
+    flux_auto = np.asarray(flux_auto, dtype=np.float64)
+    n, nb = flux_auto.shape
+    ap_area = np.asarray(ap_area, dtype=np.float64).reshape(n, -1)
+    flux_rho = np.asarray(flux_rho, dtype=np.float64).reshape(n, -1)
+    K, J = ap_area.shape[1], flux_rho.shape[1]
+    kron = np.asarray(kron, dtype=np.float64).reshape(n, 3)
+    shape = np.asarray(shape, dtype=np.float64).reshape(n, 5)
+    status = np.asarray(aper_status).reshape(n)
+    rec = np.recarray((n,), dtype=aperture_dtype(nb, K, J))
+    rec["ap_flux"] = np.asarray(ap_flux, dtype=np.float64).reshape(n, K, nb)
+    rec["ap_flux_err"] = np.nan if ap_flux_err is None else np.asarray(ap_flux_err, dtype=np.float64).reshape(n, K, nb)
+    rec["ap_area"] = ap_area
+    rec["flux_auto"] = flux_auto
+    rec["flux_auto_err"] = np.nan if flux_auto_err is None else np.asarray(flux_auto_err, dtype=np.float64)
+    rec["kron_radius"], rec["rho_auto"], rec["auto_area"] = kron[:, 0], kron[:, 1], kron[:, 2]
+    rec["flux_rho"] = flux_rho
+    rec["aper_flags"] = aper_flags
+    rec["aper_status"] = status
+    Mrr, Mrc, Mcc = shape[:, 2], shape[:, 3], shape[:, 4]
+    ok = status == 0
+    with np.errstate(all="ignore"):
+        det = Mrr * Mcc - Mrc * Mrc
+        scale = np.where(ok, np.sqrt(np.sqrt(np.where(ok, det, 1.0))), np.nan)
+        rec["flux_radius"] = flux_rho * scale[:, None]
+        half, root = 0.5 * (Mrr + Mcc), np.sqrt(0.25 * (Mrr - Mcc) * (Mrr - Mcc) + Mrc * Mrc)
+        rec["kron_a"] = np.where(ok, kron[:, 1] * np.sqrt(half + root), np.nan)
+        rec["kron_b"] = np.where(ok, kron[:, 1] * np.sqrt(half - root), np.nan)
+        if J >= 2:
+            first, last = rec["flux_radius"][:, 0], rec["flux_radius"][:, J - 1]
+            good = ok & (first > 0) & (last > 0)                    # (NaN > 0 is False)
+            rec["concentration"] = np.where(good, 5.0 * np.log10(np.where(good, last, 1.0) / np.where(good, first, 1.0)), np.nan)
+        else:
+            rec["concentration"] = np.nan
+    return rec
+
+
+def measure_apertures(mean, stddev=None, catalogue=None, radii=(3.0, 5.0, 8.0), fractions=(0.2, 0.5, 0.8), band=2, sigma0=3.0,
+                      tol=1e-10, max_iter=200, subsample=5, kron_factor=2.5, kron_min=3.5, kron_limit=6.0, bisect_iters=32,
+                      ctx=None):
+    """Aperture photometry of N deblended galaxies on the GPU.
+
+    parameters:
+        mean: the network's mean stamps, (N, cutout_size, cutout_size, bands)
+        stddev: its stddev stamps (same shape); None: the two error columns are NaN
+        catalogue: the measure_stamps recarray of the same stamps in `band` (row, col, Mrr, Mrc, Mcc and status are read);
+            None: the stamps are measured first with band, sigma0, tol, max_iter
+        radii: up to 8 radii in pixels of circular apertures about the measured centroid; () gives the Kron columns alone
+        fractions: up to 4 fractions of flux_auto[band] whose radii are wanted (0.5: the half-light radius)
+        subsample: a boundary pixel counts by the share of its subsample x subsample sub-pixel centres inside (1 .. 9)
+        kron_factor, kron_min, kron_limit: the automatic ellipse has the radius max(kron_factor r1, kron_min) in units of the
+            moment ellipse, r1 the first radial moment of the light inside kron_limit
+        bisect_iters: halvings of [0, rho_auto] per flux radius
+        ctx: the engine context to run on (None: the default context)
+    returns a np.recarray with, per galaxy: ap_flux, ap_flux_err (K, bands), ap_area (K,), flux_auto, flux_auto_err (bands,),
+    kron_radius (r1), rho_auto, auto_area, flux_rho (J,) in units of the moment ellipse, aper_flags (bit k: circle k is
+    truncated by the stamp; APER_FLAG_AUTO_TRUNCATED, APER_FLAG_LIMIT_TRUNCATED, APER_FLAG_KRON_MIN), aper_status (0;
+    STATUS_INELIGIBLE: the catalogue row could not be used, every float NaN; STATUS_NO_KRON: no positive flux inside
+    kron_limit, the Kron columns NaN) and, derived on the host, flux_radius (J,) in circularised pixels, kron_a, kron_b - the
+    semi-axes of the automatic ellipse in pixels - and concentration = 5 log10(flux_radius[J - 1] / flux_radius[0])
+    (aperture_records).
+    """
+    mean, stddev, _ = E.check_measure_args(mean, stddev, band, sigma0, tol, max_iter)
+    if ctx is None:
+        ctx = E.default_context()
+    if catalogue is None:
+        out = ctx.scene_measure(mean, None, band=band, sigma0=sigma0, tol=tol, max_iter=max_iter)
+        shape, status = out["shape"], out["status"]
+    else:
+        shape = np.stack([np.asarray(catalogue[k], dtype=np.float64) for k in ("row", "col", "Mrr", "Mrc", "Mcc")], axis=1)
+        status = np.asarray(catalogue["status"], dtype=np.int32)
+    out = ctx.scene_aperture(mean, shape, status, stddev, radii=radii, fractions=fractions, band=band, subsample=subsample,
+                             kron_factor=kron_factor, kron_min=kron_min, kron_limit=kron_limit, bisect_iters=bisect_iters)
+    return aperture_records(out["ap_flux"], out.get("ap_flux_err"), out["ap_area"], out["flux_auto"], out.get("flux_auto_err"),
+                            out["kron"], out["flux_rho"], out["aper_flags"], out["aper_status"], shape)
 
 
 def measure_blendedness(stamps_mean, catalogue, places, model_fields, data_fields=None, field_ptr=None, band=2, ctx=None):

@@ -547,6 +547,67 @@ int dv_infer_fields_measure_psf(dv_model* m, const double* fields, int32_t M, in
                                 int32_t* regauss_status, double* psf_shape, double* psf_aux, int32_t* psf_iters,
                                 int32_t* psf_status);
 
+/* ---- aperture photometry: circular apertures, Kron flux and radius, flux radii ----
+ * Float64 throughout; every expression is evaluated in the order written, each operation rounded on its own (no fused
+ * multiply-add), with + - * /, comparisons and the correctly rounded square root only.  Per galaxy i: P its mean stamp
+ * [cs][cs][nb] and S its stddev stamp (float32 widened), {r0, c0, Mrr, Mrc, Mcc} = shape[i] and status[i] its row of the
+ * measurement in band `band`, I = P[:,:,band].  aper_status[i] is 4 when the row is ineligible (status neither 0 nor 2, a
+ * value that is not finite, det = Mrr Mcc - Mrc Mrc not finite or not above 1e-6): every float output of the row is NaN and
+ * aper_flags[i] is 0.  Otherwise, with dr = r - r0, dc = c - c0, o_i = (i + 0.5) / s - 0.5 for i = 0 .. s - 1 (s = subsample),
+ * the weight of pixel (r, c) in a region inside(x, y) is w = #{(i, j): inside(dr + o_i, dc + o_j)} / (s s); circle k is
+ * x x + y y <= R_k R_k, the ellipse of radius rho is q(x, y) = (a x) x + (b x) y + (c y) y <= rho rho with a = Mcc / det,
+ * b = (-2 Mrc) / det, c = Mrr / det.  Every sum below runs over the pixels of the stamp whose weight is positive, and the
+ * weight is carried as its count n: sum w x is (sum n x) / (s s), one division per sum, and sum w adds whole numbers, so an
+ * area has the same bits in any order of summation.
+ *   1. ap_flux[i][k][b] = sum w_k P[r,c,b], ap_flux_err[i][k][b] = sqrt(sum w_k (S[r,c,b] S[r,c,b])), ap_area[i][k] = sum w_k.
+ *   2. Over the pixel centres with q(dr, dc) <= kron_limit kron_limit: r1 = sum sqrt(q) I / sum I.  If sum I is not finite or
+ *      not positive, or r1 is not finite, aper_status[i] is 7 and everything under 2 - 4 is NaN (the circles are still given).
+ *      rho_auto = kron_factor r1, or kron_min where that is smaller.
+ *   3. The ellipse of radius rho_auto gives flux_auto[i][b], flux_auto_err[i][b] and auto_area; kron[i] = {r1, rho_auto,
+ *      auto_area}.
+ *   4. F(rho) = sum w_rho I, t_j = f_j flux_auto[i][band]; from lo = 0, hi = rho_auto, bisect_iters times: mid = 0.5 (lo + hi),
+ *      F(mid) >= t_j ? hi = mid : lo = mid; flux_rho[i][j] = hi, in units of the moment ellipse (times det^(1/4): circularised
+ *      pixels).
+ * aper_flags[i]: bit k < 8 circle k leaves the stamp (r0 - R_k < -0.5, r0 + R_k > cs - 0.5, or the same for c0); bit 8 the
+ * automatic ellipse does (half-extents rho_auto sqrt(Mrr), rho_auto sqrt(Mcc)); bit 9 the kron_limit ellipse does; bit 10
+ * kron_min decided rho_auto.  Pixels outside the stamp do not exist: a flagged aperture is truncated.  A row has the same bits
+ * wherever it sits in a batch.
+ * dv_scene_aperture: host arrays; mean and stddev [N][cs][cs][nb] float32, shape [N][5], status [N]; ap_flux / ap_flux_err
+ * [N][K][nb], ap_area [N][K], flux_auto / flux_auto_err [N][nb], kron [N][3], flux_rho [N][J], aper_flags / aper_status [N].
+ * stddev, ap_flux_err and flux_auto_err are null together; with n_radii = 0 the three ap_ outputs may be null, with
+ * n_fractions = 0 flux_rho.  Chunked against half of free device memory.
+ * dv_infer_fields_measure_aper: dv_infer_fields_measure (same arguments, same bits in every output it shares with it) with the
+ * photometry as one more stage behind every chunk's measurement, on the chunk's mean and stddev stamps in device memory; the
+ * new outputs have the bits of dv_scene_aperture on dv_infer_fields' stamps and dv_infer_fields_measure's rows.  The
+ * catalogue-only form (three null field outputs) works as there.
+ * Refused before any GPU work (DV_E_INVALID): what dv_infer_fields_measure refuses (dv_scene_aperture: the same limits on
+ * cs, nb and band); null params; a missing output; n_radii outside 0 .. 8 or n_fractions outside 0 .. 4; a radius that is not
+ * finite and positive; a fraction not strictly between 0 and 1; subsample outside 1 .. 9; bisect_iters outside 1 .. 60;
+ * kron_factor, kron_min or kron_limit not finite and positive. */
+typedef struct dv_aperture_params {
+  int32_t n_radii;         /* K, 0 .. 8 (3) */
+  int32_t n_fractions;     /* J, 0 .. 4 (3) */
+  int32_t subsample;       /* sub-pixels per pixel side, 1 .. 9 (5) */
+  int32_t bisect_iters;    /* halvings per flux radius, 1 .. 60 (32) */
+  double radii[8];         /* aperture radii in pixels (3, 5, 8) */
+  double fractions[4];     /* flux fractions (0.2, 0.5, 0.8) */
+  double kron_factor;      /* rho_auto = kron_factor r1 (2.5) */
+  double kron_min;         /* the smallest rho_auto (3.5) */
+  double kron_limit;       /* r1 is taken inside this ellipse (6.0) */
+} dv_aperture_params;
+int dv_aperture_params_default(dv_aperture_params* params);
+int dv_scene_aperture(dv_ctx* ctx, const float* mean, const float* stddev, const double* shape, const int32_t* status,
+                      int64_t N, int32_t cs, int32_t nb, int32_t band, const dv_aperture_params* params, double* ap_flux,
+                      double* ap_flux_err, double* ap_area, double* flux_auto, double* flux_auto_err, double* kron,
+                      double* flux_rho, int32_t* aper_flags, int32_t* aper_status);
+int dv_infer_fields_measure_aper(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                 const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                 const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                 double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                 int32_t* iters, int32_t* status, const dv_aperture_params* aper, double* ap_flux,
+                                 double* ap_flux_err, double* ap_area, double* flux_auto, double* flux_auto_err, double* kron,
+                                 double* flux_rho, int32_t* aper_flags, int32_t* aper_status);
+
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)
  * keeps per field, in device memory, `work` (what the next pass detects on and cuts from, at first the field), `final`

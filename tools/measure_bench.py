@@ -48,6 +48,17 @@ field -
 
 With --profile-one: warm up, one fp32 call (b), exit.
 
+--apertures: what the aperture photometry costs, on the same build and box, with the default radii
+(3, 5, 8 px) and flux fractions (0.2, 0.5, 0.8) -
+
+    (a) catalogue           :  deblend_fields(d, on_device=True, measure=True, return_fields=False): the call as it was
+    (b) catalogue+apertures :  the same with apertures=(3, 5, 8): the circles, the Kron ellipse and the flux radii are taken
+                               behind every chunk's measurement
+
+    python tools/measure_bench.py --apertures [--fields 1024] [--size 259] [--repeat 5]
+
+With --profile-one: warm up, one fp32 call (b), exit.
+
 The cost is reported, not gated.
 """
 import argparse
@@ -264,6 +275,63 @@ def main_psf(a):
     print(json.dumps(result))
 
 
+def main_apertures(a):
+    rng = np.random.default_rng(0)
+    F, M = a.size, a.fields
+    base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
+    fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    radii = (3.0, 5.0, 8.0)
+    quiet = io.StringIO()
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "apertures": list(radii)}
+    dists = None
+    for dtype in a.dtypes.split(","):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections; apertures {radii} px, flux "
+                  f"fractions 0.2 / 0.5 / 0.8; max_batch {a.max_batch}")
+        seen = []
+
+        def with_apertures():
+            res = DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=True, measure=True, return_fields=False,
+                                                                apertures=radii)
+            seen[:] = [np.concatenate([r["aper_status"] for r in res]), np.concatenate([r["aper_flags"] for r in res])]
+            return sum(len(r) for r in res)
+
+        legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False),
+                "catalogue+apertures": with_apertures}
+        with redirect_stdout(quiet):
+            for fn in legs.values():           # warm-up
+                fn()
+            if a.profile_one:
+                legs["catalogue+apertures"]()
+                net._core.engine.close()
+                return
+            times = {k: [] for k in legs}
+            n = 0
+            for _ in range(a.repeat):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    n = fn()
+                    times[k].append(time.perf_counter() - t0)
+        result[dtype] = {"stamps": n, "aper_status": np.bincount(seen[0], minlength=8).tolist(),
+                         "kron_min_decides": int(np.count_nonzero(seen[1] & (1 << 10))),
+                         "truncated": int(np.count_nonzero(seen[1] & 0x3ff))}
+        for k in legs:
+            t = np.array(times[k])
+            print(_row(f"{dtype} {k}", t, n, M))
+            result[dtype][k.replace("+", "_") + "_ms"] = [round(1e3 * x, 2) for x in t]
+        tc, tp = (float(np.median(times[k])) for k in legs)
+        spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
+        print(f"{dtype} catalogue+apertures / catalogue {tp / tc:.3f}: {1e3 * (tp - tc):+.1f} ms for {n} galaxies, "
+              f"{1e6 * (tp - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times['catalogue']):.3f} and "
+              f"{spread(times['catalogue+apertures']):.3f}); aper_status 0 .. 7: {result[dtype]['aper_status']}, kron_min decides "
+              f"{result[dtype]['kron_min_decides']}, truncated {result[dtype]['truncated']}")
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fields", type=int, default=1024)
@@ -276,7 +344,10 @@ def main():
     ap.add_argument("--samples", type=int, default=0)
     ap.add_argument("--blend", action="store_true")
     ap.add_argument("--psf", action="store_true")
+    ap.add_argument("--apertures", action="store_true")
     a = ap.parse_args()
+    if a.apertures:
+        return main_apertures(a)
     if a.psf:
         return main_psf(a)
     if a.blend:
