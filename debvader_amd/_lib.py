@@ -188,6 +188,12 @@ SIGNATURES = {
     "dv_infer_fields_measure_aper": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
                                                C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
                                                C.POINTER(DvApertureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32]),
+    "dv_scene_aperture_fields": (C.c_int, [_p, _d, _i32, _i32, _i64, _d, _i32, C.c_int64, C.c_int32, C.c_int32, _d, _d, C.c_int32,
+                                           C.c_int32, C.POINTER(DvApertureParams), _d, _d, _d, _d, _d, _d]),
+    "dv_infer_fields_measure_aper_data": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64,
+                                                    C.c_uint64, C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
+                                                    C.POINTER(DvApertureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
+                                                    _d, _d, _d, _d, _d, _d]),
     "dv_field_set_open": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),

@@ -33,11 +33,20 @@
 // wave, then through LDS in wave order (measure_dev.h): a row has the same bits wherever it sits in a batch.  Every thread
 // holds the same reduced values, so the bisection branches uniformly.  fp64 VALU; nothing here has a matrix shape for MFMA.
 // No atomics; thread 0 writes the rows with ordinary stores.
+//
+// The same apertures on the observed field with the neighbours subtracted: sum w (D - T + P) splits into the
+// child sum above and the sums of w T and w D over the stamp pixels inside the field, T the completed mean field and D the
+// observed field.  aperture_field_kernel takes the two field sums and the area inside the field for the K circles and the
+// automatic ellipse (rho_auto read from the galaxy's aperture row): one workgroup per galaxy, K + 1 passes with the walk, the
+// count and the reduction of ap_all_bands, nb contiguous doubles of T and of D per pixel of positive count, 16 + 16 statically
+// indexed band slots, no plane - 352 bytes of static LDS.
 #include "common.h"
 #include "measure_dev.h"
 
 #include <algorithm>
 #include <cmath>
+#include <new>
+#include <vector>
 
 #pragma clang fp contract(off)
 
@@ -308,6 +317,129 @@ __global__ __launch_bounds__(MS_THREADS) void aperture_kernel(const float* __res
     o.status[gi] = 0;
   }
 }
+
+// ---- the same apertures on the fields ------------------------------------------------------------------------
+// One aperture in every band of the completed mean field T and the observed field D of the galaxy's field (both [F][F][nb]
+// float64, the galaxy's stamp placed at (pr, pc)): msum [nb], dsum [nb] (NaN without DATA), *area by thread 0.  The walk is
+// ap_all_bands': the same box, the same assignment of pixels to threads, the same count; a pixel whose field pixel lies outside
+// the field is skipped (the composite dropped it).  A pixel of positive count reads the nb contiguous doubles of T and of D.
+// Where T holds a stamp's widened values and no pixel is skipped, the additions are those of ap_all_bands in its order.
+template <bool DATA>
+__device__ __forceinline__ void ap_field_bands(const double* __restrict__ T, const double* __restrict__ D, int cs, int nb, int F,
+                                               int pr, int pc, const ApForm& f, double rho, double r0, double c0, int s,
+                                               const double* s_off, double* s_red, double* __restrict__ msum,
+                                               double* __restrict__ dsum, double* __restrict__ area) {
+  double ta[AP_MAX_BANDS], da[DATA ? AP_MAX_BANDS : 1], ar[1] = {0.0};
+#pragma unroll
+  for (int b = 0; b < AP_MAX_BANDS; ++b) ta[b] = 0.0;
+#pragma unroll
+  for (int b = 0; b < (DATA ? AP_MAX_BANDS : 1); ++b) da[b] = 0.0;
+  ApWalk p(cs, f, rho, r0, c0);
+  for (int i = threadIdx.x; i < p.n; i += MS_THREADS, p.next()) {
+    const int fr = pr + p.row(), fc = pc + p.col();
+    if ((unsigned)fr >= (unsigned)F || (unsigned)fc >= (unsigned)F) continue;
+    const int cnt = ap_count(f, rho, (double)p.row() - r0, (double)p.col() - c0, s, s_off);
+    if (cnt > 0) {
+      const double w = (double)cnt;
+      ar[0] += w;                           // (whole numbers: the sum is exact in any order)
+      const long e = ((long)fr * F + fc) * nb;
+      const double* tp = T + e;
+      const double* dp = DATA ? D + e : nullptr;
+#pragma unroll
+      for (int b = 0; b < AP_MAX_BANDS; ++b) {
+        if (b < nb) {
+          ta[b] += w * tp[b];
+          if (DATA) da[DATA ? b : 0] += w * dp[b];
+        }
+      }
+    }
+  }
+  ms_block_sum<1>(ar, s_red);
+  const double s2 = (double)(s * s);
+  if (threadIdx.x == 0) *area = ar[0] / s2;
+#pragma unroll
+  for (int b = 0; b < AP_MAX_BANDS; ++b) {
+    if (b < nb) {                           // (nb is uniform: every thread takes the same barriers)
+      if (DATA) {
+        double a[2] = {ta[b], da[DATA ? b : 0]};
+        ms_block_sum<2>(a, s_red);
+        if (threadIdx.x == 0) {
+          msum[b] = a[0] / s2;
+          dsum[b] = a[1] / s2;
+        }
+      } else {
+        double a[1] = {ta[b]};
+        ms_block_sum<1>(a, s_red);
+        if (threadIdx.x == 0) {
+          msum[b] = a[0] / s2;
+          dsum[b] = __longlong_as_double(0x7ff8000000000000LL);
+        }
+      }
+    }
+  }
+}
+
+// shape [n][5], status [n], kron [n][3], aper_status [n], places [n][2], sfield [n]: the rows of n galaxies whose fields are
+// complete; model / data: the stacks from field f0 on (data read only with DATA); o: the output rows of the first galaxy.
+// LDS: the reduction scratch, the sub-pixel offsets and the radii - no plane
+template <bool DATA>
+__global__ __launch_bounds__(MS_THREADS) void aperture_field_kernel(const double* __restrict__ shape, const int* __restrict__ status,
+                                                                    const double* __restrict__ kron,
+                                                                    const int* __restrict__ aper_status,
+                                                                    const int* __restrict__ places, const int* __restrict__ sfield,
+                                                                    int f0, int cs, int nb, int F, const double* __restrict__ model,
+                                                                    const double* __restrict__ data, ApertureParams par,
+                                                                    ApertureFieldRows o) {
+  __shared__ double s_red[MS_RED];
+  __shared__ double s_off[12];
+  __shared__ double s_R[AP_MAX_RADII];
+  const int K = par.K, s = par.subsample;
+  const long gi = blockIdx.x;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  double* ap_model = o.ap_model + gi * K * nb;
+  double* ap_data = o.ap_data + gi * K * nb;
+  double* ap_farea = o.ap_farea + gi * K;
+  double* auto_model = o.auto_model + gi * nb;
+  double* auto_data = o.auto_data + gi * nb;
+
+  // eligibility: the same answer in every thread (all read the same rows)
+  const double* sh = shape + gi * 5;
+  const double r0 = sh[0], c0 = sh[1], Mrr = sh[2], Mrc = sh[3], Mcc = sh[4];
+  const int st_in = status[gi], ast = aper_status[gi];
+  const double det = Mrr * Mcc - Mrc * Mrc;
+  const bool row_ok = ast != 4 && (st_in == 0 || st_in == 2) &&
+                      (ms_finite(r0) && ms_finite(c0) && ms_finite(Mrr) && ms_finite(Mrc) && ms_finite(Mcc)) &&
+                      (ms_finite(det) && det > 1e-6);
+  if (!row_ok || ast != 0) {
+    if (threadIdx.x == 0) {
+      if (!row_ok) {
+        for (int i = 0; i < K * nb; ++i) ap_model[i] = ap_data[i] = nan;
+        for (int k = 0; k < K; ++k) ap_farea[k] = nan;
+      }
+      for (int b = 0; b < nb; ++b) auto_model[b] = auto_data[b] = nan;
+      o.auto_farea[gi] = nan;
+    }
+    if (!row_ok) return;
+  }
+
+  if (threadIdx.x < 9) s_off[threadIdx.x] = ((double)threadIdx.x + 0.5) / (double)s - 0.5;
+  if (threadIdx.x < AP_MAX_RADII) s_R[threadIdx.x] = par.radii[threadIdx.x];
+  __syncthreads();
+
+  const int pr = places[2 * gi], pc = places[2 * gi + 1];
+  const long fo = (long)(sfield[gi] - f0) * F * F * nb;
+  const double* T = model + fo;
+  const double* D = DATA ? data + fo : nullptr;
+
+  const ApForm circle = ap_form(1.0, 0.0, 1.0, 1.0, 1.0);
+  for (int k = 0; k < K; ++k)
+    ap_field_bands<DATA>(T, D, cs, nb, F, pr, pc, circle, s_R[k], r0, c0, s, s_off, s_red, ap_model + k * nb, ap_data + k * nb,
+                         ap_farea + k);
+  if (ast != 0) return;                     // (no Kron radius: the circles alone)
+  const ApForm ell = ap_form(Mcc / det, (-2.0 * Mrc) / det, Mrr / det, __dsqrt_rn(Mrr), __dsqrt_rn(Mcc));
+  ap_field_bands<DATA>(T, D, cs, nb, F, pr, pc, ell, kron[gi * 3 + 1], r0, c0, s, s_off, s_red, auto_model, auto_data,
+                       o.auto_farea + gi);
+}
 }  // namespace
 
 size_t aperture_lds_bytes(int cs) { return ((size_t)cs * cs + AP_SCRATCH) * sizeof(double); }
@@ -468,6 +600,170 @@ int scene_aperture(const float* mean_h, const float* stddev_h, const double* sha
     DV_TRY(launch_aperture(mean, stddev_h ? sd.get() : nullptr, shape, status, n, cs, nb, band, p, bufs.rows(), s));
     DV_TRY(bufs.download(aperture_rows_at(out_h, base, p, nb), n, p, nb, s));
     DV_HIP(hipStreamSynchronize(s));                   // the device buffers are reused by the next chunk
+  }
+  drain.dismiss();
+  return OK;
+}
+
+// ---- the same apertures on the fields: host side ---------------------------------------------------------------
+// the outputs a call with these parameters must give; n == 0 needs none
+int aperture_field_rows_check(const char* who, const ApertureFieldRows& o, const ApertureParams& p, int64_t n) {
+  if (n <= 0) return OK;
+  const bool circles = p.K == 0 || (o.ap_model && o.ap_data && o.ap_farea);
+  if (!circles || !o.auto_model || !o.auto_data || !o.auto_farea) {
+    set_error("%s: ap_model_sum, ap_data_sum, ap_field_area (with radii), auto_model_sum, auto_data_sum and auto_field_area must "
+              "all be given", who);
+    return E_INVALID;
+  }
+  return OK;
+}
+
+int ApertureFieldBufs::alloc(int64_t n, const ApertureParams& p, int nb) {
+  const size_t N = (size_t)n;
+  DV_TRY(ap_model.alloc(N * p.K * nb));
+  DV_TRY(ap_data.alloc(N * p.K * nb));
+  DV_TRY(ap_farea.alloc(N * p.K));
+  DV_TRY(auto_model.alloc(N * nb));
+  DV_TRY(auto_data.alloc(N * nb));
+  return auto_farea.alloc(N);
+}
+
+ApertureFieldRows ApertureFieldBufs::rows() const {
+  return ApertureFieldRows{ap_model.get(), ap_data.get(), ap_farea.get(), auto_model.get(), auto_data.get(), auto_farea.get()};
+}
+
+// the rows of `o` that start at galaxy r
+ApertureFieldRows aperture_field_rows_at(const ApertureFieldRows& o, int64_t r, const ApertureParams& p, int nb) {
+  const size_t q = (size_t)r;
+  auto at = [](double* ptr, size_t off) { return ptr ? ptr + off : ptr; };
+  return ApertureFieldRows{at(o.ap_model, q * p.K * nb), at(o.ap_data, q * p.K * nb), at(o.ap_farea, q * p.K),
+                           at(o.auto_model, q * nb), at(o.auto_data, q * nb), at(o.auto_farea, q)};
+}
+
+// the first n rows of the device buffers to the host rows `h`
+int ApertureFieldBufs::download(const ApertureFieldRows& h, int64_t n, const ApertureParams& p, int nb, hipStream_t s) const {
+  const size_t N = (size_t)n, D = sizeof(double);
+  if (N == 0) return OK;
+  if (p.K > 0) {
+    DV_HIP(hipMemcpyAsync(h.ap_model, ap_model.get(), N * p.K * nb * D, hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(h.ap_data, ap_data.get(), N * p.K * nb * D, hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(h.ap_farea, ap_farea.get(), N * p.K * D, hipMemcpyDeviceToHost, s));
+  }
+  DV_HIP(hipMemcpyAsync(h.auto_model, auto_model.get(), N * nb * D, hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(h.auto_data, auto_data.get(), N * nb * D, hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(h.auto_farea, auto_farea.get(), N * D, hipMemcpyDeviceToHost, s));
+  return OK;
+}
+
+// n galaxies whose fields are complete, with their catalogue and aperture rows, placements and fields in device memory; every
+// per-galaxy pointer is the row of the first galaxy
+int launch_aperture_field(const double* shape_dev, const int* status_dev, const double* kron_dev, const int* aper_status_dev,
+                          const int* places_dev, const int* sfield_dev, int f0, int n, int cs, int nb, int F,
+                          const double* model_dev, const double* data_dev, const ApertureParams& p,
+                          const ApertureFieldRows& rows, hipStream_t s) {
+  if (n <= 0) return OK;
+  if (data_dev)
+    hipLaunchKernelGGL(aperture_field_kernel<true>, dim3((unsigned)n), dim3(MS_THREADS), 0, s, shape_dev, status_dev, kron_dev,
+                       aper_status_dev, places_dev, sfield_dev, f0, cs, nb, F, model_dev, data_dev, p, rows);
+  else
+    hipLaunchKernelGGL(aperture_field_kernel<false>, dim3((unsigned)n), dim3(MS_THREADS), 0, s, shape_dev, status_dev, kron_dev,
+                       aper_status_dev, places_dev, sfield_dev, f0, cs, nb, F, model_dev, data_dev, p, rows);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
+
+// host arrays in, host rows out: galaxies base .. base + n of at most `chunk` galaxies and at most `gmax` fields at a time, the
+// model (and data) fields they lie in uploaded beside their rows
+int scene_aperture_fields(const double* shape_h, const int32_t* status_h, const int32_t* places_h, const int64_t* field_ptr,
+                          const double* kron_h, const int32_t* aper_status_h, int64_t N, int cs, int nb, const double* model_h,
+                          const double* data_h, int M, int F, const ApertureParams& p, const ApertureFieldRows& out_h,
+                          int64_t chunk, int64_t gmax, int device, hipStream_t s) {
+  const char* who = "dv_scene_aperture_fields";
+  DV_TRY(aperture_check(who, cs, nb, 0, p));
+  if (N < 0 || M < 0 || !field_ptr ||
+      (N > 0 && (!shape_h || !status_h || !places_h || !kron_h || !aper_status_h || !model_h))) {
+    set_error("%s: shape, status, places, field_ptr, kron, aper_status and model_fields must all be given", who);
+    return E_INVALID;
+  }
+  DV_TRY(aperture_field_rows_check(who, out_h, p, N));
+  if (N >= ((int64_t)1 << 31)) {
+    set_error("%s: %ld galaxies, at most 2^31 - 1 per call", who, (long)N);
+    return E_INVALID;
+  }
+  if (F < 1 || F > 32768) {
+    set_error("%s: fields of %d pixels, 1 .. 32768 are taken", who, F);
+    return E_INVALID;
+  }
+  if (field_ptr[0] != 0 || field_ptr[M] != N) {
+    set_error("%s: field_ptr must run from 0 to the number of galaxies (%ld), got %ld .. %ld", who, (long)N,
+              (long)field_ptr[0], (long)field_ptr[M]);
+    return E_INVALID;
+  }
+  for (int f = 0; f < M; ++f)                        // the whole table before anything is indexed by it
+    if (field_ptr[f + 1] < field_ptr[f]) {
+      set_error("%s: field_ptr decreases at field %d (%ld after %ld)", who, f, (long)field_ptr[f + 1], (long)field_ptr[f]);
+      return E_INVALID;
+    }
+  for (int64_t i = 0; i < N; ++i) {
+    const int pr = places_h[2 * i], pc = places_h[2 * i + 1];
+    if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
+      set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
+      return E_INVALID;
+    }
+  }
+  if (N == 0) return OK;
+  std::vector<int32_t> sfield;                       // every galaxy's field
+  try {
+    sfield.resize((size_t)N);
+  } catch (const std::bad_alloc&) {
+    set_error("%s: no host memory for the field table of %ld galaxies", who, (long)N);
+    return E_NOMEM;
+  }
+  for (int f = 0; f < M; ++f)
+    for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) sfield[(size_t)i] = f;
+  const size_t felems = (size_t)F * F * nb;
+  DV_HIP(hipSetDevice(device));
+  if (chunk <= 0 || gmax <= 0) {
+    size_t free_b = 0, total_b = 0;
+    DV_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t per_stamp = 8 * sizeof(double) + 5 * sizeof(int) + ApertureFieldBufs::bytes_per_stamp(p, nb);
+    chunk = (int64_t)(free_b / 4 / per_stamp);
+    gmax = (int64_t)(free_b / 4 / (felems * sizeof(double) * (data_h ? 2 : 1)));
+  }
+  chunk = std::max<int64_t>(1, std::min<int64_t>({chunk, N, (int64_t)1 << 20}));
+  gmax = std::max<int64_t>(1, std::min<int64_t>(gmax, M));
+  DevBuf<double> shape, kron, model, data;
+  DevBuf<int> status, astatus, places, sf;
+  ApertureFieldBufs bufs;
+  DV_TRY(shape.alloc((size_t)chunk * 5));
+  DV_TRY(kron.alloc((size_t)chunk * 3));
+  DV_TRY(status.alloc((size_t)chunk));
+  DV_TRY(astatus.alloc((size_t)chunk));
+  DV_TRY(places.alloc((size_t)chunk * 2));
+  DV_TRY(sf.alloc((size_t)chunk));
+  DV_TRY(bufs.alloc(chunk, p, nb));
+  DV_TRY(model.alloc((size_t)gmax * felems));
+  if (data_h) DV_TRY(data.alloc((size_t)gmax * felems));
+  StreamDrain drain(s);
+  for (int64_t base = 0; base < N;) {
+    const int fa = sfield[(size_t)base];
+    int n = 0;                                         // galaxies of at most gmax fields from fa on (at least one)
+    while (n < chunk && base + n < N && (int64_t)sfield[(size_t)(base + n)] - fa < gmax) ++n;
+    const size_t nf = (size_t)(sfield[(size_t)(base + n - 1)] - fa + 1), b = (size_t)base;
+    DV_HIP(hipMemcpyAsync(model, model_h + (size_t)fa * felems, nf * felems * sizeof(double), hipMemcpyHostToDevice, s));
+    if (data_h)
+      DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, nf * felems * sizeof(double), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(shape, shape_h + b * 5, (size_t)n * 5 * sizeof(double), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(kron, kron_h + b * 3, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(status, status_h + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(astatus, aper_status_h + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(places, places_h + b * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(sf, sfield.data() + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_TRY(launch_aperture_field(shape, status, kron, astatus, places, sf, fa, n, cs, nb, F, model,
+                                 data_h ? data.get() : nullptr, p, bufs.rows(), s));
+    DV_TRY(bufs.download(aperture_field_rows_at(out_h, base, p, nb), n, p, nb, s));
+    DV_HIP(hipStreamSynchronize(s));                   // the device buffers are reused by the next chunk
+    base += n;
   }
   drain.dismiss();
   return OK;

@@ -401,6 +401,34 @@ int launch_aperture(const float* mean_dev, const float* stddev_dev, const double
                     int nb, int band, const ApertureParams& p, const ApertureRows& rows, hipStream_t s);
 int scene_aperture(const float* mean_h, const float* stddev_h, const double* shape_h, const int32_t* status_h, int64_t N, int cs,
                    int nb, int band, const ApertureParams& p, const ApertureRows& out_h, int64_t chunk, hipStream_t s);
+// the same apertures on the fields (aperture.hip): per galaxy the sums of n T, n D and n over the stamp pixels of
+// positive count that lie inside the field, T the completed mean field and D the observed field of its field, for the K
+// circles and the automatic ellipse of radius kron[1].  ApertureFieldRows: the output rows, device or host - ap_model / ap_data
+// [.][K][nb], ap_farea [.][K], auto_model / auto_data [.][nb], auto_farea [.].  launch_aperture_field: n galaxies whose fields
+// are complete, every per-galaxy pointer at the first galaxy's row: sfield_dev [n] their fields, model_dev / data_dev stacks
+// [.][F][F][nb] that start at field f0 (data_dev null: the data sums are NaN).  scene_aperture_fields: host arrays, at most
+// `chunk` galaxies and the `gmax` fields they may span on the device at a time (either 0: a quarter of free device memory for
+// a chunk's rows, a quarter for the fields they lie in, taken after the refusals).
+struct ApertureFieldRows { double *ap_model, *ap_data, *ap_farea, *auto_model, *auto_data, *auto_farea; };
+int aperture_field_rows_check(const char* who, const ApertureFieldRows& o, const ApertureParams& p, int64_t n);
+ApertureFieldRows aperture_field_rows_at(const ApertureFieldRows& o, int64_t r, const ApertureParams& p, int nb);
+struct ApertureFieldBufs {
+  DevBuf<double> ap_model, ap_data, ap_farea, auto_model, auto_data, auto_farea;
+  static size_t bytes_per_stamp(const ApertureParams& p, int nb) {
+    return ((size_t)(2 * p.K + 2) * nb + p.K + 1) * sizeof(double);
+  }
+  int alloc(int64_t n, const ApertureParams& p, int nb);
+  ApertureFieldRows rows() const;
+  int download(const ApertureFieldRows& h, int64_t n, const ApertureParams& p, int nb, hipStream_t s) const;
+};
+int launch_aperture_field(const double* shape_dev, const int* status_dev, const double* kron_dev, const int* aper_status_dev,
+                          const int* places_dev, const int* sfield_dev, int f0, int n, int cs, int nb, int F,
+                          const double* model_dev, const double* data_dev, const ApertureParams& p,
+                          const ApertureFieldRows& rows, hipStream_t s);
+int scene_aperture_fields(const double* shape_h, const int32_t* status_h, const int32_t* places_h, const int64_t* field_ptr,
+                          const double* kron_h, const int32_t* aper_status_h, int64_t N, int cs, int nb, const double* model_h,
+                          const double* data_h, int M, int F, const ApertureParams& p, const ApertureFieldRows& out_h,
+                          int64_t chunk, int64_t gmax, int device, hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

@@ -3103,13 +3103,17 @@ struct PipeJob {
   } mcm;
   // blendedness sums (dv_infer_fields_measure_blend): behind every chunk's measurement, the child sums W, A and
   // npix of its stamps (they need the chunk's catalogue rows and sinks.places_d); blend decides.  The parent sums are the
-  // caller's, once a field's composite is complete.  Without sinks.mean_f (the catalogue-only form) the chunk's mean stamps
-  // are composited into mean_f, a device-side mean field per resident field that nothing downloads
+  // caller's, once a field's composite is complete
   struct Blend {
     double* blend = nullptr;           // device [.][4]
     int* npix = nullptr;               // device [.]
-    double* mean_f = nullptr;          // device, fields f0 .. like fields_d (the catalogue-only form)
   } bl;
+  // the device-side mean field of a catalogue-only call whose stages read the completed composite (the blendedness sums, the
+  // apertures on the fields: DESIGN.md 7l, 7p): without sinks.mean_f the chunk's mean stamps are composited into mean_f, a mean
+  // field per resident field that nothing downloads; mean_f decides (needs sinks.places_d)
+  struct MeanField {
+    double* mean_f = nullptr;          // device, fields f0 .. like fields_d
+  } mf;
   // PSF-corrected shapes (dv_infer_fields_measure_psf): behind every chunk's measurement, the re-Gaussianized
   // moments of its mean stamps from the chunk's catalogue rows and the call's PSF rows (measured before the first chunk); out
   // decides
@@ -3338,10 +3342,10 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
       DV_TRY(launch_measure(p->dloc[b], p->dscale[b], nb, cs, j.nb, j.ms.band, j.ms.sigma0, j.ms.tol, j.ms.max_iter,
                             j.ms.flux + (size_t)r * j.nb, j.ms.ferr + (size_t)r * j.nb, j.ms.shape + (size_t)r * 5,
                             j.ms.iters + r, j.ms.status + r, p->s_out));
+      if (j.mf.mean_f && !comp)
+        DV_TRY(launch_blend_composite_mean(j.mf.mean_f, j.F, j.nb, p->dloc[b], j.sinks.places_d + 2 * r, nb, cs, j.fptr_d, j.f0,
+                                           j.sfield[r], j.sfield[r + nb - 1] - j.sfield[r] + 1, (long)r, p->s_out));
       if (j.bl.blend) {
-        if (!comp)
-          DV_TRY(launch_blend_composite_mean(j.bl.mean_f, j.F, j.nb, p->dloc[b], j.sinks.places_d + 2 * r, nb, cs, j.fptr_d, j.f0,
-                                             j.sfield[r], j.sfield[r + nb - 1] - j.sfield[r] + 1, (long)r, p->s_out));
         DV_TRY(launch_blend_child(p->dloc[b], j.ms.shape + (size_t)r * 5, j.ms.status + r, j.sinks.places_d + 2 * r, nb, cs,
                                   j.nb, j.ms.band, j.F, j.bl.blend + (size_t)r * 4, j.bl.npix + r, p->s_out));
       }
@@ -3900,6 +3904,22 @@ int dv_scene_aperture(dv_ctx* c, const float* mean, const float* stddev, const d
                            ApertureBufs::bytes_per_stamp(par, nb);
   const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 2 / per_stamp);
   return scene_aperture(mean, stddev, shape, status, N, cs, nb, band, par, out, chunk, c->stream);
+}
+
+int dv_scene_aperture_fields(dv_ctx* c, const double* shape, const int32_t* status, const int32_t* places,
+                             const int64_t* field_ptr, const double* kron, const int32_t* aper_status, int64_t N, int32_t cs,
+                             int32_t nb, const double* model_fields, const double* data_fields, int32_t M, int32_t F,
+                             const dv_aperture_params* params, double* ap_model_sum, double* ap_data_sum,
+                             double* ap_field_area, double* auto_model_sum, double* auto_data_sum, double* auto_field_area) {
+  if (!c) return DV_E_INVALID;
+  if (!params) {
+    set_error("dv_scene_aperture_fields: params must be given");
+    return DV_E_INVALID;
+  }
+  const ApertureFieldRows out{ap_model_sum, ap_data_sum, ap_field_area, auto_model_sum, auto_data_sum, auto_field_area};
+  // (every refusal is scene_aperture_fields'; chunk and gmax 0: sized there, after them, against free device memory)
+  return scene_aperture_fields(shape, status, places, field_ptr, kron, aper_status, N, cs, nb, model_fields, data_fields, M, F,
+                               aperture_params(*params), out, 0, 0, c->device, c->stream);
 }
 
 int dv_scene_measure_mc(dv_ctx* c, const float* samples, int32_t S, int64_t N, int32_t cs, int32_t nb,
@@ -5059,19 +5079,13 @@ struct CatalogueMcStage {           // means and standard deviations over the Mo
 
 struct BlendOut { double* blend = nullptr; int32_t* npix = nullptr; };   // dv_infer_fields_measure_blend, host [N][4], [N]
 
-struct BlendStage {                 // the blendedness sums of every stamp (7l)
-  DevBuf<double> blend, mean;       // mean: the device-side mean field of the catalogue-only form (else the composite stage's)
-  DevBuf<int> npix;
-  static size_t bytes_per_stamp() { return 4 * sizeof(double) + sizeof(int); }
+struct MeanFieldStage {             // the device-side mean field of a catalogue-only call (7l, 7p): what the stages that read the
+  DevBuf<double> mean;              // completed composite get where no composite stage runs; empty with result fields
   static size_t bytes_per_field(bool own_mean, size_t fb) { return own_mean ? fb : 0; }
-  int alloc(int64_t N, bool own_mean, size_t elems) {
-    DV_TRY(blend.alloc((size_t)N * 4));
-    DV_TRY(npix.alloc((size_t)N));
-    return own_mean ? mean.alloc(elems) : DV_OK;
-  }
-  void bind(PipeJob::Blend& q) const { q.blend = blend; q.npix = npix; q.mean_f = mean; }
-  // a group begins (the catalogue-only form): zeros, but for a first field that was composited in part with the previous
-  // group, whose sums lie in slot `from` and go on in slot 0
+  int alloc(bool own_mean, size_t elems) { return own_mean ? mean.alloc(elems) : DV_OK; }
+  void bind(PipeJob::MeanField& q) const { q.mean_f = mean; }
+  // a group begins: zeros, but for a first field that was composited in part with the previous group, whose sums lie in slot
+  // `from` and go on in slot 0
   int begin(size_t ng, size_t felems, long from, hipStream_t s) {
     if (!mean) return DV_OK;
     const size_t fb = felems * sizeof(double);
@@ -5080,6 +5094,17 @@ struct BlendStage {                 // the blendedness sums of every stamp (7l)
     if (ng > keep) DV_HIP(hipMemsetAsync(mean.get() + keep * felems, 0, (ng - keep) * fb, s));
     return DV_OK;
   }
+};
+
+struct BlendStage {                 // the blendedness sums of every stamp (7l)
+  DevBuf<double> blend;
+  DevBuf<int> npix;
+  static size_t bytes_per_stamp() { return 4 * sizeof(double) + sizeof(int); }
+  int alloc(int64_t N) {
+    DV_TRY(blend.alloc((size_t)N * 4));
+    return npix.alloc((size_t)N);
+  }
+  void bind(PipeJob::Blend& q) const { q.blend = blend; q.npix = npix; }
   int download(const BlendOut& o, int64_t N, hipStream_t s) {
     DV_HIP(hipMemcpyAsync(o.blend, blend, (size_t)N * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
     DV_HIP(hipMemcpyAsync(o.npix, npix, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -5143,20 +5168,33 @@ struct ApertureStage {              // the aperture photometry of every stamp (7
   }
 };
 
+struct ApertureFieldOut { ApertureFieldRows rows{}; };   // dv_infer_fields_measure_aper_data: the six field rows out (host)
+
+struct ApertureFieldStage {         // the apertures of every stamp on the mean field and the source field (7p)
+  ApertureFieldBufs bufs;
+  static size_t bytes_per_stamp(const ApertureOut& o, int nb) { return ApertureFieldBufs::bytes_per_stamp(o.par, nb); }
+  int alloc(const ApertureOut& o, int64_t N, int nb) { return bufs.alloc(N, o.par, nb); }
+  int download(const ApertureFieldOut& h, const ApertureOut& o, int64_t N, int nb, hipStream_t s) {
+    DV_TRY(bufs.download(h.rows, N, o.par, nb, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return DV_OK;
+  }
+};
+
 // j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
 // the device side and the rows are filled in here
 static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
                              const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr,
                              const MeasureMcOut* mco = nullptr, const BlendOut* bo = nullptr,
                              const int32_t* blend_places = nullptr, const RegaussOut* ro = nullptr,
-                             const ApertureOut* ao = nullptr) {
+                             const ApertureOut* ao = nullptr, const ApertureFieldOut* afo = nullptr) {
   // check
   const double* fields = j.fields;
   const int F = j.F, nb = j.nb;
   if (M > 0 && !fields) return DV_E_INVALID;
   std::vector<int32_t> sfield;
   std::vector<int> fptr32;
-  const int32_t* places = fo ? fo->places : blend_places;   // (blend_places: the catalogue-only form of the blendedness call)
+  const int32_t* places = fo ? fo->places : blend_places;   // (blend_places: the catalogue-only form of a call that composites)
   DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, j.starts, places, sfield, fptr32));
   const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
   if (fo) fields_write_empty(*fo, fields, M, field_ptr, felems);
@@ -5173,7 +5211,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   double* mse_h = fo ? fo->mse : mo ? mo->mse : nullptr;
   DevBuf<double> fdev;                                // the resident group of source fields
   StampTables tab;
-  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs; ApertureStage aps;   // (a stage that does not run stays empty)
+  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs; ApertureStage aps; MeanFieldStage mfs; ApertureFieldStage afs;   // (a stage that does not run stays empty)
   ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
   if (fitting) DV_TRY(fit.make_plan(*fo, c, sfield.data()));
   size_t per_field = fb, reserve = StampTables::bytes((size_t)N, (size_t)M);
@@ -5189,18 +5227,18 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   const bool keep_samples = mco && mco->st.sample_flux;
   if (mco)
     reserve += (size_t)N * CatalogueMcStage::bytes_per_stamp(nb, mco->nsamples, keep_samples) + CatalogueMcStage::bytes_fixed(m->Bc, nb);
-  if (bo) {
-    per_field += BlendStage::bytes_per_field(!fo, fb);
-    reserve += (size_t)N * BlendStage::bytes_per_stamp();
-  }
+  const bool own_mean = (bo || afo) && !fo;           // a stage reads the completed composite and no composite stage runs
+  per_field += MeanFieldStage::bytes_per_field(own_mean, fb);
+  if (bo) reserve += (size_t)N * BlendStage::bytes_per_stamp();
   if (ro) reserve += (size_t)N * RegaussStage::bytes_per_stamp() + RegaussStage::bytes_fixed(*ro);
   if (ao) reserve += (size_t)N * ApertureStage::bytes_per_stamp(*ao, nb);
+  if (afo) reserve += (size_t)N * ApertureFieldStage::bytes_per_stamp(*ao, nb);
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
   if (G < 1) {
     set_error("%s: one %d-pixel field needs %zu bytes of device memory (field%s), %zu are available for fields", who, F,
-              per_field, fo ? " and its result fields" : bo ? " and its device-side mean field" : "", budget);
+              per_field, fo ? " and its result fields" : own_mean ? " and its device-side mean field" : "", budget);
     return DV_E_NOMEM;
   }
   std::vector<FieldGroup> groups;
@@ -5224,8 +5262,10 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     DV_TRY(catmc.alloc(N, nb, mco->nsamples, keep_samples, m->Bc));
     catmc.bind(j.mcm, mo->par);
   }
+  DV_TRY(mfs.alloc(own_mean, gelems));
+  mfs.bind(j.mf);
   if (bo) {
-    DV_TRY(bls.alloc(N, !fo, gelems));
+    DV_TRY(bls.alloc(N));
     bls.bind(j.bl);
   }
   if (ro) {
@@ -5236,6 +5276,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     DV_TRY(aps.alloc(*ao, N, nb));
     aps.bind(j.ap, *ao);
   }
+  if (afo) DV_TRY(afs.alloc(*ao, N, nb));
   if (fitting) {
     DV_TRY(fit.alloc(*fo, c, gmax, groups));
     fit.bind(j.fit);
@@ -5259,22 +5300,29 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     if (g.f0 == prev_last)
       for (ResultStack* r : stacks) DV_TRY(r->carry(goff, fb, s));
     if (fitting) DV_TRY(fit.begin(fdev, ng, c));
-    if (bo) DV_TRY(bls.begin(ng, felems, g.f0 == prev_last ? (long)(prev_last - prev_first) : -1, s));
+    DV_TRY(mfs.begin(ng, felems, g.f0 == prev_last ? (long)(prev_last - prev_first) : -1, s));
     DV_HIP(hipStreamSynchronize(s));               // the gather runs on the pipeline's copy stream
     j.f0 = g.f0;
     j.row0 = g.k0 * chunk;
     j.N = std::min<int64_t>(N, g.k1 * chunk) - j.row0;
     DV_TRY(infer_pipelined(m, j));
-    if (bo) {
+    if (bo || afo) {
       // the completed-field seam: every field of the group has all its stamps composited now, but for a last field that
-      // the next group goes on with (it is complete there); the parent sums of the complete fields' galaxies - one
-      // contiguous range of rows - read the mean field, the source field and the catalogue rows where they lie
+      // the next group goes on with (it is complete there); the parent sums and the field apertures of the complete fields'
+      // galaxies - one contiguous range of rows - read the mean field, the source field and the rows where they lie
       const int fa = g.f0, fz = gi + 1 < groups.size() && groups[gi + 1].f0 == g.f1 ? g.f1 - 1 : g.f1;
       if (fz >= fa) {
         const int r0 = fptr32[fa], r1 = fptr32[fz + 1];
-        DV_TRY(launch_blend_parent(cat.shape.get() + (size_t)r0 * 5, cat.status.get() + r0, tab.places.get() + 2 * (size_t)r0,
-                                   tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, mo->par.band, F,
-                                   fo ? comp.mean.dev.get() : bls.mean.get(), fdev, bls.blend.get() + (size_t)r0 * 4, s));
+        const double* mean_f = fo ? comp.mean.dev.get() : mfs.mean.get();
+        if (bo)
+          DV_TRY(launch_blend_parent(cat.shape.get() + (size_t)r0 * 5, cat.status.get() + r0, tab.places.get() + 2 * (size_t)r0,
+                                     tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, mo->par.band, F, mean_f, fdev,
+                                     bls.blend.get() + (size_t)r0 * 4, s));
+        if (afo)
+          DV_TRY(launch_aperture_field(cat.shape.get() + (size_t)r0 * 5, cat.status.get() + r0,
+                                       aps.bufs.kron.get() + (size_t)r0 * 3, aps.bufs.status.get() + r0,
+                                       tab.places.get() + 2 * (size_t)r0, tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, F,
+                                       mean_f, fdev, ao->par, aperture_field_rows_at(afs.bufs.rows(), r0, ao->par, nb), s));
       }
     }
     if (fo) {
@@ -5294,6 +5342,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (bo) DV_TRY(bls.download(*bo, N, s));
   if (ro) DV_TRY(rgs.download(*ro, N, s));
   if (ao) DV_TRY(aps.download(*ao, N, nb, s));
+  if (afo) DV_TRY(afs.download(*afo, *ao, N, nb, s));
   if (fo) DV_TRY(mc.download(N, s));
   if (fitting) DV_TRY(fit.download(*fo, N, s));
   drain.dismiss();
@@ -5409,12 +5458,19 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
                                       double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
                                       double* flux_err, double* shape, int32_t* iters, int32_t* status,
                                       const BlendOut* bo = nullptr, const RegaussOut* ro = nullptr,
-                                      const ApertureOut* ao = nullptr) {
+                                      const ApertureOut* ao = nullptr, const ApertureFieldOut* afo = nullptr) {
   if (!m || !params) return DV_E_INVALID;
   DV_TRY(measure_check(who, m->A.H, nb, params->band, params->sigma0, params->tol, params->max_iter));
   if (ao) {
     DV_TRY(aperture_check(who, m->A.H, nb, params->band, ao->par));
     DV_TRY(aperture_rows_check(who, ao->rows, ao->par, true, N));
+  }
+  if (afo) {                           // (the apertures on the fields go with the aperture rows: ao is given)
+    DV_TRY(aperture_field_rows_check(who, afo->rows, ao->par, N));
+    if (N > 0 && !places) {
+      set_error("%s: places must be given (the catalogue-only form needs the placements too)", who);
+      return DV_E_INVALID;
+    }
   }
   if (ro) {
     DV_TRY(regauss_check(who, m->A.H, nb, params->band, ro->K, ro->ps, ro->psf_sigma0, params->tol, params->max_iter));
@@ -5449,7 +5505,7 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
   PipeJob j = fields_job(fields, F, nb, starts, seed);
   if (!with_fields) {
     mo.mse = mse_center;
-    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo ? places : nullptr, ro, ao);
+    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo || afo ? places : nullptr, ro, ao, afo);
   }
   FieldsOut fo;
   fo.mean = mean_fields;
@@ -5457,7 +5513,7 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
   fo.residual = residual_fields;
   fo.mse = mse_center;
   fo.places = places;
-  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo, nullptr, ro, ao);
+  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo, nullptr, ro, ao, afo);
 }
 
 int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
@@ -5531,6 +5587,33 @@ int dv_infer_fields_measure_aper(dv_model* m, const double* fields, int32_t M, i
   return infer_fields_measure_entry("dv_infer_fields_measure_aper", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
                                     params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
                                     iters, status, nullptr, nullptr, &ao);
+}
+
+// ---- the same apertures on the observed field with the neighbours subtracted: dv_infer_fields_measure_aper plus
+// the sums of w T and w D inside the field, taken at the completed-field seam
+int dv_infer_fields_measure_aper_data(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb,
+                                      const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                                      uint64_t seed, const dv_measure_params* params, double* mean_fields,
+                                      double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
+                                      double* flux_err, double* shape, int32_t* iters, int32_t* status,
+                                      const dv_aperture_params* aper, double* ap_flux, double* ap_flux_err, double* ap_area,
+                                      double* flux_auto, double* flux_auto_err, double* kron, double* flux_rho,
+                                      int32_t* aper_flags, int32_t* aper_status, double* ap_model_sum, double* ap_data_sum,
+                                      double* ap_field_area, double* auto_model_sum, double* auto_data_sum,
+                                      double* auto_field_area) {
+  if (!m) return DV_E_INVALID;
+  if (!aper) {
+    set_error("dv_infer_fields_measure_aper_data: the aperture params must be given");
+    return DV_E_INVALID;
+  }
+  ApertureOut ao;
+  ao.par = aperture_params(*aper);
+  ao.rows = ApertureRows{ap_flux, ap_flux_err, ap_area, flux_auto, flux_auto_err, kron, flux_rho, aper_flags, aper_status};
+  ApertureFieldOut afo;
+  afo.rows = ApertureFieldRows{ap_model_sum, ap_data_sum, ap_field_area, auto_model_sum, auto_data_sum, auto_field_area};
+  return infer_fields_measure_entry("dv_infer_fields_measure_aper_data", m, fields, M, F, nb, starts, places, field_ptr, N,
+                                    seed, params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err,
+                                    shape, iters, status, nullptr, nullptr, &ao, &afo);
 }
 
 // ---- the Monte-Carlo catalogue beside it: dv_infer_fields_measure plus means and standard deviations of

@@ -462,6 +462,14 @@ class DeblendFieldBatch:
 
         return aperture_dtype(nb_of_bands, n_radii, n_fractions)
 
+    @staticmethod
+    def aperture_data_columns(nb_of_bands, n_radii):
+        """What deblend_fields(measure=True, apertures=..., aperture_data=True) appends behind aperture_columns: the recarray
+        of measure_apertures_on_fields."""
+        from debvader_amd.measure.measurement import aperture_data_dtype
+
+        return aperture_data_dtype(nb_of_bands, n_radii)
+
     def _psf_index(self, psf, psf_index, field_ptr):
         """(psf (K, ps, ps), index (N,)) of a deblend_fields(psf=...) call: one image for all galaxies, one per field (the
         index follows from field_ptr), or K images with the caller's index per galaxy - a flat (N,) array or a list of M
@@ -537,7 +545,8 @@ class DeblendFieldBatch:
     def deblend_fields(self, galaxy_distances_to_center=None, mse_criterion=100.0, on_device=False,
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
                        measure=False, return_fields=True, measure_samples=0, blendedness=False,
-                       psf=None, psf_index=None, apertures=None, flux_fractions=None, optimise_positions=False):
+                       psf=None, psf_index=None, apertures=None, flux_fractions=None, aperture_data=False,
+                       sky_sigma=None, optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -605,7 +614,18 @@ class DeblendFieldBatch:
         flux_radius, kron_a, kron_b, concentration; debvader_amd.measure.measurement.measure_apertures describes them).
         apertures=() gives the Kron columns alone.  The other columns and the fields are those of the same call without it.
         It is not available with psf, blendedness, measure_samples, optimise_positions=True or
-        epistemic_uncertainty_estimation=True."""
+        epistemic_uncertainty_estimation=True.
+
+        aperture_data=True (with apertures, with or without return_fields): the same apertures on the observed field with
+        the neighbours' models subtracted (dv_infer_fields_measure_aper_data).  Once a field's
+        composite is complete, the sums of the composited mean field and of the observed field over every aperture - the
+        stamp pixels inside the field, the same sub-pixel weights - are taken on the GPU; the recarrays gain
+        aperture_data_columns (ap_model_sum, ap_data_sum, ap_field_area, auto_model_sum, auto_data_sum, auto_field_area and
+        the derived ap_flux_data = ap_flux + ap_data_sum - ap_model_sum, flux_auto_data, ap_blendedness, auto_blendedness,
+        aper_data_flags, ap_flux_data_err, flux_auto_data_err; debvader_amd.measure.measurement.measure_apertures_on_fields
+        describes them).  sky_sigma, (bands,) or (M, bands), is the standard deviation of the sky per pixel the two error
+        columns are derived from; without it they are NaN.  The other columns and the fields are those of the same call
+        without it."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
@@ -669,6 +689,17 @@ class DeblendFieldBatch:
             raise ValueError("apertures cannot be combined with epistemic_uncertainty_estimation=True: the aperture "
                              "photometry is a stage of the plain measuring composite call only "
                              "(dv_infer_fields_measure_aper), not of the Monte-Carlo call")
+        aperture_data = bool(aperture_data)
+        band = 2                        # the band of the measurement (r): the engine call and the blendedness in the apertures
+        if aperture_data and not with_aper:
+            raise ValueError("aperture_data=True needs apertures: it takes the apertures of the aperture photometry on the "
+                             "observed field and the composited mean field (apertures=() for the Kron ellipse alone)")
+        if sky_sigma is not None and not aperture_data:
+            raise ValueError("sky_sigma is the sky noise of the data-flux errors of aperture_data=True: give aperture_data too")
+        if sky_sigma is not None:
+            from debvader_amd.measure.measurement import check_sky_sigma
+
+            sky_sigma = check_sky_sigma(sky_sigma, self.nb_of_fields, self.nb_of_bands)                     # (ValueError)
         if with_aper:
             from debvader_amd.engine import aperture_params
 
@@ -748,6 +779,11 @@ class DeblendFieldBatch:
                     out = eng.infer_fields_measure_psf(self.field_images, starts, field_ptr, psf, psf_index,
                                                        places=places if return_fields else None, seed=seed,
                                                        return_fields=bool(return_fields))
+                elif aperture_data:
+                    out = eng.infer_fields_measure_aper_data(self.field_images, starts, field_ptr, places, seed=seed, band=band,
+                                                             radii=list(aper_par.radii)[:aper_par.n_radii],
+                                                             fractions=list(aper_par.fractions)[:aper_par.n_fractions],
+                                                             return_fields=bool(return_fields))
                 elif with_aper:
                     out = eng.infer_fields_measure_aper(self.field_images, starts, field_ptr,
                                                         places=places if return_fields else None, seed=seed,
@@ -812,6 +848,14 @@ class DeblendFieldBatch:
                 cat_ap = aperture_records(out["ap_flux"], out["ap_flux_err"], out["ap_area"], out["flux_auto"],
                                           out["flux_auto_err"], out["kron"], out["flux_rho"], out["aper_flags"],
                                           out["aper_status"], out["shape"])
+            if aperture_data:
+                from debvader_amd.measure.measurement import aperture_data_records
+
+                columns = columns + self.aperture_data_columns(nb, aper_par.n_radii)
+                cat_ad = aperture_data_records(out["ap_model_sum"], out["ap_data_sum"], out["ap_field_area"],
+                                               out["auto_model_sum"], out["auto_data_sum"], out["auto_field_area"],
+                                               out["ap_flux"], out["ap_area"], out["flux_auto"], out["kron"][:, 2], band=band,
+                                               sky_sigma=sky_sigma, field_ptr=field_ptr)
             cat = catalogue_records(out["flux"], out["flux_err"], out["shape"], out["iters"], out["status"]) if on_device \
                 else measure_stamps(out["loc"], out["scale"], ctx=self._ctx)
             # a stamp's pixel (row, col) is the field's pixel start + (row, col); distances count from pixel int(F / 2)
@@ -843,6 +887,9 @@ class DeblendFieldBatch:
                 if with_aper:
                     for k in cat_ap.dtype.names:
                         rec[k] = cat_ap[k][lo:hi]
+                if aperture_data:
+                    for k in cat_ad.dtype.names:
+                        rec[k] = cat_ad[k][lo:hi]
             if on_device:
                 rec["mse_center"] = mse_center[lo:hi]
                 if mc:

@@ -261,6 +261,19 @@ def _aperture_out(n, nb, par, err=True):
     return out, ptrs
 
 
+APERTURE_FIELD_KEYS = ("ap_model_sum", "ap_data_sum", "ap_field_area", "auto_model_sum", "auto_data_sum", "auto_field_area")
+
+
+def _aperture_field_out(n, nb, par):
+    """The result dictionary of the apertures on the fields and its pointers in the C-ABI's order (an output without rows -
+    no radii - goes as a null pointer)."""
+    K = par.n_radii
+    out = dict(ap_model_sum=np.zeros((n, K, nb), np.float64), ap_data_sum=np.zeros((n, K, nb), np.float64),
+               ap_field_area=np.zeros((n, K), np.float64), auto_model_sum=np.zeros((n, nb), np.float64),
+               auto_data_sum=np.zeros((n, nb), np.float64), auto_field_area=np.zeros(n, np.float64))
+    return out, [None if K == 0 and k.startswith("ap_") else _dp(out[k]) for k in APERTURE_FIELD_KEYS]
+
+
 def check_measure_mc_args(samples, band, sigma0, tol, max_iter):
     """(samples, params) of scene_measure_mc: C-contiguous float32 sample stamps (S, N, cs, cs, bands), S >= 1."""
     samples = _f32c(samples)
@@ -763,6 +776,53 @@ class Context:
         if n:
             check(lib.dv_scene_aperture(self._h, _fp(mean), _fp(stddev), _dp(shape), _ip(status), n, cs, nb, mpar.band,
                                         C.byref(par), *ptrs))
+        return out
+
+    def scene_aperture_fields(self, shape, status, places, kron, aper_status, model_fields, data_fields=None, field_ptr=None, *,
+                              cutout_size: int, radii=(3.0, 5.0, 8.0), subsample: int = 5) -> Dict[str, np.ndarray]:
+        """The apertures of scene_aperture on the fields the galaxies lie in (dv_scene_aperture_fields, DESIGN.md section
+        7p): shape (N, 5) and status (N,) the scene_measure rows, kron (N, 3) and aper_status (N,) the scene_aperture rows
+        measured with the same `radii` and `subsample` on stamps of cutout_size pixels; places (N, 2) the field position
+        (row, col) of every stamp's top-left corner; model_fields (M, F, F, bands) the composited mean fields, data_fields
+        the observed fields of the same shape, or None; field_ptr (M + 1,): galaxies field_ptr[m]:field_ptr[m + 1] lie in
+        field m (None: one field holds them all).  No stamp is an input.  Returns {"ap_model_sum", "ap_data_sum" (N, K,
+        bands): the sums of w * model field and w * data field over the stamp pixels of circle k that lie inside the field, w
+        the sub-pixel weight of scene_aperture; "ap_field_area" (N, K): the sum of w over those pixels; "auto_model_sum",
+        "auto_data_sum" (N, bands), "auto_field_area" (N,): the same in the Kron ellipse of radius kron[:, 1]}.  A row with
+        aper_status APER_INELIGIBLE is NaN throughout, a row with APER_NO_KRON in the three auto_ outputs; without
+        data_fields the two _data_sum outputs are NaN; a stamp wholly outside its field gives zeros."""
+        model = np.ascontiguousarray(model_fields, dtype=np.float64)
+        if model.ndim != 4 or model.shape[1] != model.shape[2] or model.shape[3] < 1:
+            raise ValueError(f"expected model fields (M, F, F, bands), got {model.shape}")
+        M, nb = model.shape[0], model.shape[3]
+        data = None
+        if data_fields is not None:
+            data = np.ascontiguousarray(data_fields, dtype=np.float64)
+            if data.shape != model.shape:
+                raise ValueError(f"expected data fields {model.shape}, got {data.shape}")
+        shape = np.ascontiguousarray(shape, dtype=np.float64)
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        kron = np.ascontiguousarray(kron, dtype=np.float64)
+        aper_status = np.ascontiguousarray(aper_status, dtype=np.int32)
+        places = _i32_rows(places, "stamp placements")
+        n = status.shape[0] if status.ndim == 1 else -1
+        if shape.shape != (n, 5) or places.shape != (n, 2) or kron.shape != (n, 3) or aper_status.shape != (n,):
+            raise ValueError(f"expected shape (N, 5), status (N,), places (N, 2), kron (N, 3) and aper_status (N,), got "
+                             f"{shape.shape}, {status.shape}, {places.shape}, {kron.shape}, {aper_status.shape}")
+        cs = int(cutout_size)
+        if cs != cutout_size or cs < 1:
+            raise ValueError(f"cutout_size must be a positive integer (got {cutout_size})")
+        if field_ptr is None:
+            if M != 1:
+                raise ValueError(f"field_ptr is needed with {M} fields")
+            field_ptr = [0, n]
+        fp = check_field_ptr(field_ptr, M, n)
+        par = aperture_params(radii, (), subsample)
+        out, ptrs = _aperture_field_out(n, nb, par)
+        if n:
+            check(lib.dv_scene_aperture_fields(self._h, _dp(shape), _ip(status), _ip(places),
+                                               fp.ctypes.data_as(C.POINTER(C.c_int64)), _dp(kron), _ip(aper_status), n, cs, nb,
+                                               _dp(model), _dp(data), M, model.shape[1], C.byref(par), *ptrs))
         return out
 
     CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
@@ -1323,6 +1383,49 @@ class Engine:
     def scene_aperture(self, mean, shape, status, stddev=None, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_aperture on this engine's GPU context."""
         return self.ctx.scene_aperture(mean, shape, status, stddev, **kw)
+
+    def infer_fields_measure_aper_data(self, fields, starts, field_ptr, places, seed=0, band: int = 2, sigma0: float = 3.0,
+                                       tol: float = 1e-10, max_iter: int = 200, radii=(3.0, 5.0, 8.0),
+                                       fractions=(0.2, 0.5, 0.8), subsample: int = 5, kron_factor: float = 2.5,
+                                       kron_min: float = 3.5, kron_limit: float = 6.0, bisect_iters: int = 32,
+                                       return_fields=True, residual=True, mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_aper() plus the same apertures on the fields (dv_infer_fields_measure_aper_data, DESIGN.md
+        section 7p): returns its dictionary, bit for bit, plus scene_aperture_fields' {"ap_model_sum", "ap_data_sum",
+        "ap_field_area", "auto_model_sum", "auto_data_sum", "auto_field_area"} - the bits of scene_aperture_fields on
+        infer_fields_measure_aper's rows, infer_fields_composite's mean fields and the source fields as data.  The field sums
+        run once a field's composite is complete.  `places` is always needed: with return_fields=False the mean field is still
+        composited on the device (and never downloaded)."""
+        if places is None:
+            raise ValueError("places are needed for the apertures on the fields, with return_fields=False too")
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places)
+        nb = fields.shape[3]
+        par = measure_params(band, sigma0, tol, max_iter, nb)
+        apar = aperture_params(radii, fractions, subsample, kron_factor, kron_min, kron_limit, bisect_iters)
+        if return_fields:
+            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
+        else:
+            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
+            ptrs = [None, None, None, _dp(out.get("mse_center"))]
+        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
+                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
+        ap, ap_ptrs = _aperture_out(N, nb, apar)
+        out.update(ap)
+        af, af_ptrs = _aperture_field_out(N, nb, apar)
+        out.update(af)
+        check(lib.dv_infer_fields_measure_aper_data(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
+                                                    _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]),
+                                                    _ip(out["status"]), C.byref(apar), *ap_ptrs, *af_ptrs))
+        return out
+
+    def infer_cutouts_measure_aper_data(self, field, starts, places, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_aper_data() for one field (F, F, bands): the field-sized results under singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_aper_data(fields, starts, fp, places, seed=seed, **kw))
+
+    def scene_aperture_fields(self, shape, status, places, kron, aper_status, model_fields, data_fields=None,
+                              **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_aperture_fields on this engine's GPU context."""
+        return self.ctx.scene_aperture_fields(shape, status, places, kron, aper_status, model_fields, data_fields, **kw)
 
     def infer_fields_measure_mc(self, fields, starts, field_ptr, places=None, seed=0, mc_seed=0, nsamples=100, band: int = 2,
                                 sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, return_fields=True,

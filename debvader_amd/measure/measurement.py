@@ -326,6 +326,159 @@ def measure_apertures(mean, stddev=None, catalogue=None, radii=(3.0, 5.0, 8.0), 
                             out["kron"], out["flux_rho"], out["aper_flags"], out["aper_status"], shape)
 
 
+# aper_data_flags of the apertures on the fields: bit k < 8 the field edge truncates circle k inside the stamp, then this
+APER_DATA_FLAG_AUTO_TRUNCATED = 1 << 8
+
+
+def aperture_data_dtype(nb_of_bands, n_radii):
+    """The columns of measure_apertures_on_fields' recarray: what the GPU sums, then what the host derives from it."""
+    nb, K = int(nb_of_bands), int(n_radii)
+    return [("ap_model_sum", "<f8", (K, nb)), ("ap_data_sum", "<f8", (K, nb)), ("ap_field_area", "<f8", (K,)),
+            ("auto_model_sum", "<f8", (nb,)), ("auto_data_sum", "<f8", (nb,)), ("auto_field_area", "<f8"),
+            ("ap_flux_data", "<f8", (K, nb)), ("flux_auto_data", "<f8", (nb,)), ("ap_blendedness", "<f8", (K,)),
+            ("auto_blendedness", "<f8"), ("aper_data_flags", "<i4"), ("ap_flux_data_err", "<f8", (K, nb)),
+            ("flux_auto_data_err", "<f8", (nb,))]
+
+
+def check_sky_sigma(sky_sigma, n_fields, nb_of_bands):
+    """The per-band sky noise of the data-flux errors as (M, bands) float64: given as (bands,) for all fields or as (M,
+    bands); every entry finite and positive."""
+    sky = np.asarray(sky_sigma, dtype=np.float64)
+    M, nb = int(n_fields), int(nb_of_bands)
+    if sky.shape == (nb,):
+        sky = np.broadcast_to(sky, (M, nb))
+    elif sky.shape != (M, nb):
+        raise ValueError(f"sky_sigma must have shape ({nb},) - one value per band - or ({M}, {nb}) - per field and band -, got "
+                         f"{sky.shape}")
+    if not np.all(np.isfinite(sky) & (sky > 0)):
+        raise ValueError("sky_sigma must be finite and positive in every entry: it is the standard deviation of the sky noise "
+                         "per pixel")
+    return np.ascontiguousarray(sky)
+
+
+def aperture_data_records(ap_model_sum, ap_data_sum, ap_field_area, auto_model_sum, auto_data_sum, auto_field_area, ap_flux,
+                          ap_area, flux_auto, auto_area, band=2, sky_sigma=None, field_ptr=None):
+    """The recarray of measure_apertures_on_fields from the six arrays the engine returns (scene_aperture_fields') and the
+    columns ap_flux (N, K, bands), ap_area (N, K), flux_auto (N, bands), auto_area (N,) of the aperture photometry they go
+    with.  Derived on the host: ap_flux_data = ap_flux + (ap_data_sum - ap_model_sum), the aperture on the observed field
+    with the neighbours' models subtracted, and flux_auto_data likewise in the Kron ellipse; ap_blendedness = 1 -
+    ap_flux[band] / ap_model_sum[band], the share of the neighbours in the model inside circle k (NaN where the denominator
+    is not positive, exactly 0 for a galaxy alone in its field), auto_blendedness the same in the Kron ellipse;
+    aper_data_flags: bit k < 8 where ap_field_area[k] != ap_area[k], APER_DATA_FLAG_AUTO_TRUNCATED where auto_field_area !=
+    auto_area (a row whose areas are NaN sets no bit) - both are sums of whole numbers over the same s^2, so the comparison is
+    exact; a set bit means the field edge
+    truncates the aperture inside the stamp, and the model part of the data flux reaches further than its data part.  With
+    sky_sigma (bands,) or (M, bands), the per-pixel standard deviation of the sky (field_ptr (M + 1,) gives every galaxy's
+    field; None: one field): ap_flux_data_err = sky_sigma sqrt(ap_field_area), flux_auto_data_err likewise; without it the
+    two are NaN.  NaN follows the GPU's."""
+    auto_model_sum = np.asarray(auto_model_sum, dtype=np.float64)
+    n, nb = auto_model_sum.shape
+    ap_field_area = np.asarray(ap_field_area, dtype=np.float64)
+    if ap_field_area.ndim != 2 or ap_field_area.shape[0] != n:
+        raise ValueError(f"expected ap_field_area ({n}, K), got {ap_field_area.shape}")
+    K = ap_field_area.shape[1]
+    ap_model_sum = np.asarray(ap_model_sum, dtype=np.float64).reshape(n, K, nb)
+    ap_data_sum = np.asarray(ap_data_sum, dtype=np.float64).reshape(n, K, nb)
+    auto_data_sum = np.asarray(auto_data_sum, dtype=np.float64).reshape(n, nb)
+    auto_field_area = np.asarray(auto_field_area, dtype=np.float64).reshape(n)
+    ap_flux = np.asarray(ap_flux, dtype=np.float64).reshape(n, K, nb)
+    ap_area = np.asarray(ap_area, dtype=np.float64).reshape(n, K)
+    flux_auto = np.asarray(flux_auto, dtype=np.float64).reshape(n, nb)
+    auto_area = np.asarray(auto_area, dtype=np.float64).reshape(n)
+    if int(band) != band or not 0 <= int(band) < nb:
+        raise ValueError(f"band {band} asked for, the sums have bands 0 .. {nb - 1}")
+    band = int(band)
+    rec = np.recarray((n,), dtype=aperture_data_dtype(nb, K))
+    rec["ap_model_sum"], rec["ap_data_sum"], rec["ap_field_area"] = ap_model_sum, ap_data_sum, ap_field_area
+    rec["auto_model_sum"], rec["auto_data_sum"], rec["auto_field_area"] = auto_model_sum, auto_data_sum, auto_field_area
+    with np.errstate(all="ignore"):
+        rec["ap_flux_data"] = ap_flux + (ap_data_sum - ap_model_sum)
+        rec["flux_auto_data"] = flux_auto + (auto_data_sum - auto_model_sum)
+        for name, child, model in (("ap_blendedness", ap_flux[:, :, band], ap_model_sum[:, :, band]),
+                                   ("auto_blendedness", flux_auto[:, band], auto_model_sum[:, band])):
+            ok = model > 0                                    # (NaN > 0 is False)
+            rec[name] = np.where(ok, 1.0 - child / np.where(ok, model, 1.0), np.nan)
+        flags = np.zeros(n, np.int32)
+        for k in range(min(K, 8)):                            # (NaN areas - a row without apertures - set no bit)
+            cut = np.isfinite(ap_field_area[:, k]) & np.isfinite(ap_area[:, k]) & (ap_field_area[:, k] != ap_area[:, k])
+            flags |= np.where(cut, 1 << k, 0).astype(np.int32)
+        cut = np.isfinite(auto_field_area) & np.isfinite(auto_area) & (auto_field_area != auto_area)
+        flags |= np.where(cut, APER_DATA_FLAG_AUTO_TRUNCATED, 0).astype(np.int32)
+        rec["aper_data_flags"] = flags
+        if sky_sigma is None:
+            rec["ap_flux_data_err"] = np.nan
+            rec["flux_auto_data_err"] = np.nan
+        else:
+            if field_ptr is None:
+                field_ptr = [0, n]
+            fp = np.asarray(field_ptr, dtype=np.int64).reshape(-1)
+            M = fp.shape[0] - 1
+            if M < 1 or fp[0] != 0 or fp[-1] != n or (np.diff(fp) < 0).any():
+                raise ValueError(f"field_ptr must start at 0, never decrease and end at the number of galaxies ({n})")
+            sky = check_sky_sigma(sky_sigma, M, nb)[np.repeat(np.arange(M), np.diff(fp))]          # (N, bands)
+            rec["ap_flux_data_err"] = sky[:, None, :] * np.sqrt(ap_field_area)[:, :, None]
+            rec["flux_auto_data_err"] = sky * np.sqrt(auto_field_area)[:, None]
+    return rec
+
+
+def measure_apertures_on_fields(catalogue, places, model_fields, data_fields=None, field_ptr=None, sky_sigma=None,
+                                apertures=None, radii=(3.0, 5.0, 8.0), cutout_size=59, subsample=5, band=2, ctx=None):
+    """The aperture photometry of measure_apertures taken on the observed field with the neighbours' models subtracted, on the
+    GPU: the sum over an aperture of D - T + P, D the observed field, T the composited mean field and
+    P the galaxy's own stamp.  The sum over P is measure_apertures' ap_flux; the sums over T and D are taken here, over the
+    pixels of the stamp that lie inside the field, with the same sub-pixel weights.
+
+    parameters:
+        catalogue: the measure_stamps recarray of the galaxies in `band` (row, col, Mrr, Mrc, Mcc and status are read) that
+            also has the measure_apertures columns (ap_flux, ap_area, flux_auto, rho_auto, auto_area, aper_status) - as the
+            recarrays of DeblendFieldBatch.deblend_fields(measure=True, apertures=...) do -, or `apertures` gives those
+        places: (N, 2), the field position (row, col) of every stamp's top-left corner - where the stamp was composited
+        model_fields: (M, F, F, bands), the composited mean fields (the sum of all mean stamps of a field); (F, F, bands)
+            for one field
+        data_fields: the observed fields of the same shape, or None: the data columns are NaN
+        field_ptr: (M + 1,), galaxies field_ptr[m]:field_ptr[m + 1] lie in field m; None: one field holds them all
+        sky_sigma: (bands,) or (M, bands), the standard deviation of the sky noise per pixel; None: the error columns are NaN
+        apertures: the measure_apertures recarray of the same galaxies; None: its columns are read from `catalogue`
+        radii, subsample: those the aperture photometry was taken with; cutout_size: the size of the stamps it was taken on
+        ctx: the engine context to run on (None: the default context)
+    returns a np.recarray with, per galaxy: ap_model_sum, ap_data_sum (K, bands), ap_field_area (K,), auto_model_sum,
+    auto_data_sum (bands,), auto_field_area - the sums of w T, w D and w over the stamp pixels inside the field, in the K
+    circles and in the Kron ellipse - and, derived on the host, ap_flux_data, flux_auto_data, ap_blendedness (K,),
+    auto_blendedness, aper_data_flags, ap_flux_data_err and flux_auto_data_err (aperture_data_records).  A galaxy with
+    aper_status STATUS_INELIGIBLE gets NaN, one with STATUS_NO_KRON NaN in the Kron columns.
+    """
+    model = np.asarray(model_fields, dtype=np.float64)
+    if model.ndim == 3:
+        model = model[None]
+        data_fields = None if data_fields is None else np.asarray(data_fields, dtype=np.float64)[None]
+    ap = catalogue if apertures is None else apertures
+    missing = [k for k in ("row", "col", "Mrr", "Mrc", "Mcc", "status") if k not in catalogue.dtype.names] + \
+        [k for k in ("ap_flux", "ap_area", "flux_auto", "kron_radius", "rho_auto", "auto_area", "aper_status") if k not in ap.dtype.names]
+    if missing:
+        raise ValueError(f"the catalogue lacks the columns {missing}: measure_apertures_on_fields takes the measure_stamps "
+                         "columns and the measure_apertures columns of the same galaxies")
+    radii = np.asarray(radii, dtype=np.float64).reshape(-1)
+    ap_flux = np.asarray(ap["ap_flux"], dtype=np.float64)
+    if ap_flux.ndim != 3 or ap_flux.shape[1] != radii.size:
+        raise ValueError(f"{radii.size} radii given, the catalogue's ap_flux has shape {ap_flux.shape}: give the radii the "
+                         "aperture photometry was taken with")
+    shape = np.stack([np.asarray(catalogue[k], dtype=np.float64) for k in ("row", "col", "Mrr", "Mrc", "Mcc")], axis=1)
+    kron = np.stack([np.asarray(ap[k], dtype=np.float64) for k in ("kron_radius", "rho_auto", "auto_area")], axis=1)
+    M = model.shape[0]
+    if sky_sigma is not None:
+        check_sky_sigma(sky_sigma, M, model.shape[-1])                   # (ValueError before any GPU work)
+    if field_ptr is None and M == 1:
+        field_ptr = [0, shape.shape[0]]
+    if ctx is None:
+        ctx = E.default_context()
+    out = ctx.scene_aperture_fields(shape, np.asarray(catalogue["status"], dtype=np.int32), places, kron,
+                                    np.asarray(ap["aper_status"], dtype=np.int32), model, data_fields, field_ptr=field_ptr,
+                                    cutout_size=cutout_size, radii=radii, subsample=subsample)
+    return aperture_data_records(out["ap_model_sum"], out["ap_data_sum"], out["ap_field_area"], out["auto_model_sum"],
+                                 out["auto_data_sum"], out["auto_field_area"], ap_flux, ap["ap_area"], ap["flux_auto"],
+                                 ap["auto_area"], band=band, sky_sigma=sky_sigma, field_ptr=field_ptr)
+
+
 def measure_blendedness(stamps_mean, catalogue, places, model_fields, data_fields=None, field_ptr=None, band=2, ctx=None):
     """Blendedness of N deblended galaxies on the GPU.
 

@@ -608,6 +608,49 @@ int dv_infer_fields_measure_aper(dv_model* m, const double* fields, int32_t M, i
                                  double* ap_flux_err, double* ap_area, double* flux_auto, double* flux_auto_err, double* kron,
                                  double* flux_rho, int32_t* aper_flags, int32_t* aper_status);
 
+/* ---- aperture photometry on the observed field with the neighbours subtracted ----
+ * The apertures above are sums over the network's own stamp P.  The same apertures on the observed field less the neighbours'
+ * models, sum w (D - T + P), split as the blendedness sums do: sum w P is ap_flux, the rest needs the completed composite T
+ * and the observed field D.  Float64 throughout, evaluated as above.  Per galaxy i of field m: shape[i], status[i] its row of
+ * the measurement, kron[i] and aper_status[i] its row of the aperture photometry (rho_auto = kron[i][1]), (pr, pc) =
+ * places[i], T = model_fields[m] and D = data_fields[m], both [F][F][nb].  The regions, the sub-pixel weights and their counts
+ * n are those of section 7o about (r0, c0) in stamp coordinates; the sums run over the stamp pixels (r, c), 0 <= r, c < cs, of
+ * positive count whose field pixel (pr + r, pc + c) lies inside the field - the pixels the composite keeps:
+ *   ap_model_sum[i][k][b] = (sum n T[pr+r,pc+c,b]) / (s s), ap_data_sum[i][k][b] the same of D, ap_field_area[i][k] = (sum n) / (s s)
+ *   auto_model_sum[i][b], auto_data_sum[i][b], auto_field_area[i]: the same three in the ellipse of radius rho_auto.
+ * A row with aper_status 4, or that the eligibility test of section 7o refuses, is NaN in all six; a row whose aper_status is
+ * not 0 is NaN in the three auto_ outputs (7: the circles are given).  A stamp wholly outside its field gives zero sums and
+ * zero areas.  Without data_fields the two _data_sum outputs are NaN.  A row has the same bits wherever it sits in a batch;
+ * for a galaxy alone in its field whose stamp does not leave it, ap_model_sum has the bits of ap_flux and auto_model_sum those
+ * of flux_auto; where D and T hold the same bits, so do the data and model sums.
+ * dv_scene_aperture_fields: host arrays; shape [N][5], status [N], places [N][2], field_ptr [M + 1] (stamps field_ptr[m] ..
+ * field_ptr[m + 1] lie in field m), kron [N][3], aper_status [N], model_fields [M][F][F][nb], data_fields the same or null;
+ * ap_model_sum / ap_data_sum [N][K][nb], ap_field_area [N][K], auto_model_sum / auto_data_sum [N][nb], auto_field_area [N];
+ * with n_radii = 0 the three ap_ outputs may be null.  No stamp is an input.  Chunked against free device memory.
+ * dv_infer_fields_measure_aper_data: dv_infer_fields_measure_aper (same arguments, same bits in every output it shares with
+ * it) plus the six outputs, taken once a field's composite is complete from the catalogue rows, the aperture rows, the
+ * placements, the mean field and the source field where they lie in device memory; they have the bits of
+ * dv_scene_aperture_fields on those rows, dv_infer_fields_composite's mean fields and the source fields as data.  places is
+ * always needed: in the catalogue-only form the mean field is composited on the device and never downloaded.
+ * Refused before any GPU work (DV_E_INVALID): what dv_scene_aperture / dv_infer_fields_measure_aper refuse; a missing input or
+ * output; a null places; F outside 1 .. 32768; a field_ptr that does not run from 0 to N or that decreases (the whole table is
+ * checked before anything is indexed by it); a placement beyond +-2^28. */
+int dv_scene_aperture_fields(dv_ctx* ctx, const double* shape, const int32_t* status, const int32_t* places,
+                             const int64_t* field_ptr, const double* kron, const int32_t* aper_status, int64_t N, int32_t cs,
+                             int32_t nb, const double* model_fields, const double* data_fields, int32_t M, int32_t F,
+                             const dv_aperture_params* params, double* ap_model_sum, double* ap_data_sum,
+                             double* ap_field_area, double* auto_model_sum, double* auto_data_sum, double* auto_field_area);
+int dv_infer_fields_measure_aper_data(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb,
+                                      const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                                      uint64_t seed, const dv_measure_params* params, double* mean_fields,
+                                      double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
+                                      double* flux_err, double* shape, int32_t* iters, int32_t* status,
+                                      const dv_aperture_params* aper, double* ap_flux, double* ap_flux_err, double* ap_area,
+                                      double* flux_auto, double* flux_auto_err, double* kron, double* flux_rho,
+                                      int32_t* aper_flags, int32_t* aper_status, double* ap_model_sum, double* ap_data_sum,
+                                      double* ap_field_area, double* auto_model_sum, double* auto_data_sum,
+                                      double* auto_field_area);
+
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)
  * keeps per field, in device memory, `work` (what the next pass detects on and cuts from, at first the field), `final`

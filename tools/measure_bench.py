@@ -59,6 +59,18 @@ With --profile-one: warm up, one fp32 call (b), exit.
 
 With --profile-one: warm up, one fp32 call (b), exit.
 
+--aperture-data: what the same apertures on the observed field and the composited mean field cost, on
+the same build and box, in --apertures' protocol -
+
+    (a) catalogue                :  the catalogue-only call as above
+    (b) catalogue+apertures      :  the same with apertures=(3, 5, 8): the baseline
+    (c) catalogue+apertures+data :  the same with aperture_data=True: the mean field is composited on the device and the field
+                                    sums are taken once a field's composite is complete
+
+    python tools/measure_bench.py --aperture-data [--fields 1024] [--size 259] [--repeat 5]
+
+With --profile-one: warm up, one fp32 call (c), exit.
+
 The cost is reported, not gated.
 """
 import argparse
@@ -275,7 +287,7 @@ def main_psf(a):
     print(json.dumps(result))
 
 
-def main_apertures(a):
+def main_apertures(a, data=False):
     rng = np.random.default_rng(0)
     F, M = a.size, a.fields
     base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
@@ -293,19 +305,23 @@ def main_apertures(a):
                   f"fractions 0.2 / 0.5 / 0.8; max_batch {a.max_batch}")
         seen = []
 
-        def with_apertures():
+        def with_apertures(**kw):
             res = DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=True, measure=True, return_fields=False,
-                                                                apertures=radii)
+                                                                apertures=radii, **kw)
             seen[:] = [np.concatenate([r["aper_status"] for r in res]), np.concatenate([r["aper_flags"] for r in res])]
+            if kw:
+                seen.append(np.concatenate([r["aper_data_flags"] for r in res]))
             return sum(len(r) for r in res)
 
         legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False),
                 "catalogue+apertures": with_apertures}
+        if data:
+            legs["catalogue+apertures+data"] = lambda: with_apertures(aperture_data=True)
         with redirect_stdout(quiet):
             for fn in legs.values():           # warm-up
                 fn()
             if a.profile_one:
-                legs["catalogue+apertures"]()
+                list(legs.values())[-1]()
                 net._core.engine.close()
                 return
             times = {k: [] for k in legs}
@@ -322,8 +338,15 @@ def main_apertures(a):
             t = np.array(times[k])
             print(_row(f"{dtype} {k}", t, n, M))
             result[dtype][k.replace("+", "_") + "_ms"] = [round(1e3 * x, 2) for x in t]
-        tc, tp = (float(np.median(times[k])) for k in legs)
+        tc, tp = (float(np.median(times[k])) for k in list(legs)[:2])
         spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
+        if data:
+            td = float(np.median(times["catalogue+apertures+data"]))
+            result[dtype]["field_truncated"] = int(np.count_nonzero(seen[2]))
+            print(f"{dtype} catalogue+apertures+data / catalogue+apertures {td / tp:.3f}: {1e3 * (td - tp):+.1f} ms for {n} "
+                  f"galaxies, {1e6 * (td - tp) / max(n, 1):.2f} us per galaxy (spread "
+                  f"{spread(times['catalogue+apertures+data']):.3f}); the field edge truncates an aperture of "
+                  f"{result[dtype]['field_truncated']} galaxies")
         print(f"{dtype} catalogue+apertures / catalogue {tp / tc:.3f}: {1e3 * (tp - tc):+.1f} ms for {n} galaxies, "
               f"{1e6 * (tp - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times['catalogue']):.3f} and "
               f"{spread(times['catalogue+apertures']):.3f}); aper_status 0 .. 7: {result[dtype]['aper_status']}, kron_min decides "
@@ -345,7 +368,10 @@ def main():
     ap.add_argument("--blend", action="store_true")
     ap.add_argument("--psf", action="store_true")
     ap.add_argument("--apertures", action="store_true")
+    ap.add_argument("--aperture-data", action="store_true")
     a = ap.parse_args()
+    if a.aperture_data:
+        return main_apertures(a, data=True)
     if a.apertures:
         return main_apertures(a)
     if a.psf:
