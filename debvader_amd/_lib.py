@@ -57,6 +57,11 @@ class DvApertureParams(C.Structure):
                 ("kron_limit", C.c_double)]
 
 
+class DvFitFluxParams(C.Structure):
+    """dv_fit_flux_params (include/debvader_hip.h)"""
+    _fields_ = [("min_pivot", C.c_double), ("scratch_bytes", C.c_int64)]
+
+
 class DvError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libdebvader_hip status {status}: {msg}")
@@ -194,6 +199,13 @@ SIGNATURES = {
                                                     C.c_uint64, C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
                                                     C.POINTER(DvApertureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
                                                     _d, _d, _d, _d, _d, _d]),
+    "dv_fit_flux_params_default": (C.c_int, [C.POINTER(DvFitFluxParams)]),
+    "dv_scene_fit_flux": (C.c_int, [_p, _f, _i32, _i64, C.c_int64, C.c_int32, C.c_int32, _d, C.c_int32, C.c_int32,
+                                    C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _i32]),
+    "dv_scene_fit_flux_gram": (C.c_int, [_p, _f, _i32, C.c_int64, C.c_int32, C.c_int32, _d, C.c_int32, _d, _d]),
+    "dv_infer_fields_measure_fit": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
+                                              C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
+                                              C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _i32]),
     "dv_field_set_open": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),

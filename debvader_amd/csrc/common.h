@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <memory>
 #include <utility>
+#include <vector>
 
 namespace dv {
 
@@ -429,6 +430,48 @@ int scene_aperture_fields(const double* shape_h, const int32_t* status_h, const 
                           const double* kron_h, const int32_t* aper_status_h, int64_t N, int cs, int nb, const double* model_h,
                           const double* data_h, int M, int F, const ApertureParams& p, const ApertureFieldRows& out_h,
                           int64_t chunk, int64_t gmax, int device, hipStream_t s);
+// simultaneous flux fit of the mean stamps of a field to its observed field (fitflux.hip): per band the amplitudes
+// a of min |D - sum a_i P_i|^2 over the galaxies of the field, by a dense Cholesky factorisation with dropping.  FitFluxRows: the
+// output rows [.][nb], device or host.  fitflux_check / fitflux_plan: every refusal, before any GPU work; the plan is what
+// FitFluxWork::alloc takes - the dense scratch (at most scratch_bytes, no more than the fields need) and the pair list.
+// launch_fit_flux: the complete fields fa .. fz, every per-galaxy array counted from row 0 of the call; it returns with the
+// stream idle.  scene_fit_flux: host arrays, whole fields at a time within `budget` bytes of device memory (0: half of what
+// is free beside the scratch).  scene_fit_flux_gram: step 1 of one field - the dense G and h to the host.
+int scene_fit_flux_gram(const float* stamps_h, const int32_t* places_h, int64_t n, int cs, int nb, const double* data_h, int F,
+                        double* gram_h, double* proj_h, int device, hipStream_t s);
+constexpr int FF_MAX_N = 1024;                        // galaxies per field (DV_FIT_MAX_N)
+struct FitFluxParams { double min_pivot; int64_t scratch_bytes; };
+struct FitFluxRows { double *scale, *var, *gram, *proj; int* status; };
+struct FitFluxPlan { size_t scratch_elems = 0, pair_cap = 0; };
+struct FitFluxWork {
+  DevBuf<double> scratch;
+  DevBuf<int> pairs;
+  DevBuf<long long> foff;
+  size_t cap_elems = 0;
+  std::vector<int> pairs_h;                           // host staging of one sub-range
+  std::vector<long long> foff_h;
+  static size_t bytes(const FitFluxPlan& plan, size_t fields) {
+    return plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int) + fields * sizeof(long long);
+  }
+  int alloc(const FitFluxPlan& plan, int64_t max_fields);
+};
+struct FitFluxBufs {
+  DevBuf<double> scale, var, gram, proj;
+  DevBuf<int> status;
+  static size_t bytes_per_stamp(int nb) { return (size_t)nb * (4 * sizeof(double) + sizeof(int)); }
+  int alloc(int64_t n, int nb);
+  FitFluxRows rows() const;
+  int download(const FitFluxRows& h, int64_t r, int64_t n, int nb, hipStream_t s) const;
+};
+int fitflux_check(const char* who, int cs, int nb, int F, const FitFluxParams& p);
+int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n);
+int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan);
+int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
+                    const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
+                    int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve = true);
+int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
+                   const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
+                   hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

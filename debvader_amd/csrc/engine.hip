@@ -3131,6 +3131,11 @@ struct PipeJob {
     ApertureParams par{};
     ApertureRows rows{};               // device, row 0 = global stamp 0
   } ap;
+  // the flux fit (dv_infer_fields_measure_fit) needs the mean stamps of a field once its last chunk has gone:
+  // behind every chunk's measurement its mean stamps are copied into store; store decides
+  struct FitFlux {
+    float* store = nullptr;            // device [.][cs][cs][nb], row 0 = global stamp 0
+  } ff;
 };
 
 // The loop of dv_infer_mc on the encoder output m->t of nb stamps: nsamples stochastic decodes, as many per pass as the
@@ -3356,6 +3361,9 @@ static int infer_pipelined(dv_model* m, const PipeJob& j) {
       if (j.ap.on)
         DV_TRY(launch_aperture(p->dloc[b], p->dscale[b], j.ms.shape + (size_t)r * 5, j.ms.status + r, nb, cs, j.nb, j.ms.band,
                                j.ap.par, aperture_rows_at(j.ap.rows, r, j.ap.par, j.nb), p->s_out));
+      if (j.ff.store)
+        DV_HIP(hipMemcpyAsync(j.ff.store + (size_t)r * stamp, p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToDevice,
+                              p->s_out));
     }
     if (j.loc || j.consumer) DV_HIP(hipMemcpyAsync(p->hloc[h], p->dloc[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
     if (j.scale || j.consumer) DV_HIP(hipMemcpyAsync(p->hscale[h], p->dscale[b], nb * stamp * sizeof(float), hipMemcpyDeviceToHost, p->s_out));
@@ -3920,6 +3928,34 @@ int dv_scene_aperture_fields(dv_ctx* c, const double* shape, const int32_t* stat
   // (every refusal is scene_aperture_fields'; chunk and gmax 0: sized there, after them, against free device memory)
   return scene_aperture_fields(shape, status, places, field_ptr, kron, aper_status, N, cs, nb, model_fields, data_fields, M, F,
                                aperture_params(*params), out, 0, 0, c->device, c->stream);
+}
+
+static_assert(DV_FIT_MAX_N == FF_MAX_N, "the header's field limit of the flux fit is the kernels'");
+
+int dv_fit_flux_params_default(dv_fit_flux_params* p) {
+  if (!p) return DV_E_INVALID;
+  p->min_pivot = 1e-8;
+  p->scratch_bytes = (int64_t)256 << 20;
+  return DV_OK;
+}
+
+int dv_scene_fit_flux(dv_ctx* c, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs,
+                      int32_t nb, const double* data_fields, int32_t M, int32_t F, const dv_fit_flux_params* params,
+                      double* fit_scale, double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status) {
+  if (!c) return DV_E_INVALID;
+  if (!params) {
+    set_error("dv_scene_fit_flux: params must be given");
+    return DV_E_INVALID;
+  }
+  // (every refusal is scene_fit_flux's; budget 0: sized there, after them, against free device memory)
+  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, FitFluxParams{params->min_pivot, params->scratch_bytes},
+                        FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status}, 0, c->device, c->stream);
+}
+
+int dv_scene_fit_flux_gram(dv_ctx* c, const float* stamps, const int32_t* places, int64_t n, int32_t cs, int32_t nb,
+                           const double* data_field, int32_t F, double* gram, double* proj) {
+  if (!c) return DV_E_INVALID;
+  return scene_fit_flux_gram(stamps, places, n, cs, nb, data_field, F, gram, proj, c->device, c->stream);
 }
 
 int dv_scene_measure_mc(dv_ctx* c, const float* samples, int32_t S, int64_t N, int32_t cs, int32_t nb,
@@ -5181,13 +5217,34 @@ struct ApertureFieldStage {         // the apertures of every stamp on the mean 
   }
 };
 
+struct FitFluxOut { FitFluxParams par{}; FitFluxRows rows{}; };   // dv_infer_fields_measure_fit: the parameters in, five rows out (host)
+
+struct FitFluxStage {               // the simultaneous flux fit of every field's mean stamps to its source field (7q)
+  DevBuf<float> store;              // the mean stamps of all N stamps: a field's are read when its composite is complete
+  FitFluxWork work;
+  FitFluxBufs bufs;
+  static size_t bytes_per_stamp(int cs, int nb) { return (size_t)cs * cs * nb * sizeof(float) + FitFluxBufs::bytes_per_stamp(nb); }
+  int alloc(const FitFluxPlan& plan, int64_t N, int64_t M, int cs, int nb) {
+    DV_TRY(store.alloc((size_t)N * cs * cs * nb));
+    DV_TRY(work.alloc(plan, M));
+    return bufs.alloc(N, nb);
+  }
+  void bind(PipeJob::FitFlux& q) const { q.store = store; }
+  int download(const FitFluxOut& o, int64_t N, int nb, hipStream_t s) {
+    DV_TRY(bufs.download(o.rows, 0, N, nb, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return DV_OK;
+  }
+};
+
 // j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
 // the device side and the rows are filled in here
 static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
                              const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr,
                              const MeasureMcOut* mco = nullptr, const BlendOut* bo = nullptr,
                              const int32_t* blend_places = nullptr, const RegaussOut* ro = nullptr,
-                             const ApertureOut* ao = nullptr, const ApertureFieldOut* afo = nullptr) {
+                             const ApertureOut* ao = nullptr, const ApertureFieldOut* afo = nullptr,
+                             const FitFluxOut* ffo = nullptr) {
   // check
   const double* fields = j.fields;
   const int F = j.F, nb = j.nb;
@@ -5197,6 +5254,8 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   const int32_t* places = fo ? fo->places : blend_places;   // (blend_places: the catalogue-only form of a call that composites)
   DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, j.starts, places, sfield, fptr32));
   const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
+  FitFluxPlan ffplan;
+  if (ffo) DV_TRY(fitflux_plan(who, field_ptr, M, nb, ffo->par, &ffplan));   // (before anything is written or queued)
   if (fo) fields_write_empty(*fo, fields, M, field_ptr, felems);
   if (N == 0) return DV_OK;
   TinyCall tiny(m, N);
@@ -5211,7 +5270,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   double* mse_h = fo ? fo->mse : mo ? mo->mse : nullptr;
   DevBuf<double> fdev;                                // the resident group of source fields
   StampTables tab;
-  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs; ApertureStage aps; MeanFieldStage mfs; ApertureFieldStage afs;   // (a stage that does not run stays empty)
+  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs; ApertureStage aps; MeanFieldStage mfs; ApertureFieldStage afs; FitFluxStage ffs;   // (a stage that does not run stays empty)
   ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
   if (fitting) DV_TRY(fit.make_plan(*fo, c, sfield.data()));
   size_t per_field = fb, reserve = StampTables::bytes((size_t)N, (size_t)M);
@@ -5233,6 +5292,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (ro) reserve += (size_t)N * RegaussStage::bytes_per_stamp() + RegaussStage::bytes_fixed(*ro);
   if (ao) reserve += (size_t)N * ApertureStage::bytes_per_stamp(*ao, nb);
   if (afo) reserve += (size_t)N * ApertureFieldStage::bytes_per_stamp(*ao, nb);
+  if (ffo) reserve += (size_t)N * FitFluxStage::bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M);
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
@@ -5277,6 +5337,10 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     aps.bind(j.ap, *ao);
   }
   if (afo) DV_TRY(afs.alloc(*ao, N, nb));
+  if (ffo) {
+    DV_TRY(ffs.alloc(ffplan, N, M, c.cs, nb));
+    ffs.bind(j.ff);
+  }
   if (fitting) {
     DV_TRY(fit.alloc(*fo, c, gmax, groups));
     fit.bind(j.fit);
@@ -5306,7 +5370,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     j.row0 = g.k0 * chunk;
     j.N = std::min<int64_t>(N, g.k1 * chunk) - j.row0;
     DV_TRY(infer_pipelined(m, j));
-    if (bo || afo) {
+    if (bo || afo || ffo) {
       // the completed-field seam: every field of the group has all its stamps composited now, but for a last field that
       // the next group goes on with (it is complete there); the parent sums and the field apertures of the complete fields'
       // galaxies - one contiguous range of rows - read the mean field, the source field and the rows where they lie
@@ -5323,6 +5387,9 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
                                        aps.bufs.kron.get() + (size_t)r0 * 3, aps.bufs.status.get() + r0,
                                        tab.places.get() + 2 * (size_t)r0, tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, F,
                                        mean_f, fdev, ao->par, aperture_field_rows_at(afs.bufs.rows(), r0, ao->par, nb), s));
+        if (ffo)                       // (the stamp store, the placements and the tables count from stamp 0 of the call)
+          DV_TRY(launch_fit_flux(ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, places, fptr32.data(), fa, fz, c.cs,
+                                 nb, F, ffo->par, ffs.work, ffs.bufs.rows(), s));
       }
     }
     if (fo) {
@@ -5343,6 +5410,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (ro) DV_TRY(rgs.download(*ro, N, s));
   if (ao) DV_TRY(aps.download(*ao, N, nb, s));
   if (afo) DV_TRY(afs.download(*afo, *ao, N, nb, s));
+  if (ffo) DV_TRY(ffs.download(*ffo, N, nb, s));
   if (fo) DV_TRY(mc.download(N, s));
   if (fitting) DV_TRY(fit.download(*fo, N, s));
   drain.dismiss();
@@ -5458,7 +5526,8 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
                                       double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
                                       double* flux_err, double* shape, int32_t* iters, int32_t* status,
                                       const BlendOut* bo = nullptr, const RegaussOut* ro = nullptr,
-                                      const ApertureOut* ao = nullptr, const ApertureFieldOut* afo = nullptr) {
+                                      const ApertureOut* ao = nullptr, const ApertureFieldOut* afo = nullptr,
+                                      const FitFluxOut* ffo = nullptr) {
   if (!m || !params) return DV_E_INVALID;
   DV_TRY(measure_check(who, m->A.H, nb, params->band, params->sigma0, params->tol, params->max_iter));
   if (ao) {
@@ -5467,6 +5536,14 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
   }
   if (afo) {                           // (the apertures on the fields go with the aperture rows: ao is given)
     DV_TRY(aperture_field_rows_check(who, afo->rows, ao->par, N));
+    if (N > 0 && !places) {
+      set_error("%s: places must be given (the catalogue-only form needs the placements too)", who);
+      return DV_E_INVALID;
+    }
+  }
+  if (ffo) {
+    DV_TRY(fitflux_check(who, m->A.H, nb, F, ffo->par));
+    DV_TRY(fitflux_rows_check(who, ffo->rows, N));
     if (N > 0 && !places) {
       set_error("%s: places must be given (the catalogue-only form needs the placements too)", who);
       return DV_E_INVALID;
@@ -5505,7 +5582,7 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
   PipeJob j = fields_job(fields, F, nb, starts, seed);
   if (!with_fields) {
     mo.mse = mse_center;
-    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo || afo ? places : nullptr, ro, ao, afo);
+    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo || afo || ffo ? places : nullptr, ro, ao, afo, ffo);
   }
   FieldsOut fo;
   fo.mean = mean_fields;
@@ -5513,7 +5590,7 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const double
   fo.residual = residual_fields;
   fo.mse = mse_center;
   fo.places = places;
-  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo, nullptr, ro, ao, afo);
+  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo, nullptr, ro, ao, afo, ffo);
 }
 
 int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
@@ -5614,6 +5691,28 @@ int dv_infer_fields_measure_aper_data(dv_model* m, const double* fields, int32_t
   return infer_fields_measure_entry("dv_infer_fields_measure_aper_data", m, fields, M, F, nb, starts, places, field_ptr, N,
                                     seed, params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err,
                                     shape, iters, status, nullptr, nullptr, &ao, &afo);
+}
+
+// ---- the simultaneous flux fit beside the catalogue: dv_infer_fields_measure plus, per galaxy and band, the
+// amplitude of its mean stamp in the least-squares fit of all the mean stamps of its field to the source field, taken at the
+// completed-field seam from the mean stamps the chunk loop has kept
+int dv_infer_fields_measure_fit(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                int32_t* iters, int32_t* status, const dv_fit_flux_params* fit, double* fit_scale,
+                                double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status) {
+  if (!m) return DV_E_INVALID;
+  if (!fit) {
+    set_error("dv_infer_fields_measure_fit: the flux-fit params must be given");
+    return DV_E_INVALID;
+  }
+  FitFluxOut ffo;
+  ffo.par = FitFluxParams{fit->min_pivot, fit->scratch_bytes};
+  ffo.rows = FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status};
+  return infer_fields_measure_entry("dv_infer_fields_measure_fit", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
+                                    params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
+                                    iters, status, nullptr, nullptr, nullptr, nullptr, &ffo);
 }
 
 // ---- the Monte-Carlo catalogue beside it: dv_infer_fields_measure plus means and standard deviations of

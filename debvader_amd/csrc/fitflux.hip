@@ -1,0 +1,577 @@
+// Simultaneous flux fit of the deblended models to the observed field: the shapes of the galaxies of a field
+// are held fixed at their mean stamps and all their amplitudes are fitted to the observed pixels at once, per band - the last
+// step of the SDSS deblender, the Tractor's and scarlet's flux re-fit.  Linear least squares; the reference ships an empty
+// debvader.measure package, so the quantity is defined here.
+//
+// Float64 throughout, floating-point contraction off: every product and every sum is rounded on its own.  Per field m with
+// galaxies i = 0 .. n - 1 in object order: P_i the mean stamp [cs][cs][nb] (float32, widened), (pr_i, pc_i) = places[i], D the
+// observed field [F][F][nb].  The pixels of i are the stamp pixels whose field pixel lies inside the field (the pixels the
+// composite keeps, 7l).  Per band b, independently:
+//   1. G_ij = sum P_i P_j over the field pixels both stamps cover (j <= i), exactly 0.0 where the two clipped rectangles do not
+//      intersect; h_i = sum P_i D over the pixels of i.  Every sum is one fixed-order workgroup reduction (ms_block_sum).
+//   2. A galaxy whose G_ii is not finite or not positive has status 4: fit_scale and fit_var NaN, not part of the system.
+//   3. Cholesky factorisation of G over the eligible galaxies in object order, with dropping: at column k the pivot is
+//      d_k = G_kk - sum_{j < k, kept} L_kj^2; d_k <= min_pivot G_kk drops galaxy k (status 5).  A dropped column is never
+//      applied to the others: the variable leaves the system.  Of two models that cannot be told apart the one dropped is
+//      always the later in object order - the earlier one has been factorised when the later one's pivot vanishes.
+//   4. A dropped galaxy keeps the network's amplitude: h'_i = h_i - sum_{k dropped} G_ik, fit_scale = 1, fit_var = NaN.
+//   5. G_kept a = h' by the two triangular solves: fit_scale = a; fit_var_i = (G_kept^-1)_ii, the sum of squares of column i
+//      of L^-1.  fit_gram = G_ii and fit_proj = h_i are given for every galaxy.  Amplitudes are not clipped.
+//
+// Two kernels:
+//   fitflux_gram_kernel   one 256-thread workgroup per entry of a pair list (i, j <= i) the host builds from the placements:
+//                         the pairs of one field whose clipped rectangles intersect, diagonal included.  Threads take the pixels
+//                         of the intersection in raster order, stride 256; a pixel reads the nb contiguous floats of both
+//                         stamps into statically indexed band slots (8-byte loads where the address allows); one ms_block_sum
+//                         per band; thread 0 writes G[b][i][j] of the field's dense scratch [nb][n][n] (lower triangle, zeroed
+//                         before the launch).  The diagonal entry also takes h_i against D and writes fit_gram and fit_proj.
+//   fitflux_solve_kernel  one workgroup per (field, band): steps 2 - 5 in place on that scratch in global memory.  The strict
+//                         upper triangle (transposed) and the diagonal take the working copy that becomes L - column k of L is
+//                         contiguous -, the strict lower triangle keeps G for step 4 and then takes L^-1.  The workgroup reads
+//                         only what it wrote itself, behind __syncthreads(); nothing is handed between workgroups.  Every
+//                         element is updated by one thread per column, in ascending column order, and every other sum runs in
+//                         ascending index order in one thread: a field's rows have the same bits wherever the field sits in a
+//                         batch and when it is alone.
+// No atomics; ordinary vector stores only.
+#include "common.h"
+#include "measure_dev.h"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#pragma clang fp contract(off)
+
+namespace dv {
+
+namespace {
+constexpr int FF_BANDS = 16;
+
+// the nb floats at p, widened, into the band slots; an 8-byte load for every pair of slots that starts at an aligned address
+// (ODD: p itself is 4 bytes past one, slot 0 goes alone).  Slots from nb on are left alone; nothing past p[nb - 1] is read.
+template <int ODD>
+__device__ __forceinline__ void ff_load_slots(const float* __restrict__ p, int nb, double (&v)[FF_BANDS]) {
+  if (ODD) v[0] = (double)p[0];
+#pragma unroll
+  for (int b = ODD; b < FF_BANDS; b += 2) {
+    if (b + 1 < FF_BANDS && b + 1 < nb) {
+      const float2 t = *reinterpret_cast<const float2*>(p + b);
+      v[b] = (double)t.x;
+      v[b + 1 < FF_BANDS ? b + 1 : b] = (double)t.y;
+    } else if (b < nb) {
+      v[b] = (double)p[b];
+    }
+  }
+}
+
+__device__ __forceinline__ void ff_load(const float* __restrict__ p, int nb, double (&v)[FF_BANDS]) {
+  if (((unsigned long long)p & 7ull) == 0)
+    ff_load_slots<0>(p, nb, v);
+  else
+    ff_load_slots<1>(p, nb, v);
+}
+
+// pairs [.][2]: the rows (i, j <= i) of two galaxies of one field, counted like every per-galaxy array here from row 0 of the
+// call; stamps [.][cs][cs][nb]; places [.][2]; sfield [.] the field of every row, fptr [.] the first row of every field; foff
+// [.]: where the scratch of field fbase + k begins in `scratch`, in doubles; data: the observed fields from field f0 on;
+// gram / proj [.][nb]
+__global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __restrict__ pairs, const float* __restrict__ stamps,
+                                                                  const int* __restrict__ places, const int* __restrict__ sfield,
+                                                                  const int* __restrict__ fptr, const long long* __restrict__ foff,
+                                                                  int fbase, int f0, int cs, int nb, int F,
+                                                                  const double* __restrict__ data, double* __restrict__ scratch,
+                                                                  double* __restrict__ gram, double* __restrict__ proj) {
+  __shared__ double s_red[MS_RED];
+  const long gi = pairs[2 * (long)blockIdx.x], gj = pairs[2 * (long)blockIdx.x + 1];
+  const int m = sfield[gi];
+  const int row0 = fptr[m], n = fptr[m + 1] - row0;
+  const int pri = places[2 * gi], pci = places[2 * gi + 1], prj = places[2 * gj], pcj = places[2 * gj + 1];
+  // the intersection of the two stamps and the field, in field pixels (the host lists a pair only where it is not empty)
+  const int ra = max(max(pri, prj), 0), rz = min(min(pri, prj) + cs, F);
+  const int ca = max(max(pci, pcj), 0), cz = min(min(pci, pcj) + cs, F);
+  const int w = cz - ca, npix = (rz - ra) * w;
+  const bool diag = gi == gj;                // (uniform: the whole workgroup takes one pair)
+  const float* Pi = stamps + gi * cs * cs * nb;
+  const float* Pj = stamps + gj * cs * cs * nb;
+  const double* D = data + (long)(m - f0) * F * F * nb;
+  double g[FF_BANDS], h[FF_BANDS], vi[FF_BANDS], vj[FF_BANDS];
+#pragma unroll
+  for (int b = 0; b < FF_BANDS; ++b) g[b] = h[b] = vi[b] = vj[b] = 0.0;
+  for (int e = threadIdx.x; e < npix; e += MS_THREADS) {
+    const int r = ra + e / w, c = ca + e % w;
+    ff_load(Pi + ((long)(r - pri) * cs + (c - pci)) * nb, nb, vi);
+    if (diag) {
+      const double* dp = D + ((long)r * F + c) * nb;
+#pragma unroll
+      for (int b = 0; b < FF_BANDS; ++b) {
+        if (b < nb) {
+          g[b] += vi[b] * vi[b];
+          h[b] += vi[b] * dp[b];
+        }
+      }
+    } else {
+      ff_load(Pj + ((long)(r - prj) * cs + (c - pcj)) * nb, nb, vj);
+#pragma unroll
+      for (int b = 0; b < FF_BANDS; ++b) {
+        if (b < nb) g[b] += vi[b] * vj[b];
+      }
+    }
+  }
+  const long il = gi - row0, jl = gj - row0;
+  double* S = scratch + foff[m - fbase] + il * n + jl;
+#pragma unroll
+  for (int b = 0; b < FF_BANDS; ++b) {
+    if (b < nb) {                            // (nb and diag are uniform: every thread takes the same barriers)
+      if (diag) {
+        double a[2] = {g[b], h[b]};
+        ms_block_sum<2>(a, s_red);
+        if (threadIdx.x == 0) {
+          S[(long)b * n * n] = a[0];
+          gram[gi * nb + b] = a[0];
+          proj[gi * nb + b] = a[1];
+        }
+      } else {
+        double a[1] = {g[b]};
+        ms_block_sum<1>(a, s_red);
+        if (threadIdx.x == 0) S[(long)b * n * n] = a[0];
+      }
+    }
+  }
+}
+
+// Field fbase + blockIdx.x, band blockIdx.y.  S = its [n][n] scratch: on entry G in the lower triangle, zeros above.  W(i, j),
+// j < i - the working copy, then L - lies at S[j n + i]; the diagonal in place.  LDS: the status of every galaxy and the
+// right-hand side, 12 KB.
+__global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __restrict__ fptr, const long long* __restrict__ foff,
+                                                                   int fbase, int nb, double min_pivot,
+                                                                   double* __restrict__ scratch, const double* __restrict__ gram,
+                                                                   const double* __restrict__ proj, double* __restrict__ scale,
+                                                                   double* __restrict__ var, int* __restrict__ status) {
+  __shared__ double s_y[FF_MAX_N];
+  __shared__ int s_st[FF_MAX_N];
+  const int m = fbase + (int)blockIdx.x, b = (int)blockIdx.y;
+  const long row0 = fptr[m];
+  const int n = fptr[m + 1] - (int)row0;
+  if (n <= 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double* S = scratch + foff[blockIdx.x] + (long)b * n * n;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+
+  // step 2 and the working copy
+  for (int i = tid; i < n; i += MS_THREADS) {
+    const double gii = gram[(row0 + i) * nb + b];
+    s_st[i] = (ms_finite(gii) && gii > 0.0) ? 0 : 4;
+  }
+  for (int i = wave; i < n; i += MS_THREADS / 64)
+    for (int j = lane; j < i; j += 64) S[(long)j * n + i] = S[(long)i * n + j];
+  __syncthreads();
+
+  // step 3: right-looking, column by column; element (i, j) of the trailing part belongs to one thread in every column
+  for (int k = 0; k < n; ++k) {
+    if (s_st[k] != 0) continue;              // (uniform; s_st[k] was last written behind a barrier)
+    const double d = S[(long)k * n + k];
+    const double gkk = gram[(row0 + k) * nb + b];
+    if (d <= min_pivot * gkk) {              // (uniform: every thread read the same two values)
+      __syncthreads();                       // everyone has read s_st[k]
+      if (tid == 0) s_st[k] = 5;
+      __syncthreads();
+      continue;
+    }
+    const double lkk = __dsqrt_rn(d);
+    __syncthreads();                         // everyone has read the pivot
+    if (tid == 0) S[(long)k * n + k] = lkk;
+    for (int i = k + 1 + tid; i < n; i += MS_THREADS)
+      if (s_st[i] == 0) S[(long)k * n + i] = S[(long)k * n + i] / lkk;
+    __syncthreads();
+    for (int j = k + 1 + wave; j < n; j += MS_THREADS / 64) {
+      if (s_st[j] != 0) continue;
+      const double ljk = S[(long)k * n + j];
+      for (int i = j + lane; i < n; i += 64)
+        if (s_st[i] == 0) S[(long)j * n + i] = S[(long)j * n + i] - S[(long)k * n + i] * ljk;
+    }
+    __syncthreads();
+  }
+
+  // step 4: the right-hand side less the dropped galaxies at the network's amplitude (G as the Gram kernel left it)
+  for (int i = tid; i < n; i += MS_THREADS) {
+    double hp = proj[(row0 + i) * nb + b];
+    if (s_st[i] == 0) {
+      for (int k = 0; k < n; ++k)
+        if (s_st[k] == 5) hp = hp - (k < i ? S[(long)i * n + k] : S[(long)k * n + i]);   // (G_ik lies at (max, min))
+    }
+    s_y[i] = hp;
+  }
+  __syncthreads();
+
+  // step 5: L y = h', then L^T a = y, column-oriented: once y_k is known it leaves every later right-hand side
+  for (int k = 0; k < n; ++k) {
+    if (s_st[k] != 0) continue;
+    const double yk = s_y[k] / S[(long)k * n + k];
+    __syncthreads();                         // everyone has read s_y[k]
+    if (tid == 0) s_y[k] = yk;
+    for (int i = k + 1 + tid; i < n; i += MS_THREADS)
+      if (s_st[i] == 0) s_y[i] = s_y[i] - S[(long)k * n + i] * yk;
+    __syncthreads();
+  }
+  for (int k = n - 1; k >= 0; --k) {
+    if (s_st[k] != 0) continue;
+    const double ak = s_y[k] / S[(long)k * n + k];
+    __syncthreads();
+    if (tid == 0) s_y[k] = ak;
+    for (int i = tid; i < k; i += MS_THREADS)
+      if (s_st[i] == 0) s_y[i] = s_y[i] - S[(long)i * n + k] * ak;
+    __syncthreads();
+  }
+
+  // column i of X = L^-1, one thread per column, into the strict lower triangle (X(r, i) at S[r n + i]): X(i, i) = 1 / L_ii,
+  // X(r, i) = -(sum_{i <= c < r} L_rc X(c, i)) / L_rr, c ascending.  The loops run over the same (r, c) in every lane, so
+  // the loads of L are uniform and those of X are contiguous over the lanes.
+  for (int i0 = 0; i0 < n; i0 += MS_THREADS) {
+    const int i = i0 + tid;
+    const bool on = i < n && s_st[i] == 0;
+    double xi = 0.0, acc = 0.0;
+    if (on) {
+      xi = 1.0 / S[(long)i * n + i];
+      acc = xi * xi;
+    }
+    for (int r = i0 + 1; r < n; ++r) {
+      if (s_st[r] != 0) continue;            // (uniform)
+      double sum = 0.0;
+      if (on && r > i) sum = S[(long)i * n + r] * xi;
+      for (int c = i0 + 1; c < r; ++c) {
+        if (s_st[c] != 0) continue;
+        if (on && c > i) sum = sum + S[(long)c * n + r] * S[(long)c * n + i];
+      }
+      if (on && r > i) {
+        const double x = -sum / S[(long)r * n + r];
+        S[(long)r * n + i] = x;
+        acc = acc + x * x;
+      }
+    }
+    if (i < n) {
+      const long o = (row0 + i) * nb + b;
+      const int st = s_st[i];
+      scale[o] = st == 0 ? s_y[i] : st == 5 ? 1.0 : nan;
+      var[o] = st == 0 ? acc : nan;
+      status[o] = st;
+    }
+  }
+}
+}  // namespace
+
+// the refusals that need no table, before any GPU work
+int fitflux_check(const char* who, int cs, int nb, int F, const FitFluxParams& p) {
+  if (cs < 1 || cs > 4096 || nb < 1 || nb > FF_BANDS) {
+    set_error("%s: stamps of %d pixels and %d bands; the flux fit takes 1 .. 4096 pixels and 1 .. %d bands", who, cs, nb, FF_BANDS);
+    return E_INVALID;
+  }
+  if (F < 1 || F > 32768) {
+    set_error("%s: fields of %d pixels, 1 .. 32768 are taken", who, F);
+    return E_INVALID;
+  }
+  if (!(p.min_pivot > 0.0 && p.min_pivot < 1.0)) {
+    set_error("%s: min_pivot must lie strictly between 0 and 1 (got %g)", who, p.min_pivot);
+    return E_INVALID;
+  }
+  if (p.scratch_bytes < 1) {
+    set_error("%s: scratch_bytes must be at least 1 (got %ld)", who, (long)p.scratch_bytes);
+    return E_INVALID;
+  }
+  return OK;
+}
+
+int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n) {
+  if (n > 0 && (!o.scale || !o.var || !o.gram || !o.proj || !o.status)) {
+    set_error("%s: fit_scale, fit_var, fit_gram, fit_proj and fit_status must all be given", who);
+    return E_INVALID;
+  }
+  return OK;
+}
+
+// the two refusals by field (field_ptr has passed the caller's checks) and what the fields need: the doubles of dense scratch
+// and the pair entries of the largest sub-range that goes through the scratch at once
+int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan) {
+  size_t total = 0, pairs = 0;
+  for (int f = 0; f < M; ++f) {
+    const int64_t n = field_ptr[f + 1] - field_ptr[f];
+    if (n > FF_MAX_N) {
+      set_error("%s: field %d has %ld galaxies, the dense fit takes at most %d per field", who, f, (long)n, FF_MAX_N);
+      return E_INVALID;
+    }
+    const size_t need = (size_t)nb * n * n * sizeof(double);
+    if (need > (size_t)p.scratch_bytes) {
+      set_error("%s: field %d has %ld galaxies: its Gram matrices need %zu bytes of scratch (bands x n x n doubles), "
+                "scratch_bytes is %ld", who, f, (long)n, need, (long)p.scratch_bytes);
+      return E_INVALID;
+    }
+    total += need / sizeof(double);
+    pairs += (size_t)n * (n + 1) / 2;
+  }
+  const size_t cap = std::min(total, (size_t)p.scratch_bytes / sizeof(double));
+  const size_t rows = (size_t)(M > 0 ? field_ptr[M] - field_ptr[0] : 0);
+  plan->scratch_elems = cap;
+  plan->pair_cap = std::min(pairs, (cap / nb + rows) / 2 + 1);   // sum n (n + 1) / 2 over fields with sum nb n^2 <= cap
+  return OK;
+}
+
+int FitFluxWork::alloc(const FitFluxPlan& plan, int64_t max_fields) {
+  cap_elems = plan.scratch_elems;
+  DV_TRY(scratch.alloc(plan.scratch_elems));
+  DV_TRY(pairs.alloc(2 * plan.pair_cap));
+  return foff.alloc((size_t)std::max<int64_t>(max_fields, 1));
+}
+
+int FitFluxBufs::alloc(int64_t n, int nb) {
+  const size_t N = (size_t)n * nb;
+  DV_TRY(scale.alloc(N));
+  DV_TRY(var.alloc(N));
+  DV_TRY(gram.alloc(N));
+  DV_TRY(proj.alloc(N));
+  return status.alloc(N);
+}
+
+FitFluxRows FitFluxBufs::rows() const { return FitFluxRows{scale.get(), var.get(), gram.get(), proj.get(), status.get()}; }
+
+// rows r .. r + n of the device buffers to the same rows of `h`
+int FitFluxBufs::download(const FitFluxRows& h, int64_t r, int64_t n, int nb, hipStream_t s) const {
+  const size_t o = (size_t)r * nb, c = (size_t)n * nb;
+  if (c == 0) return OK;
+  DV_HIP(hipMemcpyAsync(h.scale + o, scale.get() + o, c * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(h.var + o, var.get() + o, c * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(h.gram + o, gram.get() + o, c * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(h.proj + o, proj.get() + o, c * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(h.status + o, status.get() + o, c * sizeof(int), hipMemcpyDeviceToHost, s));
+  return OK;
+}
+
+// The complete fields fa .. fz of a call.  Every per-galaxy device array counts from row 0 of the call, like fptr (host and
+// device: the first row of every field) and sfield_dev; data_dev holds the observed fields from field f0 on.  The fields go
+// through the dense scratch in sub-ranges whose Gram matrices fit it; the split changes no bit, a field's rows depend on
+// nothing but the field.  Returns with the stream idle: the host tables of a sub-range are rebuilt for the next.  solve false:
+// step 1 alone - the scratch keeps G of the last sub-range, gram and proj are written, the other rows are not touched.
+int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
+                    const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
+                    int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve) {
+  for (int f = fa; f <= fz;) {
+    w.foff_h.clear();
+    w.pairs_h.clear();
+    size_t used = 0;
+    int g = f;
+    for (; g <= fz; ++g) {
+      const int row0 = fptr_h[g], n = fptr_h[g + 1] - row0;
+      const size_t need = (size_t)nb * n * n;
+      if (used + need > w.cap_elems) break;          // (one field fits: fitflux_plan has refused the others)
+      w.foff_h.push_back((long long)used);
+      used += need;
+      for (int i = 0; i < n; ++i) {
+        const int pri = places_h[2 * (size_t)(row0 + i)], pci = places_h[2 * (size_t)(row0 + i) + 1];
+        for (int j = 0; j <= i; ++j) {
+          const int prj = places_h[2 * (size_t)(row0 + j)], pcj = places_h[2 * (size_t)(row0 + j) + 1];
+          const int ra = std::max(std::max(pri, prj), 0), rz = std::min(std::min(pri, prj) + cs, F);
+          const int ca = std::max(std::max(pci, pcj), 0), cz = std::min(std::min(pci, pcj) + cs, F);
+          if (rz > ra && cz > ca) {
+            w.pairs_h.push_back(row0 + i);
+            w.pairs_h.push_back(row0 + j);
+          }
+        }
+      }
+    }
+    if (g == f) {                                      // (cannot happen behind fitflux_plan)
+      set_error("flux fit: field %d does not fit the scratch", f);
+      return E_STATE;
+    }
+    const int r0 = fptr_h[f], r1 = fptr_h[g];
+    const size_t npairs = w.pairs_h.size() / 2;
+    if (r1 > r0) {
+      DV_TRY(w.pairs.ensure(w.pairs_h.size()));
+      DV_TRY(w.foff.ensure(w.foff_h.size()));
+      DV_HIP(hipMemcpyAsync(w.foff, w.foff_h.data(), w.foff_h.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+      DV_HIP(hipMemsetAsync(w.scratch, 0, used * sizeof(double), s));
+      // (a stamp wholly outside its field has no pair: its G_ii and h_i are the empty sums)
+      DV_HIP(hipMemsetAsync(rows.gram + (size_t)r0 * nb, 0, (size_t)(r1 - r0) * nb * sizeof(double), s));
+      DV_HIP(hipMemsetAsync(rows.proj + (size_t)r0 * nb, 0, (size_t)(r1 - r0) * nb * sizeof(double), s));
+      if (npairs > 0) {
+        DV_HIP(hipMemcpyAsync(w.pairs, w.pairs_h.data(), w.pairs_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(fitflux_gram_kernel, dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, w.pairs.get(), stamps_dev,
+                           places_dev, sfield_dev, fptr_dev, w.foff.get(), f, f0, cs, nb, F, data_dev, w.scratch.get(),
+                           rows.gram, rows.proj);
+        DV_HIP(hipGetLastError());
+      }
+      if (solve) {
+        hipLaunchKernelGGL(fitflux_solve_kernel, dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev,
+                           w.foff.get(), f, nb, p.min_pivot, w.scratch.get(), rows.gram, rows.proj, rows.scale, rows.var,
+                           rows.status);
+        DV_HIP(hipGetLastError());
+      }
+      DV_HIP(hipStreamSynchronize(s));
+    }
+    f = g;
+  }
+  return OK;
+}
+
+// host arrays in, host rows out, whole fields at a time: as many consecutive fields as `budget` bytes of device memory hold
+// with their stamps, tables and rows (0: half of free device memory beside the scratch, taken after the refusals)
+int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
+                   const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
+                   hipStream_t s) {
+  const char* who = "dv_scene_fit_flux";
+  DV_TRY(fitflux_check(who, cs, nb, F, p));
+  if (N < 0 || M < 0 || !field_ptr || (N > 0 && (!stamps_h || !places_h || !data_h))) {
+    set_error("%s: stamps, places, field_ptr and data_fields must all be given", who);
+    return E_INVALID;
+  }
+  DV_TRY(fitflux_rows_check(who, out_h, N));
+  if (N >= ((int64_t)1 << 31)) {
+    set_error("%s: %ld stamps, at most 2^31 - 1 per call", who, (long)N);
+    return E_INVALID;
+  }
+  if (field_ptr[0] != 0 || field_ptr[M] != N) {
+    set_error("%s: field_ptr must run from 0 to the number of stamps (%ld), got %ld .. %ld", who, (long)N,
+              (long)field_ptr[0], (long)field_ptr[M]);
+    return E_INVALID;
+  }
+  for (int f = 0; f < M; ++f)                        // the whole table before anything is indexed by it
+    if (field_ptr[f + 1] < field_ptr[f]) {
+      set_error("%s: field_ptr decreases at field %d (%ld after %ld)", who, f, (long)field_ptr[f + 1], (long)field_ptr[f]);
+      return E_INVALID;
+    }
+  for (int64_t i = 0; i < N; ++i) {
+    const int pr = places_h[2 * i], pc = places_h[2 * i + 1];
+    if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
+      set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
+      return E_INVALID;
+    }
+  }
+  FitFluxPlan plan;
+  DV_TRY(fitflux_plan(who, field_ptr, M, nb, p, &plan));
+  if (N == 0) return OK;
+  const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
+  const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + FitFluxBufs::bytes_per_stamp(nb);
+  const size_t per_field = felems * sizeof(double) + sizeof(int) + sizeof(long long);
+  DV_HIP(hipSetDevice(device));
+  FitFluxWork work;
+  if (budget == 0) {
+    size_t free_b = 0, total_b = 0;
+    DV_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t fixed = plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int);
+    budget = free_b / 2 > fixed ? free_b / 2 - fixed : 0;
+  }
+  // the chunks: consecutive fields, as many as fit (at least one)
+  std::vector<int> cuts{0};
+  size_t cmax_s = 0, cmax_f = 0;
+  for (int f = 0; f < M;) {
+    size_t bytes = 0;
+    int g = f;
+    while (g < M) {
+      const size_t add = (size_t)(field_ptr[g + 1] - field_ptr[g]) * per_stamp + per_field;
+      if (g > f && bytes + add > budget) break;
+      bytes += add;
+      ++g;
+    }
+    if (bytes > budget) {
+      set_error("%s: field %d with its %ld stamps needs %zu bytes of device memory, %zu are available", who, f,
+                (long)(field_ptr[f + 1] - field_ptr[f]), bytes, budget);
+      return E_NOMEM;
+    }
+    cmax_s = std::max(cmax_s, (size_t)(field_ptr[g] - field_ptr[f]));
+    cmax_f = std::max(cmax_f, (size_t)(g - f));
+    cuts.push_back(g);
+    f = g;
+  }
+  DevBuf<float> stamps;
+  DevBuf<double> data;
+  DevBuf<int> places, sf, fptr;
+  FitFluxBufs bufs;
+  DV_TRY(work.alloc(plan, (int64_t)cmax_f));
+  DV_TRY(stamps.alloc(cmax_s * stamp));
+  DV_TRY(places.alloc(cmax_s * 2));
+  DV_TRY(sf.alloc(cmax_s));
+  DV_TRY(fptr.alloc(cmax_f + 1));
+  DV_TRY(data.alloc(cmax_f * felems));
+  DV_TRY(bufs.alloc((int64_t)cmax_s, nb));
+  std::vector<int> sf_h, fptr_h;
+  StreamDrain drain(s);
+  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+    const int fa = cuts[k], fz = cuts[k + 1];          // fields fa .. fz - 1, their rows counted from the chunk's first
+    const int64_t r0 = field_ptr[fa], n = field_ptr[fz] - r0;
+    if (n == 0) continue;
+    fptr_h.assign((size_t)(fz - fa) + 1, 0);
+    sf_h.assign((size_t)n, 0);
+    for (int f = fa; f < fz; ++f) {
+      fptr_h[(size_t)(f - fa) + 1] = (int)(field_ptr[f + 1] - r0);
+      for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) sf_h[(size_t)(i - r0)] = f - fa;
+    }
+    DV_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)r0 * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(places, places_h + (size_t)r0 * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), fptr_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
+    DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h + (size_t)r0 * 2, fptr_h.data(), 0, fz - fa - 1, cs, nb, F,
+                           p, work, bufs.rows(), s, true));
+    const FitFluxRows at{out_h.scale + (size_t)r0 * nb, out_h.var + (size_t)r0 * nb, out_h.gram + (size_t)r0 * nb,
+                         out_h.proj + (size_t)r0 * nb, out_h.status + (size_t)r0 * nb};
+    DV_TRY(bufs.download(at, 0, n, nb, s));
+    DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next chunk
+  }
+  drain.dismiss();
+  return OK;
+}
+
+// step 1 of one field alone: host arrays in, G [nb][n][n] (the lower triangle, zeros above) and h [n][nb] out
+int scene_fit_flux_gram(const float* stamps_h, const int32_t* places_h, int64_t n, int cs, int nb, const double* data_h, int F,
+                        double* gram_h, double* proj_h, int device, hipStream_t s) {
+  const char* who = "dv_scene_fit_flux_gram";
+  if (n > FF_MAX_N) {
+    set_error("%s: field 0 has %ld galaxies, the dense fit takes at most %d per field", who, (long)n, FF_MAX_N);
+    return E_INVALID;
+  }
+  const size_t need = (size_t)nb * (size_t)std::max<int64_t>(n, 0) * (size_t)std::max<int64_t>(n, 0) * sizeof(double);
+  const FitFluxParams p{0.5, (int64_t)std::max<size_t>(need, 1)};
+  DV_TRY(fitflux_check(who, cs, nb, F, p));
+  if (n < 0 || (n > 0 && (!stamps_h || !places_h || !data_h || !gram_h || !proj_h))) {
+    set_error("%s: stamps, places, data_field, gram and proj must all be given", who);
+    return E_INVALID;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int pr = places_h[2 * i], pc = places_h[2 * i + 1];
+    if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
+      set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
+      return E_INVALID;
+    }
+  }
+  const int64_t field_ptr[2] = {0, n};
+  FitFluxPlan plan;
+  DV_TRY(fitflux_plan(who, field_ptr, 1, nb, p, &plan));
+  if (n == 0) return OK;
+  const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
+  DV_HIP(hipSetDevice(device));
+  DevBuf<float> stamps;
+  DevBuf<double> data, gram, proj;
+  DevBuf<int> places, sf, fptr;
+  FitFluxWork work;
+  DV_TRY(work.alloc(plan, 1));
+  DV_TRY(stamps.alloc((size_t)n * stamp));
+  DV_TRY(places.alloc((size_t)n * 2));
+  DV_TRY(sf.alloc((size_t)n));
+  DV_TRY(fptr.alloc(2));
+  DV_TRY(data.alloc(felems));
+  DV_TRY(gram.alloc((size_t)n * nb));
+  DV_TRY(proj.alloc((size_t)n * nb));
+  const int fptr_h[2] = {0, (int)n};
+  StreamDrain drain(s);
+  DV_HIP(hipMemcpyAsync(stamps, stamps_h, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(places, places_h, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemsetAsync(sf, 0, (size_t)n * sizeof(int), s));
+  DV_HIP(hipMemcpyAsync(fptr, fptr_h, sizeof(fptr_h), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(data, data_h, felems * sizeof(double), hipMemcpyHostToDevice, s));
+  const FitFluxRows rows{nullptr, nullptr, gram.get(), proj.get(), nullptr};
+  DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h, fptr_h, 0, 0, cs, nb, F, p, work, rows, s, false));
+  DV_HIP(hipMemcpyAsync(gram_h, work.scratch, need, hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(proj_h, proj, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipStreamSynchronize(s));
+  drain.dismiss();
+  return OK;
+}
+
+}  // namespace dv

@@ -470,6 +470,13 @@ class DeblendFieldBatch:
 
         return aperture_data_dtype(nb_of_bands, n_radii)
 
+    @staticmethod
+    def fit_flux_columns(nb_of_bands):
+        """What deblend_fields(measure=True, fit_flux=True) appends behind measure_columns: the recarray of fit_fluxes."""
+        from debvader_amd.measure.measurement import fit_flux_dtype
+
+        return fit_flux_dtype(nb_of_bands)
+
     def _psf_index(self, psf, psf_index, field_ptr):
         """(psf (K, ps, ps), index (N,)) of a deblend_fields(psf=...) call: one image for all galaxies, one per field (the
         index follows from field_ptr), or K images with the caller's index per galaxy - a flat (N,) array or a list of M
@@ -546,7 +553,7 @@ class DeblendFieldBatch:
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
                        measure=False, return_fields=True, measure_samples=0, blendedness=False,
                        psf=None, psf_index=None, apertures=None, flux_fractions=None, aperture_data=False,
-                       sky_sigma=None, optimise_positions=False):
+                       sky_sigma=None, fit_flux=False, optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -625,7 +632,17 @@ class DeblendFieldBatch:
         aper_data_flags, ap_flux_data_err, flux_auto_data_err; debvader_amd.measure.measurement.measure_apertures_on_fields
         describes them).  sky_sigma, (bands,) or (M, bands), is the standard deviation of the sky per pixel the two error
         columns are derived from; without it they are NaN.  The other columns and the fields are those of the same call
-        without it."""
+        without it.
+
+        fit_flux=True (with measure=True and on_device=True, with or without return_fields): the simultaneous flux fit of
+        the deblended models to the observed field (dv_infer_fields_measure_fit).  The mean stamps are
+        kept on the device, and once a field's composite is complete the amplitudes of all its galaxies are fitted to the
+        observed pixels at once, per band, the shapes held fixed; the recarrays gain fit_flux_columns (fit_scale, fit_var,
+        fit_gram, fit_proj, fit_status and the derived flux_fit = fit_scale * flux, fit_scale_alone, fit_independence,
+        fit_scale_err, flux_fit_err; debvader_amd.measure.measurement.fit_fluxes describes them).  sky_sigma, (bands,) or (M,
+        bands), is the standard deviation of the sky per pixel the two error columns are derived from; without it they are
+        NaN.  The other columns and the fields are those of the same call without it.  It is not available with psf,
+        apertures, blendedness, measure_samples, optimise_positions=True or epistemic_uncertainty_estimation=True."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
@@ -694,7 +711,34 @@ class DeblendFieldBatch:
         if aperture_data and not with_aper:
             raise ValueError("aperture_data=True needs apertures: it takes the apertures of the aperture photometry on the "
                              "observed field and the composited mean field (apertures=() for the Kron ellipse alone)")
-        if sky_sigma is not None and not aperture_data:
+        fit_flux = bool(fit_flux)
+        if fit_flux and not (measure and on_device):
+            raise ValueError("fit_flux=True needs measure=True and on_device=True: the fit scales the measured stamp fluxes and "
+                             "runs where the mean stamps and the observed fields lie in device memory "
+                             "(dv_infer_fields_measure_fit); on the default path use "
+                             "debvader_amd.measure.measurement.fit_fluxes on the returned stamps")
+        if fit_flux and with_psf:
+            raise ValueError("fit_flux=True cannot be combined with psf: the flux fit and the PSF correction are stages of two "
+                             "different measuring calls (dv_infer_fields_measure_fit, dv_infer_fields_measure_psf)")
+        if fit_flux and with_aper:
+            raise ValueError("fit_flux=True cannot be combined with apertures: the flux fit and the aperture photometry are "
+                             "stages of two different measuring calls (dv_infer_fields_measure_fit, "
+                             "dv_infer_fields_measure_aper)")
+        if fit_flux and blendedness:
+            raise ValueError("fit_flux=True cannot be combined with blendedness=True: the flux fit and the blendedness sums are "
+                             "stages of two different measuring calls (dv_infer_fields_measure_fit, "
+                             "dv_infer_fields_measure_blend)")
+        if fit_flux and int(measure_samples or 0):
+            raise ValueError("fit_flux=True cannot be combined with measure_samples: the flux fit is not a stage of the "
+                             "Monte-Carlo catalogue call (dv_infer_fields_measure_mc)")
+        if fit_flux and fit:
+            raise ValueError("fit_flux=True cannot be combined with optimise_positions=True: the flux fit is a stage of the "
+                             "plain measuring composite call only (dv_infer_fields_measure_fit), not of the position-fit call")
+        if fit_flux and mc:
+            raise ValueError("fit_flux=True cannot be combined with epistemic_uncertainty_estimation=True: the flux fit is a "
+                             "stage of the plain measuring composite call only (dv_infer_fields_measure_fit), not of the "
+                             "Monte-Carlo call")
+        if sky_sigma is not None and not aperture_data and not fit_flux:
             raise ValueError("sky_sigma is the sky noise of the data-flux errors of aperture_data=True: give aperture_data too")
         if sky_sigma is not None:
             from debvader_amd.measure.measurement import check_sky_sigma
@@ -779,6 +823,9 @@ class DeblendFieldBatch:
                     out = eng.infer_fields_measure_psf(self.field_images, starts, field_ptr, psf, psf_index,
                                                        places=places if return_fields else None, seed=seed,
                                                        return_fields=bool(return_fields))
+                elif fit_flux:
+                    out = eng.infer_fields_measure_fit(self.field_images, starts, field_ptr, places, seed=seed, band=band,
+                                                       return_fields=bool(return_fields))
                 elif aperture_data:
                     out = eng.infer_fields_measure_aper_data(self.field_images, starts, field_ptr, places, seed=seed, band=band,
                                                              radii=list(aper_par.radii)[:aper_par.n_radii],
@@ -856,6 +903,12 @@ class DeblendFieldBatch:
                                                out["auto_model_sum"], out["auto_data_sum"], out["auto_field_area"],
                                                out["ap_flux"], out["ap_area"], out["flux_auto"], out["kron"][:, 2], band=band,
                                                sky_sigma=sky_sigma, field_ptr=field_ptr)
+            if fit_flux:
+                from debvader_amd.measure.measurement import fit_flux_records
+
+                columns = columns + self.fit_flux_columns(nb)
+                cat_ff = fit_flux_records(out["fit_scale"], out["fit_var"], out["fit_gram"], out["fit_proj"], out["fit_status"],
+                                          out["flux"], sky_sigma=sky_sigma, field_ptr=field_ptr)
             cat = catalogue_records(out["flux"], out["flux_err"], out["shape"], out["iters"], out["status"]) if on_device \
                 else measure_stamps(out["loc"], out["scale"], ctx=self._ctx)
             # a stamp's pixel (row, col) is the field's pixel start + (row, col); distances count from pixel int(F / 2)
@@ -890,6 +943,9 @@ class DeblendFieldBatch:
                 if aperture_data:
                     for k in cat_ad.dtype.names:
                         rec[k] = cat_ad[k][lo:hi]
+                if fit_flux:
+                    for k in cat_ff.dtype.names:
+                        rec[k] = cat_ff[k][lo:hi]
             if on_device:
                 rec["mse_center"] = mse_center[lo:hi]
                 if mc:

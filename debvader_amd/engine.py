@@ -274,6 +274,26 @@ def _aperture_field_out(n, nb, par):
     return out, [None if K == 0 and k.startswith("ap_") else _dp(out[k]) for k in APERTURE_FIELD_KEYS]
 
 
+FIT_FLUX_KEYS = ("fit_scale", "fit_var", "fit_gram", "fit_proj", "fit_status")
+FIT_FLUX_MAX_N = 1024       # galaxies per field of the dense flux fit (DV_FIT_MAX_N)
+
+
+def fit_flux_params(min_pivot=1e-8, scratch_bytes=256 << 20) -> "_lib.DvFitFluxParams":
+    """The checked dv_fit_flux_params of the flux-fit calls (the library refuses the same)."""
+    if not (np.isfinite(min_pivot) and 0.0 < min_pivot < 1.0):
+        raise ValueError(f"min_pivot must lie strictly between 0 and 1 (got {min_pivot})")
+    if int(scratch_bytes) != scratch_bytes or int(scratch_bytes) < 1:
+        raise ValueError(f"scratch_bytes must be an integer >= 1 (got {scratch_bytes})")
+    return _lib.DvFitFluxParams(float(min_pivot), int(scratch_bytes))
+
+
+def _fit_flux_out(n, nb):
+    """The result dictionary of the flux fit and its pointers in the C-ABI's order."""
+    out = {k: np.zeros((n, nb), np.float64) for k in FIT_FLUX_KEYS[:4]}
+    out["fit_status"] = np.zeros((n, nb), np.int32)
+    return out, [_dp(out[k]) for k in FIT_FLUX_KEYS[:4]] + [_ip(out["fit_status"])]
+
+
 def check_measure_mc_args(samples, band, sigma0, tol, max_iter):
     """(samples, params) of scene_measure_mc: C-contiguous float32 sample stamps (S, N, cs, cs, bands), S >= 1."""
     samples = _f32c(samples)
@@ -823,6 +843,66 @@ class Context:
             check(lib.dv_scene_aperture_fields(self._h, _dp(shape), _ip(status), _ip(places),
                                                fp.ctypes.data_as(C.POINTER(C.c_int64)), _dp(kron), _ip(aper_status), n, cs, nb,
                                                _dp(model), _dp(data), M, model.shape[1], C.byref(par), *ptrs))
+        return out
+
+    FIT_INELIGIBLE, FIT_DROPPED = 4, 5                 # fit_status of scene_fit_flux beside 0 (fitted)
+
+    def scene_fit_flux(self, stamps, places, data_fields, field_ptr=None, min_pivot: float = 1e-8,
+                       scratch_bytes: int = 256 << 20) -> Dict[str, np.ndarray]:
+        """The simultaneous flux fit of the deblended models to the observed field on the GPU (dv_scene_fit_flux, DESIGN.md
+        section 7q): stamps (N, cs, cs, bands), the mean stamps taken as float32; places (N, 2), the field position (row, col)
+        of every stamp's top-left corner; data_fields (M, F, F, bands), the observed fields; field_ptr (M + 1,): stamps
+        field_ptr[m]:field_ptr[m + 1] lie in field m (None: one field holds them all).  Per field and band the amplitudes a
+        that minimise |D - sum a_i P_i|^2 over the pixels inside the field, the shapes P_i held fixed.  Returns, all (N,
+        bands): {"fit_scale": a; "fit_var": the diagonal of the inverse Gram matrix of the fitted galaxies; "fit_gram": G_ii
+        = sum P_i^2; "fit_proj": h_i = sum P_i D; "fit_status": 0 fitted, FIT_INELIGIBLE G_ii not positive (scale and var
+        NaN), FIT_DROPPED the galaxy cannot be told from earlier ones of its field - pivot <= min_pivot G_ii - and keeps the
+        network's amplitude (scale 1, var NaN)}.  A field of more than 1024 galaxies, or whose bands x n x n doubles exceed
+        scratch_bytes, is refused."""
+        stamps = np.ascontiguousarray(stamps, dtype=np.float32)
+        if stamps.ndim != 4 or stamps.shape[1] != stamps.shape[2]:
+            raise ValueError(f"expected square stamps (N, cs, cs, bands), got {stamps.shape}")
+        n, cs, nb = stamps.shape[0], stamps.shape[1], stamps.shape[3]
+        data = np.ascontiguousarray(data_fields, dtype=np.float64)
+        if data.ndim != 4 or data.shape[1] != data.shape[2] or data.shape[3] != nb:
+            raise ValueError(f"expected data fields (M, F, F, {nb}), got {data.shape}")
+        places = _i32_rows(places, "stamp placements")
+        if places.shape != (n, 2):
+            raise ValueError(f"expected places ({n}, 2), got {places.shape}")
+        M = data.shape[0]
+        if field_ptr is None:
+            if M != 1:
+                raise ValueError(f"field_ptr is needed with {M} fields")
+            field_ptr = [0, n]
+        fp = check_field_ptr(field_ptr, M, n)
+        par = fit_flux_params(min_pivot, scratch_bytes)
+        out, ptrs = _fit_flux_out(n, nb)
+        if n:
+            check(lib.dv_scene_fit_flux(self._h, _fp(stamps), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs, nb,
+                                        _dp(data), M, data.shape[1], C.byref(par), *ptrs))
+        return out
+
+    def scene_fit_flux_gram(self, stamps, places, data_field) -> Dict[str, np.ndarray]:
+        """Step 1 of scene_fit_flux for the galaxies of one field (dv_scene_fit_flux_gram): stamps (n, cs, cs, bands), places
+        (n, 2), data_field (F, F, bands).  Returns {"gram" (bands, n, n): G_ij = sum P_i P_j over the field pixels both
+        stamps cover at [b, i, j] for j <= i, 0.0 above the diagonal; "proj" (n, bands): h_i = sum P_i D} with the bits the
+        fit works on."""
+        stamps = np.ascontiguousarray(stamps, dtype=np.float32)
+        if stamps.ndim != 4 or stamps.shape[1] != stamps.shape[2]:
+            raise ValueError(f"expected square stamps (n, cs, cs, bands), got {stamps.shape}")
+        n, cs, nb = stamps.shape[0], stamps.shape[1], stamps.shape[3]
+        data = np.ascontiguousarray(data_field, dtype=np.float64)
+        if data.ndim != 3 or data.shape[0] != data.shape[1] or data.shape[2] != nb:
+            raise ValueError(f"expected one data field (F, F, {nb}), got {data.shape}")
+        places = _i32_rows(places, "stamp placements")
+        if places.shape != (n, 2):
+            raise ValueError(f"expected places ({n}, 2), got {places.shape}")
+        if n > FIT_FLUX_MAX_N:
+            raise ValueError(f"{n} galaxies in one field, the dense flux fit takes at most {FIT_FLUX_MAX_N}")
+        out = dict(gram=np.zeros((nb, n, n), np.float64), proj=np.zeros((n, nb), np.float64))
+        if n:
+            check(lib.dv_scene_fit_flux_gram(self._h, _fp(stamps), _ip(places), n, cs, nb, _dp(data), data.shape[0],
+                                             _dp(out["gram"]), _dp(out["proj"])))
         return out
 
     CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
@@ -1426,6 +1506,44 @@ class Engine:
                               **kw) -> Dict[str, np.ndarray]:
         """Context.scene_aperture_fields on this engine's GPU context."""
         return self.ctx.scene_aperture_fields(shape, status, places, kron, aper_status, model_fields, data_fields, **kw)
+
+    def infer_fields_measure_fit(self, fields, starts, field_ptr, places, seed=0, band: int = 2, sigma0: float = 3.0,
+                                 tol: float = 1e-10, max_iter: int = 200, min_pivot: float = 1e-8,
+                                 scratch_bytes: int = 256 << 20, return_fields=True, residual=True,
+                                 mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure() plus the simultaneous flux fit (dv_infer_fields_measure_fit): returns
+        its dictionary, bit for bit, plus scene_fit_flux's {"fit_scale", "fit_var", "fit_gram", "fit_proj", "fit_status"} -
+        the bits of scene_fit_flux on infer_fields_keep's mean stamps and the source fields.  The mean stamps of every chunk
+        are kept on the device and the fit runs once a field's composite is complete.  `places` is always needed, with
+        return_fields=False too."""
+        if places is None:
+            raise ValueError("places are needed for the flux fit, with return_fields=False too")
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places)
+        nb = fields.shape[3]
+        par = measure_params(band, sigma0, tol, max_iter, nb)
+        fpar = fit_flux_params(min_pivot, scratch_bytes)
+        if return_fields:
+            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
+        else:
+            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
+            ptrs = [None, None, None, _dp(out.get("mse_center"))]
+        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
+                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
+        ff, ff_ptrs = _fit_flux_out(N, nb)
+        out.update(ff)
+        check(lib.dv_infer_fields_measure_fit(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
+                                              _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"]),
+                                              C.byref(fpar), *ff_ptrs))
+        return out
+
+    def infer_cutouts_measure_fit(self, field, starts, places, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_fit() for one field (F, F, bands): the field-sized results under singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_fit(fields, starts, fp, places, seed=seed, **kw))
+
+    def scene_fit_flux(self, stamps, places, data_fields, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_fit_flux on this engine's GPU context."""
+        return self.ctx.scene_fit_flux(stamps, places, data_fields, **kw)
 
     def infer_fields_measure_mc(self, fields, starts, field_ptr, places=None, seed=0, mc_seed=0, nsamples=100, band: int = 2,
                                 sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, return_fields=True,

@@ -479,6 +479,106 @@ def measure_apertures_on_fields(catalogue, places, model_fields, data_fields=Non
                                  ap["auto_area"], band=band, sky_sigma=sky_sigma, field_ptr=field_ptr)
 
 
+FIT_STATUS_INELIGIBLE, FIT_STATUS_DROPPED = 4, 5      # fit_status of the flux fit beside 0 (fitted)
+
+
+def fit_flux_dtype(nb_of_bands):
+    """The columns of fit_fluxes' recarray: what the GPU fits, then what the host derives from it."""
+    nb = int(nb_of_bands)
+    return [("fit_scale", "<f8", (nb,)), ("fit_var", "<f8", (nb,)), ("fit_gram", "<f8", (nb,)), ("fit_proj", "<f8", (nb,)),
+            ("fit_status", "<i4", (nb,)), ("flux_fit", "<f8", (nb,)), ("fit_scale_alone", "<f8", (nb,)),
+            ("fit_independence", "<f8", (nb,)), ("fit_scale_err", "<f8", (nb,)), ("flux_fit_err", "<f8", (nb,))]
+
+
+def fit_flux_records(fit_scale, fit_var, fit_gram, fit_proj, fit_status, flux, sky_sigma=None, field_ptr=None):
+    """The recarray of fit_fluxes from the five arrays the engine returns (scene_fit_flux's, all (N, bands)) and the stamp
+    fluxes `flux` (N, bands) of the catalogue they go with.  Derived on the host: flux_fit = fit_scale * flux, the flux of
+    the galaxy with the amplitude the observed pixels ask for; fit_scale_alone = fit_proj / fit_gram, the amplitude with the
+    neighbours ignored (NaN where fit_gram is not positive); fit_independence = 1 / sqrt(fit_var * fit_gram), in (0, 1]: the
+    ratio of the error of the amplitude with the neighbours held fixed to its error in the joint fit, 1 for a galaxy that
+    overlaps nobody, small where two models can hardly be told apart.  With sky_sigma (bands,) or (M, bands), the per-pixel
+    standard deviation of the sky (field_ptr (M + 1,) gives every galaxy's field; None: one field): fit_scale_err = sky_sigma
+    sqrt(fit_var) and flux_fit_err = fit_scale_err |flux|; without it the two are NaN.  NaN follows the GPU's: an ineligible
+    galaxy (fit_status 4) is NaN in every derived column of that band; a dropped one (5) has fit_scale 1, so flux_fit = flux,
+    and NaN independence and errors."""
+    fit_scale = np.asarray(fit_scale, dtype=np.float64)
+    if fit_scale.ndim != 2:
+        raise ValueError(f"expected fit_scale (N, bands), got {fit_scale.shape}")
+    n, nb = fit_scale.shape
+    fit_var = np.asarray(fit_var, dtype=np.float64).reshape(n, nb)
+    fit_gram = np.asarray(fit_gram, dtype=np.float64).reshape(n, nb)
+    fit_proj = np.asarray(fit_proj, dtype=np.float64).reshape(n, nb)
+    fit_status = np.asarray(fit_status, dtype=np.int32).reshape(n, nb)
+    flux = np.asarray(flux, dtype=np.float64)
+    if flux.shape != (n, nb):
+        raise ValueError(f"expected flux ({n}, {nb}), got {flux.shape}")
+    rec = np.recarray((n,), dtype=fit_flux_dtype(nb))
+    rec["fit_scale"], rec["fit_var"], rec["fit_gram"], rec["fit_proj"] = fit_scale, fit_var, fit_gram, fit_proj
+    rec["fit_status"] = fit_status
+    with np.errstate(all="ignore"):
+        rec["flux_fit"] = fit_scale * flux
+        ok = fit_gram > 0                                     # (NaN > 0 is False)
+        rec["fit_scale_alone"] = np.where(ok, fit_proj / np.where(ok, fit_gram, 1.0), np.nan)
+        rec["fit_independence"] = 1.0 / np.sqrt(fit_var * fit_gram)
+        if sky_sigma is None:
+            rec["fit_scale_err"] = np.nan
+            rec["flux_fit_err"] = np.nan
+        else:
+            if field_ptr is None:
+                field_ptr = [0, n]
+            fp = np.asarray(field_ptr, dtype=np.int64).reshape(-1)
+            M = fp.shape[0] - 1
+            if M < 1 or fp[0] != 0 or fp[-1] != n or (np.diff(fp) < 0).any():
+                raise ValueError(f"field_ptr must start at 0, never decrease and end at the number of galaxies ({n})")
+            sky = check_sky_sigma(sky_sigma, M, nb)[np.repeat(np.arange(M), np.diff(fp))]          # (N, bands)
+            rec["fit_scale_err"] = sky * np.sqrt(fit_var)
+            rec["flux_fit_err"] = rec["fit_scale_err"] * np.abs(flux)
+    return rec
+
+
+def fit_fluxes(stamps_mean, places, data_fields, field_ptr=None, catalogue=None, sky_sigma=None, min_pivot=1e-8, ctx=None):
+    """Simultaneous flux fit of N deblended galaxies to the observed fields on the GPU: the shapes of
+    the galaxies of a field are held fixed at the network's mean stamps and all their amplitudes are fitted to the observed
+    pixels at once, per band, by linear least squares - the flux re-fit of the SDSS deblender, the Tractor and scarlet.  A bias
+    of the network on any member of a blend does not bias the fitted fluxes of the others.
+
+    parameters:
+        stamps_mean: the network's mean stamps, (N, cutout_size, cutout_size, bands)
+        places: (N, 2), the field position (row, col) of every stamp's top-left corner - where the stamp was composited
+        data_fields: (M, F, F, bands), the observed fields; (F, F, bands) for one field
+        field_ptr: (M + 1,), stamps field_ptr[m]:field_ptr[m + 1] lie in field m; None: one field holds them all
+        catalogue: the measure_stamps recarray of the galaxies (its flux is read); None: the stamp flux is summed here, the
+            float64 sum of every band of stamps_mean
+        sky_sigma: (bands,) or (M, bands), the standard deviation of the sky noise per pixel; None: the error columns are NaN
+        min_pivot: the relative Cholesky pivot under which a galaxy is dropped from the fit, in (0, 1)
+        ctx: the engine context to run on (None: the default context)
+    returns a np.recarray with, per galaxy and band: fit_scale, fit_var, fit_gram, fit_proj, fit_status (scene_fit_flux
+    describes them) and, derived on the host, flux_fit, fit_scale_alone, fit_independence, fit_scale_err and flux_fit_err
+    (fit_flux_records).  fit_status FIT_STATUS_INELIGIBLE: the stamp is zero or wholly outside the field in that band;
+    FIT_STATUS_DROPPED: the galaxy cannot be told from the earlier galaxies of its field and keeps the network's amplitude.
+    """
+    data = np.asarray(data_fields, dtype=np.float64)
+    if data.ndim == 3:
+        data = data[None]
+    M = data.shape[0]
+    if data.ndim == 4 and sky_sigma is not None:
+        check_sky_sigma(sky_sigma, M, data.shape[-1])                    # (ValueError before any GPU work)
+    stamps = np.asarray(stamps_mean, dtype=np.float32)
+    if field_ptr is None and M == 1:
+        field_ptr = [0, stamps.shape[0]]
+    if catalogue is None:
+        flux = stamps.sum(axis=(1, 2), dtype=np.float64) if stamps.ndim == 4 else None
+    else:
+        if "flux" not in catalogue.dtype.names:
+            raise ValueError("the catalogue lacks the column flux: fit_fluxes takes the measure_stamps recarray of the galaxies")
+        flux = np.asarray(catalogue["flux"], dtype=np.float64)
+    if ctx is None:
+        ctx = E.default_context()
+    out = ctx.scene_fit_flux(stamps, places, data, field_ptr=field_ptr, min_pivot=min_pivot)
+    return fit_flux_records(out["fit_scale"], out["fit_var"], out["fit_gram"], out["fit_proj"], out["fit_status"], flux,
+                            sky_sigma=sky_sigma, field_ptr=field_ptr)
+
+
 def measure_blendedness(stamps_mean, catalogue, places, model_fields, data_fields=None, field_ptr=None, band=2, ctx=None):
     """Blendedness of N deblended galaxies on the GPU.
 

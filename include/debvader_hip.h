@@ -651,6 +651,62 @@ int dv_infer_fields_measure_aper_data(dv_model* m, const double* fields, int32_t
                                       double* ap_field_area, double* auto_model_sum, double* auto_data_sum,
                                       double* auto_field_area);
 
+/* ---- simultaneous flux fit of the deblended models to the observed field ----
+ * Every flux above takes the network's amplitudes on trust, or corrects one galaxy while its neighbours stay at theirs.  Here
+ * the shapes are held fixed and all the amplitudes of a field are fitted to the observed pixels at once, per band: linear
+ * least squares, float64 throughout, every product and every sum rounded on its own.  Per field m with galaxies i = 0 .. n - 1
+ * in object order: P_i the mean stamp [cs][cs][nb] (float32, widened), (pr_i, pc_i) = places[i], D = data_fields[m]
+ * [F][F][nb].  The pixels of i are the stamp pixels whose field pixel lies inside the field - the pixels the composite keeps.
+ * Per band b, independently:
+ *   1. G_ij = sum P_i P_j over the field pixels both stamps cover, exactly 0.0 where the two clipped rectangles do not
+ *      intersect; h_i = sum P_i D over the pixels of i.  Each sum is one fixed-order workgroup reduction.
+ *   2. A galaxy whose G_ii is not finite or not positive gets fit_status 4 (DV_FIT_INELIGIBLE) in this band: fit_scale and
+ *      fit_var NaN, not part of the system.
+ *   3. Cholesky factorisation of G over the eligible galaxies in object order.  At column k the pivot is d_k = G_kk -
+ *      sum_{j < k, kept} L_kj^2; d_k <= min_pivot G_kk drops galaxy k, fit_status 5 (DV_FIT_DROPPED).  A dropped column is
+ *      never applied to the others: the variable leaves the system.  Of two models that cannot be told apart the one dropped
+ *      is always the later one in object order.
+ *   4. A dropped galaxy keeps the network's amplitude: h'_i = h_i - sum_{k dropped} G_ik; it reports fit_scale 1, fit_var NaN.
+ *   5. G_kept a = h' by the two triangular solves.  fit_scale = a; fit_var_i = (G_kept^-1)_ii, the sum of squares of column i
+ *      of L^-1 (times the sky variance per pixel it is the variance of fit_scale); fit_gram = G_ii and fit_proj = h_i are
+ *      given for every galaxy.  Amplitudes are not clipped: a linear fit may return a negative one.  fit_status 0: fitted.
+ * All five outputs are [N][nb].  A field's rows have the same bits wherever the field sits in a batch and when it is alone.
+ * The Gram matrices of a field are dense, nb n n doubles in a scratch of at most params->scratch_bytes that the fields go
+ * through in sub-ranges (no bit depends on the split); a field of more than DV_FIT_MAX_N galaxies is refused.
+ * dv_scene_fit_flux: host arrays; stamps [N][cs][cs][nb] float32, places [N][2], field_ptr [M + 1] (stamps field_ptr[m] ..
+ * field_ptr[m + 1] lie in field m), data_fields [M][F][F][nb].  Whole fields at a time, chunked against free device memory.
+ * dv_infer_fields_measure_fit: dv_infer_fields_measure (same arguments, same bits in every output it shares with it) plus
+ * the params and the five outputs: the mean stamps of every chunk are kept in device memory, and once a field's composite is
+ * complete the fit runs on them, the placements and the source field where they lie.  The outputs have the bits of
+ * dv_scene_fit_flux on dv_infer_fields_keep's mean stamps and the source fields.  places is always needed, with and without
+ * the three result fields.
+ * Refused before any GPU work (DV_E_INVALID, the engine stays usable): what dv_scene_blend refuses about field_ptr and the
+ * placements; nb above 16; a missing array; min_pivot outside (0, 1); scratch_bytes < 1; a field of more than DV_FIT_MAX_N
+ * galaxies and a field whose nb n n doubles exceed scratch_bytes - both messages name the field and its count. */
+#define DV_FIT_MAX_N 1024
+#define DV_FIT_INELIGIBLE 4
+#define DV_FIT_DROPPED 5
+typedef struct dv_fit_flux_params {
+  double min_pivot;        /* relative pivot under which a galaxy is dropped; default 1e-8 */
+  int64_t scratch_bytes;   /* device memory for the dense Gram matrices; default 256 MiB */
+} dv_fit_flux_params;
+int dv_fit_flux_params_default(dv_fit_flux_params* p);
+int dv_scene_fit_flux(dv_ctx* ctx, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs,
+                      int32_t nb, const double* data_fields, int32_t M, int32_t F, const dv_fit_flux_params* params,
+                      double* fit_scale, double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status);
+/* dv_scene_fit_flux_gram: step 1 alone for the n galaxies of ONE field, for a caller that wants the whole normal matrix (the
+ * covariance between neighbours is sky_sigma^2 times the inverse of its kept part) - gram [nb][n][n], G_ij at [b][i][j] for
+ * j <= i and 0.0 above the diagonal, proj [n][nb] = h.  Same sums, same bits as inside dv_scene_fit_flux.  Refuses what it
+ * refuses, n above DV_FIT_MAX_N included. */
+int dv_scene_fit_flux_gram(dv_ctx* ctx, const float* stamps, const int32_t* places, int64_t n, int32_t cs, int32_t nb,
+                           const double* data_field, int32_t F, double* gram, double* proj);
+int dv_infer_fields_measure_fit(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                int32_t* iters, int32_t* status, const dv_fit_flux_params* fit, double* fit_scale,
+                                double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status);
+
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)
  * keeps per field, in device memory, `work` (what the next pass detects on and cuts from, at first the field), `final`

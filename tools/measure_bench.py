@@ -71,6 +71,17 @@ the same build and box, in --apertures' protocol -
 
 With --profile-one: warm up, one fp32 call (c), exit.
 
+--fit-flux: what the simultaneous flux fit costs, on the same build and box, in --aperture-data's
+protocol (warm-up, then --repeat alternating runs, median and spread) -
+
+    (a) catalogue          :  the catalogue-only call as above: the baseline
+    (b) catalogue+fit-flux :  the same with fit_flux=True: the mean stamps are kept on the device and every field's amplitudes
+                              are fitted to its observed pixels once its composite is complete
+
+    python tools/measure_bench.py --fit-flux [--fields 1024] [--size 259] [--repeat 5]
+
+With --profile-one: warm up, one fp32 call (b), exit.
+
 The cost is reported, not gated.
 """
 import argparse
@@ -213,6 +224,62 @@ def main_blend(a):
         spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
         print(f"{dtype} catalogue+blend / catalogue {tb / tc:.3f}: {1e3 * (tb - tc):+.1f} ms for {n} galaxies "
               f"(spreads {spread(times['catalogue']):.3f} and {spread(times['catalogue+blend']):.3f})")
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
+def main_fit_flux(a):
+    rng = np.random.default_rng(0)
+    F, M = a.size, a.fields
+    base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
+    fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    quiet = io.StringIO()
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "fit_flux": True}
+    dists = None
+    for dtype in a.dtypes.split(","):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections, at most {max(len(d) for d in dists)} "
+                  f"per field; max_batch {a.max_batch}")
+        seen = []
+
+        def with_fit():
+            res = DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=True, measure=True, return_fields=False,
+                                                                fit_flux=True)
+            seen[:] = [np.concatenate([r["fit_status"] for r in res]), np.concatenate([r["fit_independence"] for r in res])]
+            return sum(len(r) for r in res)
+
+        legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False),
+                "catalogue+fit-flux": with_fit}
+        with redirect_stdout(quiet):
+            for fn in legs.values():           # warm-up
+                fn()
+            if a.profile_one:
+                with_fit()
+                net._core.engine.close()
+                return
+            times = {k: [] for k in legs}
+            n = 0
+            for _ in range(a.repeat):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    n = fn()
+                    times[k].append(time.perf_counter() - t0)
+        counts = np.bincount(seen[0].ravel(), minlength=6).tolist()
+        result[dtype] = {"stamps": n, "fit_status": counts}
+        for k in legs:
+            t = np.array(times[k])
+            print(_row(f"{dtype} {k}", t, n, M))
+            result[dtype][k.replace("+", "_").replace("-", "_") + "_ms"] = [round(1e3 * x, 2) for x in t]
+        tc, tf = (float(np.median(times[k])) for k in legs)
+        spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
+        ind = seen[1][np.isfinite(seen[1])]
+        print(f"{dtype} catalogue+fit-flux / catalogue {tf / tc:.3f}: {1e3 * (tf - tc):+.1f} ms for {n} galaxies, "
+              f"{1e6 * (tf - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times['catalogue']):.3f} and "
+              f"{spread(times['catalogue+fit-flux']):.3f}); fit_status 0 .. 5 over galaxies x bands: {counts}; median "
+              f"fit_independence {float(np.median(ind)) if ind.size else float('nan'):.3f}")
         net._core.engine.close()
     print(json.dumps(result))
 
@@ -369,7 +436,10 @@ def main():
     ap.add_argument("--psf", action="store_true")
     ap.add_argument("--apertures", action="store_true")
     ap.add_argument("--aperture-data", action="store_true")
+    ap.add_argument("--fit-flux", action="store_true")
     a = ap.parse_args()
+    if a.fit_flux:
+        return main_fit_flux(a)
     if a.aperture_data:
         return main_apertures(a, data=True)
     if a.apertures:
