@@ -92,6 +92,18 @@ _i64 = C.POINTER(C.c_int64)
 # dv_chunk_fn of dv_infer_cutouts_stream: int (*)(void* user, int64 first, int32 count, const float* mean, const float* stddev)
 CHUNK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float))
 
+# the arguments every dv_infer_fields_measure* call shares: the model to seed, then params, the three result fields,
+# mse_center and the five catalogue rows; the Monte-Carlo call has mc_seed and nsamples between the two, and the outputs of
+# an extra follow
+_FIELDS_IN = [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64]
+_MEASURE_OUT = [C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32]
+_APER_OUT = [C.POINTER(DvApertureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32]
+
+
+def _measure_sig(*extra, between=()):
+    return C.c_int, _FIELDS_IN + list(between) + _MEASURE_OUT + list(extra)
+
+
 SIGNATURES = {
     "dv_version": (C.c_int, []),
     "dv_build_kind": (C.c_int, []),
@@ -171,41 +183,28 @@ SIGNATURES = {
     "dv_measure_params_default": (C.c_int, [C.POINTER(DvMeasureParams)]),
     "dv_scene_measure": (C.c_int, [_p, _f, _f, C.c_int64, C.c_int32, C.c_int32, C.POINTER(DvMeasureParams), _d, _d, _d, _i32,
                                    _i32]),
-    "dv_infer_fields_measure": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
-                                          C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32]),
+    "dv_infer_fields_measure": _measure_sig(),
     "dv_scene_measure_mc": (C.c_int, [_p, _f, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(DvMeasureParams), _d, _d, _d,
                                       _d, _i32, _d, _d, _i32]),
-    "dv_infer_fields_measure_mc": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
-                                             C.c_uint64, C.c_int32, C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d,
-                                             _i32, _i32, _d, _d, _d, _d, _i32, _d, _d, _i32]),
+    "dv_infer_fields_measure_mc": _measure_sig(_d, _d, _d, _d, _i32, _d, _d, _i32, between=(C.c_uint64, C.c_int32)),
     "dv_scene_blend": (C.c_int, [_p, _f, _d, _i32, _i32, _i64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _d, _d, C.c_int32,
                                  C.c_int32, _d, _i32]),
-    "dv_infer_fields_measure_blend": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
-                                                C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32, _d, _i32]),
+    "dv_infer_fields_measure_blend": _measure_sig(_d, _i32),
     "dv_scene_regauss": (C.c_int, [_p, _f, _d, _i32, _i32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _d, C.c_int32, C.c_int32,
                                    C.c_double, C.c_double, C.c_int32, _d, _i32, _i32, _d, _d, _i32, _i32]),
-    "dv_infer_fields_measure_psf": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
-                                              C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32, _d, C.c_int32,
-                                              C.c_int32, _i32, C.c_double, _d, _i32, _i32, _d, _d, _i32, _i32]),
+    "dv_infer_fields_measure_psf": _measure_sig(_d, C.c_int32, C.c_int32, _i32, C.c_double, _d, _i32, _i32, _d, _d, _i32, _i32),
     "dv_aperture_params_default": (C.c_int, [C.POINTER(DvApertureParams)]),
     "dv_scene_aperture": (C.c_int, [_p, _f, _f, _d, _i32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvApertureParams),
                                     _d, _d, _d, _d, _d, _d, _d, _i32, _i32]),
-    "dv_infer_fields_measure_aper": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
-                                               C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
-                                               C.POINTER(DvApertureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32]),
+    "dv_infer_fields_measure_aper": _measure_sig(*_APER_OUT),
     "dv_scene_aperture_fields": (C.c_int, [_p, _d, _i32, _i32, _i64, _d, _i32, C.c_int64, C.c_int32, C.c_int32, _d, _d, C.c_int32,
                                            C.c_int32, C.POINTER(DvApertureParams), _d, _d, _d, _d, _d, _d]),
-    "dv_infer_fields_measure_aper_data": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64,
-                                                    C.c_uint64, C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
-                                                    C.POINTER(DvApertureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
-                                                    _d, _d, _d, _d, _d, _d]),
+    "dv_infer_fields_measure_aper_data": _measure_sig(*_APER_OUT, _d, _d, _d, _d, _d, _d),
     "dv_fit_flux_params_default": (C.c_int, [C.POINTER(DvFitFluxParams)]),
     "dv_scene_fit_flux": (C.c_int, [_p, _f, _i32, _i64, C.c_int64, C.c_int32, C.c_int32, _d, C.c_int32, C.c_int32,
                                     C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _i32]),
     "dv_scene_fit_flux_gram": (C.c_int, [_p, _f, _i32, C.c_int64, C.c_int32, C.c_int32, _d, C.c_int32, _d, _d]),
-    "dv_infer_fields_measure_fit": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, _i64, C.c_int64, C.c_uint64,
-                                              C.POINTER(DvMeasureParams), _d, _d, _d, _d, _d, _d, _d, _i32, _i32,
-                                              C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _i32]),
+    "dv_infer_fields_measure_fit": _measure_sig(C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _i32),
     "dv_field_set_open": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),

@@ -22,6 +22,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <set>
 #include <vector>
 #ifdef DV_DEBUG_EXPORTS
@@ -4785,9 +4786,8 @@ int dv_infer_f64(dv_model* m, const double* x, int64_t N, const float* eps, uint
 // The single-field calls (dv_infer_cutouts*) are this with M = 1.
 struct FieldsOut {                  // result fields of dv_infer_fields_composite, host [M][F][F][nb]; null otherwise
   double *mean = nullptr, *stddev = nullptr, *residual = nullptr, *mse = nullptr;
-  const int32_t* places = nullptr;
   double *epistemic = nullptr, *eps_norm = nullptr;   // dv_infer_fields_mc_composite: [M][F][F][nb] and [N]
-  // dv_infer_fields_fit_composite: dist instead of places, the fit's parameters and per-galaxy results (host [N])
+  // dv_infer_fields_fit_composite: dist instead of the request's places, the fit's parameters and per-galaxy results (host [N])
   const double* dist = nullptr;
   double bound = 0.0;
   int max_iter = 0;
@@ -4805,6 +4805,7 @@ struct MeasureOut {                 // the catalogue of dv_infer_fields_measure,
 struct MeasureMcOut {               // the Monte-Carlo catalogue of dv_infer_fields_measure_mc, host, rows = global stamp numbers
   McState st{};                     // the per-sample rows given together or not at all
   int nsamples = 0;
+  uint64_t seed = 0;                // of the decodes (the pass itself draws from the job's seed)
 };
 
 // the refusals every field-sourced call takes before any GPU work, and the two tables it works from: sfield[i] = the field
@@ -5237,26 +5238,42 @@ struct FitFluxStage {               // the simultaneous flux fit of every field'
   }
 };
 
+// What a many-field call wants back, beside what its PipeJob streams to the host: each part is there or not.
+struct FieldsRequest {
+  std::optional<FieldsOut> fields;              // the composited result fields
+  std::optional<MeasureOut> cat;                // the catalogue
+  // the extras hang off the catalogue - they read its parameters or its device rows - and are given only with `cat`
+  std::optional<MeasureMcOut> mc;
+  std::optional<BlendOut> blend;
+  std::optional<RegaussOut> regauss;
+  std::optional<ApertureOut> aper;
+  std::optional<ApertureFieldOut> aper_field;   // reads the aperture rows: only with `aper`
+  std::optional<FitFluxOut> fit_flux;
+  // host [N][2], where every stamp lies in its field.  Read when the call composites - result fields without a position fit,
+  // or a stage at the completed-field seam (blend, aper_field, fit_flux), with or without result fields - and not otherwise
+  const int32_t* places = nullptr;
+};
+
 // j: the host side of the job - fields, starts, seed, the host outputs, consumer and Monte-Carlo stage the caller wants;
 // the device side and the rows are filled in here
 static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
-                             const FieldsOut* fo = nullptr, const MeasureOut* mo = nullptr,
-                             const MeasureMcOut* mco = nullptr, const BlendOut* bo = nullptr,
-                             const int32_t* blend_places = nullptr, const RegaussOut* ro = nullptr,
-                             const ApertureOut* ao = nullptr, const ApertureFieldOut* afo = nullptr,
-                             const FitFluxOut* ffo = nullptr) {
+                             const FieldsRequest& rq) {
   // check
+  if (((rq.mc || rq.blend || rq.regauss || rq.aper || rq.aper_field || rq.fit_flux) && !rq.cat) || (rq.aper_field && !rq.aper)) {
+    set_error("%s: the extras of a catalogue go with the catalogue, the apertures on the fields with the aperture rows", who);
+    return DV_E_INVALID;
+  }
   const double* fields = j.fields;
   const int F = j.F, nb = j.nb;
   if (M > 0 && !fields) return DV_E_INVALID;
   std::vector<int32_t> sfield;
   std::vector<int> fptr32;
-  const int32_t* places = fo ? fo->places : blend_places;   // (blend_places: the catalogue-only form of a call that composites)
+  const int32_t* places = rq.fields || rq.blend || rq.aper_field || rq.fit_flux ? rq.places : nullptr;
   DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, j.starts, places, sfield, fptr32));
   const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
   FitFluxPlan ffplan;
-  if (ffo) DV_TRY(fitflux_plan(who, field_ptr, M, nb, ffo->par, &ffplan));   // (before anything is written or queued)
-  if (fo) fields_write_empty(*fo, fields, M, field_ptr, felems);
+  if (rq.fit_flux) DV_TRY(fitflux_plan(who, field_ptr, M, nb, rq.fit_flux->par, &ffplan));   // (before anything is written or queued)
+  if (rq.fields) fields_write_empty(*rq.fields, fields, M, field_ptr, felems);
   if (N == 0) return DV_OK;
   TinyCall tiny(m, N);
   DV_HIP(hipSetDevice(m->ctx->device));
@@ -5264,41 +5281,41 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   const int chunk = infer_chunk(m, N);
   const FieldsCall c{N, (N + chunk - 1) / chunk, F, nb, m->A.H, chunk, s};
   InferPipe* pipe = nullptr;
-  DV_TRY(pipe_get(m, chunk, &pipe, fo == nullptr && mo == nullptr));   // before the budget below: the pipeline's buffers come first
+  DV_TRY(pipe_get(m, chunk, &pipe, !rq.fields && !rq.cat));   // before the budget below: the pipeline's buffers come first
   // plan the groups: fields per group = what free memory holds beside the per-stamp tables and the stages' own arrays
-  const bool fitting = fo && fo->dist;
-  double* mse_h = fo ? fo->mse : mo ? mo->mse : nullptr;
+  const bool fitting = rq.fields && rq.fields->dist;
+  double* mse_h = rq.fields ? rq.fields->mse : rq.cat ? rq.cat->mse : nullptr;
   DevBuf<double> fdev;                                // the resident group of source fields
   StampTables tab;
   CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs; ApertureStage aps; MeanFieldStage mfs; ApertureFieldStage afs; FitFluxStage ffs;   // (a stage that does not run stays empty)
   ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
-  if (fitting) DV_TRY(fit.make_plan(*fo, c, sfield.data()));
+  if (fitting) DV_TRY(fit.make_plan(*rq.fields, c, sfield.data()));
   size_t per_field = fb, reserve = StampTables::bytes((size_t)N, (size_t)M);
-  if (fo) {
-    per_field += CompositeStage::bytes_per_field(*fo, fb) + MonteCarloStage::bytes_per_field(*fo, fb);
-    reserve += (size_t)N * MonteCarloStage::bytes_per_stamp(*fo);
+  if (rq.fields) {
+    per_field += CompositeStage::bytes_per_field(*rq.fields, fb) + MonteCarloStage::bytes_per_field(*rq.fields, fb);
+    reserve += (size_t)N * MonteCarloStage::bytes_per_stamp(*rq.fields);
   }
   if (fitting) {
     per_field += FitStage::bytes_per_field(F);
     reserve += fit.bytes_fixed(c);
   }
-  if (mo) reserve += (size_t)N * CatalogueStage::bytes_per_stamp(nb);
-  const bool keep_samples = mco && mco->st.sample_flux;
-  if (mco)
-    reserve += (size_t)N * CatalogueMcStage::bytes_per_stamp(nb, mco->nsamples, keep_samples) + CatalogueMcStage::bytes_fixed(m->Bc, nb);
-  const bool own_mean = (bo || afo) && !fo;           // a stage reads the completed composite and no composite stage runs
+  if (rq.cat) reserve += (size_t)N * CatalogueStage::bytes_per_stamp(nb);
+  const bool keep_samples = rq.mc && rq.mc->st.sample_flux;
+  if (rq.mc)
+    reserve += (size_t)N * CatalogueMcStage::bytes_per_stamp(nb, rq.mc->nsamples, keep_samples) + CatalogueMcStage::bytes_fixed(m->Bc, nb);
+  const bool own_mean = (rq.blend || rq.aper_field) && !rq.fields;   // a stage reads the completed composite and no composite stage runs
   per_field += MeanFieldStage::bytes_per_field(own_mean, fb);
-  if (bo) reserve += (size_t)N * BlendStage::bytes_per_stamp();
-  if (ro) reserve += (size_t)N * RegaussStage::bytes_per_stamp() + RegaussStage::bytes_fixed(*ro);
-  if (ao) reserve += (size_t)N * ApertureStage::bytes_per_stamp(*ao, nb);
-  if (afo) reserve += (size_t)N * ApertureFieldStage::bytes_per_stamp(*ao, nb);
-  if (ffo) reserve += (size_t)N * FitFluxStage::bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M);
+  if (rq.blend) reserve += (size_t)N * BlendStage::bytes_per_stamp();
+  if (rq.regauss) reserve += (size_t)N * RegaussStage::bytes_per_stamp() + RegaussStage::bytes_fixed(*rq.regauss);
+  if (rq.aper) reserve += (size_t)N * ApertureStage::bytes_per_stamp(*rq.aper, nb);
+  if (rq.aper_field) reserve += (size_t)N * ApertureFieldStage::bytes_per_stamp(*rq.aper, nb);
+  if (rq.fit_flux) reserve += (size_t)N * FitFluxStage::bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M);
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
   if (G < 1) {
     set_error("%s: one %d-pixel field needs %zu bytes of device memory (field%s), %zu are available for fields", who, F,
-              per_field, fo ? " and its result fields" : own_mean ? " and its device-side mean field" : "", budget);
+              per_field, rq.fields ? " and its result fields" : own_mean ? " and its device-side mean field" : "", budget);
     return DV_E_NOMEM;
   }
   std::vector<FieldGroup> groups;
@@ -5308,41 +5325,41 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   StreamDrain drain(s, pipe->s_in, pipe->s_out);
   const size_t gelems = (size_t)gmax * felems;
   DV_TRY(fdev.alloc(gelems));
-  if (fo) {
-    DV_TRY(comp.alloc(*fo, gelems));
-    DV_TRY(mc.alloc(*fo, gelems, N));
+  if (rq.fields) {
+    DV_TRY(comp.alloc(*rq.fields, gelems));
+    DV_TRY(mc.alloc(*rq.fields, gelems, N));
     comp.bind(j.sinks);
     mc.bind(j.sinks);
   }
-  if (mo) {
+  if (rq.cat) {
     DV_TRY(cat.alloc(N, nb));
-    cat.bind(j.ms, mo->par);
+    cat.bind(j.ms, rq.cat->par);
   }
-  if (mco) {
-    DV_TRY(catmc.alloc(N, nb, mco->nsamples, keep_samples, m->Bc));
-    catmc.bind(j.mcm, mo->par);
+  if (rq.mc) {
+    DV_TRY(catmc.alloc(N, nb, rq.mc->nsamples, keep_samples, m->Bc));
+    catmc.bind(j.mcm, rq.cat->par);
   }
   DV_TRY(mfs.alloc(own_mean, gelems));
   mfs.bind(j.mf);
-  if (bo) {
+  if (rq.blend) {
     DV_TRY(bls.alloc(N));
     bls.bind(j.bl);
   }
-  if (ro) {
-    DV_TRY(rgs.alloc(*ro, N, mo->par, s));
-    rgs.bind(j.rg, *ro);
+  if (rq.regauss) {
+    DV_TRY(rgs.alloc(*rq.regauss, N, rq.cat->par, s));
+    rgs.bind(j.rg, *rq.regauss);
   }
-  if (ao) {
-    DV_TRY(aps.alloc(*ao, N, nb));
-    aps.bind(j.ap, *ao);
+  if (rq.aper) {
+    DV_TRY(aps.alloc(*rq.aper, N, nb));
+    aps.bind(j.ap, *rq.aper);
   }
-  if (afo) DV_TRY(afs.alloc(*ao, N, nb));
-  if (ffo) {
+  if (rq.aper_field) DV_TRY(afs.alloc(*rq.aper, N, nb));
+  if (rq.fit_flux) {
     DV_TRY(ffs.alloc(ffplan, N, M, c.cs, nb));
     ffs.bind(j.ff);
   }
   if (fitting) {
-    DV_TRY(fit.alloc(*fo, c, gmax, groups));
+    DV_TRY(fit.alloc(*rq.fields, c, gmax, groups));
     fit.bind(j.fit);
   }
   DV_TRY(tab.upload(N, M, j.starts, !fitting ? places : nullptr, sfield.data(), fptr32.data(), mse_h != nullptr, 0, s));
@@ -5370,29 +5387,29 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     j.row0 = g.k0 * chunk;
     j.N = std::min<int64_t>(N, g.k1 * chunk) - j.row0;
     DV_TRY(infer_pipelined(m, j));
-    if (bo || afo || ffo) {
+    if (rq.blend || rq.aper_field || rq.fit_flux) {
       // the completed-field seam: every field of the group has all its stamps composited now, but for a last field that
       // the next group goes on with (it is complete there); the parent sums and the field apertures of the complete fields'
       // galaxies - one contiguous range of rows - read the mean field, the source field and the rows where they lie
       const int fa = g.f0, fz = gi + 1 < groups.size() && groups[gi + 1].f0 == g.f1 ? g.f1 - 1 : g.f1;
       if (fz >= fa) {
         const int r0 = fptr32[fa], r1 = fptr32[fz + 1];
-        const double* mean_f = fo ? comp.mean.dev.get() : mfs.mean.get();
-        if (bo)
+        const double* mean_f = rq.fields ? comp.mean.dev.get() : mfs.mean.get();
+        if (rq.blend)
           DV_TRY(launch_blend_parent(cat.shape.get() + (size_t)r0 * 5, cat.status.get() + r0, tab.places.get() + 2 * (size_t)r0,
-                                     tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, mo->par.band, F, mean_f, fdev,
+                                     tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, rq.cat->par.band, F, mean_f, fdev,
                                      bls.blend.get() + (size_t)r0 * 4, s));
-        if (afo)
+        if (rq.aper_field)
           DV_TRY(launch_aperture_field(cat.shape.get() + (size_t)r0 * 5, cat.status.get() + r0,
                                        aps.bufs.kron.get() + (size_t)r0 * 3, aps.bufs.status.get() + r0,
                                        tab.places.get() + 2 * (size_t)r0, tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, F,
-                                       mean_f, fdev, ao->par, aperture_field_rows_at(afs.bufs.rows(), r0, ao->par, nb), s));
-        if (ffo)                       // (the stamp store, the placements and the tables count from stamp 0 of the call)
+                                       mean_f, fdev, rq.aper->par, aperture_field_rows_at(afs.bufs.rows(), r0, rq.aper->par, nb), s));
+        if (rq.fit_flux)               // (the stamp store, the placements and the tables count from stamp 0 of the call)
           DV_TRY(launch_fit_flux(ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, places, fptr32.data(), fa, fz, c.cs,
-                                 nb, F, ffo->par, ffs.work, ffs.bufs.rows(), s));
+                                 nb, F, rq.fit_flux->par, ffs.work, ffs.bufs.rows(), s));
       }
     }
-    if (fo) {
+    if (rq.fields) {
       for (ResultStack* r : stacks) DV_TRY(r->end(ng * fb, goff, s));
       DV_HIP(hipStreamSynchronize(s));
     }
@@ -5404,15 +5421,15 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     DV_HIP(hipMemcpyAsync(mse_h, tab.mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
     DV_HIP(hipStreamSynchronize(s));
   }
-  if (mo) DV_TRY(cat.download(*mo, N, nb, s));
-  if (mco) DV_TRY(catmc.download(*mco, N, nb, s));
-  if (bo) DV_TRY(bls.download(*bo, N, s));
-  if (ro) DV_TRY(rgs.download(*ro, N, s));
-  if (ao) DV_TRY(aps.download(*ao, N, nb, s));
-  if (afo) DV_TRY(afs.download(*afo, *ao, N, nb, s));
-  if (ffo) DV_TRY(ffs.download(*ffo, N, nb, s));
-  if (fo) DV_TRY(mc.download(N, s));
-  if (fitting) DV_TRY(fit.download(*fo, N, s));
+  if (rq.cat) DV_TRY(cat.download(*rq.cat, N, nb, s));
+  if (rq.mc) DV_TRY(catmc.download(*rq.mc, N, nb, s));
+  if (rq.blend) DV_TRY(bls.download(*rq.blend, N, s));
+  if (rq.regauss) DV_TRY(rgs.download(*rq.regauss, N, s));
+  if (rq.aper) DV_TRY(aps.download(*rq.aper, N, nb, s));
+  if (rq.aper_field) DV_TRY(afs.download(*rq.aper_field, *rq.aper, N, nb, s));
+  if (rq.fit_flux) DV_TRY(ffs.download(*rq.fit_flux, N, nb, s));
+  if (rq.fields) DV_TRY(mc.download(N, s));
+  if (fitting) DV_TRY(fit.download(*rq.fields, N, s));
   drain.dismiss();
   return prof_flush(m);
 }
@@ -5429,10 +5446,10 @@ static PipeJob fields_job(const double* fields, int32_t F, int32_t nb, const int
 }
 
 // ---- one field (dv_infer_cutouts, _keep, _stream, _composite): the many-field call with M = 1 ------------------------------
-static int infer_one_field(dv_model* m, const char* who, int64_t N, const PipeJob& j, const FieldsOut* fo = nullptr) {
+static int infer_one_field(dv_model* m, const char* who, int64_t N, const PipeJob& j, const FieldsRequest& rq = {}) {
   if (!j.fields || !j.starts) return DV_E_INVALID;
   const int64_t field_ptr[2] = {0, N};
-  return infer_fields_impl(m, who, 1, field_ptr, N, j, fo);
+  return infer_fields_impl(m, who, 1, field_ptr, N, j, rq);
 }
 
 int dv_infer_cutouts(dv_model* m, const double* field, int32_t F, int32_t nb, const int32_t* starts, int64_t N,
@@ -5469,13 +5486,10 @@ int dv_infer_cutouts_composite(dv_model* m, const double* field, int32_t F, int3
                                const int32_t* places, int64_t N, uint64_t seed, double* mean_field, double* stddev_field,
                                double* residual_field, double* mse_center) {
   if (!places || !mean_field || !stddev_field) return DV_E_INVALID;
-  FieldsOut fo;
-  fo.mean = mean_field;
-  fo.stddev = stddev_field;
-  fo.residual = residual_field;
-  fo.mse = mse_center;
-  fo.places = places;
-  return infer_one_field(m, "dv_infer_cutouts_composite", N, fields_job(field, F, nb, starts, seed), &fo);
+  FieldsRequest rq;
+  rq.fields = FieldsOut{mean_field, stddev_field, residual_field, mse_center};
+  rq.places = places;
+  return infer_one_field(m, "dv_infer_cutouts_composite", N, fields_job(field, F, nb, starts, seed), rq);
 }
 
 // ---- many fields ------------------------------------------------------------------------------------------------------------
@@ -5488,7 +5502,7 @@ int dv_infer_fields(dv_model* m, const double* fields, int32_t M, int32_t F, int
   j.mu = mu;
   j.zstd = zstd;
   j.z = z;
-  return infer_fields_impl(m, "dv_infer_fields", M, field_ptr, N, j);
+  return infer_fields_impl(m, "dv_infer_fields", M, field_ptr, N, j, {});
 }
 
 int dv_infer_fields_keep(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
@@ -5502,95 +5516,115 @@ int dv_infer_fields_keep(dv_model* m, const double* fields, int32_t M, int32_t F
   j.zstd = zstd;
   j.z = z;
   j.cutouts = cutouts;
-  return infer_fields_impl(m, "dv_infer_fields_keep", M, field_ptr, N, j);
+  return infer_fields_impl(m, "dv_infer_fields_keep", M, field_ptr, N, j, {});
 }
 
 int dv_infer_fields_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
                               const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
                               double* mean_fields, double* stddev_fields, double* residual_fields, double* mse_center) {
   if ((M > 0 && (!mean_fields || !stddev_fields)) || (N > 0 && !places)) return DV_E_INVALID;
-  FieldsOut fo;
-  fo.mean = mean_fields;
-  fo.stddev = stddev_fields;
-  fo.residual = residual_fields;
-  fo.mse = mse_center;
-  fo.places = places;
-  return infer_fields_impl(m, "dv_infer_fields_composite", M, field_ptr, N, fields_job(fields, F, nb, starts, seed), &fo);
+  FieldsRequest rq;
+  rq.fields = FieldsOut{mean_fields, stddev_fields, residual_fields, mse_center};
+  rq.places = places;
+  return infer_fields_impl(m, "dv_infer_fields_composite", M, field_ptr, N, fields_job(fields, F, nb, starts, seed), rq);
 }
 
 // ---- catalogue measurement as a stage of the many-field call -----------------------------------------------
-// bo: the blendedness call, which adds its two outputs and always needs the placements
-static int infer_fields_measure_entry(const char* who, dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb,
-                                      const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
-                                      uint64_t seed, const dv_measure_params* params, double* mean_fields,
-                                      double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
-                                      double* flux_err, double* shape, int32_t* iters, int32_t* status,
-                                      const BlendOut* bo = nullptr, const RegaussOut* ro = nullptr,
-                                      const ApertureOut* ao = nullptr, const ApertureFieldOut* afo = nullptr,
-                                      const FitFluxOut* ffo = nullptr) {
-  if (!m || !params) return DV_E_INVALID;
-  DV_TRY(measure_check(who, m->A.H, nb, params->band, params->sigma0, params->tol, params->max_iter));
-  if (ao) {
-    DV_TRY(aperture_check(who, m->A.H, nb, params->band, ao->par));
-    DV_TRY(aperture_rows_check(who, ao->rows, ao->par, true, N));
+// what every dv_infer_fields_measure* call takes, in the order of the C ABI (between seed and params the Monte-Carlo call
+// has its two arguments; the outputs of an extra follow status)
+struct CatalogueArgs {
+  const double* fields;
+  int32_t M, F, nb;
+  const int32_t *starts, *places;
+  const int64_t* field_ptr;
+  int64_t N;
+  uint64_t seed;
+  const dv_measure_params* params;
+  double *mean_fields, *stddev_fields, *residual_fields, *mse_center;   // all three fields null: the catalogue-only call
+  double *flux, *flux_err, *shape;
+  int32_t *iters, *status;
+};
+
+// the places of a catalogue-only call whose extra composites on the device all the same
+static int seam_places_check(const char* who, const CatalogueArgs& a) {
+  if (a.N > 0 && !a.places) {
+    set_error("%s: places must be given (the catalogue-only form needs the placements too)", who);
+    return DV_E_INVALID;
   }
-  if (afo) {                           // (the apertures on the fields go with the aperture rows: ao is given)
-    DV_TRY(aperture_field_rows_check(who, afo->rows, ao->par, N));
-    if (N > 0 && !places) {
-      set_error("%s: places must be given (the catalogue-only form needs the placements too)", who);
-      return DV_E_INVALID;
-    }
+  return DV_OK;
+}
+
+// rq: the extra of the call, filled in by its entry point; the catalogue, the result fields and the places are filled in here
+static int infer_fields_measure_entry(const char* who, dv_model* m, const CatalogueArgs& a, FieldsRequest& rq) {
+  if (!m || !a.params) return DV_E_INVALID;
+  const dv_measure_params& par = *a.params;
+  const int64_t N = a.N;
+  DV_TRY(measure_check(who, m->A.H, a.nb, par.band, par.sigma0, par.tol, par.max_iter));
+  if (rq.mc && rq.mc->nsamples < 1) {
+    set_error("%s: %d Monte-Carlo samples asked for, at least 1 is needed", who, rq.mc->nsamples);
+    return DV_E_INVALID;
   }
-  if (ffo) {
-    DV_TRY(fitflux_check(who, m->A.H, nb, F, ffo->par));
-    DV_TRY(fitflux_rows_check(who, ffo->rows, N));
-    if (N > 0 && !places) {
-      set_error("%s: places must be given (the catalogue-only form needs the placements too)", who);
-      return DV_E_INVALID;
-    }
+  if (rq.aper) {
+    DV_TRY(aperture_check(who, m->A.H, a.nb, par.band, rq.aper->par));
+    DV_TRY(aperture_rows_check(who, rq.aper->rows, rq.aper->par, true, N));
   }
-  if (ro) {
-    DV_TRY(regauss_check(who, m->A.H, nb, params->band, ro->K, ro->ps, ro->psf_sigma0, params->tol, params->max_iter));
-    if (!ro->psf || !ro->psf_shape || !ro->psf_aux || !ro->psf_iters || !ro->psf_status ||
-        (N > 0 && (!ro->index || !ro->out || !ro->iters || !ro->status))) {
+  if (rq.aper_field) {
+    DV_TRY(aperture_field_rows_check(who, rq.aper_field->rows, rq.aper->par, N));
+    DV_TRY(seam_places_check(who, a));
+  }
+  if (rq.fit_flux) {
+    DV_TRY(fitflux_check(who, m->A.H, a.nb, a.F, rq.fit_flux->par));
+    DV_TRY(fitflux_rows_check(who, rq.fit_flux->rows, N));
+    DV_TRY(seam_places_check(who, a));
+  }
+  if (rq.regauss) {
+    const RegaussOut& ro = *rq.regauss;
+    DV_TRY(regauss_check(who, m->A.H, a.nb, par.band, ro.K, ro.ps, ro.psf_sigma0, par.tol, par.max_iter));
+    if (!ro.psf || !ro.psf_shape || !ro.psf_aux || !ro.psf_iters || !ro.psf_status ||
+        (N > 0 && (!ro.index || !ro.out || !ro.iters || !ro.status))) {
       set_error("%s: psf, psf_index, regauss, regauss_iters, regauss_status, psf_shape, psf_aux, psf_iters and psf_status must "
                 "all be given", who);
       return DV_E_INVALID;
     }
   }
-  if (N > 0 && (!flux || !flux_err || !shape || !iters || !status)) {
+  if (N > 0 && (!a.flux || !a.flux_err || !a.shape || !a.iters || !a.status)) {
     set_error("%s: flux, flux_err, shape, iters and status must all be given", who);
     return DV_E_INVALID;
   }
-  const bool with_fields = mean_fields || stddev_fields || residual_fields;
-  if (with_fields && ((M > 0 && (!mean_fields || !stddev_fields)) || (N > 0 && !places))) {
+  if (rq.mc) {
+    const McState& st = rq.mc->st;
+    if (N > 0 && (!st.flux_mean || !st.flux_std || !st.shape_mean || !st.shape_std || !st.n_ok)) {
+      set_error("%s: the Monte-Carlo outputs flux_mean, flux_std, shape_mean, shape_std and n_ok must all be given", who);
+      return DV_E_INVALID;
+    }
+    const int given = (st.sample_flux != nullptr) + (st.sample_shape != nullptr) + (st.sample_status != nullptr);
+    if (given != 0 && given != 3) {
+      set_error("%s: the per-sample outputs sample_flux, sample_shape and sample_status go together (all given or all null)", who);
+      return DV_E_INVALID;
+    }
+  }
+  const bool with_fields = a.mean_fields || a.stddev_fields || a.residual_fields;
+  if (with_fields && ((a.M > 0 && (!a.mean_fields || !a.stddev_fields)) || (N > 0 && !a.places))) {
     set_error("%s: mean_fields, stddev_fields and places go together (residual_fields is optional beside them); the "
               "catalogue-only call passes all three fields as null", who);
     return DV_E_INVALID;
   }
-  MeasureOut mo;
-  mo.par = *params;
-  mo.flux = flux;
-  mo.flux_err = flux_err;
-  mo.shape = shape;
-  mo.iters = iters;
-  mo.status = status;
-  if (bo && N > 0 && (!places || !bo->blend || !bo->npix)) {
+  if (rq.blend && N > 0 && (!a.places || !rq.blend->blend || !rq.blend->npix)) {
     set_error("%s: places, blend and npix must all be given (the catalogue-only form needs the placements too)", who);
     return DV_E_INVALID;
   }
-  PipeJob j = fields_job(fields, F, nb, starts, seed);
-  if (!with_fields) {
-    mo.mse = mse_center;
-    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, nullptr, bo, bo || afo || ffo ? places : nullptr, ro, ao, afo, ffo);
+  rq.cat = MeasureOut{par, a.flux, a.flux_err, a.shape, a.iters, a.status};
+  rq.places = a.places;
+  if (with_fields)
+    rq.fields = FieldsOut{a.mean_fields, a.stddev_fields, a.residual_fields, a.mse_center};
+  else
+    rq.cat->mse = a.mse_center;      // (no FieldsOut to carry it)
+  PipeJob j = fields_job(a.fields, a.F, a.nb, a.starts, a.seed);
+  if (rq.mc) {
+    j.mc_samples = rq.mc->nsamples;
+    j.mc_seed = rq.mc->seed;
   }
-  FieldsOut fo;
-  fo.mean = mean_fields;
-  fo.stddev = stddev_fields;
-  fo.residual = residual_fields;
-  fo.mse = mse_center;
-  fo.places = places;
-  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, nullptr, bo, nullptr, ro, ao, afo, ffo);
+  return infer_fields_impl(m, who, a.M, a.field_ptr, N, j, rq);
 }
 
 int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
@@ -5598,23 +5632,24 @@ int dv_infer_fields_measure(dv_model* m, const double* fields, int32_t M, int32_
                             const dv_measure_params* params, double* mean_fields, double* stddev_fields,
                             double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
                             int32_t* iters, int32_t* status) {
-  return infer_fields_measure_entry("dv_infer_fields_measure", m, fields, M, F, nb, starts, places, field_ptr, N, seed, params,
-                                    mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape, iters,
-                                    status);
+  FieldsRequest rq;
+  return infer_fields_measure_entry("dv_infer_fields_measure", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }
 
-// ---- blendedness beside the catalogue: dv_infer_fields_measure plus the four weighted sums per galaxy
+// ---- blendedness beside the catalogue: dv_infer_fields_measure plus the four weighted sums per galaxy; the
+// placements are always needed
 int dv_infer_fields_measure_blend(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
                                   const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
                                   const dv_measure_params* params, double* mean_fields, double* stddev_fields,
                                   double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
                                   int32_t* iters, int32_t* status, double* blend, int32_t* npix) {
-  BlendOut bo;
-  bo.blend = blend;
-  bo.npix = npix;
-  return infer_fields_measure_entry("dv_infer_fields_measure_blend", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
-                                    params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
-                                    iters, status, &bo);
+  FieldsRequest rq;
+  rq.blend = BlendOut{blend, npix};
+  return infer_fields_measure_entry("dv_infer_fields_measure_blend", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }
 
 // ---- PSF-corrected shapes beside the catalogue: dv_infer_fields_measure plus the re-Gaussianized moments
@@ -5626,22 +5661,12 @@ int dv_infer_fields_measure_psf(dv_model* m, const double* fields, int32_t M, in
                                 const int32_t* psf_index, double psf_sigma0, double* regauss, int32_t* regauss_iters,
                                 int32_t* regauss_status, double* psf_shape, double* psf_aux, int32_t* psf_iters,
                                 int32_t* psf_status) {
-  RegaussOut ro;
-  ro.psf = psf;
-  ro.K = K;
-  ro.ps = ps;
-  ro.index = psf_index;
-  ro.psf_sigma0 = psf_sigma0;
-  ro.out = regauss;
-  ro.iters = regauss_iters;
-  ro.status = regauss_status;
-  ro.psf_shape = psf_shape;
-  ro.psf_aux = psf_aux;
-  ro.psf_iters = psf_iters;
-  ro.psf_status = psf_status;
-  return infer_fields_measure_entry("dv_infer_fields_measure_psf", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
-                                    params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
-                                    iters, status, nullptr, &ro);
+  FieldsRequest rq;
+  rq.regauss = RegaussOut{psf, K, ps, psf_index, psf_sigma0, regauss, regauss_iters, regauss_status, psf_shape, psf_aux,
+                          psf_iters, psf_status};
+  return infer_fields_measure_entry("dv_infer_fields_measure_psf", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }
 
 // ---- aperture photometry beside the catalogue: dv_infer_fields_measure plus circular apertures, the Kron flux
@@ -5658,12 +5683,12 @@ int dv_infer_fields_measure_aper(dv_model* m, const double* fields, int32_t M, i
     set_error("dv_infer_fields_measure_aper: the aperture params must be given");
     return DV_E_INVALID;
   }
-  ApertureOut ao;
-  ao.par = aperture_params(*aper);
-  ao.rows = ApertureRows{ap_flux, ap_flux_err, ap_area, flux_auto, flux_auto_err, kron, flux_rho, aper_flags, aper_status};
-  return infer_fields_measure_entry("dv_infer_fields_measure_aper", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
-                                    params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
-                                    iters, status, nullptr, nullptr, &ao);
+  FieldsRequest rq;
+  rq.aper = ApertureOut{aperture_params(*aper), ApertureRows{ap_flux, ap_flux_err, ap_area, flux_auto, flux_auto_err, kron,
+                                                              flux_rho, aper_flags, aper_status}};
+  return infer_fields_measure_entry("dv_infer_fields_measure_aper", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }
 
 // ---- the same apertures on the observed field with the neighbours subtracted: dv_infer_fields_measure_aper plus
@@ -5683,14 +5708,14 @@ int dv_infer_fields_measure_aper_data(dv_model* m, const double* fields, int32_t
     set_error("dv_infer_fields_measure_aper_data: the aperture params must be given");
     return DV_E_INVALID;
   }
-  ApertureOut ao;
-  ao.par = aperture_params(*aper);
-  ao.rows = ApertureRows{ap_flux, ap_flux_err, ap_area, flux_auto, flux_auto_err, kron, flux_rho, aper_flags, aper_status};
-  ApertureFieldOut afo;
-  afo.rows = ApertureFieldRows{ap_model_sum, ap_data_sum, ap_field_area, auto_model_sum, auto_data_sum, auto_field_area};
-  return infer_fields_measure_entry("dv_infer_fields_measure_aper_data", m, fields, M, F, nb, starts, places, field_ptr, N,
-                                    seed, params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err,
-                                    shape, iters, status, nullptr, nullptr, &ao, &afo);
+  FieldsRequest rq;
+  rq.aper = ApertureOut{aperture_params(*aper), ApertureRows{ap_flux, ap_flux_err, ap_area, flux_auto, flux_auto_err, kron,
+                                                              flux_rho, aper_flags, aper_status}};
+  rq.aper_field = ApertureFieldOut{ApertureFieldRows{ap_model_sum, ap_data_sum, ap_field_area, auto_model_sum, auto_data_sum,
+                                                     auto_field_area}};
+  return infer_fields_measure_entry("dv_infer_fields_measure_aper_data", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }
 
 // ---- the simultaneous flux fit beside the catalogue: dv_infer_fields_measure plus, per galaxy and band, the
@@ -5707,12 +5732,12 @@ int dv_infer_fields_measure_fit(dv_model* m, const double* fields, int32_t M, in
     set_error("dv_infer_fields_measure_fit: the flux-fit params must be given");
     return DV_E_INVALID;
   }
-  FitFluxOut ffo;
-  ffo.par = FitFluxParams{fit->min_pivot, fit->scratch_bytes};
-  ffo.rows = FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status};
-  return infer_fields_measure_entry("dv_infer_fields_measure_fit", m, fields, M, F, nb, starts, places, field_ptr, N, seed,
-                                    params, mean_fields, stddev_fields, residual_fields, mse_center, flux, flux_err, shape,
-                                    iters, status, nullptr, nullptr, nullptr, nullptr, &ffo);
+  FieldsRequest rq;
+  rq.fit_flux = FitFluxOut{FitFluxParams{fit->min_pivot, fit->scratch_bytes},
+                           FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status}};
+  return infer_fields_measure_entry("dv_infer_fields_measure_fit", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }
 
 // ---- the Monte-Carlo catalogue beside it: dv_infer_fields_measure plus means and standard deviations of
@@ -5724,56 +5749,12 @@ int dv_infer_fields_measure_mc(dv_model* m, const double* fields, int32_t M, int
                                int32_t* iters, int32_t* status, double* flux_mean, double* flux_std, double* shape_mean,
                                double* shape_std, int32_t* n_ok, double* sample_flux, double* sample_shape,
                                int32_t* sample_status) {
-  const char* who = "dv_infer_fields_measure_mc";
-  if (!m || !params) return DV_E_INVALID;
-  DV_TRY(measure_check(who, m->A.H, nb, params->band, params->sigma0, params->tol, params->max_iter));
-  if (nsamples < 1) {
-    set_error("%s: %d Monte-Carlo samples asked for, at least 1 is needed", who, nsamples);
-    return DV_E_INVALID;
-  }
-  if (N > 0 && (!flux || !flux_err || !shape || !iters || !status)) {
-    set_error("%s: flux, flux_err, shape, iters and status must all be given", who);
-    return DV_E_INVALID;
-  }
-  if (N > 0 && (!flux_mean || !flux_std || !shape_mean || !shape_std || !n_ok)) {
-    set_error("%s: the Monte-Carlo outputs flux_mean, flux_std, shape_mean, shape_std and n_ok must all be given", who);
-    return DV_E_INVALID;
-  }
-  const int given = (sample_flux != nullptr) + (sample_shape != nullptr) + (sample_status != nullptr);
-  if (given != 0 && given != 3) {
-    set_error("%s: the per-sample outputs sample_flux, sample_shape and sample_status go together (all given or all null)", who);
-    return DV_E_INVALID;
-  }
-  const bool with_fields = mean_fields || stddev_fields || residual_fields;
-  if (with_fields && ((M > 0 && (!mean_fields || !stddev_fields)) || (N > 0 && !places))) {
-    set_error("%s: mean_fields, stddev_fields and places go together (residual_fields is optional beside them); the "
-              "catalogue-only call passes all three fields as null", who);
-    return DV_E_INVALID;
-  }
-  MeasureOut mo;
-  mo.par = *params;
-  mo.flux = flux;
-  mo.flux_err = flux_err;
-  mo.shape = shape;
-  mo.iters = iters;
-  mo.status = status;
-  MeasureMcOut mco;
-  mco.st = McState{flux_mean, flux_std, shape_mean, shape_std, n_ok, sample_flux, sample_shape, sample_status};
-  mco.nsamples = nsamples;
-  PipeJob j = fields_job(fields, F, nb, starts, seed);
-  j.mc_samples = nsamples;
-  j.mc_seed = mc_seed;
-  if (!with_fields) {
-    mo.mse = mse_center;
-    return infer_fields_impl(m, who, M, field_ptr, N, j, nullptr, &mo, &mco);
-  }
-  FieldsOut fo;
-  fo.mean = mean_fields;
-  fo.stddev = stddev_fields;
-  fo.residual = residual_fields;
-  fo.mse = mse_center;
-  fo.places = places;
-  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo, &mo, &mco);
+  FieldsRequest rq;
+  rq.mc = MeasureMcOut{McState{flux_mean, flux_std, shape_mean, shape_std, n_ok, sample_flux, sample_shape, sample_status},
+                       nsamples, mc_seed};
+  return infer_fields_measure_entry("dv_infer_fields_measure_mc", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }
 
 // the refusals of the two Monte-Carlo forms, before any GPU work
@@ -5806,7 +5787,7 @@ int dv_infer_fields_mc_keep(dv_model* m, const double* fields, int32_t M, int32_
   j.eps_out = epistemic;
   j.mc_samples = nsamples;
   j.mc_seed = mc_seed;
-  return infer_fields_impl(m, "dv_infer_fields_mc_keep", M, field_ptr, N, j);
+  return infer_fields_impl(m, "dv_infer_fields_mc_keep", M, field_ptr, N, j, {});
 }
 
 int dv_infer_fields_mc_composite(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
@@ -5818,18 +5799,15 @@ int dv_infer_fields_mc_composite(dv_model* m, const double* fields, int32_t M, i
     set_error("dv_infer_fields_mc_composite: mean_fields, stddev_fields, epistemic_fields, eps_norm and places must all be given");
     return DV_E_INVALID;
   }
-  FieldsOut fo;
-  fo.mean = mean_fields;
-  fo.stddev = stddev_fields;
-  fo.residual = residual_fields;
-  fo.mse = mse_center;
-  fo.places = places;
-  fo.epistemic = epistemic_fields;
-  fo.eps_norm = eps_norm;
+  FieldsRequest rq;
+  rq.fields = FieldsOut{mean_fields, stddev_fields, residual_fields, mse_center};
+  rq.fields->epistemic = epistemic_fields;
+  rq.fields->eps_norm = eps_norm;
+  rq.places = places;
   PipeJob j = fields_job(fields, F, nb, starts, seed);
   j.mc_samples = nsamples;
   j.mc_seed = mc_seed;
-  return infer_fields_impl(m, "dv_infer_fields_mc_composite", M, field_ptr, N, j, &fo);
+  return infer_fields_impl(m, "dv_infer_fields_mc_composite", M, field_ptr, N, j, rq);
 }
 
 // ---- position fit and fractional placements in the many-field composite call -------------------------------
@@ -5867,11 +5845,8 @@ int dv_infer_fields_fit_composite(dv_model* m, const double* fields, int32_t M, 
                 (long)(i / 2));
       return DV_E_INVALID;
     }
-  FieldsOut fo;
-  fo.mean = mean_fields;
-  fo.stddev = stddev_fields;
-  fo.residual = residual_fields;
-  fo.mse = mse_center;
+  FieldsRequest rq;
+  FieldsOut& fo = rq.fields.emplace(FieldsOut{mean_fields, stddev_fields, residual_fields, mse_center});
   fo.epistemic = mc ? epistemic_fields : nullptr;
   fo.eps_norm = mc ? eps_norm : nullptr;
   fo.dist = dist;
@@ -5886,7 +5861,7 @@ int dv_infer_fields_fit_composite(dv_model* m, const double* fields, int32_t M, 
     j.mc_samples = nsamples;
     j.mc_seed = mc_seed;
   }
-  return infer_fields_impl(m, who, M, field_ptr, N, j, &fo);
+  return infer_fields_impl(m, who, M, field_ptr, N, j, rq);
 }
 
 // ---- resident field sets (dv_field_set_*) ---------------------------------------------------------------------

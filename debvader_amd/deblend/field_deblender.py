@@ -8,12 +8,16 @@ call for all galaxies instead of a scipy.optimize run per galaxy): `optimise_pos
 recarray and writes their `shifts`.  `deblend_field(optimise_positions=True)` still raises: run `deblend_field` and then
 `optimise_positions()`.  Source detection: debvader_amd.detect.detection (SExtractor's method on the GPU, not sep).
 """
+from types import SimpleNamespace
+from typing import Callable, NamedTuple, Optional
+
 import numpy as np
 import pandas as pd
 
 from debvader_amd import engine as E
 from debvader_amd.deblend_cutout.deblender import deblend, deblend_epistemic
 from debvader_amd.extract.extraction import cutout_windows, extract_cutouts  # noqa: F401  (extract_cutouts: re-exported as in the reference)
+from debvader_amd.measure import measurement as ms
 from debvader_amd.training.metrics import mse  # noqa: F401  (the reference's module imports it; the cut below is its vector form)
 
 
@@ -36,6 +40,117 @@ def _to_records(cols):
         else:
             out[k] = rest[k]
     return out
+
+
+class _Extra(NamedTuple):
+    """One optional part of the on-device catalogue of DeblendFieldBatch.deblend_fields: a keyword, the engine call that
+    serves it and what it appends to the recarrays.  `c` below is the namespace of one call: bands, band, sky_sigma,
+    field_ptr, psf, psf_index, aper_par, nmc, core."""
+    key: str                        # the keyword of deblend_fields
+    given: Callable                 # its value -> whether the extra is asked for
+    label: str                      # how a message names it
+    verb: str                       # ... "needs" / "need" measure=True and on_device=True
+    what: str                       # what the engine call adds, as a message names it
+    why: str                        # why it needs the measuring on-device call, and what to use on the default path
+    call: str                       # the C call, named in messages
+    method: str                     # the Engine method
+    places_always: bool             # whether the catalogue-only form passes the placements too
+    kwargs: Callable                # c -> the keyword arguments of the engine call beside places, seed and return_fields
+    columns: Callable               # c -> what it appends to the recarrays' dtype
+    records: Callable               # (out, c) -> the recarray of those columns, rows = global stamp numbers
+    orphans: tuple = ()             # ((keyword, message), ...): keywords that are refused without this one
+    refines: Optional[str] = None   # the key of the extra this one goes with and whose engine call it replaces; `why` is
+                                    # then the refusal without it
+
+
+def _aper_kwargs(c):
+    return dict(radii=list(c.aper_par.radii)[:c.aper_par.n_radii], fractions=list(c.aper_par.fractions)[:c.aper_par.n_fractions])
+
+
+# In the order the extras were added, which is the order of their columns.  Any two are refused together (the later one
+# speaks), but for an extra and the one that refines it.
+_EXTRAS = (
+    _Extra("measure_samples", lambda v: bool(int(v or 0)), "measure_samples", "needs", "the Monte-Carlo catalogue",
+           "the Monte-Carlo decodes are measured where they lie in device memory",
+           "dv_infer_fields_measure_mc", "infer_fields_measure_mc", False,
+           lambda c: dict(mc_seed=c.core.next_seed(), nsamples=c.nmc),
+           lambda c: ms.catalogue_mc_dtype(c.bands),
+           lambda out, c: ms.catalogue_mc_records(out["flux_mc_mean"], out["flux_mc_std"], out["shape_mc_mean"],
+                                                  out["shape_mc_std"], out["n_ok"])),
+    _Extra("blendedness", bool, "blendedness=True", "needs", "the blendedness sums",
+           "the weight of the sums is the Gaussian of the measured adaptive moments, and they are taken where the stamps and "
+           "the composited fields lie in device memory (dv_infer_fields_measure_blend); on the default path use "
+           "debvader_amd.measure.measurement.measure_blendedness on the returned stamps",
+           "dv_infer_fields_measure_blend", "infer_fields_measure_blend", True,
+           lambda c: {},
+           lambda c: ms.blend_dtype(),
+           lambda out, c: ms.blend_records(out["blend"], out["npix"])),
+    _Extra("psf", lambda v: v is not None, "psf", "needs", "the PSF correction",
+           "the correction starts from the measured adaptive moments and runs where the stamps lie in device memory "
+           "(dv_infer_fields_measure_psf); on the default path use debvader_amd.measure.measurement.measure_stamps_psf on the "
+           "returned stamps",
+           "dv_infer_fields_measure_psf", "infer_fields_measure_psf", False,
+           lambda c: dict(psf=c.psf, psf_index=c.psf_index),
+           lambda c: ms.psf_dtype(),
+           lambda out, c: ms.psf_records(out["regauss"], out["regauss_iters"], out["regauss_status"], out["psf_shape"],
+                                         out["psf_aux"], c.psf_index),
+           orphans=(("psf_index", "psf_index picks a galaxy's image out of psf: give psf too"),)),
+    _Extra("apertures", lambda v: v is not None, "apertures", "need", "the aperture photometry",
+           "the apertures are centred on the measured centroid and taken where the stamps lie in device memory "
+           "(dv_infer_fields_measure_aper); on the default path use debvader_amd.measure.measurement.measure_apertures on the "
+           "returned stamps",
+           "dv_infer_fields_measure_aper", "infer_fields_measure_aper", False,
+           _aper_kwargs,
+           lambda c: ms.aperture_dtype(c.bands, c.aper_par.n_radii, c.aper_par.n_fractions),
+           lambda out, c: ms.aperture_records(*(out[k] for k in E.APERTURE_KEYS), out["shape"]),
+           orphans=(("flux_fractions", "flux_fractions are fractions of the Kron flux of the aperture photometry: give apertures "
+                                       "too (apertures=() for the Kron columns alone)"),)),
+    _Extra("aperture_data", bool, "aperture_data=True", "needs", "the apertures on the fields",
+           "aperture_data=True needs apertures: it takes the apertures of the aperture photometry on the observed field and the "
+           "composited mean field (apertures=() for the Kron ellipse alone)",
+           "dv_infer_fields_measure_aper_data", "infer_fields_measure_aper_data", True,
+           lambda c: dict(band=c.band, **_aper_kwargs(c)),
+           lambda c: ms.aperture_data_dtype(c.bands, c.aper_par.n_radii),
+           lambda out, c: ms.aperture_data_records(*(out[k] for k in E.APERTURE_FIELD_KEYS), out["ap_flux"], out["ap_area"],
+                                                   out["flux_auto"], out["kron"][:, 2], band=c.band, sky_sigma=c.sky_sigma,
+                                                   field_ptr=c.field_ptr),
+           refines="apertures"),
+    _Extra("fit_flux", bool, "fit_flux=True", "needs", "the flux fit",
+           "the fit scales the measured stamp fluxes and runs where the mean stamps and the observed fields lie in device "
+           "memory (dv_infer_fields_measure_fit); on the default path use debvader_amd.measure.measurement.fit_fluxes on the "
+           "returned stamps",
+           "dv_infer_fields_measure_fit", "infer_fields_measure_fit", True,
+           lambda c: dict(band=c.band),
+           lambda c: ms.fit_flux_dtype(c.bands),
+           lambda out, c: ms.fit_flux_records(*(out[k] for k in E.FIT_FLUX_KEYS), out["flux"], sky_sigma=c.sky_sigma,
+                                              field_ptr=c.field_ptr)),
+)
+
+
+def _refuse_extra(x, kw, given, measure, on_device, fit, mc):
+    """The refusals of extra `x` of a deblend_fields call with keywords `kw`: what is given without it, the call it needs,
+    every older extra beside it, and the passes that have no catalogue stage.  given: the keys of the extras asked for."""
+    for key, message in x.orphans:
+        if kw[key] is not None and x.key not in given:
+            raise ValueError(message)
+    if x.key not in given:
+        return
+    if x.refines:
+        if x.refines not in given:
+            raise ValueError(x.why)
+        return
+    if not (measure and on_device):
+        lacks = " and ".join(k for k, v in (("measure=True", measure), ("on_device=True", on_device)) if not v)
+        raise ValueError(f"{x.label} {x.verb} measure=True and on_device=True: {x.why}.  Here {x.label} {x.verb} {lacks}")
+    for y in reversed(_EXTRAS[:_EXTRAS.index(x)]):
+        if y.key in given and not y.refines:
+            raise ValueError(f"{x.label} cannot be combined with {y.label}: {x.what} and {y.what} are stages of two different "
+                             f"measuring calls ({x.call}, {y.call})")
+    for on, other, kind in ((fit, "optimise_positions=True", "position-fit"), (mc, "epistemic_uncertainty_estimation=True",
+                                                                              "Monte-Carlo")):
+        if on:
+            raise ValueError(f"{x.label} cannot be combined with {other}: only the plain measuring composite call ({x.call}) "
+                             f"has a stage for {x.what}, the {kind} call has none")
 
 
 class DeblendField:
@@ -428,54 +543,40 @@ class DeblendFieldBatch:
     def measure_columns(nb_of_bands):
         """What deblend_fields(measure=True) appends to every recarray: the catalogue of measure_stamps and the measured
         centroid as a distance to the field centre."""
-        from debvader_amd.measure.measurement import catalogue_dtype
-
-        return catalogue_dtype(nb_of_bands) + [("measured_distance_x", "<f8"), ("measured_distance_y", "<f8")]
+        return ms.catalogue_dtype(nb_of_bands) + [("measured_distance_x", "<f8"), ("measured_distance_y", "<f8")]
 
     @staticmethod
     def measure_mc_columns(nb_of_bands):
         """What deblend_fields(measure_samples=S) appends behind measure_columns: the Monte-Carlo catalogue of
         measure_stamps_mc."""
-        from debvader_amd.measure.measurement import catalogue_mc_dtype
-
-        return catalogue_mc_dtype(nb_of_bands)
+        return ms.catalogue_mc_dtype(nb_of_bands)
 
     @staticmethod
     def blend_columns():
         """What deblend_fields(blendedness=True) appends behind measure_columns: the recarray of measure_blendedness."""
-        from debvader_amd.measure.measurement import blend_dtype
-
-        return blend_dtype()
+        return ms.blend_dtype()
 
     @staticmethod
     def psf_columns():
         """What deblend_fields(measure=True, psf=...) appends behind measure_columns: the recarray of measure_stamps_psf."""
-        from debvader_amd.measure.measurement import psf_dtype
-
-        return psf_dtype()
+        return ms.psf_dtype()
 
     @staticmethod
     def aperture_columns(nb_of_bands, n_radii, n_fractions):
         """What deblend_fields(measure=True, apertures=...) appends behind measure_columns: the recarray of
         measure_apertures."""
-        from debvader_amd.measure.measurement import aperture_dtype
-
-        return aperture_dtype(nb_of_bands, n_radii, n_fractions)
+        return ms.aperture_dtype(nb_of_bands, n_radii, n_fractions)
 
     @staticmethod
     def aperture_data_columns(nb_of_bands, n_radii):
         """What deblend_fields(measure=True, apertures=..., aperture_data=True) appends behind aperture_columns: the recarray
         of measure_apertures_on_fields."""
-        from debvader_amd.measure.measurement import aperture_data_dtype
-
-        return aperture_data_dtype(nb_of_bands, n_radii)
+        return ms.aperture_data_dtype(nb_of_bands, n_radii)
 
     @staticmethod
     def fit_flux_columns(nb_of_bands):
         """What deblend_fields(measure=True, fit_flux=True) appends behind measure_columns: the recarray of fit_fluxes."""
-        from debvader_amd.measure.measurement import fit_flux_dtype
-
-        return fit_flux_dtype(nb_of_bands)
+        return ms.fit_flux_dtype(nb_of_bands)
 
     def _psf_index(self, psf, psf_index, field_ptr):
         """(psf (K, ps, ps), index (N,)) of a deblend_fields(psf=...) call: one image for all galaxies, one per field (the
@@ -646,118 +747,23 @@ class DeblendFieldBatch:
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
-        blendedness = bool(blendedness)
-        if blendedness and not measure:
-            raise ValueError("blendedness=True needs measure=True: the weight of the blendedness sums is the Gaussian of the "
-                             "measured adaptive moments")
-        if blendedness and not on_device:
-            raise ValueError("blendedness=True needs on_device=True: the sums are taken where the stamps and the composited "
-                             "fields lie in device memory (dv_infer_fields_measure_blend); on the default path use "
-                             "debvader_amd.measure.measurement.measure_blendedness on the returned stamps")
-        if blendedness and (fit or mc or int(measure_samples or 0)):
-            raise ValueError("blendedness=True cannot be combined with optimise_positions=True, "
-                             "epistemic_uncertainty_estimation=True or measure_samples: the blendedness sums are a stage of "
-                             "the plain measuring composite call only (dv_infer_fields_measure_blend)")
-        with_psf = psf is not None
-        if psf_index is not None and not with_psf:
-            raise ValueError("psf_index picks a galaxy's image out of psf: give psf too")
-        if with_psf and not (measure and on_device):
-            raise ValueError("psf needs measure=True and on_device=True: the correction starts from the measured adaptive "
-                             "moments and runs where the stamps lie in device memory (dv_infer_fields_measure_psf); on the "
-                             "default path use debvader_amd.measure.measurement.measure_stamps_psf on the returned stamps")
-        if with_psf and blendedness:
-            raise ValueError("psf cannot be combined with blendedness=True: the PSF correction and the blendedness sums are "
-                             "stages of two different measuring calls (dv_infer_fields_measure_psf, "
-                             "dv_infer_fields_measure_blend)")
-        if with_psf and int(measure_samples or 0):
-            raise ValueError("psf cannot be combined with measure_samples: the PSF correction is not a stage of the "
-                             "Monte-Carlo catalogue call (dv_infer_fields_measure_mc)")
-        if with_psf and fit:
-            raise ValueError("psf cannot be combined with optimise_positions=True: the PSF correction is a stage of the plain "
-                             "measuring composite call only (dv_infer_fields_measure_psf), not of the position-fit call")
-        if with_psf and mc:
-            raise ValueError("psf cannot be combined with epistemic_uncertainty_estimation=True: the PSF correction is a "
-                             "stage of the plain measuring composite call only (dv_infer_fields_measure_psf), not of the "
-                             "Monte-Carlo call")
-        with_aper = apertures is not None
-        if flux_fractions is not None and not with_aper:
-            raise ValueError("flux_fractions are fractions of the Kron flux of the aperture photometry: give apertures too "
-                             "(apertures=() for the Kron columns alone)")
-        if with_aper and not (measure and on_device):
-            raise ValueError("apertures need measure=True and on_device=True: the apertures are centred on the measured "
-                             "centroid and taken where the stamps lie in device memory (dv_infer_fields_measure_aper); on the "
-                             "default path use debvader_amd.measure.measurement.measure_apertures on the returned stamps")
-        if with_aper and with_psf:
-            raise ValueError("apertures cannot be combined with psf: the aperture photometry and the PSF correction are "
-                             "stages of two different measuring calls (dv_infer_fields_measure_aper, "
-                             "dv_infer_fields_measure_psf)")
-        if with_aper and blendedness:
-            raise ValueError("apertures cannot be combined with blendedness=True: the aperture photometry and the blendedness "
-                             "sums are stages of two different measuring calls (dv_infer_fields_measure_aper, "
-                             "dv_infer_fields_measure_blend)")
-        if with_aper and int(measure_samples or 0):
-            raise ValueError("apertures cannot be combined with measure_samples: the aperture photometry is not a stage of "
-                             "the Monte-Carlo catalogue call (dv_infer_fields_measure_mc)")
-        if with_aper and fit:
-            raise ValueError("apertures cannot be combined with optimise_positions=True: the aperture photometry is a stage "
-                             "of the plain measuring composite call only (dv_infer_fields_measure_aper), not of the "
-                             "position-fit call")
-        if with_aper and mc:
-            raise ValueError("apertures cannot be combined with epistemic_uncertainty_estimation=True: the aperture "
-                             "photometry is a stage of the plain measuring composite call only "
-                             "(dv_infer_fields_measure_aper), not of the Monte-Carlo call")
-        aperture_data = bool(aperture_data)
+        aperture_data, fit_flux = bool(aperture_data), bool(fit_flux)
         band = 2                        # the band of the measurement (r): the engine call and the blendedness in the apertures
-        if aperture_data and not with_aper:
-            raise ValueError("aperture_data=True needs apertures: it takes the apertures of the aperture photometry on the "
-                             "observed field and the composited mean field (apertures=() for the Kron ellipse alone)")
-        fit_flux = bool(fit_flux)
-        if fit_flux and not (measure and on_device):
-            raise ValueError("fit_flux=True needs measure=True and on_device=True: the fit scales the measured stamp fluxes and "
-                             "runs where the mean stamps and the observed fields lie in device memory "
-                             "(dv_infer_fields_measure_fit); on the default path use "
-                             "debvader_amd.measure.measurement.fit_fluxes on the returned stamps")
-        if fit_flux and with_psf:
-            raise ValueError("fit_flux=True cannot be combined with psf: the flux fit and the PSF correction are stages of two "
-                             "different measuring calls (dv_infer_fields_measure_fit, dv_infer_fields_measure_psf)")
-        if fit_flux and with_aper:
-            raise ValueError("fit_flux=True cannot be combined with apertures: the flux fit and the aperture photometry are "
-                             "stages of two different measuring calls (dv_infer_fields_measure_fit, "
-                             "dv_infer_fields_measure_aper)")
-        if fit_flux and blendedness:
-            raise ValueError("fit_flux=True cannot be combined with blendedness=True: the flux fit and the blendedness sums are "
-                             "stages of two different measuring calls (dv_infer_fields_measure_fit, "
-                             "dv_infer_fields_measure_blend)")
-        if fit_flux and int(measure_samples or 0):
-            raise ValueError("fit_flux=True cannot be combined with measure_samples: the flux fit is not a stage of the "
-                             "Monte-Carlo catalogue call (dv_infer_fields_measure_mc)")
-        if fit_flux and fit:
-            raise ValueError("fit_flux=True cannot be combined with optimise_positions=True: the flux fit is a stage of the "
-                             "plain measuring composite call only (dv_infer_fields_measure_fit), not of the position-fit call")
-        if fit_flux and mc:
-            raise ValueError("fit_flux=True cannot be combined with epistemic_uncertainty_estimation=True: the flux fit is a "
-                             "stage of the plain measuring composite call only (dv_infer_fields_measure_fit), not of the "
-                             "Monte-Carlo call")
+        kw = dict(measure_samples=measure_samples, blendedness=blendedness, psf=psf, psf_index=psf_index, apertures=apertures,
+                  flux_fractions=flux_fractions, aperture_data=aperture_data, fit_flux=fit_flux)
+        given = [x.key for x in _EXTRAS if x.given(kw[x.key])]
+        for x in _EXTRAS[1:]:           # (measure_samples, the oldest, is refused below its own integer check)
+            _refuse_extra(x, kw, given, measure, on_device, fit, mc)
         if sky_sigma is not None and not aperture_data and not fit_flux:
             raise ValueError("sky_sigma is the sky noise of the data-flux errors of aperture_data=True: give aperture_data too")
         if sky_sigma is not None:
-            from debvader_amd.measure.measurement import check_sky_sigma
-
-            sky_sigma = check_sky_sigma(sky_sigma, self.nb_of_fields, self.nb_of_bands)                     # (ValueError)
-        if with_aper:
-            from debvader_amd.engine import aperture_params
-
-            aper_par = aperture_params(apertures, (0.2, 0.5, 0.8) if flux_fractions is None else flux_fractions)   # (ValueError)
+            sky_sigma = ms.check_sky_sigma(sky_sigma, self.nb_of_fields, self.nb_of_bands)                  # (ValueError)
+        aper_par = None
+        if apertures is not None:
+            aper_par = E.aperture_params(apertures, (0.2, 0.5, 0.8) if flux_fractions is None else flux_fractions)   # (ValueError)
         if int(measure_samples) != measure_samples or int(measure_samples) < 0:
             raise ValueError(f"measure_samples must be an integer >= 0, got {measure_samples}")
-        nmc = int(measure_samples)
-        if nmc and (fit or mc):
-            raise ValueError("measure_samples cannot be combined with optimise_positions=True or "
-                             "epistemic_uncertainty_estimation=True: the Monte-Carlo catalogue is a stage of the measuring "
-                             "composite call only (dv_infer_fields_measure_mc)")
-        if nmc and not (measure and on_device):
-            raise ValueError("measure_samples needs measure=True and on_device=True: the Monte-Carlo decodes are measured "
-                             "where they lie in device memory")
+        _refuse_extra(_EXTRAS[0], kw, given, measure, on_device, fit, mc)
         if measure and (fit or mc):
             raise ValueError("measure=True cannot be combined with optimise_positions=True or "
                              "epistemic_uncertainty_estimation=True: the measurement is a stage of the plain composite call "
@@ -797,8 +803,11 @@ class DeblendFieldBatch:
         self.position_fit = None
         self.psf_moments = None
         N = len(starts)
-        if with_psf:
+        if psf is not None:
             psf, psf_index = self._psf_index(psf, psf_index, field_ptr)
+        extras = [x for x in _EXTRAS if x.key in given]
+        c = SimpleNamespace(bands=nb, band=band, sky_sigma=sky_sigma, field_ptr=field_ptr, psf=psf, psf_index=psf_index,
+                            aper_par=aper_par, nmc=int(measure_samples), core=core)
         eng.set_normalise(bool(self.normalise))
         try:
             seed = core.next_seed()
@@ -812,34 +821,13 @@ class DeblendFieldBatch:
                 places = (int((F - cs) / 2) + dd).astype(np.int64)
                 if mc:
                     out = eng.infer_fields_mc_composite(self.field_images, starts, places, field_ptr, **mc_args)
-                elif nmc:
-                    out = eng.infer_fields_measure_mc(self.field_images, starts, field_ptr, places=places if return_fields else None,
-                                                      seed=seed, mc_seed=core.next_seed(), nsamples=nmc,
-                                                      return_fields=bool(return_fields))
-                elif blendedness:
-                    out = eng.infer_fields_measure_blend(self.field_images, starts, field_ptr, places, seed=seed,
-                                                         return_fields=bool(return_fields))
-                elif with_psf:
-                    out = eng.infer_fields_measure_psf(self.field_images, starts, field_ptr, psf, psf_index,
-                                                       places=places if return_fields else None, seed=seed,
-                                                       return_fields=bool(return_fields))
-                elif fit_flux:
-                    out = eng.infer_fields_measure_fit(self.field_images, starts, field_ptr, places, seed=seed, band=band,
-                                                       return_fields=bool(return_fields))
-                elif aperture_data:
-                    out = eng.infer_fields_measure_aper_data(self.field_images, starts, field_ptr, places, seed=seed, band=band,
-                                                             radii=list(aper_par.radii)[:aper_par.n_radii],
-                                                             fractions=list(aper_par.fractions)[:aper_par.n_fractions],
-                                                             return_fields=bool(return_fields))
-                elif with_aper:
-                    out = eng.infer_fields_measure_aper(self.field_images, starts, field_ptr,
-                                                        places=places if return_fields else None, seed=seed,
-                                                        radii=list(aper_par.radii)[:aper_par.n_radii],
-                                                        fractions=list(aper_par.fractions)[:aper_par.n_fractions],
-                                                        return_fields=bool(return_fields))
                 elif measure:
-                    out = eng.infer_fields_measure(self.field_images, starts, field_ptr, places=places if return_fields else None,
-                                                   seed=seed, return_fields=bool(return_fields))
+                    # the plain measuring call, or the call of the one extra given (of the refining one where there are two)
+                    x = extras[-1] if extras else None
+                    call = getattr(eng, x.method if x else "infer_fields_measure")
+                    out = call(self.field_images, starts, field_ptr,
+                               places=places if return_fields or (x and x.places_always) else None, seed=seed,
+                               **(x.kwargs(c) if x else {}), return_fields=bool(return_fields))
                 else:
                     out = eng.infer_fields_composite(self.field_images, starts, places, field_ptr, seed=seed)
             elif mc:
@@ -869,48 +857,15 @@ class DeblendFieldBatch:
         columns = self.DEFAULT_COLUMNS if not on_device else \
             self.ON_DEVICE_EPISTEMIC_COLUMNS if mc else self.ON_DEVICE_COLUMNS
         if measure:
-            from debvader_amd.measure.measurement import catalogue_mc_records, catalogue_records, measure_stamps
-
+            cat = ms.catalogue_records(out["flux"], out["flux_err"], out["shape"], out["iters"], out["status"]) if on_device \
+                else ms.measure_stamps(out["loc"], out["scale"], ctx=self._ctx)
             columns = columns + self.measure_columns(nb)
-            if nmc:
-                columns = columns + self.measure_mc_columns(nb)
-                cat_mc = catalogue_mc_records(out["flux_mc_mean"], out["flux_mc_std"], out["shape_mc_mean"],
-                                              out["shape_mc_std"], out["n_ok"])
-            if blendedness:
-                from debvader_amd.measure.measurement import blend_records
-
-                columns = columns + self.blend_columns()
-                cat_bl = blend_records(out["blend"], out["npix"])
-            if with_psf:
-                from debvader_amd.measure.measurement import psf_records
-
-                columns = columns + self.psf_columns()
-                cat_psf = psf_records(out["regauss"], out["regauss_iters"], out["regauss_status"], out["psf_shape"],
-                                      out["psf_aux"], psf_index)
+            cats = [cat]
+            for x in extras:
+                columns = columns + x.columns(c)
+                cats.append(x.records(out, c))
+            if psf is not None:
                 self.psf_moments = {k: out[k] for k in ("psf_shape", "psf_aux", "psf_iters", "psf_status")}
-            if with_aper:
-                from debvader_amd.measure.measurement import aperture_records
-
-                columns = columns + self.aperture_columns(nb, aper_par.n_radii, aper_par.n_fractions)
-                cat_ap = aperture_records(out["ap_flux"], out["ap_flux_err"], out["ap_area"], out["flux_auto"],
-                                          out["flux_auto_err"], out["kron"], out["flux_rho"], out["aper_flags"],
-                                          out["aper_status"], out["shape"])
-            if aperture_data:
-                from debvader_amd.measure.measurement import aperture_data_records
-
-                columns = columns + self.aperture_data_columns(nb, aper_par.n_radii)
-                cat_ad = aperture_data_records(out["ap_model_sum"], out["ap_data_sum"], out["ap_field_area"],
-                                               out["auto_model_sum"], out["auto_data_sum"], out["auto_field_area"],
-                                               out["ap_flux"], out["ap_area"], out["flux_auto"], out["kron"][:, 2], band=band,
-                                               sky_sigma=sky_sigma, field_ptr=field_ptr)
-            if fit_flux:
-                from debvader_amd.measure.measurement import fit_flux_records
-
-                columns = columns + self.fit_flux_columns(nb)
-                cat_ff = fit_flux_records(out["fit_scale"], out["fit_var"], out["fit_gram"], out["fit_proj"], out["fit_status"],
-                                          out["flux"], sky_sigma=sky_sigma, field_ptr=field_ptr)
-            cat = catalogue_records(out["flux"], out["flux_err"], out["shape"], out["iters"], out["status"]) if on_device \
-                else measure_stamps(out["loc"], out["scale"], ctx=self._ctx)
             # a stamp's pixel (row, col) is the field's pixel start + (row, col); distances count from pixel int(F / 2)
             measured = starts + np.stack([cat["row"], cat["col"]], axis=1) - int(F / 2) if N else np.zeros((0, 2))
         res = []
@@ -924,28 +879,11 @@ class DeblendFieldBatch:
             rec["galaxy_distances_to_center_y"] = dd[lo:hi, 1]
             rec["passed_cuts"] = passed[lo:hi]
             if measure:
-                for k in cat.dtype.names:
-                    rec[k] = cat[k][lo:hi]
+                for part in cats:
+                    for k in part.dtype.names:
+                        rec[k] = part[k][lo:hi]
                 rec["measured_distance_x"] = measured[lo:hi, 0]
                 rec["measured_distance_y"] = measured[lo:hi, 1]
-                if nmc:
-                    for k in cat_mc.dtype.names:
-                        rec[k] = cat_mc[k][lo:hi]
-                if blendedness:
-                    for k in cat_bl.dtype.names:
-                        rec[k] = cat_bl[k][lo:hi]
-                if with_psf:
-                    for k in cat_psf.dtype.names:
-                        rec[k] = cat_psf[k][lo:hi]
-                if with_aper:
-                    for k in cat_ap.dtype.names:
-                        rec[k] = cat_ap[k][lo:hi]
-                if aperture_data:
-                    for k in cat_ad.dtype.names:
-                        rec[k] = cat_ad[k][lo:hi]
-                if fit_flux:
-                    for k in cat_ff.dtype.names:
-                        rec[k] = cat_ff[k][lo:hi]
             if on_device:
                 rec["mse_center"] = mse_center[lo:hi]
                 if mc:

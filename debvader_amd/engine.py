@@ -1311,6 +1311,40 @@ class Engine:
         check(lib.dv_infer_fields_composite(self._h, *args, int(seed), *ptrs))
         return out
 
+    @staticmethod
+    def _measure_places(places, return_fields, always=None):
+        """The placements an infer_fields_measure* call passes on: None in the catalogue-only form, unless its extra composites
+        on the device all the same - `always` is then what to say when they are missing."""
+        if places is None and (always or return_fields):
+            raise ValueError(always or "places are needed to composite the fields; return_fields=False measures without them")
+        return places if always or return_fields else None
+
+    def _fields_measure(self, fn, fields, starts, field_ptr, places, seed, measure, return_fields, residual, mse_center,
+                        extras=None, between=()):
+        """The body the infer_fields_measure* methods share.  fn: the C call; places: what _measure_places gave; measure:
+        (band, sigma0, tol, max_iter); between: what the call takes between seed and params; extras(N, bands): the call's
+        own results in the order of the C ABI, each a pair (dictionary, arguments) - the arguments are what the call takes
+        for it after the catalogue's, parameters first.  Every check comes before the first use of self."""
+        fields, N, args = Engine._field_args(fields, starts, field_ptr, places)
+        nb = fields.shape[3]
+        par = measure_params(*measure, nb)
+        extras = extras(N, nb) if extras else []
+        if return_fields:
+            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
+        else:
+            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
+            ptrs = [None, None, None, _dp(out.get("mse_center"))]
+        if places is None:
+            args = args[:5] + [None] + args[5:]
+        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
+                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
+        ptrs += [_dp(out["flux"]), _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"])]
+        for res, res_args in extras:
+            out.update(res)
+            ptrs += res_args
+        check(fn(self._h, *args, int(seed), *between, C.byref(par), *ptrs))
+        return out
+
     def infer_fields_measure(self, fields, starts, field_ptr, places=None, seed=0, band: int = 2, sigma0: float = 3.0,
                              tol: float = 1e-10, max_iter: int = 200, return_fields=True, residual=True,
                              mse_center=True) -> Dict[str, np.ndarray]:
@@ -1321,21 +1355,9 @@ class Engine:
         scene_measure on the stamps infer_fields returns for the same seed.  return_fields=False is the catalogue-only
         call: no field is composited, allocated or downloaded, `places` is not needed, and the dictionary holds the
         catalogue (and mse_center) only."""
-        if return_fields and places is None:
-            raise ValueError("places are needed to composite the fields; return_fields=False measures without them")
-        fields, N, args = Engine._field_args(fields, starts, field_ptr, places if return_fields else None)
-        par = measure_params(band, sigma0, tol, max_iter, fields.shape[3])
-        if return_fields:
-            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
-        else:
-            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
-            ptrs = [None, None, None, _dp(out.get("mse_center"))]
-            args = args[:5] + [None] + args[5:]
-        out.update(flux=np.zeros((N, fields.shape[3]), np.float64), flux_err=np.zeros((N, fields.shape[3]), np.float64),
-                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
-        check(lib.dv_infer_fields_measure(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
-                                          _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"])))
-        return out
+        places = Engine._measure_places(places, return_fields)
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center)
 
     def infer_cutouts_measure(self, field, starts, places=None, seed=0, **kw) -> Dict[str, np.ndarray]:
         """infer_fields_measure() for one field (F, F, bands): the field-sized results under singular key names."""
@@ -1354,23 +1376,15 @@ class Engine:
         mean stamps, infer_fields_measure's rows, infer_fields_composite's mean fields and the source fields as data.  The
         stamp sums run behind every chunk's measurement, the field sums once a field's composite is complete.  `places` is
         always needed: with return_fields=False the mean field is still composited on the device (and never downloaded)."""
-        if places is None:
-            raise ValueError("places are needed for the blendedness sums, with return_fields=False too")
-        fields, N, args = Engine._field_args(fields, starts, field_ptr, places)
-        nb = fields.shape[3]
-        par = measure_params(band, sigma0, tol, max_iter, nb)
-        if return_fields:
-            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
-        else:
-            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
-            ptrs = [None, None, None, _dp(out.get("mse_center"))]
-        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
-                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32),
-                   blend=np.zeros((N, 4), np.float64), npix=np.zeros(N, np.int32))
-        check(lib.dv_infer_fields_measure_blend(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
-                                                _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]),
-                                                _ip(out["status"]), _dp(out["blend"]), _ip(out["npix"])))
-        return out
+        places = Engine._measure_places(places, return_fields, "places are needed for the blendedness sums, with "
+                                        "return_fields=False too")
+
+        def extras(N, nb):
+            bl = dict(blend=np.zeros((N, 4), np.float64), npix=np.zeros(N, np.int32))
+            return [(bl, [_dp(bl["blend"]), _ip(bl["npix"])])]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_blend, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
 
     def infer_cutouts_measure_blend(self, field, starts, places, seed=0, **kw) -> Dict[str, np.ndarray]:
         """infer_fields_measure_blend() for one field (F, F, bands): the field-sized results under singular key names."""
@@ -1390,30 +1404,20 @@ class Engine:
         infer_fields_measure's rows.  The PSFs (K, ps, ps) are uploaded and measured once; the correction runs behind every
         chunk's measurement on the stamps in device memory.  psf_index (N,) picks every stamp's PSF (None: PSF 0).
         return_fields=False is the catalogue-only call, as there."""
-        if return_fields and places is None:
-            raise ValueError("places are needed to composite the fields; return_fields=False measures without them")
-        fields, N, args = Engine._field_args(fields, starts, field_ptr, places if return_fields else None)
-        nb = fields.shape[3]
-        par = measure_params(band, sigma0, tol, max_iter, nb)
-        psf, index = check_psf_args(psf, psf_index, N, psf_sigma0)
-        if return_fields:
-            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
-        else:
-            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
-            ptrs = [None, None, None, _dp(out.get("mse_center"))]
-            args = args[:5] + [None] + args[5:]
-        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
-                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
-        rg, rg_ptrs = _regauss_out(N, psf.shape[0])
-        out.update(rg)
-        if N == 0:                          # (the library has nothing to run; the PSF rows come from the stamp-level call)
-            empty = self.ctx.scene_regauss(np.zeros((0,) + tuple(self.stamp_shape), np.float32), np.zeros((0, 5)), np.zeros(0, np.int32),
-                                           psf, band=band, psf_sigma0=psf_sigma0, tol=tol, max_iter=max_iter)
-            out.update({k: empty[k] for k in ("psf_shape", "psf_aux", "psf_iters", "psf_status")})
-        check(lib.dv_infer_fields_measure_psf(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
-                                              _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"]),
-                                              _dp(psf), psf.shape[0], psf.shape[1], _ip(index), float(psf_sigma0), *rg_ptrs))
-        return out
+        places = Engine._measure_places(places, return_fields)
+
+        def extras(N, nb):
+            images, index = check_psf_args(psf, psf_index, N, psf_sigma0)
+            rg, rg_ptrs = _regauss_out(N, images.shape[0])
+            if N == 0:                      # (the library has nothing to run; the PSF rows come from the stamp-level call)
+                empty = self.ctx.scene_regauss(np.zeros((0,) + tuple(self.stamp_shape), np.float32), np.zeros((0, 5)),
+                                               np.zeros(0, np.int32), images, band=band, psf_sigma0=psf_sigma0, tol=tol,
+                                               max_iter=max_iter)
+                rg.update({k: empty[k] for k in ("psf_shape", "psf_aux", "psf_iters", "psf_status")})
+            return [(rg, [_dp(images), images.shape[0], images.shape[1], _ip(index), float(psf_sigma0)] + rg_ptrs)]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_psf, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
 
     def infer_cutouts_measure_psf(self, field, starts, psf, psf_index=None, places=None, seed=0, **kw) -> Dict[str, np.ndarray]:
         """infer_fields_measure_psf() for one field (F, F, bands): the field-sized results under singular key names."""
@@ -1434,26 +1438,15 @@ class Engine:
         "flux_auto_err", "kron", "flux_rho", "aper_flags", "aper_status"} - the bits of scene_aperture on infer_fields' mean
         and stddev stamps and infer_fields_measure's rows.  The photometry runs behind every chunk's measurement on the
         stamps in device memory.  return_fields=False is the catalogue-only call, as there."""
-        if return_fields and places is None:
-            raise ValueError("places are needed to composite the fields; return_fields=False measures without them")
-        fields, N, args = Engine._field_args(fields, starts, field_ptr, places if return_fields else None)
-        nb = fields.shape[3]
-        par = measure_params(band, sigma0, tol, max_iter, nb)
-        apar = aperture_params(radii, fractions, subsample, kron_factor, kron_min, kron_limit, bisect_iters)
-        if return_fields:
-            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
-        else:
-            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
-            ptrs = [None, None, None, _dp(out.get("mse_center"))]
-            args = args[:5] + [None] + args[5:]
-        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
-                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
-        ap, ap_ptrs = _aperture_out(N, nb, apar)
-        out.update(ap)
-        check(lib.dv_infer_fields_measure_aper(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
-                                               _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"]),
-                                               C.byref(apar), *ap_ptrs))
-        return out
+        places = Engine._measure_places(places, return_fields)
+
+        def extras(N, nb):
+            apar = aperture_params(radii, fractions, subsample, kron_factor, kron_min, kron_limit, bisect_iters)
+            ap, ap_ptrs = _aperture_out(N, nb, apar)
+            return [(ap, [C.byref(apar)] + ap_ptrs)]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_aper, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
 
     def infer_cutouts_measure_aper(self, field, starts, places=None, seed=0, **kw) -> Dict[str, np.ndarray]:
         """infer_fields_measure_aper() for one field (F, F, bands): the field-sized results under singular key names."""
@@ -1475,27 +1468,16 @@ class Engine:
         infer_fields_measure_aper's rows, infer_fields_composite's mean fields and the source fields as data.  The field sums
         run once a field's composite is complete.  `places` is always needed: with return_fields=False the mean field is still
         composited on the device (and never downloaded)."""
-        if places is None:
-            raise ValueError("places are needed for the apertures on the fields, with return_fields=False too")
-        fields, N, args = Engine._field_args(fields, starts, field_ptr, places)
-        nb = fields.shape[3]
-        par = measure_params(band, sigma0, tol, max_iter, nb)
-        apar = aperture_params(radii, fractions, subsample, kron_factor, kron_min, kron_limit, bisect_iters)
-        if return_fields:
-            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
-        else:
-            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
-            ptrs = [None, None, None, _dp(out.get("mse_center"))]
-        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
-                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
-        ap, ap_ptrs = _aperture_out(N, nb, apar)
-        out.update(ap)
-        af, af_ptrs = _aperture_field_out(N, nb, apar)
-        out.update(af)
-        check(lib.dv_infer_fields_measure_aper_data(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
-                                                    _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]),
-                                                    _ip(out["status"]), C.byref(apar), *ap_ptrs, *af_ptrs))
-        return out
+        places = Engine._measure_places(places, return_fields, "places are needed for the apertures on the fields, with "
+                                        "return_fields=False too")
+
+        def extras(N, nb):
+            apar = aperture_params(radii, fractions, subsample, kron_factor, kron_min, kron_limit, bisect_iters)
+            ap, ap_ptrs = _aperture_out(N, nb, apar)
+            return [(ap, [C.byref(apar)] + ap_ptrs), _aperture_field_out(N, nb, apar)]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_aper_data, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
 
     def infer_cutouts_measure_aper_data(self, field, starts, places, seed=0, **kw) -> Dict[str, np.ndarray]:
         """infer_fields_measure_aper_data() for one field (F, F, bands): the field-sized results under singular key names."""
@@ -1516,25 +1498,15 @@ class Engine:
         the bits of scene_fit_flux on infer_fields_keep's mean stamps and the source fields.  The mean stamps of every chunk
         are kept on the device and the fit runs once a field's composite is complete.  `places` is always needed, with
         return_fields=False too."""
-        if places is None:
-            raise ValueError("places are needed for the flux fit, with return_fields=False too")
-        fields, N, args = Engine._field_args(fields, starts, field_ptr, places)
-        nb = fields.shape[3]
-        par = measure_params(band, sigma0, tol, max_iter, nb)
-        fpar = fit_flux_params(min_pivot, scratch_bytes)
-        if return_fields:
-            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
-        else:
-            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
-            ptrs = [None, None, None, _dp(out.get("mse_center"))]
-        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
-                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
-        ff, ff_ptrs = _fit_flux_out(N, nb)
-        out.update(ff)
-        check(lib.dv_infer_fields_measure_fit(self._h, *args, int(seed), C.byref(par), *ptrs, _dp(out["flux"]),
-                                              _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]), _ip(out["status"]),
-                                              C.byref(fpar), *ff_ptrs))
-        return out
+        places = Engine._measure_places(places, return_fields, "places are needed for the flux fit, with return_fields=False too")
+
+        def extras(N, nb):
+            fpar = fit_flux_params(min_pivot, scratch_bytes)
+            ff, ff_ptrs = _fit_flux_out(N, nb)
+            return [(ff, [C.byref(fpar)] + ff_ptrs)]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_fit, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
 
     def infer_cutouts_measure_fit(self, field, starts, places, seed=0, **kw) -> Dict[str, np.ndarray]:
         """infer_fields_measure_fit() for one field (F, F, bands): the field-sized results under singular key names."""
@@ -1554,27 +1526,13 @@ class Engine:
         scene_measure_mc's {"flux_mc_mean", "flux_mc_std", "shape_mc_mean", "shape_mc_std", "n_ok"} (and the per-sample rows
         with keep_samples=True) - the bits of scene_measure_mc on the stacked stamps infer_mc(cutouts.astype(float32), 1,
         mc_seed + q)[0].  No epistemic field and no eps_norm are computed; return_fields=False is the catalogue-only call."""
-        if return_fields and places is None:
-            raise ValueError("places are needed to composite the fields; return_fields=False measures without them")
+        places = Engine._measure_places(places, return_fields)
         if int(nsamples) < 1:
             raise ValueError(f"nsamples must be at least 1, got {nsamples}")
-        fields, N, args = Engine._field_args(fields, starts, field_ptr, places if return_fields else None)
-        nb = fields.shape[3]
-        par = measure_params(band, sigma0, tol, max_iter, nb)
-        if return_fields:
-            out, ptrs = Engine._composite_out(fields.shape, N, residual, mse_center)
-        else:
-            out = {"mse_center": np.empty((N,), np.float64)} if mse_center else {}
-            ptrs = [None, None, None, _dp(out.get("mse_center"))]
-            args = args[:5] + [None] + args[5:]
-        out.update(flux=np.zeros((N, nb), np.float64), flux_err=np.zeros((N, nb), np.float64),
-                   shape=np.zeros((N, 5), np.float64), iters=np.zeros(N, np.int32), status=np.zeros(N, np.int32))
-        mc, mc_ptrs = _measure_mc_out(N, nb, int(nsamples), keep_samples)
-        out.update(mc)
-        check(lib.dv_infer_fields_measure_mc(self._h, *args, int(seed), int(mc_seed), int(nsamples), C.byref(par), *ptrs,
-                                             _dp(out["flux"]), _dp(out["flux_err"]), _dp(out["shape"]), _ip(out["iters"]),
-                                             _ip(out["status"]), *mc_ptrs))
-        return out
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_mc, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center,
+                                      lambda N, nb: [_measure_mc_out(N, nb, int(nsamples), keep_samples)],
+                                      between=(int(mc_seed), int(nsamples)))
 
     def infer_cutouts_measure_mc(self, field, starts, places=None, seed=0, **kw) -> Dict[str, np.ndarray]:
         """infer_fields_measure_mc() for one field (F, F, bands): the field-sized results under singular key names."""
