@@ -42,6 +42,7 @@
 // indexed band slots, no plane - 352 bytes of static LDS.
 #include "common.h"
 #include "measure_dev.h"
+#include "rows.h"
 
 #include <algorithm>
 #include <cmath>
@@ -501,50 +502,29 @@ int aperture_rows_check(const char* who, const ApertureRows& o, const AperturePa
   return OK;
 }
 
-int ApertureBufs::alloc(int64_t n, const ApertureParams& p, int nb, bool err) {
-  const size_t N = (size_t)n;
-  DV_TRY(ap_flux.alloc(N * p.K * nb));
-  DV_TRY(ap_area.alloc(N * p.K));
-  DV_TRY(flux_auto.alloc(N * nb));
-  if (err) {
-    DV_TRY(ap_err.alloc(N * p.K * nb));
-    DV_TRY(auto_err.alloc(N * nb));
+// the columns of the aperture rows: the circles only with radii, the errors only with a stddev stamp, flux_rho only with
+// fractions
+void aperture_columns(Rows& r, ApertureRows& dev, const ApertureRows& host, const ApertureParams& p, int nb, bool err) {
+  if (p.K > 0) {
+    r.add(dev.ap_flux, host.ap_flux, (size_t)p.K * nb);
+    r.add(dev.ap_area, host.ap_area, p.K);
+    if (err) r.add(dev.ap_err, host.ap_err, (size_t)p.K * nb);
   }
-  DV_TRY(kron.alloc(N * 3));
-  DV_TRY(flux_rho.alloc(N * p.J));
-  DV_TRY(flags.alloc(N));
-  return status.alloc(N);
-}
-
-ApertureRows ApertureBufs::rows() const {
-  return ApertureRows{ap_flux.get(), ap_err.get(), ap_area.get(), flux_auto.get(), auto_err.get(),
-                      kron.get(), flux_rho.get(), flags.get(), status.get()};
+  r.add(dev.flux_auto, host.flux_auto, nb);
+  if (err) r.add(dev.auto_err, host.auto_err, nb);
+  r.add(dev.kron, host.kron, 3);
+  if (p.J > 0) r.add(dev.flux_rho, host.flux_rho, p.J);
+  r.add(dev.flags, host.flags, 1);
+  r.add(dev.status, host.status, 1);
 }
 
 // the rows of `o` that start at stamp r
 ApertureRows aperture_rows_at(const ApertureRows& o, int64_t r, const ApertureParams& p, int nb) {
-  const size_t q = (size_t)r;
-  auto at = [](auto* ptr, size_t off) { return ptr ? ptr + off : ptr; };
-  return ApertureRows{at(o.ap_flux, q * p.K * nb), at(o.ap_err, q * p.K * nb), at(o.ap_area, q * p.K), at(o.flux_auto, q * nb),
-                      at(o.auto_err, q * nb), at(o.kron, q * 3), at(o.flux_rho, q * p.J), at(o.flags, q), at(o.status, q)};
-}
-
-// the first n rows of the device buffers to the host rows `h` (null where the call has no such output)
-int ApertureBufs::download(const ApertureRows& h, int64_t n, const ApertureParams& p, int nb, hipStream_t s) const {
-  const size_t N = (size_t)n, D = sizeof(double);
-  if (N == 0) return OK;
-  if (p.K > 0) {
-    DV_HIP(hipMemcpyAsync(h.ap_flux, ap_flux.get(), N * p.K * nb * D, hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(h.ap_area, ap_area.get(), N * p.K * D, hipMemcpyDeviceToHost, s));
-    if (h.ap_err && ap_err.get()) DV_HIP(hipMemcpyAsync(h.ap_err, ap_err.get(), N * p.K * nb * D, hipMemcpyDeviceToHost, s));
-  }
-  DV_HIP(hipMemcpyAsync(h.flux_auto, flux_auto.get(), N * nb * D, hipMemcpyDeviceToHost, s));
-  if (h.auto_err && auto_err.get()) DV_HIP(hipMemcpyAsync(h.auto_err, auto_err.get(), N * nb * D, hipMemcpyDeviceToHost, s));
-  DV_HIP(hipMemcpyAsync(h.kron, kron.get(), N * 3 * D, hipMemcpyDeviceToHost, s));
-  if (p.J > 0) DV_HIP(hipMemcpyAsync(h.flux_rho, flux_rho.get(), N * p.J * D, hipMemcpyDeviceToHost, s));
-  DV_HIP(hipMemcpyAsync(h.flags, flags.get(), N * sizeof(int), hipMemcpyDeviceToHost, s));
-  DV_HIP(hipMemcpyAsync(h.status, status.get(), N * sizeof(int), hipMemcpyDeviceToHost, s));
-  return OK;
+  ApertureRows v = o;
+  Rows c;
+  aperture_columns(c, v, ApertureRows{}, p, nb, o.auto_err != nullptr);
+  c.advance(r);
+  return v;
 }
 
 // n stamps that lie in device memory with their catalogue rows; every per-galaxy pointer is the row of the first stamp
@@ -563,46 +543,33 @@ int launch_aperture(const float* mean_dev, const float* stddev_dev, const double
   return OK;
 }
 
-// host arrays in, host rows out, in chunks of at most `chunk` stamps (sized by the caller against free device memory)
+// host arrays in, host rows out, a chunk of stamps at a time
 int scene_aperture(const float* mean_h, const float* stddev_h, const double* shape_h, const int32_t* status_h, int64_t N, int cs,
-                   int nb, int band, const ApertureParams& p, const ApertureRows& out_h, int64_t chunk, hipStream_t s) {
+                   int nb, int band, const ApertureParams& p, const ApertureRows& out_h, hipStream_t s) {
   const char* who = "dv_scene_aperture";
   DV_TRY(aperture_check(who, cs, nb, band, p));
   if (N < 0 || (N > 0 && (!mean_h || !shape_h || !status_h))) {
     set_error("%s: mean, shape and status must all be given", who);
     return E_INVALID;
   }
+  DV_TRY(aperture_rows_check(who, out_h, p, stddev_h != nullptr, N));
   if ((stddev_h == nullptr) != (out_h.auto_err == nullptr) || (p.K > 0 && (stddev_h == nullptr) != (out_h.ap_err == nullptr))) {
     set_error("%s: stddev, ap_flux_err and flux_auto_err go together (all given or all null)", who);
     return E_INVALID;
   }
-  DV_TRY(aperture_rows_check(who, out_h, p, stddev_h != nullptr, N));
-  if (N == 0) return OK;
   const size_t stamp = (size_t)cs * cs * nb;
-  chunk = std::max<int64_t>(1, std::min<int64_t>({chunk, N, (int64_t)1 << 20}));
-  DevBuf<float> mean, sd;
-  DevBuf<double> shape;
-  DevBuf<int> status;
-  ApertureBufs bufs;
-  DV_TRY(mean.alloc((size_t)chunk * stamp));
-  if (stddev_h) DV_TRY(sd.alloc((size_t)chunk * stamp));
-  DV_TRY(shape.alloc((size_t)chunk * 5));
-  DV_TRY(status.alloc((size_t)chunk));
-  DV_TRY(bufs.alloc(chunk, p, nb, stddev_h != nullptr));
-  StreamDrain drain(s);
-  for (int64_t base = 0; base < N; base += chunk) {
-    const int n = (int)std::min<int64_t>(chunk, N - base);
-    const size_t b = (size_t)base;
-    DV_HIP(hipMemcpyAsync(mean, mean_h + b * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    if (stddev_h) DV_HIP(hipMemcpyAsync(sd, stddev_h + b * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(shape, shape_h + b * 5, (size_t)n * 5 * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(status, status_h + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_TRY(launch_aperture(mean, stddev_h ? sd.get() : nullptr, shape, status, n, cs, nb, band, p, bufs.rows(), s));
-    DV_TRY(bufs.download(aperture_rows_at(out_h, base, p, nb), n, p, nb, s));
-    DV_HIP(hipStreamSynchronize(s));                   // the device buffers are reused by the next chunk
-  }
-  drain.dismiss();
-  return OK;
+  float *mean = nullptr, *sd = nullptr;
+  double* shape = nullptr;
+  int* status = nullptr;
+  ApertureRows d{};
+  Rows in, out;
+  in.add(mean, mean_h, stamp);
+  if (stddev_h) in.add(sd, stddev_h, stamp);
+  in.add(shape, shape_h, 5);
+  in.add(status, status_h, 1);
+  aperture_columns(out, d, out_h, p, nb, stddev_h != nullptr);
+  return walk_rows(N, (int64_t)1 << 20, 0, in, out, s,
+                   [&](int64_t, int n) { return launch_aperture(mean, sd, shape, status, n, cs, nb, band, p, d, s); });
 }
 
 // ---- the same apertures on the fields: host side ---------------------------------------------------------------
@@ -618,41 +585,24 @@ int aperture_field_rows_check(const char* who, const ApertureFieldRows& o, const
   return OK;
 }
 
-int ApertureFieldBufs::alloc(int64_t n, const ApertureParams& p, int nb) {
-  const size_t N = (size_t)n;
-  DV_TRY(ap_model.alloc(N * p.K * nb));
-  DV_TRY(ap_data.alloc(N * p.K * nb));
-  DV_TRY(ap_farea.alloc(N * p.K));
-  DV_TRY(auto_model.alloc(N * nb));
-  DV_TRY(auto_data.alloc(N * nb));
-  return auto_farea.alloc(N);
-}
-
-ApertureFieldRows ApertureFieldBufs::rows() const {
-  return ApertureFieldRows{ap_model.get(), ap_data.get(), ap_farea.get(), auto_model.get(), auto_data.get(), auto_farea.get()};
+void aperture_field_columns(Rows& r, ApertureFieldRows& dev, const ApertureFieldRows& host, const ApertureParams& p, int nb) {
+  if (p.K > 0) {
+    r.add(dev.ap_model, host.ap_model, (size_t)p.K * nb);
+    r.add(dev.ap_data, host.ap_data, (size_t)p.K * nb);
+    r.add(dev.ap_farea, host.ap_farea, p.K);
+  }
+  r.add(dev.auto_model, host.auto_model, nb);
+  r.add(dev.auto_data, host.auto_data, nb);
+  r.add(dev.auto_farea, host.auto_farea, 1);
 }
 
 // the rows of `o` that start at galaxy r
 ApertureFieldRows aperture_field_rows_at(const ApertureFieldRows& o, int64_t r, const ApertureParams& p, int nb) {
-  const size_t q = (size_t)r;
-  auto at = [](double* ptr, size_t off) { return ptr ? ptr + off : ptr; };
-  return ApertureFieldRows{at(o.ap_model, q * p.K * nb), at(o.ap_data, q * p.K * nb), at(o.ap_farea, q * p.K),
-                           at(o.auto_model, q * nb), at(o.auto_data, q * nb), at(o.auto_farea, q)};
-}
-
-// the first n rows of the device buffers to the host rows `h`
-int ApertureFieldBufs::download(const ApertureFieldRows& h, int64_t n, const ApertureParams& p, int nb, hipStream_t s) const {
-  const size_t N = (size_t)n, D = sizeof(double);
-  if (N == 0) return OK;
-  if (p.K > 0) {
-    DV_HIP(hipMemcpyAsync(h.ap_model, ap_model.get(), N * p.K * nb * D, hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(h.ap_data, ap_data.get(), N * p.K * nb * D, hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(h.ap_farea, ap_farea.get(), N * p.K * D, hipMemcpyDeviceToHost, s));
-  }
-  DV_HIP(hipMemcpyAsync(h.auto_model, auto_model.get(), N * nb * D, hipMemcpyDeviceToHost, s));
-  DV_HIP(hipMemcpyAsync(h.auto_data, auto_data.get(), N * nb * D, hipMemcpyDeviceToHost, s));
-  DV_HIP(hipMemcpyAsync(h.auto_farea, auto_farea.get(), N * D, hipMemcpyDeviceToHost, s));
-  return OK;
+  ApertureFieldRows v = o;
+  Rows c;
+  aperture_field_columns(c, v, ApertureFieldRows{}, p, nb);
+  c.advance(r);
+  return v;
 }
 
 // n galaxies whose fields are complete, with their catalogue and aperture rows, placements and fields in device memory; every
@@ -672,12 +622,12 @@ int launch_aperture_field(const double* shape_dev, const int* status_dev, const 
   return OK;
 }
 
-// host arrays in, host rows out: galaxies base .. base + n of at most `chunk` galaxies and at most `gmax` fields at a time, the
-// model (and data) fields they lie in uploaded beside their rows
+// host arrays in, host rows out: a chunk of galaxies at a time, the model (and data) fields they lie in uploaded beside
+// their rows
 int scene_aperture_fields(const double* shape_h, const int32_t* status_h, const int32_t* places_h, const int64_t* field_ptr,
                           const double* kron_h, const int32_t* aper_status_h, int64_t N, int cs, int nb, const double* model_h,
                           const double* data_h, int M, int F, const ApertureParams& p, const ApertureFieldRows& out_h,
-                          int64_t chunk, int64_t gmax, int device, hipStream_t s) {
+                          int device, hipStream_t s) {
   const char* who = "dv_scene_aperture_fields";
   DV_TRY(aperture_check(who, cs, nb, 0, p));
   if (N < 0 || M < 0 || !field_ptr ||
@@ -686,87 +636,25 @@ int scene_aperture_fields(const double* shape_h, const int32_t* status_h, const 
     return E_INVALID;
   }
   DV_TRY(aperture_field_rows_check(who, out_h, p, N));
-  if (N >= ((int64_t)1 << 31)) {
-    set_error("%s: %ld galaxies, at most 2^31 - 1 per call", who, (long)N);
-    return E_INVALID;
-  }
-  if (F < 1 || F > 32768) {
-    set_error("%s: fields of %d pixels, 1 .. 32768 are taken", who, F);
-    return E_INVALID;
-  }
-  if (field_ptr[0] != 0 || field_ptr[M] != N) {
-    set_error("%s: field_ptr must run from 0 to the number of galaxies (%ld), got %ld .. %ld", who, (long)N,
-              (long)field_ptr[0], (long)field_ptr[M]);
-    return E_INVALID;
-  }
-  for (int f = 0; f < M; ++f)                        // the whole table before anything is indexed by it
-    if (field_ptr[f + 1] < field_ptr[f]) {
-      set_error("%s: field_ptr decreases at field %d (%ld after %ld)", who, f, (long)field_ptr[f + 1], (long)field_ptr[f]);
-      return E_INVALID;
-    }
-  for (int64_t i = 0; i < N; ++i) {
-    const int pr = places_h[2 * i], pc = places_h[2 * i + 1];
-    if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
-      set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
-      return E_INVALID;
-    }
-  }
-  if (N == 0) return OK;
   std::vector<int32_t> sfield;                       // every galaxy's field
-  try {
-    sfield.resize((size_t)N);
-  } catch (const std::bad_alloc&) {
-    set_error("%s: no host memory for the field table of %ld galaxies", who, (long)N);
-    return E_NOMEM;
-  }
-  for (int f = 0; f < M; ++f)
-    for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) sfield[(size_t)i] = f;
-  const size_t felems = (size_t)F * F * nb;
+  DV_TRY(field_tables(who, "galaxies", M, field_ptr, N, &F, places_h, &sfield, nullptr));
+  if (N == 0) return OK;
   DV_HIP(hipSetDevice(device));
-  if (chunk <= 0 || gmax <= 0) {
-    size_t free_b = 0, total_b = 0;
-    DV_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t per_stamp = 8 * sizeof(double) + 5 * sizeof(int) + ApertureFieldBufs::bytes_per_stamp(p, nb);
-    chunk = (int64_t)(free_b / 4 / per_stamp);
-    gmax = (int64_t)(free_b / 4 / (felems * sizeof(double) * (data_h ? 2 : 1)));
-  }
-  chunk = std::max<int64_t>(1, std::min<int64_t>({chunk, N, (int64_t)1 << 20}));
-  gmax = std::max<int64_t>(1, std::min<int64_t>(gmax, M));
-  DevBuf<double> shape, kron, model, data;
-  DevBuf<int> status, astatus, places, sf;
-  ApertureFieldBufs bufs;
-  DV_TRY(shape.alloc((size_t)chunk * 5));
-  DV_TRY(kron.alloc((size_t)chunk * 3));
-  DV_TRY(status.alloc((size_t)chunk));
-  DV_TRY(astatus.alloc((size_t)chunk));
-  DV_TRY(places.alloc((size_t)chunk * 2));
-  DV_TRY(sf.alloc((size_t)chunk));
-  DV_TRY(bufs.alloc(chunk, p, nb));
-  DV_TRY(model.alloc((size_t)gmax * felems));
-  if (data_h) DV_TRY(data.alloc((size_t)gmax * felems));
-  StreamDrain drain(s);
-  for (int64_t base = 0; base < N;) {
-    const int fa = sfield[(size_t)base];
-    int n = 0;                                         // galaxies of at most gmax fields from fa on (at least one)
-    while (n < chunk && base + n < N && (int64_t)sfield[(size_t)(base + n)] - fa < gmax) ++n;
-    const size_t nf = (size_t)(sfield[(size_t)(base + n - 1)] - fa + 1), b = (size_t)base;
-    DV_HIP(hipMemcpyAsync(model, model_h + (size_t)fa * felems, nf * felems * sizeof(double), hipMemcpyHostToDevice, s));
-    if (data_h)
-      DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, nf * felems * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(shape, shape_h + b * 5, (size_t)n * 5 * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(kron, kron_h + b * 3, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(status, status_h + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(astatus, aper_status_h + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(places, places_h + b * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(sf, sfield.data() + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_TRY(launch_aperture_field(shape, status, kron, astatus, places, sf, fa, n, cs, nb, F, model,
-                                 data_h ? data.get() : nullptr, p, bufs.rows(), s));
-    DV_TRY(bufs.download(aperture_field_rows_at(out_h, base, p, nb), n, p, nb, s));
-    DV_HIP(hipStreamSynchronize(s));                   // the device buffers are reused by the next chunk
-    base += n;
-  }
-  drain.dismiss();
-  return OK;
+  double *shape = nullptr, *kron = nullptr;
+  int *status = nullptr, *astatus = nullptr, *places = nullptr, *sf = nullptr;
+  ApertureFieldRows d{};
+  Rows in, out;
+  in.add(shape, shape_h, 5);
+  in.add(kron, kron_h, 3);
+  in.add(status, status_h, 1);
+  in.add(astatus, aper_status_h, 1);
+  in.add(places, places_h, 2);
+  in.add(sf, sfield.data(), 1);
+  aperture_field_columns(out, d, out_h, p, nb);
+  FieldStacks f{model_h, data_h, (size_t)F * F * nb, M};
+  return walk_field_rows(N, sfield.data(), f, in, out, s, [&](int64_t, int n, int fa) {
+    return launch_aperture_field(shape, status, kron, astatus, places, sf, fa, n, cs, nb, F, f.model_d, f.data_d, p, d, s);
+  });
 }
 
 }  // namespace dv

@@ -23,6 +23,8 @@
 // galaxy's row has the same bits wherever it sits in a batch, and for a galaxy alone in its field - T holds exactly its
 // widened stamp values - A and Bm have the same bits.  No atomics; thread 0 writes with ordinary stores.
 #include "common.h"
+#include "measure_dev.h"
+#include "rows.h"
 
 #include <algorithm>
 #include <cmath>
@@ -35,36 +37,15 @@ namespace dv {
 namespace {
 constexpr int BL_THREADS = 256;
 
-// sum of v over the workgroup, the same order on every call; every thread gets the result (measure.hip's ms_block_sum)
-template <int K>
-__device__ __forceinline__ void bl_block_sum(double (&v)[K], double* s_red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-  }
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) s_red[wave * K + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = ((s_red[k] + s_red[K + k]) + (s_red[2 * K + k] + s_red[3 * K + k]));
-}
-
-__device__ __forceinline__ bool bl_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN
-
 struct BlWeight { double r0, c0, qa, qb, qc; };
 
 // the weight of a catalogue row; false: the row is ineligible (the same answer in every thread of the workgroup)
 __device__ __forceinline__ bool bl_weight(const double* __restrict__ sh, int st, BlWeight& w) {
   if (st != 0 && st != 2) return false;
   const double r0 = sh[0], c0 = sh[1], Mrr = sh[2], Mrc = sh[3], Mcc = sh[4];
-  if (!(bl_finite(r0) && bl_finite(c0) && bl_finite(Mrr) && bl_finite(Mrc) && bl_finite(Mcc))) return false;
+  if (!(ms_finite(r0) && ms_finite(c0) && ms_finite(Mrr) && ms_finite(Mrc) && ms_finite(Mcc))) return false;
   const double det = Mrr * Mcc - Mrc * Mrc;
-  if (!(bl_finite(det) && det > 1e-6)) return false;
+  if (!(ms_finite(det) && det > 1e-6)) return false;
   w.r0 = r0;
   w.c0 = c0;
   w.qa = -0.5 * Mcc / det;
@@ -105,7 +86,7 @@ __global__ __launch_bounds__(BL_THREADS) void blend_child_kernel(const float* __
     a[0] += g;
     a[1] += g * (double)P[(long)e * nb];
   }
-  bl_block_sum<2>(a, s_red);
+  ms_block_sum<2>(a, s_red);
   if (threadIdx.x == 0) {
     // rows / columns of the stamp inside the field: [max(0, -p), min(cs, F - p))
     const int nr = min(cs, F - pr) - max(0, -pr), nc = min(cs, F - pc) - max(0, -pc);
@@ -140,7 +121,7 @@ __global__ __launch_bounds__(BL_THREADS) void blend_parent_kernel(const double* 
     a[0] += g * T[fe];
     if (D) a[1] += g * D[fe];
   }
-  bl_block_sum<2>(a, s_red);
+  ms_block_sum<2>(a, s_red);
   if (threadIdx.x == 0) {
     blend[gi * 4 + 2] = a[0];
     blend[gi * 4 + 3] = D ? a[1] : __longlong_as_double(0x7ff8000000000000LL);
@@ -214,7 +195,7 @@ __global__ __launch_bounds__(BL_THREADS) void blend_set_kernel(const double* __r
     a[2] += g * x;
     a[3] += g * xx;
   }
-  bl_block_sum<4>(a, s_red);
+  ms_block_sum<4>(a, s_red);
   if (threadIdx.x == 0) {
     sums[gi * 4 + 0] = a[0];
     sums[gi * 4 + 1] = D ? a[1] : nan;
@@ -282,85 +263,39 @@ int launch_blend_set(const double* shape_dev, const int* status_dev, const int* 
   return OK;
 }
 
-// host arrays in, host rows out: stamps base .. base + n of at most `chunk` stamps and at most `gmax` fields at a time, the
-// model (and data) fields they lie in uploaded beside them
+void blend_columns(Rows& r, BlendRows& dev, const BlendRows& host) {
+  r.add(dev.blend, host.blend, 4);
+  r.add(dev.npix, host.npix, 1);
+}
+
+// host arrays in, host rows out: a chunk of stamps at a time, the model (and data) fields they lie in uploaded beside them
 int scene_blend(const float* stamps_h, const double* shape_h, const int32_t* status_h, const int32_t* places_h,
                 const int64_t* field_ptr, int64_t N, int cs, int nb, int band, const double* model_h, const double* data_h,
-                int M, int F, double* blend_h, int32_t* npix_h, int64_t chunk, int64_t gmax, hipStream_t s) {
+                int M, int F, const BlendRows& out_h, hipStream_t s) {
   const char* who = "dv_scene_blend";
   if (N < 0 || M < 0 || !field_ptr ||
-      (N > 0 && (!stamps_h || !shape_h || !status_h || !places_h || !model_h || !blend_h || !npix_h))) {
+      (N > 0 && (!stamps_h || !shape_h || !status_h || !places_h || !model_h || !out_h.blend || !out_h.npix))) {
     set_error("%s: stamps, shape, status, places, field_ptr, model_fields, blend and npix must all be given", who);
     return E_INVALID;
   }
-  if (N >= ((int64_t)1 << 31)) {
-    set_error("%s: %ld stamps, at most 2^31 - 1 per call", who, (long)N);
-    return E_INVALID;
-  }
-  if (F < 1 || F > 32768) {
-    set_error("%s: fields of %d pixels, 1 .. 32768 are taken", who, F);
-    return E_INVALID;
-  }
-  if (field_ptr[0] != 0 || field_ptr[M] != N) {
-    set_error("%s: field_ptr must run from 0 to the number of stamps (%ld), got %ld .. %ld", who, (long)N,
-              (long)field_ptr[0], (long)field_ptr[M]);
-    return E_INVALID;
-  }
-  for (int f = 0; f < M; ++f)                        // the whole table before anything is indexed by it
-    if (field_ptr[f + 1] < field_ptr[f]) {
-      set_error("%s: field_ptr decreases at field %d (%ld after %ld)", who, f, (long)field_ptr[f + 1], (long)field_ptr[f]);
-      return E_INVALID;
-    }
-  std::vector<int32_t> sfield((size_t)N);
-  for (int f = 0; f < M; ++f) {
-    for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) {
-      sfield[(size_t)i] = f;
-      const int pr = places_h[2 * i], pc = places_h[2 * i + 1];
-      if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
-        set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
-        return E_INVALID;
-      }
-    }
-  }
-  if (N == 0) return OK;
-  const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
-  chunk = std::max<int64_t>(1, std::min<int64_t>({chunk, N, (int64_t)1 << 20}));
-  gmax = std::max<int64_t>(1, std::min<int64_t>(gmax, M));
-  DevBuf<float> stamps;
-  DevBuf<double> shape, blend, model, data;
-  DevBuf<int> status, places, sf, npix;
-  DV_TRY(stamps.alloc((size_t)chunk * stamp));
-  DV_TRY(shape.alloc((size_t)chunk * 5));
-  DV_TRY(blend.alloc((size_t)chunk * 4));
-  DV_TRY(status.alloc((size_t)chunk));
-  DV_TRY(places.alloc((size_t)chunk * 2));
-  DV_TRY(sf.alloc((size_t)chunk));
-  DV_TRY(npix.alloc((size_t)chunk));
-  DV_TRY(model.alloc((size_t)gmax * felems));
-  if (data_h) DV_TRY(data.alloc((size_t)gmax * felems));
-  StreamDrain drain(s);
-  for (int64_t base = 0; base < N;) {
-    const int fa = sfield[(size_t)base];
-    int n = 0;                                         // stamps of at most gmax fields from fa on (at least one)
-    while (n < chunk && base + n < N && (int64_t)sfield[(size_t)(base + n)] - fa < gmax) ++n;
-    const size_t nf = (size_t)(sfield[(size_t)(base + n - 1)] - fa + 1), b = (size_t)base;
-    DV_HIP(hipMemcpyAsync(model, model_h + (size_t)fa * felems, nf * felems * sizeof(double), hipMemcpyHostToDevice, s));
-    if (data_h)
-      DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, nf * felems * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(stamps, stamps_h + b * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(shape, shape_h + b * 5, (size_t)n * 5 * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(status, status_h + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(places, places_h + b * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(sf, sfield.data() + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_TRY(launch_blend_child(stamps, shape, status, places, n, cs, nb, band, F, blend, npix, s));
-    DV_TRY(launch_blend_parent(shape, status, places, sf, fa, n, cs, nb, band, F, model, data_h ? data.get() : nullptr, blend, s));
-    DV_HIP(hipMemcpyAsync(blend_h + b * 4, blend, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(npix_h + b, npix, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));                   // the device buffers are reused by the next chunk
-    base += n;
-  }
-  drain.dismiss();
-  return OK;
+  std::vector<int32_t> sfield;
+  DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, &sfield, nullptr));
+  float* stamps = nullptr;
+  double* shape = nullptr;
+  int *status = nullptr, *places = nullptr, *sf = nullptr;
+  BlendRows d{};
+  Rows in, out;
+  in.add(stamps, stamps_h, (size_t)cs * cs * nb);
+  in.add(shape, shape_h, 5);
+  in.add(status, status_h, 1);
+  in.add(places, places_h, 2);
+  in.add(sf, sfield.data(), 1);
+  blend_columns(out, d, out_h);
+  FieldStacks f{model_h, data_h, (size_t)F * F * nb, M};
+  return walk_field_rows(N, sfield.data(), f, in, out, s, [&](int64_t, int n, int fa) {
+    DV_TRY(launch_blend_child(stamps, shape, status, places, n, cs, nb, band, F, d.blend, d.npix, s));
+    return launch_blend_parent(shape, status, places, sf, fa, n, cs, nb, band, F, f.model_d, f.data_d, d.blend, s);
+  });
 }
 
 }  // namespace dv

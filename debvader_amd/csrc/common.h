@@ -286,15 +286,15 @@ int launch_posfit_band_f32(const float* src_dev, long npix, int nb, int band, do
 // catalogue measurement (measure.hip): per-band fluxes and errors and the adaptive moments of band `band` of
 // float32 mean / stddev stamps [.][cs][cs][nb]; flux / flux_err [.][nb], shape [.][5] = {r0, c0, Mrr, Mrc, Mcc}, iters and
 // status [.].  measure_check: the refusals, before any GPU work.  launch_measure: n stamps in device memory, the output
-// pointers at their first row (stddev is read only when flux_err is wanted).  scene_measure: host arrays, at most `chunk`
-// stamps on the device at a time.
+// pointers at their first row (stddev is read only when flux_err is wanted).  CatRows: the output rows, device or host.
+// scene_measure: host arrays, a chunk of stamps on the device at a time (walk_rows, rows.h).
+struct CatRows { double *flux, *flux_err, *shape; int *iters, *status; };
 int measure_check(const char* who, int cs, int nb, int band, double sigma0, double tol, int max_iter);
 int launch_measure(const float* mean_dev, const float* stddev_dev, int n, int cs, int nb, int band, double sigma0,
                    double tol, int max_iter, double* flux_dev, double* flux_err_dev, double* shape_dev, int* iters_dev,
                    int* status_dev, hipStream_t s);
 int scene_measure(const float* mean_h, const float* stddev_h, int64_t N, int cs, int nb, int band, double sigma0, double tol,
-                  int max_iter, double* flux_h, double* flux_err_h, double* shape_h, int32_t* iters_h, int32_t* status_h,
-                  int64_t chunk, hipStream_t s);
+                  int max_iter, const CatRows& out_h, hipStream_t s);
 // Monte-Carlo catalogue (measure.hip): every sample stamp of a decoder pass measured without a stddev stamp into
 // scratch rows, the rows folded per galaxy (Welford, ascending sample order) into means and standard deviations of the nb
 // fluxes and of the 8 shape quantities {row, col, Mrr, Mrc, Mcc, sigma, e1, e2}.  McScratch: the rows of one pass (device).
@@ -302,7 +302,7 @@ int scene_measure(const float* mean_h, const float* stddev_h, int64_t N, int cs,
 // per-sample rows [.][S][nb], [.][S][5], [.][S] are given together or not at all.  launch_measure_mc_samples: `rows` stamps
 // of a pass.  launch_measure_mc_fold: the pass's n galaxies x reps samples (row r * n + g = sample k0 + r of galaxy g) into
 // rows row0 .. of the state; the pass with the last sample writes the standard deviations.  scene_measure_mc: host samples
-// [S][N][cs][cs][nb] in, host results (an McState of host pointers) out, at most `chunk` galaxies on the device at a time.
+// [S][N][cs][cs][nb] in, host results (an McState of host pointers) out, a chunk of galaxies on the device at a time.
 struct McScratch { double *flux, *shape; int *iters, *status; };
 struct McState {
   double *flux_mean, *flux_std, *shape_mean, *shape_std;
@@ -315,15 +315,17 @@ int launch_measure_mc_samples(const float* pass_dev, int rows, int cs, int nb, i
 int launch_measure_mc_fold(const McScratch& w, int n, int reps, int k0, int S, int nb, const McState& st, int64_t row0,
                            hipStream_t s);
 int scene_measure_mc(const float* samples_h, int S, int64_t N, int cs, int nb, int band, double sigma0, double tol,
-                     int max_iter, const McState& out_h, int64_t chunk, hipStream_t s);
+                     int max_iter, const McState& out_h, hipStream_t s);
 // blendedness sums (blend.hip): per galaxy {W, A, Bm, Bd} = the sums of g, g P, g T, g D over the stamp pixels
 // inside the field, g the Gaussian of the galaxy's adaptive moments; an ineligible row (status not 0 or 2, a non-finite
 // shape value, det <= 1e-6) gets four NaN and npix -1.  launch_blend_child: W, A and npix of n stamps in device memory
 // (and the NaN of the ineligible rows), every per-galaxy pointer at the first stamp's row.  launch_blend_parent: Bm and Bd
 // of n galaxies whose fields are complete: sfield_dev [n] their fields, model_dev / data_dev stacks [.][F][F][nb] that start
 // at field f0 (data_dev null: Bd = NaN).  launch_blend_composite_mean: the mean sum of launch_scene_composite_chunk alone
-// (the same additions in the same order, so the same bits), for a call that keeps no stddev field.  scene_blend: host
-// arrays, at most `chunk` stamps and the `gmax` fields they may span on the device at a time.
+// (the same additions in the same order, so the same bits), for a call that keeps no stddev field.  BlendRows: the output
+// rows [.][4], [.], device or host.  scene_blend: host arrays, a chunk of stamps and the fields they span on the device at a
+// time (walk_field_rows, rows.h).
+struct BlendRows { double* blend; int* npix; };
 int blend_check(const char* who, int cs, int nb, int band);
 int launch_blend_child(const float* stamps_dev, const double* shape_dev, const int* status_dev, const int* places_dev, int n,
                        int cs, int nb, int band, int F, double* blend_dev, int* npix_dev, hipStream_t s);
@@ -340,14 +342,16 @@ int launch_blend_set(const double* shape_dev, const int* status_dev, const int* 
                      double* sums_dev, hipStream_t s);
 int scene_blend(const float* stamps_h, const double* shape_h, const int32_t* status_h, const int32_t* places_h,
                 const int64_t* field_ptr, int64_t N, int cs, int nb, int band, const double* model_h, const double* data_h,
-                int M, int F, double* blend_h, int32_t* npix_h, int64_t chunk, int64_t gmax, hipStream_t s);
+                int M, int F, const BlendRows& out_h, hipStream_t s);
 // PSF-corrected shapes (regauss.hip): per galaxy the adaptive moments {r', c', Mrr', Mrc', Mcc'} and the kurtosis
 // rho4 of the re-Gaussianized band plane, iterations and status (0 / 2 / 3 of the iteration; 4 an ineligible catalogue row,
 // 5 no usable PSF, 6 a galaxy its PSF does not resolve: six NaN, 0 iterations).  regauss_check: the refusals, before any GPU
 // work.  RegaussPsf: the K PSF images of a call in device memory with their rows - shape [K][5], aux [K][3] = {A_P, FQ,
 // rho4}, iters, status - and residuals eps [K][ps][ps]; measure() uploads and measures them on a stream, once per call.
 // launch_regauss: n stamps in device memory with their catalogue rows and PSF indices, every per-galaxy pointer at the
-// first stamp's row.  scene_regauss: host arrays, at most `chunk` stamps on the device at a time.
+// first stamp's row.  RegaussRows: the output rows [.][6], [.], [.], device or host.  scene_regauss: host arrays, a chunk of
+// stamps on the device at a time.
+struct RegaussRows { double* out; int *iters, *status; };
 int regauss_check(const char* who, int cs, int nb, int band, int K, int ps, double psf_sigma0, double tol, int max_iter);
 size_t regauss_lds_bytes(int cs, int ps);
 struct RegaussPsf {
@@ -363,17 +367,16 @@ int launch_regauss(const float* stamps_dev, const double* shape_dev, const int* 
                    int* iters_dev, int* ostatus_dev, hipStream_t s);
 int scene_regauss(const float* stamps_h, const double* shape_h, const int32_t* status_h, const int32_t* psf_index_h, int64_t N,
                   int cs, int nb, int band, const double* psf_h, int K, int ps, double psf_sigma0, double tol, int max_iter,
-                  double* out_h, int32_t* iters_h, int32_t* ostatus_h, double* psf_shape_h, double* psf_aux_h,
-                  int32_t* psf_iters_h, int32_t* psf_status_h, int64_t chunk, hipStream_t s);
+                  const RegaussRows& out_h, double* psf_shape_h, double* psf_aux_h, int32_t* psf_iters_h,
+                  int32_t* psf_status_h, hipStream_t s);
 // aperture photometry (aperture.hip): per galaxy the fluxes, errors and areas of K circular apertures, the Kron
 // radius {r1, rho_auto, auto_area}, the flux and error in the automatic ellipse, J flux radii in units of the moment ellipse,
 // flags and a status (0; 4 an ineligible catalogue row: every float NaN; 7 no Kron radius: the Kron outputs NaN).
 // ApertureParams: dv_aperture_params as the kernel takes it.  ApertureRows: the output rows, device or host - ap_flux / ap_err
 // [.][K][nb], ap_area [.][K], flux_auto / auto_err [.][nb], kron [.][3], flux_rho [.][J], flags, status [.]; the two errors are
 // null without a stddev stamp.  aperture_check: the refusals, before any GPU work; aperture_rows_check: a missing output.
-// ApertureBufs: the rows of n stamps in device memory.  launch_aperture: n stamps in device memory with their catalogue rows,
-// every per-galaxy pointer at the first stamp's row.  scene_aperture: host arrays, at most `chunk` stamps on the device at a
-// time.
+// launch_aperture: n stamps in device memory with their catalogue rows, every per-galaxy pointer at the first stamp's row.
+// scene_aperture: host arrays, a chunk of stamps on the device at a time.
 constexpr int AP_MAX_RADII = 8, AP_MAX_FRACTIONS = 4;
 struct ApertureParams {
   int K, J, subsample, bisect_iters;
@@ -388,40 +391,20 @@ int aperture_check(const char* who, int cs, int nb, int band, const AperturePara
 int aperture_rows_check(const char* who, const ApertureRows& o, const ApertureParams& p, bool err, int64_t n);
 size_t aperture_lds_bytes(int cs);
 ApertureRows aperture_rows_at(const ApertureRows& o, int64_t r, const ApertureParams& p, int nb);
-struct ApertureBufs {
-  DevBuf<double> ap_flux, ap_err, ap_area, flux_auto, auto_err, kron, flux_rho;
-  DevBuf<int> flags, status;
-  static size_t bytes_per_stamp(const ApertureParams& p, int nb) {
-    return ((size_t)(2 * p.K + 2) * nb + p.K + 3 + p.J) * sizeof(double) + 2 * sizeof(int);
-  }
-  int alloc(int64_t n, const ApertureParams& p, int nb, bool err);
-  ApertureRows rows() const;
-  int download(const ApertureRows& h, int64_t n, const ApertureParams& p, int nb, hipStream_t s) const;
-};
 int launch_aperture(const float* mean_dev, const float* stddev_dev, const double* shape_dev, const int* status_dev, int n, int cs,
                     int nb, int band, const ApertureParams& p, const ApertureRows& rows, hipStream_t s);
 int scene_aperture(const float* mean_h, const float* stddev_h, const double* shape_h, const int32_t* status_h, int64_t N, int cs,
-                   int nb, int band, const ApertureParams& p, const ApertureRows& out_h, int64_t chunk, hipStream_t s);
+                   int nb, int band, const ApertureParams& p, const ApertureRows& out_h, hipStream_t s);
 // the same apertures on the fields (aperture.hip): per galaxy the sums of n T, n D and n over the stamp pixels of
 // positive count that lie inside the field, T the completed mean field and D the observed field of its field, for the K
 // circles and the automatic ellipse of radius kron[1].  ApertureFieldRows: the output rows, device or host - ap_model / ap_data
 // [.][K][nb], ap_farea [.][K], auto_model / auto_data [.][nb], auto_farea [.].  launch_aperture_field: n galaxies whose fields
 // are complete, every per-galaxy pointer at the first galaxy's row: sfield_dev [n] their fields, model_dev / data_dev stacks
-// [.][F][F][nb] that start at field f0 (data_dev null: the data sums are NaN).  scene_aperture_fields: host arrays, at most
-// `chunk` galaxies and the `gmax` fields they may span on the device at a time (either 0: a quarter of free device memory for
-// a chunk's rows, a quarter for the fields they lie in, taken after the refusals).
+// [.][F][F][nb] that start at field f0 (data_dev null: the data sums are NaN).  scene_aperture_fields: host arrays, a chunk of
+// galaxies and the fields they span on the device at a time.
 struct ApertureFieldRows { double *ap_model, *ap_data, *ap_farea, *auto_model, *auto_data, *auto_farea; };
 int aperture_field_rows_check(const char* who, const ApertureFieldRows& o, const ApertureParams& p, int64_t n);
 ApertureFieldRows aperture_field_rows_at(const ApertureFieldRows& o, int64_t r, const ApertureParams& p, int nb);
-struct ApertureFieldBufs {
-  DevBuf<double> ap_model, ap_data, ap_farea, auto_model, auto_data, auto_farea;
-  static size_t bytes_per_stamp(const ApertureParams& p, int nb) {
-    return ((size_t)(2 * p.K + 2) * nb + p.K + 1) * sizeof(double);
-  }
-  int alloc(int64_t n, const ApertureParams& p, int nb);
-  ApertureFieldRows rows() const;
-  int download(const ApertureFieldRows& h, int64_t n, const ApertureParams& p, int nb, hipStream_t s) const;
-};
 int launch_aperture_field(const double* shape_dev, const int* status_dev, const double* kron_dev, const int* aper_status_dev,
                           const int* places_dev, const int* sfield_dev, int f0, int n, int cs, int nb, int F,
                           const double* model_dev, const double* data_dev, const ApertureParams& p,
@@ -429,7 +412,7 @@ int launch_aperture_field(const double* shape_dev, const int* status_dev, const 
 int scene_aperture_fields(const double* shape_h, const int32_t* status_h, const int32_t* places_h, const int64_t* field_ptr,
                           const double* kron_h, const int32_t* aper_status_h, int64_t N, int cs, int nb, const double* model_h,
                           const double* data_h, int M, int F, const ApertureParams& p, const ApertureFieldRows& out_h,
-                          int64_t chunk, int64_t gmax, int device, hipStream_t s);
+                          int device, hipStream_t s);
 // simultaneous flux fit of the mean stamps of a field to its observed field (fitflux.hip): per band the amplitudes
 // a of min |D - sum a_i P_i|^2 over the galaxies of the field, by a dense Cholesky factorisation with dropping.  FitFluxRows: the
 // output rows [.][nb], device or host.  fitflux_check / fitflux_plan: every refusal, before any GPU work; the plan is what
@@ -454,14 +437,6 @@ struct FitFluxWork {
     return plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int) + fields * sizeof(long long);
   }
   int alloc(const FitFluxPlan& plan, int64_t max_fields);
-};
-struct FitFluxBufs {
-  DevBuf<double> scale, var, gram, proj;
-  DevBuf<int> status;
-  static size_t bytes_per_stamp(int nb) { return (size_t)nb * (4 * sizeof(double) + sizeof(int)); }
-  int alloc(int64_t n, int nb);
-  FitFluxRows rows() const;
-  int download(const FitFluxRows& h, int64_t r, int64_t n, int nb, hipStream_t s) const;
 };
 int fitflux_check(const char* who, int cs, int nb, int F, const FitFluxParams& p);
 int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n);

@@ -35,6 +35,7 @@
 #endif
 #include <chrono>
 #include "common.h"
+#include "rows.h"
 #include "bf16.h"
 
 namespace dv {
@@ -3814,13 +3815,8 @@ int dv_scene_measure(dv_ctx* c, const float* mean, const float* stddev, int64_t 
   if (!c || !p) return DV_E_INVALID;
   DV_TRY(measure_check("dv_scene_measure", cs, nb, p->band, p->sigma0, p->tol, p->max_iter));   // before any GPU work
   DV_HIP(hipSetDevice(c->device));
-  // stamps per chunk: half of free device memory holds a chunk's mean and stddev stamps and its catalogue rows
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t per_stamp = (size_t)cs * cs * nb * 2 * sizeof(float) + (2 * (size_t)nb + 6) * sizeof(double);
-  const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 2 / per_stamp);
-  return scene_measure(mean, stddev, N, cs, nb, p->band, p->sigma0, p->tol, p->max_iter, flux, flux_err, shape, iters,
-                       status, chunk, c->stream);
+  return scene_measure(mean, stddev, N, cs, nb, p->band, p->sigma0, p->tol, p->max_iter,
+                       CatRows{flux, flux_err, shape, iters, status}, c->stream);
 }
 
 int dv_scene_blend(dv_ctx* c, const float* stamps, const double* shape, const int32_t* status, const int32_t* places,
@@ -3829,15 +3825,8 @@ int dv_scene_blend(dv_ctx* c, const float* stamps, const double* shape, const in
   if (!c) return DV_E_INVALID;
   DV_TRY(blend_check("dv_scene_blend", cs, nb, band));   // before any GPU work
   DV_HIP(hipSetDevice(c->device));
-  // a quarter of free device memory for a chunk's stamps and rows, a quarter for the fields they lie in
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t per_stamp = (size_t)cs * cs * nb * sizeof(float) + 9 * sizeof(double) + 5 * sizeof(int);
-  const size_t per_field = (size_t)std::max(F, 1) * std::max(F, 1) * nb * sizeof(double) * (data_fields ? 2 : 1);
-  const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 4 / per_stamp);
-  const int64_t gmax = (int64_t)std::max<size_t>(1, free_b / 4 / per_field);
-  return scene_blend(stamps, shape, status, places, field_ptr, N, cs, nb, band, model_fields, data_fields, M, F, blend, npix,
-                     chunk, gmax, c->stream);
+  return scene_blend(stamps, shape, status, places, field_ptr, N, cs, nb, band, model_fields, data_fields, M, F,
+                     BlendRows{blend, npix}, c->stream);
 }
 
 int dv_scene_regauss(dv_ctx* c, const float* stamps, const double* shape, const int32_t* status, const int32_t* psf_index,
@@ -3847,14 +3836,8 @@ int dv_scene_regauss(dv_ctx* c, const float* stamps, const double* shape, const 
   if (!c) return DV_E_INVALID;
   DV_TRY(regauss_check("dv_scene_regauss", cs, nb, band, K, ps, psf_sigma0, tol, max_iter));   // before any GPU work
   DV_HIP(hipSetDevice(c->device));
-  // stamps per chunk: half of free device memory, less the PSFs, holds a chunk's stamps and rows
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t per_stamp = (size_t)cs * cs * nb * sizeof(float) + 11 * sizeof(double) + 4 * sizeof(int);
-  const size_t fixed = RegaussPsf::bytes(K, ps), half = free_b / 2;
-  const int64_t chunk = (int64_t)std::max<size_t>(1, (half > fixed ? half - fixed : 0) / per_stamp);
-  return scene_regauss(stamps, shape, status, psf_index, N, cs, nb, band, psf, K, ps, psf_sigma0, tol, max_iter, regauss,
-                       regauss_iters, regauss_status, psf_shape, psf_aux, psf_iters, psf_status, chunk, c->stream);
+  return scene_regauss(stamps, shape, status, psf_index, N, cs, nb, band, psf, K, ps, psf_sigma0, tol, max_iter,
+                       RegaussRows{regauss, regauss_iters, regauss_status}, psf_shape, psf_aux, psf_iters, psf_status, c->stream);
 }
 
 static ApertureParams aperture_params(const dv_aperture_params& a) {
@@ -3902,17 +3885,8 @@ int dv_scene_aperture(dv_ctx* c, const float* mean, const float* stddev, const d
   const ApertureParams par = aperture_params(*params);
   DV_TRY(aperture_check("dv_scene_aperture", cs, nb, band, par));   // before any GPU work
   const ApertureRows out{ap_flux, ap_flux_err, ap_area, flux_auto, flux_auto_err, kron, flux_rho, aper_flags, aper_status};
-  if (N <= 0 || !mean || !shape || !status)          // (nothing to size: scene_aperture refuses or returns)
-    return scene_aperture(mean, stddev, shape, status, N, cs, nb, band, par, out, 1, c->stream);
-  DV_TRY(aperture_rows_check("dv_scene_aperture", out, par, stddev != nullptr, N));
   DV_HIP(hipSetDevice(c->device));
-  // stamps per chunk: half of free device memory holds a chunk's mean and stddev stamps and its rows
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t per_stamp = (size_t)cs * cs * nb * 2 * sizeof(float) + 5 * sizeof(double) + sizeof(int) +
-                           ApertureBufs::bytes_per_stamp(par, nb);
-  const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 2 / per_stamp);
-  return scene_aperture(mean, stddev, shape, status, N, cs, nb, band, par, out, chunk, c->stream);
+  return scene_aperture(mean, stddev, shape, status, N, cs, nb, band, par, out, c->stream);
 }
 
 int dv_scene_aperture_fields(dv_ctx* c, const double* shape, const int32_t* status, const int32_t* places,
@@ -3926,9 +3900,9 @@ int dv_scene_aperture_fields(dv_ctx* c, const double* shape, const int32_t* stat
     return DV_E_INVALID;
   }
   const ApertureFieldRows out{ap_model_sum, ap_data_sum, ap_field_area, auto_model_sum, auto_data_sum, auto_field_area};
-  // (every refusal is scene_aperture_fields'; chunk and gmax 0: sized there, after them, against free device memory)
+  // (every refusal is scene_aperture_fields')
   return scene_aperture_fields(shape, status, places, field_ptr, kron, aper_status, N, cs, nb, model_fields, data_fields, M, F,
-                               aperture_params(*params), out, 0, 0, c->device, c->stream);
+                               aperture_params(*params), out, c->device, c->stream);
 }
 
 static_assert(DV_FIT_MAX_N == FF_MAX_N, "the header's field limit of the flux fit is the kernels'");
@@ -3980,16 +3954,8 @@ int dv_scene_measure_mc(dv_ctx* c, const float* samples, int32_t S, int64_t N, i
   }
   if (N == 0) return DV_OK;
   DV_HIP(hipSetDevice(c->device));
-  // galaxies per chunk: half of free device memory holds a chunk's S sample stamps per galaxy, their scratch rows, the
-  // results and (when asked for) the per-sample rows
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t row = ((size_t)nb + 5) * sizeof(double) + 2 * sizeof(int);
-  const size_t per_galaxy = (size_t)S * ((size_t)cs * cs * nb * sizeof(float) + row * (given ? 2 : 1)) +
-                            (2 * (size_t)nb + 16) * sizeof(double) + sizeof(int);
-  const int64_t chunk = (int64_t)std::max<size_t>(1, free_b / 2 / per_galaxy);
   const McState out{flux_mean, flux_std, shape_mean, shape_std, n_ok, sample_flux, sample_shape, sample_status};
-  return scene_measure_mc(samples, S, N, cs, nb, p->band, p->sigma0, p->tol, p->max_iter, out, chunk, c->stream);
+  return scene_measure_mc(samples, S, N, cs, nb, p->band, p->sigma0, p->tol, p->max_iter, out, c->stream);
 }
 
 int dv_scene_detect(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, const dv_detect_params* p,
@@ -4820,48 +4786,24 @@ static int fields_tables(dv_model* m, const char* who, int32_t M, const int64_t*
     set_error("%s: the fields have %d bands and %d pixels, the network takes %d x %d x %d stamps", who, nb, F, cs, cs, A.C);
     return DV_E_INVALID;
   }
-  if (N >= ((int64_t)1 << 31)) {
-    set_error("%s: %ld stamps, at most 2^31 - 1 per call", who, (long)N);
-    return DV_E_INVALID;
-  }
-  if (field_ptr[0] != 0 || field_ptr[M] != N) {
-    set_error("%s: field_ptr must run from 0 to the number of stamps (%ld), got %ld .. %ld", who, (long)N,
-              (long)field_ptr[0], (long)field_ptr[M]);
-    return DV_E_INVALID;
-  }
-  for (int32_t f = 0; f < M; ++f)
-    if (field_ptr[f + 1] < field_ptr[f]) {
-      set_error("%s: field_ptr decreases at field %d (%ld after %ld)", who, f, (long)field_ptr[f + 1], (long)field_ptr[f]);
+  // (the placements are checked below, each after its stamp's cutout: the order in which a call with both wrong is refused)
+  DV_TRY(field_tables(who, "stamps", M, field_ptr, N, nullptr, nullptr, &sfield, &fptr32));
+  for (int64_t i = 0; i < N; ++i) {
+    const int x = starts[2 * i], y = starts[2 * i + 1];
+    if (x < 0 || y < 0 || x > F - cs || y > F - cs) {   // (cs <= F holds; no x + cs: it overflows near INT_MAX)
+      set_error("%s: cutout %ld of field %d (start %d,%d size %d) leaves the %d-pixel field", who, (long)i, sfield[i], x, y, cs, F);
       return DV_E_INVALID;
     }
-  sfield.assign((size_t)N, 0);
-  fptr32.assign((size_t)M + 1, 0);
-  for (int32_t f = 0; f < M; ++f) {
-    fptr32[f] = (int)field_ptr[f];
-    for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) {
-      sfield[i] = f;
-      const int x = starts[2 * i], y = starts[2 * i + 1];
-      if (x < 0 || y < 0 || x > F - cs || y > F - cs) {   // (cs <= F holds; no x + cs: it overflows near INT_MAX)
-        set_error("%s: cutout %ld of field %d (start %d,%d size %d) leaves the %d-pixel field", who, (long)i, f, x, y, cs, F);
-        return DV_E_INVALID;
-      }
-      if (places) {
-        const int pr = places[2 * i], pc = places[2 * i + 1];
-        if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
-          set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
-          return DV_E_INVALID;
-        }
-      }
-    }
+    if (places) DV_TRY(place_check(who, i, places));
   }
-  fptr32[M] = (int)N;
   return DV_OK;
 }
 
 // ---- the many-field call, stage by stage ------------------------------------------------------------------------------------
 // Every optional stage of the call owns its device buffers in one struct with three steps: allocate from the call's sizes,
 // bind into the job (one nested PipeJob member), download into the caller's arrays.  What a stage adds to the memory a
-// resident field or a stamp costs stands beside its allocations (bytes_per_field / bytes_per_stamp / bytes_fixed).
+// resident field costs stands beside its allocations (bytes_per_field / bytes_fixed); what it adds per stamp is the bytes()
+// of the columns it states (rows.h).
 struct FieldsCall {                 // the sizes of one call
   int64_t N, K;                     // stamps, chunks
   int F, nb, cs, chunk;
@@ -5044,73 +4986,46 @@ struct FitStage {                   // the position fit and the fractional place
   }
 };
 
+// The stages that add per-stamp rows state their columns (columns(): no GPU work, so the call's reserve can count
+// rows.bytes() before anything is allocated), allocate them with rows.alloc(N) and end with rows_download.
+static int rows_download(const Rows& rows, int64_t N, hipStream_t s) {
+  DV_TRY(rows.download(0, N, s));
+  DV_HIP(hipStreamSynchronize(s));
+  return DV_OK;
+}
+
+// The reserve of a many-field call has always counted one double per stamp more than the catalogue allocates.  It is slack, not
+// a column; it stays because the DV_FIELDS_GROUP_MB tests pin group boundaries that were computed with it.
+constexpr size_t CATALOGUE_RESERVE_SLACK = sizeof(double);
+
 struct CatalogueStage {             // fluxes, errors and adaptive moments of every stamp (7j)
-  DevBuf<double> flux, ferr, shape;
-  DevBuf<int> iters, status;
-  static size_t bytes_per_stamp(int nb) { return (2 * (size_t)nb + 6) * sizeof(double) + 2 * sizeof(int); }
-  int alloc(int64_t N, int nb) {
-    for (DevBuf<double>* b : {&flux, &ferr}) DV_TRY(b->alloc((size_t)N * nb));
-    for (DevBuf<int>* b : {&iters, &status}) DV_TRY(b->alloc((size_t)N));
-    return shape.alloc((size_t)N * 5);
+  CatRows dev{};
+  Rows rows;
+  void columns(const MeasureOut& mo, int nb) {
+    catalogue_columns(rows, dev, CatRows{mo.flux, mo.flux_err, mo.shape, mo.iters, mo.status}, nb, true);
   }
   void bind(PipeJob::Measure& q, const dv_measure_params& par) const {
-    q.flux = flux; q.ferr = ferr; q.shape = shape; q.iters = iters; q.status = status;
+    q.flux = dev.flux; q.ferr = dev.flux_err; q.shape = dev.shape; q.iters = dev.iters; q.status = dev.status;
     q.band = par.band; q.max_iter = par.max_iter; q.sigma0 = par.sigma0; q.tol = par.tol;
-  }
-  int download(const MeasureOut& mo, int64_t N, int nb, hipStream_t s) {
-    DV_HIP(hipMemcpyAsync(mo.flux, flux, (size_t)N * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(mo.flux_err, ferr, (size_t)N * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(mo.shape, shape, (size_t)N * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(mo.iters, iters, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(mo.status, status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));
-    return DV_OK;
   }
 };
 
 struct CatalogueMcStage {           // means and standard deviations over the Monte-Carlo decodes of every stamp (7k)
-  DevBuf<double> fmean, fstd, smean, sstd, kflux, kshape, wflux, wshape;
-  DevBuf<int> nok, kst, wit, wst;
-  // the results (and running state) of a stamp; with the per-sample rows, S rows of nb fluxes, 5 moments and a status more
-  static size_t bytes_per_stamp(int nb, int S, bool keep) {
-    return (2 * (size_t)nb + 16) * sizeof(double) + sizeof(int) +
-           (keep ? (size_t)S * (((size_t)nb + 5) * sizeof(double) + sizeof(int)) : 0);
+  McState dev{};                    // the results (and running state) of a stamp, with or without its per-sample rows
+  McScratch w{};                    // the scratch rows of one decoder pass: at most the workspace capacity
+  Rows rows, scratch;
+  void columns(const MeasureMcOut& o, int nb, bool keep) {
+    mc_columns(rows, dev, o.st, nb, o.nsamples, keep);
+    mc_scratch_columns(scratch, w, nb, 1);
   }
-  // the scratch rows of one decoder pass: at most the workspace capacity
-  static size_t bytes_fixed(int Bc, int nb) { return (size_t)Bc * (((size_t)nb + 5) * sizeof(double) + 2 * sizeof(int)); }
-  int alloc(int64_t N, int nb, int S, bool keep, int Bc) {
-    for (DevBuf<double>* b : {&fmean, &fstd}) DV_TRY(b->alloc((size_t)N * nb));
-    for (DevBuf<double>* b : {&smean, &sstd}) DV_TRY(b->alloc((size_t)N * 8));
-    DV_TRY(nok.alloc((size_t)N));
-    if (keep) {
-      DV_TRY(kflux.alloc((size_t)N * S * nb));
-      DV_TRY(kshape.alloc((size_t)N * S * 5));
-      DV_TRY(kst.alloc((size_t)N * S));
-    }
-    DV_TRY(wflux.alloc((size_t)Bc * nb));
-    DV_TRY(wshape.alloc((size_t)Bc * 5));
-    DV_TRY(wit.alloc((size_t)Bc));
-    return wst.alloc((size_t)Bc);
+  int alloc(int64_t N, int Bc) {
+    DV_TRY(rows.alloc(N));
+    return scratch.alloc(Bc);
   }
   void bind(PipeJob::MeasureMc& q, const dv_measure_params& par) const {
-    q.st = McState{fmean, fstd, smean, sstd, nok, kflux, kshape, kst};
-    q.w = McScratch{wflux, wshape, wit, wst};
+    q.st = dev;
+    q.w = w;
     q.band = par.band; q.max_iter = par.max_iter; q.sigma0 = par.sigma0; q.tol = par.tol;
-  }
-  int download(const MeasureMcOut& o, int64_t N, int nb, hipStream_t s) {
-    const size_t n = (size_t)N, S = (size_t)o.nsamples;
-    DV_HIP(hipMemcpyAsync(o.st.flux_mean, fmean, n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(o.st.flux_std, fstd, n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(o.st.shape_mean, smean, n * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(o.st.shape_std, sstd, n * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(o.st.n_ok, nok, n * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (o.st.sample_flux) {
-      DV_HIP(hipMemcpyAsync(o.st.sample_flux, kflux, n * S * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(o.st.sample_shape, kshape, n * S * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(o.st.sample_status, kst, n * S * sizeof(int), hipMemcpyDeviceToHost, s));
-    }
-    DV_HIP(hipStreamSynchronize(s));
-    return DV_OK;
   }
 };
 
@@ -5134,20 +5049,10 @@ struct MeanFieldStage {             // the device-side mean field of a catalogue
 };
 
 struct BlendStage {                 // the blendedness sums of every stamp (7l)
-  DevBuf<double> blend;
-  DevBuf<int> npix;
-  static size_t bytes_per_stamp() { return 4 * sizeof(double) + sizeof(int); }
-  int alloc(int64_t N) {
-    DV_TRY(blend.alloc((size_t)N * 4));
-    return npix.alloc((size_t)N);
-  }
-  void bind(PipeJob::Blend& q) const { q.blend = blend; q.npix = npix; }
-  int download(const BlendOut& o, int64_t N, hipStream_t s) {
-    DV_HIP(hipMemcpyAsync(o.blend, blend, (size_t)N * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(o.npix, npix, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));
-    return DV_OK;
-  }
+  BlendRows dev{};
+  Rows rows;
+  void columns(const BlendOut& o) { blend_columns(rows, dev, BlendRows{o.blend, o.npix}); }
+  void bind(PipeJob::Blend& q) const { q.blend = dev.blend; q.npix = dev.npix; }
 };
 
 struct RegaussOut {                 // dv_infer_fields_measure_psf: the PSFs and the index in, the corrected rows out (host)
@@ -5163,25 +5068,25 @@ struct RegaussOut {                 // dv_infer_fields_measure_psf: the PSFs and
 
 struct RegaussStage {               // the PSF-corrected moments of every stamp (7n)
   RegaussPsf psf;
-  DevBuf<double> out;
-  DevBuf<int> index, iters, status;
-  static size_t bytes_per_stamp() { return 6 * sizeof(double) + 3 * sizeof(int); }
+  RegaussRows dev{};
+  Rows rows;
+  DevBuf<int> index;                // every stamp's PSF: an input, uploaded once
+  void columns(const RegaussOut& o) { regauss_columns(rows, dev, RegaussRows{o.out, o.iters, o.status}); }
+  size_t bytes_per_stamp() const { return rows.bytes() + sizeof(int); }
   static size_t bytes_fixed(const RegaussOut& o) { return RegaussPsf::bytes(o.K, o.ps); }
   // the per-stamp rows, and the PSFs uploaded and measured on the call's stream: once, before the first chunk
   int alloc(const RegaussOut& o, int64_t N, const dv_measure_params& par, hipStream_t s) {
     DV_TRY(psf.alloc(o.K, o.ps));
-    DV_TRY(out.alloc((size_t)N * 6));
-    for (DevBuf<int>* b : {&index, &iters, &status}) DV_TRY(b->alloc((size_t)N));
+    DV_TRY(rows.alloc(N));
+    DV_TRY(index.alloc((size_t)N));
     DV_HIP(hipMemcpyAsync(index, o.index, (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
     return psf.measure(o.psf, o.K, o.ps, o.psf_sigma0, par.tol, par.max_iter, s);
   }
   void bind(PipeJob::Regauss& q, const RegaussOut& o) const {
-    q.psf = &psf; q.K = o.K; q.ps = o.ps; q.index = index; q.out = out; q.iters = iters; q.status = status;
+    q.psf = &psf; q.K = o.K; q.ps = o.ps; q.index = index; q.out = dev.out; q.iters = dev.iters; q.status = dev.status;
   }
   int download(const RegaussOut& o, int64_t N, hipStream_t s) {
-    DV_HIP(hipMemcpyAsync(o.out, out, (size_t)N * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(o.iters, iters, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(o.status, status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_TRY(rows.download(0, N, s));
     DV_TRY(psf.download(o.K, o.psf_shape, o.psf_aux, o.psf_iters, o.psf_status, s));
     DV_HIP(hipStreamSynchronize(s));
     return DV_OK;
@@ -5194,28 +5099,18 @@ struct ApertureOut {                // dv_infer_fields_measure_aper: the paramet
 };
 
 struct ApertureStage {              // the aperture photometry of every stamp (7o)
-  ApertureBufs bufs;
-  static size_t bytes_per_stamp(const ApertureOut& o, int nb) { return ApertureBufs::bytes_per_stamp(o.par, nb); }
-  int alloc(const ApertureOut& o, int64_t N, int nb) { return bufs.alloc(N, o.par, nb, true); }
-  void bind(PipeJob::Aper& q, const ApertureOut& o) const { q.on = true; q.par = o.par; q.rows = bufs.rows(); }
-  int download(const ApertureOut& o, int64_t N, int nb, hipStream_t s) {
-    DV_TRY(bufs.download(o.rows, N, o.par, nb, s));
-    DV_HIP(hipStreamSynchronize(s));
-    return DV_OK;
-  }
+  ApertureRows dev{};
+  Rows rows;
+  void columns(const ApertureOut& o, int nb) { aperture_columns(rows, dev, o.rows, o.par, nb, true); }
+  void bind(PipeJob::Aper& q, const ApertureOut& o) const { q.on = true; q.par = o.par; q.rows = dev; }
 };
 
 struct ApertureFieldOut { ApertureFieldRows rows{}; };   // dv_infer_fields_measure_aper_data: the six field rows out (host)
 
 struct ApertureFieldStage {         // the apertures of every stamp on the mean field and the source field (7p)
-  ApertureFieldBufs bufs;
-  static size_t bytes_per_stamp(const ApertureOut& o, int nb) { return ApertureFieldBufs::bytes_per_stamp(o.par, nb); }
-  int alloc(const ApertureOut& o, int64_t N, int nb) { return bufs.alloc(N, o.par, nb); }
-  int download(const ApertureFieldOut& h, const ApertureOut& o, int64_t N, int nb, hipStream_t s) {
-    DV_TRY(bufs.download(h.rows, N, o.par, nb, s));
-    DV_HIP(hipStreamSynchronize(s));
-    return DV_OK;
-  }
+  ApertureFieldRows dev{};
+  Rows rows;
+  void columns(const ApertureFieldOut& h, const ApertureOut& o, int nb) { aperture_field_columns(rows, dev, h.rows, o.par, nb); }
 };
 
 struct FitFluxOut { FitFluxParams par{}; FitFluxRows rows{}; };   // dv_infer_fields_measure_fit: the parameters in, five rows out (host)
@@ -5223,19 +5118,16 @@ struct FitFluxOut { FitFluxParams par{}; FitFluxRows rows{}; };   // dv_infer_fi
 struct FitFluxStage {               // the simultaneous flux fit of every field's mean stamps to its source field (7q)
   DevBuf<float> store;              // the mean stamps of all N stamps: a field's are read when its composite is complete
   FitFluxWork work;
-  FitFluxBufs bufs;
-  static size_t bytes_per_stamp(int cs, int nb) { return (size_t)cs * cs * nb * sizeof(float) + FitFluxBufs::bytes_per_stamp(nb); }
+  FitFluxRows dev{};
+  Rows rows;
+  void columns(const FitFluxOut& o, int nb) { fitflux_columns(rows, dev, o.rows, nb); }
+  size_t bytes_per_stamp(int cs, int nb) const { return (size_t)cs * cs * nb * sizeof(float) + rows.bytes(); }
   int alloc(const FitFluxPlan& plan, int64_t N, int64_t M, int cs, int nb) {
     DV_TRY(store.alloc((size_t)N * cs * cs * nb));
     DV_TRY(work.alloc(plan, M));
-    return bufs.alloc(N, nb);
+    return rows.alloc(N);
   }
   void bind(PipeJob::FitFlux& q) const { q.store = store; }
-  int download(const FitFluxOut& o, int64_t N, int nb, hipStream_t s) {
-    DV_TRY(bufs.download(o.rows, 0, N, nb, s));
-    DV_HIP(hipStreamSynchronize(s));
-    return DV_OK;
-  }
 };
 
 // What a many-field call wants back, beside what its PipeJob streams to the host: each part is there or not.
@@ -5299,17 +5191,37 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     per_field += FitStage::bytes_per_field(F);
     reserve += fit.bytes_fixed(c);
   }
-  if (rq.cat) reserve += (size_t)N * CatalogueStage::bytes_per_stamp(nb);
-  const bool keep_samples = rq.mc && rq.mc->st.sample_flux;
-  if (rq.mc)
-    reserve += (size_t)N * CatalogueMcStage::bytes_per_stamp(nb, rq.mc->nsamples, keep_samples) + CatalogueMcStage::bytes_fixed(m->Bc, nb);
+  // the row sets state their columns: what they add to the reserve is derived from those
+  if (rq.cat) {
+    cat.columns(*rq.cat, nb);
+    reserve += (size_t)N * (cat.rows.bytes() + CATALOGUE_RESERVE_SLACK);
+  }
+  if (rq.mc) {
+    catmc.columns(*rq.mc, nb, rq.mc->st.sample_flux != nullptr);
+    reserve += (size_t)N * catmc.rows.bytes() + (size_t)m->Bc * catmc.scratch.bytes();
+  }
   const bool own_mean = (rq.blend || rq.aper_field) && !rq.fields;   // a stage reads the completed composite and no composite stage runs
   per_field += MeanFieldStage::bytes_per_field(own_mean, fb);
-  if (rq.blend) reserve += (size_t)N * BlendStage::bytes_per_stamp();
-  if (rq.regauss) reserve += (size_t)N * RegaussStage::bytes_per_stamp() + RegaussStage::bytes_fixed(*rq.regauss);
-  if (rq.aper) reserve += (size_t)N * ApertureStage::bytes_per_stamp(*rq.aper, nb);
-  if (rq.aper_field) reserve += (size_t)N * ApertureFieldStage::bytes_per_stamp(*rq.aper, nb);
-  if (rq.fit_flux) reserve += (size_t)N * FitFluxStage::bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M);
+  if (rq.blend) {
+    bls.columns(*rq.blend);
+    reserve += (size_t)N * bls.rows.bytes();
+  }
+  if (rq.regauss) {
+    rgs.columns(*rq.regauss);
+    reserve += (size_t)N * rgs.bytes_per_stamp() + RegaussStage::bytes_fixed(*rq.regauss);
+  }
+  if (rq.aper) {
+    aps.columns(*rq.aper, nb);
+    reserve += (size_t)N * aps.rows.bytes();
+  }
+  if (rq.aper_field) {
+    afs.columns(*rq.aper_field, *rq.aper, nb);
+    reserve += (size_t)N * afs.rows.bytes();
+  }
+  if (rq.fit_flux) {
+    ffs.columns(*rq.fit_flux, nb);
+    reserve += (size_t)N * ffs.bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M);
+  }
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
@@ -5332,17 +5244,17 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     mc.bind(j.sinks);
   }
   if (rq.cat) {
-    DV_TRY(cat.alloc(N, nb));
+    DV_TRY(cat.rows.alloc(N));
     cat.bind(j.ms, rq.cat->par);
   }
   if (rq.mc) {
-    DV_TRY(catmc.alloc(N, nb, rq.mc->nsamples, keep_samples, m->Bc));
+    DV_TRY(catmc.alloc(N, m->Bc));
     catmc.bind(j.mcm, rq.cat->par);
   }
   DV_TRY(mfs.alloc(own_mean, gelems));
   mfs.bind(j.mf);
   if (rq.blend) {
-    DV_TRY(bls.alloc(N));
+    DV_TRY(bls.rows.alloc(N));
     bls.bind(j.bl);
   }
   if (rq.regauss) {
@@ -5350,10 +5262,10 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     rgs.bind(j.rg, *rq.regauss);
   }
   if (rq.aper) {
-    DV_TRY(aps.alloc(*rq.aper, N, nb));
+    DV_TRY(aps.rows.alloc(N));
     aps.bind(j.ap, *rq.aper);
   }
-  if (rq.aper_field) DV_TRY(afs.alloc(*rq.aper, N, nb));
+  if (rq.aper_field) DV_TRY(afs.rows.alloc(N));
   if (rq.fit_flux) {
     DV_TRY(ffs.alloc(ffplan, N, M, c.cs, nb));
     ffs.bind(j.ff);
@@ -5396,17 +5308,17 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
         const int r0 = fptr32[fa], r1 = fptr32[fz + 1];
         const double* mean_f = rq.fields ? comp.mean.dev.get() : mfs.mean.get();
         if (rq.blend)
-          DV_TRY(launch_blend_parent(cat.shape.get() + (size_t)r0 * 5, cat.status.get() + r0, tab.places.get() + 2 * (size_t)r0,
+          DV_TRY(launch_blend_parent(cat.dev.shape + (size_t)r0 * 5, cat.dev.status + r0, tab.places.get() + 2 * (size_t)r0,
                                      tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, rq.cat->par.band, F, mean_f, fdev,
-                                     bls.blend.get() + (size_t)r0 * 4, s));
+                                     bls.dev.blend + (size_t)r0 * 4, s));
         if (rq.aper_field)
-          DV_TRY(launch_aperture_field(cat.shape.get() + (size_t)r0 * 5, cat.status.get() + r0,
-                                       aps.bufs.kron.get() + (size_t)r0 * 3, aps.bufs.status.get() + r0,
+          DV_TRY(launch_aperture_field(cat.dev.shape + (size_t)r0 * 5, cat.dev.status + r0,
+                                       aps.dev.kron + (size_t)r0 * 3, aps.dev.status + r0,
                                        tab.places.get() + 2 * (size_t)r0, tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, F,
-                                       mean_f, fdev, rq.aper->par, aperture_field_rows_at(afs.bufs.rows(), r0, rq.aper->par, nb), s));
+                                       mean_f, fdev, rq.aper->par, aperture_field_rows_at(afs.dev, r0, rq.aper->par, nb), s));
         if (rq.fit_flux)               // (the stamp store, the placements and the tables count from stamp 0 of the call)
           DV_TRY(launch_fit_flux(ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, places, fptr32.data(), fa, fz, c.cs,
-                                 nb, F, rq.fit_flux->par, ffs.work, ffs.bufs.rows(), s));
+                                 nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s));
       }
     }
     if (rq.fields) {
@@ -5421,13 +5333,13 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     DV_HIP(hipMemcpyAsync(mse_h, tab.mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
     DV_HIP(hipStreamSynchronize(s));
   }
-  if (rq.cat) DV_TRY(cat.download(*rq.cat, N, nb, s));
-  if (rq.mc) DV_TRY(catmc.download(*rq.mc, N, nb, s));
-  if (rq.blend) DV_TRY(bls.download(*rq.blend, N, s));
+  if (rq.cat) DV_TRY(rows_download(cat.rows, N, s));
+  if (rq.mc) DV_TRY(rows_download(catmc.rows, N, s));
+  if (rq.blend) DV_TRY(rows_download(bls.rows, N, s));
   if (rq.regauss) DV_TRY(rgs.download(*rq.regauss, N, s));
-  if (rq.aper) DV_TRY(aps.download(*rq.aper, N, nb, s));
-  if (rq.aper_field) DV_TRY(afs.download(*rq.aper_field, *rq.aper, N, nb, s));
-  if (rq.fit_flux) DV_TRY(ffs.download(*rq.fit_flux, N, nb, s));
+  if (rq.aper) DV_TRY(rows_download(aps.rows, N, s));
+  if (rq.aper_field) DV_TRY(rows_download(afs.rows, N, s));
+  if (rq.fit_flux) DV_TRY(rows_download(ffs.rows, N, s));
   if (rq.fields) DV_TRY(mc.download(N, s));
   if (fitting) DV_TRY(fit.download(*rq.fields, N, s));
   drain.dismiss();
@@ -6077,12 +5989,11 @@ static int field_set_pass_impl(dv_field_set* fs, const char* who, const int32_t*
   std::vector<double>& fm = fs->fmse_h;
   DV_HIP(hipMemcpyAsync(mse_center, tab.mse, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
   DV_HIP(hipMemcpyAsync(fm.data(), fs->fmse, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (mo) {
-    DV_HIP(hipMemcpyAsync(mo->flux, fs->cflux, n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(mo->flux_err, fs->cferr, n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(mo->shape, fs->rshape.get() + row0 * 5, n * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(mo->iters, fs->citers, n * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(mo->status, fs->rstatus.get() + row0, n * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (mo) {                                          // the catalogue's columns, as a view of the pass's rows (the set owns them)
+    CatRows d{j.ms.flux, j.ms.ferr, j.ms.shape, j.ms.iters, j.ms.status};
+    Rows view;
+    catalogue_columns(view, d, CatRows{mo->flux, mo->flux_err, mo->shape, mo->iters, mo->status}, nb, true);
+    DV_TRY(view.download(0, N, s));
   }
   if (bo) {
     // {W, A}: the first two of the four doubles the child kernel's rows have

@@ -35,6 +35,7 @@
 // No atomics; ordinary vector stores only.
 #include "common.h"
 #include "measure_dev.h"
+#include "rows.h"
 
 #include <algorithm>
 #include <cmath>
@@ -321,27 +322,12 @@ int FitFluxWork::alloc(const FitFluxPlan& plan, int64_t max_fields) {
   return foff.alloc((size_t)std::max<int64_t>(max_fields, 1));
 }
 
-int FitFluxBufs::alloc(int64_t n, int nb) {
-  const size_t N = (size_t)n * nb;
-  DV_TRY(scale.alloc(N));
-  DV_TRY(var.alloc(N));
-  DV_TRY(gram.alloc(N));
-  DV_TRY(proj.alloc(N));
-  return status.alloc(N);
-}
-
-FitFluxRows FitFluxBufs::rows() const { return FitFluxRows{scale.get(), var.get(), gram.get(), proj.get(), status.get()}; }
-
-// rows r .. r + n of the device buffers to the same rows of `h`
-int FitFluxBufs::download(const FitFluxRows& h, int64_t r, int64_t n, int nb, hipStream_t s) const {
-  const size_t o = (size_t)r * nb, c = (size_t)n * nb;
-  if (c == 0) return OK;
-  DV_HIP(hipMemcpyAsync(h.scale + o, scale.get() + o, c * sizeof(double), hipMemcpyDeviceToHost, s));
-  DV_HIP(hipMemcpyAsync(h.var + o, var.get() + o, c * sizeof(double), hipMemcpyDeviceToHost, s));
-  DV_HIP(hipMemcpyAsync(h.gram + o, gram.get() + o, c * sizeof(double), hipMemcpyDeviceToHost, s));
-  DV_HIP(hipMemcpyAsync(h.proj + o, proj.get() + o, c * sizeof(double), hipMemcpyDeviceToHost, s));
-  DV_HIP(hipMemcpyAsync(h.status + o, status.get() + o, c * sizeof(int), hipMemcpyDeviceToHost, s));
-  return OK;
+void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb) {
+  r.add(dev.scale, host.scale, nb);
+  r.add(dev.var, host.var, nb);
+  r.add(dev.gram, host.gram, nb);
+  r.add(dev.proj, host.proj, nb);
+  r.add(dev.status, host.status, nb);
 }
 
 // The complete fields fa .. fz of a call.  Every per-galaxy device array counts from row 0 of the call, like fptr (host and
@@ -422,32 +408,15 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
     return E_INVALID;
   }
   DV_TRY(fitflux_rows_check(who, out_h, N));
-  if (N >= ((int64_t)1 << 31)) {
-    set_error("%s: %ld stamps, at most 2^31 - 1 per call", who, (long)N);
-    return E_INVALID;
-  }
-  if (field_ptr[0] != 0 || field_ptr[M] != N) {
-    set_error("%s: field_ptr must run from 0 to the number of stamps (%ld), got %ld .. %ld", who, (long)N,
-              (long)field_ptr[0], (long)field_ptr[M]);
-    return E_INVALID;
-  }
-  for (int f = 0; f < M; ++f)                        // the whole table before anything is indexed by it
-    if (field_ptr[f + 1] < field_ptr[f]) {
-      set_error("%s: field_ptr decreases at field %d (%ld after %ld)", who, f, (long)field_ptr[f + 1], (long)field_ptr[f]);
-      return E_INVALID;
-    }
-  for (int64_t i = 0; i < N; ++i) {
-    const int pr = places_h[2 * i], pc = places_h[2 * i + 1];
-    if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
-      set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
-      return E_INVALID;
-    }
-  }
+  DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));   // (the chunks build their own tables)
   FitFluxPlan plan;
   DV_TRY(fitflux_plan(who, field_ptr, M, nb, p, &plan));
   if (N == 0) return OK;
+  FitFluxRows d{};
+  Rows out;
+  fitflux_columns(out, d, out_h, nb);
   const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
-  const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + FitFluxBufs::bytes_per_stamp(nb);
+  const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + out.bytes();
   const size_t per_field = felems * sizeof(double) + sizeof(int) + sizeof(long long);
   DV_HIP(hipSetDevice(device));
   FitFluxWork work;
@@ -482,14 +451,13 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
   DevBuf<float> stamps;
   DevBuf<double> data;
   DevBuf<int> places, sf, fptr;
-  FitFluxBufs bufs;
   DV_TRY(work.alloc(plan, (int64_t)cmax_f));
   DV_TRY(stamps.alloc(cmax_s * stamp));
   DV_TRY(places.alloc(cmax_s * 2));
   DV_TRY(sf.alloc(cmax_s));
   DV_TRY(fptr.alloc(cmax_f + 1));
   DV_TRY(data.alloc(cmax_f * felems));
-  DV_TRY(bufs.alloc((int64_t)cmax_s, nb));
+  DV_TRY(out.alloc((int64_t)cmax_s));
   std::vector<int> sf_h, fptr_h;
   StreamDrain drain(s);
   for (size_t k = 0; k + 1 < cuts.size(); ++k) {
@@ -508,10 +476,8 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
     DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), fptr_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
     DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
     DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h + (size_t)r0 * 2, fptr_h.data(), 0, fz - fa - 1, cs, nb, F,
-                           p, work, bufs.rows(), s, true));
-    const FitFluxRows at{out_h.scale + (size_t)r0 * nb, out_h.var + (size_t)r0 * nb, out_h.gram + (size_t)r0 * nb,
-                         out_h.proj + (size_t)r0 * nb, out_h.status + (size_t)r0 * nb};
-    DV_TRY(bufs.download(at, 0, n, nb, s));
+                           p, work, d, s, true));
+    DV_TRY(out.download(r0, n, s));
     DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next chunk
   }
   drain.dismiss();
@@ -533,13 +499,7 @@ int scene_fit_flux_gram(const float* stamps_h, const int32_t* places_h, int64_t 
     set_error("%s: stamps, places, data_field, gram and proj must all be given", who);
     return E_INVALID;
   }
-  for (int64_t i = 0; i < n; ++i) {
-    const int pr = places_h[2 * i], pc = places_h[2 * i + 1];
-    if (pr < -(1 << 28) || pr > (1 << 28) || pc < -(1 << 28) || pc > (1 << 28)) {
-      set_error("%s: placement %ld (%d,%d) out of range", who, (long)i, pr, pc);
-      return E_INVALID;
-    }
-  }
+  for (int64_t i = 0; i < n; ++i) DV_TRY(place_check(who, i, places_h));
   const int64_t field_ptr[2] = {0, n};
   FitFluxPlan plan;
   DV_TRY(fitflux_plan(who, field_ptr, 1, nb, p, &plan));

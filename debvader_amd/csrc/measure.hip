@@ -19,6 +19,7 @@
 // iteration itself are in measure_dev.h, which the PSF correction (regauss.hip) shares.
 #include "common.h"
 #include "measure_dev.h"
+#include "rows.h"
 
 #include <algorithm>
 #include <cmath>
@@ -237,49 +238,37 @@ int launch_measure(const float* mean_dev, const float* stddev_dev, int n, int cs
   return OK;
 }
 
-// host stamps in, host catalogue out, in chunks of at most `chunk` stamps (sized by the caller against free device memory)
+// the catalogue's columns; flux_err only with a stddev stamp
+void catalogue_columns(Rows& r, CatRows& dev, const CatRows& host, int nb, bool err) {
+  r.add(dev.flux, host.flux, nb);
+  if (err) r.add(dev.flux_err, host.flux_err, nb);
+  r.add(dev.shape, host.shape, 5);
+  r.add(dev.iters, host.iters, 1);
+  r.add(dev.status, host.status, 1);
+}
+
+// host stamps in, host catalogue out, a chunk of stamps at a time
 int scene_measure(const float* mean_h, const float* stddev_h, int64_t N, int cs, int nb, int band, double sigma0, double tol,
-                  int max_iter, double* flux_h, double* flux_err_h, double* shape_h, int32_t* iters_h, int32_t* status_h,
-                  int64_t chunk, hipStream_t s) {
+                  int max_iter, const CatRows& o, hipStream_t s) {
   DV_TRY(measure_check("dv_scene_measure", cs, nb, band, sigma0, tol, max_iter));
-  if (N < 0 || (N > 0 && (!mean_h || !flux_h || !shape_h || !iters_h || !status_h))) {
+  if (N < 0 || (N > 0 && (!mean_h || !o.flux || !o.shape || !o.iters || !o.status))) {
     set_error("dv_scene_measure: mean, flux, shape, iters and status must all be given");
     return E_INVALID;
   }
-  if ((stddev_h == nullptr) != (flux_err_h == nullptr)) {
+  if ((stddev_h == nullptr) != (o.flux_err == nullptr)) {
     set_error("dv_scene_measure: stddev and flux_err go together (both given or both null)");
     return E_INVALID;
   }
-  if (N == 0) return OK;
   const size_t stamp = (size_t)cs * cs * nb;
-  chunk = std::max<int64_t>(1, std::min<int64_t>({chunk, N, (int64_t)1 << 20}));
-  DevBuf<float> mean, sd;
-  DevBuf<double> flux, ferr, shape;
-  DevBuf<int> it, st;
-  DV_TRY(mean.alloc((size_t)chunk * stamp));
-  if (stddev_h) {
-    DV_TRY(sd.alloc((size_t)chunk * stamp));
-    DV_TRY(ferr.alloc((size_t)chunk * nb));
-  }
-  DV_TRY(flux.alloc((size_t)chunk * nb));
-  DV_TRY(shape.alloc((size_t)chunk * 5));
-  DV_TRY(it.alloc((size_t)chunk));
-  DV_TRY(st.alloc((size_t)chunk));
-  for (int64_t base = 0; base < N; base += chunk) {
-    const int n = (int)std::min<int64_t>(chunk, N - base);
-    DV_HIP(hipMemcpyAsync(mean, mean_h + (size_t)base * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    if (sd)
-      DV_HIP(hipMemcpyAsync(sd, stddev_h + (size_t)base * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    DV_TRY(launch_measure(mean, sd, n, cs, nb, band, sigma0, tol, max_iter, flux, ferr, shape, it, st, s));
-    DV_HIP(hipMemcpyAsync(flux_h + (size_t)base * nb, flux, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (ferr)
-      DV_HIP(hipMemcpyAsync(flux_err_h + (size_t)base * nb, ferr, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(shape_h + (size_t)base * 5, shape, (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(iters_h + base, it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(status_h + base, st, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));               // the device buffers are reused by the next chunk
-  }
-  return OK;
+  float *mean = nullptr, *sd = nullptr;
+  CatRows d{};
+  Rows in, out;
+  in.add(mean, mean_h, stamp);
+  if (stddev_h) in.add(sd, stddev_h, stamp);
+  catalogue_columns(out, d, o, nb, stddev_h != nullptr);
+  return walk_rows(N, (int64_t)1 << 20, 0, in, out, s, [&](int64_t, int n) {
+    return launch_measure(mean, sd, n, cs, nb, band, sigma0, tol, max_iter, d.flux, d.flux_err, d.shape, d.iters, d.status, s);
+  });
 }
 
 // a decoder pass in device memory: `rows` sample stamps measured into the scratch rows
@@ -306,54 +295,45 @@ int launch_measure_mc_fold(const McScratch& w, int n, int reps, int k0, int S, i
   return OK;
 }
 
-// host sample stamps [S][N][cs][cs][nb] in, host Monte-Carlo catalogue out, in chunks of at most `chunk` galaxies with all
-// their samples (sized by the caller against free device memory): a chunk is one pass of n galaxies x S samples
+// the Monte-Carlo catalogue's columns (the per-sample rows only when kept) and the scratch rows of a pass
+void mc_columns(Rows& r, McState& dev, const McState& host, int nb, int S, bool keep) {
+  r.add(dev.flux_mean, host.flux_mean, nb);
+  r.add(dev.flux_std, host.flux_std, nb);
+  r.add(dev.shape_mean, host.shape_mean, 8);
+  r.add(dev.shape_std, host.shape_std, 8);
+  r.add(dev.n_ok, host.n_ok, 1);
+  if (!keep) return;
+  r.add(dev.sample_flux, host.sample_flux, (size_t)S * nb);
+  r.add(dev.sample_shape, host.sample_shape, (size_t)S * 5);
+  r.add(dev.sample_status, host.sample_status, S);
+}
+
+void mc_scratch_columns(Rows& r, McScratch& dev, int nb, int reps) {
+  r.add(dev.flux, nullptr, (size_t)reps * nb);
+  r.add(dev.shape, nullptr, (size_t)reps * 5);
+  r.add(dev.iters, nullptr, reps);
+  r.add(dev.status, nullptr, reps);
+}
+
+// host sample stamps [S][N][cs][cs][nb] in, host Monte-Carlo catalogue out, in chunks of galaxies with all their samples: a
+// chunk is one pass of n galaxies x S samples
 int scene_measure_mc(const float* samples_h, int S, int64_t N, int cs, int nb, int band, double sigma0, double tol,
-                     int max_iter, const McState& out_h, int64_t chunk, hipStream_t s) {
-  if (N == 0) return OK;
+                     int max_iter, const McState& out_h, hipStream_t s) {
   const size_t stamp = (size_t)cs * cs * nb;
-  chunk = std::max<int64_t>(1, std::min<int64_t>({chunk, N, ((int64_t)1 << 20) / S}));
-  const size_t rows = (size_t)chunk * S;
-  const bool keep = out_h.sample_flux != nullptr;
-  DevBuf<float> pass;
-  DevBuf<double> wflux, wshape, fmean, fstd, smean, sstd, kflux, kshape;
-  DevBuf<int> wit, wst, nok, kst;
-  DV_TRY(pass.alloc(rows * stamp));
-  DV_TRY(wflux.alloc(rows * nb));
-  DV_TRY(wshape.alloc(rows * 5));
-  DV_TRY(wit.alloc(rows));
-  DV_TRY(wst.alloc(rows));
-  for (DevBuf<double>* b : {&fmean, &fstd}) DV_TRY(b->alloc((size_t)chunk * nb));
-  for (DevBuf<double>* b : {&smean, &sstd}) DV_TRY(b->alloc((size_t)chunk * 8));
-  DV_TRY(nok.alloc((size_t)chunk));
-  if (keep) {
-    DV_TRY(kflux.alloc(rows * nb));
-    DV_TRY(kshape.alloc(rows * 5));
-    DV_TRY(kst.alloc(rows));
-  }
-  const McScratch w{wflux, wshape, wit, wst};
-  const McState st{fmean, fstd, smean, sstd, nok, kflux, kshape, kst};
-  for (int64_t base = 0; base < N; base += chunk) {
-    const int n = (int)std::min<int64_t>(chunk, N - base);
+  float* pass = nullptr;
+  McScratch w{};
+  McState st{};
+  Rows in, out;
+  in.add(pass, nullptr, (size_t)S * stamp);            // (sample q of the chunk's n galaxies at q * n: copied below)
+  mc_scratch_columns(out, w, nb, S);
+  mc_columns(out, st, out_h, nb, S, out_h.sample_flux != nullptr);
+  return walk_rows(N, ((int64_t)1 << 20) / S, 0, in, out, s, [&](int64_t base, int n) {
     for (int q = 0; q < S; ++q)
-      DV_HIP(hipMemcpyAsync(pass.get() + (size_t)q * n * stamp, samples_h + ((size_t)q * N + base) * stamp, (size_t)n * stamp * sizeof(float),
+      DV_HIP(hipMemcpyAsync(pass + (size_t)q * n * stamp, samples_h + ((size_t)q * N + base) * stamp, (size_t)n * stamp * sizeof(float),
                             hipMemcpyHostToDevice, s));
     DV_TRY(launch_measure_mc_samples(pass, n * S, cs, nb, band, sigma0, tol, max_iter, w, s));
-    DV_TRY(launch_measure_mc_fold(w, n, S, 0, S, nb, st, 0, s));
-    const size_t b = (size_t)base;
-    DV_HIP(hipMemcpyAsync(out_h.flux_mean + b * nb, fmean, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(out_h.flux_std + b * nb, fstd, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(out_h.shape_mean + b * 8, smean, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(out_h.shape_std + b * 8, sstd, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(out_h.n_ok + b, nok, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (keep) {
-      DV_HIP(hipMemcpyAsync(out_h.sample_flux + b * S * nb, kflux, (size_t)n * S * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(out_h.sample_shape + b * S * 5, kshape, (size_t)n * S * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(out_h.sample_status + b * S, kst, (size_t)n * S * sizeof(int), hipMemcpyDeviceToHost, s));
-    }
-    DV_HIP(hipStreamSynchronize(s));               // the device buffers are reused by the next chunk
-  }
-  return OK;
+    return launch_measure_mc_fold(w, n, S, 0, S, nb, st, 0, s);
+  });
 }
 
 }  // namespace dv

@@ -1,5 +1,5 @@
-// Device pieces the measurement kernels share (measure.hip, regauss.hip): the workgroup reduction and the adaptive-moments
-// iteration of DESIGN.md 7j on a float64 plane that lies in LDS.  Everything is inlined into the kernel that calls it.
+// Device pieces the measurement kernels share (measure.hip, blend.hip, regauss.hip, aperture.hip, fitflux.hip): the workgroup
+// reduction and the adaptive-moments iteration of DESIGN.md 7j on a float64 plane that lies in LDS.  Everything is inlined into the kernel that calls it.
 #pragma once
 #include "common.h"
 

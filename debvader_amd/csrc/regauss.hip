@@ -32,6 +32,7 @@
 // row with ordinary stores.
 #include "common.h"
 #include "measure_dev.h"
+#include "rows.h"
 
 #include <algorithm>
 #include <cmath>
@@ -359,54 +360,48 @@ int launch_regauss(const float* stamps_dev, const double* shape_dev, const int* 
   return OK;
 }
 
-// host arrays in, host rows out, in chunks of at most `chunk` stamps (sized by the caller against free device memory); the
-// PSFs are uploaded and measured once
+void regauss_columns(Rows& r, RegaussRows& dev, const RegaussRows& host) {
+  r.add(dev.out, host.out, 6);
+  r.add(dev.iters, host.iters, 1);
+  r.add(dev.status, host.status, 1);
+}
+
+// host arrays in, host rows out, a chunk of stamps at a time (half of free device memory less the PSFs); the PSFs are
+// uploaded and measured once
 int scene_regauss(const float* stamps_h, const double* shape_h, const int32_t* status_h, const int32_t* psf_index_h, int64_t N,
                   int cs, int nb, int band, const double* psf_h, int K, int ps, double psf_sigma0, double tol, int max_iter,
-                  double* out_h, int32_t* iters_h, int32_t* ostatus_h, double* psf_shape_h, double* psf_aux_h,
-                  int32_t* psf_iters_h, int32_t* psf_status_h, int64_t chunk, hipStream_t s) {
+                  const RegaussRows& out_h, double* psf_shape_h, double* psf_aux_h, int32_t* psf_iters_h,
+                  int32_t* psf_status_h, hipStream_t s) {
   const char* who = "dv_scene_regauss";
   DV_TRY(regauss_check(who, cs, nb, band, K, ps, psf_sigma0, tol, max_iter));
   if (!psf_h || !psf_shape_h || !psf_aux_h || !psf_iters_h || !psf_status_h) {
     set_error("%s: psf, psf_shape, psf_aux, psf_iters and psf_status must all be given", who);
     return E_INVALID;
   }
-  if (N < 0 || (N > 0 && (!stamps_h || !shape_h || !status_h || !psf_index_h || !out_h || !iters_h || !ostatus_h))) {
+  if (N < 0 || (N > 0 && (!stamps_h || !shape_h || !status_h || !psf_index_h || !out_h.out || !out_h.iters || !out_h.status))) {
     set_error("%s: stamps, shape, status, psf_index, regauss, regauss_iters and regauss_status must all be given", who);
     return E_INVALID;
   }
-  chunk = std::max<int64_t>(1, std::min<int64_t>({chunk, std::max<int64_t>(N, 1), (int64_t)1 << 20}));
-  const size_t stamp = (size_t)cs * cs * nb;
   RegaussPsf psf;
-  DevBuf<float> stamps;
-  DevBuf<double> shape, out;
-  DevBuf<int> status, index, it, ost;
   DV_TRY(psf.alloc(K, ps));
-  if (N > 0) {
-    DV_TRY(stamps.alloc((size_t)chunk * stamp));
-    DV_TRY(shape.alloc((size_t)chunk * 5));
-    DV_TRY(out.alloc((size_t)chunk * 6));
-    for (DevBuf<int>* b : {&status, &index, &it, &ost}) DV_TRY(b->alloc((size_t)chunk));
-  }
   StreamDrain drain(s);
   DV_TRY(psf.measure(psf_h, K, ps, psf_sigma0, tol, max_iter, s));
   DV_TRY(psf.download(K, psf_shape_h, psf_aux_h, psf_iters_h, psf_status_h, s));
   DV_HIP(hipStreamSynchronize(s));
-  for (int64_t base = 0; base < N; base += chunk) {
-    const int n = (int)std::min<int64_t>(chunk, N - base);
-    const size_t b = (size_t)base;
-    DV_HIP(hipMemcpyAsync(stamps, stamps_h + b * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(shape, shape_h + b * 5, (size_t)n * 5 * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(status, status_h + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(index, psf_index_h + b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_TRY(launch_regauss(stamps, shape, status, index, n, cs, nb, band, psf, K, ps, tol, max_iter, out, it, ost, s));
-    DV_HIP(hipMemcpyAsync(out_h + b * 6, out, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(iters_h + b, it, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(ostatus_h + b, ost, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));                   // the device buffers are reused by the next chunk
-  }
-  drain.dismiss();
-  return OK;
+  float* stamps = nullptr;
+  double* shape = nullptr;
+  int *status = nullptr, *index = nullptr;
+  RegaussRows d{};
+  Rows in, out;
+  in.add(stamps, stamps_h, (size_t)cs * cs * nb);
+  in.add(shape, shape_h, 5);
+  in.add(status, status_h, 1);
+  in.add(index, psf_index_h, 1);
+  regauss_columns(out, d, out_h);
+  drain.dismiss();                                     // (the stream is idle; from here on the walker waits)
+  return walk_rows(N, (int64_t)1 << 20, RegaussPsf::bytes(K, ps), in, out, s, [&](int64_t, int n) {
+    return launch_regauss(stamps, shape, status, index, n, cs, nb, band, psf, K, ps, tol, max_iter, d.out, d.iters, d.status, s);
+  });
 }
 
 }  // namespace dv

@@ -37,6 +37,10 @@ int dv_debug_wgrad_check(dv_ctx* ctx, int32_t NB, int32_t H, int32_t Cx, int32_t
  * (batch-major tiles) instead of the separate pass.  Measured slower at every batch size; kept for the A/B and for the
  * summation-order test of tests/test_gpu_api.py. */
 int dv_debug_fuse_prelu_bwd(int32_t on);
+/* process-wide: the stand-alone catalogue calls (dv_scene_measure, _measure_mc, _blend, _regauss, _aperture,
+ * _aperture_fields) hold at most max_stamps rows and max_fields fields on the device at a time, instead of what free device
+ * memory allows; 0 = no cap.  Lets a test reach the second chunk of their loops with a handful of stamps. */
+int dv_debug_scene_limits(int64_t max_stamps, int64_t max_fields);
 int dv_debug_wgrad(dv_ctx* ctx, int32_t NB, int32_t Hx, int32_t Cx, int32_t Hy, int32_t Cy, int32_t sx,
                    int32_t pad_before, int32_t single_tap, int32_t iters, float* ms_out);
 

@@ -32,6 +32,7 @@ DEBUG_SIGNATURES = {
     "dv_debug_fuse_prelu_bwd": (C.c_int, [C.c_int32]),
     "dv_debug_wgrad_check": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f]),
     "dv_debug_wgrad": (C.c_int, [_p] + [C.c_int32] * 9 + [_f]),
+    "dv_debug_scene_limits": (C.c_int, [C.c_int64, C.c_int64]),
 }
 
 _dlib = None
