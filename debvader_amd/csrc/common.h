@@ -419,34 +419,44 @@ int scene_aperture_fields(const double* shape_h, const int32_t* status_h, const 
 // FitFluxWork::alloc takes - the dense scratch (at most scratch_bytes, no more than the fields need) and the pair list.
 // launch_fit_flux: the complete fields fa .. fz, every per-galaxy array counted from row 0 of the call; it returns with the
 // stream idle.  scene_fit_flux: host arrays, whole fields at a time within `budget` bytes of device memory (0: half of what
-// is free beside the scratch).  scene_fit_flux_gram: step 1 of one field - the dense G and h to the host.
+// is free beside the scratch).  scene_fit_flux_gram: step 1 of one field - the dense G and h to the host.  With weight fields
+// (per-pixel inverse variances, a pixel counts iff 0 < W < inf) the sums are weighted, and behind the solve a third
+// kernel takes the chi-square of the refitted scene and the count of the counting pixels of every galaxy from a CSR adjacency
+// the host builds beside the pair list; without them nothing more is allocated, copied or launched than before.
 int scene_fit_flux_gram(const float* stamps_h, const int32_t* places_h, int64_t n, int cs, int nb, const double* data_h, int F,
                         double* gram_h, double* proj_h, int device, hipStream_t s);
 constexpr int FF_MAX_N = 1024;                        // galaxies per field (DV_FIT_MAX_N)
 struct FitFluxParams { double min_pivot; int64_t scratch_bytes; };
-struct FitFluxRows { double *scale, *var, *gram, *proj; int* status; };
-struct FitFluxPlan { size_t scratch_elems = 0, pair_cap = 0; };
+// (chi2, npix: the two rows of the weighted fit, 7s - null in the unweighted one)
+struct FitFluxRows { double *scale, *var, *gram, *proj; int* status; double* chi2 = nullptr; int* npix = nullptr; };
+struct FitFluxPlan { size_t scratch_elems = 0, pair_cap = 0, rows = 0; };
 struct FitFluxWork {
   DevBuf<double> scratch;
   DevBuf<int> pairs;
   DevBuf<long long> foff;
-  size_t cap_elems = 0;
+  DevBuf<int> adj_ptr, adj;                           // weighted: the CSR adjacency of a sub-range (rows + 1, <= 2 pairs)
+  size_t cap_elems = 0, adj_ptr_cap = 0, adj_cap = 0;   // (elements; the adjacency is never grown behind the plan)
   std::vector<int> pairs_h;                           // host staging of one sub-range
   std::vector<long long> foff_h;
-  static size_t bytes(const FitFluxPlan& plan, size_t fields) {
-    return plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int) + fields * sizeof(long long);
+  std::vector<int> adj_ptr_h, adj_h, adj_at_h;
+  static size_t bytes(const FitFluxPlan& plan, size_t fields, bool weighted = false) {
+    return plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int) + fields * sizeof(long long) +
+           (weighted ? (plan.pair_cap * 2 + plan.rows + 1) * sizeof(int) : 0);
   }
-  int alloc(const FitFluxPlan& plan, int64_t max_fields);
+  int alloc(const FitFluxPlan& plan, int64_t max_fields, bool weighted = false);
 };
 int fitflux_check(const char* who, int cs, int nb, int F, const FitFluxParams& p);
-int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n);
+int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n, bool weighted = false);
 int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan);
+// weight_dev: the weight fields from field f0 on, laid out like data_dev (7s), or null: the unweighted fit.  With weights the
+// chi-square kernel runs behind the solve and rows.chi2 / rows.npix are written
 int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
                     const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
-                    int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve = true);
+                    int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve = true,
+                    const double* weight_dev = nullptr);
 int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                    const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
-                   hipStream_t s);
+                   hipStream_t s, const double* weight_h = nullptr, const char* who = "dv_scene_fit_flux");
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

@@ -3927,6 +3927,25 @@ int dv_scene_fit_flux(dv_ctx* c, const float* stamps, const int32_t* places, con
                         FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status}, 0, c->device, c->stream);
 }
 
+// the same fit under per-pixel weights: every refusal is scene_fit_flux's, the null weight fields are refused here
+int dv_scene_fit_flux_weighted(dv_ctx* c, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                               int32_t cs, int32_t nb, const double* data_fields, const double* weight_fields, int32_t M,
+                               int32_t F, const dv_fit_flux_params* params, double* fit_scale, double* fit_var, double* fit_gram,
+                               double* fit_proj, int32_t* fit_status, double* fit_chi2, int32_t* fit_npix) {
+  if (!c) return DV_E_INVALID;
+  if (!params) {
+    set_error("dv_scene_fit_flux_weighted: params must be given");
+    return DV_E_INVALID;
+  }
+  if (!weight_fields) {
+    set_error("dv_scene_fit_flux_weighted: weight_fields must be given (dv_scene_fit_flux is the unweighted fit)");
+    return DV_E_INVALID;
+  }
+  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, FitFluxParams{params->min_pivot, params->scratch_bytes},
+                        FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, 0, c->device, c->stream,
+                        weight_fields, "dv_scene_fit_flux_weighted");
+}
+
 int dv_scene_fit_flux_gram(dv_ctx* c, const float* stamps, const int32_t* places, int64_t n, int32_t cs, int32_t nb,
                            const double* data_field, int32_t F, double* gram, double* proj) {
   if (!c) return DV_E_INVALID;
@@ -5113,18 +5132,20 @@ struct ApertureFieldStage {         // the apertures of every stamp on the mean 
   void columns(const ApertureFieldOut& h, const ApertureOut& o, int nb) { aperture_field_columns(rows, dev, h.rows, o.par, nb); }
 };
 
-struct FitFluxOut { FitFluxParams par{}; FitFluxRows rows{}; };   // dv_infer_fields_measure_fit: the parameters in, five rows out (host)
+// dv_infer_fields_measure_fit: the parameters in, five rows out (host); _fit_weighted (7s): the host weight fields [M][F][F][nb]
+// in too, and the rows carry fit_chi2 and fit_npix
+struct FitFluxOut { FitFluxParams par{}; FitFluxRows rows{}; const double* weights = nullptr; };
 
 struct FitFluxStage {               // the simultaneous flux fit of every field's mean stamps to its source field (7q)
   DevBuf<float> store;              // the mean stamps of all N stamps: a field's are read when its composite is complete
   FitFluxWork work;
   FitFluxRows dev{};
   Rows rows;
-  void columns(const FitFluxOut& o, int nb) { fitflux_columns(rows, dev, o.rows, nb); }
+  void columns(const FitFluxOut& o, int nb) { fitflux_columns(rows, dev, o.rows, nb, o.weights != nullptr); }
   size_t bytes_per_stamp(int cs, int nb) const { return (size_t)cs * cs * nb * sizeof(float) + rows.bytes(); }
-  int alloc(const FitFluxPlan& plan, int64_t N, int64_t M, int cs, int nb) {
+  int alloc(const FitFluxPlan& plan, int64_t N, int64_t M, int cs, int nb, bool weighted) {
     DV_TRY(store.alloc((size_t)N * cs * cs * nb));
-    DV_TRY(work.alloc(plan, M));
+    DV_TRY(work.alloc(plan, M, weighted));
     return rows.alloc(N);
   }
   void bind(PipeJob::FitFlux& q) const { q.store = store; }
@@ -5178,6 +5199,8 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   const bool fitting = rq.fields && rq.fields->dist;
   double* mse_h = rq.fields ? rq.fields->mse : rq.cat ? rq.cat->mse : nullptr;
   DevBuf<double> fdev;                                // the resident group of source fields
+  DevBuf<double> wdev;                                // ... and of their weight fields, in a weighted flux fit (7s)
+  const double* wfields = rq.fit_flux ? rq.fit_flux->weights : nullptr;
   StampTables tab;
   CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs; ApertureStage aps; MeanFieldStage mfs; ApertureFieldStage afs; FitFluxStage ffs;   // (a stage that does not run stays empty)
   ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
@@ -5220,14 +5243,16 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   }
   if (rq.fit_flux) {
     ffs.columns(*rq.fit_flux, nb);
-    reserve += (size_t)N * ffs.bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M);
+    reserve += (size_t)N * ffs.bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M, wfields != nullptr);
+    if (wfields) per_field += fb;
   }
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
   if (G < 1) {
-    set_error("%s: one %d-pixel field needs %zu bytes of device memory (field%s), %zu are available for fields", who, F,
-              per_field, rq.fields ? " and its result fields" : own_mean ? " and its device-side mean field" : "", budget);
+    set_error("%s: one %d-pixel field needs %zu bytes of device memory (field%s%s), %zu are available for fields", who, F,
+              per_field, rq.fields ? " and its result fields" : own_mean ? " and its device-side mean field" : "",
+              wfields ? " and its weight field" : "", budget);
     return DV_E_NOMEM;
   }
   std::vector<FieldGroup> groups;
@@ -5237,6 +5262,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   StreamDrain drain(s, pipe->s_in, pipe->s_out);
   const size_t gelems = (size_t)gmax * felems;
   DV_TRY(fdev.alloc(gelems));
+  if (wfields) DV_TRY(wdev.alloc(gelems));
   if (rq.fields) {
     DV_TRY(comp.alloc(*rq.fields, gelems));
     DV_TRY(mc.alloc(*rq.fields, gelems, N));
@@ -5267,7 +5293,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   }
   if (rq.aper_field) DV_TRY(afs.rows.alloc(N));
   if (rq.fit_flux) {
-    DV_TRY(ffs.alloc(ffplan, N, M, c.cs, nb));
+    DV_TRY(ffs.alloc(ffplan, N, M, c.cs, nb, wfields != nullptr));
     ffs.bind(j.ff);
   }
   if (fitting) {
@@ -5289,6 +5315,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     const FieldGroup& g = groups[gi];
     const size_t ng = (size_t)(g.f1 - g.f0 + 1), goff = (size_t)g.f0 * felems;
     DV_HIP(hipMemcpyAsync(fdev, fields + goff, ng * fb, hipMemcpyHostToDevice, s));
+    if (wfields) DV_HIP(hipMemcpyAsync(wdev, wfields + goff, ng * fb, hipMemcpyHostToDevice, s));
     for (ResultStack* r : stacks) DV_TRY(r->begin(r == &comp.residual ? fdev.get() : nullptr, ng * fb, s));
     if (g.f0 == prev_last)
       for (ResultStack* r : stacks) DV_TRY(r->carry(goff, fb, s));
@@ -5318,7 +5345,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
                                        mean_f, fdev, rq.aper->par, aperture_field_rows_at(afs.dev, r0, rq.aper->par, nb), s));
         if (rq.fit_flux)               // (the stamp store, the placements and the tables count from stamp 0 of the call)
           DV_TRY(launch_fit_flux(ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, places, fptr32.data(), fa, fz, c.cs,
-                                 nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s));
+                                 nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s, true, wfields ? wdev.get() : nullptr));
       }
     }
     if (rq.fields) {
@@ -5486,7 +5513,7 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const Catalo
   }
   if (rq.fit_flux) {
     DV_TRY(fitflux_check(who, m->A.H, a.nb, a.F, rq.fit_flux->par));
-    DV_TRY(fitflux_rows_check(who, rq.fit_flux->rows, N));
+    DV_TRY(fitflux_rows_check(who, rq.fit_flux->rows, N, rq.fit_flux->weights != nullptr));
     DV_TRY(seam_places_check(who, a));
   }
   if (rq.regauss) {
@@ -5648,6 +5675,33 @@ int dv_infer_fields_measure_fit(dv_model* m, const double* fields, int32_t M, in
   rq.fit_flux = FitFluxOut{FitFluxParams{fit->min_pivot, fit->scratch_bytes},
                            FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status}};
   return infer_fields_measure_entry("dv_infer_fields_measure_fit", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
+}
+
+// ---- the same under per-pixel inverse-variance weights: dv_infer_fields_measure_fit plus the weight fields, laid
+// out like the source fields and resident beside them, and the chi-square and pixel count of every galaxy and band
+int dv_infer_fields_measure_fit_weighted(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb,
+                                         const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                                         uint64_t seed, const dv_measure_params* params, double* mean_fields,
+                                         double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
+                                         double* flux_err, double* shape, int32_t* iters, int32_t* status,
+                                         const dv_fit_flux_params* fit, const double* weight_fields, double* fit_scale,
+                                         double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status,
+                                         double* fit_chi2, int32_t* fit_npix) {
+  if (!m) return DV_E_INVALID;
+  if (!fit) {
+    set_error("dv_infer_fields_measure_fit_weighted: the flux-fit params must be given");
+    return DV_E_INVALID;
+  }
+  if (!weight_fields) {
+    set_error("dv_infer_fields_measure_fit_weighted: weight_fields must be given (dv_infer_fields_measure_fit is the unweighted fit)");
+    return DV_E_INVALID;
+  }
+  FieldsRequest rq;
+  rq.fit_flux = FitFluxOut{FitFluxParams{fit->min_pivot, fit->scratch_bytes},
+                           FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields};
+  return infer_fields_measure_entry("dv_infer_fields_measure_fit_weighted", m,
                                     {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
                                      residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }

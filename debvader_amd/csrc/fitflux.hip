@@ -32,6 +32,17 @@
 //                         element is updated by one thread per column, in ascending column order, and every other sum runs in
 //                         ascending index order in one thread: a field's rows have the same bits wherever the field sits in a
 //                         batch and when it is alone.
+// The weighted fit takes a weight field W laid out like D, meant as the inverse variance of every pixel.  A pixel
+// of band b counts iff 0 < W < inf; every other pixel's terms are exactly +0.0, selected and not multiplied, so nothing under a
+// masked pixel reaches a sum.  Step 1 becomes G_ij = sum (W P_i) P_j and h_i = sum (W P_i) D over the counting pixels - the
+// product with W first: with W = 1.0 every term has the bits of the unweighted one -, in fitflux_gram_kernel<true>; steps 2 - 5
+// run unchanged in fitflux_solve_kernel; then, new:
+//   6. per galaxy i and band the chi-square of the refitted scene under the pixels p of i: M(p) = sum_j a_j P_j(p) over the
+//      galaxies j of the field, in ascending row order, that cover p and do not have status 4, a_j = fit_scale (1 for a dropped
+//      one), summed sequentially in one thread; r = D(p) - M(p); fit_chi2 = sum over the counting p of (W r) r, one fixed-order
+//      workgroup reduction, NaN where i has status 4; fit_npix = the number of counting pixels of i, written for every galaxy.
+//   fitflux_chi2_kernel   one 256-thread workgroup per galaxy, behind the solve of its sub-range; the neighbours come from a CSR
+//                         adjacency the host builds beside the pair list.
 // No atomics; ordinary vector stores only.
 #include "common.h"
 #include "measure_dev.h"
@@ -75,13 +86,20 @@ __device__ __forceinline__ void ff_load(const float* __restrict__ p, int nb, dou
 // pairs [.][2]: the rows (i, j <= i) of two galaxies of one field, counted like every per-galaxy array here from row 0 of the
 // call; stamps [.][cs][cs][nb]; places [.][2]; sfield [.] the field of every row, fptr [.] the first row of every field; foff
 // [.]: where the scratch of field fbase + k begins in `scratch`, in doubles; data: the observed fields from field f0 on;
-// gram / proj [.][nb]
+// gram / proj [.][nb].  WEIGHTED (7s): weight, the weight fields from field f0 on, laid out like data; a pixel of band b counts
+// iff 0 < W < inf, its terms are (W P_i) P_j and (W P_i) D, and every other pixel's terms are +0.0 by selection - nothing under
+// a masked pixel reaches a sum.  W is read per band inside the unrolled band loop, as D is: no further band slots.  The
+// unweighted instantiation never touches `weight`.
+__device__ __forceinline__ bool ff_counts(double w) { return w > 0.0 && w < __longlong_as_double(0x7ff0000000000000LL); }
+
+template <bool WEIGHTED>
 __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __restrict__ pairs, const float* __restrict__ stamps,
                                                                   const int* __restrict__ places, const int* __restrict__ sfield,
                                                                   const int* __restrict__ fptr, const long long* __restrict__ foff,
                                                                   int fbase, int f0, int cs, int nb, int F,
                                                                   const double* __restrict__ data, double* __restrict__ scratch,
-                                                                  double* __restrict__ gram, double* __restrict__ proj) {
+                                                                  double* __restrict__ gram, double* __restrict__ proj,
+                                                                  const double* __restrict__ weight) {
   __shared__ double s_red[MS_RED];
   const long gi = pairs[2 * (long)blockIdx.x], gj = pairs[2 * (long)blockIdx.x + 1];
   const int m = sfield[gi];
@@ -95,26 +113,43 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __r
   const float* Pi = stamps + gi * cs * cs * nb;
   const float* Pj = stamps + gj * cs * cs * nb;
   const double* D = data + (long)(m - f0) * F * F * nb;
+  const double* W = WEIGHTED ? weight + (long)(m - f0) * F * F * nb : nullptr;
   double g[FF_BANDS], h[FF_BANDS], vi[FF_BANDS], vj[FF_BANDS];
 #pragma unroll
   for (int b = 0; b < FF_BANDS; ++b) g[b] = h[b] = vi[b] = vj[b] = 0.0;
   for (int e = threadIdx.x; e < npix; e += MS_THREADS) {
     const int r = ra + e / w, c = ca + e % w;
     ff_load(Pi + ((long)(r - pri) * cs + (c - pci)) * nb, nb, vi);
+    const double* wp = WEIGHTED ? W + ((long)r * F + c) * nb : nullptr;
     if (diag) {
       const double* dp = D + ((long)r * F + c) * nb;
 #pragma unroll
       for (int b = 0; b < FF_BANDS; ++b) {
         if (b < nb) {
-          g[b] += vi[b] * vi[b];
-          h[b] += vi[b] * dp[b];
+          if (WEIGHTED) {
+            const double wv = wp[b];
+            const bool on = ff_counts(wv);
+            const double wi = wv * vi[b];
+            g[b] += on ? wi * vi[b] : 0.0;
+            h[b] += on ? wi * dp[b] : 0.0;
+          } else {
+            g[b] += vi[b] * vi[b];
+            h[b] += vi[b] * dp[b];
+          }
         }
       }
     } else {
       ff_load(Pj + ((long)(r - prj) * cs + (c - pcj)) * nb, nb, vj);
 #pragma unroll
       for (int b = 0; b < FF_BANDS; ++b) {
-        if (b < nb) g[b] += vi[b] * vj[b];
+        if (b < nb) {
+          if (WEIGHTED) {
+            const double wv = wp[b];
+            g[b] += ff_counts(wv) ? (wv * vi[b]) * vj[b] : 0.0;
+          } else {
+            g[b] += vi[b] * vj[b];
+          }
+        }
       }
     }
   }
@@ -258,6 +293,124 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __
     }
   }
 }
+
+// The chi-square of the refitted scene under galaxy r0 + blockIdx.x (7s, step 3), behind the solve of its sub-range.  adj_ptr
+// [rows + 1] / adj [.]: the CSR adjacency of the sub-range's rows, counted from r0: the rows of the field whose clipped
+// rectangle intersects the galaxy's, ascending, itself included.  Threads take the pixels of the clipped stamp in raster order,
+// stride 256; per pixel M = sum a_j P_j over the neighbours that cover it and do not have status 4, sequentially in one thread,
+// then r = D - M and the terms (W r) r where the pixel counts.  The neighbours' placements, amplitudes and band masks are
+// staged in LDS CHI_TILE at a time (a degree of 40 is one tile: staged once, before the pixel loop), so the inner loop reads
+// no global table; one ms_block_sum per band carries chi2 and the pixel count (an integer below 2^24, exact in a double).
+constexpr int CHI_TILE = 64;
+
+__global__ __launch_bounds__(MS_THREADS) void fitflux_chi2_kernel(const int* __restrict__ adj_ptr, const int* __restrict__ adj, int r0,
+                                                                  const float* __restrict__ stamps, const int* __restrict__ places,
+                                                                  const int* __restrict__ sfield, int f0, int cs, int nb, int F,
+                                                                  const double* __restrict__ data, const double* __restrict__ weight,
+                                                                  const double* __restrict__ scale, const int* __restrict__ status,
+                                                                  double* __restrict__ chi2, int* __restrict__ npix_out) {
+  __shared__ double s_red[MS_RED];
+  __shared__ double s_a[CHI_TILE * FF_BANDS];     // the amplitude of neighbour q in band b, 0.0 where it has status 4
+  __shared__ int s_row[CHI_TILE], s_pr[CHI_TILE], s_pc[CHI_TILE], s_mask[CHI_TILE];   // its row, placement, bands summed
+  const long gi = (long)r0 + blockIdx.x;
+  const int m = sfield[gi];
+  const int pri = places[2 * gi], pci = places[2 * gi + 1];
+  const int ra = max(pri, 0), rz = min(pri + cs, F), ca = max(pci, 0), cz = min(pci + cs, F);
+  const int w = cz - ca, npix = (rz > ra && w > 0) ? (rz - ra) * w : 0;
+  const int a0 = adj_ptr[blockIdx.x], deg = adj_ptr[blockIdx.x + 1] - a0;
+  const bool once = deg <= CHI_TILE;              // (uniform, like every bound of the loops that hold a barrier)
+  const double* D = data + (long)(m - f0) * F * F * nb;
+  const double* W = weight + (long)(m - f0) * F * F * nb;
+  const int tid = threadIdx.x;
+
+  // neighbours t0 .. t0 + cnt - 1 of the list into LDS: thread q the table of neighbour q, then all threads the amplitudes
+  auto stage = [&](int t0, int cnt) {
+    if (tid < cnt) {
+      const int j = adj[a0 + t0 + tid];
+      int mask = 0;
+      for (int b = 0; b < nb; ++b) mask |= (status[(long)j * nb + b] != 4) << b;
+      s_row[tid] = j;
+      s_pr[tid] = places[2 * (long)j];
+      s_pc[tid] = places[2 * (long)j + 1];
+      s_mask[tid] = mask;
+    }
+    for (int e = tid; e < cnt * FF_BANDS; e += MS_THREADS) {
+      const int q = e / FF_BANDS, b = e % FF_BANDS;
+      double a = 0.0;
+      if (b < nb) {
+        const long o = (long)adj[a0 + t0 + q] * nb + b;
+        if (status[o] != 4) a = scale[o];
+      }
+      s_a[e] = a;
+    }
+  };
+  if (once) {
+    stage(0, deg);
+    __syncthreads();
+  }
+
+  double acc[FF_BANDS], mdl[FF_BANDS], v[FF_BANDS];
+  int cnt[FF_BANDS];
+#pragma unroll
+  for (int b = 0; b < FF_BANDS; ++b) {
+    acc[b] = v[b] = 0.0;
+    cnt[b] = 0;
+  }
+  for (int e0 = 0; e0 < npix; e0 += MS_THREADS) {
+    const int e = e0 + tid;
+    const bool on = e < npix;
+    const int r = ra + (on ? e / w : 0), c = ca + (on ? e % w : 0);
+#pragma unroll
+    for (int b = 0; b < FF_BANDS; ++b) mdl[b] = 0.0;
+    for (int t0 = 0; t0 < deg; t0 += CHI_TILE) {
+      const int tn = min(CHI_TILE, deg - t0);
+      if (!once) {
+        __syncthreads();                         // everyone has read the previous tile
+        stage(t0, tn);
+        __syncthreads();
+      }
+      if (on) {
+        for (int q = 0; q < tn; ++q) {
+          const int dr = r - s_pr[q], dc = c - s_pc[q];
+          if (dr >= 0 && dr < cs && dc >= 0 && dc < cs) {
+            const int mask = s_mask[q];
+            ff_load(stamps + ((long)s_row[q] * cs * cs + (long)dr * cs + dc) * nb, nb, v);
+#pragma unroll
+            for (int b = 0; b < FF_BANDS; ++b) {
+              if (b < nb && ((mask >> b) & 1)) mdl[b] = mdl[b] + s_a[q * FF_BANDS + b] * v[b];
+            }
+          }
+        }
+      }
+    }
+    if (on) {
+      const double* dp = D + ((long)r * F + c) * nb;
+      const double* wp = W + ((long)r * F + c) * nb;
+#pragma unroll
+      for (int b = 0; b < FF_BANDS; ++b) {
+        if (b < nb) {
+          const double wv = wp[b];
+          const bool counts = ff_counts(wv);
+          const double res = dp[b] - mdl[b];
+          acc[b] += counts ? (wv * res) * res : 0.0;
+          cnt[b] += counts ? 1 : 0;
+        }
+      }
+    }
+  }
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+  for (int b = 0; b < FF_BANDS; ++b) {
+    if (b < nb) {                                // (nb is uniform: every thread takes the same barriers)
+      double a[2] = {acc[b], (double)cnt[b]};
+      ms_block_sum<2>(a, s_red);
+      if (tid == 0) {
+        chi2[gi * nb + b] = status[gi * nb + b] == 4 ? nan : a[0];
+        npix_out[gi * nb + b] = (int)a[1];
+      }
+    }
+  }
+}
 }  // namespace
 
 // the refusals that need no table, before any GPU work
@@ -281,9 +434,13 @@ int fitflux_check(const char* who, int cs, int nb, int F, const FitFluxParams& p
   return OK;
 }
 
-int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n) {
+int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n, bool weighted) {
   if (n > 0 && (!o.scale || !o.var || !o.gram || !o.proj || !o.status)) {
     set_error("%s: fit_scale, fit_var, fit_gram, fit_proj and fit_status must all be given", who);
+    return E_INVALID;
+  }
+  if (weighted && n > 0 && (!o.chi2 || !o.npix)) {
+    set_error("%s: fit_chi2 and fit_npix must all be given", who);
     return E_INVALID;
   }
   return OK;
@@ -311,23 +468,34 @@ int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const
   const size_t cap = std::min(total, (size_t)p.scratch_bytes / sizeof(double));
   const size_t rows = (size_t)(M > 0 ? field_ptr[M] - field_ptr[0] : 0);
   plan->scratch_elems = cap;
+  plan->rows = rows;
   plan->pair_cap = std::min(pairs, (cap / nb + rows) / 2 + 1);   // sum n (n + 1) / 2 over fields with sum nb n^2 <= cap
   return OK;
 }
 
-int FitFluxWork::alloc(const FitFluxPlan& plan, int64_t max_fields) {
+int FitFluxWork::alloc(const FitFluxPlan& plan, int64_t max_fields, bool weighted) {
   cap_elems = plan.scratch_elems;
   DV_TRY(scratch.alloc(plan.scratch_elems));
   DV_TRY(pairs.alloc(2 * plan.pair_cap));
+  if (weighted) {                                      // the adjacency: every pair once or twice, a pointer per row and one more
+    adj_cap = std::max<size_t>(2 * plan.pair_cap, 1);
+    adj_ptr_cap = plan.rows + 1;
+    DV_TRY(adj.alloc(adj_cap));
+    DV_TRY(adj_ptr.alloc(adj_ptr_cap));
+  }
   return foff.alloc((size_t)std::max<int64_t>(max_fields, 1));
 }
 
-void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb) {
+void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb, bool weighted) {
   r.add(dev.scale, host.scale, nb);
   r.add(dev.var, host.var, nb);
   r.add(dev.gram, host.gram, nb);
   r.add(dev.proj, host.proj, nb);
   r.add(dev.status, host.status, nb);
+  if (weighted) {
+    r.add(dev.chi2, host.chi2, nb);
+    r.add(dev.npix, host.npix, nb);
+  }
 }
 
 // The complete fields fa .. fz of a call.  Every per-galaxy device array counts from row 0 of the call, like fptr (host and
@@ -337,10 +505,13 @@ void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb)
 // step 1 alone - the scratch keeps G of the last sub-range, gram and proj are written, the other rows are not touched.
 int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
                     const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
-                    int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve) {
+                    int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve,
+                    const double* weight_dev) {
+  const bool chi = weight_dev && solve;                // the chi-square of the weighted fit, behind the solve
   for (int f = fa; f <= fz;) {
     w.foff_h.clear();
     w.pairs_h.clear();
+    if (chi) w.adj_ptr_h.assign(1, 0);                 // degrees first (entry k + 1: row k of the sub-range), offsets below
     size_t used = 0;
     int g = f;
     for (; g <= fz; ++g) {
@@ -349,6 +520,8 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
       if (used + need > w.cap_elems) break;          // (one field fits: fitflux_plan has refused the others)
       w.foff_h.push_back((long long)used);
       used += need;
+      if (chi) w.adj_ptr_h.resize(w.adj_ptr_h.size() + (size_t)n, 0);
+      int* deg = chi ? w.adj_ptr_h.data() + (row0 - fptr_h[f]) + 1 : nullptr;
       for (int i = 0; i < n; ++i) {
         const int pri = places_h[2 * (size_t)(row0 + i)], pci = places_h[2 * (size_t)(row0 + i) + 1];
         for (int j = 0; j <= i; ++j) {
@@ -358,6 +531,10 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
           if (rz > ra && cz > ca) {
             w.pairs_h.push_back(row0 + i);
             w.pairs_h.push_back(row0 + j);
+            if (chi) {
+              ++deg[i];
+              if (j != i) ++deg[j];
+            }
           }
         }
       }
@@ -378,15 +555,45 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
       DV_HIP(hipMemsetAsync(rows.proj + (size_t)r0 * nb, 0, (size_t)(r1 - r0) * nb * sizeof(double), s));
       if (npairs > 0) {
         DV_HIP(hipMemcpyAsync(w.pairs, w.pairs_h.data(), w.pairs_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(fitflux_gram_kernel, dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, w.pairs.get(), stamps_dev,
-                           places_dev, sfield_dev, fptr_dev, w.foff.get(), f, f0, cs, nb, F, data_dev, w.scratch.get(),
-                           rows.gram, rows.proj);
+        if (weight_dev)
+          hipLaunchKernelGGL(fitflux_gram_kernel<true>, dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, w.pairs.get(), stamps_dev,
+                             places_dev, sfield_dev, fptr_dev, w.foff.get(), f, f0, cs, nb, F, data_dev, w.scratch.get(),
+                             rows.gram, rows.proj, weight_dev);
+        else
+          hipLaunchKernelGGL(fitflux_gram_kernel<false>, dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, w.pairs.get(), stamps_dev,
+                             places_dev, sfield_dev, fptr_dev, w.foff.get(), f, f0, cs, nb, F, data_dev, w.scratch.get(),
+                             rows.gram, rows.proj, (const double*)nullptr);
         DV_HIP(hipGetLastError());
       }
       if (solve) {
         hipLaunchKernelGGL(fitflux_solve_kernel, dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev,
                            w.foff.get(), f, nb, p.min_pivot, w.scratch.get(), rows.gram, rows.proj, rows.scale, rows.var,
                            rows.status);
+        DV_HIP(hipGetLastError());
+      }
+      if (chi) {
+        // the pair list is sorted by (i, j <= i): row k takes its earlier neighbours and itself while i = k, the later ones
+        // as i goes on - every list comes out ascending
+        const size_t nr = (size_t)(r1 - r0);
+        for (size_t k = 0; k < nr; ++k) w.adj_ptr_h[k + 1] += w.adj_ptr_h[k];
+        w.adj_h.resize((size_t)w.adj_ptr_h[nr]);
+        w.adj_at_h.assign(w.adj_ptr_h.begin(), w.adj_ptr_h.end() - 1);
+        for (size_t q = 0; q < npairs; ++q) {
+          const int i = w.pairs_h[2 * q], j = w.pairs_h[2 * q + 1];
+          w.adj_h[(size_t)w.adj_at_h[i - r0]++] = j;
+          if (j != i) w.adj_h[(size_t)w.adj_at_h[j - r0]++] = i;
+        }
+        if (nr + 1 > w.adj_ptr_cap || w.adj_h.size() > w.adj_cap) {   // (cannot happen behind fitflux_plan: at most twice the pairs)
+          set_error("flux fit: the adjacency of fields %d .. %d (%zu rows, %zu entries) exceeds what the plan allocated", f, g - 1,
+                    nr, w.adj_h.size());
+          return E_STATE;
+        }
+        DV_HIP(hipMemcpyAsync(w.adj_ptr, w.adj_ptr_h.data(), (nr + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        if (!w.adj_h.empty())
+          DV_HIP(hipMemcpyAsync(w.adj, w.adj_h.data(), w.adj_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(fitflux_chi2_kernel, dim3((unsigned)nr), dim3(MS_THREADS), 0, s, w.adj_ptr.get(), w.adj.get(), r0,
+                           stamps_dev, places_dev, sfield_dev, f0, cs, nb, F, data_dev, weight_dev, rows.scale, rows.status,
+                           rows.chi2, rows.npix);
         DV_HIP(hipGetLastError());
       }
       DV_HIP(hipStreamSynchronize(s));
@@ -400,30 +607,31 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
 // with their stamps, tables and rows (0: half of free device memory beside the scratch, taken after the refusals)
 int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                    const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
-                   hipStream_t s) {
-  const char* who = "dv_scene_fit_flux";
+                   hipStream_t s, const double* weight_h, const char* who) {
+  const bool weighted = weight_h != nullptr;
   DV_TRY(fitflux_check(who, cs, nb, F, p));
   if (N < 0 || M < 0 || !field_ptr || (N > 0 && (!stamps_h || !places_h || !data_h))) {
     set_error("%s: stamps, places, field_ptr and data_fields must all be given", who);
     return E_INVALID;
   }
-  DV_TRY(fitflux_rows_check(who, out_h, N));
+  DV_TRY(fitflux_rows_check(who, out_h, N, weighted));
   DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));   // (the chunks build their own tables)
   FitFluxPlan plan;
   DV_TRY(fitflux_plan(who, field_ptr, M, nb, p, &plan));
   if (N == 0) return OK;
   FitFluxRows d{};
   Rows out;
-  fitflux_columns(out, d, out_h, nb);
+  fitflux_columns(out, d, out_h, nb, weighted);
   const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
   const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + out.bytes();
-  const size_t per_field = felems * sizeof(double) + sizeof(int) + sizeof(long long);
+  const size_t per_field = (weighted ? 2 : 1) * felems * sizeof(double) + sizeof(int) + sizeof(long long);
   DV_HIP(hipSetDevice(device));
   FitFluxWork work;
   if (budget == 0) {
     size_t free_b = 0, total_b = 0;
     DV_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t fixed = plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int);
+    const size_t fixed = plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int) +
+                         (weighted ? (plan.pair_cap * 2 + plan.rows + 1) * sizeof(int) : 0);
     budget = free_b / 2 > fixed ? free_b / 2 - fixed : 0;
   }
   // the chunks: consecutive fields, as many as fit (at least one)
@@ -449,14 +657,15 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
     f = g;
   }
   DevBuf<float> stamps;
-  DevBuf<double> data;
+  DevBuf<double> data, wdata;
   DevBuf<int> places, sf, fptr;
-  DV_TRY(work.alloc(plan, (int64_t)cmax_f));
+  DV_TRY(work.alloc(plan, (int64_t)cmax_f, weighted));
   DV_TRY(stamps.alloc(cmax_s * stamp));
   DV_TRY(places.alloc(cmax_s * 2));
   DV_TRY(sf.alloc(cmax_s));
   DV_TRY(fptr.alloc(cmax_f + 1));
   DV_TRY(data.alloc(cmax_f * felems));
+  if (weighted) DV_TRY(wdata.alloc(cmax_f * felems));
   DV_TRY(out.alloc((int64_t)cmax_s));
   std::vector<int> sf_h, fptr_h;
   StreamDrain drain(s);
@@ -475,8 +684,10 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
     DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), fptr_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
     DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
+    if (weighted)
+      DV_HIP(hipMemcpyAsync(wdata, weight_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
     DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h + (size_t)r0 * 2, fptr_h.data(), 0, fz - fa - 1, cs, nb, F,
-                           p, work, d, s, true));
+                           p, work, d, s, true, weighted ? wdata.get() : nullptr));
     DV_TRY(out.download(r0, n, s));
     DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next chunk
   }

@@ -45,7 +45,7 @@ def _to_records(cols):
 class _Extra(NamedTuple):
     """One optional part of the on-device catalogue of DeblendFieldBatch.deblend_fields: a keyword, the engine call that
     serves it and what it appends to the recarrays.  `c` below is the namespace of one call: bands, band, sky_sigma,
-    field_ptr, psf, psf_index, aper_par, nmc, core."""
+    field_ptr, psf, psf_index, aper_par, nmc, fit_weights, core."""
     key: str                        # the keyword of deblend_fields
     given: Callable                 # its value -> whether the extra is asked for
     label: str                      # how a message names it
@@ -61,6 +61,13 @@ class _Extra(NamedTuple):
     orphans: tuple = ()             # ((keyword, message), ...): keywords that are refused without this one
     refines: Optional[str] = None   # the key of the extra this one goes with and whose engine call it replaces; `why` is
                                     # then the refusal without it
+
+
+def _fit_weight_records(out, c):
+    """What fit_weights appends behind the columns of fit_flux: the last two columns of fit_flux_weighted_dtype"""
+    rec = np.recarray((len(out["fit_chi2"]),), dtype=ms.fit_flux_weighted_dtype(c.bands)[len(ms.fit_flux_dtype(c.bands)):])
+    rec["fit_chi2"], rec["fit_npix"] = out["fit_chi2"], out["fit_npix"]
+    return rec
 
 
 def _aper_kwargs(c):
@@ -123,7 +130,15 @@ _EXTRAS = (
            lambda c: dict(band=c.band),
            lambda c: ms.fit_flux_dtype(c.bands),
            lambda out, c: ms.fit_flux_records(*(out[k] for k in E.FIT_FLUX_KEYS), out["flux"], sky_sigma=c.sky_sigma,
-                                              field_ptr=c.field_ptr)),
+                                              field_ptr=c.field_ptr, weighted=c.fit_weights is not None)),
+    _Extra("fit_weights", lambda v: v is not None, "fit_weights", "need", "the weighted flux fit",
+           "fit_weights needs fit_flux=True: they are the per-pixel inverse variances (0 where a pixel is masked) the flux fit "
+           "weights the observed pixels with",
+           "dv_infer_fields_measure_fit_weighted", "infer_fields_measure_fit_weighted", True,
+           lambda c: dict(band=c.band, weight_fields=c.fit_weights),
+           lambda c: ms.fit_flux_weighted_dtype(c.bands)[len(ms.fit_flux_dtype(c.bands)):],
+           lambda out, c: _fit_weight_records(out, c),
+           refines="fit_flux"),
 )
 
 
@@ -578,6 +593,12 @@ class DeblendFieldBatch:
         """What deblend_fields(measure=True, fit_flux=True) appends behind measure_columns: the recarray of fit_fluxes."""
         return ms.fit_flux_dtype(nb_of_bands)
 
+    @staticmethod
+    def fit_flux_weighted_columns(nb_of_bands):
+        """What deblend_fields(measure=True, fit_flux=True, fit_weights=W) appends behind measure_columns: the recarray of
+        fit_fluxes_weighted - fit_flux_columns, then fit_chi2 and fit_npix."""
+        return ms.fit_flux_weighted_dtype(nb_of_bands)
+
     def _psf_index(self, psf, psf_index, field_ptr):
         """(psf (K, ps, ps), index (N,)) of a deblend_fields(psf=...) call: one image for all galaxies, one per field (the
         index follows from field_ptr), or K images with the caller's index per galaxy - a flat (N,) array or a list of M
@@ -654,7 +675,7 @@ class DeblendFieldBatch:
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
                        measure=False, return_fields=True, measure_samples=0, blendedness=False,
                        psf=None, psf_index=None, apertures=None, flux_fractions=None, aperture_data=False,
-                       sky_sigma=None, fit_flux=False, optimise_positions=False):
+                       sky_sigma=None, fit_flux=False, fit_weights=None, optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -743,19 +764,32 @@ class DeblendFieldBatch:
         fit_scale_err, flux_fit_err; debvader_amd.measure.measurement.fit_fluxes describes them).  sky_sigma, (bands,) or (M,
         bands), is the standard deviation of the sky per pixel the two error columns are derived from; without it they are
         NaN.  The other columns and the fields are those of the same call without it.  It is not available with psf,
-        apertures, blendedness, measure_samples, optimise_positions=True or epistemic_uncertainty_estimation=True."""
+        apertures, blendedness, measure_samples, optimise_positions=True or epistemic_uncertainty_estimation=True.
+
+        fit_weights=W (with fit_flux=True, with or without return_fields): the flux fit under per-pixel weights
+        (dv_infer_fields_measure_fit_weighted).  W (M, F, F, bands) is the inverse variance of every pixel
+        of the fields, 0 where a pixel is masked - any weight outside (0, inf) masks it, NaN included, and a NaN or saturated
+        value of the field under a masked pixel reaches no sum.  The recarrays gain fit_flux_weighted_columns: those of
+        fit_flux, with fit_scale_err = sqrt(fit_var) and flux_fit_err derived from the weights, then fit_chi2, the chi-square
+        of the refitted scene under the galaxy's own counting pixels, and fit_npix, their number
+        (debvader_amd.measure.measurement.fit_fluxes_weighted describes them).  sky_sigma beside fit_weights is
+        refused: the weights already carry the noise.  It changes no other refusal of fit_flux."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
         aperture_data, fit_flux = bool(aperture_data), bool(fit_flux)
         band = 2                        # the band of the measurement (r): the engine call and the blendedness in the apertures
         kw = dict(measure_samples=measure_samples, blendedness=blendedness, psf=psf, psf_index=psf_index, apertures=apertures,
-                  flux_fractions=flux_fractions, aperture_data=aperture_data, fit_flux=fit_flux)
+                  flux_fractions=flux_fractions, aperture_data=aperture_data, fit_flux=fit_flux, fit_weights=fit_weights)
         given = [x.key for x in _EXTRAS if x.given(kw[x.key])]
         for x in _EXTRAS[1:]:           # (measure_samples, the oldest, is refused below its own integer check)
             _refuse_extra(x, kw, given, measure, on_device, fit, mc)
         if sky_sigma is not None and not aperture_data and not fit_flux:
             raise ValueError("sky_sigma is the sky noise of the data-flux errors of aperture_data=True: give aperture_data too")
+        if fit_weights is not None:
+            if sky_sigma is not None:
+                raise ValueError(ms.WEIGHTS_CARRY_THE_NOISE)
+            fit_weights = E.check_fit_weights(fit_weights, self.field_images.shape)                         # (ValueError)
         if sky_sigma is not None:
             sky_sigma = ms.check_sky_sigma(sky_sigma, self.nb_of_fields, self.nb_of_bands)                  # (ValueError)
         aper_par = None
@@ -807,7 +841,7 @@ class DeblendFieldBatch:
             psf, psf_index = self._psf_index(psf, psf_index, field_ptr)
         extras = [x for x in _EXTRAS if x.key in given]
         c = SimpleNamespace(bands=nb, band=band, sky_sigma=sky_sigma, field_ptr=field_ptr, psf=psf, psf_index=psf_index,
-                            aper_par=aper_par, nmc=int(measure_samples), core=core)
+                            aper_par=aper_par, nmc=int(measure_samples), fit_weights=fit_weights, core=core)
         eng.set_normalise(bool(self.normalise))
         try:
             seed = core.next_seed()

@@ -275,6 +275,7 @@ def _aperture_field_out(n, nb, par):
 
 
 FIT_FLUX_KEYS = ("fit_scale", "fit_var", "fit_gram", "fit_proj", "fit_status")
+FIT_FLUX_WEIGHTED_KEYS = FIT_FLUX_KEYS + ("fit_chi2", "fit_npix")      # the weighted fit
 FIT_FLUX_MAX_N = 1024       # galaxies per field of the dense flux fit (DV_FIT_MAX_N)
 
 
@@ -287,11 +288,26 @@ def fit_flux_params(min_pivot=1e-8, scratch_bytes=256 << 20) -> "_lib.DvFitFluxP
     return _lib.DvFitFluxParams(float(min_pivot), int(scratch_bytes))
 
 
-def _fit_flux_out(n, nb):
-    """The result dictionary of the flux fit and its pointers in the C-ABI's order."""
+def _fit_flux_out(n, nb, weighted=False):
+    """The result dictionary of the flux fit and its pointers in the C-ABI's order (weighted: with fit_chi2 and fit_npix)."""
     out = {k: np.zeros((n, nb), np.float64) for k in FIT_FLUX_KEYS[:4]}
     out["fit_status"] = np.zeros((n, nb), np.int32)
-    return out, [_dp(out[k]) for k in FIT_FLUX_KEYS[:4]] + [_ip(out["fit_status"])]
+    ptrs = [_dp(out[k]) for k in FIT_FLUX_KEYS[:4]] + [_ip(out["fit_status"])]
+    if weighted:
+        out["fit_chi2"], out["fit_npix"] = np.zeros((n, nb), np.float64), np.zeros((n, nb), np.int32)
+        ptrs += [_dp(out["fit_chi2"]), _ip(out["fit_npix"])]
+    return out, ptrs
+
+
+def check_fit_weights(weight_fields, shape):
+    """The C-contiguous float64 weight fields of a weighted flux fit: they have the shape of the data fields (M, F, F, bands);
+    a 3-d array is taken as one field.  The values are not looked at - the kernel's comparison 0 < W < inf is the rule."""
+    w = np.asarray(weight_fields)
+    if w.ndim == 3:
+        w = w[None]
+    if w.shape != tuple(shape):
+        raise ValueError(f"expected weight fields of the shape of the data fields {tuple(shape)}, got {np.shape(weight_fields)}")
+    return np.ascontiguousarray(w, dtype=np.float64)
 
 
 def check_measure_mc_args(samples, band, sigma0, tol, max_iter):
@@ -848,7 +864,7 @@ class Context:
     FIT_INELIGIBLE, FIT_DROPPED = 4, 5                 # fit_status of scene_fit_flux beside 0 (fitted)
 
     def scene_fit_flux(self, stamps, places, data_fields, field_ptr=None, min_pivot: float = 1e-8,
-                       scratch_bytes: int = 256 << 20) -> Dict[str, np.ndarray]:
+                       scratch_bytes: int = 256 << 20, weight_fields=None) -> Dict[str, np.ndarray]:
         """The simultaneous flux fit of the deblended models to the observed field on the GPU (dv_scene_fit_flux, DESIGN.md
         section 7q): stamps (N, cs, cs, bands), the mean stamps taken as float32; places (N, 2), the field position (row, col)
         of every stamp's top-left corner; data_fields (M, F, F, bands), the observed fields; field_ptr (M + 1,): stamps
@@ -858,7 +874,13 @@ class Context:
         = sum P_i^2; "fit_proj": h_i = sum P_i D; "fit_status": 0 fitted, FIT_INELIGIBLE G_ii not positive (scale and var
         NaN), FIT_DROPPED the galaxy cannot be told from earlier ones of its field - pivot <= min_pivot G_ii - and keeps the
         network's amplitude (scale 1, var NaN)}.  A field of more than 1024 galaxies, or whose bands x n x n doubles exceed
-        scratch_bytes, is refused."""
+        scratch_bytes, is refused.
+        weight_fields (M, F, F, bands), or (F, F, bands) for one field: the weighted fit (dv_scene_fit_flux_weighted, DESIGN.md
+        section 7s).  W is the inverse variance of every pixel; a pixel counts iff 0 < W < inf, every other weight masks it and
+        nothing under it - a NaN in the data included - reaches a sum.  G_ij = sum W P_i P_j and h_i = sum W P_i D over the
+        counting pixels, fit_var is the variance of fit_scale, and the dictionary gains "fit_chi2", the chi-square of the
+        refitted scene under the galaxy's own counting pixels (NaN with FIT_INELIGIBLE), and "fit_npix" (int32), their number.
+        The five shared arrays of W = 1 everywhere have the bits of the unweighted call."""
         stamps = np.ascontiguousarray(stamps, dtype=np.float32)
         if stamps.ndim != 4 or stamps.shape[1] != stamps.shape[2]:
             raise ValueError(f"expected square stamps (N, cs, cs, bands), got {stamps.shape}")
@@ -876,8 +898,12 @@ class Context:
             field_ptr = [0, n]
         fp = check_field_ptr(field_ptr, M, n)
         par = fit_flux_params(min_pivot, scratch_bytes)
-        out, ptrs = _fit_flux_out(n, nb)
-        if n:
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, data.shape)
+        out, ptrs = _fit_flux_out(n, nb, weights is not None)
+        if n and weights is not None:
+            check(lib.dv_scene_fit_flux_weighted(self._h, _fp(stamps), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n,
+                                                 cs, nb, _dp(data), _dp(weights), M, data.shape[1], C.byref(par), *ptrs))
+        elif n:
             check(lib.dv_scene_fit_flux(self._h, _fp(stamps), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs, nb,
                                         _dp(data), M, data.shape[1], C.byref(par), *ptrs))
         return out
@@ -1512,6 +1538,33 @@ class Engine:
         """infer_fields_measure_fit() for one field (F, F, bands): the field-sized results under singular key names."""
         fields, starts, fp = Engine._one_field(field, starts)
         return Engine._singular(self.infer_fields_measure_fit(fields, starts, fp, places, seed=seed, **kw))
+
+    def infer_fields_measure_fit_weighted(self, fields, starts, field_ptr, places, weight_fields, seed=0, band: int = 2,
+                                          sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, min_pivot: float = 1e-8,
+                                          scratch_bytes: int = 256 << 20, return_fields=True, residual=True,
+                                          mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_fit() under per-pixel weights (dv_infer_fields_measure_fit_weighted):
+        weight_fields has the shape of fields, the inverse variance of every pixel, 0 (or anything not in (0, inf)) where a
+        pixel is masked.  Returns infer_fields_measure's dictionary, bit for bit, plus scene_fit_flux(weight_fields=...)'s
+        {"fit_scale", "fit_var", "fit_gram", "fit_proj", "fit_status", "fit_chi2", "fit_npix"} with the bits of that call on
+        infer_fields_keep's mean stamps.  The weight fields are resident beside the source fields, group by group."""
+        places = Engine._measure_places(places, return_fields, "places are needed for the flux fit, with return_fields=False too")
+        fields = _check_fields(fields)
+        weights = check_fit_weights(weight_fields, fields.shape)
+
+        def extras(N, nb):
+            fpar = fit_flux_params(min_pivot, scratch_bytes)
+            ff, ff_ptrs = _fit_flux_out(N, nb, True)
+            return [(ff, [C.byref(fpar), _dp(weights)] + ff_ptrs)]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_fit_weighted, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
+
+    def infer_cutouts_measure_fit_weighted(self, field, starts, places, weight_field, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_fit_weighted() for one field and its weight field (F, F, bands): the field-sized results under
+        singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_fit_weighted(fields, starts, fp, places, weight_field, seed=seed, **kw))
 
     def scene_fit_flux(self, stamps, places, data_fields, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_fit_flux on this engine's GPU context."""

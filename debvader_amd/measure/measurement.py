@@ -490,7 +490,20 @@ def fit_flux_dtype(nb_of_bands):
             ("fit_independence", "<f8", (nb,)), ("fit_scale_err", "<f8", (nb,)), ("flux_fit_err", "<f8", (nb,))]
 
 
-def fit_flux_records(fit_scale, fit_var, fit_gram, fit_proj, fit_status, flux, sky_sigma=None, field_ptr=None):
+def fit_flux_weighted_dtype(nb_of_bands):
+    """The columns of fit_fluxes_weighted: fit_flux_dtype, then the chi-square of the refitted scene under the
+    galaxy's own counting pixels and their number."""
+    nb = int(nb_of_bands)
+    return fit_flux_dtype(nb) + [("fit_chi2", "<f8", (nb,)), ("fit_npix", "<i4", (nb,))]
+
+
+WEIGHTS_CARRY_THE_NOISE = ("sky_sigma cannot be given together with weights: the weights already carry the noise (they are the "
+                           "inverse variance of every pixel, and fit_scale_err = sqrt(fit_var) follows from them); a uniform sky "
+                           "is weight_fields = 1 / sky_sigma**2 broadcast to the fields")
+
+
+def fit_flux_records(fit_scale, fit_var, fit_gram, fit_proj, fit_status, flux, sky_sigma=None, field_ptr=None, fit_chi2=None,
+                     fit_npix=None, weighted=False):
     """The recarray of fit_fluxes from the five arrays the engine returns (scene_fit_flux's, all (N, bands)) and the stamp
     fluxes `flux` (N, bands) of the catalogue they go with.  Derived on the host: flux_fit = fit_scale * flux, the flux of
     the galaxy with the amplitude the observed pixels ask for; fit_scale_alone = fit_proj / fit_gram, the amplitude with the
@@ -500,7 +513,15 @@ def fit_flux_records(fit_scale, fit_var, fit_gram, fit_proj, fit_status, flux, s
     standard deviation of the sky (field_ptr (M + 1,) gives every galaxy's field; None: one field): fit_scale_err = sky_sigma
     sqrt(fit_var) and flux_fit_err = fit_scale_err |flux|; without it the two are NaN.  NaN follows the GPU's: an ineligible
     galaxy (fit_status 4) is NaN in every derived column of that band; a dropped one (5) has fit_scale 1, so flux_fit = flux,
-    and NaN independence and errors."""
+    and NaN independence and errors.
+    weighted=True (the arrays of a weighted fit): the weights were the inverse variance of every pixel, so
+    fit_var is the variance of fit_scale - fit_scale_err = sqrt(fit_var) and flux_fit_err = fit_scale_err |flux|, and sky_sigma
+    beside them is a ValueError.  With fit_chi2 and fit_npix (N, bands) too the recarray has fit_flux_weighted_dtype."""
+    weighted = bool(weighted) or fit_chi2 is not None or fit_npix is not None
+    if weighted and sky_sigma is not None:
+        raise ValueError(WEIGHTS_CARRY_THE_NOISE)
+    if (fit_chi2 is None) != (fit_npix is None):
+        raise ValueError("fit_chi2 and fit_npix go together (both given or both None)")
     fit_scale = np.asarray(fit_scale, dtype=np.float64)
     if fit_scale.ndim != 2:
         raise ValueError(f"expected fit_scale (N, bands), got {fit_scale.shape}")
@@ -512,15 +533,21 @@ def fit_flux_records(fit_scale, fit_var, fit_gram, fit_proj, fit_status, flux, s
     flux = np.asarray(flux, dtype=np.float64)
     if flux.shape != (n, nb):
         raise ValueError(f"expected flux ({n}, {nb}), got {flux.shape}")
-    rec = np.recarray((n,), dtype=fit_flux_dtype(nb))
+    rec = np.recarray((n,), dtype=fit_flux_dtype(nb) if fit_chi2 is None else fit_flux_weighted_dtype(nb))
     rec["fit_scale"], rec["fit_var"], rec["fit_gram"], rec["fit_proj"] = fit_scale, fit_var, fit_gram, fit_proj
     rec["fit_status"] = fit_status
+    if fit_chi2 is not None:
+        rec["fit_chi2"] = np.asarray(fit_chi2, dtype=np.float64).reshape(n, nb)
+        rec["fit_npix"] = np.asarray(fit_npix, dtype=np.int32).reshape(n, nb)
     with np.errstate(all="ignore"):
         rec["flux_fit"] = fit_scale * flux
         ok = fit_gram > 0                                     # (NaN > 0 is False)
         rec["fit_scale_alone"] = np.where(ok, fit_proj / np.where(ok, fit_gram, 1.0), np.nan)
         rec["fit_independence"] = 1.0 / np.sqrt(fit_var * fit_gram)
-        if sky_sigma is None:
+        if weighted:
+            rec["fit_scale_err"] = np.sqrt(fit_var)
+            rec["flux_fit_err"] = rec["fit_scale_err"] * np.abs(flux)
+        elif sky_sigma is None:
             rec["fit_scale_err"] = np.nan
             rec["flux_fit_err"] = np.nan
         else:
@@ -540,7 +567,8 @@ def fit_fluxes(stamps_mean, places, data_fields, field_ptr=None, catalogue=None,
     """Simultaneous flux fit of N deblended galaxies to the observed fields on the GPU: the shapes of
     the galaxies of a field are held fixed at the network's mean stamps and all their amplitudes are fitted to the observed
     pixels at once, per band, by linear least squares - the flux re-fit of the SDSS deblender, the Tractor and scarlet.  A bias
-    of the network on any member of a blend does not bias the fitted fluxes of the others.
+    of the network on any member of a blend does not bias the fitted fluxes of the others.  Every pixel of a band has the same
+    weight here; fit_fluxes_weighted takes a variance plane and a mask.
 
     parameters:
         stamps_mean: the network's mean stamps, (N, cutout_size, cutout_size, bands)
@@ -557,10 +585,40 @@ def fit_fluxes(stamps_mean, places, data_fields, field_ptr=None, catalogue=None,
     (fit_flux_records).  fit_status FIT_STATUS_INELIGIBLE: the stamp is zero or wholly outside the field in that band;
     FIT_STATUS_DROPPED: the galaxy cannot be told from the earlier galaxies of its field and keeps the network's amplitude.
     """
+    return _fit_fluxes(stamps_mean, places, data_fields, None, field_ptr, catalogue, sky_sigma, min_pivot, ctx)
+
+
+def fit_fluxes_weighted(stamps_mean, places, data_fields, weight_fields, field_ptr=None, catalogue=None, sky_sigma=None,
+                        min_pivot=1e-8, ctx=None):
+    """fit_fluxes under per-pixel inverse-variance weights, with masks and a chi-square.
+
+    parameters: those of fit_fluxes, and
+        weight_fields: the inverse variance of every pixel, of the shape of data_fields ((F, F, bands) for one field), 0 where
+            a pixel is masked.  A pixel counts iff 0 < W < inf: any other weight masks it, NaN included, and nothing under a
+            masked pixel - a NaN or a saturated value of the field - is read into a sum.  The values are not validated on the
+            host; only the shape is, before any GPU work
+        sky_sigma: must stay None - the weights already carry the noise; anything else is a ValueError
+    returns a np.recarray of fit_flux_weighted_dtype: the columns of fit_fluxes, where fit_gram = sum W P^2, fit_proj = sum W P D
+    over the counting pixels, fit_var is the variance of fit_scale, fit_scale_err = sqrt(fit_var) and flux_fit_err =
+    fit_scale_err |flux|; then fit_chi2, the sum of W (D - model)^2 over the galaxy's own counting pixels with the model the
+    refitted scene (NaN where the galaxy is FIT_STATUS_INELIGIBLE - no counting pixel, or a zero stamp), and fit_npix, the
+    number of those pixels.  A user with a uniform sky passes weight_fields = 1 / sky_sigma**2 broadcast to the fields.
+    """
+    if weight_fields is None:
+        raise ValueError("weight_fields must be given: fit_fluxes is the unweighted fit")
+    return _fit_fluxes(stamps_mean, places, data_fields, weight_fields, field_ptr, catalogue, sky_sigma, min_pivot, ctx)
+
+
+def _fit_fluxes(stamps_mean, places, data_fields, weight_fields, field_ptr, catalogue, sky_sigma, min_pivot, ctx):
+    """The body fit_fluxes and fit_fluxes_weighted share (weight_fields None: the unweighted fit)"""
     data = np.asarray(data_fields, dtype=np.float64)
     if data.ndim == 3:
         data = data[None]
     M = data.shape[0]
+    if weight_fields is not None:
+        if sky_sigma is not None:
+            raise ValueError(WEIGHTS_CARRY_THE_NOISE)
+        weight_fields = E.check_fit_weights(weight_fields, data.shape)   # (ValueError before any GPU work)
     if data.ndim == 4 and sky_sigma is not None:
         check_sky_sigma(sky_sigma, M, data.shape[-1])                    # (ValueError before any GPU work)
     stamps = np.asarray(stamps_mean, dtype=np.float32)
@@ -574,6 +632,10 @@ def fit_fluxes(stamps_mean, places, data_fields, field_ptr=None, catalogue=None,
         flux = np.asarray(catalogue["flux"], dtype=np.float64)
     if ctx is None:
         ctx = E.default_context()
+    if weight_fields is not None:
+        out = ctx.scene_fit_flux(stamps, places, data, field_ptr=field_ptr, min_pivot=min_pivot, weight_fields=weight_fields)
+        return fit_flux_records(*(out[k] for k in E.FIT_FLUX_KEYS), flux, field_ptr=field_ptr, fit_chi2=out["fit_chi2"],
+                                fit_npix=out["fit_npix"])
     out = ctx.scene_fit_flux(stamps, places, data, field_ptr=field_ptr, min_pivot=min_pivot)
     return fit_flux_records(out["fit_scale"], out["fit_var"], out["fit_gram"], out["fit_proj"], out["fit_status"], flux,
                             sky_sigma=sky_sigma, field_ptr=field_ptr)

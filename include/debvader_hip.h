@@ -706,6 +706,31 @@ int dv_infer_fields_measure_fit(dv_model* m, const double* fields, int32_t M, in
                                 double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
                                 int32_t* iters, int32_t* status, const dv_fit_flux_params* fit, double* fit_scale,
                                 double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status);
+/* The same fit under per-pixel weights.  weight_fields [M][F][F][nb] float64, laid out like the data
+ * fields, is meant as the inverse variance of every pixel.  A pixel of band b COUNTS iff 0 < W < inf: zero, negative, infinite
+ * and NaN weights all mask it, its terms are exactly +0.0 by selection, and nothing under it - a NaN in the data included -
+ * reaches a sum.  No host pass validates W.  Step 1 becomes G_ij = sum (W P_i) P_j and h_i = sum (W P_i) D over the counting
+ * pixels (the product with W first; with W = 1.0 everywhere every term has the bits of the unweighted one); steps 2 - 5 are
+ * unchanged, so a galaxy without a counting pixel has fit_status 4, and fit_var IS the variance of fit_scale.  Two more
+ * outputs [N][nb]: fit_npix, the number of counting pixels of the galaxy in the band (0 for a stamp wholly outside or wholly
+ * masked), and fit_chi2 = sum over them of (W r) r with r = D - sum_j a_j P_j, j in ascending row order over the galaxies of
+ * the field that cover the pixel and do not have fit_status 4, a_j = fit_scale (1 for a dropped galaxy); NaN where the galaxy
+ * itself has fit_status 4.  dv_infer_fields_measure_fit_weighted keeps the weight fields resident beside the source fields (one
+ * more field-sized buffer per resident field); its outputs have the bits of dv_scene_fit_flux_weighted on
+ * dv_infer_fields_keep's mean stamps.  Both refuse what the unweighted calls refuse, and a null weight_fields, fit_chi2 or
+ * fit_npix, before any GPU work (DV_E_INVALID, the engine stays usable). */
+int dv_scene_fit_flux_weighted(dv_ctx* ctx, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                               int32_t cs, int32_t nb, const double* data_fields, const double* weight_fields, int32_t M,
+                               int32_t F, const dv_fit_flux_params* params, double* fit_scale, double* fit_var, double* fit_gram,
+                               double* fit_proj, int32_t* fit_status, double* fit_chi2, int32_t* fit_npix);
+int dv_infer_fields_measure_fit_weighted(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb,
+                                         const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                                         uint64_t seed, const dv_measure_params* params, double* mean_fields,
+                                         double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
+                                         double* flux_err, double* shape, int32_t* iters, int32_t* status,
+                                         const dv_fit_flux_params* fit, const double* weight_fields, double* fit_scale,
+                                         double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status,
+                                         double* fit_chi2, int32_t* fit_npix);
 
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)

@@ -82,6 +82,18 @@ protocol (warm-up, then --repeat alternating runs, median and spread) -
 
 With --profile-one: warm up, one fp32 call (b), exit.
 
+--fit-weights: what per-pixel weights, masks and the chi-square add to the flux fit, in the same
+protocol -
+
+    (a) catalogue+fit-flux         :  the catalogue-only call with fit_flux=True: the baseline, to be compared with --fit-flux's
+                                      leg (b) of the commit before - the unweighted path allocates and launches nothing new
+    (b) catalogue+fit-flux+weights :  the same with fit_weights: uniform(0.25, 4) inverse variances with a tenth of the pixels
+                                      masked, as large as the fields and uploaded beside them
+
+    python tools/measure_bench.py --fit-weights [--fields 1024] [--size 259] [--repeat 5]
+
+With --profile-one: warm up, one fp32 call (b), exit.
+
 The cost is reported, not gated.
 """
 import argparse
@@ -234,7 +246,12 @@ def main_fit_flux(a):
     base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
     fields = np.ascontiguousarray(base[np.arange(M) % 16])
     quiet = io.StringIO()
-    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "fit_flux": True}
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "fit_flux": True, "fit_weights": bool(a.fit_weights)}
+    weights = None
+    if a.fit_weights:
+        w16 = rng.uniform(0.25, 4.0, size=base.shape)
+        w16[rng.random(base.shape) < 0.1] = 0.0
+        weights = np.ascontiguousarray(w16[np.arange(M) % 16])
     dists = None
     for dtype in a.dtypes.split(","):
         net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
@@ -245,19 +262,23 @@ def main_fit_flux(a):
                   f"per field; max_batch {a.max_batch}")
         seen = []
 
-        def with_fit():
+        def with_fit(**kw):
             res = DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=True, measure=True, return_fields=False,
-                                                                fit_flux=True)
+                                                                fit_flux=True, **kw)
             seen[:] = [np.concatenate([r["fit_status"] for r in res]), np.concatenate([r["fit_independence"] for r in res])]
             return sum(len(r) for r in res)
 
-        legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False),
-                "catalogue+fit-flux": with_fit}
+        if a.fit_weights:
+            legs = {"catalogue+fit-flux": with_fit, "catalogue+fit-flux+weights": lambda: with_fit(fit_weights=weights)}
+        else:
+            legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False),
+                    "catalogue+fit-flux": with_fit}
+        first, last = list(legs)
         with redirect_stdout(quiet):
             for fn in legs.values():           # warm-up
                 fn()
             if a.profile_one:
-                with_fit()
+                legs[last]()
                 net._core.engine.close()
                 return
             times = {k: [] for k in legs}
@@ -276,9 +297,9 @@ def main_fit_flux(a):
         tc, tf = (float(np.median(times[k])) for k in legs)
         spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
         ind = seen[1][np.isfinite(seen[1])]
-        print(f"{dtype} catalogue+fit-flux / catalogue {tf / tc:.3f}: {1e3 * (tf - tc):+.1f} ms for {n} galaxies, "
-              f"{1e6 * (tf - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times['catalogue']):.3f} and "
-              f"{spread(times['catalogue+fit-flux']):.3f}); fit_status 0 .. 5 over galaxies x bands: {counts}; median "
+        print(f"{dtype} {last} / {first} {tf / tc:.3f}: {1e3 * (tf - tc):+.1f} ms for {n} galaxies, "
+              f"{1e6 * (tf - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times[first]):.3f} and "
+              f"{spread(times[last]):.3f}); fit_status 0 .. 5 over galaxies x bands: {counts}; median "
               f"fit_independence {float(np.median(ind)) if ind.size else float('nan'):.3f}")
         net._core.engine.close()
     print(json.dumps(result))
@@ -437,8 +458,9 @@ def main():
     ap.add_argument("--apertures", action="store_true")
     ap.add_argument("--aperture-data", action="store_true")
     ap.add_argument("--fit-flux", action="store_true")
+    ap.add_argument("--fit-weights", action="store_true")
     a = ap.parse_args()
-    if a.fit_flux:
+    if a.fit_flux or a.fit_weights:
         return main_fit_flux(a)
     if a.aperture_data:
         return main_apertures(a, data=True)
