@@ -429,9 +429,21 @@ constexpr int FF_MAX_N = 1024;                        // galaxies per field (DV_
 struct FitFluxParams { double min_pivot; int64_t scratch_bytes; };
 // (chi2, npix: the two rows of the weighted fit, 7s - null in the unweighted one)
 struct FitFluxRows { double *scale, *var, *gram, *proj; int* status; double* chi2 = nullptr; int* npix = nullptr; };
-struct FitFluxPlan { size_t scratch_elems = 0, pair_cap = 0, rows = 0; };
+// The sky background fitted jointly: q = 1 (a constant) or 3 (a plane) more unknowns per field and band behind
+// the galaxies.  FitFluxSky: the per-field outputs, device or host - coef [.][nb][q], cov [.][nb][q][q], status [.][nb][q],
+// npix [.][nb] -, counted from field 0 of the call; q = 0: no sky, nothing more is allocated, copied or launched.
+struct FitFluxSky { int q = 0; double* coef = nullptr; double* cov = nullptr; int* status = nullptr; long long* npix = nullptr; };
+constexpr int FF_SKY_BANDS = 16;                      // (the band limit of the flux fit)
+constexpr int FF_SKY_TILE = 4096;                     // pixels of one partial sum of the field sums
+inline int fitflux_sky_q(int order) { return order == 0 ? 1 : 3; }
+inline size_t fitflux_sky_acc(int q) { return q == 1 ? 3 : 10; }   // K (lower triangle), c, the counting pixels
+inline size_t fitflux_sky_tiles(int F) { return ((size_t)F * F + FF_SKY_TILE - 1) / FF_SKY_TILE; }
+// (q, sky_part: the sky terms and the doubles of per-tile partial sums of one field, 0 without a sky)
+struct FitFluxPlan { size_t scratch_elems = 0, pair_cap = 0, rows = 0; int q = 0; size_t sky_part = 0; };
 struct FitFluxWork {
   DevBuf<double> scratch;
+  DevBuf<double> sky_part, sky_sums;                  // sky: the partial sums and K, c of the fields of a sub-range
+  int q = 0;
   DevBuf<int> pairs;
   DevBuf<long long> foff;
   DevBuf<int> adj_ptr, adj;                           // weighted: the CSR adjacency of a sub-range (rows + 1, <= 2 pairs)
@@ -441,22 +453,33 @@ struct FitFluxWork {
   std::vector<int> adj_ptr_h, adj_h, adj_at_h;
   static size_t bytes(const FitFluxPlan& plan, size_t fields, bool weighted = false) {
     return plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int) + fields * sizeof(long long) +
-           (weighted ? (plan.pair_cap * 2 + plan.rows + 1) * sizeof(int) : 0);
+           (weighted ? (plan.pair_cap * 2 + plan.rows + 1) * sizeof(int) : 0) +
+           (plan.q ? (fields ? fields : 1) * (plan.sky_part + FF_SKY_BANDS * fitflux_sky_acc(plan.q)) * sizeof(double) : 0);
   }
   int alloc(const FitFluxPlan& plan, int64_t max_fields, bool weighted = false);
 };
 int fitflux_check(const char* who, int cs, int nb, int F, const FitFluxParams& p);
 int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n, bool weighted = false);
-int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan);
+// sky_order -1: no sky; 0 / 1: the bordered systems of 7t, (n + q)^2 doubles per band (F sizes the partial sums)
+int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan,
+                 int sky_order = -1, int F = 0);
+int fitflux_sky_check(const char* who, int sky_order, const FitFluxSky& o, const FitFluxRows& rows, bool weighted);
 // weight_dev: the weight fields from field f0 on, laid out like data_dev (7s), or null: the unweighted fit.  With weights the
 // chi-square kernel runs behind the solve and rows.chi2 / rows.npix are written
+// sky (7t): q = 1 or 3 sky terms per field and band and the device arrays of their outputs, counted from field 0 of the call; the
+// work area must have been planned for the same q.  A sub-range without galaxies is launched when there is a sky
 int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
                     const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
                     int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve = true,
-                    const double* weight_dev = nullptr);
+                    const double* weight_dev = nullptr, const FitFluxSky& sky = FitFluxSky{});
 int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                    const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
-                   hipStream_t s, const double* weight_h = nullptr, const char* who = "dv_scene_fit_flux");
+                   hipStream_t s, const double* weight_h = nullptr, const char* who = "dv_scene_fit_flux", int sky_order = -1,
+                   const FitFluxSky& sky_h = FitFluxSky{});
+// step 1 of the bordered system of one field (7t): the dense [nb][n + q][n + q] lower triangle and its right-hand side
+// [n + q][nb] to the host, the bits the solve starts from
+int scene_fit_flux_sky_gram(const float* stamps_h, const int32_t* places_h, int64_t n, int cs, int nb, const double* data_h,
+                            const double* weight_h, int F, int sky_order, double* gram_h, double* rhs_h, int device, hipStream_t s);
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,

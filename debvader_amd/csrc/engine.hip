@@ -3952,6 +3952,31 @@ int dv_scene_fit_flux_gram(dv_ctx* c, const float* stamps, const int32_t* places
   return scene_fit_flux_gram(stamps, places, n, cs, nb, data_field, F, gram, proj, c->device, c->stream);
 }
 
+// the fit with a sky background fitted jointly, with weights or without: every refusal is scene_fit_flux's
+int dv_scene_fit_flux_sky(dv_ctx* c, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs,
+                          int32_t nb, const double* data_fields, const double* weight_fields, int32_t M, int32_t F,
+                          const dv_fit_flux_params* params, int32_t sky_order, double* fit_scale, double* fit_var, double* fit_gram,
+                          double* fit_proj, int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, double* sky_coef,
+                          double* sky_cov, int32_t* sky_status, int64_t* sky_npix) {
+  if (!c) return DV_E_INVALID;
+  if (!params) {
+    set_error("dv_scene_fit_flux_sky: params must be given");
+    return DV_E_INVALID;
+  }
+  static_assert(sizeof(long long) == sizeof(int64_t), "sky_npix is int64");
+  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, FitFluxParams{params->min_pivot, params->scratch_bytes},
+                        FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, 0, c->device, c->stream,
+                        weight_fields, "dv_scene_fit_flux_sky", sky_order,
+                        FitFluxSky{-1, sky_coef, sky_cov, sky_status, (long long*)sky_npix});
+}
+
+int dv_scene_fit_flux_sky_gram(dv_ctx* c, const float* stamps, const int32_t* places, int64_t n, int32_t cs, int32_t nb,
+                               const double* data_field, const double* weight_field, int32_t F, int32_t sky_order, double* gram,
+                               double* rhs) {
+  if (!c) return DV_E_INVALID;
+  return scene_fit_flux_sky_gram(stamps, places, n, cs, nb, data_field, weight_field, F, sky_order, gram, rhs, c->device, c->stream);
+}
+
 int dv_scene_measure_mc(dv_ctx* c, const float* samples, int32_t S, int64_t N, int32_t cs, int32_t nb,
                         const dv_measure_params* p, double* flux_mean, double* flux_std, double* shape_mean,
                         double* shape_std, int32_t* n_ok, double* sample_flux, double* sample_shape, int32_t* sample_status) {
@@ -5134,7 +5159,8 @@ struct ApertureFieldStage {         // the apertures of every stamp on the mean 
 
 // dv_infer_fields_measure_fit: the parameters in, five rows out (host); _fit_weighted (7s): the host weight fields [M][F][F][nb]
 // in too, and the rows carry fit_chi2 and fit_npix
-struct FitFluxOut { FitFluxParams par{}; FitFluxRows rows{}; const double* weights = nullptr; };
+// _fit_sky (7t): the order of the sky fitted jointly (-1: none) and its per-field outputs (host)
+struct FitFluxOut { FitFluxParams par{}; FitFluxRows rows{}; const double* weights = nullptr; int sky_order = -1; FitFluxSky sky{}; };
 
 struct FitFluxStage {               // the simultaneous flux fit of every field's mean stamps to its source field (7q)
   DevBuf<float> store;              // the mean stamps of all N stamps: a field's are read when its composite is complete
@@ -5143,10 +5169,35 @@ struct FitFluxStage {               // the simultaneous flux fit of every field'
   Rows rows;
   void columns(const FitFluxOut& o, int nb) { fitflux_columns(rows, dev, o.rows, nb, o.weights != nullptr); }
   size_t bytes_per_stamp(int cs, int nb) const { return (size_t)cs * cs * nb * sizeof(float) + rows.bytes(); }
+  DevBuf<double> sky_coef, sky_cov;  // the per-field outputs of a fit with sky (7t), downloaded with the rows
+  DevBuf<int> sky_status;
+  DevBuf<long long> sky_npix;
+  FitFluxSky sky{};
+  static size_t sky_bytes(int q, size_t M, int nb) {
+    return M * nb * ((size_t)q * (q + 1) * sizeof(double) + q * sizeof(int) + sizeof(long long));
+  }
   int alloc(const FitFluxPlan& plan, int64_t N, int64_t M, int cs, int nb, bool weighted) {
     DV_TRY(store.alloc((size_t)N * cs * cs * nb));
     DV_TRY(work.alloc(plan, M, weighted));
+    if (const size_t q = (size_t)plan.q) {
+      const size_t e = (size_t)M * nb;
+      DV_TRY(sky_coef.alloc(e * q));
+      DV_TRY(sky_cov.alloc(e * q * q));
+      DV_TRY(sky_status.alloc(e * q));
+      DV_TRY(sky_npix.alloc(e));
+      sky = FitFluxSky{plan.q, sky_coef.get(), sky_cov.get(), sky_status.get(), sky_npix.get()};
+    }
     return rows.alloc(N);
+  }
+  // fields f0 .. f0 + nf - 1 of the call to the host arrays
+  int sky_download(const FitFluxSky& h, size_t f0, size_t nf, int nb, hipStream_t s) const {
+    const size_t q = (size_t)sky.q, o = f0 * nb, e = nf * nb;
+    DV_HIP(hipMemcpyAsync(h.coef + o * q, sky.coef + o * q, e * q * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(h.cov + o * q * q, sky.cov + o * q * q, e * q * q * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(h.status + o * q, sky.status + o * q, e * q * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(h.npix + o, sky.npix + o, e * sizeof(long long), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return OK;
   }
   void bind(PipeJob::FitFlux& q) const { q.store = store; }
 };
@@ -5185,9 +5236,24 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, j.starts, places, sfield, fptr32));
   const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
   FitFluxPlan ffplan;
-  if (rq.fit_flux) DV_TRY(fitflux_plan(who, field_ptr, M, nb, rq.fit_flux->par, &ffplan));   // (before anything is written or queued)
+  if (rq.fit_flux)                                     // (before anything is written or queued)
+    DV_TRY(fitflux_plan(who, field_ptr, M, nb, rq.fit_flux->par, &ffplan, rq.fit_flux->sky_order, F));
   if (rq.fields) fields_write_empty(*rq.fields, fields, M, field_ptr, felems);
-  if (N == 0) return DV_OK;
+  // A fit with sky (7t) solves the fields without galaxies too.  The seam below reaches the fields of a group; every other one
+  // - the call without stamps, the empty fields before the first group, between two groups and behind the last - takes the
+  // host-array path, whose field sums have the same bits: they depend on the field alone.
+  auto sky_alone = [&](int fa, int fz) -> int {        // the empty fields fa .. fz - 1
+    if (fz <= fa) return DV_OK;
+    const FitFluxOut& o = *rq.fit_flux;
+    const size_t q = (size_t)ffplan.q, e = (size_t)fa * nb;
+    const std::vector<int64_t> none((size_t)(fz - fa) + 1, 0);
+    const FitFluxSky h{-1, o.sky.coef + e * q, o.sky.cov + e * q * q, o.sky.status + e * q, o.sky.npix + e};
+    return scene_fit_flux(nullptr, nullptr, none.data(), 0, m->A.H, nb, fields + (size_t)fa * felems, fz - fa, F, o.par, o.rows,
+                          0, m->ctx->device, m->ctx->stream, o.weights ? o.weights + (size_t)fa * felems : nullptr, who,
+                          o.sky_order, h);
+  };
+  const bool ff_sky = rq.fit_flux && ffplan.q != 0;
+  if (N == 0) return ff_sky ? sky_alone(0, M) : DV_OK;
   TinyCall tiny(m, N);
   DV_HIP(hipSetDevice(m->ctx->device));
   hipStream_t s = m->ctx->stream;
@@ -5243,7 +5309,8 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   }
   if (rq.fit_flux) {
     ffs.columns(*rq.fit_flux, nb);
-    reserve += (size_t)N * ffs.bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M, wfields != nullptr);
+    reserve += (size_t)N * ffs.bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M, wfields != nullptr) +
+               FitFluxStage::sky_bytes(ffplan.q, (size_t)M, nb);
     if (wfields) per_field += fb;
   }
   size_t budget = 0;
@@ -5311,6 +5378,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   j.sinks.mse = tab.mse;
   // per group: upload -> the pipeline -> download the sinks
   int prev_last = -1, prev_first = -1;
+  int sky_next = 0;                                    // with sky: the first field that has not been fitted yet
   for (size_t gi = 0; gi < groups.size(); ++gi) {
     const FieldGroup& g = groups[gi];
     const size_t ng = (size_t)(g.f1 - g.f0 + 1), goff = (size_t)g.f0 * felems;
@@ -5345,7 +5413,12 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
                                        mean_f, fdev, rq.aper->par, aperture_field_rows_at(afs.dev, r0, rq.aper->par, nb), s));
         if (rq.fit_flux)               // (the stamp store, the placements and the tables count from stamp 0 of the call)
           DV_TRY(launch_fit_flux(ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, places, fptr32.data(), fa, fz, c.cs,
-                                 nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s, true, wfields ? wdev.get() : nullptr));
+                                 nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s, true, wfields ? wdev.get() : nullptr, ffs.sky));
+        if (ff_sky) {
+          DV_TRY(ffs.sky_download(rq.fit_flux->sky, (size_t)fa, (size_t)(fz - fa + 1), nb, s));
+          DV_TRY(sky_alone(sky_next, fa));
+          sky_next = fz + 1;
+        }
       }
     }
     if (rq.fields) {
@@ -5367,6 +5440,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (rq.aper) DV_TRY(rows_download(aps.rows, N, s));
   if (rq.aper_field) DV_TRY(rows_download(afs.rows, N, s));
   if (rq.fit_flux) DV_TRY(rows_download(ffs.rows, N, s));
+  if (ff_sky) DV_TRY(sky_alone(sky_next, M));
   if (rq.fields) DV_TRY(mc.download(N, s));
   if (fitting) DV_TRY(fit.download(*rq.fields, N, s));
   drain.dismiss();
@@ -5514,6 +5588,8 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const Catalo
   if (rq.fit_flux) {
     DV_TRY(fitflux_check(who, m->A.H, a.nb, a.F, rq.fit_flux->par));
     DV_TRY(fitflux_rows_check(who, rq.fit_flux->rows, N, rq.fit_flux->weights != nullptr));
+    if (rq.fit_flux->sky.q) DV_TRY(fitflux_sky_check(who, rq.fit_flux->sky_order, rq.fit_flux->sky, rq.fit_flux->rows,
+                                                     rq.fit_flux->weights != nullptr));
     DV_TRY(seam_places_check(who, a));
   }
   if (rq.regauss) {
@@ -5702,6 +5778,30 @@ int dv_infer_fields_measure_fit_weighted(dv_model* m, const double* fields, int3
   rq.fit_flux = FitFluxOut{FitFluxParams{fit->min_pivot, fit->scratch_bytes},
                            FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields};
   return infer_fields_measure_entry("dv_infer_fields_measure_fit_weighted", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
+}
+
+// ---- the flux fit with a sky background fitted jointly: dv_infer_fields_measure_fit[_weighted] - weight_fields
+// may be NULL, and fit_chi2 and fit_npix are NULL exactly then - plus the order of the sky and its per-field outputs
+int dv_infer_fields_measure_fit_sky(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                    const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                    const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                    double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                    int32_t* iters, int32_t* status, const dv_fit_flux_params* fit, const double* weight_fields,
+                                    int32_t sky_order, double* fit_scale, double* fit_var, double* fit_gram, double* fit_proj,
+                                    int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, double* sky_coef, double* sky_cov,
+                                    int32_t* sky_status, int64_t* sky_npix) {
+  if (!m) return DV_E_INVALID;
+  if (!fit) {
+    set_error("dv_infer_fields_measure_fit_sky: the flux-fit params must be given");
+    return DV_E_INVALID;
+  }
+  FieldsRequest rq;
+  rq.fit_flux = FitFluxOut{FitFluxParams{fit->min_pivot, fit->scratch_bytes},
+                           FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields,
+                           sky_order, FitFluxSky{-1, sky_coef, sky_cov, sky_status, (long long*)sky_npix}};
+  return infer_fields_measure_entry("dv_infer_fields_measure_fit_sky", m,
                                     {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
                                      residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }

@@ -43,6 +43,16 @@
 //      workgroup reduction, NaN where i has status 4; fit_npix = the number of counting pixels of i, written for every galaxy.
 //   fitflux_chi2_kernel   one 256-thread workgroup per galaxy, behind the solve of its sub-range; the neighbours come from a CSR
 //                         adjacency the host builds beside the pair list.
+// The fit with a sky background fitted jointly adds Q = 1 (a constant) or 3 (a plane) unknowns per field and band
+// behind the galaxies, in the basis B_0 = 1, B_1 = (2 r - F + 1) / F, B_2 = (2 c - F + 1) / F of the field pixel (r, c): the
+// model is sum a_i P_i + sum s_t B_t over all (counting) pixels of the field, the system [[G, E], [E^T, K]] [a; s] = [h; c] with
+// E_it = sum (W P_i) B_t, K_tu = sum (W B_t) B_u, c_t = sum (W B_t) D.  Every kernel is a template on Q, and Q = 0 is the code
+// above, instruction for instruction; new:
+//   fitflux_border_kernel     one workgroup per galaxy: E_it into row n + t of the field's scratch, whose rows hold n + Q doubles.
+//   fitflux_skysum_kernel     K, c and the counting pixels of every field: a streaming reduction over D and W in tiles of 4096
+//                             pixels, four bands per workgroup, one row of partial sums per tile;
+//   fitflux_skyreduce_kernel  the partial sums in tile order - an order that depends on F alone.
+// The sky terms are eliminated last: the factorisation of the galaxy block is the one of the fit without sky, bit for bit.
 // No atomics; ordinary vector stores only.
 #include "common.h"
 #include "measure_dev.h"
@@ -57,7 +67,7 @@
 namespace dv {
 
 namespace {
-constexpr int FF_BANDS = 16;
+constexpr int FF_BANDS = FF_SKY_BANDS;
 
 // the nb floats at p, widened, into the band slots; an 8-byte load for every pair of slots that starts at an aligned address
 // (ODD: p itself is 4 bytes past one, slot 0 goes alone).  Slots from nb on are left alone; nothing past p[nb - 1] is read.
@@ -92,7 +102,7 @@ __device__ __forceinline__ void ff_load(const float* __restrict__ p, int nb, dou
 // unweighted instantiation never touches `weight`.
 __device__ __forceinline__ bool ff_counts(double w) { return w > 0.0 && w < __longlong_as_double(0x7ff0000000000000LL); }
 
-template <bool WEIGHTED>
+template <bool WEIGHTED, int Q = 0>
 __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __restrict__ pairs, const float* __restrict__ stamps,
                                                                   const int* __restrict__ places, const int* __restrict__ sfield,
                                                                   const int* __restrict__ fptr, const long long* __restrict__ foff,
@@ -103,7 +113,7 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __r
   __shared__ double s_red[MS_RED];
   const long gi = pairs[2 * (long)blockIdx.x], gj = pairs[2 * (long)blockIdx.x + 1];
   const int m = sfield[gi];
-  const int row0 = fptr[m], n = fptr[m + 1] - row0;
+  const int row0 = fptr[m], n = fptr[m + 1] - row0 + Q;   // (the row length of the scratch: Q sky terms behind the galaxies, 7t)
   const int pri = places[2 * gi], pci = places[2 * gi + 1], prj = places[2 * gj], pcj = places[2 * gj + 1];
   // the intersection of the two stamps and the field, in field pixels (the host lists a pair only where it is not empty)
   const int ra = max(max(pri, prj), 0), rz = min(min(pri, prj) + cs, F);
@@ -175,27 +185,254 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __r
   }
 }
 
+// The weight of band b at a pixel and whether the pixel counts there; unweighted: 1.0, and every pixel counts
+template <bool WEIGHTED>
+__device__ __forceinline__ double ff_weight(const double* __restrict__ wp, int b, bool& on) {
+  const double wv = WEIGHTED ? wp[b] : 1.0;
+  on = WEIGHTED ? ff_counts(wv) : true;
+  return wv;
+}
+
+// The sky basis of the bordered fit (7t) at field row or column x of a field of side F: an integer numerator, one division.
+__device__ __forceinline__ double ff_basis(int x, int F) { return (double)(2 * x - F + 1) / (double)F; }
+
+// The sums of a field that the sky terms need (7t, step 1), Q = 1: K00, c0 and the counting pixels; Q = 3: K00 K10 K11 K20
+// K21 K22, c0 c1 c2 and the counting pixels - SKY_ACC(Q) doubles per band.  A streaming reduction over D (and W) in a tiling
+// that depends on F alone: tile blockIdx.x % ntiles holds SKY_TILE consecutive pixels in raster order, thread t takes pixels
+// t, t + 256, ... of it, consecutive lanes consecutive pixels; blockIdx.y takes SKY_GROUP bands in statically indexed slots
+// (ten accumulators per band: all sixteen bands at once would not fit the registers); blockIdx.x also counts the fields of
+// the sub-range, field fd0 + blockIdx.x / ntiles of `data`.  One ms_block_sum per band and half of its accumulators; thread 0
+// writes the tile's partial sums to part [field][band][tile][acc].
+constexpr int SKY_TILE = FF_SKY_TILE, SKY_GROUP = 4;
+__host__ __device__ constexpr int SKY_ACC(int q) { return q == 1 ? 3 : 10; }
+
+template <bool WEIGHTED, int Q>
+__global__ __launch_bounds__(MS_THREADS) void fitflux_skysum_kernel(int fd0, int nb, int F, int ntiles, const double* __restrict__ data,
+                                                                    const double* __restrict__ weight, double* __restrict__ part) {
+  constexpr int NA = SKY_ACC(Q);
+  __shared__ double s_red[MS_RED];
+  const int tile = (int)(blockIdx.x % (unsigned)ntiles), b0 = (int)blockIdx.y * SKY_GROUP, fl = (int)(blockIdx.x / (unsigned)ntiles);
+  const long npix = (long)F * F;
+  const double* D = data + (long)(fd0 + fl) * npix * nb;
+  const double* W = WEIGHTED ? weight + (long)(fd0 + fl) * npix * nb : nullptr;
+  double acc[SKY_GROUP][NA];
+#pragma unroll
+  for (int g = 0; g < SKY_GROUP; ++g)
+#pragma unroll
+    for (int a = 0; a < NA; ++a) acc[g][a] = 0.0;
+  const long e0 = (long)tile * SKY_TILE;
+  for (int k = threadIdx.x; k < SKY_TILE; k += MS_THREADS) {
+    const long e = e0 + k;
+    if (e >= npix) break;
+    const int r = (int)(e / F), c = (int)(e - (long)r * F);
+    const double B1 = Q == 3 ? ff_basis(r, F) : 0.0, B2 = Q == 3 ? ff_basis(c, F) : 0.0;
+#pragma unroll
+    for (int g = 0; g < SKY_GROUP; ++g) {
+      if (b0 + g < nb) {
+        const double d = D[e * nb + b0 + g];
+        bool on;
+        const double wv = ff_weight<WEIGHTED>(WEIGHTED ? W + e * nb : nullptr, b0 + g, on);
+        const double w0 = wv * 1.0;
+        if constexpr (Q == 1) {
+          acc[g][0] += on ? w0 * 1.0 : 0.0;
+          acc[g][1] += on ? w0 * d : 0.0;
+          acc[g][2] += on ? 1.0 : 0.0;
+        } else {
+          const double w1 = wv * B1, w2 = wv * B2;
+          acc[g][0] += on ? w0 * 1.0 : 0.0;
+          acc[g][1] += on ? w1 * 1.0 : 0.0;
+          acc[g][2] += on ? w1 * B1 : 0.0;
+          acc[g][3] += on ? w2 * 1.0 : 0.0;
+          acc[g][4] += on ? w2 * B1 : 0.0;
+          acc[g][5] += on ? w2 * B2 : 0.0;
+          acc[g][6] += on ? w0 * d : 0.0;
+          acc[g][7] += on ? w1 * d : 0.0;
+          acc[g][8] += on ? w2 * d : 0.0;
+          acc[g][9] += on ? 1.0 : 0.0;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < SKY_GROUP; ++g) {
+    if (b0 + g < nb) {                          // (uniform: every thread takes the same barriers)
+      double* o = part + (((long)fl * nb + b0 + g) * ntiles + tile) * NA;
+      if constexpr (Q == 1) {
+        double a[3] = {acc[g][0], acc[g][1], acc[g][2]};
+        ms_block_sum<3>(a, s_red);
+        if (threadIdx.x == 0) {
+          o[0] = a[0];
+          o[1] = a[1];
+          o[2] = a[2];
+        }
+      } else {
+        double a[5] = {acc[g][0], acc[g][1], acc[g][2], acc[g][3], acc[g][4]};
+        double c[5] = {acc[g][5], acc[g][6], acc[g][7], acc[g][8], acc[g][9]};
+        ms_block_sum<5>(a, s_red);
+        ms_block_sum<5>(c, s_red);
+        if (threadIdx.x == 0) {
+#pragma unroll
+          for (int k = 0; k < 5; ++k) {
+            o[k] = a[k];
+            o[5 + k] = c[k];
+          }
+        }
+      }
+    }
+  }
+}
+
+// The partial sums of field fbase + blockIdx.x, band blockIdx.y, in tile order: thread t adds tiles t, t + 256, ... one after
+// another, then one ms_block_sum - an order that depends on F alone.  Thread 0 writes K and c to sums [field of the sub-range]
+// [nb][SKY_ACC] (the solve reads its diagonal and right-hand side there), K into the corner of the field's scratch and the
+// counting pixels to npix [field of the call][nb].
+template <int Q>
+__global__ __launch_bounds__(MS_THREADS) void fitflux_skyreduce_kernel(const int* __restrict__ fptr, const long long* __restrict__ foff,
+                                                                       int fbase, int nb, int ntiles, const double* __restrict__ part,
+                                                                       double* __restrict__ scratch, double* __restrict__ sums,
+                                                                       long long* __restrict__ npix) {
+  constexpr int NA = SKY_ACC(Q);
+  __shared__ double s_red[MS_RED];
+  const int fl = (int)blockIdx.x, m = fbase + fl, b = (int)blockIdx.y;
+  const int n = fptr[m + 1] - fptr[m], nt = n + Q;
+  const double* p = part + ((long)fl * nb + b) * ntiles * NA;
+  double acc[NA];
+#pragma unroll
+  for (int a = 0; a < NA; ++a) acc[a] = 0.0;
+  for (int t = threadIdx.x; t < ntiles; t += MS_THREADS) {
+#pragma unroll
+    for (int a = 0; a < NA; ++a) acc[a] += p[(long)t * NA + a];
+  }
+  if constexpr (Q == 1) {
+    ms_block_sum<NA>(acc, s_red);
+  } else {
+    double a[5], c[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      a[k] = acc[k];
+      c[k] = acc[5 + k];
+    }
+    ms_block_sum<5>(a, s_red);
+    ms_block_sum<5>(c, s_red);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      acc[k] = a[k];
+      acc[5 + k] = c[k];
+    }
+  }
+  if (threadIdx.x == 0) {
+    double* o = sums + ((long)fl * nb + b) * NA;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) o[a] = acc[a];
+    npix[(long)m * nb + b] = (long long)acc[NA - 1];
+    double* S = scratch + foff[fl] + (long)b * nt * nt;
+    int a = 0;
+#pragma unroll
+    for (int t = 0; t < Q; ++t)
+#pragma unroll
+      for (int u = 0; u <= t; ++u) S[(long)(n + t) * nt + n + u] = acc[a++];
+  }
+}
+
+// E_it = sum over the pixels of galaxy r0 + blockIdx.x of (W P_i) B_t (7t, step 1; unweighted P_i B_t), into row n + t,
+// column i of the field's scratch.  One workgroup per galaxy: the pixels of the clipped stamp in raster order, stride 256,
+// ff_load and one ms_block_sum per band, as the diagonal path of the Gram kernel - in a kernel of its own, so that kernel
+// keeps its registers.  A stamp wholly outside its field writes the empty sums.
+template <bool WEIGHTED, int Q>
+__global__ __launch_bounds__(MS_THREADS) void fitflux_border_kernel(int r0, const float* __restrict__ stamps, const int* __restrict__ places,
+                                                                    const int* __restrict__ sfield, const int* __restrict__ fptr,
+                                                                    const long long* __restrict__ foff, int fbase, int f0, int cs,
+                                                                    int nb, int F, double* __restrict__ scratch,
+                                                                    const double* __restrict__ weight) {
+  __shared__ double s_red[MS_RED];
+  const long gi = (long)r0 + blockIdx.x;
+  const int m = sfield[gi];
+  const int row0 = fptr[m], n = fptr[m + 1] - row0, nt = n + Q;
+  const int pri = places[2 * gi], pci = places[2 * gi + 1];
+  const int ra = max(pri, 0), rz = min(pri + cs, F), ca = max(pci, 0), cz = min(pci + cs, F);
+  const int w = cz - ca, npix = (rz > ra && w > 0) ? (rz - ra) * w : 0;
+  const float* Pi = stamps + gi * cs * cs * nb;
+  const double* W = WEIGHTED ? weight + (long)(m - f0) * F * F * nb : nullptr;
+  double e[FF_BANDS][Q], vi[FF_BANDS];
+#pragma unroll
+  for (int b = 0; b < FF_BANDS; ++b) {
+    vi[b] = 0.0;
+#pragma unroll
+    for (int t = 0; t < Q; ++t) e[b][t] = 0.0;
+  }
+  for (int x = threadIdx.x; x < npix; x += MS_THREADS) {
+    const int r = ra + x / w, c = ca + x % w;
+    ff_load(Pi + ((long)(r - pri) * cs + (c - pci)) * nb, nb, vi);
+    const double* wp = WEIGHTED ? W + ((long)r * F + c) * nb : nullptr;
+    const double B1 = Q == 3 ? ff_basis(r, F) : 0.0, B2 = Q == 3 ? ff_basis(c, F) : 0.0;
+#pragma unroll
+    for (int b = 0; b < FF_BANDS; ++b) {
+      if (b < nb) {
+        bool on;
+        const double wv = ff_weight<WEIGHTED>(wp, b, on);
+        const double wi = wv * vi[b];
+        e[b][0] += on ? wi * 1.0 : 0.0;
+        if constexpr (Q == 3) {
+          e[b][1] += on ? wi * B1 : 0.0;
+          e[b][2] += on ? wi * B2 : 0.0;
+        }
+      }
+    }
+  }
+  double* S = scratch + foff[m - fbase] + (long)n * nt + (gi - row0);
+#pragma unroll
+  for (int b = 0; b < FF_BANDS; ++b) {
+    if (b < nb) {                              // (nb is uniform: every thread takes the same barriers)
+      ms_block_sum<Q>(e[b], s_red);
+      if (threadIdx.x == 0) {
+#pragma unroll
+        for (int t = 0; t < Q; ++t) S[(long)b * nt * nt + (long)t * nt] = e[b][t];
+      }
+    }
+  }
+}
+
 // Field fbase + blockIdx.x, band blockIdx.y.  S = its [n][n] scratch: on entry G in the lower triangle, zeros above.  W(i, j),
 // j < i - the working copy, then L - lies at S[j n + i]; the diagonal in place.  LDS: the status of every galaxy and the
 // right-hand side, 12 KB.
+// Q > 0 is the bordered system of 7t: nt = n + Q unknowns - the galaxies, then the sky terms, whose rows of the scratch the
+// border and sky-reduce kernels filled; the diagonal and right-hand side of sky term t come from skysums [field of the
+// sub-range][nb][SKY_ACC(Q)].  Every step below runs on the nt unknowns; what differs for a sky term: a dropped one has
+// coefficient 0.0 and leaves the right-hand sides alone (step 4 sums over the dropped GALAXIES), and its outputs go to
+// sky_coef / sky_status [field][nb][Q] and sky_cov [field][nb][Q][Q], the corner of (L^-1)^T L^-1.  The sky terms come last, so
+// every operation on the galaxy block is the one of Q = 0, in the same order; Q = 0 is the kernel as it was.
+template <int Q>
 __global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __restrict__ fptr, const long long* __restrict__ foff,
                                                                    int fbase, int nb, double min_pivot,
                                                                    double* __restrict__ scratch, const double* __restrict__ gram,
                                                                    const double* __restrict__ proj, double* __restrict__ scale,
-                                                                   double* __restrict__ var, int* __restrict__ status) {
-  __shared__ double s_y[FF_MAX_N];
-  __shared__ int s_st[FF_MAX_N];
+                                                                   double* __restrict__ var, int* __restrict__ status,
+                                                                   const double* __restrict__ skysums, double* __restrict__ sky_coef,
+                                                                   double* __restrict__ sky_cov, int* __restrict__ sky_status) {
+  __shared__ double s_y[FF_MAX_N + Q];
+  __shared__ int s_st[FF_MAX_N + Q];
   const int m = fbase + (int)blockIdx.x, b = (int)blockIdx.y;
   const long row0 = fptr[m];
-  const int n = fptr[m + 1] - (int)row0;
+  const int ng = fptr[m + 1] - (int)row0;      // the galaxies
+  const int n = ng + Q;                        // the unknowns
   if (n <= 0) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double* S = scratch + foff[blockIdx.x] + (long)b * n * n;
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double* ks = Q > 0 ? skysums + ((long)blockIdx.x * nb + b) * SKY_ACC(Q) : nullptr;
+  // G_kk as step 1 left it and the right-hand side of unknown k (sky term t: K_tt at t (t + 3) / 2 of the sums, c_t behind K)
+  auto diag0 = [&](int k) -> double {
+    if (Q > 0 && k >= ng) return ks[(k - ng) * (k - ng + 3) / 2];
+    return gram[(row0 + k) * nb + b];
+  };
+  auto rhs0 = [&](int k) -> double {
+    if (Q > 0 && k >= ng) return ks[Q * (Q + 1) / 2 + (k - ng)];
+    return proj[(row0 + k) * nb + b];
+  };
 
   // step 2 and the working copy
   for (int i = tid; i < n; i += MS_THREADS) {
-    const double gii = gram[(row0 + i) * nb + b];
+    const double gii = diag0(i);
     s_st[i] = (ms_finite(gii) && gii > 0.0) ? 0 : 4;
   }
   for (int i = wave; i < n; i += MS_THREADS / 64)
@@ -206,7 +443,7 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __
   for (int k = 0; k < n; ++k) {
     if (s_st[k] != 0) continue;              // (uniform; s_st[k] was last written behind a barrier)
     const double d = S[(long)k * n + k];
-    const double gkk = gram[(row0 + k) * nb + b];
+    const double gkk = diag0(k);
     if (d <= min_pivot * gkk) {              // (uniform: every thread read the same two values)
       __syncthreads();                       // everyone has read s_st[k]
       if (tid == 0) s_st[k] = 5;
@@ -230,9 +467,9 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __
 
   // step 4: the right-hand side less the dropped galaxies at the network's amplitude (G as the Gram kernel left it)
   for (int i = tid; i < n; i += MS_THREADS) {
-    double hp = proj[(row0 + i) * nb + b];
+    double hp = rhs0(i);
     if (s_st[i] == 0) {
-      for (int k = 0; k < n; ++k)
+      for (int k = 0; k < ng; ++k)
         if (s_st[k] == 5) hp = hp - (k < i ? S[(long)i * n + k] : S[(long)k * n + i]);   // (G_ik lies at (max, min))
     }
     s_y[i] = hp;
@@ -284,12 +521,38 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __
         acc = acc + x * x;
       }
     }
-    if (i < n) {
+    if (i < ng) {
       const long o = (row0 + i) * nb + b;
       const int st = s_st[i];
       scale[o] = st == 0 ? s_y[i] : st == 5 ? 1.0 : nan;
       var[o] = st == 0 ? acc : nan;
       status[o] = st;
+    }
+  }
+  if constexpr (Q > 0) {
+    // the sky terms: the corner of (L^-1)^T L^-1 from the last Q columns of X, rows ascending, in one thread
+    __syncthreads();                           // the columns of X are complete
+    if (tid == 0) {
+      const long o = (long)m * nb + b;
+      for (int t = 0; t < Q; ++t) {
+        const int st = s_st[ng + t];
+        sky_coef[o * Q + t] = st == 0 ? s_y[ng + t] : st == 5 ? 0.0 : nan;
+        sky_status[o * Q + t] = st;
+        for (int u = 0; u <= t; ++u) {
+          double cv = nan;
+          if (st == 0 && s_st[ng + u] == 0) {
+            cv = 0.0;
+            for (int r = ng + t; r < n; ++r) {
+              if (s_st[r] != 0) continue;
+              const double xt = r == ng + t ? 1.0 / S[(long)r * n + r] : S[(long)r * n + ng + t];
+              const double xu = r == ng + u ? 1.0 / S[(long)r * n + r] : S[(long)r * n + ng + u];
+              cv = cv + xt * xu;
+            }
+          }
+          sky_cov[(o * Q + t) * Q + u] = cv;
+          sky_cov[(o * Q + u) * Q + t] = cv;
+        }
+      }
     }
   }
 }
@@ -301,15 +564,22 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __
 // then r = D - M and the terms (W r) r where the pixel counts.  The neighbours' placements, amplitudes and band masks are
 // staged in LDS CHI_TILE at a time (a degree of 40 is one tile: staged once, before the pixel loop), so the inner loop reads
 // no global table; one ms_block_sum per band carries chi2 and the pixel count (an integer below 2^24, exact in a double).
+// Q > 0 (7t): M gains sum_t s_t B_t(p) behind the neighbours, t ascending, over the sky terms of the field with sky_status 0;
+// their coefficients and band masks lie in LDS beside the staged neighbours.  Q = 0 is the kernel as it was.
 constexpr int CHI_TILE = 64;
 
+template <int Q>
 __global__ __launch_bounds__(MS_THREADS) void fitflux_chi2_kernel(const int* __restrict__ adj_ptr, const int* __restrict__ adj, int r0,
                                                                   const float* __restrict__ stamps, const int* __restrict__ places,
                                                                   const int* __restrict__ sfield, int f0, int cs, int nb, int F,
                                                                   const double* __restrict__ data, const double* __restrict__ weight,
                                                                   const double* __restrict__ scale, const int* __restrict__ status,
-                                                                  double* __restrict__ chi2, int* __restrict__ npix_out) {
+                                                                  double* __restrict__ chi2, int* __restrict__ npix_out,
+                                                                  const double* __restrict__ sky_coef,
+                                                                  const int* __restrict__ sky_status) {
   __shared__ double s_red[MS_RED];
+  __shared__ double s_sky[(Q > 0 ? Q : 1) * FF_BANDS];   // Q > 0: the coefficient of sky term t in band b
+  __shared__ int s_skymask[Q > 0 ? Q : 1];               //        the bands in which it has sky_status 0
   __shared__ double s_a[CHI_TILE * FF_BANDS];     // the amplitude of neighbour q in band b, 0.0 where it has status 4
   __shared__ int s_row[CHI_TILE], s_pr[CHI_TILE], s_pc[CHI_TILE], s_mask[CHI_TILE];   // its row, placement, bands summed
   const long gi = (long)r0 + blockIdx.x;
@@ -344,6 +614,18 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_chi2_kernel(const int* __r
       s_a[e] = a;
     }
   };
+  if constexpr (Q > 0) {
+    if (tid < Q) {
+      int mask = 0;
+      for (int b = 0; b < nb; ++b) mask |= (sky_status[((long)m * nb + b) * Q + tid] == 0) << b;
+      s_skymask[tid] = mask;
+    }
+    if (tid < Q * FF_BANDS) {
+      const int t = tid / FF_BANDS, b = tid % FF_BANDS;
+      s_sky[tid] = b < nb ? sky_coef[((long)m * nb + b) * Q + t] : 0.0;
+    }
+    __syncthreads();
+  }
   if (once) {
     stage(0, deg);
     __syncthreads();
@@ -380,6 +662,17 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_chi2_kernel(const int* __r
               if (b < nb && ((mask >> b) & 1)) mdl[b] = mdl[b] + s_a[q * FF_BANDS + b] * v[b];
             }
           }
+        }
+      }
+    }
+    if (Q > 0 && on) {
+      const double B[3] = {1.0, ff_basis(r, F), ff_basis(c, F)};
+#pragma unroll
+      for (int t = 0; t < Q; ++t) {
+        const int mask = s_skymask[t];
+#pragma unroll
+        for (int b = 0; b < FF_BANDS; ++b) {
+          if (b < nb && ((mask >> b) & 1)) mdl[b] = mdl[b] + s_sky[t * FF_BANDS + b] * B[t];
         }
       }
     }
@@ -448,18 +741,46 @@ int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n, bool we
 
 // the two refusals by field (field_ptr has passed the caller's checks) and what the fields need: the doubles of dense scratch
 // and the pair entries of the largest sub-range that goes through the scratch at once
-int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan) {
+// the refusals of the sky calls (7t) that need no table: the order, the sky outputs, and chi-square outputs that do not match
+// the weights
+int fitflux_sky_check(const char* who, int sky_order, const FitFluxSky& o, const FitFluxRows& rows, bool weighted) {
+  if (sky_order != 0 && sky_order != 1) {
+    set_error("%s: sky_order must be 0 (a constant) or 1 (a plane), got %d", who, sky_order);
+    return E_INVALID;
+  }
+  if (!o.coef || !o.cov || !o.status || !o.npix) {
+    set_error("%s: sky_coef, sky_cov, sky_status and sky_npix must all be given", who);
+    return E_INVALID;
+  }
+  if (!weighted && (rows.chi2 || rows.npix)) {
+    set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: without weight_fields both must be NULL", who);
+    return E_INVALID;
+  }
+  if (weighted && (!rows.chi2 || !rows.npix)) {
+    set_error("%s: fit_chi2 and fit_npix must all be given", who);
+    return E_INVALID;
+  }
+  return OK;
+}
+
+int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan, int sky_order,
+                 int F) {
   size_t total = 0, pairs = 0;
+  const size_t q = sky_order < 0 ? 0 : (size_t)fitflux_sky_q(sky_order);
   for (int f = 0; f < M; ++f) {
     const int64_t n = field_ptr[f + 1] - field_ptr[f];
     if (n > FF_MAX_N) {
       set_error("%s: field %d has %ld galaxies, the dense fit takes at most %d per field", who, f, (long)n, FF_MAX_N);
       return E_INVALID;
     }
-    const size_t need = (size_t)nb * n * n * sizeof(double);
+    const size_t need = (size_t)nb * (n + q) * (n + q) * sizeof(double);
     if (need > (size_t)p.scratch_bytes) {
-      set_error("%s: field %d has %ld galaxies: its Gram matrices need %zu bytes of scratch (bands x n x n doubles), "
-                "scratch_bytes is %ld", who, f, (long)n, need, (long)p.scratch_bytes);
+      if (q)
+        set_error("%s: field %d has %ld galaxies and %zu sky terms: its bordered matrices need %zu bytes of scratch (bands x "
+                  "(n + q) x (n + q) doubles), scratch_bytes is %ld", who, f, (long)n, q, need, (long)p.scratch_bytes);
+      else
+        set_error("%s: field %d has %ld galaxies: its Gram matrices need %zu bytes of scratch (bands x n x n doubles), "
+                  "scratch_bytes is %ld", who, f, (long)n, need, (long)p.scratch_bytes);
       return E_INVALID;
     }
     total += need / sizeof(double);
@@ -470,11 +791,19 @@ int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const
   plan->scratch_elems = cap;
   plan->rows = rows;
   plan->pair_cap = std::min(pairs, (cap / nb + rows) / 2 + 1);   // sum n (n + 1) / 2 over fields with sum nb n^2 <= cap
+  plan->q = (int)q;
+  plan->sky_part = q ? (size_t)nb * fitflux_sky_tiles(F) * fitflux_sky_acc((int)q) : 0;
   return OK;
 }
 
 int FitFluxWork::alloc(const FitFluxPlan& plan, int64_t max_fields, bool weighted) {
   cap_elems = plan.scratch_elems;
+  q = plan.q;
+  if (q) {
+    const size_t nf = (size_t)std::max<int64_t>(max_fields, 1);
+    DV_TRY(sky_part.alloc(nf * plan.sky_part));
+    DV_TRY(sky_sums.alloc(nf * FF_BANDS * fitflux_sky_acc(q)));
+  }
   DV_TRY(scratch.alloc(plan.scratch_elems));
   DV_TRY(pairs.alloc(2 * plan.pair_cap));
   if (weighted) {                                      // the adjacency: every pair once or twice, a pointer per row and one more
@@ -506,8 +835,14 @@ void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb,
 int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
                     const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
                     int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve,
-                    const double* weight_dev) {
+                    const double* weight_dev, const FitFluxSky& sky) {
   const bool chi = weight_dev && solve;                // the chi-square of the weighted fit, behind the solve
+  const int q = sky.q;                                 // the sky terms of every field (7t), 0: none
+  const int ntiles = q ? (int)fitflux_sky_tiles(F) : 0;
+  if (q != w.q) {                                      // (cannot happen: the plan that sized the work carries q)
+    set_error("flux fit: %d sky terms asked of a work area planned for %d", q, w.q);
+    return E_STATE;
+  }
   for (int f = fa; f <= fz;) {
     w.foff_h.clear();
     w.pairs_h.clear();
@@ -516,7 +851,7 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
     int g = f;
     for (; g <= fz; ++g) {
       const int row0 = fptr_h[g], n = fptr_h[g + 1] - row0;
-      const size_t need = (size_t)nb * n * n;
+      const size_t need = (size_t)nb * (n + q) * (n + q);
       if (used + need > w.cap_elems) break;          // (one field fits: fitflux_plan has refused the others)
       w.foff_h.push_back((long long)used);
       used += need;
@@ -545,30 +880,65 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
     }
     const int r0 = fptr_h[f], r1 = fptr_h[g];
     const size_t npairs = w.pairs_h.size() / 2;
-    if (r1 > r0) {
+    if (r1 > r0 || q) {                                // (a field without galaxies still has its sky)
       DV_TRY(w.pairs.ensure(w.pairs_h.size()));
       DV_TRY(w.foff.ensure(w.foff_h.size()));
       DV_HIP(hipMemcpyAsync(w.foff, w.foff_h.data(), w.foff_h.size() * sizeof(long long), hipMemcpyHostToDevice, s));
       DV_HIP(hipMemsetAsync(w.scratch, 0, used * sizeof(double), s));
       // (a stamp wholly outside its field has no pair: its G_ii and h_i are the empty sums)
-      DV_HIP(hipMemsetAsync(rows.gram + (size_t)r0 * nb, 0, (size_t)(r1 - r0) * nb * sizeof(double), s));
-      DV_HIP(hipMemsetAsync(rows.proj + (size_t)r0 * nb, 0, (size_t)(r1 - r0) * nb * sizeof(double), s));
+      if (r1 > r0) {
+        DV_HIP(hipMemsetAsync(rows.gram + (size_t)r0 * nb, 0, (size_t)(r1 - r0) * nb * sizeof(double), s));
+        DV_HIP(hipMemsetAsync(rows.proj + (size_t)r0 * nb, 0, (size_t)(r1 - r0) * nb * sizeof(double), s));
+      }
       if (npairs > 0) {
         DV_HIP(hipMemcpyAsync(w.pairs, w.pairs_h.data(), w.pairs_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        if (weight_dev)
-          hipLaunchKernelGGL(fitflux_gram_kernel<true>, dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, w.pairs.get(), stamps_dev,
-                             places_dev, sfield_dev, fptr_dev, w.foff.get(), f, f0, cs, nb, F, data_dev, w.scratch.get(),
-                             rows.gram, rows.proj, weight_dev);
-        else
-          hipLaunchKernelGGL(fitflux_gram_kernel<false>, dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, w.pairs.get(), stamps_dev,
-                             places_dev, sfield_dev, fptr_dev, w.foff.get(), f, f0, cs, nb, F, data_dev, w.scratch.get(),
-                             rows.gram, rows.proj, (const double*)nullptr);
+#define DV_FF_GRAM(...)                                                                                                        \
+  hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, w.pairs.get(), stamps_dev, places_dev, sfield_dev, \
+                     fptr_dev, w.foff.get(), f, f0, cs, nb, F, data_dev, w.scratch.get(), rows.gram, rows.proj, weight_dev)
+        if (weight_dev) {
+          if (q == 0) DV_FF_GRAM(fitflux_gram_kernel<true>);
+          else if (q == 1) DV_FF_GRAM(fitflux_gram_kernel<true, 1>);
+          else DV_FF_GRAM(fitflux_gram_kernel<true, 3>);
+        } else {
+          if (q == 0) DV_FF_GRAM(fitflux_gram_kernel<false>);
+          else if (q == 1) DV_FF_GRAM(fitflux_gram_kernel<false, 1>);
+          else DV_FF_GRAM(fitflux_gram_kernel<false, 3>);
+        }
+#undef DV_FF_GRAM
+        DV_HIP(hipGetLastError());
+      }
+      if (q) {
+        // the border E (one workgroup per galaxy), then the field sums: per-tile partials, then K, c and the counting pixels
+        const unsigned nf = (unsigned)(g - f), ngrp = (unsigned)((nb + SKY_GROUP - 1) / SKY_GROUP);
+        if ((size_t)ntiles * nf > 0x7fffffffu) {
+          set_error("flux fit: %u fields of %d tiles exceed the grid of the field sums", nf, ntiles);
+          return E_INVALID;
+        }
+#define DV_FF_SKY(WT, QQ)                                                                                                       \
+  do {                                                                                                                          \
+    if (r1 > r0)                                                                                                                \
+      hipLaunchKernelGGL((fitflux_border_kernel<WT, QQ>), dim3((unsigned)(r1 - r0)), dim3(MS_THREADS), 0, s, r0, stamps_dev,       \
+                         places_dev, sfield_dev, fptr_dev, w.foff.get(), f, f0, cs, nb, F, w.scratch.get(), weight_dev);       \
+    hipLaunchKernelGGL((fitflux_skysum_kernel<WT, QQ>), dim3((unsigned)ntiles * nf, ngrp), dim3(MS_THREADS), 0, s, f - f0, nb, F,   \
+                       ntiles, data_dev, weight_dev, w.sky_part.get());                                                       \
+    hipLaunchKernelGGL((fitflux_skyreduce_kernel<QQ>), dim3(nf, (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev, w.foff.get(), f,  \
+                       nb, ntiles, w.sky_part.get(), w.scratch.get(), w.sky_sums.get(), sky.npix);                            \
+  } while (0)
+        if (weight_dev) {
+          if (q == 1) DV_FF_SKY(true, 1); else DV_FF_SKY(true, 3);
+        } else {
+          if (q == 1) DV_FF_SKY(false, 1); else DV_FF_SKY(false, 3);
+        }
+#undef DV_FF_SKY
         DV_HIP(hipGetLastError());
       }
       if (solve) {
-        hipLaunchKernelGGL(fitflux_solve_kernel, dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev,
-                           w.foff.get(), f, nb, p.min_pivot, w.scratch.get(), rows.gram, rows.proj, rows.scale, rows.var,
-                           rows.status);
+#define DV_FF_SOLVE(QQ)                                                                                                         \
+  hipLaunchKernelGGL((fitflux_solve_kernel<QQ>), dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev,         \
+                     w.foff.get(), f, nb, p.min_pivot, w.scratch.get(), rows.gram, rows.proj, rows.scale, rows.var, rows.status, \
+                     (const double*)w.sky_sums.get(), sky.coef, sky.cov, sky.status)
+        if (q == 0) DV_FF_SOLVE(0); else if (q == 1) DV_FF_SOLVE(1); else DV_FF_SOLVE(3);
+#undef DV_FF_SOLVE
         DV_HIP(hipGetLastError());
       }
       if (chi) {
@@ -591,9 +961,14 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
         DV_HIP(hipMemcpyAsync(w.adj_ptr, w.adj_ptr_h.data(), (nr + 1) * sizeof(int), hipMemcpyHostToDevice, s));
         if (!w.adj_h.empty())
           DV_HIP(hipMemcpyAsync(w.adj, w.adj_h.data(), w.adj_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(fitflux_chi2_kernel, dim3((unsigned)nr), dim3(MS_THREADS), 0, s, w.adj_ptr.get(), w.adj.get(), r0,
-                           stamps_dev, places_dev, sfield_dev, f0, cs, nb, F, data_dev, weight_dev, rows.scale, rows.status,
-                           rows.chi2, rows.npix);
+#define DV_FF_CHI2(QQ)                                                                                                          \
+  hipLaunchKernelGGL((fitflux_chi2_kernel<QQ>), dim3((unsigned)nr), dim3(MS_THREADS), 0, s, w.adj_ptr.get(), w.adj.get(), r0,     \
+                     stamps_dev, places_dev, sfield_dev, f0, cs, nb, F, data_dev, weight_dev, (const double*)rows.scale,       \
+                     (const int*)rows.status, rows.chi2, rows.npix, (const double*)sky.coef, (const int*)sky.status)
+        if (nr > 0) {
+          if (q == 0) DV_FF_CHI2(0); else if (q == 1) DV_FF_CHI2(1); else DV_FF_CHI2(3);
+        }
+#undef DV_FF_CHI2
         DV_HIP(hipGetLastError());
       }
       DV_HIP(hipStreamSynchronize(s));
@@ -607,24 +982,29 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
 // with their stamps, tables and rows (0: half of free device memory beside the scratch, taken after the refusals)
 int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                    const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
-                   hipStream_t s, const double* weight_h, const char* who) {
+                   hipStream_t s, const double* weight_h, const char* who, int sky_order, const FitFluxSky& sky_h) {
   const bool weighted = weight_h != nullptr;
+  const bool with_sky = sky_h.q != 0;                  // (the sky calls set q to a non-zero value before the order is checked)
   DV_TRY(fitflux_check(who, cs, nb, F, p));
-  if (N < 0 || M < 0 || !field_ptr || (N > 0 && (!stamps_h || !places_h || !data_h))) {
+  if (with_sky) DV_TRY(fitflux_sky_check(who, sky_order, sky_h, out_h, weighted));
+  const int q = with_sky ? fitflux_sky_q(sky_order) : 0;
+  if (N < 0 || M < 0 || !field_ptr || ((N > 0 || (q && M > 0)) && !data_h) || (N > 0 && (!stamps_h || !places_h))) {
     set_error("%s: stamps, places, field_ptr and data_fields must all be given", who);
     return E_INVALID;
   }
   DV_TRY(fitflux_rows_check(who, out_h, N, weighted));
   DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));   // (the chunks build their own tables)
   FitFluxPlan plan;
-  DV_TRY(fitflux_plan(who, field_ptr, M, nb, p, &plan));
-  if (N == 0) return OK;
+  DV_TRY(fitflux_plan(who, field_ptr, M, nb, p, &plan, with_sky ? sky_order : -1, F));
+  if (N == 0 && !(q && M > 0)) return OK;
   FitFluxRows d{};
   Rows out;
   fitflux_columns(out, d, out_h, nb, weighted);
   const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
   const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + out.bytes();
-  const size_t per_field = (weighted ? 2 : 1) * felems * sizeof(double) + sizeof(int) + sizeof(long long);
+  const size_t sky_out = q ? (size_t)nb * ((size_t)q * (q + 1) * sizeof(double) + q * sizeof(int) + sizeof(long long)) : 0;
+  const size_t per_field = (weighted ? 2 : 1) * felems * sizeof(double) + sizeof(int) + sizeof(long long) + sky_out +
+                           (q ? (plan.sky_part + FF_BANDS * fitflux_sky_acc(q)) * sizeof(double) : 0);
   DV_HIP(hipSetDevice(device));
   FitFluxWork work;
   if (budget == 0) {
@@ -667,28 +1047,48 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
   DV_TRY(data.alloc(cmax_f * felems));
   if (weighted) DV_TRY(wdata.alloc(cmax_f * felems));
   DV_TRY(out.alloc((int64_t)cmax_s));
+  DevBuf<double> sky_coef, sky_cov;
+  DevBuf<int> sky_status;
+  DevBuf<long long> sky_npix;
+  FitFluxSky sky_d{};
+  if (q) {
+    DV_TRY(sky_coef.alloc(cmax_f * nb * q));
+    DV_TRY(sky_cov.alloc(cmax_f * nb * q * q));
+    DV_TRY(sky_status.alloc(cmax_f * nb * q));
+    DV_TRY(sky_npix.alloc(cmax_f * nb));
+    sky_d = FitFluxSky{q, sky_coef.get(), sky_cov.get(), sky_status.get(), sky_npix.get()};
+  }
   std::vector<int> sf_h, fptr_h;
   StreamDrain drain(s);
   for (size_t k = 0; k + 1 < cuts.size(); ++k) {
     const int fa = cuts[k], fz = cuts[k + 1];          // fields fa .. fz - 1, their rows counted from the chunk's first
     const int64_t r0 = field_ptr[fa], n = field_ptr[fz] - r0;
-    if (n == 0) continue;
+    if (n == 0 && !q) continue;
     fptr_h.assign((size_t)(fz - fa) + 1, 0);
     sf_h.assign((size_t)n, 0);
     for (int f = fa; f < fz; ++f) {
       fptr_h[(size_t)(f - fa) + 1] = (int)(field_ptr[f + 1] - r0);
       for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) sf_h[(size_t)(i - r0)] = f - fa;
     }
-    DV_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)r0 * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(places, places_h + (size_t)r0 * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if (n > 0) {
+      DV_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)r0 * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
+      DV_HIP(hipMemcpyAsync(places, places_h + (size_t)r0 * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+      DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    }
     DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), fptr_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
     DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
     if (weighted)
       DV_HIP(hipMemcpyAsync(wdata, weight_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h + (size_t)r0 * 2, fptr_h.data(), 0, fz - fa - 1, cs, nb, F,
-                           p, work, d, s, true, weighted ? wdata.get() : nullptr));
-    DV_TRY(out.download(r0, n, s));
+    DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h ? places_h + (size_t)r0 * 2 : nullptr, fptr_h.data(), 0,
+                           fz - fa - 1, cs, nb, F, p, work, d, s, true, weighted ? wdata.get() : nullptr, sky_d));
+    if (n > 0) DV_TRY(out.download(r0, n, s));
+    if (q) {                                           // the per-field outputs, with the rows
+      const size_t nf = (size_t)(fz - fa), o = (size_t)fa * nb;
+      DV_HIP(hipMemcpyAsync(sky_h.coef + o * q, sky_coef, nf * nb * q * sizeof(double), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(sky_h.cov + o * q * q, sky_cov, nf * nb * q * q * sizeof(double), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(sky_h.status + o * q, sky_status, nf * nb * q * sizeof(int), hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(sky_h.npix + o, sky_npix, nf * nb * sizeof(long long), hipMemcpyDeviceToHost, s));
+    }
     DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next chunk
   }
   drain.dismiss();
@@ -742,6 +1142,74 @@ int scene_fit_flux_gram(const float* stamps_h, const int32_t* places_h, int64_t 
   DV_HIP(hipMemcpyAsync(proj_h, proj, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
   DV_HIP(hipStreamSynchronize(s));
   drain.dismiss();
+  return OK;
+}
+
+// step 1 of the bordered system of one field (7t): host arrays in; G, E and K [nb][n + q][n + q] (the lower triangle, zeros
+// above) and the right-hand side h, c [n + q][nb] out - the bits the solve of dv_scene_fit_flux_sky starts from
+int scene_fit_flux_sky_gram(const float* stamps_h, const int32_t* places_h, int64_t n, int cs, int nb, const double* data_h,
+                            const double* weight_h, int F, int sky_order, double* gram_h, double* rhs_h, int device, hipStream_t s) {
+  const char* who = "dv_scene_fit_flux_sky_gram";
+  if (sky_order != 0 && sky_order != 1) {
+    set_error("%s: sky_order must be 0 (a constant) or 1 (a plane), got %d", who, sky_order);
+    return E_INVALID;
+  }
+  if (n > FF_MAX_N) {
+    set_error("%s: field 0 has %ld galaxies, the dense fit takes at most %d per field", who, (long)n, FF_MAX_N);
+    return E_INVALID;
+  }
+  const int q = fitflux_sky_q(sky_order);
+  const size_t nt = (size_t)std::max<int64_t>(n, 0) + q;
+  const size_t need = (size_t)nb * nt * nt * sizeof(double);
+  const FitFluxParams p{0.5, (int64_t)need};
+  DV_TRY(fitflux_check(who, cs, nb, F, p));
+  if (n < 0 || !data_h || !gram_h || !rhs_h || (n > 0 && (!stamps_h || !places_h))) {
+    set_error("%s: stamps, places, data_field, gram and rhs must all be given", who);
+    return E_INVALID;
+  }
+  for (int64_t i = 0; i < n; ++i) DV_TRY(place_check(who, i, places_h));
+  const int64_t field_ptr[2] = {0, n};
+  FitFluxPlan plan;
+  DV_TRY(fitflux_plan(who, field_ptr, 1, nb, p, &plan, sky_order, F));
+  const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb, acc = fitflux_sky_acc(q);
+  DV_HIP(hipSetDevice(device));
+  DevBuf<float> stamps;
+  DevBuf<double> data, wdata, gram, proj, coef, cov;
+  DevBuf<int> places, sf, fptr, status;
+  DevBuf<long long> npix;
+  FitFluxWork work;
+  DV_TRY(work.alloc(plan, 1));
+  DV_TRY(stamps.alloc((size_t)n * stamp));
+  DV_TRY(places.alloc((size_t)n * 2));
+  DV_TRY(sf.alloc((size_t)n));
+  DV_TRY(fptr.alloc(2));
+  DV_TRY(data.alloc(felems));
+  if (weight_h) DV_TRY(wdata.alloc(felems));
+  DV_TRY(gram.alloc((size_t)n * nb));
+  DV_TRY(proj.alloc((size_t)n * nb));
+  DV_TRY(npix.alloc((size_t)nb));
+  const int fptr_h[2] = {0, (int)n};
+  StreamDrain drain(s);
+  if (n > 0) {
+    DV_HIP(hipMemcpyAsync(stamps, stamps_h, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(places, places_h, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemsetAsync(sf, 0, (size_t)n * sizeof(int), s));
+  }
+  DV_HIP(hipMemcpyAsync(fptr, fptr_h, sizeof(fptr_h), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(data, data_h, felems * sizeof(double), hipMemcpyHostToDevice, s));
+  if (weight_h) DV_HIP(hipMemcpyAsync(wdata, weight_h, felems * sizeof(double), hipMemcpyHostToDevice, s));
+  const FitFluxRows rows{nullptr, nullptr, gram.get(), proj.get(), nullptr};
+  const FitFluxSky sky{q, nullptr, nullptr, nullptr, npix.get()};
+  DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h, fptr_h, 0, 0, cs, nb, F, p, work, rows, s, false,
+                         weight_h ? wdata.get() : nullptr, sky));
+  std::vector<double> sums((size_t)nb * acc);
+  DV_HIP(hipMemcpyAsync(gram_h, work.scratch, need, hipMemcpyDeviceToHost, s));
+  if (n > 0) DV_HIP(hipMemcpyAsync(rhs_h, proj, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(sums.data(), work.sky_sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipStreamSynchronize(s));
+  drain.dismiss();
+  for (int b = 0; b < nb; ++b)
+    for (int t = 0; t < q; ++t) rhs_h[((size_t)n + t) * nb + b] = sums[(size_t)b * acc + (size_t)q * (q + 1) / 2 + t];
   return OK;
 }
 

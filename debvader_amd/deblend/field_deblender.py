@@ -45,7 +45,7 @@ def _to_records(cols):
 class _Extra(NamedTuple):
     """One optional part of the on-device catalogue of DeblendFieldBatch.deblend_fields: a keyword, the engine call that
     serves it and what it appends to the recarrays.  `c` below is the namespace of one call: bands, band, sky_sigma,
-    field_ptr, psf, psf_index, aper_par, nmc, fit_weights, core."""
+    field_ptr, psf, psf_index, aper_par, nmc, fit_weights, fit_sky, places, cs, F, core."""
     key: str                        # the keyword of deblend_fields
     given: Callable                 # its value -> whether the extra is asked for
     label: str                      # how a message names it
@@ -138,6 +138,17 @@ _EXTRAS = (
            lambda c: dict(band=c.band, weight_fields=c.fit_weights),
            lambda c: ms.fit_flux_weighted_dtype(c.bands)[len(ms.fit_flux_dtype(c.bands)):],
            lambda out, c: _fit_weight_records(out, c),
+           refines="fit_flux"),
+    # (behind fit_weights, which refines the same extra: the call of the LAST refining extra given serves the others too - this
+    # one passes the weights on)
+    _Extra("fit_sky", lambda v: v is not None, "fit_sky", "needs", "the flux fit with a sky background",
+           "fit_sky needs fit_flux=True: it is the order (0: a constant, 1: a plane) of the sky background the flux fit fits "
+           "jointly with the amplitudes",
+           "dv_infer_fields_measure_fit_sky", "infer_fields_measure_fit_sky", True,
+           lambda c: dict(band=c.band, sky_order=c.fit_sky, weight_fields=c.fit_weights),
+           lambda c: ms.fit_sky_dtype(c.bands),
+           lambda out, c: ms.fit_sky_records(out["sky_coef"], out["sky_cov"], out["sky_status"], c.places, c.cs, c.F,
+                                             field_ptr=c.field_ptr, sky_sigma=c.sky_sigma, weighted=c.fit_weights is not None),
            refines="fit_flux"),
 )
 
@@ -594,6 +605,12 @@ class DeblendFieldBatch:
         return ms.fit_flux_dtype(nb_of_bands)
 
     @staticmethod
+    def fit_sky_columns(nb_of_bands):
+        """What deblend_fields(measure=True, fit_flux=True, fit_sky=0 or 1) appends behind the columns of the flux fit
+        (fit_flux_columns, or fit_flux_weighted_columns with fit_weights): fit_sky and fit_sky_err."""
+        return ms.fit_sky_dtype(nb_of_bands)
+
+    @staticmethod
     def fit_flux_weighted_columns(nb_of_bands):
         """What deblend_fields(measure=True, fit_flux=True, fit_weights=W) appends behind measure_columns: the recarray of
         fit_fluxes_weighted - fit_flux_columns, then fit_chi2 and fit_npix."""
@@ -651,6 +668,9 @@ class DeblendFieldBatch:
         self._epistemic_pass = None     # the res_deblend list of the last pass, if it estimated the epistemic uncertainty
         self.position_fit = None        # per field {objective, iters, status} of the last on-device pass that fitted positions
         self.psf_moments = None         # {psf_shape, psf_aux, psf_iters, psf_status} of the last pass that took a psf
+        self.sky_fit = None             # {sky_coef (M, bands, q), sky_cov (M, bands, q, q), sky_status (M, bands, q), sky_npix
+                                        # (M, bands)} of the last pass that fitted a sky (fit_sky): the per-field arrays of
+                                        # Context.scene_fit_flux_sky, fields without galaxies included
 
     @property
     def _ctx(self):
@@ -675,7 +695,7 @@ class DeblendFieldBatch:
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
                        measure=False, return_fields=True, measure_samples=0, blendedness=False,
                        psf=None, psf_index=None, apertures=None, flux_fractions=None, aperture_data=False,
-                       sky_sigma=None, fit_flux=False, fit_weights=None, optimise_positions=False):
+                       sky_sigma=None, fit_flux=False, fit_weights=None, fit_sky=None, optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -773,19 +793,33 @@ class DeblendFieldBatch:
         fit_flux, with fit_scale_err = sqrt(fit_var) and flux_fit_err derived from the weights, then fit_chi2, the chi-square
         of the refitted scene under the galaxy's own counting pixels, and fit_npix, their number
         (debvader_amd.measure.measurement.fit_fluxes_weighted describes them).  sky_sigma beside fit_weights is
-        refused: the weights already carry the noise.  It changes no other refusal of fit_flux."""
+        refused: the weights already carry the noise.  It changes no other refusal of fit_flux.
+
+        fit_sky=0 or 1 (with fit_flux=True, with or without fit_weights and return_fields): a sky background per field and
+        band is fitted jointly with the amplitudes (dv_infer_fields_measure_fit_sky) - 0: a constant,
+        1: a plane - to all pixels of the field (with fit_weights: the counting ones).  A sky residual under a blend then no
+        longer goes into the amplitudes.  Beside fit_weights the fit runs with the weights.  The recarrays gain, behind the
+        columns of fit_flux (and fit_chi2, fit_npix if weighted), fit_sky_columns: fit_sky, the fitted background at the
+        centre pixel of the galaxy's stamp, and fit_sky_err (times sky_sigma unweighted, NaN without it;
+        debvader_amd.measure.measurement.fit_fluxes_sky describes them).  fit_var and the errors derived from it now carry the
+        covariance with the sky.  self.sky_fit holds the per-field arrays sky_coef, sky_cov, sky_status and sky_npix of the
+        pass, fields without galaxies included.  Unweighted, a non-finite pixel anywhere in a field reaches every galaxy of
+        that field through the sky: mask it with fit_weights.  It changes no other refusal of fit_flux."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
         aperture_data, fit_flux = bool(aperture_data), bool(fit_flux)
         band = 2                        # the band of the measurement (r): the engine call and the blendedness in the apertures
         kw = dict(measure_samples=measure_samples, blendedness=blendedness, psf=psf, psf_index=psf_index, apertures=apertures,
-                  flux_fractions=flux_fractions, aperture_data=aperture_data, fit_flux=fit_flux, fit_weights=fit_weights)
+                  flux_fractions=flux_fractions, aperture_data=aperture_data, fit_flux=fit_flux, fit_weights=fit_weights,
+                  fit_sky=fit_sky)
         given = [x.key for x in _EXTRAS if x.given(kw[x.key])]
         for x in _EXTRAS[1:]:           # (measure_samples, the oldest, is refused below its own integer check)
             _refuse_extra(x, kw, given, measure, on_device, fit, mc)
         if sky_sigma is not None and not aperture_data and not fit_flux:
             raise ValueError("sky_sigma is the sky noise of the data-flux errors of aperture_data=True: give aperture_data too")
+        if fit_sky is not None:
+            E.sky_terms(fit_sky)                                                                            # (ValueError)
         if fit_weights is not None:
             if sky_sigma is not None:
                 raise ValueError(ms.WEIGHTS_CARRY_THE_NOISE)
@@ -836,12 +870,14 @@ class DeblendFieldBatch:
         self._epistemic_pass = None
         self.position_fit = None
         self.psf_moments = None
+        self.sky_fit = None
         N = len(starts)
         if psf is not None:
             psf, psf_index = self._psf_index(psf, psf_index, field_ptr)
         extras = [x for x in _EXTRAS if x.key in given]
         c = SimpleNamespace(bands=nb, band=band, sky_sigma=sky_sigma, field_ptr=field_ptr, psf=psf, psf_index=psf_index,
-                            aper_par=aper_par, nmc=int(measure_samples), fit_weights=fit_weights, core=core)
+                            aper_par=aper_par, nmc=int(measure_samples), fit_weights=fit_weights, fit_sky=fit_sky,
+                            places=(int((F - cs) / 2) + dd).astype(np.int64), cs=cs, F=F, core=core)
         eng.set_normalise(bool(self.normalise))
         try:
             seed = core.next_seed()
@@ -900,6 +936,8 @@ class DeblendFieldBatch:
                 cats.append(x.records(out, c))
             if psf is not None:
                 self.psf_moments = {k: out[k] for k in ("psf_shape", "psf_aux", "psf_iters", "psf_status")}
+            if fit_sky is not None:
+                self.sky_fit = {k: out[k] for k in E.FIT_SKY_KEYS}
             # a stamp's pixel (row, col) is the field's pixel start + (row, col); distances count from pixel int(F / 2)
             measured = starts + np.stack([cat["row"], cat["col"]], axis=1) - int(F / 2) if N else np.zeros((0, 2))
         res = []

@@ -299,6 +299,24 @@ def _fit_flux_out(n, nb, weighted=False):
     return out, ptrs
 
 
+FIT_SKY_KEYS = ("sky_coef", "sky_cov", "sky_status", "sky_npix")       # per field: the sky fitted jointly
+
+
+def sky_terms(sky_order) -> int:
+    """The sky terms per field and band of a flux fit with sky: order 0, a constant, 1; order 1, a plane, 3"""
+    if isinstance(sky_order, bool) or sky_order not in (0, 1):
+        raise ValueError(f"sky_order must be 0 (a constant) or 1 (a plane), got {sky_order!r}")
+    return 1 if sky_order == 0 else 3
+
+
+def _fit_sky_out(M, nb, q):
+    """The per-field arrays of a flux fit with sky and their pointers in the C-ABI's order"""
+    out = dict(sky_coef=np.zeros((M, nb, q), np.float64), sky_cov=np.zeros((M, nb, q, q), np.float64),
+               sky_status=np.zeros((M, nb, q), np.int32), sky_npix=np.zeros((M, nb), np.int64))
+    return out, [_dp(out["sky_coef"]), _dp(out["sky_cov"]), _ip(out["sky_status"]),
+                 out["sky_npix"].ctypes.data_as(C.POINTER(C.c_int64))]
+
+
 def check_fit_weights(weight_fields, shape):
     """The C-contiguous float64 weight fields of a weighted flux fit: they have the shape of the data fields (M, F, F, bands);
     a 3-d array is taken as one field.  The values are not looked at - the kernel's comparison 0 < W < inf is the rule."""
@@ -929,6 +947,74 @@ class Context:
         if n:
             check(lib.dv_scene_fit_flux_gram(self._h, _fp(stamps), _ip(places), n, cs, nb, _dp(data), data.shape[0],
                                              _dp(out["gram"]), _dp(out["proj"])))
+        return out
+
+    def scene_fit_flux_sky(self, stamps, places, data_fields, field_ptr=None, sky_order: int = 0, weight_fields=None,
+                           min_pivot: float = 1e-8, scratch_bytes: int = 256 << 20) -> Dict[str, np.ndarray]:
+        """scene_fit_flux with a sky background fitted jointly (dv_scene_fit_flux_sky): per field and
+        band q more unknowns beside the amplitudes - sky_order 0: a constant (q = 1); 1: a plane (q = 3) in the basis B_0 = 1,
+        B_1 = (2 r - F + 1) / F, B_2 = (2 c - F + 1) / F of the field pixel (r, c) - fitted to ALL pixels of the field (with
+        weight_fields: the counting ones).  The arguments are scene_fit_flux's.  Returns its dictionary ("fit_chi2" and
+        "fit_npix" with weight_fields only; fit_var now carries the covariance with the sky; fit_status, fit_gram and fit_proj
+        have the bits of the fit without sky) plus, per field: {"sky_coef" (M, bands, q); "sky_cov" (M, bands, q, q): the
+        lower-right block of the inverse of the bordered matrix, NaN in the rows and columns of terms that are not kept;
+        "sky_status" (M, bands, q) int32: 0 fitted, FIT_INELIGIBLE the field has no counting pixel (coefficient NaN),
+        FIT_DROPPED the term cannot be told from the unknowns before it and is exactly 0.0; "sky_npix" (M, bands) int64: the
+        counting pixels of the field}.  A field without galaxies is still solved.  Unweighted, a non-finite pixel of a data
+        field anywhere reaches every galaxy of that field through the sky: mask it with weight_fields.  The scratch of a
+        field is bands x (n + q) x (n + q) doubles."""
+        stamps = np.ascontiguousarray(stamps, dtype=np.float32)
+        if stamps.ndim != 4 or stamps.shape[1] != stamps.shape[2]:
+            raise ValueError(f"expected square stamps (N, cs, cs, bands), got {stamps.shape}")
+        n, cs, nb = stamps.shape[0], stamps.shape[1], stamps.shape[3]
+        data = np.ascontiguousarray(data_fields, dtype=np.float64)
+        if data.ndim != 4 or data.shape[1] != data.shape[2] or data.shape[3] != nb:
+            raise ValueError(f"expected data fields (M, F, F, {nb}), got {data.shape}")
+        places = _i32_rows(places, "stamp placements") if n else np.zeros((0, 2), np.int32)
+        if places.shape != (n, 2):
+            raise ValueError(f"expected places ({n}, 2), got {places.shape}")
+        M = data.shape[0]
+        if field_ptr is None:
+            if M != 1:
+                raise ValueError(f"field_ptr is needed with {M} fields")
+            field_ptr = [0, n]
+        fp = check_field_ptr(field_ptr, M, n)
+        q = sky_terms(sky_order)
+        par = fit_flux_params(min_pivot, scratch_bytes)
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, data.shape)
+        out, ptrs = _fit_flux_out(n, nb, weights is not None)
+        if weights is None:
+            ptrs += [None, None]
+        sky, sky_ptrs = _fit_sky_out(M, nb, q)
+        out.update(sky)
+        if M:
+            check(lib.dv_scene_fit_flux_sky(self._h, _fp(stamps), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs, nb,
+                                            _dp(data), None if weights is None else _dp(weights), M, data.shape[1], C.byref(par),
+                                            int(sky_order), *ptrs, *sky_ptrs))
+        return out
+
+    def scene_fit_flux_sky_gram(self, stamps, places, data_field, sky_order: int = 0, weight_field=None) -> Dict[str, np.ndarray]:
+        """Step 1 of scene_fit_flux_sky for one field (dv_scene_fit_flux_sky_gram): returns {"gram" (bands, n + q, n + q): the
+        lower triangle of the bordered matrix [[G, E], [E^T, K]], 0.0 above the diagonal; "rhs" (n + q, bands): h, then c}
+        with the bits the fit works on.  The arguments are scene_fit_flux_gram's; weight_field (F, F, bands) or None."""
+        stamps = np.ascontiguousarray(stamps, dtype=np.float32)
+        if stamps.ndim != 4 or stamps.shape[1] != stamps.shape[2]:
+            raise ValueError(f"expected square stamps (n, cs, cs, bands), got {stamps.shape}")
+        n, cs, nb = stamps.shape[0], stamps.shape[1], stamps.shape[3]
+        data = np.ascontiguousarray(data_field, dtype=np.float64)
+        if data.ndim != 3 or data.shape[0] != data.shape[1] or data.shape[2] != nb:
+            raise ValueError(f"expected one data field (F, F, {nb}), got {data.shape}")
+        places = _i32_rows(places, "stamp placements") if n else np.zeros((0, 2), np.int32)
+        if places.shape != (n, 2):
+            raise ValueError(f"expected places ({n}, 2), got {places.shape}")
+        if n > FIT_FLUX_MAX_N:
+            raise ValueError(f"{n} galaxies in one field, the dense flux fit takes at most {FIT_FLUX_MAX_N}")
+        nt = n + sky_terms(sky_order)
+        weights = None if weight_field is None else check_fit_weights(weight_field, (1,) + data.shape)
+        out = dict(gram=np.zeros((nb, nt, nt), np.float64), rhs=np.zeros((nt, nb), np.float64))
+        check(lib.dv_scene_fit_flux_sky_gram(self._h, _fp(stamps), _ip(places), n, cs, nb, _dp(data),
+                                             None if weights is None else _dp(weights), data.shape[0], int(sky_order),
+                                             _dp(out["gram"]), _dp(out["rhs"])))
         return out
 
     CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
@@ -1569,6 +1655,44 @@ class Engine:
     def scene_fit_flux(self, stamps, places, data_fields, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_fit_flux on this engine's GPU context."""
         return self.ctx.scene_fit_flux(stamps, places, data_fields, **kw)
+
+    def infer_fields_measure_fit_sky(self, fields, starts, field_ptr, places, sky_order: int = 0, weight_fields=None, seed=0,
+                                     band: int = 2, sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200,
+                                     min_pivot: float = 1e-8, scratch_bytes: int = 256 << 20, return_fields=True, residual=True,
+                                     mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_fit[_weighted]() with a sky background fitted jointly (dv_infer_fields_measure_fit_sky,
+        DESIGN.md section 7t): sky_order 0 a constant, 1 a plane per field and band; weight_fields None is the unweighted
+        fit.  Returns infer_fields_measure's dictionary, bit for bit, plus scene_fit_flux_sky's - the galaxy rows ("fit_chi2"
+        and "fit_npix" with weight_fields only) and the per-field "sky_coef", "sky_cov", "sky_status", "sky_npix" - with the
+        bits of that call on infer_fields_keep's mean stamps.  Fields without galaxies are solved too."""
+        places = Engine._measure_places(places, return_fields, "places are needed for the flux fit, with return_fields=False too")
+        fields = _check_fields(fields)
+        q = sky_terms(sky_order)
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, fields.shape)
+
+        def extras(N, nb):
+            fpar = fit_flux_params(min_pivot, scratch_bytes)
+            ff, ff_ptrs = _fit_flux_out(N, nb, weights is not None)
+            if weights is None:
+                ff_ptrs += [None, None]
+            sky, sky_ptrs = _fit_sky_out(fields.shape[0], nb, q)
+            ff.update(sky)
+            return [(ff, [C.byref(fpar), None if weights is None else _dp(weights), int(sky_order)] + ff_ptrs + sky_ptrs)]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_fit_sky, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
+
+    def infer_cutouts_measure_fit_sky(self, field, starts, places, sky_order: int = 0, weight_field=None, seed=0,
+                                      **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_fit_sky() for one field (and its weight field) (F, F, bands): the field-sized results under
+        singular key names; the sky arrays keep their leading axis of one field."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_fit_sky(fields, starts, fp, places, sky_order, weight_field, seed=seed,
+                                                                  **kw))
+
+    def scene_fit_flux_sky(self, stamps, places, data_fields, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_fit_flux_sky on this engine's GPU context."""
+        return self.ctx.scene_fit_flux_sky(stamps, places, data_fields, **kw)
 
     def infer_fields_measure_mc(self, fields, starts, field_ptr, places=None, seed=0, mc_seed=0, nsamples=100, band: int = 2,
                                 sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, return_fields=True,

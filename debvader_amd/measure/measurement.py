@@ -641,6 +641,125 @@ def _fit_fluxes(stamps_mean, places, data_fields, weight_fields, field_ptr, cata
                             sky_sigma=sky_sigma, field_ptr=field_ptr)
 
 
+def _join_records(*recs):
+    """One recarray with the columns of several of the same length, in their order"""
+    out = np.recarray((len(recs[0]),), dtype=[d for r in recs for d in r.dtype.descr])
+    for r in recs:
+        for k in r.dtype.names:
+            out[k] = r[k]
+    return out
+
+
+def fit_sky_dtype(nb_of_bands):
+    """The two columns a flux fit with sky adds per galaxy: the fitted background under the galaxy and
+    its error."""
+    nb = int(nb_of_bands)
+    return [("fit_sky", "<f8", (nb,)), ("fit_sky_err", "<f8", (nb,))]
+
+
+def fit_sky_records(sky_coef, sky_cov, sky_status, places, cutout_size, field_size, field_ptr=None, sky_sigma=None,
+                    weighted=False):
+    """The recarray of fit_sky_dtype from the per-field arrays of scene_fit_flux_sky - sky_coef (M, bands, q), sky_cov (M,
+    bands, q, q), sky_status (M, bands, q) - and the placements (N, 2) of the galaxies (field_ptr (M + 1,) gives every galaxy's
+    field; None: one field).  fit_sky is the fitted background sum_t s_t B_t at the stamp's centre pixel (pr + cs // 2, pc +
+    cs // 2) of its field, in the basis B_0 = 1, B_1 = (2 r - F + 1) / F, B_2 = (2 c - F + 1) / F; fit_sky_err = sqrt(b^T
+    sky_cov b) with b that basis over the fitted terms.  A term with sky_status 5 (dropped) has coefficient exactly 0.0 and no
+    variance: it adds nothing to either.  A term with sky_status 4 (a field without a counting pixel) makes both NaN.
+    Unweighted, sky_cov is in units of the pixel variance: fit_sky_err is multiplied by sky_sigma ((bands,) or (M, bands)), and
+    is NaN without it; weighted=True (the weights carry the noise) takes it as it is, and sky_sigma beside it is a
+    ValueError."""
+    if weighted and sky_sigma is not None:
+        raise ValueError(WEIGHTS_CARRY_THE_NOISE)
+    coef = np.asarray(sky_coef, dtype=np.float64)
+    if coef.ndim != 3 or coef.shape[2] not in (1, 3):
+        raise ValueError(f"expected sky_coef (M, bands, 1 or 3), got {coef.shape}")
+    M, nb, q = coef.shape
+    cov = np.asarray(sky_cov, dtype=np.float64).reshape(M, nb, q, q)
+    status = np.asarray(sky_status, dtype=np.int32).reshape(M, nb, q)
+    places = np.asarray(places, dtype=np.int64).reshape(-1, 2)
+    n = places.shape[0]
+    if field_ptr is None:
+        field_ptr = [0, n]
+    fp = np.asarray(field_ptr, dtype=np.int64).reshape(-1)
+    if fp.shape[0] != M + 1 or fp[0] != 0 or fp[-1] != n or (np.diff(fp) < 0).any():
+        raise ValueError(f"field_ptr must have {M + 1} entries, start at 0, never decrease and end at the number of galaxies ({n})")
+    sigma = None if sky_sigma is None else check_sky_sigma(sky_sigma, M, nb)
+    cs, F = int(cutout_size), int(field_size)
+    field = np.repeat(np.arange(M), np.diff(fp))                                  # (N,)
+    b = np.ones((n, q))
+    if q == 3:
+        b[:, 1] = (2 * (places[:, 0] + cs // 2) - F + 1).astype(np.float64) / np.float64(F)
+        b[:, 2] = (2 * (places[:, 1] + cs // 2) - F + 1).astype(np.float64) / np.float64(F)
+    rec = np.recarray((n,), dtype=fit_sky_dtype(nb))
+    with np.errstate(all="ignore"):
+        rec["fit_sky"] = np.einsum("nbt,nt->nb", coef[field], b)
+        kept = status[field] == 0                                                 # (N, bands, q)
+        bk = np.where(kept, b[:, None, :], 0.0)
+        var = np.einsum("nbt,nbtu,nbu->nb", bk, np.where(kept[..., :, None] & kept[..., None, :], cov[field], 0.0), bk)
+        err = np.where((status[field] == FIT_STATUS_INELIGIBLE).any(axis=2) | ~kept.any(axis=2), np.nan, np.sqrt(var))
+        if weighted:
+            rec["fit_sky_err"] = err
+        elif sigma is None:
+            rec["fit_sky_err"] = np.nan
+        else:
+            rec["fit_sky_err"] = sigma[field] * err
+    return rec
+
+
+def fit_fluxes_sky(stamps_mean, places, data_fields, sky_order=0, weight_fields=None, field_ptr=None, catalogue=None,
+                   sky_sigma=None, min_pivot=1e-8, ctx=None):
+    """fit_fluxes (weight_fields None) or fit_fluxes_weighted with a local sky background fitted jointly with the amplitudes
+    (DESIGN.md section 7t), as the SDSS deblender, the Tractor and scarlet do: a sky residual under a blend no longer goes into
+    the amplitudes of the models with the widest wings.
+
+    parameters: those of fit_fluxes / fit_fluxes_weighted, and
+        sky_order: 0, a constant per field and band; 1, a plane s_0 + s_1 B_1 + s_2 B_2 with B_1 = (2 r - F + 1) / F and B_2 =
+            (2 c - F + 1) / F of the field pixel (r, c).  The sky is fitted to ALL pixels of the field (weighted: the counting
+            ones), not only to those under a stamp
+    returns (catalogue, sky): the np.recarray of fit_fluxes (with weight_fields: of fit_fluxes_weighted) plus fit_sky_dtype -
+    fit_sky, the fitted background at the centre pixel of the galaxy's stamp, and fit_sky_err (fit_sky_records) - and the
+    dictionary of the per-field arrays sky_coef (M, bands, q), sky_cov (M, bands, q, q), sky_status (M, bands, q) and sky_npix
+    (M, bands) of Context.scene_fit_flux_sky.  fit_var, and with it fit_scale_err, now carries the covariance with the sky;
+    fit_status, fit_gram and fit_proj are those of the fit without sky.  A field without galaxies still gets its sky.
+    Unweighted, a non-finite pixel of data_fields ANYWHERE in a field reaches every galaxy of that field through the sky
+    sums (without sky it reached only the galaxies whose stamps cover it): mask such pixels with weight_fields.
+    """
+    q = E.sky_terms(sky_order)                                            # (ValueError before any GPU work)
+    data = np.asarray(data_fields, dtype=np.float64)
+    if data.ndim == 3:
+        data = data[None]
+    M = data.shape[0]
+    weighted = weight_fields is not None
+    if weighted:
+        if sky_sigma is not None:
+            raise ValueError(WEIGHTS_CARRY_THE_NOISE)
+        weight_fields = E.check_fit_weights(weight_fields, data.shape)
+    if data.ndim == 4 and sky_sigma is not None:
+        check_sky_sigma(sky_sigma, M, data.shape[-1])
+    stamps = np.asarray(stamps_mean, dtype=np.float32)
+    if field_ptr is None and M == 1:
+        field_ptr = [0, stamps.shape[0]]
+    if catalogue is None:
+        flux = stamps.sum(axis=(1, 2), dtype=np.float64) if stamps.ndim == 4 else None
+    else:
+        if "flux" not in catalogue.dtype.names:
+            raise ValueError("the catalogue lacks the column flux: fit_fluxes_sky takes the measure_stamps recarray of the galaxies")
+        flux = np.asarray(catalogue["flux"], dtype=np.float64)
+    if ctx is None:
+        ctx = E.default_context()
+    out = ctx.scene_fit_flux_sky(stamps, places, data, field_ptr=field_ptr, sky_order=sky_order, weight_fields=weight_fields,
+                                 min_pivot=min_pivot)
+    if weighted:
+        fit = fit_flux_records(*(out[k] for k in E.FIT_FLUX_KEYS), flux, field_ptr=field_ptr, fit_chi2=out["fit_chi2"],
+                               fit_npix=out["fit_npix"])
+    else:
+        fit = fit_flux_records(*(out[k] for k in E.FIT_FLUX_KEYS), flux, sky_sigma=sky_sigma, field_ptr=field_ptr)
+    sky = fit_sky_records(out["sky_coef"], out["sky_cov"], out["sky_status"], places, stamps.shape[1], data.shape[1],
+                          field_ptr=field_ptr, sky_sigma=sky_sigma, weighted=weighted)
+    assert out["sky_coef"].shape[2] == q
+    return _join_records(fit, sky), {k: out[k] for k in E.FIT_SKY_KEYS}
+
+
 def measure_blendedness(stamps_mean, catalogue, places, model_fields, data_fields=None, field_ptr=None, band=2, ctx=None):
     """Blendedness of N deblended galaxies on the GPU.
 

@@ -731,6 +731,45 @@ int dv_infer_fields_measure_fit_weighted(dv_model* m, const double* fields, int3
                                          const dv_fit_flux_params* fit, const double* weight_fields, double* fit_scale,
                                          double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status,
                                          double* fit_chi2, int32_t* fit_npix);
+/* The same fit with a sky background fitted jointly: q terms per field and band beside the amplitudes,
+ * sky_order 0: q = 1, a constant; sky_order 1: q = 3, a plane.  Per field of side F and pixel (r, c): B_0 = 1, B_1 = (double)
+ * (2 r - F + 1) / (double)F, B_2 = (double)(2 c - F + 1) / (double)F; the model is D(p) = sum_i a_i P_i(p) + sum_t s_t B_t(p)
+ * over ALL pixels of the field - with weight_fields the counting ones, masked terms selected to +0.0 as above; weight_fields
+ * may be NULL, the unweighted fit.  Beside G and h of step 1: E_it = sum over the pixels of i of (W P_i) B_t, and per field
+ * K_tu = sum (W B_t) B_u (u <= t), c_t = sum (W B_t) D and sky_npix, the counting pixels of the field (F F unweighted), summed
+ * in a fixed tiling that depends on F alone.  The unknowns are the eligible galaxies in object order, then the sky terms: [[G,
+ * E], [E^T, K]] [a; s] = [h; c], steps 2 - 5 as above.  The sky is eliminated last: fit_status, fit_gram and fit_proj of the
+ * galaxies have the bits of the fit without sky.  A sky term whose K_tt is not finite or not positive has sky_status 4 (a
+ * wholly masked field), coefficient and covariance NaN; one whose pivot d <= min_pivot K_tt has sky_status 5: its coefficient
+ * is exactly 0.0, it is never applied to the others and nothing is subtracted from the right-hand side for it.  Dropped
+ * galaxies keep amplitude 1 in the sky rows too: c'_t = c_t - sum_{k dropped} E_kt.  fit_var now carries the covariance with
+ * the sky.  A field without galaxies is still solved: its sky is the (weighted) mean or plane of D.  fit_chi2 (weighted calls
+ * only): M(p) gains sum_t s_t B_t(p) after the neighbours, t ascending, over the terms with sky_status 0.  Unweighted, a
+ * non-finite pixel of D anywhere in the field now reaches every galaxy of the field through the sky; weight_fields mask it.
+ * Outputs: the seven galaxy outputs of the weighted calls - fit_chi2 and fit_npix are NULL exactly when weight_fields is -,
+ * then per field sky_coef [M][nb][q], sky_cov [M][nb][q][q] (the lower-right block of the inverse; NaN in the rows and columns
+ * of terms that are not kept), sky_status [M][nb][q] and sky_npix [M][nb] int64.  A field's outputs have the same bits
+ * wherever it sits in a batch.  The scratch of a field is nb (n + q) (n + q) doubles.  Both calls refuse, before any GPU work
+ * (DV_E_INVALID, the engine stays usable), what the weighted calls refuse, a sky_order outside {0, 1}, a missing sky output
+ * and chi-square outputs that do not match the weights.
+ * dv_scene_fit_flux_sky_gram: step 1 of the bordered system of ONE field - gram [nb][n + q][n + q], the lower triangle of
+ * [[G, E], [E^T, K]] and 0.0 above the diagonal, rhs [n + q][nb] = h, c: the bits the solve starts from. */
+int dv_scene_fit_flux_sky(dv_ctx* ctx, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs,
+                          int32_t nb, const double* data_fields, const double* weight_fields, int32_t M, int32_t F,
+                          const dv_fit_flux_params* params, int32_t sky_order, double* fit_scale, double* fit_var, double* fit_gram,
+                          double* fit_proj, int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, double* sky_coef,
+                          double* sky_cov, int32_t* sky_status, int64_t* sky_npix);
+int dv_scene_fit_flux_sky_gram(dv_ctx* ctx, const float* stamps, const int32_t* places, int64_t n, int32_t cs, int32_t nb,
+                               const double* data_field, const double* weight_field, int32_t F, int32_t sky_order, double* gram,
+                               double* rhs);
+int dv_infer_fields_measure_fit_sky(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                    const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                    const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                    double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                    int32_t* iters, int32_t* status, const dv_fit_flux_params* fit, const double* weight_fields,
+                                    int32_t sky_order, double* fit_scale, double* fit_var, double* fit_gram, double* fit_proj,
+                                    int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, double* sky_coef, double* sky_cov,
+                                    int32_t* sky_status, int64_t* sky_npix);
 
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)

@@ -94,6 +94,19 @@ protocol -
 
 With --profile-one: warm up, one fp32 call (b), exit.
 
+--fit-sky ORDER: what a sky background fitted jointly (ORDER 0: a constant, 1: a plane) adds to the flux
+fit, in the same protocol, four legs alternating -
+
+    (a) catalogue+fit-flux             :  the catalogue-only call with fit_flux=True, to be compared with --fit-weights' leg (a)
+                                          of the commit before: without fit_sky nothing new is allocated or launched
+    (b) catalogue+fit-flux+sky         :  the same with fit_sky=ORDER
+    (c) catalogue+fit-flux+weights     :  leg (b) of --fit-weights, to be compared with it likewise
+    (d) catalogue+fit-flux+weights+sky :  the same with fit_sky=ORDER
+
+    python tools/measure_bench.py --fit-sky 1 [--fields 1024] [--size 259] [--repeat 5]
+
+With --profile-one: warm up, one fp32 call (d), exit.
+
 The cost is reported, not gated.
 """
 import argparse
@@ -246,9 +259,10 @@ def main_fit_flux(a):
     base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
     fields = np.ascontiguousarray(base[np.arange(M) % 16])
     quiet = io.StringIO()
-    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "fit_flux": True, "fit_weights": bool(a.fit_weights)}
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "fit_flux": True, "fit_weights": bool(a.fit_weights),
+              "fit_sky": a.fit_sky}
     weights = None
-    if a.fit_weights:
+    if a.fit_weights or a.fit_sky is not None:
         w16 = rng.uniform(0.25, 4.0, size=base.shape)
         w16[rng.random(base.shape) < 0.1] = 0.0
         weights = np.ascontiguousarray(w16[np.arange(M) % 16])
@@ -268,12 +282,17 @@ def main_fit_flux(a):
             seen[:] = [np.concatenate([r["fit_status"] for r in res]), np.concatenate([r["fit_independence"] for r in res])]
             return sum(len(r) for r in res)
 
-        if a.fit_weights:
+        if a.fit_sky is not None:
+            legs = {"catalogue+fit-flux": with_fit, "catalogue+fit-flux+sky": lambda: with_fit(fit_sky=a.fit_sky),
+                    "catalogue+fit-flux+weights": lambda: with_fit(fit_weights=weights),
+                    "catalogue+fit-flux+weights+sky": lambda: with_fit(fit_weights=weights, fit_sky=a.fit_sky)}
+        elif a.fit_weights:
             legs = {"catalogue+fit-flux": with_fit, "catalogue+fit-flux+weights": lambda: with_fit(fit_weights=weights)}
         else:
             legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False),
                     "catalogue+fit-flux": with_fit}
-        first, last = list(legs)
+        names = list(legs)
+        last = names[-1]
         with redirect_stdout(quiet):
             for fn in legs.values():           # warm-up
                 fn()
@@ -294,13 +313,14 @@ def main_fit_flux(a):
             t = np.array(times[k])
             print(_row(f"{dtype} {k}", t, n, M))
             result[dtype][k.replace("+", "_").replace("-", "_") + "_ms"] = [round(1e3 * x, 2) for x in t]
-        tc, tf = (float(np.median(times[k])) for k in legs)
         spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
         ind = seen[1][np.isfinite(seen[1])]
-        print(f"{dtype} {last} / {first} {tf / tc:.3f}: {1e3 * (tf - tc):+.1f} ms for {n} galaxies, "
-              f"{1e6 * (tf - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times[first]):.3f} and "
-              f"{spread(times[last]):.3f}); fit_status 0 .. 5 over galaxies x bands: {counts}; median "
-              f"fit_independence {float(np.median(ind)) if ind.size else float('nan'):.3f}")
+        for first, second in zip(names[0::2], names[1::2]):       # (every pair: a leg and the leg that adds to it)
+            tc, tf = float(np.median(times[first])), float(np.median(times[second]))
+            print(f"{dtype} {second} / {first} {tf / tc:.3f}: {1e3 * (tf - tc):+.1f} ms for {n} galaxies, "
+                  f"{1e6 * (tf - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times[first]):.3f} and "
+                  f"{spread(times[second]):.3f}); fit_status 0 .. 5 over galaxies x bands: {counts}; median "
+                  f"fit_independence {float(np.median(ind)) if ind.size else float('nan'):.3f}")
         net._core.engine.close()
     print(json.dumps(result))
 
@@ -459,8 +479,9 @@ def main():
     ap.add_argument("--aperture-data", action="store_true")
     ap.add_argument("--fit-flux", action="store_true")
     ap.add_argument("--fit-weights", action="store_true")
+    ap.add_argument("--fit-sky", type=int, choices=(0, 1), default=None, metavar="ORDER")
     a = ap.parse_args()
-    if a.fit_flux or a.fit_weights:
+    if a.fit_flux or a.fit_weights or a.fit_sky is not None:
         return main_fit_flux(a)
     if a.aperture_data:
         return main_apertures(a, data=True)
