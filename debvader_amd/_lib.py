@@ -213,7 +213,12 @@ SIGNATURES = {
     "dv_scene_fit_flux_sky_gram": (C.c_int, [_p, _f, _i32, C.c_int64, C.c_int32, C.c_int32, _d, _d, C.c_int32, C.c_int32, _d, _d]),
     "dv_infer_fields_measure_fit_sky": _measure_sig(C.POINTER(DvFitFluxParams), _d, C.c_int32, _d, _d, _d, _d, _i32, _d, _i32,
                                                     _d, _d, _i32, _i64),
-    "dv_field_set_open": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
+    "dv_scene_fit_flux_nonneg": (C.c_int, [_p, _f, _i32, _i64, C.c_int64, C.c_int32, C.c_int32, _d, _d, C.c_int32, C.c_int32,
+                                           C.POINTER(DvFitFluxParams), C.c_int32, C.c_int32, _d, _d, _d, _d, _i32, _d, _i32,
+                                           _d, _d, _i32, _i64, _d, _i32, _d, _i32, _i32]),
+    "dv_infer_fields_measure_fit_nonneg": _measure_sig(C.POINTER(DvFitFluxParams), _d, C.c_int32, C.c_int32, _d, _d, _d, _d, _i32,
+                                                       _d, _i32, _d, _d, _i32, _i64, _d, _i32, _d, _i32, _i32),
+    "dv_field_set_open":(C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),
     "dv_field_set_pass": (C.c_int, [_p, _i32, _i32, _i64, C.c_int64, C.c_uint64, _d, _d]),

@@ -428,7 +428,15 @@ int scene_fit_flux_gram(const float* stamps_h, const int32_t* places_h, int64_t 
 constexpr int FF_MAX_N = 1024;                        // galaxies per field (DV_FIT_MAX_N)
 struct FitFluxParams { double min_pivot; int64_t scratch_bytes; };
 // (chi2, npix: the two rows of the weighted fit, 7s - null in the unweighted one)
-struct FitFluxRows { double *scale, *var, *gram, *proj; int* status; double* chi2 = nullptr; int* npix = nullptr; };
+// (scale_free, clamped, dual: the three rows of the non-negative fit, 7u - null in the unconstrained one)
+struct FitFluxRows {
+  double *scale, *var, *gram, *proj; int* status; double* chi2 = nullptr; int* npix = nullptr;
+  double* scale_free = nullptr; int* clamped = nullptr; double* dual = nullptr;
+};
+// The non-negative fit: amplitudes >= 0 by block principal pivoting, at most max_iter factorisations per field and
+// band.  iters / status [.][nb]: the per-field outputs, device or host, counted from field 0 of the call like FitFluxSky's.
+// on false: the unconstrained fit - nothing more is allocated, copied or launched, and fitflux_solve_kernel runs as before.
+struct FitFluxNonneg { bool on = false; int max_iter = 100; int* iters = nullptr; int* status = nullptr; };
 // The sky background fitted jointly: q = 1 (a constant) or 3 (a plane) more unknowns per field and band behind
 // the galaxies.  FitFluxSky: the per-field outputs, device or host - coef [.][nb][q], cov [.][nb][q][q], status [.][nb][q],
 // npix [.][nb] -, counted from field 0 of the call; q = 0: no sky, nothing more is allocated, copied or launched.
@@ -464,18 +472,25 @@ int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n, bool we
 int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan,
                  int sky_order = -1, int F = 0);
 int fitflux_sky_check(const char* who, int sky_order, const FitFluxSky& o, const FitFluxRows& rows, bool weighted);
+// the refusals of the non-negative calls (7u) that need no table: max_iter, the five new outputs, sky outputs given without
+// a sky, and (without a sky, where fitflux_sky_check does not run) chi-square outputs that do not match the weights
+int fitflux_nonneg_check(const char* who, const FitFluxNonneg& nn, const FitFluxRows& rows, int64_t n, const FitFluxSky& sky,
+                         bool weighted);
 // weight_dev: the weight fields from field f0 on, laid out like data_dev (7s), or null: the unweighted fit.  With weights the
 // chi-square kernel runs behind the solve and rows.chi2 / rows.npix are written
 // sky (7t): q = 1 or 3 sky terms per field and band and the device arrays of their outputs, counted from field 0 of the call; the
 // work area must have been planned for the same q.  A sub-range without galaxies is launched when there is a sky
+// nn (7u): on - fitflux_nonneg_kernel runs in place of the solve, rows.scale_free / clamped / dual and nn.iters / nn.status
+// (device, counted from field 0 of the call) are written; the fields of a sub-range that launches nothing get iters 0, status 0
 int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
                     const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
                     int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve = true,
-                    const double* weight_dev = nullptr, const FitFluxSky& sky = FitFluxSky{});
+                    const double* weight_dev = nullptr, const FitFluxSky& sky = FitFluxSky{},
+                    const FitFluxNonneg& nn = FitFluxNonneg{});
 int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                    const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
                    hipStream_t s, const double* weight_h = nullptr, const char* who = "dv_scene_fit_flux", int sky_order = -1,
-                   const FitFluxSky& sky_h = FitFluxSky{});
+                   const FitFluxSky& sky_h = FitFluxSky{}, const FitFluxNonneg& nn_h = FitFluxNonneg{});
 // step 1 of the bordered system of one field (7t): the dense [nb][n + q][n + q] lower triangle and its right-hand side
 // [n + q][nb] to the host, the bits the solve starts from
 int scene_fit_flux_sky_gram(const float* stamps_h, const int32_t* places_h, int64_t n, int cs, int nb, const double* data_h,

@@ -3970,6 +3970,27 @@ int dv_scene_fit_flux_sky(dv_ctx* c, const float* stamps, const int32_t* places,
                         FitFluxSky{-1, sky_coef, sky_cov, sky_status, (long long*)sky_npix});
 }
 
+// the non-negative fit, with or without weights and sky (sky_order -1: none): every refusal is scene_fit_flux's
+int dv_scene_fit_flux_nonneg(dv_ctx* c, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs,
+                             int32_t nb, const double* data_fields, const double* weight_fields, int32_t M, int32_t F,
+                             const dv_fit_flux_params* params, int32_t sky_order, int32_t max_iter, double* fit_scale,
+                             double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status, double* fit_chi2,
+                             int32_t* fit_npix, double* sky_coef, double* sky_cov, int32_t* sky_status, int64_t* sky_npix,
+                             double* fit_scale_free, int32_t* fit_clamped, double* fit_dual, int32_t* nonneg_iters,
+                             int32_t* nonneg_status) {
+  if (!c) return DV_E_INVALID;
+  if (!params) {
+    set_error("dv_scene_fit_flux_nonneg: params must be given");
+    return DV_E_INVALID;
+  }
+  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, FitFluxParams{params->min_pivot, params->scratch_bytes},
+                        FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix, fit_scale_free,
+                                    fit_clamped, fit_dual},
+                        0, c->device, c->stream, weight_fields, "dv_scene_fit_flux_nonneg", sky_order,
+                        FitFluxSky{sky_order == -1 ? 0 : -1, sky_coef, sky_cov, sky_status, (long long*)sky_npix},
+                        FitFluxNonneg{true, max_iter, nonneg_iters, nonneg_status});
+}
+
 int dv_scene_fit_flux_sky_gram(dv_ctx* c, const float* stamps, const int32_t* places, int64_t n, int32_t cs, int32_t nb,
                                const double* data_field, const double* weight_field, int32_t F, int32_t sky_order, double* gram,
                                double* rhs) {
@@ -5160,25 +5181,37 @@ struct ApertureFieldStage {         // the apertures of every stamp on the mean 
 // dv_infer_fields_measure_fit: the parameters in, five rows out (host); _fit_weighted (7s): the host weight fields [M][F][F][nb]
 // in too, and the rows carry fit_chi2 and fit_npix
 // _fit_sky (7t): the order of the sky fitted jointly (-1: none) and its per-field outputs (host)
-struct FitFluxOut { FitFluxParams par{}; FitFluxRows rows{}; const double* weights = nullptr; int sky_order = -1; FitFluxSky sky{}; };
+// _fit_nonneg (7u): the non-negativity constraint, max_iter and its per-field outputs (host)
+struct FitFluxOut {
+  FitFluxParams par{}; FitFluxRows rows{}; const double* weights = nullptr; int sky_order = -1; FitFluxSky sky{};
+  FitFluxNonneg nonneg{};
+};
 
 struct FitFluxStage {               // the simultaneous flux fit of every field's mean stamps to its source field (7q)
   DevBuf<float> store;              // the mean stamps of all N stamps: a field's are read when its composite is complete
   FitFluxWork work;
   FitFluxRows dev{};
   Rows rows;
-  void columns(const FitFluxOut& o, int nb) { fitflux_columns(rows, dev, o.rows, nb, o.weights != nullptr); }
+  void columns(const FitFluxOut& o, int nb) { fitflux_columns(rows, dev, o.rows, nb, o.weights != nullptr, o.nonneg.on); }
   size_t bytes_per_stamp(int cs, int nb) const { return (size_t)cs * cs * nb * sizeof(float) + rows.bytes(); }
   DevBuf<double> sky_coef, sky_cov;  // the per-field outputs of a fit with sky (7t), downloaded with the rows
   DevBuf<int> sky_status;
   DevBuf<long long> sky_npix;
   FitFluxSky sky{};
+  DevBuf<int> nn_iters, nn_status;   // the per-field outputs of a non-negative fit (7u), downloaded with the rows
+  FitFluxNonneg nonneg{};
   static size_t sky_bytes(int q, size_t M, int nb) {
     return M * nb * ((size_t)q * (q + 1) * sizeof(double) + q * sizeof(int) + sizeof(long long));
   }
-  int alloc(const FitFluxPlan& plan, int64_t N, int64_t M, int cs, int nb, bool weighted) {
+  static size_t nonneg_bytes(const FitFluxNonneg& o, size_t M, int nb) { return o.on ? 2 * M * nb * sizeof(int) : 0; }
+  int alloc(const FitFluxPlan& plan, int64_t N, int64_t M, int cs, int nb, bool weighted, const FitFluxNonneg& nn) {
     DV_TRY(store.alloc((size_t)N * cs * cs * nb));
     DV_TRY(work.alloc(plan, M, weighted));
+    if (nn.on) {
+      DV_TRY(nn_iters.alloc((size_t)M * nb));
+      DV_TRY(nn_status.alloc((size_t)M * nb));
+      nonneg = FitFluxNonneg{true, nn.max_iter, nn_iters.get(), nn_status.get()};
+    }
     if (const size_t q = (size_t)plan.q) {
       const size_t e = (size_t)M * nb;
       DV_TRY(sky_coef.alloc(e * q));
@@ -5196,6 +5229,13 @@ struct FitFluxStage {               // the simultaneous flux fit of every field'
     DV_HIP(hipMemcpyAsync(h.cov + o * q * q, sky.cov + o * q * q, e * q * q * sizeof(double), hipMemcpyDeviceToHost, s));
     DV_HIP(hipMemcpyAsync(h.status + o * q, sky.status + o * q, e * q * sizeof(int), hipMemcpyDeviceToHost, s));
     DV_HIP(hipMemcpyAsync(h.npix + o, sky.npix + o, e * sizeof(long long), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipStreamSynchronize(s));
+    return OK;
+  }
+  int nonneg_download(const FitFluxNonneg& h, size_t f0, size_t nf, int nb, hipStream_t s) const {
+    const size_t o = f0 * nb, e = nf * nb * sizeof(int);
+    DV_HIP(hipMemcpyAsync(h.iters + o, nonneg.iters + o, e, hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(h.status + o, nonneg.status + o, e, hipMemcpyDeviceToHost, s));
     DV_HIP(hipStreamSynchronize(s));
     return OK;
   }
@@ -5238,6 +5278,10 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   FitFluxPlan ffplan;
   if (rq.fit_flux)                                     // (before anything is written or queued)
     DV_TRY(fitflux_plan(who, field_ptr, M, nb, rq.fit_flux->par, &ffplan, rq.fit_flux->sky_order, F));
+  if (rq.fit_flux && rq.fit_flux->nonneg.on && M > 0) {   // (7u: a field without unknowns has no factorisation and converged)
+    std::fill(rq.fit_flux->nonneg.iters, rq.fit_flux->nonneg.iters + (size_t)M * nb, 0);
+    std::fill(rq.fit_flux->nonneg.status, rq.fit_flux->nonneg.status + (size_t)M * nb, 0);
+  }
   if (rq.fields) fields_write_empty(*rq.fields, fields, M, field_ptr, felems);
   // A fit with sky (7t) solves the fields without galaxies too.  The seam below reaches the fields of a group; every other one
   // - the call without stamps, the empty fields before the first group, between two groups and behind the last - takes the
@@ -5248,9 +5292,11 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     const size_t q = (size_t)ffplan.q, e = (size_t)fa * nb;
     const std::vector<int64_t> none((size_t)(fz - fa) + 1, 0);
     const FitFluxSky h{-1, o.sky.coef + e * q, o.sky.cov + e * q * q, o.sky.status + e * q, o.sky.npix + e};
+    FitFluxNonneg nn = o.nonneg;
+    if (nn.on) nn.iters += e, nn.status += e;
     return scene_fit_flux(nullptr, nullptr, none.data(), 0, m->A.H, nb, fields + (size_t)fa * felems, fz - fa, F, o.par, o.rows,
                           0, m->ctx->device, m->ctx->stream, o.weights ? o.weights + (size_t)fa * felems : nullptr, who,
-                          o.sky_order, h);
+                          o.sky_order, h, nn);
   };
   const bool ff_sky = rq.fit_flux && ffplan.q != 0;
   if (N == 0) return ff_sky ? sky_alone(0, M) : DV_OK;
@@ -5310,7 +5356,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (rq.fit_flux) {
     ffs.columns(*rq.fit_flux, nb);
     reserve += (size_t)N * ffs.bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M, wfields != nullptr) +
-               FitFluxStage::sky_bytes(ffplan.q, (size_t)M, nb);
+               FitFluxStage::sky_bytes(ffplan.q, (size_t)M, nb) + FitFluxStage::nonneg_bytes(rq.fit_flux->nonneg, (size_t)M, nb);
     if (wfields) per_field += fb;
   }
   size_t budget = 0;
@@ -5360,7 +5406,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   }
   if (rq.aper_field) DV_TRY(afs.rows.alloc(N));
   if (rq.fit_flux) {
-    DV_TRY(ffs.alloc(ffplan, N, M, c.cs, nb, wfields != nullptr));
+    DV_TRY(ffs.alloc(ffplan, N, M, c.cs, nb, wfields != nullptr, rq.fit_flux->nonneg));
     ffs.bind(j.ff);
   }
   if (fitting) {
@@ -5413,7 +5459,10 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
                                        mean_f, fdev, rq.aper->par, aperture_field_rows_at(afs.dev, r0, rq.aper->par, nb), s));
         if (rq.fit_flux)               // (the stamp store, the placements and the tables count from stamp 0 of the call)
           DV_TRY(launch_fit_flux(ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, places, fptr32.data(), fa, fz, c.cs,
-                                 nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s, true, wfields ? wdev.get() : nullptr, ffs.sky));
+                                 nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s, true, wfields ? wdev.get() : nullptr, ffs.sky,
+                                 ffs.nonneg));
+        if (rq.fit_flux && rq.fit_flux->nonneg.on)
+          DV_TRY(ffs.nonneg_download(rq.fit_flux->nonneg, (size_t)fa, (size_t)(fz - fa + 1), nb, s));
         if (ff_sky) {
           DV_TRY(ffs.sky_download(rq.fit_flux->sky, (size_t)fa, (size_t)(fz - fa + 1), nb, s));
           DV_TRY(sky_alone(sky_next, fa));
@@ -5590,6 +5639,8 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const Catalo
     DV_TRY(fitflux_rows_check(who, rq.fit_flux->rows, N, rq.fit_flux->weights != nullptr));
     if (rq.fit_flux->sky.q) DV_TRY(fitflux_sky_check(who, rq.fit_flux->sky_order, rq.fit_flux->sky, rq.fit_flux->rows,
                                                      rq.fit_flux->weights != nullptr));
+    if (rq.fit_flux->nonneg.on) DV_TRY(fitflux_nonneg_check(who, rq.fit_flux->nonneg, rq.fit_flux->rows, N, rq.fit_flux->sky,
+                                                            rq.fit_flux->weights != nullptr));
     DV_TRY(seam_places_check(who, a));
   }
   if (rq.regauss) {
@@ -5802,6 +5853,34 @@ int dv_infer_fields_measure_fit_sky(dv_model* m, const double* fields, int32_t M
                            FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields,
                            sky_order, FitFluxSky{-1, sky_coef, sky_cov, sky_status, (long long*)sky_npix}};
   return infer_fields_measure_entry("dv_infer_fields_measure_fit_sky", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
+}
+
+// ---- the non-negative flux fit: dv_infer_fields_measure_fit_sky - sky_order may be -1, no sky, and the four
+// sky outputs are NULL exactly then - plus max_iter, three more galaxy rows and the two per-field outputs of the iteration
+int dv_infer_fields_measure_fit_nonneg(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                       const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                       const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                       double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                       int32_t* iters, int32_t* status, const dv_fit_flux_params* fit, const double* weight_fields,
+                                       int32_t sky_order, int32_t max_iter, double* fit_scale, double* fit_var, double* fit_gram,
+                                       double* fit_proj, int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, double* sky_coef,
+                                       double* sky_cov, int32_t* sky_status, int64_t* sky_npix, double* fit_scale_free,
+                                       int32_t* fit_clamped, double* fit_dual, int32_t* nonneg_iters, int32_t* nonneg_status) {
+  if (!m) return DV_E_INVALID;
+  if (!fit) {
+    set_error("dv_infer_fields_measure_fit_nonneg: the flux-fit params must be given");
+    return DV_E_INVALID;
+  }
+  FieldsRequest rq;
+  rq.fit_flux = FitFluxOut{FitFluxParams{fit->min_pivot, fit->scratch_bytes},
+                           FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix, fit_scale_free,
+                                       fit_clamped, fit_dual},
+                           weight_fields, sky_order,
+                           FitFluxSky{sky_order == -1 ? 0 : -1, sky_coef, sky_cov, sky_status, (long long*)sky_npix},
+                           FitFluxNonneg{true, max_iter, nonneg_iters, nonneg_status}};
+  return infer_fields_measure_entry("dv_infer_fields_measure_fit_nonneg", m,
                                     {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
                                      residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }

@@ -53,6 +53,10 @@
 //                             pixels, four bands per workgroup, one row of partial sums per tile;
 //   fitflux_skyreduce_kernel  the partial sums in tile order - an order that depends on F alone.
 // The sky terms are eliminated last: the factorisation of the galaxy block is the one of the fit without sky, bit for bit.
+// The non-negative fit minimises the same quadratic subject to a_i >= 0 for the galaxies, the sky left free:
+//   fitflux_nonneg_kernel     in place of fitflux_solve_kernel when the constraint is asked for, on the same scratch: iteration
+//                             1 is steps 2 - 5 above, then the active set is exchanged and the kept unknowns that are not
+//                             clamped are factorised again until no amplitude and no multiplier is negative.
 // No atomics; ordinary vector stores only.
 #include "common.h"
 #include "measure_dev.h"
@@ -557,6 +561,245 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __
   }
 }
 
+// The non-negative fit: the same quadratic minimised subject to a_i >= 0 for the galaxies, the sky left free,
+// by block principal pivoting (Kim & Park) with Murty's single exchange as the backup rule.  Field fbase + blockIdx.x, band
+// blockIdx.y, on the scratch of fitflux_solve_kernel and in its place.  Iteration 1 is that kernel's steps 2 - 5, operation
+// for operation: it fixes fit_status, the dropped set, h' (s_hp) and the unconstrained amplitudes (scale_free).  Every
+// iteration rebuilds the working copy - the strict upper triangle from the strict lower one, which keeps G, the diagonal
+// from gram / skysums -, factorises it over the kept unknowns that are not clamped (s_on; no pivot test after iteration 1: a
+// pivot over a subset of the predecessors is not smaller), solves, and takes y_i = (sum_j G_ij a_j) - h'_i for every clamped
+// i, j ascending over s_on, sequentially in one thread.  s_y holds a_i for the passive unknowns and y_i for the clamped
+// galaxies, so V is the kept galaxies with s_y < 0.0; its size and largest member come from integer reductions in LDS, and
+// every thread keeps the same exchange state (best, p).  L^-1 comes last, on the last passive set, because it overwrites G.
+// LDS: 2 x 8 KB of doubles, 3 x 4 KB of flags, 2 KB of reduction.  No atomics, nothing handed between workgroups.
+template <int Q>
+__global__ __launch_bounds__(MS_THREADS) void fitflux_nonneg_kernel(const int* __restrict__ fptr, const long long* __restrict__ foff,
+                                                                    int fbase, int nb, double min_pivot, int max_iter,
+                                                                    double* __restrict__ scratch, const double* __restrict__ gram,
+                                                                    const double* __restrict__ proj, double* __restrict__ scale,
+                                                                    double* __restrict__ var, int* __restrict__ status,
+                                                                    double* __restrict__ scale_free, int* __restrict__ clamped,
+                                                                    double* __restrict__ dual, int* __restrict__ nn_iters,
+                                                                    int* __restrict__ nn_status, const double* __restrict__ skysums,
+                                                                    double* __restrict__ sky_coef, double* __restrict__ sky_cov,
+                                                                    int* __restrict__ sky_status) {
+  __shared__ double s_y[FF_MAX_N + Q];         // a_i of a passive unknown, y_i of a clamped galaxy
+  __shared__ double s_hp[FF_MAX_N + Q];        // h' (step 4), fixed by iteration 1
+  __shared__ int s_st[FF_MAX_N + Q];           // 0 / 4 / 5, frozen after iteration 1
+  __shared__ int s_z[FF_MAX_N + Q];            // bit 0: clamped; bit 1: in V of this iteration
+  __shared__ int s_on[FF_MAX_N + Q];           // kept and not clamped: part of this iteration's system
+  __shared__ int s_cnt[MS_THREADS], s_max[MS_THREADS];
+  const int m = fbase + (int)blockIdx.x, b = (int)blockIdx.y;
+  const long row0 = fptr[m];
+  const int ng = fptr[m + 1] - (int)row0;      // the galaxies
+  const int n = ng + Q;                        // the unknowns
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (n <= 0) {
+    if (tid == 0) nn_iters[(long)m * nb + b] = nn_status[(long)m * nb + b] = 0;
+    return;
+  }
+  double* S = scratch + foff[blockIdx.x] + (long)b * n * n;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double* ks = Q > 0 ? skysums + ((long)blockIdx.x * nb + b) * SKY_ACC(Q) : nullptr;
+  auto diag0 = [&](int k) -> double {
+    if (Q > 0 && k >= ng) return ks[(k - ng) * (k - ng + 3) / 2];
+    return gram[(row0 + k) * nb + b];
+  };
+  auto rhs0 = [&](int k) -> double {
+    if (Q > 0 && k >= ng) return ks[Q * (Q + 1) / 2 + (k - ng)];
+    return proj[(row0 + k) * nb + b];
+  };
+
+  // step 2
+  for (int i = tid; i < n; i += MS_THREADS) {
+    const double gii = diag0(i);
+    s_st[i] = (ms_finite(gii) && gii > 0.0) ? 0 : 4;
+    s_z[i] = 0;
+  }
+  int best = ng + 1, p = 3, iters = 0, nviol = 0;
+  for (int t = 1;; ++t) {
+    // the working copy, and who is in the system (thread i % 256 owns the flags of unknown i throughout)
+    for (int i = tid; i < n; i += MS_THREADS) {
+      s_on[i] = s_st[i] == 0 && !(s_z[i] & 1);
+      S[(long)i * n + i] = diag0(i);
+    }
+    for (int i = wave; i < n; i += MS_THREADS / 64)
+      for (int j = lane; j < i; j += 64) S[(long)j * n + i] = S[(long)i * n + j];
+    __syncthreads();
+
+    // step 3 over s_on, right-looking as in fitflux_solve_kernel; the pivot test and the dropping in iteration 1 alone
+    for (int k = 0; k < n; ++k) {
+      if (!s_on[k]) continue;                  // (uniform; s_on[k] was last written behind a barrier)
+      const double d = S[(long)k * n + k];
+      if (t == 1 && d <= min_pivot * diag0(k)) {
+        __syncthreads();                       // everyone has read s_on[k]
+        if (tid == 0) {
+          s_st[k] = 5;
+          s_on[k] = 0;
+        }
+        __syncthreads();
+        continue;
+      }
+      const double lkk = __dsqrt_rn(d);
+      __syncthreads();                         // everyone has read the pivot
+      if (tid == 0) S[(long)k * n + k] = lkk;
+      for (int i = k + 1 + tid; i < n; i += MS_THREADS)
+        if (s_on[i]) S[(long)k * n + i] = S[(long)k * n + i] / lkk;
+      __syncthreads();
+      for (int j = k + 1 + wave; j < n; j += MS_THREADS / 64) {
+        if (!s_on[j]) continue;
+        const double ljk = S[(long)k * n + j];
+        for (int i = j + lane; i < n; i += 64)
+          if (s_on[i]) S[(long)j * n + i] = S[(long)j * n + i] - S[(long)k * n + i] * ljk;
+      }
+      __syncthreads();
+    }
+
+    // step 4, once: the dropped set is frozen
+    if (t == 1) {
+      for (int i = tid; i < n; i += MS_THREADS) {
+        double hp = rhs0(i);
+        if (s_st[i] == 0) {
+          for (int k = 0; k < ng; ++k)
+            if (s_st[k] == 5) hp = hp - (k < i ? S[(long)i * n + k] : S[(long)k * n + i]);   // (G_ik lies at (max, min))
+        }
+        s_hp[i] = hp;
+      }
+    }
+    for (int i = tid; i < n; i += MS_THREADS) s_y[i] = s_hp[i];
+    __syncthreads();
+
+    // step 5 over s_on
+    for (int k = 0; k < n; ++k) {
+      if (!s_on[k]) continue;
+      const double yk = s_y[k] / S[(long)k * n + k];
+      __syncthreads();                         // everyone has read s_y[k]
+      if (tid == 0) s_y[k] = yk;
+      for (int i = k + 1 + tid; i < n; i += MS_THREADS)
+        if (s_on[i]) s_y[i] = s_y[i] - S[(long)k * n + i] * yk;
+      __syncthreads();
+    }
+    for (int k = n - 1; k >= 0; --k) {
+      if (!s_on[k]) continue;
+      const double ak = s_y[k] / S[(long)k * n + k];
+      __syncthreads();
+      if (tid == 0) s_y[k] = ak;
+      for (int i = tid; i < k; i += MS_THREADS)
+        if (s_on[i]) s_y[i] = s_y[i] - S[(long)i * n + k] * ak;
+      __syncthreads();
+    }
+
+    // the unconstrained amplitudes; the duals of the clamped galaxies; V
+    int cnt = 0, mx = -1;
+    for (int i = tid; i < ng; i += MS_THREADS) {
+      const int st = s_st[i];
+      if (t == 1) scale_free[(row0 + i) * nb + b] = st == 0 ? s_y[i] : st == 5 ? 1.0 : nan;
+      if (s_z[i] & 1) {
+        double sum = 0.0;
+        for (int j = 0; j < n; ++j)
+          if (s_on[j]) sum = sum + (j < i ? S[(long)i * n + j] : S[(long)j * n + i]) * s_y[j];
+        s_y[i] = sum - s_hp[i];                // (i is not in the system: nobody reads s_y[i] in this loop)
+      }
+      const int v = st == 0 && s_y[i] < 0.0;
+      s_z[i] = (s_z[i] & 1) | (v << 1);
+      cnt += v;
+      if (v) mx = i;                           // (i ascends)
+    }
+    s_cnt[tid] = cnt;
+    s_max[tid] = mx;
+    __syncthreads();
+    for (int o = MS_THREADS / 2; o > 0; o >>= 1) {
+      if (tid < o) {
+        s_cnt[tid] += s_cnt[tid + o];
+        s_max[tid] = max(s_max[tid], s_max[tid + o]);
+      }
+      __syncthreads();
+    }
+    nviol = s_cnt[0];
+    mx = s_max[0];
+    iters = t;
+    if (nviol == 0 || t >= max_iter) break;    // (uniform)
+
+    // the exchange: all of V while that makes progress or p allows, else its largest member alone
+    bool all = true;
+    if (nviol < best) {
+      best = nviol;
+      p = 3;
+    } else if (p > 0) {
+      p -= 1;
+    } else {
+      all = false;
+    }
+    for (int i = tid; i < ng; i += MS_THREADS)
+      if ((s_z[i] & 2) && (all || i == mx)) s_z[i] ^= 1;
+    __syncthreads();                           // everyone has read the reduction
+  }
+  if (tid == 0) {
+    nn_iters[(long)m * nb + b] = iters;
+    nn_status[(long)m * nb + b] = nviol == 0 ? 0 : 1;
+  }
+
+  // L^-1 on the last passive set, as in fitflux_solve_kernel, and the rows
+  for (int i0 = 0; i0 < n; i0 += MS_THREADS) {
+    const int i = i0 + tid;
+    const bool on = i < n && s_on[i];
+    double xi = 0.0, acc = 0.0;
+    if (on) {
+      xi = 1.0 / S[(long)i * n + i];
+      acc = xi * xi;
+    }
+    for (int r = i0 + 1; r < n; ++r) {
+      if (!s_on[r]) continue;                  // (uniform)
+      double sum = 0.0;
+      if (on && r > i) sum = S[(long)i * n + r] * xi;
+      for (int c = i0 + 1; c < r; ++c) {
+        if (!s_on[c]) continue;
+        if (on && c > i) sum = sum + S[(long)c * n + r] * S[(long)c * n + i];
+      }
+      if (on && r > i) {
+        const double x = -sum / S[(long)r * n + r];
+        S[(long)r * n + i] = x;
+        acc = acc + x * x;
+      }
+    }
+    if (i < ng) {
+      const long o = (row0 + i) * nb + b;
+      const int st = s_st[i], z = s_z[i] & 1;
+      scale[o] = st == 0 ? (z ? 0.0 : s_y[i]) : st == 5 ? 1.0 : nan;
+      var[o] = on ? acc : nan;
+      status[o] = st;
+      clamped[o] = z;
+      dual[o] = st == 0 ? (z ? s_y[i] : 0.0) : nan;
+    }
+  }
+  if constexpr (Q > 0) {
+    // the sky terms, never clamped: s_on is s_st == 0 for them
+    __syncthreads();                           // the columns of X are complete
+    if (tid == 0) {
+      const long o = (long)m * nb + b;
+      for (int t = 0; t < Q; ++t) {
+        const int st = s_st[ng + t];
+        sky_coef[o * Q + t] = st == 0 ? s_y[ng + t] : st == 5 ? 0.0 : nan;
+        sky_status[o * Q + t] = st;
+        for (int u = 0; u <= t; ++u) {
+          double cv = nan;
+          if (st == 0 && s_st[ng + u] == 0) {
+            cv = 0.0;
+            for (int r = ng + t; r < n; ++r) {
+              if (s_st[r] != 0) continue;
+              const double xt = r == ng + t ? 1.0 / S[(long)r * n + r] : S[(long)r * n + ng + t];
+              const double xu = r == ng + u ? 1.0 / S[(long)r * n + r] : S[(long)r * n + ng + u];
+              cv = cv + xt * xu;
+            }
+          }
+          sky_cov[(o * Q + t) * Q + u] = cv;
+          sky_cov[(o * Q + u) * Q + t] = cv;
+        }
+      }
+    }
+  }
+}
+
 // The chi-square of the refitted scene under galaxy r0 + blockIdx.x (7s, step 3), behind the solve of its sub-range.  adj_ptr
 // [rows + 1] / adj [.]: the CSR adjacency of the sub-range's rows, counted from r0: the rows of the field whose clipped
 // rectangle intersects the galaxy's, ascending, itself included.  Threads take the pixels of the clipped stamp in raster order,
@@ -763,6 +1006,29 @@ int fitflux_sky_check(const char* who, int sky_order, const FitFluxSky& o, const
   return OK;
 }
 
+int fitflux_nonneg_check(const char* who, const FitFluxNonneg& nn, const FitFluxRows& rows, int64_t n, const FitFluxSky& sky,
+                         bool weighted) {
+  if (nn.max_iter < 1) {
+    set_error("%s: max_iter must be at least 1 (got %d)", who, nn.max_iter);
+    return E_INVALID;
+  }
+  if (!nn.iters || !nn.status || (n > 0 && (!rows.scale_free || !rows.clamped || !rows.dual))) {
+    set_error("%s: fit_scale_free, fit_clamped, fit_dual, nonneg_iters and nonneg_status must all be given", who);
+    return E_INVALID;
+  }
+  if (sky.q == 0) {
+    if (sky.coef || sky.cov || sky.status || sky.npix) {
+      set_error("%s: sky_order -1 fits no sky: sky_coef, sky_cov, sky_status and sky_npix must all be NULL", who);
+      return E_INVALID;
+    }
+    if (!weighted && (rows.chi2 || rows.npix)) {
+      set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: without weight_fields both must be NULL", who);
+      return E_INVALID;
+    }
+  }
+  return OK;
+}
+
 int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan, int sky_order,
                  int F) {
   size_t total = 0, pairs = 0;
@@ -815,7 +1081,7 @@ int FitFluxWork::alloc(const FitFluxPlan& plan, int64_t max_fields, bool weighte
   return foff.alloc((size_t)std::max<int64_t>(max_fields, 1));
 }
 
-void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb, bool weighted) {
+void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb, bool weighted, bool nonneg) {
   r.add(dev.scale, host.scale, nb);
   r.add(dev.var, host.var, nb);
   r.add(dev.gram, host.gram, nb);
@@ -824,6 +1090,11 @@ void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb,
   if (weighted) {
     r.add(dev.chi2, host.chi2, nb);
     r.add(dev.npix, host.npix, nb);
+  }
+  if (nonneg) {
+    r.add(dev.scale_free, host.scale_free, nb);
+    r.add(dev.clamped, host.clamped, nb);
+    r.add(dev.dual, host.dual, nb);
   }
 }
 
@@ -835,7 +1106,7 @@ void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb,
 int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
                     const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
                     int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve,
-                    const double* weight_dev, const FitFluxSky& sky) {
+                    const double* weight_dev, const FitFluxSky& sky, const FitFluxNonneg& nn) {
   const bool chi = weight_dev && solve;                // the chi-square of the weighted fit, behind the solve
   const int q = sky.q;                                 // the sky terms of every field (7t), 0: none
   const int ntiles = q ? (int)fitflux_sky_tiles(F) : 0;
@@ -880,6 +1151,10 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
     }
     const int r0 = fptr_h[f], r1 = fptr_h[g];
     const size_t npairs = w.pairs_h.size() / 2;
+    if (nn.on && solve) {                              // (a sub-range that launches nothing: no unknowns, no factorisation)
+      DV_HIP(hipMemsetAsync(nn.iters + (size_t)f * nb, 0, (size_t)(g - f) * nb * sizeof(int), s));
+      DV_HIP(hipMemsetAsync(nn.status + (size_t)f * nb, 0, (size_t)(g - f) * nb * sizeof(int), s));
+    }
     if (r1 > r0 || q) {                                // (a field without galaxies still has its sky)
       DV_TRY(w.pairs.ensure(w.pairs_h.size()));
       DV_TRY(w.foff.ensure(w.foff_h.size()));
@@ -937,7 +1212,17 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
   hipLaunchKernelGGL((fitflux_solve_kernel<QQ>), dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev,         \
                      w.foff.get(), f, nb, p.min_pivot, w.scratch.get(), rows.gram, rows.proj, rows.scale, rows.var, rows.status, \
                      (const double*)w.sky_sums.get(), sky.coef, sky.cov, sky.status)
-        if (q == 0) DV_FF_SOLVE(0); else if (q == 1) DV_FF_SOLVE(1); else DV_FF_SOLVE(3);
+#define DV_FF_NONNEG(QQ)                                                                                                        \
+  hipLaunchKernelGGL((fitflux_nonneg_kernel<QQ>), dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev,        \
+                     w.foff.get(), f, nb, p.min_pivot, nn.max_iter, w.scratch.get(), rows.gram, rows.proj, rows.scale, rows.var, \
+                     rows.status, rows.scale_free, rows.clamped, rows.dual, nn.iters, nn.status,                               \
+                     (const double*)w.sky_sums.get(), sky.coef, sky.cov, sky.status)
+        if (nn.on) {                                   // (7u: in place of the solve, on the same scratch)
+          if (q == 0) DV_FF_NONNEG(0); else if (q == 1) DV_FF_NONNEG(1); else DV_FF_NONNEG(3);
+        } else {
+          if (q == 0) DV_FF_SOLVE(0); else if (q == 1) DV_FF_SOLVE(1); else DV_FF_SOLVE(3);
+        }
+#undef DV_FF_NONNEG
 #undef DV_FF_SOLVE
         DV_HIP(hipGetLastError());
       }
@@ -982,11 +1267,13 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
 // with their stamps, tables and rows (0: half of free device memory beside the scratch, taken after the refusals)
 int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                    const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
-                   hipStream_t s, const double* weight_h, const char* who, int sky_order, const FitFluxSky& sky_h) {
+                   hipStream_t s, const double* weight_h, const char* who, int sky_order, const FitFluxSky& sky_h,
+                   const FitFluxNonneg& nn_h) {
   const bool weighted = weight_h != nullptr;
   const bool with_sky = sky_h.q != 0;                  // (the sky calls set q to a non-zero value before the order is checked)
   DV_TRY(fitflux_check(who, cs, nb, F, p));
   if (with_sky) DV_TRY(fitflux_sky_check(who, sky_order, sky_h, out_h, weighted));
+  if (nn_h.on) DV_TRY(fitflux_nonneg_check(who, nn_h, out_h, N, sky_h, weighted));
   const int q = with_sky ? fitflux_sky_q(sky_order) : 0;
   if (N < 0 || M < 0 || !field_ptr || ((N > 0 || (q && M > 0)) && !data_h) || (N > 0 && (!stamps_h || !places_h))) {
     set_error("%s: stamps, places, field_ptr and data_fields must all be given", who);
@@ -996,14 +1283,19 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
   DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));   // (the chunks build their own tables)
   FitFluxPlan plan;
   DV_TRY(fitflux_plan(who, field_ptr, M, nb, p, &plan, with_sky ? sky_order : -1, F));
+  if (nn_h.on && M > 0) {                              // (a field without unknowns: no factorisation, converged)
+    std::fill(nn_h.iters, nn_h.iters + (size_t)M * nb, 0);
+    std::fill(nn_h.status, nn_h.status + (size_t)M * nb, 0);
+  }
   if (N == 0 && !(q && M > 0)) return OK;
   FitFluxRows d{};
   Rows out;
-  fitflux_columns(out, d, out_h, nb, weighted);
+  fitflux_columns(out, d, out_h, nb, weighted, nn_h.on);
   const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
   const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + out.bytes();
   const size_t sky_out = q ? (size_t)nb * ((size_t)q * (q + 1) * sizeof(double) + q * sizeof(int) + sizeof(long long)) : 0;
   const size_t per_field = (weighted ? 2 : 1) * felems * sizeof(double) + sizeof(int) + sizeof(long long) + sky_out +
+                           (nn_h.on ? 2 * (size_t)nb * sizeof(int) : 0) +
                            (q ? (plan.sky_part + FF_BANDS * fitflux_sky_acc(q)) * sizeof(double) : 0);
   DV_HIP(hipSetDevice(device));
   FitFluxWork work;
@@ -1058,6 +1350,13 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
     DV_TRY(sky_npix.alloc(cmax_f * nb));
     sky_d = FitFluxSky{q, sky_coef.get(), sky_cov.get(), sky_status.get(), sky_npix.get()};
   }
+  DevBuf<int> nn_iters, nn_status;
+  FitFluxNonneg nn_d{};
+  if (nn_h.on) {
+    DV_TRY(nn_iters.alloc(std::max<size_t>(cmax_f, 1) * nb));
+    DV_TRY(nn_status.alloc(std::max<size_t>(cmax_f, 1) * nb));
+    nn_d = FitFluxNonneg{true, nn_h.max_iter, nn_iters.get(), nn_status.get()};
+  }
   std::vector<int> sf_h, fptr_h;
   StreamDrain drain(s);
   for (size_t k = 0; k + 1 < cuts.size(); ++k) {
@@ -1080,8 +1379,13 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
     if (weighted)
       DV_HIP(hipMemcpyAsync(wdata, weight_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
     DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h ? places_h + (size_t)r0 * 2 : nullptr, fptr_h.data(), 0,
-                           fz - fa - 1, cs, nb, F, p, work, d, s, true, weighted ? wdata.get() : nullptr, sky_d));
+                           fz - fa - 1, cs, nb, F, p, work, d, s, true, weighted ? wdata.get() : nullptr, sky_d, nn_d));
     if (n > 0) DV_TRY(out.download(r0, n, s));
+    if (nn_h.on) {                                     // the per-field outputs, with the rows
+      const size_t e = (size_t)(fz - fa) * nb * sizeof(int), o = (size_t)fa * nb;
+      DV_HIP(hipMemcpyAsync(nn_h.iters + o, nn_iters, e, hipMemcpyDeviceToHost, s));
+      DV_HIP(hipMemcpyAsync(nn_h.status + o, nn_status, e, hipMemcpyDeviceToHost, s));
+    }
     if (q) {                                           // the per-field outputs, with the rows
       const size_t nf = (size_t)(fz - fa), o = (size_t)fa * nb;
       DV_HIP(hipMemcpyAsync(sky_h.coef + o * q, sky_coef, nf * nb * q * sizeof(double), hipMemcpyDeviceToHost, s));

@@ -46,7 +46,7 @@ void blend_columns(Rows& r, BlendRows& dev, const BlendRows& host);
 void regauss_columns(Rows& r, RegaussRows& dev, const RegaussRows& host);
 void aperture_columns(Rows& r, ApertureRows& dev, const ApertureRows& host, const ApertureParams& p, int nb, bool err);
 void aperture_field_columns(Rows& r, ApertureFieldRows& dev, const ApertureFieldRows& host, const ApertureParams& p, int nb);
-void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb, bool weighted = false);
+void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb, bool weighted = false, bool nonneg = false);
 
 // The refusals every field-grouped call takes for its tables, before any GPU work, and the tables: N < 2^31 `noun`s, F within
 // 1 .. 32768 (F null: the caller has its own bound), field_ptr from 0 to N and never decreasing, every placement within

@@ -150,6 +150,14 @@ _EXTRAS = (
            lambda out, c: ms.fit_sky_records(out["sky_coef"], out["sky_cov"], out["sky_status"], c.places, c.cs, c.F,
                                              field_ptr=c.field_ptr, sky_sigma=c.sky_sigma, weighted=c.fit_weights is not None),
            refines="fit_flux"),
+    # (the last refining extra: its call passes the weights and the order of the sky on - None: no sky)
+    _Extra("fit_nonneg", bool, "fit_nonneg=True", "needs", "the non-negative flux fit",
+           "fit_nonneg=True needs fit_flux=True: it constrains the amplitudes of the flux fit to be >= 0",
+           "dv_infer_fields_measure_fit_nonneg", "infer_fields_measure_fit_nonneg", True,
+           lambda c: dict(band=c.band, sky_order=c.fit_sky, weight_fields=c.fit_weights),
+           lambda c: ms.fit_nonneg_dtype(c.bands),
+           lambda out, c: ms.fit_nonneg_records(*(out[k] for k in E.FIT_NONNEG_KEYS), out["flux"]),
+           refines="fit_flux"),
 )
 
 
@@ -611,6 +619,13 @@ class DeblendFieldBatch:
         return ms.fit_sky_dtype(nb_of_bands)
 
     @staticmethod
+    def fit_nonneg_columns(nb_of_bands):
+        """What deblend_fields(measure=True, fit_flux=True, fit_nonneg=True) appends behind every other column of the flux fit
+        (fit_flux_columns or fit_flux_weighted_columns, then fit_sky_columns with fit_sky): fit_scale_free, flux_fit_free,
+        fit_clamped and fit_dual."""
+        return ms.fit_nonneg_dtype(nb_of_bands)
+
+    @staticmethod
     def fit_flux_weighted_columns(nb_of_bands):
         """What deblend_fields(measure=True, fit_flux=True, fit_weights=W) appends behind measure_columns: the recarray of
         fit_fluxes_weighted - fit_flux_columns, then fit_chi2 and fit_npix."""
@@ -671,6 +686,8 @@ class DeblendFieldBatch:
         self.sky_fit = None             # {sky_coef (M, bands, q), sky_cov (M, bands, q, q), sky_status (M, bands, q), sky_npix
                                         # (M, bands)} of the last pass that fitted a sky (fit_sky): the per-field arrays of
                                         # Context.scene_fit_flux_sky, fields without galaxies included
+        self.nonneg_fit = None          # {nonneg_iters, nonneg_status (M, bands)} of the last pass that constrained the flux fit
+                                        # to amplitudes >= 0 (fit_nonneg): the per-field arrays of Context.scene_fit_flux_nonneg
 
     @property
     def _ctx(self):
@@ -695,7 +712,8 @@ class DeblendFieldBatch:
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
                        measure=False, return_fields=True, measure_samples=0, blendedness=False,
                        psf=None, psf_index=None, apertures=None, flux_fractions=None, aperture_data=False,
-                       sky_sigma=None, fit_flux=False, fit_weights=None, fit_sky=None, optimise_positions=False):
+                       sky_sigma=None, fit_flux=False, fit_weights=None, fit_nonneg=False, fit_sky=None,
+                       optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -804,15 +822,25 @@ class DeblendFieldBatch:
         debvader_amd.measure.measurement.fit_fluxes_sky describes them).  fit_var and the errors derived from it now carry the
         covariance with the sky.  self.sky_fit holds the per-field arrays sky_coef, sky_cov, sky_status and sky_npix of the
         pass, fields without galaxies included.  Unweighted, a non-finite pixel anywhere in a field reaches every galaxy of
-        that field through the sky: mask it with fit_weights.  It changes no other refusal of fit_flux."""
+        that field through the sky: mask it with fit_weights.  It changes no other refusal of fit_flux.
+
+        fit_nonneg=True (with fit_flux=True, with or without fit_weights, fit_sky and return_fields): the amplitudes of the
+        flux fit are constrained to be >= 0, the sky left free (dv_infer_fields_measure_fit_nonneg).  A
+        spurious or very faint detection under a brighter neighbour then gets exactly zero flux instead of a negative one, and
+        the neighbour is no longer biased upwards by the light the negative model gave back.  In the columns of the flux fit
+        fit_scale and flux_fit are 0 for a clamped galaxy and fit_var, fit_scale_err, flux_fit_err and fit_independence NaN;
+        the recarrays gain, behind every other column, fit_nonneg_columns: fit_scale_free and flux_fit_free, the amplitude and
+        flux of the fit without the constraint, fit_clamped and fit_dual (debvader_amd.measure.measurement.fit_fluxes_nonneg
+        describes them).  self.nonneg_fit holds the per-field arrays nonneg_iters and nonneg_status of the pass.  A field and
+        band without a negative amplitude keeps the values of the call without it.  It changes no other refusal of fit_flux."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
-        aperture_data, fit_flux = bool(aperture_data), bool(fit_flux)
+        aperture_data, fit_flux, fit_nonneg = bool(aperture_data), bool(fit_flux), bool(fit_nonneg)
         band = 2                        # the band of the measurement (r): the engine call and the blendedness in the apertures
         kw = dict(measure_samples=measure_samples, blendedness=blendedness, psf=psf, psf_index=psf_index, apertures=apertures,
                   flux_fractions=flux_fractions, aperture_data=aperture_data, fit_flux=fit_flux, fit_weights=fit_weights,
-                  fit_sky=fit_sky)
+                  fit_sky=fit_sky, fit_nonneg=fit_nonneg)
         given = [x.key for x in _EXTRAS if x.given(kw[x.key])]
         for x in _EXTRAS[1:]:           # (measure_samples, the oldest, is refused below its own integer check)
             _refuse_extra(x, kw, given, measure, on_device, fit, mc)
@@ -871,6 +899,7 @@ class DeblendFieldBatch:
         self.position_fit = None
         self.psf_moments = None
         self.sky_fit = None
+        self.nonneg_fit = None
         N = len(starts)
         if psf is not None:
             psf, psf_index = self._psf_index(psf, psf_index, field_ptr)
@@ -938,6 +967,8 @@ class DeblendFieldBatch:
                 self.psf_moments = {k: out[k] for k in ("psf_shape", "psf_aux", "psf_iters", "psf_status")}
             if fit_sky is not None:
                 self.sky_fit = {k: out[k] for k in E.FIT_SKY_KEYS}
+            if fit_nonneg:
+                self.nonneg_fit = {k: out[k] for k in E.FIT_NONNEG_FIELD_KEYS}
             # a stamp's pixel (row, col) is the field's pixel start + (row, col); distances count from pixel int(F / 2)
             measured = starts + np.stack([cat["row"], cat["col"]], axis=1) - int(F / 2) if N else np.zeros((0, 2))
         res = []

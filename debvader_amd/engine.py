@@ -317,6 +317,55 @@ def _fit_sky_out(M, nb, q):
                  out["sky_npix"].ctypes.data_as(C.POINTER(C.c_int64))]
 
 
+FIT_NONNEG_KEYS = ("fit_scale_free", "fit_clamped", "fit_dual")       # per galaxy: the non-negative fit
+FIT_NONNEG_FIELD_KEYS = ("nonneg_iters", "nonneg_status")             # per field and band
+
+
+def nonneg_max_iter(max_iter) -> int:
+    """The checked iteration cap of a non-negative flux fit (the library refuses the same)"""
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or int(max_iter) < 1:
+        raise ValueError(f"max_iter must be an integer >= 1 (got {max_iter!r})")
+    return int(max_iter)
+
+
+def _fit_nonneg_out(n, M, nb):
+    """The arrays a non-negative flux fit adds - three per galaxy, two per field - and their pointers in the C-ABI's order"""
+    out = dict(fit_scale_free=np.zeros((n, nb), np.float64), fit_clamped=np.zeros((n, nb), np.int32),
+               fit_dual=np.zeros((n, nb), np.float64), nonneg_iters=np.zeros((M, nb), np.int32),
+               nonneg_status=np.zeros((M, nb), np.int32))
+    return out, [_dp(out["fit_scale_free"]), _ip(out["fit_clamped"]), _dp(out["fit_dual"]), _ip(out["nonneg_iters"]),
+                 _ip(out["nonneg_status"])]
+
+
+def _fit_sky_args(sky_order, M, nb):
+    """A non-negative call's sky: (arrays, order for the C ABI, pointers) - sky_order None is no sky: order -1, NULL outputs"""
+    if sky_order is None:
+        return {}, -1, [None, None, None, None]
+    sky, ptrs = _fit_sky_out(M, nb, sky_terms(sky_order))
+    return sky, int(sky_order), ptrs
+
+
+def _fit_scene_inputs(stamps, places, data_fields, field_ptr):
+    """The checked host arrays of scene_fit_flux_sky and scene_fit_flux_nonneg: (stamps float32 (N, cs, cs, bands), places int32
+    (N, 2), data float64 (M, F, F, bands), field_ptr int64 (M + 1,)); field_ptr None: one field holds every stamp"""
+    stamps = np.ascontiguousarray(stamps, dtype=np.float32)
+    if stamps.ndim != 4 or stamps.shape[1] != stamps.shape[2]:
+        raise ValueError(f"expected square stamps (N, cs, cs, bands), got {stamps.shape}")
+    n, nb = stamps.shape[0], stamps.shape[3]
+    data = np.ascontiguousarray(data_fields, dtype=np.float64)
+    if data.ndim != 4 or data.shape[1] != data.shape[2] or data.shape[3] != nb:
+        raise ValueError(f"expected data fields (M, F, F, {nb}), got {data.shape}")
+    places = _i32_rows(places, "stamp placements") if n else np.zeros((0, 2), np.int32)
+    if places.shape != (n, 2):
+        raise ValueError(f"expected places ({n}, 2), got {places.shape}")
+    M = data.shape[0]
+    if field_ptr is None:
+        if M != 1:
+            raise ValueError(f"field_ptr is needed with {M} fields")
+        field_ptr = [0, n]
+    return stamps, places, data, check_field_ptr(field_ptr, M, n)
+
+
 def check_fit_weights(weight_fields, shape):
     """The C-contiguous float64 weight fields of a weighted flux fit: they have the shape of the data fields (M, F, F, bands);
     a 3-d array is taken as one field.  The values are not looked at - the kernel's comparison 0 < W < inf is the rule."""
@@ -963,22 +1012,8 @@ class Context:
         counting pixels of the field}.  A field without galaxies is still solved.  Unweighted, a non-finite pixel of a data
         field anywhere reaches every galaxy of that field through the sky: mask it with weight_fields.  The scratch of a
         field is bands x (n + q) x (n + q) doubles."""
-        stamps = np.ascontiguousarray(stamps, dtype=np.float32)
-        if stamps.ndim != 4 or stamps.shape[1] != stamps.shape[2]:
-            raise ValueError(f"expected square stamps (N, cs, cs, bands), got {stamps.shape}")
-        n, cs, nb = stamps.shape[0], stamps.shape[1], stamps.shape[3]
-        data = np.ascontiguousarray(data_fields, dtype=np.float64)
-        if data.ndim != 4 or data.shape[1] != data.shape[2] or data.shape[3] != nb:
-            raise ValueError(f"expected data fields (M, F, F, {nb}), got {data.shape}")
-        places = _i32_rows(places, "stamp placements") if n else np.zeros((0, 2), np.int32)
-        if places.shape != (n, 2):
-            raise ValueError(f"expected places ({n}, 2), got {places.shape}")
-        M = data.shape[0]
-        if field_ptr is None:
-            if M != 1:
-                raise ValueError(f"field_ptr is needed with {M} fields")
-            field_ptr = [0, n]
-        fp = check_field_ptr(field_ptr, M, n)
+        stamps, places, data, fp = _fit_scene_inputs(stamps, places, data_fields, field_ptr)
+        n, cs, nb, M = stamps.shape[0], stamps.shape[1], stamps.shape[3], data.shape[0]
         q = sky_terms(sky_order)
         par = fit_flux_params(min_pivot, scratch_bytes)
         weights = None if weight_fields is None else check_fit_weights(weight_fields, data.shape)
@@ -991,6 +1026,37 @@ class Context:
             check(lib.dv_scene_fit_flux_sky(self._h, _fp(stamps), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs, nb,
                                             _dp(data), None if weights is None else _dp(weights), M, data.shape[1], C.byref(par),
                                             int(sky_order), *ptrs, *sky_ptrs))
+        return out
+
+    def scene_fit_flux_nonneg(self, stamps, places, data_fields, field_ptr=None, sky_order=None, weight_fields=None,
+                              min_pivot: float = 1e-8, max_iter: int = 100, scratch_bytes: int = 256 << 20) -> Dict[str, np.ndarray]:
+        """scene_fit_flux / scene_fit_flux_sky with the amplitudes constrained to be >= 0 (dv_scene_fit_flux_nonneg, DESIGN.md
+        section 7u): the same quadratic minimised subject to a_i >= 0 for every galaxy, the sky (sky_order None: none; 0 a
+        constant, 1 a plane) left free, by block principal pivoting on the GPU - at most max_iter factorisations per field
+        and band.  The arguments are scene_fit_flux_sky's.  Returns the dictionary of the call without the constraint -
+        "fit_scale" is exactly +0.0 where clamped, "fit_var" NaN there; "fit_gram", "fit_proj" and "fit_status" keep the bits
+        of the unconstrained fit; the sky arrays with sky_order only, "fit_chi2" and "fit_npix" with weight_fields only - plus
+        {"fit_scale_free" (N, bands): the fit_scale of the unconstrained call, bit for bit; "fit_clamped" (N, bands) int32;
+        "fit_dual" (N, bands): the multiplier y_i >= 0 of a clamped galaxy, +0.0 of a passive one, NaN with FIT_INELIGIBLE or
+        FIT_DROPPED; per field "nonneg_iters" (M, bands) int32: the factorisations (1: the unconstrained fit was feasible and
+        every shared array has its bits; 0: no unknowns), "nonneg_status" (M, bands) int32: 0 converged, 1 max_iter reached -
+        the rows then hold the last iterate and may be negative}."""
+        stamps, places, data, fp = _fit_scene_inputs(stamps, places, data_fields, field_ptr)
+        n, cs, nb, M = stamps.shape[0], stamps.shape[1], stamps.shape[3], data.shape[0]
+        sky, order, sky_ptrs = _fit_sky_args(sky_order, M, nb)
+        par = fit_flux_params(min_pivot, scratch_bytes)
+        max_iter = nonneg_max_iter(max_iter)
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, data.shape)
+        out, ptrs = _fit_flux_out(n, nb, weights is not None)
+        if weights is None:
+            ptrs += [None, None]
+        out.update(sky)
+        nn, nn_ptrs = _fit_nonneg_out(n, M, nb)
+        out.update(nn)
+        if M:
+            check(lib.dv_scene_fit_flux_nonneg(self._h, _fp(stamps), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs,
+                                               nb, _dp(data), None if weights is None else _dp(weights), M, data.shape[1],
+                                               C.byref(par), order, max_iter, *ptrs, *sky_ptrs, *nn_ptrs))
         return out
 
     def scene_fit_flux_sky_gram(self, stamps, places, data_field, sky_order: int = 0, weight_field=None) -> Dict[str, np.ndarray]:
@@ -1693,6 +1759,49 @@ class Engine:
     def scene_fit_flux_sky(self, stamps, places, data_fields, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_fit_flux_sky on this engine's GPU context."""
         return self.ctx.scene_fit_flux_sky(stamps, places, data_fields, **kw)
+
+    def infer_fields_measure_fit_nonneg(self, fields, starts, field_ptr, places, sky_order=None, weight_fields=None, seed=0,
+                                        band: int = 2, sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200,
+                                        min_pivot: float = 1e-8, fit_max_iter: int = 100, scratch_bytes: int = 256 << 20,
+                                        return_fields=True, residual=True, mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_fit[_weighted / _sky]() with the amplitudes constrained to be >= 0
+        (dv_infer_fields_measure_fit_nonneg): sky_order None fits no sky, weight_fields None is the
+        unweighted fit, fit_max_iter caps the factorisations per field and band (max_iter is the moments').  Returns
+        infer_fields_measure's dictionary, bit for bit, plus scene_fit_flux_nonneg's, with the bits of that call on
+        infer_fields_keep's mean stamps."""
+        places = Engine._measure_places(places, return_fields, "places are needed for the flux fit, with return_fields=False too")
+        fields = _check_fields(fields)
+        if sky_order is not None:
+            sky_terms(sky_order)
+        fit_max_iter = nonneg_max_iter(fit_max_iter)
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, fields.shape)
+
+        def extras(N, nb):
+            fpar = fit_flux_params(min_pivot, scratch_bytes)
+            ff, ff_ptrs = _fit_flux_out(N, nb, weights is not None)
+            if weights is None:
+                ff_ptrs += [None, None]
+            sky, order, sky_ptrs = _fit_sky_args(sky_order, fields.shape[0], nb)
+            ff.update(sky)
+            nn, nn_ptrs = _fit_nonneg_out(N, fields.shape[0], nb)
+            ff.update(nn)
+            return [(ff, [C.byref(fpar), None if weights is None else _dp(weights), order, fit_max_iter] + ff_ptrs + sky_ptrs +
+                     nn_ptrs)]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_fit_nonneg, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
+
+    def infer_cutouts_measure_fit_nonneg(self, field, starts, places, sky_order=None, weight_field=None, seed=0,
+                                         **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_fit_nonneg() for one field (and its weight field) (F, F, bands): the field-sized results under
+        singular key names; the per-field arrays keep their leading axis of one field."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_fit_nonneg(fields, starts, fp, places, sky_order, weight_field,
+                                                                     seed=seed, **kw))
+
+    def scene_fit_flux_nonneg(self, stamps, places, data_fields, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_fit_flux_nonneg on this engine's GPU context."""
+        return self.ctx.scene_fit_flux_nonneg(stamps, places, data_fields, **kw)
 
     def infer_fields_measure_mc(self, fields, starts, field_ptr, places=None, seed=0, mc_seed=0, nsamples=100, band: int = 2,
                                 sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, return_fields=True,

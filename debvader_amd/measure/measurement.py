@@ -706,6 +706,31 @@ def fit_sky_records(sky_coef, sky_cov, sky_status, places, cutout_size, field_si
     return rec
 
 
+def _fit_host_inputs(who, stamps_mean, data_fields, weight_fields, field_ptr, catalogue, sky_sigma, ctx):
+    """What fit_fluxes_sky and fit_fluxes_nonneg check and derive before the engine call, every ValueError before any GPU work:
+    (stamps float32, data (M, F, F, bands), the checked weight fields or None, field_ptr, the stamp fluxes, the context)"""
+    data = np.asarray(data_fields, dtype=np.float64)
+    if data.ndim == 3:
+        data = data[None]
+    M = data.shape[0]
+    if weight_fields is not None:
+        if sky_sigma is not None:
+            raise ValueError(WEIGHTS_CARRY_THE_NOISE)
+        weight_fields = E.check_fit_weights(weight_fields, data.shape)
+    if data.ndim == 4 and sky_sigma is not None:
+        check_sky_sigma(sky_sigma, M, data.shape[-1])
+    stamps = np.asarray(stamps_mean, dtype=np.float32)
+    if field_ptr is None and M == 1:
+        field_ptr = [0, stamps.shape[0]]
+    if catalogue is None:
+        flux = stamps.sum(axis=(1, 2), dtype=np.float64) if stamps.ndim == 4 else None
+    else:
+        if "flux" not in catalogue.dtype.names:
+            raise ValueError(f"the catalogue lacks the column flux: {who} takes the measure_stamps recarray of the galaxies")
+        flux = np.asarray(catalogue["flux"], dtype=np.float64)
+    return stamps, data, weight_fields, field_ptr, flux, E.default_context() if ctx is None else ctx
+
+
 def fit_fluxes_sky(stamps_mean, places, data_fields, sky_order=0, weight_fields=None, field_ptr=None, catalogue=None,
                    sky_sigma=None, min_pivot=1e-8, ctx=None):
     """fit_fluxes (weight_fields None) or fit_fluxes_weighted with a local sky background fitted jointly with the amplitudes
@@ -725,28 +750,9 @@ def fit_fluxes_sky(stamps_mean, places, data_fields, sky_order=0, weight_fields=
     sums (without sky it reached only the galaxies whose stamps cover it): mask such pixels with weight_fields.
     """
     q = E.sky_terms(sky_order)                                            # (ValueError before any GPU work)
-    data = np.asarray(data_fields, dtype=np.float64)
-    if data.ndim == 3:
-        data = data[None]
-    M = data.shape[0]
+    stamps, data, weight_fields, field_ptr, flux, ctx = _fit_host_inputs("fit_fluxes_sky", stamps_mean, data_fields, weight_fields,
+                                                                         field_ptr, catalogue, sky_sigma, ctx)
     weighted = weight_fields is not None
-    if weighted:
-        if sky_sigma is not None:
-            raise ValueError(WEIGHTS_CARRY_THE_NOISE)
-        weight_fields = E.check_fit_weights(weight_fields, data.shape)
-    if data.ndim == 4 and sky_sigma is not None:
-        check_sky_sigma(sky_sigma, M, data.shape[-1])
-    stamps = np.asarray(stamps_mean, dtype=np.float32)
-    if field_ptr is None and M == 1:
-        field_ptr = [0, stamps.shape[0]]
-    if catalogue is None:
-        flux = stamps.sum(axis=(1, 2), dtype=np.float64) if stamps.ndim == 4 else None
-    else:
-        if "flux" not in catalogue.dtype.names:
-            raise ValueError("the catalogue lacks the column flux: fit_fluxes_sky takes the measure_stamps recarray of the galaxies")
-        flux = np.asarray(catalogue["flux"], dtype=np.float64)
-    if ctx is None:
-        ctx = E.default_context()
     out = ctx.scene_fit_flux_sky(stamps, places, data, field_ptr=field_ptr, sky_order=sky_order, weight_fields=weight_fields,
                                  min_pivot=min_pivot)
     if weighted:
@@ -758,6 +764,75 @@ def fit_fluxes_sky(stamps_mean, places, data_fields, sky_order=0, weight_fields=
                           field_ptr=field_ptr, sky_sigma=sky_sigma, weighted=weighted)
     assert out["sky_coef"].shape[2] == q
     return _join_records(fit, sky), {k: out[k] for k in E.FIT_SKY_KEYS}
+
+
+def fit_nonneg_dtype(nb_of_bands):
+    """The four columns a non-negative flux fit adds per galaxy."""
+    nb = int(nb_of_bands)
+    return [("fit_scale_free", "<f8", (nb,)), ("flux_fit_free", "<f8", (nb,)), ("fit_clamped", "<i4", (nb,)),
+            ("fit_dual", "<f8", (nb,))]
+
+
+def fit_nonneg_records(fit_scale_free, fit_clamped, fit_dual, flux):
+    """The recarray of fit_nonneg_dtype from the three per-galaxy arrays of scene_fit_flux_nonneg, all (N, bands), and the
+    stamp fluxes `flux` (N, bands): fit_scale_free, the amplitude of the fit without the constraint (negative where the
+    constraint bites); flux_fit_free = fit_scale_free * flux; fit_clamped, 1 where the galaxy was clamped to zero flux;
+    fit_dual, the multiplier of a clamped galaxy - how much the residual sum of squares grows per unit of amplitude given
+    back to it, halved -, +0.0 of a fitted one, NaN where fit_status is not 0."""
+    free = np.asarray(fit_scale_free, dtype=np.float64)
+    if free.ndim != 2:
+        raise ValueError(f"expected fit_scale_free (N, bands), got {free.shape}")
+    n, nb = free.shape
+    flux = np.asarray(flux, dtype=np.float64)
+    if flux.shape != (n, nb):
+        raise ValueError(f"expected flux ({n}, {nb}), got {flux.shape}")
+    rec = np.recarray((n,), dtype=fit_nonneg_dtype(nb))
+    rec["fit_scale_free"] = free
+    rec["fit_clamped"] = np.asarray(fit_clamped, dtype=np.int32).reshape(n, nb)
+    rec["fit_dual"] = np.asarray(fit_dual, dtype=np.float64).reshape(n, nb)
+    with np.errstate(all="ignore"):
+        rec["flux_fit_free"] = free * flux
+    return rec
+
+
+def fit_fluxes_nonneg(stamps_mean, places, data_fields, sky_order=None, weight_fields=None, field_ptr=None, catalogue=None,
+                      sky_sigma=None, min_pivot=1e-8, max_iter=100, ctx=None):
+    """fit_fluxes, fit_fluxes_weighted or fit_fluxes_sky with the amplitudes constrained to be >= 0, as
+    scarlet and the Tractor fit them.  On a noisy field a spurious or very faint detection that overlaps a brighter neighbour
+    has about an even chance of a negative amplitude in the linear fit, and its neighbours absorb the light it "gives back";
+    clipping afterwards leaves them biased.  Here the same quadratic is minimised subject to a_i >= 0, the sky left free.
+
+    parameters: those of fit_fluxes_sky, and
+        sky_order: None fits no sky (the default); 0 or 1 as in fit_fluxes_sky
+        max_iter: the cap on the factorisations per field and band, >= 1.  The iteration ends by itself after a handful; a
+            field and band that reaches the cap reports nonneg_status 1, and its rows - the last iterate - may be negative
+    returns (catalogue, per_field): the np.recarray of the call without the constraint - fit_fluxes, with weight_fields
+    fit_fluxes_weighted, with sky_order plus fit_sky_dtype - where fit_scale is exactly 0 for a clamped galaxy and fit_var,
+    fit_scale_err, flux_fit_err and fit_independence are NaN there, then fit_nonneg_dtype (fit_nonneg_records); and the
+    dictionary of the per-field arrays nonneg_iters and nonneg_status (M, bands) and, with sky_order, those of fit_fluxes_sky.
+    A field and band whose unconstrained fit has no negative amplitude has nonneg_iters 1 and the values of the call without
+    the constraint, bit for bit.
+    """
+    if sky_order is not None:
+        E.sky_terms(sky_order)                                            # (ValueError before any GPU work)
+    E.nonneg_max_iter(max_iter)
+    stamps, data, weight_fields, field_ptr, flux, ctx = _fit_host_inputs("fit_fluxes_nonneg", stamps_mean, data_fields,
+                                                                         weight_fields, field_ptr, catalogue, sky_sigma, ctx)
+    weighted = weight_fields is not None
+    out = ctx.scene_fit_flux_nonneg(stamps, places, data, field_ptr=field_ptr, sky_order=sky_order, weight_fields=weight_fields,
+                                    min_pivot=min_pivot, max_iter=max_iter)
+    if weighted:
+        recs = [fit_flux_records(*(out[k] for k in E.FIT_FLUX_KEYS), flux, field_ptr=field_ptr, fit_chi2=out["fit_chi2"],
+                                 fit_npix=out["fit_npix"])]
+    else:
+        recs = [fit_flux_records(*(out[k] for k in E.FIT_FLUX_KEYS), flux, sky_sigma=sky_sigma, field_ptr=field_ptr)]
+    per_field = {k: out[k] for k in E.FIT_NONNEG_FIELD_KEYS}
+    if sky_order is not None:
+        recs.append(fit_sky_records(out["sky_coef"], out["sky_cov"], out["sky_status"], places, stamps.shape[1], data.shape[1],
+                                    field_ptr=field_ptr, sky_sigma=sky_sigma, weighted=weighted))
+        per_field.update({k: out[k] for k in E.FIT_SKY_KEYS})
+    recs.append(fit_nonneg_records(*(out[k] for k in E.FIT_NONNEG_KEYS), flux))
+    return _join_records(*recs), per_field
 
 
 def measure_blendedness(stamps_mean, catalogue, places, model_fields, data_fields=None, field_ptr=None, band=2, ctx=None):

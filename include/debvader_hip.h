@@ -770,6 +770,40 @@ int dv_infer_fields_measure_fit_sky(dv_model* m, const double* fields, int32_t M
                                     int32_t sky_order, double* fit_scale, double* fit_var, double* fit_gram, double* fit_proj,
                                     int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, double* sky_coef, double* sky_cov,
                                     int32_t* sky_status, int64_t* sky_npix);
+/* The non-negative fit: the same quadratic minimised subject to a_i >= 0 for every galaxy, the sky terms
+ * left free - what scarlet and the Tractor solve; clipping the negative amplitudes of the linear fit afterwards leaves the
+ * neighbours biased.  sky_order -1: no sky, and sky_coef, sky_cov, sky_status and sky_npix must all be NULL; 0 / 1 as above.
+ * weight_fields may be NULL, and fit_chi2 and fit_npix are NULL exactly then.  Iteration 1 is the fit above: it fixes
+ * fit_status, the dropped set (amplitude 1), h' and the unconstrained amplitudes.  With Z the clamped galaxies (empty at
+ * first), p = 3 and best = n + 1, iteration t = 1, 2, ...: factorise G over the kept unknowns not in Z (no pivot test after
+ * iteration 1) and solve for a, a_i = +0.0 in Z; y_i = (sum_j G_ij a_j) - h'_i for i in Z, j ascending over the kept unknowns
+ * not in Z, sky terms included; V = {kept galaxies not in Z with a_i < 0} + {i in Z with y_i < 0}, strict; V empty: converged.
+ * Otherwise, |V| < best: best = |V|, p = 3, every member of V changes sides; else p > 0: p -= 1, every member changes sides;
+ * else the largest index of V alone does.  After max_iter (>= 1) iterations with V not empty the rows hold the last solved
+ * iterate - negative amplitudes may remain - and nonneg_status is 1.  fit_var, sky_cov and fit_chi2 come from the last
+ * iteration; fit_var is NaN for a clamped galaxy.  Outputs: those of the sky calls - fit_scale exactly +0.0 where clamped;
+ * fit_gram, fit_proj and fit_status with the bits of the unconstrained fit - then fit_scale_free [N][nb], the fit_scale of the
+ * unconstrained call, bit for bit; fit_clamped [N][nb] int32, 0 or 1; fit_dual [N][nb], y_i where clamped, +0.0 where
+ * passive, NaN for status 4 or 5; and per field nonneg_iters [M][nb] int32, the factorisations (1: the unconstrained fit was
+ * feasible, and every output shared with the calls above has their bits; 0: no unknowns), and nonneg_status [M][nb] int32, 0
+ * converged, 1 max_iter reached.  Both calls refuse, before any GPU work (DV_E_INVALID, the engine stays usable), what the sky
+ * and weighted calls refuse, max_iter < 1, a missing new output and sky outputs given with sky_order -1. */
+int dv_scene_fit_flux_nonneg(dv_ctx* ctx, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                             int32_t cs, int32_t nb, const double* data_fields, const double* weight_fields, int32_t M, int32_t F,
+                             const dv_fit_flux_params* params, int32_t sky_order, int32_t max_iter, double* fit_scale,
+                             double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status, double* fit_chi2,
+                             int32_t* fit_npix, double* sky_coef, double* sky_cov, int32_t* sky_status, int64_t* sky_npix,
+                             double* fit_scale_free, int32_t* fit_clamped, double* fit_dual, int32_t* nonneg_iters,
+                             int32_t* nonneg_status);
+int dv_infer_fields_measure_fit_nonneg(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                       const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                       const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                       double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                       int32_t* iters, int32_t* status, const dv_fit_flux_params* fit, const double* weight_fields,
+                                       int32_t sky_order, int32_t max_iter, double* fit_scale, double* fit_var, double* fit_gram,
+                                       double* fit_proj, int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, double* sky_coef,
+                                       double* sky_cov, int32_t* sky_status, int64_t* sky_npix, double* fit_scale_free,
+                                       int32_t* fit_clamped, double* fit_dual, int32_t* nonneg_iters, int32_t* nonneg_status);
 
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)

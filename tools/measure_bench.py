@@ -107,6 +107,20 @@ fit, in the same protocol, four legs alternating -
 
 With --profile-one: warm up, one fp32 call (d), exit.
 
+--fit-nonneg: what the constraint a_i >= 0 adds to the flux fit, in the same protocol, four legs
+alternating -
+
+    (a) catalogue+fit-flux            :  leg (a) of --fit-sky, to be compared with it on the commit before: without fit_nonneg
+                                         nothing new is allocated or launched
+    (b) catalogue+fit-flux+nonneg     :  the same with fit_nonneg=True: the active-set kernel in place of the solve
+    (c) catalogue+fit-flux+sky        :  leg (b) of --fit-sky 1, to be compared with it likewise
+    (d) catalogue+fit-flux+sky+nonneg :  the same with fit_nonneg=True
+
+    python tools/measure_bench.py --fit-nonneg [--fields 1024] [--size 259] [--repeat 5]
+
+It also prints how many (field, band) systems took 0, 1, 2, ... factorisations (nonneg_iters) in legs (b) and (d), and how many
+galaxy-bands were clamped.  With --profile-one: warm up, one fp32 call (d), exit.
+
 The cost is reported, not gated.
 """
 import argparse
@@ -260,7 +274,7 @@ def main_fit_flux(a):
     fields = np.ascontiguousarray(base[np.arange(M) % 16])
     quiet = io.StringIO()
     result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "fit_flux": True, "fit_weights": bool(a.fit_weights),
-              "fit_sky": a.fit_sky}
+              "fit_sky": a.fit_sky, "fit_nonneg": bool(a.fit_nonneg)}
     weights = None
     if a.fit_weights or a.fit_sky is not None:
         w16 = rng.uniform(0.25, 4.0, size=base.shape)
@@ -274,15 +288,23 @@ def main_fit_flux(a):
             dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
             print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections, at most {max(len(d) for d in dists)} "
                   f"per field; max_batch {a.max_batch}")
-        seen = []
+        seen, nonneg = [], {}
 
         def with_fit(**kw):
-            res = DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=True, measure=True, return_fields=False,
-                                                                fit_flux=True, **kw)
+            batch = DeblendFieldBatch(net, fields)
+            res = batch.deblend_fields(dists, on_device=True, measure=True, return_fields=False, fit_flux=True, **kw)
             seen[:] = [np.concatenate([r["fit_status"] for r in res]), np.concatenate([r["fit_independence"] for r in res])]
+            if batch.nonneg_fit is not None:      # per leg (keyed by its sky): the iterations and the clamped galaxy-bands
+                nonneg[kw.get("fit_sky")] = (np.bincount(batch.nonneg_fit["nonneg_iters"].ravel()).tolist(),
+                                             int(batch.nonneg_fit["nonneg_status"].sum()),
+                                             int(sum(r["fit_clamped"].sum() for r in res)), int(seen[0].size))
             return sum(len(r) for r in res)
 
-        if a.fit_sky is not None:
+        if a.fit_nonneg:
+            legs = {"catalogue+fit-flux": with_fit, "catalogue+fit-flux+nonneg": lambda: with_fit(fit_nonneg=True),
+                    "catalogue+fit-flux+sky": lambda: with_fit(fit_sky=1),
+                    "catalogue+fit-flux+sky+nonneg": lambda: with_fit(fit_sky=1, fit_nonneg=True)}
+        elif a.fit_sky is not None:
             legs = {"catalogue+fit-flux": with_fit, "catalogue+fit-flux+sky": lambda: with_fit(fit_sky=a.fit_sky),
                     "catalogue+fit-flux+weights": lambda: with_fit(fit_weights=weights),
                     "catalogue+fit-flux+weights+sky": lambda: with_fit(fit_weights=weights, fit_sky=a.fit_sky)}
@@ -321,6 +343,10 @@ def main_fit_flux(a):
                   f"{1e6 * (tf - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times[first]):.3f} and "
                   f"{spread(times[second]):.3f}); fit_status 0 .. 5 over galaxies x bands: {counts}; median "
                   f"fit_independence {float(np.median(ind)) if ind.size else float('nan'):.3f}")
+        for sky, (iters, capped, clamped, total) in nonneg.items():
+            print(f"{dtype} fit_nonneg{'' if sky is None else f' with fit_sky={sky}'}: (field, band) systems by nonneg_iters 0, 1, 2, ... "
+                  f"{iters}; {capped} reached max_iter; {clamped} of {total} galaxy-bands clamped")
+            result[dtype]["nonneg_iters" + ("" if sky is None else "_sky")] = iters
         net._core.engine.close()
     print(json.dumps(result))
 
@@ -480,8 +506,9 @@ def main():
     ap.add_argument("--fit-flux", action="store_true")
     ap.add_argument("--fit-weights", action="store_true")
     ap.add_argument("--fit-sky", type=int, choices=(0, 1), default=None, metavar="ORDER")
+    ap.add_argument("--fit-nonneg", action="store_true")
     a = ap.parse_args()
-    if a.fit_flux or a.fit_weights or a.fit_sky is not None:
+    if a.fit_flux or a.fit_weights or a.fit_sky is not None or a.fit_nonneg:
         return main_fit_flux(a)
     if a.aperture_data:
         return main_apertures(a, data=True)
