@@ -487,6 +487,10 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
                     int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve = true,
                     const double* weight_dev = nullptr, const FitFluxSky& sky = FitFluxSky{},
                     const FitFluxNonneg& nn = FitFluxNonneg{});
+// the regrouping of a resident field set's rows for the joint fit of all passes: destination row d takes the stamp,
+// the placement and the field of source row rowmap_dev[d]; n destination rows, every rowmap entry a row the source holds
+int launch_fitflux_regroup(const int* rowmap_dev, const float* src, const int* src_places, const int* src_field, int64_t n, int cs,
+                           int nb, float* dst, int* dst_places, int* dst_field, hipStream_t s);
 int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                    const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
                    hipStream_t s, const double* weight_h = nullptr, const char* who = "dv_scene_fit_flux", int sky_order = -1,

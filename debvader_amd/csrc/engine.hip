@@ -614,6 +614,28 @@ struct dv_field_set {
     rcap = cap;
     return dv::OK;
   }
+  // the stamp store of the joint flux fit (dv_field_set_keep_stamps): with `keep` on, a pass that keeps resident
+  // rows also keeps its float32 mean stamps, each at its resident row number, and the host remembers the pass's field_ptr and
+  // placements - what dv_field_set_fit_flux regroups field by field
+  bool keep = false;
+  dv::DevBuf<float> rstamps;                     // [scap][cs][cs][nb]
+  size_t scap = 0;
+  std::vector<std::vector<int>> pass_fptr;       // per kept pass: the first row of every field, counted from the pass's row 0
+  std::vector<int32_t> places_h;                 // [nrows][2]: the host's copy of rplaces
+  // room for the stamps of `need` resident rows of `stamp` floats: grows like rows_reserve, the kept stamps copied over on s
+  int stamps_reserve(size_t need, size_t stamp, hipStream_t s) {
+    if (need <= scap) return dv::OK;
+    const size_t cap = std::max<size_t>({need, 2 * scap, 1024});
+    dv::DevBuf<float> st;
+    DV_TRY(st.alloc(cap * stamp));
+    if (nrows > 0) {
+      DV_HIP(hipMemcpyAsync(st, rstamps, nrows * stamp * sizeof(float), hipMemcpyDeviceToDevice, s));
+      DV_HIP(hipStreamSynchronize(s));
+    }
+    rstamps = std::move(st);
+    scap = cap;
+    return dv::OK;
+  }
 };
 
 static void field_set_release(dv_field_set* fs) {
@@ -622,6 +644,10 @@ static void field_set_release(dv_field_set* fs) {
     b->reset();
   for (dv::DevBuf<int>* b : {&fs->rstatus, &fs->rplaces, &fs->rfield, &fs->citers, &fs->cnpix}) b->reset();
   fs->nrows = fs->rcap = 0;
+  fs->rstamps.reset();
+  fs->scap = 0;
+  fs->pass_fptr.clear();
+  fs->places_h.clear();
   fs->tab = dv::StampTables();
   fs->open = false;
 }
@@ -6213,6 +6239,11 @@ static int field_set_pass_impl(dv_field_set* fs, const char* who, const int32_t*
       DV_TRY(fs->cnpix.ensure(n));
       j.bl.blend = fs->cblend;
       j.bl.npix = fs->cnpix;
+      if (fs->keep) {                                  // (7v: the pass's mean stamps, behind every chunk's measurement)
+        const size_t stamp = (size_t)m->A.H * m->A.H * nb;
+        DV_TRY(fs->stamps_reserve(row0 + n, stamp, s));
+        j.ff.store = fs->rstamps.get() + row0 * stamp;
+      }
     }
   }
   DV_TRY(infer_pipelined(m, j));
@@ -6240,6 +6271,10 @@ static int field_set_pass_impl(dv_field_set* fs, const char* who, const int32_t*
   for (int f = 0; f < M; ++f)
     if (fptr32[f + 1] > fptr32[f]) field_mse[f] = fm[f];
   if (bo) fs->nrows = row0 + n;
+  if (bo && fs->keep) {
+    fs->pass_fptr.push_back(fptr32);
+    fs->places_h.insert(fs->places_h.end(), places, places + 2 * n);
+  }
   drain.dismiss();
   return prof_flush(m);
 }
@@ -6301,6 +6336,208 @@ int dv_field_set_blend(dv_field_set* fs, int32_t band, int64_t n_expected, doubl
   DV_HIP(hipMemcpyAsync(sums, fs->rsums, n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
   DV_HIP(hipStreamSynchronize(s));
   drain.dismiss();
+  return DV_OK;
+}
+
+// ---- the joint flux fit of all passes of the iterative loop ------------------------------------------------------
+int dv_field_set_keep_stamps(dv_field_set* fs, int32_t on) {
+  const char* who = "dv_field_set_keep_stamps";
+  DV_TRY(field_set_live(fs, who));
+  if (fs->nrows > 0) {
+    set_error("%s: the set holds %zu resident rows whose stamps %s: the switch is set before the first measured pass", who,
+              fs->nrows, fs->keep ? "are kept" : "are gone");
+    return DV_E_STATE;
+  }
+  fs->keep = on != 0;
+  return DV_OK;
+}
+
+int dv_field_set_fit_flux(dv_field_set* fs, int64_t n_expected, const double* data, const double* weight, int32_t sky_order,
+                          int32_t nonneg, const dv_fit_flux_params* params, int32_t nonneg_max_iter, double* fit_scale,
+                          double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status, double* fit_chi2,
+                          int32_t* fit_npix, double* sky_coef, double* sky_cov, int32_t* sky_status, int64_t* sky_npix,
+                          double* fit_scale_free, int32_t* fit_clamped, double* fit_dual, int32_t* nonneg_iters,
+                          int32_t* nonneg_status) {
+  const char* who = "dv_field_set_fit_flux";
+  DV_TRY(field_set_live(fs, who));
+  if (!fs->keep) {
+    set_error("%s: the set keeps no stamps: dv_field_set_keep_stamps(set, 1) comes before the first measured pass", who);
+    return DV_E_STATE;
+  }
+  if (!params) {
+    set_error("%s: params must be given", who);
+    return DV_E_INVALID;
+  }
+  if (n_expected != (int64_t)fs->nrows) {
+    set_error("%s: %ld rows expected, the set holds %zu resident rows", who, (long)n_expected, fs->nrows);
+    return DV_E_INVALID;
+  }
+  if (sky_order < -1 || sky_order > 1) {
+    set_error("%s: sky_order must be -1 (no sky), 0 (a constant) or 1 (a plane), got %d", who, sky_order);
+    return DV_E_INVALID;
+  }
+  dv_model* m = fs->m;
+  const int M = fs->M, F = fs->F, nb = fs->nb, cs = m->A.H;
+  const int64_t N = (int64_t)fs->nrows;
+  const bool weighted = weight != nullptr, with_sky = sky_order >= 0, nn_on = nonneg != 0;
+  const FitFluxParams par{params->min_pivot, params->scratch_bytes};
+  DV_TRY(fitflux_check(who, cs, nb, F, par));
+  if (nn_on && nonneg_max_iter < 1) {
+    set_error("%s: max_iter must be at least 1 (got %d)", who, nonneg_max_iter);
+    return DV_E_INVALID;
+  }
+  // every output the chosen variant produces, and no other
+  if (N > 0 && (!fit_scale || !fit_var || !fit_gram || !fit_proj || !fit_status)) {
+    set_error("%s: fit_scale, fit_var, fit_gram, fit_proj and fit_status must all be given", who);
+    return DV_E_INVALID;
+  }
+  if (weighted ? (N > 0 && (!fit_chi2 || !fit_npix)) : (fit_chi2 || fit_npix)) {
+    set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: both given with weight, both NULL without", who);
+    return DV_E_INVALID;
+  }
+  if (with_sky ? (!sky_coef || !sky_cov || !sky_status || !sky_npix) : (sky_coef || sky_cov || sky_status || sky_npix)) {
+    set_error("%s: sky_coef, sky_cov, sky_status and sky_npix are the outputs of the fit with sky: all given with sky_order 0 or "
+              "1, all NULL with -1", who);
+    return DV_E_INVALID;
+  }
+  if (nn_on ? (!nonneg_iters || !nonneg_status || (N > 0 && (!fit_scale_free || !fit_clamped || !fit_dual)))
+            : (fit_scale_free || fit_clamped || fit_dual || nonneg_iters || nonneg_status)) {
+    set_error("%s: fit_scale_free, fit_clamped, fit_dual, nonneg_iters and nonneg_status are the outputs of the non-negative fit: "
+              "all given with nonneg, all NULL without", who);
+    return DV_E_INVALID;
+  }
+  if (!data && fs->cumulative) {
+    set_error("%s: a cumulative set keeps no copy of the fields as uploaded (every pass subtracts from the working residual): "
+              "data must be given", who);
+    return DV_E_INVALID;
+  }
+  // the joint field_ptr of all passes and rowmap[dst] = resident row, field-major: pass ascending inside a field, then the
+  // in-pass order (of two models that cannot be told apart the copy from the later pass is the one dropped)
+  std::vector<int64_t> fp64((size_t)M + 1, 0);
+  for (int f = 0; f < M; ++f) {
+    int64_t n = 0;
+    for (const std::vector<int>& p : fs->pass_fptr) n += p[(size_t)f + 1] - p[(size_t)f];
+    fp64[(size_t)f + 1] = fp64[(size_t)f] + n;
+  }
+  if (fp64[(size_t)M] != N) {                           // (cannot happen: both count the passes that kept rows)
+    set_error("%s: the passes on record hold %ld rows, the set %zu", who, (long)fp64[(size_t)M], fs->nrows);
+    return DV_E_STATE;
+  }
+  FitFluxPlan plan;
+  DV_TRY(fitflux_plan(who, fp64.data(), M, nb, par, &plan, sky_order, F));
+  if (N == 0) return DV_OK;
+  std::vector<int> rowmap((size_t)N), fptr32((size_t)M + 1);
+  std::vector<int32_t> places_h((size_t)N * 2);
+  {
+    size_t d = 0;
+    for (int f = 0; f < M; ++f) {
+      fptr32[(size_t)f] = (int)fp64[(size_t)f];
+      size_t base = 0;
+      for (const std::vector<int>& p : fs->pass_fptr) {
+        for (int i = p[(size_t)f]; i < p[(size_t)f + 1]; ++i) rowmap[d++] = (int)(base + (size_t)i);
+        base += (size_t)p[(size_t)M];
+      }
+    }
+    fptr32[(size_t)M] = (int)N;
+    for (size_t k = 0; k < (size_t)N; ++k) {
+      places_h[2 * k] = fs->places_h[2 * (size_t)rowmap[k]];
+      places_h[2 * k + 1] = fs->places_h[2 * (size_t)rowmap[k] + 1];
+    }
+  }
+  // host staging in regrouped order; the outputs leave in resident-row order through rowmap
+  const size_t nn = (size_t)N * nb, stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
+  std::vector<double> h_scale(nn), h_var(nn), h_gram(nn), h_proj(nn), h_chi2(weighted ? nn : 0), h_free(nn_on ? nn : 0),
+      h_dual(nn_on ? nn : 0);
+  std::vector<int> h_status(nn), h_npix(weighted ? nn : 0), h_clamped(nn_on ? nn : 0);
+  FitFluxRows stage{h_scale.data(), h_var.data(), h_gram.data(), h_proj.data(), h_status.data()};
+  if (weighted) stage.chi2 = h_chi2.data(), stage.npix = h_npix.data();
+  if (nn_on) stage.scale_free = h_free.data(), stage.clamped = h_clamped.data(), stage.dual = h_dual.data();
+  FitFluxRows d{};
+  Rows out;
+  fitflux_columns(out, d, stage, nb, weighted, nn_on);
+  const int q = plan.q;
+  DV_HIP(hipSetDevice(m->ctx->device));
+  // what the call holds beside the set: the regrouped copy with its tables, the rows, the dense scratch, the per-field outputs
+  // and the fields it uploads
+  const size_t need = (size_t)N * (stamp * sizeof(float) + 4 * sizeof(int) + out.bytes()) + ((size_t)M + 1) * sizeof(int) +
+                      FitFluxWork::bytes(plan, (size_t)M, weighted) + FitFluxStage::sky_bytes(q, (size_t)M, nb) +
+                      (nn_on ? 2 * (size_t)M * nb * sizeof(int) : 0) + ((data ? 1 : 0) + (weighted ? 1 : 0)) * M * felems * sizeof(double);
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  if (need > free_b / 10 * 9) {
+    set_error("%s: the regrouped stamps of %ld rows, the dense scratch and the uploaded fields need %zu bytes of device memory, "
+              "%zu are free", who, (long)N, need, free_b);
+    return DV_E_NOMEM;
+  }
+  hipStream_t s = m->ctx->stream;
+  DevBuf<float> stamps;
+  DevBuf<int> places, sf, fptr, rmap;
+  DevBuf<double> data_d, weight_d;
+  FitFluxWork work;
+  DV_TRY(stamps.alloc((size_t)N * stamp));
+  DV_TRY(places.alloc((size_t)N * 2));
+  DV_TRY(sf.alloc((size_t)N));
+  DV_TRY(rmap.alloc((size_t)N));
+  DV_TRY(fptr.alloc((size_t)M + 1));
+  DV_TRY(work.alloc(plan, M, weighted));
+  DV_TRY(out.alloc(N));
+  DevBuf<double> sky_coef_d, sky_cov_d;
+  DevBuf<int> sky_status_d, nn_iters_d, nn_status_d;
+  DevBuf<long long> sky_npix_d;
+  FitFluxSky sky_d{};
+  if (q) {
+    DV_TRY(sky_coef_d.alloc((size_t)M * nb * q));
+    DV_TRY(sky_cov_d.alloc((size_t)M * nb * q * q));
+    DV_TRY(sky_status_d.alloc((size_t)M * nb * q));
+    DV_TRY(sky_npix_d.alloc((size_t)M * nb));
+    sky_d = FitFluxSky{q, sky_coef_d.get(), sky_cov_d.get(), sky_status_d.get(), sky_npix_d.get()};
+  }
+  FitFluxNonneg nn_d{};
+  if (nn_on) {
+    DV_TRY(nn_iters_d.alloc((size_t)M * nb));
+    DV_TRY(nn_status_d.alloc((size_t)M * nb));
+    nn_d = FitFluxNonneg{true, nonneg_max_iter, nn_iters_d.get(), nn_status_d.get()};
+  }
+  StreamDrain drain(s);                                // a failure waits for the stream before the call's buffers go
+  if (data) {
+    DV_TRY(data_d.alloc((size_t)M * felems));
+    DV_HIP(hipMemcpyAsync(data_d, data, (size_t)M * felems * sizeof(double), hipMemcpyHostToDevice, s));
+  }
+  if (weighted) {
+    DV_TRY(weight_d.alloc((size_t)M * felems));
+    DV_HIP(hipMemcpyAsync(weight_d, weight, (size_t)M * felems * sizeof(double), hipMemcpyHostToDevice, s));
+  }
+  DV_HIP(hipMemcpyAsync(rmap, rowmap.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(fptr, fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_TRY(launch_fitflux_regroup(rmap, fs->rstamps, fs->rplaces, fs->rfield, N, cs, nb, stamps, places, sf, s));
+  DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data ? data_d.get() : fs->base.get(), 0, places_h.data(), fptr32.data(), 0,
+                         M - 1, cs, nb, F, par, work, d, s, true, weighted ? weight_d.get() : nullptr, sky_d, nn_d));
+  DV_TRY(out.download(0, N, s));
+  if (nn_on) {
+    DV_HIP(hipMemcpyAsync(nonneg_iters, nn_iters_d, (size_t)M * nb * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(nonneg_status, nn_status_d, (size_t)M * nb * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+  if (q) {
+    DV_HIP(hipMemcpyAsync(sky_coef, sky_coef_d, (size_t)M * nb * q * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(sky_cov, sky_cov_d, (size_t)M * nb * q * q * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(sky_status, sky_status_d, (size_t)M * nb * q * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(sky_npix, sky_npix_d, (size_t)M * nb * sizeof(long long), hipMemcpyDeviceToHost, s));
+  }
+  DV_HIP(hipStreamSynchronize(s));
+  drain.dismiss();
+  // regrouped row k is resident row rowmap[k]
+  for (size_t k = 0; k < (size_t)N; ++k) {
+    const size_t r = (size_t)rowmap[k] * nb, o = k * nb;
+    for (int b = 0; b < nb; ++b) {
+      fit_scale[r + b] = h_scale[o + b];
+      fit_var[r + b] = h_var[o + b];
+      fit_gram[r + b] = h_gram[o + b];
+      fit_proj[r + b] = h_proj[o + b];
+      fit_status[r + b] = h_status[o + b];
+      if (weighted) fit_chi2[r + b] = h_chi2[o + b], fit_npix[r + b] = h_npix[o + b];
+      if (nn_on) fit_scale_free[r + b] = h_free[o + b], fit_clamped[r + b] = h_clamped[o + b], fit_dual[r + b] = h_dual[o + b];
+    }
+  }
   return DV_OK;
 }
 

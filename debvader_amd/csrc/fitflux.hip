@@ -947,7 +947,42 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_chi2_kernel(const int* __r
     }
   }
 }
+
+// The joint fit of a resident field set: the set holds the rows of its passes pass-major, the kernels above take
+// a field's rows contiguously.  One 256-thread workgroup per destination row d copies row rowmap[d] of the stamp store, its
+// placement and its field: cs cs nb floats, coalesced, by 8-byte copies where both addresses allow (the address decides, as in
+// ff_load) and 4-byte copies otherwise.  64-bit offsets; every destination element is written by one thread.
+__global__ __launch_bounds__(MS_THREADS) void fitflux_regroup_kernel(const int* __restrict__ rowmap, const float* __restrict__ src,
+                                                                     const int* __restrict__ src_places,
+                                                                     const int* __restrict__ src_field, int cs, int nb,
+                                                                     float* __restrict__ dst, int* __restrict__ dst_places,
+                                                                     int* __restrict__ dst_field) {
+  const long long d = blockIdx.x, r = rowmap[d];
+  const long long stamp = (long long)cs * cs * nb;
+  const float* __restrict__ p = src + r * stamp;
+  float* __restrict__ q = dst + d * stamp;
+  const int tid = threadIdx.x;
+  if ((((unsigned long long)p | (unsigned long long)q) & 7ull) == 0) {
+    const long long half = stamp >> 1;
+    for (long long i = tid; i < half; i += MS_THREADS)
+      reinterpret_cast<float2*>(q)[i] = reinterpret_cast<const float2*>(p)[i];
+    if ((stamp & 1) && tid == 0) q[stamp - 1] = p[stamp - 1];
+  } else {
+    for (long long i = tid; i < stamp; i += MS_THREADS) q[i] = p[i];
+  }
+  if (tid < 2) dst_places[2 * d + tid] = src_places[2 * r + tid];
+  if (tid == 2) dst_field[d] = src_field[r];
+}
 }  // namespace
+
+int launch_fitflux_regroup(const int* rowmap_dev, const float* src, const int* src_places, const int* src_field, int64_t n, int cs,
+                           int nb, float* dst, int* dst_places, int* dst_field, hipStream_t s) {
+  if (n <= 0) return OK;
+  hipLaunchKernelGGL(fitflux_regroup_kernel, dim3((unsigned)n), dim3(MS_THREADS), 0, s, rowmap_dev, src, src_places, src_field, cs,
+                     nb, dst, dst_places, dst_field);
+  DV_HIP(hipGetLastError());
+  return OK;
+}
 
 // the refusals that need no table, before any GPU work
 int fitflux_check(const char* who, int cs, int nb, int F, const FitFluxParams& p) {

@@ -216,6 +216,9 @@ class IterativeDeblendFieldBatch:
         self.mse = [[] for _ in range(self.nb_of_fields)]
         self._fields = None
         self._no_fields = False
+        self.sky_fit = None             # iterative_catalogue(fit_flux=True, fit_sky=...): the per-field arrays sky_coef, sky_cov,
+                                        # sky_status, sky_npix of the joint fit, as DeblendFieldBatch holds them
+        self.nonneg_fit = None          # ... (fit_nonneg=True): nonneg_iters and nonneg_status (M, bands)
 
     def _records(self, kept, dd, mse_center, passed, offset, iteration):
         n = len(kept)
@@ -281,7 +284,8 @@ class IterativeDeblendFieldBatch:
 
     def iterative_catalogue(self, mse_criterion=100.0, mode="reference", max_iterations=None, measure=False,
                             blendedness=False, return_fields=True, band=2, sigma0=3.0, tol=1e-10, max_iter=200,
-                            match_radius=2.0):
+                            match_radius=2.0, fit_flux=False, fit_weights=None, fit_sky=None, fit_nonneg=False,
+                            sky_sigma=None, min_pivot=1e-8):
         """iterative_deblending() with a catalogue measured on the GPU: the same loop, the same
         list of M recarrays (kept in self.res_deblend), self.mse and fields, and with every argument behind the first
         three left at its default the same calls.  The arguments are a method of their own because the parameter list of
@@ -304,6 +308,18 @@ class IterativeDeblendFieldBatch:
             NaN on every row.
         return_fields=False: the three field-sized downloads at the end of the loop are skipped;
             get_residual_fields() and get_predicted_fields() then raise.
+        fit_flux=True (needs measure=True): after the last pass ONE joint flux fit per field and band over the galaxies of
+            EVERY pass, against the fields as given, on mean stamps that stayed on the GPU (FieldSet.keep_stamps and
+            FieldSet.fit_flux): the model a bright galaxy got in pass 0 from a field that still held an
+            undetected neighbour is refitted together with that neighbour's model of pass 1.  Every pass then takes the
+            child sums, with or without blendedness.  Inside a field the unknowns stand in recarray order, so of two models
+            that cannot be told apart - in mode="reference" a galaxy deblended again in a later pass - the later copy is
+            dropped (fit_status 5, fit_scale 1) and the earlier detection is fitted.  The recarrays gain, behind the
+            blendedness and residual columns, measurement.fit_flux_dtype(bands), with flux_fit = fit_scale * flux of the
+            row's own pass.  fit_weights, fit_sky, fit_nonneg, sky_sigma and min_pivot mean what they mean in
+            DeblendFieldBatch.deblend_fields and need fit_flux=True: fit_weights (M, F, F, bands) adds fit_chi2 and fit_npix
+            and is refused beside sky_sigma, fit_sky = 0 or 1 adds measurement.fit_sky_dtype(bands) and self.sky_fit,
+            fit_nonneg=True adds measurement.fit_nonneg_dtype(bands) and self.nonneg_fit - in that order.
 
         mse_criterion, mode, max_iterations: as in iterative_deblending."""
         if mode not in ("reference", "cumulative"):
@@ -319,6 +335,30 @@ class IterativeDeblendFieldBatch:
         if measure and not (np.isfinite(match_radius) and match_radius >= 0):
             raise ValueError(f"match_radius must be finite and at least 0, got {match_radius}")
         M, F, cs = self.nb_of_fields, self.field_size, self.cutout_size
+        fit_flux, fit_nonneg = bool(fit_flux), bool(fit_nonneg)
+        if fit_flux and not measure:
+            raise ValueError("fit_flux=True needs measure=True: the fit scales the measured fluxes of the passes")
+        for given, name in ((fit_weights is not None, "fit_weights"), (fit_sky is not None, "fit_sky"),
+                            (fit_nonneg, "fit_nonneg=True"), (sky_sigma is not None, "sky_sigma")):
+            if given and not fit_flux:
+                raise ValueError(f"{name} needs fit_flux=True: it belongs to the joint flux fit after the last pass")
+        if fit_flux:
+            from debvader_amd import engine as E
+            from debvader_amd.measure import measurement as ms
+
+            if fit_sky is not None:
+                E.sky_terms(fit_sky)
+            if fit_weights is not None:
+                if sky_sigma is not None:
+                    raise ValueError(ms.WEIGHTS_CARRY_THE_NOISE)
+                fit_weights = E.check_fit_weights(fit_weights, self.field_images.shape)
+            if sky_sigma is not None:
+                sky_sigma = ms.check_sky_sigma(sky_sigma, M, self.nb_of_bands)
+            E.fit_flux_params(min_pivot)
+        take_sums = bool(blendedness) or fit_flux        # the passes that keep resident rows
+        fit = None
+        self.sky_fit = None
+        self.nonneg_fit = None
         self._fields = None
         self._no_fields = not return_fields
         extra = [[] for _ in range(M)]       # measure=True: per field and pass, what joins the records at the end
@@ -335,6 +375,8 @@ class IterativeDeblendFieldBatch:
         po = int((F - cs) / 2)
         fs = eng.open_field_set(self.field_images, cumulative=cumulative)
         try:
+            if fit_flux:
+                fs.keep_stamps()
             k = 0
             while active.any() and (max_iterations is None or k < int(max_iterations)):
                 det = fs.detect(active=active)
@@ -352,7 +394,7 @@ class IterativeDeblendFieldBatch:
                 try:
                     if measure:
                         out = fs.deblend_pass_measure(starts, places, field_ptr, seed=core.next_seed(), band=band,
-                                                      sigma0=sigma0, tol=tol, max_iter=max_iter, blend=bool(blendedness))
+                                                      sigma0=sigma0, tol=tol, max_iter=max_iter, blend=take_sums)
                     else:
                         out = fs.deblend_pass(starts, places, field_ptr, seed=core.next_seed())
                 finally:
@@ -373,7 +415,9 @@ class IterativeDeblendFieldBatch:
                         e = {k: out[k][lo:hi] for k in ("flux", "flux_err", "shape", "iters", "status")}
                         e["places"] = np.asarray(places[lo:hi], dtype=np.float64)
                         if blendedness:
-                            e.update(child=out["child"][lo:hi], npix=out["npix"][lo:hi], rows=np.arange(nrows + lo, nrows + hi))
+                            e.update(child=out["child"][lo:hi], npix=out["npix"][lo:hi])
+                        if take_sums:
+                            e.update(rows=np.arange(nrows + lo, nrows + hi))
                         extra[m].append(e)
                     self.mse[m].append(float(out["field_mse"][m]))
                     total[m] += n
@@ -388,6 +432,9 @@ class IterativeDeblendFieldBatch:
                     nrows += N
                 k += 1
             sums = fs.blend_sums(band=band) if blendedness else None
+            if fit_flux:
+                fit = fs.fit_flux(data_fields=self.field_images if cumulative else None, weight_fields=fit_weights,
+                                  sky_order=fit_sky, nonneg=fit_nonneg, min_pivot=min_pivot)
             if return_fields:
                 self._fields = {"final": fs.read("final"), "mean": fs.read("mean"), "stddev": fs.read("stddev")}
         finally:
@@ -397,7 +444,40 @@ class IterativeDeblendFieldBatch:
         if measure:
             self.res_deblend = [self._with_catalogue(r, e, sums, bool(blendedness), match_radius)
                                 for r, e in zip(self.res_deblend, extra)]
+        if fit_flux:
+            from debvader_amd import engine as E
+
+            self.res_deblend = [self._with_fit(r, e, fit, m, sky_sigma, fit_weights is not None)
+                                for m, (r, e) in enumerate(zip(self.res_deblend, extra))]
+            if fit_sky is not None:
+                self.sky_fit = {k: fit[k] for k in E.FIT_SKY_KEYS}
+            if fit_nonneg:
+                self.nonneg_fit = {k: fit[k] for k in E.FIT_NONNEG_FIELD_KEYS}
         return self.res_deblend
+
+    def _with_fit(self, rec, extra, fit, m, sky_sigma, weighted):
+        """The catalogue of field m with the columns of the joint flux fit behind it: the rows of the fit joined by the
+        resident row number, the per-field sky of field m, and what the host derives from them."""
+        from debvader_amd import engine as E
+        from debvader_amd.measure import measurement as ms
+
+        nb = self.nb_of_bands
+        rows = np.concatenate([e["rows"] for e in extra]).astype(np.int64) if extra else np.zeros(0, np.int64)
+        sigma = None if sky_sigma is None else sky_sigma[m:m + 1]
+        chi = dict(fit_chi2=fit["fit_chi2"][rows], fit_npix=fit["fit_npix"][rows]) if weighted else {}
+        parts = [ms.fit_flux_records(*(fit[k][rows] for k in E.FIT_FLUX_KEYS), rec["flux"], sky_sigma=sigma, weighted=weighted,
+                                     **chi)]
+        if "sky_coef" in fit:
+            places = np.concatenate([e["places"] for e in extra]) if extra else np.zeros((0, 2))
+            parts.append(ms.fit_sky_records(fit["sky_coef"][m:m + 1], fit["sky_cov"][m:m + 1], fit["sky_status"][m:m + 1],
+                                            places, self.cutout_size, self.field_size, sky_sigma=sigma, weighted=weighted))
+        if "fit_scale_free" in fit:
+            parts.append(ms.fit_nonneg_records(*(fit[k][rows] for k in E.FIT_NONNEG_KEYS), rec["flux"]))
+        out = np.recarray((len(rec),), dtype=rec.dtype.descr + [d for p in parts for d in p.dtype.descr])
+        for p in [rec] + parts:
+            for k in p.dtype.names:
+                out[k] = p[k]
+        return out
 
     def _with_catalogue(self, rec, extra, sums, blendedness, match_radius):
         """The records of one field with the catalogue columns behind them: the rows every pass measured, the end-of-loop

@@ -2182,6 +2182,51 @@ class FieldSet:
         check(lib.dv_field_set_blend(h, int(band), self._rows, _dp(sums)))
         return sums
 
+    def keep_stamps(self, on: bool = True):
+        """From now on every deblend_pass_measure(blend=True) call also keeps its float32 mean stamps on the device, each at its
+        resident row number (dv_field_set_keep_stamps): what fit_flux() works on.  Allowed only before
+        the first such pass (DvError, DV_E_STATE, afterwards)."""
+        check(lib.dv_field_set_keep_stamps(self._handle(), int(bool(on))))
+
+    def fit_flux(self, data_fields=None, weight_fields=None, sky_order=None, nonneg=False, min_pivot: float = 1e-8,
+                 max_iter: int = 100, scratch_bytes: int = 256 << 20) -> Dict[str, np.ndarray]:
+        """The joint flux fit of the stamps of ALL deblend_pass_measure(blend=True) calls since keep_stamps(), one linear system
+        per field and band, on stamps that never left the GPU (dv_field_set_fit_flux).  Inside a field the
+        galaxies stand pass after pass, each pass in its own order: of two models that cannot be told apart the copy from the
+        later pass is dropped (fit_status 5, fit_scale 1).  data_fields (M, F, F, bands): what the models are fitted to; None:
+        the fields as uploaded, which only a set with cumulative=False keeps.  weight_fields, sky_order (None: no sky), nonneg,
+        min_pivot, max_iter and scratch_bytes are those of Context.scene_fit_flux, scene_fit_flux_sky and
+        scene_fit_flux_nonneg, and the dictionary has the keys of the one of them the arguments choose - the per-galaxy arrays
+        (Ntot, bands) in call order, like blend_sums(); the sky arrays and nonneg_iters / nonneg_status per field - with the
+        bits of that call on the same stamps regrouped field by field.  The set is only read: the call may be repeated.  A set
+        without resident rows fits nothing, no sky either: the per-field arrays come back as zeros."""
+        h = self._handle()
+        M, F, _, nb = self.shape
+        data = None
+        if data_fields is not None:
+            data = np.ascontiguousarray(data_fields, dtype=np.float64)
+            if data.shape != tuple(self.shape):
+                raise ValueError(f"expected data fields of the shape of the set's fields {tuple(self.shape)}, got {data.shape}")
+        elif self.cumulative:
+            raise ValueError("a cumulative set keeps no copy of the fields as uploaded: give data_fields")
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, self.shape)
+        sky, order, sky_ptrs = _fit_sky_args(sky_order, M, nb)
+        par = fit_flux_params(min_pivot, scratch_bytes)
+        nonneg = bool(nonneg)
+        max_iter = nonneg_max_iter(max_iter) if nonneg else 1
+        n = self._rows
+        out, ptrs = _fit_flux_out(n, nb, weights is not None)
+        if weights is None:
+            ptrs += [None, None]
+        out.update(sky)
+        nn_ptrs = [None] * 5
+        if nonneg:
+            nn, nn_ptrs = _fit_nonneg_out(n, M, nb)
+            out.update(nn)
+        check(lib.dv_field_set_fit_flux(h, n, None if data is None else _dp(data), None if weights is None else _dp(weights),
+                                        order, int(nonneg), C.byref(par), max_iter, *ptrs, *sky_ptrs, *nn_ptrs))
+        return out
+
     def read(self, which: str) -> np.ndarray:
         """One of the set's stacks as (M, F, F, bands) float64: "work", "final", "mean" or "stddev"."""
         h = self._handle()

@@ -868,6 +868,32 @@ int dv_field_set_pass_measure(dv_field_set* set, const int32_t* starts, const in
                               int32_t* status, double* child, int32_t* npix);
 int dv_field_set_blend(dv_field_set* set, int32_t band, int64_t n_expected, double* sums);
 
+/* ---- the joint flux fit of all passes of the iterative loop ----
+ * dv_field_set_keep_stamps(set, on): from now on a dv_field_set_pass_measure call that keeps resident rows (child and npix
+ * given) also keeps the pass's float32 mean stamps in device memory, each at its resident row number; they grow with the
+ * rows and are freed by dv_field_set_close.  Allowed only while the set holds no resident rows (DV_E_STATE otherwise, and on
+ * a closed set).  With the switch off every other call queues what it queued before and returns the same bits.
+ * dv_field_set_fit_flux: ONE linear system per field and band over the models of EVERY pass - the fit of dv_scene_fit_flux,
+ * _weighted, _sky or _nonneg, chosen by weight (NULL: unweighted), sky_order (-1: none, 0, 1) and nonneg - against `data`
+ * [M][F][F][nb] (host), or with data NULL against the fields as uploaded (reference mode only: a cumulative set keeps no
+ * copy, DV_E_INVALID).  Inside a field the galaxies stand in resident-row order, pass ascending and then the in-pass order:
+ * of two models that cannot be told apart the copy from the LATER pass is dropped (status 5, scale 1).  The set's rows are
+ * regrouped field by field in device memory and run through the kernels of the stand-alone calls: every output has the bits
+ * of the stand-alone call on the same stamps regrouped the same way.  Per-row outputs [Ntot][nb] are in resident-row (call)
+ * order; the sky outputs and nonneg_iters / nonneg_status are per field as in the stand-alone calls.  An output the chosen
+ * variant does not produce must be NULL, one it produces must not.  The call reads the set and never writes it: it may be
+ * repeated.  Zero rows: returns at once.  Refused before any GPU work, the set left as it was: n_expected is not Ntot
+ * (DV_E_INVALID); a closed set, or stamps never kept (DV_E_STATE); sky_order outside -1 .. 1; what the stand-alone calls
+ * refuse of params, nb above 16 among it; nonneg_max_iter < 1 with nonneg; a field whose scratch exceeds scratch_bytes; a
+ * field of more than DV_FIT_MAX_N galaxies summed over its passes (the message names the field and the count). */
+int dv_field_set_keep_stamps(dv_field_set* set, int32_t on);
+int dv_field_set_fit_flux(dv_field_set* set, int64_t n_expected, const double* data, const double* weight, int32_t sky_order,
+                          int32_t nonneg, const dv_fit_flux_params* params, int32_t nonneg_max_iter, double* fit_scale,
+                          double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status, double* fit_chi2,
+                          int32_t* fit_npix, double* sky_coef, double* sky_cov, int32_t* sky_status, int64_t* sky_npix,
+                          double* fit_scale_free, int32_t* fit_clamped, double* fit_dual, int32_t* nonneg_iters,
+                          int32_t* nonneg_status);
+
 /* ---- introspection for tests and bench ----------------------------------------------------- */
 /* copy a named activation of the last step to host: "t","z","kl","eps","loc","scale","head_pre" */
 int dv_model_get_activation(dv_model* m, const char* name, float* host, size_t nbytes);

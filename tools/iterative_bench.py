@@ -12,12 +12,16 @@ link per pass are counted from the passes the run made: field-sized arrays and f
 and per-stamp scalars in the batched form.  GPU only; prints a table and one JSON line.
 
     python tools/iterative_bench.py [--fields 64] [--size 259] [--repeat 5] [--max-batch 8192] [--dtype both]
-                                    [--measure] [--no-fields]
+                                    [--measure] [--no-fields] [--fit-flux [--fit-weights] [--fit-sky 0|1] [--fit-nonneg]]
 
---profile-one: warm up, run the batched form once (float32 unless --dtype says otherwise) and exit - for a kernel trace.
+--profile-one: warm up, run the batched form once (float32 unless --dtype says otherwise) and exit - for a kernel trace; with
+--measure --fit-flux that one run is the catalogue with the joint flux fit.
 --measure / --no-fields: instead of the loop, the batched form against itself through
 iterative_catalogue with measure=True, blendedness=True and / or return_fields=False - every combination the switches name,
 alternating from the same seed counter: the cost of the catalogue stage and of the three field-sized downloads.
+--fit-flux (with --measure): one more form per catalogue form, the same call with fit_flux=True - the
+joint flux fit of all passes after the last one - and the milliseconds per loop and microseconds per galaxy it adds.
+--fit-weights (uniform random inverse variances with a tenth of the pixels masked), --fit-sky and --fit-nonneg pick the variant.
 """
 import argparse
 import io
@@ -93,11 +97,23 @@ def main():
     ap.add_argument("--profile-one", action="store_true", help="warm up, one batched run, exit")
     ap.add_argument("--measure", action="store_true", help="time the batched form with and without the catalogue")
     ap.add_argument("--no-fields", action="store_true", help="time the batched form with and without the field downloads")
+    ap.add_argument("--fit-flux", action="store_true", help="with --measure: time the catalogue with and without the joint flux fit")
+    ap.add_argument("--fit-weights", action="store_true", help="the weighted fit")
+    ap.add_argument("--fit-sky", type=int, choices=(0, 1), default=None, help="the fit with a sky of that order")
+    ap.add_argument("--fit-nonneg", action="store_true", help="the non-negative fit")
     a = ap.parse_args()
+    if a.fit_flux and not a.measure:
+        ap.error("--fit-flux needs --measure: the fit belongs to the catalogue")
+    if (a.fit_weights or a.fit_sky is not None or a.fit_nonneg) and not a.fit_flux:
+        ap.error("--fit-weights, --fit-sky and --fit-nonneg need --fit-flux")
     rng = np.random.default_rng(0)
     F, M = a.size, a.fields
     base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
     fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    fit = dict(fit_flux=True, fit_sky=a.fit_sky, fit_nonneg=a.fit_nonneg)
+    if a.fit_weights:
+        wrng = np.random.default_rng(1)
+        fit["fit_weights"] = np.where(wrng.random(fields.shape) < 0.1, 0.0, wrng.uniform(0.5, 2.0, size=fields.shape))
     quiet = io.StringIO()                      # both classes print their progress
     result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat}
     print(f"{M} fields of {F} px, six bands; max_batch {a.max_batch}; reference mode")
@@ -107,6 +123,10 @@ def main():
         with redirect_stdout(quiet):
             _loop(net, fields[:2])                                                    # warm-up
             _batch(net, fields[:min(M, 8)])
+            if a.profile_one and a.fit_flux:                                          # (the catalogue with the joint fit)
+                _batch(net, fields, measure=True, blendedness=True, return_fields=not a.no_fields, **fit)
+                core.engine.close()
+                return
             if a.profile_one:
                 _batch(net, fields)
                 core.engine.close()
@@ -120,9 +140,16 @@ def main():
                 forms.append(("batch, no fields", dict(return_fields=False)))
             if a.measure and a.no_fields:
                 forms.append(("catalogue, no fields", dict(cat, return_fields=False)))
+            pairs = []                         # (form with the fit, the same form without it)
+            if a.fit_flux:
+                forms.append(("catalogue + fit", dict(cat, **fit)))
+                pairs.append(("catalogue + fit", "batch + catalogue"))
+                if a.no_fields:
+                    forms.append(("cat. + fit, no fields", dict(cat, return_fields=False, **fit)))
+                    pairs.append(("cat. + fit, no fields", "catalogue, no fields"))
             with redirect_stdout(quiet):
                 for _, kw in forms[1:]:                                               # warm-up of the new stages
-                    _batch(net, fields[:min(M, 8)], **kw)
+                    _batch(net, fields[:min(M, 8)], **{k: (v[:min(M, 8)] if k == "fit_weights" else v) for k, v in kw.items()})
             times = {label: [] for label, _ in forms}
             for _ in range(a.repeat):          # alternating; every run starts from the same seed counter
                 for label, kw in forms:
@@ -136,6 +163,10 @@ def main():
             med = {label: float(np.median(t)) for label, t in times.items()}
             for label, _ in forms[1:]:
                 print(f"{dtype} {label} / batch: {med[label] / med['batch']:.3f} x")
+            for with_fit, without in pairs:
+                add = med[with_fit] - med[without]
+                print(f"{dtype} {with_fit} - {without}: {1e3 * add:+.1f} ms per loop, {1e6 * add / max(n, 1):+.1f} us per galaxy "
+                      f"({n} galaxies)")
             result[dtype] = {label: [round(1e3 * x, 2) for x in t] for label, t in times.items()}
             result[dtype]["galaxies"] = int(n)
             core.engine.close()
