@@ -100,6 +100,31 @@ int exp_switch(const char* name);        // engine.hip: atoi of the variable (un
 #endif
 
 #ifdef __HIPCC__
+// Range-checked gathers (gconv2.hip, gconv_s2.hip).  One raw-buffer descriptor per gathered tensor whose record count is
+// the tensor's byte size: a buffer load whose byte offset lies outside [0, bytes) returns zeros, so a lane that has to
+// contribute zeros only needs an out-of-range offset (the byte size itself) and nothing after the load.  The descriptor
+// is built from kernel arguments passed through readfirstlane, once per kernel: the compiler then keeps it in scalar
+// registers and every load is a single buffer_load_dwordx4 ... offen.  Everything that decides validity is in the
+// per-lane offset; the scalar offset operand stays 0.
+typedef __amdgpu_buffer_rsrc_t BufRsrc;
+__device__ __forceinline__ BufRsrc make_gather_rsrc(const float* base, unsigned bytes) {
+  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+  void* q = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
+  return __builtin_amdgcn_make_buffer_rsrc(q, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+__device__ __forceinline__ f32x4 gather_b128(BufRsrc rs, unsigned byte_off) {
+  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+  const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 0);
+  return __builtin_bit_cast(f32x4, v);
+}
+// Bytes of headroom the out-of-range offsets need above a tensor of `bytes` bytes: an invalid lane's offset is `bytes`
+// plus a wave-uniform term below `uniform_max` bytes, and the access adds 16.  False: take the select form.
+inline bool gather_range_fits(unsigned long long bytes, unsigned long long uniform_max) {
+  return bytes + uniform_max + 16ull <= 0xffffffffull;
+}
+
 // Philox4x32-10 and the standard normal the engine derives from it (pairs (0,1), (2,3) of a block are one
 // Box-Muller draw): shared by the sampler and the sampled-"mse" metric of the head kernels
 __device__ __forceinline__ void dv_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
@@ -199,7 +224,12 @@ struct GConv2Params {
   int dbg;             // timing build: phase stamps
   float* dbg_out;
   int prio;            // ablation switch: 4 = one-chunk prefetch with the loads in front of the MFMA block
+  unsigned xbytes, wbytes;   // set by launch_gconv2: byte sizes of X and W, the ranges of the gather descriptors
 };
+// process-wide (development library only, bit 1 of dv_debug_general_kernels): 0 sends gconv2 / gconv_s2 through the select form of
+// their gathers instead of the range-checked buffer loads
+void debug_set_buffer_gather(int on);
+bool buffer_gather_on();
 void debug_set_gconv2_dbg(int v, float* out);
 void debug_set_gconv2_prio(int v);
 int launch_splitk_finish(const float* slabs, int ksplit, long total, int N, const float* bias, const float* alpha,
@@ -590,6 +620,7 @@ struct GConvS2Params {
   int cph[4], cpw[4];  // output parity of class c
   int wt[4][4];        // weight tap index of (neighbour e, class c); unused pairs 0
   unsigned* dbg_out;   // per-workgroup timeline stamps (tuning aid) or null
+  unsigned xbytes, wbytes;   // set by launch_gconv_s2: byte sizes of X and W, the ranges of the gather descriptors
 };
 int launch_gconv_s2(const GConvS2Params& p, hipStream_t s);
 void debug_set_gconv_s2_tile(int code);

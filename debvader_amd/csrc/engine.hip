@@ -6902,11 +6902,18 @@ int dv_debug_gconv(dv_ctx* ctx, int32_t NB, int32_t Hs, int32_t Cs, int32_t Ht, 
   return st;
 }
 
+static int debug_gather_check(dv_ctx* ctx, int32_t NB, int32_t Hs, int32_t Cs, int32_t Ht, int32_t Ct, int32_t stride,
+                              int32_t pb, int32_t dgrad_form, int32_t nmajor, int32_t epi, int32_t tile, float* out3);
+
 // Cross-check of the specialised gather-GEMM kernels (gconv_strip, gconv_s2) against the general gconv2 path on the
 // same pseudo-random operands: out2 = {max |difference| over both outputs, max |reference|}.
+// epi bit 8 selects the gather cross-check instead (debug_gather_check below): epilogue in bits 0-7, tile code + 1 in bits
+// 16-23 (0 = automatic), THREE floats out.
 int dv_debug_gconv_check(dv_ctx* ctx, int32_t NB, int32_t Hs, int32_t Cs, int32_t Ht, int32_t Ct, int32_t stride,
                          int32_t pb, int32_t dgrad_form, int32_t nmajor, int32_t epi, float* out2) {
   if (!ctx || !out2) return DV_E_INVALID;
+  if (epi & 0x100)
+    return debug_gather_check(ctx, NB, Hs, Cs, Ht, Ct, stride, pb, dgrad_form, nmajor, epi & 0xff, ((epi >> 16) & 0xff) - 1, out2);
   dv_model m;
   m.ctx = ctx;
   float *X, *W, *Y;
@@ -6951,6 +6958,102 @@ int dv_debug_gconv_check(dv_ctx* ctx, int32_t NB, int32_t Hs, int32_t Cs, int32_
   }
   (void)hipFree(X); (void)hipFree(W); (void)hipFree(Y); (void)hipFree(m.ws1); (void)hipFree(m.zero_page);
   for (auto& b : bufs) (void)hipFree(b);
+  for (void* q : m.allocs) (void)hipFree(q);      // Winograd weights registered on the fly
+  return st;
+}
+
+// The gather-GEMM kernels (gconv2, gconv_s2) on the select form of their gathers and on the range-checked buffer loads, same
+// launch, same pseudo-random operands.  X and W each lie INSIDE a larger allocation between two bands of NaN (64 KiB each):
+// the descriptors cover the tensors alone, so a buffer load that strays past a tensor shows as a NaN or a differing word,
+// never as a fault.  out3 = {output words (U and A) whose bit patterns differ, NaNs in the buffer path's outputs,
+// max |select-path output|}.  tile: -1 automatic, else the tile code of both kernel families.
+static int debug_gather_check(dv_ctx* ctx, int32_t NB, int32_t Hs, int32_t Cs, int32_t Ht, int32_t Ct, int32_t stride,
+                              int32_t pb, int32_t dgrad_form, int32_t nmajor, int32_t epi, int32_t tile, float* out3) {
+  if (!ctx || !out3 || NB < 1 || Hs < 1 || Ht < 1 || Cs < 1 || Ct < 1) return DV_E_INVALID;
+  dv_model m;
+  m.ctx = ctx;
+  DV_HIP(hipSetDevice(ctx->device));
+  const bool single_tap = !dgrad_form && Hs == 1 && Ht == 1 && stride == 1;
+  const size_t band = 16384;                                     // floats: 64 KiB in front of and behind each tensor
+  const size_t nx = (size_t)NB * Hs * Hs * Cs, nw = (size_t)(single_tap ? 1 : 9) * Cs * Ct, ny = (size_t)NB * Ht * Ht * Ct;
+  const size_t nal = (size_t)Ht * Ht * Ct, npar = (size_t)Ct + nal;
+  DevBuf<float> Xa, Wa, Par, out[4];                             // U, A of the select path; U, A of the buffer path
+  DV_TRY(Xa.alloc(nx + 2 * band));
+  DV_TRY(Wa.alloc(nw + 2 * band));
+  DV_TRY(Par.alloc(npar));
+  for (auto& b : out) DV_TRY(b.alloc(ny));
+  {
+    std::vector<float> h(std::max(std::max(nx, nw) + 2 * band, npar));
+    uint32_t st = 12345u;
+    auto fill = [&](size_t n0, size_t n) {           // n0 NaNs, n values in [-1, 1), n0 NaNs
+      for (size_t i = 0; i < n0 + n + n0; ++i) {
+        st = st * 1664525u + 1013904223u;
+        h[i] = (i < n0 || i >= n0 + n) ? __builtin_nanf("") : ((st >> 8) * (1.0f / 8388608.0f)) - 1.0f;
+      }
+    };
+    fill(band, nx);
+    DV_HIP(hipMemcpy(Xa.get(), h.data(), (nx + 2 * band) * sizeof(float), hipMemcpyHostToDevice));
+    fill(band, nw);
+    DV_HIP(hipMemcpy(Wa.get(), h.data(), (nw + 2 * band) * sizeof(float), hipMemcpyHostToDevice));
+    fill(0, npar);
+    DV_HIP(hipMemcpy(Par.get(), h.data(), npar * sizeof(float), hipMemcpyHostToDevice));
+  }
+  const float* X = Xa.get() + band;
+  const float* W = Wa.get() + band;
+  const float* bias = Par.get();
+  const float* alpha = Par.get() + Ct;
+  DevBuf<float> ws1, zero_page;
+  m.ws1_elems = (size_t)1 << 20;
+  DV_TRY(ws1.alloc(m.ws1_elems));
+  DV_TRY(zero_page.alloc(64));
+  m.ws1 = ws1.get();
+  m.zero_page = zero_page.get();
+  DV_HIP(hipMemset(m.zero_page, 0, 256));
+  for (auto& b : out) DV_HIP(hipMemset(b.get(), 0, ny * sizeof(float)));
+  DV_HIP(hipDeviceSynchronize());     // hipMemset runs on the null stream, the kernels under test on a non-blocking one
+  const bool was_on = buffer_gather_on();
+  if (tile >= 0) {
+    debug_set_gconv2_tile(tile);
+    debug_set_gconv_s2_tile(tile);
+  }
+  int st = OK;
+  for (int pass = 0; pass < 2 && st == OK; ++pass) {
+    debug_set_buffer_gather(pass);
+    float* U = out[2 * pass].get();
+    float* A = out[2 * pass + 1].get();
+    if (dgrad_form)
+      st = gconv_dgrad(&m, X, W, nmajor != 0, bias, alpha, U, A, epi, NB, Hs, Cs, Ht, Ct, stride, pb);
+    else
+      st = gconv_fprop(&m, X, W, nmajor != 0, bias, alpha, U, A, epi, NB, Hs, Cs, Ht, Ct, stride, pb, single_tap);
+  }
+  debug_set_buffer_gather(was_on ? 1 : 0);
+  debug_set_gconv2_tile(-1);
+  debug_set_gconv_s2_tile(-1);
+  const hipError_t se = hipStreamSynchronize(ctx->stream);
+  if (st == OK && se != hipSuccess) st = hip_fail(se, "hipStreamSynchronize", __FILE__, __LINE__);
+  if (st == OK) {
+    std::vector<uint32_t> a(ny), b(ny);
+    double ndiff = 0, nnan = 0, mr = 0;
+    for (int k = 0; k < 2 && st == OK; ++k) {
+      const hipError_t e1 = hipMemcpy(a.data(), out[k].get(), ny * sizeof(float), hipMemcpyDeviceToHost);
+      const hipError_t e2 = hipMemcpy(b.data(), out[2 + k].get(), ny * sizeof(float), hipMemcpyDeviceToHost);
+      if (e1 != hipSuccess || e2 != hipSuccess) {
+        st = hip_fail(e1 != hipSuccess ? e1 : e2, "hipMemcpy", __FILE__, __LINE__);
+        break;
+      }
+      for (size_t i = 0; i < ny; ++i) {
+        float fa, fb;
+        memcpy(&fa, &a[i], 4);
+        memcpy(&fb, &b[i], 4);
+        if (a[i] != b[i]) ndiff += 1;
+        if (fb != fb) nnan += 1;
+        if (fa == fa) mr = std::max(mr, (double)fabsf(fa));
+      }
+    }
+    out3[0] = (float)ndiff;
+    out3[1] = (float)nnan;
+    out3[2] = (float)mr;
+  }
   for (void* q : m.allocs) (void)hipFree(q);      // Winograd weights registered on the fly
   return st;
 }
@@ -7006,7 +7109,8 @@ int dv_debug_fuse_prelu_bwd(int32_t on) {
 }
 
 int dv_debug_general_kernels(int32_t on) {
-  g_no_special = on != 0;
+  g_no_special = (on & 1) != 0;
+  debug_set_buffer_gather((on & 2) == 0);        // bit 1: select form of the gconv2 / gconv_s2 gathers
   return DV_OK;
 }
 

@@ -30,7 +30,11 @@ __device__ __forceinline__ int t_wt(unsigned long long code, int t) { return (in
 // SUB = taps per 32-wide K chunk: 1 for Cin % 32 == 0, 2 for Cin == 16, 4 for Cin == 8 (tap then varies per lane)
 // RAG: Cin is a multiple of 4 but not of 32 (the 560-wide dense operands, model.py:96-98,113-117): the last chunk of a tap
 // is ragged, its missing quads / rows are zero-filled through the same masks that handle out-of-image rows
-template <int BM, int BN, int WGM, int WGN, bool NMAJOR, int SUB = 1, bool RAG = false>
+// BUF: both operands are gathered with range-checked buffer loads (common.h: make_gather_rsrc / gather_b128).  The per-row
+// and per-column offsets are bytes; a lane that has to read zeros (tap outside the image, row beyond M, column beyond
+// Cout, ragged channel quad) gets the tensor's byte size as its offset and the load returns zeros, so the validity masks
+// and the selects against zero at the LDS store are gone.  !BUF is the select form, for tensors too large for that.
+template <int BM, int BN, int WGM, int WGN, bool NMAJOR, int SUB = 1, bool RAG = false, bool BUF = true>
 // occupancy target: two workgroups per CU for the 128 x 128 tile (LDS-limited anyway), three for the smaller ones -
 // with the second register set the compiler otherwise settles just above the 168-register line of three waves / SIMD
 __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) void gconv2_kernel(const GConv2Params p) {
@@ -117,8 +121,22 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
 #pragma unroll
   for (int i = 0; i < AROWS; ++i) {
     rin[i] = s_in[r0 + 32 * i] + (SUB == 1 ? kq : kq % QPT) * 4;
+    if (BUF) rin[i] *= 4;                          // bytes
     rmask[i] = s_mask[r0 + 32 * i];
   }
+  // descriptors from kernel arguments only (wave-uniform to the compiler: no per-load readfirstlane loop)
+  const BufRsrc xrs = make_gather_rsrc(p.X, BUF ? p.xbytes : 0u);
+  const BufRsrc wrs = make_gather_rsrc(p.W, BUF ? p.wbytes : 0u);
+  // load of one float4 at element offset `off` (BUF: byte offset) of X / W; invalid lanes read zeros (BUF) or offset 0
+  auto ldx = [&](bool ok, int off) -> f32x4 {
+    if constexpr (BUF) return gather_b128(xrs, ok ? (unsigned)off : p.xbytes);
+    else return *reinterpret_cast<const f32x4*>(p.X + (ok ? (unsigned)off : 0u));
+  };
+  auto ldw = [&](bool ok, int off) -> f32x4 {
+    if constexpr (BUF) return gather_b128(wrs, ok ? (unsigned)off : p.wbytes);
+    else return *reinterpret_cast<const f32x4*>(p.W + (ok ? (unsigned)off : 0u));
+  };
+  constexpr int ES = BUF ? 4 : 1;                  // offset unit of rin / wthr / tapoff / wbase
   // weight addressing: thread-constant part
   int wthr[NMAJOR ? BROWS_N : BPASS];
   unsigned wok = 0;
@@ -127,7 +145,9 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
     for (int i = 0; i < BROWS_N; ++i) {
       const int n = n0 + r0 + 32 * i;
       const bool ok = n < p.Cout && r0 + 32 * i < BN;
-      wthr[i] = ok ? n * p.Cin + (SUB == 1 ? kq : kq % QPT) * 4 : 0;
+      // BUF: an invalid column keeps the out-of-range offset through the add of the uniform tap / chunk base, which is
+      // below the tensor's size (launch_gconv2 checks that twice the size fits)
+      wthr[i] = ok ? (n * p.Cin + (SUB == 1 ? kq : kq % QPT) * 4) * ES : (BUF ? (int)p.wbytes : 0);
       wok |= (ok ? 1u : 0u) << i;
     }
   } else {
@@ -137,7 +157,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
       const int kr = kr0 + BKR * i;
       const int n = n0 + nq * 4;
       const bool ok = kr < BK2 && n < p.Cout;
-      wthr[i] = ok ? (SUB == 1 ? kr : kr % CINS) * p.Cout + n : 0;
+      wthr[i] = ok ? ((SUB == 1 ? kr : kr % CINS) * p.Cout + n) * ES : (BUF ? (int)p.wbytes : 0);
       wok |= (ok ? 1u : 0u) << i;
     }
   }
@@ -156,31 +176,27 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
     if constexpr (SUB == 1) {
       const int dh = t_dh(cl.tapcode, tap), dw = t_dw(cl.tapcode, tap);
       const int wt = t_wt(cl.wtcode, tap);
-      const int tapoff = (dh * p.Win + dw) * p.Cin + cc * BK2;
+      const int tapoff = ((dh * p.Win + dw) * p.Cin + cc * BK2) * ES;
       const bool kv = !RAG || cc * BK2 + kq * 4 < p.Cin;       // this lane's channel quad exists
+      const int tapbit = 1 << tap;
 #pragma unroll
       for (int i = 0; i < AROWS; ++i) {
-        const bool ok = ((rmask[i] >> tap) & 1) && kv;
-        const unsigned off = ok ? (unsigned)(rin[i] + tapoff) : 0u;
-        areg[S][i] = *reinterpret_cast<const f32x4*>(p.X + off);
+        const bool ok = (rmask[i] & tapbit) && kv;
+        areg[S][i] = ldx(ok, rin[i] + tapoff);
         amask |= (ok ? 1u : 0u) << i;
       }
       if (NMAJOR) {
-        const int wbase = wt * p.Cout * p.Cin + cc * BK2;
+        const int wbase = (wt * p.Cout * p.Cin + cc * BK2) * ES;
         if (RAG) bmaskv = kv ? 0xffffffffu : 0u;
 #pragma unroll
-        for (int i = 0; i < BROWS_N; ++i) {
-          const unsigned off = (((wok >> i) & 1u) && kv) ? (unsigned)(wbase + wthr[i]) : 0u;
-          breg[S][i] = *reinterpret_cast<const f32x4*>(p.W + off);
-        }
+        for (int i = 0; i < BROWS_N; ++i) breg[S][i] = ldw((BUF || ((wok >> i) & 1u)) && kv, wbase + wthr[i]);
       } else {
-        const int wbase = (wt * p.Cin + cc * BK2) * p.Cout;
+        const int wbase = (wt * p.Cin + cc * BK2) * p.Cout * ES;
         if (RAG) bmaskv = 0;
 #pragma unroll
         for (int i = 0; i < BPASS; ++i) {
           const bool kvb = !RAG || cc * BK2 + (int)(tid / BQ) + BKR * i < p.Cin;   // this pass's weight row exists
-          const unsigned off = (((wok >> i) & 1u) && kvb) ? (unsigned)(wbase + wthr[i]) : 0u;
-          breg[S][i] = *reinterpret_cast<const f32x4*>(p.W + off);
+          breg[S][i] = ldw((BUF || ((wok >> i) & 1u)) && kvb, wbase + wthr[i]);
           if (RAG) bmaskv |= (kvb ? 1u : 0u) << i;
         }
       }
@@ -193,12 +209,11 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
       const int mytap = tap + kq / QPT;
       const int tcl = min(mytap, 8);
       const int dh = t_dh(cl.tapcode, tcl), dw = t_dw(cl.tapcode, tcl);
-      const int tapoff = (dh * p.Win + dw) * p.Cin;
+      const int tapoff = (dh * p.Win + dw) * p.Cin * ES;
 #pragma unroll
       for (int i = 0; i < AROWS; ++i) {
         const bool ok = mytap < cl.ntaps && ((rmask[i] >> tcl) & 1);
-        const unsigned off = ok ? (unsigned)(rin[i] + tapoff) : 0u;
-        areg[S][i] = *reinterpret_cast<const f32x4*>(p.X + off);
+        areg[S][i] = ldx(ok, rin[i] + tapoff);
         amask |= (ok ? 1u : 0u) << i;
       }
       bmaskv = 0;
@@ -207,8 +222,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
 #pragma unroll
         for (int i = 0; i < BROWS_N; ++i) {
           const bool ok = ((wok >> i) & 1u) && mytap < cl.ntaps;
-          const unsigned off = ok ? (unsigned)(wt * p.Cout * p.Cin + wthr[i]) : 0u;
-          breg[S][i] = *reinterpret_cast<const f32x4*>(p.W + off);
+          breg[S][i] = ldw(ok, wt * p.Cout * p.Cin * ES + wthr[i]);
           bmaskv |= (ok ? 1u : 0u) << i;
         }
       } else {
@@ -219,8 +233,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
           const int btap = tap + kr / CINS;
           const int bcl = min(btap, 8);
           const bool ok = ((wok >> i) & 1u) && btap < cl.ntaps;
-          const unsigned off = ok ? (unsigned)(t_wt(cl.wtcode, bcl) * p.Cin * p.Cout + wthr[i]) : 0u;
-          breg[S][i] = *reinterpret_cast<const f32x4*>(p.W + off);
+          breg[S][i] = ldw(ok, t_wt(cl.wtcode, bcl) * p.Cin * p.Cout * ES + wthr[i]);
           bmaskv |= (ok ? 1u : 0u) << i;
         }
       }
@@ -238,19 +251,22 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
     float* a = As + buf * A_ELEMS;
 #pragma unroll
     for (int i = 0; i < AROWS; ++i)
-      *reinterpret_cast<f32x4*>(a + (r0 + 32 * i) * BK2 + ((kq ^ sw_w) << 2)) = ((amask >> i) & 1u) ? areg[S][i] : zero4;
+      *reinterpret_cast<f32x4*>(a + (r0 + 32 * i) * BK2 + ((kq ^ sw_w) << 2)) =
+          (BUF || ((amask >> i) & 1u)) ? areg[S][i] : zero4;
     float* b = Bs + buf * B_ELEMS;
     if (NMAJOR) {
 #pragma unroll
       for (int i = 0; i < BROWS_N; ++i)
         if (r0 + 32 * i < BN)
-          *reinterpret_cast<f32x4*>(b + (r0 + 32 * i) * BK2 + ((kq ^ sw_w) << 2)) = (((wok & bmaskv) >> i) & 1u) ? breg[S][i] : zero4;
+          *reinterpret_cast<f32x4*>(b + (r0 + 32 * i) * BK2 + ((kq ^ sw_w) << 2)) =
+              (BUF || (((wok & bmaskv) >> i) & 1u)) ? breg[S][i] : zero4;
     } else {
       const int nq = tid % BQ, kr0 = tid / BQ;
 #pragma unroll
       for (int i = 0; i < BPASS; ++i) {
         const int kr = kr0 + BKR * i;
-        if (kr < BK2) *reinterpret_cast<f32x4*>(b + kr * LDBK + nq * 4) = (((wok & bmaskv) >> i) & 1u) ? breg[S][i] : zero4;
+        if (kr < BK2)
+          *reinterpret_cast<f32x4*>(b + kr * LDBK + nq * 4) = (BUF || (((wok & bmaskv) >> i) & 1u)) ? breg[S][i] : zero4;
       }
     }
   };
@@ -324,7 +340,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
       for (int i = 0; i < 8; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, TM * TN, 0);   // MFMA
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);         // VMEM read
-        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);         // VALU
+        __builtin_amdgcn_sched_group_barrier(0x002, BUF ? 3 : 8, 0);   // VALU
       }
       store_lds(st, cur ^ 1);
       __syncthreads();
@@ -469,13 +485,13 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || BM >= 256) ? 2 : 3) v
   }
 }
 
-template <int BM, int BN, int WGM, int WGN, bool NMAJOR, int SUB = 1, bool RAG = false>
-static int launch2_cfg(GConv2Params p, hipStream_t s) {
+template <int BM, int BN, int WGM, int WGN, bool NMAJOR, int SUB, bool RAG, bool BUF>
+static int launch2_buf(GConv2Params p, hipStream_t s) {
   constexpr int A_ELEMS = BM * BK2;
   constexpr int B_ELEMS = NMAJOR ? BN * BK2 : BK2 * (BN + 4);
   constexpr size_t smem = (size_t)(2 * A_ELEMS + 2 * B_ELEMS) * sizeof(float) + 4 * BM * sizeof(int);
   static bool attr_set = false;
-  auto kern = gconv2_kernel<BM, BN, WGM, WGN, NMAJOR, SUB, RAG>;
+  auto kern = gconv2_kernel<BM, BN, WGM, WGN, NMAJOR, SUB, RAG, BUF>;
   if (!attr_set) {
     DV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)smem));
@@ -491,6 +507,21 @@ static int launch2_cfg(GConv2Params p, hipStream_t s) {
   hipLaunchKernelGGL(kern, dim3(tiles, p.ksplit > 1 ? p.ksplit : 1), dim3(256), smem, s, p);
   DV_HIP(hipGetLastError());
   return OK;
+}
+
+static int g2_buffer_gather = 1;
+void debug_set_buffer_gather(int on) { g2_buffer_gather = on != 0; }
+bool buffer_gather_on() { return g2_buffer_gather != 0; }
+
+template <int BM, int BN, int WGM, int WGN, bool NMAJOR, int SUB = 1, bool RAG = false>
+static int launch2_cfg(const GConv2Params& p, hipStream_t s) {
+  // range-checked buffer gathers unless the out-of-range offsets would not fit in 32 bits: an invalid lane of X sits at
+  // xbytes, one of W at wbytes or at wbytes plus a tap / chunk base below wbytes.  (The kernel keeps its byte offsets in
+  // signed registers like the element offsets of the select form: X below 2 GiB.)
+  if (buffer_gather_on() && p.xbytes < 0x7fffffffu && gather_range_fits(p.xbytes, 0) &&
+      gather_range_fits(p.wbytes, p.wbytes) && 2ull * p.wbytes < 0x7fffffffull)
+    return launch2_buf<BM, BN, WGM, WGN, NMAJOR, SUB, RAG, true>(p, s);
+  return launch2_buf<BM, BN, WGM, WGN, NMAJOR, SUB, RAG, false>(p, s);
 }
 
 static int g2_tile_override = -1;
@@ -608,6 +639,8 @@ int launch_gconv2(const GConv2Params& p0, hipStream_t s) {
     set_error("gconv2: tensor too large for 32-bit byte offsets; lower max_batch");
     return E_INVALID;
   }
+  p.xbytes = (unsigned)((size_t)p.NB * p.Hin * p.Win * p.Cin * sizeof(float));
+  p.wbytes = (unsigned)((size_t)wslices * p.Cin * p.Cout * sizeof(float));
   if (p.epi == 2 && (!p.alpha || !p.A)) {
     set_error("gconv2: PReLU epilogue needs alpha and A");
     return E_INVALID;

@@ -37,7 +37,13 @@ __host__ __device__ constexpr int popc4(int m) { return (m & 1) + ((m >> 1) & 1)
 
 // TMW: 16-row MFMA blocks per wave along M (2: 32 base pixels per wave; 1: 16, half the LDS and accumulators, so
 // three workgroups fit a CU)
-template <int WGM, int WGN, int TMW = 2>
+// BUF: both operands are gathered with buffer loads through one descriptor per tensor whose range is the tensor's byte
+// size.  A lane that has to read zeros (neighbour outside the image, row beyond M, column beyond Cout) carries an
+// out-of-range byte offset and the range check returns zeros: no validity masks and no selects against zero at the LDS
+// store.  Validity is fixed per (row, neighbour) for a tile, so the A offsets are precomputed per neighbour with the
+// validity folded in, and a steady-state load costs one add of the wave-uniform chunk offset.  !BUF is the select form
+// for tensors whose byte size does not leave room for the out-of-range offsets in 32 bits.
+template <int WGM, int WGN, int TMW = 2, bool BUF = true>
 __global__ __launch_bounds__(64 * WGM * WGN) void gconv_s2_kernel(const GConvS2Params p) {
   constexpr int NW = WGM * WGN, NT = 64 * NW;
   constexpr int WMR = 16 * TMW;                   // rows per wave
@@ -98,20 +104,34 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gconv_s2_kernel(const GConvS2P
   const int kq = tid & 7, r0 = tid >> 3;
   int rin[AROWS];
   unsigned rnm = 0;                                // 4 neighbour bits per A row of this thread
+  unsigned avo[BUF ? 4 : 1][AROWS];                // BUF: byte offset of (neighbour e, row i), out of range where invalid
 #pragma unroll
   for (int i = 0; i < AROWS; ++i) {
     rin[i] = s_in[r0 + RP * i] + kq * 4;
-    rnm |= (unsigned)(s_nm[r0 + RP * i] & 15) << (4 * i);
+    const unsigned nm = (unsigned)(s_nm[r0 + RP * i] & 15);
+    rnm |= nm << (4 * i);
+    if constexpr (BUF) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        avo[e][i] = ((nm >> e) & 1u) ? (unsigned)(rin[i] + (p.ndh[e] * p.Win + p.ndw[e]) * p.Cin) * 4u : p.xbytes;
+    }
   }
-  int wthr[BROWS];
+  int wthr[BROWS];                                 // BUF: byte offset inside a tap, out of range beyond Cout
   unsigned wok = 0;
 #pragma unroll
   for (int i = 0; i < BROWS; ++i) {
     const int n = n0 + r0 + RP * i;
     const bool ok = n < p.Cout;
-    wthr[i] = ok ? n * p.Cin + kq * 4 : 0;
-    wok |= (ok ? 1u : 0u) << i;
+    if constexpr (BUF) {
+      wthr[i] = ok ? (n * p.Cin + kq * 4) * 4 : (int)p.wbytes;
+    } else {
+      wthr[i] = ok ? n * p.Cin + kq * 4 : 0;
+      wok |= (ok ? 1u : 0u) << i;
+    }
   }
+  // descriptors from kernel arguments only (wave-uniform to the compiler: no per-load readfirstlane loop)
+  const BufRsrc xrs = make_gather_rsrc(p.X, BUF ? p.xbytes : 0u);
+  const BufRsrc wrs = make_gather_rsrc(p.W, BUF ? p.wbytes : 0u);
 
   f32x4 areg[AROWS];
   f32x4 breg[4][BROWS];
@@ -122,23 +142,39 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gconv_s2_kernel(const GConvS2P
   auto load_global = [&](auto phase, int cc) {
     constexpr int E = phase_nbr(decltype(phase)::value);
     constexpr int MK = nbr_mask(E);
-    const int tapoff = (p.ndh[E] * p.Win + p.ndw[E]) * p.Cin + cc * BKS;
-    amask = 0;
+    if constexpr (BUF) {
+      // an invalid lane stays out of range: its offset is the tensor's byte size plus a uniform term below that size
+      // (launch_gconv_s2 takes this form only where that sum and the 16 bytes of the access fit in 32 bits)
+      const unsigned ccb = (unsigned)(cc * BKS) * 4u;
 #pragma unroll
-    for (int i = 0; i < AROWS; ++i) {
-      const bool ok = (rnm >> (4 * i + E)) & 1;
-      const unsigned off = ok ? (unsigned)(rin[i] + tapoff) : 0u;
-      areg[i] = *reinterpret_cast<const f32x4*>(p.X + off);
-      amask |= (ok ? 1u : 0u) << i;
-    }
+      for (int i = 0; i < AROWS; ++i) areg[i] = gather_b128(xrs, avo[E][i] + ccb);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if ((MK >> c) & 1) {
-        const int wbase = p.wt[E][c] * CC + cc * BKS;
+      for (int c = 0; c < 4; ++c) {
+        if ((MK >> c) & 1) {
+          const unsigned wbase = (unsigned)(p.wt[E][c] * CC + cc * BKS) * 4u;
 #pragma unroll
-        for (int i = 0; i < BROWS; ++i) {
-          const unsigned off = ((wok >> i) & 1u) ? (unsigned)(wbase + wthr[i]) : 0u;
-          breg[c][i] = *reinterpret_cast<const f32x4*>(p.W + off);
+          for (int i = 0; i < BROWS; ++i) breg[c][i] = gather_b128(wrs, (unsigned)wthr[i] + wbase);
+        }
+      }
+    } else {
+      const int tapoff = (p.ndh[E] * p.Win + p.ndw[E]) * p.Cin + cc * BKS;
+      amask = 0;
+#pragma unroll
+      for (int i = 0; i < AROWS; ++i) {
+        const bool ok = (rnm >> (4 * i + E)) & 1;
+        const unsigned off = ok ? (unsigned)(rin[i] + tapoff) : 0u;
+        areg[i] = *reinterpret_cast<const f32x4*>(p.X + off);
+        amask |= (ok ? 1u : 0u) << i;
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if ((MK >> c) & 1) {
+          const int wbase = p.wt[E][c] * CC + cc * BKS;
+#pragma unroll
+          for (int i = 0; i < BROWS; ++i) {
+            const unsigned off = ((wok >> i) & 1u) ? (unsigned)(wbase + wthr[i]) : 0u;
+            breg[c][i] = *reinterpret_cast<const f32x4*>(p.W + off);
+          }
         }
       }
     }
@@ -151,14 +187,16 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gconv_s2_kernel(const GConvS2P
     float* a = smem + buf * STAGE;
 #pragma unroll
     for (int i = 0; i < AROWS; ++i)
-      *reinterpret_cast<f32x4*>(a + (r0 + RP * i) * BKS + ((kq ^ sw_w) << 2)) = ((amask >> i) & 1u) ? areg[i] : zero4;
+      *reinterpret_cast<f32x4*>(a + (r0 + RP * i) * BKS + ((kq ^ sw_w) << 2)) =
+          (BUF || ((amask >> i) & 1u)) ? areg[i] : zero4;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       if ((MK >> c) & 1) {
         float* b = a + A_ELEMS + c * B_ELEMS;
 #pragma unroll
         for (int i = 0; i < BROWS; ++i)
-          *reinterpret_cast<f32x4*>(b + (r0 + RP * i) * BKS + ((kq ^ sw_w) << 2)) = ((wok >> i) & 1u) ? breg[c][i] : zero4;
+          *reinterpret_cast<f32x4*>(b + (r0 + RP * i) * BKS + ((kq ^ sw_w) << 2)) =
+              (BUF || ((wok >> i) & 1u)) ? breg[c][i] : zero4;
       }
     }
   };
@@ -202,17 +240,29 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gconv_s2_kernel(const GConvS2P
     }
   };
 
-  // one K step of phase PH whose prefetch belongs to phase PN: a single basic block, the gather's VALU / VMEM
-  // instructions spread between the MFMAs
+  // one K step of phase PH whose prefetch belongs to phase PN: a single basic block; select form: the gather's VALU /
+  // VMEM instructions spread between the MFMAs, buffer form: the loads first, fragment reads spread between the MFMAs
   auto step = [&](auto ph, auto pn, int cc_next, int cur) {
     constexpr int NMF = 16 * TMW * popc4(nbr_mask(phase_nbr(decltype(ph)::value)));
     load_global(pn, cc_next);
+    if constexpr (BUF) __builtin_amdgcn_sched_barrier(0);
     compute(ph, cur);
+    if constexpr (BUF) {
+      // what is left of the gather is one add and one buffer load per float4.  Spread between the MFMAs the scheduler
+      // sinks the loads to the end of the step, against the LDS store that waits for them; in front of the MFMAs (the
+      // fence above) the whole step hides their latency, and they issue while the first fragment reads are in flight.
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, NMF / 8, 0);   // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);         // VMEM read
-      __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);        // VALU
+      for (int i = 0; i < 8; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, NMF / 8, 0);   // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);         // DS read
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, NMF / 8, 0);   // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);         // VMEM read
+        __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);        // VALU
+      }
     }
     store_lds(pn, cur ^ 1);
     __syncthreads();
@@ -308,12 +358,12 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gconv_s2_kernel(const GConvS2P
   }
 }
 
-template <int WGM, int WGN, int TMW = 2>
+template <int WGM, int WGN, int TMW = 2, bool BUF = true>
 static int launch_s2_cfg(const GConvS2Params& p, hipStream_t s) {
   constexpr int BM = 16 * TMW * WGM, BN = 32 * WGN;
   constexpr size_t smem = (size_t)2 * (BM * BKS + 4 * BN * BKS) * sizeof(float) + 4 * BM * sizeof(int);
   static bool attr_set = false;
-  auto kern = gconv_s2_kernel<WGM, WGN, TMW>;
+  auto kern = gconv_s2_kernel<WGM, WGN, TMW, BUF>;
   if (!attr_set) {
     DV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)smem));
@@ -360,6 +410,21 @@ int launch_gconv_s2(const GConvS2Params& p0, hipStream_t s) {
     // (4x4x256 -> 8x8x256: 66 -> 54 us); everywhere else the 128 x 32 tile wins
     const long wgs128 = (long)((p.M + 127) / 128) * ((p.Cout + 31) / 32);
     t = wgs128 < 512 ? 4 : 1;
+  }
+  // range-checked buffer gathers unless the out-of-range offsets would not fit in 32 bits: an invalid lane of X sits at
+  // xbytes plus a channel-chunk offset below one pixel's channels, one of W at wbytes plus a tap / chunk base below wbytes
+  p.xbytes = (unsigned)((size_t)p.NB * p.Hin * p.Win * p.Cin * sizeof(float));
+  p.wbytes = (unsigned)((size_t)9 * p.Cin * p.Cout * sizeof(float));
+  const bool buf = buffer_gather_on() && gather_range_fits(p.xbytes, (size_t)p.Cin * sizeof(float)) &&
+                   gather_range_fits(p.wbytes, p.wbytes);
+  if (!buf) {
+    switch (t) {
+      case 0: return launch_s2_cfg<2, 2, 2, false>(p, s);
+      case 1: return launch_s2_cfg<4, 1, 2, false>(p, s);
+      case 2: return launch_s2_cfg<2, 1, 2, false>(p, s);
+      case 4: return launch_s2_cfg<4, 1, 1, false>(p, s);
+      default: return launch_s2_cfg<1, 2, 2, false>(p, s);
+    }
   }
   switch (t) {
     case 0: return launch_s2_cfg<2, 2>(p, s);

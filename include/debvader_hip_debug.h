@@ -17,7 +17,12 @@ int dv_debug_gconv(dv_ctx* ctx, int32_t NB, int32_t Hs, int32_t Cs, int32_t Ht, 
                    int32_t pad_before, int32_t dgrad_form, int32_t nmajor, int32_t epi, int32_t single_tap,
                    int32_t tile, int32_t iters, float* ms_out);
 /* runs one layer through the specialised kernel the dispatcher picks (strip form, fused stride-2 form) and through the
- * general gather-GEMM on the same pseudo-random operands: out2 = {max |difference|, max |reference|} over U and A */
+ * general gather-GEMM on the same pseudo-random operands: out2 = {max |difference|, max |reference|} over U and A.
+ * With bit 8 of epi set (epilogue in bits 0-7, tile code + 1 in bits 16-23, 0 = automatic; Hs = Ht = 1 with stride 1 is the
+ * one-tap dense form) it is the gather cross-check instead: the one gconv2 / gconv_s2 launch the dispatcher picks, on the
+ * select form of the gathers and on the range-checked buffer loads, X and W each inside a larger allocation between two
+ * 64 KiB bands of NaN; out2 then receives THREE floats = {output words (U and A) whose bit patterns differ, NaNs in the
+ * buffer path's outputs, max |output|} */
 int dv_debug_gconv_check(dv_ctx* ctx, int32_t NB, int32_t Hs, int32_t Cs, int32_t Ht, int32_t Ct, int32_t stride,
                          int32_t pad_before, int32_t dgrad_form, int32_t nmajor, int32_t epi, float* out2);
 /* issue-rate probe of v_mfma_f32_16x16x4_f32 (no memory traffic), nacc = 16 or 36 independent accumulators,
@@ -25,7 +30,10 @@ int dv_debug_gconv_check(dv_ctx* ctx, int32_t NB, int32_t Hs, int32_t Cs, int32_
 int dv_debug_mfma_peak(dv_ctx* ctx, int32_t blocks, int32_t iters, int32_t nacc, int32_t randomize, float* out3);
 /* process-wide: the fp32 engine routes every conv / conv-transpose / weight-gradient launch through the general
  * gather-GEMM and tiled weight-gradient kernels (no strip or fused stride-2 forms): the same arithmetic in another
- * summation order.  The control of tests/test_gpu_bf16.py (two fp32 summation orders against the bf16 engine). */
+ * summation order.  The control of tests/test_gpu_bf16.py (two fp32 summation orders against the bf16 engine).
+ * `on` is a bit set: bit 0 is the above; bit 1 sends the gather-GEMM kernels (gconv2, gconv_s2) through the select form of
+ * their gathers (loads from offset 0 plus a select against zero at the LDS store), which the product takes only for
+ * tensors too large for a 32-bit range-checked offset.  Same arithmetic, bit-identical results.  0 restores both. */
 int dv_debug_general_kernels(int32_t on);
 /* process-wide: on = 0 sends the stride-1 3x3 layers of the fp32 engine through the direct kernels (strip form /
  * gather-GEMM) instead of the Winograd F(2x2, 3x3) kernel (wino.hip); on = 1 restores the default */
