@@ -208,6 +208,11 @@ SIGNATURES = {
     "dv_scene_fit_flux_weighted": (C.c_int, [_p, _f, _i32, _i64, C.c_int64, C.c_int32, C.c_int32, _d, _d, C.c_int32, C.c_int32,
                                              C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _i32, _d, _i32]),
     "dv_infer_fields_measure_fit_weighted": _measure_sig(C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _d, _i32, _d, _i32),
+    "dv_scene_fit_flux_groups": (C.c_int, [_p, _f, _i32, _i64, C.c_int64, C.c_int32, C.c_int32, _d, C.c_int32, C.c_int32,
+                                           C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _d, _i32, _d, _i32, _i32, _i32]),
+    "dv_infer_fields_measure_fit_groups": _measure_sig(C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _d, _i32, _d, _i32, _i32, _i32),
+    "dv_scene_fit_groups": (C.c_int, [_p, _i32, _i64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _i32, _i32, C.c_int64, _i64,
+                                      _i32, C.c_int64, _i64, _i32, _i32]),
     "dv_scene_fit_flux_sky": (C.c_int, [_p, _f, _i32, _i64, C.c_int64, C.c_int32, C.c_int32, _d, _d, C.c_int32, C.c_int32,
                                         C.POINTER(DvFitFluxParams), C.c_int32, _d, _d, _d, _d, _i32, _d, _i32, _d, _d, _i32, _i64]),
     "dv_scene_fit_flux_sky_gram": (C.c_int, [_p, _f, _i32, C.c_int64, C.c_int32, C.c_int32, _d, _d, C.c_int32, C.c_int32, _d, _d]),

@@ -525,6 +525,34 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
                    const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
                    hipStream_t s, const double* weight_h = nullptr, const char* who = "dv_scene_fit_flux", int sky_order = -1,
                    const FitFluxSky& sky_h = FitFluxSky{}, const FitFluxNonneg& nn_h = FitFluxNonneg{});
+// The fit by blend groups: the connected components of the overlap graph of every field are found on the GPU and
+// each is solved on its own - no limit per field, FF_MAX_N per group, the scratch sum nb n_g^2 doubles.  FitGroupsWork: the
+// device tables (counts, scans, pair list, adjacency, labels, group tables, scratch), grown as a call needs them, and their host
+// staging.  launch_fit_flux_groups: the complete fields fa .. fz like launch_fit_flux; group_h / gsize_h [.] are HOST rows,
+// counted from row 0 of the tables (the host derives them from the labels); field_base: the number of field 0 of the tables in
+// the caller's call, for the refusals.  It returns with the stream idle, also when it refuses.  stamps_dev null: the groups alone,
+// nothing is solved or refused.  lists: when given, the pair list and the adjacency of the launch are copied out.
+struct FitGroupsLists { std::vector<int> pairs, adj_ptr, adj; };
+struct FitGroupsWork {
+  DevBuf<int> cnt, ptr, pairs, adj, lab, label, rtab, grows;
+  DevBuf<long long> gtab;
+  DevBuf<double> scratch;
+  std::vector<int> label_h, rtab_h, grows_h, gsize_h;
+  std::vector<long long> gtab_h;
+};
+int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* places_dev, const int* sfield_dev,
+                           const int* fptr_dev, const double* data_dev, int f0, const int* fptr_h, int fa, int fz, int field_base,
+                           int cs, int nb, int F, const FitFluxParams& p, FitGroupsWork& w, const FitFluxRows& rows,
+                           int32_t* group_h, int32_t* gsize_h, hipStream_t s, const double* weight_dev = nullptr,
+                           FitGroupsLists* lists = nullptr);
+int scene_fit_flux_groups(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
+                          const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, int32_t* group_h,
+                          int32_t* gsize_h, int device, hipStream_t s, const double* weight_h);
+// the blend groups alone, from the placements (no stamps, no fit, no limit on a group), and optionally the pair list and the CSR
+// adjacency the fit works from, rows of the call: n_pairs / n_adj are always written, the lists where all three are given
+int scene_fit_groups(const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int M, int F, int32_t* group_h,
+                     int32_t* gsize_h, int64_t pair_cap, int64_t* n_pairs, int32_t* pairs_h, int64_t adj_cap, int64_t* n_adj,
+                     int32_t* adj_ptr_h, int32_t* adj_h, int device, hipStream_t s);
 // step 1 of the bordered system of one field (7t): the dense [nb][n + q][n + q] lower triangle and its right-hand side
 // [n + q][nb] to the host, the bits the solve starts from
 int scene_fit_flux_sky_gram(const float* stamps_h, const int32_t* places_h, int64_t n, int cs, int nb, const double* data_h,

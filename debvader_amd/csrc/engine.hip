@@ -3972,6 +3972,31 @@ int dv_scene_fit_flux_weighted(dv_ctx* c, const float* stamps, const int32_t* pl
                         weight_fields, "dv_scene_fit_flux_weighted");
 }
 
+// the fit by blend groups, with weights or without: every refusal is scene_fit_flux_groups'
+int dv_scene_fit_flux_groups(dv_ctx* c, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs,
+                             int32_t nb, const double* data_fields, int32_t M, int32_t F, const dv_fit_flux_params* params,
+                             const double* weight_fields, double* fit_scale, double* fit_var, double* fit_gram, double* fit_proj,
+                             int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, int32_t* fit_group,
+                             int32_t* fit_group_size) {
+  if (!c) return DV_E_INVALID;
+  if (!params) {
+    set_error("dv_scene_fit_flux_groups: params must be given");
+    return DV_E_INVALID;
+  }
+  return scene_fit_flux_groups(stamps, places, field_ptr, N, cs, nb, data_fields, M, F,
+                               FitFluxParams{params->min_pivot, params->scratch_bytes},
+                               FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, fit_group,
+                               fit_group_size, c->device, c->stream, weight_fields);
+}
+
+int dv_scene_fit_groups(dv_ctx* c, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs, int32_t M, int32_t F,
+                        int32_t* fit_group, int32_t* fit_group_size, int64_t pair_cap, int64_t* n_pairs, int32_t* pairs,
+                        int64_t adj_cap, int64_t* n_adj, int32_t* adj_ptr, int32_t* adj) {
+  if (!c) return DV_E_INVALID;
+  return scene_fit_groups(places, field_ptr, N, cs, M, F, fit_group, fit_group_size, pair_cap, n_pairs, pairs, adj_cap, n_adj,
+                          adj_ptr, adj, c->device, c->stream);
+}
+
 int dv_scene_fit_flux_gram(dv_ctx* c, const float* stamps, const int32_t* places, int64_t n, int32_t cs, int32_t nb,
                            const double* data_field, int32_t F, double* gram, double* proj) {
   if (!c) return DV_E_INVALID;
@@ -5208,14 +5233,18 @@ struct ApertureFieldStage {         // the apertures of every stamp on the mean 
 // in too, and the rows carry fit_chi2 and fit_npix
 // _fit_sky (7t): the order of the sky fitted jointly (-1: none) and its per-field outputs (host)
 // _fit_nonneg (7u): the non-negativity constraint, max_iter and its per-field outputs (host)
+// _fit_groups (7w): the fit by blend groups - group / group_size [N] (host), written at the seam by the host's grouping
 struct FitFluxOut {
   FitFluxParams par{}; FitFluxRows rows{}; const double* weights = nullptr; int sky_order = -1; FitFluxSky sky{};
   FitFluxNonneg nonneg{};
+  int32_t* group = nullptr; int32_t* group_size = nullptr;
+  bool grouped() const { return group != nullptr; }
 };
 
 struct FitFluxStage {               // the simultaneous flux fit of every field's mean stamps to its source field (7q)
   DevBuf<float> store;              // the mean stamps of all N stamps: a field's are read when its composite is complete
   FitFluxWork work;
+  FitGroupsWork gwork;              // the fit by blend groups (7w): its tables and scratch grow at the seam as the fields need
   FitFluxRows dev{};
   Rows rows;
   void columns(const FitFluxOut& o, int nb) { fitflux_columns(rows, dev, o.rows, nb, o.weights != nullptr, o.nonneg.on); }
@@ -5302,7 +5331,8 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, j.starts, places, sfield, fptr32));
   const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
   FitFluxPlan ffplan;
-  if (rq.fit_flux)                                     // (before anything is written or queued)
+  const bool ff_groups = rq.fit_flux && rq.fit_flux->grouped();   // (7w: no plan by field - the groups are known at the seam)
+  if (rq.fit_flux && !ff_groups)                       // (before anything is written or queued)
     DV_TRY(fitflux_plan(who, field_ptr, M, nb, rq.fit_flux->par, &ffplan, rq.fit_flux->sky_order, F));
   if (rq.fit_flux && rq.fit_flux->nonneg.on && M > 0) {   // (7u: a field without unknowns has no factorisation and converged)
     std::fill(rq.fit_flux->nonneg.iters, rq.fit_flux->nonneg.iters + (size_t)M * nb, 0);
@@ -5384,6 +5414,12 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     reserve += (size_t)N * ffs.bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M, wfields != nullptr) +
                FitFluxStage::sky_bytes(ffplan.q, (size_t)M, nb) + FitFluxStage::nonneg_bytes(rq.fit_flux->nonneg, (size_t)M, nb);
     if (wfields) per_field += fb;
+    if (ff_groups) {                                   // the tables of the grouping per stamp, and the scratch: at most the
+      int64_t nmax = 0;                                // dense matrices of the largest field, at most scratch_bytes
+      for (int f = 0; f < M; ++f) nmax = std::max(nmax, field_ptr[f + 1] - field_ptr[f]);
+      reserve += (size_t)N * (12 * sizeof(int) + 4 * sizeof(long long)) +
+                 std::min((size_t)rq.fit_flux->par.scratch_bytes, (size_t)nb * (size_t)nmax * (size_t)nmax * sizeof(double));
+    }
   }
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
@@ -5483,7 +5519,11 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
                                        aps.dev.kron + (size_t)r0 * 3, aps.dev.status + r0,
                                        tab.places.get() + 2 * (size_t)r0, tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, F,
                                        mean_f, fdev, rq.aper->par, aperture_field_rows_at(afs.dev, r0, rq.aper->par, nb), s));
-        if (rq.fit_flux)               // (the stamp store, the placements and the tables count from stamp 0 of the call)
+        if (ff_groups)                 // (7w: the groups' rows go to the host arrays here; the call's fields are the tables')
+          DV_TRY(launch_fit_flux_groups(who, ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, fptr32.data(), fa, fz, 0,
+                                        c.cs, nb, F, rq.fit_flux->par, ffs.gwork, ffs.dev, rq.fit_flux->group,
+                                        rq.fit_flux->group_size, s, wfields ? wdev.get() : nullptr));
+        else if (rq.fit_flux)          // (the stamp store, the placements and the tables count from stamp 0 of the call)
           DV_TRY(launch_fit_flux(ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, places, fptr32.data(), fa, fz, c.cs,
                                  nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s, true, wfields ? wdev.get() : nullptr, ffs.sky,
                                  ffs.nonneg));
@@ -5667,6 +5707,10 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const Catalo
                                                      rq.fit_flux->weights != nullptr));
     if (rq.fit_flux->nonneg.on) DV_TRY(fitflux_nonneg_check(who, rq.fit_flux->nonneg, rq.fit_flux->rows, N, rq.fit_flux->sky,
                                                             rq.fit_flux->weights != nullptr));
+    if (rq.fit_flux->grouped() && !rq.fit_flux->weights && (rq.fit_flux->rows.chi2 || rq.fit_flux->rows.npix)) {
+      set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: without weight_fields both must be NULL", who);
+      return DV_E_INVALID;
+    }
     DV_TRY(seam_places_check(who, a));
   }
   if (rq.regauss) {
@@ -5855,6 +5899,34 @@ int dv_infer_fields_measure_fit_weighted(dv_model* m, const double* fields, int3
   rq.fit_flux = FitFluxOut{FitFluxParams{fit->min_pivot, fit->scratch_bytes},
                            FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields};
   return infer_fields_measure_entry("dv_infer_fields_measure_fit_weighted", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
+}
+
+// ---- the flux fit by blend groups: dv_infer_fields_measure_fit[_weighted] - weight_fields may be NULL, and
+// fit_chi2 and fit_npix are NULL exactly then - without a limit per field, plus the group and the group size of every galaxy
+int dv_infer_fields_measure_fit_groups(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                       const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                       const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                       double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                       int32_t* iters, int32_t* status, const dv_fit_flux_params* fit, const double* weight_fields,
+                                       double* fit_scale, double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status,
+                                       double* fit_chi2, int32_t* fit_npix, int32_t* fit_group, int32_t* fit_group_size) {
+  if (!m) return DV_E_INVALID;
+  if (!fit) {
+    set_error("dv_infer_fields_measure_fit_groups: the flux-fit params must be given");
+    return DV_E_INVALID;
+  }
+  if (!fit_group || !fit_group_size) {
+    set_error("dv_infer_fields_measure_fit_groups: fit_group and fit_group_size must all be given");
+    return DV_E_INVALID;
+  }
+  FieldsRequest rq;
+  rq.fit_flux = FitFluxOut{FitFluxParams{fit->min_pivot, fit->scratch_bytes},
+                           FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields};
+  rq.fit_flux->group = fit_group;
+  rq.fit_flux->group_size = fit_group_size;
+  return infer_fields_measure_entry("dv_infer_fields_measure_fit_groups", m,
                                     {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
                                      residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }

@@ -57,6 +57,10 @@
 //   fitflux_nonneg_kernel     in place of fitflux_solve_kernel when the constraint is asked for, on the same scratch: iteration
 //                             1 is steps 2 - 5 above, then the active set is exchanged and the kept unknowns that are not
 //                             clamped are factorised again until no amplitude and no multiplier is negative.
+// The fit by blend groups lifts the limit of FF_MAX_N galaxies from the field to the group: the connected
+// components of the graph of adjacent galaxies - the pairs of the list above - are found on the GPU (fitgroups_count / scan /
+// fill / label kernels, below) and every group is solved on its own by the GROUPED instantiations of the Gram and solve
+// kernels, which reach their rows through group tables; GROUPED = false is the code as it was, instruction for instruction.
 // No atomics; ordinary vector stores only.
 #include "common.h"
 #include "measure_dev.h"
@@ -106,18 +110,26 @@ __device__ __forceinline__ void ff_load(const float* __restrict__ p, int nb, dou
 // unweighted instantiation never touches `weight`.
 __device__ __forceinline__ bool ff_counts(double w) { return w > 0.0 && w < __longlong_as_double(0x7ff0000000000000LL); }
 
-template <bool WEIGHTED, int Q = 0>
+template <bool WEIGHTED, int Q = 0, bool GROUPED = false>
 __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __restrict__ pairs, const float* __restrict__ stamps,
                                                                   const int* __restrict__ places, const int* __restrict__ sfield,
                                                                   const int* __restrict__ fptr, const long long* __restrict__ foff,
                                                                   int fbase, int f0, int cs, int nb, int F,
                                                                   const double* __restrict__ data, double* __restrict__ scratch,
                                                                   double* __restrict__ gram, double* __restrict__ proj,
-                                                                  const double* __restrict__ weight) {
+                                                                  const double* __restrict__ weight,
+                                                                  const int* __restrict__ rtab = nullptr,
+                                                                  const long long* __restrict__ gtab = nullptr, int rbase = 0,
+                                                                  int sub = 0) {
   __shared__ double s_red[MS_RED];
   const long gi = pairs[2 * (long)blockIdx.x], gj = pairs[2 * (long)blockIdx.x + 1];
   const int m = sfield[gi];
-  const int row0 = fptr[m], n = fptr[m + 1] - row0 + Q;   // (the row length of the scratch: Q sky terms behind the galaxies, 7t)
+  // GROUPED (7w): the blend group of the pair in place of its field - the group's scratch, its size, the positions of the two
+  // rows inside it; a pair of a group that goes through the scratch in another sub-range is left to that sub-range's launch
+  const long long* gt = GROUPED ? gtab + 4 * (long)rtab[2 * (gi - rbase)] : nullptr;
+  if (GROUPED && gt[3] != sub) return;         // (uniform: the whole workgroup takes one pair)
+  const int row0 = GROUPED ? 0 : fptr[m];
+  const int n = GROUPED ? (int)gt[2] : fptr[m + 1] - row0 + Q;   // (the row length of the scratch: Q sky terms behind the galaxies, 7t)
   const int pri = places[2 * gi], pci = places[2 * gi + 1], prj = places[2 * gj], pcj = places[2 * gj + 1];
   // the intersection of the two stamps and the field, in field pixels (the host lists a pair only where it is not empty)
   const int ra = max(max(pri, prj), 0), rz = min(min(pri, prj) + cs, F);
@@ -167,8 +179,8 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __r
       }
     }
   }
-  const long il = gi - row0, jl = gj - row0;
-  double* S = scratch + foff[m - fbase] + il * n + jl;
+  const long il = GROUPED ? rtab[2 * (gi - rbase) + 1] : gi - row0, jl = GROUPED ? rtab[2 * (gj - rbase) + 1] : gj - row0;
+  double* S = scratch + (GROUPED ? gt[0] : foff[m - fbase]) + il * n + jl;
 #pragma unroll
   for (int b = 0; b < FF_BANDS; ++b) {
     if (b < nb) {                            // (nb and diag are uniform: every thread takes the same barriers)
@@ -405,33 +417,40 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_border_kernel(int r0, cons
 // coefficient 0.0 and leaves the right-hand sides alone (step 4 sums over the dropped GALAXIES), and its outputs go to
 // sky_coef / sky_status [field][nb][Q] and sky_cov [field][nb][Q][Q], the corner of (L^-1)^T L^-1.  The sky terms come last, so
 // every operation on the galaxy block is the one of Q = 0, in the same order; Q = 0 is the kernel as it was.
-template <int Q>
+template <int Q, bool GROUPED = false>
 __global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __restrict__ fptr, const long long* __restrict__ foff,
                                                                    int fbase, int nb, double min_pivot,
                                                                    double* __restrict__ scratch, const double* __restrict__ gram,
                                                                    const double* __restrict__ proj, double* __restrict__ scale,
                                                                    double* __restrict__ var, int* __restrict__ status,
                                                                    const double* __restrict__ skysums, double* __restrict__ sky_coef,
-                                                                   double* __restrict__ sky_cov, int* __restrict__ sky_status) {
+                                                                   double* __restrict__ sky_cov, int* __restrict__ sky_status,
+                                                                   const int* __restrict__ grows = nullptr,
+                                                                   const long long* __restrict__ gtab = nullptr) {
   __shared__ double s_y[FF_MAX_N + Q];
   __shared__ int s_st[FF_MAX_N + Q];
+  // GROUPED (7w): blend group fbase + blockIdx.x in place of a field - gtab [.][4]: where its scratch begins, its first slot of
+  // `grows`, its size; unknown k is row grows[first + k] of the call, the members in ascending row order
+  const long long* gt = GROUPED ? gtab + 4 * (long)(fbase + (int)blockIdx.x) : nullptr;
   const int m = fbase + (int)blockIdx.x, b = (int)blockIdx.y;
-  const long row0 = fptr[m];
-  const int ng = fptr[m + 1] - (int)row0;      // the galaxies
+  const long row0 = GROUPED ? 0 : fptr[m];
+  const int ng = GROUPED ? (int)gt[2] : fptr[m + 1] - (int)row0;      // the galaxies
   const int n = ng + Q;                        // the unknowns
   if (n <= 0) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double* S = scratch + foff[blockIdx.x] + (long)b * n * n;
+  double* S = scratch + (GROUPED ? gt[0] : foff[blockIdx.x]) + (long)b * n * n;
+  const int* gr = GROUPED ? grows + gt[1] : nullptr;
+  auto row = [&](int k) -> long { return GROUPED ? (long)gr[k] : row0 + k; };
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   const double* ks = Q > 0 ? skysums + ((long)blockIdx.x * nb + b) * SKY_ACC(Q) : nullptr;
   // G_kk as step 1 left it and the right-hand side of unknown k (sky term t: K_tt at t (t + 3) / 2 of the sums, c_t behind K)
   auto diag0 = [&](int k) -> double {
     if (Q > 0 && k >= ng) return ks[(k - ng) * (k - ng + 3) / 2];
-    return gram[(row0 + k) * nb + b];
+    return gram[row(k) * nb + b];
   };
   auto rhs0 = [&](int k) -> double {
     if (Q > 0 && k >= ng) return ks[Q * (Q + 1) / 2 + (k - ng)];
-    return proj[(row0 + k) * nb + b];
+    return proj[row(k) * nb + b];
   };
 
   // step 2 and the working copy
@@ -526,7 +545,7 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_solve_kernel(const int* __
       }
     }
     if (i < ng) {
-      const long o = (row0 + i) * nb + b;
+      const long o = row(i) * nb + b;
       const int st = s_st[i];
       scale[o] = st == 0 ? s_y[i] : st == 5 ? 1.0 : nan;
       var[o] = st == 0 ? acc : nan;
@@ -972,6 +991,155 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_regroup_kernel(const int* 
   }
   if (tid < 2) dst_places[2 * d + tid] = src_places[2 * r + tid];
   if (tid == 2) dst_field[d] = src_field[r];
+}
+
+// The blend groups of a field: the connected components of the graph whose edges are the pairs of galaxies whose
+// stamp rectangles, clipped to the field, intersect - the test of the pair list above.  Four kernels, integers only:
+//   fitgroups_count_kernel  one workgroup per row i: its threads test every row j of i's field, stride 256, and count the
+//                           adjacent j <= i and the adjacent j in all; integer sums, any order gives the same number.
+//   fitgroups_scan_kernel   one workgroup: the exclusive scans of both counts, 256 rows at a time with a carry.
+//   fitgroups_fill_kernel   one workgroup per row i, j ascending 256 at a time: an exclusive scan of the hits gives every hit its
+//                           place - an ordered compaction.  No atomics.  The hits j <= i come first, so one scan places both the
+//                           pair (i, j <= i) and the entry j of row i's adjacency list: the pair list comes out sorted by i and
+//                           then j, every adjacency list ascending - the lists the host built.
+//   fitgroups_label_kernel  one workgroup per field: label[i] starts at i (counted from the field's first row); a sweep gives
+//                           every row the minimum label of its neighbours and itself and then that label's label (pointer
+//                           jumping: a sorted chain of n links takes log2 n sweeps, any chain at most n), from one array into
+//                           the other, __syncthreads() between sweeps, until a sweep changes nothing.  A label is always a
+//                           row of the component that is not above the row itself, so the fixed point is the component's
+//                           smallest row whatever the order of the threads.
+__device__ __forceinline__ bool fg_adjacent(int pri, int pci, int prj, int pcj, int cs, int F) {
+  const int ra = max(max(pri, prj), 0), rz = min(min(pri, prj) + cs, F);
+  const int ca = max(max(pci, pcj), 0), cz = min(min(pci, pcj) + cs, F);
+  return rz > ra && cz > ca;
+}
+
+// the exclusive prefix sum of v over the workgroup in thread order and the workgroup's total (s_w: one int per wave)
+__device__ __forceinline__ int fg_block_scan(int v, int* s_w, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(x, o, 64);
+    if (lane >= o) x += t;
+  }
+  __syncthreads();                           // s_w of the previous call has been read by everyone
+  if (lane == 63) s_w[wave] = x;
+  __syncthreads();
+  int base = 0;
+#pragma unroll
+  for (int k = 0; k < MS_THREADS / 64; ++k) base += k < wave ? s_w[k] : 0;
+  total = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+  return base + x - v;
+}
+
+// rows r0 + blockIdx.x; cnt [2][nr]: the adjacent rows j <= i, then the adjacent rows in all
+__global__ __launch_bounds__(MS_THREADS) void fitgroups_count_kernel(int r0, int nr, const int* __restrict__ places,
+                                                                     const int* __restrict__ sfield, const int* __restrict__ fptr,
+                                                                     int cs, int F, int* __restrict__ cnt) {
+  __shared__ int s_w[MS_THREADS / 64];
+  const int gi = r0 + (int)blockIdx.x, m = sfield[gi];
+  const int ja = fptr[m], jz = fptr[m + 1];
+  const int pri = places[2 * (long)gi], pci = places[2 * (long)gi + 1];
+  int le = 0, all = 0;
+  for (int j = ja + (int)threadIdx.x; j < jz; j += MS_THREADS) {
+    const int hit = fg_adjacent(pri, pci, places[2 * (long)j], places[2 * (long)j + 1], cs, F) ? 1 : 0;
+    all += hit;
+    le += j <= gi ? hit : 0;
+  }
+  int tle, tall;
+  fg_block_scan(le, s_w, tle);
+  fg_block_scan(all, s_w, tall);
+  if (threadIdx.x == 0) {
+    cnt[blockIdx.x] = tle;
+    cnt[(long)nr + blockIdx.x] = tall;
+  }
+}
+
+// ptr [2][nr + 1]: the exclusive scans of cnt [2][nr], the totals at [nr]
+__global__ __launch_bounds__(MS_THREADS) void fitgroups_scan_kernel(int nr, const int* __restrict__ cnt, int* __restrict__ ptr) {
+  __shared__ int s_w[MS_THREADS / 64];
+  for (int a = 0; a < 2; ++a) {
+    const int* c = cnt + (long)a * nr;
+    int* p = ptr + (long)a * (nr + 1);
+    int carry = 0;
+    for (int i0 = 0; i0 < nr; i0 += MS_THREADS) {   // (uniform: every thread takes the same barriers)
+      const int i = i0 + (int)threadIdx.x;
+      const int v = i < nr ? c[i] : 0;
+      int total;
+      const int x = fg_block_scan(v, s_w, total);
+      if (i < nr) p[i] = carry + x;
+      carry += total;
+    }
+    if (threadIdx.x == 0) p[nr] = carry;
+  }
+}
+
+// pairs [.][2] and adj [.] from ptr; nothing is written past the places the scan gave row i
+__global__ __launch_bounds__(MS_THREADS) void fitgroups_fill_kernel(int r0, int nr, const int* __restrict__ places,
+                                                                    const int* __restrict__ sfield, const int* __restrict__ fptr,
+                                                                    int cs, int F, const int* __restrict__ ptr,
+                                                                    int* __restrict__ pairs, int* __restrict__ adj) {
+  __shared__ int s_w[MS_THREADS / 64];
+  const int gi = r0 + (int)blockIdx.x, m = sfield[gi];
+  const int ja = fptr[m], jz = fptr[m + 1];
+  const int pri = places[2 * (long)gi], pci = places[2 * (long)gi + 1];
+  const int pl = ptr[blockIdx.x], plz = ptr[blockIdx.x + 1];
+  const int pa = ptr[(long)nr + 1 + blockIdx.x], paz = ptr[(long)nr + 2 + blockIdx.x];
+  int base = 0;
+  for (int j0 = ja; j0 < jz; j0 += MS_THREADS) {    // (uniform)
+    const int j = j0 + (int)threadIdx.x;
+    const int hit = (j < jz && fg_adjacent(pri, pci, places[2 * (long)j], places[2 * (long)j + 1], cs, F)) ? 1 : 0;
+    int total;
+    const int pos = base + fg_block_scan(hit, s_w, total);
+    if (hit) {
+      if (pa + pos < paz) adj[pa + pos] = j;
+      if (j <= gi && pl + pos < plz) {
+        pairs[2 * (long)(pl + pos)] = gi;
+        pairs[2 * (long)(pl + pos) + 1] = j;
+      }
+    }
+    base += total;
+  }
+}
+
+// field fa + blockIdx.x; adj_ptr [nr + 1] / adj: the adjacency of rows r0 .., the entries rows of the call; lab [2][nr] the two
+// label arrays, out [nr] the labels, counted from the field's first row
+__global__ __launch_bounds__(MS_THREADS) void fitgroups_label_kernel(int r0, int nr, int fa, const int* __restrict__ fptr,
+                                                                     const int* __restrict__ adj_ptr, const int* __restrict__ adj,
+                                                                     int* lab, int* __restrict__ out) {
+  __shared__ int s_changed;
+  const int m = fa + (int)blockIdx.x;
+  const int row0 = fptr[m], n = fptr[m + 1] - row0;
+  const int l0 = row0 - r0;                  // the field's first row in the arrays of this launch
+  int* A = lab + l0;
+  int* B = lab + (long)nr + l0;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += MS_THREADS) A[i] = i;
+  if (tid == 0) s_changed = 0;
+  __syncthreads();
+  for (;;) {
+    int changed = 0;
+    for (int i = tid; i < n; i += MS_THREADS) {
+      const int old = A[i];
+      int l = old;
+      for (int e = adj_ptr[l0 + i]; e < adj_ptr[l0 + i + 1]; ++e) l = min(l, A[adj[e] - row0]);
+      l = A[l];
+      B[i] = l;
+      changed |= l != old;
+    }
+    if (changed) s_changed = 1;              // (every writer writes the same value)
+    __syncthreads();
+    const bool again = s_changed != 0;       // (uniform)
+    __syncthreads();                         // everyone has read the flag
+    if (tid == 0) s_changed = 0;
+    __syncthreads();                         // the flag is clear before the next sweep sets it
+    int* t = A;
+    A = B;
+    B = t;
+    if (!again) break;
+  }
+  for (int i = tid; i < n; i += MS_THREADS) out[l0 + i] = A[i];
 }
 }  // namespace
 
@@ -1431,6 +1599,313 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
     DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next chunk
   }
   drain.dismiss();
+  return OK;
+}
+
+// The fit by blend groups of the complete fields fa .. fz (7w).  Neighbour listing and labelling on the GPU; the host downloads
+// the two totals and then the labels, 4 bytes per galaxy, and does the O(N) grouping: the groups of a field ordered by their
+// smallest row, the members in ascending row order, fit_group / fit_group_size, the refusals, and the cut into sub-ranges of
+// consecutive groups whose sum nb n_g^2 doubles fit the scratch.  One upload of the group tables serves every sub-range: a
+// group's scratch offset and the number of its sub-range are part of its table entry.  The pair list is sorted by row, not by
+// group, so every sub-range launches the Gram kernel over the whole list and a workgroup whose group belongs to another
+// sub-range returns at once; with the default scratch there is one sub-range.  The chi-square runs once, behind the last solve,
+// on the adjacency the fill kernel wrote.
+int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* places_dev, const int* sfield_dev,
+                           const int* fptr_dev, const double* data_dev, int f0, const int* fptr_h, int fa, int fz, int field_base,
+                           int cs, int nb, int F, const FitFluxParams& p, FitGroupsWork& w, const FitFluxRows& rows,
+                           int32_t* group_h, int32_t* gsize_h, hipStream_t s, const double* weight_dev, FitGroupsLists* lists) {
+  const int r0 = fptr_h[fa], r1 = fptr_h[fz + 1], nr = r1 - r0, nf = fz - fa + 1;
+  if (nr <= 0) return OK;
+  StreamDrain drain(s);                                // (a refusal or a failure below leaves the stream idle)
+  DV_TRY(w.cnt.ensure(2 * (size_t)nr));
+  DV_TRY(w.ptr.ensure(2 * ((size_t)nr + 1)));
+  DV_TRY(w.lab.ensure(2 * (size_t)nr));
+  DV_TRY(w.label.ensure((size_t)nr));
+  hipLaunchKernelGGL(fitgroups_count_kernel, dim3((unsigned)nr), dim3(MS_THREADS), 0, s, r0, nr, places_dev, sfield_dev, fptr_dev, cs,
+                     F, w.cnt.get());
+  hipLaunchKernelGGL(fitgroups_scan_kernel, dim3(1), dim3(MS_THREADS), 0, s, nr, (const int*)w.cnt.get(), w.ptr.get());
+  DV_HIP(hipGetLastError());
+  int totals[2] = {0, 0};                              // the pairs (i, j <= i) and the adjacency entries
+  DV_HIP(hipMemcpyAsync(&totals[0], w.ptr.get() + nr, sizeof(int), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipMemcpyAsync(&totals[1], w.ptr.get() + 2 * (size_t)nr + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+  DV_HIP(hipStreamSynchronize(s));
+  const size_t npairs = (size_t)totals[0], nadj = (size_t)totals[1];
+  if (totals[0] < 0 || totals[1] < 0 || nadj > 2 * npairs) {   // (more than 2^31 entries wrap the 32-bit scan)
+    set_error("%s: fields %d .. %d: the overlapping pairs of %d galaxies do not fit 32-bit offsets", who, field_base + fa,
+              field_base + fz, nr);
+    return E_INVALID;
+  }
+  DV_TRY(w.pairs.ensure(std::max<size_t>(2 * npairs, 1)));
+  DV_TRY(w.adj.ensure(std::max<size_t>(nadj, 1)));
+  const int* adj_ptr = w.ptr.get() + nr + 1;
+  hipLaunchKernelGGL(fitgroups_fill_kernel, dim3((unsigned)nr), dim3(MS_THREADS), 0, s, r0, nr, places_dev, sfield_dev, fptr_dev, cs, F,
+                     (const int*)w.ptr.get(), w.pairs.get(), w.adj.get());
+  hipLaunchKernelGGL(fitgroups_label_kernel, dim3((unsigned)nf), dim3(MS_THREADS), 0, s, r0, nr, fa, fptr_dev, adj_ptr,
+                     (const int*)w.adj.get(), w.lab.get(), w.label.get());
+  DV_HIP(hipGetLastError());
+  w.label_h.resize((size_t)nr);
+  DV_HIP(hipMemcpyAsync(w.label_h.data(), w.label.get(), (size_t)nr * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (lists) {
+    lists->pairs.resize(2 * npairs);
+    lists->adj_ptr.resize((size_t)nr + 1);
+    lists->adj.resize(nadj);
+    if (npairs) DV_HIP(hipMemcpyAsync(lists->pairs.data(), w.pairs.get(), 2 * npairs * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(lists->adj_ptr.data(), adj_ptr, ((size_t)nr + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (nadj) DV_HIP(hipMemcpyAsync(lists->adj.data(), w.adj.get(), nadj * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+  DV_HIP(hipStreamSynchronize(s));
+
+  // the grouping: a row whose label is its own row opens a group, and rows ascend, so the groups of a field come out ordered
+  // by their smallest row and every group's members in ascending row order
+  w.rtab_h.assign(2 * (size_t)nr, 0);
+  w.gsize_h.assign((size_t)nr, 0);                     // by row of the launch: the group it opens, then that group's size
+  w.gtab_h.clear();
+  for (int f = fa; f <= fz; ++f) {
+    const int a = fptr_h[f] - r0, z = fptr_h[f + 1] - r0;
+    for (int i = a; i < z; ++i) {
+      const int l = w.label_h[(size_t)i];
+      if (l < 0 || l > i - a || w.label_h[(size_t)(a + l)] != l) {   // (cannot happen: a label is a root not above its row)
+        set_error("%s: field %d: row %d came back with the label %d", who, field_base + f, i - a, l);
+        return E_STATE;
+      }
+      if (l == i - a) {
+        w.rtab_h[2 * (size_t)i] = (int)(w.gtab_h.size() / 4);
+        w.gtab_h.insert(w.gtab_h.end(), {0, 0, 0, 0});
+      }
+      const int g = w.rtab_h[2 * (size_t)(a + l)];
+      w.rtab_h[2 * (size_t)i] = g;
+      w.rtab_h[2 * (size_t)i + 1] = (int)w.gtab_h[4 * (size_t)g + 2]++;
+    }
+    for (int i = a; i < z; ++i) {
+      const long long n = w.gtab_h[4 * (size_t)w.rtab_h[2 * (size_t)i] + 2];
+      group_h[(size_t)r0 + i] = w.label_h[(size_t)i];
+      gsize_h[(size_t)r0 + i] = (int32_t)n;
+      if (!stamps_dev) continue;                       // (the groups alone: nothing is solved, nothing is refused)
+      if (n > FF_MAX_N && w.label_h[(size_t)i] == i - a) {
+        set_error("%s: field %d: the blend group of row %ld has %ld galaxies, the grouped fit takes at most %d per group", who,
+                  field_base + f, (long)(i - a), (long)n, FF_MAX_N);
+        return E_INVALID;
+      }
+      const size_t need = (size_t)nb * (size_t)n * (size_t)n * sizeof(double);
+      if (need > (size_t)p.scratch_bytes && w.label_h[(size_t)i] == i - a) {
+        set_error("%s: field %d: the blend group of row %ld has %ld galaxies: its Gram matrices need %zu bytes of scratch (bands x "
+                  "n_g x n_g doubles), scratch_bytes is %ld", who, field_base + f, (long)(i - a), (long)n, need,
+                  (long)p.scratch_bytes);
+        return E_INVALID;
+      }
+    }
+  }
+  if (!stamps_dev) {
+    drain.dismiss();                                   // (the stream is idle behind the download of the labels)
+    return OK;
+  }
+  // the slots, the scratch offsets and the sub-ranges
+  const size_t ng = w.gtab_h.size() / 4, cap = (size_t)p.scratch_bytes / sizeof(double);
+  std::vector<int> sub_first{0};                       // the first group of every sub-range
+  size_t used = 0, most = 0;
+  long long slot = 0;
+  for (size_t g = 0; g < ng; ++g) {
+    const size_t n = (size_t)w.gtab_h[4 * g + 2], need = (size_t)nb * n * n;
+    if (used + need > cap) {
+      sub_first.push_back((int)g);
+      used = 0;
+    }
+    w.gtab_h[4 * g] = (long long)used;
+    w.gtab_h[4 * g + 1] = slot;
+    w.gtab_h[4 * g + 3] = (long long)sub_first.size() - 1;
+    used += need;
+    most = std::max(most, used);
+    slot += (long long)n;
+  }
+  sub_first.push_back((int)ng);
+  w.grows_h.resize((size_t)nr);
+  for (int i = 0; i < nr; ++i) {
+    const size_t g = (size_t)w.rtab_h[2 * (size_t)i];
+    w.grows_h[(size_t)w.gtab_h[4 * g + 1] + (size_t)w.rtab_h[2 * (size_t)i + 1]] = r0 + i;
+  }
+  DV_TRY(w.rtab.ensure(2 * (size_t)nr));
+  DV_TRY(w.grows.ensure((size_t)nr));
+  DV_TRY(w.gtab.ensure(4 * ng));
+  DV_TRY(w.scratch.ensure(std::max<size_t>(most, 1)));
+  DV_HIP(hipMemcpyAsync(w.rtab, w.rtab_h.data(), 2 * (size_t)nr * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(w.grows, w.grows_h.data(), (size_t)nr * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(w.gtab, w.gtab_h.data(), 4 * ng * sizeof(long long), hipMemcpyHostToDevice, s));
+  // (a stamp wholly outside its field has no pair: its G_ii and h_i are the empty sums)
+  DV_HIP(hipMemsetAsync(rows.gram + (size_t)r0 * nb, 0, (size_t)nr * nb * sizeof(double), s));
+  DV_HIP(hipMemsetAsync(rows.proj + (size_t)r0 * nb, 0, (size_t)nr * nb * sizeof(double), s));
+  for (size_t k = 0; k + 1 < sub_first.size(); ++k) {
+    const int ga = sub_first[k], gz = sub_first[k + 1];
+    if (gz <= ga) continue;
+    const size_t last = (size_t)gz - 1, n = (size_t)w.gtab_h[4 * last + 2];
+    const size_t elems = (size_t)w.gtab_h[4 * last] + (size_t)nb * n * n;
+    DV_HIP(hipMemsetAsync(w.scratch, 0, elems * sizeof(double), s));
+    if (npairs > 0) {
+#define DV_FG_GRAM(WT)                                                                                                          \
+  hipLaunchKernelGGL((fitflux_gram_kernel<WT, 0, true>), dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, (const int*)w.pairs.get(), \
+                     stamps_dev, places_dev, sfield_dev, (const int*)nullptr, (const long long*)nullptr, 0, f0, cs, nb, F,     \
+                     data_dev, w.scratch.get(), rows.gram, rows.proj, weight_dev, (const int*)w.rtab.get(),                    \
+                     (const long long*)w.gtab.get(), r0, (int)k)
+      if (weight_dev) DV_FG_GRAM(true); else DV_FG_GRAM(false);
+#undef DV_FG_GRAM
+    }
+    hipLaunchKernelGGL((fitflux_solve_kernel<0, true>), dim3((unsigned)(gz - ga), (unsigned)nb), dim3(MS_THREADS), 0, s,
+                       (const int*)nullptr, (const long long*)nullptr, ga, nb, p.min_pivot, w.scratch.get(),
+                       (const double*)rows.gram, (const double*)rows.proj, rows.scale, rows.var, rows.status, (const double*)nullptr,
+                       (double*)nullptr, (double*)nullptr, (int*)nullptr, (const int*)w.grows.get(), (const long long*)w.gtab.get());
+    DV_HIP(hipGetLastError());
+  }
+  if (weight_dev) {
+    hipLaunchKernelGGL((fitflux_chi2_kernel<0>), dim3((unsigned)nr), dim3(MS_THREADS), 0, s, adj_ptr, (const int*)w.adj.get(), r0,
+                       stamps_dev, places_dev, sfield_dev, f0, cs, nb, F, data_dev, weight_dev, (const double*)rows.scale,
+                       (const int*)rows.status, rows.chi2, rows.npix, (const double*)nullptr, (const int*)nullptr);
+    DV_HIP(hipGetLastError());
+  }
+  DV_HIP(hipStreamSynchronize(s));
+  drain.dismiss();
+  return OK;
+}
+
+// host arrays in, host rows out, whole fields at a time, as scene_fit_flux takes them: half of free device memory beside the
+// scratch for the stamps, tables, rows and fields of a chunk
+int scene_fit_flux_groups(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
+                          const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, int32_t* group_h,
+                          int32_t* gsize_h, int device, hipStream_t s, const double* weight_h) {
+  const char* who = "dv_scene_fit_flux_groups";
+  const bool weighted = weight_h != nullptr;
+  DV_TRY(fitflux_check(who, cs, nb, F, p));
+  if (N < 0 || M < 0 || !field_ptr || (N > 0 && (!data_h || !stamps_h || !places_h))) {
+    set_error("%s: stamps, places, field_ptr and data_fields must all be given", who);
+    return E_INVALID;
+  }
+  DV_TRY(fitflux_rows_check(who, out_h, N, weighted));
+  if (!weighted && (out_h.chi2 || out_h.npix)) {
+    set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: without weight_fields both must be NULL", who);
+    return E_INVALID;
+  }
+  if (N > 0 && (!group_h || !gsize_h)) {
+    set_error("%s: fit_group and fit_group_size must all be given", who);
+    return E_INVALID;
+  }
+  DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));
+  if (N == 0) return OK;
+  FitFluxRows d{};
+  Rows out;
+  fitflux_columns(out, d, out_h, nb, weighted, false);
+  const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
+  // per stamp: the stamp, placement and field, the rows, and the tables of the grouping (counts, scans, labels, group tables)
+  const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + out.bytes() + 12 * sizeof(int) + 4 * sizeof(long long);
+  const size_t per_field = (weighted ? 2 : 1) * felems * sizeof(double) + sizeof(int);
+  DV_HIP(hipSetDevice(device));
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t budget = free_b / 2 > (size_t)p.scratch_bytes ? free_b / 2 - (size_t)p.scratch_bytes : 0;
+  std::vector<int> cuts{0};
+  size_t cmax_s = 0, cmax_f = 0;
+  for (int f = 0; f < M;) {
+    size_t bytes = 0;
+    int g = f;
+    while (g < M) {
+      const size_t add = (size_t)(field_ptr[g + 1] - field_ptr[g]) * per_stamp + per_field;
+      if (g > f && bytes + add > budget) break;
+      bytes += add;
+      ++g;
+    }
+    if (bytes > budget) {
+      set_error("%s: field %d with its %ld stamps needs %zu bytes of device memory, %zu are available", who, f,
+                (long)(field_ptr[f + 1] - field_ptr[f]), bytes, budget);
+      return E_NOMEM;
+    }
+    cmax_s = std::max(cmax_s, (size_t)(field_ptr[g] - field_ptr[f]));
+    cmax_f = std::max(cmax_f, (size_t)(g - f));
+    cuts.push_back(g);
+    f = g;
+  }
+  FitGroupsWork work;
+  DevBuf<float> stamps;
+  DevBuf<double> data, wdata;
+  DevBuf<int> places, sf, fptr;
+  DV_TRY(stamps.alloc(cmax_s * stamp));
+  DV_TRY(places.alloc(cmax_s * 2));
+  DV_TRY(sf.alloc(cmax_s));
+  DV_TRY(fptr.alloc(cmax_f + 1));
+  DV_TRY(data.alloc(cmax_f * felems));
+  if (weighted) DV_TRY(wdata.alloc(cmax_f * felems));
+  DV_TRY(out.alloc((int64_t)cmax_s));
+  std::vector<int> sf_h, fptr_h;
+  StreamDrain drain(s);
+  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+    const int fa = cuts[k], fz = cuts[k + 1];          // fields fa .. fz - 1, their rows counted from the chunk's first
+    const int64_t r0 = field_ptr[fa], n = field_ptr[fz] - r0;
+    if (n == 0) continue;
+    fptr_h.assign((size_t)(fz - fa) + 1, 0);
+    sf_h.assign((size_t)n, 0);
+    for (int f = fa; f < fz; ++f) {
+      fptr_h[(size_t)(f - fa) + 1] = (int)(field_ptr[f + 1] - r0);
+      for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) sf_h[(size_t)(i - r0)] = f - fa;
+    }
+    DV_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)r0 * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(places, places_h + (size_t)r0 * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), fptr_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
+    if (weighted)
+      DV_HIP(hipMemcpyAsync(wdata, weight_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
+    DV_TRY(launch_fit_flux_groups(who, stamps, places, sf, fptr, data, 0, fptr_h.data(), 0, fz - fa - 1, fa, cs, nb, F, p, work, d,
+                                  group_h + r0, gsize_h + r0, s, weighted ? wdata.get() : nullptr));
+    DV_TRY(out.download(r0, n, s));
+    DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next chunk
+  }
+  drain.dismiss();
+  return OK;
+}
+
+// the blend groups alone, from the placements: no stamps, no fit, no limit on a group.  n_pairs / n_adj are always written;
+// pairs [n_pairs][2], adj_ptr [N + 1] and adj [n_adj] - the lists the fit works from, rows of the call - where they are given
+int scene_fit_groups(const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int M, int F, int32_t* group_h,
+                     int32_t* gsize_h, int64_t pair_cap, int64_t* n_pairs, int32_t* pairs_h, int64_t adj_cap, int64_t* n_adj,
+                     int32_t* adj_ptr_h, int32_t* adj_h, int device, hipStream_t s) {
+  const char* who = "dv_scene_fit_groups";
+  DV_TRY(fitflux_check(who, cs, 1, F, FitFluxParams{0.5, 1}));
+  if (N < 0 || M < 0 || !field_ptr || !n_pairs || !n_adj || (N > 0 && (!places_h || !group_h || !gsize_h))) {
+    set_error("%s: places, field_ptr, fit_group, fit_group_size, n_pairs and n_adj must all be given", who);
+    return E_INVALID;
+  }
+  if ((pairs_h == nullptr) != (adj_h == nullptr) || (pairs_h == nullptr) != (adj_ptr_h == nullptr)) {
+    set_error("%s: pairs, adj_ptr and adj go together (all given or all NULL)", who);
+    return E_INVALID;
+  }
+  std::vector<int32_t> sf_h;
+  std::vector<int> fptr_h;
+  DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, &sf_h, &fptr_h));
+  *n_pairs = *n_adj = 0;
+  if (adj_ptr_h) std::fill(adj_ptr_h, adj_ptr_h + N + 1, 0);
+  if (N == 0) return OK;
+  DV_HIP(hipSetDevice(device));
+  DevBuf<int> places, sf, fptr;
+  DV_TRY(places.alloc((size_t)N * 2));
+  DV_TRY(sf.alloc((size_t)N));
+  DV_TRY(fptr.alloc((size_t)M + 1));
+  FitGroupsWork work;
+  FitGroupsLists lists;
+  StreamDrain drain(s);
+  DV_HIP(hipMemcpyAsync(places, places_h, (size_t)N * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_TRY(launch_fit_flux_groups(who, nullptr, places, sf, fptr, nullptr, 0, fptr_h.data(), 0, M - 1, 0, cs, 1, F,
+                                FitFluxParams{0.5, 1}, work, FitFluxRows{}, group_h, gsize_h, s, nullptr, &lists));
+  drain.dismiss();
+  *n_pairs = (int64_t)(lists.pairs.size() / 2);
+  *n_adj = (int64_t)lists.adj.size();
+  if (pairs_h) {
+    if (*n_pairs > pair_cap || *n_adj > adj_cap) {
+      set_error("%s: %ld pairs and %ld adjacency entries, the arrays given hold %ld and %ld", who, (long)*n_pairs, (long)*n_adj,
+                (long)pair_cap, (long)adj_cap);
+      return E_INVALID;
+    }
+    std::copy(lists.pairs.begin(), lists.pairs.end(), pairs_h);
+    std::copy(lists.adj_ptr.begin(), lists.adj_ptr.end(), adj_ptr_h);
+    std::copy(lists.adj.begin(), lists.adj.end(), adj_h);
+  }
   return OK;
 }
 

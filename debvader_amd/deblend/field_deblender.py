@@ -139,6 +139,16 @@ _EXTRAS = (
            lambda c: ms.fit_flux_weighted_dtype(c.bands)[len(ms.fit_flux_dtype(c.bands)):],
            lambda out, c: _fit_weight_records(out, c),
            refines="fit_flux"),
+    # (behind fit_weights, whose call it replaces: it passes the weights on.  deblend_fields refuses it together with the two
+    # refining extras below, so its call is never replaced by theirs)
+    _Extra("fit_groups", bool, "fit_groups=True", "needs", "the flux fit by blend groups",
+           "fit_groups=True needs fit_flux=True: it solves the flux fit blend group by blend group, without a limit on the "
+           "galaxies of a field",
+           "dv_infer_fields_measure_fit_groups", "infer_fields_measure_fit_groups", True,
+           lambda c: dict(band=c.band, weight_fields=c.fit_weights),
+           lambda c: ms.fit_groups_dtype(c.bands),
+           lambda out, c: ms.fit_groups_records(out["fit_group"], out["fit_group_size"]),
+           refines="fit_flux"),
     # (behind fit_weights, which refines the same extra: the call of the LAST refining extra given serves the others too - this
     # one passes the weights on)
     _Extra("fit_sky", lambda v: v is not None, "fit_sky", "needs", "the flux fit with a sky background",
@@ -626,6 +636,12 @@ class DeblendFieldBatch:
         return ms.fit_nonneg_dtype(nb_of_bands)
 
     @staticmethod
+    def fit_groups_columns(nb_of_bands):
+        """What deblend_fields(measure=True, fit_flux=True, fit_groups=True) appends behind the columns of the flux fit
+        (fit_flux_columns, or fit_flux_weighted_columns with fit_weights): fit_group and fit_group_size."""
+        return ms.fit_groups_dtype(nb_of_bands)
+
+    @staticmethod
     def fit_flux_weighted_columns(nb_of_bands):
         """What deblend_fields(measure=True, fit_flux=True, fit_weights=W) appends behind measure_columns: the recarray of
         fit_fluxes_weighted - fit_flux_columns, then fit_chi2 and fit_npix."""
@@ -712,7 +728,7 @@ class DeblendFieldBatch:
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
                        measure=False, return_fields=True, measure_samples=0, blendedness=False,
                        psf=None, psf_index=None, apertures=None, flux_fractions=None, aperture_data=False,
-                       sky_sigma=None, fit_flux=False, fit_weights=None, fit_nonneg=False, fit_sky=None,
+                       sky_sigma=None, fit_flux=False, fit_groups=False, fit_weights=None, fit_nonneg=False, fit_sky=None,
                        optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
@@ -832,16 +848,28 @@ class DeblendFieldBatch:
         the recarrays gain, behind every other column, fit_nonneg_columns: fit_scale_free and flux_fit_free, the amplitude and
         flux of the fit without the constraint, fit_clamped and fit_dual (debvader_amd.measure.measurement.fit_fluxes_nonneg
         describes them).  self.nonneg_fit holds the per-field arrays nonneg_iters and nonneg_status of the pass.  A field and
-        band without a negative amplitude keeps the values of the call without it.  It changes no other refusal of fit_flux."""
+        band without a negative amplitude keeps the values of the call without it.  It changes no other refusal of fit_flux.
+
+        fit_groups=True (with fit_flux=True, with or without fit_weights, sky_sigma and return_fields): the flux fit is solved
+        blend group by blend group (dv_infer_fields_measure_fit_groups) - the connected components of
+        the graph of stamps whose rectangles, clipped to the field, intersect.  A field may then hold any number of galaxies
+        (1024 per group), and the columns of the flux fit keep the bits of the fit without it wherever that one takes the
+        field.  The recarrays gain, behind the columns of fit_flux (and fit_chi2, fit_npix if weighted), fit_groups_columns:
+        fit_group, the smallest row of the galaxy's group in its field's recarray, and fit_group_size.  Together with fit_sky
+        or fit_nonneg it is a ValueError: those two are not built for the grouped fit yet."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
-        aperture_data, fit_flux, fit_nonneg = bool(aperture_data), bool(fit_flux), bool(fit_nonneg)
+        aperture_data, fit_flux, fit_nonneg, fit_groups = bool(aperture_data), bool(fit_flux), bool(fit_nonneg), bool(fit_groups)
         band = 2                        # the band of the measurement (r): the engine call and the blendedness in the apertures
         kw = dict(measure_samples=measure_samples, blendedness=blendedness, psf=psf, psf_index=psf_index, apertures=apertures,
                   flux_fractions=flux_fractions, aperture_data=aperture_data, fit_flux=fit_flux, fit_weights=fit_weights,
-                  fit_sky=fit_sky, fit_nonneg=fit_nonneg)
+                  fit_sky=fit_sky, fit_nonneg=fit_nonneg, fit_groups=fit_groups)
         given = [x.key for x in _EXTRAS if x.given(kw[x.key])]
+        if fit_groups and (fit_sky is not None or fit_nonneg):
+            raise ValueError("fit_groups=True cannot be combined with fit_sky or fit_nonneg: those two are not built for the "
+                             "grouped fit yet (the sky couples all groups of a field, and the non-negative fit reports per "
+                             "field and band)")
         for x in _EXTRAS[1:]:           # (measure_samples, the oldest, is refused below its own integer check)
             _refuse_extra(x, kw, given, measure, on_device, fit, mc)
         if sky_sigma is not None and not aperture_data and not fit_flux:

@@ -975,6 +975,51 @@ class Context:
                                         _dp(data), M, data.shape[1], C.byref(par), *ptrs))
         return out
 
+    def scene_fit_flux_groups(self, stamps, places, data_fields, field_ptr=None, min_pivot: float = 1e-8,
+                              scratch_bytes: int = 256 << 20, weight_fields=None) -> Dict[str, np.ndarray]:
+        """scene_fit_flux by blend groups (dv_scene_fit_flux_groups): the connected components of the
+        overlap graph of every field - two galaxies are adjacent iff their stamp rectangles, clipped to the field, intersect -
+        are found on the GPU and each is solved on its own.  A field may hold any number of galaxies; a group of more than 1024,
+        or whose bands x n_g x n_g doubles exceed scratch_bytes, is refused by name.  Arguments and the dictionary are
+        scene_fit_flux's, with weight_fields or without, with the bits of that call wherever it takes the field; two more
+        arrays (N,) int32: "fit_group", the smallest row of the galaxy's group counted from the first row of its field, and
+        "fit_group_size", the members of that group."""
+        stamps, places, data, fp = _fit_scene_inputs(stamps, places, data_fields, field_ptr)
+        n, cs, nb = stamps.shape[0], stamps.shape[1], stamps.shape[3]
+        par = fit_flux_params(min_pivot, scratch_bytes)
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, data.shape)
+        out, ptrs = _fit_flux_out(n, nb, weights is not None)
+        if weights is None:
+            ptrs += [None, None]
+        out["fit_group"], out["fit_group_size"] = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        if n:
+            check(lib.dv_scene_fit_flux_groups(self._h, _fp(stamps), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs,
+                                               nb, _dp(data), data.shape[0], data.shape[1], C.byref(par),
+                                               None if weights is None else _dp(weights), *ptrs, _ip(out["fit_group"]),
+                                               _ip(out["fit_group_size"])))
+        return out
+
+    def scene_fit_groups(self, places, cutout_size: int, field_size: int, field_ptr=None, lists: bool = False) -> Dict[str, np.ndarray]:
+        """The blend groups of scene_fit_flux_groups from the placements alone (dv_scene_fit_groups): places (N, 2), stamps of
+        cutout_size pixels in fields of field_size; field_ptr (M + 1,), None: one field.  No fit, no limit on a group.  Returns
+        {"fit_group", "fit_group_size"} (N,) int32 and, with lists=True, the lists the fit works from in rows of the call:
+        "pairs" (n_pairs, 2), the adjacent (i, j <= i) sorted by i and then j, and the CSR adjacency "adj_ptr" (N + 1,) / "adj"
+        with ascending lists."""
+        places = _i32_rows(places, "stamp placements") if len(places) else np.zeros((0, 2), np.int32)
+        n = places.shape[0]
+        fp = check_field_ptr([0, n] if field_ptr is None else field_ptr, 1 if field_ptr is None else len(field_ptr) - 1, n)
+        M = fp.shape[0] - 1
+        out = dict(fit_group=np.zeros(n, np.int32), fit_group_size=np.zeros(n, np.int32))
+        np_, na = C.c_int64(0), C.c_int64(0)
+        args = [self._h, _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n, int(cutout_size), M, int(field_size),
+                _ip(out["fit_group"]), _ip(out["fit_group_size"])]
+        check(lib.dv_scene_fit_groups(*args, 0, C.byref(np_), None, 0, C.byref(na), None, None))
+        if lists:
+            out.update(pairs=np.zeros((np_.value, 2), np.int32), adj_ptr=np.zeros(n + 1, np.int32), adj=np.zeros(na.value, np.int32))
+            check(lib.dv_scene_fit_groups(*args, np_.value, C.byref(np_), _ip(out["pairs"]), na.value, C.byref(na),
+                                          _ip(out["adj_ptr"]), _ip(out["adj"])))
+        return out
+
     def scene_fit_flux_gram(self, stamps, places, data_field) -> Dict[str, np.ndarray]:
         """Step 1 of scene_fit_flux for the galaxies of one field (dv_scene_fit_flux_gram): stamps (n, cs, cs, bands), places
         (n, 2), data_field (F, F, bands).  Returns {"gram" (bands, n, n): G_ij = sum P_i P_j over the field pixels both
@@ -1721,6 +1766,38 @@ class Engine:
     def scene_fit_flux(self, stamps, places, data_fields, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_fit_flux on this engine's GPU context."""
         return self.ctx.scene_fit_flux(stamps, places, data_fields, **kw)
+
+    def infer_fields_measure_fit_groups(self, fields, starts, field_ptr, places, weight_fields=None, seed=0, band: int = 2,
+                                        sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, min_pivot: float = 1e-8,
+                                        scratch_bytes: int = 256 << 20, return_fields=True, residual=True,
+                                        mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_fit[_weighted]() by blend groups (dv_infer_fields_measure_fit_groups): no
+        limit on the galaxies of a field, 1024 per group.  Returns infer_fields_measure's dictionary, bit for bit, plus
+        scene_fit_flux_groups' - with "fit_chi2" and "fit_npix" iff weight_fields is given - with the bits of that call on
+        infer_fields_keep's mean stamps."""
+        places = Engine._measure_places(places, return_fields, "places are needed for the flux fit, with return_fields=False too")
+        fields = _check_fields(fields)
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, fields.shape)
+
+        def extras(N, nb):
+            fpar = fit_flux_params(min_pivot, scratch_bytes)
+            ff, ff_ptrs = _fit_flux_out(N, nb, weights is not None)
+            if weights is None:
+                ff_ptrs += [None, None]
+            ff["fit_group"], ff["fit_group_size"] = np.zeros(N, np.int32), np.zeros(N, np.int32)
+            return [(ff, [C.byref(fpar), None if weights is None else _dp(weights)] + ff_ptrs +
+                     [_ip(ff["fit_group"]), _ip(ff["fit_group_size"])])]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_fit_groups, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
+
+    def scene_fit_flux_groups(self, stamps, places, data_fields, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_fit_flux_groups on this engine's GPU context."""
+        return self.ctx.scene_fit_flux_groups(stamps, places, data_fields, **kw)
+
+    def scene_fit_groups(self, places, cutout_size, field_size, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_fit_groups on this engine's GPU context."""
+        return self.ctx.scene_fit_groups(places, cutout_size, field_size, **kw)
 
     def infer_fields_measure_fit_sky(self, fields, starts, field_ptr, places, sky_order: int = 0, weight_fields=None, seed=0,
                                      band: int = 2, sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200,

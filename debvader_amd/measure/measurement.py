@@ -641,6 +641,65 @@ def _fit_fluxes(stamps_mean, places, data_fields, weight_fields, field_ptr, cata
                             sky_sigma=sky_sigma, field_ptr=field_ptr)
 
 
+def fit_groups_dtype(nb_of_bands):
+    """The two columns a flux fit by blend groups adds per galaxy; they do not depend on the band."""
+    int(nb_of_bands)
+    return [("fit_group", "<i4"), ("fit_group_size", "<i4")]
+
+
+def fit_groups_records(fit_group, fit_group_size):
+    """The recarray of fit_groups_dtype from the two arrays (N,) of scene_fit_flux_groups: fit_group, the smallest row of the
+    galaxy's blend group counted from the first row of its field, and fit_group_size, the members of that group."""
+    group = np.asarray(fit_group, dtype=np.int32)
+    size = np.asarray(fit_group_size, dtype=np.int32)
+    if group.ndim != 1 or size.shape != group.shape:
+        raise ValueError(f"expected fit_group and fit_group_size (N,), got {group.shape} and {size.shape}")
+    rec = np.recarray(group.shape, dtype=fit_groups_dtype(1))
+    rec["fit_group"], rec["fit_group_size"] = group, size
+    return rec
+
+
+def fit_fluxes_groups(stamps_mean, places, data_fields, field_ptr=None, catalogue=None, sky_sigma=None, weights=None,
+                      min_pivot=1e-8, ctx=None):
+    """fit_fluxes, or fit_fluxes_weighted with `weights`, solved blend group by blend group on the GPU:
+    the connected components of the graph of stamps whose rectangles, clipped to their field, intersect are found on the GPU
+    and each is fitted on its own.  A field may hold any number of galaxies; a group of more than 1024 is refused.
+
+    parameters: those of fit_fluxes, and
+        weights: the weight fields of fit_fluxes_weighted, or None: the unweighted fit; with them sky_sigma must stay None
+    returns a np.recarray of the columns of fit_fluxes (of fit_fluxes_weighted with weights) - the same bits wherever that
+    call takes the field - and then fit_group, the smallest row of the galaxy's group counted from the first row of its field,
+    and fit_group_size, the members of that group (fit_groups_dtype)."""
+    data = np.asarray(data_fields, dtype=np.float64)
+    if data.ndim == 3:
+        data = data[None]
+    M = data.shape[0]
+    if weights is not None:
+        if sky_sigma is not None:
+            raise ValueError(WEIGHTS_CARRY_THE_NOISE)
+        weights = E.check_fit_weights(weights, data.shape)                   # (ValueError before any GPU work)
+    if data.ndim == 4 and sky_sigma is not None:
+        check_sky_sigma(sky_sigma, M, data.shape[-1])                        # (ValueError before any GPU work)
+    stamps = np.asarray(stamps_mean, dtype=np.float32)
+    if field_ptr is None and M == 1:
+        field_ptr = [0, stamps.shape[0]]
+    if catalogue is None:
+        flux = stamps.sum(axis=(1, 2), dtype=np.float64) if stamps.ndim == 4 else None
+    else:
+        if "flux" not in catalogue.dtype.names:
+            raise ValueError("the catalogue lacks the column flux: fit_fluxes_groups takes the measure_stamps recarray of the galaxies")
+        flux = np.asarray(catalogue["flux"], dtype=np.float64)
+    if ctx is None:
+        ctx = E.default_context()
+    out = ctx.scene_fit_flux_groups(stamps, places, data, field_ptr=field_ptr, min_pivot=min_pivot, weight_fields=weights)
+    if weights is not None:
+        fit = fit_flux_records(*(out[k] for k in E.FIT_FLUX_KEYS), flux, field_ptr=field_ptr, fit_chi2=out["fit_chi2"],
+                               fit_npix=out["fit_npix"])
+    else:
+        fit = fit_flux_records(*(out[k] for k in E.FIT_FLUX_KEYS), flux, sky_sigma=sky_sigma, field_ptr=field_ptr)
+    return _join_records(fit, fit_groups_records(out["fit_group"], out["fit_group_size"]))
+
+
 def _join_records(*recs):
     """One recarray with the columns of several of the same length, in their order"""
     out = np.recarray((len(recs[0]),), dtype=[d for r in recs for d in r.dtype.descr])

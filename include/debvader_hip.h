@@ -731,6 +731,46 @@ int dv_infer_fields_measure_fit_weighted(dv_model* m, const double* fields, int3
                                          const dv_fit_flux_params* fit, const double* weight_fields, double* fit_scale,
                                          double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status,
                                          double* fit_chi2, int32_t* fit_npix);
+/* The same fit by blend groups: no limit on the galaxies of a field.  Two galaxies of a field are
+ * ADJACENT iff their stamp rectangles, clipped to the field, intersect (a stamp wholly outside its field is adjacent to
+ * nothing, itself included); a BLEND GROUP is a connected component of that graph.  The groups depend on the placements alone,
+ * not on the band, the weights or eligibility.  Two more outputs [N] int32: fit_group, the smallest row of the galaxy's group
+ * counted from the first row of its field, and fit_group_size, the members of that group.  The neighbours are listed and the
+ * components labelled on the GPU (an ordered compaction and min-label propagation with pointer jumping: no result depends on
+ * the order of the threads); the host takes the labels, 4 bytes per galaxy, and orders the groups of a field by fit_group, the
+ * members of a group staying in ascending row order.  Steps 1 - 5 (and the chi-square of the weighted fit) then run per group
+ * as they run per field above: a group is the unit of scratch, nb n_g n_g doubles, and of solve workgroup; the field stays
+ * the unit of data_fields and weight_fields.  Galaxies of different groups share no term, so on a field the dense calls take,
+ * every output has the bits of dv_scene_fit_flux (weight_fields NULL; fit_chi2 and fit_npix NULL with it) or
+ * dv_scene_fit_flux_weighted, as long as the factors are finite.  Refused before any GPU work (DV_E_INVALID, the engine stays
+ * usable): what those two calls refuse except the count per field, a missing fit_group or fit_group_size, chi-square outputs
+ * that do not match the weights.  Refused behind the labelling and before any solve (DV_E_INVALID, the stream idle, the engine
+ * usable): a group of more than DV_FIT_MAX_N galaxies - "field f: the blend group of row r has n galaxies, the grouped fit
+ * takes at most 1024 per group" - and a group whose nb n_g n_g doubles exceed scratch_bytes; both name the field, the group's
+ * first row (counted from the field's first row) and its size.
+ * dv_infer_fields_measure_fit_groups: dv_infer_fields_measure_fit_weighted with weight_fields nullable (fit_chi2 and fit_npix
+ * NULL exactly then) plus the two outputs, at the completed-field seam on the same stamp store, with and without the result
+ * fields: the bits of dv_scene_fit_flux_groups on dv_infer_fields_keep's mean stamps.  The group refusals come from the seam:
+ * the catalogue rows of the call are then not delivered.
+ * dv_scene_fit_groups: the groups alone from the placements - no stamps, no fit, no limit on a group - and, where pairs, adj_ptr
+ * and adj are all given, the lists the fit works from, in rows of the call: pairs [n_pairs][2], the adjacent (i, j <= i) sorted
+ * by i and then j, and the CSR adjacency adj_ptr [N + 1] / adj [n_adj] with ascending lists.  n_pairs and n_adj are always
+ * written; lists shorter than them (pair_cap, adj_cap entries) are refused, so a caller asks twice. */
+int dv_scene_fit_flux_groups(dv_ctx* ctx, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                             int32_t cs, int32_t nb, const double* data_fields, int32_t M, int32_t F,
+                             const dv_fit_flux_params* params, const double* weight_fields, double* fit_scale, double* fit_var,
+                             double* fit_gram, double* fit_proj, int32_t* fit_status, double* fit_chi2, int32_t* fit_npix,
+                             int32_t* fit_group, int32_t* fit_group_size);
+int dv_infer_fields_measure_fit_groups(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                       const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                       const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                       double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                       int32_t* iters, int32_t* status, const dv_fit_flux_params* fit, const double* weight_fields,
+                                       double* fit_scale, double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status,
+                                       double* fit_chi2, int32_t* fit_npix, int32_t* fit_group, int32_t* fit_group_size);
+int dv_scene_fit_groups(dv_ctx* ctx, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs, int32_t M, int32_t F,
+                        int32_t* fit_group, int32_t* fit_group_size, int64_t pair_cap, int64_t* n_pairs, int32_t* pairs,
+                        int64_t adj_cap, int64_t* n_adj, int32_t* adj_ptr, int32_t* adj);
 /* The same fit with a sky background fitted jointly: q terms per field and band beside the amplitudes,
  * sky_order 0: q = 1, a constant; sky_order 1: q = 3, a plane.  Per field of side F and pixel (r, c): B_0 = 1, B_1 = (double)
  * (2 r - F + 1) / (double)F, B_2 = (double)(2 c - F + 1) / (double)F; the model is D(p) = sum_i a_i P_i(p) + sum_t s_t B_t(p)

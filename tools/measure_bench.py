@@ -121,6 +121,18 @@ alternating -
 It also prints how many (field, band) systems took 0, 1, 2, ... factorisations (nonneg_iters) in legs (b) and (d), and how many
 galaxy-bands were clamped.  With --profile-one: warm up, one fp32 call (d), exit.
 
+--fit-groups: the flux fit by blend groups, in the same protocol, two legs:
+
+    (a) catalogue+fit-flux / catalogue+fit-flux+groups :  the catalogue-only call with fit_flux=True, dense and then with
+                                                          fit_groups=True, alternating in one process; it also prints the
+                                                          histogram of fit_group_size
+    (b) one field of --tile pixels (4096) with --tile-stamps (20000) stamps of 31 pixels in 3 bands, the places a seeded uniform
+        draw, through Context.scene_fit_flux_groups: time alone - the dense call refuses this field.  A draw with a group above
+        1024 is thinned (every second member of such a group leaves, until none is left) and the run says so; the histogram of
+        the group sizes is printed.
+
+    python tools/measure_bench.py --fit-groups [--fields 1024] [--size 259] [--repeat 5] [--tile 4096] [--tile-stamps 20000]
+
 The cost is reported, not gated.
 """
 import argparse
@@ -274,7 +286,7 @@ def main_fit_flux(a):
     fields = np.ascontiguousarray(base[np.arange(M) % 16])
     quiet = io.StringIO()
     result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "fit_flux": True, "fit_weights": bool(a.fit_weights),
-              "fit_sky": a.fit_sky, "fit_nonneg": bool(a.fit_nonneg)}
+              "fit_sky": a.fit_sky, "fit_nonneg": bool(a.fit_nonneg), "fit_groups": bool(a.fit_groups)}
     weights = None
     if a.fit_weights or a.fit_sky is not None:
         w16 = rng.uniform(0.25, 4.0, size=base.shape)
@@ -288,19 +300,23 @@ def main_fit_flux(a):
             dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
             print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections, at most {max(len(d) for d in dists)} "
                   f"per field; max_batch {a.max_batch}")
-        seen, nonneg = [], {}
+        seen, nonneg, sizes = [], {}, []
 
         def with_fit(**kw):
             batch = DeblendFieldBatch(net, fields)
             res = batch.deblend_fields(dists, on_device=True, measure=True, return_fields=False, fit_flux=True, **kw)
             seen[:] = [np.concatenate([r["fit_status"] for r in res]), np.concatenate([r["fit_independence"] for r in res])]
+            if kw.get("fit_groups"):
+                sizes[:] = [np.concatenate([r["fit_group_size"][r["fit_group"] == np.arange(len(r))] for r in res])]
             if batch.nonneg_fit is not None:      # per leg (keyed by its sky): the iterations and the clamped galaxy-bands
                 nonneg[kw.get("fit_sky")] = (np.bincount(batch.nonneg_fit["nonneg_iters"].ravel()).tolist(),
                                              int(batch.nonneg_fit["nonneg_status"].sum()),
                                              int(sum(r["fit_clamped"].sum() for r in res)), int(seen[0].size))
             return sum(len(r) for r in res)
 
-        if a.fit_nonneg:
+        if a.fit_groups:
+            legs = {"catalogue+fit-flux": with_fit, "catalogue+fit-flux+groups": lambda: with_fit(fit_groups=True)}
+        elif a.fit_nonneg:
             legs = {"catalogue+fit-flux": with_fit, "catalogue+fit-flux+nonneg": lambda: with_fit(fit_nonneg=True),
                     "catalogue+fit-flux+sky": lambda: with_fit(fit_sky=1),
                     "catalogue+fit-flux+sky+nonneg": lambda: with_fit(fit_sky=1, fit_nonneg=True)}
@@ -347,8 +363,55 @@ def main_fit_flux(a):
             print(f"{dtype} fit_nonneg{'' if sky is None else f' with fit_sky={sky}'}: (field, band) systems by nonneg_iters 0, 1, 2, ... "
                   f"{iters}; {capped} reached max_iter; {clamped} of {total} galaxy-bands clamped")
             result[dtype]["nonneg_iters" + ("" if sky is None else "_sky")] = iters
+        if sizes:
+            hist = np.bincount(sizes[0]).tolist()
+            print(f"{dtype} fit_groups: {len(sizes[0])} blend groups; groups by fit_group_size 0, 1, 2, ... {hist}")
+            result[dtype]["group_sizes"] = hist
         net._core.engine.close()
+    if a.fit_groups:
+        result["tile"] = main_fit_groups_tile(a)
     print(json.dumps(result))
+
+
+def main_fit_groups_tile(a):
+    """Leg (b) of --fit-groups: one large field beyond the dense limit, host arrays in, time alone"""
+    from debvader_amd import engine as E
+    from tests import fit_flux_oracle as fo
+
+    F, n, cs, nb = a.tile, a.tile_stamps, 31, 3
+    rng = np.random.default_rng(11)
+    places = rng.integers(-cs // 2, F - cs // 2, size=(n, 2)).astype(np.int32)
+    ctx = E.default_context()
+    thinned = 0
+    while True:                                  # thin the groups the fit would refuse: every second member leaves
+        g = ctx.scene_fit_groups(places, cs, F)
+        big = g["fit_group_size"] > E.FIT_FLUX_MAX_N
+        if not big.any():
+            break
+        drop = np.nonzero(big)[0][::2]
+        thinned += len(drop)
+        places = np.delete(places, drop, axis=0)
+    n = len(places)
+    roots = g["fit_group"] == np.arange(n)
+    sizes = g["fit_group_size"][roots]
+    edges = [1, 2, 3, 5, 9, 17, 33, 65, 129, 257, 513, 1025]
+    hist = np.histogram(sizes, bins=edges)[0].tolist()
+    blobs = np.stack([fo.elliptical_gaussian(cs, (rng.uniform(3, 8), 0.0, rng.uniform(3, 8))) for _ in range(64)])
+    stamps = (blobs[rng.integers(0, 64, n)][..., None] * rng.uniform(0.5, 2.0, size=(n, 1, 1, nb))).astype(np.float32)
+    data = rng.normal(0.0, 0.05, size=(1, F, F, nb))
+    ctx.scene_fit_flux_groups(stamps, places, data)                  # warm-up
+    t = []
+    for _ in range(a.repeat):
+        t0 = time.perf_counter()
+        out = ctx.scene_fit_flux_groups(stamps, places, data)
+        t.append(time.perf_counter() - t0)
+    t = np.array(t)
+    print(f"tile of {F} px, {n} stamps of {cs} px x {nb} bands ({thinned} thinned out of groups above {E.FIT_FLUX_MAX_N}): "
+          f"{int(roots.sum())} blend groups, the largest {int(sizes.max())}; groups by size [1, 2, 3-4, 5-8, ..., 513-1024]: {hist}")
+    print(f"scene_fit_flux_groups, host arrays in and out: median {1e3 * np.median(t):.1f} ms, min {1e3 * t.min():.1f}, max "
+          f"{1e3 * t.max():.1f} over {a.repeat} runs; fit_status 0 .. 5: {np.bincount(out['fit_status'].ravel(), minlength=6).tolist()}")
+    return {"F": F, "stamps": n, "thinned": thinned, "groups": int(roots.sum()), "largest": int(sizes.max()), "size_hist": hist,
+            "ms": [round(1e3 * x, 2) for x in t]}
 
 
 def _bench_psfs(M, ps=21):
@@ -507,8 +570,11 @@ def main():
     ap.add_argument("--fit-weights", action="store_true")
     ap.add_argument("--fit-sky", type=int, choices=(0, 1), default=None, metavar="ORDER")
     ap.add_argument("--fit-nonneg", action="store_true")
+    ap.add_argument("--fit-groups", action="store_true")
+    ap.add_argument("--tile", type=int, default=4096)
+    ap.add_argument("--tile-stamps", type=int, default=20000)
     a = ap.parse_args()
-    if a.fit_flux or a.fit_weights or a.fit_sky is not None or a.fit_nonneg:
+    if a.fit_flux or a.fit_weights or a.fit_sky is not None or a.fit_nonneg or a.fit_groups:
         return main_fit_flux(a)
     if a.aperture_data:
         return main_apertures(a, data=True)
