@@ -223,6 +223,9 @@ SIGNATURES = {
                                            _d, _d, _i32, _i64, _d, _i32, _d, _i32, _i32]),
     "dv_infer_fields_measure_fit_nonneg": _measure_sig(C.POINTER(DvFitFluxParams), _d, C.c_int32, C.c_int32, _d, _d, _d, _d, _i32,
                                                        _d, _i32, _d, _d, _i32, _i64, _d, _i32, _d, _i32, _i32),
+    "dv_scene_moments_fields": (C.c_int, [_p, _f, _i32, _i64, C.c_int64, C.c_int32, C.c_int32, _d, _d, _d, C.c_int32, C.c_int32,
+                                          C.POINTER(DvMeasureParams), _d, _i32, _d, _i32, _i32]),
+    "dv_infer_fields_measure_moments_data": _measure_sig(_d, _d, _i32, _d, _i32, _i32),
     "dv_field_set_open":(C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),

@@ -325,6 +325,22 @@ int launch_measure(const float* mean_dev, const float* stddev_dev, int n, int cs
                    int* status_dev, hipStream_t s);
 int scene_measure(const float* mean_h, const float* stddev_h, int64_t N, int cs, int nb, int band, double sigma0, double tol,
                   int max_iter, const CatRows& out_h, hipStream_t s);
+// the same moments on the observed field with the neighbours subtracted (moments_field.hip): per galaxy the child
+// image C = (D - T) + P where the stamp pixel counts (inside the field and, with weights, 0 < W < inf) and P elsewhere; its
+// per-band sums and counting pixels, and the adaptive moments of its band plane.  MomentsFieldRows: the output rows, device or
+// host - flux / npix [.][nb], shape [.][5], iters, status [.].  launch_moments_field: the complete fields fa .. fz, every
+// per-galaxy array counted from row 0 of the call like fptr_h; the field stacks start at field f0 (weight_dev null: no mask).
+// scene_moments_fields: host arrays, whole fields at a time within half of free device memory; every refusal before GPU work.
+size_t measure_lds_bytes(int cs);
+struct MomentsFieldRows { double* flux; int* npix; double* shape; int *iters, *status; };
+int moments_field_rows_check(const char* who, const MomentsFieldRows& o, int64_t n);
+int launch_moments_field(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const double* model_dev,
+                         const double* data_dev, const double* weight_dev, int f0, const int* fptr_h, int fa, int fz, int cs,
+                         int nb, int band, int F, double sigma0, double tol, int max_iter, const MomentsFieldRows& rows,
+                         hipStream_t s);
+int scene_moments_fields(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
+                         const double* model_h, const double* data_h, const double* weight_h, int M, int F, int band,
+                         double sigma0, double tol, int max_iter, const MomentsFieldRows& out_h, int device, hipStream_t s);
 // Monte-Carlo catalogue (measure.hip): every sample stamp of a decoder pass measured without a stddev stamp into
 // scratch rows, the rows folded per galaxy (Welford, ascending sample order) into means and standard deviations of the nb
 // fluxes and of the 8 shape quantities {row, col, Mrr, Mrc, Mcc, sigma, e1, e2}.  McScratch: the rows of one pass (device).

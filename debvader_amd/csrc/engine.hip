@@ -3160,7 +3160,8 @@ struct PipeJob {
     ApertureRows rows{};               // device, row 0 = global stamp 0
   } ap;
   // the flux fit (dv_infer_fields_measure_fit) needs the mean stamps of a field once its last chunk has gone:
-  // behind every chunk's measurement its mean stamps are copied into store; store decides
+  // behind every chunk's measurement its mean stamps are copied into store; store decides.  The moments on the child image
+  // (dv_infer_fields_measure_moments_data) read the same store: one copy of the chunk serves both
   struct FitFlux {
     float* store = nullptr;            // device [.][cs][cs][nb], row 0 = global stamp 0
   } ff;
@@ -3951,6 +3952,21 @@ int dv_scene_fit_flux(dv_ctx* c, const float* stamps, const int32_t* places, con
   // (every refusal is scene_fit_flux's; budget 0: sized there, after them, against free device memory)
   return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, FitFluxParams{params->min_pivot, params->scratch_bytes},
                         FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status}, 0, c->device, c->stream);
+}
+
+// the adaptive moments on the child images D - T + P: every refusal is scene_moments_fields'
+int dv_scene_moments_fields(dv_ctx* c, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs,
+                            int32_t nb, const double* model_fields, const double* data_fields, const double* weight_fields,
+                            int32_t M, int32_t F, const dv_measure_params* params, double* flux_data, int32_t* npix_data,
+                            double* shape_data, int32_t* iters_data, int32_t* status_data) {
+  if (!c) return DV_E_INVALID;
+  if (!params) {
+    set_error("dv_scene_moments_fields: params must be given");
+    return DV_E_INVALID;
+  }
+  return scene_moments_fields(stamps, places, field_ptr, N, cs, nb, model_fields, data_fields, weight_fields, M, F, params->band,
+                              params->sigma0, params->tol, params->max_iter,
+                              MomentsFieldRows{flux_data, npix_data, shape_data, iters_data, status_data}, c->device, c->stream);
 }
 
 // the same fit under per-pixel weights: every refusal is scene_fit_flux's, the null weight fields are refused here
@@ -5297,6 +5313,26 @@ struct FitFluxStage {               // the simultaneous flux fit of every field'
   void bind(PipeJob::FitFlux& q) const { q.store = store; }
 };
 
+// dv_infer_fields_measure_moments_data (7x): the optional host weight fields [M][F][F][nb] in, the five rows out (host)
+struct MomentsFieldOut { MomentsFieldRows rows{}; const double* weights = nullptr; };
+
+struct MomentsFieldStage {          // the adaptive moments of every galaxy's child image D - T + P (7x)
+  DevBuf<float> store;              // the mean stamps of all N stamps, unless the flux fit keeps them already
+  DevBuf<double> wdev;              // the resident group of weight fields, unless the flux fit has uploaded the same ones
+  MomentsFieldRows dev{};
+  Rows rows;
+  void columns(const MomentsFieldOut& o, int nb) { moments_field_columns(rows, dev, o.rows, nb); }
+  size_t bytes_per_stamp(int cs, int nb, bool own_store) const {
+    return (own_store ? (size_t)cs * cs * nb * sizeof(float) : 0) + rows.bytes();
+  }
+  int alloc(int64_t N, int cs, int nb, bool own_store, size_t welems) {
+    if (own_store) DV_TRY(store.alloc((size_t)N * cs * cs * nb));
+    if (welems) DV_TRY(wdev.alloc(welems));
+    return rows.alloc(N);
+  }
+  void bind(PipeJob::FitFlux& q) const { if (store) q.store = store; }
+};
+
 // What a many-field call wants back, beside what its PipeJob streams to the host: each part is there or not.
 struct FieldsRequest {
   std::optional<FieldsOut> fields;              // the composited result fields
@@ -5308,8 +5344,9 @@ struct FieldsRequest {
   std::optional<ApertureOut> aper;
   std::optional<ApertureFieldOut> aper_field;   // reads the aperture rows: only with `aper`
   std::optional<FitFluxOut> fit_flux;
+  std::optional<MomentsFieldOut> moments;       // reads the completed composite, the source field and the kept mean stamps
   // host [N][2], where every stamp lies in its field.  Read when the call composites - result fields without a position fit,
-  // or a stage at the completed-field seam (blend, aper_field, fit_flux), with or without result fields - and not otherwise
+  // or a stage at the completed-field seam (blend, aper_field, fit_flux, moments), with or without result fields - and not otherwise
   const int32_t* places = nullptr;
 };
 
@@ -5318,7 +5355,7 @@ struct FieldsRequest {
 static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int64_t* field_ptr, int64_t N, PipeJob j,
                              const FieldsRequest& rq) {
   // check
-  if (((rq.mc || rq.blend || rq.regauss || rq.aper || rq.aper_field || rq.fit_flux) && !rq.cat) || (rq.aper_field && !rq.aper)) {
+  if (((rq.mc || rq.blend || rq.regauss || rq.aper || rq.aper_field || rq.fit_flux || rq.moments) && !rq.cat) || (rq.aper_field && !rq.aper)) {
     set_error("%s: the extras of a catalogue go with the catalogue, the apertures on the fields with the aperture rows", who);
     return DV_E_INVALID;
   }
@@ -5327,7 +5364,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (M > 0 && !fields) return DV_E_INVALID;
   std::vector<int32_t> sfield;
   std::vector<int> fptr32;
-  const int32_t* places = rq.fields || rq.blend || rq.aper_field || rq.fit_flux ? rq.places : nullptr;
+  const int32_t* places = rq.fields || rq.blend || rq.aper_field || rq.fit_flux || rq.moments ? rq.places : nullptr;
   DV_TRY(fields_tables(m, who, M, field_ptr, N, F, nb, j.starts, places, sfield, fptr32));
   const size_t felems = (size_t)F * F * nb, fb = felems * sizeof(double);
   FitFluxPlan ffplan;
@@ -5370,7 +5407,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   DevBuf<double> wdev;                                // ... and of their weight fields, in a weighted flux fit (7s)
   const double* wfields = rq.fit_flux ? rq.fit_flux->weights : nullptr;
   StampTables tab;
-  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs; ApertureStage aps; MeanFieldStage mfs; ApertureFieldStage afs; FitFluxStage ffs;   // (a stage that does not run stays empty)
+  CompositeStage comp; MonteCarloStage mc; FitStage fit; CatalogueStage cat; CatalogueMcStage catmc; BlendStage bls; RegaussStage rgs; ApertureStage aps; MeanFieldStage mfs; ApertureFieldStage afs; FitFluxStage ffs; MomentsFieldStage mds;   // (a stage that does not run stays empty)
   ResultStack* const stacks[] = {&comp.mean, &comp.stddev, &mc.eps, &comp.residual};   // in the order their copies are queued
   if (fitting) DV_TRY(fit.make_plan(*rq.fields, c, sfield.data()));
   size_t per_field = fb, reserve = StampTables::bytes((size_t)N, (size_t)M);
@@ -5391,7 +5428,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     catmc.columns(*rq.mc, nb, rq.mc->st.sample_flux != nullptr);
     reserve += (size_t)N * catmc.rows.bytes() + (size_t)m->Bc * catmc.scratch.bytes();
   }
-  const bool own_mean = (rq.blend || rq.aper_field) && !rq.fields;   // a stage reads the completed composite and no composite stage runs
+  const bool own_mean = (rq.blend || rq.aper_field || rq.moments) && !rq.fields;   // a stage reads the completed composite and no composite stage runs
   per_field += MeanFieldStage::bytes_per_field(own_mean, fb);
   if (rq.blend) {
     bls.columns(*rq.blend);
@@ -5421,13 +5458,21 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
                  std::min((size_t)rq.fit_flux->par.scratch_bytes, (size_t)nb * (size_t)nmax * (size_t)nmax * sizeof(double));
     }
   }
+  // (7x) the moments keep the mean stamps and upload the weight fields themselves unless the flux fit does either already
+  const double* mwfields = rq.moments ? rq.moments->weights : nullptr;
+  const bool md_store = rq.moments && !rq.fit_flux, md_wdev = mwfields && mwfields != wfields;
+  if (rq.moments) {
+    mds.columns(*rq.moments, nb);
+    reserve += (size_t)N * mds.bytes_per_stamp(c.cs, nb, md_store);
+    if (md_wdev) per_field += fb;
+  }
   size_t budget = 0;
   DV_TRY(fields_budget(reserve, &budget));
   const int64_t G = (int64_t)(budget / per_field);
   if (G < 1) {
     set_error("%s: one %d-pixel field needs %zu bytes of device memory (field%s%s), %zu are available for fields", who, F,
               per_field, rq.fields ? " and its result fields" : own_mean ? " and its device-side mean field" : "",
-              wfields ? " and its weight field" : "", budget);
+              wfields || mwfields ? " and its weight field" : "", budget);
     return DV_E_NOMEM;
   }
   std::vector<FieldGroup> groups;
@@ -5471,6 +5516,10 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     DV_TRY(ffs.alloc(ffplan, N, M, c.cs, nb, wfields != nullptr, rq.fit_flux->nonneg));
     ffs.bind(j.ff);
   }
+  if (rq.moments) {
+    DV_TRY(mds.alloc(N, c.cs, nb, md_store, md_wdev ? gelems : 0));
+    mds.bind(j.ff);
+  }
   if (fitting) {
     DV_TRY(fit.alloc(*rq.fields, c, gmax, groups));
     fit.bind(j.fit);
@@ -5492,6 +5541,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     const size_t ng = (size_t)(g.f1 - g.f0 + 1), goff = (size_t)g.f0 * felems;
     DV_HIP(hipMemcpyAsync(fdev, fields + goff, ng * fb, hipMemcpyHostToDevice, s));
     if (wfields) DV_HIP(hipMemcpyAsync(wdev, wfields + goff, ng * fb, hipMemcpyHostToDevice, s));
+    if (md_wdev) DV_HIP(hipMemcpyAsync(mds.wdev, mwfields + goff, ng * fb, hipMemcpyHostToDevice, s));
     for (ResultStack* r : stacks) DV_TRY(r->begin(r == &comp.residual ? fdev.get() : nullptr, ng * fb, s));
     if (g.f0 == prev_last)
       for (ResultStack* r : stacks) DV_TRY(r->carry(goff, fb, s));
@@ -5502,7 +5552,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
     j.row0 = g.k0 * chunk;
     j.N = std::min<int64_t>(N, g.k1 * chunk) - j.row0;
     DV_TRY(infer_pipelined(m, j));
-    if (rq.blend || rq.aper_field || rq.fit_flux) {
+    if (rq.blend || rq.aper_field || rq.fit_flux || rq.moments) {
       // the completed-field seam: every field of the group has all its stamps composited now, but for a last field that
       // the next group goes on with (it is complete there); the parent sums and the field apertures of the complete fields'
       // galaxies - one contiguous range of rows - read the mean field, the source field and the rows where they lie
@@ -5527,6 +5577,11 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
           DV_TRY(launch_fit_flux(ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, places, fptr32.data(), fa, fz, c.cs,
                                  nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s, true, wfields ? wdev.get() : nullptr, ffs.sky,
                                  ffs.nonneg));
+        if (rq.moments)                // (7x: the stamp store, the placements and the tables count from stamp 0 of the call)
+          DV_TRY(launch_moments_field(md_store ? mds.store.get() : ffs.store.get(), tab.places, tab.sfield, mean_f, fdev,
+                                      md_wdev ? mds.wdev.get() : mwfields ? wdev.get() : nullptr, g.f0, fptr32.data(), fa, fz,
+                                      c.cs, nb, rq.cat->par.band, F, rq.cat->par.sigma0, rq.cat->par.tol, rq.cat->par.max_iter,
+                                      mds.dev, s));
         if (rq.fit_flux && rq.fit_flux->nonneg.on)
           DV_TRY(ffs.nonneg_download(rq.fit_flux->nonneg, (size_t)fa, (size_t)(fz - fa + 1), nb, s));
         if (ff_sky) {
@@ -5555,6 +5610,7 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (rq.aper) DV_TRY(rows_download(aps.rows, N, s));
   if (rq.aper_field) DV_TRY(rows_download(afs.rows, N, s));
   if (rq.fit_flux) DV_TRY(rows_download(ffs.rows, N, s));
+  if (rq.moments) DV_TRY(rows_download(mds.rows, N, s));
   if (ff_sky) DV_TRY(sky_alone(sky_next, M));
   if (rq.fields) DV_TRY(mc.download(N, s));
   if (fitting) DV_TRY(fit.download(*rq.fields, N, s));
@@ -5711,6 +5767,10 @@ static int infer_fields_measure_entry(const char* who, dv_model* m, const Catalo
       set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: without weight_fields both must be NULL", who);
       return DV_E_INVALID;
     }
+    DV_TRY(seam_places_check(who, a));
+  }
+  if (rq.moments) {
+    DV_TRY(moments_field_rows_check(who, rq.moments->rows, N));
     DV_TRY(seam_places_check(who, a));
   }
   if (rq.regauss) {
@@ -5899,6 +5959,22 @@ int dv_infer_fields_measure_fit_weighted(dv_model* m, const double* fields, int3
   rq.fit_flux = FitFluxOut{FitFluxParams{fit->min_pivot, fit->scratch_bytes},
                            FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields};
   return infer_fields_measure_entry("dv_infer_fields_measure_fit_weighted", m,
+                                    {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
+                                     residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
+}
+
+// ---- the adaptive moments on the observed field with the neighbours subtracted: dv_infer_fields_measure plus,
+// per galaxy, the sums, the counting pixels and the moments of its child image D - T + P, taken at the completed-field seam from
+// the mean stamps the chunk loop has kept; weight_fields may be NULL (no mask)
+int dv_infer_fields_measure_moments_data(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb, const int32_t* starts,
+                                         const int32_t* places, const int64_t* field_ptr, int64_t N, uint64_t seed,
+                                         const dv_measure_params* params, double* mean_fields, double* stddev_fields,
+                                         double* residual_fields, double* mse_center, double* flux, double* flux_err, double* shape,
+                                         int32_t* iters, int32_t* status, const double* weight_fields, double* flux_data,
+                                         int32_t* npix_data, double* shape_data, int32_t* iters_data, int32_t* status_data) {
+  FieldsRequest rq;
+  rq.moments = MomentsFieldOut{MomentsFieldRows{flux_data, npix_data, shape_data, iters_data, status_data}, weight_fields};
+  return infer_fields_measure_entry("dv_infer_fields_measure_moments_data", m,
                                     {fields, M, F, nb, starts, places, field_ptr, N, seed, params, mean_fields, stddev_fields,
                                      residual_fields, mse_center, flux, flux_err, shape, iters, status}, rq);
 }

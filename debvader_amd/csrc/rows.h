@@ -36,7 +36,7 @@ struct Rows {
   int download(int64_t r, int64_t n, hipStream_t s) const;   // device rows [0, n) to host rows [r, r + n)
 };
 
-// The columns of the seven row sets, each stated once, in the file of its kernels: `dev` is where the device pointers are
+// The columns of the row sets, each stated once, in the file of its kernels: `dev` is where the device pointers are
 // kept (alloc() sets them; a caller with rows of its own sets them itself), `host` the caller's arrays - all null for rows
 // that stay on the device.  The scratch rows of a Monte-Carlo pass (`reps` rows per galaxy) are never copied.
 void catalogue_columns(Rows& r, CatRows& dev, const CatRows& host, int nb, bool err);
@@ -46,6 +46,7 @@ void blend_columns(Rows& r, BlendRows& dev, const BlendRows& host);
 void regauss_columns(Rows& r, RegaussRows& dev, const RegaussRows& host);
 void aperture_columns(Rows& r, ApertureRows& dev, const ApertureRows& host, const ApertureParams& p, int nb, bool err);
 void aperture_field_columns(Rows& r, ApertureFieldRows& dev, const ApertureFieldRows& host, const ApertureParams& p, int nb);
+void moments_field_columns(Rows& r, MomentsFieldRows& dev, const MomentsFieldRows& host, int nb);
 void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb, bool weighted = false, bool nonneg = false);
 
 // The refusals every field-grouped call takes for its tables, before any GPU work, and the tables: N < 2^31 `noun`s, F within

@@ -45,7 +45,7 @@ def _to_records(cols):
 class _Extra(NamedTuple):
     """One optional part of the on-device catalogue of DeblendFieldBatch.deblend_fields: a keyword, the engine call that
     serves it and what it appends to the recarrays.  `c` below is the namespace of one call: bands, band, sky_sigma,
-    field_ptr, psf, psf_index, aper_par, nmc, fit_weights, fit_sky, places, cs, F, core."""
+    field_ptr, psf, psf_index, aper_par, nmc, fit_weights, fit_sky, moments_weights, places, cs, F, core."""
     key: str                        # the keyword of deblend_fields
     given: Callable                 # its value -> whether the extra is asked for
     label: str                      # how a message names it
@@ -160,6 +160,20 @@ _EXTRAS = (
            lambda out, c: ms.fit_sky_records(out["sky_coef"], out["sky_cov"], out["sky_status"], c.places, c.cs, c.F,
                                              field_ptr=c.field_ptr, sky_sigma=c.sky_sigma, weighted=c.fit_weights is not None),
            refines="fit_flux"),
+    # (behind every extra that stands alone, so it speaks in every refusal beside one of them; it is combined with none, so its
+    # columns meet no others.  fit_nonneg stays the last row: it refines, and its call replaces those of the rows before it)
+    _Extra("moments_data", bool, "moments_data=True", "needs", "the moments on the observed field",
+           "the adaptive moments are re-measured on the observed field with the neighbours' models subtracted where the mean "
+           "stamps, the composited field and the observed field lie in device memory "
+           "(dv_infer_fields_measure_moments_data); on the default path use "
+           "debvader_amd.measure.measurement.measure_moments_on_fields on the returned stamps",
+           "dv_infer_fields_measure_moments_data", "infer_fields_measure_moments_data", True,
+           lambda c: dict(band=c.band, weight_fields=c.moments_weights),
+           lambda c: ms.moments_data_dtype(c.bands),
+           lambda out, c: ms.moments_data_records(out["flux_data"], out["npix_data"], out["shape_data"], out["iters_data"],
+                                                  out["status_data"], sky_sigma=c.sky_sigma, field_ptr=c.field_ptr),
+           orphans=(("moments_weights", "moments_weights are the mask of the moments on the observed field: give "
+                                        "moments_data=True too"),)),
     # (the last refining extra: its call passes the weights and the order of the sky on - None: no sky)
     _Extra("fit_nonneg", bool, "fit_nonneg=True", "needs", "the non-negative flux fit",
            "fit_nonneg=True needs fit_flux=True: it constrains the amplitudes of the flux fit to be >= 0",
@@ -642,6 +656,12 @@ class DeblendFieldBatch:
         return ms.fit_groups_dtype(nb_of_bands)
 
     @staticmethod
+    def moments_data_columns(nb_of_bands):
+        """What deblend_fields(measure=True, moments_data=True) appends behind measure_columns: the recarray of
+        measure_moments_on_fields."""
+        return ms.moments_data_dtype(nb_of_bands)
+
+    @staticmethod
     def fit_flux_weighted_columns(nb_of_bands):
         """What deblend_fields(measure=True, fit_flux=True, fit_weights=W) appends behind measure_columns: the recarray of
         fit_fluxes_weighted - fit_flux_columns, then fit_chi2 and fit_npix."""
@@ -728,8 +748,8 @@ class DeblendFieldBatch:
                        epistemic_uncertainty_estimation=False, epistemic_criterion=100.0, epistemic_samples=100, *,
                        measure=False, return_fields=True, measure_samples=0, blendedness=False,
                        psf=None, psf_index=None, apertures=None, flux_fractions=None, aperture_data=False,
-                       sky_sigma=None, fit_flux=False, fit_groups=False, fit_weights=None, fit_nonneg=False, fit_sky=None,
-                       optimise_positions=False):
+                       sky_sigma=None, fit_flux=False, fit_groups=False, moments_data=False, moments_weights=None,
+                       fit_weights=None, fit_nonneg=False, fit_sky=None, optimise_positions=False):
         """Deblend the galaxies of every field in one engine call.
 
         galaxy_distances_to_center: a list of M arrays (n_m, 2); None detects them first (detect_objects_batch).
@@ -856,15 +876,29 @@ class DeblendFieldBatch:
         (1024 per group), and the columns of the flux fit keep the bits of the fit without it wherever that one takes the
         field.  The recarrays gain, behind the columns of fit_flux (and fit_chi2, fit_npix if weighted), fit_groups_columns:
         fit_group, the smallest row of the galaxy's group in its field's recarray, and fit_group_size.  Together with fit_sky
-        or fit_nonneg it is a ValueError: those two are not built for the grouped fit yet."""
+        or fit_nonneg it is a ValueError: those two are not built for the grouped fit yet.
+
+        moments_data=True (with measure=True and on_device=True, with or without return_fields): the adaptive moments
+        re-measured on the observed field with the neighbours' models subtracted (dv_infer_fields_measure_moments_data,
+        DESIGN.md section 7x).  The mean stamps are kept on the device, and once a field's composite is complete the child
+        image of every galaxy - the observed pixels less the composited mean field plus the galaxy's own stamp - is measured as
+        the mean stamp was; the recarrays gain moments_data_columns (flux_data, npix_data, row_data, col_data, Mrr_data,
+        Mrc_data, Mcc_data, iters_data, status_data and the derived sigma_data, e1_data, e2_data, flux_data_err;
+        debvader_amd.measure.measurement.measure_moments_on_fields describes them).  moments_weights=W (M, F, F, bands) is a
+        mask: a pixel counts iff 0 < W < inf, elsewhere the galaxy's own model stands in.  sky_sigma, (bands,) or (M, bands),
+        is the standard deviation of the sky per pixel flux_data_err is derived from; without it that column is NaN.  The other
+        columns and the fields are those of the same call without it.  It is not available with any other extra, with
+        optimise_positions=True or with epistemic_uncertainty_estimation=True."""
         mc = bool(epistemic_uncertainty_estimation)
         fit = bool(optimise_positions)
         measure = bool(measure)
         aperture_data, fit_flux, fit_nonneg, fit_groups = bool(aperture_data), bool(fit_flux), bool(fit_nonneg), bool(fit_groups)
+        moments_data = bool(moments_data)
         band = 2                        # the band of the measurement (r): the engine call and the blendedness in the apertures
         kw = dict(measure_samples=measure_samples, blendedness=blendedness, psf=psf, psf_index=psf_index, apertures=apertures,
                   flux_fractions=flux_fractions, aperture_data=aperture_data, fit_flux=fit_flux, fit_weights=fit_weights,
-                  fit_sky=fit_sky, fit_nonneg=fit_nonneg, fit_groups=fit_groups)
+                  fit_sky=fit_sky, fit_nonneg=fit_nonneg, fit_groups=fit_groups, moments_data=moments_data,
+                  moments_weights=moments_weights)
         given = [x.key for x in _EXTRAS if x.given(kw[x.key])]
         if fit_groups and (fit_sky is not None or fit_nonneg):
             raise ValueError("fit_groups=True cannot be combined with fit_sky or fit_nonneg: those two are not built for the "
@@ -872,7 +906,7 @@ class DeblendFieldBatch:
                              "field and band)")
         for x in _EXTRAS[1:]:           # (measure_samples, the oldest, is refused below its own integer check)
             _refuse_extra(x, kw, given, measure, on_device, fit, mc)
-        if sky_sigma is not None and not aperture_data and not fit_flux:
+        if sky_sigma is not None and not aperture_data and not fit_flux and not moments_data:
             raise ValueError("sky_sigma is the sky noise of the data-flux errors of aperture_data=True: give aperture_data too")
         if fit_sky is not None:
             E.sky_terms(fit_sky)                                                                            # (ValueError)
@@ -880,6 +914,8 @@ class DeblendFieldBatch:
             if sky_sigma is not None:
                 raise ValueError(ms.WEIGHTS_CARRY_THE_NOISE)
             fit_weights = E.check_fit_weights(fit_weights, self.field_images.shape)                         # (ValueError)
+        if moments_weights is not None:
+            moments_weights = E.check_fit_weights(moments_weights, self.field_images.shape)                 # (ValueError)
         if sky_sigma is not None:
             sky_sigma = ms.check_sky_sigma(sky_sigma, self.nb_of_fields, self.nb_of_bands)                  # (ValueError)
         aper_par = None
@@ -934,7 +970,7 @@ class DeblendFieldBatch:
         extras = [x for x in _EXTRAS if x.key in given]
         c = SimpleNamespace(bands=nb, band=band, sky_sigma=sky_sigma, field_ptr=field_ptr, psf=psf, psf_index=psf_index,
                             aper_par=aper_par, nmc=int(measure_samples), fit_weights=fit_weights, fit_sky=fit_sky,
-                            places=(int((F - cs) / 2) + dd).astype(np.int64), cs=cs, F=F, core=core)
+                            moments_weights=moments_weights, places=(int((F - cs) / 2) + dd).astype(np.int64), cs=cs, F=F, core=core)
         eng.set_normalise(bool(self.normalise))
         try:
             seed = core.next_seed()

@@ -377,6 +377,14 @@ def check_fit_weights(weight_fields, shape):
     return np.ascontiguousarray(w, dtype=np.float64)
 
 
+def _moments_data_out(n, nb):
+    """The result dictionary of the moments on the child images and its pointers in the C-ABI's order."""
+    out = dict(flux_data=np.zeros((n, nb), np.float64), npix_data=np.zeros((n, nb), np.int32),
+               shape_data=np.zeros((n, 5), np.float64), iters_data=np.zeros(n, np.int32), status_data=np.zeros(n, np.int32))
+    return out, [_dp(out["flux_data"]), _ip(out["npix_data"]), _dp(out["shape_data"]), _ip(out["iters_data"]),
+                 _ip(out["status_data"])]
+
+
 def check_measure_mc_args(samples, band, sigma0, tol, max_iter):
     """(samples, params) of scene_measure_mc: C-contiguous float32 sample stamps (S, N, cs, cs, bands), S >= 1."""
     samples = _f32c(samples)
@@ -973,6 +981,35 @@ class Context:
         elif n:
             check(lib.dv_scene_fit_flux(self._h, _fp(stamps), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs, nb,
                                         _dp(data), M, data.shape[1], C.byref(par), *ptrs))
+        return out
+
+    def scene_moments_fields(self, stamps, places, model_fields, data_fields, weight_fields=None, field_ptr=None, band: int = 2,
+                             sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200) -> Dict[str, np.ndarray]:
+        """Adaptive moments on the observed field with the neighbours subtracted (dv_scene_moments_fields, DESIGN.md section
+        7x): stamps (N, cs, cs, bands), the mean stamps taken as float32; places (N, 2), the field position (row, col) of every
+        stamp's top-left corner; model_fields (M, F, F, bands), the composited mean fields T; data_fields of the same shape,
+        the observed fields D; weight_fields of the same shape or None - a mask only: a pixel counts iff it lies inside the
+        field and 0 < W < inf; field_ptr (M + 1,): stamps field_ptr[m]:field_ptr[m + 1] lie in field m (None: one field holds
+        them all).  Per galaxy the child image C = (D - T) + stamp where the pixel counts and the stamp elsewhere.  Returns
+        {"flux_data" (N, bands): the sum of every band of C; "npix_data" (N, bands) int32: the counting pixels; "shape_data"
+        (N, 5), "iters_data", "status_data" (N,): scene_measure's adaptive moments of band `band` of C}.  Where D has the bits
+        of T every output has the bits of scene_measure on the stamps."""
+        stamps, places, model, fp = _fit_scene_inputs(stamps, places, model_fields, field_ptr)
+        n, cs, nb = stamps.shape[0], stamps.shape[1], stamps.shape[3]
+        if cs < 1 or nb < 1:
+            raise ValueError(f"expected square stamps (N, cs, cs, bands), got {stamps.shape}")
+        if cs > MEASURE_MAX_STAMP:
+            raise ValueError(f"stamps of {cs} pixels: the measurement takes at most {MEASURE_MAX_STAMP}")
+        data = np.ascontiguousarray(data_fields, dtype=np.float64)
+        if data.shape != model.shape:
+            raise ValueError(f"expected data fields {model.shape}, got {data.shape}")
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, model.shape)
+        par = measure_params(band, sigma0, tol, max_iter, nb)
+        out, ptrs = _moments_data_out(n, nb)
+        if n:
+            check(lib.dv_scene_moments_fields(self._h, _fp(stamps), _ip(places), fp.ctypes.data_as(C.POINTER(C.c_int64)), n, cs,
+                                              nb, _dp(model), _dp(data), None if weights is None else _dp(weights),
+                                              model.shape[0], model.shape[1], C.byref(par), *ptrs))
         return out
 
     def scene_fit_flux_groups(self, stamps, places, data_fields, field_ptr=None, min_pivot: float = 1e-8,
@@ -1790,6 +1827,37 @@ class Engine:
 
         return Engine._fields_measure(self, lib.dv_infer_fields_measure_fit_groups, fields, starts, field_ptr, places, seed,
                                       (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
+
+    def infer_fields_measure_moments_data(self, fields, starts, field_ptr, places, weight_fields=None, seed=0, band: int = 2,
+                                          sigma0: float = 3.0, tol: float = 1e-10, max_iter: int = 200, return_fields=True,
+                                          residual=True, mse_center=True) -> Dict[str, np.ndarray]:
+        """infer_fields_measure() plus the adaptive moments on the observed field with the neighbours subtracted
+        (dv_infer_fields_measure_moments_data): returns its dictionary, bit for bit, plus
+        scene_moments_fields' {"flux_data", "npix_data", "shape_data", "iters_data", "status_data"} - the bits of that call on
+        infer_fields_keep's mean stamps, infer_fields_composite's mean fields and the source fields as data, taken once a
+        field's composite is complete.  weight_fields has the shape of fields or is None (a mask: a pixel counts iff 0 < W <
+        inf).  `places` is always needed: with return_fields=False the mean field is still composited on the device."""
+        places = Engine._measure_places(places, return_fields, "places are needed for the moments on the fields, with "
+                                        "return_fields=False too")
+        fields = _check_fields(fields)
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, fields.shape)
+
+        def extras(N, nb):
+            md, md_ptrs = _moments_data_out(N, nb)
+            return [(md, [None if weights is None else _dp(weights)] + md_ptrs)]
+
+        return Engine._fields_measure(self, lib.dv_infer_fields_measure_moments_data, fields, starts, field_ptr, places, seed,
+                                      (band, sigma0, tol, max_iter), return_fields, residual, mse_center, extras)
+
+    def infer_cutouts_measure_moments_data(self, field, starts, places, weight_field=None, seed=0, **kw) -> Dict[str, np.ndarray]:
+        """infer_fields_measure_moments_data() for one field and its optional weight field (F, F, bands): the field-sized
+        results under singular key names."""
+        fields, starts, fp = Engine._one_field(field, starts)
+        return Engine._singular(self.infer_fields_measure_moments_data(fields, starts, fp, places, weight_field, seed=seed, **kw))
+
+    def scene_moments_fields(self, stamps, places, model_fields, data_fields, **kw) -> Dict[str, np.ndarray]:
+        """Context.scene_moments_fields on this engine's GPU context."""
+        return self.ctx.scene_moments_fields(stamps, places, model_fields, data_fields, **kw)
 
     def scene_fit_flux_groups(self, stamps, places, data_fields, **kw) -> Dict[str, np.ndarray]:
         """Context.scene_fit_flux_groups on this engine's GPU context."""

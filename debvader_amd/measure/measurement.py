@@ -14,7 +14,9 @@ adaptive moments of what remains are measured, and the PSF's moments are subtrac
 e1_corr, e2_corr and the resolution of every galaxy from a PSF image per galaxy, per field or for all.  Aperture photometry
 is DESIGN.md section 7o (measure_apertures, csrc/aperture.hip): fluxes in fixed circular apertures about the measured
 centroid, the Kron radius and the flux in the Kron ellipse of the galaxy's own moments (SExtractor's FLUX_AUTO and
-KRON_RADIUS), and the radii that hold given fractions of that flux (FLUX_RADIUS).
+KRON_RADIUS), and the radii that hold given fractions of that flux (FLUX_RADIUS).  The adaptive moments re-measured on the
+observed field with the neighbours' models subtracted are DESIGN.md section 7x (measure_moments_on_fields,
+csrc/moments_field.hip).
 """
 import numpy as np
 
@@ -47,14 +49,20 @@ def catalogue_records(flux, flux_err, shape, iters, status):
         rec[name] = shape[:, k]
     rec["iters"] = iters
     rec["status"] = status
+    rec["sigma"], rec["e1"], rec["e2"] = derived_shape(shape, status)
+    return rec
+
+
+def derived_shape(shape, status):
+    """(sigma, e1, e2) of the adaptive-moments rows shape (N, 5) = {row, col, Mrr, Mrc, Mcc}: sigma = det(M)^(1/4), e1 = (Mcc -
+    Mrr) / (Mcc + Mrr), e2 = 2 Mrc / (Mcc + Mrr); NaN where status is 3."""
+    shape = np.asarray(shape, dtype=np.float64)
     Mrr, Mrc, Mcc = shape[:, 2], shape[:, 3], shape[:, 4]
     failed = np.asarray(status) == STATUS_FAILED
     with np.errstate(all="ignore"):
         det, tr = Mrr * Mcc - Mrc * Mrc, Mcc + Mrr
-        rec["sigma"] = np.where(failed, np.nan, np.sqrt(np.sqrt(det)))
-        rec["e1"] = np.where(failed, np.nan, (Mcc - Mrr) / tr)
-        rec["e2"] = np.where(failed, np.nan, 2.0 * Mrc / tr)
-    return rec
+        return (np.where(failed, np.nan, np.sqrt(np.sqrt(det))), np.where(failed, np.nan, (Mcc - Mrr) / tr),
+                np.where(failed, np.nan, 2.0 * Mrc / tr))
 
 
 MC_SHAPE_NAMES = E.MC_SHAPE_NAMES
@@ -892,6 +900,101 @@ def fit_fluxes_nonneg(stamps_mean, places, data_fields, sky_order=None, weight_f
         per_field.update({k: out[k] for k in E.FIT_SKY_KEYS})
     recs.append(fit_nonneg_records(*(out[k] for k in E.FIT_NONNEG_KEYS), flux))
     return _join_records(*recs), per_field
+
+
+def moments_data_dtype(nb_of_bands):
+    """The columns of measure_moments_on_fields' recarray: what the GPU measures on the child image, then
+    what the host derives from it."""
+    nb = int(nb_of_bands)
+    return [("flux_data", "<f8", (nb,)), ("npix_data", "<i4", (nb,)), ("row_data", "<f8"), ("col_data", "<f8"),
+            ("Mrr_data", "<f8"), ("Mrc_data", "<f8"), ("Mcc_data", "<f8"), ("iters_data", "<i4"), ("status_data", "<i4"),
+            ("sigma_data", "<f8"), ("e1_data", "<f8"), ("e2_data", "<f8"), ("flux_data_err", "<f8", (nb,))]
+
+
+def moments_data_records(flux_data, npix_data, shape_data, iters_data, status_data, sky_sigma=None, field_ptr=None):
+    """The recarray of measure_moments_on_fields from the five arrays the engine returns (scene_moments_fields').  Derived on
+    the host: sigma_data, e1_data and e2_data from the moments as catalogue_records derives sigma, e1 and e2 (derived_shape; NaN
+    where status_data is 3), and, with sky_sigma (bands,) or (M, bands) - the per-pixel standard deviation of the sky;
+    field_ptr (M + 1,) gives every galaxy's field, None: one field - flux_data_err = sky_sigma sqrt(npix_data): the noise of
+    the counting pixels, the only ones where the data enter.  Without sky_sigma it is NaN."""
+    flux = np.asarray(flux_data, dtype=np.float64)
+    if flux.ndim != 2:
+        raise ValueError(f"expected flux_data (N, bands), got {flux.shape}")
+    n, nb = flux.shape
+    npix = np.asarray(npix_data, dtype=np.int32)
+    shape = np.asarray(shape_data, dtype=np.float64)
+    iters, status = np.asarray(iters_data, dtype=np.int32), np.asarray(status_data, dtype=np.int32)
+    if npix.shape != (n, nb) or shape.shape != (n, 5) or iters.shape != (n,) or status.shape != (n,):
+        raise ValueError(f"expected npix_data ({n}, {nb}), shape_data ({n}, 5), iters_data and status_data ({n},), got "
+                         f"{npix.shape}, {shape.shape}, {iters.shape}, {status.shape}")
+    rec = np.recarray((n,), dtype=moments_data_dtype(nb))
+    rec["flux_data"], rec["npix_data"] = flux, npix
+    for k, name in enumerate(("row_data", "col_data", "Mrr_data", "Mrc_data", "Mcc_data")):
+        rec[name] = shape[:, k]
+    rec["iters_data"], rec["status_data"] = iters, status
+    rec["sigma_data"], rec["e1_data"], rec["e2_data"] = derived_shape(shape, status)
+    if sky_sigma is None:
+        rec["flux_data_err"] = np.nan
+    else:
+        if field_ptr is None:
+            field_ptr = [0, n]
+        fp = np.asarray(field_ptr, dtype=np.int64).reshape(-1)
+        M = fp.shape[0] - 1
+        if M < 1 or fp[0] != 0 or fp[-1] != n or (np.diff(fp) < 0).any():
+            raise ValueError(f"field_ptr must start at 0, never decrease and end at the number of galaxies ({n})")
+        sky = check_sky_sigma(sky_sigma, M, nb)[np.repeat(np.arange(M), np.diff(fp))]              # (N, bands)
+        rec["flux_data_err"] = sky * np.sqrt(npix.astype(np.float64))
+    return rec
+
+
+def measure_moments_on_fields(stamps_mean, places, data_fields, model_fields, weight_fields=None, field_ptr=None,
+                              catalogue=None, sky_sigma=None, band=2, sigma0=3.0, tol=1e-10, max_iter=200, ctx=None):
+    """The adaptive moments of measure_stamps re-measured on the observed field with the neighbours' models subtracted, on the
+    GPU: per galaxy the child image C = D - T + P, D the observed field, T the composited mean field and
+    P the galaxy's own mean stamp, as SExtractor, the SDSS deblender and LSST's deblended children measure shapes.  A network
+    that makes a galaxy too round or too large biases the shape of P; it does not bias the shape of C.  Where a stamp pixel lies
+    outside the field or under a masked pixel, C is P: the model fills in what is hidden.
+
+    parameters:
+        stamps_mean: the network's mean stamps, (N, cutout_size, cutout_size, bands)
+        places: (N, 2), the field position (row, col) of every stamp's top-left corner - where the stamp was composited
+        data_fields: (M, F, F, bands), the observed fields; (F, F, bands) for one field
+        model_fields: the composited mean fields (the sum of all mean stamps of a field), of the same shape
+        weight_fields: of the same shape, or None.  A mask only: a pixel counts iff 0 < W < inf, and a NaN or a saturated value
+            of the data under a masked pixel reaches nothing.  The moments are not inverse-variance weighted
+        field_ptr: (M + 1,), stamps field_ptr[m]:field_ptr[m + 1] lie in field m; None: one field holds them all
+        catalogue: the measure_stamps recarray of the same galaxies, or None.  Only its length is checked: the iteration starts
+            from the stamp centre and sigma0, as measure_stamps does, not from the model's moments
+        sky_sigma: (bands,) or (M, bands), the standard deviation of the sky noise per pixel; None: flux_data_err is NaN
+        band, sigma0, tol, max_iter: those of measure_stamps
+        ctx: the engine context to run on (None: the default context)
+    returns a np.recarray of moments_data_dtype: flux_data (bands,), the sum of C; npix_data (bands,), the counting pixels;
+    row_data, col_data, Mrr_data, Mrc_data, Mcc_data, iters_data, status_data, the adaptive moments of band `band` of C with
+    measure_stamps' status codes (a non-finite value of D at a counting pixel ends in STATUS_FAILED); and, derived on the host,
+    sigma_data, e1_data, e2_data and flux_data_err (moments_data_records).  Where D equals T bit for bit the measured columns
+    have the bits of measure_stamps.
+    """
+    data = np.asarray(data_fields, dtype=np.float64)
+    model = np.asarray(model_fields, dtype=np.float64)
+    if data.ndim == 3:
+        data = data[None]
+    if model.ndim == 3:
+        model = model[None]
+    M = model.shape[0]
+    if model.ndim == 4 and sky_sigma is not None:
+        check_sky_sigma(sky_sigma, M, model.shape[-1])                   # (ValueError before any GPU work)
+    stamps = np.asarray(stamps_mean, dtype=np.float32)
+    if catalogue is not None and len(catalogue) != stamps.shape[0]:
+        raise ValueError(f"the catalogue has {len(catalogue)} rows for {stamps.shape[0]} stamps: measure_moments_on_fields takes "
+                         "the measure_stamps recarray of the same galaxies")
+    if field_ptr is None and M == 1:
+        field_ptr = [0, stamps.shape[0]]
+    if ctx is None:
+        ctx = E.default_context()
+    out = ctx.scene_moments_fields(stamps, places, model, data, weight_fields=weight_fields, field_ptr=field_ptr, band=band,
+                                   sigma0=sigma0, tol=tol, max_iter=max_iter)
+    return moments_data_records(out["flux_data"], out["npix_data"], out["shape_data"], out["iters_data"], out["status_data"],
+                                sky_sigma=sky_sigma, field_ptr=field_ptr)
 
 
 def measure_blendedness(stamps_mean, catalogue, places, model_fields, data_fields=None, field_ptr=None, band=2, ctx=None):

@@ -845,6 +845,41 @@ int dv_infer_fields_measure_fit_nonneg(dv_model* m, const double* fields, int32_
                                        double* sky_cov, int32_t* sky_status, int64_t* sky_npix, double* fit_scale_free,
                                        int32_t* fit_clamped, double* fit_dual, int32_t* nonneg_iters, int32_t* nonneg_status);
 
+/* ---- adaptive moments on the observed field with the neighbours subtracted ----
+ * The measurement of dv_scene_measure on the CHILD IMAGE of every galaxy instead of on the network's mean stamp.  Per galaxy i
+ * of field m: P_i [cs][cs][nb] float32 its mean stamp, (pr, pc) = places[i] its place, T = model_fields[m] and D =
+ * data_fields[m], both [F][F][nb] float64, and optionally W = weight_fields[m] of the same shape (NULL: none).  Stamp pixel
+ * (r, c), band b lies on field pixel (R, Cc) = (pr + r, pc + c).  The pixel COUNTS iff it lies inside the field and, where W is
+ * given, 0 < W[R, Cc, b] < inf (the rule of the weighted flux fit: a NaN or saturated value of D under a masked pixel reaches
+ * nothing).  Child image: C_i[r, c, b] = (D[R, Cc, b] - T[R, Cc, b]) + (double)P_i[r, c, b] where the pixel counts - two
+ * roundings in that order, no contraction - and (double)P_i[r, c, b] elsewhere: the model fills in what the field edge or the
+ * mask hides.  Outputs: flux_data [N][nb] = the sum of C_i[., ., b] over the whole stamp, in the thread assignment and
+ * reduction order of dv_scene_measure's flux; npix_data [N][nb] int32 = the counting pixels; shape_data [N][5], iters_data [N]
+ * and status_data [N] = the adaptive-moments iteration of dv_scene_measure on the float64 plane C_i[:, :, band], from the stamp
+ * centre and sigma0^2 I, with the same status codes.  A non-finite D at a counting pixel of `band` ends in status 3 and is not
+ * hidden.  A stamp wholly outside its field has npix_data 0 and C = P: it gets the model's row.  Where D has the bits of T,
+ * every output has the bits of dv_scene_measure on the same stamps.  The weights are a mask only: the moments are not
+ * inverse-variance weighted.  A galaxy's outputs have the same bits wherever it sits in a batch.
+ * dv_scene_moments_fields: host arrays in and out, whole fields at a time within free device memory; field_ptr [M + 1] as in
+ * dv_scene_fit_flux.  Refused before any GPU work (DV_E_INVALID, the engine stays usable): what dv_scene_measure refuses (band,
+ * sigma0, tol, max_iter, a stamp above 90 pixels), a missing input or output, a null places, a bad field_ptr (checked whole
+ * before anything is indexed by it), F outside 1 .. 32768, a placement beyond +-2^28.
+ * dv_infer_fields_measure_moments_data: dv_infer_fields_measure plus weight_fields [M][F][F][nb] (nullable) and the five
+ * outputs, taken at the completed-field seam from the mean stamps the chunk loop has kept, with and without the result fields
+ * (the catalogue-only form composites T on the device and needs places too): the bits of dv_scene_moments_fields on
+ * dv_infer_fields_keep's mean stamps, dv_infer_fields_composite's mean fields and the source fields. */
+int dv_scene_moments_fields(dv_ctx* ctx, const float* stamps, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                            int32_t cs, int32_t nb, const double* model_fields, const double* data_fields,
+                            const double* weight_fields, int32_t M, int32_t F, const dv_measure_params* params,
+                            double* flux_data, int32_t* npix_data, double* shape_data, int32_t* iters_data, int32_t* status_data);
+int dv_infer_fields_measure_moments_data(dv_model* m, const double* fields, int32_t M, int32_t F, int32_t nb,
+                                         const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
+                                         uint64_t seed, const dv_measure_params* params, double* mean_fields,
+                                         double* stddev_fields, double* residual_fields, double* mse_center, double* flux,
+                                         double* flux_err, double* shape, int32_t* iters, int32_t* status,
+                                         const double* weight_fields, double* flux_data, int32_t* npix_data, double* shape_data,
+                                         int32_t* iters_data, int32_t* status_data);
+
 /* ---- resident field sets: iterative deblending with the fields on the GPU ----
  * dv_field_set_open uploads M float64 fields [M][F][F][nb] once; the set (owned by the model: dv_model_destroy frees it)
  * keeps per field, in device memory, `work` (what the next pass detects on and cuts from, at first the field), `final`

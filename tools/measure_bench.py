@@ -133,6 +133,18 @@ galaxy-bands were clamped.  With --profile-one: warm up, one fp32 call (d), exit
 
     python tools/measure_bench.py --fit-groups [--fields 1024] [--size 259] [--repeat 5] [--tile 4096] [--tile-stamps 20000]
 
+--moments-data: what the adaptive moments on the observed field with the neighbours subtracted cost in
+the catalogue-only call, on the same build and box, in --blend's protocol -
+
+    (a) catalogue              :  deblend_fields(d, on_device=True, measure=True, return_fields=False): the call as it was
+    (b) catalogue+moments-data :  the same with moments_data=True: the mean stamps are kept on the device, the mean field is
+                                  composited there, and every galaxy's child image is measured once its field is complete
+
+    python tools/measure_bench.py --moments-data [--fields 1024] [--size 259] [--repeat 5]
+
+It also prints the histograms of status and status_data and the mean ratio iters_data / iters over the galaxies converged in
+both.  With --profile-one: warm up, one fp32 call (b), exit.
+
 The cost is reported, not gated.
 """
 import argparse
@@ -552,6 +564,66 @@ def main_apertures(a, data=False):
     print(json.dumps(result))
 
 
+def main_moments_data(a):
+    rng = np.random.default_rng(0)
+    F, M = a.size, a.fields
+    base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
+    fields = np.ascontiguousarray(base[np.arange(M) % 16])
+    quiet = io.StringIO()
+    result = {"fields": M, "F": F, "max_batch": a.max_batch, "repeat": a.repeat, "moments_data": True}
+    dists = None
+    for dtype in a.dtypes.split(","):
+        net, _, _, _ = model.create_model_vae(**ARCH, max_batch=a.max_batch, seed=1, dtype=dtype)
+        if dists is None:
+            dists = detect_objects_batch(fields, ctx=net._core.ctx)
+            dists = [np.round(np.asarray(d, dtype=np.float64).reshape(-1, 2)) for d in dists]
+            print(f"{M} fields of {F} px, six bands; {sum(len(d) for d in dists)} detections; max_batch {a.max_batch}")
+        seen = []
+
+        def with_moments():
+            res = DeblendFieldBatch(net, fields).deblend_fields(dists, on_device=True, measure=True, return_fields=False,
+                                                                moments_data=True)
+            seen[:] = [np.concatenate([r[k] for r in res]) for k in ("status", "status_data", "iters", "iters_data")]
+            return sum(len(r) for r in res)
+
+        legs = {"catalogue": lambda: _device(net, fields, dists, measure=True, return_fields=False),
+                "catalogue+moments-data": with_moments}
+        with redirect_stdout(quiet):
+            for fn in legs.values():           # warm-up
+                fn()
+            if a.profile_one:
+                with_moments()
+                net._core.engine.close()
+                return
+            times = {k: [] for k in legs}
+            n = 0
+            for _ in range(a.repeat):
+                for k, fn in legs.items():
+                    t0 = time.perf_counter()
+                    n = fn()
+                    times[k].append(time.perf_counter() - t0)
+        both = (seen[0] == 0) & (seen[1] == 0)
+        ratio = float(np.mean(seen[3][both] / seen[2][both])) if both.any() else float("nan")
+        result[dtype] = {"stamps": n, "status": np.bincount(seen[0], minlength=4).tolist(),
+                         "status_data": np.bincount(seen[1], minlength=4).tolist(), "converged_in_both": int(both.sum()),
+                         "mean_iters": round(float(np.mean(seen[2])), 2), "mean_iters_data": round(float(np.mean(seen[3])), 2),
+                         "mean_iters_data_over_iters": round(ratio, 3)}
+        for k in legs:
+            t = np.array(times[k])
+            print(_row(f"{dtype} {k}", t, n, M))
+            result[dtype][k.replace("+", "_").replace("-", "_") + "_ms"] = [round(1e3 * x, 2) for x in t]
+        tc, tm = (float(np.median(times[k])) for k in legs)
+        spread = lambda t: float((np.max(t) - np.min(t)) / np.median(t))
+        print(f"{dtype} catalogue+moments-data / catalogue {tm / tc:.3f}: {1e3 * (tm - tc):+.1f} ms for {n} galaxies, "
+              f"{1e6 * (tm - tc) / max(n, 1):.2f} us per galaxy (spreads {spread(times['catalogue']):.3f} and "
+              f"{spread(times['catalogue+moments-data']):.3f}); status 0 .. 3 {result[dtype]['status']}, status_data "
+              f"{result[dtype]['status_data']}; iterations per galaxy {result[dtype]['mean_iters']} on the model and "
+              f"{result[dtype]['mean_iters_data']} on the data, mean iters_data / iters over the {int(both.sum())} converged in "
+              f"both {ratio:.3f}")
+        net._core.engine.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fields", type=int, default=1024)
@@ -571,11 +643,14 @@ def main():
     ap.add_argument("--fit-sky", type=int, choices=(0, 1), default=None, metavar="ORDER")
     ap.add_argument("--fit-nonneg", action="store_true")
     ap.add_argument("--fit-groups", action="store_true")
+    ap.add_argument("--moments-data", action="store_true")
     ap.add_argument("--tile", type=int, default=4096)
     ap.add_argument("--tile-stamps", type=int, default=20000)
     a = ap.parse_args()
     if a.fit_flux or a.fit_weights or a.fit_sky is not None or a.fit_nonneg or a.fit_groups:
         return main_fit_flux(a)
+    if a.moments_data:
+        return main_moments_data(a)
     if a.aperture_data:
         return main_apertures(a, data=True)
     if a.apertures:
