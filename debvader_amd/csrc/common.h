@@ -328,16 +328,22 @@ int scene_measure(const float* mean_h, const float* stddev_h, int64_t N, int cs,
 // the same moments on the observed field with the neighbours subtracted (moments_field.hip): per galaxy the child
 // image C = (D - T) + P where the stamp pixel counts (inside the field and, with weights, 0 < W < inf) and P elsewhere; its
 // per-band sums and counting pixels, and the adaptive moments of its band plane.  MomentsFieldRows: the output rows, device or
-// host - flux / npix [.][nb], shape [.][5], iters, status [.].  launch_moments_field: the complete fields fa .. fz, every
-// per-galaxy array counted from row 0 of the call like fptr_h; the field stacks start at field f0 (weight_dev null: no mask).
-// scene_moments_fields: host arrays, whole fields at a time within half of free device memory; every refusal before GPU work.
+// host - flux / npix [.][nb], shape [.][5], iters, status [.].  launch_moments_field: the complete fields fa .. fz of the view
+// v (v.weight null: no mask), the rows counted like its stamps.
+// scene_moments_fields: host arrays, whole fields at a time (walk_whole_fields, rows.h); every refusal before GPU work.
 size_t measure_lds_bytes(int cs);
+// The device view of the stamps of a set of fields, as the kernels that read stamps against fields take it: every per-galaxy
+// array - stamps [.][cs][cs][nb], places [.][2], sfield [.] - counts from row 0 of the set, like fptr (the first row of every
+// field, and one more); the field stacks [.][F][F][nb] hold the fields from f0 on (data: the observed fields; weight: their
+// inverse variances, laid out alike; model: the composited means - each null where the call has none).
+struct FieldStamps {
+  const float* stamps; const int *places, *sfield, *fptr; const double *data, *weight, *model;
+  int f0, cs, nb, F;
+};
 struct MomentsFieldRows { double* flux; int* npix; double* shape; int *iters, *status; };
 int moments_field_rows_check(const char* who, const MomentsFieldRows& o, int64_t n);
-int launch_moments_field(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const double* model_dev,
-                         const double* data_dev, const double* weight_dev, int f0, const int* fptr_h, int fa, int fz, int cs,
-                         int nb, int band, int F, double sigma0, double tol, int max_iter, const MomentsFieldRows& rows,
-                         hipStream_t s);
+int launch_moments_field(const FieldStamps& v, const int* fptr_h, int fa, int fz, int band, double sigma0, double tol,
+                         int max_iter, const MomentsFieldRows& rows, hipStream_t s);
 int scene_moments_fields(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                          const double* model_h, const double* data_h, const double* weight_h, int M, int F, int band,
                          double sigma0, double tol, int max_iter, const MomentsFieldRows& out_h, int device, hipStream_t s);
@@ -463,9 +469,9 @@ int scene_aperture_fields(const double* shape_h, const int32_t* status_h, const 
 // a of min |D - sum a_i P_i|^2 over the galaxies of the field, by a dense Cholesky factorisation with dropping.  FitFluxRows: the
 // output rows [.][nb], device or host.  fitflux_check / fitflux_plan: every refusal, before any GPU work; the plan is what
 // FitFluxWork::alloc takes - the dense scratch (at most scratch_bytes, no more than the fields need) and the pair list.
-// launch_fit_flux: the complete fields fa .. fz, every per-galaxy array counted from row 0 of the call; it returns with the
-// stream idle.  scene_fit_flux: host arrays, whole fields at a time within `budget` bytes of device memory (0: half of what
-// is free beside the scratch).  scene_fit_flux_gram: step 1 of one field - the dense G and h to the host.  With weight fields
+// launch_fit_flux: the complete fields fa .. fz of a view (FieldStamps above), the rows counted like its stamps; it returns with
+// the stream idle.  scene_fit_flux: host arrays, whole fields at a time (walk_whole_fields, rows.h) within half of the device
+// memory that is free beside the scratch.  scene_fit_flux_gram: step 1 of one field - the dense G and h to the host.  With weight fields
 // (per-pixel inverse variances, a pixel counts iff 0 < W < inf) the sums are weighted, and behind the solve a third
 // kernel takes the chi-square of the refitted scene and the count of the counting pixels of every galaxy from a CSR adjacency
 // the host builds beside the pair list; without them nothing more is allocated, copied or launched than before.
@@ -505,49 +511,80 @@ struct FitFluxWork {
   std::vector<int> pairs_h;                           // host staging of one sub-range
   std::vector<long long> foff_h;
   std::vector<int> adj_ptr_h, adj_h, adj_at_h;
-  static size_t bytes(const FitFluxPlan& plan, size_t fields, bool weighted = false) {
-    return plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int) + fields * sizeof(long long) +
-           (weighted ? (plan.pair_cap * 2 + plan.rows + 1) * sizeof(int) : 0) +
-           (plan.q ? (fields ? fields : 1) * (plan.sky_part + FF_SKY_BANDS * fitflux_sky_acc(plan.q)) * sizeof(double) : 0);
+  // what the plan allocates whatever the fields at a time, the sums of one field's sky, and all of it for `fields` fields
+  static size_t fixed_bytes(const FitFluxPlan& plan, bool weighted) {
+    return plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int) +
+           (weighted ? (plan.pair_cap * 2 + plan.rows + 1) * sizeof(int) : 0);
   }
-  int alloc(const FitFluxPlan& plan, int64_t max_fields, bool weighted = false);
+  static size_t sky_field_bytes(const FitFluxPlan& plan) {
+    return plan.q ? (plan.sky_part + FF_SKY_BANDS * fitflux_sky_acc(plan.q)) * sizeof(double) : 0;
+  }
+  static size_t bytes(const FitFluxPlan& plan, size_t fields, bool weighted) {
+    return fixed_bytes(plan, weighted) + fields * sizeof(long long) + (fields ? fields : 1) * sky_field_bytes(plan);
+  }
+  int alloc(const FitFluxPlan& plan, int64_t max_fields, bool weighted);
+};
+// The per-field outputs of a fit on the device (the sky's coef, cov, status and npix, the non-negative fit's iters and status),
+// for every caller that holds them beside its rows: alloc() for `fields` fields sets `sky` and `nonneg`, the device-side
+// structs launch_fit_flux takes (q = 0 / on = false: nothing is allocated); download() queues the copies of nf fields, device
+// field dev_f0 on, to field host_f0 on of the caller's arrays.
+struct FitFluxFieldOut {
+  DevBuf<double> coef, cov;
+  DevBuf<int> status, iters, nn_status;
+  DevBuf<long long> npix;
+  FitFluxSky sky{};
+  FitFluxNonneg nonneg{};
+  static size_t bytes(int q, bool nonneg, size_t fields, int nb) {
+    return fields * nb * ((q ? (size_t)q * (q + 1) * sizeof(double) + q * sizeof(int) + sizeof(long long) : 0) +
+                          (nonneg ? 2 * sizeof(int) : 0));
+  }
+  int alloc(int q, const FitFluxNonneg& nn, size_t fields, int nb);
+  int download(const FitFluxSky& sky_h, const FitFluxNonneg& nn_h, size_t host_f0, size_t dev_f0, size_t nf, int nb,
+               hipStream_t s) const;
 };
 int fitflux_check(const char* who, int cs, int nb, int F, const FitFluxParams& p);
-int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n, bool weighted = false);
+int fitflux_rows_check(const char* who, const FitFluxRows& o, int64_t n, bool weighted);
 // sky_order -1: no sky; 0 / 1: the bordered systems of 7t, (n + q)^2 doubles per band (F sizes the partial sums)
 int fitflux_plan(const char* who, const int64_t* field_ptr, int M, int nb, const FitFluxParams& p, FitFluxPlan* plan,
-                 int sky_order = -1, int F = 0);
+                 int sky_order, int F);
 int fitflux_sky_check(const char* who, int sky_order, const FitFluxSky& o, const FitFluxRows& rows, bool weighted);
 // the refusals of the non-negative calls (7u) that need no table: max_iter, the five new outputs, sky outputs given without
 // a sky, and (without a sky, where fitflux_sky_check does not run) chi-square outputs that do not match the weights
 int fitflux_nonneg_check(const char* who, const FitFluxNonneg& nn, const FitFluxRows& rows, int64_t n, const FitFluxSky& sky,
                          bool weighted);
-// weight_dev: the weight fields from field f0 on, laid out like data_dev (7s), or null: the unweighted fit.  With weights the
-// chi-square kernel runs behind the solve and rows.chi2 / rows.npix are written
+// v.weight: the weight fields (7s), or null: the unweighted fit.  With weights the chi-square kernel runs behind the solve and
+// rows.chi2 / rows.npix are written.  places_h / fptr_h: the host copies of v.places / v.fptr, for the pair list
 // sky (7t): q = 1 or 3 sky terms per field and band and the device arrays of their outputs, counted from field 0 of the call; the
 // work area must have been planned for the same q.  A sub-range without galaxies is launched when there is a sky
 // nn (7u): on - fitflux_nonneg_kernel runs in place of the solve, rows.scale_free / clamped / dual and nn.iters / nn.status
 // (device, counted from field 0 of the call) are written; the fields of a sub-range that launches nothing get iters 0, status 0
-int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
-                    const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
-                    int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve = true,
-                    const double* weight_dev = nullptr, const FitFluxSky& sky = FitFluxSky{},
-                    const FitFluxNonneg& nn = FitFluxNonneg{});
+// solve false: step 1 alone
+int launch_fit_flux(const FieldStamps& v, const int32_t* places_h, const int* fptr_h, int fa, int fz, const FitFluxParams& p,
+                    FitFluxWork& w, const FitFluxRows& rows, const FitFluxSky& sky, const FitFluxNonneg& nn, bool solve,
+                    hipStream_t s);
+// What a fit is asked to do, by every caller: the parameters, the host rows, the host weight fields (null: unweighted), the
+// order of the sky (-1: none) with its host outputs, the non-negative fit with its, the host rows of the fit by blend groups
+// (7w; null: the dense fit), and the name the refusals carry.
+struct FitFluxOut {
+  FitFluxParams par{}; FitFluxRows rows{}; const double* weights = nullptr; int sky_order = -1; FitFluxSky sky{};
+  FitFluxNonneg nonneg{};
+  int32_t* group = nullptr; int32_t* group_size = nullptr;
+  const char* who = "dv_scene_fit_flux";
+  bool grouped() const { return group != nullptr; }
+};
 // the regrouping of a resident field set's rows for the joint fit of all passes: destination row d takes the stamp,
 // the placement and the field of source row rowmap_dev[d]; n destination rows, every rowmap entry a row the source holds
 int launch_fitflux_regroup(const int* rowmap_dev, const float* src, const int* src_places, const int* src_field, int64_t n, int cs,
                            int nb, float* dst, int* dst_places, int* dst_field, hipStream_t s);
 int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
-                   const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
-                   hipStream_t s, const double* weight_h = nullptr, const char* who = "dv_scene_fit_flux", int sky_order = -1,
-                   const FitFluxSky& sky_h = FitFluxSky{}, const FitFluxNonneg& nn_h = FitFluxNonneg{});
+                   const double* data_h, int M, int F, const FitFluxOut& rq, int device, hipStream_t s);
 // The fit by blend groups: the connected components of the overlap graph of every field are found on the GPU and
 // each is solved on its own - no limit per field, FF_MAX_N per group, the scratch sum nb n_g^2 doubles.  FitGroupsWork: the
 // device tables (counts, scans, pair list, adjacency, labels, group tables, scratch), grown as a call needs them, and their host
 // staging.  launch_fit_flux_groups: the complete fields fa .. fz like launch_fit_flux; group_h / gsize_h [.] are HOST rows,
 // counted from row 0 of the tables (the host derives them from the labels); field_base: the number of field 0 of the tables in
-// the caller's call, for the refusals.  It returns with the stream idle, also when it refuses.  stamps_dev null: the groups alone,
-// nothing is solved or refused.  lists: when given, the pair list and the adjacency of the launch are copied out.
+// the caller's call, for the refusals.  It returns with the stream idle, also when it refuses.  v.stamps null: the groups alone,
+// nothing is solved or refused.  lists: when given (null: not wanted), the pair list and the adjacency of the launch are copied out.
 struct FitGroupsLists { std::vector<int> pairs, adj_ptr, adj; };
 struct FitGroupsWork {
   DevBuf<int> cnt, ptr, pairs, adj, lab, label, rtab, grows;
@@ -555,15 +592,15 @@ struct FitGroupsWork {
   DevBuf<double> scratch;
   std::vector<int> label_h, rtab_h, grows_h, gsize_h;
   std::vector<long long> gtab_h;
+  // the tables per galaxy beside the scratch: counts, scans, labels, pair list and adjacency, group tables
+  static constexpr size_t BYTES_PER_ROW = 12 * sizeof(int) + 4 * sizeof(long long);
 };
-int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* places_dev, const int* sfield_dev,
-                           const int* fptr_dev, const double* data_dev, int f0, const int* fptr_h, int fa, int fz, int field_base,
-                           int cs, int nb, int F, const FitFluxParams& p, FitGroupsWork& w, const FitFluxRows& rows,
-                           int32_t* group_h, int32_t* gsize_h, hipStream_t s, const double* weight_dev = nullptr,
-                           FitGroupsLists* lists = nullptr);
+int launch_fit_flux_groups(const char* who, const FieldStamps& v, const int* fptr_h, int fa, int fz, int field_base,
+                           const FitFluxParams& p, FitGroupsWork& w, const FitFluxRows& rows, int32_t* group_h, int32_t* gsize_h,
+                           FitGroupsLists* lists, hipStream_t s);
+// (rq.group / rq.group_size: the two host rows of the grouping; no sky, no non-negative fit)
 int scene_fit_flux_groups(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
-                          const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, int32_t* group_h,
-                          int32_t* gsize_h, int device, hipStream_t s, const double* weight_h);
+                          const double* data_h, int M, int F, const FitFluxOut& rq, int device, hipStream_t s);
 // the blend groups alone, from the placements (no stamps, no fit, no limit on a group), and optionally the pair list and the CSR
 // adjacency the fit works from, rows of the call: n_pairs / n_adj are always written, the lists where all three are given
 int scene_fit_groups(const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int M, int F, int32_t* group_h,

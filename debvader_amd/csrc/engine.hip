@@ -3949,9 +3949,9 @@ int dv_scene_fit_flux(dv_ctx* c, const float* stamps, const int32_t* places, con
     set_error("dv_scene_fit_flux: params must be given");
     return DV_E_INVALID;
   }
-  // (every refusal is scene_fit_flux's; budget 0: sized there, after them, against free device memory)
-  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, FitFluxParams{params->min_pivot, params->scratch_bytes},
-                        FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status}, 0, c->device, c->stream);
+  // (every refusal is scene_fit_flux's)
+  FitFluxOut rq{FitFluxParams{params->min_pivot, params->scratch_bytes}, FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status}};
+  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, rq, c->device, c->stream);
 }
 
 // the adaptive moments on the child images D - T + P: every refusal is scene_moments_fields'
@@ -3983,9 +3983,10 @@ int dv_scene_fit_flux_weighted(dv_ctx* c, const float* stamps, const int32_t* pl
     set_error("dv_scene_fit_flux_weighted: weight_fields must be given (dv_scene_fit_flux is the unweighted fit)");
     return DV_E_INVALID;
   }
-  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, FitFluxParams{params->min_pivot, params->scratch_bytes},
-                        FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, 0, c->device, c->stream,
-                        weight_fields, "dv_scene_fit_flux_weighted");
+  FitFluxOut rq{FitFluxParams{params->min_pivot, params->scratch_bytes},
+                FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields};
+  rq.who = "dv_scene_fit_flux_weighted";
+  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, rq, c->device, c->stream);
 }
 
 // the fit by blend groups, with weights or without: every refusal is scene_fit_flux_groups'
@@ -3999,10 +4000,12 @@ int dv_scene_fit_flux_groups(dv_ctx* c, const float* stamps, const int32_t* plac
     set_error("dv_scene_fit_flux_groups: params must be given");
     return DV_E_INVALID;
   }
-  return scene_fit_flux_groups(stamps, places, field_ptr, N, cs, nb, data_fields, M, F,
-                               FitFluxParams{params->min_pivot, params->scratch_bytes},
-                               FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, fit_group,
-                               fit_group_size, c->device, c->stream, weight_fields);
+  FitFluxOut rq{FitFluxParams{params->min_pivot, params->scratch_bytes},
+                FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields};
+  rq.group = fit_group;
+  rq.group_size = fit_group_size;
+  rq.who = "dv_scene_fit_flux_groups";
+  return scene_fit_flux_groups(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, rq, c->device, c->stream);
 }
 
 int dv_scene_fit_groups(dv_ctx* c, const int32_t* places, const int64_t* field_ptr, int64_t N, int32_t cs, int32_t M, int32_t F,
@@ -4031,10 +4034,11 @@ int dv_scene_fit_flux_sky(dv_ctx* c, const float* stamps, const int32_t* places,
     return DV_E_INVALID;
   }
   static_assert(sizeof(long long) == sizeof(int64_t), "sky_npix is int64");
-  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, FitFluxParams{params->min_pivot, params->scratch_bytes},
-                        FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, 0, c->device, c->stream,
-                        weight_fields, "dv_scene_fit_flux_sky", sky_order,
-                        FitFluxSky{-1, sky_coef, sky_cov, sky_status, (long long*)sky_npix});
+  FitFluxOut rq{FitFluxParams{params->min_pivot, params->scratch_bytes},
+                FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight_fields, sky_order,
+                FitFluxSky{-1, sky_coef, sky_cov, sky_status, (long long*)sky_npix}};
+  rq.who = "dv_scene_fit_flux_sky";
+  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, rq, c->device, c->stream);
 }
 
 // the non-negative fit, with or without weights and sky (sky_order -1: none): every refusal is scene_fit_flux's
@@ -4050,12 +4054,14 @@ int dv_scene_fit_flux_nonneg(dv_ctx* c, const float* stamps, const int32_t* plac
     set_error("dv_scene_fit_flux_nonneg: params must be given");
     return DV_E_INVALID;
   }
-  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, FitFluxParams{params->min_pivot, params->scratch_bytes},
-                        FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix, fit_scale_free,
-                                    fit_clamped, fit_dual},
-                        0, c->device, c->stream, weight_fields, "dv_scene_fit_flux_nonneg", sky_order,
-                        FitFluxSky{sky_order == -1 ? 0 : -1, sky_coef, sky_cov, sky_status, (long long*)sky_npix},
-                        FitFluxNonneg{true, max_iter, nonneg_iters, nonneg_status});
+  FitFluxOut rq{FitFluxParams{params->min_pivot, params->scratch_bytes},
+                FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix, fit_scale_free, fit_clamped,
+                            fit_dual},
+                weight_fields, sky_order,
+                FitFluxSky{sky_order == -1 ? 0 : -1, sky_coef, sky_cov, sky_status, (long long*)sky_npix},
+                FitFluxNonneg{true, max_iter, nonneg_iters, nonneg_status}};
+  rq.who = "dv_scene_fit_flux_nonneg";
+  return scene_fit_flux(stamps, places, field_ptr, N, cs, nb, data_fields, M, F, rq, c->device, c->stream);
 }
 
 int dv_scene_fit_flux_sky_gram(dv_ctx* c, const float* stamps, const int32_t* places, int64_t n, int32_t cs, int32_t nb,
@@ -5250,12 +5256,7 @@ struct ApertureFieldStage {         // the apertures of every stamp on the mean 
 // _fit_sky (7t): the order of the sky fitted jointly (-1: none) and its per-field outputs (host)
 // _fit_nonneg (7u): the non-negativity constraint, max_iter and its per-field outputs (host)
 // _fit_groups (7w): the fit by blend groups - group / group_size [N] (host), written at the seam by the host's grouping
-struct FitFluxOut {
-  FitFluxParams par{}; FitFluxRows rows{}; const double* weights = nullptr; int sky_order = -1; FitFluxSky sky{};
-  FitFluxNonneg nonneg{};
-  int32_t* group = nullptr; int32_t* group_size = nullptr;
-  bool grouped() const { return group != nullptr; }
-};
+// (FitFluxOut, common.h: the request every caller of the fit fills)
 
 struct FitFluxStage {               // the simultaneous flux fit of every field's mean stamps to its source field (7q)
   DevBuf<float> store;              // the mean stamps of all N stamps: a field's are read when its composite is complete
@@ -5263,52 +5264,14 @@ struct FitFluxStage {               // the simultaneous flux fit of every field'
   FitGroupsWork gwork;              // the fit by blend groups (7w): its tables and scratch grow at the seam as the fields need
   FitFluxRows dev{};
   Rows rows;
+  FitFluxFieldOut fields;           // the per-field outputs of a fit with sky (7t) or non-negative (7u), downloaded at the seam
   void columns(const FitFluxOut& o, int nb) { fitflux_columns(rows, dev, o.rows, nb, o.weights != nullptr, o.nonneg.on); }
   size_t bytes_per_stamp(int cs, int nb) const { return (size_t)cs * cs * nb * sizeof(float) + rows.bytes(); }
-  DevBuf<double> sky_coef, sky_cov;  // the per-field outputs of a fit with sky (7t), downloaded with the rows
-  DevBuf<int> sky_status;
-  DevBuf<long long> sky_npix;
-  FitFluxSky sky{};
-  DevBuf<int> nn_iters, nn_status;   // the per-field outputs of a non-negative fit (7u), downloaded with the rows
-  FitFluxNonneg nonneg{};
-  static size_t sky_bytes(int q, size_t M, int nb) {
-    return M * nb * ((size_t)q * (q + 1) * sizeof(double) + q * sizeof(int) + sizeof(long long));
-  }
-  static size_t nonneg_bytes(const FitFluxNonneg& o, size_t M, int nb) { return o.on ? 2 * M * nb * sizeof(int) : 0; }
   int alloc(const FitFluxPlan& plan, int64_t N, int64_t M, int cs, int nb, bool weighted, const FitFluxNonneg& nn) {
     DV_TRY(store.alloc((size_t)N * cs * cs * nb));
     DV_TRY(work.alloc(plan, M, weighted));
-    if (nn.on) {
-      DV_TRY(nn_iters.alloc((size_t)M * nb));
-      DV_TRY(nn_status.alloc((size_t)M * nb));
-      nonneg = FitFluxNonneg{true, nn.max_iter, nn_iters.get(), nn_status.get()};
-    }
-    if (const size_t q = (size_t)plan.q) {
-      const size_t e = (size_t)M * nb;
-      DV_TRY(sky_coef.alloc(e * q));
-      DV_TRY(sky_cov.alloc(e * q * q));
-      DV_TRY(sky_status.alloc(e * q));
-      DV_TRY(sky_npix.alloc(e));
-      sky = FitFluxSky{plan.q, sky_coef.get(), sky_cov.get(), sky_status.get(), sky_npix.get()};
-    }
+    DV_TRY(fields.alloc(plan.q, nn, (size_t)M, nb));
     return rows.alloc(N);
-  }
-  // fields f0 .. f0 + nf - 1 of the call to the host arrays
-  int sky_download(const FitFluxSky& h, size_t f0, size_t nf, int nb, hipStream_t s) const {
-    const size_t q = (size_t)sky.q, o = f0 * nb, e = nf * nb;
-    DV_HIP(hipMemcpyAsync(h.coef + o * q, sky.coef + o * q, e * q * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(h.cov + o * q * q, sky.cov + o * q * q, e * q * q * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(h.status + o * q, sky.status + o * q, e * q * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(h.npix + o, sky.npix + o, e * sizeof(long long), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));
-    return OK;
-  }
-  int nonneg_download(const FitFluxNonneg& h, size_t f0, size_t nf, int nb, hipStream_t s) const {
-    const size_t o = f0 * nb, e = nf * nb * sizeof(int);
-    DV_HIP(hipMemcpyAsync(h.iters + o, nonneg.iters + o, e, hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(h.status + o, nonneg.status + o, e, hipMemcpyDeviceToHost, s));
-    DV_HIP(hipStreamSynchronize(s));
-    return OK;
   }
   void bind(PipeJob::FitFlux& q) const { q.store = store; }
 };
@@ -5381,15 +5344,15 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   // host-array path, whose field sums have the same bits: they depend on the field alone.
   auto sky_alone = [&](int fa, int fz) -> int {        // the empty fields fa .. fz - 1
     if (fz <= fa) return DV_OK;
-    const FitFluxOut& o = *rq.fit_flux;
+    FitFluxOut o = *rq.fit_flux;                       // the same request, its per-field outputs and weights from field fa on
     const size_t q = (size_t)ffplan.q, e = (size_t)fa * nb;
     const std::vector<int64_t> none((size_t)(fz - fa) + 1, 0);
-    const FitFluxSky h{-1, o.sky.coef + e * q, o.sky.cov + e * q * q, o.sky.status + e * q, o.sky.npix + e};
-    FitFluxNonneg nn = o.nonneg;
-    if (nn.on) nn.iters += e, nn.status += e;
-    return scene_fit_flux(nullptr, nullptr, none.data(), 0, m->A.H, nb, fields + (size_t)fa * felems, fz - fa, F, o.par, o.rows,
-                          0, m->ctx->device, m->ctx->stream, o.weights ? o.weights + (size_t)fa * felems : nullptr, who,
-                          o.sky_order, h, nn);
+    o.sky = FitFluxSky{-1, o.sky.coef + e * q, o.sky.cov + e * q * q, o.sky.status + e * q, o.sky.npix + e};
+    if (o.nonneg.on) o.nonneg.iters += e, o.nonneg.status += e;
+    if (o.weights) o.weights += (size_t)fa * felems;
+    o.who = who;
+    return scene_fit_flux(nullptr, nullptr, none.data(), 0, m->A.H, nb, fields + (size_t)fa * felems, fz - fa, F, o, m->ctx->device,
+                          m->ctx->stream);
   };
   const bool ff_sky = rq.fit_flux && ffplan.q != 0;
   if (N == 0) return ff_sky ? sky_alone(0, M) : DV_OK;
@@ -5449,12 +5412,15 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
   if (rq.fit_flux) {
     ffs.columns(*rq.fit_flux, nb);
     reserve += (size_t)N * ffs.bytes_per_stamp(c.cs, nb) + FitFluxWork::bytes(ffplan, (size_t)M, wfields != nullptr) +
-               FitFluxStage::sky_bytes(ffplan.q, (size_t)M, nb) + FitFluxStage::nonneg_bytes(rq.fit_flux->nonneg, (size_t)M, nb);
+               FitFluxFieldOut::bytes(ffplan.q, rq.fit_flux->nonneg.on, (size_t)M, nb);
+    // (a fit without sky has always set a counting-pixel row per field and band aside that nothing allocates: the group
+    // boundaries follow from the reserve to the byte, so it stays)
+    if (!ffplan.q) reserve += (size_t)M * nb * sizeof(long long);
     if (wfields) per_field += fb;
     if (ff_groups) {                                   // the tables of the grouping per stamp, and the scratch: at most the
       int64_t nmax = 0;                                // dense matrices of the largest field, at most scratch_bytes
       for (int f = 0; f < M; ++f) nmax = std::max(nmax, field_ptr[f + 1] - field_ptr[f]);
-      reserve += (size_t)N * (12 * sizeof(int) + 4 * sizeof(long long)) +
+      reserve += (size_t)N * FitGroupsWork::BYTES_PER_ROW +
                  std::min((size_t)rq.fit_flux->par.scratch_bytes, (size_t)nb * (size_t)nmax * (size_t)nmax * sizeof(double));
     }
   }
@@ -5569,23 +5535,26 @@ static int infer_fields_impl(dv_model* m, const char* who, int32_t M, const int6
                                        aps.dev.kron + (size_t)r0 * 3, aps.dev.status + r0,
                                        tab.places.get() + 2 * (size_t)r0, tab.sfield.get() + r0, g.f0, r1 - r0, c.cs, nb, F,
                                        mean_f, fdev, rq.aper->par, aperture_field_rows_at(afs.dev, r0, rq.aper->par, nb), s));
+        // the stamps of the group's fields as the fit and the moments read them: the stamp store, the placements and the tables
+        // count from stamp 0 of the call, the resident fields from g.f0
+        FieldStamps fv{md_store ? mds.store.get() : ffs.store.get(), tab.places, tab.sfield, tab.fptr, fdev,
+                       wfields ? wdev.get() : nullptr, mean_f, g.f0, c.cs, nb, F};
         if (ff_groups)                 // (7w: the groups' rows go to the host arrays here; the call's fields are the tables')
-          DV_TRY(launch_fit_flux_groups(who, ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, fptr32.data(), fa, fz, 0,
-                                        c.cs, nb, F, rq.fit_flux->par, ffs.gwork, ffs.dev, rq.fit_flux->group,
-                                        rq.fit_flux->group_size, s, wfields ? wdev.get() : nullptr));
-        else if (rq.fit_flux)          // (the stamp store, the placements and the tables count from stamp 0 of the call)
-          DV_TRY(launch_fit_flux(ffs.store, tab.places, tab.sfield, tab.fptr, fdev, g.f0, places, fptr32.data(), fa, fz, c.cs,
-                                 nb, F, rq.fit_flux->par, ffs.work, ffs.dev, s, true, wfields ? wdev.get() : nullptr, ffs.sky,
-                                 ffs.nonneg));
-        if (rq.moments)                // (7x: the stamp store, the placements and the tables count from stamp 0 of the call)
-          DV_TRY(launch_moments_field(md_store ? mds.store.get() : ffs.store.get(), tab.places, tab.sfield, mean_f, fdev,
-                                      md_wdev ? mds.wdev.get() : mwfields ? wdev.get() : nullptr, g.f0, fptr32.data(), fa, fz,
-                                      c.cs, nb, rq.cat->par.band, F, rq.cat->par.sigma0, rq.cat->par.tol, rq.cat->par.max_iter,
-                                      mds.dev, s));
-        if (rq.fit_flux && rq.fit_flux->nonneg.on)
-          DV_TRY(ffs.nonneg_download(rq.fit_flux->nonneg, (size_t)fa, (size_t)(fz - fa + 1), nb, s));
+          DV_TRY(launch_fit_flux_groups(who, fv, fptr32.data(), fa, fz, 0, rq.fit_flux->par, ffs.gwork, ffs.dev,
+                                        rq.fit_flux->group, rq.fit_flux->group_size, nullptr, s));
+        else if (rq.fit_flux)
+          DV_TRY(launch_fit_flux(fv, places, fptr32.data(), fa, fz, rq.fit_flux->par, ffs.work, ffs.dev, ffs.fields.sky,
+                                 ffs.fields.nonneg, true, s));
+        if (rq.moments) {              // (7x: its own mask, whatever the fit weighs with)
+          fv.weight = md_wdev ? mds.wdev.get() : mwfields ? wdev.get() : nullptr;
+          DV_TRY(launch_moments_field(fv, fptr32.data(), fa, fz, rq.cat->par.band, rq.cat->par.sigma0, rq.cat->par.tol,
+                                      rq.cat->par.max_iter, mds.dev, s));
+        }
+        if (rq.fit_flux && (ff_sky || rq.fit_flux->nonneg.on)) {
+          DV_TRY(ffs.fields.download(rq.fit_flux->sky, rq.fit_flux->nonneg, (size_t)fa, (size_t)fa, (size_t)(fz - fa + 1), nb, s));
+          DV_HIP(hipStreamSynchronize(s));
+        }
         if (ff_sky) {
-          DV_TRY(ffs.sky_download(rq.fit_flux->sky, (size_t)fa, (size_t)(fz - fa + 1), nb, s));
           DV_TRY(sky_alone(sky_next, fa));
           sky_next = fz + 1;
         }
@@ -6600,16 +6569,19 @@ int dv_field_set_fit_flux(dv_field_set* fs, int64_t n_expected, const double* da
   FitFluxRows stage{h_scale.data(), h_var.data(), h_gram.data(), h_proj.data(), h_status.data()};
   if (weighted) stage.chi2 = h_chi2.data(), stage.npix = h_npix.data();
   if (nn_on) stage.scale_free = h_free.data(), stage.clamped = h_clamped.data(), stage.dual = h_dual.data();
+  // the request as every caller of the fit states it: the staged rows, the caller's per-field outputs
+  const int q = plan.q;
+  FitFluxOut rq{par, stage, weight, sky_order, FitFluxSky{q, sky_coef, sky_cov, sky_status, (long long*)sky_npix},
+                FitFluxNonneg{nn_on, nonneg_max_iter, nonneg_iters, nonneg_status}};
   FitFluxRows d{};
   Rows out;
-  fitflux_columns(out, d, stage, nb, weighted, nn_on);
-  const int q = plan.q;
+  fitflux_columns(out, d, rq.rows, nb, weighted, rq.nonneg.on);
   DV_HIP(hipSetDevice(m->ctx->device));
   // what the call holds beside the set: the regrouped copy with its tables, the rows, the dense scratch, the per-field outputs
   // and the fields it uploads
   const size_t need = (size_t)N * (stamp * sizeof(float) + 4 * sizeof(int) + out.bytes()) + ((size_t)M + 1) * sizeof(int) +
-                      FitFluxWork::bytes(plan, (size_t)M, weighted) + FitFluxStage::sky_bytes(q, (size_t)M, nb) +
-                      (nn_on ? 2 * (size_t)M * nb * sizeof(int) : 0) + ((data ? 1 : 0) + (weighted ? 1 : 0)) * M * felems * sizeof(double);
+                      FitFluxWork::bytes(plan, (size_t)M, weighted) + FitFluxFieldOut::bytes(q, nn_on, (size_t)M, nb) +
+                      ((data ? 1 : 0) + (weighted ? 1 : 0)) * M * felems * sizeof(double);
   size_t free_b = 0, total_b = 0;
   DV_HIP(hipMemGetInfo(&free_b, &total_b));
   if (need > free_b / 10 * 9) {
@@ -6622,6 +6594,7 @@ int dv_field_set_fit_flux(dv_field_set* fs, int64_t n_expected, const double* da
   DevBuf<int> places, sf, fptr, rmap;
   DevBuf<double> data_d, weight_d;
   FitFluxWork work;
+  FitFluxFieldOut fout;
   DV_TRY(stamps.alloc((size_t)N * stamp));
   DV_TRY(places.alloc((size_t)N * 2));
   DV_TRY(sf.alloc((size_t)N));
@@ -6629,23 +6602,7 @@ int dv_field_set_fit_flux(dv_field_set* fs, int64_t n_expected, const double* da
   DV_TRY(fptr.alloc((size_t)M + 1));
   DV_TRY(work.alloc(plan, M, weighted));
   DV_TRY(out.alloc(N));
-  DevBuf<double> sky_coef_d, sky_cov_d;
-  DevBuf<int> sky_status_d, nn_iters_d, nn_status_d;
-  DevBuf<long long> sky_npix_d;
-  FitFluxSky sky_d{};
-  if (q) {
-    DV_TRY(sky_coef_d.alloc((size_t)M * nb * q));
-    DV_TRY(sky_cov_d.alloc((size_t)M * nb * q * q));
-    DV_TRY(sky_status_d.alloc((size_t)M * nb * q));
-    DV_TRY(sky_npix_d.alloc((size_t)M * nb));
-    sky_d = FitFluxSky{q, sky_coef_d.get(), sky_cov_d.get(), sky_status_d.get(), sky_npix_d.get()};
-  }
-  FitFluxNonneg nn_d{};
-  if (nn_on) {
-    DV_TRY(nn_iters_d.alloc((size_t)M * nb));
-    DV_TRY(nn_status_d.alloc((size_t)M * nb));
-    nn_d = FitFluxNonneg{true, nonneg_max_iter, nn_iters_d.get(), nn_status_d.get()};
-  }
+  DV_TRY(fout.alloc(q, rq.nonneg, (size_t)M, nb));
   StreamDrain drain(s);                                // a failure waits for the stream before the call's buffers go
   if (data) {
     DV_TRY(data_d.alloc((size_t)M * felems));
@@ -6658,19 +6615,11 @@ int dv_field_set_fit_flux(dv_field_set* fs, int64_t n_expected, const double* da
   DV_HIP(hipMemcpyAsync(rmap, rowmap.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
   DV_HIP(hipMemcpyAsync(fptr, fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
   DV_TRY(launch_fitflux_regroup(rmap, fs->rstamps, fs->rplaces, fs->rfield, N, cs, nb, stamps, places, sf, s));
-  DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data ? data_d.get() : fs->base.get(), 0, places_h.data(), fptr32.data(), 0,
-                         M - 1, cs, nb, F, par, work, d, s, true, weighted ? weight_d.get() : nullptr, sky_d, nn_d));
+  const FieldStamps v{stamps, places, sf, fptr, data ? data_d.get() : fs->base.get(), weighted ? weight_d.get() : nullptr, nullptr,
+                     0, cs, nb, F};
+  DV_TRY(launch_fit_flux(v, places_h.data(), fptr32.data(), 0, M - 1, rq.par, work, d, fout.sky, fout.nonneg, true, s));
   DV_TRY(out.download(0, N, s));
-  if (nn_on) {
-    DV_HIP(hipMemcpyAsync(nonneg_iters, nn_iters_d, (size_t)M * nb * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(nonneg_status, nn_status_d, (size_t)M * nb * sizeof(int), hipMemcpyDeviceToHost, s));
-  }
-  if (q) {
-    DV_HIP(hipMemcpyAsync(sky_coef, sky_coef_d, (size_t)M * nb * q * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(sky_cov, sky_cov_d, (size_t)M * nb * q * q * sizeof(double), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(sky_status, sky_status_d, (size_t)M * nb * q * sizeof(int), hipMemcpyDeviceToHost, s));
-    DV_HIP(hipMemcpyAsync(sky_npix, sky_npix_d, (size_t)M * nb * sizeof(long long), hipMemcpyDeviceToHost, s));
-  }
+  DV_TRY(fout.download(rq.sky, rq.nonneg, 0, 0, (size_t)M, nb, s));
   DV_HIP(hipStreamSynchronize(s));
   drain.dismiss();
   // regrouped row k is resident row rowmap[k]

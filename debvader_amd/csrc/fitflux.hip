@@ -68,6 +68,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -1301,16 +1302,64 @@ void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb,
   }
 }
 
-// The complete fields fa .. fz of a call.  Every per-galaxy device array counts from row 0 of the call, like fptr (host and
-// device: the first row of every field) and sfield_dev; data_dev holds the observed fields from field f0 on.  The fields go
-// through the dense scratch in sub-ranges whose Gram matrices fit it; the split changes no bit, a field's rows depend on
-// nothing but the field.  Returns with the stream idle: the host tables of a sub-range are rebuilt for the next.  solve false:
-// step 1 alone - the scratch keeps G of the last sub-range, gram and proj are written, the other rows are not touched.
-int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const int* fptr_dev,
-                    const double* data_dev, int f0, const int32_t* places_h, const int* fptr_h, int fa, int fz, int cs, int nb,
-                    int F, const FitFluxParams& p, FitFluxWork& w, const FitFluxRows& rows, hipStream_t s, bool solve,
-                    const double* weight_dev, const FitFluxSky& sky, const FitFluxNonneg& nn) {
-  const bool chi = weight_dev && solve;                // the chi-square of the weighted fit, behind the solve
+int FitFluxFieldOut::alloc(int q, const FitFluxNonneg& nn, size_t fields, int nb) {
+  const size_t e = fields * nb;
+  if (q) {
+    DV_TRY(coef.alloc(e * q));
+    DV_TRY(cov.alloc(e * q * q));
+    DV_TRY(status.alloc(e * q));
+    DV_TRY(npix.alloc(e));
+    sky = FitFluxSky{q, coef.get(), cov.get(), status.get(), npix.get()};
+  }
+  if (nn.on) {
+    DV_TRY(iters.alloc(e));
+    DV_TRY(nn_status.alloc(e));
+    nonneg = FitFluxNonneg{true, nn.max_iter, iters.get(), nn_status.get()};
+  }
+  return OK;
+}
+
+int FitFluxFieldOut::download(const FitFluxSky& sky_h, const FitFluxNonneg& nn_h, size_t host_f0, size_t dev_f0, size_t nf, int nb,
+                              hipStream_t s) const {
+  const size_t q = (size_t)sky.q, h = host_f0 * nb, d = dev_f0 * nb, e = nf * nb;
+  if (nonneg.on) {
+    DV_HIP(hipMemcpyAsync(nn_h.iters + h, nonneg.iters + d, e * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(nn_h.status + h, nonneg.status + d, e * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+  if (q) {
+    DV_HIP(hipMemcpyAsync(sky_h.coef + h * q, sky.coef + d * q, e * q * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(sky_h.cov + h * q * q, sky.cov + d * q * q, e * q * q * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(sky_h.status + h * q, sky.status + d * q, e * q * sizeof(int), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(sky_h.npix + h, sky.npix + d, e * sizeof(long long), hipMemcpyDeviceToHost, s));
+  }
+  return OK;
+}
+
+namespace {
+// The kernel templates of the fit are picked by whether it is weighted and by its sky terms q (0, 1 or 3): fn(wt, qc) is called
+// with both as compile-time constants (std::bool_constant, std::integral_constant<int>).  A combination a call site does not
+// build is left out there with `if constexpr`: nothing is instantiated for it.
+template <typename Fn>
+void fit_variant(bool weighted, int q, Fn&& fn) {
+  auto with_q = [&](auto wt) {
+    if (q == 0) fn(wt, std::integral_constant<int, 0>{});
+    else if (q == 1) fn(wt, std::integral_constant<int, 1>{});
+    else fn(wt, std::integral_constant<int, 3>{});
+  };
+  if (weighted) with_q(std::true_type{});
+  else with_q(std::false_type{});
+}
+}  // namespace
+
+// The complete fields fa .. fz of the view v.  The fields go through the dense scratch in sub-ranges whose Gram matrices fit it;
+// the split changes no bit, a field's rows depend on nothing but the field.  Returns with the stream idle: the host tables of a
+// sub-range are rebuilt for the next.  solve false: step 1 alone - the scratch keeps G of the last sub-range, gram and proj are
+// written, the other rows are not touched.
+int launch_fit_flux(const FieldStamps& v, const int32_t* places_h, const int* fptr_h, int fa, int fz, const FitFluxParams& p,
+                    FitFluxWork& w, const FitFluxRows& rows, const FitFluxSky& sky, const FitFluxNonneg& nn, bool solve,
+                    hipStream_t s) {
+  const int cs = v.cs, nb = v.nb, F = v.F;
+  const bool chi = v.weight && solve;                  // the chi-square of the weighted fit, behind the solve
   const int q = sky.q;                                 // the sky terms of every field (7t), 0: none
   const int ntiles = q ? (int)fitflux_sky_tiles(F) : 0;
   if (q != w.q) {                                      // (cannot happen: the plan that sized the work carries q)
@@ -1370,19 +1419,11 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
       }
       if (npairs > 0) {
         DV_HIP(hipMemcpyAsync(w.pairs, w.pairs_h.data(), w.pairs_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
-#define DV_FF_GRAM(...)                                                                                                        \
-  hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, w.pairs.get(), stamps_dev, places_dev, sfield_dev, \
-                     fptr_dev, w.foff.get(), f, f0, cs, nb, F, data_dev, w.scratch.get(), rows.gram, rows.proj, weight_dev)
-        if (weight_dev) {
-          if (q == 0) DV_FF_GRAM(fitflux_gram_kernel<true>);
-          else if (q == 1) DV_FF_GRAM(fitflux_gram_kernel<true, 1>);
-          else DV_FF_GRAM(fitflux_gram_kernel<true, 3>);
-        } else {
-          if (q == 0) DV_FF_GRAM(fitflux_gram_kernel<false>);
-          else if (q == 1) DV_FF_GRAM(fitflux_gram_kernel<false, 1>);
-          else DV_FF_GRAM(fitflux_gram_kernel<false, 3>);
-        }
-#undef DV_FF_GRAM
+        fit_variant(v.weight != nullptr, q, [&](auto wt, auto qc) {
+          hipLaunchKernelGGL((fitflux_gram_kernel<decltype(wt)::value, decltype(qc)::value>), dim3((unsigned)npairs), dim3(MS_THREADS), 0, s,
+                             w.pairs.get(), v.stamps, v.places, v.sfield, v.fptr, w.foff.get(), f, v.f0, cs, nb, F, v.data,
+                             w.scratch.get(), rows.gram, rows.proj, v.weight);
+        });
         DV_HIP(hipGetLastError());
       }
       if (q) {
@@ -1392,41 +1433,34 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
           set_error("flux fit: %u fields of %d tiles exceed the grid of the field sums", nf, ntiles);
           return E_INVALID;
         }
-#define DV_FF_SKY(WT, QQ)                                                                                                       \
-  do {                                                                                                                          \
-    if (r1 > r0)                                                                                                                \
-      hipLaunchKernelGGL((fitflux_border_kernel<WT, QQ>), dim3((unsigned)(r1 - r0)), dim3(MS_THREADS), 0, s, r0, stamps_dev,       \
-                         places_dev, sfield_dev, fptr_dev, w.foff.get(), f, f0, cs, nb, F, w.scratch.get(), weight_dev);       \
-    hipLaunchKernelGGL((fitflux_skysum_kernel<WT, QQ>), dim3((unsigned)ntiles * nf, ngrp), dim3(MS_THREADS), 0, s, f - f0, nb, F,   \
-                       ntiles, data_dev, weight_dev, w.sky_part.get());                                                       \
-    hipLaunchKernelGGL((fitflux_skyreduce_kernel<QQ>), dim3(nf, (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev, w.foff.get(), f,  \
-                       nb, ntiles, w.sky_part.get(), w.scratch.get(), w.sky_sums.get(), sky.npix);                            \
-  } while (0)
-        if (weight_dev) {
-          if (q == 1) DV_FF_SKY(true, 1); else DV_FF_SKY(true, 3);
-        } else {
-          if (q == 1) DV_FF_SKY(false, 1); else DV_FF_SKY(false, 3);
-        }
-#undef DV_FF_SKY
+        fit_variant(v.weight != nullptr, q, [&](auto wt, auto qc) {
+          constexpr bool WT = decltype(wt)::value;
+          constexpr int Q = decltype(qc)::value;
+          if constexpr (Q != 0) {
+            if (r1 > r0)
+              hipLaunchKernelGGL((fitflux_border_kernel<WT, Q>), dim3((unsigned)(r1 - r0)), dim3(MS_THREADS), 0, s, r0, v.stamps,
+                                 v.places, v.sfield, v.fptr, w.foff.get(), f, v.f0, cs, nb, F, w.scratch.get(), v.weight);
+            hipLaunchKernelGGL((fitflux_skysum_kernel<WT, Q>), dim3((unsigned)ntiles * nf, ngrp), dim3(MS_THREADS), 0, s, f - v.f0,
+                               nb, F, ntiles, v.data, v.weight, w.sky_part.get());
+            hipLaunchKernelGGL((fitflux_skyreduce_kernel<Q>), dim3(nf, (unsigned)nb), dim3(MS_THREADS), 0, s, v.fptr, w.foff.get(),
+                               f, nb, ntiles, w.sky_part.get(), w.scratch.get(), w.sky_sums.get(), sky.npix);
+          }
+        });
         DV_HIP(hipGetLastError());
       }
       if (solve) {
-#define DV_FF_SOLVE(QQ)                                                                                                         \
-  hipLaunchKernelGGL((fitflux_solve_kernel<QQ>), dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev,         \
-                     w.foff.get(), f, nb, p.min_pivot, w.scratch.get(), rows.gram, rows.proj, rows.scale, rows.var, rows.status, \
-                     (const double*)w.sky_sums.get(), sky.coef, sky.cov, sky.status)
-#define DV_FF_NONNEG(QQ)                                                                                                        \
-  hipLaunchKernelGGL((fitflux_nonneg_kernel<QQ>), dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, fptr_dev,        \
-                     w.foff.get(), f, nb, p.min_pivot, nn.max_iter, w.scratch.get(), rows.gram, rows.proj, rows.scale, rows.var, \
-                     rows.status, rows.scale_free, rows.clamped, rows.dual, nn.iters, nn.status,                               \
-                     (const double*)w.sky_sums.get(), sky.coef, sky.cov, sky.status)
-        if (nn.on) {                                   // (7u: in place of the solve, on the same scratch)
-          if (q == 0) DV_FF_NONNEG(0); else if (q == 1) DV_FF_NONNEG(1); else DV_FF_NONNEG(3);
-        } else {
-          if (q == 0) DV_FF_SOLVE(0); else if (q == 1) DV_FF_SOLVE(1); else DV_FF_SOLVE(3);
-        }
-#undef DV_FF_NONNEG
-#undef DV_FF_SOLVE
+        fit_variant(false, q, [&](auto, auto qc) {     // (the solvers are the same with weights and without)
+          constexpr int Q = decltype(qc)::value;
+          if (nn.on)                                  // (7u: in place of the solve, on the same scratch)
+            hipLaunchKernelGGL((fitflux_nonneg_kernel<Q>), dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, v.fptr,
+                               w.foff.get(), f, nb, p.min_pivot, nn.max_iter, w.scratch.get(), rows.gram, rows.proj, rows.scale,
+                               rows.var, rows.status, rows.scale_free, rows.clamped, rows.dual, nn.iters, nn.status,
+                               (const double*)w.sky_sums.get(), sky.coef, sky.cov, sky.status);
+          else
+            hipLaunchKernelGGL((fitflux_solve_kernel<Q>), dim3((unsigned)(g - f), (unsigned)nb), dim3(MS_THREADS), 0, s, v.fptr,
+                               w.foff.get(), f, nb, p.min_pivot, w.scratch.get(), rows.gram, rows.proj, rows.scale, rows.var,
+                               rows.status, (const double*)w.sky_sums.get(), sky.coef, sky.cov, sky.status);
+        });
         DV_HIP(hipGetLastError());
       }
       if (chi) {
@@ -1449,14 +1483,13 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
         DV_HIP(hipMemcpyAsync(w.adj_ptr, w.adj_ptr_h.data(), (nr + 1) * sizeof(int), hipMemcpyHostToDevice, s));
         if (!w.adj_h.empty())
           DV_HIP(hipMemcpyAsync(w.adj, w.adj_h.data(), w.adj_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
-#define DV_FF_CHI2(QQ)                                                                                                          \
-  hipLaunchKernelGGL((fitflux_chi2_kernel<QQ>), dim3((unsigned)nr), dim3(MS_THREADS), 0, s, w.adj_ptr.get(), w.adj.get(), r0,     \
-                     stamps_dev, places_dev, sfield_dev, f0, cs, nb, F, data_dev, weight_dev, (const double*)rows.scale,       \
-                     (const int*)rows.status, rows.chi2, rows.npix, (const double*)sky.coef, (const int*)sky.status)
-        if (nr > 0) {
-          if (q == 0) DV_FF_CHI2(0); else if (q == 1) DV_FF_CHI2(1); else DV_FF_CHI2(3);
-        }
-#undef DV_FF_CHI2
+        if (nr > 0)
+          fit_variant(true, q, [&](auto, auto qc) {
+            hipLaunchKernelGGL((fitflux_chi2_kernel<decltype(qc)::value>), dim3((unsigned)nr), dim3(MS_THREADS), 0, s,
+                               w.adj_ptr.get(), w.adj.get(), r0, v.stamps, v.places, v.sfield, v.f0, cs, nb, F, v.data, v.weight,
+                               (const double*)rows.scale, (const int*)rows.status, rows.chi2, rows.npix, (const double*)sky.coef,
+                               (const int*)sky.status);
+          });
         DV_HIP(hipGetLastError());
       }
       DV_HIP(hipStreamSynchronize(s));
@@ -1466,141 +1499,56 @@ int launch_fit_flux(const float* stamps_dev, const int* places_dev, const int* s
   return OK;
 }
 
-// host arrays in, host rows out, whole fields at a time: as many consecutive fields as `budget` bytes of device memory hold
-// with their stamps, tables and rows (0: half of free device memory beside the scratch, taken after the refusals)
+// host arrays in, host rows out, whole fields at a time (walk_whole_fields): beside the dense scratch, the stamps, tables, rows
+// and per-field outputs of as many consecutive fields as half of free device memory holds
 int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
-                   const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, size_t budget, int device,
-                   hipStream_t s, const double* weight_h, const char* who, int sky_order, const FitFluxSky& sky_h,
-                   const FitFluxNonneg& nn_h) {
-  const bool weighted = weight_h != nullptr;
-  const bool with_sky = sky_h.q != 0;                  // (the sky calls set q to a non-zero value before the order is checked)
-  DV_TRY(fitflux_check(who, cs, nb, F, p));
-  if (with_sky) DV_TRY(fitflux_sky_check(who, sky_order, sky_h, out_h, weighted));
-  if (nn_h.on) DV_TRY(fitflux_nonneg_check(who, nn_h, out_h, N, sky_h, weighted));
-  const int q = with_sky ? fitflux_sky_q(sky_order) : 0;
+                   const double* data_h, int M, int F, const FitFluxOut& rq, int device, hipStream_t s) {
+  const char* who = rq.who;
+  const bool weighted = rq.weights != nullptr;
+  const bool with_sky = rq.sky.q != 0;                 // (the sky calls set q to a non-zero value before the order is checked)
+  DV_TRY(fitflux_check(who, cs, nb, F, rq.par));
+  if (with_sky) DV_TRY(fitflux_sky_check(who, rq.sky_order, rq.sky, rq.rows, weighted));
+  if (rq.nonneg.on) DV_TRY(fitflux_nonneg_check(who, rq.nonneg, rq.rows, N, rq.sky, weighted));
+  const int q = with_sky ? fitflux_sky_q(rq.sky_order) : 0;
   if (N < 0 || M < 0 || !field_ptr || ((N > 0 || (q && M > 0)) && !data_h) || (N > 0 && (!stamps_h || !places_h))) {
     set_error("%s: stamps, places, field_ptr and data_fields must all be given", who);
     return E_INVALID;
   }
-  DV_TRY(fitflux_rows_check(who, out_h, N, weighted));
-  DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));   // (the chunks build their own tables)
+  DV_TRY(fitflux_rows_check(who, rq.rows, N, weighted));
+  DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));   // (the walker builds its own tables)
   FitFluxPlan plan;
-  DV_TRY(fitflux_plan(who, field_ptr, M, nb, p, &plan, with_sky ? sky_order : -1, F));
-  if (nn_h.on && M > 0) {                              // (a field without unknowns: no factorisation, converged)
-    std::fill(nn_h.iters, nn_h.iters + (size_t)M * nb, 0);
-    std::fill(nn_h.status, nn_h.status + (size_t)M * nb, 0);
+  DV_TRY(fitflux_plan(who, field_ptr, M, nb, rq.par, &plan, with_sky ? rq.sky_order : -1, F));
+  if (rq.nonneg.on && M > 0) {                         // (a field without unknowns: no factorisation, converged)
+    std::fill(rq.nonneg.iters, rq.nonneg.iters + (size_t)M * nb, 0);
+    std::fill(rq.nonneg.status, rq.nonneg.status + (size_t)M * nb, 0);
   }
   if (N == 0 && !(q && M > 0)) return OK;
+  FieldStamps v{};
+  v.cs = cs, v.nb = nb, v.F = F;
   FitFluxRows d{};
-  Rows out;
-  fitflux_columns(out, d, out_h, nb, weighted, nn_h.on);
-  const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
-  const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + out.bytes();
-  const size_t sky_out = q ? (size_t)nb * ((size_t)q * (q + 1) * sizeof(double) + q * sizeof(int) + sizeof(long long)) : 0;
-  const size_t per_field = (weighted ? 2 : 1) * felems * sizeof(double) + sizeof(int) + sizeof(long long) + sky_out +
-                           (nn_h.on ? 2 * (size_t)nb * sizeof(int) : 0) +
-                           (q ? (plan.sky_part + FF_BANDS * fitflux_sky_acc(q)) * sizeof(double) : 0);
+  Rows in, out;
+  in.add(v.stamps, stamps_h, (size_t)cs * cs * nb);
+  in.add(v.places, places_h, 2);
+  fitflux_columns(out, d, rq.rows, nb, weighted, rq.nonneg.on);
+  // beside the walker's: per field its scratch offset, the sums of its sky and its outputs; once, the scratch and the lists
+  WholeFields f{nullptr, data_h, rq.weights, 0,
+                sizeof(long long) + FitFluxWork::sky_field_bytes(plan) + FitFluxFieldOut::bytes(q, rq.nonneg.on, 1, nb),
+                FitFluxWork::fixed_bytes(plan, weighted), q != 0};
   DV_HIP(hipSetDevice(device));
   FitFluxWork work;
-  if (budget == 0) {
-    size_t free_b = 0, total_b = 0;
-    DV_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t fixed = plan.scratch_elems * sizeof(double) + plan.pair_cap * 2 * sizeof(int) +
-                         (weighted ? (plan.pair_cap * 2 + plan.rows + 1) * sizeof(int) : 0);
-    budget = free_b / 2 > fixed ? free_b / 2 - fixed : 0;
-  }
-  // the chunks: consecutive fields, as many as fit (at least one)
-  std::vector<int> cuts{0};
-  size_t cmax_s = 0, cmax_f = 0;
-  for (int f = 0; f < M;) {
-    size_t bytes = 0;
-    int g = f;
-    while (g < M) {
-      const size_t add = (size_t)(field_ptr[g + 1] - field_ptr[g]) * per_stamp + per_field;
-      if (g > f && bytes + add > budget) break;
-      bytes += add;
-      ++g;
+  FitFluxFieldOut fout;
+  return walk_whole_fields(who, M, field_ptr, N, f, v, in, out, s, [&](const FieldStamps& run, int fa, int nf, int64_t r0,
+                                                                         const int* fptr_h) {
+    if (!work.scratch) {                               // (sized by the largest run)
+      DV_TRY(work.alloc(plan, (int64_t)f.max_fields, weighted));
+      DV_TRY(fout.alloc(q, rq.nonneg, f.max_fields, nb));
     }
-    if (bytes > budget) {
-      set_error("%s: field %d with its %ld stamps needs %zu bytes of device memory, %zu are available", who, f,
-                (long)(field_ptr[f + 1] - field_ptr[f]), bytes, budget);
-      return E_NOMEM;
-    }
-    cmax_s = std::max(cmax_s, (size_t)(field_ptr[g] - field_ptr[f]));
-    cmax_f = std::max(cmax_f, (size_t)(g - f));
-    cuts.push_back(g);
-    f = g;
-  }
-  DevBuf<float> stamps;
-  DevBuf<double> data, wdata;
-  DevBuf<int> places, sf, fptr;
-  DV_TRY(work.alloc(plan, (int64_t)cmax_f, weighted));
-  DV_TRY(stamps.alloc(cmax_s * stamp));
-  DV_TRY(places.alloc(cmax_s * 2));
-  DV_TRY(sf.alloc(cmax_s));
-  DV_TRY(fptr.alloc(cmax_f + 1));
-  DV_TRY(data.alloc(cmax_f * felems));
-  if (weighted) DV_TRY(wdata.alloc(cmax_f * felems));
-  DV_TRY(out.alloc((int64_t)cmax_s));
-  DevBuf<double> sky_coef, sky_cov;
-  DevBuf<int> sky_status;
-  DevBuf<long long> sky_npix;
-  FitFluxSky sky_d{};
-  if (q) {
-    DV_TRY(sky_coef.alloc(cmax_f * nb * q));
-    DV_TRY(sky_cov.alloc(cmax_f * nb * q * q));
-    DV_TRY(sky_status.alloc(cmax_f * nb * q));
-    DV_TRY(sky_npix.alloc(cmax_f * nb));
-    sky_d = FitFluxSky{q, sky_coef.get(), sky_cov.get(), sky_status.get(), sky_npix.get()};
-  }
-  DevBuf<int> nn_iters, nn_status;
-  FitFluxNonneg nn_d{};
-  if (nn_h.on) {
-    DV_TRY(nn_iters.alloc(std::max<size_t>(cmax_f, 1) * nb));
-    DV_TRY(nn_status.alloc(std::max<size_t>(cmax_f, 1) * nb));
-    nn_d = FitFluxNonneg{true, nn_h.max_iter, nn_iters.get(), nn_status.get()};
-  }
-  std::vector<int> sf_h, fptr_h;
-  StreamDrain drain(s);
-  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-    const int fa = cuts[k], fz = cuts[k + 1];          // fields fa .. fz - 1, their rows counted from the chunk's first
-    const int64_t r0 = field_ptr[fa], n = field_ptr[fz] - r0;
-    if (n == 0 && !q) continue;
-    fptr_h.assign((size_t)(fz - fa) + 1, 0);
-    sf_h.assign((size_t)n, 0);
-    for (int f = fa; f < fz; ++f) {
-      fptr_h[(size_t)(f - fa) + 1] = (int)(field_ptr[f + 1] - r0);
-      for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) sf_h[(size_t)(i - r0)] = f - fa;
-    }
-    if (n > 0) {
-      DV_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)r0 * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-      DV_HIP(hipMemcpyAsync(places, places_h + (size_t)r0 * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
-      DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    }
-    DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), fptr_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
-    if (weighted)
-      DV_HIP(hipMemcpyAsync(wdata, weight_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h ? places_h + (size_t)r0 * 2 : nullptr, fptr_h.data(), 0,
-                           fz - fa - 1, cs, nb, F, p, work, d, s, true, weighted ? wdata.get() : nullptr, sky_d, nn_d));
-    if (n > 0) DV_TRY(out.download(r0, n, s));
-    if (nn_h.on) {                                     // the per-field outputs, with the rows
-      const size_t e = (size_t)(fz - fa) * nb * sizeof(int), o = (size_t)fa * nb;
-      DV_HIP(hipMemcpyAsync(nn_h.iters + o, nn_iters, e, hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(nn_h.status + o, nn_status, e, hipMemcpyDeviceToHost, s));
-    }
-    if (q) {                                           // the per-field outputs, with the rows
-      const size_t nf = (size_t)(fz - fa), o = (size_t)fa * nb;
-      DV_HIP(hipMemcpyAsync(sky_h.coef + o * q, sky_coef, nf * nb * q * sizeof(double), hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(sky_h.cov + o * q * q, sky_cov, nf * nb * q * q * sizeof(double), hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(sky_h.status + o * q, sky_status, nf * nb * q * sizeof(int), hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(sky_h.npix + o, sky_npix, nf * nb * sizeof(long long), hipMemcpyDeviceToHost, s));
-    }
-    DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next chunk
-  }
-  drain.dismiss();
-  return OK;
+    DV_TRY(launch_fit_flux(run, places_h ? places_h + (size_t)r0 * 2 : nullptr, fptr_h, 0, nf - 1, rq.par, work, d, fout.sky,
+                           fout.nonneg, true, s));
+    return fout.download(rq.sky, rq.nonneg, (size_t)fa, 0, (size_t)nf, nb, s);   // the per-field outputs, with the rows
+  });
 }
+
 
 // The fit by blend groups of the complete fields fa .. fz (7w).  Neighbour listing and labelling on the GPU; the host downloads
 // the two totals and then the labels, 4 bytes per galaxy, and does the O(N) grouping: the groups of a field ordered by their
@@ -1610,10 +1558,10 @@ int scene_fit_flux(const float* stamps_h, const int32_t* places_h, const int64_t
 // group, so every sub-range launches the Gram kernel over the whole list and a workgroup whose group belongs to another
 // sub-range returns at once; with the default scratch there is one sub-range.  The chi-square runs once, behind the last solve,
 // on the adjacency the fill kernel wrote.
-int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* places_dev, const int* sfield_dev,
-                           const int* fptr_dev, const double* data_dev, int f0, const int* fptr_h, int fa, int fz, int field_base,
-                           int cs, int nb, int F, const FitFluxParams& p, FitGroupsWork& w, const FitFluxRows& rows,
-                           int32_t* group_h, int32_t* gsize_h, hipStream_t s, const double* weight_dev, FitGroupsLists* lists) {
+int launch_fit_flux_groups(const char* who, const FieldStamps& v, const int* fptr_h, int fa, int fz, int field_base,
+                           const FitFluxParams& p, FitGroupsWork& w, const FitFluxRows& rows, int32_t* group_h, int32_t* gsize_h,
+                           FitGroupsLists* lists, hipStream_t s) {
+  const int cs = v.cs, nb = v.nb, F = v.F;
   const int r0 = fptr_h[fa], r1 = fptr_h[fz + 1], nr = r1 - r0, nf = fz - fa + 1;
   if (nr <= 0) return OK;
   StreamDrain drain(s);                                // (a refusal or a failure below leaves the stream idle)
@@ -1621,7 +1569,7 @@ int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* 
   DV_TRY(w.ptr.ensure(2 * ((size_t)nr + 1)));
   DV_TRY(w.lab.ensure(2 * (size_t)nr));
   DV_TRY(w.label.ensure((size_t)nr));
-  hipLaunchKernelGGL(fitgroups_count_kernel, dim3((unsigned)nr), dim3(MS_THREADS), 0, s, r0, nr, places_dev, sfield_dev, fptr_dev, cs,
+  hipLaunchKernelGGL(fitgroups_count_kernel, dim3((unsigned)nr), dim3(MS_THREADS), 0, s, r0, nr, v.places, v.sfield, v.fptr, cs,
                      F, w.cnt.get());
   hipLaunchKernelGGL(fitgroups_scan_kernel, dim3(1), dim3(MS_THREADS), 0, s, nr, (const int*)w.cnt.get(), w.ptr.get());
   DV_HIP(hipGetLastError());
@@ -1638,9 +1586,9 @@ int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* 
   DV_TRY(w.pairs.ensure(std::max<size_t>(2 * npairs, 1)));
   DV_TRY(w.adj.ensure(std::max<size_t>(nadj, 1)));
   const int* adj_ptr = w.ptr.get() + nr + 1;
-  hipLaunchKernelGGL(fitgroups_fill_kernel, dim3((unsigned)nr), dim3(MS_THREADS), 0, s, r0, nr, places_dev, sfield_dev, fptr_dev, cs, F,
+  hipLaunchKernelGGL(fitgroups_fill_kernel, dim3((unsigned)nr), dim3(MS_THREADS), 0, s, r0, nr, v.places, v.sfield, v.fptr, cs, F,
                      (const int*)w.ptr.get(), w.pairs.get(), w.adj.get());
-  hipLaunchKernelGGL(fitgroups_label_kernel, dim3((unsigned)nf), dim3(MS_THREADS), 0, s, r0, nr, fa, fptr_dev, adj_ptr,
+  hipLaunchKernelGGL(fitgroups_label_kernel, dim3((unsigned)nf), dim3(MS_THREADS), 0, s, r0, nr, fa, v.fptr, adj_ptr,
                      (const int*)w.adj.get(), w.lab.get(), w.label.get());
   DV_HIP(hipGetLastError());
   w.label_h.resize((size_t)nr);
@@ -1680,7 +1628,7 @@ int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* 
       const long long n = w.gtab_h[4 * (size_t)w.rtab_h[2 * (size_t)i] + 2];
       group_h[(size_t)r0 + i] = w.label_h[(size_t)i];
       gsize_h[(size_t)r0 + i] = (int32_t)n;
-      if (!stamps_dev) continue;                       // (the groups alone: nothing is solved, nothing is refused)
+      if (!v.stamps) continue;                       // (the groups alone: nothing is solved, nothing is refused)
       if (n > FF_MAX_N && w.label_h[(size_t)i] == i - a) {
         set_error("%s: field %d: the blend group of row %ld has %ld galaxies, the grouped fit takes at most %d per group", who,
                   field_base + f, (long)(i - a), (long)n, FF_MAX_N);
@@ -1695,7 +1643,7 @@ int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* 
       }
     }
   }
-  if (!stamps_dev) {
+  if (!v.stamps) {
     drain.dismiss();                                   // (the stream is idle behind the download of the labels)
     return OK;
   }
@@ -1740,13 +1688,13 @@ int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* 
     const size_t elems = (size_t)w.gtab_h[4 * last] + (size_t)nb * n * n;
     DV_HIP(hipMemsetAsync(w.scratch, 0, elems * sizeof(double), s));
     if (npairs > 0) {
-#define DV_FG_GRAM(WT)                                                                                                          \
-  hipLaunchKernelGGL((fitflux_gram_kernel<WT, 0, true>), dim3((unsigned)npairs), dim3(MS_THREADS), 0, s, (const int*)w.pairs.get(), \
-                     stamps_dev, places_dev, sfield_dev, (const int*)nullptr, (const long long*)nullptr, 0, f0, cs, nb, F,     \
-                     data_dev, w.scratch.get(), rows.gram, rows.proj, weight_dev, (const int*)w.rtab.get(),                    \
-                     (const long long*)w.gtab.get(), r0, (int)k)
-      if (weight_dev) DV_FG_GRAM(true); else DV_FG_GRAM(false);
-#undef DV_FG_GRAM
+      fit_variant(v.weight != nullptr, 0, [&](auto wt, auto qc) {
+        if constexpr (decltype(qc)::value == 0)        // (the groups fit no sky)
+          hipLaunchKernelGGL((fitflux_gram_kernel<decltype(wt)::value, 0, true>), dim3((unsigned)npairs), dim3(MS_THREADS), 0, s,
+                             (const int*)w.pairs.get(), v.stamps, v.places, v.sfield, (const int*)nullptr,
+                             (const long long*)nullptr, 0, v.f0, cs, nb, F, v.data, w.scratch.get(), rows.gram, rows.proj, v.weight,
+                             (const int*)w.rtab.get(), (const long long*)w.gtab.get(), r0, (int)k);
+      });
     }
     hipLaunchKernelGGL((fitflux_solve_kernel<0, true>), dim3((unsigned)(gz - ga), (unsigned)nb), dim3(MS_THREADS), 0, s,
                        (const int*)nullptr, (const long long*)nullptr, ga, nb, p.min_pivot, w.scratch.get(),
@@ -1754,9 +1702,9 @@ int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* 
                        (double*)nullptr, (double*)nullptr, (int*)nullptr, (const int*)w.grows.get(), (const long long*)w.gtab.get());
     DV_HIP(hipGetLastError());
   }
-  if (weight_dev) {
+  if (v.weight) {
     hipLaunchKernelGGL((fitflux_chi2_kernel<0>), dim3((unsigned)nr), dim3(MS_THREADS), 0, s, adj_ptr, (const int*)w.adj.get(), r0,
-                       stamps_dev, places_dev, sfield_dev, f0, cs, nb, F, data_dev, weight_dev, (const double*)rows.scale,
+                       v.stamps, v.places, v.sfield, v.f0, cs, nb, F, v.data, v.weight, (const double*)rows.scale,
                        (const int*)rows.status, rows.chi2, rows.npix, (const double*)nullptr, (const int*)nullptr);
     DV_HIP(hipGetLastError());
   }
@@ -1765,99 +1713,44 @@ int launch_fit_flux_groups(const char* who, const float* stamps_dev, const int* 
   return OK;
 }
 
-// host arrays in, host rows out, whole fields at a time, as scene_fit_flux takes them: half of free device memory beside the
-// scratch for the stamps, tables, rows and fields of a chunk
+// host arrays in, host rows out, whole fields at a time, as scene_fit_flux takes them: beside the scratch, the stamps, tables,
+// rows and grouping tables of a run of fields
 int scene_fit_flux_groups(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
-                          const double* data_h, int M, int F, const FitFluxParams& p, const FitFluxRows& out_h, int32_t* group_h,
-                          int32_t* gsize_h, int device, hipStream_t s, const double* weight_h) {
-  const char* who = "dv_scene_fit_flux_groups";
-  const bool weighted = weight_h != nullptr;
-  DV_TRY(fitflux_check(who, cs, nb, F, p));
+                          const double* data_h, int M, int F, const FitFluxOut& rq, int device, hipStream_t s) {
+  const char* who = rq.who;
+  const bool weighted = rq.weights != nullptr;
+  DV_TRY(fitflux_check(who, cs, nb, F, rq.par));
   if (N < 0 || M < 0 || !field_ptr || (N > 0 && (!data_h || !stamps_h || !places_h))) {
     set_error("%s: stamps, places, field_ptr and data_fields must all be given", who);
     return E_INVALID;
   }
-  DV_TRY(fitflux_rows_check(who, out_h, N, weighted));
-  if (!weighted && (out_h.chi2 || out_h.npix)) {
+  DV_TRY(fitflux_rows_check(who, rq.rows, N, weighted));
+  if (!weighted && (rq.rows.chi2 || rq.rows.npix)) {
     set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: without weight_fields both must be NULL", who);
     return E_INVALID;
   }
-  if (N > 0 && (!group_h || !gsize_h)) {
+  if (N > 0 && (!rq.group || !rq.group_size)) {
     set_error("%s: fit_group and fit_group_size must all be given", who);
     return E_INVALID;
   }
   DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));
   if (N == 0) return OK;
+  FieldStamps v{};
+  v.cs = cs, v.nb = nb, v.F = F;
   FitFluxRows d{};
-  Rows out;
-  fitflux_columns(out, d, out_h, nb, weighted, false);
-  const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
-  // per stamp: the stamp, placement and field, the rows, and the tables of the grouping (counts, scans, labels, group tables)
-  const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + out.bytes() + 12 * sizeof(int) + 4 * sizeof(long long);
-  const size_t per_field = (weighted ? 2 : 1) * felems * sizeof(double) + sizeof(int);
+  Rows in, out;
+  in.add(v.stamps, stamps_h, (size_t)cs * cs * nb);
+  in.add(v.places, places_h, 2);
+  fitflux_columns(out, d, rq.rows, nb, weighted, false);
+  WholeFields f{nullptr, data_h, rq.weights, FitGroupsWork::BYTES_PER_ROW, 0, (size_t)rq.par.scratch_bytes, false};
   DV_HIP(hipSetDevice(device));
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t budget = free_b / 2 > (size_t)p.scratch_bytes ? free_b / 2 - (size_t)p.scratch_bytes : 0;
-  std::vector<int> cuts{0};
-  size_t cmax_s = 0, cmax_f = 0;
-  for (int f = 0; f < M;) {
-    size_t bytes = 0;
-    int g = f;
-    while (g < M) {
-      const size_t add = (size_t)(field_ptr[g + 1] - field_ptr[g]) * per_stamp + per_field;
-      if (g > f && bytes + add > budget) break;
-      bytes += add;
-      ++g;
-    }
-    if (bytes > budget) {
-      set_error("%s: field %d with its %ld stamps needs %zu bytes of device memory, %zu are available", who, f,
-                (long)(field_ptr[f + 1] - field_ptr[f]), bytes, budget);
-      return E_NOMEM;
-    }
-    cmax_s = std::max(cmax_s, (size_t)(field_ptr[g] - field_ptr[f]));
-    cmax_f = std::max(cmax_f, (size_t)(g - f));
-    cuts.push_back(g);
-    f = g;
-  }
   FitGroupsWork work;
-  DevBuf<float> stamps;
-  DevBuf<double> data, wdata;
-  DevBuf<int> places, sf, fptr;
-  DV_TRY(stamps.alloc(cmax_s * stamp));
-  DV_TRY(places.alloc(cmax_s * 2));
-  DV_TRY(sf.alloc(cmax_s));
-  DV_TRY(fptr.alloc(cmax_f + 1));
-  DV_TRY(data.alloc(cmax_f * felems));
-  if (weighted) DV_TRY(wdata.alloc(cmax_f * felems));
-  DV_TRY(out.alloc((int64_t)cmax_s));
-  std::vector<int> sf_h, fptr_h;
-  StreamDrain drain(s);
-  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-    const int fa = cuts[k], fz = cuts[k + 1];          // fields fa .. fz - 1, their rows counted from the chunk's first
-    const int64_t r0 = field_ptr[fa], n = field_ptr[fz] - r0;
-    if (n == 0) continue;
-    fptr_h.assign((size_t)(fz - fa) + 1, 0);
-    sf_h.assign((size_t)n, 0);
-    for (int f = fa; f < fz; ++f) {
-      fptr_h[(size_t)(f - fa) + 1] = (int)(field_ptr[f + 1] - r0);
-      for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) sf_h[(size_t)(i - r0)] = f - fa;
-    }
-    DV_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)r0 * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(places, places_h + (size_t)r0 * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), fptr_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(data, data_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
-    if (weighted)
-      DV_HIP(hipMemcpyAsync(wdata, weight_h + (size_t)fa * felems, (size_t)(fz - fa) * felems * sizeof(double), hipMemcpyHostToDevice, s));
-    DV_TRY(launch_fit_flux_groups(who, stamps, places, sf, fptr, data, 0, fptr_h.data(), 0, fz - fa - 1, fa, cs, nb, F, p, work, d,
-                                  group_h + r0, gsize_h + r0, s, weighted ? wdata.get() : nullptr));
-    DV_TRY(out.download(r0, n, s));
-    DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next chunk
-  }
-  drain.dismiss();
-  return OK;
+  return walk_whole_fields(who, M, field_ptr, N, f, v, in, out, s, [&](const FieldStamps& run, int fa, int nf, int64_t r0,
+                                                                         const int* fptr_h) {
+    return launch_fit_flux_groups(who, run, fptr_h, 0, nf - 1, fa, rq.par, work, d, rq.group + r0, rq.group_size + r0, nullptr, s);
+  });
 }
+
 
 // the blend groups alone, from the placements: no stamps, no fit, no limit on a group.  n_pairs / n_adj are always written;
 // pairs [n_pairs][2], adj_ptr [N + 1] and adj [n_adj] - the lists the fit works from, rows of the call - where they are given
@@ -1891,8 +1784,9 @@ int scene_fit_groups(const int32_t* places_h, const int64_t* field_ptr, int64_t 
   DV_HIP(hipMemcpyAsync(places, places_h, (size_t)N * 2 * sizeof(int), hipMemcpyHostToDevice, s));
   DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
   DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-  DV_TRY(launch_fit_flux_groups(who, nullptr, places, sf, fptr, nullptr, 0, fptr_h.data(), 0, M - 1, 0, cs, 1, F,
-                                FitFluxParams{0.5, 1}, work, FitFluxRows{}, group_h, gsize_h, s, nullptr, &lists));
+  const FieldStamps v{nullptr, places, sf, fptr, nullptr, nullptr, nullptr, 0, cs, 1, F};
+  DV_TRY(launch_fit_flux_groups(who, v, fptr_h.data(), 0, M - 1, 0, FitFluxParams{0.5, 1}, work, FitFluxRows{}, group_h, gsize_h,
+                                &lists, s));
   drain.dismiss();
   *n_pairs = (int64_t)(lists.pairs.size() / 2);
   *n_adj = (int64_t)lists.adj.size();
@@ -1927,7 +1821,7 @@ int scene_fit_flux_gram(const float* stamps_h, const int32_t* places_h, int64_t 
   for (int64_t i = 0; i < n; ++i) DV_TRY(place_check(who, i, places_h));
   const int64_t field_ptr[2] = {0, n};
   FitFluxPlan plan;
-  DV_TRY(fitflux_plan(who, field_ptr, 1, nb, p, &plan));
+  DV_TRY(fitflux_plan(who, field_ptr, 1, nb, p, &plan, -1, F));
   if (n == 0) return OK;
   const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
   DV_HIP(hipSetDevice(device));
@@ -1935,7 +1829,7 @@ int scene_fit_flux_gram(const float* stamps_h, const int32_t* places_h, int64_t 
   DevBuf<double> data, gram, proj;
   DevBuf<int> places, sf, fptr;
   FitFluxWork work;
-  DV_TRY(work.alloc(plan, 1));
+  DV_TRY(work.alloc(plan, 1, false));   // (step 1 alone: no adjacency)
   DV_TRY(stamps.alloc((size_t)n * stamp));
   DV_TRY(places.alloc((size_t)n * 2));
   DV_TRY(sf.alloc((size_t)n));
@@ -1951,7 +1845,8 @@ int scene_fit_flux_gram(const float* stamps_h, const int32_t* places_h, int64_t 
   DV_HIP(hipMemcpyAsync(fptr, fptr_h, sizeof(fptr_h), hipMemcpyHostToDevice, s));
   DV_HIP(hipMemcpyAsync(data, data_h, felems * sizeof(double), hipMemcpyHostToDevice, s));
   const FitFluxRows rows{nullptr, nullptr, gram.get(), proj.get(), nullptr};
-  DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h, fptr_h, 0, 0, cs, nb, F, p, work, rows, s, false));
+  const FieldStamps v{stamps, places, sf, fptr, data, nullptr, nullptr, 0, cs, nb, F};
+  DV_TRY(launch_fit_flux(v, places_h, fptr_h, 0, 0, p, work, rows, FitFluxSky{}, FitFluxNonneg{}, false, s));
   DV_HIP(hipMemcpyAsync(gram_h, work.scratch, need, hipMemcpyDeviceToHost, s));
   DV_HIP(hipMemcpyAsync(proj_h, proj, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));
   DV_HIP(hipStreamSynchronize(s));
@@ -1992,7 +1887,7 @@ int scene_fit_flux_sky_gram(const float* stamps_h, const int32_t* places_h, int6
   DevBuf<int> places, sf, fptr, status;
   DevBuf<long long> npix;
   FitFluxWork work;
-  DV_TRY(work.alloc(plan, 1));
+  DV_TRY(work.alloc(plan, 1, false));   // (step 1 alone: no adjacency)
   DV_TRY(stamps.alloc((size_t)n * stamp));
   DV_TRY(places.alloc((size_t)n * 2));
   DV_TRY(sf.alloc((size_t)n));
@@ -2014,8 +1909,8 @@ int scene_fit_flux_sky_gram(const float* stamps_h, const int32_t* places_h, int6
   if (weight_h) DV_HIP(hipMemcpyAsync(wdata, weight_h, felems * sizeof(double), hipMemcpyHostToDevice, s));
   const FitFluxRows rows{nullptr, nullptr, gram.get(), proj.get(), nullptr};
   const FitFluxSky sky{q, nullptr, nullptr, nullptr, npix.get()};
-  DV_TRY(launch_fit_flux(stamps, places, sf, fptr, data, 0, places_h, fptr_h, 0, 0, cs, nb, F, p, work, rows, s, false,
-                         weight_h ? wdata.get() : nullptr, sky));
+  const FieldStamps v{stamps, places, sf, fptr, data, weight_h ? wdata.get() : nullptr, nullptr, 0, cs, nb, F};
+  DV_TRY(launch_fit_flux(v, places_h, fptr_h, 0, 0, p, work, rows, sky, FitFluxNonneg{}, false, s));
   std::vector<double> sums((size_t)nb * acc);
   DV_HIP(hipMemcpyAsync(gram_h, work.scratch, need, hipMemcpyDeviceToHost, s));
   if (n > 0) DV_HIP(hipMemcpyAsync(rhs_h, proj, (size_t)n * nb * sizeof(double), hipMemcpyDeviceToHost, s));

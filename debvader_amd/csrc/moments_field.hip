@@ -140,32 +140,30 @@ void moments_field_columns(Rows& r, MomentsFieldRows& dev, const MomentsFieldRow
   r.add(dev.status, host.status, 1);
 }
 
-// The complete fields fa .. fz of a call: every per-galaxy device array counts from row 0 of the call, like fptr_h (the first
-// row of every field); the field stacks hold the fields from f0 on.  weight_dev null: no mask.
-int launch_moments_field(const float* stamps_dev, const int* places_dev, const int* sfield_dev, const double* model_dev,
-                         const double* data_dev, const double* weight_dev, int f0, const int* fptr_h, int fa, int fz, int cs,
-                         int nb, int band, int F, double sigma0, double tol, int max_iter, const MomentsFieldRows& rows,
-                         hipStream_t s) {
+// The complete fields fa .. fz of the view v: the rows count from row 0 of the set like its stamps, fptr_h is the host copy of
+// v.fptr.  v.weight null: no mask.
+int launch_moments_field(const FieldStamps& v, const int* fptr_h, int fa, int fz, int band, double sigma0, double tol,
+                         int max_iter, const MomentsFieldRows& rows, hipStream_t s) {
   if (fz < fa) return OK;
   const size_t r0 = (size_t)fptr_h[fa];
-  const int n = fptr_h[fz + 1] - fptr_h[fa];
+  const int n = fptr_h[fz + 1] - fptr_h[fa], cs = v.cs, nb = v.nb;
   if (n <= 0) return OK;
-  const float* st = stamps_dev + r0 * cs * cs * nb;
-  const int *pl = places_dev + 2 * r0, *sf = sfield_dev + r0;
+  const float* st = v.stamps + r0 * cs * cs * nb;
+  const int *pl = v.places + 2 * r0, *sf = v.sfield + r0;
   double *fl = rows.flux + r0 * nb, *sh = rows.shape + r0 * 5;
   int *np = rows.npix + r0 * nb, *it = rows.iters + r0, *stt = rows.status + r0;
-  if (weight_dev)
-    hipLaunchKernelGGL(moments_field_kernel<true>, dim3((unsigned)n), dim3(MS_THREADS), measure_lds_bytes(cs), s, st, pl, sf, f0, cs,
-                       nb, band, F, model_dev, data_dev, weight_dev, sigma0, tol, max_iter, fl, np, sh, it, stt);
+  if (v.weight)
+    hipLaunchKernelGGL(moments_field_kernel<true>, dim3((unsigned)n), dim3(MS_THREADS), measure_lds_bytes(cs), s, st, pl, sf, v.f0,
+                       cs, nb, band, v.F, v.model, v.data, v.weight, sigma0, tol, max_iter, fl, np, sh, it, stt);
   else
-    hipLaunchKernelGGL(moments_field_kernel<false>, dim3((unsigned)n), dim3(MS_THREADS), measure_lds_bytes(cs), s, st, pl, sf, f0, cs,
-                       nb, band, F, model_dev, data_dev, weight_dev, sigma0, tol, max_iter, fl, np, sh, it, stt);
+    hipLaunchKernelGGL(moments_field_kernel<false>, dim3((unsigned)n), dim3(MS_THREADS), measure_lds_bytes(cs), s, st, pl, sf, v.f0,
+                       cs, nb, band, v.F, v.model, v.data, v.weight, sigma0, tol, max_iter, fl, np, sh, it, stt);
   DV_HIP(hipGetLastError());
   return OK;
 }
 
-// host arrays in, host rows out, whole fields at a time: as many consecutive fields as half of free device memory holds with
-// their stamps, tables and rows
+// host arrays in, host rows out, whole fields at a time (walk_whole_fields): the stamps, tables, rows and the two or three
+// field stacks of a run of fields
 int scene_moments_fields(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                          const double* model_h, const double* data_h, const double* weight_h, int M, int F,
                          int band, double sigma0, double tol, int max_iter, const MomentsFieldRows& out_h, int device,
@@ -177,76 +175,20 @@ int scene_moments_fields(const float* stamps_h, const int32_t* places_h, const i
     return E_INVALID;
   }
   DV_TRY(moments_field_rows_check(who, out_h, N));
-  DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));   // (the chunks build their own tables)
+  DV_TRY(field_tables(who, "stamps", M, field_ptr, N, &F, places_h, nullptr, nullptr));   // (the walker builds its own tables)
   if (N == 0) return OK;
+  FieldStamps v{};
+  v.cs = cs, v.nb = nb, v.F = F;
   MomentsFieldRows d{};
-  Rows out;
+  Rows in, out;
+  in.add(v.stamps, stamps_h, (size_t)cs * cs * nb);
+  in.add(v.places, places_h, 2);
   moments_field_columns(out, d, out_h, nb);
-  const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
-  const size_t per_stamp = stamp * sizeof(float) + 3 * sizeof(int) + out.bytes();
-  const size_t per_field = (weight_h ? 3 : 2) * felems * sizeof(double);
+  WholeFields f{model_h, data_h, weight_h, 0, 0, 0, false};
   DV_HIP(hipSetDevice(device));
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t budget = free_b / 2;
-  // the chunks: consecutive fields, as many as fit (at least one)
-  std::vector<int> cuts{0};
-  size_t cmax_s = 0, cmax_f = 0;
-  for (int f = 0; f < M;) {
-    size_t bytes = 0;
-    int g = f;
-    while (g < M) {
-      const size_t add = (size_t)(field_ptr[g + 1] - field_ptr[g]) * per_stamp + per_field;
-      if (g > f && bytes + add > budget) break;
-      bytes += add;
-      ++g;
-    }
-    if (bytes > budget) {
-      set_error("%s: field %d with its %ld stamps needs %zu bytes of device memory, %zu are available", who, f,
-                (long)(field_ptr[f + 1] - field_ptr[f]), bytes, budget);
-      return E_NOMEM;
-    }
-    cmax_s = std::max(cmax_s, (size_t)(field_ptr[g] - field_ptr[f]));
-    cmax_f = std::max(cmax_f, (size_t)(g - f));
-    cuts.push_back(g);
-    f = g;
-  }
-  DevBuf<float> stamps;
-  DevBuf<double> model, data, wdata;
-  DevBuf<int> places, sf;
-  DV_TRY(stamps.alloc(cmax_s * stamp));
-  DV_TRY(places.alloc(cmax_s * 2));
-  DV_TRY(sf.alloc(cmax_s));
-  DV_TRY(model.alloc(cmax_f * felems));
-  DV_TRY(data.alloc(cmax_f * felems));
-  if (weight_h) DV_TRY(wdata.alloc(cmax_f * felems));
-  DV_TRY(out.alloc((int64_t)cmax_s));
-  std::vector<int> sf_h, fptr_h;
-  StreamDrain drain(s);
-  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-    const int fa = cuts[k], fz = cuts[k + 1];          // fields fa .. fz - 1, their rows counted from the chunk's first
-    const int64_t r0 = field_ptr[fa], n = field_ptr[fz] - r0;
-    if (n == 0) continue;
-    fptr_h.assign((size_t)(fz - fa) + 1, 0);
-    sf_h.assign((size_t)n, 0);
-    for (int f = fa; f < fz; ++f) {
-      fptr_h[(size_t)(f - fa) + 1] = (int)(field_ptr[f + 1] - r0);
-      for (int64_t i = field_ptr[f]; i < field_ptr[f + 1]; ++i) sf_h[(size_t)(i - r0)] = f - fa;
-    }
-    const size_t fbytes = (size_t)(fz - fa) * felems * sizeof(double), foff = (size_t)fa * felems;
-    DV_HIP(hipMemcpyAsync(stamps, stamps_h + (size_t)r0 * stamp, (size_t)n * stamp * sizeof(float), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(places, places_h + (size_t)r0 * 2, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(model, model_h + foff, fbytes, hipMemcpyHostToDevice, s));
-    DV_HIP(hipMemcpyAsync(data, data_h + foff, fbytes, hipMemcpyHostToDevice, s));
-    if (weight_h) DV_HIP(hipMemcpyAsync(wdata, weight_h + foff, fbytes, hipMemcpyHostToDevice, s));
-    DV_TRY(launch_moments_field(stamps, places, sf, model, data, weight_h ? wdata.get() : nullptr, 0, fptr_h.data(), 0,
-                                fz - fa - 1, cs, nb, band, F, sigma0, tol, max_iter, d, s));
-    DV_TRY(out.download(r0, n, s));
-    DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next chunk
-  }
-  drain.dismiss();
-  return OK;
+  return walk_whole_fields(who, M, field_ptr, N, f, v, in, out, s, [&](const FieldStamps& run, int, int nf, int64_t, const int* fptr_h) {
+    return launch_moments_field(run, fptr_h, 0, nf - 1, band, sigma0, tol, max_iter, d, s);
+  });
 }
 
 }  // namespace dv

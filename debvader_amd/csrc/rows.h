@@ -29,6 +29,10 @@ struct Rows {
   }
   template <typename T>
   void add(T*& dev, std::nullptr_t, size_t elems) { add(dev, (const T*)nullptr, elems); }
+  template <typename T>                                 // (an input column the kernels only read)
+  void add(const T*& dev, const T* host, size_t elems) {
+    cols[ncols++] = Column{(void**)&dev, (char*)const_cast<T*>(host), elems * sizeof(T)};
+  }
   size_t bytes() const;                                 // per galaxy
   int alloc(int64_t n);                                 // device memory for n rows: every column's device pointer at its row 0
   void advance(int64_t r);                              // every device pointer r rows on (the view that starts at row r)
@@ -47,7 +51,7 @@ void regauss_columns(Rows& r, RegaussRows& dev, const RegaussRows& host);
 void aperture_columns(Rows& r, ApertureRows& dev, const ApertureRows& host, const ApertureParams& p, int nb, bool err);
 void aperture_field_columns(Rows& r, ApertureFieldRows& dev, const ApertureFieldRows& host, const ApertureParams& p, int nb);
 void moments_field_columns(Rows& r, MomentsFieldRows& dev, const MomentsFieldRows& host, int nb);
-void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb, bool weighted = false, bool nonneg = false);
+void fitflux_columns(Rows& r, FitFluxRows& dev, const FitFluxRows& host, int nb, bool weighted, bool nonneg);
 
 // The refusals every field-grouped call takes for its tables, before any GPU work, and the tables: N < 2^31 `noun`s, F within
 // 1 .. 32768 (F null: the caller has its own bound), field_ptr from 0 to N and never decreasing, every placement within
@@ -82,5 +86,38 @@ struct FieldStacks {
 // body(base, n, fa) gets the chunk's first field.
 int walk_field_rows(int64_t N, const int32_t* sfield, FieldStacks& f, Rows& in, Rows& out, hipStream_t s,
                     const std::function<int(int64_t base, int n, int fa)>& body);
+
+// The cut of M fields into runs of consecutive WHOLE fields (no HIP call): run k is the fields first[k] .. first[k + 1] - 1.  A
+// run takes fields while its bytes - row_bytes per row, field_bytes per field - stay within `budget`, its fields within
+// max_fields and its rows within max_stamps (either 0: no cap); it always holds at least one field.  Returns -1, or the field
+// that exceeds the budget alone, with its bytes in *need.
+struct FieldRuns {
+  std::vector<int> first{0};
+  size_t max_rows = 0, max_fields = 0;                  // of the largest run
+};
+int plan_field_runs(const int64_t* field_ptr, int M, size_t row_bytes, size_t field_bytes, size_t budget, int64_t max_stamps,
+                    int64_t max_fields, FieldRuns* runs, size_t* need);
+
+// The host side of a call that reads the stamps of complete fields against the fields (flux fit, moments on the fields): the
+// field stacks [M][F][F][nb], any of them null; the bytes the caller allocates beside the walker's - per row, per field, and
+// `fixed` once; empty_runs: a run without rows is visited too (the sky fit solves fields that hold no galaxy).  The walker
+// sets max_rows / max_fields, the largest run, before the first body call: what the body allocates is sized by them.
+struct WholeFields {
+  const double *model_h, *data_h, *weight_h;
+  size_t row_bytes, field_bytes, fixed;
+  bool empty_runs;
+  size_t max_rows = 0, max_fields = 0;
+};
+
+// Fields [0, M) a run of whole fields at a time (plan_field_runs within half of free device memory less f.fixed, and within
+// dv_debug_scene_limits in the development build; a field that does not fit alone is refused with E_NOMEM).  `in` holds the
+// per-row inputs - the stamps and placements are columns at v.stamps / v.places - and `out` the rows; v carries cs, nb and F.
+// The walker allocates both, the field of every row, the run's field_ptr and the stacks for the largest run, and per run
+// uploads them, points v at them (f0 = 0: rows and fields count from the run's first), runs body(v, fa, nf, r0, fptr_h) for the
+// nf fields from fa, whose first row is r0 and whose rows fptr_h [nf + 1] counts from r0, downloads out to host rows r0 .. and
+// waits.  A failure waits for the stream before any buffer of the caller goes.
+int walk_whole_fields(const char* who, int M, const int64_t* field_ptr, int64_t N, WholeFields& f, FieldStamps& v, Rows& in,
+                      Rows& out, hipStream_t s,
+                      const std::function<int(const FieldStamps& v, int fa, int nf, int64_t r0, const int* fptr_h)>& body);
 
 }  // namespace dv

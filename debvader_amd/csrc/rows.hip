@@ -162,6 +162,104 @@ int walk_field_rows(int64_t N, const int32_t* sfield, FieldStacks& f, Rows& in, 
   return OK;
 }
 
+int plan_field_runs(const int64_t* field_ptr, int M, size_t row_bytes, size_t field_bytes, size_t budget, int64_t max_stamps,
+                    int64_t max_fields, FieldRuns* runs, size_t* need) {
+  std::vector<int> cuts{0};
+  size_t cmax_s = 0, cmax_f = 0;
+  for (int f = 0; f < M;) {
+    size_t bytes = 0;
+    int g = f;
+    while (g < M) {
+      const size_t add = (size_t)(field_ptr[g + 1] - field_ptr[g]) * row_bytes + field_bytes;
+      if (g > f && (bytes + add > budget || (max_fields > 0 && g - f >= max_fields) ||
+                    (max_stamps > 0 && field_ptr[g + 1] - field_ptr[f] > max_stamps)))
+        break;
+      bytes += add;
+      ++g;
+    }
+    if (bytes > budget) {
+      *need = bytes;
+      return f;
+    }
+    cmax_s = std::max(cmax_s, (size_t)(field_ptr[g] - field_ptr[f]));
+    cmax_f = std::max(cmax_f, (size_t)(g - f));
+    cuts.push_back(g);
+    f = g;
+  }
+  runs->first = std::move(cuts);
+  runs->max_rows = cmax_s;
+  runs->max_fields = cmax_f;
+  return -1;
+}
+
+int walk_whole_fields(const char* who, int M, const int64_t* field_ptr, int64_t N, WholeFields& f, FieldStamps& v, Rows& in,
+                      Rows& out, hipStream_t s,
+                      const std::function<int(const FieldStamps& v, int fa, int nf, int64_t r0, const int* fptr_h)>& body) {
+  if (N == 0 && !f.empty_runs) return OK;
+  const double* const stack_h[3] = {f.model_h, f.data_h, f.weight_h};
+  const double** const stack_v[3] = {&v.model, &v.data, &v.weight};
+  const size_t felems = (size_t)v.F * v.F * v.nb, fb = felems * sizeof(double);
+  size_t per_field = sizeof(int) + f.field_bytes;     // (the run's field_ptr)
+  for (const double* h : stack_h)
+    if (h) per_field += fb;
+  const size_t per_row = in.bytes() + out.bytes() + sizeof(int) + f.row_bytes;   // (the field of the row)
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t budget = free_b / 2 > f.fixed ? free_b / 2 - f.fixed : 0;
+  int64_t cap_rows = 0, cap_fields = 0;
+#ifdef DV_DEBUG_EXPORTS
+  cap_rows = g_cap_rows;
+  cap_fields = g_cap_fields;
+#endif
+  FieldRuns runs;
+  size_t need = 0;
+  const int refused = plan_field_runs(field_ptr, M, per_row, per_field, budget, cap_rows, cap_fields, &runs, &need);
+  if (refused >= 0) {
+    set_error("%s: field %d with its %ld stamps needs %zu bytes of device memory, %zu are available", who, refused,
+              (long)(field_ptr[refused + 1] - field_ptr[refused]), need, budget);
+    return E_NOMEM;
+  }
+  f.max_rows = runs.max_rows;
+  f.max_fields = runs.max_fields;
+  DevBuf<int> sf, fptr;
+  DevBuf<double> stack[3];
+  DV_TRY(in.alloc((int64_t)runs.max_rows));
+  DV_TRY(out.alloc((int64_t)runs.max_rows));
+  DV_TRY(sf.alloc(runs.max_rows));
+  DV_TRY(fptr.alloc(runs.max_fields + 1));
+  for (int k = 0; k < 3; ++k) {
+    if (stack_h[k]) DV_TRY(stack[k].alloc(runs.max_fields * felems));
+    *stack_v[k] = stack_h[k] ? stack[k].get() : nullptr;
+  }
+  v.sfield = sf;
+  v.fptr = fptr;
+  v.f0 = 0;
+  std::vector<int> sf_h, fptr_h;
+  StreamDrain drain(s);
+  for (size_t k = 0; k + 1 < runs.first.size(); ++k) {
+    const int fa = runs.first[k], fz = runs.first[k + 1];   // fields fa .. fz - 1, their rows counted from the run's first
+    const int64_t r0 = field_ptr[fa], n = field_ptr[fz] - r0;
+    if (n == 0 && !f.empty_runs) continue;
+    fptr_h.assign((size_t)(fz - fa) + 1, 0);
+    sf_h.assign((size_t)n, 0);
+    for (int g = fa; g < fz; ++g) {
+      fptr_h[(size_t)(g - fa) + 1] = (int)(field_ptr[g + 1] - r0);
+      for (int64_t i = field_ptr[g]; i < field_ptr[g + 1]; ++i) sf_h[(size_t)(i - r0)] = g - fa;
+    }
+    DV_TRY(in.upload(r0, n, s));
+    if (n > 0) DV_HIP(hipMemcpyAsync(sf, sf_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(fptr, fptr_h.data(), fptr_h.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    for (int j = 0; j < 3; ++j)
+      if (stack_h[j])
+        DV_HIP(hipMemcpyAsync(stack[j], stack_h[j] + (size_t)fa * felems, (size_t)(fz - fa) * fb, hipMemcpyHostToDevice, s));
+    DV_TRY(body(v, fa, fz - fa, r0, fptr_h.data()));
+    DV_TRY(out.download(r0, n, s));
+    DV_HIP(hipStreamSynchronize(s));                   // the device buffers and the host tables are reused by the next run
+  }
+  drain.dismiss();
+  return OK;
+}
+
 }  // namespace dv
 
 #ifdef DV_DEBUG_EXPORTS

@@ -47,7 +47,10 @@ int dv_debug_wgrad_check(dv_ctx* ctx, int32_t NB, int32_t H, int32_t Cx, int32_t
 int dv_debug_fuse_prelu_bwd(int32_t on);
 /* process-wide: the stand-alone catalogue calls (dv_scene_measure, _measure_mc, _blend, _regauss, _aperture,
  * _aperture_fields) hold at most max_stamps rows and max_fields fields on the device at a time, instead of what free device
- * memory allows; 0 = no cap.  Lets a test reach the second chunk of their loops with a handful of stamps. */
+ * memory allows; 0 = no cap.  Lets a test reach the second chunk of their loops with a handful of stamps.
+ * The calls that take whole fields at a time (dv_scene_fit_flux, _weighted, _sky, _nonneg, _groups, dv_scene_moments_fields)
+ * end a chunk at max_fields fields and before the field that would take it past max_stamps rows; a chunk always holds at
+ * least one field, however many rows that field has. */
 int dv_debug_scene_limits(int64_t max_stamps, int64_t max_fields);
 int dv_debug_wgrad(dv_ctx* ctx, int32_t NB, int32_t Hx, int32_t Cx, int32_t Hy, int32_t Cy, int32_t sx,
                    int32_t pad_before, int32_t single_tap, int32_t iters, float* ms_out);

@@ -1,5 +1,6 @@
 """The chunk walkers of the stand-alone catalogue calls (csrc/rows.hip): a call cut into chunks of stamps and groups of
-fields gives the bits of the call that goes through in one piece.
+fields - or, for the flux fits and the moments on the fields, into runs of whole fields - gives the bits of the call that goes
+through in one piece.
 
 Free device memory holds any test input many times over, so the second chunk of these loops - the list cut at a chunk or
 field-group boundary, every host row offset by the chunk's base - is reached only under dv_debug_scene_limits of the
@@ -8,7 +9,10 @@ test files of each call.
 
 The smallest input that crosses every kind of boundary: 5 stamps of 9 x 9 pixels and 2 bands in 3 fields of 16 pixels with
 field_ptr (0, 2, 2, 5) - the middle field is empty and a cap of 2 cuts inside the last -, one ineligible catalogue row (an
-all-zero stamp), one stamp partly outside its field, 2 PSFs of 7 pixels, 3 Monte-Carlo samples.
+all-zero stamp), one stamp partly outside its field, 2 PSFs of 7 pixels, 3 Monte-Carlo samples, one stack of weight fields
+(positive, a few zeros, one inf).  The calls that take whole fields at a time are cut by the same caps into one field per run
+- field 2 goes through with its three rows on the at-least-one-field rule, and a sky fit visits the run of the empty field 1 -
+and into fields 0 - 1, then field 2.
 """
 import ctypes as C
 import functools
@@ -23,6 +27,7 @@ pytestmark = pytest.mark.gpu
 N, CS, NB, M, F, S, BAND = 5, 9, 2, 3, 16, 3, 1
 FIELD_PTR = np.array([0, 2, 2, 5], np.int64)
 CAPS = ((2, 1), (3, 2))               # (stamps, fields): chunks of 2 + 2 + 1 in one field each; 2 + 3, the first of two fields
+#                                       (whole fields at a time: fields 0 | 1 | 2; fields 0 - 1 | 2)
 RADII, FRACTIONS, SUBSAMPLE = (1.5, 2.5), (0.5,), 3
 
 
@@ -33,7 +38,7 @@ def _blob(cs, r0, c0, s_r, s_c, amp):
 
 @functools.lru_cache(maxsize=None)
 def _inputs():
-    """(mean, stddev float32 (N, CS, CS, NB), samples float32 (S, N, CS, CS, NB), places, psf, psf_index, model, data)"""
+    """(mean, stddev float32 (N, CS, CS, NB), samples float32 (S, N, CS, CS, NB), places, psf, psf_index, model, data, weights)"""
     rng = np.random.default_rng(77)
     mean = np.zeros((N, CS, CS, NB), np.float32)
     blobs = [(4.0, 4.0, 1.4, 1.4), (3.6, 4.3, 1.2, 1.7), None, (4.4, 3.8, 1.6, 1.3), (4.1, 4.2, 1.3, 1.3)]
@@ -50,20 +55,25 @@ def _inputs():
     psf_index = np.array([0, 1, 0, 1, 1], np.int32)
     model = rng.random((M, F, F, NB))
     data = model + 0.1 * rng.standard_normal(model.shape)
-    for a in (mean, stddev, samples, places, psf, psf_index, model, data):
+    weights = rng.uniform(0.25, 4.0, size=model.shape)           # (drawn last: the inputs above keep their values)
+    weights[rng.random(model.shape) < 0.05] = 0.0
+    weights[2, 7, 12, 1] = np.inf                                # field 2, under stamps 2 and 4
+    for a in (mean, stddev, samples, places, psf, psf_index, model, data, weights):
         a.setflags(write=False)
-    return mean, stddev, samples, places, psf, psf_index, model, data
+    return mean, stddev, samples, places, psf, psf_index, model, data, weights
 
 
 def _calls(ctx):
     """name -> the call, every input fixed; the catalogue and aperture rows the later calls read are measured here, uncapped"""
-    mean, stddev, samples, places, psf, psf_index, model, data = _inputs()
+    mean, stddev, samples, places, psf, psf_index, model, data, weights = _inputs()
     cat = ctx.scene_measure(mean, band=BAND)
     assert cat["status"][2] == 3 and set(np.delete(cat["status"], 2)) <= {0, 2}      # one ineligible row among eligible ones
     shape, status = cat["shape"], cat["status"]
     ap = ctx.scene_aperture(mean, shape, status, radii=RADII, fractions=FRACTIONS, band=BAND, subsample=SUBSAMPLE)
     akw = dict(radii=RADII, fractions=FRACTIONS, band=BAND, subsample=SUBSAMPLE)
     fkw = dict(field_ptr=FIELD_PTR, cutout_size=CS, radii=RADII, subsample=SUBSAMPLE)
+    fit = (mean, places, data)
+    wkw = dict(field_ptr=FIELD_PTR, weight_fields=weights)
     return {
         "measure": lambda: ctx.scene_measure(mean, band=BAND),
         "measure_stddev": lambda: ctx.scene_measure(mean, stddev, band=BAND),
@@ -77,11 +87,23 @@ def _calls(ctx):
         "aperture_fields": lambda: ctx.scene_aperture_fields(shape, status, places, ap["kron"], ap["aper_status"], model, **fkw),
         "aperture_fields_data": lambda: ctx.scene_aperture_fields(shape, status, places, ap["kron"], ap["aper_status"], model,
                                                                   data, **fkw),
+        "fit_flux": lambda: ctx.scene_fit_flux(*fit, field_ptr=FIELD_PTR),
+        "fit_flux_weighted": lambda: ctx.scene_fit_flux(*fit, **wkw),
+        "fit_flux_sky0": lambda: ctx.scene_fit_flux_sky(*fit, field_ptr=FIELD_PTR, sky_order=0),
+        "fit_flux_sky1_weighted": lambda: ctx.scene_fit_flux_sky(*fit, sky_order=1, **wkw),
+        "fit_flux_nonneg_sky1_weighted": lambda: ctx.scene_fit_flux_nonneg(*fit, sky_order=1, **wkw),
+        "fit_flux_nonneg": lambda: ctx.scene_fit_flux_nonneg(*fit, field_ptr=FIELD_PTR),
+        "fit_flux_groups": lambda: ctx.scene_fit_flux_groups(*fit, field_ptr=FIELD_PTR),
+        "fit_flux_groups_weighted": lambda: ctx.scene_fit_flux_groups(*fit, **wkw),
+        "moments_fields_weighted": lambda: ctx.scene_moments_fields(mean, places, model, data, weights, field_ptr=FIELD_PTR, band=BAND),
+        "moments_fields": lambda: ctx.scene_moments_fields(mean, places, model, data, field_ptr=FIELD_PTR, band=BAND),
     }
 
 
 CALLS = ("measure", "measure_stddev", "measure_mc", "measure_mc_keep", "regauss", "aperture", "aperture_stddev", "blend",
-         "blend_data", "aperture_fields", "aperture_fields_data")
+         "blend_data", "aperture_fields", "aperture_fields_data", "fit_flux", "fit_flux_weighted", "fit_flux_sky0",
+         "fit_flux_sky1_weighted", "fit_flux_nonneg_sky1_weighted", "fit_flux_nonneg", "fit_flux_groups",
+         "fit_flux_groups_weighted", "moments_fields_weighted", "moments_fields")
 
 
 @pytest.mark.parametrize("name", CALLS)
@@ -92,7 +114,7 @@ def test_a_call_cut_into_chunks_gives_the_bits_of_the_whole_call(name):
     with debug_lib.debug_build() as dlib:
         call = _calls(E.default_context())[name]
         want = call()
-        assert want and all(v.shape[0] in (N, 2) for v in want.values())            # (2: the PSFs' own rows)
+        assert want and all(v.shape[0] in (N, M, 2) for v in want.values())         # (2: the PSFs' own rows; M: per field)
         for caps in CAPS:
             check(dlib.dv_debug_scene_limits(*caps))
             try:
