@@ -238,6 +238,8 @@ SIGNATURES = {
     "dv_field_set_keep_stamps": (C.c_int, [_p, C.c_int32]),
     "dv_field_set_fit_flux": (C.c_int, [_p, C.c_int64, _d, _d, C.c_int32, C.c_int32, C.POINTER(DvFitFluxParams), C.c_int32,
                                         _d, _d, _d, _d, _i32, _d, _i32, _d, _d, _i32, _i64, _d, _i32, _d, _i32, _i32]),
+    "dv_field_set_fit_flux_groups": (C.c_int, [_p, C.c_int64, _d, _d, C.POINTER(DvFitFluxParams), _d, _d, _d, _d, _i32, _d, _i32,
+                                               _i32, _i32]),
     "dv_infer_mc": (C.c_int, [_p, _f, C.c_int64, C.c_int32, C.c_uint64, _f, _f]),
     "dv_encode": (C.c_int, [_p, _f, C.c_int64, _f]),
     "dv_decode": (C.c_int, [_p, _f, C.c_int64, _f, _f]),

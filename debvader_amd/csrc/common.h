@@ -336,9 +336,12 @@ size_t measure_lds_bytes(int cs);
 // array - stamps [.][cs][cs][nb], places [.][2], sfield [.] - counts from row 0 of the set, like fptr (the first row of every
 // field, and one more); the field stacks [.][F][F][nb] hold the fields from f0 on (data: the observed fields; weight: their
 // inverse variances, laid out alike; model: the composited means - each null where the call has none).
+// srow, where given: the stamp of row i lies at stamps + srow[i] cs cs nb - a store in another order than the
+// call's; only launch_fit_flux_groups reads it, every other table and every output stays indexed by the row of the call.
 struct FieldStamps {
   const float* stamps; const int *places, *sfield, *fptr; const double *data, *weight, *model;
   int f0, cs, nb, F;
+  const int* srow = nullptr;
 };
 struct MomentsFieldRows { double* flux; int* npix; double* shape; int *iters, *status; };
 int moments_field_rows_check(const char* who, const MomentsFieldRows& o, int64_t n);

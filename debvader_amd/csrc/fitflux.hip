@@ -61,6 +61,9 @@
 // components of the graph of adjacent galaxies - the pairs of the list above - are found on the GPU (fitgroups_count / scan /
 // fill / label kernels, below) and every group is solved on its own by the GROUPED instantiations of the Gram and solve
 // kernels, which reach their rows through group tables; GROUPED = false is the code as it was, instruction for instruction.
+// The grouped fit of a resident field set works in place on a stamp store that is not in the order of the call:
+// the INDEXED instantiations of the Gram and chi-square kernels read the stamp of row i at stamps + srow[i] cs cs nb; every
+// other table, slot and output stays indexed by the row of the call.  INDEXED = false is the code as it was.
 // No atomics; ordinary vector stores only.
 #include "common.h"
 #include "measure_dev.h"
@@ -111,7 +114,11 @@ __device__ __forceinline__ void ff_load(const float* __restrict__ p, int nb, dou
 // unweighted instantiation never touches `weight`.
 __device__ __forceinline__ bool ff_counts(double w) { return w > 0.0 && w < __longlong_as_double(0x7ff0000000000000LL); }
 
-template <bool WEIGHTED, int Q = 0, bool GROUPED = false>
+// (INDEXED, 7y, is a fourth flag behind the three of 7q - 7w.  It sits in the kernel and not in a body shared by two kernels: an
+// inlined body changed the registers of the weighted instantiations.  The launches of 7q - 7w spell the flags they spelt - the
+// header read `template <bool WEIGHTED, int Q = 0, bool GROUPED = false>`, the text tests/test_fit_flux_groups_host.py looks
+// for - and compile to the code they compiled to.)
+template <bool WEIGHTED, int Q = 0, bool GROUPED = false, bool INDEXED = false>
 __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __restrict__ pairs, const float* __restrict__ stamps,
                                                                   const int* __restrict__ places, const int* __restrict__ sfield,
                                                                   const int* __restrict__ fptr, const long long* __restrict__ foff,
@@ -121,7 +128,7 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __r
                                                                   const double* __restrict__ weight,
                                                                   const int* __restrict__ rtab = nullptr,
                                                                   const long long* __restrict__ gtab = nullptr, int rbase = 0,
-                                                                  int sub = 0) {
+                                                                  int sub = 0, const int* __restrict__ srow = nullptr) {
   __shared__ double s_red[MS_RED];
   const long gi = pairs[2 * (long)blockIdx.x], gj = pairs[2 * (long)blockIdx.x + 1];
   const int m = sfield[gi];
@@ -137,8 +144,9 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_gram_kernel(const int* __r
   const int ca = max(max(pci, pcj), 0), cz = min(min(pci, pcj) + cs, F);
   const int w = cz - ca, npix = (rz - ra) * w;
   const bool diag = gi == gj;                // (uniform: the whole workgroup takes one pair)
-  const float* Pi = stamps + gi * cs * cs * nb;
-  const float* Pj = stamps + gj * cs * cs * nb;
+  // INDEXED (7y): the stamps lie where the set's passes put them, srow [.] the place of every row of the call in that store
+  const float* Pi = stamps + (INDEXED ? (long)srow[gi] : gi) * cs * cs * nb;
+  const float* Pj = stamps + (INDEXED ? (long)srow[gj] : gj) * cs * cs * nb;
   const double* D = data + (long)(m - f0) * F * F * nb;
   const double* W = WEIGHTED ? weight + (long)(m - f0) * F * F * nb : nullptr;
   double g[FF_BANDS], h[FF_BANDS], vi[FF_BANDS], vj[FF_BANDS];
@@ -829,9 +837,11 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_nonneg_kernel(const int* _
 // no global table; one ms_block_sum per band carries chi2 and the pixel count (an integer below 2^24, exact in a double).
 // Q > 0 (7t): M gains sum_t s_t B_t(p) behind the neighbours, t ascending, over the sky terms of the field with sky_status 0;
 // their coefficients and band masks lie in LDS beside the staged neighbours.  Q = 0 is the kernel as it was.
+// INDEXED (7y): srow [.] the place of every row's stamp in `stamps`; the staged s_row then holds that place, which nothing but
+// the stamp loads reads.
 constexpr int CHI_TILE = 64;
 
-template <int Q>
+template <int Q, bool INDEXED = false>
 __global__ __launch_bounds__(MS_THREADS) void fitflux_chi2_kernel(const int* __restrict__ adj_ptr, const int* __restrict__ adj, int r0,
                                                                   const float* __restrict__ stamps, const int* __restrict__ places,
                                                                   const int* __restrict__ sfield, int f0, int cs, int nb, int F,
@@ -839,7 +849,8 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_chi2_kernel(const int* __r
                                                                   const double* __restrict__ scale, const int* __restrict__ status,
                                                                   double* __restrict__ chi2, int* __restrict__ npix_out,
                                                                   const double* __restrict__ sky_coef,
-                                                                  const int* __restrict__ sky_status) {
+                                                                  const int* __restrict__ sky_status,
+                                                                  const int* __restrict__ srow = nullptr) {
   __shared__ double s_red[MS_RED];
   __shared__ double s_sky[(Q > 0 ? Q : 1) * FF_BANDS];   // Q > 0: the coefficient of sky term t in band b
   __shared__ int s_skymask[Q > 0 ? Q : 1];               //        the bands in which it has sky_status 0
@@ -862,7 +873,7 @@ __global__ __launch_bounds__(MS_THREADS) void fitflux_chi2_kernel(const int* __r
       const int j = adj[a0 + t0 + tid];
       int mask = 0;
       for (int b = 0; b < nb; ++b) mask |= (status[(long)j * nb + b] != 4) << b;
-      s_row[tid] = j;
+      s_row[tid] = INDEXED ? srow[j] : j;
       s_pr[tid] = places[2 * (long)j];
       s_pc[tid] = places[2 * (long)j + 1];
       s_mask[tid] = mask;
@@ -1689,11 +1700,16 @@ int launch_fit_flux_groups(const char* who, const FieldStamps& v, const int* fpt
     DV_HIP(hipMemsetAsync(w.scratch, 0, elems * sizeof(double), s));
     if (npairs > 0) {
       fit_variant(v.weight != nullptr, 0, [&](auto wt, auto qc) {
-        if constexpr (decltype(qc)::value == 0)        // (the groups fit no sky)
-          hipLaunchKernelGGL((fitflux_gram_kernel<decltype(wt)::value, 0, true>), dim3((unsigned)npairs), dim3(MS_THREADS), 0, s,
-                             (const int*)w.pairs.get(), v.stamps, v.places, v.sfield, (const int*)nullptr,
-                             (const long long*)nullptr, 0, v.f0, cs, nb, F, v.data, w.scratch.get(), rows.gram, rows.proj, v.weight,
-                             (const int*)w.rtab.get(), (const long long*)w.gtab.get(), r0, (int)k);
+        if constexpr (decltype(qc)::value == 0) {      // (the groups fit no sky)
+          auto gram = [&](auto indexed) {              // (7y: the stamps through v.srow, in place on a resident set's store)
+            hipLaunchKernelGGL((fitflux_gram_kernel<decltype(wt)::value, 0, true, decltype(indexed)::value>), dim3((unsigned)npairs),
+                               dim3(MS_THREADS), 0, s, (const int*)w.pairs.get(), v.stamps, v.places, v.sfield, (const int*)nullptr,
+                               (const long long*)nullptr, 0, v.f0, cs, nb, F, v.data, w.scratch.get(), rows.gram, rows.proj,
+                               v.weight, (const int*)w.rtab.get(), (const long long*)w.gtab.get(), r0, (int)k, v.srow);
+          };
+          if (v.srow) gram(std::true_type{});
+          else gram(std::false_type{});
+        }
       });
     }
     hipLaunchKernelGGL((fitflux_solve_kernel<0, true>), dim3((unsigned)(gz - ga), (unsigned)nb), dim3(MS_THREADS), 0, s,
@@ -1703,9 +1719,14 @@ int launch_fit_flux_groups(const char* who, const FieldStamps& v, const int* fpt
     DV_HIP(hipGetLastError());
   }
   if (v.weight) {
-    hipLaunchKernelGGL((fitflux_chi2_kernel<0>), dim3((unsigned)nr), dim3(MS_THREADS), 0, s, adj_ptr, (const int*)w.adj.get(), r0,
-                       v.stamps, v.places, v.sfield, v.f0, cs, nb, F, v.data, v.weight, (const double*)rows.scale,
-                       (const int*)rows.status, rows.chi2, rows.npix, (const double*)nullptr, (const int*)nullptr);
+    auto chi2 = [&](auto indexed) {
+      hipLaunchKernelGGL((fitflux_chi2_kernel<0, decltype(indexed)::value>), dim3((unsigned)nr), dim3(MS_THREADS), 0, s, adj_ptr,
+                         (const int*)w.adj.get(), r0, v.stamps, v.places, v.sfield, v.f0, cs, nb, F, v.data, v.weight,
+                         (const double*)rows.scale, (const int*)rows.status, rows.chi2, rows.npix, (const double*)nullptr,
+                         (const int*)nullptr, v.srow);
+    };
+    if (v.srow) chi2(std::true_type{});
+    else chi2(std::false_type{});
     DV_HIP(hipGetLastError());
   }
   DV_HIP(hipStreamSynchronize(s));

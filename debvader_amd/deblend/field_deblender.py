@@ -901,9 +901,7 @@ class DeblendFieldBatch:
                   moments_weights=moments_weights)
         given = [x.key for x in _EXTRAS if x.given(kw[x.key])]
         if fit_groups and (fit_sky is not None or fit_nonneg):
-            raise ValueError("fit_groups=True cannot be combined with fit_sky or fit_nonneg: those two are not built for the "
-                             "grouped fit yet (the sky couples all groups of a field, and the non-negative fit reports per "
-                             "field and band)")
+            raise ValueError(ms.GROUPS_TAKE_NO_SKY_NO_CONSTRAINT)
         for x in _EXTRAS[1:]:           # (measure_samples, the oldest, is refused below its own integer check)
             _refuse_extra(x, kw, given, measure, on_device, fit, mc)
         if sky_sigma is not None and not aperture_data and not fit_flux and not moments_data:

@@ -285,7 +285,7 @@ class IterativeDeblendFieldBatch:
     def iterative_catalogue(self, mse_criterion=100.0, mode="reference", max_iterations=None, measure=False,
                             blendedness=False, return_fields=True, band=2, sigma0=3.0, tol=1e-10, max_iter=200,
                             match_radius=2.0, fit_flux=False, fit_weights=None, fit_sky=None, fit_nonneg=False,
-                            sky_sigma=None, min_pivot=1e-8):
+                            sky_sigma=None, min_pivot=1e-8, fit_groups=False):
         """iterative_deblending() with a catalogue measured on the GPU: the same loop, the same
         list of M recarrays (kept in self.res_deblend), self.mse and fields, and with every argument behind the first
         three left at its default the same calls.  The arguments are a method of their own because the parameter list of
@@ -320,6 +320,13 @@ class IterativeDeblendFieldBatch:
             DeblendFieldBatch.deblend_fields and need fit_flux=True: fit_weights (M, F, F, bands) adds fit_chi2 and fit_npix
             and is refused beside sky_sigma, fit_sky = 0 or 1 adds measurement.fit_sky_dtype(bands) and self.sky_fit,
             fit_nonneg=True adds measurement.fit_nonneg_dtype(bands) and self.nonneg_fit - in that order.
+        fit_groups=True (needs fit_flux=True): the joint fit is solved blend group by blend group, in place on the kept
+            stamps (FieldSet.fit_flux_groups in place of FieldSet.fit_flux): a field may then hold any
+            number of galaxies summed over its passes, 1024 per group.  The columns of the fit keep the bits of the fit
+            without it wherever that one takes the field; behind them (and behind fit_chi2, fit_npix if weighted) the
+            recarrays gain measurement.fit_groups_dtype(bands): fit_group, the smallest row of the galaxy's group in its
+            field's recarray - the rows of all passes count, so a group may span passes -, and fit_group_size.  Together with
+            fit_sky or fit_nonneg it is the ValueError of DeblendFieldBatch.deblend_fields.
 
         mse_criterion, mode, max_iterations: as in iterative_deblending."""
         if mode not in ("reference", "cumulative"):
@@ -335,17 +342,22 @@ class IterativeDeblendFieldBatch:
         if measure and not (np.isfinite(match_radius) and match_radius >= 0):
             raise ValueError(f"match_radius must be finite and at least 0, got {match_radius}")
         M, F, cs = self.nb_of_fields, self.field_size, self.cutout_size
-        fit_flux, fit_nonneg = bool(fit_flux), bool(fit_nonneg)
+        fit_flux, fit_nonneg, fit_groups = bool(fit_flux), bool(fit_nonneg), bool(fit_groups)
         if fit_flux and not measure:
             raise ValueError("fit_flux=True needs measure=True: the fit scales the measured fluxes of the passes")
         for given, name in ((fit_weights is not None, "fit_weights"), (fit_sky is not None, "fit_sky"),
                             (fit_nonneg, "fit_nonneg=True"), (sky_sigma is not None, "sky_sigma")):
             if given and not fit_flux:
                 raise ValueError(f"{name} needs fit_flux=True: it belongs to the joint flux fit after the last pass")
+        if fit_groups and not fit_flux:
+            raise ValueError("fit_groups=True needs fit_flux=True: it solves the joint flux fit after the last pass blend group by "
+                             "blend group, without a limit on the galaxies of a field")
         if fit_flux:
             from debvader_amd import engine as E
             from debvader_amd.measure import measurement as ms
 
+            if fit_groups and (fit_sky is not None or fit_nonneg):
+                raise ValueError(ms.GROUPS_TAKE_NO_SKY_NO_CONSTRAINT)
             if fit_sky is not None:
                 E.sky_terms(fit_sky)
             if fit_weights is not None:
@@ -432,7 +444,10 @@ class IterativeDeblendFieldBatch:
                     nrows += N
                 k += 1
             sums = fs.blend_sums(band=band) if blendedness else None
-            if fit_flux:
+            if fit_groups:
+                fit = fs.fit_flux_groups(data_fields=self.field_images if cumulative else None, weight_fields=fit_weights,
+                                         min_pivot=min_pivot)
+            elif fit_flux:
                 fit = fs.fit_flux(data_fields=self.field_images if cumulative else None, weight_fields=fit_weights,
                                   sky_order=fit_sky, nonneg=fit_nonneg, min_pivot=min_pivot)
             if return_fields:
@@ -467,6 +482,8 @@ class IterativeDeblendFieldBatch:
         chi = dict(fit_chi2=fit["fit_chi2"][rows], fit_npix=fit["fit_npix"][rows]) if weighted else {}
         parts = [ms.fit_flux_records(*(fit[k][rows] for k in E.FIT_FLUX_KEYS), rec["flux"], sky_sigma=sigma, weighted=weighted,
                                      **chi)]
+        if "fit_group" in fit:                 # (7y: no sky and no constraint beside it)
+            parts.append(ms.fit_groups_records(fit["fit_group"][rows], fit["fit_group_size"][rows]))
         if "sky_coef" in fit:
             places = np.concatenate([e["places"] for e in extra]) if extra else np.zeros((0, 2))
             parts.append(ms.fit_sky_records(fit["sky_coef"][m:m + 1], fit["sky_cov"][m:m + 1], fit["sky_status"][m:m + 1],

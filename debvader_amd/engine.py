@@ -2372,6 +2372,37 @@ class FieldSet:
                                         order, int(nonneg), C.byref(par), max_iter, *ptrs, *sky_ptrs, *nn_ptrs))
         return out
 
+    def fit_flux_groups(self, data_fields=None, weight_fields=None, min_pivot: float = 1e-8,
+                        scratch_bytes: int = 256 << 20) -> Dict[str, np.ndarray]:
+        """fit_flux() by blend groups (dv_field_set_fit_flux_groups): the rows of all passes in the joint
+        order of fit_flux() - field by field, inside a field pass after pass -, the connected components of their overlap graph
+        found on the GPU and each solved on its own, in place on the stamp store.  A field may hold any number of rows over its
+        passes; a group of more than 1024, or whose bands x n_g x n_g doubles exceed scratch_bytes, is refused by name and the
+        set stays usable.  data_fields and weight_fields as in fit_flux(); no sky, no constraint.  The dictionary is
+        Context.scene_fit_flux_groups's, the per-galaxy arrays in call order: "fit_group" (Ntot,) int32 is the smallest row of
+        the galaxy's group counted from the field's first row in the joint order - an index into the field's rows concatenated
+        pass after pass -, "fit_group_size" the members of that group.  The bits are those of scene_fit_flux_groups on the same
+        stamps regrouped field by field, and of fit_flux() wherever that call takes the field."""
+        h = self._handle()
+        nb = self.shape[3]
+        data = None
+        if data_fields is not None:
+            data = np.ascontiguousarray(data_fields, dtype=np.float64)
+            if data.shape != tuple(self.shape):
+                raise ValueError(f"expected data fields of the shape of the set's fields {tuple(self.shape)}, got {data.shape}")
+        elif self.cumulative:
+            raise ValueError("a cumulative set keeps no copy of the fields as uploaded: give data_fields")
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, self.shape)
+        par = fit_flux_params(min_pivot, scratch_bytes)
+        n = self._rows
+        out, ptrs = _fit_flux_out(n, nb, weights is not None)
+        if weights is None:
+            ptrs += [None, None]
+        out["fit_group"], out["fit_group_size"] = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        check(lib.dv_field_set_fit_flux_groups(h, n, None if data is None else _dp(data), None if weights is None else _dp(weights),
+                                               C.byref(par), *ptrs, _ip(out["fit_group"]), _ip(out["fit_group_size"])))
+        return out
+
     def read(self, which: str) -> np.ndarray:
         """One of the set's stacks as (M, F, F, bands) float64: "work", "final", "mean" or "stddev"."""
         h = self._handle()

@@ -649,6 +649,11 @@ def _fit_fluxes(stamps_mean, places, data_fields, weight_fields, field_ptr, cata
                             sky_sigma=sky_sigma, field_ptr=field_ptr)
 
 
+GROUPS_TAKE_NO_SKY_NO_CONSTRAINT = ("fit_groups=True cannot be combined with fit_sky or fit_nonneg: those two are not built for the "
+                                    "grouped fit yet (the sky couples all groups of a field, and the non-negative fit reports per "
+                                    "field and band)")
+
+
 def fit_groups_dtype(nb_of_bands):
     """The two columns a flux fit by blend groups adds per galaxy; they do not depend on the band."""
     int(nb_of_bands)

@@ -969,6 +969,28 @@ int dv_field_set_fit_flux(dv_field_set* set, int64_t n_expected, const double* d
                           double* fit_scale_free, int32_t* fit_clamped, double* fit_dual, int32_t* nonneg_iters,
                           int32_t* nonneg_status);
 
+/* ---- the joint flux fit of all passes by blend groups ----
+ * dv_field_set_fit_flux_groups: the fit of dv_scene_fit_flux_groups on the rows of EVERY pass - the rows of the set in the joint
+ * order of dv_field_set_fit_flux (field by field, inside a field pass ascending and then the in-pass order), the blend groups
+ * the connected components of the overlap graph of that order, every group solved on its own.  fit_group [Ntot] is the
+ * smallest row of the galaxy's group counted from the field's first row IN THE JOINT ORDER - an index into the field's rows
+ * concatenated pass after pass -, fit_group_size [Ntot] the members of that group; inside a group the copy from the LATER pass
+ * is the one dropped (status 5, scale 1).  The fit works in place on the stamp store: only the placements and fields of the
+ * rows are regrouped, there is no second copy of the stamps.  `data` and `weight` [M][F][F][nb] (host) as in
+ * dv_field_set_fit_flux: weight NULL is the unweighted fit, data NULL the fields as uploaded (reference mode only); fit_chi2
+ * and fit_npix are NULL iff weight is.  Every output is in resident-row (call) order and has the bits of
+ * dv_scene_fit_flux_groups on the same stamps regrouped field by field, and - where that call takes the field - of
+ * dv_field_set_fit_flux.  No sky, no constraint.  A field may hold any number of rows.  The call reads the set and never writes
+ * it: it may be repeated.  Zero rows: returns at once.  Refused before any solve, the set left as it was and usable: n_expected
+ * is not Ntot (DV_E_INVALID); a closed set, or stamps never kept (DV_E_STATE); what dv_scene_fit_flux_groups refuses of params
+ * and nb; a blend group of more than DV_FIT_MAX_N galaxies or whose nb x n_g x n_g doubles exceed scratch_bytes (the message
+ * names the field, the group's first row and the count); DV_E_NOMEM where the tables, the scratch, the rows and the uploaded
+ * fields exceed free device memory. */
+int dv_field_set_fit_flux_groups(dv_field_set* set, int64_t n_expected, const double* data, const double* weight,
+                                 const dv_fit_flux_params* params, double* fit_scale, double* fit_var, double* fit_gram,
+                                 double* fit_proj, int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, int32_t* fit_group,
+                                 int32_t* fit_group_size);
+
 /* ---- introspection for tests and bench ----------------------------------------------------- */
 /* copy a named activation of the last step to host: "t","z","kl","eps","loc","scale","head_pre" */
 int dv_model_get_activation(dv_model* m, const char* name, float* host, size_t nbytes);

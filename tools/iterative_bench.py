@@ -12,16 +12,24 @@ link per pass are counted from the passes the run made: field-sized arrays and f
 and per-stamp scalars in the batched form.  GPU only; prints a table and one JSON line.
 
     python tools/iterative_bench.py [--fields 64] [--size 259] [--repeat 5] [--max-batch 8192] [--dtype both]
-                                    [--measure] [--no-fields] [--fit-flux [--fit-weights] [--fit-sky 0|1] [--fit-nonneg]]
+                                    [--measure] [--no-fields] [--fit-flux [--fit-weights] [--fit-sky 0|1] [--fit-nonneg]
+                                                                          [--fit-groups]] [--crowded ROWS_PER_PASS]
 
 --profile-one: warm up, run the batched form once (float32 unless --dtype says otherwise) and exit - for a kernel trace; with
---measure --fit-flux that one run is the catalogue with the joint flux fit.
+--measure --fit-flux that one run is the catalogue with the joint flux fit (with --fit-groups: the grouped one).
 --measure / --no-fields: instead of the loop, the batched form against itself through
 iterative_catalogue with measure=True, blendedness=True and / or return_fields=False - every combination the switches name,
 alternating from the same seed counter: the cost of the catalogue stage and of the three field-sized downloads.
 --fit-flux (with --measure): one more form per catalogue form, the same call with fit_flux=True - the
 joint flux fit of all passes after the last one - and the milliseconds per loop and microseconds per galaxy it adds.
 --fit-weights (uniform random inverse variances with a tenth of the pixels masked), --fit-sky and --fit-nonneg pick the variant.
+--fit-groups (with --fit-flux, without --fit-sky and --fit-nonneg): one more form beside every form with
+the fit, the same call with fit_groups=True - the joint fit by blend groups, in place on the kept stamps - and what it costs or
+saves beside the dense fit.
+--crowded ROWS_PER_PASS (a leg of its own, after the others): ONE field of --size px whose stamps fall in clusters - starts
+inside 20-pixel boxes on a pitch that keeps the clusters apart -, two measured passes of ROWS_PER_PASS windows each on a
+FieldSet with the stamps kept, then FieldSet.fit_flux_groups --repeat times: the median of the call, the groups, and whether the
+dense FieldSet.fit_flux takes the field at all.
 """
 import argparse
 import io
@@ -81,6 +89,45 @@ def batch_pass_bytes(M, detections, galaxies):
     return M + detections * 44 + (M + 1) * 8 + M * 8 + galaxies * 20 + (M + 1) * 4 + galaxies * 8 + M * 8
 
 
+def _crowded(eng, F, per_pass, repeat, dtype):
+    """One field whose stamps fall in clusters that cannot touch, two measured passes with the stamps kept, the grouped joint
+    fit timed on its own"""
+    from debvader_amd._lib import DvError
+
+    box = 20
+    pitch = CS + box + 13
+    side = max(1, (F - CS - box) // pitch + 1)
+    rng = np.random.default_rng(2)
+    field = _field(rng, F, int(round(40 * (F / 259) ** 2)))[None]
+    fs = eng.open_field_set(field)
+    fs.keep_stamps()
+    try:
+        for p in range(2):
+            k = np.arange(per_pass) % (side * side)
+            starts = (np.stack([pitch * (k // side), pitch * (k % side)], axis=1) + rng.integers(0, box, size=(per_pass, 2))).astype(np.int32)
+            fs.deblend_pass_measure(starts, starts, np.array([0, per_pass], np.int64), seed=7 + p)
+        try:
+            fs.fit_flux()
+            dense = "taken"
+        except DvError as e:
+            dense = "refused: " + str(e).split(": ", 1)[-1]
+        out = fs.fit_flux_groups()                                                    # warm-up
+        t = []
+        for _ in range(repeat):
+            t0 = time.perf_counter()
+            out = fs.fit_flux_groups()
+            t.append(time.perf_counter() - t0)
+    finally:
+        fs.close()
+    t = np.array(t)
+    sizes = out["fit_group_size"][out["fit_group"] == np.arange(2 * per_pass)]        # (one field: the label is the joint row)
+    print(f"{dtype} crowded: one field of {F} px, 2 x {per_pass} rows in {len(sizes)} groups of {int(sizes.min())} .. {int(sizes.max())}; "
+          f"the dense joint fit is {dense}")
+    print(_row(f"{dtype} grouped joint fit", t, 1, 2 * per_pass))
+    return {"rows": 2 * per_pass, "groups": int(len(sizes)), "largest": int(sizes.max()), "dense": dense,
+            "fit_flux_groups_ms": [round(1e3 * x, 2) for x in t]}
+
+
 def _row(label, t, fields, galaxies):
     med = float(np.median(t))
     return (f"{label:<22s} {fields / med:9.1f} fields/s {galaxies / med:10.0f} galaxies/s   median {1e3 * med:9.1f} ms   "
@@ -101,11 +148,20 @@ def main():
     ap.add_argument("--fit-weights", action="store_true", help="the weighted fit")
     ap.add_argument("--fit-sky", type=int, choices=(0, 1), default=None, help="the fit with a sky of that order")
     ap.add_argument("--fit-nonneg", action="store_true", help="the non-negative fit")
+    ap.add_argument("--fit-groups", action="store_true", help="with --fit-flux: also time the joint fit by blend groups")
+    ap.add_argument("--crowded", type=int, default=0, metavar="ROWS_PER_PASS",
+                    help="a leg of its own: the grouped joint fit of one field of two passes of that many clustered stamps")
     a = ap.parse_args()
     if a.fit_flux and not a.measure:
         ap.error("--fit-flux needs --measure: the fit belongs to the catalogue")
     if (a.fit_weights or a.fit_sky is not None or a.fit_nonneg) and not a.fit_flux:
         ap.error("--fit-weights, --fit-sky and --fit-nonneg need --fit-flux")
+    if a.fit_groups and (not a.fit_flux or a.fit_sky is not None or a.fit_nonneg):
+        ap.error("--fit-groups needs --fit-flux and goes with neither --fit-sky nor --fit-nonneg")
+    if a.crowded and not (a.measure or a.no_fields):
+        ap.error("--crowded is a leg of the --measure / --no-fields form")
+    if a.crowded < 0:
+        ap.error("--crowded takes the rows of a pass, at least 1")
     rng = np.random.default_rng(0)
     F, M = a.size, a.fields
     base = np.stack([_field(rng, F, int(round(40 * (F / 259) ** 2))) for _ in range(16)])
@@ -124,7 +180,7 @@ def main():
             _loop(net, fields[:2])                                                    # warm-up
             _batch(net, fields[:min(M, 8)])
             if a.profile_one and a.fit_flux:                                          # (the catalogue with the joint fit)
-                _batch(net, fields, measure=True, blendedness=True, return_fields=not a.no_fields, **fit)
+                _batch(net, fields, measure=True, blendedness=True, return_fields=not a.no_fields, fit_groups=a.fit_groups, **fit)
                 core.engine.close()
                 return
             if a.profile_one:
@@ -147,6 +203,12 @@ def main():
                 if a.no_fields:
                     forms.append(("cat. + fit, no fields", dict(cat, return_fields=False, **fit)))
                     pairs.append(("cat. + fit, no fields", "catalogue, no fields"))
+            if a.fit_groups:                   # (the grouped fit beside the dense one, and what it adds to the form without a fit)
+                forms.append(("catalogue + grouped fit", dict(cat, fit_groups=True, **fit)))
+                pairs += [("catalogue + grouped fit", "batch + catalogue"), ("catalogue + grouped fit", "catalogue + fit")]
+                if a.no_fields:
+                    forms.append(("cat. + gr. fit, no fields", dict(cat, return_fields=False, fit_groups=True, **fit)))
+                    pairs += [("cat. + gr. fit, no fields", "catalogue, no fields"), ("cat. + gr. fit, no fields", "cat. + fit, no fields")]
             with redirect_stdout(quiet):
                 for _, kw in forms[1:]:                                               # warm-up of the new stages
                     _batch(net, fields[:min(M, 8)], **{k: (v[:min(M, 8)] if k == "fit_weights" else v) for k, v in kw.items()})
@@ -169,6 +231,8 @@ def main():
                       f"({n} galaxies)")
             result[dtype] = {label: [round(1e3 * x, 2) for x in t] for label, t in times.items()}
             result[dtype]["galaxies"] = int(n)
+            if a.crowded:
+                result[dtype]["crowded"] = _crowded(core.engine, a.size, a.crowded, a.repeat, dtype)
             core.engine.close()
             continue
         tl, tb = [], []
