@@ -572,8 +572,18 @@ struct FitFluxOut {
   FitFluxParams par{}; FitFluxRows rows{}; const double* weights = nullptr; int sky_order = -1; FitFluxSky sky{};
   FitFluxNonneg nonneg{};
   int32_t* group = nullptr; int32_t* group_size = nullptr;
+  bool by_groups = false;          // the fit by groups whatever rows were given: a call that refuses missing group rows by name
   const char* who = "dv_scene_fit_flux";
-  bool grouped() const { return group != nullptr; }
+  bool grouped() const { return by_groups || group != nullptr; }
+};
+// A resident field set as the joint fit of all its passes reads it, in plain pointers.  Device: the stamp store
+// [.][cs][cs][nb] with the placement [.][2] and the field [.] of every resident row, and `base`, the fields as uploaded (null: a
+// cumulative set, which keeps none).  Host: the placements again, and per kept pass the first row of every field counted from the
+// pass's row 0 - what joint_order (rows.h) takes.
+struct ResidentRows {
+  const float* stamps; const int *places, *field; const double* base;
+  const int32_t* places_h; const std::vector<std::vector<int>>& pass_fptr;
+  size_t nrows; int M, F, nb, cs;
 };
 // the regrouping of a resident field set's rows for the joint fit of all passes: destination row d takes the stamp,
 // the placement and the field of source row rowmap_dev[d]; n destination rows, every rowmap entry a row the source holds
@@ -604,6 +614,10 @@ int launch_fit_flux_groups(const char* who, const FieldStamps& v, const int* fpt
 // (rq.group / rq.group_size: the two host rows of the grouping; no sky, no non-negative fit)
 int scene_fit_flux_groups(const float* stamps_h, const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int nb,
                           const double* data_h, int M, int F, const FitFluxOut& rq, int device, hipStream_t s);
+// The joint fit of all passes of a resident field set: the rows in joint order, the dense fit (7v) on a regrouped copy of the
+// stamps or, with rq.grouped(), the fit by blend groups (7y) in place on the store.  rq as the stand-alone calls fill it, its
+// rows [nrows][.] in resident-row order; data_h null: the set's base.  Every refusal behind the caller's own, before any GPU work.
+int field_set_fit_flux(const ResidentRows& set, const double* data_h, const FitFluxOut& rq, int device, hipStream_t s);
 // the blend groups alone, from the placements (no stamps, no fit, no limit on a group), and optionally the pair list and the CSR
 // adjacency the fit works from, rows of the call: n_pairs / n_adj are always written, the lists where all three are given
 int scene_fit_groups(const int32_t* places_h, const int64_t* field_ptr, int64_t N, int cs, int M, int F, int32_t* group_h,

@@ -6469,6 +6469,30 @@ int dv_field_set_keep_stamps(dv_field_set* fs, int32_t on) {
   return DV_OK;
 }
 
+// The two calls below are wrappers of field_set_fit_flux (fitflux.hip), which has every refusal behind these: the set's state
+// here, then what the call was given.
+static int field_set_fit_ready(const dv_field_set* fs, const char* who, const dv_fit_flux_params* params, int64_t n_expected) {
+  DV_TRY(field_set_live(fs, who));
+  if (!fs->keep) {
+    set_error("%s: the set keeps no stamps: dv_field_set_keep_stamps(set, 1) comes before the first measured pass", who);
+    return DV_E_STATE;
+  }
+  if (!params) {
+    set_error("%s: params must be given", who);
+    return DV_E_INVALID;
+  }
+  if (n_expected != (int64_t)fs->nrows) {
+    set_error("%s: %ld rows expected, the set holds %zu resident rows", who, (long)n_expected, fs->nrows);
+    return DV_E_INVALID;
+  }
+  return DV_OK;
+}
+
+static ResidentRows field_set_resident(const dv_field_set* fs) {
+  return ResidentRows{fs->rstamps.get(), fs->rplaces.get(), fs->rfield.get(), fs->base.get(), fs->places_h.data(), fs->pass_fptr,
+                      fs->nrows, fs->M, fs->F, fs->nb, fs->m->A.H};
+}
+
 int dv_field_set_fit_flux(dv_field_set* fs, int64_t n_expected, const double* data, const double* weight, int32_t sky_order,
                           int32_t nonneg, const dv_fit_flux_params* params, int32_t nonneg_max_iter, double* fit_scale,
                           double* fit_var, double* fit_gram, double* fit_proj, int32_t* fit_status, double* fit_chi2,
@@ -6476,310 +6500,35 @@ int dv_field_set_fit_flux(dv_field_set* fs, int64_t n_expected, const double* da
                           double* fit_scale_free, int32_t* fit_clamped, double* fit_dual, int32_t* nonneg_iters,
                           int32_t* nonneg_status) {
   const char* who = "dv_field_set_fit_flux";
-  DV_TRY(field_set_live(fs, who));
-  if (!fs->keep) {
-    set_error("%s: the set keeps no stamps: dv_field_set_keep_stamps(set, 1) comes before the first measured pass", who);
-    return DV_E_STATE;
-  }
-  if (!params) {
-    set_error("%s: params must be given", who);
-    return DV_E_INVALID;
-  }
-  if (n_expected != (int64_t)fs->nrows) {
-    set_error("%s: %ld rows expected, the set holds %zu resident rows", who, (long)n_expected, fs->nrows);
-    return DV_E_INVALID;
-  }
+  DV_TRY(field_set_fit_ready(fs, who, params, n_expected));
   if (sky_order < -1 || sky_order > 1) {
     set_error("%s: sky_order must be -1 (no sky), 0 (a constant) or 1 (a plane), got %d", who, sky_order);
     return DV_E_INVALID;
   }
-  dv_model* m = fs->m;
-  const int M = fs->M, F = fs->F, nb = fs->nb, cs = m->A.H;
-  const int64_t N = (int64_t)fs->nrows;
-  const bool weighted = weight != nullptr, with_sky = sky_order >= 0, nn_on = nonneg != 0;
-  const FitFluxParams par{params->min_pivot, params->scratch_bytes};
-  DV_TRY(fitflux_check(who, cs, nb, F, par));
-  if (nn_on && nonneg_max_iter < 1) {
-    set_error("%s: max_iter must be at least 1 (got %d)", who, nonneg_max_iter);
-    return DV_E_INVALID;
-  }
-  // every output the chosen variant produces, and no other
-  if (N > 0 && (!fit_scale || !fit_var || !fit_gram || !fit_proj || !fit_status)) {
-    set_error("%s: fit_scale, fit_var, fit_gram, fit_proj and fit_status must all be given", who);
-    return DV_E_INVALID;
-  }
-  if (weighted ? (N > 0 && (!fit_chi2 || !fit_npix)) : (fit_chi2 || fit_npix)) {
-    set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: both given with weight, both NULL without", who);
-    return DV_E_INVALID;
-  }
-  if (with_sky ? (!sky_coef || !sky_cov || !sky_status || !sky_npix) : (sky_coef || sky_cov || sky_status || sky_npix)) {
-    set_error("%s: sky_coef, sky_cov, sky_status and sky_npix are the outputs of the fit with sky: all given with sky_order 0 or "
-              "1, all NULL with -1", who);
-    return DV_E_INVALID;
-  }
-  if (nn_on ? (!nonneg_iters || !nonneg_status || (N > 0 && (!fit_scale_free || !fit_clamped || !fit_dual)))
-            : (fit_scale_free || fit_clamped || fit_dual || nonneg_iters || nonneg_status)) {
-    set_error("%s: fit_scale_free, fit_clamped, fit_dual, nonneg_iters and nonneg_status are the outputs of the non-negative fit: "
-              "all given with nonneg, all NULL without", who);
-    return DV_E_INVALID;
-  }
-  if (!data && fs->cumulative) {
-    set_error("%s: a cumulative set keeps no copy of the fields as uploaded (every pass subtracts from the working residual): "
-              "data must be given", who);
-    return DV_E_INVALID;
-  }
-  // the joint field_ptr of all passes and rowmap[dst] = resident row, field-major: pass ascending inside a field, then the
-  // in-pass order (of two models that cannot be told apart the copy from the later pass is the one dropped)
-  std::vector<int64_t> fp64((size_t)M + 1, 0);
-  for (int f = 0; f < M; ++f) {
-    int64_t n = 0;
-    for (const std::vector<int>& p : fs->pass_fptr) n += p[(size_t)f + 1] - p[(size_t)f];
-    fp64[(size_t)f + 1] = fp64[(size_t)f] + n;
-  }
-  if (fp64[(size_t)M] != N) {                           // (cannot happen: both count the passes that kept rows)
-    set_error("%s: the passes on record hold %ld rows, the set %zu", who, (long)fp64[(size_t)M], fs->nrows);
-    return DV_E_STATE;
-  }
-  FitFluxPlan plan;
-  DV_TRY(fitflux_plan(who, fp64.data(), M, nb, par, &plan, sky_order, F));
-  if (N == 0) return DV_OK;
-  std::vector<int> rowmap((size_t)N), fptr32((size_t)M + 1);
-  std::vector<int32_t> places_h((size_t)N * 2);
-  {
-    size_t d = 0;
-    for (int f = 0; f < M; ++f) {
-      fptr32[(size_t)f] = (int)fp64[(size_t)f];
-      size_t base = 0;
-      for (const std::vector<int>& p : fs->pass_fptr) {
-        for (int i = p[(size_t)f]; i < p[(size_t)f + 1]; ++i) rowmap[d++] = (int)(base + (size_t)i);
-        base += (size_t)p[(size_t)M];
-      }
-    }
-    fptr32[(size_t)M] = (int)N;
-    for (size_t k = 0; k < (size_t)N; ++k) {
-      places_h[2 * k] = fs->places_h[2 * (size_t)rowmap[k]];
-      places_h[2 * k + 1] = fs->places_h[2 * (size_t)rowmap[k] + 1];
-    }
-  }
-  // host staging in regrouped order; the outputs leave in resident-row order through rowmap
-  const size_t nn = (size_t)N * nb, stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
-  std::vector<double> h_scale(nn), h_var(nn), h_gram(nn), h_proj(nn), h_chi2(weighted ? nn : 0), h_free(nn_on ? nn : 0),
-      h_dual(nn_on ? nn : 0);
-  std::vector<int> h_status(nn), h_npix(weighted ? nn : 0), h_clamped(nn_on ? nn : 0);
-  FitFluxRows stage{h_scale.data(), h_var.data(), h_gram.data(), h_proj.data(), h_status.data()};
-  if (weighted) stage.chi2 = h_chi2.data(), stage.npix = h_npix.data();
-  if (nn_on) stage.scale_free = h_free.data(), stage.clamped = h_clamped.data(), stage.dual = h_dual.data();
-  // the request as every caller of the fit states it: the staged rows, the caller's per-field outputs
-  const int q = plan.q;
-  FitFluxOut rq{par, stage, weight, sky_order, FitFluxSky{q, sky_coef, sky_cov, sky_status, (long long*)sky_npix},
-                FitFluxNonneg{nn_on, nonneg_max_iter, nonneg_iters, nonneg_status}};
-  FitFluxRows d{};
-  Rows out;
-  fitflux_columns(out, d, rq.rows, nb, weighted, rq.nonneg.on);
-  DV_HIP(hipSetDevice(m->ctx->device));
-  // what the call holds beside the set: the regrouped copy with its tables, the rows, the dense scratch, the per-field outputs
-  // and the fields it uploads
-  const size_t need = (size_t)N * (stamp * sizeof(float) + 4 * sizeof(int) + out.bytes()) + ((size_t)M + 1) * sizeof(int) +
-                      FitFluxWork::bytes(plan, (size_t)M, weighted) + FitFluxFieldOut::bytes(q, nn_on, (size_t)M, nb) +
-                      ((data ? 1 : 0) + (weighted ? 1 : 0)) * M * felems * sizeof(double);
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (need > free_b / 10 * 9) {
-    set_error("%s: the regrouped stamps of %ld rows, the dense scratch and the uploaded fields need %zu bytes of device memory, "
-              "%zu are free", who, (long)N, need, free_b);
-    return DV_E_NOMEM;
-  }
-  hipStream_t s = m->ctx->stream;
-  DevBuf<float> stamps;
-  DevBuf<int> places, sf, fptr, rmap;
-  DevBuf<double> data_d, weight_d;
-  FitFluxWork work;
-  FitFluxFieldOut fout;
-  DV_TRY(stamps.alloc((size_t)N * stamp));
-  DV_TRY(places.alloc((size_t)N * 2));
-  DV_TRY(sf.alloc((size_t)N));
-  DV_TRY(rmap.alloc((size_t)N));
-  DV_TRY(fptr.alloc((size_t)M + 1));
-  DV_TRY(work.alloc(plan, M, weighted));
-  DV_TRY(out.alloc(N));
-  DV_TRY(fout.alloc(q, rq.nonneg, (size_t)M, nb));
-  StreamDrain drain(s);                                // a failure waits for the stream before the call's buffers go
-  if (data) {
-    DV_TRY(data_d.alloc((size_t)M * felems));
-    DV_HIP(hipMemcpyAsync(data_d, data, (size_t)M * felems * sizeof(double), hipMemcpyHostToDevice, s));
-  }
-  if (weighted) {
-    DV_TRY(weight_d.alloc((size_t)M * felems));
-    DV_HIP(hipMemcpyAsync(weight_d, weight, (size_t)M * felems * sizeof(double), hipMemcpyHostToDevice, s));
-  }
-  DV_HIP(hipMemcpyAsync(rmap, rowmap.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
-  DV_HIP(hipMemcpyAsync(fptr, fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-  DV_TRY(launch_fitflux_regroup(rmap, fs->rstamps, fs->rplaces, fs->rfield, N, cs, nb, stamps, places, sf, s));
-  const FieldStamps v{stamps, places, sf, fptr, data ? data_d.get() : fs->base.get(), weighted ? weight_d.get() : nullptr, nullptr,
-                     0, cs, nb, F};
-  DV_TRY(launch_fit_flux(v, places_h.data(), fptr32.data(), 0, M - 1, rq.par, work, d, fout.sky, fout.nonneg, true, s));
-  DV_TRY(out.download(0, N, s));
-  DV_TRY(fout.download(rq.sky, rq.nonneg, 0, 0, (size_t)M, nb, s));
-  DV_HIP(hipStreamSynchronize(s));
-  drain.dismiss();
-  // regrouped row k is resident row rowmap[k]
-  for (size_t k = 0; k < (size_t)N; ++k) {
-    const size_t r = (size_t)rowmap[k] * nb, o = k * nb;
-    for (int b = 0; b < nb; ++b) {
-      fit_scale[r + b] = h_scale[o + b];
-      fit_var[r + b] = h_var[o + b];
-      fit_gram[r + b] = h_gram[o + b];
-      fit_proj[r + b] = h_proj[o + b];
-      fit_status[r + b] = h_status[o + b];
-      if (weighted) fit_chi2[r + b] = h_chi2[o + b], fit_npix[r + b] = h_npix[o + b];
-      if (nn_on) fit_scale_free[r + b] = h_free[o + b], fit_clamped[r + b] = h_clamped[o + b], fit_dual[r + b] = h_dual[o + b];
-    }
-  }
-  return DV_OK;
+  FitFluxOut rq{FitFluxParams{params->min_pivot, params->scratch_bytes},
+                FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix, fit_scale_free, fit_clamped,
+                            fit_dual},
+                weight, sky_order,
+                FitFluxSky{sky_order == -1 ? 0 : -1, sky_coef, sky_cov, sky_status, (long long*)sky_npix},
+                FitFluxNonneg{nonneg != 0, nonneg_max_iter, nonneg_iters, nonneg_status}};
+  rq.who = who;
+  return field_set_fit_flux(field_set_resident(fs), data, rq, fs->m->ctx->device, fs->m->ctx->stream);
 }
 
-// ---- the joint flux fit of all passes by blend groups, in place on the stamp store -------------------------------
-// The rows of the set in 7v's joint order, the groups and solves of 7w on that order.  Only the per-row scalars are regrouped
-// - placement, field and srow[joint row] = resident row, built on the host from what the set remembers and uploaded -; the
-// stamps stay at their resident rows and the INDEXED kernels reach them through srow.
+// the same by blend groups, in place on the stamp store
 int dv_field_set_fit_flux_groups(dv_field_set* fs, int64_t n_expected, const double* data, const double* weight,
                                  const dv_fit_flux_params* params, double* fit_scale, double* fit_var, double* fit_gram,
                                  double* fit_proj, int32_t* fit_status, double* fit_chi2, int32_t* fit_npix, int32_t* fit_group,
                                  int32_t* fit_group_size) {
   const char* who = "dv_field_set_fit_flux_groups";
-  DV_TRY(field_set_live(fs, who));
-  if (!fs->keep) {
-    set_error("%s: the set keeps no stamps: dv_field_set_keep_stamps(set, 1) comes before the first measured pass", who);
-    return DV_E_STATE;
-  }
-  if (!params) {
-    set_error("%s: params must be given", who);
-    return DV_E_INVALID;
-  }
-  if (n_expected != (int64_t)fs->nrows) {
-    set_error("%s: %ld rows expected, the set holds %zu resident rows", who, (long)n_expected, fs->nrows);
-    return DV_E_INVALID;
-  }
-  dv_model* m = fs->m;
-  const int M = fs->M, F = fs->F, nb = fs->nb, cs = m->A.H;
-  const int64_t N = (int64_t)fs->nrows;
-  const bool weighted = weight != nullptr;
-  const FitFluxParams par{params->min_pivot, params->scratch_bytes};
-  DV_TRY(fitflux_check(who, cs, nb, F, par));
-  if (N > 0 && (!fit_scale || !fit_var || !fit_gram || !fit_proj || !fit_status)) {
-    set_error("%s: fit_scale, fit_var, fit_gram, fit_proj and fit_status must all be given", who);
-    return DV_E_INVALID;
-  }
-  if (weighted ? (N > 0 && (!fit_chi2 || !fit_npix)) : (fit_chi2 || fit_npix)) {
-    set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: both given with weight, both NULL without", who);
-    return DV_E_INVALID;
-  }
-  if (N > 0 && (!fit_group || !fit_group_size)) {
-    set_error("%s: fit_group and fit_group_size must all be given", who);
-    return DV_E_INVALID;
-  }
-  if (!data && fs->cumulative) {
-    set_error("%s: a cumulative set keeps no copy of the fields as uploaded (every pass subtracts from the working residual): "
-              "data must be given", who);
-    return DV_E_INVALID;
-  }
-  if (N == 0) return DV_OK;
-  // the joint order (7v): field by field, pass ascending inside a field, then the in-pass order
-  std::vector<int> rowmap((size_t)N), fptr32((size_t)M + 1), sfield_h((size_t)N);
-  std::vector<int32_t> places_h((size_t)N * 2);
-  size_t dense = 0;                                     // sum nb n_f^2: no sub-range needs more scratch than all groups at once
-  {
-    size_t d = 0;
-    for (int f = 0; f < M; ++f) {
-      fptr32[(size_t)f] = (int)d;
-      size_t base = 0;
-      for (const std::vector<int>& p : fs->pass_fptr) {
-        for (int i = p[(size_t)f]; i < p[(size_t)f + 1]; ++i) {
-          sfield_h[d] = f;
-          rowmap[d++] = (int)(base + (size_t)i);
-        }
-        base += (size_t)p[(size_t)M];
-      }
-      const size_t n = d - (size_t)fptr32[(size_t)f];
-      dense += (size_t)nb * n * n;
-    }
-    fptr32[(size_t)M] = (int)d;
-    if ((int64_t)d != N) {                              // (cannot happen: both count the passes that kept rows)
-      set_error("%s: the passes on record hold %zu rows, the set %zu", who, d, fs->nrows);
-      return DV_E_STATE;
-    }
-    for (size_t k = 0; k < (size_t)N; ++k) {
-      places_h[2 * k] = fs->places_h[2 * (size_t)rowmap[k]];
-      places_h[2 * k + 1] = fs->places_h[2 * (size_t)rowmap[k] + 1];
-    }
-  }
-  // host staging in joint order; the outputs leave in resident-row order through rowmap
-  const size_t nn = (size_t)N * nb, felems = (size_t)F * F * nb;
-  std::vector<double> h_scale(nn), h_var(nn), h_gram(nn), h_proj(nn), h_chi2(weighted ? nn : 0);
-  std::vector<int> h_status(nn), h_npix(weighted ? nn : 0);
-  std::vector<int32_t> h_group((size_t)N), h_gsize((size_t)N);
-  FitFluxRows stage{h_scale.data(), h_var.data(), h_gram.data(), h_proj.data(), h_status.data()};
-  if (weighted) stage.chi2 = h_chi2.data(), stage.npix = h_npix.data();
-  FitFluxRows d{};
-  Rows out;
-  fitflux_columns(out, d, stage, nb, weighted, false);
-  DV_HIP(hipSetDevice(m->ctx->device));
-  // what the call holds beside the set: the regrouped scalars, the group tables and lists (the lists at the two entries per row
-  // the stand-alone call counts; their true size is known behind the count kernel and allocated there), the scratch - at most
-  // scratch_bytes, and never more than every field dense -, the rows and the fields it uploads.  No second copy of the stamps.
-  const size_t scratch_b = std::min((size_t)par.scratch_bytes, dense * sizeof(double));
-  const size_t need = (size_t)N * (4 * sizeof(int) + FitGroupsWork::BYTES_PER_ROW + out.bytes()) + ((size_t)M + 1) * sizeof(int) +
-                      scratch_b + ((data ? 1 : 0) + (weighted ? 1 : 0)) * (size_t)M * felems * sizeof(double);
-  size_t free_b = 0, total_b = 0;
-  DV_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (need > free_b / 10 * 9) {
-    set_error("%s: the tables of %ld rows, the scratch of the groups and the uploaded fields need %zu bytes of device memory, %zu "
-              "are free", who, (long)N, need, free_b);
-    return DV_E_NOMEM;
-  }
-  hipStream_t s = m->ctx->stream;
-  DevBuf<int> places, sf, fptr, srow;
-  DevBuf<double> data_d, weight_d;
-  FitGroupsWork work;
-  DV_TRY(places.alloc((size_t)N * 2));
-  DV_TRY(sf.alloc((size_t)N));
-  DV_TRY(srow.alloc((size_t)N));
-  DV_TRY(fptr.alloc((size_t)M + 1));
-  DV_TRY(out.alloc(N));
-  StreamDrain drain(s);                                // a failure waits for the stream before the call's buffers go
-  if (data) {
-    DV_TRY(data_d.alloc((size_t)M * felems));
-    DV_HIP(hipMemcpyAsync(data_d, data, (size_t)M * felems * sizeof(double), hipMemcpyHostToDevice, s));
-  }
-  if (weighted) {
-    DV_TRY(weight_d.alloc((size_t)M * felems));
-    DV_HIP(hipMemcpyAsync(weight_d, weight, (size_t)M * felems * sizeof(double), hipMemcpyHostToDevice, s));
-  }
-  DV_HIP(hipMemcpyAsync(places, places_h.data(), (size_t)N * 2 * sizeof(int), hipMemcpyHostToDevice, s));
-  DV_HIP(hipMemcpyAsync(sf, sfield_h.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
-  DV_HIP(hipMemcpyAsync(srow, rowmap.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
-  DV_HIP(hipMemcpyAsync(fptr, fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-  const FieldStamps v{fs->rstamps, places, sf, fptr, data ? data_d.get() : fs->base.get(), weighted ? weight_d.get() : nullptr,
-                     nullptr, 0, cs, nb, F, srow};
-  DV_TRY(launch_fit_flux_groups(who, v, fptr32.data(), 0, M - 1, 0, par, work, d, h_group.data(), h_gsize.data(), nullptr, s));
-  DV_TRY(out.download(0, N, s));
-  DV_HIP(hipStreamSynchronize(s));
-  drain.dismiss();
-  // joint row k is resident row rowmap[k]
-  for (size_t k = 0; k < (size_t)N; ++k) {
-    const size_t r = (size_t)rowmap[k] * nb, o = k * nb;
-    for (int b = 0; b < nb; ++b) {
-      fit_scale[r + b] = h_scale[o + b];
-      fit_var[r + b] = h_var[o + b];
-      fit_gram[r + b] = h_gram[o + b];
-      fit_proj[r + b] = h_proj[o + b];
-      fit_status[r + b] = h_status[o + b];
-      if (weighted) fit_chi2[r + b] = h_chi2[o + b], fit_npix[r + b] = h_npix[o + b];
-    }
-    fit_group[rowmap[k]] = h_group[k];
-    fit_group_size[rowmap[k]] = h_gsize[k];
-  }
-  return DV_OK;
+  DV_TRY(field_set_fit_ready(fs, who, params, n_expected));
+  FitFluxOut rq{FitFluxParams{params->min_pivot, params->scratch_bytes},
+                FitFluxRows{fit_scale, fit_var, fit_gram, fit_proj, fit_status, fit_chi2, fit_npix}, weight};
+  rq.group = fit_group;
+  rq.group_size = fit_group_size;
+  rq.by_groups = true;                                  // (group rows that are missing are refused by name, in their turn)
+  rq.who = who;
+  return field_set_fit_flux(field_set_resident(fs), data, rq, fs->m->ctx->device, fs->m->ctx->stream);
 }
 
 int dv_field_set_read(dv_field_set* fs, int32_t which, double* out) {

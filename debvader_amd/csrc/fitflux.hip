@@ -1772,6 +1772,153 @@ int scene_fit_flux_groups(const float* stamps_h, const int32_t* places_h, const 
   });
 }
 
+namespace {
+// the refusals of a resident set's call for its outputs: every output the chosen variant produces, and no other
+int field_set_outputs_check(const char* who, const FitFluxOut& rq, int64_t N) {
+  const FitFluxRows& o = rq.rows;
+  const FitFluxSky& sky = rq.sky;
+  const FitFluxNonneg& nn = rq.nonneg;
+  if (nn.on && nn.max_iter < 1) {
+    set_error("%s: max_iter must be at least 1 (got %d)", who, nn.max_iter);
+    return E_INVALID;
+  }
+  if (N > 0 && (!o.scale || !o.var || !o.gram || !o.proj || !o.status)) {
+    set_error("%s: fit_scale, fit_var, fit_gram, fit_proj and fit_status must all be given", who);
+    return E_INVALID;
+  }
+  if (rq.weights ? (N > 0 && (!o.chi2 || !o.npix)) : (o.chi2 || o.npix)) {
+    set_error("%s: fit_chi2 and fit_npix are the outputs of the weighted fit: both given with weight, both NULL without", who);
+    return E_INVALID;
+  }
+  if (rq.sky_order >= 0 ? (!sky.coef || !sky.cov || !sky.status || !sky.npix) : (sky.coef || sky.cov || sky.status || sky.npix)) {
+    set_error("%s: sky_coef, sky_cov, sky_status and sky_npix are the outputs of the fit with sky: all given with sky_order 0 or "
+              "1, all NULL with -1", who);
+    return E_INVALID;
+  }
+  if (nn.on ? (!nn.iters || !nn.status || (N > 0 && (!o.scale_free || !o.clamped || !o.dual)))
+            : (o.scale_free || o.clamped || o.dual || nn.iters || nn.status)) {
+    set_error("%s: fit_scale_free, fit_clamped, fit_dual, nonneg_iters and nonneg_status are the outputs of the non-negative fit: "
+              "all given with nonneg, all NULL without", who);
+    return E_INVALID;
+  }
+  if (rq.grouped() && N > 0 && (!rq.group || !rq.group_size)) {
+    set_error("%s: fit_group and fit_group_size must all be given", who);
+    return E_INVALID;
+  }
+  return OK;
+}
+}  // namespace
+
+// The rows go through the kernels in joint order (joint_order, rows.h) and leave in resident-row order: they are downloaded into
+// host staging and scattered through rowmap.  Dense: the stamps, placements and fields are regrouped into a copy on the device
+// and launch_fit_flux runs on the copy.  Grouped: only the per-row scalars - placement, field and srow = rowmap - are uploaded in
+// joint order, and launch_fit_flux_groups reads the stamps in place through srow.
+int field_set_fit_flux(const ResidentRows& set, const double* data_h, const FitFluxOut& rq, int device, hipStream_t s) {
+  const char* who = rq.who;
+  const int M = set.M, F = set.F, nb = set.nb, cs = set.cs;
+  const int64_t N = (int64_t)set.nrows;
+  const bool weighted = rq.weights != nullptr, grouped = rq.grouped();
+  DV_TRY(fitflux_check(who, cs, nb, F, rq.par));
+  DV_TRY(field_set_outputs_check(who, rq, N));
+  if (!data_h && !set.base) {
+    set_error("%s: a cumulative set keeps no copy of the fields as uploaded (every pass subtracts from the working residual): "
+              "data must be given", who);
+    return E_INVALID;
+  }
+  const JointOrder jo = joint_order(set.pass_fptr, M);
+  if (jo.fptr64[(size_t)M] != N) {                      // (cannot happen: both count the passes that kept rows)
+    set_error("%s: the passes on record hold %ld rows, the set %zu", who, (long)jo.fptr64[(size_t)M], set.nrows);
+    return E_STATE;
+  }
+  FitFluxPlan plan;
+  if (!grouped) DV_TRY(fitflux_plan(who, jo.fptr64.data(), M, nb, rq.par, &plan, rq.sky_order, F));
+  if (N == 0) return OK;
+  const std::vector<int32_t> places_h = jo.places(set.places_h);
+  const int q = plan.q;
+  const size_t stamp = (size_t)cs * cs * nb, felems = (size_t)F * F * nb;
+  FitFluxRows d{};
+  Rows out;
+  fitflux_columns(out, d, rq.rows, nb, weighted, rq.nonneg.on);
+  RowStage stage;
+  stage.take(out, N);
+  int32_t* const group_j = grouped ? (int32_t*)stage.add(rq.group, sizeof(int32_t), N) : nullptr;
+  int32_t* const gsize_j = grouped ? (int32_t*)stage.add(rq.group_size, sizeof(int32_t), N) : nullptr;
+  DV_HIP(hipSetDevice(device));
+  // what the call holds beside the set: the tables in joint order, the rows, the fields it uploads, and - dense - the regrouped
+  // copy, the dense scratch and the per-field outputs, or - grouped - the group tables and lists (the lists at the two entries
+  // per row the stand-alone call counts; their true size is known behind the count kernel and allocated there) and the scratch:
+  // at most scratch_bytes, and never more than every field dense, which no sub-range exceeds.  No second copy of the stamps.
+  const size_t fields_b = ((data_h ? 1 : 0) + (weighted ? 1 : 0)) * (size_t)M * felems * sizeof(double);
+  size_t need = 0;
+  if (grouped) {
+    size_t dense = 0;                                   // sum nb n_f^2
+    for (int f = 0; f < M; ++f) {
+      const size_t n = (size_t)(jo.fptr64[(size_t)f + 1] - jo.fptr64[(size_t)f]);
+      dense += (size_t)nb * n * n;
+    }
+    const size_t scratch_b = std::min((size_t)rq.par.scratch_bytes, dense * sizeof(double));
+    need = (size_t)N * (4 * sizeof(int) + FitGroupsWork::BYTES_PER_ROW + out.bytes()) + ((size_t)M + 1) * sizeof(int) + scratch_b +
+           fields_b;
+  } else {
+    need = (size_t)N * (stamp * sizeof(float) + 4 * sizeof(int) + out.bytes()) + ((size_t)M + 1) * sizeof(int) +
+           FitFluxWork::bytes(plan, (size_t)M, weighted) + FitFluxFieldOut::bytes(q, rq.nonneg.on, (size_t)M, nb) + fields_b;
+  }
+  size_t free_b = 0, total_b = 0;
+  DV_HIP(hipMemGetInfo(&free_b, &total_b));
+  if (need > free_b / 10 * 9) {
+    if (grouped)
+      set_error("%s: the tables of %ld rows, the scratch of the groups and the uploaded fields need %zu bytes of device memory, %zu "
+                "are free", who, (long)N, need, free_b);
+    else
+      set_error("%s: the regrouped stamps of %ld rows, the dense scratch and the uploaded fields need %zu bytes of device memory, "
+                "%zu are free", who, (long)N, need, free_b);
+    return E_NOMEM;
+  }
+  DevBuf<float> stamps;
+  DevBuf<int> places, sf, rmap, fptr;
+  const double* const field_h[2] = {data_h, rq.weights};
+  DevBuf<double> field_d[2];
+  FitFluxWork work;
+  FitFluxFieldOut fout;
+  FitGroupsWork gwork;
+  if (!grouped) DV_TRY(stamps.alloc((size_t)N * stamp));
+  DV_TRY(places.alloc((size_t)N * 2));
+  DV_TRY(sf.alloc((size_t)N));
+  DV_TRY(rmap.alloc((size_t)N));
+  DV_TRY(fptr.alloc((size_t)M + 1));
+  if (!grouped) DV_TRY(work.alloc(plan, M, weighted));
+  DV_TRY(out.alloc(N));
+  if (!grouped) DV_TRY(fout.alloc(q, rq.nonneg, (size_t)M, nb));
+  StreamDrain drain(s);                                // a failure waits for the stream before the call's buffers go
+  for (int k = 0; k < 2; ++k)
+    if (field_h[k]) {
+      DV_TRY(field_d[k].alloc((size_t)M * felems));
+      DV_HIP(hipMemcpyAsync(field_d[k], field_h[k], (size_t)M * felems * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+  FieldStamps v{set.stamps, places, sf, fptr, data_h ? field_d[0].get() : set.base, field_d[1].get(), nullptr, 0, cs, nb, F};
+  if (grouped) {
+    DV_HIP(hipMemcpyAsync(places, places_h.data(), (size_t)N * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(sf, jo.sfield.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  DV_HIP(hipMemcpyAsync(rmap, jo.rowmap.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+  DV_HIP(hipMemcpyAsync(fptr, jo.fptr32.data(), ((size_t)M + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  if (grouped) {
+    v.srow = rmap;
+    DV_TRY(launch_fit_flux_groups(who, v, jo.fptr32.data(), 0, M - 1, 0, rq.par, gwork, d, group_j, gsize_j, nullptr, s));
+    DV_TRY(out.download(0, N, s));
+  } else {
+    DV_TRY(launch_fitflux_regroup(rmap, set.stamps, set.places, set.field, N, cs, nb, stamps, places, sf, s));
+    v.stamps = stamps;
+    DV_TRY(launch_fit_flux(v, places_h.data(), jo.fptr32.data(), 0, M - 1, rq.par, work, d, fout.sky, fout.nonneg, true, s));
+    DV_TRY(out.download(0, N, s));
+    DV_TRY(fout.download(rq.sky, rq.nonneg, 0, 0, (size_t)M, nb, s));
+  }
+  DV_HIP(hipStreamSynchronize(s));
+  drain.dismiss();
+  stage.scatter(jo.rowmap.data(), N);                  // joint row k is resident row rowmap[k]
+  return OK;
+}
+
 
 // the blend groups alone, from the placements: no stamps, no fit, no limit on a group.  n_pairs / n_adj are always written;
 // pairs [n_pairs][2], adj_ptr [N + 1] and adj [n_adj] - the lists the fit works from, rows of the call - where they are given

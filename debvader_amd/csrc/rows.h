@@ -40,6 +40,18 @@ struct Rows {
   int download(int64_t r, int64_t n, hipStream_t s) const;   // device rows [0, n) to host rows [r, r + n)
 };
 
+// Host staging for rows that are computed in another order than the caller's: take() gives every column of r that has a host
+// array n staged rows and makes them the column's host, add() stages a host-only column and returns its rows;
+// scatter() copies staged row k to row rowmap[k] of every caller's array.
+struct RowStage {
+  struct Col { char* dest; size_t width; std::vector<char> rows; };
+  Col cols[Rows::MAX_COLS];
+  int ncols = 0;
+  void* add(void* dest, size_t width, int64_t n);
+  void take(Rows& r, int64_t n);
+  void scatter(const int* rowmap, int64_t n) const;
+};
+
 // The columns of the row sets, each stated once, in the file of its kernels: `dev` is where the device pointers are
 // kept (alloc() sets them; a caller with rows of its own sets them itself), `host` the caller's arrays - all null for rows
 // that stay on the device.  The scratch rows of a Monte-Carlo pass (`reps` rows per galaxy) are never copied.
@@ -97,6 +109,18 @@ struct FieldRuns {
 };
 int plan_field_runs(const int64_t* field_ptr, int M, size_t row_bytes, size_t field_bytes, size_t budget, int64_t max_stamps,
                     int64_t max_fields, FieldRuns* runs, size_t* need);
+
+// The joint order of the rows of a resident field set (no HIP call).  The set holds its rows pass after pass;
+// pass_fptr[p][f] is the first row of field f counted from row 0 of kept pass p, pass_fptr[p][M] the rows of the pass.  The
+// joint order goes field by field, pass ascending inside a field, then the in-pass order: joint row k is resident row
+// rowmap[k] and lies in field sfield[k]; fptr32 / fptr64 [M + 1] are the joint field_ptr.  This is what fit_group indexes and
+// what decides which copy of a twin stamp is dropped.  places(): the resident placements [.][2] gathered into joint order.
+struct JointOrder {
+  std::vector<int> rowmap, sfield, fptr32;
+  std::vector<int64_t> fptr64;
+  std::vector<int32_t> places(const int32_t* resident) const;
+};
+JointOrder joint_order(const std::vector<std::vector<int>>& pass_fptr, int M);
 
 // The host side of a call that reads the stamps of complete fields against the fields (flux fit, moments on the fields): the
 // field stacks [M][F][F][nb], any of them null; the bytes the caller allocates beside the walker's - per row, per field, and

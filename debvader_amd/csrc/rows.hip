@@ -2,6 +2,7 @@
 #include "rows.h"
 
 #include <algorithm>
+#include <cstring>
 #include <new>
 
 #ifdef DV_DEBUG_EXPORTS
@@ -49,6 +50,25 @@ int Rows::download(int64_t r, int64_t n, hipStream_t s) const {
     if (c.host && n > 0) DV_HIP(hipMemcpyAsync(c.host + (size_t)r * c.width, *c.dev, (size_t)n * c.width, hipMemcpyDeviceToHost, s));
   }
   return OK;
+}
+
+void* RowStage::add(void* dest, size_t width, int64_t n) {
+  Col& c = cols[ncols++];
+  c.dest = (char*)dest;
+  c.width = width;
+  c.rows.assign((size_t)n * width, 0);
+  return c.rows.data();
+}
+
+void RowStage::take(Rows& r, int64_t n) {
+  for (int i = 0; i < r.ncols; ++i)
+    if (r.cols[i].host) r.cols[i].host = (char*)add(r.cols[i].host, r.cols[i].width, n);
+}
+
+void RowStage::scatter(const int* rowmap, int64_t n) const {
+  for (int i = 0; i < ncols; ++i)
+    for (int64_t k = 0; k < n; ++k)
+      std::memcpy(cols[i].dest + (size_t)rowmap[k] * cols[i].width, cols[i].rows.data() + (size_t)k * cols[i].width, cols[i].width);
 }
 
 int place_check(const char* who, int64_t i, const int32_t* places) {
@@ -190,6 +210,33 @@ int plan_field_runs(const int64_t* field_ptr, int M, size_t row_bytes, size_t fi
   runs->max_rows = cmax_s;
   runs->max_fields = cmax_f;
   return -1;
+}
+
+JointOrder joint_order(const std::vector<std::vector<int>>& pass_fptr, int M) {
+  JointOrder o;
+  for (int f = 0; f < M; ++f) {
+    o.fptr64.push_back((int64_t)o.rowmap.size());
+    size_t base = 0;                                   // the resident row of the pass's row 0
+    for (const std::vector<int>& p : pass_fptr) {
+      for (int i = p[(size_t)f]; i < p[(size_t)f + 1]; ++i) {
+        o.rowmap.push_back((int)(base + (size_t)i));
+        o.sfield.push_back(f);
+      }
+      base += (size_t)p[(size_t)M];
+    }
+  }
+  o.fptr64.push_back((int64_t)o.rowmap.size());
+  o.fptr32.assign(o.fptr64.begin(), o.fptr64.end());
+  return o;
+}
+
+std::vector<int32_t> JointOrder::places(const int32_t* resident) const {
+  std::vector<int32_t> p(rowmap.size() * 2);
+  for (size_t k = 0; k < rowmap.size(); ++k) {
+    p[2 * k] = resident[2 * (size_t)rowmap[k]];
+    p[2 * k + 1] = resident[2 * (size_t)rowmap[k] + 1];
+  }
+  return p;
 }
 
 int walk_whole_fields(const char* who, int M, const int64_t* field_ptr, int64_t N, WholeFields& f, FieldStamps& v, Rows& in,

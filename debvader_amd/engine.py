@@ -2333,6 +2333,22 @@ class FieldSet:
         the first such pass (DvError, DV_E_STATE, afterwards)."""
         check(lib.dv_field_set_keep_stamps(self._handle(), int(bool(on))))
 
+    def _fit_flux_args(self, data_fields, weight_fields):
+        """What fit_flux() and fit_flux_groups() share: the checked float64 data and weight fields (None where not given) and
+        the per-row result dictionary with its pointers in the C-ABI's order, fit_chi2 / fit_npix NULL without weights."""
+        data = None
+        if data_fields is not None:
+            data = np.ascontiguousarray(data_fields, dtype=np.float64)
+            if data.shape != tuple(self.shape):
+                raise ValueError(f"expected data fields of the shape of the set's fields {tuple(self.shape)}, got {data.shape}")
+        elif self.cumulative:
+            raise ValueError("a cumulative set keeps no copy of the fields as uploaded: give data_fields")
+        weights = None if weight_fields is None else check_fit_weights(weight_fields, self.shape)
+        out, ptrs = _fit_flux_out(self._rows, self.shape[3], weights is not None)
+        if weights is None:
+            ptrs += [None, None]
+        return data, weights, out, ptrs
+
     def fit_flux(self, data_fields=None, weight_fields=None, sky_order=None, nonneg=False, min_pivot: float = 1e-8,
                  max_iter: int = 100, scratch_bytes: int = 256 << 20) -> Dict[str, np.ndarray]:
         """The joint flux fit of the stamps of ALL deblend_pass_measure(blend=True) calls since keep_stamps(), one linear system
@@ -2347,22 +2363,12 @@ class FieldSet:
         without resident rows fits nothing, no sky either: the per-field arrays come back as zeros."""
         h = self._handle()
         M, F, _, nb = self.shape
-        data = None
-        if data_fields is not None:
-            data = np.ascontiguousarray(data_fields, dtype=np.float64)
-            if data.shape != tuple(self.shape):
-                raise ValueError(f"expected data fields of the shape of the set's fields {tuple(self.shape)}, got {data.shape}")
-        elif self.cumulative:
-            raise ValueError("a cumulative set keeps no copy of the fields as uploaded: give data_fields")
-        weights = None if weight_fields is None else check_fit_weights(weight_fields, self.shape)
+        data, weights, out, ptrs = self._fit_flux_args(data_fields, weight_fields)
         sky, order, sky_ptrs = _fit_sky_args(sky_order, M, nb)
         par = fit_flux_params(min_pivot, scratch_bytes)
         nonneg = bool(nonneg)
         max_iter = nonneg_max_iter(max_iter) if nonneg else 1
         n = self._rows
-        out, ptrs = _fit_flux_out(n, nb, weights is not None)
-        if weights is None:
-            ptrs += [None, None]
         out.update(sky)
         nn_ptrs = [None] * 5
         if nonneg:
@@ -2384,20 +2390,9 @@ class FieldSet:
         pass after pass -, "fit_group_size" the members of that group.  The bits are those of scene_fit_flux_groups on the same
         stamps regrouped field by field, and of fit_flux() wherever that call takes the field."""
         h = self._handle()
-        nb = self.shape[3]
-        data = None
-        if data_fields is not None:
-            data = np.ascontiguousarray(data_fields, dtype=np.float64)
-            if data.shape != tuple(self.shape):
-                raise ValueError(f"expected data fields of the shape of the set's fields {tuple(self.shape)}, got {data.shape}")
-        elif self.cumulative:
-            raise ValueError("a cumulative set keeps no copy of the fields as uploaded: give data_fields")
-        weights = None if weight_fields is None else check_fit_weights(weight_fields, self.shape)
+        data, weights, out, ptrs = self._fit_flux_args(data_fields, weight_fields)
         par = fit_flux_params(min_pivot, scratch_bytes)
         n = self._rows
-        out, ptrs = _fit_flux_out(n, nb, weights is not None)
-        if weights is None:
-            ptrs += [None, None]
         out["fit_group"], out["fit_group_size"] = np.zeros(n, np.int32), np.zeros(n, np.int32)
         check(lib.dv_field_set_fit_flux_groups(h, n, None if data is None else _dp(data), None if weights is None else _dp(weights),
                                                C.byref(par), *ptrs, _ip(out["fit_group"]), _ip(out["fit_group_size"])))
