@@ -45,6 +45,15 @@ class DvDetectParams(C.Structure):
     ]
 
 
+class DvDetectWeights(C.Structure):
+    """dv_detect_weights (include/debvader_hip.h)"""
+    _fields_ = [("weights", C.POINTER(C.c_double)), ("noise", C.c_int32), ("filter", C.c_int32)]
+
+
+DETECT_NOISE = {"absolute": 0, "relative": 1}     # DV_DETECT_NOISE_*
+DETECT_FILTER = {"conv": 0, "matched": 1}         # DV_DETECT_FILTER_*
+
+
 class DvMeasureParams(C.Structure):
     """dv_measure_params (include/debvader_hip.h)"""
     _fields_ = [("band", C.c_int32), ("sigma0", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int32)]
@@ -180,6 +189,9 @@ SIGNATURES = {
                                              C.c_int32, _d, _d, _i32, _i32]),
     "dv_scene_detect": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams), C.c_int64, _i64,
                                   _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d, _d, _d, _d, _i32]),
+    "dv_scene_detect_weighted": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams), C.c_int64, _i64,
+                                           _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d, _d, _d, _d, _i32,
+                                           C.POINTER(DvDetectWeights), _i32]),
     "dv_measure_params_default": (C.c_int, [C.POINTER(DvMeasureParams)]),
     "dv_scene_measure": (C.c_int, [_p, _f, _f, C.c_int64, C.c_int32, C.c_int32, C.POINTER(DvMeasureParams), _d, _d, _d, _i32,
                                    _i32]),
@@ -229,6 +241,7 @@ SIGNATURES = {
     "dv_field_set_open":(C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_p)]),
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),
+    "dv_field_set_detect_weights": (C.c_int, [_p, _d, C.c_int32, C.c_int32]),
     "dv_field_set_pass": (C.c_int, [_p, _i32, _i32, _i64, C.c_int64, C.c_uint64, _d, _d]),
     "dv_field_set_read": (C.c_int, [_p, C.c_int32, _d]),
     "dv_field_set_close": (C.c_int, [_p]),

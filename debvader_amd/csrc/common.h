@@ -627,24 +627,33 @@ int scene_fit_groups(const int32_t* places_h, const int64_t* field_ptr, int64_t 
 // [n + q][nb] to the host, the bits the solve starts from
 int scene_fit_flux_sky_gram(const float* stamps_h, const int32_t* places_h, int64_t n, int cs, int nb, const double* data_h,
                             const double* weight_h, int F, int sky_order, double* gram_h, double* rhs_h, int device, hipStream_t s);
+// the weighted rules of DESIGN 7z: the planes [M][H][W] of a host call (a device source carries its own in DetectDevSrc),
+// noise 0 absolute / 1 relative, filter 0 conv / 1 matched, bad_meshes_h [M] nullable
+struct DetectWeights {
+  const double* weights_h;
+  int noise, filter;
+  int32_t* bad_meshes_h;
+};
 // batched source detection on one band (detect.hip): host float64 fields in, host catalog out
 int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
                  int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
                  int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s);
+                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s,
+                 const DetectWeights* wq = nullptr);
 // the same detector on one band of fields that lie in device memory (dv_field_set_detect): field i of the call is band
 // `band` of the [H][W][nb] field number which_h[i] of the stack fields_dev, gathered into the detector's planes on the GPU
 struct DetectDevSrc {
   const double* fields_dev;
   int nb, band;
   const int32_t* which_h;
+  const double* weights_dev = nullptr;   // (7z) planes [..][H][W] in the stack's numbering, read with a DetectWeights
 };
 int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                      int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
                      int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
                      int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                     hipStream_t s);
+                     hipStream_t s, const DetectWeights* wq = nullptr);
 
 // Strip form of the stride-1 3x3 gather-GEMM for the 32-channel high-resolution layers (gconv_strip.hip)
 struct GStripParams {

@@ -21,6 +21,9 @@
 //                        run the same code on global scratch.
 // The catalog is sized in two phases: the component table comes back to the host, which places every component's
 // scratch and catalog slots (an object holds >= minarea core pixels, so a component has at most n / minarea of them).
+// With a per-pixel noise map and a mask (tests/detect_weighted_oracle.py) kernels 1, 2, 4 and 5 run
+// in their WEIGHTED instantiations: only counting pixels (0 < w < inf) enter the meshes, bad meshes are filled from their
+// nearest good ones, v is 0 under the mask and D holds the significance S; kernels 6 to 8 read S where they read D.
 // fp64 VALU and integer work; nothing here has a matrix shape for MFMA.
 #include "common.h"
 
@@ -121,10 +124,18 @@ __device__ __forceinline__ double median_sorted(const double* s, int n) {
   return (n & 1) ? s[n / 2] : 0.5 * (s[n / 2 - 1] + s[n / 2]);
 }
 
-__global__ __launch_bounds__(DT) void bkg_mesh_kernel(const double* __restrict__ data, int H, int W, int bs, int ny,
-                                                      int nx, double* __restrict__ mback, double* __restrict__ mrms) {
+// a pixel counts iff 0 < w < inf (a comparison: NaN does not count), DESIGN 7z
+__device__ __forceinline__ bool counts(double w) { return w > 0.0 && w < INFINITY; }
+
+// WEIGHTED (7z): only the counting pixels of wt enter the clipping, a mesh with fewer than half of its pixels counting is
+// marked bad with NaN
+template <bool WEIGHTED>
+__global__ __launch_bounds__(DT) void bkg_mesh_kernel(const double* __restrict__ data, const double* __restrict__ wt, int H,
+                                                      int W, int bs, int ny, int nx, double* __restrict__ mback,
+                                                      double* __restrict__ mrms) {
   __shared__ double s[MESH_MAX];
   __shared__ double s_red[4];
+  __shared__ int s_w[4];
   const int tid = threadIdx.x;
   const long mesh = blockIdx.x;
   const int per = ny * nx;
@@ -132,11 +143,36 @@ __global__ __launch_bounds__(DT) void bkg_mesh_kernel(const double* __restrict__
   const int mi = (int)(mesh - f * per), i = mi / nx, j = mi - (mi / nx) * nx;
   const int r0 = i * bs, c0 = j * bs;
   const int bh = min(bs, H - r0), bw = min(bs, W - c0);
-  const int n = bh * bw;
+  const int nall = bh * bw;
   int N = 1;
-  while (N < n) N <<= 1;
+  while (N < nall) N <<= 1;
   const double* src = data + f * (long)H * W;
-  for (int e = tid; e < N; e += DT) s[e] = e < n ? src[(long)(r0 + e / bw) * W + c0 + e % bw] : INFINITY;
+  int n = nall;
+  if constexpr (WEIGHTED) {
+    // a pixel that does not count sorts behind every value: the first n sorted values are the counting ones
+    const double* wsrc = wt + f * (long)H * W;
+    int mine = 0;
+    for (int e = tid; e < N; e += DT) {
+      bool on = false;
+      long at = 0;
+      if (e < nall) {
+        at = (long)(r0 + e / bw) * W + c0 + e % bw;
+        on = counts(wsrc[at]);
+      }
+      s[e] = on ? src[at] : INFINITY;
+      mine += on;
+    }
+    n = blk_isum(mine, s_w);
+    if (2 * n < nall) {                            // a bad mesh (the same for every thread): bkg_grid_kernel fills it
+      if (tid == 0) {
+        mback[mesh] = NAN;
+        mrms[mesh] = NAN;
+      }
+      return;
+    }
+  } else {
+    for (int e = tid; e < N; e += DT) s[e] = e < nall ? src[(long)(r0 + e / bw) * W + c0 + e % bw] : INFINITY;
+  }
   __syncthreads();
   for (int k = 2; k <= N; k <<= 1) {            // bitonic sort, ascending
     for (int jj = k >> 1; jj > 0; jj >>= 1) {
@@ -209,19 +245,57 @@ __device__ __forceinline__ double spline_eval(const double* y, const double* m, 
          (t * t * t - t) * m[(k + 1) * st] / 6.0;
 }
 
-// per field: median-filtered mesh grids (fb, fr), globalrms, second derivatives along the mesh rows (d2b, d2r)
+// per field: median-filtered mesh grids (fb, fr), globalrms, second derivatives along the mesh rows (d2b, d2r).
+// WEIGHTED (7z): before the median filter a bad mesh (NaN) takes, for background and rms separately, the mean of the good
+// meshes of its field at the smallest squared distance, the tied ones added in raster order; the filled grids stand in d2b /
+// d2r until the splines overwrite them.  nbad = the field's bad meshes; a field without a good mesh keeps NaN everywhere.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(DT) void bkg_grid_kernel(const double* __restrict__ mback, const double* __restrict__ mrms,
                                                       int ny, int nx, int fs, const double* __restrict__ cco,
                                                       double* fb, double* fr, double* d2b, double* d2r,
-                                                      double* __restrict__ grms) {
+                                                      double* __restrict__ grms, int* __restrict__ nbad) {
   __shared__ double s_red[4];
+  __shared__ int s_w[4];
   const int tid = threadIdx.x;
   const int per = ny * nx;
   const long base = (long)blockIdx.x * per;
   const int h = fs / 2;
+  if constexpr (WEIGHTED) {
+    int bad = 0;
+    for (int mi = tid; mi < per; mi += DT) {
+      double b = mback[base + mi], r = mrms[base + mi];
+      if (b != b) {
+        ++bad;
+        const int i = mi / nx, j = mi - (mi / nx) * nx;
+        long best = -1;
+        for (int q = 0; q < per; ++q) {
+          if (mback[base + q] != mback[base + q]) continue;
+          const long di = q / nx - i, dj = q - (q / nx) * nx - j, d = di * di + dj * dj;
+          if (best < 0 || d < best) best = d;
+        }
+        double sb = 0.0, sr = 0.0;
+        int cnt = 0;
+        for (int q = 0; q < per && best >= 0; ++q) {
+          if (mback[base + q] != mback[base + q]) continue;
+          const long di = q / nx - i, dj = q - (q / nx) * nx - j;
+          if (di * di + dj * dj != best) continue;
+          sb += mback[base + q];
+          sr += mrms[base + q];
+          ++cnt;
+        }
+        b = best >= 0 ? sb / cnt : NAN;
+        r = best >= 0 ? sr / cnt : NAN;
+      }
+      d2b[base + mi] = b;
+      d2r[base + mi] = r;
+    }
+    bad = blk_isum(bad, s_w);
+    if (tid == 0) nbad[blockIdx.x] = bad;
+    __syncthreads();
+  }
   for (int e = tid; e < 2 * per; e += DT) {
     const int which = e / per, mi = e - which * per, i = mi / nx, j = mi - (mi / nx) * nx;
-    const double* g = (which ? mrms : mback) + base;
+    const double* g = (WEIGHTED ? (which ? d2r : d2b) : (which ? mrms : mback)) + base;
     double w[MF_MAX * MF_MAX];
     int n = 0;
     for (int a = max(0, i - h); a <= min(ny - 1, i + h); ++a)
@@ -266,7 +340,10 @@ __global__ __launch_bounds__(DT) void bkg_row_kernel(const double* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(DT) void bkg_pixel_kernel(const double* __restrict__ data, long total, int W, int nx,
+// WEIGHTED (7z): v = 0 where the pixel does not count (a select: the value under the mask reaches nothing)
+template <bool WEIGHTED>
+__global__ __launch_bounds__(DT) void bkg_pixel_kernel(const double* __restrict__ data, const double* __restrict__ wt,
+                                                       long total, int W, int nx,
                                                        int bs, const double* __restrict__ gb, const double* __restrict__ gb2,
                                                        const double* __restrict__ gr, const double* __restrict__ gr2,
                                                        double* __restrict__ v, double* __restrict__ back,
@@ -277,17 +354,24 @@ __global__ __launch_bounds__(DT) void bkg_pixel_kernel(const double* __restrict_
   const int c = (int)(e - row * W);
   const double u = (c + 0.5) / bs - 0.5;
   const double b = spline_eval(gb + row * nx, gb2 + row * nx, 1, nx, u);
-  v[e] = data[e] - b;
+  if constexpr (WEIGHTED) v[e] = counts(wt[e]) ? data[e] - b : 0.0;
+  else v[e] = data[e] - b;
   if (back) back[e] = b;
   if (rms) rms[e] = spline_eval(gr + row * nx, gr2 + row * nx, 1, nx, u);
 }
 
-// D = correlation of v with kn (normalised taps), zero outside the field; par = own index where D > thresh * globalrms
-__global__ __launch_bounds__(DT) void filter_kernel(const double* __restrict__ v, int H, int W,
+// D = correlation of v with kn (normalised taps), zero outside the field; par = own index where D > T, T = thresh * globalrms
+// or (absolute) thresh.  WEIGHTED (7z): D holds the significance S.  A second tile holds w, zero where the pixel does not
+// count and outside the field; conv: S = (sum kn v) sqrt(w); MATCHED: the first tile holds v w and
+// S = (sum kn (v w)) / sqrt(sum (kn kn) w), -inf where the denominator is 0; S = -inf at a pixel that does not count, and
+// nothing is above the threshold in a field without a good mesh (globalrms NaN).
+template <bool WEIGHTED, bool MATCHED>
+__global__ __launch_bounds__(DT) void filter_kernel(const double* __restrict__ v, const double* __restrict__ wt, int H, int W,
                                                     const double* __restrict__ kn, int kh, int kw,
-                                                    const double* __restrict__ grms, double thresh,
+                                                    const double* __restrict__ grms, double thresh, int absolute,
                                                     double* __restrict__ D, int* __restrict__ par) {
   __shared__ double t[(FT + KMAX - 1) * (FT + KMAX - 1)];
+  __shared__ double tw[WEIGHTED ? (FT + KMAX - 1) * (FT + KMAX - 1) : 1];
   const int tid = threadIdx.x;
   const long f = blockIdx.z;
   const int r0 = blockIdx.y * FT, c0 = blockIdx.x * FT, ry = kh / 2, rx = kw / 2;
@@ -295,17 +379,40 @@ __global__ __launch_bounds__(DT) void filter_kernel(const double* __restrict__ v
   const long fb = f * (long)H * W;
   for (int e = tid; e < TH * TW; e += DT) {
     const int a = e / TW, b = e - (e / TW) * TW, r = r0 - ry + a, c = c0 - rx + b;
-    t[e] = (r >= 0 && r < H && c >= 0 && c < W) ? v[fb + (long)r * W + c] : 0.0;
+    const bool in = r >= 0 && r < H && c >= 0 && c < W;
+    if constexpr (WEIGHTED) {
+      const double w = in ? wt[fb + (long)r * W + c] : 0.0;
+      const bool on = counts(w);
+      const double x = on ? v[fb + (long)r * W + c] : 0.0;
+      tw[e] = on ? w : 0.0;
+      t[e] = MATCHED ? (on ? x * w : 0.0) : x;
+    } else {
+      t[e] = in ? v[fb + (long)r * W + c] : 0.0;
+    }
   }
   __syncthreads();
   const int ty = tid / FT, tx = tid % FT, r = r0 + ty, c = c0 + tx;
   if (r >= H || c >= W) return;
-  double acc = 0.0;
+  double acc = 0.0, den = 0.0;
   for (int a = 0; a < kh; ++a)
-    for (int b = 0; b < kw; ++b) acc += kn[a * kw + b] * t[(ty + a) * TW + tx + b];
+    for (int b = 0; b < kw; ++b) {
+      const double k = kn[a * kw + b];
+      acc += k * t[(ty + a) * TW + tx + b];
+      if constexpr (WEIGHTED && MATCHED) den += (k * k) * tw[(ty + a) * TW + tx + b];
+    }
   const long o = fb + (long)r * W + c;
-  D[o] = acc;
-  par[o] = acc > thresh * grms[f] ? r * W + c : -1;
+  if constexpr (WEIGHTED) {
+    const double wc = tw[(ty + ry) * TW + tx + rx];
+    if (MATCHED) acc = (wc > 0.0 && den > 0.0) ? acc / sqrt(den) : -INFINITY;
+    else acc = wc > 0.0 ? acc * sqrt(wc) : -INFINITY;
+    const double g = grms[f];
+    const double T = absolute ? thresh : thresh * g;
+    D[o] = acc;
+    par[o] = (g == g && acc > T) ? r * W + c : -1;
+  } else {
+    D[o] = acc;
+    par[o] = acc > thresh * grms[f] ? r * W + c : -1;
+  }
 }
 
 // ---- connected components ---------------------------------------------------------------------------------------
@@ -733,10 +840,11 @@ inline unsigned nblk(long total) { return (unsigned)((total + DT - 1) / DT); }
 
 // device bytes one H x W field can need in a launch: deblend scratch and catalog slots sized as if every pixel lay in
 // a component
-long field_bytes(long H, long W, long ny, long nx, int minarea, bool maps) {
+long field_bytes(long H, long W, long ny, long nx, int minarea, bool maps, bool weighted) {
   const long HW = H * W, capn = HW / minarea + 1;
   long b = HW * (8 + 8 + 8 + 4 * 7);                          // data v D | par lab area cmin cmax rmax lidx
   if (maps) b += HW * (8 + 8 + 4);                            // back rms labels
+  if (weighted) b += HW * 8 + 4;                              // the weight plane, the bad-mesh count
   b += H * nx * 4 * 8 + ny * nx * 6 * 8;                      // row splines, mesh grids
   b += capn * 5 * 4;                                          // component table
   b += HW * (8 + 6 * 4) + capn * ((2 + OBJ_D) * 8 + 3 * 4);   // deblend scratch
@@ -757,10 +865,10 @@ __global__ __launch_bounds__(DT) void band_gather_kernel(const double* __restric
 // ny x nx background meshes); back / rms / labout exist only when the caller wants those maps, wdev (the nwhich field numbers
 // of a device source) only when the fields come from device memory.
 struct DetectWork {
-  DevBuf<double> data, v, D, mb, mr, fbk, frm, d2b, d2r, gb, gb2, gr, gr2, grms, kdev, cdev, back, rms;
-  DevBuf<int> par, lab, area, cmin, cmax, rmax, lidx, table, ncomp, labout, wdev;
+  DevBuf<double> data, v, D, mb, mr, fbk, frm, d2b, d2r, gb, gb2, gr, gr2, grms, kdev, cdev, back, rms, wt;
+  DevBuf<int> par, lab, area, cmin, cmax, rmax, lidx, table, ncomp, labout, wdev, nbad;
   int alloc(int chunk, int H, int W, int ny, int nx, long ccap, size_t ktaps, size_t ccoef, bool want_back, bool want_rms,
-            bool want_labels, int nwhich) {
+            bool want_labels, int nwhich, bool weighted) {
     const size_t px = (size_t)chunk * H * W, grid = (size_t)chunk * ny * nx, rows = (size_t)chunk * H * nx;
     for (DevBuf<double>* b : {&data, &v, &D}) DV_TRY(b->alloc(px));
     for (DevBuf<int>* b : {&par, &lab, &area, &cmin, &cmax, &rmax, &lidx}) DV_TRY(b->alloc(px));
@@ -772,6 +880,7 @@ struct DetectWork {
     if (want_rms) DV_TRY(rms.alloc(px));
     if (want_labels) DV_TRY(labout.alloc(px));
     if (nwhich > 0) DV_TRY(wdev.alloc((size_t)nwhich));
+    if (weighted) { DV_TRY(wt.alloc(px)); DV_TRY(nbad.alloc((size_t)chunk)); }   // (7z) the weight planes, the bad meshes
     return OK;
   }
 };
@@ -790,8 +899,10 @@ struct DeblendScratch {
   }
 };
 
-// the detector: the fields come from the host (fields_h) or, with `dev`, from a stack that lies in device memory
-int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, int W, double thresh, double cont, int minarea,
+// the detector: the fields come from the host (fields_h) or, with `dev`, from a stack that lies in device memory; with `wq`
+// the weighted rules of DESIGN 7z, the planes coming from where the fields come from
+int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWeights* wq, int M, int H, int W, double thresh,
+                double cont, int minarea,
                 int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
                 int64_t workspace_bytes, int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h,
                 int32_t* field_h, int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h,
@@ -808,6 +919,22 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
     set_error("scene_detect: bad arguments");
     return E_INVALID;
   }
+  if (wq) {
+    if (dev ? !dev->weights_dev : !wq->weights_h) {
+      set_error("scene_detect: weighted detection without weights");
+      return E_INVALID;
+    }
+    if ((wq->noise != 0 && wq->noise != 1) || (wq->filter != 0 && wq->filter != 1)) {
+      set_error("scene_detect: noise must be 0 (absolute) or 1 (relative) and filter 0 (conv) or 1 (matched), got %d, %d",
+                wq->noise, wq->filter);
+      return E_INVALID;
+    }
+    if (wq->noise == 0 && !(thresh > 0.0)) {
+      set_error("scene_detect: with absolute noise the threshold is in units of sigma and must be > 0 (got %g)", thresh);
+      return E_INVALID;
+    }
+  }
+  const bool absolute = wq && wq->noise == 0, matched = wq && wq->filter == 1;
   if (kernel_h && (kh < 1 || kw < 1 || kh > KMAX || kw > KMAX || (kh & 1) == 0 || (kw & 1) == 0)) {
     set_error("scene_detect: the filter kernel must have odd sizes of 1 .. %d (got %d x %d)", KMAX, kh, kw);
     return E_INVALID;
@@ -836,7 +963,7 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
   const int ny = (H + back_size - 1) / back_size, nx = (W + back_size - 1) / back_size;
   const bool maps = back_h || rms_h || D_h || labels_h;
   const long cap_ws = workspace_bytes > 0 ? (long)workspace_bytes : (4L << 30);
-  const long per_field = field_bytes(H, W, ny, nx, minarea, maps);
+  const long per_field = field_bytes(H, W, ny, nx, minarea, maps, wq != nullptr);
   if (M > 0 && per_field > cap_ws) {
     set_error("scene_detect: one %d x %d field needs up to %ld bytes of device workspace, above the cap of %ld bytes per "
               "launch", H, W, per_field, cap_ws);
@@ -857,7 +984,7 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
   DetectWork w;
   if (chunk > 0) {
     DV_TRY(w.alloc(chunk, H, W, ny, nx, ccap, kn.size(), cco.size(), back_h != nullptr, rms_h != nullptr,
-                   labels_h != nullptr, dev ? M : 0));
+                   labels_h != nullptr, dev ? M : 0, wq != nullptr));
     DV_HIP(hipMemcpyAsync(w.kdev, kn.data(), kn.size() * sizeof(double), hipMemcpyHostToDevice, s));
     DV_HIP(hipMemcpyAsync(w.cdev, cco.data(), cco.size() * sizeof(double), hipMemcpyHostToDevice, s));
     if (dev) DV_HIP(hipMemcpyAsync(w.wdev, dev->which_h, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
@@ -871,23 +998,49 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
       hipLaunchKernelGGL(band_gather_kernel, dim3(nblk(HW), (unsigned)m), dim3(DT), 0, s, dev->fields_dev, HW, dev->nb,
                          dev->band, w.wdev + f0, w.data);
       DV_HIP(hipGetLastError());
+      if (wq) {
+        hipLaunchKernelGGL(band_gather_kernel, dim3(nblk(HW), (unsigned)m), dim3(DT), 0, s, dev->weights_dev, HW, 1, 0,
+                           w.wdev + f0, w.wt);
+        DV_HIP(hipGetLastError());
+      }
     } else {
       DV_HIP(hipMemcpyAsync(w.data, fields_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
+      if (wq)
+        DV_HIP(hipMemcpyAsync(w.wt, wq->weights_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    hipLaunchKernelGGL(bkg_mesh_kernel, dim3((unsigned)((long)m * ny * nx)), dim3(DT), 0, s, w.data, H, W, back_size, ny,
-                       nx, w.mb, w.mr);
-    DV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bkg_grid_kernel, dim3((unsigned)m), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev, w.fbk,
-                       w.frm, w.d2b, w.d2r, w.grms);
+    const dim3 gmesh((unsigned)((long)m * ny * nx)), gfilt((unsigned)((W + FT - 1) / FT), (unsigned)((H + FT - 1) / FT),
+                                                            (unsigned)m);
+    if (wq) {
+      hipLaunchKernelGGL(bkg_mesh_kernel<true>, gmesh, dim3(DT), 0, s, w.data, w.wt, H, W, back_size, ny, nx, w.mb, w.mr);
+      DV_HIP(hipGetLastError());
+      hipLaunchKernelGGL(bkg_grid_kernel<true>, dim3((unsigned)m), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev,
+                         w.fbk, w.frm, w.d2b, w.d2r, w.grms, w.nbad);
+    } else {
+      hipLaunchKernelGGL(bkg_mesh_kernel<false>, gmesh, dim3(DT), 0, s, w.data, nullptr, H, W, back_size, ny, nx, w.mb, w.mr);
+      DV_HIP(hipGetLastError());
+      hipLaunchKernelGGL(bkg_grid_kernel<false>, dim3((unsigned)m), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev,
+                         w.fbk, w.frm, w.d2b, w.d2r, w.grms, nullptr);
+    }
     DV_HIP(hipGetLastError());
     hipLaunchKernelGGL(bkg_row_kernel, dim3(nblk((long)m * H)), dim3(DT), 0, s, w.fbk, w.frm, w.d2b, w.d2r, m, H, ny, nx,
                        back_size, w.rms ? 1 : 0, w.cdev, w.gb, w.gb2, w.gr, w.gr2);
     DV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bkg_pixel_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.data, px, W, nx, back_size, w.gb, w.gb2, w.gr,
-                       w.gr2, w.v, w.back, w.rms);
+    if (wq)
+      hipLaunchKernelGGL(bkg_pixel_kernel<true>, dim3(nblk(px)), dim3(DT), 0, s, w.data, w.wt, px, W, nx, back_size, w.gb,
+                         w.gb2, w.gr, w.gr2, w.v, w.back, w.rms);
+    else
+      hipLaunchKernelGGL(bkg_pixel_kernel<false>, dim3(nblk(px)), dim3(DT), 0, s, w.data, nullptr, px, W, nx, back_size, w.gb,
+                         w.gb2, w.gr, w.gr2, w.v, w.back, w.rms);
     DV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(filter_kernel, dim3((unsigned)((W + FT - 1) / FT), (unsigned)((H + FT - 1) / FT), (unsigned)m),
-                       dim3(DT), 0, s, w.v, H, W, w.kdev, kh, kw, w.grms, thresh, w.D, w.par);
+    if (matched)
+      hipLaunchKernelGGL((filter_kernel<true, true>), gfilt, dim3(DT), 0, s, w.v, w.wt, H, W, w.kdev, kh, kw, w.grms, thresh,
+                         absolute ? 1 : 0, w.D, w.par);
+    else if (wq)
+      hipLaunchKernelGGL((filter_kernel<true, false>), gfilt, dim3(DT), 0, s, w.v, w.wt, H, W, w.kdev, kh, kw, w.grms, thresh,
+                         absolute ? 1 : 0, w.D, w.par);
+    else
+      hipLaunchKernelGGL((filter_kernel<false, false>), gfilt, dim3(DT), 0, s, w.v, nullptr, H, W, w.kdev, kh, kw, w.grms,
+                         thresh, 0, w.D, w.par);
     DV_HIP(hipGetLastError());
     DV_HIP(hipMemsetAsync(w.area, 0, (size_t)px * sizeof(int), s));
     DV_HIP(hipMemsetAsync(w.cmin, 0x7f, (size_t)px * sizeof(int), s));
@@ -907,6 +1060,8 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
     }
     DV_HIP(hipMemcpyAsync(globalrms_h + f0, w.grms, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
     DV_HIP(hipMemcpyAsync(h_ncomp.data(), w.ncomp, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (wq && wq->bad_meshes_h)
+      DV_HIP(hipMemcpyAsync(wq->bad_meshes_h + f0, w.nbad, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
     if (back_h) DV_HIP(hipMemcpyAsync(back_h + (size_t)f0 * HW, w.back, (size_t)px * 8, hipMemcpyDeviceToHost, s));
     if (rms_h) DV_HIP(hipMemcpyAsync(rms_h + (size_t)f0 * HW, w.rms, (size_t)px * 8, hipMemcpyDeviceToHost, s));
     if (D_h) DV_HIP(hipMemcpyAsync(D_h + (size_t)f0 * HW, w.D, (size_t)px * 8, hipMemcpyDeviceToHost, s));
@@ -936,7 +1091,7 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, int M, int H, i
         j.c1 = row[3];
         j.r1 = row[4];
         j.cap = std::max(1, j.n / minarea);
-        j.T = thresh * globalrms_h[f0 + f];
+        j.T = absolute ? thresh : thresh * globalrms_h[f0 + f];
         j.dws = dws;
         j.iws = iws;
         j.slot = slots;
@@ -1002,12 +1157,12 @@ int scene_detect(const double* fields_h, int M, int H, int W, double thresh, dou
                  int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
                  int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
                  int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s) {
+                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s, const DetectWeights* wq) {
   if (!fields_h) {
     set_error("scene_detect: bad arguments");
     return E_INVALID;
   }
-  return detect_impl(fields_h, nullptr, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
+  return detect_impl(fields_h, nullptr, wq, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
                      workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
                      y_h, back_h, rms_h, D_h, labels_h, s);
 }
@@ -1016,8 +1171,8 @@ int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh
                      int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
                      int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
                      int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                     hipStream_t s) {
-  return detect_impl(nullptr, &src, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
+                     hipStream_t s, const DetectWeights* wq) {
+  return detect_impl(nullptr, &src, wq, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
                      workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
                      y_h, nullptr, nullptr, nullptr, nullptr, s);
 }

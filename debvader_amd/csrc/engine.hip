@@ -580,6 +580,10 @@ struct dv_field_set {
   // pass's later chunks still gather from `work`.
   dv::DevBuf<double> base, work, next, fin, mean, stddev;
   dv::DevBuf<double> mse_part, fmse;             // partial sums and results of the field_mse reduction
+  // the detector's weight planes [M][F][F] (dv_field_set_detect_weights): while held, dv_field_set_detect
+  // takes the weighted path with dnoise / dfilter
+  dv::DevBuf<double> dweights;
+  int dnoise = 0, dfilter = 0;
   dv::StampTables tab;                           // the per-stamp tables of a pass, kept between passes and grown on demand
   std::vector<double> fmse_h;                     // host side of fmse
   // the catalogue of the measured passes (dv_field_set_pass_measure).  Resident rows: {shape[5], status,
@@ -640,7 +644,7 @@ struct dv_field_set {
 
 static void field_set_release(dv_field_set* fs) {
   for (dv::DevBuf<double>* b : {&fs->base, &fs->work, &fs->next, &fs->fin, &fs->mean, &fs->stddev, &fs->mse_part, &fs->fmse,
-                                &fs->rshape, &fs->rsums, &fs->cflux, &fs->cferr, &fs->cblend})
+                                &fs->dweights, &fs->rshape, &fs->rsums, &fs->cflux, &fs->cferr, &fs->cblend})
     b->reset();
   for (dv::DevBuf<int>* b : {&fs->rstatus, &fs->rplaces, &fs->rfield, &fs->citers, &fs->cnpix}) b->reset();
   fs->nrows = fs->rcap = 0;
@@ -4107,6 +4111,22 @@ int dv_scene_detect(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32
                       peak, flux, x, y, back, rms, D, labels, c->stream);
 }
 
+int dv_scene_detect_weighted(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, const dv_detect_params* p,
+                             int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms, int32_t* field,
+                             int32_t* parent, int32_t* npix, double* peak, double* flux, double* x, double* y, double* back,
+                             double* rms, double* D, int32_t* labels, const dv_detect_weights* wt, int32_t* bad_meshes) {
+  if (!c || !p) return DV_E_INVALID;
+  if (!wt || !wt->weights) {
+    set_error("dv_scene_detect_weighted: the weights must be given (dv_scene_detect is the call without them)");
+    return DV_E_INVALID;
+  }
+  DV_HIP(hipSetDevice(c->device));
+  const DetectWeights wq{wt->weights, wt->noise, wt->filter, bad_meshes};
+  return scene_detect(fields, M, H, W, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
+                      p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, offsets, globalrms, field, parent, npix,
+                      peak, flux, x, y, back, rms, D, labels, c->stream, &wq);
+}
+
 int dv_ctx_allreduce_host(dv_ctx* c, float* buf, int32_t n) {
   if (!c || !buf || n < 0 || n > 4096) return DV_E_INVALID;
   if (!c->comm || n == 0) return DV_OK;
@@ -6256,12 +6276,13 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
   std::vector<int64_t> off((size_t)Ma + 1, 0);
   std::vector<double> grms((size_t)std::max(Ma, 1), 0.0);
   DV_HIP(hipSetDevice(fs->m->ctx->device));
-  DetectDevSrc src{fs->work, fs->nb, 2, act.data()};
+  DetectDevSrc src{fs->work, fs->nb, 2, act.data(), fs->dweights};
+  const DetectWeights wq{nullptr, fs->dnoise, fs->dfilter, nullptr};
   *n_out = 0;
   if (Ma > 0)
     DV_TRY(scene_detect_dev(src, Ma, fs->F, fs->F, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
                           p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, off.data(), grms.data(), field, parent,
-                          npix, peak, flux, x, y, fs->m->ctx->stream));
+                          npix, peak, flux, x, y, fs->m->ctx->stream, fs->dweights ? &wq : nullptr));
   // the catalogue of the active fields in the numbering of the set: an inactive field has an empty range
   offsets[0] = 0;
   int a = 0;
@@ -6273,6 +6294,43 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
   }
   if (*n_out <= cap)
     for (int64_t i = 0; i < *n_out; ++i) field[i] = act[field[i]];
+  return DV_OK;
+}
+
+int dv_field_set_detect_weights(dv_field_set* fs, const double* weights, int32_t noise, int32_t filter) {
+  DV_TRY(field_set_live(fs, "dv_field_set_detect_weights"));
+  DV_HIP(hipSetDevice(fs->m->ctx->device));
+  hipStream_t s = fs->m->ctx->stream;
+  if (!weights) {                               // drop the planes: dv_field_set_detect is the unweighted call again
+    DV_HIP(hipStreamSynchronize(s));
+    fs->dweights.reset();
+    return DV_OK;
+  }
+  if ((noise != DV_DETECT_NOISE_ABSOLUTE && noise != DV_DETECT_NOISE_RELATIVE) ||
+      (filter != DV_DETECT_FILTER_CONV && filter != DV_DETECT_FILTER_MATCHED)) {
+    set_error("dv_field_set_detect_weights: noise must be 0 (absolute) or 1 (relative) and filter 0 (conv) or 1 (matched), "
+              "got %d, %d", noise, filter);
+    return DV_E_INVALID;
+  }
+  const size_t n = (size_t)fs->M * fs->F * fs->F;
+  if (!fs->dweights) {
+    // counted like the set itself: against free memory less the detector's workspace and the per-stamp tables
+    const size_t reserve = std::min<size_t>((size_t)4 << 30, n * 128) + ((size_t)64 << 20);
+    size_t budget = 0;
+    DV_TRY(fields_budget(reserve, &budget));
+    if (n * sizeof(double) > budget) {
+      set_error("dv_field_set_detect_weights: the weight planes of %d %d-pixel fields need %zu bytes of device memory, %zu "
+                "bytes are available", fs->M, fs->F, n * sizeof(double), budget);
+      return DV_E_NOMEM;
+    }
+    DV_TRY(fs->dweights.alloc(std::max<size_t>(n, 1)));
+  }
+  if (n > 0) {
+    DV_HIP(hipMemcpyAsync(fs->dweights, weights, n * sizeof(double), hipMemcpyHostToDevice, s));
+    DV_HIP(hipStreamSynchronize(s));
+  }
+  fs->dnoise = noise;
+  fs->dfilter = filter;
   return DV_OK;
 }
 

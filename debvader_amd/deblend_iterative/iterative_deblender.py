@@ -285,7 +285,8 @@ class IterativeDeblendFieldBatch:
     def iterative_catalogue(self, mse_criterion=100.0, mode="reference", max_iterations=None, measure=False,
                             blendedness=False, return_fields=True, band=2, sigma0=3.0, tol=1e-10, max_iter=200,
                             match_radius=2.0, fit_flux=False, fit_weights=None, fit_sky=None, fit_nonneg=False,
-                            sky_sigma=None, min_pivot=1e-8, fit_groups=False):
+                            sky_sigma=None, min_pivot=1e-8, detect_weights=None, detect_noise=None, detect_filter="conv",
+                            detect_thresh=None, fit_groups=False):
         """iterative_deblending() with a catalogue measured on the GPU: the same loop, the same
         list of M recarrays (kept in self.res_deblend), self.mse and fields, and with every argument behind the first
         three left at its default the same calls.  The arguments are a method of their own because the parameter list of
@@ -327,6 +328,15 @@ class IterativeDeblendFieldBatch:
             recarrays gain measurement.fit_groups_dtype(bands): fit_group, the smallest row of the galaxy's group in its
             field's recarray - the rows of all passes count, so a group may span passes -, and fit_group_size.  Together with
             fit_sky or fit_nonneg it is the ValueError of DeblendFieldBatch.deblend_fields.
+        detect_weights (M, F, F) or (M, F, F, bands), of which band 2 is taken: every detection pass runs with a per-pixel
+            noise map and a mask (FieldSet.set_detect_weights before the first pass): a pixel counts
+            iff 0 < w < inf.  detect_noise "absolute" (the default with weights: inverse variances, the threshold in units
+            of the pixel's sigma) or "relative" (relative weights, the threshold in units of globalrms), detect_filter "conv"
+            or "matched", as in Context.scene_detect; both need detect_weights.  The fields themselves must stay finite,
+            because the network reads them: fill the pixels under a bleed trail, a saturated core or a chip gap with finite
+            values (the local sky, say) - the weights keep them out of every detection pass, whatever they hold.
+        detect_thresh: the detection threshold of every pass (None: the detector's 1.5), with or without weights.
+            (The four detect_* arguments are keywords: pass them, and fit_groups behind them, by name.)
 
         mse_criterion, mode, max_iterations: as in iterative_deblending."""
         if mode not in ("reference", "cumulative"):
@@ -367,6 +377,17 @@ class IterativeDeblendFieldBatch:
             if sky_sigma is not None:
                 sky_sigma = ms.check_sky_sigma(sky_sigma, M, self.nb_of_bands)
             E.fit_flux_params(min_pivot)
+        if detect_weights is None and (detect_noise is not None or detect_filter != "conv"):
+            raise ValueError("detect_noise and detect_filter need detect_weights: they belong to the weighted detector")
+        detect_kw = {} if detect_thresh is None else {"thresh": float(detect_thresh)}
+        if detect_weights is not None:
+            from debvader_amd import engine as E
+
+            detect_weights = np.asarray(detect_weights, dtype=np.float64)
+            if detect_weights.ndim == 4 and detect_weights.shape[:3] == (M, F, F) and detect_weights.shape[3] > 2:
+                detect_weights = detect_weights[:, :, :, 2]
+            E.check_detect_weights((M, F, F), detect_weights, None, detect_noise, detect_filter,
+                                   1.5 if detect_thresh is None else detect_thresh)
         take_sums = bool(blendedness) or fit_flux        # the passes that keep resident rows
         fit = None
         self.sky_fit = None
@@ -389,9 +410,11 @@ class IterativeDeblendFieldBatch:
         try:
             if fit_flux:
                 fs.keep_stamps()
+            if detect_weights is not None:
+                fs.set_detect_weights(detect_weights, noise=detect_noise, filter_type=detect_filter)
             k = 0
             while active.any() and (max_iterations is None or k < int(max_iterations)):
-                det = fs.detect(active=active)
+                det = fs.detect(active=active, **detect_kw)
                 off = det["offsets"]
                 dist = [_distances(det["x"][off[m]:off[m + 1]], det["y"][off[m]:off[m + 1]], F) if active[m]
                         else np.zeros((0, 2)) for m in range(M)]

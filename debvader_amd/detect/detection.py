@@ -30,10 +30,23 @@ def _bands_r(images):
     return a[:, :, :, R_BAND]
 
 
+def _planes_r(kw, n):
+    """the detector's keywords with weights / mask of (N, F, F, bands) cut to band 2, the first n
+    fields of them; (N, F, F) planes pass as they are"""
+    kw = dict(kw)
+    for name in ("weights", "mask"):
+        if kw.get(name) is not None:
+            a = np.asarray(kw[name])
+            kw[name] = _bands_r(a[:n]) if a.ndim == 4 else a[:n]
+    return kw
+
+
 def detect_objects_batch(field_images, ctx=None, **kw):
     """detect_objects for every field of (N, F, F, bands) in one engine call; returns a list of N arrays as
-    detect_objects returns them.  kw: the detector's settings (Context.scene_detect)."""
+    detect_objects returns them.  kw: the detector's settings (Context.scene_detect), among them weights, mask, noise and
+    filter_type: the noise map and the mask that sep takes as err= and mask=."""
     r_band = _bands_r(field_images)
+    kw = _planes_r(kw, len(r_band))
     ctx = ctx or E.default_context()
     r = ctx.scene_detect(r_band, **kw)
     F = r_band.shape[1]
@@ -52,6 +65,7 @@ def detect_objects(field_image, ctx=None, **kw):
         raise ValueError(f"expected a field (1, F, F, bands), got {field_image.shape}")
     field_size = field_image.shape[1]
     r_band = _bands_r(field_image[:1])
+    kw = _planes_r(kw, 1)
     ctx = ctx or E.default_context()
     r = ctx.scene_detect(r_band, **kw)
     return _distances(r["x"], r["y"], field_size)

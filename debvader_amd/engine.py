@@ -412,13 +412,17 @@ def _measure_mc_out(n, nb, S, keep_samples):
 
 
 def check_detect_args(fields_r, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
-                      workspace_bytes=0) -> np.ndarray:
-    """Context.scene_detect's argument checks (before any GPU work); returns the fields as float64 (M, H, W)."""
+                      workspace_bytes=0, weights=None) -> np.ndarray:
+    """Context.scene_detect's argument checks (before any GPU work); returns the fields as float64 (M, H, W).  weights
+    (M, H, W): the weighted call, where the fields must be finite only at the counting pixels."""
     f = np.ascontiguousarray(fields_r, dtype=np.float64)
     if f.ndim != 3 or f.shape[1] < 1 or f.shape[2] < 1:
         raise ValueError(f"expected fields (M, H, W), got {f.shape}")
-    if not np.isfinite(f).all():
-        raise ValueError("the fields must be finite")
+    if not np.isfinite(f).all():                      # (one pass over the fields; the weights are read only behind a miss)
+        if weights is None:
+            raise ValueError("the fields must be finite")
+        if not np.isfinite(f[counting_pixels(weights)]).all():
+            raise ValueError("the fields must be finite at every pixel that counts (0 < weight < inf)")
     if not (np.isfinite(thresh) and np.isfinite(cont)) or int(minarea) < 1 or not 1 <= int(nthresh) <= 1024:
         raise ValueError(f"thresh and cont must be finite, minarea >= 1 and nthresh 1 .. 1024 "
                          f"(got {thresh}, {cont}, {minarea}, {nthresh})")
@@ -431,6 +435,45 @@ def check_detect_args(fields_r, thresh, minarea, nthresh, cont, filter_kernel, b
             raise ValueError(f"filter_kernel must be a finite, non-zero, odd-sized 2-d array up to 15 x 15, got shape "
                              f"{k.shape}")
     return f
+
+
+def check_detect_weights(shape, weights, mask, noise, filter_type, thresh):
+    """The weight arguments of Context.scene_detect and FieldSet.set_detect_weights, checked before
+    any GPU work, for fields of `shape` (M, H, W).  weights: inverse variances or relative weights, a pixel counts iff
+    0 < w < inf; mask: booleans, True = bad, zeroes the weights; mask alone: unit weights and noise "relative"; noise
+    defaults to "absolute" when weights are given.  Returns (planes float64 (M, H, W), DV_DETECT_NOISE_*, DV_DETECT_FILTER_*)."""
+    shape = tuple(int(n) for n in shape)
+    if weights is None and mask is None:
+        raise ValueError("weighted detection needs weights, a mask or both")
+    if noise is None:
+        noise = "absolute" if weights is not None else "relative"
+    if noise not in _lib.DETECT_NOISE:
+        raise ValueError(f"noise must be 'absolute' (the weights are inverse variances, thresh in sigma) or 'relative' "
+                         f"(relative weights, thresh in units of globalrms), got {noise!r}")
+    if filter_type not in _lib.DETECT_FILTER:
+        raise ValueError(f"filter_type must be 'conv' or 'matched', got {filter_type!r}")
+    if weights is None:
+        w = np.ones(shape, np.float64)
+    else:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if mask is not None:
+            w = w.copy()                                  # (the caller's array is kept)
+        if w.shape != shape:
+            raise ValueError(f"expected weights of the fields' shape {shape}, got {w.shape}")
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.dtype != np.bool_ or m.shape != shape:
+            raise ValueError(f"expected a boolean mask (True = bad) of the fields' shape {shape}, got {m.dtype} {m.shape}")
+        w[m] = 0.0
+    if noise == "absolute" and not float(thresh) > 0:
+        raise ValueError(f"with noise='absolute' thresh is in units of the pixel's sigma and must be > 0, got {thresh}")
+    return w, _lib.DETECT_NOISE[noise], _lib.DETECT_FILTER[filter_type]
+
+
+def counting_pixels(w):
+    """the pixels that count: 0 < w < inf (NaN does not)"""
+    with np.errstate(invalid="ignore"):
+        return (w > 0) & (w < np.inf)
 
 
 class _Lease:
@@ -1169,7 +1212,8 @@ class Context:
 
     def scene_detect(self, fields_r, thresh: float = 1.5, minarea: int = 4, nthresh: int = 64, cont: float = 1e-5,
                      filter_kernel=None, back_size: int = 64, back_filter: int = 3, return_maps: bool = False,
-                     workspace_bytes: int = 0) -> Dict[str, np.ndarray]:
+                     workspace_bytes: int = 0, weights=None, mask=None, noise=None,
+                     filter_type: str = "conv") -> Dict[str, np.ndarray]:
         """Source detection on one band of M fields (detect/detection.py's sep call, on the GPU).
 
         fields_r (M, H, W).  SExtractor's method, float64: background meshes of back_size px with a back_filter median
@@ -1179,9 +1223,28 @@ class Context:
         per object ordered by field, component and peak pixel, plus offsets (M + 1: the rows of field f are
         offsets[f]:offsets[f + 1]) and globalrms (M,); with return_maps also back, rms, D (M, H, W) and labels (M, H, W)
         (the component's parent, -1 outside kept components).  workspace_bytes caps the device workspace per launch
-        (0: 4 GiB); a field that needs more is refused."""
+        (0: 4 GiB); a field that needs more is refused.
+
+        weights and / or mask: detection with a per-pixel noise map and a mask (dv_scene_detect_weighted, DESIGN.md
+        section 7z).  weights (M, H, W): a pixel counts iff 0 < w < inf; mask (M, H, W) booleans, True = bad, zeroes the
+        weights; a mask alone means unit weights and noise="relative".  noise="absolute" (the default with weights): w is
+        an inverse variance and thresh is in units of the pixel's own sigma; noise="relative": w is a relative weight and
+        the threshold is thresh * globalrms.  filter_type "conv": S = (sum kn v) sqrt(w); "matched":
+        S = (sum kn v w) / sqrt(sum kn^2 w).  The D map then holds S and peak is its maximum; the fields must be finite only
+        at counting pixels; the result gains bad_meshes (M,), the meshes of every field with fewer than half of their
+        pixels counting; a field without a good mesh has no objects, globalrms NaN and labels -1.  With weights and mask
+        both None the call is the unweighted one, argument for argument (noise and filter_type must then be left alone)."""
+        weighted = weights is not None or mask is not None
+        wts = None
+        if weighted:
+            shape = np.shape(fields_r)
+            if len(shape) != 3:
+                raise ValueError(f"expected fields (M, H, W), got {shape}")
+            wts, noise_id, filter_id = check_detect_weights(shape, weights, mask, noise, filter_type, thresh)
+        elif noise is not None or filter_type != "conv":
+            raise ValueError("noise and filter_type belong to the weighted call: give weights, a mask or both")
         f = check_detect_args(fields_r, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
-                              workspace_bytes)
+                              workspace_bytes, weights=wts)
         kern, kptr, kh, kw = None, None, 0, 0
         if filter_kernel is not None:
             kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
@@ -1206,16 +1269,24 @@ class Context:
             cat = {k: np.empty(cap, np.int32 if k in ("field", "parent", "npix") else np.float64)
                    for k in self.CATALOG_KEYS}
             n = C.c_int64()
-            check(lib.dv_scene_detect(self._h, f.ctypes.data_as(dp), M, H, W, C.byref(params), cap, C.byref(n),
-                                      offsets.ctypes.data_as(C.POINTER(C.c_int64)), grms.ctypes.data_as(dp),
-                                      *[_ptr(cat[k], ip if cat[k].dtype == np.int32 else dp) for k in self.CATALOG_KEYS],
-                                      _ptr(maps.get("back"), dp), _ptr(maps.get("rms"), dp), _ptr(maps.get("D"), dp),
-                                      _ptr(maps.get("labels"), ip)))
+            args = [self._h, f.ctypes.data_as(dp), M, H, W, C.byref(params), cap, C.byref(n),
+                    offsets.ctypes.data_as(C.POINTER(C.c_int64)), grms.ctypes.data_as(dp),
+                    *[_ptr(cat[k], ip if cat[k].dtype == np.int32 else dp) for k in self.CATALOG_KEYS],
+                    _ptr(maps.get("back"), dp), _ptr(maps.get("rms"), dp), _ptr(maps.get("D"), dp),
+                    _ptr(maps.get("labels"), ip)]
+            if weighted:
+                bad = np.zeros(M, np.int32)
+                wstruct = _lib.DvDetectWeights(wts.ctypes.data_as(dp), noise_id, filter_id)
+                check(lib.dv_scene_detect_weighted(*args, C.byref(wstruct), bad.ctypes.data_as(ip)))
+            else:
+                check(lib.dv_scene_detect(*args))
             if n.value <= cap:
                 break
             cap = n.value
         out = {k: v[:n.value].copy() for k, v in cat.items()}
         out.update(offsets=offsets, globalrms=grms, **maps)
+        if weighted:
+            out["bad_meshes"] = bad
         return out
 
     def close(self):
@@ -2212,6 +2283,7 @@ class FieldSet:
         self.cumulative = bool(cumulative)
         self._h = C.c_void_p()
         self._rows = 0                      # stamps of the deblend_pass_measure(blend=True) calls: the set's resident rows
+        self._detect_noise = None           # DV_DETECT_NOISE_* while set_detect_weights holds planes
         if not engine._h:
             raise RuntimeError("the Engine of this FieldSet has been closed")
         M, F, _, nb = fields.shape
@@ -2223,6 +2295,28 @@ class FieldSet:
             raise _lib.DvError(-5, "the field set has been closed")
         return self._h
 
+    def set_detect_weights(self, weights, noise=None, filter_type: str = "conv", mask=None):
+        """The weight planes of every later detect() (dv_field_set_detect_weights): weights (M, F, F),
+        or (M, F, F, bands) from which band 2 is taken, uploaded once and kept until close() or set_detect_weights(None),
+        which goes back to the unweighted detector.  noise, filter_type and mask (M, F, F) as in Context.scene_detect.  The
+        working residuals themselves must stay finite (the network reads them): fill masked pixels with finite values, the
+        weights keep them out of every detection pass."""
+        h = self._handle()
+        M, F = self.shape[0], self.shape[1]
+        if weights is None and mask is None:
+            check(lib.dv_field_set_detect_weights(h, None, 0, 0))
+            self._detect_noise = None
+            return
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.ndim == 4:
+                if weights.shape[3] <= 2:
+                    raise ValueError(f"detection uses band 2; these weights have {weights.shape[3]} band(s)")
+                weights = weights[:, :, :, 2]
+        w, noise_id, filter_id = check_detect_weights((M, F, F), weights, mask, noise, filter_type, 1.0)
+        check(lib.dv_field_set_detect_weights(h, _dp(w), noise_id, filter_id))
+        self._detect_noise = noise_id
+
     def detect(self, active=None, thresh: float = 1.5, minarea: int = 4, nthresh: int = 64, cont: float = 1e-5,
                filter_kernel=None, back_size: int = 64, back_filter: int = 3, workspace_bytes: int = 0) -> Dict[str, np.ndarray]:
         """Context.scene_detect on band 2 of the working residuals, which do not leave the GPU (dv_field_set_detect).
@@ -2232,6 +2326,8 @@ class FieldSet:
         M, F = self.shape[0], self.shape[1]
         check_detect_args(np.zeros((0, F, F)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
                           workspace_bytes)
+        if getattr(self, "_detect_noise", None) == _lib.DETECT_NOISE["absolute"] and not float(thresh) > 0:
+            raise ValueError(f"with noise='absolute' thresh is in units of the pixel's sigma and must be > 0, got {thresh}")
         act = None
         if active is not None:
             act = np.ascontiguousarray(np.asarray(active, dtype=bool).astype(np.uint8))

@@ -400,6 +400,38 @@ int dv_scene_detect(dv_ctx* ctx, const double* fields, int32_t M, int32_t H, int
                     int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms, int32_t* field, int32_t* parent,
                     int32_t* npix, double* peak, double* flux, double* x, double* y, double* back, double* rms,
                     double* D, int32_t* labels);
+/* dv_scene_detect_weighted: dv_scene_detect with a per-pixel noise map and a mask.  weights [M][H][W]
+ * float64, the convention of the flux fit (7s): a pixel COUNTS iff 0 < w < inf (a comparison: NaN does not count); a data
+ * value under a pixel that does not count reaches no sum (selects, never a product with zero), so the fields must be finite
+ * only where the pixel counts.  noise = DV_DETECT_NOISE_ABSOLUTE: w is an inverse variance and thresh is in units of the
+ * pixel's own sigma; DV_DETECT_NOISE_RELATIVE: w is a relative weight and the threshold is thresh * globalrms (SExtractor's
+ * MAP_WEIGHT; with w in {0, 1} a mask only).  The steps of dv_scene_detect with these changes: only counting pixels enter a
+ * mesh's clipping; a mesh is good iff 2 * n_counting >= its pixels; a bad mesh takes, for background and rms separately, the
+ * mean of the good meshes of its field at the smallest squared mesh distance (ties added in raster order) before the median
+ * filter; v = data - back where the pixel counts, 0 elsewhere; the significance map S takes the place of D everywhere
+ * downstream (segmentation, deblending levels, core moments, peak; the D map holds S): filter = DV_DETECT_FILTER_CONV:
+ * S = (sum kn v) sqrt(w); DV_DETECT_FILTER_MATCHED: S = (sum kn (v w)) / sqrt(sum (kn kn) w), -inf where the denominator is
+ * 0; S = -inf at a pixel that does not count.  T = thresh (absolute) or thresh * globalrms (relative).  flux and the
+ * barycentres stay sums over v.  A field without a good mesh has no objects, an empty offsets range, globalrms NaN, labels
+ * -1 and otherwise unspecified maps; the other fields of the call are untouched.  bad_meshes [M] (nullable): the bad meshes
+ * of every field.  With w = 1 everywhere and relative noise, and with w = 1, absolute noise and thresh' = thresh * globalrms,
+ * every output has the bits of dv_scene_detect.
+ * Refused before any GPU work (DV_E_INVALID, the engine stays usable): what dv_scene_detect refuses, a null struct or null
+ * weights, an unknown noise or filter, thresh <= 0 with absolute noise. */
+#define DV_DETECT_NOISE_ABSOLUTE 0
+#define DV_DETECT_NOISE_RELATIVE 1
+#define DV_DETECT_FILTER_CONV 0
+#define DV_DETECT_FILTER_MATCHED 1
+typedef struct dv_detect_weights {
+  const double* weights;   /* [M][H][W] */
+  int32_t noise;           /* DV_DETECT_NOISE_* */
+  int32_t filter;          /* DV_DETECT_FILTER_* */
+} dv_detect_weights;
+int dv_scene_detect_weighted(dv_ctx* ctx, const double* fields, int32_t M, int32_t H, int32_t W,
+                             const dv_detect_params* params, int64_t cap, int64_t* n_out, int64_t* offsets,
+                             double* globalrms, int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux,
+                             double* x, double* y, double* back, double* rms, double* D, int32_t* labels,
+                             const dv_detect_weights* weights, int32_t* bad_meshes);
 
 /* ---- catalogue measurement: fluxes and adaptive moments per galaxy ----
  * The reference ships an empty debvader.measure package; the measurement is defined here, float64 throughout.  Per stamp,
@@ -912,6 +944,14 @@ int dv_field_set_open(dv_model* m, const double* fields, int32_t M, int32_t F, i
 int dv_field_set_detect(dv_field_set* set, const uint8_t* active, const dv_detect_params* params, int64_t cap,
                         int64_t* n_out, int64_t* offsets, double* globalrms, int32_t* field, int32_t* parent,
                         int32_t* npix, double* peak, double* flux, double* x, double* y);
+/* dv_field_set_detect_weights: weights [M][F][F] float64 (one plane per field, for band 2), noise and
+ * filter as in dv_scene_detect_weighted.  The planes are uploaded once and stay with the set until dv_field_set_close or a
+ * call with weights = NULL, which drops them; their M * F * F * 8 bytes are counted against free device memory
+ * (DV_E_NOMEM, the set left as it was).  While planes are held dv_field_set_detect takes the weighted path: the bits of
+ * dv_scene_detect_weighted on band 2 of `work` read back and the planes of the active fields; a field without a good mesh
+ * has an empty range and globalrms NaN.  With no planes held it is as above.  With absolute noise dv_field_set_detect
+ * refuses thresh <= 0.  Refused (DV_E_INVALID): an unknown noise or filter; a closed set: DV_E_STATE. */
+int dv_field_set_detect_weights(dv_field_set* set, const double* weights, int32_t noise, int32_t filter);
 int dv_field_set_pass(dv_field_set* set, const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
                       uint64_t seed, double* mse_center, double* field_mse);
 int dv_field_set_read(dv_field_set* set, int32_t which, double* out);

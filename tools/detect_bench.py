@@ -3,6 +3,12 @@ fields, milliseconds for one 4096-px survey tile, and the numpy restatement's CP
 Fields: Gaussian noise plus ~40 Gaussian galaxies per 259 px (some blended).  GPU only; prints one JSON line.
 
     python tools/detect_bench.py [--batch 1024] [--tile 4096] [--repeat 3]
+
+--weights [--filter matched]: the same two workloads with a per-pixel noise map and a mask (inverse
+variances, every 97th column and one block per 259 px masked), the unweighted and the weighted leg alternating in one
+process, --runs (5) timed runs each; prints the medians, the spread (min .. max) and the ratio of the medians.
+
+    python tools/detect_bench.py --weights [--filter matched] [--runs 5]
 """
 import argparse
 import json
@@ -39,12 +45,60 @@ def _best(fn, repeat):
     return min(times), out
 
 
+def _weights(shape):
+    """inverse variances of the fields' unit noise, with every 97th column and a 9 x 13 block per 259 px masked"""
+    w = np.ones(shape)
+    w[..., :, 50::97] = 0.0
+    for r in range(100, shape[-2], 259):
+        for c in range(120, shape[-1], 259):
+            w[..., r:r + 9, c:c + 13] = 0.0
+    return w
+
+
+def _alternate(plain, weighted, runs):
+    """runs timed calls of each leg, alternating: per leg (median, min, max) seconds and the last result"""
+    tp, tw, rp, rw = [], [], None, None
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        rp = plain()
+        t1 = time.perf_counter()
+        rw = weighted()
+        t2 = time.perf_counter()
+        tp.append(t1 - t0)
+        tw.append(t2 - t1)
+    stats = lambda t: (float(np.median(t)), min(t), max(t))
+    return stats(tp), stats(tw), rp, rw
+
+
+def main_weighted(a, ctx, batch, tile):
+    # thresh in units of the pixel's sigma: 1.5 on the smoothed map of "conv" as in the unweighted leg, 5 on the matched
+    # filter's S, which is in units of the FILTERED noise (1.5 there is a forest of noise peaks)
+    kw = dict(noise="absolute", filter_type=a.filter, thresh=5.0 if a.filter == "matched" else 1.5)
+    wb, wt = _weights(batch.shape), _weights(tile.shape)
+    ctx.scene_detect(batch[:2], weights=wb[:2], **kw)                  # warm-up of the weighted kernels
+    out = {"batch": a.batch, "F": batch.shape[1], "tile": a.tile, "filter": a.filter, "noise": "absolute", "thresh": kw["thresh"],
+           "runs": a.runs,
+           "masked_fraction": round(float((wb[0] == 0).mean()), 4)}
+    for name, f, w, scale in (("batch", batch, wb, 1.0), ("tile", tile, wt, 1e3)):
+        p, q, rp, rw = _alternate(lambda: ctx.scene_detect(f), lambda: ctx.scene_detect(f, weights=w, **kw), a.runs)
+        unit = "seconds" if name == "batch" else "ms"
+        for leg, t, r in (("unweighted", p, rp), ("weighted", q, rw)):
+            out[f"{name}_{leg}_{unit}_median"] = round(scale * t[0], 5)
+            out[f"{name}_{leg}_{unit}_min_max"] = [round(scale * t[1], 5), round(scale * t[2], 5)]
+            out[f"{name}_{leg}_objects"] = int(len(r["x"]))
+        out[f"{name}_weighted_over_unweighted"] = round(q[0] / p[0], 4)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--tile", type=int, default=4096)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--oracle-fields", type=int, default=4)
+    ap.add_argument("--weights", action="store_true", help="alternate the unweighted and the weighted detector")
+    ap.add_argument("--filter", choices=("conv", "matched"), default="conv")
+    ap.add_argument("--runs", type=int, default=5)
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     F = 259
@@ -53,6 +107,8 @@ def main():
     tile = _field(rng, a.tile, a.tile, int(40 * (a.tile / F) ** 2))[None]
     ctx = E.default_context()
     ctx.scene_detect(batch[:2])                                        # warm-up (module load, first allocations)
+    if a.weights:
+        return main_weighted(a, ctx, batch, tile)
     tb, rb = _best(lambda: ctx.scene_detect(batch), a.repeat)
     tt, rt = _best(lambda: ctx.scene_detect(tile), a.repeat)
     t0 = time.perf_counter()
