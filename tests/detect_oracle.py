@@ -32,9 +32,10 @@ def _mean_sigma(x):
     return mean, np.sqrt(np.square(x - mean).sum() / n)
 
 
-def mesh_stats(vals):
+def mesh_stats(vals, details=None):
     """(background, rms) of one mesh: 3-sigma clipping around the exact median, repeated until the kept set does not
-    change, at most 100 rounds; every kept set is a contiguous range of the sorted values"""
+    change, at most 100 rounds; every kept set is a contiguous range of the sorted values.  A dict given as details
+    gains the final kept set and its mean, med and sig."""
     s = np.sort(np.asarray(vals, dtype=np.float64).ravel())
     lo, hi = 0, len(s)
     for _ in range(100):
@@ -50,6 +51,8 @@ def mesh_stats(vals):
     mean, sig = _mean_sigma(x)
     med = _median_sorted(x)
     back = 2.5 * med - 1.5 * mean if abs(mean - med) < 0.3 * sig else med
+    if details is not None:
+        details.update(mean=mean, med=med, sig=sig, kept=x)
     return back, sig
 
 
@@ -150,9 +153,14 @@ def _components(mask):
     return sorted(groups, key=lambda g: g[0])
 
 
-def deblend_component(pix, D, W, T, nthresh, minarea, cont):
+def deblend_component(pix, D, W, T, nthresh, minarea, cont, details=None):
     """multi-threshold deblending of one component (pixels pix, ascending raster indices).  Returns the final objects as
-    (core mask over pix, threshold of the core's level) and the object every pixel of pix is assigned to."""
+    (core mask over pix, threshold of the core's level) and the object every pixel of pix is assigned to.  A dict given as
+    details is filled with what the rules went through (tests/detect_shapes.py checks its premises on it): values (D over
+    pix), levels (every t_k computed), nobj (the length of the object list after each of them), split_levels (the k at
+    which an object was replaced), core_first (the first pixel of every final object's core, in the order of the object
+    list), score (objects x pixels, None for one object) and free (the pixels assigned by score); no returned value
+    depends on it."""
     Dp = D.ravel()[pix]
     rows, cols = pix // W, pix % W
     r0, c0 = rows.min(), cols.min()
@@ -160,8 +168,13 @@ def deblend_component(pix, D, W, T, nthresh, minarea, cont):
     P = Dp.max()
     cflux = Dp.sum()
     objs = [(np.ones(len(pix), dtype=bool), T)]
+    if details is not None:
+        details.update(values=Dp, levels=[], nobj=[], split_levels=[], score=None, free=np.zeros(len(pix), dtype=bool))
     for k in range(1, nthresh):
         t = T * (P / T) ** (k / nthresh)
+        if details is not None:
+            details["levels"].append(t)
+            details["nobj"].append(len(objs))
         above = Dp > t
         if above.sum() < minarea:            # no node at this level or above
             break
@@ -182,8 +195,14 @@ def deblend_component(pix, D, W, T, nthresh, minarea, cont):
                 new += [(m, t) for m in sig]
             else:
                 new.append((om, ot))
+        if details is not None:
+            details["nobj"][-1] = len(new)
+            if len(new) != len(objs):
+                details["split_levels"].append(k)
         objs = new
     assign = np.full(len(pix), -1, dtype=np.int64)
+    if details is not None:
+        details["core_first"] = [int(pix[np.argmax(m)]) for m, _ in objs]
     if len(objs) == 1:
         assign[:] = 0
         return objs, assign
@@ -203,6 +222,8 @@ def deblend_component(pix, D, W, T, nthresh, minarea, cont):
         q = (syy * ex * ex - 2.0 * sxy * ex * ey + sxx * ey * ey) / det
         score[o] = A * np.exp(-0.5 * q)
     free = assign < 0
+    if details is not None:
+        details.update(score=score, free=free)
     assign[free] = np.argmax(score[:, free], axis=0)     # the first maximum: ties go to the earlier object
     return objs, assign
 
@@ -210,10 +231,13 @@ def deblend_component(pix, D, W, T, nthresh, minarea, cont):
 CAT_KEYS = ("npix", "peak", "flux", "x", "y", "parent")
 
 
-def detect(data, thresh=1.5, minarea=4, nthresh=64, cont=1e-5, filter_kernel=None, back_size=64, back_filter=3):
+def detect(data, thresh=1.5, minarea=4, nthresh=64, cont=1e-5, filter_kernel=None, back_size=64, back_filter=3,
+           details=None):
     """one field (H, W) -> dict with the maps back, rms, v, D, labels (raster index of the component's first pixel for
     the pixels of every component of >= minarea pixels, -1 elsewhere), globalrms and the catalog npix, peak, flux, x
-    (column), y (row), parent (the component's label); objects ordered by component, then by peak pixel"""
+    (column), y (row), parent (the component's label); objects ordered by component, then by peak pixel.  A list given
+    as details gains one dict per kept component: deblend_component's, plus pix, T, assign and peak_pixels (every object's
+    peak pixel, in the order of the object list; the catalogue's order is the sorted one)."""
     data = np.asarray(data, dtype=np.float64)
     H, W = data.shape
     bk = background(data, back_size, back_filter)
@@ -227,7 +251,8 @@ def detect(data, thresh=1.5, minarea=4, nthresh=64, cont=1e-5, filter_kernel=Non
         if len(pix) < minarea:
             continue
         labels[pix] = pix[0]
-        objs, assign = deblend_component(pix, D, W, T, nthresh, minarea, cont)
+        det = None if details is None else dict(pix=pix, T=T)
+        objs, assign = deblend_component(pix, D, W, T, nthresh, minarea, cont, details=det)
         rows = []
         for o in range(len(objs)):
             p = pix[assign == o]
@@ -241,6 +266,9 @@ def detect(data, thresh=1.5, minarea=4, nthresh=64, cont=1e-5, filter_kernel=Non
             else:
                 x, y = c.mean(), r.mean()
             rows.append((int(p[pk]), len(p), dp[pk], sv, x, y))
+        if det is not None:
+            det.update(peak_pixels=[e[0] for e in rows], assign=assign)
+            details.append(det)
         for _, n, peak, sv, x, y in sorted(rows, key=lambda e: e[0]):
             for key, val in zip(CAT_KEYS, (n, peak, sv, x, y, int(pix[0]))):
                 cat[key].append(val)

@@ -92,8 +92,8 @@ def significance(v, w, kernel, filter_type):
 
 
 def detect(data, weights, noise="absolute", filter_type="conv", thresh=1.5, minarea=4, nthresh=64, cont=1e-5,
-           filter_kernel=None, back_size=64, back_filter=3):
-    """detect_oracle.detect with the weighted rules; the D map holds S; gains bad_meshes"""
+           filter_kernel=None, back_size=64, back_filter=3, details=None):
+    """detect_oracle.detect with the weighted rules; the D map holds S; gains bad_meshes; details as there"""
     assert noise in ("absolute", "relative") and filter_type in ("conv", "matched")
     data = np.asarray(data, dtype=np.float64)
     w = np.asarray(weights, dtype=np.float64)
@@ -116,7 +116,8 @@ def detect(data, weights, noise="absolute", filter_type="conv", thresh=1.5, mina
         if len(pix) < minarea:
             continue
         labels[pix] = pix[0]
-        objs, assign = deblend_component(pix, S, W, T, nthresh, minarea, cont)
+        det = None if details is None else dict(pix=pix, T=T)
+        objs, assign = deblend_component(pix, S, W, T, nthresh, minarea, cont, details=det)
         rows = []
         for o in range(len(objs)):
             p = pix[assign == o]
@@ -130,6 +131,9 @@ def detect(data, weights, noise="absolute", filter_type="conv", thresh=1.5, mina
             else:
                 x, y = c.mean(), r.mean()
             rows.append((int(p[pk]), len(p), sp[pk], sv, x, y))
+        if det is not None:
+            det.update(peak_pixels=[e[0] for e in rows], assign=assign)
+            details.append(det)
         for _, n, peak, sv, x, y in sorted(rows, key=lambda e: e[0]):
             for key, val in zip(CAT_KEYS, (n, peak, sv, x, y, int(pix[0]))):
                 cat[key].append(val)
