@@ -50,6 +50,12 @@ class DvDetectWeights(C.Structure):
     _fields_ = [("weights", C.POINTER(C.c_double)), ("noise", C.c_int32), ("filter", C.c_int32)]
 
 
+class DvDetectBands(C.Structure):
+    """dv_detect_bands (include/debvader_hip.h)"""
+    _fields_ = [("bands", C.POINTER(C.c_int32)), ("k", C.c_int32), ("band_weights", C.POINTER(C.c_double)),
+                ("planes", C.POINTER(C.c_double)), ("noise", C.c_int32), ("filter", C.c_int32)]
+
+
 DETECT_NOISE = {"absolute": 0, "relative": 1}     # DV_DETECT_NOISE_*
 DETECT_FILTER = {"conv": 0, "matched": 1}         # DV_DETECT_FILTER_*
 
@@ -192,6 +198,9 @@ SIGNATURES = {
     "dv_scene_detect_weighted": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams), C.c_int64, _i64,
                                            _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d, _d, _d, _d, _i32,
                                            C.POINTER(DvDetectWeights), _i32]),
+    "dv_scene_detect_multiband": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams),
+                                            C.c_int64, _i64, _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d, _d, _d, _d, _d, _d, _i32,
+                                            C.POINTER(DvDetectBands), _d, _i32]),
     "dv_measure_params_default": (C.c_int, [C.POINTER(DvMeasureParams)]),
     "dv_scene_measure": (C.c_int, [_p, _f, _f, C.c_int64, C.c_int32, C.c_int32, C.POINTER(DvMeasureParams), _d, _d, _d, _i32,
                                    _i32]),
@@ -242,6 +251,7 @@ SIGNATURES = {
     "dv_field_set_detect": (C.c_int, [_p, C.POINTER(C.c_uint8), C.POINTER(DvDetectParams), C.c_int64, _i64, _i64, _d, _i32,
                                       _i32, _i32, _d, _d, _d, _d]),
     "dv_field_set_detect_weights": (C.c_int, [_p, _d, C.c_int32, C.c_int32]),
+    "dv_field_set_detect_bands": (C.c_int, [_p, _i32, C.c_int32, _d, _d, C.c_int32, C.c_int32]),
     "dv_field_set_pass": (C.c_int, [_p, _i32, _i32, _i64, C.c_int64, C.c_uint64, _d, _d]),
     "dv_field_set_read": (C.c_int, [_p, C.c_int32, _d]),
     "dv_field_set_close": (C.c_int, [_p]),

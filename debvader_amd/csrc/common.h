@@ -648,12 +648,37 @@ struct DetectDevSrc {
   int nb, band;
   const int32_t* which_h;
   const double* weights_dev = nullptr;   // (7z) planes [..][H][W] in the stack's numbering, read with a DetectWeights
+  const double* planes_dev = nullptr;    // (7za) planes [..][H][W][k] in the stack's numbering, read with a DetectBands
 };
+// detection on the inverse-variance combination of k bands: the selection, the spectral shape c [k] (null: all
+// 1.0), the planes [M][H][W][k] of a host call (null: none; a device source says with has_planes that its planes_dev are
+// meant), noise / filter as in DetectWeights, and the outputs only this path has: band_grms_h [M][k], bad_meshes_h [M][k],
+// Wt_h [M][H][W], all nullable.  back_h / rms_h of the call are then [M][H][W][k] and the v map (V) comes back through V_h.
+struct DetectBands {
+  const int32_t* bands;
+  int k;
+  const double* c;
+  const double* planes_h;
+  bool has_planes;
+  int noise, filter;
+  double* band_grms_h;
+  int32_t* bad_meshes_h;
+  double* V_h;
+  double* Wt_h;
+};
+// the argument checks of a DetectBands for fields of nb bands, before any GPU work (who: the caller's name in the message)
+int detect_bands_check(const char* who, const int32_t* bands, int k, const double* c, int nb, int noise, int filter);
 int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                      int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
                      int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
                      int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                     hipStream_t s, const DetectWeights* wq = nullptr);
+                     hipStream_t s, const DetectWeights* wq = nullptr, const DetectBands* mb = nullptr);
+// host fields [M][H][W][nb], interleaved, uploaded as they are and gathered on the GPU
+int scene_detect_multiband(const double* fields_h, int nb, const DetectBands& mb, int M, int H, int W, double thresh, double cont,
+                           int minarea, int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
+                           int64_t workspace_bytes, int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h,
+                           int32_t* field_h, int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h,
+                           double* y_h, double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s);
 
 // Strip form of the stride-1 3x3 gather-GEMM for the 32-channel high-resolution layers (gconv_strip.hip)
 struct GStripParams {

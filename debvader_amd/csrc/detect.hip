@@ -24,6 +24,9 @@
 // With a per-pixel noise map and a mask (tests/detect_weighted_oracle.py) kernels 1, 2, 4 and 5 run
 // in their WEIGHTED instantiations: only counting pixels (0 < w < inf) enter the meshes, bad meshes are filled from their
 // nearest good ones, v is 0 under the mask and D holds the significance S; kernels 6 to 8 read S where they read D.
+// On the inverse-variance combination of several bands (tests/detect_multiband_oracle.py)
+// bands_gather_kernel writes the selected planes of the interleaved fields, kernels 1 to 3 run over fields x bands planes,
+// multiband_pixel_kernel stands where kernel 4 stood and writes the combined v and its weight, and kernel 5 runs WEIGHTED on them.
 // fp64 VALU and integer work; nothing here has a matrix shape for MFMA.
 #include "common.h"
 
@@ -358,6 +361,73 @@ __global__ __launch_bounds__(DT) void bkg_pixel_kernel(const double* __restrict_
   else v[e] = data[e] - b;
   if (back) back[e] = b;
   if (rms) rms[e] = spline_eval(gr + row * nx, gr2 + row * nx, 1, nx, u);
+}
+
+// Multi-band detection (7za): one thread per pixel, the k selected bands in an inner loop; plane f * k + j is band j of field
+// f in data, pl (the planes P, PLANES only), the row splines and bgrms.  Per band the two splines as bkg_pixel_kernel
+// evaluates them, v_j = data_j - back_j, w_j = 1 / rms^2 | P / rms^2 | P (ABSOLUTE); the band counts iff 0 < w_j < inf, with
+// planes also 0 < P_j < inf, and it has a good mesh in the field (bgrms not NaN).  num = sum (c_j w_j) v_j and
+// Wt = sum (c_j c_j) w_j over the counting bands in scalar accumulators, V = 0 | v_j / c_j | num / Wt for 0 | 1 | more of
+// them.  A value under a band that does not count is not read.  back / rms [..][k] only when the caller wants the maps; with
+// ABSOLUTE and no rms map the rms splines are not evaluated (bkg_row_kernel did not make them).
+template <bool PLANES, bool ABSOLUTE>
+__global__ __launch_bounds__(DT) void multiband_pixel_kernel(const double* __restrict__ data, const double* __restrict__ pl,
+                                                             long total, int H, int W, int k, int nx, int bs,
+                                                             const double* __restrict__ gb, const double* __restrict__ gb2,
+                                                             const double* __restrict__ gr, const double* __restrict__ gr2,
+                                                             const double* __restrict__ bgrms, const double* __restrict__ cw,
+                                                             double* __restrict__ V, double* __restrict__ Wt,
+                                                             double* __restrict__ back, double* __restrict__ rms) {
+  const long e = (long)blockIdx.x * DT + threadIdx.x;
+  if (e >= total) return;
+  const long HW = (long)H * W;
+  const long f = e / HW;
+  const long p = e - f * HW;
+  const int r = (int)(p / W), c = (int)(p - (long)r * W);
+  const double u = (c + 0.5) / bs - 0.5;
+  const bool need_rms = !ABSOLUTE || rms != nullptr;
+  double num = 0.0, wsum = 0.0, v1 = 0.0, c1 = 1.0;
+  int n = 0;
+  for (int j = 0; j < k; ++j) {
+    const long plane = f * k + j;
+    const long row = plane * H + r;
+    const double b = spline_eval(gb + row * nx, gb2 + row * nx, 1, nx, u);
+    const double sg = need_rms ? spline_eval(gr + row * nx, gr2 + row * nx, 1, nx, u) : 0.0;
+    if (back) back[e * k + j] = b;
+    if (rms) rms[e * k + j] = sg;
+    const double P = PLANES ? pl[plane * HW + p] : 1.0;
+    const double w = ABSOLUTE ? P : P / (sg * sg);
+    const double g = bgrms[plane];
+    if (g == g && counts(w) && (!PLANES || counts(P))) {
+      const double cj = cw[j];
+      const double v = data[plane * HW + p] - b;
+      num += (cj * w) * v;
+      wsum += (cj * cj) * w;
+      v1 = v;
+      c1 = cj;
+      ++n;
+    }
+  }
+  V[e] = n == 0 ? 0.0 : (n == 1 ? v1 / c1 : num / wsum);
+  Wt[e] = n == 0 ? 0.0 : wsum;
+}
+
+// (7za) the diagnostic globalrms of the combination per field, 1 / sqrt(sum (c_j c_j) / (g_j g_j)) over the bands with a good
+// mesh, j ascending; NaN for a field without one (filter_kernel then puts nothing above the threshold)
+__global__ __launch_bounds__(DT) void multiband_grms_kernel(const double* __restrict__ bgrms, const double* __restrict__ cw,
+                                                            int m, int k, double* __restrict__ fgrms) {
+  const int f = blockIdx.x * DT + threadIdx.x;
+  if (f >= m) return;
+  double acc = 0.0;
+  bool any = false;
+  for (int j = 0; j < k; ++j) {
+    const double g = bgrms[(long)f * k + j];
+    if (g == g) {
+      acc += (cw[j] * cw[j]) / (g * g);
+      any = true;
+    }
+  }
+  fgrms[f] = any ? 1.0 / sqrt(acc) : NAN;
 }
 
 // D = correlation of v with kn (normalised taps), zero outside the field; par = own index where D > T, T = thresh * globalrms
@@ -840,11 +910,19 @@ inline unsigned nblk(long total) { return (unsigned)((total + DT - 1) / DT); }
 
 // device bytes one H x W field can need in a launch: deblend scratch and catalog slots sized as if every pixel lay in
 // a component
-long field_bytes(long H, long W, long ny, long nx, int minarea, bool maps, bool weighted) {
+// (7za) k > 0: k data planes, k planes of P when given, k x the mesh grids and row splines, the combined weight Wt, and for a
+// host source the interleaved staging lines of max(nb, k) values per pixel
+long field_bytes(long H, long W, long ny, long nx, int minarea, bool maps, bool weighted, int k = 0, bool planes = false,
+                 int stage = 0) {
   const long HW = H * W, capn = HW / minarea + 1;
   long b = HW * (8 + 8 + 8 + 4 * 7);                          // data v D | par lab area cmin cmax rmax lidx
   if (maps) b += HW * (8 + 8 + 4);                            // back rms labels
   if (weighted) b += HW * 8 + 4;                              // the weight plane, the bad-mesh count
+  if (k > 0) {
+    b += HW * 8 * (k - 1) + HW * 8 + (planes ? HW * 8 * k : 0) + HW * 8 * stage;
+    if (maps) b += HW * (8 + 8) * (k - 1);
+    b += (k - 1) * (H * nx * 4 * 8 + ny * nx * 6 * 8) + (long)k * (8 + 4) + 8;   // ... band globalrms, bad meshes, globalrms
+  }
   b += H * nx * 4 * 8 + ny * nx * 6 * 8;                      // row splines, mesh grids
   b += capn * 5 * 4;                                          // component table
   b += HW * (8 + 6 * 4) + capn * ((2 + OBJ_D) * 8 + 3 * 4);   // deblend scratch
@@ -861,26 +939,49 @@ __global__ __launch_bounds__(DT) void band_gather_kernel(const double* __restric
   data[(long)blockIdx.y * HW + e] = fields[(f * HW + e) * nb + band];
 }
 
+// (7za) plane blockIdx.y * k + j of data = band bands[j] of field which[blockIdx.y] (null: blockIdx.y itself) of a stack of
+// [HW][nb] fields: one pass in which every pixel's line is read once, for the k selected bands
+__global__ __launch_bounds__(DT) void bands_gather_kernel(const double* __restrict__ fields, long HW, int nb,
+                                                          const int* __restrict__ bands, int k, const int* __restrict__ which,
+                                                          double* __restrict__ data) {
+  const long e = (long)blockIdx.x * DT + threadIdx.x;
+  if (e >= HW) return;
+  const long f = which ? which[blockIdx.y] : blockIdx.y;
+  const double* line = fields + (f * HW + e) * nb;
+  for (int j = 0; j < k; ++j) data[((long)blockIdx.y * k + j) * HW + e] = line[bands[j]];
+}
+
 // the device buffers of detect_impl.  DetectWork: the workspace of one launch's fields (chunk fields of H x W pixels on
 // ny x nx background meshes); back / rms / labout exist only when the caller wants those maps, wdev (the nwhich field numbers
 // of a device source) only when the fields come from device memory.
 struct DetectWork {
   DevBuf<double> data, v, D, mb, mr, fbk, frm, d2b, d2r, gb, gb2, gr, gr2, grms, kdev, cdev, back, rms, wt;
   DevBuf<int> par, lab, area, cmin, cmax, rmax, lidx, table, ncomp, labout, wdev, nbad;
+  // (7za) bands > 0: everything per band (data, wt, the mesh grids, the row splines, grms, nbad, the back / rms maps) holds
+  // bands planes per field, plane f * bands + j; cw = Wt, fgrms = the fields' globalrms, stage = the interleaved lines of a
+  // host source, bsel = the band numbers then 0 .. bands - 1, cband = the c_j
+  DevBuf<double> cw, fgrms, stage, cband;
+  DevBuf<int> bsel;
   int alloc(int chunk, int H, int W, int ny, int nx, long ccap, size_t ktaps, size_t ccoef, bool want_back, bool want_rms,
-            bool want_labels, int nwhich, bool weighted) {
-    const size_t px = (size_t)chunk * H * W, grid = (size_t)chunk * ny * nx, rows = (size_t)chunk * H * nx;
-    for (DevBuf<double>* b : {&data, &v, &D}) DV_TRY(b->alloc(px));
+            bool want_labels, int nwhich, bool weighted, int bands = 0, int stage_nb = 0) {
+    const size_t kk = bands > 0 ? (size_t)bands : 1;
+    const size_t px = (size_t)chunk * H * W, grid = kk * chunk * ny * nx, rows = kk * chunk * H * nx;
+    DV_TRY(data.alloc(kk * px));
+    for (DevBuf<double>* b : {&v, &D}) DV_TRY(b->alloc(px));
     for (DevBuf<int>* b : {&par, &lab, &area, &cmin, &cmax, &rmax, &lidx}) DV_TRY(b->alloc(px));
     for (DevBuf<double>* b : {&mb, &mr, &fbk, &frm, &d2b, &d2r}) DV_TRY(b->alloc(grid));
     for (DevBuf<double>* b : {&gb, &gb2, &gr, &gr2}) DV_TRY(b->alloc(rows));
-    DV_TRY(grms.alloc((size_t)chunk)); DV_TRY(ncomp.alloc((size_t)chunk)); DV_TRY(table.alloc((size_t)chunk * ccap * 5));
+    DV_TRY(grms.alloc(kk * chunk)); DV_TRY(ncomp.alloc((size_t)chunk)); DV_TRY(table.alloc((size_t)chunk * ccap * 5));
     DV_TRY(kdev.alloc(ktaps)); DV_TRY(cdev.alloc(ccoef));
-    if (want_back) DV_TRY(back.alloc(px));
-    if (want_rms) DV_TRY(rms.alloc(px));
+    if (want_back) DV_TRY(back.alloc(kk * px));
+    if (want_rms) DV_TRY(rms.alloc(kk * px));
     if (want_labels) DV_TRY(labout.alloc(px));
     if (nwhich > 0) DV_TRY(wdev.alloc((size_t)nwhich));
-    if (weighted) { DV_TRY(wt.alloc(px)); DV_TRY(nbad.alloc((size_t)chunk)); }   // (7z) the weight planes, the bad meshes
+    if (weighted) { DV_TRY(wt.alloc(kk * px)); DV_TRY(nbad.alloc(kk * chunk)); }   // (7z) the weight planes, the bad meshes
+    if (bands > 0) {
+      DV_TRY(cw.alloc(px)); DV_TRY(fgrms.alloc((size_t)chunk)); DV_TRY(bsel.alloc(2 * kk)); DV_TRY(cband.alloc(kk));
+      if (stage_nb > 0) DV_TRY(stage.alloc(px * stage_nb));
+    }
     return OK;
   }
 };
@@ -901,8 +1002,10 @@ struct DeblendScratch {
 
 // the detector: the fields come from the host (fields_h) or, with `dev`, from a stack that lies in device memory; with `wq`
 // the weighted rules of DESIGN 7z, the planes coming from where the fields come from
-int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWeights* wq, int M, int H, int W, double thresh,
-                double cont, int minarea,
+// ; with `mb` the multi-band source of DESIGN 7za (wq null): the fields are interleaved [M][H][W][nb] (nb_h of a host source),
+// back_h / rms_h are [M][H][W][k]
+int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWeights* wq, const DetectBands* mb, int nb_h, int M,
+                int H, int W, double thresh, double cont, int minarea,
                 int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
                 int64_t workspace_bytes, int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h,
                 int32_t* field_h, int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h,
@@ -919,6 +1022,24 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
     set_error("scene_detect: bad arguments");
     return E_INVALID;
   }
+  const int nbk = mb ? mb->k : 0, nb_src = dev ? dev->nb : nb_h;
+  if (mb) {
+    if (wq) {
+      set_error("scene_detect: single-band weights and a band selection exclude each other");
+      return E_INVALID;
+    }
+    DV_TRY(detect_bands_check("scene_detect_multiband", mb->bands, mb->k, mb->c, nb_src, mb->has_planes ? mb->noise : 0,
+                              mb->filter));
+    if (mb->has_planes && (dev ? !dev->planes_dev : !mb->planes_h)) {
+      set_error("scene_detect_multiband: planes announced but not given");
+      return E_INVALID;
+    }
+    if (!(thresh > 0.0)) {
+      set_error("scene_detect_multiband: the threshold is in units of the combined pixel's sigma and must be > 0 (got %g)",
+                thresh);
+      return E_INVALID;
+    }
+  }
   if (wq) {
     if (dev ? !dev->weights_dev : !wq->weights_h) {
       set_error("scene_detect: weighted detection without weights");
@@ -934,7 +1055,8 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
       return E_INVALID;
     }
   }
-  const bool absolute = wq && wq->noise == 0, matched = wq && wq->filter == 1;
+  const bool mplanes = mb && mb->has_planes, mabs = mplanes && mb->noise == 0;
+  const bool absolute = mb || (wq && wq->noise == 0), matched = mb ? mb->filter == 1 : (wq && wq->filter == 1);
   if (kernel_h && (kh < 1 || kw < 1 || kh > KMAX || kw > KMAX || (kh & 1) == 0 || (kw & 1) == 0)) {
     set_error("scene_detect: the filter kernel must have odd sizes of 1 .. %d (got %d x %d)", KMAX, kh, kw);
     return E_INVALID;
@@ -962,8 +1084,9 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
 
   const int ny = (H + back_size - 1) / back_size, nx = (W + back_size - 1) / back_size;
   const bool maps = back_h || rms_h || D_h || labels_h;
+  const int stage_nb = (mb && !dev) ? std::max(nb_src, nbk) : 0;
   const long cap_ws = workspace_bytes > 0 ? (long)workspace_bytes : (4L << 30);
-  const long per_field = field_bytes(H, W, ny, nx, minarea, maps, wq != nullptr);
+  const long per_field = field_bytes(H, W, ny, nx, minarea, maps, wq != nullptr, nbk, mplanes, stage_nb);
   if (M > 0 && per_field > cap_ws) {
     set_error("scene_detect: one %d x %d field needs up to %ld bytes of device workspace, above the cap of %ld bytes per "
               "launch", H, W, per_field, cap_ws);
@@ -984,17 +1107,53 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
   DetectWork w;
   if (chunk > 0) {
     DV_TRY(w.alloc(chunk, H, W, ny, nx, ccap, kn.size(), cco.size(), back_h != nullptr, rms_h != nullptr,
-                   labels_h != nullptr, dev ? M : 0, wq != nullptr));
+                   labels_h != nullptr, dev ? M : 0, wq != nullptr || mplanes, nbk, stage_nb));
     DV_HIP(hipMemcpyAsync(w.kdev, kn.data(), kn.size() * sizeof(double), hipMemcpyHostToDevice, s));
     DV_HIP(hipMemcpyAsync(w.cdev, cco.data(), cco.size() * sizeof(double), hipMemcpyHostToDevice, s));
     if (dev) DV_HIP(hipMemcpyAsync(w.wdev, dev->which_h, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
+    if (mb) {
+      std::vector<int> sel((size_t)2 * nbk);
+      std::vector<double> cb((size_t)nbk, 1.0);
+      for (int j = 0; j < nbk; ++j) {
+        sel[j] = mb->bands[j];
+        sel[nbk + j] = j;
+        if (mb->c) cb[j] = mb->c[j];
+      }
+      DV_HIP(hipMemcpyAsync(w.bsel, sel.data(), sel.size() * sizeof(int), hipMemcpyHostToDevice, s));
+      DV_HIP(hipMemcpyAsync(w.cband, cb.data(), cb.size() * sizeof(double), hipMemcpyHostToDevice, s));
+      DV_HIP(hipStreamSynchronize(s));                  // (sel and cb leave scope)
+    }
   }
   std::vector<int> h_ncomp((size_t)std::max(chunk, 1));
   std::vector<int> h_tab;
   for (int f0 = 0; f0 < M; f0 += chunk) {
     const int m = std::min(chunk, M - f0);
     const long px = (long)m * HW;
-    if (dev) {
+    const int mk = m * std::max(nbk, 1);                  // planes of the launch
+    if (mb) {
+      const dim3 ggath(nblk(HW), (unsigned)m);
+      if (dev) {
+        hipLaunchKernelGGL(bands_gather_kernel, ggath, dim3(DT), 0, s, dev->fields_dev, HW, nb_src, w.bsel, nbk, w.wdev + f0,
+                           w.data);
+        DV_HIP(hipGetLastError());
+        if (mplanes) {
+          hipLaunchKernelGGL(bands_gather_kernel, ggath, dim3(DT), 0, s, dev->planes_dev, HW, nbk, w.bsel + nbk, nbk,
+                             w.wdev + f0, w.wt);
+          DV_HIP(hipGetLastError());
+        }
+      } else {
+        DV_HIP(hipMemcpyAsync(w.stage, fields_h + (size_t)f0 * HW * nb_src, (size_t)px * nb_src * sizeof(double),
+                              hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(bands_gather_kernel, ggath, dim3(DT), 0, s, w.stage, HW, nb_src, w.bsel, nbk, nullptr, w.data);
+        DV_HIP(hipGetLastError());
+        if (mplanes) {
+          DV_HIP(hipMemcpyAsync(w.stage, mb->planes_h + (size_t)f0 * HW * nbk, (size_t)px * nbk * sizeof(double),
+                                hipMemcpyHostToDevice, s));
+          hipLaunchKernelGGL(bands_gather_kernel, ggath, dim3(DT), 0, s, w.stage, HW, nbk, w.bsel + nbk, nbk, nullptr, w.wt);
+          DV_HIP(hipGetLastError());
+        }
+      }
+    } else if (dev) {
       hipLaunchKernelGGL(band_gather_kernel, dim3(nblk(HW), (unsigned)m), dim3(DT), 0, s, dev->fields_dev, HW, dev->nb,
                          dev->band, w.wdev + f0, w.data);
       DV_HIP(hipGetLastError());
@@ -1008,31 +1167,50 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
       if (wq)
         DV_HIP(hipMemcpyAsync(w.wt, wq->weights_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    const dim3 gmesh((unsigned)((long)m * ny * nx)), gfilt((unsigned)((W + FT - 1) / FT), (unsigned)((H + FT - 1) / FT),
+    const dim3 gmesh((unsigned)((long)mk * ny * nx)), gfilt((unsigned)((W + FT - 1) / FT), (unsigned)((H + FT - 1) / FT),
                                                             (unsigned)m);
-    if (wq) {
+    if (wq || mplanes) {
       hipLaunchKernelGGL(bkg_mesh_kernel<true>, gmesh, dim3(DT), 0, s, w.data, w.wt, H, W, back_size, ny, nx, w.mb, w.mr);
       DV_HIP(hipGetLastError());
-      hipLaunchKernelGGL(bkg_grid_kernel<true>, dim3((unsigned)m), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev,
+      hipLaunchKernelGGL(bkg_grid_kernel<true>, dim3((unsigned)mk), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev,
                          w.fbk, w.frm, w.d2b, w.d2r, w.grms, w.nbad);
     } else {
       hipLaunchKernelGGL(bkg_mesh_kernel<false>, gmesh, dim3(DT), 0, s, w.data, nullptr, H, W, back_size, ny, nx, w.mb, w.mr);
       DV_HIP(hipGetLastError());
-      hipLaunchKernelGGL(bkg_grid_kernel<false>, dim3((unsigned)m), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev,
+      hipLaunchKernelGGL(bkg_grid_kernel<false>, dim3((unsigned)mk), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev,
                          w.fbk, w.frm, w.d2b, w.d2r, w.grms, nullptr);
     }
     DV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bkg_row_kernel, dim3(nblk((long)m * H)), dim3(DT), 0, s, w.fbk, w.frm, w.d2b, w.d2r, m, H, ny, nx,
-                       back_size, w.rms ? 1 : 0, w.cdev, w.gb, w.gb2, w.gr, w.gr2);
+    hipLaunchKernelGGL(bkg_row_kernel, dim3(nblk((long)mk * H)), dim3(DT), 0, s, w.fbk, w.frm, w.d2b, w.d2r, mk, H, ny, nx,
+                       back_size, (w.rms || (mb && !mabs)) ? 1 : 0, w.cdev, w.gb, w.gb2, w.gr, w.gr2);
     DV_HIP(hipGetLastError());
-    if (wq)
+    if (mb) {
+      hipLaunchKernelGGL(multiband_grms_kernel, dim3(nblk(m)), dim3(DT), 0, s, w.grms, w.cband, m, nbk, w.fgrms);
+      DV_HIP(hipGetLastError());
+      if (mabs)
+        hipLaunchKernelGGL((multiband_pixel_kernel<true, true>), dim3(nblk(px)), dim3(DT), 0, s, w.data, w.wt, px, H, W, nbk, nx,
+                           back_size, w.gb, w.gb2, w.gr, w.gr2, w.grms, w.cband, w.v, w.cw, w.back, w.rms);
+      else if (mplanes)
+        hipLaunchKernelGGL((multiband_pixel_kernel<true, false>), dim3(nblk(px)), dim3(DT), 0, s, w.data, w.wt, px, H, W, nbk, nx,
+                           back_size, w.gb, w.gb2, w.gr, w.gr2, w.grms, w.cband, w.v, w.cw, w.back, w.rms);
+      else
+        hipLaunchKernelGGL((multiband_pixel_kernel<false, false>), dim3(nblk(px)), dim3(DT), 0, s, w.data, nullptr, px, H, W, nbk,
+                           nx, back_size, w.gb, w.gb2, w.gr, w.gr2, w.grms, w.cband, w.v, w.cw, w.back, w.rms);
+    } else if (wq)
       hipLaunchKernelGGL(bkg_pixel_kernel<true>, dim3(nblk(px)), dim3(DT), 0, s, w.data, w.wt, px, W, nx, back_size, w.gb,
                          w.gb2, w.gr, w.gr2, w.v, w.back, w.rms);
     else
       hipLaunchKernelGGL(bkg_pixel_kernel<false>, dim3(nblk(px)), dim3(DT), 0, s, w.data, nullptr, px, W, nx, back_size, w.gb,
                          w.gb2, w.gr, w.gr2, w.v, w.back, w.rms);
     DV_HIP(hipGetLastError());
-    if (matched)
+    if (mb) {                                             // (7za) V, Wt in the place of v, w; absolute noise
+      if (matched)
+        hipLaunchKernelGGL((filter_kernel<true, true>), gfilt, dim3(DT), 0, s, w.v, w.cw, H, W, w.kdev, kh, kw, w.fgrms, thresh,
+                           1, w.D, w.par);
+      else
+        hipLaunchKernelGGL((filter_kernel<true, false>), gfilt, dim3(DT), 0, s, w.v, w.cw, H, W, w.kdev, kh, kw, w.fgrms, thresh,
+                           1, w.D, w.par);
+    } else if (matched)
       hipLaunchKernelGGL((filter_kernel<true, true>), gfilt, dim3(DT), 0, s, w.v, w.wt, H, W, w.kdev, kh, kw, w.grms, thresh,
                          absolute ? 1 : 0, w.D, w.par);
     else if (wq)
@@ -1058,12 +1236,23 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
       hipLaunchKernelGGL(cc_labels_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.lab, w.area, px, HW, minarea, w.labout);
       DV_HIP(hipGetLastError());
     }
-    DV_HIP(hipMemcpyAsync(globalrms_h + f0, w.grms, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    DV_HIP(hipMemcpyAsync(globalrms_h + f0, mb ? w.fgrms : w.grms, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (mb) {
+      const size_t o = (size_t)f0 * nbk;
+      if (mb->band_grms_h) DV_HIP(hipMemcpyAsync(mb->band_grms_h + o, w.grms, (size_t)mk * 8, hipMemcpyDeviceToHost, s));
+      if (mb->bad_meshes_h) {
+        if (mplanes) DV_HIP(hipMemcpyAsync(mb->bad_meshes_h + o, w.nbad, (size_t)mk * 4, hipMemcpyDeviceToHost, s));
+        else std::fill(mb->bad_meshes_h + o, mb->bad_meshes_h + o + mk, 0);
+      }
+      if (mb->V_h) DV_HIP(hipMemcpyAsync(mb->V_h + (size_t)f0 * HW, w.v, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+      if (mb->Wt_h) DV_HIP(hipMemcpyAsync(mb->Wt_h + (size_t)f0 * HW, w.cw, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+    }
     DV_HIP(hipMemcpyAsync(h_ncomp.data(), w.ncomp, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
     if (wq && wq->bad_meshes_h)
       DV_HIP(hipMemcpyAsync(wq->bad_meshes_h + f0, w.nbad, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (back_h) DV_HIP(hipMemcpyAsync(back_h + (size_t)f0 * HW, w.back, (size_t)px * 8, hipMemcpyDeviceToHost, s));
-    if (rms_h) DV_HIP(hipMemcpyAsync(rms_h + (size_t)f0 * HW, w.rms, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+    const size_t bpx = (size_t)px * std::max(nbk, 1);     // (7za: [..][k] maps)
+    if (back_h) DV_HIP(hipMemcpyAsync(back_h + (size_t)f0 * HW * std::max(nbk, 1), w.back, bpx * 8, hipMemcpyDeviceToHost, s));
+    if (rms_h) DV_HIP(hipMemcpyAsync(rms_h + (size_t)f0 * HW * std::max(nbk, 1), w.rms, bpx * 8, hipMemcpyDeviceToHost, s));
     if (D_h) DV_HIP(hipMemcpyAsync(D_h + (size_t)f0 * HW, w.D, (size_t)px * 8, hipMemcpyDeviceToHost, s));
     if (labels_h) DV_HIP(hipMemcpyAsync(labels_h + (size_t)f0 * HW, w.labout, (size_t)px * 4, hipMemcpyDeviceToHost, s));
     DV_HIP(hipStreamSynchronize(s));
@@ -1162,7 +1351,7 @@ int scene_detect(const double* fields_h, int M, int H, int W, double thresh, dou
     set_error("scene_detect: bad arguments");
     return E_INVALID;
   }
-  return detect_impl(fields_h, nullptr, wq, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
+  return detect_impl(fields_h, nullptr, wq, nullptr, 0, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
                      workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
                      y_h, back_h, rms_h, D_h, labels_h, s);
 }
@@ -1171,10 +1360,51 @@ int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh
                      int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
                      int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
                      int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                     hipStream_t s, const DetectWeights* wq) {
-  return detect_impl(nullptr, &src, wq, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
+                     hipStream_t s, const DetectWeights* wq, const DetectBands* mb) {
+  return detect_impl(nullptr, &src, wq, mb, 0, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
                      workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
                      y_h, nullptr, nullptr, nullptr, nullptr, s);
+}
+
+int detect_bands_check(const char* who, const int32_t* bands, int k, const double* c, int nb, int noise, int filter) {
+  if (nb < 1 || k < 1 || k > nb || !bands) {
+    set_error("%s: %d band(s) selected, 1 .. %d of the fields' must be given", who, k, nb);
+    return E_INVALID;
+  }
+  for (int j = 0; j < k; ++j) {
+    if (bands[j] < 0 || bands[j] >= nb) {
+      set_error("%s: band %d is outside the fields' %d band(s)", who, bands[j], nb);
+      return E_INVALID;
+    }
+    for (int i = 0; i < j; ++i)
+      if (bands[i] == bands[j]) {
+        set_error("%s: band %d is given twice", who, bands[j]);
+        return E_INVALID;
+      }
+    if (c && !(c[j] > 0.0 && std::isfinite(c[j]))) {
+      set_error("%s: band weight %d must be finite and > 0 (got %g)", who, j, c[j]);
+      return E_INVALID;
+    }
+  }
+  if ((noise != 0 && noise != 1) || (filter != 0 && filter != 1)) {
+    set_error("%s: noise must be 0 (absolute) or 1 (relative) and filter 0 (conv) or 1 (matched), got %d, %d", who, noise, filter);
+    return E_INVALID;
+  }
+  return OK;
+}
+
+int scene_detect_multiband(const double* fields_h, int nb, const DetectBands& mb, int M, int H, int W, double thresh, double cont,
+                           int minarea, int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
+                           int64_t workspace_bytes, int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h,
+                           int32_t* field_h, int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h,
+                           double* y_h, double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s) {
+  if (!fields_h) {
+    set_error("scene_detect_multiband: bad arguments");
+    return E_INVALID;
+  }
+  return detect_impl(fields_h, nullptr, nullptr, &mb, nb, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter,
+                     kernel_h, kh, kw, workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h,
+                     flux_h, x_h, y_h, back_h, rms_h, D_h, labels_h, s);
 }
 
 }  // namespace dv

@@ -584,6 +584,12 @@ struct dv_field_set {
   // takes the weighted path with dnoise / dfilter
   dv::DevBuf<double> dweights;
   int dnoise = 0, dfilter = 0;
+  // the detector's band selection (dv_field_set_detect_bands): while dbands is not empty, dv_field_set_detect
+  // takes the multi-band path with the c_j in dbw, the planes [M][F][F][k] in dplanes (if any) and dbnoise / dbfilter
+  std::vector<int32_t> dbands;
+  std::vector<double> dbw;
+  dv::DevBuf<double> dplanes;
+  int dbnoise = 0, dbfilter = 0;
   dv::StampTables tab;                           // the per-stamp tables of a pass, kept between passes and grown on demand
   std::vector<double> fmse_h;                     // host side of fmse
   // the catalogue of the measured passes (dv_field_set_pass_measure).  Resident rows: {shape[5], status,
@@ -644,7 +650,7 @@ struct dv_field_set {
 
 static void field_set_release(dv_field_set* fs) {
   for (dv::DevBuf<double>* b : {&fs->base, &fs->work, &fs->next, &fs->fin, &fs->mean, &fs->stddev, &fs->mse_part, &fs->fmse,
-                                &fs->dweights, &fs->rshape, &fs->rsums, &fs->cflux, &fs->cferr, &fs->cblend})
+                                &fs->dweights, &fs->dplanes, &fs->rshape, &fs->rsums, &fs->cflux, &fs->cferr, &fs->cblend})
     b->reset();
   for (dv::DevBuf<int>* b : {&fs->rstatus, &fs->rplaces, &fs->rfield, &fs->citers, &fs->cnpix}) b->reset();
   fs->nrows = fs->rcap = 0;
@@ -4127,6 +4133,24 @@ int dv_scene_detect_weighted(dv_ctx* c, const double* fields, int32_t M, int32_t
                       peak, flux, x, y, back, rms, D, labels, c->stream, &wq);
 }
 
+int dv_scene_detect_multiband(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, int32_t nb,
+                              const dv_detect_params* p, int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms,
+                              int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux, double* x, double* y,
+                              double* back, double* rms, double* V, double* Wt, double* D, int32_t* labels,
+                              const dv_detect_bands* b, double* band_globalrms, int32_t* bad_meshes) {
+  if (!c || !p) return DV_E_INVALID;
+  if (!b) {
+    set_error("dv_scene_detect_multiband: the band selection must be given");
+    return DV_E_INVALID;
+  }
+  DV_HIP(hipSetDevice(c->device));
+  const DetectBands mb{b->bands, b->k, b->band_weights, b->planes, b->planes != nullptr, b->noise, b->filter, band_globalrms,
+                       bad_meshes, V, Wt};
+  return scene_detect_multiband(fields, nb, mb, M, H, W, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size,
+                                p->back_filter, p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, offsets, globalrms,
+                                field, parent, npix, peak, flux, x, y, back, rms, D, labels, c->stream);
+}
+
 int dv_ctx_allreduce_host(dv_ctx* c, float* buf, int32_t n) {
   if (!c || !buf || n < 0 || n > 4096) return DV_E_INVALID;
   if (!c->comm || n == 0) return DV_OK;
@@ -6265,7 +6289,8 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
                         double* flux, double* x, double* y) {
   DV_TRY(field_set_live(fs, "dv_field_set_detect"));
   if (!p || !n_out || !offsets || !globalrms) return DV_E_INVALID;
-  if (fs->nb < 3) {
+  const bool multi = !fs->dbands.empty();
+  if (!multi && fs->nb < 3) {
     set_error("dv_field_set_detect: detection reads band 2, the fields have %d band(s)", fs->nb);
     return DV_E_INVALID;
   }
@@ -6276,10 +6301,16 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
   std::vector<int64_t> off((size_t)Ma + 1, 0);
   std::vector<double> grms((size_t)std::max(Ma, 1), 0.0);
   DV_HIP(hipSetDevice(fs->m->ctx->device));
-  DetectDevSrc src{fs->work, fs->nb, 2, act.data(), fs->dweights};
+  DetectDevSrc src{fs->work, fs->nb, multi ? 0 : 2, act.data(), fs->dweights, fs->dplanes};
   const DetectWeights wq{nullptr, fs->dnoise, fs->dfilter, nullptr};
+  const DetectBands mb{fs->dbands.data(), (int)fs->dbands.size(), fs->dbw.data(), nullptr, (bool)fs->dplanes, fs->dbnoise,
+                       fs->dbfilter, nullptr, nullptr, nullptr, nullptr};
   *n_out = 0;
-  if (Ma > 0)
+  if (Ma > 0 && multi)
+    DV_TRY(scene_detect_dev(src, Ma, fs->F, fs->F, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
+                          p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, off.data(), grms.data(), field, parent,
+                          npix, peak, flux, x, y, fs->m->ctx->stream, nullptr, &mb));
+  else if (Ma > 0)
     DV_TRY(scene_detect_dev(src, Ma, fs->F, fs->F, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
                           p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, off.data(), grms.data(), field, parent,
                           npix, peak, flux, x, y, fs->m->ctx->stream, fs->dweights ? &wq : nullptr));
@@ -6297,10 +6328,66 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
   return DV_OK;
 }
 
+int dv_field_set_detect_bands(dv_field_set* fs, const int32_t* bands, int32_t k, const double* band_weights,
+                              const double* planes, int32_t noise, int32_t filter) {
+  DV_TRY(field_set_live(fs, "dv_field_set_detect_bands"));
+  DV_HIP(hipSetDevice(fs->m->ctx->device));
+  hipStream_t s = fs->m->ctx->stream;
+  if (k == 0) {                                 // drop the selection: dv_field_set_detect reads band 2 again
+    DV_HIP(hipStreamSynchronize(s));
+    fs->dplanes.reset();
+    fs->dbands.clear();
+    fs->dbw.clear();
+    return DV_OK;
+  }
+  if (fs->dweights) {
+    set_error("dv_field_set_detect_bands: the set holds single-band planes of dv_field_set_detect_weights; drop them first");
+    return DV_E_INVALID;
+  }
+  DV_TRY(detect_bands_check("dv_field_set_detect_bands", bands, k, band_weights, fs->nb, planes ? noise : 0, filter));
+  const size_t n = (size_t)fs->M * fs->F * fs->F * (size_t)k;
+  if (!planes) {
+    DV_HIP(hipStreamSynchronize(s));
+    fs->dplanes.reset();
+  } else {
+    if (!fs->dplanes || fs->dbands.size() != (size_t)k) {
+      // counted like the set itself: against free memory less the detector's workspace and the per-stamp tables (planes of
+      // another k that the set holds are not counted as free: a refusal leaves them in place)
+      const size_t reserve = std::min<size_t>((size_t)4 << 30, (size_t)fs->M * fs->F * fs->F * 128) + ((size_t)64 << 20);
+      size_t budget = 0;
+      DV_TRY(fields_budget(reserve, &budget));
+      if (n * sizeof(double) > budget) {
+        set_error("dv_field_set_detect_bands: the %d planes of %d %d-pixel fields need %zu bytes of device memory, %zu bytes "
+                  "are available", k, fs->M, fs->F, n * sizeof(double), budget);
+        return DV_E_NOMEM;
+      }
+      DV_HIP(hipStreamSynchronize(s));
+      fs->dplanes.reset();
+      fs->dbands.clear();
+      fs->dbw.clear();
+      DV_TRY(fs->dplanes.alloc(std::max<size_t>(n, 1)));
+    }
+    if (n > 0) {
+      DV_HIP(hipMemcpyAsync(fs->dplanes, planes, n * sizeof(double), hipMemcpyHostToDevice, s));
+      DV_HIP(hipStreamSynchronize(s));
+    }
+  }
+  fs->dbands.assign(bands, bands + k);
+  fs->dbw.assign((size_t)k, 1.0);
+  if (band_weights) fs->dbw.assign(band_weights, band_weights + k);
+  fs->dbnoise = noise;
+  fs->dbfilter = filter;
+  return DV_OK;
+}
+
 int dv_field_set_detect_weights(dv_field_set* fs, const double* weights, int32_t noise, int32_t filter) {
   DV_TRY(field_set_live(fs, "dv_field_set_detect_weights"));
   DV_HIP(hipSetDevice(fs->m->ctx->device));
   hipStream_t s = fs->m->ctx->stream;
+  if (weights && !fs->dbands.empty()) {
+    set_error("dv_field_set_detect_weights: the set holds a band selection of dv_field_set_detect_bands; drop it first");
+    return DV_E_INVALID;
+  }
   if (!weights) {                               // drop the planes: dv_field_set_detect is the unweighted call again
     DV_HIP(hipStreamSynchronize(s));
     fs->dweights.reset();

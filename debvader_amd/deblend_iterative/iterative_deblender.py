@@ -285,8 +285,8 @@ class IterativeDeblendFieldBatch:
     def iterative_catalogue(self, mse_criterion=100.0, mode="reference", max_iterations=None, measure=False,
                             blendedness=False, return_fields=True, band=2, sigma0=3.0, tol=1e-10, max_iter=200,
                             match_radius=2.0, fit_flux=False, fit_weights=None, fit_sky=None, fit_nonneg=False,
-                            sky_sigma=None, min_pivot=1e-8, detect_weights=None, detect_noise=None, detect_filter="conv",
-                            detect_thresh=None, fit_groups=False):
+                            sky_sigma=None, min_pivot=1e-8, detect_bands=None, detect_band_weights=None, detect_weights=None,
+                            detect_noise=None, detect_filter="conv", detect_thresh=None, fit_groups=False):
         """iterative_deblending() with a catalogue measured on the GPU: the same loop, the same
         list of M recarrays (kept in self.res_deblend), self.mse and fields, and with every argument behind the first
         three left at its default the same calls.  The arguments are a method of their own because the parameter list of
@@ -336,7 +336,13 @@ class IterativeDeblendFieldBatch:
             because the network reads them: fill the pixels under a bleed trail, a saturated core or a chip gap with finite
             values (the local sky, say) - the weights keep them out of every detection pass, whatever they hold.
         detect_thresh: the detection threshold of every pass (None: the detector's 1.5), with or without weights.
-            (The four detect_* arguments are keywords: pass them, and fit_groups behind them, by name.)
+        detect_bands: a list of band numbers: every detection pass runs on the inverse-variance weighted combination of those
+            bands of the working residual (FieldSet.set_detect_bands before the first pass) in place of
+            band 2 alone, matched to the spectral shape detect_band_weights (None: flat).  detect_thresh is then in units of
+            the combined pixel's own sigma.  detect_weights, if given, must be (M, F, F, bands): the planes of the selected
+            bands are taken from it; three-dimensional weights are refused.  detect_noise and detect_filter mean what they mean
+            without detect_bands; detect_filter then needs no weights.
+            (The detect_* arguments are keywords: pass them, and fit_groups behind them, by name.)
 
         mse_criterion, mode, max_iterations: as in iterative_deblending."""
         if mode not in ("reference", "cumulative"):
@@ -377,10 +383,24 @@ class IterativeDeblendFieldBatch:
             if sky_sigma is not None:
                 sky_sigma = ms.check_sky_sigma(sky_sigma, M, self.nb_of_bands)
             E.fit_flux_params(min_pivot)
-        if detect_weights is None and (detect_noise is not None or detect_filter != "conv"):
+        if detect_bands is None and detect_band_weights is not None:
+            raise ValueError("detect_band_weights need detect_bands: they belong to the multi-band detector")
+        if detect_bands is None and detect_weights is None and (detect_noise is not None or detect_filter != "conv"):
             raise ValueError("detect_noise and detect_filter need detect_weights: they belong to the weighted detector")
         detect_kw = {} if detect_thresh is None else {"thresh": float(detect_thresh)}
-        if detect_weights is not None:
+        if detect_bands is not None:
+            from debvader_amd import engine as E
+
+            detect_bands, detect_band_weights = E.check_detect_bands(self.nb_of_bands, detect_bands, detect_band_weights)
+            if detect_weights is not None:
+                detect_weights = np.asarray(detect_weights, dtype=np.float64)
+                if detect_weights.shape != (M, F, F, self.nb_of_bands):
+                    raise ValueError(f"with detect_bands the detect_weights must hold a plane per band, "
+                                     f"{(M, F, F, self.nb_of_bands)}: got {detect_weights.shape}")
+                detect_weights = np.ascontiguousarray(detect_weights[:, :, :, detect_bands])
+            E.check_detect_band_planes((M, F, F, len(detect_bands)), detect_weights, None, detect_noise, detect_filter,
+                                       1.5 if detect_thresh is None else detect_thresh)
+        elif detect_weights is not None:
             from debvader_amd import engine as E
 
             detect_weights = np.asarray(detect_weights, dtype=np.float64)
@@ -410,7 +430,10 @@ class IterativeDeblendFieldBatch:
         try:
             if fit_flux:
                 fs.keep_stamps()
-            if detect_weights is not None:
+            if detect_bands is not None:
+                fs.set_detect_bands(detect_bands, band_weights=detect_band_weights, weights=detect_weights,
+                                    noise=detect_noise, filter_type=detect_filter)
+            elif detect_weights is not None:
                 fs.set_detect_weights(detect_weights, noise=detect_noise, filter_type=detect_filter)
             k = 0
             while active.any() and (max_iterations is None or k < int(max_iterations)):

@@ -470,6 +470,44 @@ def check_detect_weights(shape, weights, mask, noise, filter_type, thresh):
     return w, _lib.DETECT_NOISE[noise], _lib.DETECT_FILTER[filter_type]
 
 
+def check_detect_bands(nb, bands, band_weights):
+    """The band selection of Context.scene_detect_multiband and FieldSet.set_detect_bands for fields
+    of nb bands, checked before any GPU work: k distinct band numbers (None: all), 1 <= k <= nb, and finite band_weights
+    c_j > 0 (None: all 1.0).  Returns (bands int32 (k,), band_weights float64 (k,))."""
+    nb = int(nb)
+    b = np.arange(nb) if bands is None else np.asarray(list(np.atleast_1d(bands)))
+    if b.ndim != 1 or not 1 <= len(b) <= nb or not np.issubdtype(b.dtype, np.integer):
+        raise ValueError(f"bands must be 1 .. {nb} distinct band numbers, got {bands!r}")
+    if (b < 0).any() or (b >= nb).any() or len(np.unique(b)) != len(b):
+        raise ValueError(f"bands must be distinct and within the fields' {nb} band(s), got {b.tolist()}")
+    c = np.ones(len(b), np.float64) if band_weights is None else np.ascontiguousarray(band_weights, dtype=np.float64)
+    if c.shape != b.shape or not (np.isfinite(c) & (c > 0)).all():
+        raise ValueError(f"band_weights must be {len(b)} finite values > 0, got {band_weights!r}")
+    return np.ascontiguousarray(b, dtype=np.int32), c
+
+
+def check_detect_band_planes(shape, weights, mask, noise, filter_type, thresh):
+    """The planes of the multi-band detector for fields (M, H, W) and k selected bands, shape = (M, H, W, k): weights
+    (M, H, W, k) as in check_detect_weights; mask (M, H, W) or (M, H, W, k), True = bad, zeroes the planes; a mask alone means
+    unit planes and noise "relative".  thresh must be > 0 whatever the noise: it is in units of the combined pixel's sigma.
+    Returns (planes float64 (M, H, W, k) or None, DV_DETECT_NOISE_*, DV_DETECT_FILTER_*)."""
+    shape = tuple(int(n) for n in shape)
+    if filter_type not in _lib.DETECT_FILTER:
+        raise ValueError(f"filter_type must be 'conv' or 'matched', got {filter_type!r}")
+    if not float(thresh) > 0:
+        raise ValueError(f"multi-band detection: thresh is in units of the combined pixel's sigma and must be > 0, got {thresh}")
+    if weights is None and mask is None:
+        if noise is not None:
+            raise ValueError("noise belongs to the planes: give weights, a mask or both")
+        return None, 0, _lib.DETECT_FILTER[filter_type]
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.dtype != np.bool_ or m.shape not in (shape, shape[:3]):
+            raise ValueError(f"expected a boolean mask (True = bad) of shape {shape[:3]} or {shape}, got {m.dtype} {m.shape}")
+        mask = np.ascontiguousarray(np.broadcast_to(m if m.ndim == 4 else m[..., None], shape))
+    return check_detect_weights(shape, weights, mask, noise, filter_type, thresh)
+
+
 def counting_pixels(w):
     """the pixels that count: 0 < w < inf (NaN does not)"""
     with np.errstate(invalid="ignore"):
@@ -1287,6 +1325,74 @@ class Context:
         out.update(offsets=offsets, globalrms=grms, **maps)
         if weighted:
             out["bad_meshes"] = bad
+        return out
+
+    def scene_detect_multiband(self, fields, bands=None, band_weights=None, thresh: float = 1.5, minarea: int = 4,
+                               nthresh: int = 64, cont: float = 1e-5, filter_kernel=None, back_size: int = 64,
+                               back_filter: int = 3, return_maps: bool = False, workspace_bytes: int = 0, weights=None,
+                               mask=None, noise=None, filter_type: str = "conv") -> Dict[str, np.ndarray]:
+        """Source detection on the inverse-variance weighted combination of several bands (dv_scene_detect_multiband,
+        DESIGN.md section 7za).
+
+        fields (M, H, W, nb), interleaved as the network reads them.  bands: k distinct band numbers (None: all), their order
+        is the order of every sum; band_weights c_j > 0 (None: all 1.0): the spectral shape the combination is matched to.
+        Per selected band the background of scene_detect gives back_j, rms_j and v_j = data_j - back_j; the band's weight
+        is w_j = 1 / rms_j^2, with weights (M, H, W, k) P_j / rms_j^2 (noise="relative") or P_j (noise="absolute", the
+        default with weights); mask (M, H, W) or (M, H, W, k), True = bad, zeroes the planes, and a mask alone means unit
+        planes and noise="relative".  A band counts at a pixel iff 0 < w_j < inf (with planes also 0 < P_j < inf).
+        V = sum c_j w_j v_j / sum c_j^2 w_j over the counting bands, Wt = sum c_j^2 w_j its inverse variance; segmentation,
+        deblending and the catalogue run on them as in scene_detect(weights=Wt, noise="absolute"): thresh (> 0) is in units
+        of the combined pixel's own sigma, D holds the significance, flux and the barycentres are sums over V.  The fields
+        must be finite in every selected band where that band counts (everywhere without planes).
+
+        Returns the dictionary of scene_detect plus band_globalrms (M, k) and bad_meshes (M, k); globalrms (M,) is
+        1 / sqrt(sum c_j^2 / globalrms_j^2), a diagnostic.  With return_maps also back, rms (M, H, W, k) and V, Wt, D, labels
+        (M, H, W)."""
+        f = np.ascontiguousarray(fields, dtype=np.float64)
+        if f.ndim != 4 or min(f.shape[1:]) < 1:
+            raise ValueError(f"expected fields (M, H, W, bands), got {f.shape}")
+        M, H, W, nb = f.shape
+        sel, cw = check_detect_bands(nb, bands, band_weights)
+        k = len(sel)
+        planes, noise_id, filter_id = check_detect_band_planes((M, H, W, k), weights, mask, noise, filter_type, thresh)
+        if not np.isfinite(f).all():                  # (one pass over the fields; bands are selected only behind a miss)
+            fsel = f[:, :, :, sel]
+            if planes is None and not np.isfinite(fsel).all():
+                raise ValueError("the fields must be finite in the selected bands")
+            if planes is not None and not np.isfinite(fsel[counting_pixels(planes)]).all():
+                raise ValueError("the fields must be finite in every selected band where that band counts (0 < weight < inf)")
+        check_detect_args(np.zeros((0, H, W)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
+                          workspace_bytes)
+        kern, kptr, kh, kw = None, None, 0, 0
+        if filter_kernel is not None:
+            kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
+            kptr, (kh, kw) = kern.ctypes.data_as(C.POINTER(C.c_double)), kern.shape
+        params = _lib.DvDetectParams(float(thresh), float(cont), int(minarea), int(nthresh), int(back_size),
+                                     int(back_filter), kptr, kh, kw, int(workspace_bytes))
+        offsets = np.zeros(M + 1, np.int64)
+        grms = np.zeros(M, np.float64)
+        bgrms = np.zeros((M, k), np.float64)
+        bad = np.zeros((M, k), np.int32)
+        maps = {}
+        if return_maps:
+            maps = dict(back=np.empty((M, H, W, k)), rms=np.empty((M, H, W, k)), V=np.empty((M, H, W)), Wt=np.empty((M, H, W)),
+                        D=np.empty((M, H, W)), labels=np.empty((M, H, W), np.int32))
+        bstruct = _lib.DvDetectBands(_ip(sel), k, _dp(cw), None if planes is None else _dp(planes), noise_id, filter_id)
+        cap = max(4096, 64 * M, M * H * W // 1024)
+        while True:                                   # the catalog's size is known after the call: grow once if needed
+            cat = {key: np.empty(cap, np.int32 if key in ("field", "parent", "npix") else np.float64)
+                   for key in self.CATALOG_KEYS}
+            n = C.c_int64()
+            check(lib.dv_scene_detect_multiband(
+                self._h, _dp(f), M, H, W, nb, C.byref(params), cap, C.byref(n), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                _dp(grms), *[_ip(cat[key]) if cat[key].dtype == np.int32 else _dp(cat[key]) for key in self.CATALOG_KEYS],
+                *[None if maps.get(key) is None else _dp(maps[key]) for key in ("back", "rms", "V", "Wt", "D")],
+                None if maps.get("labels") is None else _ip(maps["labels"]), C.byref(bstruct), _dp(bgrms), _ip(bad)))
+            if n.value <= cap:
+                break
+            cap = n.value
+        out = {key: v[:n.value].copy() for key, v in cat.items()}
+        out.update(offsets=offsets, globalrms=grms, band_globalrms=bgrms, bad_meshes=bad, **maps)
         return out
 
     def close(self):
@@ -2284,6 +2390,7 @@ class FieldSet:
         self._h = C.c_void_p()
         self._rows = 0                      # stamps of the deblend_pass_measure(blend=True) calls: the set's resident rows
         self._detect_noise = None           # DV_DETECT_NOISE_* while set_detect_weights holds planes
+        self._detect_bands = False          # while set_detect_bands holds a selection
         if not engine._h:
             raise RuntimeError("the Engine of this FieldSet has been closed")
         M, F, _, nb = fields.shape
@@ -2317,6 +2424,23 @@ class FieldSet:
         check(lib.dv_field_set_detect_weights(h, _dp(w), noise_id, filter_id))
         self._detect_noise = noise_id
 
+    def set_detect_bands(self, bands, band_weights=None, weights=None, mask=None, noise=None, filter_type: str = "conv"):
+        """The band selection of every later detect() (dv_field_set_detect_bands): detect() then is
+        Context.scene_detect_multiband on the working residuals with these bands, band_weights, planes (weights (M, F, F, k)
+        and / or mask (M, F, F) or (M, F, F, k), uploaded once), noise and filter_type, and its thresh is in units of the
+        combined pixel's sigma.  set_detect_bands(None) drops the selection: detect() reads band 2 again.  Refused while
+        set_detect_weights holds single-band planes, and the other way round."""
+        h = self._handle()
+        M, F, nb = self.shape[0], self.shape[1], self.shape[3]
+        if bands is None:
+            check(lib.dv_field_set_detect_bands(h, None, 0, None, None, 0, 0))
+            self._detect_bands = False
+            return
+        sel, cw = check_detect_bands(nb, bands, band_weights)
+        planes, noise_id, filter_id = check_detect_band_planes((M, F, F, len(sel)), weights, mask, noise, filter_type, 1.0)
+        check(lib.dv_field_set_detect_bands(h, _ip(sel), len(sel), _dp(cw), _dp(planes), noise_id, filter_id))
+        self._detect_bands = True
+
     def detect(self, active=None, thresh: float = 1.5, minarea: int = 4, nthresh: int = 64, cont: float = 1e-5,
                filter_kernel=None, back_size: int = 64, back_filter: int = 3, workspace_bytes: int = 0) -> Dict[str, np.ndarray]:
         """Context.scene_detect on band 2 of the working residuals, which do not leave the GPU (dv_field_set_detect).
@@ -2328,6 +2452,8 @@ class FieldSet:
                           workspace_bytes)
         if getattr(self, "_detect_noise", None) == _lib.DETECT_NOISE["absolute"] and not float(thresh) > 0:
             raise ValueError(f"with noise='absolute' thresh is in units of the pixel's sigma and must be > 0, got {thresh}")
+        if getattr(self, "_detect_bands", False) and not float(thresh) > 0:
+            raise ValueError(f"with a band selection thresh is in units of the combined pixel's sigma and must be > 0, got {thresh}")
         act = None
         if active is not None:
             act = np.ascontiguousarray(np.asarray(active, dtype=bool).astype(np.uint8))

@@ -432,6 +432,37 @@ int dv_scene_detect_weighted(dv_ctx* ctx, const double* fields, int32_t M, int32
                              double* globalrms, int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux,
                              double* x, double* y, double* back, double* rms, double* D, int32_t* labels,
                              const dv_detect_weights* weights, int32_t* bad_meshes);
+/* dv_scene_detect_multiband: detection on the inverse-variance weighted combination of k bands.
+ * fields [M][H][W][nb] float64, interleaved as the network reads them.  bands->bands: k distinct band numbers, 1 <= k <= nb,
+ * their order is the order of every sum; band_weights c_j > 0 finite (NULL: all 1.0), the spectral shape the combination is
+ * matched to; planes [M][H][W][k] (NULL: none) with noise as in dv_scene_detect_weighted, one plane per selected band.
+ * Per band j the background steps of dv_scene_detect (without planes) or dv_scene_detect_weighted (with P_j) give back_j,
+ * rms_j, the band's globalrms g_j and v_j = data_j - back_j.  The band's weight is w_j = 1 / (rms_j rms_j) without planes,
+ * P_j / (rms_j rms_j) with relative noise, P_j with absolute noise; band j COUNTS at a pixel iff 0 < w_j < inf, with planes
+ * also 0 < P_j < inf, and the band has a good mesh in the field.  Over the counting bands, j ascending:
+ * num = sum (c_j w_j) v_j, Wt = sum (c_j c_j) w_j; no counting band: V = Wt = 0 and the pixel does not count; one:
+ * V = v_j / c_j; more: V = num / Wt.  Everything behind runs as dv_scene_detect_weighted with (V, Wt) in the place of
+ * (v, w), absolute noise and T = thresh (> 0 always: it is in units of the combined pixel's own sigma): D holds the
+ * significance S, flux and the barycentres are sums over V.  globalrms[f] = 1 / sqrt(sum (c_j c_j) / (g_j g_j)) over the
+ * bands with a good mesh (a diagnostic), NaN for a field without one, which has no objects.  band_globalrms [M][k],
+ * bad_meshes [M][k] and the maps back, rms [M][H][W][k], V, Wt, D, labels [M][H][W] are nullable.  With k = 1, c = 1 and no
+ * planes every output has the bits of dv_scene_detect_weighted on that band with weights = 1 / (rms rms) of its own maps and
+ * absolute noise.
+ * Refused before any GPU work (DV_E_INVALID, the engine stays usable): what dv_scene_detect refuses, k < 1 or k > nb, a band
+ * out of range or given twice, a c_j that is not finite and positive, an unknown noise or filter, thresh <= 0. */
+typedef struct dv_detect_bands {
+  const int32_t* bands;        /* [k] */
+  int32_t k;
+  const double* band_weights;  /* [k] or NULL */
+  const double* planes;        /* [M][H][W][k] or NULL */
+  int32_t noise;               /* DV_DETECT_NOISE_* (read with planes) */
+  int32_t filter;              /* DV_DETECT_FILTER_* */
+} dv_detect_bands;
+int dv_scene_detect_multiband(dv_ctx* ctx, const double* fields, int32_t M, int32_t H, int32_t W, int32_t nb,
+                              const dv_detect_params* params, int64_t cap, int64_t* n_out, int64_t* offsets,
+                              double* globalrms, int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux,
+                              double* x, double* y, double* back, double* rms, double* V, double* Wt, double* D,
+                              int32_t* labels, const dv_detect_bands* bands, double* band_globalrms, int32_t* bad_meshes);
 
 /* ---- catalogue measurement: fluxes and adaptive moments per galaxy ----
  * The reference ships an empty debvader.measure package; the measurement is defined here, float64 throughout.  Per stamp,
@@ -952,6 +983,15 @@ int dv_field_set_detect(dv_field_set* set, const uint8_t* active, const dv_detec
  * has an empty range and globalrms NaN.  With no planes held it is as above.  With absolute noise dv_field_set_detect
  * refuses thresh <= 0.  Refused (DV_E_INVALID): an unknown noise or filter; a closed set: DV_E_STATE. */
 int dv_field_set_detect_weights(dv_field_set* set, const double* weights, int32_t noise, int32_t filter);
+/* dv_field_set_detect_bands: the band selection of dv_scene_detect_multiband for every later
+ * dv_field_set_detect, which then takes the multi-band path on `work` (the bits of dv_scene_detect_multiband on `work` read
+ * back).  bands [k], band_weights [k] or NULL, planes [M][F][F][k] or NULL with noise, filter as there; the planes are uploaded
+ * once, counted against free device memory like those of dv_field_set_detect_weights (DV_E_NOMEM, the set left as it was).
+ * k = 0 drops the selection and its planes.  Refused (DV_E_INVALID): what dv_scene_detect_multiband refuses of these
+ * arguments, and a selection while single-band planes of dv_field_set_detect_weights are held (which in turn is refused
+ * while a selection is held); a closed set: DV_E_STATE. */
+int dv_field_set_detect_bands(dv_field_set* set, const int32_t* bands, int32_t k, const double* band_weights,
+                              const double* planes, int32_t noise, int32_t filter);
 int dv_field_set_pass(dv_field_set* set, const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
                       uint64_t seed, double* mse_center, double* field_mse);
 int dv_field_set_read(dv_field_set* set, int32_t which, double* out);

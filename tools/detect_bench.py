@@ -9,6 +9,12 @@ variances, every 97th column and one block per 259 px masked), the unweighted an
 process, --runs (5) timed runs each; prints the medians, the spread (min .. max) and the ratio of the medians.
 
     python tools/detect_bench.py --weights [--filter matched] [--runs 5]
+
+--bands 0,1,2,3,4,5: the same two workloads with those bands combined (Context.scene_detect_multiband on
+interleaved six-band fields whose band 2 is the single-band leg's field), the single-band and the multi-band leg alternating
+in one process as above.
+
+    python tools/detect_bench.py --bands 0,1,2,3,4,5 [--filter matched] [--runs 5]
 """
 import argparse
 import json
@@ -90,6 +96,36 @@ def main_weighted(a, ctx, batch, tile):
     print(json.dumps(out))
 
 
+def _six_bands(rng, f):
+    """(.., H, W) -> (.., H, W, 6): band 2 is f, the others f's sources at another amplitude on a sky and noise of their own"""
+    out = np.empty(f.shape + (6,))
+    for b, (amp, sky, sig) in enumerate(((0.6, 50.0, 1.0), (0.8, 20.0, 1.5), (1.0, 100.0, 1.0), (1.1, 10.0, 1.25), (1.2, 5.0, 0.8),
+                                         (0.9, 200.0, 2.0))):
+        out[..., b] = f if b == 2 else sky + amp * (f - 100.0) + rng.normal(0, sig, f.shape[-2:])
+    return out
+
+
+def main_bands(a, ctx, batch, tile):
+    bands = [int(b) for b in a.bands.split(",")]
+    rng = np.random.default_rng(1)
+    # the combined threshold is in units of the combined pixel's sigma: 1.5 on the smoothed map as in the single-band leg, 5 on
+    # the matched filter's S
+    kw = dict(bands=bands, filter_type=a.filter, thresh=5.0 if a.filter == "matched" else 1.5)
+    mb, mt = _six_bands(rng, batch), _six_bands(rng, tile)
+    ctx.scene_detect_multiband(mb[:2], **kw)                           # warm-up of the multi-band kernels
+    out = {"batch": a.batch, "F": batch.shape[1], "tile": a.tile, "bands": bands, "filter": a.filter, "thresh": kw["thresh"],
+           "runs": a.runs}
+    for name, f, m, scale in (("batch", batch, mb, 1.0), ("tile", tile, mt, 1e3)):
+        p, q, rp, rq = _alternate(lambda: ctx.scene_detect(f), lambda: ctx.scene_detect_multiband(m, **kw), a.runs)
+        unit = "seconds" if name == "batch" else "ms"
+        for leg, t, r in (("single", p, rp), ("multiband", q, rq)):
+            out[f"{name}_{leg}_{unit}_median"] = round(scale * t[0], 5)
+            out[f"{name}_{leg}_{unit}_min_max"] = [round(scale * t[1], 5), round(scale * t[2], 5)]
+            out[f"{name}_{leg}_objects"] = int(len(r["x"]))
+        out[f"{name}_multiband_over_single"] = round(q[0] / p[0], 4)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -99,6 +135,8 @@ def main():
     ap.add_argument("--weights", action="store_true", help="alternate the unweighted and the weighted detector")
     ap.add_argument("--filter", choices=("conv", "matched"), default="conv")
     ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--bands", default=None, help="comma-separated band numbers: alternate the single-band and the multi-band "
+                                                  "detector")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     F = 259
@@ -109,6 +147,8 @@ def main():
     ctx.scene_detect(batch[:2])                                        # warm-up (module load, first allocations)
     if a.weights:
         return main_weighted(a, ctx, batch, tile)
+    if a.bands:
+        return main_bands(a, ctx, batch, tile)
     tb, rb = _best(lambda: ctx.scene_detect(batch), a.repeat)
     tt, rt = _best(lambda: ctx.scene_detect(tile), a.repeat)
     t0 = time.perf_counter()
