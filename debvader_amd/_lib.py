@@ -56,6 +56,18 @@ class DvDetectBands(C.Structure):
                 ("planes", C.POINTER(C.c_double)), ("noise", C.c_int32), ("filter", C.c_int32)]
 
 
+# the columns of dv_detect_objects in the struct's order
+DETECT_OBJECT_INT = ("xmin", "xmax", "ymin", "ymax", "xpeak", "ypeak", "xvpeak", "yvpeak", "flag")
+DETECT_OBJECT_DOUBLE = ("vpeak", "dflux", "x_iso", "y_iso", "x2", "y2", "xy")
+DETECT_FLAG_BLENDED, DETECT_FLAG_BORDER, DETECT_FLAG_SINGULAR, DETECT_FLAG_MASKED = 1, 2, 4, 8    # DV_DETECT_FLAG_*
+
+
+class DvDetectObjects(C.Structure):
+    """dv_detect_objects (include/debvader_hip.h)"""
+    _fields_ = ([(k, C.POINTER(C.c_int32)) for k in DETECT_OBJECT_INT]
+                + [(k, C.POINTER(C.c_double)) for k in DETECT_OBJECT_DOUBLE] + [("segmap", C.POINTER(C.c_int32))])
+
+
 DETECT_NOISE = {"absolute": 0, "relative": 1}     # DV_DETECT_NOISE_*
 DETECT_FILTER = {"conv": 0, "matched": 1}         # DV_DETECT_FILTER_*
 
@@ -201,6 +213,9 @@ SIGNATURES = {
     "dv_scene_detect_multiband": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams),
                                             C.c_int64, _i64, _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d, _d, _d, _d, _d, _d, _i32,
                                             C.POINTER(DvDetectBands), _d, _i32]),
+    "dv_scene_detect_objects": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams),
+                                          C.c_int64, _i64, _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d,
+                                          C.POINTER(DvDetectWeights), C.POINTER(DvDetectBands), C.POINTER(DvDetectObjects)]),
     "dv_measure_params_default": (C.c_int, [C.POINTER(DvMeasureParams)]),
     "dv_scene_measure": (C.c_int, [_p, _f, _f, C.c_int64, C.c_int32, C.c_int32, C.POINTER(DvMeasureParams), _d, _d, _d, _i32,
                                    _i32]),
@@ -252,6 +267,8 @@ SIGNATURES = {
                                       _i32, _i32, _d, _d, _d, _d]),
     "dv_field_set_detect_weights": (C.c_int, [_p, _d, C.c_int32, C.c_int32]),
     "dv_field_set_detect_bands": (C.c_int, [_p, _i32, C.c_int32, _d, _d, C.c_int32, C.c_int32]),
+    "dv_field_set_detect_objects": (C.c_int, [_p, C.c_int32, C.c_int32]),
+    "dv_field_set_detect_objects_read": (C.c_int, [_p, C.c_int64, C.POINTER(DvDetectObjects)]),
     "dv_field_set_pass": (C.c_int, [_p, _i32, _i32, _i64, C.c_int64, C.c_uint64, _d, _d]),
     "dv_field_set_read": (C.c_int, [_p, C.c_int32, _d]),
     "dv_field_set_close": (C.c_int, [_p]),

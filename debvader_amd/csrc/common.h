@@ -668,11 +668,28 @@ struct DetectBands {
 };
 // the argument checks of a DetectBands for fields of nb bands, before any GPU work (who: the caller's name in the message)
 int detect_bands_check(const char* who, const int32_t* bands, int k, const double* c, int nb, int noise, int filter);
+// the per-object outputs of DESIGN 7zb, all nullable: the integer columns in the order xmin xmax ymin ymax xpeak ypeak
+// xvpeak yvpeak flag, the double columns in the order vpeak dflux x_iso y_iso x2 y2 xy, [cap] each and written like the
+// catalogue (only when it fits); segmap [M][H][W] is always written
+constexpr int DET_OBJ_I = 9, DET_OBJ_D = 7;
+struct DetectObjects {
+  int32_t* icol[DET_OBJ_I];
+  double* dcol[DET_OBJ_D];
+  int32_t* segmap_h;
+};
 int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
                      int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
                      int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
                      int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                     hipStream_t s, const DetectWeights* wq = nullptr, const DetectBands* mb = nullptr);
+                     hipStream_t s, const DetectWeights* wq = nullptr, const DetectBands* mb = nullptr,
+                     const DetectObjects* oq = nullptr);
+// the three host calls behind one entry with the outputs of DESIGN 7zb and no maps: nb = 0 and mb null: fields [M][H][W],
+// unweighted or, with wq, weighted; mb given: fields [M][H][W][nb] (wq null)
+int scene_detect_objects(const double* fields_h, int nb, const DetectWeights* wq, const DetectBands* mb, const DetectObjects& oq,
+                         int M, int H, int W, double thresh, double cont, int minarea, int nthresh, int back_size,
+                         int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes, int64_t cap,
+                         int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h, int32_t* parent_h,
+                         int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h, hipStream_t s);
 // host fields [M][H][W][nb], interleaved, uploaded as they are and gathered on the GPU
 int scene_detect_multiband(const double* fields_h, int nb, const DetectBands& mb, int M, int H, int W, double thresh, double cont,
                            int minarea, int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,

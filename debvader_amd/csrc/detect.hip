@@ -27,11 +27,16 @@
 // On the inverse-variance combination of several bands (tests/detect_multiband_oracle.py)
 // bands_gather_kernel writes the selected planes of the interleaved fields, kernels 1 to 3 run over fields x bands planes,
 // multiband_pixel_kernel stands where kernel 4 stood and writes the combined v and its weight, and kernel 5 runs WEIGHTED on them.
+// With the object columns or the segmentation map asked for (tests/detect_objects_oracle.py) kernel 8 runs
+// in its OBJECTS instantiation (deblend_dev.h, launched from detect_objects.hip): step e also takes every object's box, peak
+// pixels, isophotal moments and flags and numbers the object's pixels within the component; seg_base_kernel adds the objects of
+// the field's earlier components.
 // fp64 VALU and integer work; nothing here has a matrix shape for MFMA.
 #include "common.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <initializer_list>
 #include <vector>
 
@@ -39,96 +44,23 @@
 // could move a D value across the threshold or reorder two near-equal assignment scores.
 #pragma clang fp contract(off)
 
+#include "deblend_dev.h"
+
 namespace dv {
 
 namespace {
-constexpr int DT = 256;              // threads of every workgroup here (four waves)
 constexpr int MESH_MAX = 4096;       // back_size <= 64
-constexpr int DB_LDS = 2048;         // component pixels the deblend keeps in LDS
 constexpr int MF_MAX = 7;            // back_filter <= 7
 constexpr int KMAX = 15;             // filter kernels up to 15 x 15
 constexpr int FT = 16;               // filter output tile
 constexpr int DIM_MAX = 1 << 19;     // H, W (filter grid rows)
 constexpr int CHUNK_MAX = 65535;     // fields per launch (filter grid z)
 
-__device__ __forceinline__ int ald(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int amin(int* p, int v) {
-  return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void ast(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void aadd(int* p, int v) {
-  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// sum of v over the workgroup in a fixed order; every thread gets the result
-template <int K>
-__device__ __forceinline__ void blk_sum(double (&v)[K], double* s_red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-  }
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) s_red[wave * K + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = ((s_red[k] + s_red[K + k]) + (s_red[2 * K + k] + s_red[3 * K + k]));
-}
-
-// (max v, smallest i at it) over the workgroup; every thread gets the result
-__device__ __forceinline__ void blk_argmax(double& v, int& i, double* s_v, int* s_i) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o, 64);
-    const int oi = __shfl_xor(i, o, 64);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-  __syncthreads();
-  if (lane == 0) { s_v[wave] = v; s_i[wave] = i; }
-  __syncthreads();
-  v = s_v[0];
-  i = s_i[0];
-  for (int w = 1; w < 4; ++w)
-    if (s_v[w] > v || (s_v[w] == v && s_i[w] < i)) { v = s_v[w]; i = s_i[w]; }
-}
-
-// exclusive prefix sum of x over the workgroup in thread order; total = the sum
-__device__ __forceinline__ int blk_scan(int x, int* s_w, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = x;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += y;
-  }
-  __syncthreads();
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  int base = 0;
-  total = 0;
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) base += s_w[w];
-    total += s_w[w];
-  }
-  return base + inc - x;
-}
-
-__device__ __forceinline__ int blk_isum(int x, int* s_w) {
-  int t;
-  (void)blk_scan(x, s_w, t);
-  return t;
-}
-
 // ---- background --------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double median_sorted(const double* s, int n) {
   return (n & 1) ? s[n / 2] : 0.5 * (s[n / 2 - 1] + s[n / 2]);
 }
 
-// a pixel counts iff 0 < w < inf (a comparison: NaN does not count), DESIGN 7z
-__device__ __forceinline__ bool counts(double w) { return w > 0.0 && w < INFINITY; }
 
 // WEIGHTED (7z): only the counting pixels of wt enter the clipping, a mesh with fewer than half of its pixels counting is
 // marked bad with NaN
@@ -486,29 +418,6 @@ __global__ __launch_bounds__(DT) void filter_kernel(const double* __restrict__ v
 }
 
 // ---- connected components ---------------------------------------------------------------------------------------
-__device__ __forceinline__ int uf_find(int* par, int x) {
-  int p = ald(par + x);
-  while (p != x) {
-    x = p;
-    p = ald(par + x);
-  }
-  return x;
-}
-
-// links the larger root under the smaller one; a failed link (the root was linked meanwhile, or the min replaced a parent)
-// carries on with the entry it found there, so no connection is lost
-__device__ void uf_union(int* par, int a, int b) {
-  for (;;) {
-    a = uf_find(par, a);
-    b = uf_find(par, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = amin(par + a, b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
 __global__ __launch_bounds__(DT) void cc_merge_kernel(int* par, long total, int W, long HW) {
   const long e = (long)blockIdx.x * DT + threadIdx.x;
   if (e >= total) return;
@@ -592,318 +501,14 @@ __global__ __launch_bounds__(DT) void cc_labels_kernel(const int* __restrict__ l
 }
 
 // ---- deblending -------------------------------------------------------------------------------------------------
-struct DbJob {
-  long fbase;          // first pixel of the component's field in the chunk arrays
-  long dws, iws;       // double / int scratch offsets
-  long slot;           // first catalog slot
-  int root, n, c0, c1, r1, cap;
-  double T;
-};
-
-// object table row (doubles): threshold, mx, my, sxx, sxy, syy, det, A
-constexpr int OBJ_D = 8;
-
-__global__ __launch_bounds__(DT) void deblend_kernel(const DbJob* __restrict__ jobs, int W, const double* __restrict__ Dall,
-                                                     const double* __restrict__ vall, const int* __restrict__ laball,
-                                                     int* lidxall, double* dscr, int* iscr, int nthresh, int minarea,
-                                                     double cont, int* __restrict__ o_npix, int* __restrict__ o_peakpix,
-                                                     double* __restrict__ o_peak, double* __restrict__ o_flux,
-                                                     double* __restrict__ o_x, double* __restrict__ o_y,
-                                                     int* __restrict__ nobj_out) {
-  __shared__ double s_D[DB_LDS];
-  __shared__ int s_pix[DB_LDS], s_par[DB_LDS], s_obj[DB_LDS];
-  __shared__ double s_red[4 * 8];
-  __shared__ int s_w[4], s_i[4], s_b[2];
-  const int tid = threadIdx.x;
-  const DbJob J = jobs[blockIdx.x];
-  const int n = J.n, cap = J.cap;
-  const bool small = n <= DB_LDS;
-  double* dw = dscr + J.dws;
-  int* iw = iscr + J.iws;
-  // scratch: doubles Dp[n] | nflux[cap] | object table [cap][OBJ_D] | next thresholds [cap]
-  //          ints    pix[n] | par[n] | obj[n] | rk[n] | cnt[n] | chid[n] | nodes[cap] | ostate[cap] | nsig[cap]
-  double* Dp = small ? s_D : dw;
-  double* nflux = dw + n;
-  double* otab = nflux + cap;
-  double* othr2 = otab + (long)OBJ_D * cap;
-  int* pix = small ? s_pix : iw;
-  int* par = small ? s_par : iw + n;
-  int* obj = small ? s_obj : iw + 2L * n;
-  int* rk = iw + 3L * n;
-  int* cnt = iw + 4L * n;
-  int* chid = iw + 5L * n;
-  int* nodes = iw + 6L * n;
-  int* ostate = nodes + cap;
-  int* nsig = ostate + cap;
-  const double* Df = Dall + J.fbase;
-  const double* vf = vall + J.fbase;
-  const int* labf = laball + J.fbase;
-  int* lidx = lidxall + J.fbase;
-
-  // a. the pixels in raster order (scan of the bounding box)
-  {
-    const int r0 = J.root / W, bw = J.c1 - J.c0 + 1;
-    const long total = (long)(J.r1 - r0 + 1) * bw;
-    int count = 0;
-    for (long base = 0; base < total; base += DT) {
-      const long e = base + tid;
-      int p = 0;
-      bool on = false;
-      if (e < total) {
-        p = (r0 + (int)(e / bw)) * W + J.c0 + (int)(e % bw);
-        on = labf[p] == J.root;
-      }
-      int tot;
-      const int at = count + blk_scan(on ? 1 : 0, s_w, tot);
-      if (on) {
-        pix[at] = p;
-        Dp[at] = Df[p];
-        lidx[p] = at;
-      }
-      count += tot;
-    }
-  }
-  __syncthreads();
-  // b. peak and flux of the component
-  double P = -INFINITY;
-  int pidx = 0x7fffffff;
-  double cf[1] = {0.0};
-  for (int i = tid; i < n; i += DT) {
-    cf[0] += Dp[i];
-    if (Dp[i] > P) { P = Dp[i]; pidx = i; }
-  }
-  blk_argmax(P, pidx, s_red, s_i);
-  blk_sum<1>(cf, s_red);
-  const double cflux = cf[0];
-  for (int i = tid; i < n; i += DT) obj[i] = 0;
-  if (tid == 0) otab[0] = J.T;
-  int nobj = 1;
-  __syncthreads();
-
-  // c. the levels
-  for (int k = 1; k < nthresh; ++k) {
-    const double t = J.T * pow(P / J.T, (double)k / (double)nthresh);
-    int mine = 0;
-    for (int i = tid; i < n; i += DT) {
-      const bool up = Dp[i] > t;
-      ast(par + i, up ? i : -1);                    // words the union-find updates with atomics: atomics only
-      ast(cnt + i, 0);
-      chid[i] = -1;
-      mine += up;
-    }
-    if (blk_isum(mine, s_w) < minarea) break;      // no node at this level or above (the same for every thread)
-    __syncthreads();
-    for (int i = tid; i < n; i += DT) {
-      if (ald(par + i) < 0) continue;
-      const int p = pix[i], r = p / W, c = p - (p / W) * W;
-      int q[4];
-      int nq = 0;
-      if (c > 0) q[nq++] = p - 1;
-      if (r > 0) {
-        if (c > 0) q[nq++] = p - W - 1;
-        q[nq++] = p - W;
-        if (c + 1 < W) q[nq++] = p - W + 1;
-      }
-      for (int a = 0; a < nq; ++a) {
-        if (labf[q[a]] != J.root) continue;
-        const int j = lidx[q[a]];
-        if (ald(par + j) >= 0) uf_union(par, i, j);
-      }
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += DT) {
-      const int rt = ald(par + i) < 0 ? -1 : uf_find(par, i);
-      rk[i] = rt;
-      if (rt >= 0) aadd(cnt + rt, 1);
-    }
-    __syncthreads();
-    // the nodes in root order
-    int nn = 0;
-    for (int base = 0; base < n; base += DT) {
-      const int i = base + tid;
-      const bool nd = i < n && rk[i] == i && ald(cnt + i) >= minarea;
-      int tot;
-      const int at = nn + blk_scan(nd ? 1 : 0, s_w, tot);
-      if (nd) nodes[at] = i;
-      nn += tot;
-    }
-    __syncthreads();
-    // node fluxes in a fixed order; nodes outside every object do not matter
-    for (int q = 0; q < nn; ++q) {
-      const int rt = nodes[q];
-      if (obj[rt] < 0) {
-        if (tid == 0) nflux[q] = 0.0;
-        continue;
-      }
-      double a[1] = {0.0};
-      for (int i = rt + tid; i < n; i += DT)
-        if (rk[i] == rt) a[0] += Dp[i];
-      blk_sum<1>(a, s_red);
-      if (tid == 0) nflux[q] = a[0];
-    }
-    __syncthreads();
-    // the decision rule (one thread: the object list is short)
-    if (tid == 0) {
-      for (int o = 0; o < nobj; ++o) nsig[o] = 0;
-      for (int q = 0; q < nn; ++q) {
-        const int o = obj[nodes[q]];
-        if (o >= 0 && nflux[q] > cont * cflux) ++nsig[o];
-      }
-      int nnew = 0, split = 0;
-      for (int o = 0; o < nobj; ++o) {
-        if (nsig[o] >= 2) {
-          split = 1;
-          ostate[o] = -1;
-          for (int q = 0; q < nn; ++q) {
-            const int rt = nodes[q];
-            if (obj[rt] == o && nflux[q] > cont * cflux) {
-              chid[rt] = nnew;
-              othr2[nnew++] = t;
-            }
-          }
-        } else {
-          ostate[o] = nnew;
-          othr2[nnew++] = otab[(long)o * OBJ_D];
-        }
-      }
-      for (int o = 0; o < nnew; ++o) otab[(long)o * OBJ_D] = othr2[o];
-      s_b[0] = nnew;
-      s_b[1] = split;
-    }
-    __syncthreads();
-    const int split = s_b[1];
-    nobj = s_b[0];
-    if (split) {
-      for (int i = tid; i < n; i += DT) {
-        const int o = obj[i];
-        if (o < 0) continue;
-        const int st = ostate[o];
-        obj[i] = st >= 0 ? st : (rk[i] >= 0 ? chid[rk[i]] : -1);
-      }
-    }
-    __syncthreads();
-  }
-
-  // d. the pixels outside every core go to the object of the largest A exp(-d' S^-1 d / 2)
-  if (nobj == 1) {
-    for (int i = tid; i < n; i += DT) obj[i] = 0;
-  } else {
-    for (int o = 0; o < nobj; ++o) {
-      double* row = otab + (long)o * OBJ_D;
-      const double th = row[0];
-      double a[3] = {0.0, 0.0, 0.0};
-      double A = -INFINITY;
-      int ai = 0x7fffffff;
-      for (int i = tid; i < n; i += DT) {
-        if (obj[i] != o) continue;
-        const double w = Dp[i] - th;
-        const int p = pix[i];
-        a[0] += w;
-        a[1] += w * (p - (p / W) * W);
-        a[2] += w * (p / W);
-        if (Dp[i] > A) { A = Dp[i]; ai = i; }
-      }
-      blk_sum<3>(a, s_red);
-      blk_argmax(A, ai, s_red + 12, s_i);
-      const double mx = a[1] / a[0], my = a[2] / a[0];
-      double b[3] = {0.0, 0.0, 0.0};
-      for (int i = tid; i < n; i += DT) {
-        if (obj[i] != o) continue;
-        const double w = Dp[i] - th;
-        const int p = pix[i];
-        const double dx = (p - (p / W) * W) - mx, dy = (p / W) - my;
-        b[0] += w * dx * dx;
-        b[1] += w * dx * dy;
-        b[2] += w * dy * dy;
-      }
-      blk_sum<3>(b, s_red);
-      if (tid == 0) {
-        const double sxx = b[0] / a[0] + 1.0 / 12.0, sxy = b[1] / a[0], syy = b[2] / a[0] + 1.0 / 12.0;
-        row[1] = mx;
-        row[2] = my;
-        row[3] = sxx;
-        row[4] = sxy;
-        row[5] = syy;
-        row[6] = sxx * syy - sxy * sxy;
-        row[7] = A;
-      }
-      __syncthreads();
-    }
-    for (int i = tid; i < n; i += DT) {
-      if (obj[i] >= 0) continue;
-      const int p = pix[i];
-      const double cx = p - (p / W) * W, cy = p / W;
-      double best = -INFINITY;
-      int bo = 0;
-      for (int o = 0; o < nobj; ++o) {
-        const double* row = otab + (long)o * OBJ_D;
-        const double ex = cx - row[1], ey = cy - row[2];
-        const double q = (row[5] * ex * ex - 2.0 * row[4] * ex * ey + row[3] * ey * ey) / row[6];
-        const double sc = row[7] * exp(-0.5 * q);
-        if (sc > best) { best = sc; bo = o; }
-      }
-      rk[i] = bo;
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += DT)
-      if (obj[i] < 0) obj[i] = rk[i];
-  }
-  __syncthreads();
-
-  // e. the catalog, then the objects ordered by peak pixel
-  for (int o = 0; o < nobj; ++o) {
-    double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // npix, sum v, sum v c, sum v r, sum c, sum r
-    double pk = -INFINITY;
-    int pi = 0x7fffffff;
-    for (int i = tid; i < n; i += DT) {
-      if (obj[i] != o) continue;
-      const int p = pix[i];
-      const double v = vf[p], c = p - (p / W) * W, r = p / W;
-      a[0] += 1.0;
-      a[1] += v;
-      a[2] += v * c;
-      a[3] += v * r;
-      a[4] += c;
-      a[5] += r;
-      if (Dp[i] > pk) { pk = Dp[i]; pi = i; }
-    }
-    blk_sum<6>(a, s_red);
-    blk_argmax(pk, pi, s_red + 24, s_i);
-    if (tid == 0) {
-      const long sl = J.slot + o;
-      o_npix[sl] = (int)a[0];
-      o_peakpix[sl] = pix[pi];
-      o_peak[sl] = pk;
-      o_flux[sl] = a[1];
-      o_x[sl] = a[1] > 0.0 ? a[2] / a[1] : a[4] / a[0];
-      o_y[sl] = a[1] > 0.0 ? a[3] / a[1] : a[5] / a[0];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const long b = J.slot;
-    for (int o = 1; o < nobj; ++o) {                 // insertion sort of the slots by peak pixel
-      const int kp = o_peakpix[b + o], kn = o_npix[b + o];
-      const double k1 = o_peak[b + o], k2 = o_flux[b + o], k3 = o_x[b + o], k4 = o_y[b + o];
-      int q = o;
-      while (q > 0 && o_peakpix[b + q - 1] > kp) {
-        o_peakpix[b + q] = o_peakpix[b + q - 1];
-        o_npix[b + q] = o_npix[b + q - 1];
-        o_peak[b + q] = o_peak[b + q - 1];
-        o_flux[b + q] = o_flux[b + q - 1];
-        o_x[b + q] = o_x[b + q - 1];
-        o_y[b + q] = o_y[b + q - 1];
-        --q;
-      }
-      o_peakpix[b + q] = kp;
-      o_npix[b + q] = kn;
-      o_peak[b + q] = k1;
-      o_flux[b + q] = k2;
-      o_x[b + q] = k3;
-      o_y[b + q] = k4;
-    }
-    nobj_out[blockIdx.x] = nobj;
-  }
+// (7zb) seg holds 0 outside every object and the object's rank in its component + 1 inside, job the component's job there:
+// base[j] = the objects of the earlier components of the job's field
+__global__ __launch_bounds__(DT) void seg_base_kernel(int* __restrict__ seg, const int* __restrict__ job,
+                                                      const int* __restrict__ base, long total) {
+  const long e = (long)blockIdx.x * DT + threadIdx.x;
+  if (e >= total) return;
+  const int v = seg[e];
+  if (v > 0) seg[e] = v + base[job[e]];
 }
 
 inline unsigned nblk(long total) { return (unsigned)((total + DT - 1) / DT); }
@@ -912,8 +517,9 @@ inline unsigned nblk(long total) { return (unsigned)((total + DT - 1) / DT); }
 // a component
 // (7za) k > 0: k data planes, k planes of P when given, k x the mesh grids and row splines, the combined weight Wt, and for a
 // host source the interleaved staging lines of max(nb, k) values per pixel
+// (7zb) objects: the slots of the new columns and every job's segmap base; segmap: 4 bytes per pixel
 long field_bytes(long H, long W, long ny, long nx, int minarea, bool maps, bool weighted, int k = 0, bool planes = false,
-                 int stage = 0) {
+                 int stage = 0, bool objects = false, bool segmap = false) {
   const long HW = H * W, capn = HW / minarea + 1;
   long b = HW * (8 + 8 + 8 + 4 * 7);                          // data v D | par lab area cmin cmax rmax lidx
   if (maps) b += HW * (8 + 8 + 4);                            // back rms labels
@@ -927,6 +533,8 @@ long field_bytes(long H, long W, long ny, long nx, int minarea, bool maps, bool 
   b += capn * 5 * 4;                                          // component table
   b += HW * (8 + 6 * 4) + capn * ((2 + OBJ_D) * 8 + 3 * 4);   // deblend scratch
   b += capn * ((long)sizeof(DbJob) + 4 * 4 + 4 * 8);          // jobs and catalog slots
+  if (objects) b += capn * (OBJ_I * 4 + DET_OBJ_D * 8 + 4);
+  if (segmap) b += HW * 4;
   return b;
 }
 
@@ -962,8 +570,10 @@ struct DetectWork {
   // host source, bsel = the band numbers then 0 .. bands - 1, cband = the c_j
   DevBuf<double> cw, fgrms, stage, cband;
   DevBuf<int> bsel;
+  DevBuf<int> seg;                                   // (7zb) the launch's segmap, when asked for
   int alloc(int chunk, int H, int W, int ny, int nx, long ccap, size_t ktaps, size_t ccoef, bool want_back, bool want_rms,
-            bool want_labels, int nwhich, bool weighted, int bands = 0, int stage_nb = 0) {
+            bool want_labels, int nwhich, bool weighted, int bands = 0, int stage_nb = 0, bool want_seg = false) {
+    if (want_seg) DV_TRY(seg.alloc((size_t)chunk * H * W));
     const size_t kk = bands > 0 ? (size_t)bands : 1;
     const size_t px = (size_t)chunk * H * W, grid = kk * chunk * ny * nx, rows = kk * chunk * H * nx;
     DV_TRY(data.alloc(kk * px));
@@ -991,8 +601,13 @@ struct DeblendScratch {
   DevBuf<DbJob> djobs;
   DevBuf<double> dscr, o_peak, o_flux, o_x, o_y;
   DevBuf<int> iscr, nobj, o_npix, o_pp;
-  int alloc(long nj, long dws, long iws, long slots) {
-    DV_TRY(djobs.alloc((size_t)nj)); DV_TRY(nobj.alloc((size_t)nj));
+  DevBuf<int> oi, jbase;                             // (7zb) [slots][OBJ_I], [nj]; od [slots][DET_OBJ_D]
+  DevBuf<double> od;
+  int alloc(long nj, long dws, long iws, long slots, bool objects = false) {
+    if (objects) {
+      DV_TRY(oi.alloc((size_t)slots * OBJ_I)); DV_TRY(od.alloc((size_t)slots * DET_OBJ_D)); DV_TRY(jbase.alloc((size_t)nj));
+    }
+    DV_TRY(djobs.alloc((size_t)nj + (objects ? 1 : 0))); DV_TRY(nobj.alloc((size_t)nj));
     DV_TRY(dscr.alloc((size_t)dws)); DV_TRY(iscr.alloc((size_t)iws));
     for (DevBuf<int>* b : {&o_npix, &o_pp}) DV_TRY(b->alloc((size_t)slots));
     for (DevBuf<double>* b : {&o_peak, &o_flux, &o_x, &o_y}) DV_TRY(b->alloc((size_t)slots));
@@ -1009,7 +624,8 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
                 int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
                 int64_t workspace_bytes, int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h,
                 int32_t* field_h, int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h,
-                double* y_h, double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s) {
+                double* y_h, double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s,
+                const DetectObjects* oq = nullptr) {
   if (dev && (!dev->fields_dev || !dev->which_h || dev->nb < 1 || dev->band < 0 || dev->band >= dev->nb)) {
     set_error("scene_detect: bad device source");
     return E_INVALID;
@@ -1020,6 +636,10 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
       !n_out || !offsets_h || !globalrms_h || workspace_bytes < 0 ||
       (cap > 0 && (!field_h || !parent_h || !npix_h || !peak_h || !flux_h || !x_h || !y_h))) {
     set_error("scene_detect: bad arguments");
+    return E_INVALID;
+  }
+  if (oq && thresh < 0.0) {                             // (7zb) the moments' weights D > T must be positive
+    set_error("scene_detect: the object shapes and the segmap need thresh >= 0 (got %g)", thresh);
     return E_INVALID;
   }
   const int nbk = mb ? mb->k : 0, nb_src = dev ? dev->nb : nb_h;
@@ -1086,7 +706,8 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
   const bool maps = back_h || rms_h || D_h || labels_h;
   const int stage_nb = (mb && !dev) ? std::max(nb_src, nbk) : 0;
   const long cap_ws = workspace_bytes > 0 ? (long)workspace_bytes : (4L << 30);
-  const long per_field = field_bytes(H, W, ny, nx, minarea, maps, wq != nullptr, nbk, mplanes, stage_nb);
+  const bool want_seg = oq && oq->segmap_h;
+  const long per_field = field_bytes(H, W, ny, nx, minarea, maps, wq != nullptr, nbk, mplanes, stage_nb, oq != nullptr, want_seg);
   if (M > 0 && per_field > cap_ws) {
     set_error("scene_detect: one %d x %d field needs up to %ld bytes of device workspace, above the cap of %ld bytes per "
               "launch", H, W, per_field, cap_ws);
@@ -1102,12 +723,14 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
 
   std::vector<int32_t> c_field, c_parent, c_npix;      // the catalog of all fields
   std::vector<double> c_peak, c_flux, c_x, c_y;
+  std::vector<int32_t> c_oi;                           // (7zb) rows of DET_OBJ_I ints and of DET_OBJ_D doubles
+  std::vector<double> c_od;
   offsets_h[0] = 0;
 
   DetectWork w;
   if (chunk > 0) {
     DV_TRY(w.alloc(chunk, H, W, ny, nx, ccap, kn.size(), cco.size(), back_h != nullptr, rms_h != nullptr,
-                   labels_h != nullptr, dev ? M : 0, wq != nullptr || mplanes, nbk, stage_nb));
+                   labels_h != nullptr, dev ? M : 0, wq != nullptr || mplanes, nbk, stage_nb, want_seg));
     DV_HIP(hipMemcpyAsync(w.kdev, kn.data(), kn.size() * sizeof(double), hipMemcpyHostToDevice, s));
     DV_HIP(hipMemcpyAsync(w.cdev, cco.data(), cco.size() * sizeof(double), hipMemcpyHostToDevice, s));
     if (dev) DV_HIP(hipMemcpyAsync(w.wdev, dev->which_h, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
@@ -1294,19 +917,54 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
     const long nj = (long)jobs.size();
     std::vector<int> h_nobj((size_t)nj), h_npix((size_t)slots);
     std::vector<double> h_peak((size_t)slots), h_flux((size_t)slots), h_x((size_t)slots), h_y((size_t)slots);
+    std::vector<int> h_oi(oq ? (size_t)slots * OBJ_I : 0);
+    std::vector<double> h_od(oq ? (size_t)slots * DET_OBJ_D : 0);
+    if (want_seg) DV_HIP(hipMemsetAsync(w.seg, 0, (size_t)px * sizeof(int), s));
     if (nj > 0) {
       DeblendScratch d;
-      DV_TRY(d.alloc(nj, dws, iws, slots));
-      DV_HIP(hipMemcpyAsync(d.djobs, jobs.data(), (size_t)nj * sizeof(DbJob), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(deblend_kernel, dim3((unsigned)nj), dim3(DT), 0, s, d.djobs, W, w.D, w.v, w.lab, w.lidx, d.dscr,
-                         d.iscr, nthresh, minarea, cont, d.o_npix, d.o_pp, d.o_peak, d.o_flux, d.o_x, d.o_y, d.nobj);
+      DV_TRY(d.alloc(nj, dws, iws, slots, oq != nullptr));
+      if (oq) {                                           // the request rides behind the jobs, in the place of one more
+        const DbObjects oo{mb ? (const double*)w.cw : (wq ? (const double*)w.wt : nullptr), H, want_seg ? (int*)w.seg : nullptr,
+                           d.oi, d.od};
+        jobs.push_back(DbJob{});
+        std::memcpy(&jobs[(size_t)nj], &oo, sizeof(oo));
+      }
+      DV_HIP(hipMemcpyAsync(d.djobs, jobs.data(), jobs.size() * sizeof(DbJob), hipMemcpyHostToDevice, s));
+      if (oq) {
+        DV_TRY(deblend_objects_launch(nj, s, d.djobs, W, w.D, w.v, w.lab, w.lidx, d.dscr, d.iscr, nthresh, minarea, cont,
+                                      d.o_npix, d.o_pp, d.o_peak, d.o_flux, d.o_x, d.o_y, d.nobj));
+      } else {
+        hipLaunchKernelGGL(deblend_kernel<false>, dim3((unsigned)nj), dim3(DT), 0, s, d.djobs, W, w.D, w.v, w.lab, w.lidx, d.dscr,
+                           d.iscr, nthresh, minarea, cont, d.o_npix, d.o_pp, d.o_peak, d.o_flux, d.o_x, d.o_y, d.nobj);
+      }
       DV_HIP(hipGetLastError());
+      if (oq) {
+        DV_HIP(hipMemcpyAsync(h_oi.data(), d.oi, h_oi.size() * 4, hipMemcpyDeviceToHost, s));
+        DV_HIP(hipMemcpyAsync(h_od.data(), d.od, h_od.size() * 8, hipMemcpyDeviceToHost, s));
+      }
       DV_HIP(hipMemcpyAsync(h_nobj.data(), d.nobj, (size_t)nj * 4, hipMemcpyDeviceToHost, s));
       DV_HIP(hipMemcpyAsync(h_npix.data(), d.o_npix, (size_t)slots * 4, hipMemcpyDeviceToHost, s));
       DV_HIP(hipMemcpyAsync(h_peak.data(), d.o_peak, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
       DV_HIP(hipMemcpyAsync(h_flux.data(), d.o_flux, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
       DV_HIP(hipMemcpyAsync(h_x.data(), d.o_x, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
       DV_HIP(hipMemcpyAsync(h_y.data(), d.o_y, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DV_HIP(hipStreamSynchronize(s));
+      if (want_seg) {                                     // every job's base: the objects of its field's earlier components
+        std::vector<int> jb((size_t)nj);
+        int run = 0;
+        for (long j = 0; j < nj; ++j) {
+          if (j > 0 && jfield[j] != jfield[j - 1]) run = 0;
+          jb[j] = run;
+          run += h_nobj[j];
+        }
+        DV_HIP(hipMemcpyAsync(d.jbase, jb.data(), (size_t)nj * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(seg_base_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.seg, w.lidx, d.jbase, px);
+        DV_HIP(hipGetLastError());
+        DV_HIP(hipStreamSynchronize(s));                  // (jb and the scratch leave scope)
+      }
+    }
+    if (want_seg) {
+      DV_HIP(hipMemcpyAsync(oq->segmap_h + (size_t)f0 * HW, w.seg, (size_t)px * 4, hipMemcpyDeviceToHost, s));
       DV_HIP(hipStreamSynchronize(s));
     }
     long ji = 0;
@@ -1322,6 +980,10 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
           c_flux.push_back(h_flux[sl]);
           c_x.push_back(h_x[sl]);
           c_y.push_back(h_y[sl]);
+          if (oq) {
+            c_oi.insert(c_oi.end(), h_oi.begin() + sl * OBJ_I, h_oi.begin() + sl * OBJ_I + DET_OBJ_I);
+            c_od.insert(c_od.end(), h_od.begin() + sl * DET_OBJ_D, h_od.begin() + (sl + 1) * DET_OBJ_D);
+          }
         }
       }
       offsets_h[f0 + f + 1] = (int64_t)c_field.size();
@@ -1337,6 +999,13 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
     std::copy(c_flux.begin(), c_flux.end(), flux_h);
     std::copy(c_x.begin(), c_x.end(), x_h);
     std::copy(c_y.begin(), c_y.end(), y_h);
+    if (oq)
+      for (size_t i = 0; i < n; ++i) {
+        for (int e = 0; e < DET_OBJ_I; ++e)
+          if (oq->icol[e]) oq->icol[e][i] = c_oi[i * DET_OBJ_I + e];
+        for (int e = 0; e < DET_OBJ_D; ++e)
+          if (oq->dcol[e]) oq->dcol[e][i] = c_od[i * DET_OBJ_D + e];
+      }
   }
   return OK;
 }
@@ -1360,10 +1029,25 @@ int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh
                      int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
                      int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
                      int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                     hipStream_t s, const DetectWeights* wq, const DetectBands* mb) {
+                     hipStream_t s, const DetectWeights* wq, const DetectBands* mb, const DetectObjects* oq) {
   return detect_impl(nullptr, &src, wq, mb, 0, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
                      workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
-                     y_h, nullptr, nullptr, nullptr, nullptr, s);
+                     y_h, nullptr, nullptr, nullptr, nullptr, s, oq);
+}
+
+int scene_detect_objects(const double* fields_h, int nb, const DetectWeights* wq, const DetectBands* mb, const DetectObjects& oq,
+                         int M, int H, int W, double thresh, double cont, int minarea, int nthresh, int back_size,
+                         int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes, int64_t cap,
+                         int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h, int32_t* parent_h,
+                         int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h, hipStream_t s) {
+  if (!fields_h || (mb ? wq != nullptr : nb != 0)) {
+    set_error("scene_detect_objects: bad arguments (fields [M][H][W] with nb = 0, or [M][H][W][nb] with a band selection and "
+              "no single-band weights)");
+    return E_INVALID;
+  }
+  return detect_impl(fields_h, nullptr, wq, mb, nb, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h,
+                     kh, kw, workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
+                     y_h, nullptr, nullptr, nullptr, nullptr, s, &oq);
 }
 
 int detect_bands_check(const char* who, const int32_t* bands, int k, const double* c, int nb, int noise, int filter) {

@@ -590,7 +590,13 @@ struct dv_field_set {
   std::vector<double> dbw;
   dv::DevBuf<double> dplanes;
   int dbnoise = 0, dbfilter = 0;
-  dv::StampTables tab;                           // the per-stamp tables of a pass, kept between passes and grown on demand
+  // the object columns of the last detection (dv_field_set_detect_objects), on the host: while dobj is set
+  // dv_field_set_detect asks for them (dseg: and for the segmap [M][F][F]); do_n rows are held, -1: none
+  bool dobj = false, dseg = false;
+  int64_t do_n = -1;
+  std::vector<int32_t> do_i[dv::DET_OBJ_I], do_seg;
+  std::vector<double> do_d[dv::DET_OBJ_D];
+  dv::StampTables tab;                          // the per-stamp tables of a pass, kept between passes and grown on demand
   std::vector<double> fmse_h;                     // host side of fmse
   // the catalogue of the measured passes (dv_field_set_pass_measure).  Resident rows: {shape[5], status,
   // place, field} of every stamp of every pass that took child sums, in call order; nrows of them are kept, the tail up
@@ -4151,6 +4157,46 @@ int dv_scene_detect_multiband(dv_ctx* c, const double* fields, int32_t M, int32_
                                 field, parent, npix, peak, flux, x, y, back, rms, D, labels, c->stream);
 }
 
+// the request of DESIGN 7zb as detect.hip reads it
+static DetectObjects detect_objects_of(const dv_detect_objects* o) {
+  return DetectObjects{{o->xmin, o->xmax, o->ymin, o->ymax, o->xpeak, o->ypeak, o->xvpeak, o->yvpeak, o->flag},
+                       {o->vpeak, o->dflux, o->x_iso, o->y_iso, o->x2, o->y2, o->xy},
+                       o->segmap};
+}
+
+int dv_scene_detect_objects(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, int32_t nb,
+                            const dv_detect_params* p, int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms,
+                            int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux, double* x, double* y,
+                            const dv_detect_weights* wt, const dv_detect_bands* b, const dv_detect_objects* objects) {
+  if (!c || !p) return DV_E_INVALID;
+  if (!objects) {
+    set_error("dv_scene_detect_objects: the objects request must be given (the other detect calls are the ones without it)");
+    return DV_E_INVALID;
+  }
+  if (wt && b) {
+    set_error("dv_scene_detect_objects: single-band weights and a band selection exclude each other");
+    return DV_E_INVALID;
+  }
+  if (wt && !wt->weights) {
+    set_error("dv_scene_detect_objects: a weights struct without weights");
+    return DV_E_INVALID;
+  }
+  if (p->thresh < 0.0) {
+    set_error("dv_scene_detect_objects: thresh must be >= 0, the moments' weights are the pixels above it (got %g)", p->thresh);
+    return DV_E_INVALID;
+  }
+  DV_HIP(hipSetDevice(c->device));
+  const DetectObjects oq = detect_objects_of(objects);
+  DetectWeights wq{nullptr, 0, 0, nullptr};
+  if (wt) wq = DetectWeights{wt->weights, wt->noise, wt->filter, nullptr};
+  DetectBands mb{};
+  if (b) mb = DetectBands{b->bands, b->k, b->band_weights, b->planes, b->planes != nullptr, b->noise, b->filter, nullptr, nullptr,
+                          nullptr, nullptr};
+  return scene_detect_objects(fields, nb, wt ? &wq : nullptr, b ? &mb : nullptr, oq, M, H, W, p->thresh, p->cont, p->minarea,
+                              p->nthresh, p->back_size, p->back_filter, p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out,
+                              offsets, globalrms, field, parent, npix, peak, flux, x, y, c->stream);
+}
+
 int dv_ctx_allreduce_host(dv_ctx* c, float* buf, int32_t n) {
   if (!c || !buf || n < 0 || n > 4096) return DV_E_INVALID;
   if (!c->comm || n == 0) return DV_OK;
@@ -6306,14 +6352,46 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
   const DetectBands mb{fs->dbands.data(), (int)fs->dbands.size(), fs->dbw.data(), nullptr, (bool)fs->dplanes, fs->dbnoise,
                        fs->dbfilter, nullptr, nullptr, nullptr, nullptr};
   *n_out = 0;
+  // (7zb) the object columns land in the set's host arrays, the segmap of the active fields in seg_a
+  DetectObjects oq{};
+  std::vector<int32_t> seg_a;
+  const size_t FF = (size_t)fs->F * fs->F;
+  if (fs->dobj) {
+    if (p->thresh < 0.0) {
+      set_error("dv_field_set_detect: with the object columns on thresh must be >= 0 (got %g)", p->thresh);
+      return DV_E_INVALID;
+    }
+    fs->do_n = -1;
+    for (int e = 0; e < DET_OBJ_I; ++e) {
+      fs->do_i[e].assign((size_t)std::max<int64_t>(cap, 0), 0);
+      oq.icol[e] = fs->do_i[e].data();
+    }
+    for (int e = 0; e < DET_OBJ_D; ++e) {
+      fs->do_d[e].assign((size_t)std::max<int64_t>(cap, 0), 0.0);
+      oq.dcol[e] = fs->do_d[e].data();
+    }
+    if (fs->dseg) {
+      seg_a.assign(std::max<size_t>((size_t)Ma * FF, 1), 0);
+      oq.segmap_h = seg_a.data();
+    }
+  }
+  const DetectObjects* oqp = fs->dobj ? &oq : nullptr;
   if (Ma > 0 && multi)
     DV_TRY(scene_detect_dev(src, Ma, fs->F, fs->F, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
                           p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, off.data(), grms.data(), field, parent,
-                          npix, peak, flux, x, y, fs->m->ctx->stream, nullptr, &mb));
+                          npix, peak, flux, x, y, fs->m->ctx->stream, nullptr, &mb, oqp));
   else if (Ma > 0)
     DV_TRY(scene_detect_dev(src, Ma, fs->F, fs->F, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
                           p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, off.data(), grms.data(), field, parent,
-                          npix, peak, flux, x, y, fs->m->ctx->stream, fs->dweights ? &wq : nullptr));
+                          npix, peak, flux, x, y, fs->m->ctx->stream, fs->dweights ? &wq : nullptr, nullptr, oqp));
+  if (fs->dobj) {
+    if (*n_out <= cap) fs->do_n = *n_out;
+    if (fs->dseg) {
+      fs->do_seg.assign((size_t)fs->M * FF, 0);
+      for (int a = 0; a < Ma; ++a)
+        std::copy(seg_a.begin() + (size_t)a * FF, seg_a.begin() + (size_t)(a + 1) * FF, fs->do_seg.begin() + (size_t)act[a] * FF);
+    }
+  }
   // the catalogue of the active fields in the numbering of the set: an inactive field has an empty range
   offsets[0] = 0;
   int a = 0;
@@ -6325,6 +6403,48 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
   }
   if (*n_out <= cap)
     for (int64_t i = 0; i < *n_out; ++i) field[i] = act[field[i]];
+  return DV_OK;
+}
+
+int dv_field_set_detect_objects(dv_field_set* fs, int32_t on, int32_t segmap_on) {
+  DV_TRY(field_set_live(fs, "dv_field_set_detect_objects"));
+  fs->dobj = on != 0;
+  fs->dseg = on != 0 && segmap_on != 0;
+  fs->do_n = -1;
+  for (auto& v : fs->do_i) std::vector<int32_t>().swap(v);
+  for (auto& v : fs->do_d) std::vector<double>().swap(v);
+  std::vector<int32_t>().swap(fs->do_seg);
+  return DV_OK;
+}
+
+int dv_field_set_detect_objects_read(dv_field_set* fs, int64_t n_expected, const dv_detect_objects* out) {
+  DV_TRY(field_set_live(fs, "dv_field_set_detect_objects_read"));
+  if (!out) return DV_E_INVALID;
+  if (!fs->dobj) {
+    set_error("dv_field_set_detect_objects_read: the object columns are off (dv_field_set_detect_objects)");
+    return DV_E_INVALID;
+  }
+  if (fs->do_n < 0) {
+    set_error("dv_field_set_detect_objects_read: no detection is kept (none since the switch went on, or its catalogue did not "
+              "fit its cap)");
+    return DV_E_INVALID;
+  }
+  if (n_expected != fs->do_n) {
+    set_error("dv_field_set_detect_objects_read: %lld rows expected, the last detection has %lld", (long long)n_expected,
+              (long long)fs->do_n);
+    return DV_E_INVALID;
+  }
+  if (out->segmap && !fs->dseg) {
+    set_error("dv_field_set_detect_objects_read: the segmap was not asked for (dv_field_set_detect_objects)");
+    return DV_E_INVALID;
+  }
+  const DetectObjects o = detect_objects_of(out);
+  const size_t n = (size_t)fs->do_n;
+  for (int e = 0; e < DET_OBJ_I; ++e)
+    if (o.icol[e]) std::copy(fs->do_i[e].begin(), fs->do_i[e].begin() + n, o.icol[e]);
+  for (int e = 0; e < DET_OBJ_D; ++e)
+    if (o.dcol[e]) std::copy(fs->do_d[e].begin(), fs->do_d[e].begin() + n, o.dcol[e]);
+  if (o.segmap_h) std::copy(fs->do_seg.begin(), fs->do_seg.end(), o.segmap_h);
   return DV_OK;
 }
 

@@ -285,8 +285,8 @@ class IterativeDeblendFieldBatch:
     def iterative_catalogue(self, mse_criterion=100.0, mode="reference", max_iterations=None, measure=False,
                             blendedness=False, return_fields=True, band=2, sigma0=3.0, tol=1e-10, max_iter=200,
                             match_radius=2.0, fit_flux=False, fit_weights=None, fit_sky=None, fit_nonneg=False,
-                            sky_sigma=None, min_pivot=1e-8, detect_bands=None, detect_band_weights=None, detect_weights=None,
-                            detect_noise=None, detect_filter="conv", detect_thresh=None, fit_groups=False):
+                            sky_sigma=None, min_pivot=1e-8, detect_shapes=False, detect_bands=None, detect_band_weights=None,
+                            detect_weights=None, detect_noise=None, detect_filter="conv", detect_thresh=None, fit_groups=False):
         """iterative_deblending() with a catalogue measured on the GPU: the same loop, the same
         list of M recarrays (kept in self.res_deblend), self.mse and fields, and with every argument behind the first
         three left at its default the same calls.  The arguments are a method of their own because the parameter list of
@@ -343,6 +343,12 @@ class IterativeDeblendFieldBatch:
             bands are taken from it; three-dimensional weights are refused.  detect_noise and detect_filter mean what they mean
             without detect_bands; detect_filter then needs no weights.
             (The detect_* arguments are keywords: pass them, and fit_groups behind them, by name.)
+        detect_shapes=True: every row carries the detection it was cut for, as the detector of its pass saw it
+            (FieldSet.set_detect_objects before the first pass): behind all other columns DETECT_COLUMNS,
+            det_npix, det_peak, det_flux, det_x, det_y, the box det_xmin .. det_ymax, the isophotal moments det_x2, det_y2,
+            det_xy with det_a, det_b, det_theta, and det_flag (bit 1: the detection was split off a blend, 2: cut by the
+            field's edge, 4: singular moments, 8: next to a pixel that does not count).  With or without measure; every other
+            column, self.mse and the fields keep their bits.  detect_thresh must then be >= 0.
 
         mse_criterion, mode, max_iterations: as in iterative_deblending."""
         if mode not in ("reference", "cumulative"):
@@ -388,6 +394,11 @@ class IterativeDeblendFieldBatch:
         if detect_bands is None and detect_weights is None and (detect_noise is not None or detect_filter != "conv"):
             raise ValueError("detect_noise and detect_filter need detect_weights: they belong to the weighted detector")
         detect_kw = {} if detect_thresh is None else {"thresh": float(detect_thresh)}
+        detect_shapes = bool(detect_shapes)
+        if detect_shapes and detect_thresh is not None and not float(detect_thresh) >= 0:
+            raise ValueError(f"detect_shapes=True needs detect_thresh >= 0 (the moments weight every pixel above it), "
+                             f"got {detect_thresh}")
+        shapes = [[] for _ in range(M)]      # detect_shapes: per field and pass, the detections of the kept rows
         if detect_bands is not None:
             from debvader_amd import engine as E
 
@@ -435,6 +446,8 @@ class IterativeDeblendFieldBatch:
                                     noise=detect_noise, filter_type=detect_filter)
             elif detect_weights is not None:
                 fs.set_detect_weights(detect_weights, noise=detect_noise, filter_type=detect_filter)
+            if detect_shapes:
+                fs.set_detect_objects(True)
             k = 0
             while active.any() and (max_iterations is None or k < int(max_iterations)):
                 det = fs.detect(active=active, **detect_kw)
@@ -469,6 +482,9 @@ class IterativeDeblendFieldBatch:
                         continue
                     counts[m] = n
                     steps[m].append(self._records(kept[m], dd[lo:hi], out["mse_center"][lo:hi], passed[lo:hi], total[m], k))
+                    if detect_shapes:
+                        rows_m = int(off[m]) + np.asarray(kept[m], dtype=np.int64)
+                        shapes[m].append({name: np.asarray(det[name[4:]])[rows_m] for name, _ in self.DETECT_COLUMNS})
                     if measure:
                         e = {k: out[k][lo:hi] for k in ("flux", "flux_err", "shape", "iters", "status")}
                         e["places"] = np.asarray(places[lo:hi], dtype=np.float64)
@@ -514,7 +530,23 @@ class IterativeDeblendFieldBatch:
                 self.sky_fit = {k: fit[k] for k in E.FIT_SKY_KEYS}
             if fit_nonneg:
                 self.nonneg_fit = {k: fit[k] for k in E.FIT_NONNEG_FIELD_KEYS}
+        if detect_shapes:
+            self.res_deblend = [self._with_detections(r, d) for r, d in zip(self.res_deblend, shapes)]
         return self.res_deblend
+
+    # what iterative_catalogue(detect_shapes=True) appends behind every other column: the detection of the row's pass
+    DETECT_COLUMNS = ([("det_npix", "<i4"), ("det_peak", "<f8"), ("det_flux", "<f8"), ("det_x", "<f8"), ("det_y", "<f8")]
+                      + [("det_" + k, "<i4") for k in ("xmin", "xmax", "ymin", "ymax")]
+                      + [("det_" + k, "<f8") for k in ("x2", "y2", "xy", "a", "b", "theta")] + [("det_flag", "<i4")])
+
+    def _with_detections(self, rec, passes):
+        """The records of one field with DETECT_COLUMNS behind them: per pass, the detector's rows of the kept stamps."""
+        out = np.recarray((len(rec),), dtype=rec.dtype.descr + self.DETECT_COLUMNS)
+        for k in rec.dtype.names:
+            out[k] = rec[k]
+        for name, t in self.DETECT_COLUMNS:
+            out[name] = np.concatenate([d[name] for d in passes]) if passes else np.zeros(0, dtype=t)
+        return out
 
     def _with_fit(self, rec, extra, fit, m, sky_sigma, weighted):
         """The catalogue of field m with the columns of the joint flux fit behind it: the rows of the fit joined by the

@@ -102,3 +102,67 @@ def detect_objects(field_image, ctx=None, bands=_SINGLE, band_weights=None, **kw
     ctx = ctx or E.default_context()
     r = ctx.scene_detect(r_band, **kw)
     return _distances(r["x"], r["y"], field_size)
+
+
+# ---- objects with shapes and a segmentation map -------------------------------------------------
+# sep's column names where the meaning is sep's, then this detector's own
+_OBJECT_COLUMNS = (("npix", np.int32), ("xmin", np.int32), ("xmax", np.int32), ("ymin", np.int32), ("ymax", np.int32),
+                   ("x", np.float64), ("y", np.float64), ("x2", np.float64), ("y2", np.float64), ("xy", np.float64),
+                   ("a", np.float64), ("b", np.float64), ("theta", np.float64), ("cxx", np.float64), ("cyy", np.float64),
+                   ("cxy", np.float64), ("flux", np.float64), ("peak", np.float64), ("xpeak", np.int32), ("ypeak", np.int32),
+                   ("flag", np.int32), ("parent", np.int32), ("dflux", np.float64), ("vpeak", np.float64),
+                   ("xvpeak", np.int32), ("yvpeak", np.int32), ("x_iso", np.float64), ("y_iso", np.float64))
+
+
+def object_dtype():
+    """the record type of extract_objects: sep's columns npix .. flag, then parent, dflux, vpeak, xvpeak, yvpeak, x_iso, y_iso"""
+    return np.dtype([(name, t) for name, t in _OBJECT_COLUMNS])
+
+
+def object_records(r, lo=0, hi=None):
+    """rows lo:hi of a result of Context.scene_detect_objects (or of FieldSet.detect after set_detect_objects) as a recarray
+    of object_dtype(); a, b, theta, cxx, cyy, cxy are derived from x2, y2, xy where the result does not carry them"""
+    hi = len(r["x"]) if hi is None else hi
+    if "a" not in r:
+        r = dict(r, **E.detect_object_shapes(r["x2"], r["y2"], r["xy"]))
+    rec = np.recarray(hi - lo, dtype=object_dtype())
+    for name, _ in _OBJECT_COLUMNS:
+        rec[name] = r[name][lo:hi]
+    return rec
+
+
+def extract_objects_batch(field_images, ctx=None, bands=_SINGLE, band_weights=None, segmentation_map=False, **kw):
+    """The objects of every field of (N, F, F, bands) with their shapes, as sep.extract gives them: a list of N recarrays of
+    object_dtype(), with segmentation_map=True a pair of that list and the maps (N, F, F) int32 (0: no object, k + 1: row k
+    of the field's recarray).  Arguments as in detect_objects_batch."""
+    a = np.asarray(field_images)
+    ctx = ctx or E.default_context()
+    if bands is not _SINGLE:
+        if a.ndim != 4:
+            raise ValueError(f"expected fields (N, F, F, bands), got {a.shape}")
+        kw = dict(kw)
+        sel = list(range(a.shape[3])) if bands is None else list(bands)
+        for name in ("weights", "mask"):
+            if kw.get(name) is not None:
+                p = np.asarray(kw[name])
+                kw[name] = p[:len(a)][:, :, :, sel] if p.ndim == 4 else p[:len(a)]
+        r = ctx.scene_detect_objects(a, bands=bands, band_weights=band_weights, segmentation_map=segmentation_map, **kw)
+    else:
+        if band_weights is not None:
+            raise ValueError("band_weights belong to the multi-band call: give bands")
+        r_band = _bands_r(a)
+        r = ctx.scene_detect_objects(r_band, segmentation_map=segmentation_map, **_planes_r(kw, len(r_band)))
+    off = r["offsets"]
+    recs = [object_records(r, off[i], off[i + 1]) for i in range(len(off) - 1)]
+    return (recs, r["segmap"]) if segmentation_map else recs
+
+
+def extract_objects(field_image, ctx=None, bands=_SINGLE, band_weights=None, segmentation_map=False, **kw):
+    """extract_objects_batch for one field (1, F, F, bands): the recarray, with segmentation_map=True the pair
+    (recarray, map (F, F)) that sep.extract(..., segmentation_map=True) returns."""
+    field_image = np.asarray(field_image)
+    if field_image.ndim != 4 or field_image.shape[0] < 1:
+        raise ValueError(f"expected a field (1, F, F, bands), got {field_image.shape}")
+    out = extract_objects_batch(field_image[:1], ctx=ctx, bands=bands, band_weights=band_weights,
+                                segmentation_map=segmentation_map, **kw)
+    return (out[0][0], out[1][0]) if segmentation_map else out[0]

@@ -508,6 +508,37 @@ def check_detect_band_planes(shape, weights, mask, noise, filter_type, thresh):
     return check_detect_weights(shape, weights, mask, noise, filter_type, thresh)
 
 
+OBJECT_KEYS = _lib.DETECT_OBJECT_INT + _lib.DETECT_OBJECT_DOUBLE
+OBJECT_DERIVED = ("a", "b", "theta", "cxx", "cyy", "cxy")
+
+
+def detect_object_shapes(x2, y2, xy) -> Dict[str, np.ndarray]:
+    """The ellipse of the isophotal moments, derived on the host as sigma, e1 and e2 are for the
+    catalogue: a, b the semi-axes, theta the position angle of a from the x axis (0 where both arguments of atan2 are 0),
+    and SExtractor's cxx, cyy, cxy."""
+    x2, y2, xy = (np.asarray(v, dtype=np.float64) for v in (x2, y2, xy))
+    p, d = x2 + y2, x2 - y2
+    t = np.sqrt(d * d / 4.0 + xy * xy)
+    det = x2 * y2 - xy * xy
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = dict(a=np.sqrt(p / 2.0 + t), b=np.sqrt(np.maximum(p / 2.0 - t, 0.0)),
+                   theta=np.where((xy == 0.0) & (d == 0.0), 0.0, 0.5 * np.arctan2(2.0 * xy, d)),
+                   cxx=y2 / det, cyy=x2 / det, cxy=-2.0 * xy / det)
+    return out
+
+
+def _object_buffers(cap, segmap_shape=None, columns=True):
+    """(arrays, dv_detect_objects) for cap rows: the columns (when asked for) and the segmap (when a shape is given)"""
+    arr = {}
+    if columns:
+        arr.update({k: np.zeros(cap, np.int32) for k in _lib.DETECT_OBJECT_INT})
+        arr.update({k: np.zeros(cap, np.float64) for k in _lib.DETECT_OBJECT_DOUBLE})
+    if segmap_shape is not None:
+        arr["segmap"] = np.zeros(segmap_shape, np.int32)
+    st = _lib.DvDetectObjects(**{k: (_ip(v) if v.dtype == np.int32 else _dp(v)) for k, v in arr.items()})
+    return arr, st
+
+
 def counting_pixels(w):
     """the pixels that count: 0 < w < inf (NaN does not)"""
     with np.errstate(invalid="ignore"):
@@ -1393,6 +1424,91 @@ class Context:
             cap = n.value
         out = {key: v[:n.value].copy() for key, v in cat.items()}
         out.update(offsets=offsets, globalrms=grms, band_globalrms=bgrms, bad_meshes=bad, **maps)
+        return out
+
+    def scene_detect_objects(self, fields, bands=None, band_weights=None, thresh: float = 1.5, minarea: int = 4,
+                             nthresh: int = 64, cont: float = 1e-5, filter_kernel=None, back_size: int = 64,
+                             back_filter: int = 3, workspace_bytes: int = 0, weights=None, mask=None, noise=None,
+                             filter_type: str = "conv", segmentation_map: bool = False,
+                             columns: bool = True) -> Dict[str, np.ndarray]:
+        """The detector with the object segmentation map and the isophotal shapes (dv_scene_detect_objects, DESIGN.md
+        section 7zb).
+
+        fields (M, H, W): scene_detect, argument for argument (weights / mask: its weighted call); fields (M, H, W, nb):
+        scene_detect_multiband with bands, band_weights and the planes in weights / mask.  Returns the dictionary of that call
+        (without maps) plus, per object over the pixels the deblender gave it: the inclusive box xmin, xmax, ymin, ymax;
+        xpeak, ypeak, the pixel of peak; vpeak at xvpeak, yvpeak, the largest background-subtracted value; dflux, the sum of
+        the thresholded map D; x_iso, y_iso and x2, y2, xy, the first and second moments with weights D (SExtractor's
+        singular rule applied); flag, bits 1 blended, 2 at the border, 4 singular rule applied, 8 next to a pixel that does
+        not count; the derived a, b, theta, cxx, cyy, cxy; and with segmentation_map segmap (M, H, W) int32: 0 outside
+        every object, k + 1 on the pixels of row offsets[f] + k of field f.  columns=False leaves the columns out (the
+        segmap alone).  thresh must be >= 0."""
+        if not float(thresh) >= 0:
+            raise ValueError(f"the object shapes weight every pixel with D > thresh: thresh must be >= 0, got {thresh}")
+        if not (columns or segmentation_map):
+            raise ValueError("nothing asked for: columns, segmentation_map or both")
+        f = np.ascontiguousarray(fields, dtype=np.float64)
+        multi = f.ndim == 4
+        bstruct, wstruct, bgrms = None, None, None
+        if multi:
+            if min(f.shape[1:]) < 1:
+                raise ValueError(f"expected fields (M, H, W, bands), got {f.shape}")
+            M, H, W, nb = f.shape
+            sel, cw = check_detect_bands(nb, bands, band_weights)
+            planes, noise_id, filter_id = check_detect_band_planes((M, H, W, len(sel)), weights, mask, noise, filter_type, thresh)
+            if not np.isfinite(f).all():
+                fsel = f[:, :, :, sel]
+                if planes is None and not np.isfinite(fsel).all():
+                    raise ValueError("the fields must be finite in the selected bands")
+                if planes is not None and not np.isfinite(fsel[counting_pixels(planes)]).all():
+                    raise ValueError("the fields must be finite in every selected band where that band counts (0 < weight < inf)")
+            check_detect_args(np.zeros((0, H, W)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
+                              workspace_bytes)
+            bstruct = _lib.DvDetectBands(_ip(sel), len(sel), _dp(cw), None if planes is None else _dp(planes), noise_id,
+                                         filter_id)
+        else:
+            if bands is not None or band_weights is not None:
+                raise ValueError("bands and band_weights belong to fields (M, H, W, bands)")
+            nb = 0
+            wts = None
+            if weights is not None or mask is not None:
+                shape = np.shape(fields)
+                if len(shape) != 3:
+                    raise ValueError(f"expected fields (M, H, W) or (M, H, W, bands), got {shape}")
+                wts, noise_id, filter_id = check_detect_weights(shape, weights, mask, noise, filter_type, thresh)
+                wstruct = _lib.DvDetectWeights(_dp(wts), noise_id, filter_id)
+            elif noise is not None or filter_type != "conv":
+                raise ValueError("noise and filter_type belong to the weighted call: give weights, a mask or both")
+            f = check_detect_args(f, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter, workspace_bytes,
+                                  weights=wts)
+            M, H, W = f.shape
+        kern, kptr, kh, kw = None, None, 0, 0
+        if filter_kernel is not None:
+            kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
+            kptr, (kh, kw) = kern.ctypes.data_as(C.POINTER(C.c_double)), kern.shape
+        params = _lib.DvDetectParams(float(thresh), float(cont), int(minarea), int(nthresh), int(back_size),
+                                     int(back_filter), kptr, kh, kw, int(workspace_bytes))
+        offsets = np.zeros(M + 1, np.int64)
+        grms = np.zeros(M, np.float64)
+        cap = max(4096, 64 * M, M * H * W // 1024)
+        while True:                                   # the catalog's size is known after the call: grow once if needed
+            cat = {key: np.empty(cap, np.int32 if key in ("field", "parent", "npix") else np.float64)
+                   for key in self.CATALOG_KEYS}
+            obj, ostruct = _object_buffers(cap, (M, H, W) if segmentation_map else None, columns)
+            n = C.c_int64()
+            check(lib.dv_scene_detect_objects(
+                self._h, _dp(f), M, H, W, nb, C.byref(params), cap, C.byref(n), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                _dp(grms), *[_ip(cat[key]) if cat[key].dtype == np.int32 else _dp(cat[key]) for key in self.CATALOG_KEYS],
+                None if wstruct is None else C.byref(wstruct), None if bstruct is None else C.byref(bstruct),
+                C.byref(ostruct)))
+            if n.value <= cap:
+                break
+            cap = n.value
+        out = {key: v[:n.value].copy() for key, v in cat.items()}
+        out.update(offsets=offsets, globalrms=grms)
+        out.update({key: (v if key == "segmap" else v[:n.value].copy()) for key, v in obj.items()})
+        if columns:
+            out.update(detect_object_shapes(out["x2"], out["y2"], out["xy"]))
         return out
 
     def close(self):
@@ -2441,13 +2557,24 @@ class FieldSet:
         check(lib.dv_field_set_detect_bands(h, _ip(sel), len(sel), _dp(cw), _dp(planes), noise_id, filter_id))
         self._detect_bands = True
 
+    def set_detect_objects(self, on: bool = True, segmentation_map: bool = False):
+        """Every later detect() also returns the columns of Context.scene_detect_objects (dv_field_set_detect_objects,
+        DESIGN.md section 7zb), with segmentation_map also segmap (M, F, F), 0 in fields that were not active.
+        set_detect_objects(False) goes back to the catalogue alone.  While on, detect() refuses thresh < 0."""
+        check(lib.dv_field_set_detect_objects(self._handle(), int(bool(on)), int(bool(on) and bool(segmentation_map))))
+        self._detect_objects = (bool(on), bool(on) and bool(segmentation_map))
+
     def detect(self, active=None, thresh: float = 1.5, minarea: int = 4, nthresh: int = 64, cont: float = 1e-5,
                filter_kernel=None, back_size: int = 64, back_filter: int = 3, workspace_bytes: int = 0) -> Dict[str, np.ndarray]:
         """Context.scene_detect on band 2 of the working residuals, which do not leave the GPU (dv_field_set_detect).
         active: (M,) booleans, None for all fields; an inactive field gets an empty catalogue range.  Returns the
-        catalogue, offsets (M + 1,) and globalrms (M,) of scene_detect, without maps, in the set's field numbering."""
+        catalogue, offsets (M + 1,) and globalrms (M,) of scene_detect, without maps, in the set's field numbering; after
+        set_detect_objects also the columns of Context.scene_detect_objects."""
         h = self._handle()
         M, F = self.shape[0], self.shape[1]
+        objects_on, segmap_on = getattr(self, "_detect_objects", (False, False))
+        if objects_on and not float(thresh) >= 0:
+            raise ValueError(f"with the object columns on thresh must be >= 0, got {thresh}")
         check_detect_args(np.zeros((0, F, F)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
                           workspace_bytes)
         if getattr(self, "_detect_noise", None) == _lib.DETECT_NOISE["absolute"] and not float(thresh) > 0:
@@ -2483,6 +2610,11 @@ class FieldSet:
             cap = n.value
         out = {k: v[:n.value].copy() for k, v in cat.items()}
         out.update(offsets=offsets, globalrms=grms)
+        if objects_on:
+            obj, ostruct = _object_buffers(n.value, (M, F, F) if segmap_on else None)
+            check(lib.dv_field_set_detect_objects_read(h, n.value, C.byref(ostruct)))
+            out.update(obj)
+            out.update(detect_object_shapes(out["x2"], out["y2"], out["xy"]))
         return out
 
     def deblend_pass(self, starts, places, field_ptr, seed=0) -> Dict[str, np.ndarray]:

@@ -463,6 +463,32 @@ int dv_scene_detect_multiband(dv_ctx* ctx, const double* fields, int32_t M, int3
                               double* globalrms, int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux,
                               double* x, double* y, double* back, double* rms, double* V, double* Wt, double* D,
                               int32_t* labels, const dv_detect_bands* bands, double* band_globalrms, int32_t* bad_meshes);
+/* dv_scene_detect_objects: the detector with the object segmentation map and the isophotal shapes of DESIGN.md section 7zb.
+ * nb = 0 with bands = NULL: fields [M][H][W], dv_scene_detect or, with weights, dv_scene_detect_weighted; bands given: fields
+ * [M][H][W][nb], dv_scene_detect_multiband (weights must then be NULL).  offsets, globalrms and the seven catalogue arrays
+ * have the bits of that call; no back / rms / D / labels come back.  Per object, over the pixels the deblender assigned to
+ * it, with D the thresholded map (the significance S in the weighted and multi-band calls) and v the map flux sums (V):
+ * the inclusive box xmin xmax ymin ymax; xpeak ypeak, the pixel of peak (max D), and vpeak at xvpeak yvpeak, the largest v,
+ * ties to the smallest raster index; dflux = sum D; x_iso, y_iso = sum D c / sum D, sum D r / sum D; x2, y2, xy the second
+ * moments about that centre with weights D, to which SExtractor's singular rule is applied (x2 y2 - xy xy < 1/144: x2 and y2
+ * gain 1/12); flag: DV_DETECT_FLAG_*.  segmap [M][H][W]: 0 outside every object, k + 1 on the pixels of the object in row
+ * offsets[f] + k of field f.  Every pointer of the struct is nullable; the columns [cap] are written like the catalogue,
+ * only when *n_out <= cap, the segmap always.
+ * Refused before any GPU work (DV_E_INVALID, the engine stays usable): what the corresponding call refuses, a null `objects`,
+ * weights together with bands, nb != 0 without bands, thresh < 0 (the weights D must be positive). */
+#define DV_DETECT_FLAG_BLENDED 1   /* the object's component gave more than one object */
+#define DV_DETECT_FLAG_BORDER 2    /* the box touches the field's border */
+#define DV_DETECT_FLAG_SINGULAR 4  /* the singular rule was applied */
+#define DV_DETECT_FLAG_MASKED 8    /* weighted / multi-band: a pixel among the 8 neighbours of one of its pixels does not count */
+typedef struct dv_detect_objects {
+  int32_t *xmin, *xmax, *ymin, *ymax, *xpeak, *ypeak, *xvpeak, *yvpeak, *flag; /* [cap] */
+  double *vpeak, *dflux, *x_iso, *y_iso, *x2, *y2, *xy;                        /* [cap] */
+  int32_t* segmap;                                                             /* [M][H][W] */
+} dv_detect_objects;
+int dv_scene_detect_objects(dv_ctx* ctx, const double* fields, int32_t M, int32_t H, int32_t W, int32_t nb,
+                            const dv_detect_params* params, int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms,
+                            int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux, double* x, double* y,
+                            const dv_detect_weights* weights, const dv_detect_bands* bands, const dv_detect_objects* objects);
 
 /* ---- catalogue measurement: fluxes and adaptive moments per galaxy ----
  * The reference ships an empty debvader.measure package; the measurement is defined here, float64 throughout.  Per stamp,
@@ -992,6 +1018,16 @@ int dv_field_set_detect_weights(dv_field_set* set, const double* weights, int32_
  * while a selection is held); a closed set: DV_E_STATE. */
 int dv_field_set_detect_bands(dv_field_set* set, const int32_t* bands, int32_t k, const double* band_weights,
                               const double* planes, int32_t noise, int32_t filter);
+/* dv_field_set_detect_objects: on != 0: every later dv_field_set_detect also computes the columns of
+ * dv_scene_detect_objects (segmap_on != 0: and the segmap) and the set keeps those of its last detection on the host;
+ * dv_field_set_detect itself keeps its signature and its outputs.  on = 0 drops them.
+ * dv_field_set_detect_objects_read copies them out: the non-null columns of `out` [n_expected], rows as in the catalogue of
+ * that detection, and segmap [M][F][F] in the set's numbering, 0 in fields that were not active.  Refused (DV_E_INVALID):
+ * the switch off, no detection kept (none since the switch went on, or its catalogue did not fit its cap), n_expected
+ * other than that detection's *n_out, a segmap asked for with segmap_on = 0, a null `out`; a closed set: DV_E_STATE.  While
+ * the switch is on dv_field_set_detect refuses thresh < 0. */
+int dv_field_set_detect_objects(dv_field_set* set, int32_t on, int32_t segmap_on);
+int dv_field_set_detect_objects_read(dv_field_set* set, int64_t n_expected, const dv_detect_objects* out);
 int dv_field_set_pass(dv_field_set* set, const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
                       uint64_t seed, double* mse_center, double* field_mse);
 int dv_field_set_read(dv_field_set* set, int32_t which, double* out);

@@ -15,6 +15,11 @@ interleaved six-band fields whose band 2 is the single-band leg's field), the si
 in one process as above.
 
     python tools/detect_bench.py --bands 0,1,2,3,4,5 [--filter matched] [--runs 5]
+
+--objects: the same two workloads through Context.scene_detect_objects: the existing call, the new call
+with the object columns, and the new call with the columns and the segmentation map, the three legs alternating in one process.
+
+    python tools/detect_bench.py --objects [--runs 5]
 """
 import argparse
 import json
@@ -126,6 +131,30 @@ def main_bands(a, ctx, batch, tile):
     print(json.dumps(out))
 
 
+def main_objects(a, ctx, batch, tile):
+    ctx.scene_detect_objects(batch[:2], segmentation_map=True)         # warm-up of the objects kernel
+    legs = (("existing", lambda f: ctx.scene_detect(f)), ("columns", lambda f: ctx.scene_detect_objects(f)),
+            ("columns_segmap", lambda f: ctx.scene_detect_objects(f, segmentation_map=True)))
+    out = {"batch": a.batch, "F": batch.shape[1], "tile": a.tile, "runs": a.runs}
+    for name, f, scale in (("batch", batch, 1.0), ("tile", tile, 1e3)):
+        times = {leg: [] for leg, _ in legs}
+        res = {}
+        for _ in range(a.runs):                                        # the three legs alternating
+            for leg, fn in legs:
+                t0 = time.perf_counter()
+                res[leg] = fn(f)
+                times[leg].append(time.perf_counter() - t0)
+        unit = "seconds" if name == "batch" else "ms"
+        for leg, _ in legs:
+            t = times[leg]
+            out[f"{name}_{leg}_{unit}_median"] = round(scale * float(np.median(t)), 5)
+            out[f"{name}_{leg}_{unit}_min_max"] = [round(scale * min(t), 5), round(scale * max(t), 5)]
+            out[f"{name}_{leg}_objects"] = int(len(res[leg]["x"]))
+        for leg in ("columns", "columns_segmap"):
+            out[f"{name}_{leg}_over_existing"] = round(float(np.median(times[leg]) / np.median(times["existing"])), 4)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -137,6 +166,8 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--bands", default=None, help="comma-separated band numbers: alternate the single-band and the multi-band "
                                                   "detector")
+    ap.add_argument("--objects", action="store_true", help="alternate the existing call and Context.scene_detect_objects "
+                                                           "without and with the segmentation map")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     F = 259
@@ -149,6 +180,8 @@ def main():
         return main_weighted(a, ctx, batch, tile)
     if a.bands:
         return main_bands(a, ctx, batch, tile)
+    if a.objects:
+        return main_objects(a, ctx, batch, tile)
     tb, rb = _best(lambda: ctx.scene_detect(batch), a.repeat)
     tt, rt = _best(lambda: ctx.scene_detect(tile), a.repeat)
     t0 = time.perf_counter()
