@@ -7,6 +7,8 @@
 #include <utility>
 #include <vector>
 
+struct dv_detect_params;   // include/debvader_hip.h: the detector reads the C ABI's parameter block as it is (DetectRequest)
+
 namespace dv {
 
 // status codes (mirrored in include/debvader_hip.h)
@@ -632,15 +634,8 @@ int scene_fit_flux_sky_gram(const float* stamps_h, const int32_t* places_h, int6
 struct DetectWeights {
   const double* weights_h;
   int noise, filter;
-  int32_t* bad_meshes_h;
+  int32_t* bad_meshes_h = nullptr;
 };
-// batched source detection on one band (detect.hip): host float64 fields in, host catalog out
-int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
-                 int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
-                 int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
-                 int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s,
-                 const DetectWeights* wq = nullptr);
 // the same detector on one band of fields that lie in device memory (dv_field_set_detect): field i of the call is band
 // `band` of the [H][W][nb] field number which_h[i] of the stack fields_dev, gathered into the detector's planes on the GPU
 struct DetectDevSrc {
@@ -661,10 +656,10 @@ struct DetectBands {
   const double* planes_h;
   bool has_planes;
   int noise, filter;
-  double* band_grms_h;
-  int32_t* bad_meshes_h;
-  double* V_h;
-  double* Wt_h;
+  double* band_grms_h = nullptr;
+  int32_t* bad_meshes_h = nullptr;
+  double* V_h = nullptr;
+  double* Wt_h = nullptr;
 };
 // the argument checks of a DetectBands for fields of nb bands, before any GPU work (who: the caller's name in the message)
 int detect_bands_check(const char* who, const int32_t* bands, int k, const double* c, int nb, int noise, int filter);
@@ -677,25 +672,27 @@ struct DetectObjects {
   double* dcol[DET_OBJ_D];
   int32_t* segmap_h;
 };
-int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
-                     int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
-                     int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
-                     int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                     hipStream_t s, const DetectWeights* wq = nullptr, const DetectBands* mb = nullptr,
-                     const DetectObjects* oq = nullptr);
-// the three host calls behind one entry with the outputs of DESIGN 7zb and no maps: nb = 0 and mb null: fields [M][H][W],
-// unweighted or, with wq, weighted; mb given: fields [M][H][W][nb] (wq null)
-int scene_detect_objects(const double* fields_h, int nb, const DetectWeights* wq, const DetectBands* mb, const DetectObjects& oq,
-                         int M, int H, int W, double thresh, double cont, int minarea, int nthresh, int back_size,
-                         int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes, int64_t cap,
-                         int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h, int32_t* parent_h,
-                         int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h, hipStream_t s);
-// host fields [M][H][W][nb], interleaved, uploaded as they are and gathered on the GPU
-int scene_detect_multiband(const double* fields_h, int nb, const DetectBands& mb, int M, int H, int W, double thresh, double cont,
-                           int minarea, int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
-                           int64_t workspace_bytes, int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h,
-                           int32_t* field_h, int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h,
-                           double* y_h, double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s);
+// the catalogue of a detection, host arrays: offsets_h [M + 1], globalrms_h [M] and *n_out are always written, the seven
+// columns [cap] only when *n_out <= cap (the caller then calls again with cap >= *n_out: the result is deterministic)
+struct DetectCatalog {
+  int64_t cap; int64_t* n_out; int64_t* offsets_h; double* globalrms_h;
+  int32_t *field_h, *parent_h, *npix_h; double *peak_h, *flux_h, *x_h, *y_h;
+};
+// One detection, as every caller asks for it (detect.hip): M fields of H x W pixels, from the host - fields_h
+// [M][H][W] with nb = 0, or interleaved [M][H][W][nb] with a band selection, uploaded as they are and gathered on the GPU - or,
+// with dev, from a stack in device memory; par as the C ABI carries it; the modes weights (7z), bands (7za; weights null) and
+// objects (7zb), each null when not asked for; the maps [M][H][W], each nullable (with bands back_h and rms_h are
+// [M][H][W][k], and V and Wt come back through the DetectBands); the catalogue.
+struct DetectRequest {
+  const double* fields_h = nullptr; int nb = 0;
+  int M = 0, H = 0, W = 0;
+  const dv_detect_params* par = nullptr;
+  const DetectDevSrc* dev = nullptr;
+  const DetectWeights* weights = nullptr; const DetectBands* bands = nullptr; const DetectObjects* objects = nullptr;
+  double *back_h = nullptr, *rms_h = nullptr, *D_h = nullptr; int32_t* labels_h = nullptr;
+  DetectCatalog cat{};
+};
+int scene_detect(const DetectRequest& rq, hipStream_t s);
 
 // Strip form of the stride-1 3x3 gather-GEMM for the 32-channel high-resolution layers (gconv_strip.hip)
 struct GStripParams {

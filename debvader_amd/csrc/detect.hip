@@ -33,6 +33,7 @@
 // the field's earlier components.
 // fp64 VALU and integer work; nothing here has a matrix shape for MFMA.
 #include "common.h"
+#include "../../include/debvader_hip.h"   // dv_detect_params
 
 #include <algorithm>
 #include <cmath>
@@ -518,23 +519,40 @@ inline unsigned nblk(long total) { return (unsigned)((total + DT - 1) / DT); }
 // (7za) k > 0: k data planes, k planes of P when given, k x the mesh grids and row splines, the combined weight Wt, and for a
 // host source the interleaved staging lines of max(nb, k) values per pixel
 // (7zb) objects: the slots of the new columns and every job's segmap base; segmap: 4 bytes per pixel
-long field_bytes(long H, long W, long ny, long nx, int minarea, bool maps, bool weighted, int k = 0, bool planes = false,
-                 int stage = 0, bool objects = false, bool segmap = false) {
-  const long HW = H * W, capn = HW / minarea + 1;
+// DetectMode: what a call runs, derived once from its request; every stage, field_bytes and DetectWork::alloc read it.
+// DetectGeom: H x W pixel fields on ny x nx background meshes, HW pixels and at most ccap components of >= minarea pixels each.
+struct DetectMode {
+  bool dev;                        // the fields lie in device memory (nwhich field numbers, 0 for a host source)
+  int nwhich;
+  bool weighted;                   // (7z) single-band weights
+  int k;                           // (7za) the selected bands, 0: one band
+  bool planes, planes_abs;         // (7za) planes are given; and their noise is absolute
+  int nb_src, stage_nb;            // bands of the source; values per pixel of a host multi-band source's staging lines
+  bool absolute, matched;          // T = thresh, not thresh * globalrms; the matched filter
+  bool objects, segmap;            // (7zb) the object columns; and the segmap
+  bool back, rms, labels, maps;    // the maps asked for; maps: any of back, rms, D, labels
+  bool multi() const { return k > 0; }
+  bool wplanes() const { return weighted || planes; }    // the WEIGHTED background kernels run: wt and nbad exist
+  int kk() const { return k > 0 ? k : 1; }               // planes per field
+};
+struct DetectGeom { int H, W, ny, nx; long HW, ccap; };
+
+long field_bytes(const DetectGeom& g, const DetectMode& md) {
+  const long H = g.H, HW = g.HW, ny = g.ny, nx = g.nx, capn = g.ccap, k = md.k;
   long b = HW * (8 + 8 + 8 + 4 * 7);                          // data v D | par lab area cmin cmax rmax lidx
-  if (maps) b += HW * (8 + 8 + 4);                            // back rms labels
-  if (weighted) b += HW * 8 + 4;                              // the weight plane, the bad-mesh count
+  if (md.maps) b += HW * (8 + 8 + 4);                         // back rms labels
+  if (md.weighted) b += HW * 8 + 4;                           // the weight plane, the bad-mesh count
   if (k > 0) {
-    b += HW * 8 * (k - 1) + HW * 8 + (planes ? HW * 8 * k : 0) + HW * 8 * stage;
-    if (maps) b += HW * (8 + 8) * (k - 1);
-    b += (k - 1) * (H * nx * 4 * 8 + ny * nx * 6 * 8) + (long)k * (8 + 4) + 8;   // ... band globalrms, bad meshes, globalrms
+    b += HW * 8 * (k - 1) + HW * 8 + (md.planes ? HW * 8 * k : 0) + HW * 8 * md.stage_nb;
+    if (md.maps) b += HW * (8 + 8) * (k - 1);
+    b += (k - 1) * (H * nx * 4 * 8 + ny * nx * 6 * 8) + k * (8 + 4) + 8;   // ... band globalrms, bad meshes, globalrms
   }
   b += H * nx * 4 * 8 + ny * nx * 6 * 8;                      // row splines, mesh grids
   b += capn * 5 * 4;                                          // component table
   b += HW * (8 + 6 * 4) + capn * ((2 + OBJ_D) * 8 + 3 * 4);   // deblend scratch
   b += capn * ((long)sizeof(DbJob) + 4 * 4 + 4 * 8);          // jobs and catalog slots
-  if (objects) b += capn * (OBJ_I * 4 + DET_OBJ_D * 8 + 4);
-  if (segmap) b += HW * 4;
+  if (md.objects) b += capn * (OBJ_I * 4 + DET_OBJ_D * 8 + 4);
+  if (md.segmap) b += HW * 4;
   return b;
 }
 
@@ -559,7 +577,7 @@ __global__ __launch_bounds__(DT) void bands_gather_kernel(const double* __restri
   for (int j = 0; j < k; ++j) data[((long)blockIdx.y * k + j) * HW + e] = line[bands[j]];
 }
 
-// the device buffers of detect_impl.  DetectWork: the workspace of one launch's fields (chunk fields of H x W pixels on
+// the device buffers of scene_detect.  DetectWork: the workspace of one launch's fields (chunk fields of H x W pixels on
 // ny x nx background meshes); back / rms / labout exist only when the caller wants those maps, wdev (the nwhich field numbers
 // of a device source) only when the fields come from device memory.
 struct DetectWork {
@@ -571,26 +589,25 @@ struct DetectWork {
   DevBuf<double> cw, fgrms, stage, cband;
   DevBuf<int> bsel;
   DevBuf<int> seg;                                   // (7zb) the launch's segmap, when asked for
-  int alloc(int chunk, int H, int W, int ny, int nx, long ccap, size_t ktaps, size_t ccoef, bool want_back, bool want_rms,
-            bool want_labels, int nwhich, bool weighted, int bands = 0, int stage_nb = 0, bool want_seg = false) {
-    if (want_seg) DV_TRY(seg.alloc((size_t)chunk * H * W));
-    const size_t kk = bands > 0 ? (size_t)bands : 1;
-    const size_t px = (size_t)chunk * H * W, grid = kk * chunk * ny * nx, rows = kk * chunk * H * nx;
+  int alloc(int chunk, const DetectGeom& g, const DetectMode& md, size_t ktaps, size_t ccoef) {
+    if (md.segmap) DV_TRY(seg.alloc((size_t)chunk * g.H * g.W));
+    const size_t kk = (size_t)md.kk();
+    const size_t px = (size_t)chunk * g.H * g.W, grid = kk * chunk * g.ny * g.nx, rows = kk * chunk * g.H * g.nx;
     DV_TRY(data.alloc(kk * px));
     for (DevBuf<double>* b : {&v, &D}) DV_TRY(b->alloc(px));
     for (DevBuf<int>* b : {&par, &lab, &area, &cmin, &cmax, &rmax, &lidx}) DV_TRY(b->alloc(px));
     for (DevBuf<double>* b : {&mb, &mr, &fbk, &frm, &d2b, &d2r}) DV_TRY(b->alloc(grid));
     for (DevBuf<double>* b : {&gb, &gb2, &gr, &gr2}) DV_TRY(b->alloc(rows));
-    DV_TRY(grms.alloc(kk * chunk)); DV_TRY(ncomp.alloc((size_t)chunk)); DV_TRY(table.alloc((size_t)chunk * ccap * 5));
+    DV_TRY(grms.alloc(kk * chunk)); DV_TRY(ncomp.alloc((size_t)chunk)); DV_TRY(table.alloc((size_t)chunk * g.ccap * 5));
     DV_TRY(kdev.alloc(ktaps)); DV_TRY(cdev.alloc(ccoef));
-    if (want_back) DV_TRY(back.alloc(kk * px));
-    if (want_rms) DV_TRY(rms.alloc(kk * px));
-    if (want_labels) DV_TRY(labout.alloc(px));
-    if (nwhich > 0) DV_TRY(wdev.alloc((size_t)nwhich));
-    if (weighted) { DV_TRY(wt.alloc(kk * px)); DV_TRY(nbad.alloc(kk * chunk)); }   // (7z) the weight planes, the bad meshes
-    if (bands > 0) {
+    if (md.back) DV_TRY(back.alloc(kk * px));
+    if (md.rms) DV_TRY(rms.alloc(kk * px));
+    if (md.labels) DV_TRY(labout.alloc(px));
+    if (md.nwhich > 0) DV_TRY(wdev.alloc((size_t)md.nwhich));
+    if (md.wplanes()) { DV_TRY(wt.alloc(kk * px)); DV_TRY(nbad.alloc(kk * chunk)); }   // (7z) the weight planes, the bad meshes
+    if (md.multi()) {
       DV_TRY(cw.alloc(px)); DV_TRY(fgrms.alloc((size_t)chunk)); DV_TRY(bsel.alloc(2 * kk)); DV_TRY(cband.alloc(kk));
-      if (stage_nb > 0) DV_TRY(stage.alloc(px * stage_nb));
+      if (md.stage_nb > 0) DV_TRY(stage.alloc(px * md.stage_nb));
     }
     return OK;
   }
@@ -615,48 +632,45 @@ struct DeblendScratch {
   }
 };
 
-// the detector: the fields come from the host (fields_h) or, with `dev`, from a stack that lies in device memory; with `wq`
-// the weighted rules of DESIGN 7z, the planes coming from where the fields come from
-// ; with `mb` the multi-band source of DESIGN 7za (wq null): the fields are interleaved [M][H][W][nb] (nb_h of a host source),
-// back_h / rms_h are [M][H][W][k]
-int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWeights* wq, const DetectBands* mb, int nb_h, int M,
-                int H, int W, double thresh, double cont, int minarea,
-                int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
-                int64_t workspace_bytes, int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h,
-                int32_t* field_h, int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h,
-                double* y_h, double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s,
-                const DetectObjects* oq = nullptr) {
+// ---- the host path: the checks, the mode, and one call's stages (DetectRun) in the order they run --------------------
+// 1. the argument checks, before any GPU work, in the order the refusals have always had
+int detect_check(const DetectRequest& rq) {
+  const DetectDevSrc* dev = rq.dev;
+  const DetectWeights* wq = rq.weights;
+  const DetectBands* mb = rq.bands;
+  const DetectCatalog& c = rq.cat;
   if (dev && (!dev->fields_dev || !dev->which_h || dev->nb < 1 || dev->band < 0 || dev->band >= dev->nb)) {
     set_error("scene_detect: bad device source");
     return E_INVALID;
   }
-  if ((!fields_h && !dev) || M < 0 || H < 1 || W < 1 || H > DIM_MAX || W > DIM_MAX || (long)H * W > 0x7fffffffL ||
-      !std::isfinite(thresh) || !std::isfinite(cont) || minarea < 1 || nthresh < 1 || nthresh > 1024 ||
-      back_size < 1 || back_size > 64 || back_filter < 1 || back_filter > MF_MAX || (back_filter & 1) == 0 || cap < 0 ||
-      !n_out || !offsets_h || !globalrms_h || workspace_bytes < 0 ||
-      (cap > 0 && (!field_h || !parent_h || !npix_h || !peak_h || !flux_h || !x_h || !y_h))) {
+  const dv_detect_params* p = rq.par;
+  if (!p || (!rq.fields_h && !dev) || rq.M < 0 || rq.H < 1 || rq.W < 1 || rq.H > DIM_MAX || rq.W > DIM_MAX ||
+      (long)rq.H * rq.W > 0x7fffffffL || !std::isfinite(p->thresh) || !std::isfinite(p->cont) || p->minarea < 1 ||
+      p->nthresh < 1 || p->nthresh > 1024 || p->back_size < 1 || p->back_size > 64 || p->back_filter < 1 ||
+      p->back_filter > MF_MAX || (p->back_filter & 1) == 0 || c.cap < 0 || !c.n_out || !c.offsets_h || !c.globalrms_h ||
+      p->workspace_bytes < 0 ||
+      (c.cap > 0 && (!c.field_h || !c.parent_h || !c.npix_h || !c.peak_h || !c.flux_h || !c.x_h || !c.y_h))) {
     set_error("scene_detect: bad arguments");
     return E_INVALID;
   }
-  if (oq && thresh < 0.0) {                             // (7zb) the moments' weights D > T must be positive
-    set_error("scene_detect: the object shapes and the segmap need thresh >= 0 (got %g)", thresh);
+  if (rq.objects && p->thresh < 0.0) {                  // (7zb) the moments' weights D > T must be positive
+    set_error("scene_detect: the object shapes and the segmap need thresh >= 0 (got %g)", p->thresh);
     return E_INVALID;
   }
-  const int nbk = mb ? mb->k : 0, nb_src = dev ? dev->nb : nb_h;
   if (mb) {
     if (wq) {
       set_error("scene_detect: single-band weights and a band selection exclude each other");
       return E_INVALID;
     }
-    DV_TRY(detect_bands_check("scene_detect_multiband", mb->bands, mb->k, mb->c, nb_src, mb->has_planes ? mb->noise : 0,
-                              mb->filter));
+    DV_TRY(detect_bands_check("scene_detect_multiband", mb->bands, mb->k, mb->c, dev ? dev->nb : rq.nb,
+                              mb->has_planes ? mb->noise : 0, mb->filter));
     if (mb->has_planes && (dev ? !dev->planes_dev : !mb->planes_h)) {
       set_error("scene_detect_multiband: planes announced but not given");
       return E_INVALID;
     }
-    if (!(thresh > 0.0)) {
+    if (!(p->thresh > 0.0)) {
       set_error("scene_detect_multiband: the threshold is in units of the combined pixel's sigma and must be > 0 (got %g)",
-                thresh);
+                p->thresh);
       return E_INVALID;
     }
   }
@@ -670,385 +684,387 @@ int detect_impl(const double* fields_h, const DetectDevSrc* dev, const DetectWei
                 wq->noise, wq->filter);
       return E_INVALID;
     }
-    if (wq->noise == 0 && !(thresh > 0.0)) {
-      set_error("scene_detect: with absolute noise the threshold is in units of sigma and must be > 0 (got %g)", thresh);
+    if (wq->noise == 0 && !(p->thresh > 0.0)) {
+      set_error("scene_detect: with absolute noise the threshold is in units of sigma and must be > 0 (got %g)", p->thresh);
       return E_INVALID;
     }
   }
-  const bool mplanes = mb && mb->has_planes, mabs = mplanes && mb->noise == 0;
-  const bool absolute = mb || (wq && wq->noise == 0), matched = mb ? mb->filter == 1 : (wq && wq->filter == 1);
-  if (kernel_h && (kh < 1 || kw < 1 || kh > KMAX || kw > KMAX || (kh & 1) == 0 || (kw & 1) == 0)) {
-    set_error("scene_detect: the filter kernel must have odd sizes of 1 .. %d (got %d x %d)", KMAX, kh, kw);
+  if (p->kernel && (p->kh < 1 || p->kw < 1 || p->kh > KMAX || p->kw > KMAX || (p->kh & 1) == 0 || (p->kw & 1) == 0)) {
+    set_error("scene_detect: the filter kernel must have odd sizes of 1 .. %d (got %d x %d)", KMAX, p->kh, p->kw);
     return E_INVALID;
   }
-  // the filter taps divided by sum |k|; the default is the pixel-integrated circular Gaussian of DESIGN 7e
-  std::vector<double> kn;
-  if (kernel_h) {
-    kn.assign(kernel_h, kernel_h + (size_t)kh * kw);
+  return OK;
+}
+
+// the mode of a checked request (with bands the weights are null and the fields interleaved)
+DetectMode detect_mode(const DetectRequest& rq) {
+  const DetectWeights* wq = rq.weights;
+  const DetectBands* mb = rq.bands;
+  DetectMode md{};
+  md.dev = rq.dev != nullptr; md.nwhich = rq.dev ? rq.M : 0;
+  md.weighted = wq != nullptr;
+  md.k = mb ? mb->k : 0; md.planes = mb && mb->has_planes; md.planes_abs = md.planes && mb->noise == 0;
+  md.nb_src = rq.dev ? rq.dev->nb : rq.nb; md.stage_nb = (mb && !rq.dev) ? std::max(md.nb_src, md.k) : 0;
+  md.absolute = mb || (wq && wq->noise == 0); md.matched = mb ? mb->filter == 1 : (wq && wq->filter == 1);
+  md.objects = rq.objects != nullptr; md.segmap = rq.objects && rq.objects->segmap_h;
+  md.back = rq.back_h != nullptr; md.rms = rq.rms_h != nullptr; md.labels = rq.labels_h != nullptr;
+  md.maps = rq.back_h || rq.rms_h || rq.D_h || rq.labels_h;
+  return md;
+}
+
+// 2. the filter taps divided by sum |k|; the default is the pixel-integrated circular Gaussian of DESIGN 7e
+struct DetectTaps { std::vector<double> kn; int kh, kw; };
+int detect_taps(const dv_detect_params& p, DetectTaps& t) {
+  if (p.kernel) {
+    t.kh = p.kh; t.kw = p.kw;
+    t.kn.assign(p.kernel, p.kernel + (size_t)p.kh * p.kw);
   } else {
-    kh = kw = 7;
+    t.kh = t.kw = 7;
     const double sq = std::sqrt(2.0) * 1.27627;
     double g[7];
     for (int a = 0; a < 7; ++a) g[a] = std::erf((a - 3 + 0.5) / sq) - std::erf((a - 3 - 0.5) / sq);
-    kn.resize(49);
+    t.kn.resize(49);
     for (int a = 0; a < 7; ++a)
-      for (int b = 0; b < 7; ++b) kn[a * 7 + b] = g[a] * g[b];
+      for (int b = 0; b < 7; ++b) t.kn[a * 7 + b] = g[a] * g[b];
   }
   double ksum = 0.0;
-  for (double k : kn) ksum += std::fabs(k);
+  for (double k : t.kn) ksum += std::fabs(k);
   if (!(ksum > 0.0) || !std::isfinite(ksum)) {
     set_error("scene_detect: the filter kernel has no finite non-zero tap");
     return E_INVALID;
   }
-  for (double& k : kn) k /= ksum;
+  for (double& k : t.kn) k /= ksum;
+  return OK;
+}
 
-  const int ny = (H + back_size - 1) / back_size, nx = (W + back_size - 1) / back_size;
-  const bool maps = back_h || rms_h || D_h || labels_h;
-  const int stage_nb = (mb && !dev) ? std::max(nb_src, nbk) : 0;
-  const long cap_ws = workspace_bytes > 0 ? (long)workspace_bytes : (4L << 30);
-  const bool want_seg = oq && oq->segmap_h;
-  const long per_field = field_bytes(H, W, ny, nx, minarea, maps, wq != nullptr, nbk, mplanes, stage_nb, oq != nullptr, want_seg);
-  if (M > 0 && per_field > cap_ws) {
-    set_error("scene_detect: one %d x %d field needs up to %ld bytes of device workspace, above the cap of %ld bytes per "
-              "launch", H, W, per_field, cap_ws);
-    return E_INVALID;
-  }
-  const long HW = (long)H * W;
-  const long ccap = HW / minarea + 1;
-  const int chunk = M > 0 ? (int)std::min<long>({(long)M, (long)CHUNK_MAX, std::max<long>(1, cap_ws / per_field)}) : 0;
+// one launch: the fields f0 .. f0 + m of the call, px pixels, mk planes
+struct DetectLaunch { int f0, m; long px; int mk; };
+// its components as the deblender takes them: a job each with its scratch and catalogue slots placed, jfield the job's field
+// in the call, and the totals
+struct DetectJobs { std::vector<DbJob> jobs; std::vector<int> jfield; long nj = 0, dws = 0, iws = 0, slots = 0; };
+// what the deblender wrote, on the host: objects per job, the columns per catalogue slot (oi, od: the rows of 7zb); and as
+// HostCatalog the catalogue of all fields of the call, grown launch by launch (oi, od: rows of DET_OBJ_I ints, DET_OBJ_D doubles)
+struct DetectSlots { std::vector<int> nobj, npix, oi; std::vector<double> peak, flux, x, y, od; };
+struct HostCatalog { std::vector<int32_t> field, parent, npix, oi; std::vector<double> peak, flux, x, y, od; };
 
-  std::vector<double> cco((size_t)std::max(ny, nx) + 1);
-  cco[0] = 0.25;
-  for (size_t i = 1; i < cco.size(); ++i) cco[i] = 1.0 / (4.0 - cco[i - 1]);
-
-  std::vector<int32_t> c_field, c_parent, c_npix;      // the catalog of all fields
-  std::vector<double> c_peak, c_flux, c_x, c_y;
-  std::vector<int32_t> c_oi;                           // (7zb) rows of DET_OBJ_I ints and of DET_OBJ_D doubles
-  std::vector<double> c_od;
-  offsets_h[0] = 0;
-
+// one call: the request, what it asks for, the device workspace and the catalogue so far; the stages are its methods
+struct DetectRun {
+  const DetectRequest& rq; const dv_detect_params& p; const DetectMode md; const DetectGeom g; const DetectTaps& taps;
+  hipStream_t s;
   DetectWork w;
-  if (chunk > 0) {
-    DV_TRY(w.alloc(chunk, H, W, ny, nx, ccap, kn.size(), cco.size(), back_h != nullptr, rms_h != nullptr,
-                   labels_h != nullptr, dev ? M : 0, wq != nullptr || mplanes, nbk, stage_nb, want_seg));
-    DV_HIP(hipMemcpyAsync(w.kdev, kn.data(), kn.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  std::vector<double> cco;
+  std::vector<int> h_ncomp;
+  HostCatalog cat;
+
+  // what every launch reads, once: the workspace for `chunk` fields, the taps, the coefficients of the spline's tridiagonal
+  // solve, a device source's field numbers, the band numbers (then 0 .. k - 1) and the c_j
+  int prepare(int chunk) {
+    h_ncomp.resize((size_t)std::max(chunk, 1));
+    if (chunk == 0) return OK;
+    cco.resize((size_t)std::max(g.ny, g.nx) + 1);
+    cco[0] = 0.25;
+    for (size_t i = 1; i < cco.size(); ++i) cco[i] = 1.0 / (4.0 - cco[i - 1]);
+    DV_TRY(w.alloc(chunk, g, md, taps.kn.size(), cco.size()));
+    DV_HIP(hipMemcpyAsync(w.kdev, taps.kn.data(), taps.kn.size() * sizeof(double), hipMemcpyHostToDevice, s));
     DV_HIP(hipMemcpyAsync(w.cdev, cco.data(), cco.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    if (dev) DV_HIP(hipMemcpyAsync(w.wdev, dev->which_h, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
-    if (mb) {
-      std::vector<int> sel((size_t)2 * nbk);
-      std::vector<double> cb((size_t)nbk, 1.0);
-      for (int j = 0; j < nbk; ++j) {
-        sel[j] = mb->bands[j];
-        sel[nbk + j] = j;
-        if (mb->c) cb[j] = mb->c[j];
+    if (md.dev) DV_HIP(hipMemcpyAsync(w.wdev, rq.dev->which_h, (size_t)rq.M * sizeof(int), hipMemcpyHostToDevice, s));
+    if (md.multi()) {
+      std::vector<int> sel((size_t)2 * md.k);
+      std::vector<double> cb((size_t)md.k, 1.0);
+      for (int j = 0; j < md.k; ++j) {
+        sel[j] = rq.bands->bands[j];
+        sel[md.k + j] = j;
+        if (rq.bands->c) cb[j] = rq.bands->c[j];
       }
       DV_HIP(hipMemcpyAsync(w.bsel, sel.data(), sel.size() * sizeof(int), hipMemcpyHostToDevice, s));
       DV_HIP(hipMemcpyAsync(w.cband, cb.data(), cb.size() * sizeof(double), hipMemcpyHostToDevice, s));
-      DV_HIP(hipStreamSynchronize(s));                  // (sel and cb leave scope)
+      DV_HIP(hipStreamSynchronize(s));                    // (sel and cb leave scope)
     }
+    return OK;
   }
-  std::vector<int> h_ncomp((size_t)std::max(chunk, 1));
-  std::vector<int> h_tab;
-  for (int f0 = 0; f0 < M; f0 += chunk) {
-    const int m = std::min(chunk, M - f0);
-    const long px = (long)m * HW;
-    const int mk = m * std::max(nbk, 1);                  // planes of the launch
-    if (mb) {
-      const dim3 ggath(nblk(HW), (unsigned)m);
-      if (dev) {
-        hipLaunchKernelGGL(bands_gather_kernel, ggath, dim3(DT), 0, s, dev->fields_dev, HW, nb_src, w.bsel, nbk, w.wdev + f0,
-                           w.data);
-        DV_HIP(hipGetLastError());
-        if (mplanes) {
-          hipLaunchKernelGGL(bands_gather_kernel, ggath, dim3(DT), 0, s, dev->planes_dev, HW, nbk, w.bsel + nbk, nbk,
-                             w.wdev + f0, w.wt);
-          DV_HIP(hipGetLastError());
-        }
-      } else {
-        DV_HIP(hipMemcpyAsync(w.stage, fields_h + (size_t)f0 * HW * nb_src, (size_t)px * nb_src * sizeof(double),
-                              hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(bands_gather_kernel, ggath, dim3(DT), 0, s, w.stage, HW, nb_src, w.bsel, nbk, nullptr, w.data);
-        DV_HIP(hipGetLastError());
-        if (mplanes) {
-          DV_HIP(hipMemcpyAsync(w.stage, mb->planes_h + (size_t)f0 * HW * nbk, (size_t)px * nbk * sizeof(double),
-                                hipMemcpyHostToDevice, s));
-          hipLaunchKernelGGL(bands_gather_kernel, ggath, dim3(DT), 0, s, w.stage, HW, nbk, w.bsel + nbk, nbk, nullptr, w.wt);
-          DV_HIP(hipGetLastError());
-        }
+
+  // (7za) the md.k planes `sel` of the launch's lines of nb values at src -> dst; which: a device stack's field numbers
+  int gather(const double* src, int nb, const int* sel, const int* which, double* dst, const DetectLaunch& L) {
+    hipLaunchKernelGGL(bands_gather_kernel, dim3(nblk(g.HW), (unsigned)L.m), dim3(DT), 0, s, src, g.HW, nb, sel, md.k, which, dst);
+    DV_HIP(hipGetLastError());
+    return OK;
+  }
+  // 3. the launch's planes into w.data (and w.wt): uploaded, or gathered from the staged interleaved lines or the device stack
+  int load_planes(const DetectLaunch& L) {
+    const DetectDevSrc* dev = rq.dev;
+    const size_t at = (size_t)L.f0 * g.HW, px = (size_t)L.px;
+    const int* which = dev ? w.wdev + L.f0 : nullptr;
+    if (md.multi()) {
+      const size_t nb = (size_t)md.nb_src, k = (size_t)md.k;
+      if (!dev) DV_HIP(hipMemcpyAsync(w.stage, rq.fields_h + at * nb, px * nb * sizeof(double), hipMemcpyHostToDevice, s));
+      DV_TRY(gather(dev ? dev->fields_dev : w.stage.get(), md.nb_src, w.bsel, which, w.data, L));
+      if (md.planes) {
+        if (!dev) DV_HIP(hipMemcpyAsync(w.stage, rq.bands->planes_h + at * k, px * k * sizeof(double), hipMemcpyHostToDevice, s));
+        DV_TRY(gather(dev ? dev->planes_dev : w.stage.get(), md.k, w.bsel + md.k, which, w.wt, L));
       }
     } else if (dev) {
-      hipLaunchKernelGGL(band_gather_kernel, dim3(nblk(HW), (unsigned)m), dim3(DT), 0, s, dev->fields_dev, HW, dev->nb,
-                         dev->band, w.wdev + f0, w.data);
+      const dim3 grid(nblk(g.HW), (unsigned)L.m);
+      hipLaunchKernelGGL(band_gather_kernel, grid, dim3(DT), 0, s, dev->fields_dev, g.HW, dev->nb, dev->band, which, w.data);
       DV_HIP(hipGetLastError());
-      if (wq) {
-        hipLaunchKernelGGL(band_gather_kernel, dim3(nblk(HW), (unsigned)m), dim3(DT), 0, s, dev->weights_dev, HW, 1, 0,
-                           w.wdev + f0, w.wt);
+      if (md.weighted) {
+        hipLaunchKernelGGL(band_gather_kernel, grid, dim3(DT), 0, s, dev->weights_dev, g.HW, 1, 0, which, w.wt);
         DV_HIP(hipGetLastError());
       }
     } else {
-      DV_HIP(hipMemcpyAsync(w.data, fields_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
-      if (wq)
-        DV_HIP(hipMemcpyAsync(w.wt, wq->weights_h + (size_t)f0 * HW, (size_t)px * sizeof(double), hipMemcpyHostToDevice, s));
+      DV_HIP(hipMemcpyAsync(w.data, rq.fields_h + at, px * sizeof(double), hipMemcpyHostToDevice, s));
+      if (md.weighted) DV_HIP(hipMemcpyAsync(w.wt, rq.weights->weights_h + at, px * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    const dim3 gmesh((unsigned)((long)mk * ny * nx)), gfilt((unsigned)((W + FT - 1) / FT), (unsigned)((H + FT - 1) / FT),
-                                                            (unsigned)m);
-    if (wq || mplanes) {
-      hipLaunchKernelGGL(bkg_mesh_kernel<true>, gmesh, dim3(DT), 0, s, w.data, w.wt, H, W, back_size, ny, nx, w.mb, w.mr);
+    return OK;
+  }
+
+  // 4. the background: meshes, grids and row splines per plane, then v per pixel - or (7za) V and Wt of the bands combined
+  int background(const DetectLaunch& L) {
+    const int H = g.H, W = g.W, ny = g.ny, nx = g.nx, bs = p.back_size, mk = L.mk;
+    const long px = L.px;
+    const dim3 gmesh((unsigned)((long)mk * ny * nx)), gpix(nblk(px)), blk(DT);
+    if (md.wplanes()) {
+      hipLaunchKernelGGL(bkg_mesh_kernel<true>, gmesh, blk, 0, s, w.data, w.wt, H, W, bs, ny, nx, w.mb, w.mr);
       DV_HIP(hipGetLastError());
-      hipLaunchKernelGGL(bkg_grid_kernel<true>, dim3((unsigned)mk), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev,
-                         w.fbk, w.frm, w.d2b, w.d2r, w.grms, w.nbad);
+      hipLaunchKernelGGL(bkg_grid_kernel<true>, dim3((unsigned)mk), blk, 0, s, w.mb, w.mr, ny, nx, p.back_filter, w.cdev, w.fbk,
+                         w.frm, w.d2b, w.d2r, w.grms, w.nbad);
     } else {
-      hipLaunchKernelGGL(bkg_mesh_kernel<false>, gmesh, dim3(DT), 0, s, w.data, nullptr, H, W, back_size, ny, nx, w.mb, w.mr);
+      hipLaunchKernelGGL(bkg_mesh_kernel<false>, gmesh, blk, 0, s, w.data, nullptr, H, W, bs, ny, nx, w.mb, w.mr);
       DV_HIP(hipGetLastError());
-      hipLaunchKernelGGL(bkg_grid_kernel<false>, dim3((unsigned)mk), dim3(DT), 0, s, w.mb, w.mr, ny, nx, back_filter, w.cdev,
-                         w.fbk, w.frm, w.d2b, w.d2r, w.grms, nullptr);
+      hipLaunchKernelGGL(bkg_grid_kernel<false>, dim3((unsigned)mk), blk, 0, s, w.mb, w.mr, ny, nx, p.back_filter, w.cdev, w.fbk,
+                         w.frm, w.d2b, w.d2r, w.grms, nullptr);
     }
     DV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bkg_row_kernel, dim3(nblk((long)mk * H)), dim3(DT), 0, s, w.fbk, w.frm, w.d2b, w.d2r, mk, H, ny, nx,
-                       back_size, (w.rms || (mb && !mabs)) ? 1 : 0, w.cdev, w.gb, w.gb2, w.gr, w.gr2);
+    hipLaunchKernelGGL(bkg_row_kernel, dim3(nblk((long)mk * H)), blk, 0, s, w.fbk, w.frm, w.d2b, w.d2r, mk, H, ny, nx, bs,
+                       (md.rms || (md.multi() && !md.planes_abs)) ? 1 : 0, w.cdev, w.gb, w.gb2, w.gr, w.gr2);
     DV_HIP(hipGetLastError());
-    if (mb) {
-      hipLaunchKernelGGL(multiband_grms_kernel, dim3(nblk(m)), dim3(DT), 0, s, w.grms, w.cband, m, nbk, w.fgrms);
+    if (md.multi()) {
+      hipLaunchKernelGGL(multiband_grms_kernel, dim3(nblk(L.m)), blk, 0, s, w.grms, w.cband, L.m, md.k, w.fgrms);
       DV_HIP(hipGetLastError());
-      if (mabs)
-        hipLaunchKernelGGL((multiband_pixel_kernel<true, true>), dim3(nblk(px)), dim3(DT), 0, s, w.data, w.wt, px, H, W, nbk, nx,
-                           back_size, w.gb, w.gb2, w.gr, w.gr2, w.grms, w.cband, w.v, w.cw, w.back, w.rms);
-      else if (mplanes)
-        hipLaunchKernelGGL((multiband_pixel_kernel<true, false>), dim3(nblk(px)), dim3(DT), 0, s, w.data, w.wt, px, H, W, nbk, nx,
-                           back_size, w.gb, w.gb2, w.gr, w.gr2, w.grms, w.cband, w.v, w.cw, w.back, w.rms);
+      if (md.planes_abs)
+        hipLaunchKernelGGL((multiband_pixel_kernel<true, true>), gpix, blk, 0, s, w.data, w.wt, px, H, W, md.k, nx, bs, w.gb,
+                           w.gb2, w.gr, w.gr2, w.grms, w.cband, w.v, w.cw, w.back, w.rms);
+      else if (md.planes)
+        hipLaunchKernelGGL((multiband_pixel_kernel<true, false>), gpix, blk, 0, s, w.data, w.wt, px, H, W, md.k, nx, bs, w.gb,
+                           w.gb2, w.gr, w.gr2, w.grms, w.cband, w.v, w.cw, w.back, w.rms);
       else
-        hipLaunchKernelGGL((multiband_pixel_kernel<false, false>), dim3(nblk(px)), dim3(DT), 0, s, w.data, nullptr, px, H, W, nbk,
-                           nx, back_size, w.gb, w.gb2, w.gr, w.gr2, w.grms, w.cband, w.v, w.cw, w.back, w.rms);
-    } else if (wq)
-      hipLaunchKernelGGL(bkg_pixel_kernel<true>, dim3(nblk(px)), dim3(DT), 0, s, w.data, w.wt, px, W, nx, back_size, w.gb,
-                         w.gb2, w.gr, w.gr2, w.v, w.back, w.rms);
+        hipLaunchKernelGGL((multiband_pixel_kernel<false, false>), gpix, blk, 0, s, w.data, nullptr, px, H, W, md.k, nx, bs, w.gb,
+                           w.gb2, w.gr, w.gr2, w.grms, w.cband, w.v, w.cw, w.back, w.rms);
+    } else if (md.weighted)
+      hipLaunchKernelGGL(bkg_pixel_kernel<true>, gpix, blk, 0, s, w.data, w.wt, px, W, nx, bs, w.gb, w.gb2, w.gr, w.gr2, w.v,
+                         w.back, w.rms);
     else
-      hipLaunchKernelGGL(bkg_pixel_kernel<false>, dim3(nblk(px)), dim3(DT), 0, s, w.data, nullptr, px, W, nx, back_size, w.gb,
-                         w.gb2, w.gr, w.gr2, w.v, w.back, w.rms);
+      hipLaunchKernelGGL(bkg_pixel_kernel<false>, gpix, blk, 0, s, w.data, nullptr, px, W, nx, bs, w.gb, w.gb2, w.gr, w.gr2, w.v,
+                         w.back, w.rms);
     DV_HIP(hipGetLastError());
-    if (mb) {                                             // (7za) V, Wt in the place of v, w; absolute noise
-      if (matched)
-        hipLaunchKernelGGL((filter_kernel<true, true>), gfilt, dim3(DT), 0, s, w.v, w.cw, H, W, w.kdev, kh, kw, w.fgrms, thresh,
-                           1, w.D, w.par);
-      else
-        hipLaunchKernelGGL((filter_kernel<true, false>), gfilt, dim3(DT), 0, s, w.v, w.cw, H, W, w.kdev, kh, kw, w.fgrms, thresh,
-                           1, w.D, w.par);
-    } else if (matched)
-      hipLaunchKernelGGL((filter_kernel<true, true>), gfilt, dim3(DT), 0, s, w.v, w.wt, H, W, w.kdev, kh, kw, w.grms, thresh,
-                         absolute ? 1 : 0, w.D, w.par);
-    else if (wq)
-      hipLaunchKernelGGL((filter_kernel<true, false>), gfilt, dim3(DT), 0, s, w.v, w.wt, H, W, w.kdev, kh, kw, w.grms, thresh,
-                         absolute ? 1 : 0, w.D, w.par);
+    return OK;
+  }
+
+  // 5. D (with weights the significance S) and the segmentation's initial parents; (7za) V, Wt and the combined globalrms
+  // stand where v, w and globalrms stand, with absolute noise
+  int filter(const DetectLaunch& L) {
+    const dim3 grid((unsigned)((g.W + FT - 1) / FT), (unsigned)((g.H + FT - 1) / FT), (unsigned)L.m);
+    const double* wplane = md.multi() ? w.cw.get() : (md.weighted ? w.wt.get() : nullptr);
+    const double* grms = md.multi() ? w.fgrms : w.grms;
+    const int absolute = md.absolute ? 1 : 0;
+    if (md.matched)
+      hipLaunchKernelGGL((filter_kernel<true, true>), grid, dim3(DT), 0, s, w.v, wplane, g.H, g.W, w.kdev, taps.kh, taps.kw, grms,
+                         p.thresh, absolute, w.D, w.par);
+    else if (wplane)
+      hipLaunchKernelGGL((filter_kernel<true, false>), grid, dim3(DT), 0, s, w.v, wplane, g.H, g.W, w.kdev, taps.kh, taps.kw, grms,
+                         p.thresh, absolute, w.D, w.par);
     else
-      hipLaunchKernelGGL((filter_kernel<false, false>), gfilt, dim3(DT), 0, s, w.v, nullptr, H, W, w.kdev, kh, kw, w.grms,
-                         thresh, 0, w.D, w.par);
+      hipLaunchKernelGGL((filter_kernel<false, false>), grid, dim3(DT), 0, s, w.v, nullptr, g.H, g.W, w.kdev, taps.kh, taps.kw,
+                         grms, p.thresh, 0, w.D, w.par);
     DV_HIP(hipGetLastError());
+    return OK;
+  }
+
+  // 6. the components: union-find, labels with areas and boxes, the table of those of >= minarea pixels, the labels map
+  int components(const DetectLaunch& L) {
+    const long px = L.px, HW = g.HW;
+    const dim3 gpix(nblk(px)), blk(DT);
     DV_HIP(hipMemsetAsync(w.area, 0, (size_t)px * sizeof(int), s));
     DV_HIP(hipMemsetAsync(w.cmin, 0x7f, (size_t)px * sizeof(int), s));
     DV_HIP(hipMemsetAsync(w.cmax, 0xff, (size_t)px * sizeof(int), s));
     DV_HIP(hipMemsetAsync(w.rmax, 0xff, (size_t)px * sizeof(int), s));
-    hipLaunchKernelGGL(cc_merge_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.par, px, W, HW);
+    hipLaunchKernelGGL(cc_merge_kernel, gpix, blk, 0, s, w.par, px, g.W, HW);
     DV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cc_flatten_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.par, px, W, HW, w.lab, w.area, w.cmin,
-                       w.cmax, w.rmax);
+    hipLaunchKernelGGL(cc_flatten_kernel, gpix, blk, 0, s, w.par, px, g.W, HW, w.lab, w.area, w.cmin, w.cmax, w.rmax);
     DV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cc_compact_kernel, dim3((unsigned)m), dim3(DT), 0, s, w.lab, w.area, w.cmin, w.cmax, w.rmax, HW,
-                       minarea, ccap, w.table, w.ncomp);
+    hipLaunchKernelGGL(cc_compact_kernel, dim3((unsigned)L.m), blk, 0, s, w.lab, w.area, w.cmin, w.cmax, w.rmax, HW, p.minarea,
+                       g.ccap, w.table, w.ncomp);
     DV_HIP(hipGetLastError());
-    if (w.labout) {
-      hipLaunchKernelGGL(cc_labels_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.lab, w.area, px, HW, minarea, w.labout);
+    if (md.labels) {
+      hipLaunchKernelGGL(cc_labels_kernel, gpix, blk, 0, s, w.lab, w.area, px, HW, p.minarea, w.labout);
       DV_HIP(hipGetLastError());
     }
-    DV_HIP(hipMemcpyAsync(globalrms_h + f0, mb ? w.fgrms : w.grms, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    return OK;
+  }
+
+  int to_host(void* dst, const void* src, size_t bytes) {
+    DV_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+    return OK;
+  }
+  // 7a. the launch's per-field outputs and maps to the caller's arrays at field f0 (7za: at f0 * k, the back / rms maps
+  // [..][k]), the component counts to h_ncomp; returns with the stream idle
+  int copy_out(const DetectLaunch& L) {
+    const DetectWeights* wq = rq.weights;
+    const DetectBands* mb = rq.bands;
+    const size_t f0 = (size_t)L.f0, at = f0 * g.HW, px = (size_t)L.px, m = (size_t)L.m, mk = (size_t)L.mk, kk = (size_t)md.kk();
+    DV_TRY(to_host(rq.cat.globalrms_h + f0, mb ? w.fgrms : w.grms, m * 8));
     if (mb) {
-      const size_t o = (size_t)f0 * nbk;
-      if (mb->band_grms_h) DV_HIP(hipMemcpyAsync(mb->band_grms_h + o, w.grms, (size_t)mk * 8, hipMemcpyDeviceToHost, s));
-      if (mb->bad_meshes_h) {
-        if (mplanes) DV_HIP(hipMemcpyAsync(mb->bad_meshes_h + o, w.nbad, (size_t)mk * 4, hipMemcpyDeviceToHost, s));
-        else std::fill(mb->bad_meshes_h + o, mb->bad_meshes_h + o + mk, 0);
-      }
-      if (mb->V_h) DV_HIP(hipMemcpyAsync(mb->V_h + (size_t)f0 * HW, w.v, (size_t)px * 8, hipMemcpyDeviceToHost, s));
-      if (mb->Wt_h) DV_HIP(hipMemcpyAsync(mb->Wt_h + (size_t)f0 * HW, w.cw, (size_t)px * 8, hipMemcpyDeviceToHost, s));
+      if (mb->band_grms_h) DV_TRY(to_host(mb->band_grms_h + f0 * kk, w.grms, mk * 8));
+      if (mb->bad_meshes_h && md.planes) DV_TRY(to_host(mb->bad_meshes_h + f0 * kk, w.nbad, mk * 4));
+      if (mb->bad_meshes_h && !md.planes) std::fill(mb->bad_meshes_h + f0 * kk, mb->bad_meshes_h + f0 * kk + mk, 0);
+      if (mb->V_h) DV_TRY(to_host(mb->V_h + at, w.v, px * 8));
+      if (mb->Wt_h) DV_TRY(to_host(mb->Wt_h + at, w.cw, px * 8));
     }
-    DV_HIP(hipMemcpyAsync(h_ncomp.data(), w.ncomp, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (wq && wq->bad_meshes_h)
-      DV_HIP(hipMemcpyAsync(wq->bad_meshes_h + f0, w.nbad, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, s));
-    const size_t bpx = (size_t)px * std::max(nbk, 1);     // (7za: [..][k] maps)
-    if (back_h) DV_HIP(hipMemcpyAsync(back_h + (size_t)f0 * HW * std::max(nbk, 1), w.back, bpx * 8, hipMemcpyDeviceToHost, s));
-    if (rms_h) DV_HIP(hipMemcpyAsync(rms_h + (size_t)f0 * HW * std::max(nbk, 1), w.rms, bpx * 8, hipMemcpyDeviceToHost, s));
-    if (D_h) DV_HIP(hipMemcpyAsync(D_h + (size_t)f0 * HW, w.D, (size_t)px * 8, hipMemcpyDeviceToHost, s));
-    if (labels_h) DV_HIP(hipMemcpyAsync(labels_h + (size_t)f0 * HW, w.labout, (size_t)px * 4, hipMemcpyDeviceToHost, s));
+    DV_TRY(to_host(h_ncomp.data(), w.ncomp, m * 4));
+    if (wq && wq->bad_meshes_h) DV_TRY(to_host(wq->bad_meshes_h + f0, w.nbad, m * 4));
+    if (rq.back_h) DV_TRY(to_host(rq.back_h + at * kk, w.back, px * kk * 8));
+    if (rq.rms_h) DV_TRY(to_host(rq.rms_h + at * kk, w.rms, px * kk * 8));
+    if (rq.D_h) DV_TRY(to_host(rq.D_h + at, w.D, px * 8));
+    if (rq.labels_h) DV_TRY(to_host(rq.labels_h + at, w.labout, px * 4));
     DV_HIP(hipStreamSynchronize(s));
-    // phase two: every component's scratch and catalog slots
-    std::vector<DbJob> jobs;
-    std::vector<int> jfield;
-    long dws = 0, iws = 0, slots = 0;
-    std::vector<long> tab_off((size_t)m + 1, 0);          // every field's component table, one synchronisation
-    for (int f = 0; f < m; ++f) tab_off[f + 1] = tab_off[f] + h_ncomp[f];
-    h_tab.resize((size_t)std::max(tab_off[m], 1L) * 5);
-    for (int f = 0; f < m; ++f)
-      if (h_ncomp[f] > 0)
-        DV_HIP(hipMemcpyAsync(h_tab.data() + tab_off[f] * 5, w.table + (long)f * ccap * 5,
-                              (size_t)h_ncomp[f] * 5 * sizeof(int), hipMemcpyDeviceToHost, s));
+    return OK;
+  }
+
+  // 7b. phase two: every field's component table in one synchronisation, then every component's scratch and catalog slots
+  int job_table(const DetectLaunch& L, DetectJobs& J) {
+    std::vector<long> tab_off((size_t)L.m + 1, 0);
+    for (int f = 0; f < L.m; ++f) tab_off[f + 1] = tab_off[f] + h_ncomp[f];
+    std::vector<int> h_tab((size_t)std::max(tab_off[L.m], 1L) * 5);
+    for (int f = 0; f < L.m; ++f)
+      if (h_ncomp[f] > 0) DV_TRY(to_host(h_tab.data() + tab_off[f] * 5, w.table + (long)f * g.ccap * 5, (size_t)h_ncomp[f] * 5 * 4));
     DV_HIP(hipStreamSynchronize(s));
-    for (int f = 0; f < m; ++f) {
-      const int nc = h_ncomp[f];
-      for (int c = 0; c < nc; ++c) {
+    for (int f = 0; f < L.m; ++f) {
+      for (int c = 0; c < h_ncomp[f]; ++c) {
         const int* row = &h_tab[(size_t)(tab_off[f] + c) * 5];
         DbJob j{};
-        j.fbase = (long)f * HW;
-        j.root = row[0];
-        j.n = row[1];
-        j.c0 = row[2];
-        j.c1 = row[3];
-        j.r1 = row[4];
-        j.cap = std::max(1, j.n / minarea);
-        j.T = absolute ? thresh : thresh * globalrms_h[f0 + f];
-        j.dws = dws;
-        j.iws = iws;
-        j.slot = slots;
-        dws += (long)j.n + (long)j.cap * (2 + OBJ_D);
-        iws += 6L * j.n + 3L * j.cap;
-        slots += j.cap;
-        jobs.push_back(j);
-        jfield.push_back(f0 + f);
+        j.fbase = (long)f * g.HW;
+        j.root = row[0]; j.n = row[1]; j.c0 = row[2]; j.c1 = row[3]; j.r1 = row[4];
+        j.cap = std::max(1, j.n / p.minarea);
+        j.T = md.absolute ? p.thresh : p.thresh * rq.cat.globalrms_h[L.f0 + f];
+        j.dws = J.dws; j.iws = J.iws; j.slot = J.slots;
+        J.dws += (long)j.n + (long)j.cap * (2 + OBJ_D);
+        J.iws += 6L * j.n + 3L * j.cap;
+        J.slots += j.cap;
+        J.jobs.push_back(j);
+        J.jfield.push_back(L.f0 + f);
       }
     }
-    const long nj = (long)jobs.size();
-    std::vector<int> h_nobj((size_t)nj), h_npix((size_t)slots);
-    std::vector<double> h_peak((size_t)slots), h_flux((size_t)slots), h_x((size_t)slots), h_y((size_t)slots);
-    std::vector<int> h_oi(oq ? (size_t)slots * OBJ_I : 0);
-    std::vector<double> h_od(oq ? (size_t)slots * DET_OBJ_D : 0);
-    if (want_seg) DV_HIP(hipMemsetAsync(w.seg, 0, (size_t)px * sizeof(int), s));
+    J.nj = (long)J.jobs.size();
+    return OK;
+  }
+
+  // 9. the launch's segmap holds ranks within the component: add every job's base, the objects of its field's earlier
+  // components (d.jbase must outlive the kernel: returns with the stream idle)
+  int segmap_base(const DetectLaunch& L, const DetectJobs& J, const DetectSlots& h, DeblendScratch& d) {
+    std::vector<int> jb((size_t)J.nj);
+    int run = 0;
+    for (long j = 0; j < J.nj; ++j) {
+      if (j > 0 && J.jfield[j] != J.jfield[j - 1]) run = 0;
+      jb[j] = run;
+      run += h.nobj[j];
+    }
+    DV_HIP(hipMemcpyAsync(d.jbase, jb.data(), (size_t)J.nj * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(seg_base_kernel, dim3(nblk(L.px)), dim3(DT), 0, s, w.seg, w.lidx, d.jbase, L.px);
+    DV_HIP(hipGetLastError());
+    DV_HIP(hipStreamSynchronize(s));                      // (jb and the scratch leave scope)
+    return OK;
+  }
+  // 8. the deblend launch over the launch's jobs and its read-back into h, then (9) the segmap to the caller's array at f0
+  int deblend(const DetectLaunch& L, DetectJobs& J, DetectSlots& h) {
+    const size_t nj = (size_t)J.nj, slots = (size_t)J.slots;
+    h.nobj.resize(nj); h.npix.resize(slots);
+    for (std::vector<double>* v : {&h.peak, &h.flux, &h.x, &h.y}) v->resize(slots);
+    if (md.objects) { h.oi.resize(slots * OBJ_I); h.od.resize(slots * DET_OBJ_D); }
+    if (md.segmap) DV_HIP(hipMemsetAsync(w.seg, 0, (size_t)L.px * sizeof(int), s));
     if (nj > 0) {
       DeblendScratch d;
-      DV_TRY(d.alloc(nj, dws, iws, slots, oq != nullptr));
-      if (oq) {                                           // the request rides behind the jobs, in the place of one more
-        const DbObjects oo{mb ? (const double*)w.cw : (wq ? (const double*)w.wt : nullptr), H, want_seg ? (int*)w.seg : nullptr,
-                           d.oi, d.od};
-        jobs.push_back(DbJob{});
-        std::memcpy(&jobs[(size_t)nj], &oo, sizeof(oo));
+      DV_TRY(d.alloc(J.nj, J.dws, J.iws, J.slots, md.objects));
+      if (md.objects) {                                   // the request rides behind the jobs, in the place of one more
+        const DbObjects oo{md.multi() ? w.cw.get() : (md.weighted ? w.wt.get() : nullptr), g.H,
+                           md.segmap ? w.seg.get() : nullptr, d.oi, d.od};
+        J.jobs.push_back(DbJob{});
+        std::memcpy(&J.jobs[nj], &oo, sizeof(oo));
       }
-      DV_HIP(hipMemcpyAsync(d.djobs, jobs.data(), jobs.size() * sizeof(DbJob), hipMemcpyHostToDevice, s));
-      if (oq) {
-        DV_TRY(deblend_objects_launch(nj, s, d.djobs, W, w.D, w.v, w.lab, w.lidx, d.dscr, d.iscr, nthresh, minarea, cont,
+      DV_HIP(hipMemcpyAsync(d.djobs, J.jobs.data(), J.jobs.size() * sizeof(DbJob), hipMemcpyHostToDevice, s));
+      if (md.objects) {
+        DV_TRY(deblend_objects_launch(J.nj, s, d.djobs, g.W, w.D, w.v, w.lab, w.lidx, d.dscr, d.iscr, p.nthresh, p.minarea, p.cont,
                                       d.o_npix, d.o_pp, d.o_peak, d.o_flux, d.o_x, d.o_y, d.nobj));
       } else {
-        hipLaunchKernelGGL(deblend_kernel<false>, dim3((unsigned)nj), dim3(DT), 0, s, d.djobs, W, w.D, w.v, w.lab, w.lidx, d.dscr,
-                           d.iscr, nthresh, minarea, cont, d.o_npix, d.o_pp, d.o_peak, d.o_flux, d.o_x, d.o_y, d.nobj);
+        hipLaunchKernelGGL(deblend_kernel<false>, dim3((unsigned)nj), dim3(DT), 0, s, d.djobs, g.W, w.D, w.v, w.lab, w.lidx, d.dscr,
+                           d.iscr, p.nthresh, p.minarea, p.cont, d.o_npix, d.o_pp, d.o_peak, d.o_flux, d.o_x, d.o_y, d.nobj);
       }
       DV_HIP(hipGetLastError());
-      if (oq) {
-        DV_HIP(hipMemcpyAsync(h_oi.data(), d.oi, h_oi.size() * 4, hipMemcpyDeviceToHost, s));
-        DV_HIP(hipMemcpyAsync(h_od.data(), d.od, h_od.size() * 8, hipMemcpyDeviceToHost, s));
+      if (md.objects) {
+        DV_TRY(to_host(h.oi.data(), d.oi, h.oi.size() * 4));
+        DV_TRY(to_host(h.od.data(), d.od, h.od.size() * 8));
       }
-      DV_HIP(hipMemcpyAsync(h_nobj.data(), d.nobj, (size_t)nj * 4, hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(h_npix.data(), d.o_npix, (size_t)slots * 4, hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(h_peak.data(), d.o_peak, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(h_flux.data(), d.o_flux, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(h_x.data(), d.o_x, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
-      DV_HIP(hipMemcpyAsync(h_y.data(), d.o_y, (size_t)slots * 8, hipMemcpyDeviceToHost, s));
+      DV_TRY(to_host(h.nobj.data(), d.nobj, nj * 4));
+      DV_TRY(to_host(h.npix.data(), d.o_npix, slots * 4));
+      DV_TRY(to_host(h.peak.data(), d.o_peak, slots * 8));
+      DV_TRY(to_host(h.flux.data(), d.o_flux, slots * 8));
+      DV_TRY(to_host(h.x.data(), d.o_x, slots * 8));
+      DV_TRY(to_host(h.y.data(), d.o_y, slots * 8));
       DV_HIP(hipStreamSynchronize(s));
-      if (want_seg) {                                     // every job's base: the objects of its field's earlier components
-        std::vector<int> jb((size_t)nj);
-        int run = 0;
-        for (long j = 0; j < nj; ++j) {
-          if (j > 0 && jfield[j] != jfield[j - 1]) run = 0;
-          jb[j] = run;
-          run += h_nobj[j];
-        }
-        DV_HIP(hipMemcpyAsync(d.jbase, jb.data(), (size_t)nj * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(seg_base_kernel, dim3(nblk(px)), dim3(DT), 0, s, w.seg, w.lidx, d.jbase, px);
-        DV_HIP(hipGetLastError());
-        DV_HIP(hipStreamSynchronize(s));                  // (jb and the scratch leave scope)
-      }
+      if (md.segmap) DV_TRY(segmap_base(L, J, h, d));
     }
-    if (want_seg) {
-      DV_HIP(hipMemcpyAsync(oq->segmap_h + (size_t)f0 * HW, w.seg, (size_t)px * 4, hipMemcpyDeviceToHost, s));
+    if (md.segmap) {
+      DV_TRY(to_host(rq.objects->segmap_h + (size_t)L.f0 * g.HW, w.seg, (size_t)L.px * 4));
       DV_HIP(hipStreamSynchronize(s));
     }
+    return OK;
+  }
+
+  // 10. the launch's objects behind the catalogue, field by field, and the fields' offsets
+  void append_catalogue(const DetectLaunch& L, const DetectJobs& J, const DetectSlots& h) {
     long ji = 0;
-    for (int f = 0; f < m; ++f) {
-      for (; ji < nj && jfield[ji] == f0 + f; ++ji) {
-        const DbJob& j = jobs[ji];
-        for (int o = 0; o < h_nobj[ji]; ++o) {
-          const long sl = j.slot + o;
-          c_field.push_back(f0 + f);
-          c_parent.push_back(j.root);
-          c_npix.push_back(h_npix[sl]);
-          c_peak.push_back(h_peak[sl]);
-          c_flux.push_back(h_flux[sl]);
-          c_x.push_back(h_x[sl]);
-          c_y.push_back(h_y[sl]);
-          if (oq) {
-            c_oi.insert(c_oi.end(), h_oi.begin() + sl * OBJ_I, h_oi.begin() + sl * OBJ_I + DET_OBJ_I);
-            c_od.insert(c_od.end(), h_od.begin() + sl * DET_OBJ_D, h_od.begin() + (sl + 1) * DET_OBJ_D);
+    for (int f = 0; f < L.m; ++f) {
+      for (; ji < J.nj && J.jfield[ji] == L.f0 + f; ++ji) {
+        for (int o = 0; o < h.nobj[ji]; ++o) {
+          const long sl = J.jobs[ji].slot + o;
+          cat.field.push_back(L.f0 + f);
+          cat.parent.push_back(J.jobs[ji].root);
+          cat.npix.push_back(h.npix[sl]);
+          cat.peak.push_back(h.peak[sl]);
+          cat.flux.push_back(h.flux[sl]);
+          cat.x.push_back(h.x[sl]);
+          cat.y.push_back(h.y[sl]);
+          if (md.objects) {
+            cat.oi.insert(cat.oi.end(), h.oi.begin() + sl * OBJ_I, h.oi.begin() + sl * OBJ_I + DET_OBJ_I);
+            cat.od.insert(cat.od.end(), h.od.begin() + sl * DET_OBJ_D, h.od.begin() + (sl + 1) * DET_OBJ_D);
           }
         }
       }
-      offsets_h[f0 + f + 1] = (int64_t)c_field.size();
+      rq.cat.offsets_h[L.f0 + f + 1] = (int64_t)cat.field.size();
     }
   }
-  const size_t n = c_field.size();
-  *n_out = (int64_t)n;
-  if ((int64_t)n <= cap && n > 0) {
-    std::copy(c_field.begin(), c_field.end(), field_h);
-    std::copy(c_parent.begin(), c_parent.end(), parent_h);
-    std::copy(c_npix.begin(), c_npix.end(), npix_h);
-    std::copy(c_peak.begin(), c_peak.end(), peak_h);
-    std::copy(c_flux.begin(), c_flux.end(), flux_h);
-    std::copy(c_x.begin(), c_x.end(), x_h);
-    std::copy(c_y.begin(), c_y.end(), y_h);
-    if (oq)
-      for (size_t i = 0; i < n; ++i) {
-        for (int e = 0; e < DET_OBJ_I; ++e)
-          if (oq->icol[e]) oq->icol[e][i] = c_oi[i * DET_OBJ_I + e];
-        for (int e = 0; e < DET_OBJ_D; ++e)
-          if (oq->dcol[e]) oq->dcol[e][i] = c_od[i * DET_OBJ_D + e];
-      }
+
+  // the count always, the rows when they fit into the caller's cap
+  void write_catalogue() {
+    const DetectCatalog& out = rq.cat;
+    const size_t n = cat.field.size();
+    *out.n_out = (int64_t)n;
+    if ((int64_t)n > out.cap || n == 0) return;
+    std::copy(cat.field.begin(), cat.field.end(), out.field_h);
+    std::copy(cat.parent.begin(), cat.parent.end(), out.parent_h);
+    std::copy(cat.npix.begin(), cat.npix.end(), out.npix_h);
+    std::copy(cat.peak.begin(), cat.peak.end(), out.peak_h);
+    std::copy(cat.flux.begin(), cat.flux.end(), out.flux_h);
+    std::copy(cat.x.begin(), cat.x.end(), out.x_h);
+    std::copy(cat.y.begin(), cat.y.end(), out.y_h);
+    if (!md.objects) return;
+    for (size_t i = 0; i < n; ++i) {
+      for (int e = 0; e < DET_OBJ_I; ++e)
+        if (rq.objects->icol[e]) rq.objects->icol[e][i] = cat.oi[i * DET_OBJ_I + e];
+      for (int e = 0; e < DET_OBJ_D; ++e)
+        if (rq.objects->dcol[e]) rq.objects->dcol[e][i] = cat.od[i * DET_OBJ_D + e];
+    }
   }
-  return OK;
-}
+};
 }  // namespace
-
-int scene_detect(const double* fields_h, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
-                 int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
-                 int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
-                 int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                 double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s, const DetectWeights* wq) {
-  if (!fields_h) {
-    set_error("scene_detect: bad arguments");
-    return E_INVALID;
-  }
-  return detect_impl(fields_h, nullptr, wq, nullptr, 0, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
-                     workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
-                     y_h, back_h, rms_h, D_h, labels_h, s);
-}
-
-int scene_detect_dev(const DetectDevSrc& src, int M, int H, int W, double thresh, double cont, int minarea, int nthresh,
-                     int back_size, int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes,
-                     int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h,
-                     int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h,
-                     hipStream_t s, const DetectWeights* wq, const DetectBands* mb, const DetectObjects* oq) {
-  return detect_impl(nullptr, &src, wq, mb, 0, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h, kh, kw,
-                     workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
-                     y_h, nullptr, nullptr, nullptr, nullptr, s, oq);
-}
-
-int scene_detect_objects(const double* fields_h, int nb, const DetectWeights* wq, const DetectBands* mb, const DetectObjects& oq,
-                         int M, int H, int W, double thresh, double cont, int minarea, int nthresh, int back_size,
-                         int back_filter, const double* kernel_h, int kh, int kw, int64_t workspace_bytes, int64_t cap,
-                         int64_t* n_out, int64_t* offsets_h, double* globalrms_h, int32_t* field_h, int32_t* parent_h,
-                         int32_t* npix_h, double* peak_h, double* flux_h, double* x_h, double* y_h, hipStream_t s) {
-  if (!fields_h || (mb ? wq != nullptr : nb != 0)) {
-    set_error("scene_detect_objects: bad arguments (fields [M][H][W] with nb = 0, or [M][H][W][nb] with a band selection and "
-              "no single-band weights)");
-    return E_INVALID;
-  }
-  return detect_impl(fields_h, nullptr, wq, mb, nb, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter, kernel_h,
-                     kh, kw, workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h, flux_h, x_h,
-                     y_h, nullptr, nullptr, nullptr, nullptr, s, &oq);
-}
 
 int detect_bands_check(const char* who, const int32_t* bands, int k, const double* c, int nb, int noise, int filter) {
   if (nb < 1 || k < 1 || k > nb || !bands) {
@@ -1077,18 +1093,41 @@ int detect_bands_check(const char* who, const int32_t* bands, int k, const doubl
   return OK;
 }
 
-int scene_detect_multiband(const double* fields_h, int nb, const DetectBands& mb, int M, int H, int W, double thresh, double cont,
-                           int minarea, int nthresh, int back_size, int back_filter, const double* kernel_h, int kh, int kw,
-                           int64_t workspace_bytes, int64_t cap, int64_t* n_out, int64_t* offsets_h, double* globalrms_h,
-                           int32_t* field_h, int32_t* parent_h, int32_t* npix_h, double* peak_h, double* flux_h, double* x_h,
-                           double* y_h, double* back_h, double* rms_h, double* D_h, int32_t* labels_h, hipStream_t s) {
-  if (!fields_h) {
-    set_error("scene_detect_multiband: bad arguments");
+int scene_detect(const DetectRequest& rq, hipStream_t s) {
+  DV_TRY(detect_check(rq));
+  const dv_detect_params& p = *rq.par;
+  DetectTaps taps;
+  DV_TRY(detect_taps(p, taps));
+  const int M = rq.M;
+  const long HW = (long)rq.H * rq.W;
+  DetectRun run{rq, p, detect_mode(rq), DetectGeom{rq.H, rq.W, (rq.H + p.back_size - 1) / p.back_size,
+                                                   (rq.W + p.back_size - 1) / p.back_size, HW, HW / p.minarea + 1}, taps, s};
+  const long cap_ws = p.workspace_bytes > 0 ? (long)p.workspace_bytes : (4L << 30);
+  const long per_field = field_bytes(run.g, run.md);
+  if (M > 0 && per_field > cap_ws) {
+    set_error("scene_detect: one %d x %d field needs up to %ld bytes of device workspace, above the cap of %ld bytes per "
+              "launch", rq.H, rq.W, per_field, cap_ws);
     return E_INVALID;
   }
-  return detect_impl(fields_h, nullptr, nullptr, &mb, nb, M, H, W, thresh, cont, minarea, nthresh, back_size, back_filter,
-                     kernel_h, kh, kw, workspace_bytes, cap, n_out, offsets_h, globalrms_h, field_h, parent_h, npix_h, peak_h,
-                     flux_h, x_h, y_h, back_h, rms_h, D_h, labels_h, s);
+  const int chunk = M > 0 ? (int)std::min<long>({(long)M, (long)CHUNK_MAX, std::max<long>(1, cap_ws / per_field)}) : 0;
+  rq.cat.offsets_h[0] = 0;
+  DV_TRY(run.prepare(chunk));
+  for (int f0 = 0; f0 < M; f0 += chunk) {
+    const int m = std::min(chunk, M - f0);
+    const DetectLaunch L{f0, m, (long)m * HW, m * run.md.kk()};
+    DV_TRY(run.load_planes(L));
+    DV_TRY(run.background(L));
+    DV_TRY(run.filter(L));
+    DV_TRY(run.components(L));
+    DV_TRY(run.copy_out(L));
+    DetectJobs jobs;
+    DetectSlots slots;
+    DV_TRY(run.job_table(L, jobs));
+    DV_TRY(run.deblend(L, jobs, slots));
+    run.append_catalogue(L, jobs, slots);
+  }
+  run.write_catalogue();
+  return OK;
 }
 
 }  // namespace dv

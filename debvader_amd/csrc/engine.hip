@@ -4112,15 +4112,30 @@ int dv_scene_measure_mc(dv_ctx* c, const float* samples, int32_t S, int64_t N, i
   return scene_measure_mc(samples, S, N, cs, nb, p->band, p->sigma0, p->tol, p->max_iter, out, c->stream);
 }
 
+// the C ABI's detector structs as detect.hip reads them: the weights of DESIGN 7z, the selection of 7za (the outputs only
+// dv_scene_detect_multiband has stay null here) and the request of 7zb
+static DetectWeights detect_weights_of(const dv_detect_weights* wt, int32_t* bad_meshes) {
+  return DetectWeights{wt->weights, wt->noise, wt->filter, bad_meshes};
+}
+static DetectBands detect_bands_of(const dv_detect_bands* b) {
+  return DetectBands{b->bands, b->k, b->band_weights, b->planes, b->planes != nullptr, b->noise, b->filter};
+}
+static DetectObjects detect_objects_of(const dv_detect_objects* o) {
+  return DetectObjects{{o->xmin, o->xmax, o->ymin, o->ymax, o->xpeak, o->ypeak, o->xvpeak, o->yvpeak, o->flag},
+                       {o->vpeak, o->dflux, o->x_iso, o->y_iso, o->x2, o->y2, o->xy},
+                       o->segmap};
+}
+
 int dv_scene_detect(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, const dv_detect_params* p,
                     int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms, int32_t* field, int32_t* parent,
                     int32_t* npix, double* peak, double* flux, double* x, double* y, double* back, double* rms,
                     double* D, int32_t* labels) {
   if (!c || !p) return DV_E_INVALID;
   DV_HIP(hipSetDevice(c->device));
-  return scene_detect(fields, M, H, W, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
-                      p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, offsets, globalrms, field, parent, npix,
-                      peak, flux, x, y, back, rms, D, labels, c->stream);
+  DetectRequest rq{fields, 0, M, H, W, p};
+  rq.back_h = back; rq.rms_h = rms; rq.D_h = D; rq.labels_h = labels;
+  rq.cat = DetectCatalog{cap, n_out, offsets, globalrms, field, parent, npix, peak, flux, x, y};
+  return scene_detect(rq, c->stream);
 }
 
 int dv_scene_detect_weighted(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, const dv_detect_params* p,
@@ -4133,10 +4148,12 @@ int dv_scene_detect_weighted(dv_ctx* c, const double* fields, int32_t M, int32_t
     return DV_E_INVALID;
   }
   DV_HIP(hipSetDevice(c->device));
-  const DetectWeights wq{wt->weights, wt->noise, wt->filter, bad_meshes};
-  return scene_detect(fields, M, H, W, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
-                      p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, offsets, globalrms, field, parent, npix,
-                      peak, flux, x, y, back, rms, D, labels, c->stream, &wq);
+  const DetectWeights wq = detect_weights_of(wt, bad_meshes);
+  DetectRequest rq{fields, 0, M, H, W, p};
+  rq.weights = &wq;
+  rq.back_h = back; rq.rms_h = rms; rq.D_h = D; rq.labels_h = labels;
+  rq.cat = DetectCatalog{cap, n_out, offsets, globalrms, field, parent, npix, peak, flux, x, y};
+  return scene_detect(rq, c->stream);
 }
 
 int dv_scene_detect_multiband(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, int32_t nb,
@@ -4150,18 +4167,17 @@ int dv_scene_detect_multiband(dv_ctx* c, const double* fields, int32_t M, int32_
     return DV_E_INVALID;
   }
   DV_HIP(hipSetDevice(c->device));
-  const DetectBands mb{b->bands, b->k, b->band_weights, b->planes, b->planes != nullptr, b->noise, b->filter, band_globalrms,
-                       bad_meshes, V, Wt};
-  return scene_detect_multiband(fields, nb, mb, M, H, W, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size,
-                                p->back_filter, p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, offsets, globalrms,
-                                field, parent, npix, peak, flux, x, y, back, rms, D, labels, c->stream);
-}
-
-// the request of DESIGN 7zb as detect.hip reads it
-static DetectObjects detect_objects_of(const dv_detect_objects* o) {
-  return DetectObjects{{o->xmin, o->xmax, o->ymin, o->ymax, o->xpeak, o->ypeak, o->xvpeak, o->yvpeak, o->flag},
-                       {o->vpeak, o->dflux, o->x_iso, o->y_iso, o->x2, o->y2, o->xy},
-                       o->segmap};
+  if (!fields) {
+    set_error("scene_detect_multiband: bad arguments");
+    return DV_E_INVALID;
+  }
+  DetectBands mb = detect_bands_of(b);
+  mb.band_grms_h = band_globalrms; mb.bad_meshes_h = bad_meshes; mb.V_h = V; mb.Wt_h = Wt;
+  DetectRequest rq{fields, nb, M, H, W, p};
+  rq.bands = &mb;
+  rq.back_h = back; rq.rms_h = rms; rq.D_h = D; rq.labels_h = labels;
+  rq.cat = DetectCatalog{cap, n_out, offsets, globalrms, field, parent, npix, peak, flux, x, y};
+  return scene_detect(rq, c->stream);
 }
 
 int dv_scene_detect_objects(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, int32_t nb,
@@ -4186,15 +4202,20 @@ int dv_scene_detect_objects(dv_ctx* c, const double* fields, int32_t M, int32_t 
     return DV_E_INVALID;
   }
   DV_HIP(hipSetDevice(c->device));
+  if (!fields || (!b && nb != 0)) {
+    set_error("scene_detect_objects: bad arguments (fields [M][H][W] with nb = 0, or [M][H][W][nb] with a band selection and "
+              "no single-band weights)");
+    return DV_E_INVALID;
+  }
   const DetectObjects oq = detect_objects_of(objects);
-  DetectWeights wq{nullptr, 0, 0, nullptr};
-  if (wt) wq = DetectWeights{wt->weights, wt->noise, wt->filter, nullptr};
+  DetectWeights wq{};
+  if (wt) wq = detect_weights_of(wt, nullptr);
   DetectBands mb{};
-  if (b) mb = DetectBands{b->bands, b->k, b->band_weights, b->planes, b->planes != nullptr, b->noise, b->filter, nullptr, nullptr,
-                          nullptr, nullptr};
-  return scene_detect_objects(fields, nb, wt ? &wq : nullptr, b ? &mb : nullptr, oq, M, H, W, p->thresh, p->cont, p->minarea,
-                              p->nthresh, p->back_size, p->back_filter, p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out,
-                              offsets, globalrms, field, parent, npix, peak, flux, x, y, c->stream);
+  if (b) mb = detect_bands_of(b);
+  DetectRequest rq{fields, nb, M, H, W, p};
+  rq.weights = wt ? &wq : nullptr; rq.bands = b ? &mb : nullptr; rq.objects = &oq;
+  rq.cat = DetectCatalog{cap, n_out, offsets, globalrms, field, parent, npix, peak, flux, x, y};
+  return scene_detect(rq, c->stream);
 }
 
 int dv_ctx_allreduce_host(dv_ctx* c, float* buf, int32_t n) {
@@ -6348,9 +6369,10 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
   std::vector<double> grms((size_t)std::max(Ma, 1), 0.0);
   DV_HIP(hipSetDevice(fs->m->ctx->device));
   DetectDevSrc src{fs->work, fs->nb, multi ? 0 : 2, act.data(), fs->dweights, fs->dplanes};
-  const DetectWeights wq{nullptr, fs->dnoise, fs->dfilter, nullptr};
+  // (the planes of either mode lie in the set: src carries them, the host pointers stay null)
+  const DetectWeights wq{nullptr, fs->dnoise, fs->dfilter};
   const DetectBands mb{fs->dbands.data(), (int)fs->dbands.size(), fs->dbw.data(), nullptr, (bool)fs->dplanes, fs->dbnoise,
-                       fs->dbfilter, nullptr, nullptr, nullptr, nullptr};
+                       fs->dbfilter};
   *n_out = 0;
   // (7zb) the object columns land in the set's host arrays, the segmap of the active fields in seg_a
   DetectObjects oq{};
@@ -6375,15 +6397,12 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
       oq.segmap_h = seg_a.data();
     }
   }
-  const DetectObjects* oqp = fs->dobj ? &oq : nullptr;
-  if (Ma > 0 && multi)
-    DV_TRY(scene_detect_dev(src, Ma, fs->F, fs->F, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
-                          p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, off.data(), grms.data(), field, parent,
-                          npix, peak, flux, x, y, fs->m->ctx->stream, nullptr, &mb, oqp));
-  else if (Ma > 0)
-    DV_TRY(scene_detect_dev(src, Ma, fs->F, fs->F, p->thresh, p->cont, p->minarea, p->nthresh, p->back_size, p->back_filter,
-                          p->kernel, p->kh, p->kw, p->workspace_bytes, cap, n_out, off.data(), grms.data(), field, parent,
-                          npix, peak, flux, x, y, fs->m->ctx->stream, fs->dweights ? &wq : nullptr, nullptr, oqp));
+  if (Ma > 0) {
+    DetectRequest rq{nullptr, 0, Ma, fs->F, fs->F, p, &src};
+    rq.weights = (!multi && fs->dweights) ? &wq : nullptr; rq.bands = multi ? &mb : nullptr; rq.objects = fs->dobj ? &oq : nullptr;
+    rq.cat = DetectCatalog{cap, n_out, off.data(), grms.data(), field, parent, npix, peak, flux, x, y};
+    DV_TRY(scene_detect(rq, fs->m->ctx->stream));
+  }
   if (fs->dobj) {
     if (*n_out <= cap) fs->do_n = *n_out;
     if (fs->dseg) {

@@ -539,6 +539,53 @@ def _object_buffers(cap, segmap_shape=None, columns=True):
     return arr, st
 
 
+CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
+
+
+def _detect_params(thresh, cont, minarea, nthresh, back_size, back_filter, filter_kernel, workspace_bytes):
+    """(dv_detect_params, the kernel array it points into: the caller keeps it alive for the call)"""
+    kern, kptr, kh, kw = None, None, 0, 0
+    if filter_kernel is not None:
+        kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
+        kptr, (kh, kw) = _dp(kern), kern.shape
+    params = _lib.DvDetectParams(float(thresh), float(cont), int(minarea), int(nthresh), int(back_size), int(back_filter),
+                                 kptr, kh, kw, int(workspace_bytes))
+    return params, kern
+
+
+def _check_multiband_finite(f, sel, planes):
+    """fields (M, H, W, nb) of the multi-band detector: finite in the selected bands, with planes only where the band counts"""
+    if np.isfinite(f).all():                          # (one pass over the fields; bands are selected only behind a miss)
+        return
+    fsel = f[:, :, :, sel]
+    if planes is None and not np.isfinite(fsel).all():
+        raise ValueError("the fields must be finite in the selected bands")
+    if planes is not None and not np.isfinite(fsel[counting_pixels(planes)]).all():
+        raise ValueError("the fields must be finite in every selected band where that band counts (0 < weight < inf)")
+
+
+def _run_detect(M, field_pixels, call):
+    """The catalogue of a detect call for M fields of field_pixels pixels each, whose size is known only after the call:
+    call(cap, n, offsets, globalrms, columns) makes the library call with room for cap rows - the arguments are the pointers
+    in the C ABI's order, columns the seven of CATALOG_KEYS - and is made once unless the catalogue exceeds one object per
+    1024 pixels, then once more at the exact size.  Returns ({the columns trimmed to their rows (copies), offsets (M + 1,),
+    globalrms (M,)}, rows)."""
+    offsets = np.zeros(M + 1, np.int64)
+    grms = np.zeros(M, np.float64)
+    cap = max(4096, 64 * M, M * field_pixels // 1024)
+    while True:
+        cat = {k: np.empty(cap, np.int32 if k in ("field", "parent", "npix") else np.float64) for k in CATALOG_KEYS}
+        n = C.c_int64()
+        call(cap, C.byref(n), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _dp(grms),
+             [_ip(cat[k]) if cat[k].dtype == np.int32 else _dp(cat[k]) for k in CATALOG_KEYS])
+        if n.value <= cap:
+            break
+        cap = n.value
+    out = {k: v[:n.value].copy() for k, v in cat.items()}
+    out.update(offsets=offsets, globalrms=grms)
+    return out, n.value
+
+
 def counting_pixels(w):
     """the pixels that count: 0 < w < inf (NaN does not)"""
     with np.errstate(invalid="ignore"):
@@ -1277,7 +1324,7 @@ class Context:
                                              _dp(out["gram"]), _dp(out["rhs"])))
         return out
 
-    CATALOG_KEYS = ("field", "parent", "npix", "peak", "flux", "x", "y")
+    CATALOG_KEYS = CATALOG_KEYS
 
     def scene_detect(self, fields_r, thresh: float = 1.5, minarea: int = 4, nthresh: int = 64, cont: float = 1e-5,
                      filter_kernel=None, back_size: int = 64, back_filter: int = 3, return_maps: bool = False,
@@ -1314,46 +1361,27 @@ class Context:
             raise ValueError("noise and filter_type belong to the weighted call: give weights, a mask or both")
         f = check_detect_args(fields_r, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
                               workspace_bytes, weights=wts)
-        kern, kptr, kh, kw = None, None, 0, 0
-        if filter_kernel is not None:
-            kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
-            kptr, (kh, kw) = kern.ctypes.data_as(C.POINTER(C.c_double)), kern.shape
         M, H, W = f.shape
-        params = _lib.DvDetectParams(float(thresh), float(cont), int(minarea), int(nthresh), int(back_size),
-                                     int(back_filter), kptr, kh, kw, int(workspace_bytes))
-        offsets = np.zeros(M + 1, np.int64)
-        grms = np.zeros(M, np.float64)
+        params, kern = _detect_params(thresh, cont, minarea, nthresh, back_size, back_filter, filter_kernel, workspace_bytes)
         maps = {}
         if return_maps:
             maps = dict(back=np.empty((M, H, W)), rms=np.empty((M, H, W)), D=np.empty((M, H, W)),
                         labels=np.empty((M, H, W), np.int32))
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        if weighted:
+            bad = np.zeros(M, np.int32)
+            wstruct = _lib.DvDetectWeights(_dp(wts), noise_id, filter_id)
 
-        def _ptr(a, t):
-            return None if a is None else a.ctypes.data_as(t)
-
-        # one call unless the catalog exceeds one object per 1024 pixels (then a second call with the exact size)
-        cap = max(4096, 64 * M, M * H * W // 1024)
-        while True:                                   # the catalog's size is known after the call: grow once if needed
-            cat = {k: np.empty(cap, np.int32 if k in ("field", "parent", "npix") else np.float64)
-                   for k in self.CATALOG_KEYS}
-            n = C.c_int64()
-            args = [self._h, f.ctypes.data_as(dp), M, H, W, C.byref(params), cap, C.byref(n),
-                    offsets.ctypes.data_as(C.POINTER(C.c_int64)), grms.ctypes.data_as(dp),
-                    *[_ptr(cat[k], ip if cat[k].dtype == np.int32 else dp) for k in self.CATALOG_KEYS],
-                    _ptr(maps.get("back"), dp), _ptr(maps.get("rms"), dp), _ptr(maps.get("D"), dp),
-                    _ptr(maps.get("labels"), ip)]
+        def call(cap, n, offsets, grms, columns):
+            args = [self._h, _dp(f), M, H, W, C.byref(params), cap, n, offsets, grms, *columns,
+                    _dp(maps.get("back")), _dp(maps.get("rms")), _dp(maps.get("D")),
+                    _ip(maps["labels"]) if return_maps else None]
             if weighted:
-                bad = np.zeros(M, np.int32)
-                wstruct = _lib.DvDetectWeights(wts.ctypes.data_as(dp), noise_id, filter_id)
-                check(lib.dv_scene_detect_weighted(*args, C.byref(wstruct), bad.ctypes.data_as(ip)))
+                check(lib.dv_scene_detect_weighted(*args, C.byref(wstruct), _ip(bad)))
             else:
                 check(lib.dv_scene_detect(*args))
-            if n.value <= cap:
-                break
-            cap = n.value
-        out = {k: v[:n.value].copy() for k, v in cat.items()}
-        out.update(offsets=offsets, globalrms=grms, **maps)
+
+        out, _ = _run_detect(M, H * W, call)
+        out.update(maps)
         if weighted:
             out["bad_meshes"] = bad
         return out
@@ -1386,44 +1414,26 @@ class Context:
         sel, cw = check_detect_bands(nb, bands, band_weights)
         k = len(sel)
         planes, noise_id, filter_id = check_detect_band_planes((M, H, W, k), weights, mask, noise, filter_type, thresh)
-        if not np.isfinite(f).all():                  # (one pass over the fields; bands are selected only behind a miss)
-            fsel = f[:, :, :, sel]
-            if planes is None and not np.isfinite(fsel).all():
-                raise ValueError("the fields must be finite in the selected bands")
-            if planes is not None and not np.isfinite(fsel[counting_pixels(planes)]).all():
-                raise ValueError("the fields must be finite in every selected band where that band counts (0 < weight < inf)")
+        _check_multiband_finite(f, sel, planes)
         check_detect_args(np.zeros((0, H, W)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
                           workspace_bytes)
-        kern, kptr, kh, kw = None, None, 0, 0
-        if filter_kernel is not None:
-            kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
-            kptr, (kh, kw) = kern.ctypes.data_as(C.POINTER(C.c_double)), kern.shape
-        params = _lib.DvDetectParams(float(thresh), float(cont), int(minarea), int(nthresh), int(back_size),
-                                     int(back_filter), kptr, kh, kw, int(workspace_bytes))
-        offsets = np.zeros(M + 1, np.int64)
-        grms = np.zeros(M, np.float64)
+        params, kern = _detect_params(thresh, cont, minarea, nthresh, back_size, back_filter, filter_kernel, workspace_bytes)
         bgrms = np.zeros((M, k), np.float64)
         bad = np.zeros((M, k), np.int32)
         maps = {}
         if return_maps:
             maps = dict(back=np.empty((M, H, W, k)), rms=np.empty((M, H, W, k)), V=np.empty((M, H, W)), Wt=np.empty((M, H, W)),
                         D=np.empty((M, H, W)), labels=np.empty((M, H, W), np.int32))
-        bstruct = _lib.DvDetectBands(_ip(sel), k, _dp(cw), None if planes is None else _dp(planes), noise_id, filter_id)
-        cap = max(4096, 64 * M, M * H * W // 1024)
-        while True:                                   # the catalog's size is known after the call: grow once if needed
-            cat = {key: np.empty(cap, np.int32 if key in ("field", "parent", "npix") else np.float64)
-                   for key in self.CATALOG_KEYS}
-            n = C.c_int64()
+        bstruct = _lib.DvDetectBands(_ip(sel), k, _dp(cw), _dp(planes), noise_id, filter_id)
+
+        def call(cap, n, offsets, grms, columns):
             check(lib.dv_scene_detect_multiband(
-                self._h, _dp(f), M, H, W, nb, C.byref(params), cap, C.byref(n), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
-                _dp(grms), *[_ip(cat[key]) if cat[key].dtype == np.int32 else _dp(cat[key]) for key in self.CATALOG_KEYS],
-                *[None if maps.get(key) is None else _dp(maps[key]) for key in ("back", "rms", "V", "Wt", "D")],
-                None if maps.get("labels") is None else _ip(maps["labels"]), C.byref(bstruct), _dp(bgrms), _ip(bad)))
-            if n.value <= cap:
-                break
-            cap = n.value
-        out = {key: v[:n.value].copy() for key, v in cat.items()}
-        out.update(offsets=offsets, globalrms=grms, band_globalrms=bgrms, bad_meshes=bad, **maps)
+                self._h, _dp(f), M, H, W, nb, C.byref(params), cap, n, offsets, grms, *columns,
+                *[_dp(maps.get(key)) for key in ("back", "rms", "V", "Wt", "D")],
+                _ip(maps["labels"]) if return_maps else None, C.byref(bstruct), _dp(bgrms), _ip(bad)))
+
+        out, _ = _run_detect(M, H * W, call)
+        out.update(band_globalrms=bgrms, bad_meshes=bad, **maps)
         return out
 
     def scene_detect_objects(self, fields, bands=None, band_weights=None, thresh: float = 1.5, minarea: int = 4,
@@ -1456,16 +1466,10 @@ class Context:
             M, H, W, nb = f.shape
             sel, cw = check_detect_bands(nb, bands, band_weights)
             planes, noise_id, filter_id = check_detect_band_planes((M, H, W, len(sel)), weights, mask, noise, filter_type, thresh)
-            if not np.isfinite(f).all():
-                fsel = f[:, :, :, sel]
-                if planes is None and not np.isfinite(fsel).all():
-                    raise ValueError("the fields must be finite in the selected bands")
-                if planes is not None and not np.isfinite(fsel[counting_pixels(planes)]).all():
-                    raise ValueError("the fields must be finite in every selected band where that band counts (0 < weight < inf)")
+            _check_multiband_finite(f, sel, planes)
             check_detect_args(np.zeros((0, H, W)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
                               workspace_bytes)
-            bstruct = _lib.DvDetectBands(_ip(sel), len(sel), _dp(cw), None if planes is None else _dp(planes), noise_id,
-                                         filter_id)
+            bstruct = _lib.DvDetectBands(_ip(sel), len(sel), _dp(cw), _dp(planes), noise_id, filter_id)
         else:
             if bands is not None or band_weights is not None:
                 raise ValueError("bands and band_weights belong to fields (M, H, W, bands)")
@@ -1482,31 +1486,20 @@ class Context:
             f = check_detect_args(f, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter, workspace_bytes,
                                   weights=wts)
             M, H, W = f.shape
-        kern, kptr, kh, kw = None, None, 0, 0
-        if filter_kernel is not None:
-            kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
-            kptr, (kh, kw) = kern.ctypes.data_as(C.POINTER(C.c_double)), kern.shape
-        params = _lib.DvDetectParams(float(thresh), float(cont), int(minarea), int(nthresh), int(back_size),
-                                     int(back_filter), kptr, kh, kw, int(workspace_bytes))
-        offsets = np.zeros(M + 1, np.int64)
-        grms = np.zeros(M, np.float64)
-        cap = max(4096, 64 * M, M * H * W // 1024)
-        while True:                                   # the catalog's size is known after the call: grow once if needed
-            cat = {key: np.empty(cap, np.int32 if key in ("field", "parent", "npix") else np.float64)
-                   for key in self.CATALOG_KEYS}
-            obj, ostruct = _object_buffers(cap, (M, H, W) if segmentation_map else None, columns)
-            n = C.c_int64()
+        params, kern = _detect_params(thresh, cont, minarea, nthresh, back_size, back_filter, filter_kernel, workspace_bytes)
+        obj = {}
+
+        def call(cap, n, offsets, grms, catalogue):       # (the object buffers of this size: a retry makes its own)
+            arrays, ostruct = _object_buffers(cap, (M, H, W) if segmentation_map else None, columns)
+            obj.clear()
+            obj.update(arrays)
             check(lib.dv_scene_detect_objects(
-                self._h, _dp(f), M, H, W, nb, C.byref(params), cap, C.byref(n), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
-                _dp(grms), *[_ip(cat[key]) if cat[key].dtype == np.int32 else _dp(cat[key]) for key in self.CATALOG_KEYS],
+                self._h, _dp(f), M, H, W, nb, C.byref(params), cap, n, offsets, grms, *catalogue,
                 None if wstruct is None else C.byref(wstruct), None if bstruct is None else C.byref(bstruct),
                 C.byref(ostruct)))
-            if n.value <= cap:
-                break
-            cap = n.value
-        out = {key: v[:n.value].copy() for key, v in cat.items()}
-        out.update(offsets=offsets, globalrms=grms)
-        out.update({key: (v if key == "segmap" else v[:n.value].copy()) for key, v in obj.items()})
+
+        out, rows = _run_detect(M, H * W, call)
+        out.update({key: (v if key == "segmap" else v[:rows].copy()) for key, v in obj.items()})
         if columns:
             out.update(detect_object_shapes(out["x2"], out["y2"], out["xy"]))
         return out
@@ -2586,33 +2579,16 @@ class FieldSet:
             act = np.ascontiguousarray(np.asarray(active, dtype=bool).astype(np.uint8))
             if act.shape != (M,):
                 raise ValueError(f"expected one active flag per field ({M}), got shape {act.shape}")
-        kern, kptr, kh, kw = None, None, 0, 0
-        if filter_kernel is not None:
-            kern = np.ascontiguousarray(filter_kernel, dtype=np.float64)
-            kptr, (kh, kw) = kern.ctypes.data_as(C.POINTER(C.c_double)), kern.shape
-        params = _lib.DvDetectParams(float(thresh), float(cont), int(minarea), int(nthresh), int(back_size),
-                                     int(back_filter), kptr, kh, kw, int(workspace_bytes))
-        offsets = np.zeros(M + 1, np.int64)
-        grms = np.zeros(M, np.float64)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        cap = max(4096, 64 * M, M * F * F // 1024)
-        while True:                                   # the catalog's size is known after the call: grow once if needed
-            cat = {k: np.empty(cap, np.int32 if k in ("field", "parent", "npix") else np.float64)
-                   for k in Context.CATALOG_KEYS}
-            n = C.c_int64()
+        params, kern = _detect_params(thresh, cont, minarea, nthresh, back_size, back_filter, filter_kernel, workspace_bytes)
+
+        def call(cap, n, offsets, grms, columns):
             check(lib.dv_field_set_detect(h, None if act is None else act.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                          C.byref(params), cap, C.byref(n), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
-                                          grms.ctypes.data_as(dp),
-                                          *[cat[k].ctypes.data_as(ip if cat[k].dtype == np.int32 else dp)
-                                            for k in Context.CATALOG_KEYS]))
-            if n.value <= cap:
-                break
-            cap = n.value
-        out = {k: v[:n.value].copy() for k, v in cat.items()}
-        out.update(offsets=offsets, globalrms=grms)
+                                          C.byref(params), cap, n, offsets, grms, *columns))
+
+        out, rows = _run_detect(M, F * F, call)
         if objects_on:
-            obj, ostruct = _object_buffers(n.value, (M, F, F) if segmap_on else None)
-            check(lib.dv_field_set_detect_objects_read(h, n.value, C.byref(ostruct)))
+            obj, ostruct = _object_buffers(rows, (M, F, F) if segmap_on else None)
+            check(lib.dv_field_set_detect_objects_read(h, rows, C.byref(ostruct)))
             out.update(obj)
             out.update(detect_object_shapes(out["x2"], out["y2"], out["xy"]))
         return out

@@ -111,6 +111,31 @@ def test_bit_reproducible_and_independent_of_the_batch():
         np.testing.assert_array_equal(one["globalrms"][0], a["globalrms"][i])
 
 
+def test_one_field_per_launch_gives_the_same_bytes_on_non_square_fields():
+    """three 48 x 40 fields on 3 x 3 meshes of 16 px, a few sources each: the default workspace (one launch) against a
+    workspace that holds exactly one field (three launches), every output"""
+    import re
+
+    from debvader_amd._lib import DvError
+
+    rng = np.random.default_rng(21)
+    fields = 10.0 + rng.normal(0, 1.0, (3, 48, 40))
+    for i, srcs in enumerate((((12, 10), (30, 28), (40, 8)), ((8, 30), (24, 20)), ((20, 12), (36, 30), (10, 34)))):
+        for cy, cx in srcs:
+            fields[i] += _gauss((48, 40), cy, cx, 1.8, 30.0)
+    ctx = _ctx()
+    kw = dict(back_size=16, return_maps=True)
+    a = ctx.scene_detect(fields, **kw)
+    assert (np.diff(a["offsets"]) >= 2).all()
+    with pytest.raises(DvError, match="workspace") as refused:
+        ctx.scene_detect(fields, workspace_bytes=1, **kw)
+    need = int(re.search(r"needs up to (\d+) bytes", str(refused.value)).group(1))
+    b = ctx.scene_detect(fields, workspace_bytes=need, **kw)
+    assert set(a) == set(b) and {"back", "rms", "D", "labels"} <= set(a)
+    for k in a:
+        assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), k
+
+
 def test_detect_objects_equals_the_oracle_restatement():
     from debvader_amd.detect.detection import detect_objects, detect_objects_batch
 

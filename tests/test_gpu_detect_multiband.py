@@ -225,6 +225,39 @@ def test_bit_reproducible_independent_of_the_batch_and_of_the_workspace():
     _same_bits(a, ctx.scene_detect_multiband(fields, **kw))
 
 
+@pytest.mark.parametrize("with_planes", [False, True])
+def test_one_field_per_launch_gives_the_same_bytes_with_two_of_three_bands(with_planes):
+    """three 48 x 40 fields of three bands on 3 x 3 meshes of 16 px, bands 2 and 0 selected in that order, a few sources
+    each: the default workspace (one launch) against a workspace that holds exactly one field (three launches), every
+    output - the [..][k] maps, band_globalrms and bad_meshes at field * k among them"""
+    from debvader_amd._lib import DvError
+
+    rng = np.random.default_rng(22)
+    y, x = np.mgrid[:48, :40]
+    fields = np.array([4.0, -1.0, 9.0]) + rng.normal(0, 1.0, (3, 48, 40, 3)) * np.array([1.0, 3.0, 0.5])
+    for i, srcs in enumerate((((12, 10), (30, 28), (40, 8)), ((8, 30), (24, 20)), ((20, 12), (36, 30), (10, 34)))):
+        for cy, cx in srcs:
+            g = np.exp(-0.5 * ((x - cx) ** 2 + (y - cy) ** 2) / 1.8 ** 2)
+            fields[i] += g[:, :, None] * np.array([30.0, 5.0, 12.0])
+    kw = dict(bands=[2, 0], band_weights=[1.0, 0.5], thresh=3.0, back_size=16, return_maps=True)
+    if with_planes:
+        P = rng.uniform(0.5, 2.0, (3, 48, 40, 2))
+        P[1, :, 17, :] = 0.0                              # a masked column in field 1, a bad mesh in band 2 of field 2
+        P[2, 32:, 24:, 0] = 0.0
+        kw.update(weights=P, noise="absolute")
+    ctx = _ctx()
+    a = ctx.scene_detect_multiband(fields, **kw)
+    assert (np.diff(a["offsets"]) >= 2).all()
+    if with_planes:
+        assert a["bad_meshes"].tolist() == [[0, 0], [0, 0], [1, 0]]
+    with pytest.raises(DvError, match="workspace") as refused:
+        ctx.scene_detect_multiband(fields, **dict(kw, workspace_bytes=1))
+    b = ctx.scene_detect_multiband(fields, **dict(kw, workspace_bytes=_need(str(refused.value))))
+    assert set(a) == set(b) and set(MAPS) <= set(a)
+    for k in a:
+        assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), k
+
+
 def test_values_under_bands_that_do_not_count_reach_no_sum():
     fields, P, mask, _ = _defects()
     ctx = _ctx()

@@ -154,6 +154,58 @@ def test_detection_on_the_resident_residual(dtype):
     fs.close()
 
 
+def test_detection_one_field_per_launch_gives_the_same_bytes():
+    """three resident 72-pixel fields (a set's fields are square; 4.5 meshes of 16 px a side), a few sources each, the middle
+    one inactive in half of the calls: detect() with the default workspace (one launch) against a workspace that holds exactly
+    one field (one launch per active field, the set's field numbers read at an offset), every output, in each mode the set can
+    hold: band 2 alone, single-band planes, a band selection without and with planes, and the object columns with the segmap"""
+    import re
+
+    from debvader_amd._lib import DvError
+
+    net = _net("float32")
+    eng = net._core.engine
+    F = 72
+    rng = np.random.default_rng(23)
+    y, x = np.mgrid[:F, :F]
+    fields = rng.normal(0, 0.05, (3, F, F, NB))
+    for i, srcs in enumerate((((12, 10), (30, 50), (60, 8)), ((8, 30), (44, 20)), ((20, 12), (36, 60), (10, 34)))):
+        for cy, cx in srcs:
+            g = np.exp(-0.5 * ((x - cx) ** 2 + (y - cy) ** 2) / 1.8 ** 2)
+            fields[i] += g[:, :, None] * rng.uniform(2.0, 6.0, NB)
+    w = rng.uniform(200.0, 600.0, (3, F, F, NB))
+    w[:, :, 40, :] = 0.0
+    fs = eng.open_field_set(fields)
+
+    def both():
+        for active in (None, np.array([True, False, True])):
+            kw = dict(active=active, thresh=3.0, back_size=16)
+            a = fs.detect(**kw)
+            on = np.ones(3, bool) if active is None else active
+            assert (np.diff(a["offsets"])[on] >= 2).all() and not np.diff(a["offsets"])[~on].any()
+            with pytest.raises(DvError, match="workspace") as refused:
+                fs.detect(workspace_bytes=1, **kw)
+            need = int(re.search(r"needs up to (\d+) bytes", str(refused.value)).group(1))
+            b = fs.detect(workspace_bytes=need, **kw)
+            assert set(a) == set(b)
+            for k in a:
+                assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), k
+        return a
+
+    assert "segmap" not in both()                           # band 2 alone
+    fs.set_detect_weights(w[..., 2])
+    both()
+    fs.set_detect_weights(None)
+    fs.set_detect_bands((4, 1, 2), band_weights=(1.0, 0.5, 2.0))
+    both()
+    fs.set_detect_bands((5, 0), weights=w[..., [5, 0]], noise="absolute", filter_type="matched")
+    both()
+    fs.set_detect_objects(True, segmentation_map=True)
+    last = both()
+    assert last["segmap"].shape == (3, F, F) and last["segmap"][0].any() and not last["segmap"][1].any()
+    fs.close()
+
+
 def _loop_fields():
     """Six 131-pixel fields for the loop tests: blob fields of different crowding and brightness, and one of pure noise."""
     F = 131
