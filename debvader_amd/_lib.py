@@ -68,6 +68,16 @@ class DvDetectObjects(C.Structure):
                 + [(k, C.POINTER(C.c_double)) for k in DETECT_OBJECT_DOUBLE] + [("segmap", C.POINTER(C.c_int32))])
 
 
+DETECT_FLAG_MERGED = 16                           # DV_DETECT_FLAG_MERGED
+DETECT_CLEAN_MINAREA_MAX = 64                     # the cleaning pass takes minarea up to this
+
+
+class DvDetectClean(C.Structure):
+    """dv_detect_clean (include/debvader_hip.h)"""
+    _fields_ = [("clean_param", C.c_double), ("nmerged", C.POINTER(C.c_int32)), ("mthresh", C.POINTER(C.c_double)),
+                ("n_raw", C.POINTER(C.c_int64))]
+
+
 DETECT_NOISE = {"absolute": 0, "relative": 1}     # DV_DETECT_NOISE_*
 DETECT_FILTER = {"conv": 0, "matched": 1}         # DV_DETECT_FILTER_*
 
@@ -216,6 +226,10 @@ SIGNATURES = {
     "dv_scene_detect_objects": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams),
                                           C.c_int64, _i64, _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d,
                                           C.POINTER(DvDetectWeights), C.POINTER(DvDetectBands), C.POINTER(DvDetectObjects)]),
+    "dv_scene_detect_clean": (C.c_int, [_p, _d, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DvDetectParams),
+                                        C.c_int64, _i64, _i64, _d, _i32, _i32, _i32, _d, _d, _d, _d,
+                                        C.POINTER(DvDetectWeights), C.POINTER(DvDetectBands), C.POINTER(DvDetectObjects),
+                                        C.POINTER(DvDetectClean)]),
     "dv_measure_params_default": (C.c_int, [C.POINTER(DvMeasureParams)]),
     "dv_scene_measure": (C.c_int, [_p, _f, _f, C.c_int64, C.c_int32, C.c_int32, C.POINTER(DvMeasureParams), _d, _d, _d, _i32,
                                    _i32]),
@@ -269,6 +283,8 @@ SIGNATURES = {
     "dv_field_set_detect_bands": (C.c_int, [_p, _i32, C.c_int32, _d, _d, C.c_int32, C.c_int32]),
     "dv_field_set_detect_objects": (C.c_int, [_p, C.c_int32, C.c_int32]),
     "dv_field_set_detect_objects_read": (C.c_int, [_p, C.c_int64, C.POINTER(DvDetectObjects)]),
+    "dv_field_set_detect_clean": (C.c_int, [_p, C.c_int32, C.c_double]),
+    "dv_field_set_detect_clean_read": (C.c_int, [_p, C.c_int64, _i32, _d, _i64]),
     "dv_field_set_pass": (C.c_int, [_p, _i32, _i32, _i64, C.c_int64, C.c_uint64, _d, _d]),
     "dv_field_set_read": (C.c_int, [_p, C.c_int32, _d]),
     "dv_field_set_close": (C.c_int, [_p]),

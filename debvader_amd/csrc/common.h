@@ -672,6 +672,26 @@ struct DetectObjects {
   double* dcol[DET_OBJ_D];
   int32_t* segmap_h;
 };
+// the cleaning pass of DESIGN 7zc: clean_param (beta), and the columns only it has, nullable: nmerged_h, mthresh_h [cap],
+// written like the catalogue, and n_raw_h [M], the raw objects of every field, always written
+struct DetectClean {
+  double clean_param;
+  int32_t* nmerged_h;
+  double* mthresh_h;
+  int64_t* n_raw_h;
+};
+// the device tables of the cleaning pass over one launch (detect_clean.hip): D and seg of the launch's nf fields of HW pixels,
+// rows W wide; per raw object, in catalogue order, rfield (the field in the launch), rbox xmin xmax ymin ymax, rnum (its segmap
+// number), rnpix, rd dflux x_iso y_iso x2 y2 xy; per field T and fptr, the first raw object (nf + 1 entries).  Written:
+// mthresh [n], der [n][6] a amp alpha cxx cyy cxy, absorber [n], root [2][n] (scratch), rootout [n] the root's raw object,
+// newrow [n] the root's row among its field's survivors, nsurv [nf]
+struct CleanTables {
+  const double* D; const int* seg; int W; long HW; int n, nf;
+  const int *rfield, *rbox, *rnum, *rnpix; const double* rd; const double* fT; const int* fptr;
+  double *mthresh, *der; int *absorber, *root, *rootout, *newrow, *nsurv;
+};
+// the four kernels on s; seg is the launch's segmap of px pixels, renumbered in place
+int detect_clean_launch(const CleanTables& t, int* seg, long px, int minarea, double beta, hipStream_t s);
 // the catalogue of a detection, host arrays: offsets_h [M + 1], globalrms_h [M] and *n_out are always written, the seven
 // columns [cap] only when *n_out <= cap (the caller then calls again with cap >= *n_out: the result is deterministic)
 struct DetectCatalog {
@@ -689,6 +709,7 @@ struct DetectRequest {
   const dv_detect_params* par = nullptr;
   const DetectDevSrc* dev = nullptr;
   const DetectWeights* weights = nullptr; const DetectBands* bands = nullptr; const DetectObjects* objects = nullptr;
+  const DetectClean* clean = nullptr;   // (7zc) the cleaning pass; objects may then be null (the catalogue alone)
   double *back_h = nullptr, *rms_h = nullptr, *D_h = nullptr; int32_t* labels_h = nullptr;
   DetectCatalog cat{};
 };

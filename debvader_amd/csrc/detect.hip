@@ -31,6 +31,8 @@
 // in its OBJECTS instantiation (deblend_dev.h, launched from detect_objects.hip): step e also takes every object's box, peak
 // pixels, isophotal moments and flags and numbers the object's pixels within the component; seg_base_kernel adds the objects of
 // the field's earlier components.
+// With the cleaning pass (tests/detect_clean_oracle.py) the four kernels of detect_clean.hip run behind
+// seg_base_kernel on the launch's raw objects; the merge of the rows is the host's (append_catalogue).
 // fp64 VALU and integer work; nothing here has a matrix shape for MFMA.
 #include "common.h"
 #include "../../include/debvader_hip.h"   // dv_detect_params
@@ -519,6 +521,7 @@ inline unsigned nblk(long total) { return (unsigned)((total + DT - 1) / DT); }
 // (7za) k > 0: k data planes, k planes of P when given, k x the mesh grids and row splines, the combined weight Wt, and for a
 // host source the interleaved staging lines of max(nb, k) values per pixel
 // (7zb) objects: the slots of the new columns and every job's segmap base; segmap: 4 bytes per pixel
+// (7zc) clean: the tables of CleanTables per raw object (at most HW / minarea of them in a field) and per field
 // DetectMode: what a call runs, derived once from its request; every stage, field_bytes and DetectWork::alloc read it.
 // DetectGeom: H x W pixel fields on ny x nx background meshes, HW pixels and at most ccap components of >= minarea pixels each.
 struct DetectMode {
@@ -530,12 +533,18 @@ struct DetectMode {
   int nb_src, stage_nb;            // bands of the source; values per pixel of a host multi-band source's staging lines
   bool absolute, matched;          // T = thresh, not thresh * globalrms; the matched filter
   bool objects, segmap;            // (7zb) the object columns; and the segmap
+  bool clean;                      // (7zc) the cleaning pass: objects and segmap are then on, whatever the caller asks for
   bool back, rms, labels, maps;    // the maps asked for; maps: any of back, rms, D, labels
   bool multi() const { return k > 0; }
   bool wplanes() const { return weighted || planes; }    // the WEIGHTED background kernels run: wt and nbad exist
   int kk() const { return k > 0 ? k : 1; }               // planes per field
 };
 struct DetectGeom { int H, W, ny, nx; long HW, ccap; };
+
+// (7zc) ints rfield rbox[4] rnum rnpix absorber root[2] rootout newrow, doubles rd[6] mthresh der[6]; fptr nsurv, T
+constexpr long CLEAN_ROW_INTS = 12, CLEAN_ROW_DOUBLES = 13, CLEAN_ROW_BYTES = CLEAN_ROW_INTS * 4 + CLEAN_ROW_DOUBLES * 8;
+constexpr long CLEAN_FIELD_BYTES = 2 * 4 + 4 + 8;
+constexpr int CLEAN_MINAREA_MAX = 64;
 
 long field_bytes(const DetectGeom& g, const DetectMode& md) {
   const long H = g.H, HW = g.HW, ny = g.ny, nx = g.nx, capn = g.ccap, k = md.k;
@@ -553,6 +562,7 @@ long field_bytes(const DetectGeom& g, const DetectMode& md) {
   b += capn * ((long)sizeof(DbJob) + 4 * 4 + 4 * 8);          // jobs and catalog slots
   if (md.objects) b += capn * (OBJ_I * 4 + DET_OBJ_D * 8 + 4);
   if (md.segmap) b += HW * 4;
+  if (md.clean) b += capn * CLEAN_ROW_BYTES + CLEAN_FIELD_BYTES;
   return b;
 }
 
@@ -653,9 +663,24 @@ int detect_check(const DetectRequest& rq) {
     set_error("scene_detect: bad arguments");
     return E_INVALID;
   }
-  if (rq.objects && p->thresh < 0.0) {                  // (7zb) the moments' weights D > T must be positive
+  if ((rq.objects || rq.clean) && p->thresh < 0.0) {    // (7zb) the moments' weights D > T must be positive
     set_error("scene_detect: the object shapes and the segmap need thresh >= 0 (got %g)", p->thresh);
     return E_INVALID;
+  }
+  if (rq.clean) {                                       // (7zc)
+    const double beta = rq.clean->clean_param;
+    if (!std::isfinite(beta) || !(beta > 0.0)) {
+      set_error("scene_detect: clean_param must be finite and > 0 (got %g)", beta);
+      return E_INVALID;
+    }
+    if (!(p->thresh > 0.0)) {
+      set_error("scene_detect: the cleaning pass compares profiles with the threshold, thresh must be > 0 (got %g)", p->thresh);
+      return E_INVALID;
+    }
+    if (p->minarea > CLEAN_MINAREA_MAX) {
+      set_error("scene_detect: the cleaning pass takes minarea up to %d (got %d)", CLEAN_MINAREA_MAX, p->minarea);
+      return E_INVALID;
+    }
   }
   if (mb) {
     if (wq) {
@@ -706,7 +731,8 @@ DetectMode detect_mode(const DetectRequest& rq) {
   md.k = mb ? mb->k : 0; md.planes = mb && mb->has_planes; md.planes_abs = md.planes && mb->noise == 0;
   md.nb_src = rq.dev ? rq.dev->nb : rq.nb; md.stage_nb = (mb && !rq.dev) ? std::max(md.nb_src, md.k) : 0;
   md.absolute = mb || (wq && wq->noise == 0); md.matched = mb ? mb->filter == 1 : (wq && wq->filter == 1);
-  md.objects = rq.objects != nullptr; md.segmap = rq.objects && rq.objects->segmap_h;
+  md.clean = rq.clean != nullptr;
+  md.objects = rq.objects || md.clean; md.segmap = (rq.objects && rq.objects->segmap_h) || md.clean;
   md.back = rq.back_h != nullptr; md.rms = rq.rms_h != nullptr; md.labels = rq.labels_h != nullptr;
   md.maps = rq.back_h || rq.rms_h || rq.D_h || rq.labels_h;
   return md;
@@ -745,7 +771,18 @@ struct DetectJobs { std::vector<DbJob> jobs; std::vector<int> jfield; long nj = 
 // what the deblender wrote, on the host: objects per job, the columns per catalogue slot (oi, od: the rows of 7zb); and as
 // HostCatalog the catalogue of all fields of the call, grown launch by launch (oi, od: rows of DET_OBJ_I ints, DET_OBJ_D doubles)
 struct DetectSlots { std::vector<int> nobj, npix, oi; std::vector<double> peak, flux, x, y, od; };
-struct HostCatalog { std::vector<int32_t> field, parent, npix, oi; std::vector<double> peak, flux, x, y, od; };
+struct HostCatalog {
+  std::vector<int32_t> field, parent, npix, oi, nmerged; std::vector<double> peak, flux, x, y, od, mthresh;
+  void truncate(size_t n) {
+    for (std::vector<int32_t>* v : {&field, &parent, &npix, &nmerged}) if (v->size() > n) v->resize(n);
+    for (std::vector<double>* v : {&peak, &flux, &x, &y, &mthresh}) if (v->size() > n) v->resize(n);
+    if (oi.size() > n * DET_OBJ_I) oi.resize(n * DET_OBJ_I);
+    if (od.size() > n * DET_OBJ_D) od.resize(n * DET_OBJ_D);
+  }
+};
+// (7zc) what the cleaning pass found, per raw object of the launch in catalogue order: its root (a raw object of the launch),
+// the root's row among the survivors of its field, its mthresh; fptr: every field's first raw object
+struct DetectCleaned { std::vector<int> root, newrow, fptr; std::vector<double> mthresh; };
 
 // one call: the request, what it asks for, the device workspace and the catalogue so far; the stages are its methods
 struct DetectRun {
@@ -973,8 +1010,60 @@ struct DetectRun {
     DV_HIP(hipStreamSynchronize(s));                      // (jb and the scratch leave scope)
     return OK;
   }
+  // 9b. (7zc) the cleaning pass: the launch's raw objects in catalogue order go up as tables, the four kernels run on D and
+  // the numbered segmap, and every object's root, new row and mthresh come back; returns with the stream idle
+  int clean(const DetectLaunch& L, const DetectJobs& J, const DetectSlots& h, DetectCleaned& c) {
+    std::vector<int> up;                                  // rfield | rbox | rnum | rnpix | fptr
+    std::vector<double> upd;                              // rd | fT
+    std::vector<int> rfield, rbox, rnum, rnpix;
+    c.fptr.assign((size_t)L.m + 1, 0);
+    std::vector<double> rd, fT((size_t)L.m);
+    long ji = 0;
+    for (int f = 0; f < L.m; ++f) {
+      fT[f] = md.absolute ? p.thresh : p.thresh * rq.cat.globalrms_h[L.f0 + f];
+      int k = 0;
+      for (; ji < J.nj && J.jfield[ji] == L.f0 + f; ++ji) {
+        for (int o = 0; o < h.nobj[ji]; ++o) {
+          const long sl = J.jobs[ji].slot + o;
+          rfield.push_back(f);
+          rbox.insert(rbox.end(), h.oi.begin() + sl * OBJ_I, h.oi.begin() + sl * OBJ_I + 4);
+          rnum.push_back(++k);
+          rnpix.push_back(h.npix[sl]);
+          rd.insert(rd.end(), h.od.begin() + sl * DET_OBJ_D + 1, h.od.begin() + (sl + 1) * DET_OBJ_D);
+        }
+      }
+      c.fptr[f + 1] = (int)rfield.size();
+    }
+    const size_t n = rfield.size(), nf = (size_t)L.m;
+    c.root.resize(n); c.newrow.resize(n); c.mthresh.resize(n);
+    if (n == 0) return OK;
+    for (const std::vector<int>* v : {&rfield, &rbox, &rnum, &rnpix, &c.fptr}) up.insert(up.end(), v->begin(), v->end());
+    upd = rd;
+    upd.insert(upd.end(), fT.begin(), fT.end());
+    DevBuf<int> ib;
+    DevBuf<double> db;
+    DV_TRY(ib.alloc(CLEAN_ROW_INTS * n + 2 * nf + 1));
+    DV_TRY(db.alloc(CLEAN_ROW_DOUBLES * n + nf));
+    DV_HIP(hipMemcpyAsync(ib, up.data(), up.size() * 4, hipMemcpyHostToDevice, s));
+    DV_HIP(hipMemcpyAsync(db, upd.data(), upd.size() * 8, hipMemcpyHostToDevice, s));
+    int* i0 = ib;
+    double* d0 = db;
+    CleanTables t{};
+    t.D = w.D; t.seg = w.seg; t.W = g.W; t.HW = g.HW; t.n = (int)n; t.nf = (int)nf;
+    t.rfield = i0; t.rbox = i0 + n; t.rnum = i0 + 5 * n; t.rnpix = i0 + 6 * n; t.fptr = i0 + 7 * n;
+    int* iw = i0 + 7 * n + nf + 1;
+    t.absorber = iw; t.root = iw + n; t.rootout = iw + 3 * n; t.newrow = iw + 4 * n; t.nsurv = iw + 5 * n;
+    t.rd = d0; t.fT = d0 + 6 * n;
+    t.mthresh = d0 + 6 * n + nf; t.der = d0 + 7 * n + nf;
+    DV_TRY(detect_clean_launch(t, w.seg, L.px, p.minarea, rq.clean->clean_param, s));
+    DV_TRY(to_host(c.root.data(), t.rootout, n * 4));
+    DV_TRY(to_host(c.newrow.data(), t.newrow, n * 4));
+    DV_TRY(to_host(c.mthresh.data(), t.mthresh, n * 8));
+    DV_HIP(hipStreamSynchronize(s));                      // (the tables leave scope)
+    return OK;
+  }
   // 8. the deblend launch over the launch's jobs and its read-back into h, then (9) the segmap to the caller's array at f0
-  int deblend(const DetectLaunch& L, DetectJobs& J, DetectSlots& h) {
+  int deblend(const DetectLaunch& L, DetectJobs& J, DetectSlots& h, DetectCleaned& cl) {
     const size_t nj = (size_t)J.nj, slots = (size_t)J.slots;
     h.nobj.resize(nj); h.npix.resize(slots);
     for (std::vector<double>* v : {&h.peak, &h.flux, &h.x, &h.y}) v->resize(slots);
@@ -1010,8 +1099,9 @@ struct DetectRun {
       DV_TRY(to_host(h.y.data(), d.o_y, slots * 8));
       DV_HIP(hipStreamSynchronize(s));
       if (md.segmap) DV_TRY(segmap_base(L, J, h, d));
+      if (md.clean) DV_TRY(clean(L, J, h, cl));
     }
-    if (md.segmap) {
+    if (rq.objects && rq.objects->segmap_h) {
       DV_TRY(to_host(rq.objects->segmap_h + (size_t)L.f0 * g.HW, w.seg, (size_t)L.px * 4));
       DV_HIP(hipStreamSynchronize(s));
     }
@@ -1019,9 +1109,10 @@ struct DetectRun {
   }
 
   // 10. the launch's objects behind the catalogue, field by field, and the fields' offsets
-  void append_catalogue(const DetectLaunch& L, const DetectJobs& J, const DetectSlots& h) {
+  void append_catalogue(const DetectLaunch& L, const DetectJobs& J, const DetectSlots& h, const DetectCleaned& cl) {
     long ji = 0;
     for (int f = 0; f < L.m; ++f) {
+      const size_t row0 = cat.field.size();
       for (; ji < J.nj && J.jfield[ji] == L.f0 + f; ++ji) {
         for (int o = 0; o < h.nobj[ji]; ++o) {
           const long sl = J.jobs[ji].slot + o;
@@ -1038,7 +1129,69 @@ struct DetectRun {
           }
         }
       }
+      if (md.clean) {
+        if (rq.clean->n_raw_h) rq.clean->n_raw_h[L.f0 + f] = (int64_t)(cat.field.size() - row0);
+        if (!cl.fptr.empty()) merge_cleaned(row0, cl, cl.fptr[f]);
+      }
       rq.cat.offsets_h[L.f0 + f + 1] = (int64_t)cat.field.size();
+    }
+  }
+
+  // (7zc) the raw rows of one field, the catalogue's from row0 on (raw object r0 of the launch first), become its cleaned rows:
+  // the survivors in order, every victim merged into its root in ascending raw row (sep's mergeobject)
+  void merge_cleaned(size_t row0, const DetectCleaned& cl, int r0) {
+    const size_t n = cat.field.size() - row0;
+    cat.nmerged.resize(row0 + n, 1);
+    cat.mthresh.resize(row0 + n, 0.0);
+    bool any = false;
+    for (size_t r = 0; r < n; ++r) {
+      cat.mthresh[row0 + r] = cl.mthresh[r0 + r];
+      any = any || cl.root[r0 + r] != r0 + (int)r;
+    }
+    if (!any) return;                                     // nothing absorbed: the rows stay as they are, bit for bit
+    HostCatalog raw;
+    const auto take = [&](auto& dst, const auto& src, size_t width) {
+      dst.assign(src.begin() + row0 * width, src.end());
+    };
+    take(raw.field, cat.field, 1); take(raw.parent, cat.parent, 1); take(raw.npix, cat.npix, 1); take(raw.peak, cat.peak, 1);
+    take(raw.flux, cat.flux, 1); take(raw.x, cat.x, 1); take(raw.y, cat.y, 1); take(raw.oi, cat.oi, DET_OBJ_I);
+    take(raw.od, cat.od, DET_OBJ_D); take(raw.mthresh, cat.mthresh, 1);
+    // surv[k]: the raw row of survivor k; the victims join in ascending raw row
+    std::vector<size_t> surv;
+    for (size_t r = 0; r < n; ++r)
+      if (cl.root[r0 + r] == r0 + (int)r) surv.push_back(r);
+    cat.truncate(row0);
+    for (size_t r : surv) {
+      cat.field.push_back(raw.field[r]); cat.parent.push_back(raw.parent[r]); cat.npix.push_back(raw.npix[r]);
+      cat.peak.push_back(raw.peak[r]); cat.flux.push_back(raw.flux[r]); cat.x.push_back(raw.x[r]); cat.y.push_back(raw.y[r]);
+      cat.oi.insert(cat.oi.end(), raw.oi.begin() + r * DET_OBJ_I, raw.oi.begin() + (r + 1) * DET_OBJ_I);
+      cat.od.insert(cat.od.end(), raw.od.begin() + r * DET_OBJ_D, raw.od.begin() + (r + 1) * DET_OBJ_D);
+      cat.nmerged.push_back(1); cat.mthresh.push_back(raw.mthresh[r]);
+    }
+    std::vector<size_t> pk = surv, vk = surv;
+    for (size_t r = 0; r < n; ++r) {
+      if (cl.root[r0 + r] == r0 + (int)r) continue;
+      const size_t k = row0 + (size_t)cl.newrow[r0 + r];
+      int32_t* si = &cat.oi[k * DET_OBJ_I];
+      double* sd = &cat.od[k * DET_OBJ_D];
+      const int32_t* vi = &raw.oi[r * DET_OBJ_I];
+      const double* vd = &raw.od[r * DET_OBJ_D];
+      cat.npix[k] += raw.npix[r];
+      cat.flux[k] += raw.flux[r];
+      sd[1] += vd[1];                                      // dflux
+      // the largest value, a tie to the earlier raw row: pk / vk hold the raw row the merged row's peak / vpeak come from
+      if (raw.peak[r] > cat.peak[k] || (raw.peak[r] == cat.peak[k] && r < pk[k - row0])) {
+        cat.peak[k] = raw.peak[r]; si[4] = vi[4]; si[5] = vi[5];
+        pk[k - row0] = r;
+      }
+      if (vd[0] > sd[0] || (vd[0] == sd[0] && r < vk[k - row0])) {
+        sd[0] = vd[0]; si[6] = vi[6]; si[7] = vi[7];
+        vk[k - row0] = r;
+      }
+      si[0] = std::min(si[0], vi[0]); si[1] = std::max(si[1], vi[1]);
+      si[2] = std::min(si[2], vi[2]); si[3] = std::max(si[3], vi[3]);
+      si[8] |= vi[8] | DV_DETECT_FLAG_MERGED;
+      ++cat.nmerged[k];
     }
   }
 
@@ -1055,7 +1208,11 @@ struct DetectRun {
     std::copy(cat.flux.begin(), cat.flux.end(), out.flux_h);
     std::copy(cat.x.begin(), cat.x.end(), out.x_h);
     std::copy(cat.y.begin(), cat.y.end(), out.y_h);
-    if (!md.objects) return;
+    if (md.clean) {
+      if (rq.clean->nmerged_h) std::copy(cat.nmerged.begin(), cat.nmerged.end(), rq.clean->nmerged_h);
+      if (rq.clean->mthresh_h) std::copy(cat.mthresh.begin(), cat.mthresh.end(), rq.clean->mthresh_h);
+    }
+    if (!rq.objects) return;
     for (size_t i = 0; i < n; ++i) {
       for (int e = 0; e < DET_OBJ_I; ++e)
         if (rq.objects->icol[e]) rq.objects->icol[e][i] = cat.oi[i * DET_OBJ_I + e];
@@ -1122,9 +1279,10 @@ int scene_detect(const DetectRequest& rq, hipStream_t s) {
     DV_TRY(run.copy_out(L));
     DetectJobs jobs;
     DetectSlots slots;
+    DetectCleaned cleaned;
     DV_TRY(run.job_table(L, jobs));
-    DV_TRY(run.deblend(L, jobs, slots));
-    run.append_catalogue(L, jobs, slots);
+    DV_TRY(run.deblend(L, jobs, slots, cleaned));
+    run.append_catalogue(L, jobs, slots, cleaned);
   }
   run.write_catalogue();
   return OK;

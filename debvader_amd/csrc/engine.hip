@@ -596,7 +596,15 @@ struct dv_field_set {
   int64_t do_n = -1;
   std::vector<int32_t> do_i[dv::DET_OBJ_I], do_seg;
   std::vector<double> do_d[dv::DET_OBJ_D];
-  dv::StampTables tab;                          // the per-stamp tables of a pass, kept between passes and grown on demand
+  // the cleaning pass (dv_field_set_detect_clean): while dclean is set dv_field_set_detect runs it with
+  // dclean_param and the set keeps the clean columns of its last detection on the host: dc_n rows (-1: none), dc_nraw [M]
+  bool dclean = false;
+  double dclean_param = 1.0;
+  int64_t dc_n = -1;
+  std::vector<int32_t> dc_nmerged;
+  std::vector<double> dc_mthresh;
+  std::vector<int64_t> dc_nraw;
+  dv::StampTables tab;                         // the per-stamp tables of a pass, kept between passes and grown on demand
   std::vector<double> fmse_h;                     // host side of fmse
   // the catalogue of the measured passes (dv_field_set_pass_measure).  Resident rows: {shape[5], status,
   // place, field} of every stamp of every pass that took child sums, in call order; nrows of them are kept, the tail up
@@ -4218,6 +4226,61 @@ int dv_scene_detect_objects(dv_ctx* c, const double* fields, int32_t M, int32_t 
   return scene_detect(rq, c->stream);
 }
 
+// (7zc) the refusals of a cleaning request that need no field: a null struct, clean_param, thresh, minarea
+static int detect_clean_check(const char* who, bool given, double clean_param, const dv_detect_params* p) {
+  if (!given) {
+    set_error("%s: the clean request must be given (dv_scene_detect_objects is the call without it)", who);
+    return DV_E_INVALID;
+  }
+  if (!std::isfinite(clean_param) || !(clean_param > 0.0)) {
+    set_error("%s: clean_param must be finite and > 0 (got %g)", who, clean_param);
+    return DV_E_INVALID;
+  }
+  if (!(p->thresh > 0.0)) {
+    set_error("%s: the cleaning pass compares profiles with the threshold, thresh must be > 0 (got %g)", who, p->thresh);
+    return DV_E_INVALID;
+  }
+  if (p->minarea > 64) {
+    set_error("%s: the cleaning pass takes minarea up to 64 (got %d)", who, p->minarea);
+    return DV_E_INVALID;
+  }
+  return DV_OK;
+}
+
+int dv_scene_detect_clean(dv_ctx* c, const double* fields, int32_t M, int32_t H, int32_t W, int32_t nb,
+                          const dv_detect_params* p, int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms,
+                          int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux, double* x, double* y,
+                          const dv_detect_weights* wt, const dv_detect_bands* b, const dv_detect_objects* objects,
+                          const dv_detect_clean* clean) {
+  if (!c || !p) return DV_E_INVALID;
+  if (wt && b) {
+    set_error("dv_scene_detect_clean: single-band weights and a band selection exclude each other");
+    return DV_E_INVALID;
+  }
+  if (wt && !wt->weights) {
+    set_error("dv_scene_detect_clean: a weights struct without weights");
+    return DV_E_INVALID;
+  }
+  DV_TRY(detect_clean_check("dv_scene_detect_clean", clean != nullptr, clean ? clean->clean_param : 0.0, p));
+  DV_HIP(hipSetDevice(c->device));
+  if (!fields || (!b && nb != 0)) {
+    set_error("scene_detect_clean: bad arguments (fields [M][H][W] with nb = 0, or [M][H][W][nb] with a band selection and "
+              "no single-band weights)");
+    return DV_E_INVALID;
+  }
+  DetectObjects oq{};
+  if (objects) oq = detect_objects_of(objects);
+  DetectWeights wq{};
+  if (wt) wq = detect_weights_of(wt, nullptr);
+  DetectBands mb{};
+  if (b) mb = detect_bands_of(b);
+  const DetectClean cq{clean->clean_param, clean->nmerged, clean->mthresh, clean->n_raw};
+  DetectRequest rq{fields, nb, M, H, W, p};
+  rq.weights = wt ? &wq : nullptr; rq.bands = b ? &mb : nullptr; rq.objects = objects ? &oq : nullptr; rq.clean = &cq;
+  rq.cat = DetectCatalog{cap, n_out, offsets, globalrms, field, parent, npix, peak, flux, x, y};
+  return scene_detect(rq, c->stream);
+}
+
 int dv_ctx_allreduce_host(dv_ctx* c, float* buf, int32_t n) {
   if (!c || !buf || n < 0 || n > 4096) return DV_E_INVALID;
   if (!c->comm || n == 0) return DV_OK;
@@ -6397,9 +6460,21 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
       oq.segmap_h = seg_a.data();
     }
   }
+  // (7zc) the clean columns land in the set's host arrays, n_raw of the active fields in nraw_a
+  DetectClean cq{};
+  std::vector<int64_t> nraw_a;
+  if (fs->dclean) {
+    DV_TRY(detect_clean_check("dv_field_set_detect", true, fs->dclean_param, p));
+    fs->dc_n = -1;
+    fs->dc_nmerged.assign((size_t)std::max<int64_t>(cap, 0), 0);
+    fs->dc_mthresh.assign((size_t)std::max<int64_t>(cap, 0), 0.0);
+    nraw_a.assign((size_t)std::max(Ma, 1), 0);
+    cq = DetectClean{fs->dclean_param, fs->dc_nmerged.data(), fs->dc_mthresh.data(), nraw_a.data()};
+  }
   if (Ma > 0) {
     DetectRequest rq{nullptr, 0, Ma, fs->F, fs->F, p, &src};
     rq.weights = (!multi && fs->dweights) ? &wq : nullptr; rq.bands = multi ? &mb : nullptr; rq.objects = fs->dobj ? &oq : nullptr;
+    rq.clean = fs->dclean ? &cq : nullptr;
     rq.cat = DetectCatalog{cap, n_out, off.data(), grms.data(), field, parent, npix, peak, flux, x, y};
     DV_TRY(scene_detect(rq, fs->m->ctx->stream));
   }
@@ -6410,6 +6485,11 @@ int dv_field_set_detect(dv_field_set* fs, const uint8_t* active, const dv_detect
       for (int a = 0; a < Ma; ++a)
         std::copy(seg_a.begin() + (size_t)a * FF, seg_a.begin() + (size_t)(a + 1) * FF, fs->do_seg.begin() + (size_t)act[a] * FF);
     }
+  }
+  if (fs->dclean) {
+    if (*n_out <= cap) fs->dc_n = *n_out;
+    fs->dc_nraw.assign((size_t)fs->M, 0);
+    for (int a = 0; a < Ma; ++a) fs->dc_nraw[act[a]] = nraw_a[a];
   }
   // the catalogue of the active fields in the numbering of the set: an inactive field has an empty range
   offsets[0] = 0;
@@ -6464,6 +6544,44 @@ int dv_field_set_detect_objects_read(dv_field_set* fs, int64_t n_expected, const
   for (int e = 0; e < DET_OBJ_D; ++e)
     if (o.dcol[e]) std::copy(fs->do_d[e].begin(), fs->do_d[e].begin() + n, o.dcol[e]);
   if (o.segmap_h) std::copy(fs->do_seg.begin(), fs->do_seg.end(), o.segmap_h);
+  return DV_OK;
+}
+
+int dv_field_set_detect_clean(dv_field_set* fs, int32_t on, double clean_param) {
+  DV_TRY(field_set_live(fs, "dv_field_set_detect_clean"));
+  if (on != 0 && (!std::isfinite(clean_param) || !(clean_param > 0.0))) {
+    set_error("dv_field_set_detect_clean: clean_param must be finite and > 0 (got %g)", clean_param);
+    return DV_E_INVALID;
+  }
+  fs->dclean = on != 0;
+  fs->dclean_param = on != 0 ? clean_param : 1.0;
+  fs->dc_n = -1;
+  std::vector<int32_t>().swap(fs->dc_nmerged);
+  std::vector<double>().swap(fs->dc_mthresh);
+  std::vector<int64_t>().swap(fs->dc_nraw);
+  return DV_OK;
+}
+
+int dv_field_set_detect_clean_read(dv_field_set* fs, int64_t n_expected, int32_t* nmerged, double* mthresh, int64_t* n_raw) {
+  DV_TRY(field_set_live(fs, "dv_field_set_detect_clean_read"));
+  if (!fs->dclean) {
+    set_error("dv_field_set_detect_clean_read: the cleaning pass is off (dv_field_set_detect_clean)");
+    return DV_E_INVALID;
+  }
+  if (fs->dc_n < 0) {
+    set_error("dv_field_set_detect_clean_read: no detection is kept (none since the switch went on, or its catalogue did not "
+              "fit its cap)");
+    return DV_E_INVALID;
+  }
+  if (n_expected != fs->dc_n) {
+    set_error("dv_field_set_detect_clean_read: %lld rows expected, the last detection has %lld", (long long)n_expected,
+              (long long)fs->dc_n);
+    return DV_E_INVALID;
+  }
+  const size_t n = (size_t)fs->dc_n;
+  if (nmerged) std::copy(fs->dc_nmerged.begin(), fs->dc_nmerged.begin() + n, nmerged);
+  if (mthresh) std::copy(fs->dc_mthresh.begin(), fs->dc_mthresh.begin() + n, mthresh);
+  if (n_raw) std::copy(fs->dc_nraw.begin(), fs->dc_nraw.end(), n_raw);
   return DV_OK;
 }
 

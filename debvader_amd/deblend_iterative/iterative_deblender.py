@@ -286,7 +286,7 @@ class IterativeDeblendFieldBatch:
                             blendedness=False, return_fields=True, band=2, sigma0=3.0, tol=1e-10, max_iter=200,
                             match_radius=2.0, fit_flux=False, fit_weights=None, fit_sky=None, fit_nonneg=False,
                             sky_sigma=None, min_pivot=1e-8, detect_shapes=False, detect_bands=None, detect_band_weights=None,
-                            detect_weights=None, detect_noise=None, detect_filter="conv", detect_thresh=None, fit_groups=False):
+                            detect_clean=None, detect_weights=None, detect_noise=None, detect_filter="conv", detect_thresh=None, fit_groups=False):
         """iterative_deblending() with a catalogue measured on the GPU: the same loop, the same
         list of M recarrays (kept in self.res_deblend), self.mse and fields, and with every argument behind the first
         three left at its default the same calls.  The arguments are a method of their own because the parameter list of
@@ -349,6 +349,12 @@ class IterativeDeblendFieldBatch:
             det_xy with det_a, det_b, det_theta, and det_flag (bit 1: the detection was split off a blend, 2: cut by the
             field's edge, 4: singular moments, 8: next to a pixel that does not count).  With or without measure; every other
             column, self.mse and the fields keep their bits.  detect_thresh must then be >= 0.
+        detect_clean: True (clean_param 1.0) or a clean_param > 0: every detection pass is followed by SExtractor's cleaning
+            pass (FieldSet.set_detect_clean before the first pass; sep's clean=True, which the
+            reference's sep call leaves on): a detection that the wings of a brighter neighbour explain is merged into that
+            neighbour and gets no stamp - in the first pass and in every residual pass.  None or False: no cleaning, the
+            calls as they were.  detect_thresh must then be > 0.  With detect_shapes=True the det_ columns are the cleaned
+            rows' and gain det_nmerged behind det_flag (1 + the detections merged into the row).
 
         mse_criterion, mode, max_iterations: as in iterative_deblending."""
         if mode not in ("reference", "cumulative"):
@@ -398,6 +404,14 @@ class IterativeDeblendFieldBatch:
         if detect_shapes and detect_thresh is not None and not float(detect_thresh) >= 0:
             raise ValueError(f"detect_shapes=True needs detect_thresh >= 0 (the moments weight every pixel above it), "
                              f"got {detect_thresh}")
+        if isinstance(detect_clean, (bool, np.bool_)):
+            detect_clean = 1.0 if detect_clean else None
+        if detect_clean is not None:
+            from debvader_amd import engine as E
+
+            E.check_detect_clean(detect_clean, 1.5 if detect_thresh is None else detect_thresh, None)
+            detect_clean = float(detect_clean)
+        det_columns = self.DETECT_COLUMNS + (self.DETECT_CLEAN_COLUMNS if detect_clean is not None else [])
         shapes = [[] for _ in range(M)]      # detect_shapes: per field and pass, the detections of the kept rows
         if detect_bands is not None:
             from debvader_amd import engine as E
@@ -448,6 +462,8 @@ class IterativeDeblendFieldBatch:
                 fs.set_detect_weights(detect_weights, noise=detect_noise, filter_type=detect_filter)
             if detect_shapes:
                 fs.set_detect_objects(True)
+            if detect_clean is not None:
+                fs.set_detect_clean(True, detect_clean)
             k = 0
             while active.any() and (max_iterations is None or k < int(max_iterations)):
                 det = fs.detect(active=active, **detect_kw)
@@ -484,7 +500,7 @@ class IterativeDeblendFieldBatch:
                     steps[m].append(self._records(kept[m], dd[lo:hi], out["mse_center"][lo:hi], passed[lo:hi], total[m], k))
                     if detect_shapes:
                         rows_m = int(off[m]) + np.asarray(kept[m], dtype=np.int64)
-                        shapes[m].append({name: np.asarray(det[name[4:]])[rows_m] for name, _ in self.DETECT_COLUMNS})
+                        shapes[m].append({name: np.asarray(det[name[4:]])[rows_m] for name, _ in det_columns})
                     if measure:
                         e = {k: out[k][lo:hi] for k in ("flux", "flux_err", "shape", "iters", "status")}
                         e["places"] = np.asarray(places[lo:hi], dtype=np.float64)
@@ -531,7 +547,7 @@ class IterativeDeblendFieldBatch:
             if fit_nonneg:
                 self.nonneg_fit = {k: fit[k] for k in E.FIT_NONNEG_FIELD_KEYS}
         if detect_shapes:
-            self.res_deblend = [self._with_detections(r, d) for r, d in zip(self.res_deblend, shapes)]
+            self.res_deblend = [self._with_detections(r, d, det_columns) for r, d in zip(self.res_deblend, shapes)]
         return self.res_deblend
 
     # what iterative_catalogue(detect_shapes=True) appends behind every other column: the detection of the row's pass
@@ -539,12 +555,17 @@ class IterativeDeblendFieldBatch:
                       + [("det_" + k, "<i4") for k in ("xmin", "xmax", "ymin", "ymax")]
                       + [("det_" + k, "<f8") for k in ("x2", "y2", "xy", "a", "b", "theta")] + [("det_flag", "<i4")])
 
-    def _with_detections(self, rec, passes):
-        """The records of one field with DETECT_COLUMNS behind them: per pass, the detector's rows of the kept stamps."""
-        out = np.recarray((len(rec),), dtype=rec.dtype.descr + self.DETECT_COLUMNS)
+    # ... and behind them with detect_clean
+    DETECT_CLEAN_COLUMNS = [("det_nmerged", "<i4")]
+
+    def _with_detections(self, rec, passes, columns=None):
+        """The records of one field with DETECT_COLUMNS (or `columns`) behind them: per pass, the detector's rows of the
+        kept stamps."""
+        columns = self.DETECT_COLUMNS if columns is None else columns
+        out = np.recarray((len(rec),), dtype=rec.dtype.descr + columns)
         for k in rec.dtype.names:
             out[k] = rec[k]
-        for name, t in self.DETECT_COLUMNS:
+        for name, t in columns:
             out[name] = np.concatenate([d[name] for d in passes]) if passes else np.zeros(0, dtype=t)
         return out
 

@@ -508,7 +508,23 @@ def check_detect_band_planes(shape, weights, mask, noise, filter_type, thresh):
     return check_detect_weights(shape, weights, mask, noise, filter_type, thresh)
 
 
+def check_detect_clean(clean_param, thresh, minarea):
+    """The arguments of the cleaning pass (Context.scene_detect_clean, FieldSet.set_detect_clean),
+    checked before any GPU work: clean_param finite and > 0, thresh > 0, minarea <= 64."""
+    try:
+        ok = np.isfinite(float(clean_param)) and float(clean_param) > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or isinstance(clean_param, (bool, np.bool_)):
+        raise ValueError(f"clean_param must be a finite number > 0, got {clean_param!r}")
+    if thresh is not None and not float(thresh) > 0:
+        raise ValueError(f"the cleaning pass compares profiles with the threshold: thresh must be > 0, got {thresh}")
+    if minarea is not None and int(minarea) > _lib.DETECT_CLEAN_MINAREA_MAX:
+        raise ValueError(f"the cleaning pass takes minarea up to {_lib.DETECT_CLEAN_MINAREA_MAX}, got {minarea}")
+
+
 OBJECT_KEYS = _lib.DETECT_OBJECT_INT + _lib.DETECT_OBJECT_DOUBLE
+CLEAN_KEYS = ("nmerged", "mthresh")
 OBJECT_DERIVED = ("a", "b", "theta", "cxx", "cyy", "cxy")
 
 
@@ -590,6 +606,73 @@ def counting_pixels(w):
     """the pixels that count: 0 < w < inf (NaN does not)"""
     with np.errstate(invalid="ignore"):
         return (w > 0) & (w < np.inf)
+
+
+def _scene_detect_objects(ctx, fields, bands, band_weights, thresh, minarea, nthresh, cont, filter_kernel, back_size,
+                          back_filter, workspace_bytes, weights, mask, noise, filter_type, segmentation_map, columns,
+                          clean_param) -> Dict[str, np.ndarray]:
+    """Context.scene_detect_objects (clean_param None) and Context.scene_detect_clean: the checks, all before the context is
+    touched, the buffers and the library call"""
+    clean = clean_param is not None
+    if not float(thresh) >= 0:
+        raise ValueError(f"the object shapes weight every pixel with D > thresh: thresh must be >= 0, got {thresh}")
+    if not (columns or segmentation_map or clean):
+        raise ValueError("nothing asked for: columns, segmentation_map or both")
+    f = np.ascontiguousarray(fields, dtype=np.float64)
+    multi = f.ndim == 4
+    bstruct, wstruct, bgrms = None, None, None
+    if multi:
+        if min(f.shape[1:]) < 1:
+            raise ValueError(f"expected fields (M, H, W, bands), got {f.shape}")
+        M, H, W, nb = f.shape
+        sel, cw = check_detect_bands(nb, bands, band_weights)
+        planes, noise_id, filter_id = check_detect_band_planes((M, H, W, len(sel)), weights, mask, noise, filter_type, thresh)
+        _check_multiband_finite(f, sel, planes)
+        check_detect_args(np.zeros((0, H, W)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
+                          workspace_bytes)
+        bstruct = _lib.DvDetectBands(_ip(sel), len(sel), _dp(cw), _dp(planes), noise_id, filter_id)
+    else:
+        if bands is not None or band_weights is not None:
+            raise ValueError("bands and band_weights belong to fields (M, H, W, bands)")
+        nb = 0
+        wts = None
+        if weights is not None or mask is not None:
+            shape = np.shape(fields)
+            if len(shape) != 3:
+                raise ValueError(f"expected fields (M, H, W) or (M, H, W, bands), got {shape}")
+            wts, noise_id, filter_id = check_detect_weights(shape, weights, mask, noise, filter_type, thresh)
+            wstruct = _lib.DvDetectWeights(_dp(wts), noise_id, filter_id)
+        elif noise is not None or filter_type != "conv":
+            raise ValueError("noise and filter_type belong to the weighted call: give weights, a mask or both")
+        f = check_detect_args(f, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter, workspace_bytes,
+                              weights=wts)
+        M, H, W = f.shape
+    params, kern = _detect_params(thresh, cont, minarea, nthresh, back_size, back_filter, filter_kernel, workspace_bytes)
+    obj = {}
+    n_raw = np.zeros(M, np.int64)
+
+    def call(cap, n, offsets, grms, catalogue):       # (the object buffers of this size: a retry makes its own)
+        arrays, ostruct = _object_buffers(cap, (M, H, W) if segmentation_map else None, columns)
+        obj.clear()
+        obj.update(arrays)
+        args = [ctx._h, _dp(f), M, H, W, nb, C.byref(params), cap, n, offsets, grms, *catalogue,
+                None if wstruct is None else C.byref(wstruct), None if bstruct is None else C.byref(bstruct)]
+        if not clean:
+            check(lib.dv_scene_detect_objects(*args, C.byref(ostruct)))
+            return
+        obj.update(nmerged=np.zeros(cap, np.int32), mthresh=np.zeros(cap, np.float64))
+        cstruct = _lib.DvDetectClean(clean_param, _ip(obj["nmerged"]), _dp(obj["mthresh"]),
+                                     n_raw.ctypes.data_as(C.POINTER(C.c_int64)))
+        check(lib.dv_scene_detect_clean(*args, C.byref(ostruct) if (columns or segmentation_map) else None,
+                                        C.byref(cstruct)))
+
+    out, rows = _run_detect(M, H * W, call)
+    out.update({key: (v if key == "segmap" else v[:rows].copy()) for key, v in obj.items()})
+    if clean:
+        out["n_raw"] = n_raw
+    if columns:
+        out.update(detect_object_shapes(out["x2"], out["y2"], out["xy"]))
+    return out
 
 
 class _Lease:
@@ -1453,56 +1536,31 @@ class Context:
         not count; the derived a, b, theta, cxx, cyy, cxy; and with segmentation_map segmap (M, H, W) int32: 0 outside
         every object, k + 1 on the pixels of row offsets[f] + k of field f.  columns=False leaves the columns out (the
         segmap alone).  thresh must be >= 0."""
-        if not float(thresh) >= 0:
-            raise ValueError(f"the object shapes weight every pixel with D > thresh: thresh must be >= 0, got {thresh}")
-        if not (columns or segmentation_map):
-            raise ValueError("nothing asked for: columns, segmentation_map or both")
-        f = np.ascontiguousarray(fields, dtype=np.float64)
-        multi = f.ndim == 4
-        bstruct, wstruct, bgrms = None, None, None
-        if multi:
-            if min(f.shape[1:]) < 1:
-                raise ValueError(f"expected fields (M, H, W, bands), got {f.shape}")
-            M, H, W, nb = f.shape
-            sel, cw = check_detect_bands(nb, bands, band_weights)
-            planes, noise_id, filter_id = check_detect_band_planes((M, H, W, len(sel)), weights, mask, noise, filter_type, thresh)
-            _check_multiband_finite(f, sel, planes)
-            check_detect_args(np.zeros((0, H, W)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
-                              workspace_bytes)
-            bstruct = _lib.DvDetectBands(_ip(sel), len(sel), _dp(cw), _dp(planes), noise_id, filter_id)
-        else:
-            if bands is not None or band_weights is not None:
-                raise ValueError("bands and band_weights belong to fields (M, H, W, bands)")
-            nb = 0
-            wts = None
-            if weights is not None or mask is not None:
-                shape = np.shape(fields)
-                if len(shape) != 3:
-                    raise ValueError(f"expected fields (M, H, W) or (M, H, W, bands), got {shape}")
-                wts, noise_id, filter_id = check_detect_weights(shape, weights, mask, noise, filter_type, thresh)
-                wstruct = _lib.DvDetectWeights(_dp(wts), noise_id, filter_id)
-            elif noise is not None or filter_type != "conv":
-                raise ValueError("noise and filter_type belong to the weighted call: give weights, a mask or both")
-            f = check_detect_args(f, thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter, workspace_bytes,
-                                  weights=wts)
-            M, H, W = f.shape
-        params, kern = _detect_params(thresh, cont, minarea, nthresh, back_size, back_filter, filter_kernel, workspace_bytes)
-        obj = {}
+        return _scene_detect_objects(self, fields, bands, band_weights, thresh, minarea, nthresh, cont, filter_kernel, back_size,
+                                     back_filter, workspace_bytes, weights, mask, noise, filter_type, segmentation_map,
+                                     columns, None)
 
-        def call(cap, n, offsets, grms, catalogue):       # (the object buffers of this size: a retry makes its own)
-            arrays, ostruct = _object_buffers(cap, (M, H, W) if segmentation_map else None, columns)
-            obj.clear()
-            obj.update(arrays)
-            check(lib.dv_scene_detect_objects(
-                self._h, _dp(f), M, H, W, nb, C.byref(params), cap, n, offsets, grms, *catalogue,
-                None if wstruct is None else C.byref(wstruct), None if bstruct is None else C.byref(bstruct),
-                C.byref(ostruct)))
+    def scene_detect_clean(self, fields, bands=None, band_weights=None, thresh: float = 1.5, minarea: int = 4,
+                           nthresh: int = 64, cont: float = 1e-5, filter_kernel=None, back_size: int = 64,
+                           back_filter: int = 3, workspace_bytes: int = 0, weights=None, mask=None, noise=None,
+                           filter_type: str = "conv", segmentation_map: bool = False, columns: bool = True,
+                           clean_param: float = 1.0) -> Dict[str, np.ndarray]:
+        """scene_detect_objects followed by SExtractor's cleaning pass (dv_scene_detect_clean; sep's
+        clean=True, which the reference's sep call leaves on): an object that would not have been detected without the
+        extrapolated Moffat wings of a brighter neighbour of its field is merged into that neighbour.  clean_param is the
+        profile's beta (> 0; larger: steeper wings, less is absorbed).
 
-        out, rows = _run_detect(M, H * W, call)
-        out.update({key: (v if key == "segmap" else v[:rows].copy()) for key, v in obj.items()})
-        if columns:
-            out.update(detect_object_shapes(out["x2"], out["y2"], out["xy"]))
-        return out
+        Arguments as in scene_detect_objects; thresh must be > 0 and minarea <= 64.  Returns its dictionary over the cleaned
+        rows - a merged row has npix, flux and dflux summed, the peak and vpeak of its brightest member, the union of the
+        boxes, the OR of the flags with bit 16, and the survivor's own x, y, x_iso, y_iso, x2, y2, xy and parent - plus
+        nmerged (1 + the objects merged into the row), mthresh (the minarea-th largest D - T of the row's own pixels) and
+        n_raw (M,), the objects of every field before the pass.  segmap carries the cleaned rows' numbers.  columns=False
+        leaves the object columns out (the catalogue, nmerged, mthresh and n_raw alone, with or without the segmap).  A
+        field in which nothing is absorbed has the bits of scene_detect_objects."""
+        check_detect_clean(clean_param, thresh, minarea)
+        return _scene_detect_objects(self, fields, bands, band_weights, thresh, minarea, nthresh, cont, filter_kernel, back_size,
+                                     back_filter, workspace_bytes, weights, mask, noise, filter_type, segmentation_map,
+                                     columns, float(clean_param))
 
     def close(self):
         """Destroys the engines created on this context, then the context.  Idempotent."""
@@ -2557,6 +2615,17 @@ class FieldSet:
         check(lib.dv_field_set_detect_objects(self._handle(), int(bool(on)), int(bool(on) and bool(segmentation_map))))
         self._detect_objects = (bool(on), bool(on) and bool(segmentation_map))
 
+    def set_detect_clean(self, on: bool = True, clean_param: float = 1.0):
+        """Every later detect() runs the cleaning pass of Context.scene_detect_clean with clean_param
+        (dv_field_set_detect_clean) and returns the cleaned catalogue with nmerged, mthresh and n_raw
+        (M,), 0 for a field that was not active; the columns of set_detect_objects are then the cleaned ones.
+        set_detect_clean(False) goes back to the detection as it was.  While on, detect() refuses thresh <= 0 and
+        minarea > 64."""
+        if on:
+            check_detect_clean(clean_param, None, None)
+        check(lib.dv_field_set_detect_clean(self._handle(), int(bool(on)), float(clean_param) if on else 1.0))
+        self._detect_clean = bool(on)
+
     def detect(self, active=None, thresh: float = 1.5, minarea: int = 4, nthresh: int = 64, cont: float = 1e-5,
                filter_kernel=None, back_size: int = 64, back_filter: int = 3, workspace_bytes: int = 0) -> Dict[str, np.ndarray]:
         """Context.scene_detect on band 2 of the working residuals, which do not leave the GPU (dv_field_set_detect).
@@ -2568,6 +2637,9 @@ class FieldSet:
         objects_on, segmap_on = getattr(self, "_detect_objects", (False, False))
         if objects_on and not float(thresh) >= 0:
             raise ValueError(f"with the object columns on thresh must be >= 0, got {thresh}")
+        clean_on = getattr(self, "_detect_clean", False)
+        if clean_on:
+            check_detect_clean(1.0, thresh, minarea)
         check_detect_args(np.zeros((0, F, F)), thresh, minarea, nthresh, cont, filter_kernel, back_size, back_filter,
                           workspace_bytes)
         if getattr(self, "_detect_noise", None) == _lib.DETECT_NOISE["absolute"] and not float(thresh) > 0:
@@ -2591,6 +2663,11 @@ class FieldSet:
             check(lib.dv_field_set_detect_objects_read(h, rows, C.byref(ostruct)))
             out.update(obj)
             out.update(detect_object_shapes(out["x2"], out["y2"], out["xy"]))
+        if clean_on:
+            cl = dict(nmerged=np.zeros(rows, np.int32), mthresh=np.zeros(rows, np.float64), n_raw=np.zeros(M, np.int64))
+            check(lib.dv_field_set_detect_clean_read(h, rows, _ip(cl["nmerged"]), _dp(cl["mthresh"]),
+                                                     cl["n_raw"].ctypes.data_as(C.POINTER(C.c_int64))))
+            out.update(cl)
         return out
 
     def deblend_pass(self, starts, places, field_ptr, seed=0) -> Dict[str, np.ndarray]:

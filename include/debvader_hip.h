@@ -489,6 +489,37 @@ int dv_scene_detect_objects(dv_ctx* ctx, const double* fields, int32_t M, int32_
                             const dv_detect_params* params, int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms,
                             int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux, double* x, double* y,
                             const dv_detect_weights* weights, const dv_detect_bands* bands, const dv_detect_objects* objects);
+/* dv_scene_detect_clean: dv_scene_detect_objects followed by the cleaning pass of DESIGN.md section 7zc (after SExtractor's
+ * clean.c / sep's clean=True; this project's own rule, not sep's bits).  Over the raw objects of a field, the rows of
+ * dv_scene_detect_objects, with T the field's threshold (thresh * globalrms, or thresh in the weighted and multi-band calls),
+ * beta = clean_param and pi = 3.141592653589793: det = x2 y2 - xy xy, area = pi sqrt(det), cxx = y2 / det, cyy = x2 / det,
+ * cxy = -2 xy / det, a = sqrt((x2 + y2) / 2 + sqrt(((x2 - y2) / 2)^2 + xy^2)), amp = dflux / (2 area),
+ * alpha = (pow(amp / T, 1 / beta) - 1) area / npix, and mthresh the minarea-th largest D - T over the object's pixels (0 with
+ * fewer).  j is a candidate to absorb i iff j != i, dflux_j > dflux_i (or equal and j < i), T > 0,
+ * dx dx + dy dy < 100 (a_i + a_j)^2 with dx = x_iso_i - x_iso_j, dy = y_iso_i - y_iso_j, and P > mthresh_i, where
+ * val = 1 + alpha_j ((cxx_j dx) dx + (cyy_j dy) dy + (cxy_j dx) dy) and P = amp_j pow(val, -beta) if 1 < val < 1e10, else 0.
+ * absorber[i] is the candidate of the largest P (ties to the smaller row), every object goes to the root of its chain; every
+ * test reads the raw values.  The survivors keep their order; a merged row has npix, flux and dflux summed (survivor, then
+ * victims in ascending raw row), peak / xpeak / ypeak and vpeak / xvpeak / yvpeak of the member with the largest value (ties
+ * to the earlier raw row), the union of the boxes, the OR of the flags with DV_DETECT_FLAG_MERGED, and the survivor's own
+ * x, y, x_iso, y_iso, x2, y2, xy and parent.  nmerged: 1 + the victims; mthresh: the survivor's own; n_raw [M]: the raw
+ * objects of every field (always written); the segmap carries the cleaned rows' numbers, a victim's pixels its survivor's.
+ * A field in which nothing is absorbed keeps the bits of dv_scene_detect_objects in every shared output.  `objects` may be
+ * NULL (the catalogue and the clean columns alone); every pointer of `clean` but the struct itself is nullable.
+ * Refused before any GPU work (DV_E_INVALID, the engine stays usable): what the underlying call refuses, a null `clean`,
+ * clean_param not finite or <= 0, thresh <= 0, minarea > 64. */
+#define DV_DETECT_FLAG_MERGED 16   /* the cleaning pass merged other objects into this one */
+typedef struct dv_detect_clean {
+  double   clean_param;
+  int32_t* nmerged;   /* [cap] */
+  double*  mthresh;   /* [cap] */
+  int64_t* n_raw;     /* [M]   */
+} dv_detect_clean;
+int dv_scene_detect_clean(dv_ctx* ctx, const double* fields, int32_t M, int32_t H, int32_t W, int32_t nb,
+                          const dv_detect_params* params, int64_t cap, int64_t* n_out, int64_t* offsets, double* globalrms,
+                          int32_t* field, int32_t* parent, int32_t* npix, double* peak, double* flux, double* x, double* y,
+                          const dv_detect_weights* weights, const dv_detect_bands* bands, const dv_detect_objects* objects,
+                          const dv_detect_clean* clean);
 
 /* ---- catalogue measurement: fluxes and adaptive moments per galaxy ----
  * The reference ships an empty debvader.measure package; the measurement is defined here, float64 throughout.  Per stamp,
@@ -1028,6 +1059,16 @@ int dv_field_set_detect_bands(dv_field_set* set, const int32_t* bands, int32_t k
  * the switch is on dv_field_set_detect refuses thresh < 0. */
 int dv_field_set_detect_objects(dv_field_set* set, int32_t on, int32_t segmap_on);
 int dv_field_set_detect_objects_read(dv_field_set* set, int64_t n_expected, const dv_detect_objects* out);
+/* dv_field_set_detect_clean: on != 0: every later dv_field_set_detect (same signature) runs the
+ * cleaning pass of dv_scene_detect_clean with clean_param and returns the cleaned catalogue; the set keeps nmerged, mthresh
+ * and n_raw of its last detection on the host, and the columns of dv_field_set_detect_objects, when that switch is on, are
+ * the cleaned ones.  on = 0 drops them: the detection is the one it was.  dv_field_set_detect_clean_read copies out the
+ * non-null nmerged, mthresh [n_expected] and n_raw [M] (0 for a field that was not active).  Refused (DV_E_INVALID): on != 0
+ * with clean_param not finite or <= 0; reading with the switch off, with no detection kept or with n_expected other than
+ * that detection's *n_out; a closed set: DV_E_STATE.  While the switch is on dv_field_set_detect refuses thresh <= 0 and
+ * minarea > 64. */
+int dv_field_set_detect_clean(dv_field_set* set, int32_t on, double clean_param);
+int dv_field_set_detect_clean_read(dv_field_set* set, int64_t n_expected, int32_t* nmerged, double* mthresh, int64_t* n_raw);
 int dv_field_set_pass(dv_field_set* set, const int32_t* starts, const int32_t* places, const int64_t* field_ptr, int64_t N,
                       uint64_t seed, double* mse_center, double* field_mse);
 int dv_field_set_read(dv_field_set* set, int32_t which, double* out);

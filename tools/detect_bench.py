@@ -20,6 +20,12 @@ in one process as above.
 with the object columns, and the new call with the columns and the segmentation map, the three legs alternating in one process.
 
     python tools/detect_bench.py --objects [--runs 5]
+
+--clean: the same two workloads through Context.scene_detect_objects and through Context.scene_detect_clean (DESIGN.md section
+7zc: the cleaning pass behind the same detection), both with the columns and the segmentation map, alternating in one process;
+also how many objects the pass merged away.
+
+    python tools/detect_bench.py --clean [--clean-param 1.0] [--runs 5]
 """
 import argparse
 import json
@@ -155,6 +161,32 @@ def main_objects(a, ctx, batch, tile):
     print(json.dumps(out))
 
 
+def main_clean(a, ctx, batch, tile):
+    ctx.scene_detect_clean(batch[:2], segmentation_map=True, clean_param=a.clean_param)      # warm-up of the clean kernels
+    legs = (("objects", lambda f: ctx.scene_detect_objects(f, segmentation_map=True)),
+            ("clean", lambda f: ctx.scene_detect_clean(f, segmentation_map=True, clean_param=a.clean_param)))
+    out = {"batch": a.batch, "F": batch.shape[1], "tile": a.tile, "runs": a.runs, "clean_param": a.clean_param}
+    for name, f, scale in (("batch", batch, 1.0), ("tile", tile, 1e3)):
+        times = {leg: [] for leg, _ in legs}
+        res = {}
+        for _ in range(a.runs):                                        # the two legs alternating
+            for leg, fn in legs:
+                t0 = time.perf_counter()
+                res[leg] = fn(f)
+                times[leg].append(time.perf_counter() - t0)
+        unit = "seconds" if name == "batch" else "ms"
+        for leg, _ in legs:
+            t = times[leg]
+            out[f"{name}_{leg}_{unit}_median"] = round(scale * float(np.median(t)), 5)
+            out[f"{name}_{leg}_{unit}_min_max"] = [round(scale * min(t), 5), round(scale * max(t), 5)]
+            out[f"{name}_{leg}_objects"] = int(len(res[leg]["x"]))
+        assert int(res["clean"]["n_raw"].sum()) == len(res["objects"]["x"])
+        out[f"{name}_merged_away"] = int(len(res["objects"]["x"]) - len(res["clean"]["x"]))
+        out[f"{name}_largest_nmerged"] = int(res["clean"]["nmerged"].max(initial=0))
+        out[f"{name}_clean_over_objects"] = round(float(np.median(times["clean"]) / np.median(times["objects"])), 4)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -168,6 +200,9 @@ def main():
                                                   "detector")
     ap.add_argument("--objects", action="store_true", help="alternate the existing call and Context.scene_detect_objects "
                                                            "without and with the segmentation map")
+    ap.add_argument("--clean", action="store_true", help="alternate Context.scene_detect_objects and "
+                                                         "Context.scene_detect_clean, both with the segmentation map")
+    ap.add_argument("--clean-param", type=float, default=1.0)
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     F = 259
@@ -182,6 +217,8 @@ def main():
         return main_bands(a, ctx, batch, tile)
     if a.objects:
         return main_objects(a, ctx, batch, tile)
+    if a.clean:
+        return main_clean(a, ctx, batch, tile)
     tb, rb = _best(lambda: ctx.scene_detect(batch), a.repeat)
     tt, rt = _best(lambda: ctx.scene_detect(tile), a.repeat)
     t0 = time.perf_counter()
